@@ -14,8 +14,14 @@ on --warmup.  N>1 (torch.distributed.run, one rank per GPU): decisions are
 independent, so ranks shard the model axis with no data-path collective and the
 line reports weak scaling (100k decisions per rank per step).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-`roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run
+does only what the headline needs: set-up, warm-up, the timed steps and the
+line (`value`, `ms_per_step`, `config`).  `--full` adds everything else the
+bench measures or checks: the kernel-duration passes and `roofline`, the parity
+gate against the CPU oracle, and the additional legs (`pod_axis`, latency,
+`churn`, `full_cluster`, per-kernel `kernels`, `cpu_baseline`, ...).
+`--dump-outputs DIR` writes the result rows of the last timed step as
+DIR/<field>.npy (float64).
 """
 from __future__ import annotations
 
@@ -137,6 +143,26 @@ def make_step_batch(fleet, seeds):
     if len(parts) == 1:
         return parts[0], ex_parts[0], len(ex_parts[0])
     return np.concatenate(parts), np.concatenate(ex_parts), len(ex_parts[0])
+
+
+DUMP_LIMIT_BYTES = 64_000_000 - 4096  # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir: str, rows) -> None:
+    """`rows`: the PLACE_OUT result rows of one step.  One float64 array per field (32-bit integers: exact in float64); above
+    DUMP_LIMIT_BYTES a fixed seeded sample of rows, whose indices go to row.npy."""
+    names = rows.dtype.names
+    if len(rows) * 8 * len(names) > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (8 * (len(names) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), k, replace=False))
+        rows = rows[idx]
+    else:
+        idx = None
+    os.makedirs(out_dir, exist_ok=True)
+    for f in names:
+        np.save(os.path.join(out_dir, f"{f}.npy"), rows[f].astype(np.float64))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "row.npy"), idx.astype(np.float64))
 
 
 def measured_traffic(workload: str, decisions_per_launch: int, kernel: str = "place_batch_kernel", tag: str = ""):
@@ -1190,6 +1216,11 @@ def main():
     ap.add_argument("--kernel-only", action="store_true",
                     help="skip the n=1 latency / host-boundary legs (used under rocprofv3 so that every "
                          "place_batch_kernel dispatch in the trace is a full batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel-duration passes and roofline, the parity gate against the CPU oracle and "
+                         "the additional legs (the --no-* / --kernel-only options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result rows of the last timed step as DIR/<field>.npy (float64)")
     args = ap.parse_args()
 
     # stdout carries ONE JSON line and nothing else: native libraries write banners to file descriptor 1 (RCCL prints
@@ -1340,11 +1371,13 @@ def main():
     fence()
     # ... and the host: the first region of this shape a process runs was measured at 200 us against 86-93 us for the next
     # ones (its 20 launches take the host 112 us instead of 56, the closing synchronize 43 us instead of 7) — code and
-    # data of the launch path are not in the host's caches yet.  Two untimed rehearsals of the region's shape.
+    # data of the launch path are not in the host's caches yet.  Two untimed rehearsals of the region's shape (at most 1000
+    # steps each: a longer region no longer feels that first-region cost, and the rehearsals would double the run's length).
+    rehearsal = min(args.steps, 1000)
     for rep_ in range(2 if args.ramp else 0):
-        for i in range(args.steps):
+        for i in range(rehearsal):
             _fn(*_args[i % period])
-        _last_stream[0] = (args.steps - 1) % n_streams
+        _last_stream[0] = (rehearsal - 1) % n_streams
         fence()
     n_helpers = max(0, min(args.issue_threads, n_streams))
     _flush = solver.lib.mmp_issue_flush
@@ -1421,6 +1454,49 @@ def main():
     check(rcs)
     if n_helpers:
         check(solver.lib.mmp_issue_threads(solver.h, 0))  # the passes below bracket launches with events: issued in line
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    from modelmesh_amd._lib import PLACE_OUT
+    if args.dump_outputs and rank == 0:
+        # the last timed step decided batch (warmup + steps - 1) mod R; every step on that batch writes the same rows
+        last_b = (args.warmup + args.steps - 1) % n_batches
+        dump_outputs(args.dump_outputs, np.frombuffer(d_bufs[last_b][2].cpu().numpy().tobytes(), dtype=PLACE_OUT))
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "placement decisions/sec at 100k models x 10k pods; p99 decision latency",
+            "value": n * args.steps * world / elapsed, "unit": "decisions/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "i64", "data": "synthetic",
+            "config": {"workload": f"{args.workload}: {fleet.n_models} models x {fleet.n_pods} pods, {sets_per_step} load-target "
+                                   f"decision(s) per model per step = {n} decisions per launch (SURVEY.md §8d synthetic fleet)",
+                       "decisions_per_step_per_gpu": n, "request_sets_per_step": sets_per_step,
+                       "sharding": "model axis, no collective",
+                       "region_barrier": None if world == 1 else ("shared memory, one node (NodeBarrier)" if node_barrier is not None
+                                                                  else "dist.barrier()"),
+                       "streams": n_streams, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "distinct_batches": n_batches, "issuers": n_issuers,
+                       "library_submission_threads": n_helpers,
+                       "resident_input_bytes": int(n_batches * n * (64 + 16)),
+                       "host_issue_us_per_step": None if issue_s is None else issue_s / args.steps * 1e6},
+        }
+
+    def close():
+        solver.close()
+        if world > 1:
+            if node_barrier is not None:
+                dist.barrier()  # nobody is still inside a wait() when rank 0 removes the page
+                node_barrier.close()
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        close()
+        return
+
     # the kernel's own launch duration: K back-to-back launches on ONE stream (rotating through the batches like the
     # timed region) between a HIP event pair recorded on that stream — region time / K is what
     # rocprofv3 --kernel-trace reports as the kernel's average duration for the same single-stream command ...
@@ -1498,13 +1574,7 @@ def main():
         fence()
         set_ms = ev0.elapsed_time(ev1) / 400
 
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
     # every batch the GPU decided must equal the oracle's answer (parity gate before any number)
-    from modelmesh_amd._lib import PLACE_OUT
     parity, want = None, None
     if rank == 0:
         from oracle.bind import OracleFleet
@@ -1523,10 +1593,7 @@ def main():
     # The headline is complete here.  Everything below is an additional leg; a watchdog makes sure the
     # ONE JSON line is still printed (with the legs finished so far) if a leg hangs — e.g. a collective
     # of the pod-axis leg on a node whose RCCL setup misbehaves — instead of losing the measurement.
-    line = None
     if rank == 0:
-        total = n * args.steps * world
-        value = total / elapsed
         alg = int(np.mean([algorithmic_bytes(fleet, bq[0]) for bq in batches[:4]]))
         kb = int(np.mean([kernel_bytes(fleet, bq[0]) for bq in batches[:4]]))
         # launches from 393 216 decisions on are SPLIT: the per-type shortlists checked in a launch of its own (place_memo_kernel, the
@@ -1548,21 +1615,7 @@ def main():
         if first_ms is not None:
             gpu_ms_per_step = first_ms  # the dominant kernel's own duration
         achieved = moved / (gpu_ms_per_step * 1e-3) / 1e9
-        line = {
-            "metric": "placement decisions/sec at 100k models x 10k pods; p99 decision latency",
-            "value": value, "unit": "decisions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "i64", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {fleet.n_models} models x {fleet.n_pods} pods, {sets_per_step} load-target "
-                                   f"decision(s) per model per step = {n} decisions per launch (SURVEY.md §8d synthetic fleet)",
-                       "decisions_per_step_per_gpu": n, "request_sets_per_step": sets_per_step,
-                       "sharding": "model axis, no collective",
-                       "region_barrier": None if world == 1 else ("shared memory, one node (NodeBarrier)" if node_barrier is not None
-                                                                  else "dist.barrier()"),
-                       "streams": n_streams, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "distinct_batches": n_batches, "issuers": n_issuers,
-                       "library_submission_threads": n_helpers,
-                       "resident_input_bytes": int(n_batches * n * (64 + 16)),
-                       "host_issue_us_per_step": None if issue_s is None else issue_s / args.steps * 1e6},
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_provenance": traffic_prov,
                          "kernel": kname, "kernel_ms": gpu_ms_per_step,
@@ -1603,7 +1656,7 @@ def main():
                              "algorithmic_bytes_per_launch": alg,
                              "rate_GBs": alg / (gpu_ms_per_step * 1e-3) / 1e9}},
             "parity_vs_oracle": parity,
-        }
+        })
         if parity is False:
             line["invalid"] = "parity_vs_oracle is false: the numbers of this line describe a wrong kernel"
 
@@ -1809,12 +1862,7 @@ def main():
         dist.barrier()
     dog.cancel()
 
-    solver.close()
-    if world > 1:
-        if node_barrier is not None:
-            dist.barrier()  # nobody is still inside a wait() when rank 0 removes the page
-            node_barrier.close()
-        dist.destroy_process_group()
+    close()
     if rank == 0 and parity is False:
         sys.exit(3)
 

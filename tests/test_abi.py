@@ -25,6 +25,9 @@ def test_header_symbols_are_all_exported_and_typed():
     declared = set(re.findall(r"\b(mmp_[a-z0-9_]+)\s*\(", hdr))
     bound = {name for name, _, _ in _lib.SYMBOLS}
     assert declared == bound, (declared - bound, bound - declared)
+    # _lib.load() first: it lets torch's HIP runtime load before libmmplace; a bare dlopen here would bind the system's copy
+    # first, and torch in this process (every later test of the session) would then find no GPU
+    _lib.load()
     lib = C.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/mmplace.h but not exported"

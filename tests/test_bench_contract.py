@@ -80,3 +80,33 @@ def test_a_step_batch_of_several_request_sets_decides_like_its_sets():
         for f in ("chosen", "best", "n_candidates", "hash"):
             assert np.array_equal(sl[f], one[f]), (j, f)
     assert (rq["n_extra"] > 0).any(), "the sets carry late-bound exclusions, or the offsets were never exercised"
+
+
+def test_dumped_outputs_are_exact_float64_within_64_mb(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one float64 file per result field, every 32-bit value exact; a step larger than
+    the 64 MB budget is written as a fixed seeded sample of rows whose indices go to row.npy."""
+    import bench
+    from modelmesh_amd._lib import PLACE_OUT
+    rng = np.random.default_rng(1)
+    for n in (800_000, 3_000_000):
+        rows = np.zeros(n, PLACE_OUT)
+        for f in PLACE_OUT.names:
+            info = np.iinfo(PLACE_OUT[f])
+            rows[f] = rng.integers(info.min, info.max, n, endpoint=True, dtype=PLACE_OUT[f])
+        dumps = []
+        for rep in range(2):  # the same rows give the same files
+            out = tmp_path / f"{n}_{rep}"
+            bench.dump_outputs(str(out), rows)
+            assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+            dumps.append({p.name: np.load(p) for p in out.iterdir()})
+        assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+        got = dumps[0]
+        if n == 800_000:
+            assert "row.npy" not in got
+            idx = np.arange(n)
+        else:
+            idx = got["row.npy"].astype(np.int64)
+            assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+        for f in PLACE_OUT.names:
+            assert got[f"{f}.npy"].dtype == np.float64
+            assert np.array_equal(got[f"{f}.npy"].astype(PLACE_OUT[f]), rows[f][idx])

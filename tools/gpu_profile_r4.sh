@@ -14,14 +14,14 @@ timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; tail -1 $OUT/
 profile_one() {
   local tag=$1 kern=$2; shift 2
   rm -rf /tmp/p_$tag
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag/stats -- python bench.py --kernel-only --steps 200 --warmup 20 --streams 1 "$@" > $OUT/bench_${tag}_kernel_only_1stream.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag/stats -- python bench.py --full --kernel-only --steps 200 --warmup 20 --streams 1 "$@" > $OUT/bench_${tag}_kernel_only_1stream.log 2>&1
   f=$(find /tmp/p_$tag/stats -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/${tag}_kernel_stats_1stream.csv && grep "$kern" $OUT/${tag}_kernel_stats_1stream.csv | cut -c1-160
   grep "^{" $OUT/bench_${tag}_kernel_only_1stream.log | tail -1 > $OUT/bench_${tag}_kernel_only_1stream.json.log
-  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/p_$tag/f -- python bench.py --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
-  timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/p_$tag/w -- python bench.py --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/p_$tag/f -- python bench.py --full --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/p_$tag/w -- python bench.py --full --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
   python tools/pmc_summary.py /tmp/p_$tag/f /tmp/p_$tag/w $kern $OUT/pmc_place_batch_$tag.json > /dev/null; cut -c1-400 $OUT/pmc_place_batch_$tag.json | tr '\n' ' '; echo
-  timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d /tmp/p_$tag/sq1 -- python bench.py --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
-  timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --kernel-trace --output-format csv -d /tmp/p_$tag/sq2 -- python bench.py --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d /tmp/p_$tag/sq1 -- python bench.py --full --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --kernel-trace --output-format csv -d /tmp/p_$tag/sq2 -- python bench.py --full --kernel-only --steps 20 --warmup 2 --streams 1 "$@" > /dev/null 2>&1
   (python tools/sq_summary.py /tmp/p_$tag/sq1 $kern; python tools/sq_summary.py /tmp/p_$tag/sq2 $kern) > $OUT/sq_$tag.jsonl; cut -c1-260 $OUT/sq_$tag.jsonl
 }
 if [ -n "${PROFILE_ONLY:-}" ]; then  # one configuration again (after a script fix): PROFILE_ONLY="<tag> <kernel> <bench args...>"
@@ -36,17 +36,17 @@ profile_one C3_full_cluster_800k place_batch_long4_kernel --workload C3 --full-c
 
 # two overlapping streams (the timed region's shape): kernel stats only
 rm -rf /tmp/p_2s
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_2s -- python bench.py --kernel-only --steps 200 --warmup 20 --streams 2 > $OUT/bench_C3_800k_kernel_only_2streams.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_2s -- python bench.py --full --kernel-only --steps 200 --warmup 20 --streams 2 > $OUT/bench_C3_800k_kernel_only_2streams.log 2>&1
 f=$(find /tmp/p_2s -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/C3_800k_kernel_stats_2streams.csv
 
 # the secondary kernels: the whole bench under the kernel trace, then under the two SQ passes
 rm -rf /tmp/p_full
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_full/stats -- python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > $OUT/prof_full_bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_full/stats -- python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > $OUT/prof_full_bench.log 2>&1
 f=$(find /tmp/p_full/stats -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/bench_full_kernel_stats.csv && grep -E "serve_batch|gate_batch|evict_batch|cache_replay|ingest_|build_b|build_wins" $OUT/bench_full_kernel_stats.csv | cut -c1-140
-timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d /tmp/p_full/sq1 -- python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
-timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --kernel-trace --output-format csv -d /tmp/p_full/sq2 -- python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/p_full/f -- python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/p_full/w -- python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
+timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d /tmp/p_full/sq1 -- python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
+timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --kernel-trace --output-format csv -d /tmp/p_full/sq2 -- python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/p_full/f -- python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/p_full/w -- python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline > /dev/null 2>&1
 # per-kernel digests by launch size in WORK-ITEMS (the run launches these kernels for single requests, for the churn leg's mixed
 # sizes, and for the `kernels` leg at 100k and 800k units): serve / gate one lane per unit, evict 8 lanes per evaluation, cache
 # replay one wavefront per cache (10k caches)
@@ -66,10 +66,10 @@ digest route_batch_kernel route_batch_kernel 50000 400000
 digest route_batch_kernel route_batch_kernel_800k 500000 2000000
 
 # the bench lines: the driver's flags, then the defaults; C4
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_C3_n1_steps20.json.log 2> $OUT/bench_C3_steps20.err; echo "bench(20) exit $?"
-timeout 900 python bench.py > $OUT/bench_C3_n1.json.log 2> $OUT/bench_C3.err; echo "bench exit $?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_C3_n1_steps20.json.log 2> $OUT/bench_C3_steps20.err; echo "bench(20) exit $?"
+timeout 900 python bench.py --full > $OUT/bench_C3_n1.json.log 2> $OUT/bench_C3.err; echo "bench exit $?"
 python tools/benchline.py steps20 < $OUT/bench_C3_n1_steps20.json.log; python tools/benchline.py default < $OUT/bench_C3_n1.json.log
-if [[ "${PROFILE_WORKLOADS:-C3 C4}" == *C4* ]]; then timeout 600 python bench.py --workload C4 --steps 200 --warmup 10 --no-secondary > $OUT/bench_C4_n1.json.log 2> $OUT/bench_C4.err; echo "bench C4 exit $?"; python tools/benchline.py C4 < $OUT/bench_C4_n1.json.log; fi
+if [[ "${PROFILE_WORKLOADS:-C3 C4}" == *C4* ]]; then timeout 600 python bench.py --full --workload C4 --steps 200 --warmup 10 --no-secondary > $OUT/bench_C4_n1.json.log 2> $OUT/bench_C4.err; echo "bench C4 exit $?"; python tools/benchline.py C4 < $OUT/bench_C4_n1.json.log; fi
 timeout 300 python tools/full_cluster_by_type.py 2>&1 | grep -v amdgpu.ids > $OUT/full_cluster_by_type.txt; cat $OUT/full_cluster_by_type.txt
 timeout 300 python tools/case_b_timing.py 2>&1 | grep -v amdgpu.ids > $OUT/case_b_timing.txt; cat $OUT/case_b_timing.txt
 
@@ -99,5 +99,5 @@ fi
 mkdir -p $OUT/pod_axis
 timeout 300 python tools/pod_axis_timing.py C3 200 2>&1 | grep "_leg" > $OUT/pod_axis/one_shard_C3_200steps.txt; cat $OUT/pod_axis/one_shard_C3_200steps.txt
 MMP_BENCH_ONE_DEVICE=1 MMP_BENCH_BACKEND=gloo timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-  --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --steps 20 --warmup 5 > $OUT/bench_8ranks_one_device_gloo.json.log 2> $OUT/bench8.err; echo "bench8 exit $?"
+  --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 8 --steps 20 --warmup 5 > $OUT/bench_8ranks_one_device_gloo.json.log 2> $OUT/bench8.err; echo "bench8 exit $?"
 tail -1 $OUT/bench_8ranks_one_device_gloo.json.log | cut -c1-300

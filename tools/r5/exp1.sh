@@ -8,7 +8,7 @@ mkdir -p $OUT
 timeout 900 python -m pytest tests/test_stream_gpu.py -x -q > $OUT/pytest_stream.log 2>&1; echo "pytest exit $?" >> $OUT/pytest_stream.log; tail -3 $OUT/pytest_stream.log
 one() {  # $1 tag; env from the caller; rest: bench args
   local tag=$1; shift
-  timeout 600 python bench.py --kernel-only --steps 200 --warmup 20 "$@" > $OUT/$tag.log 2> $OUT/$tag.err
+  timeout 600 python bench.py --full --kernel-only --steps 200 --warmup 20 "$@" > $OUT/$tag.log 2> $OUT/$tag.err
   grep "^{" $OUT/$tag.log | tail -1 > $OUT/$tag.json
   python - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
@@ -24,6 +24,6 @@ for m in 0 1 2; do MMP_STREAM=$m one k1_stream$m --streams 1; done
 for sl in 512 1024; do MMP_STREAM=2 MMP_STREAM_SLOTS=$sl one k1_stream2_slots$sl --streams 1; done
 for m in 0 2; do MMP_STREAM=$m one k4_stream$m --streams 4; done
 for m in 0 2; do
-  MMP_STREAM=$m timeout 900 python bench.py --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline > $OUT/bench20_stream$m.log 2> $OUT/bench20_stream$m.err
+  MMP_STREAM=$m timeout 900 python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline > $OUT/bench20_stream$m.log 2> $OUT/bench20_stream$m.err
   grep "^{" $OUT/bench20_stream$m.log | tail -1 | cut -c1-600
 done

@@ -7,7 +7,7 @@ mkdir -p $OUT
 V=modelmesh_amd/lib/variants
 one() {  # $1 tag, $2 lib; env from the caller; rest: bench args
   local tag=$1 lib=$2; shift 2
-  MMP_LIB_PATH=$PWD/$V/libmmplace_$lib.so timeout 600 python bench.py --kernel-only --steps 200 --warmup 20 "$@" > $OUT/$tag.log 2> $OUT/$tag.err
+  MMP_LIB_PATH=$PWD/$V/libmmplace_$lib.so timeout 600 python bench.py --full --kernel-only --steps 200 --warmup 20 "$@" > $OUT/$tag.log 2> $OUT/$tag.err
   grep "^{" $OUT/$tag.log | tail -1 > $OUT/$tag.json
   python - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys

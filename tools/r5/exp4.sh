@@ -9,7 +9,7 @@ export MMP_LIB_PATH=$PWD/modelmesh_amd/lib/variants/libmmplace_base.so MMP_STREA
 for x in 0 1; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/p4_$x$c
-    MMP_XMAP=$x timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/p4_$x$c -- python bench.py --kernel-only --steps 20 --warmup 2 --streams 1 > /dev/null 2>&1
+    MMP_XMAP=$x timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/p4_$x$c -- python bench.py --full --kernel-only --steps 20 --warmup 2 --streams 1 > /dev/null 2>&1
   done
   python tools/pmc_summary.py /tmp/p4_${x}FETCH_SIZE /tmp/p4_${x}WRITE_SIZE place_batch_kernel $OUT/pmc_xmap$x.json > /dev/null; cut -c1-500 $OUT/pmc_xmap$x.json | tr '\n' ' '; echo
 done

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/long}
 mkdir -p $OUT
 timeout 900 python -m pytest tests/test_place_parity_gpu.py tests/test_ref_vectors_gpu.py tests/test_place_caller_gpu.py tests/test_place_multi_gpu.py -x -q -k "full or long or every_device or caller or case_b or sparse or multi" > $OUT/pytest.log 2>&1; tail -2 $OUT/pytest.log
 for n in 100000 800000; do
-  timeout 300 python bench.py --kernel-only --steps 200 --warmup 20 --streams 1 --full-cluster --decisions-per-step $n > $OUT/fc_$n.log 2> $OUT/fc_$n.err
+  timeout 300 python bench.py --full --kernel-only --steps 200 --warmup 20 --streams 1 --full-cluster --decisions-per-step $n > $OUT/fc_$n.log 2> $OUT/fc_$n.err
   grep "^{" $OUT/fc_$n.log | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d.get('roofline',{})

@@ -5,7 +5,7 @@ OUT=gpurun_out/r6_exp20
 mkdir -p $OUT
 run() {
   label=$1; shift
-  env "$@" MMP_BENCH_REPEAT=14 timeout 300 python bench.py --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline --kernel-only $ARGS > $OUT/b_$label.log 2> $OUT/b_$label.err
+  env "$@" MMP_BENCH_REPEAT=14 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline --kernel-only $ARGS > $OUT/b_$label.log 2> $OUT/b_$label.err
   echo "== $label"; grep "^region" $OUT/b_$label.err | sed 's/region [0-9]*: issue //; s/ us, known done [0-9.]*//; s/ us, total /\//; s/ us//' | tr '\n' ' '; echo; python tools/benchline.py $label < $OUT/b_$label.log
 }
 ARGS=""; run split_plain X=1

@@ -6,5 +6,5 @@ OUT=gpurun_out/r6_exp28
 mkdir -p $OUT
 for env in "X=1" "MMP_NO_SPLIT=1"; do
   echo "== $env"
-  env $env MMP_BENCH_REPEAT=8 timeout 600 python bench.py --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline --kernel-only 2>&1 >/dev/null | grep "^region"
+  env $env MMP_BENCH_REPEAT=8 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-secondary --no-cpu-baseline --kernel-only 2>&1 >/dev/null | grep "^region"
 done | tee $OUT/regions.txt

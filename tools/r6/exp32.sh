@@ -10,7 +10,7 @@ V=$PWD/modelmesh_amd/lib/variants
 for rep in 1 2; do
  for lib in "" "$V/libmmplace_ntsec.so"; do
   echo "== ${lib:-product}"
-  MMP_LIB_PATH=$lib timeout 600 python bench.py --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline 2>/dev/null | python -c "
+  MMP_LIB_PATH=$lib timeout 600 python bench.py --full --steps 20 --warmup 5 --no-pod-axis --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for r in d.get('kernels', []):

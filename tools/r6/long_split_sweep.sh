@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests/test_long_memo_gpu.py tests/test_place_parit
 for env in "MMP_LONG_SPLIT_FROM=0" "MMP_NO_SPLIT=1" "MMP_NO_SPLIT=1 MMP_LONG_DENSE_FROM=2000000000" "MMP_NO_LONG_MEMO=1"; do
   for n in 200000 400000 800000; do
    for st in 1 4; do
-    env $env timeout 600 python bench.py --kernel-only --steps 200 --warmup 20 --streams $st --workload C3 --full-cluster --no-pod-axis --no-secondary --no-cpu-baseline --decisions-per-step $n 2>/dev/null | python -c "
+    env $env timeout 600 python bench.py --full --kernel-only --steps 200 --warmup 20 --streams $st --workload C3 --full-cluster --no-pod-axis --no-secondary --no-cpu-baseline --decisions-per-step $n 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$env', 'n $n streams $st', 'kernel_ms', round(r['kernel_ms']*1e3,2), 'us  ms_per_step', round(d['ms_per_step']*1e3,2), 'us  parity', d['parity_vs_oracle'])"
