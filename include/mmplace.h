@@ -532,7 +532,11 @@ int mmp_place_batch(mmp_ctx *ctx, const mmp_place_req *reqs, int32_t n, const in
  * (a hipStream_t, NULL = default) without synchronising.  The library remembers every stream it was handed:
  * before it rewrites state such a launch may still be reading (the second commit after it, registry loads
  * and events, cache-table loads) it waits for those streams as it waits for its own.  A stream must
- * therefore stay valid until mmp_stream_retire() or mmp_destroy(). */
+ * therefore stay valid until mmp_stream_retire() or mmp_destroy().  Several host threads may call the *_dev entry points
+ * concurrently, on one stream (NULL included) or on several: the two launches of a split batch (mmp_split_batches) share a buffer per
+ * stream and are enqueued back to back under that buffer's lock.  hipStreamPerThread (handle 2) is refused with MMP_EINVAL by every
+ * entry point that takes a stream: it names a different stream in every thread that uses it, so the library could neither wait for
+ * what another thread enqueued on it before rewriting state nor keep one split buffer per stream.  Pass a stream of your own. */
 int mmp_place_batch_dev(mmp_ctx *ctx, const void *d_reqs, int32_t n, const void *d_extra_pool,
                         int64_t now_ms, void *d_outs, void *stream);
 /* mmp_place_batch_dev with the pool's length (entries): a request whose exclusion range [extra_off, extra_off + n_extra) does not
@@ -576,8 +580,9 @@ int mmp_resident_stats(mmp_ctx *ctx, uint64_t *launches, uint64_t *served, uint6
  * any); call it before synchronising the streams.  n = 0 stops the helpers. */
 int mmp_issue_threads(mmp_ctx *ctx, int32_t n);
 int mmp_issue_flush(mmp_ctx *ctx);
-/* Forget a caller-owned stream (waits for what was enqueued on it first); call before destroying a stream
- * that was passed to a *_dev entry point. */
+/* Forget a caller-owned stream (waits for what was enqueued on it first, then frees the stream's split-batch buffer); call before
+ * destroying a stream that was passed to a *_dev entry point.  A context keeps split-batch buffers for 64 streams at a time: batches
+ * on a stream beyond those go unsplit (same results) until a retire frees a buffer. */
 int mmp_stream_retire(mmp_ctx *ctx, void *stream);
 
 /* n serve-target decisions = n × ForwardingLB.getNext (MM.java:4315-4392).

@@ -215,17 +215,22 @@ struct mmp_ctx {
     int32_t memo_lds_min = 0;  // MMP_MEMO_LDS_MIN=bytes: dynamic LDS the first launch of a split batch asks for at least (an occupancy cap: see kMemoLdsMin)
     int32_t split_notail = 0;  // MMP_SPLIT_NOTAIL=1: the tail launch is left out — the batch's results are INCOMPLETE (timing the first launch alone)
     // per stream that has issued a split batch: the words its first launches leave for its tails (launches of one stream are ordered,
-    // so one buffer per stream will do) and a pinned pair the tail reports to: {undecided, of how many}
+    // so one buffer per stream will do) and a pinned pair the tail reports to: {undecided, of how many}.  A tail decides whatever
+    // the lists hold and zeroes them, so the two launches of a batch must follow each other on the stream: `mu` is held from the
+    // buffer's lookup until the tail is enqueued (two host threads on one stream).  Slots have fixed addresses; mmp_stream_retire
+    // returns a stream's slot.
     struct MissBuf {
+        std::mutex mu;             // taken after the state lock, before miss_mu; guards words / cap
+        bool used = false;         // (used, st, report: under miss_mu; a slot in use is returned only with mu held as well)
         hipStream_t st = nullptr;
         int32_t *words = nullptr;  // place_kernel.hpp: rest_buffer_ints — counters + kRestLists lists
         size_t cap = 0;            // ints
         int32_t *report = nullptr;
     };
-    std::vector<MissBuf> miss_bufs;   // guarded by miss_mu (a leaf lock)
-    std::vector<void *> miss_retired; // outgrown word buffers: a launch in flight may still read them; freed with the context
-    int32_t *miss_reports = nullptr;  // pinned, kMaxMissBufs pairs
-    std::mutex miss_mu;
+    MissBuf miss_bufs[kMaxMissBufs];
+    std::vector<void *> miss_retired; // outgrown word buffers: a launch in flight may still read them; freed with the context (miss_mu)
+    int32_t *miss_reports = nullptr;  // pinned, kMaxMissBufs pairs (slot i: pair i)
+    std::mutex miss_mu;               // a leaf lock: slot lookup / allocation, miss_retired, miss_reports
     std::atomic<bool> split_off{false};  // a tail reported more than 1/32 of its batch: batches go unsplit until the next commit / registry event
     std::atomic<int64_t> n_split{0};     // split batches issued (mmp_split_batches)
 
@@ -451,6 +456,16 @@ hipError_t quiesce_decisions(mmp_ctx *c)
     return hipStreamSynchronize(c->stream);
 }
 
+// hipStreamPerThread is a different stream in every thread that names it: the library could neither wait for what another thread
+// enqueued on it (quiesce_decisions) nor keep one split buffer per stream (miss_buffer).  Every entry point that takes a stream
+// refuses it (include/mmplace.h).
+int refuse_per_thread_stream(mmp_ctx *c, const void *stream, const char *who)
+{
+    if (stream != static_cast<const void *>(hipStreamPerThread)) return MMP_OK;
+    return fail(c, MMP_EINVAL, "%s: hipStreamPerThread (stream handle %p) names a different stream in every thread; pass a stream "
+                "created with hipStreamCreate", who, stream);
+}
+
 // a *_dev call was enqueued on `st` (called with c->mu held)
 void note_caller_stream(mmp_ctx *c, hipStream_t st)
 {
@@ -518,40 +533,62 @@ hipError_t order_after_registry(mmp_ctx *c, hipStream_t st);
 #ifdef MMP_XP_EMPTYTAIL  // (experiment builds only, tools/r6: what the runtime charges for a second launch per call, whatever it does)
 __global__ void xp_noop_kernel(int32_t *p) { if (p == nullptr) __builtin_trap(); }
 #endif
-// The buffer of a split batch on `st` (`ints`: rest_buffer_ints of its first launch) and the stream's report pair; false: none to be
-// had (too many streams, no memory) — the batch goes unsplit.  Also reads what the stream's last tail reported.
-bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32_t **report)
+// The buffer of a split batch on `st` (`ints`: rest_buffer_ints of its first launch) and the stream's report pair, returned with the
+// stream's slot locked in `hold` (the caller enqueues both launches before it lets go); false: none to be had (too many streams, no
+// memory) — the batch goes unsplit, nothing is held.  Also reads what the stream's last tail reported.
+bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32_t **report, std::unique_lock<std::mutex> &hold)
 {
-    std::lock_guard<std::mutex> g(c->miss_mu);
     mmp_ctx::MissBuf *mb = nullptr;
-    for (auto &b : c->miss_bufs)
-        if (b.st == st) mb = &b;
-    if (!mb) {
-        if ((int)c->miss_bufs.size() >= kMaxMissBufs) return false;
-        if (!c->miss_reports) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&c->miss_reports), (size_t)kMaxMissBufs * 2 * sizeof(int32_t), kPinnedFlags) != hipSuccess) {
-                c->miss_reports = nullptr;
-                return false;
+    while (!mb) {
+        {
+            std::lock_guard<std::mutex> g(c->miss_mu);
+            mmp_ctx::MissBuf *fresh = nullptr;
+            for (auto &b : c->miss_bufs) {
+                if (b.used && b.st == st) mb = &b;
+                if (!b.used && !fresh) fresh = &b;
             }
-            memset(c->miss_reports, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
+            if (!mb) {
+                if (!fresh) return false;
+                if (!c->miss_reports) {
+                    if (hipHostMalloc(reinterpret_cast<void **>(&c->miss_reports), (size_t)kMaxMissBufs * 2 * sizeof(int32_t), kPinnedFlags) != hipSuccess) {
+                        c->miss_reports = nullptr;
+                        return false;
+                    }
+                    memset(c->miss_reports, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
+                }
+                fresh->used = true;
+                fresh->st = st;
+                fresh->report = c->miss_reports + 2 * (fresh - c->miss_bufs);
+                fresh->report[0] = fresh->report[1] = 0;  // (a reused slot: what the retired stream's tails reported is not this one's)
+                mb = fresh;
+            }
         }
-        mmp_ctx::MissBuf nb;
-        nb.st = st;
-        nb.report = c->miss_reports + 2 * c->miss_bufs.size();
-        c->miss_bufs.push_back(nb);
-        mb = &c->miss_bufs.back();
+        // the slot's lock with miss_mu let go: a thread enqueueing on the same stream holds it for two launches, the other streams go on
+        hold = std::unique_lock<std::mutex>(mb->mu);
+        std::lock_guard<std::mutex> g(c->miss_mu);
+        if (!mb->used || mb->st != st) {  // retired (and maybe handed to another stream) meanwhile: look again
+            hold.unlock();
+            mb = nullptr;
+        }
     }
     if (mb->cap < ints) {
         size_t want = std::max<size_t>(ints, 65536);
         want = std::max(want, mb->cap + mb->cap / 2);
         void *p = nullptr;
-        if (hipMalloc(&p, want * sizeof(int32_t)) != hipSuccess) return false;
+        if (hipMalloc(&p, want * sizeof(int32_t)) != hipSuccess) {
+            hold.unlock();
+            return false;
+        }
         // the counters start at zero (every tail leaves them so); ordered before the stream's first launch on this buffer
         if (hipMemsetAsync(p, 0, (size_t)kRestLists * kRestCntStride * sizeof(int32_t), st) != hipSuccess) {
             (void)hipFree(p);
+            hold.unlock();
             return false;
         }
-        if (mb->words) c->miss_retired.push_back(mb->words);  // (a launch in flight may still read it)
+        if (mb->words) {  // (a launch in flight may still read it)
+            std::lock_guard<std::mutex> g(c->miss_mu);
+            c->miss_retired.push_back(mb->words);
+        }
         mb->words = static_cast<int32_t *>(p);
         mb->cap = want;
     }
@@ -678,7 +715,8 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
         const int cap = rest_list_cap(n_words);
         int32_t *words = nullptr;
         int32_t *report = nullptr;
-        if (lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report) &&
+        std::unique_lock<std::mutex> pair;  // the stream's buffer, held until the tail is enqueued (miss_buffer)
+        if (lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report, pair) &&
             !c->split_off.load(std::memory_order_relaxed)) {
             size_t lds_memo = (size_t)kPlaceWaves * memo_stage_bytes(c->snap.T);  // a copy of the types' records per wavefront
             lds_memo = std::max(lds_memo, (size_t)c->memo_lds_min);
@@ -711,9 +749,10 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
         const int cap = rest_list_cap(n_words);
         int32_t *words = nullptr;
         int32_t *report = nullptr;
+        std::unique_lock<std::mutex> pair;  // (as above)
         // (the tail reads the tables from global memory: its requests are a handful)
         const size_t lds_tail = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(c->snap.T));
-        if (lds_tail + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report) &&
+        if (lds_tail + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report, pair) &&
             !c->split_off.load(std::memory_order_relaxed)) {
             PlaceArgs At = A;
             At.long_first = 1;
@@ -2860,6 +2899,7 @@ int mmp_shard_place_phase_dev(mmp_ctx *c, int32_t phase, const void *d_reqs, int
 try {
     if (!c || phase < 1 || phase > 7 || n < 0 || !d_xchg || (n > 0 && (!d_reqs || (phase == 7 && !d_outs))))
         return fail(c, MMP_EINVAL, "mmp_shard_place_phase_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_shard_place_phase_dev")) return rc;
     for (int i = 0; i < 6; i++)
         if (n > 0 && !d_xchg[i]) return fail(c, MMP_EINVAL, "mmp_shard_place_phase_dev: exchange buffer %d is null", i + 1);
     std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published shard snapshot + enqueue; no wait
@@ -2903,6 +2943,7 @@ int mmp_shard_place_fast_dev(mmp_ctx *c, const void *d_reqs, int32_t n, const vo
                              void *stream)
 try {
     if (!c || n < 0 || (n > 0 && (!d_reqs || !d_xf))) return fail(c, MMP_EINVAL, "mmp_shard_place_fast_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_shard_place_fast_dev")) return rc;
     std::lock_guard<std::shared_mutex> g(c->mu);
     if (c->n_shards < 1 || !c->committed) return fail(c, MMP_ESTATE, "no committed shard snapshot");
     if (n == 0) return MMP_OK;
@@ -3005,6 +3046,7 @@ int mmp_shard_place_fast_finish_dev(mmp_ctx *c, const void *d_reqs, int32_t n, c
 try {
     if (!c || n < 0 || !n_rest_out || !d_rest_reqs_out || !d_rest_outs_out || (n > 0 && (!d_reqs || !d_xf || !d_outs)))
         return fail(c, MMP_EINVAL, "mmp_shard_place_fast_finish_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_shard_place_fast_finish_dev")) return rc;
     *n_rest_out = 0;
     *d_rest_reqs_out = *d_rest_outs_out = nullptr;
     std::lock_guard<std::shared_mutex> g(c->mu);
@@ -3035,6 +3077,7 @@ try {
 int mmp_shard_place_fast_scatter_dev(mmp_ctx *c, int32_t n_rest, void *d_outs, void *stream)
 try {
     if (!c || n_rest < 0 || (n_rest > 0 && !d_outs)) return fail(c, MMP_EINVAL, "mmp_shard_place_fast_scatter_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_shard_place_fast_scatter_dev")) return rc;
     std::lock_guard<std::shared_mutex> g(c->mu);
     if (c->n_shards < 1 || !c->committed) return fail(c, MMP_ESTATE, "no committed shard snapshot");
     if (n_rest == 0) return MMP_OK;
@@ -3757,6 +3800,7 @@ try {
     if (!c || k < 0 || (k > 0 && (!d_reqs || !n || !d_outs))) return fail(c, MMP_EINVAL, "mmp_place_multi_dev: bad argument");
     for (int32_t i = 0; i < k; i++)
         if (n[i] < 0 || (n[i] > 0 && (!d_reqs[i] || !d_outs[i]))) return fail(c, MMP_EINVAL, "mmp_place_multi_dev: bad argument (array %d)", i);
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_place_multi_dev")) return rc;
     {  // launches handed to submission threads earlier are issued first: this call launches from the calling thread, in stream order
         std::shared_ptr<IssuePool> P;
         pool_get(c, P);
@@ -3803,6 +3847,7 @@ int mmp_place_batch_dev(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d
                         void *stream)
 try {
     if (!c || n < 0 || (n > 0 && (!d_reqs || !d_outs))) return fail(c, MMP_EINVAL, "mmp_place_batch_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_place_batch_dev")) return rc;
     std::shared_ptr<IssuePool> P;
     pool_get(c, P);
     if (P) {  // submission threads: append and return
@@ -3839,6 +3884,7 @@ try {
 int mmp_stream_retire(mmp_ctx *c, void *stream)
 try {
     if (!c) return MMP_EINVAL;
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_stream_retire")) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     (void)issue_flush(c);  // launches submitted for this stream have reached it
     {
@@ -3849,6 +3895,28 @@ try {
     }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(st));  // what was enqueued on it has finished reading the library's tables
+    // ... and its split batches with their buffer: the slot goes back (a stream created later may get the same handle)
+    mmp_ctx::MissBuf *mb = nullptr;
+    {
+        std::lock_guard<std::mutex> g(c->miss_mu);
+        for (auto &b : c->miss_bufs)
+            if (b.used && b.st == st) mb = &b;
+    }
+    if (mb) {
+        std::lock_guard<std::mutex> gs(mb->mu);
+        void *words = nullptr;
+        {
+            std::lock_guard<std::mutex> g(c->miss_mu);
+            if (mb->used && mb->st == st) {
+                words = mb->words;
+                mb->words = nullptr;
+                mb->cap = 0;
+                mb->used = false;
+                mb->st = nullptr;
+            }
+        }
+        if (words) HIP_TRY(c, hipFree(words));
+    }
     return MMP_OK;
 } catch (const std::bad_alloc &) {
     return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_stream_retire");
@@ -3861,6 +3929,7 @@ int mmp_place_batch_dev2(mmp_ctx *c, const void *d_reqs, int32_t n, const void *
 try {
     if (!c || n < 0 || n_extra_pool < 0 || (n > 0 && (!d_reqs || !d_outs)) || (n_extra_pool > 0 && !d_extra))
         return fail(c, MMP_EINVAL, "mmp_place_batch_dev2: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_place_batch_dev2")) return rc;
     std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published snapshot + enqueue; no wait
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
@@ -3880,6 +3949,7 @@ int mmp_place_batch_c_dev(mmp_ctx *c, const mmp_place_caller *caller, const void
 try {
     if (!c || !caller || n < 0 || n_extra_pool < 0 || (n > 0 && (!d_reqs || !d_outs)) || (n_extra_pool > 0 && !d_extra))
         return fail(c, MMP_EINVAL, "mmp_place_batch_c_dev: bad argument");
+    if (const int rc = refuse_per_thread_stream(c, stream, "mmp_place_batch_c_dev")) return rc;
     std::shared_lock<std::shared_mutex> g(c->mu);
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");

@@ -84,43 +84,82 @@ def test_requests_with_hostile_fields_are_decided_or_refused(ctx, data):
     assert (got["chosen"][~known] == -1).all() and (got["n_candidates"][~known] == 0).all()
 
 
+ROUTES = {  # how a batch of the bounded device-pointer calls is decided: the environment of mmp_create
+    "default": {},  # (600 rows: the one-launch kernels)
+    "split": {"MMP_MEMO_FROM": "0", "MMP_SPLIT_FROM": "0"},  # place_memo_kernel / place_memo_c_kernel + their tails
+    "long split": {"MMP_LONG_SPLIT_FROM": "0"},  # a full cluster: place_long_memo_kernel / place_long_memo_c_kernel + their tails
+}
+
+
+@pytest.fixture(scope="module", params=list(ROUTES))
+def route_ctx(request, ctx):
+    if request.param == "default":
+        yield request.param, ctx
+        return
+    with pytest.MonkeyPatch.context() as mp:
+        for k, v in ROUTES[request.param].items():
+            mp.setenv(k, v)
+        fleet = wl.make_fleet("C3") if request.param == "split" else wl.make_full_cluster(wl.make_fleet("C3"))
+        s = Solver(fleet.min_space_units, fleet.min_churn_age_ms)
+        s.load_fleet(fleet)
+    yield request.param, (s, fleet, OracleFleet(fleet))
+    s.close()
+
+
 @pytest.mark.parametrize("off,cnt", [(-1, 1), (0, -1), (INT_MAX, 1), (INT_MAX, INT_MAX), (5, 100), (0, 2**20), (INT_MIN, 3), (7, INT_MIN)])
-def test_exclusion_ranges_that_leave_the_pool_are_refused(ctx, off, cnt):
+def test_exclusion_ranges_that_leave_the_pool_are_refused(route_ctx, off, cnt):
     """Host-pointer calls validate every request's range against the pool's length (int64 arithmetic: off + cnt must not wrap);
-    bounded device-pointer calls answer such a request {MMP_NONE, MMP_BAD_REQUEST, 0, 0} and decide the others."""
+    bounded device-pointer calls answer such a request {MMP_NONE, MMP_BAD_REQUEST, 0, 0} and decide the others — by every route a
+    batch can take: in the split ones the first launch answers it (place_memo_body, place_long_memo_body), in a wavefront whose other
+    rows it leaves to the tail (their exclusions name the first instances of the placement order, where the records are)."""
     import torch
-    s, fleet, orc = ctx
-    reqs, extra = wl.make_requests(fleet, 5, n=600)
+    route, (s, fleet, orc) = route_ctx
+    split = route != "default"
+    # (split routes: no exclusions of the generator's own, so that the pool stays shorter than the ranges above that must leave it)
+    reqs, extra = wl.make_requests(fleet, 5, n=4096 if split else 600, extra_frac=0.0 if split else 0.05)
     extra = np.concatenate([extra, np.zeros(8, np.int32)])
+    if split:  # every fourth row of the bad row's wavefront excludes the head of the order: the first launch leaves those
+        reqs["extra_off"][0:64:4], reqs["n_extra"][0:64:4] = len(extra), 2
+        extra = np.concatenate([extra, np.asarray(orc.order[:2], dtype=np.int32)])
     bad = reqs.copy()
     bad["extra_off"][17], bad["n_extra"][17] = off, cnt
     out = np.zeros(len(bad), _lib.PLACE_OUT)
     rc = s.lib.mmp_place_batch(s.h, _lib.ptr(bad), len(bad), _lib.ptr(extra), len(extra), fleet.now, _lib.ptr(out))
     assert rc == EINVAL, rc
-    caller, rc_rows = _lib.split_caller(_one_caller(fleet, bad))
+    pod = 3 if not split else int(orc.order[-1])  # (split routes: a caller that does not steer every walk of the batch)
+    caller, rc_rows = _lib.split_caller(_one_caller(fleet, bad, pod))
     cp = np.ascontiguousarray(caller, dtype=_lib.PLACE_CALLER).reshape(1)
     assert s.lib.mmp_place_batch_c(s.h, _lib.ptr(cp), _lib.ptr(rc_rows), len(rc_rows), _lib.ptr(extra), len(extra), fleet.now, _lib.ptr(out)) == EINVAL
-    # the bounded device-pointer call: the request is refused by the kernel, its neighbours are decided
+    # the bounded device-pointer calls: the request is refused by the kernel, its neighbours are decided
     dev = torch.device("cuda", 0)
-    d_r = torch.from_numpy(bad.view(np.uint8).reshape(-1)).to(dev)
     d_e = torch.from_numpy(extra).to(dev)
-    d_o = torch.zeros(len(bad) * 16, dtype=torch.uint8, device=dev)
-    st_ = torch.cuda.Stream(dev)
-    s.place_dev2(d_r.data_ptr(), len(bad), d_e.data_ptr(), len(extra), fleet.now, d_o.data_ptr(), st_.cuda_stream)
-    torch.cuda.synchronize()
-    got = np.frombuffer(d_o.cpu().numpy().tobytes(), dtype=_lib.PLACE_OUT)
-    assert (got["chosen"][17], got["best"][17], got["n_candidates"][17], got["hash"][17]) == (-1, BAD_REQUEST, 0, 0)
-    want = orc.place(reqs, extra, fleet.now)
     keep = np.arange(len(bad)) != 17
-    for f in ("chosen", "best", "n_candidates", "hash"):
-        assert np.array_equal(got[f][keep], want[f][keep]), f
-    s.lib.mmp_stream_retire(s.h, C.c_void_p(st_.cuda_stream))
+    for form in ("rows", "caller"):
+        rows = bad if form == "rows" else rc_rows
+        d_r = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(-1).copy()).to(dev)
+        d_o = torch.full((len(bad) * 16,), 0xFF, dtype=torch.uint8, device=dev)
+        st_ = torch.cuda.Stream(dev)
+        n_split = s.split_batches()[0]
+        if form == "rows":
+            s.place_dev2(d_r.data_ptr(), len(bad), d_e.data_ptr(), len(extra), fleet.now, d_o.data_ptr(), st_.cuda_stream)
+        else:
+            s.place_c_dev(cp, d_r.data_ptr(), len(bad), d_e.data_ptr(), len(extra), fleet.now, d_o.data_ptr(), st_.cuda_stream)
+        torch.cuda.synchronize()
+        if split:
+            assert s.split_batches()[0] == n_split + 1, (route, form, "the batch did not take the split route")
+        got = np.frombuffer(d_o.cpu().numpy().tobytes(), dtype=_lib.PLACE_OUT)
+        assert (got["chosen"][17], got["best"][17], got["n_candidates"][17], got["hash"][17]) == (-1, BAD_REQUEST, 0, 0), (route, form)
+        good = reqs if form == "rows" else _one_caller(fleet, reqs, pod)
+        want = orc.place(good, extra, fleet.now)
+        for f in ("chosen", "best", "n_candidates", "hash"):
+            assert np.array_equal(got[f][keep], want[f][keep]), (route, form, f)
+        assert s.lib.mmp_stream_retire(s.h, C.c_void_p(st_.cuda_stream)) == 0
 
 
-def _one_caller(fleet, reqs):
+def _one_caller(fleet, reqs, pod=3):
     out = reqs.copy()
-    row = fleet.pods[3]
-    out["self_pod"], out["flags"], out["fresh_rpm"] = 3, 0, 0
+    row = fleet.pods[pod]
+    out["self_pod"], out["flags"], out["fresh_rpm"] = pod, 0, 0
     out["fresh_lru"], out["fresh_capacity"], out["fresh_used"], out["fresh_count"] = row["lru_time"], row["capacity"], row["used"], row["count"]
     return out
 
