@@ -142,6 +142,30 @@ struct FastSlot {
     std::atomic<uint32_t> seq{0};
 };
 
+// The environment switches (all MMP_*), read once per context at mmp_create (read_tuning).  The defaults are the product's routes;
+// the switches force routes for the tests and for comparison runs.
+struct Tuning {
+    int32_t force_wave = 0;      // MMP_FORCE_WAVE=1: every decision takes the wave-per-decision kernel (tests)
+    int32_t no_memo = 0;         // MMP_NO_MEMO=1: batches do not use the per-type shortlists (place_kernel.hpp: TypeMemo)
+    int32_t memo_from = -1;      // MMP_MEMO_FROM=n: decisions from which a batch takes the kernel with the shortlists in front (default kMemoFrom / kMemoFromC)
+    int32_t no_long_memo = 0;    // MMP_NO_LONG_MEMO=1: commit records no walks of the long shortlists (place_kernel.hpp: LongMemo)
+    int32_t no_split = 0;        // MMP_NO_SPLIT=1: batches are never split (place_memo_kernel + place_tail_kernel); the one-launch kernels instead
+    int32_t split_from = -1;     // MMP_SPLIT_FROM=n: decisions from which a batch is split (default kSplitFrom / kSplitFromC)
+    int32_t long_split_from = -1;  // MMP_LONG_SPLIT_FROM=n: requests from which a full-cluster batch is split (default kLongSplitFrom)
+    int32_t tail_blocks = kTailBlocks;  // MMP_TAIL_BLOCKS=n: workgroups of a split batch's tail launch (1 .. kRestLists)
+    int32_t split_notail = 0;    // MMP_SPLIT_NOTAIL=1: the tail launch is left out — the batch's results are INCOMPLETE (bench.py times the first launch alone)
+    int32_t no_long_lds = 0;     // MMP_NO_LONG_LDS=1: the long path reads its per-type tables from global memory (tests, comparison)
+    int32_t no_caseb = 0;        // MMP_NO_CASEB=1: case (b) decisions never use the whole-window tables (tests: the wave path decides them)
+    int32_t long_dense_from = kLongDenseFrom;  // MMP_LONG_DENSE_FROM=n: decisions from which a full-cluster batch takes the 4-wavefront instantiation with its tables staged in LDS
+    bool long_dense_env = false;                // (... and whether it was given: see dense_from)
+    int32_t long_mode = -1;      // MMP_LONG_MODE: -1 auto (the long-shortlist kernel for snapshots whose instances are nearly all full), 0 never, 1 always (tests)
+    int32_t rank_mode = 0;       // MMP_RANK_MODE: 0 auto (rank by sampling from kRankSortMinPods pods), 1 all-pairs, 2 by sampling whenever legal, 3 merge sort whenever legal (tests)
+    int32_t no_delta = 0;        // MMP_NO_DELTA=1: every commit ranks from scratch (tests)
+    int32_t plan_sorted = 0;     // MMP_PLAN_SORTED=1: mmp_proactive_plan takes its sorted (fallback) path on every input; 2: never (tests)
+    int32_t plan_fused = 1;      // MMP_PLAN_FUSED=0: the plan as its eight dependent launches (comparison; the one-launch form is the default)
+    int32_t resident = 0;        // MMP_RESIDENT=1: mmp_create turns the resident decision kernel on (mmp_resident)
+};
+
 struct mmp_ctx {
     mmp_config cfg{};
     hipStream_t stream = nullptr;
@@ -188,7 +212,6 @@ struct mmp_ctx {
     bool prof = false, prof_armed = false;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     double last_kernel_ms = -1.0;
-    int32_t force_wave = 0;  // MMP_FORCE_WAVE=1: every decision takes the wave-per-decision kernel (tests)
     size_t lds_limit = 64 * 1024;    // LDS a workgroup may use on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     // a registry event's in-place rewrite is enqueued under the state lock and finishes after it: kernels that read the registry
     // from other streams are ordered behind reg_event while reg_pending (order_after_registry)
@@ -196,24 +219,9 @@ struct mmp_ctx {
     hipEvent_t reg_event = nullptr;
     std::atomic<bool> reg_pending{false};
     std::atomic<size_t> lds_granted{48 * 1024};  // dynamic LDS the place kernels may be launched with so far
-    int32_t no_caseb = 0;    // MMP_NO_CASEB=1: case (b) decisions never use the whole-window tables (tests: the wave path decides them)
-    int32_t cfg_plan_sorted = 0;  // MMP_PLAN_SORTED=1: mmp_proactive_plan takes its sorted (fallback) path on every input; 2: never (tests)
-    int32_t cfg_plan_fused = 1;   // MMP_PLAN_FUSED=0: the plan as its eight dependent launches (comparison; the one-launch form is the default)
+    Tuning tune;                  // the environment switches (read_tuning)
     int32_t plan_grid_max = 0;    // workgroups the one-launch plan may have: all of them resident at once
-    int32_t no_long_lds = 0; // MMP_NO_LONG_LDS=1: the long path reads its per-type tables from global memory (tests, comparison)
-    int32_t long_split_from = -1;  // MMP_LONG_SPLIT_FROM=n: requests from which a full-cluster batch is split (default kLongSplitFrom)
-    int32_t no_long_memo = 0;  // MMP_NO_LONG_MEMO=1: commit records no walks of the long shortlists (place_kernel.hpp: LongMemo)
-    int32_t no_memo = 0;     // MMP_NO_MEMO=1: batches do not use the per-type shortlists (place_kernel.hpp: TypeMemo)
-    int32_t memo_from = -1;  // MMP_MEMO_FROM=n: decisions from which a batch takes the kernel with the shortlists in front (default kMemoFrom)
-    bool long_dense_env = false;  // MMP_LONG_DENSE_FROM was given
-    int32_t long_dense_from = kLongDenseFrom;  // MMP_LONG_DENSE_FROM=n: decisions from which a full-cluster batch takes the 4-wavefront instantiation with its tables staged in LDS
-    int32_t no_heads = 0;    // MMP_NO_HEADS=1: decisions do not use the per-type head windows (tests: lane_decide_r alone)
-    // the split form of a large batch (place_kernel.hpp: place_memo_kernel + place_tail_kernel)
-    int32_t no_split = 0;    // MMP_NO_SPLIT=1: never (the one-launch kernels with the check in front instead)
-    int32_t split_from = -1; // MMP_SPLIT_FROM=n: decisions from which a batch is split (default kSplitFrom / kSplitFromC)
-    int32_t tail_blocks = kTailBlocks;  // MMP_TAIL_BLOCKS: workgroups of the tail launch
-    int32_t memo_lds_min = 0;  // MMP_MEMO_LDS_MIN=bytes: dynamic LDS the first launch of a split batch asks for at least (an occupancy cap: see kMemoLdsMin)
-    int32_t split_notail = 0;  // MMP_SPLIT_NOTAIL=1: the tail launch is left out — the batch's results are INCOMPLETE (timing the first launch alone)
+    // the split form of a large batch (place_kernel.hpp: place_memo_kernel + place_tail_kernel):
     // per stream that has issued a split batch: the words its first launches leave for its tails (launches of one stream are ordered,
     // so one buffer per stream will do) and a pinned pair the tail reports to: {undecided, of how many}.  A tail decides whatever
     // the lists hold and zeroes them, so the two launches of a batch must follow each other on the stream: `mu` is held from the
@@ -256,7 +264,6 @@ struct mmp_ctx {
     int32_t shard = 0, n_shards = 0;
     ShardSnap ssnap{};
     DevBuf rk_rows, rk_idx, rk_tmp;  // ranking by sorting (snapshot.hpp)
-    int32_t long_mode = -1;  // MMP_LONG_MODE: -1 auto (the long-shortlist kernel for snapshots whose instances are nearly all full), 0 never, 1 always (tests)
     bool snap_long = false;  // the committed snapshot takes place_batch_long_kernel
     bool snap_full = false;  // ... because (nearly) all of its instances are full (not only because a type is sparse)
     // the rows written since the last commit (a commit of a few changed rows re-ranks by insertion: delta_scatter_kernel)
@@ -270,10 +277,7 @@ struct mmp_ctx {
     bool order_total = false;       // the published order came from a total order (sort-legal rows): unchanged rows keep their order
     std::vector<int32_t> h_order, h_pos;  // host mirror of the published order (position -> row, row -> position), fetched lazily
     bool h_order_valid = false;
-    int32_t single_block = 0;       // MMP_SINGLE_BLOCK=1: a single decision runs the batch kernel's workgroup (place_single_kernel)
-    int32_t no_delta = 0;           // MMP_NO_DELTA=1: every commit ranks from scratch (tests)
     int64_t n_delta_commits = 0;
-    int32_t rank_mode = 0;  // MMP_RANK_MODE: 0 auto (rank by sampling from kRankSortMinPods pods), 1 all-pairs, 2 by sampling whenever legal, 3 merge sort whenever legal (tests)
     Snap sview{};  // the lane path's view of this shard's slice (place_shard_fast_kernel)
     DevBuf f_offs, f_idx, f_reqs, f_outs, f_scan_tmp;  // speculative form: the compacted rest of a batch
     // ... and what ONE batch in flight owns until its rest count has been read, twice (slot = batch parity): an asynchronous
@@ -530,9 +534,6 @@ hipError_t slot_wait(FastSlot *f, uint32_t seq)
 }
 
 hipError_t order_after_registry(mmp_ctx *c, hipStream_t st);
-#ifdef MMP_XP_EMPTYTAIL  // (experiment builds only, tools/r6: what the runtime charges for a second launch per call, whatever it does)
-__global__ void xp_noop_kernel(int32_t *p) { if (p == nullptr) __builtin_trap(); }
-#endif
 // The buffer of a split batch on `st` (`ints`: rest_buffer_ints of its first launch) and the stream's report pair, returned with the
 // stream's slot locked in `hold` (the caller enqueues both launches before it lets go); false: none to be had (too many streams, no
 // memory) — the batch goes unsplit, nothing is held.  Also reads what the stream's last tail reported.
@@ -606,51 +607,187 @@ void split_reset(mmp_ctx *c)
     if (c->miss_reports) memset(c->miss_reports, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
     c->split_off.store(false, std::memory_order_relaxed);
 }
-// what only some callers of place_launch bring: the caller's side of the single-caller form (d_reqs are mmp_place_req_c rows then),
-// the declared length of the exclusion pool (bounded calls; extra_bound = 1 + entries, 0 = not declared)
-struct PlaceOpts {
-    const mmp_place_caller *caller = nullptr;
-    int32_t extra_bound = 0;
-};
-int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int64_t now, void *d_outs,
-                 hipStream_t st, uint32_t *done_flag = nullptr, uint32_t done_seq = 0, const mmp_place_req *inline_req = nullptr,
-                 uint32_t *done_blocks = nullptr, const PlaceSegs *segs = nullptr, int32_t seg_blocks = 0, const GateArgs *fused_gate = nullptr,
-                 const mmp_gate_req *fused_greq = nullptr, const PlaceOpts *opts = nullptr)
+
+Tuning read_tuning()
 {
-    if (n == 0) return MMP_OK;
+    Tuning t;
+    const auto flag = [](const char *name, int32_t &v) { if (const char *e = getenv(name)) v = e[0] == '1'; };
+    const auto num = [](const char *name, int32_t &v) { if (const char *e = getenv(name)) v = atoi(e); };
+    flag("MMP_FORCE_WAVE", t.force_wave);
+    flag("MMP_NO_MEMO", t.no_memo), num("MMP_MEMO_FROM", t.memo_from), flag("MMP_NO_LONG_MEMO", t.no_long_memo);
+    flag("MMP_NO_SPLIT", t.no_split), num("MMP_SPLIT_FROM", t.split_from), num("MMP_LONG_SPLIT_FROM", t.long_split_from);
+    num("MMP_TAIL_BLOCKS", t.tail_blocks);
+    t.tail_blocks = std::max(1, std::min(t.tail_blocks, kRestLists));
+    flag("MMP_SPLIT_NOTAIL", t.split_notail), flag("MMP_NO_LONG_LDS", t.no_long_lds), flag("MMP_NO_CASEB", t.no_caseb);
+    t.long_dense_env = getenv("MMP_LONG_DENSE_FROM") != nullptr;
+    num("MMP_LONG_DENSE_FROM", t.long_dense_from), num("MMP_LONG_MODE", t.long_mode);
+    num("MMP_RANK_MODE", t.rank_mode), flag("MMP_NO_DELTA", t.no_delta);
+    num("MMP_PLAN_SORTED", t.plan_sorted), num("MMP_PLAN_FUSED", t.plan_fused);
+    flag("MMP_RESIDENT", t.resident);
+    return t;
+}
+
+// The argument block of the place kernels, as far as every caller fills it alike: `rmodels` is the registry view resolved against the
+// published snapshot (null where the caller does not use it, or it is not built); the caller sets what is its own (wins, mtw, n_dev,
+// force_wave, the latency fields) afterwards.
+PlaceArgs place_args(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int64_t now, void *d_outs, bool resolved, int32_t n_pods_all)
+{
     PlaceArgs A{};
     A.reqs = static_cast<const mmp_place_req *>(d_reqs);
     A.models = c->models.as<mmp_model_row>();
-    A.rmodels = cur_side(c).rmodels_ok ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr;
-    A.mtw = cur_side(c).rmodels_ok ? cur_side(c).mtw.as<int32_t>() : nullptr;
-    A.wins = (c->no_heads || c->n_shards > 0) ? nullptr : c->sb[c->cur].heads.as<TypeWin>();
+    A.rmodels = (resolved && cur_side(c).rmodels_ok) ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr;
     A.ent_pod = c->ent_pod.as<int32_t>();
     A.extra = static_cast<const int32_t *>(d_extra);
     A.outs = static_cast<mmp_place_out *>(d_outs);
     A.n = n;
     A.n_models = c->n_models;
     A.now = now;
-    A.n_dev = nullptr;
-    A.force_wave = c->force_wave;
-    A.n_pods_all = c->snap.P;
-    A.done_flag = done_flag;
-    A.done_seq = done_seq;
-    A.extra_bound = opts ? opts->extra_bound : 0;
-    const mmp_place_caller *caller = opts ? opts->caller : nullptr;
-    if (caller && (segs || inline_req || done_flag)) return fail(c, MMP_EINVAL, "the single-caller form takes the batch kernels only");
-    const int wpad = (c->snap.W + 1) & ~1;
+    A.n_pods_all = n_pods_all;
+    return A;
+}
+
+// What only some callers of place_launch bring; all unset: a batch of mmp_place_req rows on one stream.
+struct PlaceCall {
+    const mmp_place_caller *caller = nullptr;  // the single-caller form: the requests are mmp_place_req_c rows (batch kernels only)
+    int32_t extra_bound = 0;                   // bounded calls: 1 + the entries of the exclusion pool the caller declared; 0: not declared
+    // the latency path (FastSlot): the pinned completion flag, this launch's sequence number, the slot's workgroup counter
+    uint32_t *done_flag = nullptr;
+    uint32_t done_seq = 0;
+    uint32_t *done_blocks = nullptr;
+    const mmp_place_req *inline_req = nullptr;  // one request without exclusions, passed in the kernel arguments
+    const PlaceSegs *segs = nullptr;            // several request arrays in one launch of seg_blocks workgroups (multi_kernel.hpp)
+    int32_t seg_blocks = 0;
+    const GateArgs *fused_gate = nullptr;       // with inline_req: the cache-miss route, the guards beside the load target
+    const mmp_gate_req *fused_greq = nullptr;
+};
+
+// the latency path's launch on slot `f` (called with the state lock held: the sequence number is bumped here)
+PlaceCall slot_call(FastSlot *f, const mmp_place_req *inline_req)
+{
+    PlaceCall o;
+    o.done_flag = f->done;
+    o.done_seq = ++f->seq;
+    o.done_blocks = f->blocks;
+    o.inline_req = inline_req;
+    return o;
+}
+
+// The kernel (or, for a split batch, the pair of kernels) a place launch takes.
+enum class PlaceRoute {
+    memo_split, memo_split_c,  // place_memo_kernel + place_tail_kernel (_c: the single-caller form)
+    long_split, long_split_c,  // place_long_memo_kernel + place_long_tail_kernel
+    multi, multi_m, multi_long, multi_long4,
+    miss_single, single_lean, flag,
+    batch, batch_m, batch_c, batch_c_m, batch_long, batch_long4, batch_long_c, batch_long4_c,
+};
+bool is_split(PlaceRoute r) { return r <= PlaceRoute::long_split_c; }  // (the split routes come first)
+
+// What the route depends on besides the tuning, the call and its size: plain values, captured under the state lock.
+struct RouteState {
+    bool snap_long = false, snap_full = false;  // mmp_ctx::snap_long / snap_full
+    bool memo = false, lmemo = false;           // the snapshot has TypeMemo / LongMemo records
+    bool wins = false, rmodels = false;         // PlaceArgs::wins / rmodels are set
+    bool split_ok = false;                      // a split buffer is to be had for the stream and split_off is not set
+    bool memo_tail_lds = false, long_tail_lds = false;  // the tail of a memo / long split fits the device's LDS
+};
+
+// the long kernel on a full cluster: the case (b) tables and the first lane phase on the prefix tables (PlaceArgs::long_first)
+bool long_first(const RouteState &s) { return s.snap_long && s.snap_full && s.rmodels; }
+
+// decisions from which a full-cluster batch takes the 4-wavefront instantiation with its tables in LDS.  With the recorded long walks
+// (place_kernel.hpp: LongMemo) hardly a request searches those tables, and the barrier-free instantiation is the faster one at every
+// size (C3 full cluster, 200k / 400k / 800k requests per launch: 16.0 / 25.6 / 40.3 us against 18.5 / 28.9 / 43.5 us;
+// profiles/r6/long_records.txt) — unless MMP_LONG_DENSE_FROM is given.
+int32_t dense_from(const Tuning &t, const RouteState &s)
+{
+    return (long_first(s) && s.lmemo && !t.long_dense_env) ? INT32_MAX : t.long_dense_from;
+}
+
+PlaceRoute place_route(const Tuning &t, const RouteState &s, int32_t n, const PlaceCall &o)
+{
+    const bool caller = o.caller != nullptr, latency = o.inline_req || o.done_flag;
+    // batches with the per-type shortlists in front: head windows and the resolved registry view in place, not the full-cluster
+    // regime (its shortlists span the table), none of the diagnostic routes, a launch that fills the chip
+    const bool use_memo = !latency && !s.snap_long && !t.no_memo && !t.force_wave && s.wins && s.rmodels && s.memo &&
+                          n >= (t.memo_from >= 0 ? t.memo_from : (caller ? kMemoFromC : kMemoFrom));
+    // the split form: the check alone in a launch of its own, the rest in a dense tail behind it (place_kernel.hpp: place_memo_kernel);
+    // one launch instead when there is no buffer, split_off is set or the tail's LDS does not fit
+    const bool split = !o.segs && !t.no_split && s.split_ok;
+    if (use_memo && split && s.memo_tail_lds && n >= (t.split_from >= 0 ? t.split_from : (caller ? kSplitFromC : kSplitFrom)))
+        return caller ? PlaceRoute::memo_split_c : PlaceRoute::memo_split;
+    // ... and on a full cluster: the recorded long walks alone in the first launch (place_kernel.hpp: place_long_memo_kernel)
+    if (long_first(s) && s.lmemo && split && !latency && !t.force_wave && s.long_tail_lds &&
+        n >= (t.long_split_from >= 0 ? t.long_split_from : kLongSplitFrom))
+        return caller ? PlaceRoute::long_split_c : PlaceRoute::long_split;
+    if (o.segs) {
+        // (the multi path compares with MMP_LONG_DENSE_FROM's value as it is, the batch path with dense_from())
+        if (s.snap_long) return n >= t.long_dense_from ? PlaceRoute::multi_long4 : PlaceRoute::multi_long;
+        return use_memo ? PlaceRoute::multi_m : PlaceRoute::multi;
+    }
+    if (o.inline_req) return o.fused_gate ? PlaceRoute::miss_single : PlaceRoute::single_lean;
+    if (o.done_flag && n > kPlaceBlock) return PlaceRoute::flag;
+    if (caller && s.snap_long) return n >= dense_from(t, s) ? PlaceRoute::batch_long4_c : PlaceRoute::batch_long_c;
+    if (use_memo) return caller ? PlaceRoute::batch_c_m : PlaceRoute::batch_m;
+    if (caller) return PlaceRoute::batch_c;
+    if (s.snap_long) return n >= dense_from(t, s) ? PlaceRoute::batch_long4 : PlaceRoute::batch_long;
+    return PlaceRoute::batch;
+}
+
+template <class K>
+const void *kfn(K *k) { return reinterpret_cast<const void *>(k); }
+// Dynamic LDS beyond the default grant (48 KB): asked once for every place kernel, up to the device's limit less the static part.
+int grant_place_lds(mmp_ctx *c)
+{
+    static std::mutex grant_mu;  // (decision paths hold the state lock shared)
+    std::lock_guard<std::mutex> g(grant_mu);
+    const int want = (int)(c->lds_limit - kPlaceStaticLds);
+    const int tail = want - kTailStaticLds;  // the tails keep kTailStaticLds of static LDS beside place_block's own
+    const struct {
+        const void *fn;
+        int max_lds;
+    } kernels[] = {
+        {kfn(place_batch_kernel), want}, {kfn(place_batch_m_kernel), want}, {kfn(place_batch_c_kernel), want},
+        {kfn(place_batch_c_m_kernel), want}, {kfn(place_batch_long_kernel), want}, {kfn(place_batch_long4_kernel), want},
+        {kfn(place_batch_long_c_kernel), want}, {kfn(place_batch_long4_c_kernel), want}, {kfn(place_batch_flag_kernel), want},
+        {kfn(place_single_lean_kernel), want}, {kfn(miss_single_kernel), want}, {kfn(place_multi_kernel), want},
+        {kfn(place_multi_m_kernel), want}, {kfn(place_multi_long_kernel), want}, {kfn(place_multi_long4_kernel), want},
+        {kfn(place_tail_kernel), tail}, {kfn(place_tail_c_kernel), tail}, {kfn(place_long_tail_kernel), tail},
+        {kfn(place_long_tail_c_kernel), tail},
+    };
+    for (const auto &k : kernels) HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.max_lds));
+    c->lds_granted.store((size_t)want, std::memory_order_release);
+    return MMP_OK;
+}
+
+int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int64_t now, void *d_outs, hipStream_t st,
+                 const PlaceCall &o = PlaceCall{})
+{
+    if (n == 0) return MMP_OK;
+    if (o.caller && (o.segs || o.inline_req || o.done_flag)) return fail(c, MMP_EINVAL, "the single-caller form takes the batch kernels only");
+    const Tuning &t = c->tune;
+    const Snap &S = c->snap;
+    const SnapBufs &B = c->sb[c->cur];
+    // 1. the argument block and the dynamic LDS
+    PlaceArgs A = place_args(c, d_reqs, n, d_extra, now, d_outs, true, S.P);
+    A.mtw = cur_side(c).rmodels_ok ? cur_side(c).mtw.as<int32_t>() : nullptr;
+    A.wins = c->n_shards > 0 ? nullptr : B.heads.as<TypeWin>();
+    A.force_wave = t.force_wave;
+    A.done_flag = o.done_flag;
+    A.done_seq = o.done_seq;
+    A.extra_bound = o.extra_bound;
+    RouteState rs;
+    rs.snap_long = c->snap_long, rs.snap_full = c->snap_full, rs.memo = S.memo != nullptr, rs.lmemo = S.lmemo != nullptr;
+    rs.wins = A.wins != nullptr, rs.rmodels = A.rmodels != nullptr;
+    const bool latency = o.inline_req || o.done_flag;
+    const int wpad = (S.W + 1) & ~1;
     // one dynamic region: the lane phase's windows + scratch, re-used by the wave path's tiles (place_block)
-    size_t lds = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(c->snap.T));
-    // the long kernel on a full cluster: the case (b) tables of the snapshot's preferring types (place_kernel.hpp: BSlot)
-    A.long_first = (c->snap_long && c->snap_full && A.rmodels) ? 1 : 0;
+    const size_t lds_base = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(S.T));
+    size_t lds = lds_base;
+    A.long_first = long_first(rs) ? 1 : 0;
     // the long path's per-type tables in LDS when they are small (C3: 20 KB) and the launch fills the chip: measured on the full
     // cluster, 800k decisions per launch 70.8 -> 67.1 us; at 100k (1.5 wavefronts per SIMD) 20.4 -> 21.0 us, hence the size condition
-    // With the recorded long walks (place_kernel.hpp: LongMemo) hardly a request searches those tables, and the barrier-free
-    // instantiation is the faster one at every size (C3 full cluster, 200k / 400k / 800k requests per launch: 16.0 / 25.6 / 40.3 us against
-    // 18.5 / 28.9 / 43.5 us; profiles/r6/long_records.txt)
-    const int32_t dense_from = (A.long_first && c->snap.lmemo && !c->long_dense_env) ? INT32_MAX : c->long_dense_from;
-    if (A.long_first && !inline_req && !done_flag && !c->no_long_lds && n >= dense_from) {
-        const size_t tb = long_tables_bytes(c->snap.T, c->snap.W);
+    if (A.long_first && !latency && !t.no_long_lds && n >= dense_from(t, rs)) {
+        const size_t tb = long_tables_bytes(S.T, S.W);
         // (only where they fit beside the wave tile and the static part: a device with 64 KB of LDS per workgroup keeps reading
         // them from global memory instead of failing the launch)
         if (tb <= 24 * 1024 && ((lds + 15) & ~(size_t)15) + tb + kPlaceStaticLds <= c->lds_limit) {
@@ -659,153 +796,85 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
             lds = off + tb;
         }
     }
-    if (c->snap_long && !inline_req && !done_flag && A.wins && !c->no_caseb) {
-        const SnapBufs &B = c->sb[c->cur];
-        if (B.n_bslots > 0) {
-            A.bslots = B.bslots.as<BSlot>();
-            A.n_bslots = std::min(B.n_bslots, kBSlots);
-            A.bwin = B.bwin.as<BLaunch>();
-            A.bsurv = B.bsurv.as<uint64_t>();
-            A.bpcs = B.bpcs.as<int32_t>();
-        }
+    if (c->snap_long && !latency && A.wins && !t.no_caseb && B.n_bslots > 0) {
+        A.bslots = B.bslots.as<BSlot>();
+        A.n_bslots = std::min(B.n_bslots, kBSlots);
+        A.bwin = B.bwin.as<BLaunch>();
+        A.bsurv = B.bsurv.as<uint64_t>();
+        A.bpcs = B.bpcs.as<int32_t>();
     }
     // the wave path's tile (two bitmaps of the whole table per wavefront) next to the static LDS of place_block;
     // gfx950 gives a workgroup up to 160 KB (c->lds_limit is the device's answer), which admits ~120k instances
     if (lds + kPlaceStaticLds > c->lds_limit)
         return fail(c, MMP_EINVAL, "instance table too large for the LDS staging tile (%d pods: %zu + %d bytes of LDS, the device "
-                    "gives a workgroup %zu)", c->snap.P, lds, kPlaceStaticLds, c->lds_limit);
-    if (lds > c->lds_granted.load(std::memory_order_acquire)) {  // beyond the default dynamic-LDS grant: ask once, for every variant
-        static std::mutex grant_mu;  // (decision paths hold the state lock shared)
-        std::lock_guard<std::mutex> gg(grant_mu);
-        const int want = (int)(c->lds_limit - kPlaceStaticLds);
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_long4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_flag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_single_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_single_lean_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(miss_single_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_multi_m_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_multi_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_multi_long4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_c_m_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_m_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_long_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_batch_long4_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want - kTailStaticLds));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_tail_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want - kTailStaticLds));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_long_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want - kTailStaticLds));
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(place_long_tail_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, want - kTailStaticLds));
-        c->lds_granted.store((size_t)want, std::memory_order_release);
-    }
-    // batches with the per-type shortlists in front (place_batch_m_kernel / place_batch_c_m_kernel): head windows and the resolved registry
-    // view in place, not the full-cluster regime (its shortlists span the table), none of the diagnostic routes, a launch that fills the chip
-    const bool use_memo = !inline_req && !done_flag && !c->snap_long && !c->no_memo && !c->force_wave && A.wins && A.rmodels && c->snap.memo &&
-                          n >= (c->memo_from >= 0 ? c->memo_from : (caller ? kMemoFromC : kMemoFrom));
+                    "gives a workgroup %zu)", S.P, lds, kPlaceStaticLds, c->lds_limit);
+    if (lds > c->lds_granted.load(std::memory_order_acquire))
+        if (const int rc = grant_place_lds(c)) return rc;
     // NOBAR kernels: a region per wavefront (place_wave_lds) instead of the shared one
     const size_t lds_nobar = (size_t)kPlaceWaves * place_wave_lds(wpad);
+    // (the memo split checks its tail against `lds`, the long split against lds_base: the long tail reads the tables from global
+    // memory, its requests are a handful)
+    rs.memo_tail_lds = lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit;
+    rs.long_tail_lds = lds_base + kPlaceStaticLds + kTailStaticLds <= c->lds_limit;
     HIP_TRY(c, order_after_registry(c, st));
-    // the split form: the check alone in a launch of its own, the rest in a dense tail behind it (place_kernel.hpp: place_memo_kernel)
-    if (use_memo && !segs && !c->no_split && !c->split_off.load(std::memory_order_relaxed) &&
-        n >= (c->split_from >= 0 ? c->split_from : (caller ? kSplitFromC : kSplitFrom))) {
-        const int grid = div_up(n, kPlaceBlock);
-        const int n_words = grid * kPlaceWaves;  // wavefronts of the first launch
-        const int cap = rest_list_cap(n_words);
-        int32_t *words = nullptr;
-        int32_t *report = nullptr;
-        std::unique_lock<std::mutex> pair;  // the stream's buffer, held until the tail is enqueued (miss_buffer)
-        if (lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report, pair) &&
-            !c->split_off.load(std::memory_order_relaxed)) {
-            size_t lds_memo = (size_t)kPlaceWaves * memo_stage_bytes(c->snap.T);  // a copy of the types' records per wavefront
-            lds_memo = std::max(lds_memo, (size_t)c->memo_lds_min);
-            if (c->split_notail) words = nullptr;  // (diagnostics: the undecided requests are not even recorded)
-            if (caller) {
-                hipLaunchKernelGGL(place_memo_c_kernel, dim3(grid), dim3(kPlaceBlock), lds_memo, st, c->snap, A, words, cap, *caller);
-                if (!c->split_notail)
-                    hipLaunchKernelGGL(place_tail_c_kernel, dim3(c->tail_blocks), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, words, cap, report, *caller);
-            } else {
-                hipLaunchKernelGGL(place_memo_kernel, dim3(grid), dim3(kPlaceBlock), lds_memo, st, c->snap, A, words, cap);
-#ifdef MMP_XP_EMPTYTAIL
-                if (getenv("MMP_XP_EMPTYTAIL")) {
-                    hipLaunchKernelGGL(xp_noop_kernel, dim3(atoi(getenv("MMP_XP_EMPTYTAIL"))), dim3(kPlaceBlock), 0, st, words);
-                    return MMP_OK;
-                }
-#endif
-                if (!c->split_notail)
-                    hipLaunchKernelGGL(place_tail_kernel, dim3(c->tail_blocks), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, words, cap, report);
-            }
-            HIP_TRY(c, hipGetLastError());
-            c->n_split.fetch_add(1, std::memory_order_relaxed);
-            return MMP_OK;
-        }
+    // 2. the route; a split route holds the stream's buffer from here until its tail is enqueued (miss_buffer)
+    const int grid = div_up(n, kPlaceBlock);
+    const int cap = rest_list_cap(grid * kPlaceWaves);  // the first launch's wavefronts share kRestLists lists
+    int32_t *words = nullptr, *report = nullptr;
+    std::unique_lock<std::mutex> pair;
+    rs.split_ok = !c->split_off.load(std::memory_order_relaxed);
+    PlaceRoute r = place_route(t, rs, n, o);
+    if (is_split(r) && (!miss_buffer(c, st, rest_buffer_ints(grid * kPlaceWaves), &words, &report, pair) ||
+                        c->split_off.load(std::memory_order_relaxed))) {
+        if (pair) pair.unlock();
+        rs.split_ok = false;
+        r = place_route(t, rs, n, o);
     }
-    // ... and on a full cluster: the recorded long walks alone in the first launch (place_kernel.hpp: place_long_memo_kernel)
-    if (A.long_first && c->snap.lmemo && !segs && !inline_req && !done_flag && !c->force_wave && !c->no_split &&
-        !c->split_off.load(std::memory_order_relaxed) && n >= (c->long_split_from >= 0 ? c->long_split_from : kLongSplitFrom)) {
-        const int grid = div_up(n, kPlaceBlock);
-        const int n_words = grid * kPlaceWaves;
-        const int cap = rest_list_cap(n_words);
-        int32_t *words = nullptr;
-        int32_t *report = nullptr;
-        std::unique_lock<std::mutex> pair;  // (as above)
-        // (the tail reads the tables from global memory: its requests are a handful)
-        const size_t lds_tail = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(c->snap.T));
-        if (lds_tail + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && miss_buffer(c, st, rest_buffer_ints(n_words), &words, &report, pair) &&
-            !c->split_off.load(std::memory_order_relaxed)) {
-            PlaceArgs At = A;
-            At.long_first = 1;
-            if (c->split_notail) words = nullptr;
-            if (caller) {
-                hipLaunchKernelGGL(place_long_memo_c_kernel, dim3(grid), dim3(kPlaceBlock), 0, st, c->snap, A, words, cap, *caller);
-                if (!c->split_notail)
-                    hipLaunchKernelGGL(place_long_tail_c_kernel, dim3(c->tail_blocks), dim3(kPlaceBlock), lds_tail, st, c->snap, At, wpad, words, cap, report, *caller);
-            } else {
-                hipLaunchKernelGGL(place_long_memo_kernel, dim3(grid), dim3(kPlaceBlock), 0, st, c->snap, A, words, cap);
-                if (!c->split_notail)
-                    hipLaunchKernelGGL(place_long_tail_kernel, dim3(c->tail_blocks), dim3(kPlaceBlock), lds_tail, st, c->snap, At, wpad, words, cap, report);
-            }
-            HIP_TRY(c, hipGetLastError());
-            c->n_split.fetch_add(1, std::memory_order_relaxed);
-            return MMP_OK;
-        }
+    if (t.split_notail) words = nullptr;  // (diagnostics: the undecided requests are not even recorded)
+    // 3. the launch
+    PlaceArgs At = A;  // the long tail's (it reads the tables from global memory)
+    At.long_first = 1;
+    const size_t lds_memo = (size_t)kPlaceWaves * memo_stage_bytes(S.T);  // a copy of the types' records per wavefront
+    const dim3 block(kPlaceBlock), tails(t.tail_blocks);
+    const bool tail = !t.split_notail;
+    const mmp_place_caller C = o.caller ? *o.caller : mmp_place_caller{};
+    switch (r) {
+    case PlaceRoute::memo_split:
+        hipLaunchKernelGGL(place_memo_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap);
+        if (tail) hipLaunchKernelGGL(place_tail_kernel, tails, block, lds, st, S, A, wpad, words, cap, report);
+        break;
+    case PlaceRoute::memo_split_c:
+        hipLaunchKernelGGL(place_memo_c_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap, C);
+        if (tail) hipLaunchKernelGGL(place_tail_c_kernel, tails, block, lds, st, S, A, wpad, words, cap, report, C);
+        break;
+    case PlaceRoute::long_split:
+        hipLaunchKernelGGL(place_long_memo_kernel, dim3(grid), block, 0, st, S, A, words, cap);
+        if (tail) hipLaunchKernelGGL(place_long_tail_kernel, tails, block, lds_base, st, S, At, wpad, words, cap, report);
+        break;
+    case PlaceRoute::long_split_c:
+        hipLaunchKernelGGL(place_long_memo_c_kernel, dim3(grid), block, 0, st, S, A, words, cap, C);
+        if (tail) hipLaunchKernelGGL(place_long_tail_c_kernel, tails, block, lds_base, st, S, At, wpad, words, cap, report, C);
+        break;
+    case PlaceRoute::multi: hipLaunchKernelGGL(place_multi_kernel, dim3(o.seg_blocks), block, lds, st, S, A, wpad, *o.segs); break;
+    case PlaceRoute::multi_m: hipLaunchKernelGGL(place_multi_m_kernel, dim3(o.seg_blocks), block, lds_nobar, st, S, A, wpad, *o.segs); break;
+    case PlaceRoute::multi_long: hipLaunchKernelGGL(place_multi_long_kernel, dim3(o.seg_blocks), block, lds, st, S, A, wpad, *o.segs); break;
+    case PlaceRoute::multi_long4: hipLaunchKernelGGL(place_multi_long4_kernel, dim3(o.seg_blocks), block, lds, st, S, A, wpad, *o.segs); break;
+    case PlaceRoute::miss_single:
+        hipLaunchKernelGGL(miss_single_kernel, dim3(1), dim3(128), lds, st, S, A, wpad, *o.inline_req, *o.fused_gate, *o.fused_greq);
+        break;
+    case PlaceRoute::single_lean: hipLaunchKernelGGL(place_single_lean_kernel, dim3(1), dim3(64), lds, st, S, A, wpad, *o.inline_req); break;
+    case PlaceRoute::flag: hipLaunchKernelGGL(place_batch_flag_kernel, dim3(grid), block, lds, st, S, A, wpad, o.done_blocks); break;
+    case PlaceRoute::batch: hipLaunchKernelGGL(place_batch_kernel, dim3(grid), block, lds, st, S, A, wpad); break;
+    case PlaceRoute::batch_m: hipLaunchKernelGGL(place_batch_m_kernel, dim3(grid), block, lds_nobar, st, S, A, wpad); break;
+    case PlaceRoute::batch_c: hipLaunchKernelGGL(place_batch_c_kernel, dim3(grid), block, lds, st, S, A, wpad, C); break;
+    case PlaceRoute::batch_c_m: hipLaunchKernelGGL(place_batch_c_m_kernel, dim3(grid), block, lds_nobar, st, S, A, wpad, C); break;
+    case PlaceRoute::batch_long: hipLaunchKernelGGL(place_batch_long_kernel, dim3(grid), block, lds_nobar, st, S, A, wpad); break;
+    case PlaceRoute::batch_long4: hipLaunchKernelGGL(place_batch_long4_kernel, dim3(grid), block, lds, st, S, A, wpad); break;
+    case PlaceRoute::batch_long_c: hipLaunchKernelGGL(place_batch_long_c_kernel, dim3(grid), block, lds_nobar, st, S, A, wpad, C); break;
+    case PlaceRoute::batch_long4_c: hipLaunchKernelGGL(place_batch_long4_c_kernel, dim3(grid), block, lds, st, S, A, wpad, C); break;
     }
-    if (segs) {  // several request arrays, one launch (multi_kernel.hpp); n = the decisions of all of them
-        if (c->snap_long && n >= c->long_dense_from)
-            hipLaunchKernelGGL(place_multi_long4_kernel, dim3(seg_blocks), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *segs);
-        else if (c->snap_long)
-            hipLaunchKernelGGL(place_multi_long_kernel, dim3(seg_blocks), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *segs);
-        else if (use_memo)
-            hipLaunchKernelGGL(place_multi_m_kernel, dim3(seg_blocks), dim3(kPlaceBlock), lds_nobar, st, c->snap, A, wpad, *segs);
-        else
-            hipLaunchKernelGGL(place_multi_kernel, dim3(seg_blocks), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *segs);
-    } else if (inline_req && fused_gate)  // one cache-miss route: the guards beside the load target (multi_kernel.hpp)
-        hipLaunchKernelGGL(miss_single_kernel, dim3(1), dim3(128), lds, st, c->snap, A, wpad, *inline_req, *fused_gate, *fused_greq);
-    else if (inline_req && !c->single_block)
-        hipLaunchKernelGGL(place_single_lean_kernel, dim3(1), dim3(64), lds, st, c->snap, A, wpad, *inline_req);
-    else if (inline_req)
-        hipLaunchKernelGGL(place_single_kernel, dim3(1), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *inline_req);
-    else if (done_flag && n > kPlaceBlock)
-        hipLaunchKernelGGL(place_batch_flag_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds, st, c->snap, A, wpad,
-                           done_blocks);
-    else if (caller && c->snap_long && n >= dense_from)
-        hipLaunchKernelGGL(place_batch_long4_c_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *caller);
-    else if (caller && c->snap_long)
-        hipLaunchKernelGGL(place_batch_long_c_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds_nobar, st, c->snap, A, wpad, *caller);
-    else if (use_memo && !caller)
-        hipLaunchKernelGGL(place_batch_m_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds_nobar, st, c->snap, A, wpad);
-    else if (use_memo)
-        hipLaunchKernelGGL(place_batch_c_m_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds_nobar, st, c->snap, A, wpad, *caller);
-    else if (caller)
-        hipLaunchKernelGGL(place_batch_c_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds, st, c->snap, A, wpad, *caller);
-    else if (c->snap_long && n >= dense_from)
-        hipLaunchKernelGGL(place_batch_long4_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds, st, c->snap, A, wpad);
-    else if (c->snap_long)
-        hipLaunchKernelGGL(place_batch_long_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds_nobar, st, c->snap, A, wpad);
-    else
-        hipLaunchKernelGGL(place_batch_kernel, dim3(div_up(n, kPlaceBlock)), dim3(kPlaceBlock), lds, st, c->snap, A, wpad);
     HIP_TRY(c, hipGetLastError());
+    if (is_split(r)) c->n_split.fetch_add(1, std::memory_order_relaxed);
     return MMP_OK;
 }
 
@@ -845,30 +914,7 @@ int mmp_create(const mmp_config *cfg, mmp_ctx **out)
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device) == hipSuccess && v > 0) c->lds_limit = (size_t)v;
     }
-    if (const char *fw = getenv("MMP_FORCE_WAVE")) c->force_wave = fw[0] == '1';
-    if (const char *nh = getenv("MMP_NO_HEADS")) c->no_heads = nh[0] == '1';
-    if (const char *nm = getenv("MMP_NO_MEMO")) c->no_memo = nm[0] == '1';
-    if (const char *nm = getenv("MMP_NO_LONG_MEMO")) c->no_long_memo = nm[0] == '1';
-    if (const char *lf = getenv("MMP_LONG_SPLIT_FROM")) c->long_split_from = atoi(lf);
-    if (const char *mf = getenv("MMP_MEMO_FROM")) c->memo_from = atoi(mf);
-    if (const char *ns = getenv("MMP_NO_SPLIT")) c->no_split = ns[0] == '1';
-    if (const char *sf = getenv("MMP_SPLIT_FROM")) c->split_from = atoi(sf);
-    if (const char *tb = getenv("MMP_TAIL_BLOCKS")) c->tail_blocks = std::max(1, std::min(atoi(tb), kRestLists));
-    if (const char *nt = getenv("MMP_SPLIT_NOTAIL")) c->split_notail = nt[0] == '1';
-    if (const char *ml = getenv("MMP_MEMO_LDS_MIN")) c->memo_lds_min = std::max(0, std::min(atoi(ml), 60 * 1024));
-    if (const char *nl = getenv("MMP_NO_LONG_LDS")) c->no_long_lds = nl[0] == '1';
-    if (const char *nb = getenv("MMP_NO_CASEB")) c->no_caseb = nb[0] == '1';
-    const bool want_resident = getenv("MMP_RESIDENT") && getenv("MMP_RESIDENT")[0] == '1';
-    if (const char *rm = getenv("MMP_RANK_MODE")) c->rank_mode = atoi(rm);
-    if (const char *lm = getenv("MMP_LONG_MODE")) c->long_mode = atoi(lm);
-    if (const char *ld = getenv("MMP_LONG_DENSE_FROM")) {
-        c->long_dense_from = atoi(ld);
-        c->long_dense_env = true;
-    }
-    if (const char *nd = getenv("MMP_NO_DELTA")) c->no_delta = nd[0] == '1';
-    if (const char *sb = getenv("MMP_SINGLE_BLOCK")) c->single_block = sb[0] == '1';
-    if (const char *sp = getenv("MMP_PLAN_SORTED")) c->cfg_plan_sorted = atoi(sp);
-    if (const char *pf = getenv("MMP_PLAN_FUSED")) c->cfg_plan_fused = atoi(pf);
+    c->tune = read_tuning();  // per context: tests change the environment between contexts
     {
         // the one-launch plan waits at grid-wide barriers: every workgroup has to be on the chip (one per compute unit at most);
         // it keeps the bucket offsets in 64 KB of dynamic LDS beside its 23 KB of static
@@ -908,7 +954,7 @@ int mmp_create(const mmp_config *cfg, mmp_ctx **out)
     }
     (void)hipStreamSynchronize(c->stream);
     *out = c;
-    if (want_resident && mmp_resident(c, 1) != MMP_OK) {
+    if (c->tune.resident && mmp_resident(c, 1) != MMP_OK) {
         *out = nullptr;
         mmp_destroy(c);
         return fail(nullptr, MMP_EHIP, "the resident decision kernel could not be set up");
@@ -1759,7 +1805,7 @@ try {
     DeltaRows dl{};
     std::vector<int32_t> new_order;
     bool delta = false;
-    if (c->committed && !c->dirty_all && !c->no_delta && sort_legal && c->order_total && P >= 2 && P == c->snap.P) {
+    if (c->committed && !c->dirty_all && !c->tune.no_delta && sort_legal && c->order_total && P >= 2 && P == c->snap.P) {
         std::vector<int32_t> chg(c->dirty);
         std::sort(chg.begin(), chg.end());
         chg.erase(std::unique(chg.begin(), chg.end()), chg.end());
@@ -1903,12 +1949,12 @@ try {
     S.memo_cand = B.memo_cand.as<int32_t>();
     S.memo_rk = B.memo_rk.as<int16_t>();
     S.lmemo = nullptr;
-    if (P > 0 && have_sel && !c->no_long_memo) {  // the recorded walks of the long shortlists (place_kernel.hpp: LongMemo)
+    if (P > 0 && have_sel && !c->tune.no_long_memo) {  // the recorded walks of the long shortlists (place_kernel.hpp: LongMemo)
         HIP_TRY(c, B.lmemo.ensure((size_t)T * kLongLevels * sizeof(LongMemo)));
         S.lmemo = B.lmemo.as<LongMemo>();
     }
 
-    bool next_long = c->long_mode == 1, next_full = false;
+    bool next_long = c->tune.long_mode == 1, next_full = false;
     {  // the partitions of the type constraints (host) and their uploads: inputs, like the table itself
         const int rc = build_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, min_space, st, 0);
         if (rc != MMP_OK) return rc;
@@ -1916,17 +1962,17 @@ try {
     KT_BEGIN(c, st);
     if (P > 0) {
         // (nearly) every instance full: getNext is in its LRU-window mode and whole-table shortlists are common
-        next_long = c->long_mode == 1 || (c->long_mode != 0 && n_present > 0 && n_nonfull * 16 <= n_present);
+        next_long = c->tune.long_mode == 1 || (c->tune.long_mode != 0 && n_present > 0 && n_nonfull * 16 <= n_present);
         next_full = n_present > 0 && n_nonfull * 16 <= n_present;
         // all-pairs is embarrassingly parallel and wins below ~8k pods (measured: 10k pods 172 us all-pairs vs 120 us
         // sort; 50k pods 4.3 ms vs 0.25 ms); a merge sort of a few thousand 64-byte keys is latency bound
-        const bool want_sort = c->rank_mode == 2 || c->rank_mode == 3 || (c->rank_mode == 0 && P >= kRankSortMinPods);
+        const bool want_sort = c->tune.rank_mode == 2 || c->tune.rank_mode == 3 || (c->tune.rank_mode == 0 && P >= kRankSortMinPods);
         if (delta) {
             const SnapBufs &A = c->sb[c->cur];
             hipLaunchKernelGGL(delta_scatter_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, A.pods.as<mmp_pod_row>(), A.pos_of.as<int32_t>(),
                                P, dl, B.pods.as<mmp_pod_row>(), c->rank.as<int32_t>(), B.lru.as<int64_t>(), B.rem.as<int64_t>(),
                                B.cnt.as<int32_t>(), B.rpm.as<int32_t>(), B.orig.as<int32_t>(), B.pos_of.as<int32_t>());
-        } else if (want_sort && P >= kSampleMinPods && sort_legal && c->rank_mode != 3) {
+        } else if (want_sort && P >= kSampleMinPods && sort_legal && c->tune.rank_mode != 3) {
             const int rc = rank_by_sampling(c, B.pods.as<mmp_pod_row>(), P, min_space, churn2, 0, P, c->rank.as<int32_t>(), st);
             if (rc != MMP_OK) return rc;
         } else if (want_sort && P >= 2 && sort_legal) {
@@ -2053,7 +2099,7 @@ try {
 
     // a type only a few instances may host: its first candidate is usually beyond a lane scan's reach, and only the
     // long variant carries the prefix-table jump that finds it without the wave path
-    if (c->long_mode < 0 && acc.sparse_types) next_long = true;
+    if (c->tune.long_mode < 0 && acc.sparse_types) next_long = true;
     // publish: the only part of a commit a decision can ever wait for
     std::lock_guard<std::shared_mutex> g(c->mu);
     resident_stop(c);  // it answers for the snapshot it was launched with; the next single request starts one on the new
@@ -2621,8 +2667,8 @@ try {
                 if (rem < min_space && r.lru_time <= churn2) full_low_lru = true;
             }
             const bool sort_legal = !(versions_differ && full_low_lru) && !wide_count;
-            const bool want_sort = c->rank_mode == 2 || c->rank_mode == 3 || (c->rank_mode == 0 && (int64_t)(p_hi - p_lo) * P >= (int64_t)kRankSortMinPods * kRankSortMinPods);
-            if (want_sort && sort_legal && P >= kSampleMinPods && c->rank_mode != 3) {
+            const bool want_sort = c->tune.rank_mode == 2 || c->tune.rank_mode == 3 || (c->tune.rank_mode == 0 && (int64_t)(p_hi - p_lo) * P >= (int64_t)kRankSortMinPods * kRankSortMinPods);
+            if (want_sort && sort_legal && P >= kSampleMinPods && c->tune.rank_mode != 3) {
                 const int rc = rank_by_sampling(c, B.pods.as<mmp_pod_row>(), P, min_space, churn2, p_lo, p_hi, static_cast<int32_t *>(d_rank), st);
                 if (rc != MMP_OK) return rc;
             } else if (want_sort && sort_legal && P >= 2) {
@@ -2856,22 +2902,8 @@ int shard_phase_launch(mmp_ctx *c, int32_t phase, const void *d_reqs, int32_t n,
                        int64_t now, void *const *d_xchg, void *d_outs, hipStream_t st)
 {
     HIP_TRY(c, order_after_registry(c, st));
-    PlaceArgs A{};
-    A.reqs = static_cast<const mmp_place_req *>(d_reqs);
-    A.models = c->models.as<mmp_model_row>();
-    A.rmodels = nullptr;
-    A.wins = nullptr;
-    A.ent_pod = c->ent_pod.as<int32_t>();
-    A.extra = static_cast<const int32_t *>(d_extra);
-    A.outs = static_cast<mmp_place_out *>(d_outs);
-    A.n = n;
-    A.n_models = c->n_models;
-    A.now = now;
+    PlaceArgs A = place_args(c, d_reqs, n, d_extra, now, d_outs, false, c->ssnap.P);
     A.n_dev = n_dev;
-    A.force_wave = 0;
-    A.n_pods_all = c->ssnap.P;
-    A.done_flag = nullptr;
-    A.done_seq = 0;
     XchgPtrs X{static_cast<int64_t *>(d_xchg[0]), static_cast<int64_t *>(d_xchg[1]), static_cast<int64_t *>(d_xchg[2]),
                static_cast<int64_t *>(d_xchg[3]), static_cast<int64_t *>(d_xchg[4]), static_cast<int64_t *>(d_xchg[5])};
     const ShardSnap &S = c->ssnap;
@@ -2919,22 +2951,8 @@ int32_t mmp_shard_fast_slots(void) { return kXF; }
 namespace {
 PlaceArgs shard_args(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int64_t now, void *d_outs)
 {
-    PlaceArgs A{};
-    A.reqs = static_cast<const mmp_place_req *>(d_reqs);
-    A.models = c->models.as<mmp_model_row>();
-    A.rmodels = cur_side(c).rmodels_ok ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr;
-    A.wins = (c->no_heads || c->sview.P <= 0) ? nullptr : c->sb[c->cur].heads.as<TypeWin>();
-    A.ent_pod = c->ent_pod.as<int32_t>();
-    A.extra = static_cast<const int32_t *>(d_extra);
-    A.outs = static_cast<mmp_place_out *>(d_outs);
-    A.n = n;
-    A.n_models = c->n_models;
-    A.now = now;
-    A.n_dev = nullptr;
-    A.force_wave = 0;
-    A.n_pods_all = c->ssnap.P;
-    A.done_flag = nullptr;
-    A.done_seq = 0;
+    PlaceArgs A = place_args(c, d_reqs, n, d_extra, now, d_outs, true, c->ssnap.P);
+    A.wins = c->sview.P <= 0 ? nullptr : c->sb[c->cur].heads.as<TypeWin>();
     return A;
 }
 }  // namespace
@@ -3628,34 +3646,23 @@ int resident_ensure(mmp_ctx *c)
     if (c->n_shards > 0) return kResidentFallback;
     std::lock_guard<std::mutex> g(R.launch_mu);
     if (R.running && __atomic_load_n(&R.ctl->exited, __ATOMIC_ACQUIRE) != R.generation) return MMP_OK;
-    static const bool dbg = getenv("MMP_RESIDENT_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[resident] ensure: running %d exited %u -> (re)launch #%llu\n", (int)R.running.load(), R.ctl->exited,
-                     (unsigned long long)R.launches.load() + 1);
     if (R.running) {
         HIP_TRY(c, hipStreamSynchronize(R.stream));  // it left by itself (idle): returns at once
         R.running = false;
-        if (dbg) fprintf(stderr, "[resident] previous kernel retired\n");
     }
     {
         uint32_t g2 = R.generation.load(std::memory_order_relaxed) + 1;
         if (g2 == 0) g2 = 1;
         R.generation.store(g2, std::memory_order_release);
     }
-    PlaceArgs A{};
-    A.models = c->models.as<mmp_model_row>();
-    A.rmodels = cur_side(c).rmodels_ok ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr;
-    A.wins = c->no_heads ? nullptr : c->sb[c->cur].heads.as<TypeWin>();
-    A.ent_pod = c->ent_pod.as<int32_t>();
-    A.n = 1;
-    A.n_models = c->n_models;
-    A.n_pods_all = c->snap.P;
+    PlaceArgs A = place_args(c, nullptr, 1, nullptr, 0, nullptr, true, c->snap.P);
+    A.wins = c->sb[c->cur].heads.as<TypeWin>();
     HIP_TRY(c, order_after_registry(c, R.stream));
     hipLaunchKernelGGL(place_resident_kernel, dim3(1), dim3(64), (size_t)kPlaceLaneLds, R.stream, c->snap, A, R.slots, R.answers, R.ctl,
                        R.idle_ticks, R.generation.load(std::memory_order_relaxed));
     HIP_TRY(c, hipGetLastError());
     R.running = true;
     R.launches.fetch_add(1, std::memory_order_relaxed);
-    if (dbg) fprintf(stderr, "[resident] launched\n");
     return MMP_OK;
 }
 
@@ -3728,9 +3735,6 @@ int resident_place(mmp_ctx *c, const mmp_place_req &rq, int64_t now, mmp_place_o
         }
         if ((spins & 255) == 255) {
             if (__atomic_load_n(&R.ctl->exited, __ATOMIC_ACQUIRE) == R.generation) {  // it left (idle, or stopped for a commit) before it saw the bell
-                if (getenv("MMP_RESIDENT_DEBUG"))
-                    fprintf(stderr, "[resident] slot %d waits for seq %u: done %#x bell seq %u, spins %u\n", si, seq, Ans->done,
-                            (unsigned)(S->bell >> kResidentNowBits), spins);
                 const int rc = resident_ensure(c);
                 if (rc != MMP_OK) return rc;
                 restarted = true;
@@ -3833,7 +3837,10 @@ try {
         i0 = i;
         if (G.n_segs == 0) continue;
         if (total > INT32_MAX - kPlaceBlock * (int64_t)kMaxSegs) return fail(c, MMP_EINVAL, "mmp_place_multi_dev: more than 2^31 decisions in one launch");
-        const int rc = place_launch(c, G.seg[0].reqs, (int32_t)total, G.seg[0].extra, now, G.seg[0].outs, st, nullptr, 0, nullptr, nullptr, &G, blocks);
+        PlaceCall o;
+        o.segs = &G;
+        o.seg_blocks = blocks;
+        const int rc = place_launch(c, G.seg[0].reqs, (int32_t)total, G.seg[0].extra, now, G.seg[0].outs, st, o);
         if (rc != MMP_OK) return rc;
     }
     return MMP_OK;
@@ -3934,10 +3941,9 @@ try {
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
     note_caller_stream(c, static_cast<hipStream_t>(stream));
-    PlaceOpts o;
+    PlaceCall o;
     o.extra_bound = n_extra_pool + 1;
-    return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                        nullptr, &o);
+    return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), o);
 } catch (const std::bad_alloc &) {
     return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_dev2");
 } catch (const std::exception &e) {
@@ -3954,11 +3960,10 @@ try {
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
     note_caller_stream(c, static_cast<hipStream_t>(stream));
-    PlaceOpts o;
+    PlaceCall o;
     o.caller = caller;
     o.extra_bound = n_extra_pool + 1;
-    return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                        nullptr, &o);
+    return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), o);
 } catch (const std::bad_alloc &) {
     return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_c_dev");
 } catch (const std::exception &e) {
@@ -4008,11 +4013,10 @@ try {
         std::lock_guard<std::shared_mutex> g(c->mu);
         if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
         if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-        PlaceOpts o;
+        PlaceCall o;
         o.caller = caller;
         KT_BEGIN(c, st);
-        const int rc = place_launch(c, c->s_reqs.p, n, c->s_extra.p, now, c->s_outs.p, st, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                                    nullptr, &o);
+        const int rc = place_launch(c, c->s_reqs.p, n, c->s_extra.p, now, c->s_outs.p, st, o);
         if (rc != MMP_OK) return rc;
         KT_END(c, st);
     }
@@ -4050,38 +4054,20 @@ try {
     if (n <= kFastN && n_extra <= kFastExtra) {
         // latency path: the kernel reads the requests from, and writes the results to, pinned host
         // memory over the fabric — no staging copies, no contention with batches on c->stream
-        static const bool trace = getenv("MMP_TRACE_SLOT") != nullptr;  // where a single decision's wall time goes (stderr)
-        const auto t0 = std::chrono::steady_clock::now();
         std::unique_lock<std::mutex> fl;
         FastSlot *f = slot_acquire(c, fl);
         memcpy(f->reqs, reqs, (size_t)n * sizeof(mmp_place_req));
         if (n_extra) memcpy(f->extra, extra_pool, (size_t)n_extra * sizeof(int32_t));
-        const auto t1 = std::chrono::steady_clock::now();
         {
             std::shared_lock<std::shared_mutex> g(c->mu);
             if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
             if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-            const int rc = place_launch(c, f->reqs, n, f->extra, now, f->outs, f->stream, f->done, ++f->seq,
-                                        (n == 1 && reqs[0].n_extra == 0) ? &reqs[0] : nullptr, f->blocks);
+            const int rc = place_launch(c, f->reqs, n, f->extra, now, f->outs, f->stream,
+                                        slot_call(f, (n == 1 && reqs[0].n_extra == 0) ? &reqs[0] : nullptr));
             if (rc != MMP_OK) return rc;
         }
-        const auto t2 = std::chrono::steady_clock::now();
         HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
         memcpy(outs, f->outs, (size_t)n * sizeof(mmp_place_out));
-        if (trace) {
-            static thread_local double acc[3] = {0, 0, 0};
-            static thread_local int cnt = 0;
-            const auto t3 = std::chrono::steady_clock::now();
-            acc[0] += std::chrono::duration<double, std::micro>(t1 - t0).count();
-            acc[1] += std::chrono::duration<double, std::micro>(t2 - t1).count();
-            acc[2] += std::chrono::duration<double, std::micro>(t3 - t2).count();
-            if (++cnt == 2000) {
-                fprintf(stderr, "[slot path] per call: slot + copy %.2f us, lock + launch %.2f us, wait for the flag %.2f us\n", acc[0] / cnt,
-                        acc[1] / cnt, acc[2] / cnt);
-                acc[0] = acc[1] = acc[2] = 0;
-                cnt = 0;
-            }
-        }
         return MMP_OK;
     }
 
@@ -4377,15 +4363,17 @@ try {
         G.done = DoneFlag{nullptr, nullptr, 0};
         const bool one = n == 1 && preqs[0].n_extra == 0;
         if (one) {  // ONE launch: both requests in the kernel arguments, guards and load target on two wavefronts
-            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream, f->done, ++f->seq, &preqs[0], f->blocks, nullptr, 0, &G,
-                                        &greqs[0]);
+            PlaceCall o = slot_call(f, &preqs[0]);
+            o.fused_gate = &G;
+            o.fused_greq = &greqs[0];
+            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream, o);
             if (rc != MMP_OK) return rc;
         } else {
             HIP_TRY(c, order_after_registry(c, f->stream));
             hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, f->stream, G);
             HIP_TRY(c, hipGetLastError());
-            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream, f->done, ++f->seq,
-                                        (n == 1 && preqs[0].n_extra == 0) ? &preqs[0] : nullptr, f->blocks);
+            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream,
+                                        slot_call(f, (n == 1 && preqs[0].n_extra == 0) ? &preqs[0] : nullptr));
             if (rc != MMP_OK) return rc;
         }
     }
@@ -4607,7 +4595,7 @@ try {
     // The one-launch form prefetches registry / instance rows unconditionally and waits at grid-wide barriers: it needs a registry
     // and a table to read (an empty or never-loaded one takes the eight launches, which guard every access: ADVICE r5), and every
     // workgroup on the chip at once — plan_grid_max is what the occupancy query granted at mmp_create; a launch never asks for more
-    const bool fused_ok = c->cfg_plan_fused && c->plan_grid_max > 0 && M > 0 && P > 0 && models != nullptr && pods != nullptr;
+    const bool fused_ok = c->tune.plan_fused && c->plan_grid_max > 0 && M > 0 && P > 0 && models != nullptr && pods != nullptr;
     if (fused_ok) {
         // ONE launch, the steps separated by grid-wide barriers (rebalance_kernels.hpp: proactive_plan_fused_kernel)
         const int G = std::max(std::min(div_up(std::max(M, 1), kPlanFusedBlock), (int)c->plan_grid_max), 1);
@@ -4636,8 +4624,8 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     // (overflow == 2: the one-launch plan gave up at a grid barrier — its workgroups were not all on the chip; the general path below)
-    if (h.overflow && c->cfg_plan_sorted == 2) return fail(c, MMP_ESTATE, "mmp_proactive_plan: a key bucket overflowed and MMP_PLAN_SORTED=2 forbids the sorted path");
-    if (!h.overflow && c->cfg_plan_sorted != 1) {
+    if (h.overflow && c->tune.plan_sorted == 2) return fail(c, MMP_ESTATE, "mmp_proactive_plan: a key bucket overflowed and MMP_PLAN_SORTED=2 forbids the sorted path");
+    if (!h.overflow && c->tune.plan_sorted != 1) {
         const int32_t n_copy = std::min(h.n_selected, max_out);
         if (n_copy > 0) {
             HIP_TRY(c, copy_sync(c, out_model, c->r_out_model.p, (size_t)n_copy * 4, hipMemcpyDeviceToHost));

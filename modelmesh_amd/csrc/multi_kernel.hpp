@@ -67,8 +67,8 @@ __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(4, 
 }
 
 // ---- one decision, one wavefront ------------------------------------------------------------------------------------------------
-// mmp_place_batch(n = 1) through a launch is launch latency + this kernel + the completion flag's way to the host.  place_single_kernel
-// is the batch kernel's workgroup (256 lanes, three workgroup barriers, a system-scope fence by every wavefront before the flag) run
+// mmp_place_batch(n = 1) through a launch is launch latency + this kernel + the completion flag's way to the host.  The batch kernel's
+// workgroup (256 lanes, three workgroup barriers, a system-scope fence by every wavefront before the flag) run
 // for ONE lane's work: 5.6-6.9 us in the kernel trace.  The same decision code on one wavefront: the request comes in the kernel
 // arguments, the windows are staged by the one wavefront, lane 0 decides (lane_decide_win -> lane_decide_r -> the prefix-table
 // phase), the wave path runs on the same wavefront if it is needed, ONE fence, the flag.

@@ -260,7 +260,7 @@ struct PlaceArgs {
     const mmp_model_row *models;
     const ResolvedModel *rmodels;  // null: not built (pod-axis shard contexts)
     const int32_t *mtw;            // rmodels[i].type as an array of its own (the shortlist kernel's gather: 4 bytes per model instead of a 32-byte row)
-    const TypeWin *wins;           // null: not built (pod-axis shard contexts, MMP_NO_HEADS=1)
+    const TypeWin *wins;           // null: not built (pod-axis shard contexts)
     const struct BSlot *bslots;    // case (b) slots of the snapshot (long kernel only; see BSlot), n_bslots of them,
     const struct BLaunch *bwin;    // ... their whole-window tables (build_bsurv_kernel)
     const uint64_t *bsurv;
@@ -586,7 +586,7 @@ __device__ __forceinline__ void build_bslots_kernel_body(int bid, int nblk, Snap
     const int t = bid, lane = lane_id();
     if (!S.has_pref[t]) return;
     const int P = S.P, W = S.W;
-    const uint64_t *E = S.elig + (size_t)t * W, *Pm = S.pref + (size_t)t * W;
+    const uint64_t *E = S.elig + (size_t)t * W;
     const int best0 = first_set_from(E, nullptr, 0, W);
     if (best0 == kNoPos) return;
     if (!test_bit(S.fullw, best0)) return;  // case (b) needs a full first instance (whether a request's first one is preferred is the request's)
@@ -2098,14 +2098,8 @@ __device__ __forceinline__ int lane_decide_win(const Snap &S, const PlaceArgs &A
     return kLaneDone;
 }
 
-// (MMP_PLACE_ONE_NOINLINE: experiment builds, tools/r6 — the general path as a function of its own)
-#ifdef MMP_PLACE_ONE_NOINLINE
-#define MMP_PLACE_ONE_ATTR __attribute__((noinline))
-#else
-#define MMP_PLACE_ONE_ATTR __forceinline__
-#endif
 template <int FORM = kReq64>
-__device__ MMP_PLACE_ONE_ATTR void place_one(const Snap &S, const PlaceArgs &A, int d, uint64_t *ew, uint64_t *fw,
+__device__ __forceinline__ void place_one(const Snap &S, const PlaceArgs &A, int d, uint64_t *ew, uint64_t *fw,
                                           const mmp_place_caller &C = mmp_place_caller{})
 {
     const int lane = lane_id();
@@ -2403,7 +2397,7 @@ __host__ __device__ constexpr int place_wave_lds(int wpad)
 {
     return (((kWinWords * 64 * 8 > 2 * wpad * 8 ? kWinWords * 64 * 8 : 2 * wpad * 8) + 15) / 16) * 16;
 }
-constexpr int kPlaceStaticLds = 2 * kPlaceBlock * 4 + 64 + 256;                // the lists (+ place_single_kernel's request)
+constexpr int kPlaceStaticLds = 2 * kPlaceBlock * 4 + 64 + 256;                // the lists + headroom (its size decides which tables fit: keep it)
 // bytes of the long path's per-type tables when they are staged in LDS: elig + pref ([T][W] words each), pc + nz ([2][T][W + 1] ints each)
 __host__ __device__ constexpr size_t long_tables_bytes(int T, int W) { return (size_t)T * W * 16 + (size_t)4 * T * (W + 1) * 4; }
 // A request against its type's recorded shortlists (see TypeMemo), a lane per request, the tables read from (L1-resident) global
@@ -2411,11 +2405,11 @@ __host__ __device__ constexpr size_t long_tables_bytes(int T, int W) { return (s
 // exclusions than the check sees, no recorded list for the type) — the ordinary path decides.
 // `rows`: the snapshot's records — S.memo, or the wavefront's copy of it in LDS.
 // The result row of a request the check decides, as a NON-TEMPORAL 16-byte store: nobody on the device reads the rows again, and 12.8 MB
-// of them per 800k batch otherwise take lines of L2 from the tables every request gathers from.  Measured (tools/r6/exp30.sh, one visit,
+// of them per 800k batch otherwise take lines of L2 from the tables every request gathers from.  Measured (round 6, one visit,
 // alternating builds): the first launch alone 19.06 -> 18.36 us per 800k rows, a split call on four streams 13.12 -> 12.2 us (61 -> 65.5 G
 // decisions/s).  The same for the request LOADS is a loss (21.8 / 17.4 us): they are read once, but in 64-byte pieces a lane.  The lane
 // phase of place_block stores its rows the same way (800k rows through place_batch_kernel 25.6 -> 24.6 us, the full cluster 41.8 -> 40.8 us,
-// 100k launches unchanged: tools/r6/exp31.sh).
+// 100k launches unchanged; round 6).
 __device__ __forceinline__ void store_out_streaming(mmp_place_out *p, const mmp_place_out &o)
 {
     typedef int v4i_ __attribute__((ext_vector_type(4)));
@@ -2488,9 +2482,6 @@ __device__ __forceinline__ bool memo_try(const Snap &S, const PlaceArgs &A, cons
     int ks = 0;              // the caller's candidate number when its own entry is a candidate (self_in)
     bool self_in = false, self_best = false;
     int32_t e_rpm = 0;
-#ifdef MMP_XP_NOOWN  // (experiment builds only, tools/r6: what the own-positions block costs)
-    miss |= x_in || sp_in || moff != 0;
-#endif
     const bool own = !miss && (x_in || sp_in || moff != 0);
     if (__ballot(own)) {  // (wave-uniform: a third of the wavefronts of a batch of request rows, C3)
         if (own) {
@@ -2623,9 +2614,6 @@ __device__ __forceinline__ bool memo_try(const Snap &S, const PlaceArgs &A, cons
     }
     o.chosen = MMP_NONE;
     if (remaining >= 1) {
-#ifdef MMP_XP_NOCAND  // (experiment builds only: the last gather of the chain left out — wrong results)
-        o.chosen = best_idx + k;
-#else
         o.chosen = Mp->cand64[k < kMemoNear ? k : 0];
         if (k >= kMemoNear) {  // (see rk_of)
             int32_t g = S.memo_cand[type * kMemoCand + k];
@@ -2633,7 +2621,6 @@ __device__ __forceinline__ bool memo_try(const Snap &S, const PlaceArgs &A, cons
             o.chosen = g;
         }
         if (k == 0) o.chosen = best_idx;
-#endif
         if (self_in && k == ks) o.chosen = MMP_SELF;  // :4989-4991
     }
     o.n_candidates = ccount;
@@ -3339,18 +3326,7 @@ __device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &
         }
     }
     bool todo = false;
-#ifdef MMP_XP_STREAM  // (experiment builds only: the batch streamed in and out, nothing decided — the floor of a kernel of this form)
-    if (live) {
-        mmp_place_out o;
-        o.chosen = rq.model ^ rq.self_pod;
-        o.best = (int32_t)(rq.pick ^ rq.flags) + rq.n_extra + rq.extra_off;
-        o.n_candidates = (int32_t)(rq.last_used ^ rq.fresh_lru);
-        o.hash = (uint32_t)(rq.fresh_capacity ^ rq.fresh_used) + (uint32_t)rq.fresh_count + (uint32_t)rq.fresh_rpm;
-        A.outs[d] = o;
-    }
-#else
     if (live) todo = !memo_try<FORM>(S, A, rq, d, reinterpret_cast<const TypeMemo *>(mine));
-#endif
     rest_append(rest, cap, d, todo);
 }
 __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void place_memo_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap)
@@ -3512,19 +3488,6 @@ __global__ __launch_bounds__(kPlaceBlock) void place_batch_flag_kernel(Snap S, P
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     place_block<true>(S, A, wpad, smem, done_blocks);
-}
-
-// One decision whose request rides in the kernel arguments (the latency path's n = 1 call without extra
-// exclusions): the kernel does not have to fetch the request from pinned host memory over the fabric.
-__global__ __launch_bounds__(kPlaceBlock) void place_single_kernel(Snap S, PlaceArgs A, int32_t wpad, mmp_place_req rq)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ mmp_place_req srq;
-    if (threadIdx.x == 0) srq = rq;
-    __syncthreads();
-    A.reqs = &srq;
-    A.n = 1;
-    place_block<true>(S, A, wpad, smem);
 }
 
 

@@ -2,7 +2,7 @@
 """place_batch_kernel launch time on C3 (or argv[1]): K launches back to back on ONE stream between a HIP event pair,
 (a) the same request batch every launch (inputs served from L2 / Infinity Cache) and (b) rotating through 48 distinct
 batches (384 MB: inputs from HBM); then the same on 16 streams (step time).  One line per measurement.
-Environment switches of the library apply (MMP_NO_HEADS=1: without the per-type head records)."""
+Environment switches of the library apply."""
 import ctypes as C
 import os
 import sys
@@ -30,7 +30,6 @@ for b in range(R):
                  torch.zeros(len(rq) * 16, dtype=torch.uint8, device=dev)))
 n = len(rq)
 fn = s.lib.mmp_place_batch_dev
-tag = "no-heads" if os.environ.get("MMP_NO_HEADS") == "1" else "heads"
 
 
 def args_of(b, st):
@@ -70,13 +69,13 @@ def many_streams(ns, rotate, steps):
 
 for rot in (False, True):
     us = one_stream(rot)
-    print(f"{name} {tag} 1 stream, {'rotating %d batches' % R if rot else 'same batch':>19}: {us:7.2f} us per launch of {n} decisions "
+    print(f"{name} 1 stream, {'rotating %d batches' % R if rot else 'same batch':>19}: {us:7.2f} us per launch of {n} decisions "
           f"({n / us / 1e3:6.2f} G/s)", flush=True)
 for ns in (4, 16):
     for rot in (False, True):
         for steps in (20, 1000):
             us = many_streams(ns, rot, steps)
-            print(f"{name} {tag} {ns:2d} streams, {'rotating' if rot else 'one batch per stream':>20}, {steps:4d} steps: {us:7.2f} us per step "
+            print(f"{name} {ns:2d} streams, {'rotating' if rot else 'one batch per stream':>20}, {steps:4d} steps: {us:7.2f} us per step "
                   f"({n / us / 1e3:6.2f} G/s)", flush=True)
 pass
 
@@ -123,7 +122,7 @@ if os.environ.get("KT_GRAPH", "1") == "1":
         for steps in (20, 200, 1000):
             try:
                 best, med = graph_steps(ns, steps)
-                print(f"{name} {tag} hipGraph, {ns} branches, {steps:4d} steps: best {best:7.2f} median {med:7.2f} us per step "
+                print(f"{name} hipGraph, {ns} branches, {steps:4d} steps: best {best:7.2f} median {med:7.2f} us per step "
                       f"({n / med / 1e3:6.2f} G/s)", flush=True)
             except Exception as e:  # noqa: BLE001
-                print(f"{name} {tag} hipGraph, {ns} branches, {steps} steps: failed: {type(e).__name__}: {e}", flush=True)
+                print(f"{name} hipGraph, {ns} branches, {steps} steps: failed: {type(e).__name__}: {e}", flush=True)

@@ -83,7 +83,7 @@ __global__ void echo_slots(Slot *slots, Ans *ans, volatile uint32_t *stop, long 
 }
 
 // E: what makes a launch-per-request round trip slow?  The same echo with a ~400-byte by-value argument block (the size of
-// place_single_kernel's Snap + PlaceArgs + request) and with 38 KB of dynamic LDS.
+// a single-decision kernel's Snap + PlaceArgs + request) and with 38 KB of dynamic LDS.
 struct BigArgs { uint64_t w[50]; };
 __global__ void echo_once_big(BigArgs a, uint32_t b, volatile uint32_t *answer, const int32_t *tab)
 {
