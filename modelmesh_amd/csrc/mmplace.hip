@@ -151,7 +151,6 @@ struct Tuning {
     int32_t no_long_memo = 0;    // MMP_NO_LONG_MEMO=1: commit records no walks of the long shortlists (place_kernel.hpp: LongMemo)
     int32_t no_split = 0;        // MMP_NO_SPLIT=1: batches are never split (place_memo_kernel + place_tail_kernel); the one-launch kernels instead
     int32_t split_from = -1;     // MMP_SPLIT_FROM=n: decisions from which a batch is split (default kSplitFrom / kSplitFromC)
-    int32_t long_split_from = -1;  // MMP_LONG_SPLIT_FROM=n: requests from which a full-cluster batch is split (default kLongSplitFrom)
     int32_t tail_blocks = kTailBlocks;  // MMP_TAIL_BLOCKS=n: workgroups of a split batch's tail launch (1 .. kRestLists)
     int32_t split_notail = 0;    // MMP_SPLIT_NOTAIL=1: the tail launch is left out — the batch's results are INCOMPLETE (bench.py times the first launch alone)
     int32_t no_long_lds = 0;     // MMP_NO_LONG_LDS=1: the long path reads its per-type tables from global memory (tests, comparison)
@@ -615,7 +614,7 @@ Tuning read_tuning()
     const auto num = [](const char *name, int32_t &v) { if (const char *e = getenv(name)) v = atoi(e); };
     flag("MMP_FORCE_WAVE", t.force_wave);
     flag("MMP_NO_MEMO", t.no_memo), num("MMP_MEMO_FROM", t.memo_from), flag("MMP_NO_LONG_MEMO", t.no_long_memo);
-    flag("MMP_NO_SPLIT", t.no_split), num("MMP_SPLIT_FROM", t.split_from), num("MMP_LONG_SPLIT_FROM", t.long_split_from);
+    flag("MMP_NO_SPLIT", t.no_split), num("MMP_SPLIT_FROM", t.split_from);
     num("MMP_TAIL_BLOCKS", t.tail_blocks);
     t.tail_blocks = std::max(1, std::min(t.tail_blocks, kRestLists));
     flag("MMP_SPLIT_NOTAIL", t.split_notail), flag("MMP_NO_LONG_LDS", t.no_long_lds), flag("MMP_NO_CASEB", t.no_caseb);
@@ -675,12 +674,11 @@ PlaceCall slot_call(FastSlot *f, const mmp_place_req *inline_req)
 // The kernel (or, for a split batch, the pair of kernels) a place launch takes.
 enum class PlaceRoute {
     memo_split, memo_split_c,  // place_memo_kernel + place_tail_kernel (_c: the single-caller form)
-    long_split, long_split_c,  // place_long_memo_kernel + place_long_tail_kernel
     multi, multi_m, multi_long, multi_long4,
     miss_single, single_lean, flag,
     batch, batch_m, batch_c, batch_c_m, batch_long, batch_long4, batch_long_c, batch_long4_c,
 };
-bool is_split(PlaceRoute r) { return r <= PlaceRoute::long_split_c; }  // (the split routes come first)
+bool is_split(PlaceRoute r) { return r == PlaceRoute::memo_split || r == PlaceRoute::memo_split_c; }
 
 // What the route depends on besides the tuning, the call and its size: plain values, captured under the state lock.
 struct RouteState {
@@ -688,7 +686,7 @@ struct RouteState {
     bool memo = false, lmemo = false;           // the snapshot has TypeMemo / LongMemo records
     bool wins = false, rmodels = false;         // PlaceArgs::wins / rmodels are set
     bool split_ok = false;                      // a split buffer is to be had for the stream and split_off is not set
-    bool memo_tail_lds = false, long_tail_lds = false;  // the tail of a memo / long split fits the device's LDS
+    bool memo_tail_lds = false;                 // the tail of a memo split fits the device's LDS
 };
 
 // the long kernel on a full cluster: the case (b) tables and the first lane phase on the prefix tables (PlaceArgs::long_first)
@@ -715,10 +713,6 @@ PlaceRoute place_route(const Tuning &t, const RouteState &s, int32_t n, const Pl
     const bool split = !o.segs && !t.no_split && s.split_ok;
     if (use_memo && split && s.memo_tail_lds && n >= (t.split_from >= 0 ? t.split_from : (caller ? kSplitFromC : kSplitFrom)))
         return caller ? PlaceRoute::memo_split_c : PlaceRoute::memo_split;
-    // ... and on a full cluster: the recorded long walks alone in the first launch (place_kernel.hpp: place_long_memo_kernel)
-    if (long_first(s) && s.lmemo && split && !latency && !t.force_wave && s.long_tail_lds &&
-        n >= (t.long_split_from >= 0 ? t.long_split_from : kLongSplitFrom))
-        return caller ? PlaceRoute::long_split_c : PlaceRoute::long_split;
     if (o.segs) {
         // (the multi path compares with MMP_LONG_DENSE_FROM's value as it is, the batch path with dense_from())
         if (s.snap_long) return n >= t.long_dense_from ? PlaceRoute::multi_long4 : PlaceRoute::multi_long;
@@ -751,8 +745,7 @@ int grant_place_lds(mmp_ctx *c)
         {kfn(place_batch_long_c_kernel), want}, {kfn(place_batch_long4_c_kernel), want}, {kfn(place_batch_flag_kernel), want},
         {kfn(place_single_lean_kernel), want}, {kfn(miss_single_kernel), want}, {kfn(place_multi_kernel), want},
         {kfn(place_multi_m_kernel), want}, {kfn(place_multi_long_kernel), want}, {kfn(place_multi_long4_kernel), want},
-        {kfn(place_tail_kernel), tail}, {kfn(place_tail_c_kernel), tail}, {kfn(place_long_tail_kernel), tail},
-        {kfn(place_long_tail_c_kernel), tail},
+        {kfn(place_tail_kernel), tail}, {kfn(place_tail_c_kernel), tail},
     };
     for (const auto &k : kernels) HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.max_lds));
     c->lds_granted.store((size_t)want, std::memory_order_release);
@@ -781,8 +774,7 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     const bool latency = o.inline_req || o.done_flag;
     const int wpad = (S.W + 1) & ~1;
     // one dynamic region: the lane phase's windows + scratch, re-used by the wave path's tiles (place_block)
-    const size_t lds_base = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(S.T));
-    size_t lds = lds_base;
+    size_t lds = std::max<size_t>((size_t)kPlaceWaves * 2 * wpad * sizeof(uint64_t), (size_t)place_lane_lds(S.T));
     A.long_first = long_first(rs) ? 1 : 0;
     // the long path's per-type tables in LDS when they are small (C3: 20 KB) and the launch fills the chip: measured on the full
     // cluster, 800k decisions per launch 70.8 -> 67.1 us; at 100k (1.5 wavefronts per SIMD) 20.4 -> 21.0 us, hence the size condition
@@ -812,10 +804,7 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
         if (const int rc = grant_place_lds(c)) return rc;
     // NOBAR kernels: a region per wavefront (place_wave_lds) instead of the shared one
     const size_t lds_nobar = (size_t)kPlaceWaves * place_wave_lds(wpad);
-    // (the memo split checks its tail against `lds`, the long split against lds_base: the long tail reads the tables from global
-    // memory, its requests are a handful)
     rs.memo_tail_lds = lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit;
-    rs.long_tail_lds = lds_base + kPlaceStaticLds + kTailStaticLds <= c->lds_limit;
     HIP_TRY(c, order_after_registry(c, st));
     // 2. the route; a split route holds the stream's buffer from here until its tail is enqueued (miss_buffer)
     const int grid = div_up(n, kPlaceBlock);
@@ -832,8 +821,6 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     }
     if (t.split_notail) words = nullptr;  // (diagnostics: the undecided requests are not even recorded)
     // 3. the launch
-    PlaceArgs At = A;  // the long tail's (it reads the tables from global memory)
-    At.long_first = 1;
     const size_t lds_memo = (size_t)kPlaceWaves * memo_stage_bytes(S.T);  // a copy of the types' records per wavefront
     const dim3 block(kPlaceBlock), tails(t.tail_blocks);
     const bool tail = !t.split_notail;
@@ -846,14 +833,6 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     case PlaceRoute::memo_split_c:
         hipLaunchKernelGGL(place_memo_c_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap, C);
         if (tail) hipLaunchKernelGGL(place_tail_c_kernel, tails, block, lds, st, S, A, wpad, words, cap, report, C);
-        break;
-    case PlaceRoute::long_split:
-        hipLaunchKernelGGL(place_long_memo_kernel, dim3(grid), block, 0, st, S, A, words, cap);
-        if (tail) hipLaunchKernelGGL(place_long_tail_kernel, tails, block, lds_base, st, S, At, wpad, words, cap, report);
-        break;
-    case PlaceRoute::long_split_c:
-        hipLaunchKernelGGL(place_long_memo_c_kernel, dim3(grid), block, 0, st, S, A, words, cap, C);
-        if (tail) hipLaunchKernelGGL(place_long_tail_c_kernel, tails, block, lds_base, st, S, At, wpad, words, cap, report, C);
         break;
     case PlaceRoute::multi: hipLaunchKernelGGL(place_multi_kernel, dim3(o.seg_blocks), block, lds, st, S, A, wpad, *o.segs); break;
     case PlaceRoute::multi_m: hipLaunchKernelGGL(place_multi_m_kernel, dim3(o.seg_blocks), block, lds_nobar, st, S, A, wpad, *o.segs); break;

@@ -3091,6 +3091,9 @@ __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP
 // the same with the long-shortlist phase (see place_block): 144 VGPRs, 3 wavefronts per SIMD
 // (launches below kLongDenseFrom decisions: the per-type tables are never staged in LDS for them, so the workgroup needs no barrier —
 // place_block<..., NOBAR>: no window staging either, which the full-cluster path does not read)
+// (Measured and not kept, round 6: a full-cluster batch split like the memo split — the recorded walks alone, the rest in a tail —
+// is slower per call, for the tail is the walk: 800k, 47.9 against 40.5 us on one stream, 30.2 against 30.1 on four;
+// profiles/r6/long_records.txt.)
 __global__ __launch_bounds__(kPlaceBlock) void place_batch_long_kernel(Snap S, PlaceArgs A, int32_t wpad)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -3343,7 +3346,7 @@ __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 
 
 // `report` (may be null): workgroup 0 leaves {undecided requests, n} there (pinned host memory: the host reads the pair some launches
 // later, never waits for it)
-template <int FORM, bool WITH_LONG = false>
+template <int FORM>
 __device__ __forceinline__ void place_tail_body(const Snap &S, const PlaceArgs &A, int32_t wpad, unsigned char *smem, int32_t *__restrict__ rest, int32_t cap,
                                                 int32_t *report, const mmp_place_caller &C)
 {
@@ -3381,7 +3384,7 @@ __device__ __forceinline__ void place_tail_body(const Snap &S, const PlaceArgs &
             d = rest[kRestLists * kRestCntStride + (size_t)(g + k * G) * cap + (i - t_cnt[k])];
         }
         PHASE(14);  // (tail) this pass's entries read
-        place_block<WITH_LONG, FORM, false, false, true>(S, A, wpad, smem, nullptr, C, d);
+        place_block<false, FORM, false, false, true>(S, A, wpad, smem, nullptr, C, d);
     }
     if (tid < mine) rest[(g + tid * G) * kRestCntStride] = 0;  // for the stream's next batch (ordered behind this launch)
 }
@@ -3401,69 +3404,6 @@ __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     place_tail_body<kReqC>(S, A, wpad, smem, rest, cap, report, C);
 }
-
-// ---- the split form on a full cluster (round 6): the recorded long walks in a launch of their own ------------------------------------
-// place_batch_long_kernel carries the record check (long_memo_try) AND the walk it replaces: 139 VGPRs, three wavefronts per SIMD, for
-// requests of which one in a hundred thousand needs the walk.  From kLongSplitFrom requests on the check runs alone — request ->
-// {registry row with the model's positions, caller position, late exclusions} -> record -> rk / amul lookups -> sel -> orig — and leaves
-// what it cannot answer in the stream's lists for place_long_tail_kernel (place_block<WITH_LONG, ..., LIST>: the walk, case (b), the
-// general path), exactly as place_memo_kernel / place_tail_kernel do for the head windows.
-template <int FORM>
-__device__ __forceinline__ void place_long_memo_body(const Snap &S, const PlaceArgs &A, int32_t *__restrict__ rest, int32_t cap, const mmp_place_caller &C)
-{
-    const int d = blockIdx.x * kPlaceBlock + threadIdx.x;
-    bool live = d < A.n;
-    mmp_place_req rq{};
-    if (live) rq = fetch_req<FORM>(A, C, d);
-    if (A.extra_bound != 0) {  // (wave-uniform) bounded calls: as place_block answers them
-        if (live && bad_extra_range(A, rq)) {
-            live = false;
-            mmp_place_out bo;
-            bo.chosen = MMP_NONE;
-            bo.best = MMP_BAD_REQUEST;
-            bo.n_candidates = 0;
-            bo.hash = 0;
-            A.outs[d] = bo;
-        }
-    }
-    bool todo = false;
-    if (live) {
-        ResolvedReq r = resolve_req<false, true>(S, A, rq);
-        merge_late_extras(r);
-        mmp_place_out o;
-        if (long_memo_try(S, A, r, o))
-            A.outs[d] = o;
-        else
-            todo = true;
-    }
-    rest_append(rest, cap, d, todo);
-}
-#ifndef MMP_LONG_MEMO_EU
-#define MMP_LONG_MEMO_EU 6
-#endif
-__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP_LONG_MEMO_EU, MMP_LONG_MEMO_EU))) void place_long_memo_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap)
-{
-    place_long_memo_body<kReq64>(S, A, rest, cap, mmp_place_caller{});
-}
-__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP_LONG_MEMO_EU, MMP_LONG_MEMO_EU))) void place_long_memo_c_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap,
-                                                                                                                          mmp_place_caller C)
-{
-    place_long_memo_body<kReqC>(S, A, rest, cap, C);
-}
-__global__ __launch_bounds__(kPlaceBlock) void place_long_tail_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t *report)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_tail_body<kReq64, true>(S, A, wpad, smem, rest, cap, report, mmp_place_caller{});
-}
-__global__ __launch_bounds__(kPlaceBlock) void place_long_tail_c_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t *report, mmp_place_caller C)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_tail_body<kReqC, true>(S, A, wpad, smem, rest, cap, report, C);
-}
-// Requests from which a full-cluster batch is split: NEVER by default.  Measured (tools/r6/long_split_sweep.sh, profiles/r6/long_records.txt,
-// C3 full cluster, 800k requests): the first launch alone 33.1 us against 40.3 us for the one-launch kernel, but its tail — the walk,
-// 194 VGPRs — is 14.8 us: 47.9 us per call on one stream, 30.2 us on four (one launch: 30.1).  MMP_LONG_SPLIT_FROM=n switches it on.
-constexpr int kLongSplitFrom = INT32_MAX;
 
 __global__ __launch_bounds__(kPlaceBlock) void place_batch_long_c_kernel(Snap S, PlaceArgs A, int32_t wpad, mmp_place_caller C)
 {

@@ -87,7 +87,7 @@ def test_requests_with_hostile_fields_are_decided_or_refused(ctx, data):
 ROUTES = {  # how a batch of the bounded device-pointer calls is decided: the environment of mmp_create
     "default": {},  # (600 rows: the one-launch kernels)
     "split": {"MMP_MEMO_FROM": "0", "MMP_SPLIT_FROM": "0"},  # place_memo_kernel / place_memo_c_kernel + their tails
-    "long split": {"MMP_LONG_SPLIT_FROM": "0"},  # a full cluster: place_long_memo_kernel / place_long_memo_c_kernel + their tails
+    "full cluster": {},  # place_batch_long_kernel / place_batch_long_c_kernel (600 rows: the barrier-free instantiation)
 }
 
 
@@ -110,12 +110,12 @@ def route_ctx(request, ctx):
 def test_exclusion_ranges_that_leave_the_pool_are_refused(route_ctx, off, cnt):
     """Host-pointer calls validate every request's range against the pool's length (int64 arithmetic: off + cnt must not wrap);
     bounded device-pointer calls answer such a request {MMP_NONE, MMP_BAD_REQUEST, 0, 0} and decide the others — by every route a
-    batch can take: in the split ones the first launch answers it (place_memo_body, place_long_memo_body), in a wavefront whose other
-    rows it leaves to the tail (their exclusions name the first instances of the placement order, where the records are)."""
+    batch can take: in the split one the first launch answers it (place_memo_body), in a wavefront whose other rows it leaves to the
+    tail (their exclusions name the first instances of the placement order, where the records are)."""
     import torch
     route, (s, fleet, orc) = route_ctx
-    split = route != "default"
-    # (split routes: no exclusions of the generator's own, so that the pool stays shorter than the ranges above that must leave it)
+    split = route == "split"
+    # (the split route: no exclusions of the generator's own, so that the pool stays shorter than the ranges above that must leave it)
     reqs, extra = wl.make_requests(fleet, 5, n=4096 if split else 600, extra_frac=0.0 if split else 0.05)
     extra = np.concatenate([extra, np.zeros(8, np.int32)])
     if split:  # every fourth row of the bad row's wavefront excludes the head of the order: the first launch leaves those
@@ -126,7 +126,7 @@ def test_exclusion_ranges_that_leave_the_pool_are_refused(route_ctx, off, cnt):
     out = np.zeros(len(bad), _lib.PLACE_OUT)
     rc = s.lib.mmp_place_batch(s.h, _lib.ptr(bad), len(bad), _lib.ptr(extra), len(extra), fleet.now, _lib.ptr(out))
     assert rc == EINVAL, rc
-    pod = 3 if not split else int(orc.order[-1])  # (split routes: a caller that does not steer every walk of the batch)
+    pod = 3 if not split else int(orc.order[-1])  # (the split route: a caller that does not steer every walk of the batch)
     caller, rc_rows = _lib.split_caller(_one_caller(fleet, bad, pod))
     cp = np.ascontiguousarray(caller, dtype=_lib.PLACE_CALLER).reshape(1)
     assert s.lib.mmp_place_batch_c(s.h, _lib.ptr(cp), _lib.ptr(rc_rows), len(rc_rows), _lib.ptr(extra), len(extra), fleet.now, _lib.ptr(out)) == EINVAL

@@ -83,19 +83,6 @@ def test_recorded_long_walks_next_to_requests_that_steer_the_walk(seed, monkeypa
             assert_same_decisions(fleet, reqs[i:i + 1], one, want[i:i + 1])
     finally:
         s.close()
-    # the same batch as two launches: the records alone, then the walk for what they leave (place_long_memo_kernel + place_long_tail_kernel)
-    monkeypatch.setenv("MMP_LONG_SPLIT_FROM", "0")
-    for tails in ("16", "3"):
-        monkeypatch.setenv("MMP_TAIL_BLOCKS", tails)
-        s = Solver(fleet.min_space_units, fleet.min_churn_age_ms)
-        try:
-            s.load_fleet(fleet)
-            for _ in range(2):  # (the second call finds the stream's lists as the first one's tail left them)
-                assert_same_decisions(fleet, reqs, s.place(reqs, extra, fleet.now), want)
-            assert s.split_batches()[0] == 2 or s.split_batches()[1]
-        finally:
-            s.close()
-    monkeypatch.delenv("MMP_TAIL_BLOCKS")
     monkeypatch.setenv("MMP_NO_LONG_MEMO", "1")
     s = Solver(fleet.min_space_units, fleet.min_churn_age_ms)
     try:
@@ -106,10 +93,11 @@ def test_recorded_long_walks_next_to_requests_that_steer_the_walk(seed, monkeypa
         s.close()
 
 
-@pytest.mark.parametrize("n,split", [(100_000, False), (250_000, False), (250_000, True)])
-def test_full_cluster_c3_batches_on_both_long_kernels(n, split, monkeypatch):
+@pytest.mark.parametrize("n", [100_000, 250_000], ids=["100000-False", "250000-False"])
+def test_full_cluster_c3_batches_on_both_long_kernels(n):
     """C3 with every instance full: a batch below and one above the size from which the 4-wavefront instantiation with its tables in
-    LDS takes over (kLongDenseFrom), hostile rows mixed in; the records must exist for every type of the workload."""
+    LDS takes over (kLongDenseFrom), hostile rows mixed in; the records must exist for every type of the workload, and a full
+    cluster's batch is never split."""
     fleet = wl.make_full_cluster(wl.make_fleet("C3"))
     rng = np.random.default_rng(77)
     parts, ex_parts, off = [], [], 0
@@ -121,8 +109,6 @@ def test_full_cluster_c3_batches_on_both_long_kernels(n, split, monkeypatch):
         parts.append(rq)
         ex_parts.append(ex)
     reqs, extra = np.concatenate(parts)[:n], np.concatenate(ex_parts)
-    if split:
-        monkeypatch.setenv("MMP_LONG_SPLIT_FROM", "0")
     s = Solver(fleet.min_space_units, fleet.min_churn_age_ms)
     try:
         s.load_fleet(fleet)
@@ -131,7 +117,7 @@ def test_full_cluster_c3_batches_on_both_long_kernels(n, split, monkeypatch):
         assert rows["valid"][0::2].sum() >= max(fleet.n_types, 1) - 1, rows  # (a preferring type in case (b) has no record)
         reqs, extra = _hostile(fleet, s.order(), reqs, extra, rng)
         got = s.place(reqs, extra, fleet.now)
-        assert (s.split_batches()[0] > 0) == split
+        assert s.split_batches()[0] == 0
     finally:
         s.close()
     want = OracleFleet(fleet).place(reqs, extra, fleet.now, threads=16)

@@ -1,17 +1,17 @@
 """GPU: split batches (include/mmplace.h: mmp_split_batches) from several host threads, on many streams, and with work in flight.
 
-A split batch is two launches on the call's stream: the first (place_memo_kernel / place_long_memo_kernel) appends the indices it
-leaves undecided to lists in a buffer the context keeps per stream, the second (place_tail_kernel / place_long_tail_kernel) decides
-them and zeroes the lists for the stream's next batch.  The pair must follow each other on the stream: between two threads that share
-one, a tail would decide the other batch's indices with its own requests, and the other tail would find its lists empty — rows never
-written.  The cases here put threads on one stream (every entry point, the NULL stream, the full-cluster pair, submission threads next
-to direct calls), pass hipStreamPerThread (refused: it is another stream in every thread), use more streams over a context's life than
-it keeps buffers for (mmp_stream_retire returns them), and grow a stream's buffer while earlier pairs are still queued.  Every result
+A split batch is two launches on the call's stream: the first (place_memo_kernel) appends the indices it leaves undecided to lists
+in a buffer the context keeps per stream, the second (place_tail_kernel) decides them and zeroes the lists for the stream's next
+batch.  The pair must follow each other on the stream: between two threads that share one, a tail would decide the other batch's
+indices with its own requests, and the other tail would find its lists empty — rows never written.  The cases here put threads on
+one stream (every entry point, the NULL stream, submission threads next to direct calls, and a full cluster, whose batches are never
+split), pass hipStreamPerThread (refused: it is another stream in every thread), use more streams over a context's life than it
+keeps buffers for (mmp_stream_retire returns them), and grow a stream's buffer while earlier pairs are still queued.  Every result
 buffer starts as 0xFF bytes (a row nobody wrote cannot pass) and every row is compared with the oracle bit for bit.
 
-Every batch the threads share a stream with is one the records cover (fewer than 1/32 of its rows undecided, checked first): two or
-more batches' undecided indices then fit one batch's lists, and all batches of a case have the same length, so even a library that
-interleaves the pairs only loses rows, never reads or writes out of bounds."""
+Every split batch the threads share a stream with is one the records cover (fewer than 1/32 of its rows undecided, checked first):
+two or more batches' undecided indices then fit one batch's lists, and all batches of a case have the same length, so even a library
+that interleaves the pairs only loses rows, never reads or writes out of bounds."""
 import ctypes as C
 import threading
 
@@ -89,14 +89,13 @@ def _check(fleet, b, out, what):
     assert_same_decisions(fleet, b.reqs, got, b.want)
 
 
-@pytest.mark.parametrize("case", ["place_dev", "place_dev2", "place_c_dev", "null stream", "full cluster", "issue threads"])
+@pytest.mark.parametrize("case", ["place_dev", "place_dev2", "place_c_dev", "null stream", "full cluster unsplit", "issue threads"])
 def test_threads_sharing_one_stream_get_every_row(case, monkeypatch):
     """4 threads released together by a barrier each enqueue 24 split batches of 65 536 rows on ONE stream without synchronising
     (ctypes lets go of the GIL in the call: the launches interleave); every call writes a buffer of its own."""
     torch, dev = _torch()
-    full = case == "full cluster"
-    if full:
-        monkeypatch.setenv("MMP_LONG_SPLIT_FROM", "0")
+    full = case == "full cluster unsplit"
+    if full:  # the default route: place_batch_long_kernel
         fleet = wl.make_full_cluster(wl.make_fleet("C3"))
     else:
         monkeypatch.setenv("MMP_MEMO_FROM", "0")
@@ -117,13 +116,6 @@ def test_threads_sharing_one_stream_get_every_row(case, monkeypatch):
             sets.append(Batch(fleet, orc, reqs, extra, one_caller=case == "place_c_dev"))
         how = {"place_dev": "place_dev", "place_c_dev": "place_c_dev"}.get(case, "place_dev2")
         stream = 0 if case == "null stream" else torch.cuda.Stream(dev).cuda_stream
-        if full:  # the records must cover every batch: each alone, then once more so that the last tail's report is read
-            for b in sets + sets[:1]:
-                o = _outs(b.n)
-                b.launch(s, how, o, stream, fleet.now)
-                torch.cuda.synchronize()
-                _check(fleet, b, o, "alone")
-            assert s.split_batches() == (THREADS + 1, False), s.split_batches()
         n0 = s.split_batches()[0]
         outs = [[_outs(N) for _ in range(CALLS)] for _ in range(THREADS)]
         torch.cuda.synchronize()
@@ -156,7 +148,10 @@ def test_threads_sharing_one_stream_get_every_row(case, monkeypatch):
             for j in range(CALLS):
                 _check(fleet, sets[k], outs[k][j], (case, k, j))
         n_split, off = s.split_batches()
-        assert n_split - n0 == THREADS * CALLS and not off, (n_split - n0, off)
+        if full:
+            assert n_split == 0, n_split
+        else:
+            assert n_split - n0 == THREADS * CALLS and not off, (n_split - n0, off)
     finally:
         if case == "issue threads":
             s.lib.mmp_issue_threads(s.h, 0)
