@@ -94,6 +94,30 @@ struct SnapBufs {
     }
 };
 
+// What Snap and ShardSnap share: the sizes, and B's rank-ordered columns and bitmaps (a template: in front of the extern "C" part).
+template <class SnapT>
+SnapT snap_columns(const SnapBufs &B, int32_t P, int32_t W, int32_t T, bool any_rs, int64_t min_space)
+{
+    SnapT S{};
+    S.P = P;
+    S.W = W;
+    S.T = T;
+    S.any_rs = any_rs;
+    S.min_space = min_space;
+    S.lru = B.lru.as<int64_t>();
+    S.rem = B.rem.as<int64_t>();
+    S.cnt = B.cnt.as<int32_t>();
+    S.rpm = B.rpm.as<int32_t>();
+    S.orig = B.orig.as<int32_t>();
+    S.pos_of = B.pos_of.as<int32_t>();
+    S.elig = B.elig.as<uint64_t>();
+    S.elig_nors = B.elig_nors.as<uint64_t>();
+    S.pref = B.pref.as<uint64_t>();
+    S.has_pref = B.has_pref.as<uint8_t>();
+    S.fullw = B.fullw.as<uint64_t>();
+    return S;
+}
+
 // What decisions read besides the Snap columns, one set per committed snapshot (double-buffered with SnapBufs, so
 // that a commit builds the next set while decisions keep reading the published one): the type table's allowed
 // rows, the cluster / partition / type-set stats (device + host mirrors), the instance partitions, and the
@@ -375,6 +399,11 @@ int fail(mmp_ctx *c, int code, const char *fmt, ...)
             return fail((c), MMP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                         __FILE__, __LINE__);                                                   \
     } while (0)
+
+// The end of every entry point's function-try-block: no C++ exception crosses the C boundary.
+#define MMP_CATCH(c, name)                                                                  \
+    catch (const std::bad_alloc &) { return fail((c), MMP_ENOMEM, "%s: out of host memory", name); } \
+    catch (const std::exception &e_) { return fail((c), MMP_EHIP, "%s: %s", name, e_.what()); }
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
@@ -1023,11 +1052,7 @@ try {
     c->prof = enable != 0;
     c->last_kernel_ms = -1.0;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_backend");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_backend", e.what());
-}
+} MMP_CATCH(c, "mmp_backend")
 
 double mmp_last_kernel_ms(mmp_ctx *c) { return c ? c->last_kernel_ms : -1.0; }
 
@@ -1036,11 +1061,7 @@ try {
     if (!c) return MMP_EINVAL;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_sync");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_sync", e.what());
-}
+} MMP_CATCH(c, "mmp_sync")
 
 /* ---- staging of the instance table -------------------------------------- */
 
@@ -1066,11 +1087,7 @@ try {
     c->pods.assign(rows, rows + n);
     c->dirty_all = true;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pods_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pods_load", e.what());
-}
+} MMP_CATCH(c, "mmp_pods_load")
 
 int mmp_pods_upsert(mmp_ctx *c, const int32_t *idx, const mmp_pod_row *rows, int32_t n)
 try {
@@ -1095,11 +1112,7 @@ try {
         }
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pods_upsert");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pods_upsert", e.what());
-}
+} MMP_CATCH(c, "mmp_pods_upsert")
 
 int mmp_pods_remove(mmp_ctx *c, const int32_t *idx, int32_t n)
 try {
@@ -1115,11 +1128,7 @@ try {
         note_dirty(c, k);
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pods_remove");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pods_remove", e.what());
-}
+} MMP_CATCH(c, "mmp_pods_remove")
 
 int mmp_types_load(mmp_ctx *c, int32_t n_types, const uint64_t *allowed, const uint64_t *prefer,
                    const uint8_t *has_allowed, const uint8_t *has_prefer)
@@ -1150,11 +1159,7 @@ try {
         }
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_types_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_types_load", e.what());
-}
+} MMP_CATCH(c, "mmp_types_load")
 
 int mmp_types_from_labels(mmp_ctx *c, int32_t n_types, const uint64_t *required, const uint64_t *preferred,
                           const uint64_t *pod_labels, uint64_t *allowed_out, uint64_t *prefer_out,
@@ -1216,11 +1221,7 @@ try {
     if (has_allowed_out) memcpy(has_allowed_out, c->has_allowed.data(), R);
     if (has_prefer_out) memcpy(has_prefer_out, c->has_prefer.data(), R);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_types_from_labels");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_types_from_labels", e.what());
-}
+} MMP_CATCH(c, "mmp_types_from_labels")
 
 int mmp_replaced_rs_load(mmp_ctx *c, const int32_t *rs, int32_t n)
 try {
@@ -1229,11 +1230,7 @@ try {
     std::lock_guard<std::shared_mutex> g(c->mu);
     c->replaced_rs.assign(rs, rs + n);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_replaced_rs_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_replaced_rs_load", e.what());
-}
+} MMP_CATCH(c, "mmp_replaced_rs_load")
 
 static void publish_upgrades(mmp_ctx *c)
 {
@@ -1249,11 +1246,7 @@ try {
     c->upgrades.instance_added(labels_key, rs, start_time, now);
     publish_upgrades(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_upgrade_instance_added");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_upgrade_instance_added", e.what());
-}
+} MMP_CATCH(c, "mmp_upgrade_instance_added")
 
 int mmp_upgrade_instance_removed(mmp_ctx *c, int64_t labels_key, int32_t rs, int64_t now)
 try {
@@ -1263,11 +1256,7 @@ try {
     c->upgrades.instance_removed(labels_key, rs, now);
     publish_upgrades(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_upgrade_instance_removed");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_upgrade_instance_removed", e.what());
-}
+} MMP_CATCH(c, "mmp_upgrade_instance_removed")
 
 int mmp_upgrade_housekeeping(mmp_ctx *c, int64_t now)
 try {
@@ -1277,11 +1266,7 @@ try {
     c->upgrades.housekeeping(now);
     publish_upgrades(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_upgrade_housekeeping");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_upgrade_housekeeping", e.what());
-}
+} MMP_CATCH(c, "mmp_upgrade_housekeeping")
 
 int mmp_upgrade_replaced(mmp_ctx *c, int32_t *rs_out, int64_t *expiry_out, int32_t max, int32_t *n_out)
 try {
@@ -1297,11 +1282,7 @@ try {
     }
     *n_out = i;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_upgrade_replaced");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_upgrade_replaced", e.what());
-}
+} MMP_CATCH(c, "mmp_upgrade_replaced")
 
 int mmp_models_load(mmp_ctx *c, const mmp_model_row *rows, int32_t n_models, const int32_t *ent_pod,
                     const int64_t *ent_time, int32_t n_entries)
@@ -1337,11 +1318,7 @@ try {
     }
     split_reset(c);
     return rebuild_resolved(c);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_models_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_models_load", e.what());
-}
+} MMP_CATCH(c, "mmp_models_load")
 
 namespace {
 // grow a device buffer, keeping its first `used` bytes
@@ -1555,19 +1532,11 @@ try {
     // more garbage than live entries (and enough to matter): squeeze the arena
     if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_models_upsert");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_models_upsert", e.what());
-}
+} MMP_CATCH(c, "mmp_models_upsert")
 
 /* ---- commit: rank + permute + bitmaps + stats, all on the device --------- */
 
 namespace {
-// Partition the present instances by their ProhibitedTypeSet and build the per-partition / per-type
-// ClusterStats of the snapshot being committed (snapshot.hpp "instance partitions").  Enqueues on st; the
-// host mirrors are valid once the caller has synchronised st.  Call after cluster_stats_kernel.  N = the side
-// state of the snapshot being built (its d_has_allowed / stats_acc are already filled).
 // Rank the table from scratch by sampling (rank_sample.hpp): ranks of the rows [p_lo, p_hi) into `rank` (the others untouched).
 // Only for a table on which the comparator is a strict total order (the caller's O(P) check).
 int rank_by_sampling(mmp_ctx *c, const mmp_pod_row *d_pods, int32_t P, int64_t min_space, int64_t churn2, int32_t p_lo, int32_t p_hi,
@@ -1613,78 +1582,511 @@ struct ZeroBatch {  // collects buffers, clears them with one zero_regions_kerne
         most = 0;
     }
 };
-// part 0: the host's interning of the partitions + the uploads; part 1: the kernels + the results back; 2: the results only; -1: all
-int build_subset_stats(mmp_ctx *c, SnapSide &N, const mmp_pod_row *d_pods, int32_t P, int64_t min_space, hipStream_t st, int part = -1)
+
+/* The stages of a commit.  mmp_snapshot_commit and the pod-axis pair mmp_shard_rank_dev / mmp_shard_commit_dev are lists of these;
+   every stage enqueues on the stream it is given and none synchronises it, except where its comment says so. */
+
+inline int64_t churn2_of(const mmp_ctx *c) { return (int64_t)((uint64_t)c->cfg.min_churn_age_ms * 2u); }
+
+// The sizes of an unsharded commit, and which optional tables it builds.
+struct CommitDims {
+    int32_t P, W, T;  // rows, 64-position words (>= 1), bitmap rows (>= 1)
+    int32_t n_rs;     // replaced replica sets
+    size_t padded;    // W * 64
+    int64_t min_space, churn2;
+    // the long path's inverse tables (Snap::sel / ::rk): 512 bytes per type row and 64-position word, each, rebuilt at every commit —
+    // 320 KB on C3, but a table of 100 type rows x 100 000 instances would be 80 MB a piece: beyond kSelMaxBytes they are not built
+    // and a shortlist that spans the table takes the wave path (ADVICE r5)
+    size_t sel_bytes;
+    bool have_sel;
+    bool have_lmemo;    // the recorded walks of the long shortlists (place_kernel.hpp: LongMemo)
+    size_t wins_bytes;  // rounded up to the 1 KB chunks place_block stages (rows beyond T are never read as windows)
+};
+CommitDims commit_dims(const mmp_ctx *c)
+{
+    CommitDims D{};
+    D.P = (int32_t)c->pods.size();
+    D.W = std::max(div_up(D.P, 64), 1);
+    D.T = std::max(c->n_types, 1);
+    D.n_rs = (int32_t)c->replaced_rs.size();
+    D.padded = (size_t)D.W * 64;
+    D.min_space = c->cfg.min_space_units;
+    D.churn2 = churn2_of(c);
+    D.sel_bytes = (size_t)2 * D.T * D.W * 64 * 4;
+    D.have_sel = D.sel_bytes <= kSelMaxBytes;
+    D.have_lmemo = D.P > 0 && D.have_sel && !c->tune.no_long_memo;
+    D.wins_bytes = (((size_t)std::max(D.T, kWinLds) * sizeof(TypeWin) + 1023) / 1024) * 1024;
+    return D;
+}
+
+// The rank-ordered columns and bitmaps, Wc words a row (a pod-axis shard: its slice); pos_of spans the whole table's W words.
+int ensure_columns(mmp_ctx *c, SnapBufs &B, int32_t T, int32_t Wc, int32_t W)
+{
+    const size_t padded = (size_t)Wc * 64;
+    HIP_TRY(c, B.lru.ensure(padded * 8));
+    HIP_TRY(c, B.rem.ensure(padded * 8));
+    HIP_TRY(c, B.cnt.ensure(padded * 4));
+    HIP_TRY(c, B.rpm.ensure(padded * 4));
+    HIP_TRY(c, B.orig.ensure(padded * 4));
+    HIP_TRY(c, B.pos_of.ensure((size_t)W * 64 * 4));
+    HIP_TRY(c, B.elig.ensure((size_t)T * Wc * 8));
+    HIP_TRY(c, B.elig_nors.ensure((size_t)T * Wc * 8));
+    HIP_TRY(c, B.pref.ensure((size_t)T * Wc * 8));
+    HIP_TRY(c, B.has_pref.ensure(T));
+    HIP_TRY(c, B.fullw.ensure((size_t)Wc * 8));
+    HIP_TRY(c, B.ge.ensure((size_t)kGeRows * Wc * 8));
+    return MMP_OK;
+}
+// What a commit reads or scribbles on besides the table: the scatter's scratch, the staged type table, the replica-set list.
+int ensure_commit_scratch(mmp_ctx *c, SnapSide &N, int32_t T, int32_t W)
+{
+    HIP_TRY(c, c->occupancy.ensure((size_t)W * 64 * 4));
+    HIP_TRY(c, c->flag.ensure(sizeof(int32_t)));
+    HIP_TRY(c, N.stats_acc.ensure(sizeof(StatsAcc)));
+    HIP_TRY(c, c->rs_bad.ensure((size_t)W * 64));
+    HIP_TRY(c, c->rs_list.ensure(std::max<size_t>(c->replaced_rs.size(), 1) * 4));
+    HIP_TRY(c, N.d_allowed.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
+    HIP_TRY(c, c->d_prefer.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
+    HIP_TRY(c, N.d_has_allowed.ensure(T));
+    return MMP_OK;
+}
+// Everything an unsharded snapshot is made of.
+int ensure_snapshot_buffers(mmp_ctx *c, SnapBufs &B, SnapSide &N, const CommitDims &D)
+{
+    const int32_t T = D.T, W = D.W;
+    HIP_TRY(c, B.pods.ensure(std::max<size_t>(D.P, 1) * sizeof(mmp_pod_row)));
+    if (const int rc = ensure_columns(c, B, T, W, W)) return rc;
+    HIP_TRY(c, B.ctpos.ensure((size_t)(kGeRows + 1) * 4));
+    HIP_TRY(c, B.pc.ensure((size_t)2 * T * (W + 1) * 4));
+    HIP_TRY(c, B.nz.ensure((size_t)2 * T * (W + 1) * 4));
+    HIP_TRY(c, B.ph.ensure((size_t)2 * T * (W + 1) * 8));
+    if (D.have_sel) {
+        HIP_TRY(c, B.sel.ensure(D.sel_bytes));
+        HIP_TRY(c, B.rk.ensure(D.sel_bytes));
+    }
+    if (D.have_lmemo) HIP_TRY(c, B.lmemo.ensure((size_t)T * kLongLevels * sizeof(LongMemo)));
+    HIP_TRY(c, B.memo.ensure((size_t)kWinLds * sizeof(TypeMemo)));
+    HIP_TRY(c, B.memo_cand.ensure((size_t)kWinLds * kMemoCand * 4));
+    HIP_TRY(c, B.memo_rk.ensure((size_t)kWinLds * kMemoCand * 2));
+    HIP_TRY(c, B.heads.ensure(D.wins_bytes));
+    HIP_TRY(c, B.bslots.ensure(kBSlots * sizeof(BSlot) + 16));
+    HIP_TRY(c, B.bpm.ensure((size_t)kBSlots * W * 64 * 4));
+    HIP_TRY(c, B.bwin.ensure(kBSlots * sizeof(BLaunch)));
+    HIP_TRY(c, B.bsurv.ensure((size_t)kBSlots * kBClasses * W * 8));
+    HIP_TRY(c, B.bpcs.ensure((size_t)kBSlots * kBClasses * (W + 1) * 4));
+    HIP_TRY(c, c->rank.ensure(D.padded * 4));
+    return ensure_commit_scratch(c, N, T, W);
+}
+
+// The unsharded commit's scratch cleared, and the tails of its columns beyond P.
+void clear_commit_scratch(mmp_ctx *c, SnapBufs &B, const CommitDims &D, hipStream_t st)
+{
+    ZeroBatch zb(st);
+    zb.add(c->rank.p, D.padded * 4);
+    zb.add(c->occupancy.p, D.padded * 4);
+    zb.add(c->flag.p, sizeof(int32_t));
+    zb.add(B.bslots.p, kBSlots * sizeof(BSlot) + 16);
+    zb.launch(st);
+    hipLaunchKernelGGL(zero_tails_kernel, dim3(1), dim3(64), 0, st, B.lru.as<int64_t>(), B.rem.as<int64_t>(), B.cnt.as<int32_t>(),
+                       B.rpm.as<int32_t>(), B.orig.as<int32_t>(), B.pos_of.as<int32_t>(), D.P, (int32_t)D.padded);
+}
+
+// Is the literal comparator a strict total order on these rows?  (see snapshot.hpp "ranking by sorting")
+struct OrderCheck {
+    bool sort_legal;
+    int32_t n_present, n_nonfull;
+};
+OrderCheck check_placement_order(const std::vector<mmp_pod_row> &pods, int64_t min_space, int64_t churn2)
+{
+    bool versions_differ = false, full_low_lru = false, wide_count = false;
+    OrderCheck oc{};
+    for (const mmp_pod_row &r : pods) {
+        if (r.version != pods[0].version) versions_differ = true;
+        if (r.count > (1 << 30) || r.count < -(1 << 30)) wide_count = true;  // :4676 is an int subtraction
+        const uint64_t d = (uint64_t)r.capacity - (uint64_t)r.used;
+        const int64_t rem = (int64_t)d > 0 ? (int64_t)d : 0;
+        if (rem < min_space && r.lru_time <= churn2) full_low_lru = true;
+        if (!(r.flags & (MMP_POD_SHUTTING_DOWN | MMP_POD_TOMBSTONE))) {
+            oc.n_present++;
+            if (!(rem < min_space)) oc.n_nonfull++;
+        }
+    }
+    oc.sort_legal = !(versions_differ && full_low_lru) && !wide_count;
+    return oc;
+}
+
+// A few rows changed since the published snapshot, and both orders are total: re-rank by insertion (snapshot.hpp "a commit
+// whose table differs ... in a few rows"); the unpublished set is then rebuilt from the PUBLISHED one.  Sets `delta` when this
+// commit can go that way, and then fills `dl` and the host mirror of the new order.  The only stage that may wait for the
+// device: the first delta after a commit from scratch fetches the published order.
+int plan_delta(mmp_ctx *c, const CommitDims &D, bool sort_legal, DeltaRows &dl, std::vector<int32_t> &new_order, bool &delta)
+{
+    const int32_t P = D.P;
+    delta = false;
+    if (!(c->committed && !c->dirty_all && !c->tune.no_delta && sort_legal && c->order_total && P >= 2 && P == c->snap.P)) return MMP_OK;
+    std::vector<int32_t> chg(c->dirty);
+    std::sort(chg.begin(), chg.end());
+    chg.erase(std::unique(chg.begin(), chg.end()), chg.end());
+    if ((int32_t)chg.size() > kDeltaRows) return MMP_OK;
+    if (!c->h_order_valid) {  // the host's mirror of the published order, fetched when a delta first needs it
+        c->h_order.resize(P);
+        c->h_pos.resize(P);
+        HIP_TRY(c, copy_sync(c, c->h_order.data(), c->sb[c->cur].orig.p, (size_t)P * 4, hipMemcpyDeviceToHost));
+        for (int32_t q = 0; q < P; q++) c->h_pos[c->h_order[q]] = q;
+        c->h_order_valid = true;
+    }
+    const int32_t K = (int32_t)chg.size();
+    dl.K = K;
+    std::vector<int32_t> rem_sorted(K);
+    for (int32_t k = 0; k < K; k++) rem_sorted[k] = c->h_pos[chg[k]];
+    std::sort(rem_sorted.begin(), rem_sorted.end());
+    auto unchanged_at = [&](int32_t j) {  // the j-th row of the old order with the changed rows taken out
+        int32_t pos = j;
+        for (int32_t k = 0; k < K; k++)
+            if (rem_sorted[k] <= pos) pos++;
+        return c->h_order[pos];
+    };
+    RankRow rr[kDeltaRows];
+    for (int32_t k = 0; k < K; k++) rr[k] = make_rank_row(c->pods[chg[k]], D.min_space);
+    // The order this path publishes must be STRICT, as the one from scratch is (scatter_pods_kernel reports two rows
+    // of one rank as MMP_EORDER): a changed row that now ties with its neighbour or with another changed row — a
+    // duplicate or unset id_order, every other field equal — sends the commit down the full path, which reports it.
+    bool strict = true;
+    for (int32_t k = 0; k < K; k++) {
+        int32_t lo = 0, hi = P - K;
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (placement_less(make_rank_row(c->pods[unchanged_at(mid)], D.min_space), rr[k], D.churn2))
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        // (every unchanged row before lo is less than the row by the search; the one at lo must be greater, not equal)
+        if (lo < P - K && !placement_less(rr[k], make_rank_row(c->pods[unchanged_at(lo)], D.min_space), D.churn2)) strict = false;
+        int32_t before = 0;
+        for (int32_t k2 = 0; k2 < K; k2++) {
+            if (k2 == k) continue;
+            const bool lt = placement_less(rr[k2], rr[k], D.churn2);
+            if (lt) before++;
+            else if (!placement_less(rr[k], rr[k2], D.churn2)) strict = false;  // neither before the other: a tie
+        }
+        dl.pod[k] = chg[k];
+        dl.removed[k] = rem_sorted[k];
+        dl.ins[k] = lo;
+        dl.newrank[k] = lo + before;
+        dl.rows[k] = c->pods[chg[k]];
+    }
+    // the host mirror of the NEW order (published with the snapshot)
+    if (strict) {
+        new_order.assign(P, -1);
+        std::vector<uint8_t> is_chg(P, 0);
+        for (int32_t k = 0; k < K; k++) {
+            new_order[dl.newrank[k]] = chg[k];
+            is_chg[chg[k]] = 1;
+        }
+        int32_t w = 0;
+        for (int32_t q = 0; q < P; q++) {
+            const int32_t pod = c->h_order[q];
+            if (is_chg[pod]) continue;
+            while (new_order[w] >= 0) w++;
+            new_order[w++] = pod;
+        }
+    }
+    delta = strict;
+    return MMP_OK;
+}
+
+// The host sources of upload_commit_inputs' copies: pageable, so they stay with the caller until it has synchronised the stream.
+struct InputStage {
+    std::vector<uint8_t> hp, ha;
+    StatsAcc init{};
+};
+// The inputs besides the instance table: the type table's flags and allowed / prefer rows, the replica-set list and the
+// cluster stats' initial value.  A type table goes up only when it was reloaded since the buffer set / the side / the staging
+// copy last took it (their types_gen), or always when `force`; the caller marks the generations once the copies have landed.
+int upload_commit_inputs(mmp_ctx *c, SnapBufs &B, SnapSide &N, int32_t T, bool force, InputStage &in, hipStream_t st)
+{
+    in.hp.assign(T, 0);
+    in.ha.assign(T, 0);
+    for (int32_t t = 0; t < c->n_types; t++) {
+        in.hp[t] = c->has_prefer[t];
+        in.ha[t] = c->has_allowed[t];
+    }
+    const bool side_stale = force || N.types_gen != c->types_gen;
+    if (force || B.types_gen != c->types_gen) HIP_TRY(c, hipMemcpyAsync(B.has_pref.p, in.hp.data(), T, hipMemcpyHostToDevice, st));
+    if (side_stale) HIP_TRY(c, hipMemcpyAsync(N.d_has_allowed.p, in.ha.data(), T, hipMemcpyHostToDevice, st));
+    if (c->n_types > 0 && !c->allowed.empty()) {
+        if (side_stale) HIP_TRY(c, hipMemcpyAsync(N.d_allowed.p, c->allowed.data(), c->allowed.size() * 8, hipMemcpyHostToDevice, st));
+        if (force || c->d_prefer_gen != c->types_gen)
+            HIP_TRY(c, hipMemcpyAsync(c->d_prefer.p, c->prefer.data(), c->prefer.size() * 8, hipMemcpyHostToDevice, st));
+    }
+    const size_t n_rs = c->replaced_rs.size();
+    if (n_rs) HIP_TRY(c, hipMemcpyAsync(c->rs_list.p, c->replaced_rs.data(), n_rs * 4, hipMemcpyHostToDevice, st));
+    in.init = StatsAcc{};
+    in.init.global_lru = INT64_MAX;
+    HIP_TRY(c, hipMemcpyAsync(N.stats_acc.p, &in.init, sizeof in.init, hipMemcpyHostToDevice, st));
+    return MMP_OK;
+}
+
+// The audit hash's word multipliers (Snap::amul): a function of the word index alone, so uploaded, and waited for, once per table size.
+int ensure_audit_multipliers(mmp_ctx *c, SnapBufs &B, int32_t W, hipStream_t st)
+{
+    if (B.amul_w == W) return MMP_OK;
+    HIP_TRY(c, B.amul.ensure((size_t)W * 8));
+    std::vector<uint64_t> am((size_t)W);
+    for (int32_t w = 0; w < W; w++) am[(size_t)w] = audit_mul((uint64_t)w);
+    HIP_TRY(c, hipMemcpyAsync(B.amul.p, am.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));  // (`am` leaves scope)
+    B.amul_w = W;
+    return MMP_OK;
+}
+
+// The unsharded snapshot over B (B.amul is in place: ensure_audit_multipliers).
+Snap snap_of(const SnapBufs &B, const CommitDims &D)
+{
+    Snap S = snap_columns<Snap>(B, D.P, D.W, D.T, D.n_rs > 0, D.min_space);
+    S.ge = B.ge.as<uint64_t>();
+    S.pc = B.pc.as<int32_t>();
+    S.nz = B.nz.as<int32_t>();
+    S.ph = B.ph.as<uint64_t>();
+    S.ctpos = D.P > 0 ? B.ctpos.as<int32_t>() : nullptr;
+    S.amul = B.amul.as<uint64_t>();
+    S.sel = D.P > 0 && D.have_sel ? B.sel.as<int32_t>() : nullptr;
+    S.rk = D.P > 0 && D.have_sel ? B.rk.as<int32_t>() : nullptr;
+    S.memo = B.memo.as<TypeMemo>();
+    S.memo_cand = B.memo_cand.as<int32_t>();
+    S.memo_rk = B.memo_rk.as<int16_t>();
+    S.lmemo = D.have_lmemo ? B.lmemo.as<LongMemo>() : nullptr;
+    return S;
+}
+
+// Ranks of the rows [p_lo, p_hi) of the P-row table at d_pods into d_rank, from scratch: by sampling, by a merge sort of the
+// whole table, or all pairs.  all-pairs is embarrassingly parallel and wins below ~8k pods (measured: 10k pods 172 us all-pairs
+// vs 120 us sort; 50k pods 4.3 ms vs 0.25 ms); a merge sort of a few thousand 64-byte keys is latency bound.  `want_sort` is
+// the caller's threshold (the whole table against a shard's slice of the pairs); sorting also needs the comparator to be a
+// total order (`sort_legal`).  `slice`: the caller is a pod-axis shard, whose d_rank holds only its range's ranks.
+int launch_rank(mmp_ctx *c, const mmp_pod_row *d_pods, int32_t P, int32_t p_lo, int32_t p_hi, bool slice, bool want_sort, bool sort_legal,
+                int32_t *d_rank, hipStream_t st)
+{
+    const int64_t min_space = c->cfg.min_space_units, churn2 = churn2_of(c);
+    if (want_sort && sort_legal && P >= kSampleMinPods && c->tune.rank_mode != 3)
+        return rank_by_sampling(c, d_pods, P, min_space, churn2, p_lo, p_hi, d_rank, st);
+    if (want_sort && sort_legal && P >= 2) {
+        HIP_TRY(c, c->rk_rows.ensure((size_t)P * sizeof(RankRow)));
+        HIP_TRY(c, c->rk_idx.ensure((size_t)P * sizeof(RankRow)));
+        const PlacementRowLess less{churn2};
+        size_t tmp_bytes = 0;
+        HIP_TRY(c, rocprim::merge_sort(nullptr, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
+        HIP_TRY(c, c->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+        hipLaunchKernelGGL(rank_rows_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, d_pods, P, min_space, c->rk_rows.as<RankRow>());
+        HIP_TRY(c, rocprim::merge_sort(c->rk_tmp.p, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
+        if (slice)
+            hipLaunchKernelGGL(rank_from_order_range_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, c->rk_idx.as<RankRow>(), P, p_lo, p_hi, d_rank);
+        else
+            hipLaunchKernelGGL(rank_from_order_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, c->rk_idx.as<RankRow>(), P, d_rank);
+        return MMP_OK;
+    }
+    const int pb = div_up(p_hi - p_lo, kRankBlock);
+    const int slices = std::max(1, std::min(64, 2048 / pb));
+    hipLaunchKernelGGL(rank_pods_kernel, dim3(pb, slices), dim3(kRankBlock), 0, st, d_pods, P, min_space, churn2, slices, p_lo, p_hi, d_rank);
+    return MMP_OK;
+}
+
+void launch_mark_replaced(mmp_ctx *c, const SnapBufs &B, int32_t P, hipStream_t st)
+{
+    const int32_t n_rs = (int32_t)c->replaced_rs.size();
+    if (n_rs)
+        hipLaunchKernelGGL(mark_replaced_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(), P, c->rs_list.as<int32_t>(),
+                           n_rs, c->rs_bad.as<uint8_t>());
+}
+
+// level 1: everything that needs only the table and the rank-ordered columns, in ONE launch (place_kernel.hpp CommitL1)
+CommitL1 make_commit_l1(const mmp_ctx *c, const SnapBufs &B, const SnapSide &N, const CommitDims &D)
+{
+    const int32_t P = D.P, W = D.W, T = D.T;
+    CommitL1 L1{};
+    L1.pods = B.pods.as<mmp_pod_row>();
+    L1.P = P;
+    L1.W = W;
+    L1.T = T;
+    L1.min_space = D.min_space;
+    L1.orig = B.orig.as<int32_t>();
+    L1.cnt = B.cnt.as<int32_t>();
+    L1.allowed = N.d_allowed.as<uint64_t>();
+    L1.prefer = c->d_prefer.as<uint64_t>();
+    L1.has_allowed = N.d_has_allowed.as<uint8_t>();
+    L1.has_prefer = B.has_pref.as<uint8_t>();
+    L1.rs_bad = D.n_rs ? c->rs_bad.as<uint8_t>() : nullptr;
+    L1.elig = B.elig.as<uint64_t>();
+    L1.elig_nors = B.elig_nors.as<uint64_t>();
+    L1.pref = B.pref.as<uint64_t>();
+    L1.fullw = B.fullw.as<uint64_t>();
+    L1.ge = B.ge.as<uint64_t>();
+    L1.ctpos = B.ctpos.as<int32_t>();
+    L1.acc = N.stats_acc.as<StatsAcc>();
+    L1.pod_pts = N.d_pts.as<int32_t>();
+    L1.NP = N.n_pts;
+    L1.pstats = N.pstats.as<StatsAcc>();
+    L1.nb_masks = div_up(T * W, 4);
+    L1.nb_ge = div_up(kGeRows * W, 4);
+    L1.nb_stats = std::min(div_up(P, 256), 512);
+    L1.nb_pstats = N.n_pts > 0 ? std::min(div_up(P, 256), 64) : 0;
+    return L1;
+}
+inline int32_t *n_bslots_dev(const SnapBufs &B) { return reinterpret_cast<int32_t *>(static_cast<char *>(B.bslots.p) + kBSlots * sizeof(BSlot)); }
+// level 2: what needs the bitmaps / the stats: prefix tables, head windows (place_kernel.hpp: TypeWin), case (b) slots
+// (where case (b) starts per preferring type), partition / type subset stats
+CommitL2 make_commit_l2(const mmp_ctx *c, const SnapBufs &B, const SnapSide &N, const Snap &S)
+{
+    CommitL2 L2{};
+    L2.S = S;
+    L2.pods = B.pods.as<mmp_pod_row>();
+    L2.wins = B.heads.as<TypeWin>();
+    L2.slots = B.bslots.as<BSlot>();
+    L2.n_slots = n_bslots_dev(B);
+    L2.acc = N.stats_acc.as<StatsAcc>();
+    L2.pstats = N.pstats.as<StatsAcc>();
+    L2.NP = N.n_pts;
+    L2.Tw = N.pts_tw;
+    L2.prohib = N.d_prohib.as<uint64_t>();
+    L2.has_allowed = c->n_types > 0 ? N.d_has_allowed.as<uint8_t>() : nullptr;
+    L2.tstats = N.tstats.as<StatsAcc>();
+    L2.nb_finish = div_up(std::max(N.n_pts, S.T), 64);
+    return L2;
+}
+// The tables of a non-empty unsharded snapshot, from its rank-ordered columns: level 1, level 2, the inverse tables and
+// shortlists, the case (b) tables.
+void launch_snapshot_tables(mmp_ctx *c, SnapBufs &B, SnapSide &N, const Snap &S, const CommitDims &D, hipStream_t st)
+{
+    const int32_t T = D.T, W = D.W;
+    const CommitL1 L1 = make_commit_l1(c, B, N, D);
+    hipLaunchKernelGGL(commit_level1_kernel, dim3(L1.nb_stats + L1.nb_pstats + 1 + L1.nb_masks + L1.nb_ge), dim3(256), 0, st, L1);
+    const CommitL2 L2 = make_commit_l2(c, B, N, S);
+    hipLaunchKernelGGL(commit_level2_kernel, dim3(4 * T + L2.nb_finish), dim3(64), 0, st, L2);
+    // sel / rk from the prefix tables, and the per-type shortlists (TypeMemo) from the finished head windows (every row a decision
+    // can name is written, valid or not): one launch; the registry view is resolved against the shortlists' ranges afterwards
+    hipLaunchKernelGGL(build_sel_memo_kernel, dim3((D.have_sel ? 2 * T * W : 0) + std::min(T, kWinLds) + (S.lmemo ? T : 0)), dim3(64), 0, st, S,
+                       D.have_sel ? B.sel.as<int32_t>() : nullptr, D.have_sel ? B.rk.as<int32_t>() : nullptr, B.heads.as<TypeWin>(),
+                       B.memo.as<TypeMemo>(), B.memo_cand.as<int32_t>(), B.memo_rk.as<int16_t>(), B.lmemo.as<LongMemo>());
+    // the running minimum of the case (b) candidates' rpm, then the survivor bitmaps of the rpm rule's four limits
+    hipLaunchKernelGGL(prefix_min_rpm_kernel, dim3(kBSlots), dim3(64), 0, st, S, B.bslots.as<BSlot>(), n_bslots_dev(B), B.bpm.as<int32_t>(),
+                       (int32_t)(W * 64));
+    hipLaunchKernelGGL(build_bsurv_kernel, dim3(kBSlots), dim3(256), 0, st, S, B.bslots.as<BSlot>(), n_bslots_dev(B), B.bpm.as<int32_t>(),
+                       (int32_t)(W * 64), B.bwin.as<BLaunch>(), B.bsurv.as<uint64_t>(), B.bpcs.as<int32_t>());
+}
+// The same tables of an empty one.
+int clear_snapshot_tables(mmp_ctx *c, SnapBufs &B, const CommitDims &D, hipStream_t st)
+{
+    const size_t T = D.T, W = D.W;
+    HIP_TRY(c, hipMemsetAsync(B.heads.p, 0, D.wins_bytes, st));
+    HIP_TRY(c, hipMemsetAsync(B.memo.p, 0, (size_t)kWinLds * sizeof(TypeMemo), st));
+    HIP_TRY(c, hipMemsetAsync(B.pc.p, 0, 2 * T * (W + 1) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(B.nz.p, 0, 2 * T * (W + 1) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(B.ph.p, 0, 2 * T * (W + 1) * 8, st));
+    HIP_TRY(c, hipMemsetAsync(B.elig.p, 0, T * W * 8, st));
+    HIP_TRY(c, hipMemsetAsync(B.elig_nors.p, 0, T * W * 8, st));
+    HIP_TRY(c, hipMemsetAsync(B.pref.p, 0, T * W * 8, st));
+    HIP_TRY(c, hipMemsetAsync(B.fullw.p, 0, W * 8, st));
+    HIP_TRY(c, hipMemsetAsync(B.ge.p, 0, kGeRows * W * 8, st));
+    return MMP_OK;
+}
+
+/* Partition the present instances by their ProhibitedTypeSet and build the per-partition / per-type ClusterStats of the
+   snapshot being committed (snapshot.hpp "instance partitions"), in three stages.  N = the side state of the snapshot being built. */
+
+// The host's interning of the partitions and their uploads: inputs, like the table itself.
+int stage_partitions(mmp_ctx *c, SnapSide &N, int32_t P, hipStream_t st)
 {
     const int32_t T = std::max(c->n_types, 1), Tw = div_up(T, 64);
-    if (part <= 0) {
-        N.pts_of.assign(P, -1);
-        N.pts_prohib.clear();
-        N.n_pts = 0;
-        N.pts_tw = Tw;
-        if (c->n_types > 0) {
-            // every instance's ProhibitedTypeSet as an id of the distinct sets: a function of the type table alone, kept until
-            // that table is reloaded (interning P signatures of T bits through a map was most of a small commit's host time)
-            if (!c->sig_valid || (int32_t)c->sig_of.size() != P) {
-                std::map<std::vector<uint64_t>, int32_t> intern;
-                std::vector<uint64_t> sig(Tw);
-                const int32_t Wf = c->types_w;
-                c->sig_of.assign(P, 0);
-                c->sig_rows.clear();
-                for (int32_t p = 0; p < P; p++) {
-                    std::fill(sig.begin(), sig.end(), 0);
-                    for (int32_t t = 0; t < c->n_types; t++)
-                        if (c->has_allowed[t] && !((c->allowed[(size_t)t * Wf + (p >> 6)] >> (p & 63)) & 1ull))
-                            sig[t >> 6] |= 1ull << (t & 63);
-                    auto it = intern.find(sig);
-                    if (it == intern.end()) {
-                        it = intern.emplace(sig, (int32_t)intern.size()).first;
-                        c->sig_rows.insert(c->sig_rows.end(), sig.begin(), sig.end());
-                    }
-                    c->sig_of[p] = it->second;
-                }
-                c->sig_valid = true;
-            }
-            // partitions are numbered by first appearance among the instances PRESENT in this table
-            std::vector<int32_t> number(c->sig_rows.size() / std::max(Tw, 1), -1);
+    N.pts_of.assign(P, -1);
+    N.pts_prohib.clear();
+    N.n_pts = 0;
+    N.pts_tw = Tw;
+    if (c->n_types > 0) {
+        // every instance's ProhibitedTypeSet as an id of the distinct sets: a function of the type table alone, kept until
+        // that table is reloaded (interning P signatures of T bits through a map was most of a small commit's host time)
+        if (!c->sig_valid || (int32_t)c->sig_of.size() != P) {
+            std::map<std::vector<uint64_t>, int32_t> intern;
+            std::vector<uint64_t> sig(Tw);
+            const int32_t Wf = c->types_w;
+            c->sig_of.assign(P, 0);
+            c->sig_rows.clear();
             for (int32_t p = 0; p < P; p++) {
-                if (c->pods[p].flags & (MMP_POD_SHUTTING_DOWN | MMP_POD_TOMBSTONE)) continue;
-                const int32_t sid = c->sig_of[p];
-                if (number[sid] < 0) {
-                    number[sid] = N.n_pts++;
-                    N.pts_prohib.insert(N.pts_prohib.end(), c->sig_rows.begin() + (size_t)sid * Tw, c->sig_rows.begin() + (size_t)(sid + 1) * Tw);
+                std::fill(sig.begin(), sig.end(), 0);
+                for (int32_t t = 0; t < c->n_types; t++)
+                    if (c->has_allowed[t] && !((c->allowed[(size_t)t * Wf + (p >> 6)] >> (p & 63)) & 1ull))
+                        sig[t >> 6] |= 1ull << (t & 63);
+                auto it = intern.find(sig);
+                if (it == intern.end()) {
+                    it = intern.emplace(sig, (int32_t)intern.size()).first;
+                    c->sig_rows.insert(c->sig_rows.end(), sig.begin(), sig.end());
                 }
-                N.pts_of[p] = number[sid];
+                c->sig_of[p] = it->second;
             }
+            c->sig_valid = true;
         }
-        const int32_t NP = N.n_pts;
-        N.pstats_h.assign(NP + 1, StatsAcc{});
-        N.pstats_h[NP].global_lru = INT64_MAX;  // InstanceSetStatsTracker.EMPTY_STATS
-        N.tstats_h.assign(T, StatsAcc{});
-        HIP_TRY(c, N.d_pts.ensure(std::max<size_t>(P, 1) * 4));
-        HIP_TRY(c, N.d_prohib.ensure(std::max<size_t>((size_t)NP * Tw, 1) * 8));
-        HIP_TRY(c, N.pstats.ensure((size_t)(NP + 1) * sizeof(StatsAcc)));
-        HIP_TRY(c, N.tstats.ensure((size_t)T * sizeof(StatsAcc)));
-        if (P) HIP_TRY(c, hipMemcpyAsync(N.d_pts.p, N.pts_of.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-        if (NP) HIP_TRY(c, hipMemcpyAsync(N.d_prohib.p, N.pts_prohib.data(), (size_t)NP * Tw * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(N.pstats.p, N.pstats_h.data(), (size_t)(NP + 1) * sizeof(StatsAcc), hipMemcpyHostToDevice, st));
+        // partitions are numbered by first appearance among the instances PRESENT in this table
+        std::vector<int32_t> number(c->sig_rows.size() / std::max(Tw, 1), -1);
+        for (int32_t p = 0; p < P; p++) {
+            if (c->pods[p].flags & (MMP_POD_SHUTTING_DOWN | MMP_POD_TOMBSTONE)) continue;
+            const int32_t sid = c->sig_of[p];
+            if (number[sid] < 0) {
+                number[sid] = N.n_pts++;
+                N.pts_prohib.insert(N.pts_prohib.end(), c->sig_rows.begin() + (size_t)sid * Tw, c->sig_rows.begin() + (size_t)(sid + 1) * Tw);
+            }
+            N.pts_of[p] = number[sid];
+        }
     }
-    if (part != 0) {
-        const int32_t NP = N.n_pts;
-        if (part == 2) {
-            // (the kernels ran inside the commit's level launches)
-        } else if (NP > 0 && P > 0)
-            hipLaunchKernelGGL(partition_stats_kernel, dim3(std::min(div_up(P, 256), 64)), dim3(256), 0, st, d_pods, P, min_space,
-                               N.d_pts.as<int32_t>(), NP, N.pstats.as<StatsAcc>());
-        if (part != 2)
-            hipLaunchKernelGGL(subset_stats_finish_kernel, dim3(div_up(std::max(NP, T), 256)), dim3(256), 0, st,
-                               N.stats_acc.as<StatsAcc>(), N.pstats.as<StatsAcc>(), NP, N.d_prohib.as<uint64_t>(), Tw, T,
-                               c->n_types > 0 ? N.d_has_allowed.as<uint8_t>() : nullptr, N.tstats.as<StatsAcc>());
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(N.pstats_h.data(), N.pstats.p, (size_t)(NP + 1) * sizeof(StatsAcc), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(N.tstats_h.data(), N.tstats.p, (size_t)T * sizeof(StatsAcc), hipMemcpyDeviceToHost, st));
-    }
+    const int32_t NP = N.n_pts;
+    N.pstats_h.assign(NP + 1, StatsAcc{});
+    N.pstats_h[NP].global_lru = INT64_MAX;  // InstanceSetStatsTracker.EMPTY_STATS
+    N.tstats_h.assign(T, StatsAcc{});
+    HIP_TRY(c, N.d_pts.ensure(std::max<size_t>(P, 1) * 4));
+    HIP_TRY(c, N.d_prohib.ensure(std::max<size_t>((size_t)NP * Tw, 1) * 8));
+    HIP_TRY(c, N.pstats.ensure((size_t)(NP + 1) * sizeof(StatsAcc)));
+    HIP_TRY(c, N.tstats.ensure((size_t)T * sizeof(StatsAcc)));
+    if (P) HIP_TRY(c, hipMemcpyAsync(N.d_pts.p, N.pts_of.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+    if (NP) HIP_TRY(c, hipMemcpyAsync(N.d_prohib.p, N.pts_prohib.data(), (size_t)NP * Tw * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(N.pstats.p, N.pstats_h.data(), (size_t)(NP + 1) * sizeof(StatsAcc), hipMemcpyHostToDevice, st));
     return MMP_OK;
+}
+// The kernels, for a commit whose level launches do not hold them (an empty table, a pod-axis shard).  After the cluster
+// stats: N.stats_acc and N.d_has_allowed are filled.
+int launch_subset_stats(mmp_ctx *c, SnapSide &N, const mmp_pod_row *d_pods, int32_t P, int64_t min_space, hipStream_t st)
+{
+    const int32_t T = std::max(c->n_types, 1), NP = N.n_pts;
+    if (NP > 0 && P > 0)
+        hipLaunchKernelGGL(partition_stats_kernel, dim3(std::min(div_up(P, 256), 64)), dim3(256), 0, st, d_pods, P, min_space,
+                           N.d_pts.as<int32_t>(), NP, N.pstats.as<StatsAcc>());
+    hipLaunchKernelGGL(subset_stats_finish_kernel, dim3(div_up(std::max(NP, T), 256)), dim3(256), 0, st, N.stats_acc.as<StatsAcc>(),
+                       N.pstats.as<StatsAcc>(), NP, N.d_prohib.as<uint64_t>(), N.pts_tw, T,
+                       c->n_types > 0 ? N.d_has_allowed.as<uint8_t>() : nullptr, N.tstats.as<StatsAcc>());
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+// The results into the host mirrors, valid once the caller has synchronised st.
+int fetch_subset_stats(mmp_ctx *c, SnapSide &N, hipStream_t st)
+{
+    const int32_t T = std::max(c->n_types, 1), NP = N.n_pts;
+    HIP_TRY(c, hipMemcpyAsync(N.pstats_h.data(), N.pstats.p, (size_t)(NP + 1) * sizeof(StatsAcc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(N.tstats_h.data(), N.tstats.p, (size_t)T * sizeof(StatsAcc), hipMemcpyDeviceToHost, st));
+    return MMP_OK;
+}
+
+// The scatter's "two rows of one rank" flag and the cluster stats, into the caller's words: valid once it has synchronised st.
+int fetch_commit_result(mmp_ctx *c, SnapSide &N, int32_t *bad, StatsAcc *acc, hipStream_t st)
+{
+    HIP_TRY(c, hipMemcpyAsync(bad, c->flag.p, sizeof *bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(acc, N.stats_acc.p, sizeof *acc, hipMemcpyDeviceToHost, st));
+    return MMP_OK;
+}
+void publish_cluster_stats(mmp_ctx *c, const StatsAcc &acc)
+{
+    c->stats.total_capacity = (int64_t)acc.total_capacity;
+    c->stats.total_free = (int64_t)acc.total_free;
+    c->stats.global_lru = (int64_t)acc.global_lru;
+    c->stats.instance_count = acc.instance_count;
+    c->stats.model_copy_count = acc.model_copy_count;
 }
 }  // namespace
 
@@ -1704,369 +2106,71 @@ try {
     // was enqueued before that swap.  Waiting for the decision streams (without c->mu: new decisions only ever
     // capture the published set) retires those.
     HIP_TRY(c, quiesce_decisions(c));
-    const int32_t P = (int32_t)c->pods.size();
-    const int32_t W = std::max(div_up(P, 64), 1);
-    const int32_t T = std::max(c->n_types, 1);
+
+    // sizes
+    const CommitDims D = commit_dims(c);
+    const int32_t P = D.P;
     if (c->n_types > 0 && c->types_w != div_up(P, 64))
         return fail(c, MMP_ESTATE, "type bitmaps were loaded for a different pod count; reload them before commit");
-    const size_t padded = (size_t)W * 64;
     SnapBufs &B = c->sb[1 - c->cur];
     SnapSide &N = c->side[1 - c->cur];
     hipStream_t st = c->stream;
+    if (const int rc = ensure_snapshot_buffers(c, B, N, D)) return rc;
 
-    HIP_TRY(c, B.pods.ensure(std::max<size_t>(P, 1) * sizeof(mmp_pod_row)));
-    HIP_TRY(c, B.lru.ensure(padded * 8));
-    HIP_TRY(c, B.rem.ensure(padded * 8));
-    HIP_TRY(c, B.cnt.ensure(padded * 4));
-    HIP_TRY(c, B.rpm.ensure(padded * 4));
-    HIP_TRY(c, B.orig.ensure(padded * 4));
-    HIP_TRY(c, B.pos_of.ensure(padded * 4));
-    HIP_TRY(c, B.elig.ensure((size_t)T * W * 8));
-    HIP_TRY(c, B.elig_nors.ensure((size_t)T * W * 8));
-    HIP_TRY(c, B.pref.ensure((size_t)T * W * 8));
-    HIP_TRY(c, B.has_pref.ensure(T));
-    HIP_TRY(c, B.fullw.ensure((size_t)W * 8));
-    HIP_TRY(c, B.ge.ensure((size_t)kGeRows * W * 8));
-    HIP_TRY(c, B.ctpos.ensure((size_t)(kGeRows + 1) * 4));
-    HIP_TRY(c, B.pc.ensure((size_t)2 * T * (W + 1) * 4));
-    HIP_TRY(c, B.nz.ensure((size_t)2 * T * (W + 1) * 4));
-    HIP_TRY(c, B.ph.ensure((size_t)2 * T * (W + 1) * 8));
-    // the long path's inverse tables (Snap::sel / ::rk): 512 bytes per type row and 64-position word, each, rebuilt at every commit —
-    // 320 KB on C3, but a table of 100 type rows x 100 000 instances would be 80 MB a piece: beyond kSelMaxBytes they are not built
-    // and a shortlist that spans the table takes the wave path (ADVICE r5)
-    const size_t sel_bytes = (size_t)2 * T * W * 64 * 4;
-    const bool have_sel = sel_bytes <= kSelMaxBytes;
-    if (have_sel) {
-        HIP_TRY(c, B.sel.ensure(sel_bytes));
-        HIP_TRY(c, B.rk.ensure(sel_bytes));
-    }
-    HIP_TRY(c, B.memo.ensure((size_t)kWinLds * sizeof(TypeMemo)));
-    HIP_TRY(c, B.memo_cand.ensure((size_t)kWinLds * kMemoCand * 4));
-    HIP_TRY(c, B.memo_rk.ensure((size_t)kWinLds * kMemoCand * 2));
-    // rounded up to the 1 KB chunks place_block stages (rows beyond T are never read as windows)
-    const size_t wins_bytes = (((size_t)std::max(T, kWinLds) * sizeof(TypeWin) + 1023) / 1024) * 1024;
-    HIP_TRY(c, B.heads.ensure(wins_bytes));
-    HIP_TRY(c, B.bslots.ensure(kBSlots * sizeof(BSlot) + 16));
-    HIP_TRY(c, B.bpm.ensure((size_t)kBSlots * W * 64 * 4));
-    HIP_TRY(c, B.bwin.ensure(kBSlots * sizeof(BLaunch)));
-    HIP_TRY(c, B.bsurv.ensure((size_t)kBSlots * kBClasses * W * 8));
-    HIP_TRY(c, B.bpcs.ensure((size_t)kBSlots * kBClasses * (W + 1) * 4));
-    HIP_TRY(c, c->rank.ensure(padded * 4));
-    HIP_TRY(c, c->occupancy.ensure(padded * 4));
-    HIP_TRY(c, c->flag.ensure(sizeof(int32_t)));
-    HIP_TRY(c, N.stats_acc.ensure(sizeof(StatsAcc)));
-    HIP_TRY(c, c->rs_bad.ensure(padded));
-    HIP_TRY(c, c->rs_list.ensure(std::max<size_t>(c->replaced_rs.size(), 1) * 4));
-    HIP_TRY(c, N.d_allowed.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
-    HIP_TRY(c, c->d_prefer.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
-    HIP_TRY(c, N.d_has_allowed.ensure(T));
-
-    const int64_t min_space = c->cfg.min_space_units;
-    const int64_t churn2 = (int64_t)((uint64_t)c->cfg.min_churn_age_ms * 2u);
-    // is the literal comparator a strict total order on these rows?  (see snapshot.hpp "ranking by sorting")
-    bool versions_differ = false, full_low_lru = false, wide_count = false;
-    int32_t n_present = 0, n_nonfull = 0;
-    for (int32_t p = 0; p < P; p++) {
-        const mmp_pod_row &r = c->pods[p];
-        if (r.version != c->pods[0].version) versions_differ = true;
-        if (r.count > (1 << 30) || r.count < -(1 << 30)) wide_count = true;  // :4676 is an int subtraction
-        const uint64_t d = (uint64_t)r.capacity - (uint64_t)r.used;
-        const int64_t rem = (int64_t)d > 0 ? (int64_t)d : 0;
-        if (rem < min_space && r.lru_time <= churn2) full_low_lru = true;
-        if (!(r.flags & (MMP_POD_SHUTTING_DOWN | MMP_POD_TOMBSTONE))) {
-            n_present++;
-            if (!(rem < min_space)) n_nonfull++;
-        }
-    }
-    const bool sort_legal = !(versions_differ && full_low_lru) && !wide_count;
-    // A few rows changed since the published snapshot, and both orders are total: re-rank by insertion (snapshot.hpp
-    // "a commit whose table differs ... in a few rows").  The unpublished set is rebuilt from the PUBLISHED one.
+    // order check, delta plan
+    const OrderCheck oc = check_placement_order(c->pods, D.min_space, D.churn2);
     DeltaRows dl{};
     std::vector<int32_t> new_order;
     bool delta = false;
-    if (c->committed && !c->dirty_all && !c->tune.no_delta && sort_legal && c->order_total && P >= 2 && P == c->snap.P) {
-        std::vector<int32_t> chg(c->dirty);
-        std::sort(chg.begin(), chg.end());
-        chg.erase(std::unique(chg.begin(), chg.end()), chg.end());
-        if ((int32_t)chg.size() <= kDeltaRows) {
-            const SnapBufs &A = c->sb[c->cur];
-            if (!c->h_order_valid) {  // the host's mirror of the published order, fetched when a delta first needs it
-                c->h_order.resize(P);
-                c->h_pos.resize(P);
-                HIP_TRY(c, copy_sync(c, c->h_order.data(), A.orig.p, (size_t)P * 4, hipMemcpyDeviceToHost));
-                for (int32_t q = 0; q < P; q++) c->h_pos[c->h_order[q]] = q;
-                c->h_order_valid = true;
-            }
-            const int32_t K = (int32_t)chg.size();
-            dl.K = K;
-            std::vector<int32_t> rem_sorted(K);
-            for (int32_t k = 0; k < K; k++) rem_sorted[k] = c->h_pos[chg[k]];
-            std::sort(rem_sorted.begin(), rem_sorted.end());
-            auto unchanged_at = [&](int32_t j) {  // the j-th row of the old order with the changed rows taken out
-                int32_t pos = j;
-                for (int32_t k = 0; k < K; k++)
-                    if (rem_sorted[k] <= pos) pos++;
-                return c->h_order[pos];
-            };
-            RankRow rr[kDeltaRows];
-            for (int32_t k = 0; k < K; k++) rr[k] = make_rank_row(c->pods[chg[k]], min_space);
-            // The order this path publishes must be STRICT, as the one from scratch is (scatter_pods_kernel reports two rows
-            // of one rank as MMP_EORDER): a changed row that now ties with its neighbour or with another changed row — a
-            // duplicate or unset id_order, every other field equal — sends the commit down the full path, which reports it.
-            bool strict = true;
-            for (int32_t k = 0; k < K; k++) {
-                int32_t lo = 0, hi = P - K;
-                while (lo < hi) {
-                    const int32_t mid = (lo + hi) >> 1;
-                    if (placement_less(make_rank_row(c->pods[unchanged_at(mid)], min_space), rr[k], churn2))
-                        lo = mid + 1;
-                    else
-                        hi = mid;
-                }
-                // (every unchanged row before lo is less than the row by the search; the one at lo must be greater, not equal)
-                if (lo < P - K && !placement_less(rr[k], make_rank_row(c->pods[unchanged_at(lo)], min_space), churn2)) strict = false;
-                int32_t before = 0;
-                for (int32_t k2 = 0; k2 < K; k2++) {
-                    if (k2 == k) continue;
-                    const bool lt = placement_less(rr[k2], rr[k], churn2);
-                    if (lt) before++;
-                    else if (!placement_less(rr[k], rr[k2], churn2)) strict = false;  // neither before the other: a tie
-                }
-                dl.pod[k] = chg[k];
-                dl.removed[k] = rem_sorted[k];
-                dl.ins[k] = lo;
-                dl.newrank[k] = lo + before;
-                dl.rows[k] = c->pods[chg[k]];
-            }
-            // the host mirror of the NEW order (published with the snapshot below)
-            if (strict) {
-                new_order.assign(P, -1);
-                std::vector<uint8_t> is_chg(P, 0);
-                for (int32_t k = 0; k < K; k++) {
-                    new_order[dl.newrank[k]] = chg[k];
-                    is_chg[chg[k]] = 1;
-                }
-                int32_t w = 0;
-                for (int32_t q = 0; q < P; q++) {
-                    const int32_t pod = c->h_order[q];
-                    if (is_chg[pod]) continue;
-                    while (new_order[w] >= 0) w++;
-                    new_order[w++] = pod;
-                }
-            }
-            delta = strict;
-        }
-    }
+    if (const int rc = plan_delta(c, D, oc.sort_legal, dl, new_order, delta)) return rc;
+
+    // uploads (a delta takes its rows inside `dl`), with the scratch and the column tails cleared
     if (P && !delta) HIP_TRY(c, hipMemcpyAsync(B.pods.p, c->pods.data(), (size_t)P * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
-    {
-        ZeroBatch zb(st);
-        zb.add(c->rank.p, padded * 4);
-        zb.add(c->occupancy.p, padded * 4);
-        zb.add(c->flag.p, sizeof(int32_t));
-        zb.add(B.bslots.p, kBSlots * sizeof(BSlot) + 16);
-        zb.launch(st);
-    }
-    hipLaunchKernelGGL(zero_tails_kernel, dim3(1), dim3(64), 0, st, B.lru.as<int64_t>(), B.rem.as<int64_t>(), B.cnt.as<int32_t>(),
-                       B.rpm.as<int32_t>(), B.orig.as<int32_t>(), B.pos_of.as<int32_t>(), P, (int32_t)padded);
-
-    // the type table goes up only when it was reloaded since this buffer set / side / the staging copy last took it
-    std::vector<uint8_t> hp(T, 0), ha(T, 0);
-    for (int32_t t = 0; t < c->n_types; t++) {
-        hp[t] = c->has_prefer[t];
-        ha[t] = c->has_allowed[t];
-    }
-    if (B.types_gen != c->types_gen) HIP_TRY(c, hipMemcpyAsync(B.has_pref.p, hp.data(), T, hipMemcpyHostToDevice, st));
-    if (N.types_gen != c->types_gen) HIP_TRY(c, hipMemcpyAsync(N.d_has_allowed.p, ha.data(), T, hipMemcpyHostToDevice, st));
-    if (c->n_types > 0 && !c->allowed.empty()) {
-        if (N.types_gen != c->types_gen)
-            HIP_TRY(c, hipMemcpyAsync(N.d_allowed.p, c->allowed.data(), c->allowed.size() * 8, hipMemcpyHostToDevice, st));
-        if (c->d_prefer_gen != c->types_gen)
-            HIP_TRY(c, hipMemcpyAsync(c->d_prefer.p, c->prefer.data(), c->prefer.size() * 8, hipMemcpyHostToDevice, st));
-    }
+    clear_commit_scratch(c, B, D, st);
+    InputStage in;
+    if (const int rc = upload_commit_inputs(c, B, N, D.T, false, in, st)) return rc;
     const uint64_t types_gen_uploaded = c->types_gen;  // (marked current once the copies have landed: behind the synchronisation)
-    const int32_t n_rs = (int32_t)c->replaced_rs.size();
-    if (n_rs) HIP_TRY(c, hipMemcpyAsync(c->rs_list.p, c->replaced_rs.data(), (size_t)n_rs * 4, hipMemcpyHostToDevice, st));
-
-    StatsAcc init{};
-    init.global_lru = INT64_MAX;
-    HIP_TRY(c, hipMemcpyAsync(N.stats_acc.p, &init, sizeof init, hipMemcpyHostToDevice, st));
-
-    Snap S{};
-    S.P = P;
-    S.W = W;
-    S.T = T;
-    S.any_rs = c->replaced_rs.size() > 0;
-    S.min_space = min_space;
-    S.lru = B.lru.as<int64_t>();
-    S.rem = B.rem.as<int64_t>();
-    S.cnt = B.cnt.as<int32_t>();
-    S.rpm = B.rpm.as<int32_t>();
-    S.orig = B.orig.as<int32_t>();
-    S.pos_of = B.pos_of.as<int32_t>();
-    S.elig = B.elig.as<uint64_t>();
-    S.elig_nors = B.elig_nors.as<uint64_t>();
-    S.pref = B.pref.as<uint64_t>();
-    S.has_pref = B.has_pref.as<uint8_t>();
-    S.fullw = B.fullw.as<uint64_t>();
-    S.ge = B.ge.as<uint64_t>();
-    S.pc = B.pc.as<int32_t>();
-    S.nz = B.nz.as<int32_t>();
-    S.ph = B.ph.as<uint64_t>();
-    S.ctpos = P > 0 ? B.ctpos.as<int32_t>() : nullptr;
-    if (B.amul_w != W) {  // the audit hash's word multipliers: a function of the word index alone
-        HIP_TRY(c, B.amul.ensure((size_t)W * 8));
-        std::vector<uint64_t> am((size_t)W);
-        for (int32_t w = 0; w < W; w++) am[(size_t)w] = audit_mul((uint64_t)w);
-        HIP_TRY(c, hipMemcpyAsync(B.amul.p, am.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipStreamSynchronize(st));  // (`am` leaves scope; once per table size)
-        B.amul_w = W;
-    }
-    S.amul = B.amul.as<uint64_t>();
-    S.sel = P > 0 && have_sel ? B.sel.as<int32_t>() : nullptr;
-    S.rk = P > 0 && have_sel ? B.rk.as<int32_t>() : nullptr;
-    S.memo = B.memo.as<TypeMemo>();
-    S.memo_cand = B.memo_cand.as<int32_t>();
-    S.memo_rk = B.memo_rk.as<int16_t>();
-    S.lmemo = nullptr;
-    if (P > 0 && have_sel && !c->tune.no_long_memo) {  // the recorded walks of the long shortlists (place_kernel.hpp: LongMemo)
-        HIP_TRY(c, B.lmemo.ensure((size_t)T * kLongLevels * sizeof(LongMemo)));
-        S.lmemo = B.lmemo.as<LongMemo>();
-    }
+    if (const int rc = ensure_audit_multipliers(c, B, D.W, st)) return rc;
+    const Snap S = snap_of(B, D);
+    if (const int rc = stage_partitions(c, N, P, st)) return rc;
 
     bool next_long = c->tune.long_mode == 1, next_full = false;
-    {  // the partitions of the type constraints (host) and their uploads: inputs, like the table itself
-        const int rc = build_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, min_space, st, 0);
-        if (rc != MMP_OK) return rc;
-    }
     KT_BEGIN(c, st);
     if (P > 0) {
         // (nearly) every instance full: getNext is in its LRU-window mode and whole-table shortlists are common
-        next_long = c->tune.long_mode == 1 || (c->tune.long_mode != 0 && n_present > 0 && n_nonfull * 16 <= n_present);
-        next_full = n_present > 0 && n_nonfull * 16 <= n_present;
-        // all-pairs is embarrassingly parallel and wins below ~8k pods (measured: 10k pods 172 us all-pairs vs 120 us
-        // sort; 50k pods 4.3 ms vs 0.25 ms); a merge sort of a few thousand 64-byte keys is latency bound
-        const bool want_sort = c->tune.rank_mode == 2 || c->tune.rank_mode == 3 || (c->tune.rank_mode == 0 && P >= kRankSortMinPods);
+        next_full = oc.n_present > 0 && oc.n_nonfull * 16 <= oc.n_present;
+        next_long = c->tune.long_mode == 1 || (c->tune.long_mode != 0 && next_full);
+        // rank + scatter into the rank-ordered columns
         if (delta) {
             const SnapBufs &A = c->sb[c->cur];
             hipLaunchKernelGGL(delta_scatter_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, A.pods.as<mmp_pod_row>(), A.pos_of.as<int32_t>(),
                                P, dl, B.pods.as<mmp_pod_row>(), c->rank.as<int32_t>(), B.lru.as<int64_t>(), B.rem.as<int64_t>(),
                                B.cnt.as<int32_t>(), B.rpm.as<int32_t>(), B.orig.as<int32_t>(), B.pos_of.as<int32_t>());
-        } else if (want_sort && P >= kSampleMinPods && sort_legal && c->tune.rank_mode != 3) {
-            const int rc = rank_by_sampling(c, B.pods.as<mmp_pod_row>(), P, min_space, churn2, 0, P, c->rank.as<int32_t>(), st);
-            if (rc != MMP_OK) return rc;
-        } else if (want_sort && P >= 2 && sort_legal) {
-            HIP_TRY(c, c->rk_rows.ensure((size_t)P * sizeof(RankRow)));
-            HIP_TRY(c, c->rk_idx.ensure((size_t)P * sizeof(RankRow)));
-            const PlacementRowLess less{churn2};
-            size_t tmp_bytes = 0;
-            HIP_TRY(c, rocprim::merge_sort(nullptr, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
-            HIP_TRY(c, c->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-            hipLaunchKernelGGL(rank_rows_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(), P, min_space,
-                               c->rk_rows.as<RankRow>());
-            HIP_TRY(c, rocprim::merge_sort(c->rk_tmp.p, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
-            hipLaunchKernelGGL(rank_from_order_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, c->rk_idx.as<RankRow>(), P,
-                               c->rank.as<int32_t>());
         } else {
-            const int pb = div_up(P, kRankBlock);
-            const int slices = std::max(1, std::min(64, 2048 / pb));
-            hipLaunchKernelGGL(rank_pods_kernel, dim3(pb, slices), dim3(kRankBlock), 0, st, B.pods.as<mmp_pod_row>(), P,
-                               min_space, churn2, slices, 0, P, c->rank.as<int32_t>());
-        }
-        if (!delta)
+            const bool want_sort = c->tune.rank_mode == 2 || c->tune.rank_mode == 3 || (c->tune.rank_mode == 0 && P >= kRankSortMinPods);
+            if (const int rc = launch_rank(c, B.pods.as<mmp_pod_row>(), P, 0, P, false, want_sort, oc.sort_legal, c->rank.as<int32_t>(), st))
+                return rc;
             hipLaunchKernelGGL(scatter_pods_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(), P,
-                               min_space, c->rank.as<int32_t>(), c->occupancy.as<int32_t>(), B.lru.as<int64_t>(),
+                               D.min_space, c->rank.as<int32_t>(), c->occupancy.as<int32_t>(), B.lru.as<int64_t>(),
                                B.rem.as<int64_t>(), B.cnt.as<int32_t>(), B.rpm.as<int32_t>(), B.orig.as<int32_t>(),
                                B.pos_of.as<int32_t>(), c->flag.as<int32_t>());
-        if (n_rs)
-            hipLaunchKernelGGL(mark_replaced_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(),
-                               P, c->rs_list.as<int32_t>(), n_rs, c->rs_bad.as<uint8_t>());
-        // level 1: everything that needs only the table and the rank-ordered columns, in ONE launch (place_kernel.hpp CommitL1)
-        CommitL1 L1{};
-        L1.pods = B.pods.as<mmp_pod_row>();
-        L1.P = P;
-        L1.W = W;
-        L1.T = T;
-        L1.min_space = min_space;
-        L1.orig = B.orig.as<int32_t>();
-        L1.cnt = B.cnt.as<int32_t>();
-        L1.allowed = N.d_allowed.as<uint64_t>();
-        L1.prefer = c->d_prefer.as<uint64_t>();
-        L1.has_allowed = N.d_has_allowed.as<uint8_t>();
-        L1.has_prefer = B.has_pref.as<uint8_t>();
-        L1.rs_bad = n_rs ? c->rs_bad.as<uint8_t>() : nullptr;
-        L1.elig = B.elig.as<uint64_t>();
-        L1.elig_nors = B.elig_nors.as<uint64_t>();
-        L1.pref = B.pref.as<uint64_t>();
-        L1.fullw = B.fullw.as<uint64_t>();
-        L1.ge = B.ge.as<uint64_t>();
-        L1.ctpos = B.ctpos.as<int32_t>();
-        L1.acc = N.stats_acc.as<StatsAcc>();
-        L1.pod_pts = N.d_pts.as<int32_t>();
-        L1.NP = N.n_pts;
-        L1.pstats = N.pstats.as<StatsAcc>();
-        L1.nb_masks = div_up(T * W, 4);
-        L1.nb_ge = div_up(kGeRows * W, 4);
-        L1.nb_stats = std::min(div_up(P, 256), 512);
-        L1.nb_pstats = N.n_pts > 0 ? std::min(div_up(P, 256), 64) : 0;
-        hipLaunchKernelGGL(commit_level1_kernel, dim3(L1.nb_stats + L1.nb_pstats + 1 + L1.nb_masks + L1.nb_ge), dim3(256), 0, st, L1);
-        // level 2: what needs the bitmaps / the stats: prefix tables, head windows (place_kernel.hpp: TypeWin), case (b) slots
-        // (where case (b) starts per preferring type), partition / type subset stats
-        int32_t *n_bslots_dev = reinterpret_cast<int32_t *>(static_cast<char *>(B.bslots.p) + kBSlots * sizeof(BSlot));
-        CommitL2 L2{};
-        L2.S = S;
-        L2.pods = B.pods.as<mmp_pod_row>();
-        L2.wins = B.heads.as<TypeWin>();
-        L2.slots = B.bslots.as<BSlot>();
-        L2.n_slots = n_bslots_dev;
-        L2.acc = N.stats_acc.as<StatsAcc>();
-        L2.pstats = N.pstats.as<StatsAcc>();
-        L2.NP = N.n_pts;
-        L2.Tw = N.pts_tw;
-        L2.prohib = N.d_prohib.as<uint64_t>();
-        L2.has_allowed = c->n_types > 0 ? N.d_has_allowed.as<uint8_t>() : nullptr;
-        L2.tstats = N.tstats.as<StatsAcc>();
-        L2.nb_finish = div_up(std::max(N.n_pts, T), 64);
-        hipLaunchKernelGGL(commit_level2_kernel, dim3(4 * T + L2.nb_finish), dim3(64), 0, st, L2);
-        // sel / rk from the prefix tables, and the per-type shortlists (TypeMemo) from the finished head windows (every row a decision
-        // can name is written, valid or not): one launch; the registry view below is resolved against the shortlists' ranges
-        hipLaunchKernelGGL(build_sel_memo_kernel, dim3((have_sel ? 2 * T * W : 0) + std::min(T, kWinLds) + (S.lmemo ? T : 0)), dim3(64), 0, st, S,
-                           have_sel ? B.sel.as<int32_t>() : nullptr, have_sel ? B.rk.as<int32_t>() : nullptr,
-                           B.heads.as<TypeWin>(), B.memo.as<TypeMemo>(), B.memo_cand.as<int32_t>(), B.memo_rk.as<int16_t>(),
-                           B.lmemo.as<LongMemo>());
-        // the running minimum of the case (b) candidates' rpm, then the survivor bitmaps of the rpm rule's four limits
-        hipLaunchKernelGGL(prefix_min_rpm_kernel, dim3(kBSlots), dim3(64), 0, st, S, B.bslots.as<BSlot>(), n_bslots_dev, B.bpm.as<int32_t>(),
-                           (int32_t)(W * 64));
-        hipLaunchKernelGGL(build_bsurv_kernel, dim3(kBSlots), dim3(256), 0, st, S, B.bslots.as<BSlot>(), n_bslots_dev, B.bpm.as<int32_t>(),
-                           (int32_t)(W * 64), B.bwin.as<BLaunch>(), B.bsurv.as<uint64_t>(), B.bpcs.as<int32_t>());
+        }
+        launch_mark_replaced(c, B, P, st);
+        // level 1, level 2 (the subset stats ride in them), sel / memo, case (b) tables
+        launch_snapshot_tables(c, B, N, S, D, st);
         HIP_TRY(c, hipGetLastError());
     } else {
-        HIP_TRY(c, hipMemsetAsync(B.heads.p, 0, wins_bytes, st));
-        HIP_TRY(c, hipMemsetAsync(B.memo.p, 0, (size_t)kWinLds * sizeof(TypeMemo), st));
-        HIP_TRY(c, hipMemsetAsync(B.pc.p, 0, (size_t)2 * T * (W + 1) * 4, st));
-        HIP_TRY(c, hipMemsetAsync(B.nz.p, 0, (size_t)2 * T * (W + 1) * 4, st));
-        HIP_TRY(c, hipMemsetAsync(B.ph.p, 0, (size_t)2 * T * (W + 1) * 8, st));
-        HIP_TRY(c, hipMemsetAsync(B.elig.p, 0, (size_t)T * W * 8, st));
-        HIP_TRY(c, hipMemsetAsync(B.elig_nors.p, 0, (size_t)T * W * 8, st));
-        HIP_TRY(c, hipMemsetAsync(B.pref.p, 0, (size_t)T * W * 8, st));
-        HIP_TRY(c, hipMemsetAsync(B.fullw.p, 0, (size_t)W * 8, st));
-        HIP_TRY(c, hipMemsetAsync(B.ge.p, 0, (size_t)kGeRows * W * 8, st));
+        if (const int rc = clear_snapshot_tables(c, B, D, st)) return rc;
+        if (const int rc = launch_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, D.min_space, st)) return rc;
     }
-    {
-        const int rc = build_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, min_space, st, P > 0 ? 2 : 1);
-        if (rc != MMP_OK) return rc;
-    }
+    if (const int rc = fetch_subset_stats(c, N, st)) return rc;
     KT_END(c, st);
     // the registry view resolved against the new order (still invisible to decisions), queued before the one synchronisation
-    {
-        const int rc = rebuild_resolved(c, N, S, true, false);
-        if (rc != MMP_OK) return rc;
-    }
-    int32_t bad = 0;
+    if (const int rc = rebuild_resolved(c, N, S, true, false)) return rc;
+    int32_t bad = 0, n_bslots = 0;
     StatsAcc acc{};
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->flag.p, sizeof bad, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&acc, N.stats_acc.p, sizeof acc, hipMemcpyDeviceToHost, st));
-    int32_t n_bslots = 0;
-    HIP_TRY(c, hipMemcpyAsync(&n_bslots, static_cast<char *>(B.bslots.p) + kBSlots * sizeof(BSlot), sizeof n_bslots, hipMemcpyDeviceToHost, st));
+    if (const int rc = fetch_commit_result(c, N, &bad, &acc, st)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(&n_bslots, n_bslots_dev(B), sizeof n_bslots, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     B.types_gen = N.types_gen = c->d_prefer_gen = types_gen_uploaded;
     B.n_bslots = std::min(n_bslots, kBSlots);
@@ -2082,7 +2186,7 @@ try {
     // publish: the only part of a commit a decision can ever wait for
     std::lock_guard<std::shared_mutex> g(c->mu);
     resident_stop(c);  // it answers for the snapshot it was launched with; the next single request starts one on the new
-    c->order_total = sort_legal;
+    c->order_total = oc.sort_legal;
     if (delta) {
         c->h_order.swap(new_order);
         for (int32_t q = 0; q < P; q++) c->h_pos[c->h_order[q]] = q;
@@ -2097,17 +2201,9 @@ try {
     c->cur = 1 - c->cur;
     c->committed = true;
     split_reset(c);
-    c->stats.total_capacity = (int64_t)acc.total_capacity;
-    c->stats.total_free = (int64_t)acc.total_free;
-    c->stats.global_lru = (int64_t)acc.global_lru;
-    c->stats.instance_count = acc.instance_count;
-    c->stats.model_copy_count = acc.model_copy_count;
+    publish_cluster_stats(c, acc);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_snapshot_commit");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_snapshot_commit", e.what());
-}
+} MMP_CATCH(c, "mmp_snapshot_commit")
 
 int mmp_delta_commits(mmp_ctx *c, int64_t *n_out)
 {
@@ -2129,11 +2225,7 @@ try {
     if (n) HIP_TRY(c, copy_sync(c, order_out, c->snap.orig, (size_t)n * 4, hipMemcpyDeviceToHost));
     *n_out = n;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_get_order");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_get_order", e.what());
-}
+} MMP_CATCH(c, "mmp_get_order")
 
 int mmp_shortlists(mmp_ctx *c, mmp_shortlist_row *rows, int32_t cap_rows, int32_t *n_rows_out)
 try {
@@ -2151,11 +2243,7 @@ try {
     }
     *n_rows_out = 2 * nt;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shortlists");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shortlists", e.what());
-}
+} MMP_CATCH(c, "mmp_shortlists")
 
 int mmp_long_shortlists(mmp_ctx *c, mmp_shortlist_row *rows, int32_t cap_rows, int32_t *n_rows_out)
 try {
@@ -2174,11 +2262,7 @@ try {
     }
     *n_rows_out = 2 * nt;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_long_shortlists");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_long_shortlists", e.what());
-}
+} MMP_CATCH(c, "mmp_long_shortlists")
 
 int mmp_split_batches(mmp_ctx *c, int64_t *n_split_out, int32_t *off_out)
 {
@@ -2196,11 +2280,7 @@ try {
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     *out = c->stats;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_cluster_stats");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_cluster_stats", e.what());
-}
+} MMP_CATCH(c, "mmp_cluster_stats")
 
 namespace {
 mmp_stats stats_of(const StatsAcc &a)
@@ -2223,11 +2303,7 @@ try {
     const int32_t T = (int32_t)cur_side(c).tstats_h.size();
     *out = stats_of(cur_side(c).tstats_h[(type < 0 || type >= T) ? 0 : type]);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_type_stats");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_type_stats", e.what());
-}
+} MMP_CATCH(c, "mmp_type_stats")
 
 int mmp_partition_count(mmp_ctx *c, int32_t *n_out)
 try {
@@ -2236,11 +2312,7 @@ try {
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     *n_out = cur_side(c).n_pts;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_partition_count");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_partition_count", e.what());
-}
+} MMP_CATCH(c, "mmp_partition_count")
 
 int mmp_partition_stats(mmp_ctx *c, int32_t partition, mmp_stats *out, uint64_t *prohibited_out, int32_t max_words)
 try {
@@ -2253,11 +2325,7 @@ try {
     for (int32_t w = 0; w < max_words; w++)
         prohibited_out[w] = w < cur_side(c).pts_tw ? cur_side(c).pts_prohib[(size_t)partition * cur_side(c).pts_tw + w] : 0;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_partition_stats");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_partition_stats", e.what());
-}
+} MMP_CATCH(c, "mmp_partition_stats")
 
 int mmp_pod_partitions(mmp_ctx *c, int32_t *partition_out, int32_t max_pods, int32_t *n_out)
 try {
@@ -2269,11 +2337,7 @@ try {
     const int32_t m = std::min(*n_out, max_pods);
     if (m > 0) memcpy(partition_out, cur_side(c).pts_of.data(), (size_t)m * 4);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pod_partitions");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pod_partitions", e.what());
-}
+} MMP_CATCH(c, "mmp_pod_partitions")
 
 /* ---- wire-format ingestion (§8f-1) ------------------------------------------ */
 
@@ -2364,11 +2428,7 @@ try {
     if (id_order_out && n_pods) memcpy(id_order_out, c->id_order_v.data(), (size_t)n_pods * 4);
     if (replica_set_out && n_pods) memcpy(replica_set_out, c->replica_set_v.data(), (size_t)n_pods * 4);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pod_ids_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pod_ids_load", e.what());
-}
+} MMP_CATCH(c, "mmp_pod_ids_load")
 
 int mmp_pods_ingest_json(mmp_ctx *c, const char *buf, const int64_t *off, int32_t n, const int32_t *pod_idx,
                          const uint8_t *live, int64_t *start_time_out, int32_t *status_out)
@@ -2425,11 +2485,7 @@ try {
         if (start_time_out) start_time_out[i] = stt[i];
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pods_ingest_json");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pods_ingest_json", e.what());
-}
+} MMP_CATCH(c, "mmp_pods_ingest_json")
 
 int mmp_type_names_load(mmp_ctx *c, const char *names, const int32_t *name_off, int32_t n_types, int32_t unknown_type)
 try {
@@ -2448,11 +2504,7 @@ try {
             c->default_type = i;
     c->have_types = true;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_type_names_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_type_names_load", e.what());
-}
+} MMP_CATCH(c, "mmp_type_names_load")
 
 int mmp_models_ingest_json(mmp_ctx *c, const char *buf, const int64_t *off, int32_t n_models, int64_t *last_unload_out,
                            int32_t *status_out)
@@ -2537,11 +2589,7 @@ try {
     c->n_entries = total;
     c->ent_live = total;
     return rebuild_resolved(c);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_models_ingest_json");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_models_ingest_json", e.what());
-}
+} MMP_CATCH(c, "mmp_models_ingest_json")
 
 int mmp_pods_get(mmp_ctx *c, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out)
 try {
@@ -2551,11 +2599,7 @@ try {
     const int32_t m = std::min(*n_out, max_rows);
     if (m > 0) memcpy(rows_out, c->pods.data(), (size_t)m * sizeof(mmp_pod_row));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_pods_get");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_pods_get", e.what());
-}
+} MMP_CATCH(c, "mmp_pods_get")
 
 int mmp_models_get(mmp_ctx *c, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,
                    int32_t max_entries, int32_t *n_models_out, int32_t *n_entries_out)
@@ -2573,11 +2617,7 @@ try {
     if (e > 0 && ent_pod_out) HIP_TRY(c, copy_sync(c, ent_pod_out, c->ent_pod.p, (size_t)e * 4, hipMemcpyDeviceToHost));
     if (e > 0 && ent_time_out) HIP_TRY(c, copy_sync(c, ent_time_out, c->ent_time.p, (size_t)e * 8, hipMemcpyDeviceToHost));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_models_get");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_models_get", e.what());
-}
+} MMP_CATCH(c, "mmp_models_get")
 
 /* ---- pod-axis sharding --------------------------------- */
 
@@ -2592,11 +2632,7 @@ try {
     c->committed = false;
     c->rank_pending = false;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_configure");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_configure", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_configure")
 
 int32_t mmp_shard_xchg_slots(int32_t phase, int32_t n_shards)
 {
@@ -2632,53 +2668,19 @@ try {
         const int per = div_up(P, c->n_shards);
         const int p_lo = std::min(P, c->shard * per), p_hi = std::min(P, p_lo + per);
         if (p_hi > p_lo) {
-            const int64_t churn2 = (int64_t)((uint64_t)c->cfg.min_churn_age_ms * 2u);
-            const int64_t min_space = c->cfg.min_space_units;
             // the slice against all rows is (P / shards) x P comparator calls; from where an unsharded commit sorts (8192^2 pairs)
             // sorting the whole table is cheaper — when the comparator is a total order on it (snapshot.hpp "ranking by sorting")
-            bool versions_differ = false, full_low_lru = false, wide_count = false;
-            for (int32_t p = 0; p < P; p++) {
-                const mmp_pod_row &r = c->pods[p];
-                if (r.version != c->pods[0].version) versions_differ = true;
-                if (r.count > (1 << 30) || r.count < -(1 << 30)) wide_count = true;
-                const uint64_t d = (uint64_t)r.capacity - (uint64_t)r.used;
-                const int64_t rem = (int64_t)d > 0 ? (int64_t)d : 0;
-                if (rem < min_space && r.lru_time <= churn2) full_low_lru = true;
-            }
-            const bool sort_legal = !(versions_differ && full_low_lru) && !wide_count;
             const bool want_sort = c->tune.rank_mode == 2 || c->tune.rank_mode == 3 || (c->tune.rank_mode == 0 && (int64_t)(p_hi - p_lo) * P >= (int64_t)kRankSortMinPods * kRankSortMinPods);
-            if (want_sort && sort_legal && P >= kSampleMinPods && c->tune.rank_mode != 3) {
-                const int rc = rank_by_sampling(c, B.pods.as<mmp_pod_row>(), P, min_space, churn2, p_lo, p_hi, static_cast<int32_t *>(d_rank), st);
-                if (rc != MMP_OK) return rc;
-            } else if (want_sort && sort_legal && P >= 2) {
-                HIP_TRY(c, c->rk_rows.ensure((size_t)P * sizeof(RankRow)));
-                HIP_TRY(c, c->rk_idx.ensure((size_t)P * sizeof(RankRow)));
-                const PlacementRowLess less{churn2};
-                size_t tmp_bytes = 0;
-                HIP_TRY(c, rocprim::merge_sort(nullptr, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
-                HIP_TRY(c, c->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-                hipLaunchKernelGGL(rank_rows_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(), P, min_space,
-                                   c->rk_rows.as<RankRow>());
-                HIP_TRY(c, rocprim::merge_sort(c->rk_tmp.p, tmp_bytes, c->rk_rows.as<RankRow>(), c->rk_idx.as<RankRow>(), (size_t)P, less, st));
-                hipLaunchKernelGGL(rank_from_order_range_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, c->rk_idx.as<RankRow>(), P, p_lo, p_hi,
-                                   static_cast<int32_t *>(d_rank));
-            } else {
-                const int pb = div_up(p_hi - p_lo, kRankBlock);
-                const int slices = std::max(1, std::min(64, 2048 / pb));
-                hipLaunchKernelGGL(rank_pods_kernel, dim3(pb, slices), dim3(kRankBlock), 0, st, B.pods.as<mmp_pod_row>(), P,
-                                   min_space, churn2, slices, p_lo, p_hi, static_cast<int32_t *>(d_rank));
-            }
+            const bool sort_legal = check_placement_order(c->pods, c->cfg.min_space_units, churn2_of(c)).sort_legal;
+            if (const int rc = launch_rank(c, B.pods.as<mmp_pod_row>(), P, p_lo, p_hi, true, want_sort, sort_legal, static_cast<int32_t *>(d_rank), st))
+                return rc;
             HIP_TRY(c, hipGetLastError());
         }
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     c->rank_pending = true;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_rank_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_rank_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_rank_dev")
 
 int mmp_shard_commit_dev(mmp_ctx *c, const void *d_rank)
 try {
@@ -2688,6 +2690,8 @@ try {
     if (c->n_shards < 1 || !c->rank_pending) return fail(c, MMP_ESTATE, "mmp_shard_commit_dev: call mmp_shard_rank_dev first");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, quiesce_decisions(c));
+
+    // sizes: the table's, and the slice of its words this shard owns
     const int32_t P = (int32_t)c->pods.size();
     const int32_t W = std::max(div_up(P, 64), 1);
     const int32_t Wfull = div_up(P, 64);
@@ -2698,32 +2702,17 @@ try {
     const int32_t w_lo = std::min(W, c->shard * Wl);
     const int32_t Wn = std::min(W, w_lo + Wl) - w_lo;
     const int32_t Wn1 = std::max(Wn, 1);
+    const int32_t P_local = std::max(0, std::min(P - w_lo * 64, Wn * 64));
     const size_t padded = (size_t)Wn1 * 64, padded_full = (size_t)W * 64;
+    const int64_t min_space = c->cfg.min_space_units;
+    const int32_t n_rs = (int32_t)c->replaced_rs.size();
     SnapBufs &B = c->sb[1 - c->cur];  // B.pods was filled by mmp_shard_rank_dev
     SnapSide &N = c->side[1 - c->cur];
     hipStream_t st = c->stream;
+    if (const int rc = ensure_columns(c, B, T, Wn1, W)) return rc;
+    if (const int rc = ensure_commit_scratch(c, N, T, W)) return rc;
 
-    HIP_TRY(c, B.lru.ensure(padded * 8));
-    HIP_TRY(c, B.rem.ensure(padded * 8));
-    HIP_TRY(c, B.cnt.ensure(padded * 4));
-    HIP_TRY(c, B.rpm.ensure(padded * 4));
-    HIP_TRY(c, B.orig.ensure(padded * 4));
-    HIP_TRY(c, B.pos_of.ensure(padded_full * 4));
-    HIP_TRY(c, B.elig.ensure((size_t)T * Wn1 * 8));
-    HIP_TRY(c, B.elig_nors.ensure((size_t)T * Wn1 * 8));
-    HIP_TRY(c, B.pref.ensure((size_t)T * Wn1 * 8));
-    HIP_TRY(c, B.has_pref.ensure(T));
-    HIP_TRY(c, B.fullw.ensure((size_t)Wn1 * 8));
-    HIP_TRY(c, B.ge.ensure((size_t)kGeRows * Wn1 * 8));
-    HIP_TRY(c, c->occupancy.ensure(padded_full * 4));
-    HIP_TRY(c, c->flag.ensure(sizeof(int32_t)));
-    HIP_TRY(c, N.stats_acc.ensure(sizeof(StatsAcc)));
-    HIP_TRY(c, c->rs_bad.ensure(padded_full));
-    HIP_TRY(c, c->rs_list.ensure(std::max<size_t>(c->replaced_rs.size(), 1) * 4));
-    HIP_TRY(c, N.d_allowed.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
-    HIP_TRY(c, c->d_prefer.ensure(std::max<size_t>((size_t)T * W, 1) * 8));
-    HIP_TRY(c, N.d_has_allowed.ensure(T));
-
+    // uploads, with the scratch and the slice's columns cleared
     {
         ZeroBatch zb(st);
         zb.add(c->occupancy.p, padded_full * 4);
@@ -2742,41 +2731,23 @@ try {
         zb.launch(st);
         HIP_TRY(c, hipGetLastError());
     }
-
-    std::vector<uint8_t> hp(T, 0), ha(T, 0);
-    for (int32_t t = 0; t < c->n_types; t++) {
-        hp[t] = c->has_prefer[t];
-        ha[t] = c->has_allowed[t];
-    }
-    HIP_TRY(c, hipMemcpyAsync(B.has_pref.p, hp.data(), T, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(N.d_has_allowed.p, ha.data(), T, hipMemcpyHostToDevice, st));
-    if (c->n_types > 0 && !c->allowed.empty()) {
-        HIP_TRY(c, hipMemcpyAsync(N.d_allowed.p, c->allowed.data(), c->allowed.size() * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->d_prefer.p, c->prefer.data(), c->prefer.size() * 8, hipMemcpyHostToDevice, st));
-    }
+    InputStage in;
+    if (const int rc = upload_commit_inputs(c, B, N, T, true, in, st)) return rc;
     B.types_gen = N.types_gen = c->d_prefer_gen = 0;  // (uploaded unconditionally here; "unknown" makes an ordinary commit upload again)
-    const int32_t n_rs = (int32_t)c->replaced_rs.size();
-    if (n_rs) HIP_TRY(c, hipMemcpyAsync(c->rs_list.p, c->replaced_rs.data(), (size_t)n_rs * 4, hipMemcpyHostToDevice, st));
-    const int64_t min_space = c->cfg.min_space_units;
-    StatsAcc init{};
-    init.global_lru = INT64_MAX;
-    HIP_TRY(c, hipMemcpyAsync(N.stats_acc.p, &init, sizeof init, hipMemcpyHostToDevice, st));
 
     if (P > 0) {
+        // scatter by the all-reduced ranks, then the slice's bitmaps and the cluster stats, a launch each
         hipLaunchKernelGGL(scatter_shard_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(), P,
                            static_cast<const int32_t *>(d_rank), c->occupancy.as<int32_t>(), w_lo * 64, (w_lo + Wn) * 64,
                            B.lru.as<int64_t>(), B.rem.as<int64_t>(), B.cnt.as<int32_t>(), B.rpm.as<int32_t>(),
                            B.orig.as<int32_t>(), B.pos_of.as<int32_t>(), c->flag.as<int32_t>());
-        if (n_rs)
-            hipLaunchKernelGGL(mark_replaced_kernel, dim3(div_up(P, 256)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(),
-                               P, c->rs_list.as<int32_t>(), n_rs, c->rs_bad.as<uint8_t>());
+        launch_mark_replaced(c, B, P, st);
         if (Wn > 0)
             hipLaunchKernelGGL(build_masks_shard_kernel, dim3(div_up(T * Wn, 4)), dim3(256), 0, st, B.pods.as<mmp_pod_row>(),
                                P, Wfull, w_lo, Wn, T, min_space, B.orig.as<int32_t>(), N.d_allowed.as<uint64_t>(),
                                N.d_has_allowed.as<uint8_t>(), c->d_prefer.as<uint64_t>(), B.has_pref.as<uint8_t>(),
                                n_rs ? c->rs_bad.as<uint8_t>() : nullptr, B.elig.as<uint64_t>(),
                                B.elig_nors.as<uint64_t>(), B.pref.as<uint64_t>(), B.fullw.as<uint64_t>());
-        const int32_t P_local = std::max(0, std::min(P - w_lo * 64, Wn * 64));
         if (Wn > 0)  // the count-threshold bitmaps of the slice (the lane path's count break)
             hipLaunchKernelGGL(build_ge_kernel, dim3(div_up(kGeRows * Wn, 4)), dim3(256), 0, st, B.cnt.as<int32_t>(), P_local, Wn,
                                B.ge.as<uint64_t>());
@@ -2784,64 +2755,31 @@ try {
                            B.pods.as<mmp_pod_row>(), P, min_space, N.stats_acc.as<StatsAcc>());
         HIP_TRY(c, hipGetLastError());
     }
-    {
-        const int rc = build_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, min_space, st);
-        if (rc != MMP_OK) return rc;
-    }
+    // subset stats, in one go
+    if (const int rc = stage_partitions(c, N, P, st)) return rc;
+    if (const int rc = launch_subset_stats(c, N, B.pods.as<mmp_pod_row>(), P, min_space, st)) return rc;
+    if (const int rc = fetch_subset_stats(c, N, st)) return rc;
     int32_t bad = 0;
     StatsAcc acc{};
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->flag.p, sizeof bad, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&acc, N.stats_acc.p, sizeof acc, hipMemcpyDeviceToHost, st));
+    if (const int rc = fetch_commit_result(c, N, &bad, &acc, st)) return rc;
     HIP_TRY(c, hipStreamSynchronize(st));
     c->rank_pending = false;
     if (bad)
         return fail(c, MMP_EORDER, "PLACEMENT_ORDER is not a total order on these rows; snapshot not published");
 
-    ShardSnap S{};
-    S.P = P;
-    S.W = W;
-    S.T = T;
-    S.any_rs = n_rs > 0;
-    S.min_space = min_space;
+    ShardSnap S = snap_columns<ShardSnap>(B, P, W, T, n_rs > 0, min_space);
     S.shard = c->shard;
     S.n_shards = c->n_shards;
     S.Wl = Wl;
     S.w_lo = w_lo;
     S.Wn = Wn;
-    S.lru = B.lru.as<int64_t>();
-    S.rem = B.rem.as<int64_t>();
-    S.cnt = B.cnt.as<int32_t>();
-    S.rpm = B.rpm.as<int32_t>();
-    S.orig = B.orig.as<int32_t>();
-    S.pos_of = B.pos_of.as<int32_t>();
-    S.elig = B.elig.as<uint64_t>();
-    S.elig_nors = B.elig_nors.as<uint64_t>();
-    S.pref = B.pref.as<uint64_t>();
-    S.has_pref = B.has_pref.as<uint8_t>();
-    S.fullw = B.fullw.as<uint64_t>();
     c->ssnap = S;
-    Snap V{};  // the slice as the lane-per-decision path sees it: local positions, global pos_of
-    V.P = std::max(0, std::min(P - w_lo * 64, Wn * 64));
-    V.W = Wn;
-    V.T = T;
-    V.any_rs = S.any_rs;
-    V.min_space = min_space;
-    V.lru = S.lru;
-    V.rem = S.rem;
-    V.cnt = S.cnt;
-    V.rpm = S.rpm;
-    V.orig = S.orig;
-    V.pos_of = S.pos_of;
-    V.elig = S.elig;
-    V.elig_nors = S.elig_nors;
-    V.pref = S.pref;
-    V.has_pref = S.has_pref;
-    V.fullw = S.fullw;
+    Snap V = snap_columns<Snap>(B, P_local, Wn, T, n_rs > 0, min_space);  // the slice as the lane-per-decision path sees it: local positions, global pos_of
     V.ge = B.ge.as<uint64_t>();
     V.pos_base = w_lo * 64;
     V.w_base = w_lo;
     V.more_after = (w_lo + Wn) * 64 < P ? 1 : 0;
-    Snap M{};  // what the non-placement entry points read in shard mode
+    Snap M{};  // what the non-placement entry points read in shard mode: the sizes and pos_of alone
     M.P = P;
     M.W = W;
     M.T = T;
@@ -2856,24 +2794,16 @@ try {
         HIP_TRY(c, hipMemsetAsync(B.heads.p, 0, wins_bytes, st));
         if (V.P > 0 && V.W > 0) hipLaunchKernelGGL(build_wins_kernel, dim3(T), dim3(64), 0, st, V, B.heads.as<TypeWin>());
         HIP_TRY(c, hipGetLastError());
-        const int rc = rebuild_resolved(c, N, M, true);  // (synchronizes the stream)
-        if (rc != MMP_OK) return rc;
+        if (const int rc = rebuild_resolved(c, N, M, true)) return rc;  // (synchronizes the stream)
     }
+    // publish (c->mu has been held throughout)
     c->sview = V;
     c->snap = M;
     c->cur = 1 - c->cur;
     c->committed = true;
-    c->stats.total_capacity = (int64_t)acc.total_capacity;
-    c->stats.total_free = (int64_t)acc.total_free;
-    c->stats.global_lru = (int64_t)acc.global_lru;
-    c->stats.instance_count = acc.instance_count;
-    c->stats.model_copy_count = acc.model_copy_count;
+    publish_cluster_stats(c, acc);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_commit_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_commit_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_commit_dev")
 
 namespace {
 // one phase of the general protocol on `st` (called with c->mu held); n_dev: see PlaceArgs::n_dev
@@ -2919,11 +2849,7 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     note_caller_stream(c, st);
     return shard_phase_launch(c, phase, d_reqs, n, nullptr, d_extra, now, d_xchg, d_outs, st);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_phase_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_phase_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_phase_dev")
 
 int32_t mmp_shard_fast_slots(void) { return kXF; }
 
@@ -2951,11 +2877,7 @@ try {
                        static_cast<hipStream_t>(stream), c->sview, A, c->shard, static_cast<int64_t *>(d_xf));
     HIP_TRY(c, hipGetLastError());
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_fast_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_fast_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_fast_dev")
 
 namespace {
 // After the all-reduce: the decided rows are written, the rest flagged and COUNTED; the count reaches the host through a
@@ -3065,11 +2987,7 @@ try {
         *d_rest_outs_out = c->f_outs.p;
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_fast_finish_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_fast_finish_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_fast_finish_dev")
 
 int mmp_shard_place_fast_scatter_dev(mmp_ctx *c, int32_t n_rest, void *d_outs, void *stream)
 try {
@@ -3082,11 +3000,7 @@ try {
                        c->f_outs.as<mmp_place_out>(), c->f_idx.as<int32_t>(), n_rest, static_cast<mmp_place_out *>(d_outs));
     HIP_TRY(c, hipGetLastError());
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_fast_scatter_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_fast_scatter_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_fast_scatter_dev")
 
 /* ---- RCCL inside the boundary: the pod-axis group ------------------------- */
 namespace {
@@ -3233,11 +3147,7 @@ try {
     c->g_world = world;
     c->group = true;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_group_init");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_group_init", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_group_init")
 
 int mmp_shard_group_set_exchange(mmp_ctx *c, mmp_exchange_fn fn, void *user)
 {
@@ -3290,11 +3200,7 @@ try {
     if (rc != MMP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return mmp_shard_commit_dev(c, c->g_rankbuf.p);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_commit");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_commit", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_commit")
 
 /* One batch on the pod-axis group, device pointers, collective: returns when d_outs is complete on every shard.
  * fast kernel -> ncclAllReduce(MIN, 2 int64 per decision) -> decided rows + compaction of the rest -> the six
@@ -3313,11 +3219,7 @@ try {
     if (!c || n < 0 || (n > 0 && (!d_reqs || !d_outs))) return fail(c, MMP_EINVAL, "mmp_shard_place_batch_dev: bad argument");
     std::lock_guard<std::mutex> gg(c->group_mu);
     return shard_place_batch_locked(c, d_reqs, n, d_extra, now, d_outs, n_rest_out, true);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_batch_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_batch_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_batch_dev")
 
 namespace {
 // the batch of mmp_shard_place_batch_async_dev that is still open: wait for its finish kernel, read the rest count, run the six
@@ -3418,11 +3320,7 @@ try {
     if (!c || n < 0 || (n > 0 && (!d_reqs || !d_outs))) return fail(c, MMP_EINVAL, "mmp_shard_place_batch_async_dev: bad argument");
     std::lock_guard<std::mutex> gg(c->group_mu);
     return shard_place_batch_locked(c, d_reqs, n, d_extra, now, d_outs, nullptr, false);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_batch_async_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_batch_async_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_batch_async_dev")
 
 int mmp_shard_wait(mmp_ctx *c, int32_t *n_rest_out)
 try {
@@ -3435,11 +3333,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (n_rest_out) *n_rest_out = c->last_n_rest;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_wait");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_wait", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_wait")
 
 /* The same with host pointers (what a JVM holds): staged through the context's scratch. */
 int mmp_shard_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
@@ -3466,11 +3360,7 @@ try {
     if (rc != MMP_OK) return rc;
     HIP_TRY(c, copy_sync(c, outs, c->s_outs.p, (size_t)n * sizeof(mmp_place_out), hipMemcpyDeviceToHost));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_shard_place_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_shard_place_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_shard_place_batch")
 
 /* ---- submission threads ---------------------------------------------------
  * One host thread needs ~3 us per kernel launch (HIP's launch path), which is more than a 100k-decision batch takes the
@@ -3599,11 +3489,7 @@ try {
         c->pool = P;
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_issue_threads");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_issue_threads", e.what());
-}
+} MMP_CATCH(c, "mmp_issue_threads")
 
 int mmp_issue_flush(mmp_ctx *c)
 {
@@ -3760,11 +3646,7 @@ try {
     }
     R.enabled = true;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_resident");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_resident", e.what());
-}
+} MMP_CATCH(c, "mmp_resident")
 
 int mmp_resident_stats(mmp_ctx *c, uint64_t *launches, uint64_t *served, uint64_t *punted)
 {
@@ -3823,11 +3705,7 @@ try {
         if (rc != MMP_OK) return rc;
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_multi_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_multi_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_place_multi_dev")
 
 int mmp_place_batch_dev(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int64_t now, void *d_outs,
                         void *stream)
@@ -3861,11 +3739,7 @@ try {
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
     note_caller_stream(c, static_cast<hipStream_t>(stream));
     return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream));
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_batch_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_place_batch_dev")
 
 int mmp_stream_retire(mmp_ctx *c, void *stream)
 try {
@@ -3904,11 +3778,7 @@ try {
         if (words) HIP_TRY(c, hipFree(words));
     }
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_stream_retire");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_stream_retire", e.what());
-}
+} MMP_CATCH(c, "mmp_stream_retire")
 
 int mmp_place_batch_dev2(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra, int32_t n_extra_pool, int64_t now,
                          void *d_outs, void *stream)
@@ -3923,11 +3793,7 @@ try {
     PlaceCall o;
     o.extra_bound = n_extra_pool + 1;
     return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), o);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_dev2");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_batch_dev2", e.what());
-}
+} MMP_CATCH(c, "mmp_place_batch_dev2")
 
 int mmp_place_batch_c_dev(mmp_ctx *c, const mmp_place_caller *caller, const void *d_reqs, int32_t n, const void *d_extra,
                           int32_t n_extra_pool, int64_t now, void *d_outs, void *stream)
@@ -3943,11 +3809,7 @@ try {
     o.caller = caller;
     o.extra_bound = n_extra_pool + 1;
     return place_launch(c, d_reqs, n, d_extra, now, d_outs, static_cast<hipStream_t>(stream), o);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_c_dev");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_batch_c_dev", e.what());
-}
+} MMP_CATCH(c, "mmp_place_batch_c_dev")
 
 int mmp_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
                     int64_t now, mmp_place_out *outs);
@@ -4003,11 +3865,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch_c");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_batch_c", e.what());
-}
+} MMP_CATCH(c, "mmp_place_batch_c")
 
 int mmp_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
                     int64_t now, mmp_place_out *outs)
@@ -4070,11 +3928,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_place_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_place_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_place_batch")
 
 int mmp_serve_batch(mmp_ctx *c, const mmp_serve_req *reqs, int32_t n, const mmp_serve_counter *counters, int32_t n_counters,
                     const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, int64_t now, mmp_serve_out *outs)
@@ -4171,11 +4025,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_serve_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_serve_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_serve_batch")
 
 namespace {
 GateArgs gate_args(mmp_ctx *c, int32_t n, int64_t now, int64_t in_use_expiry)
@@ -4282,11 +4132,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_gate_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_gate_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_gate_batch")
 
 int mmp_miss_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_place_req *preqs, int32_t n, const int32_t *excl_pod,
                    const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool,
@@ -4360,11 +4206,7 @@ try {
     memcpy(pouts, obase, (size_t)n * sizeof(mmp_place_out));
     memcpy(gouts, obase + kMissGoutOff, (size_t)n * sizeof(mmp_gate_out));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_miss_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_miss_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_miss_batch")
 
 int mmp_route_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_serve_req *sreqs, int32_t n, const mmp_serve_counter *counters,
                     int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
@@ -4498,21 +4340,13 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_route_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_route_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_route_batch")
 
 int mmp_proactive_plan(mmp_ctx *c, int32_t default_units, int64_t now, int32_t max_out, int32_t *out_model,
                        int64_t *out_last_used, mmp_proactive_info *info)
 try {
     return mmp_proactive_plan_subset(c, -1, nullptr, 0, default_units, now, max_out, out_model, out_last_used, info);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_proactive_plan");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_proactive_plan", e.what());
-}
+} MMP_CATCH(c, "mmp_proactive_plan")
 
 int mmp_proactive_plan_subset(mmp_ctx *c, int32_t partition, const int32_t *skip_models, int32_t n_skip, int32_t default_units,
                               int64_t now, int32_t max_out, int32_t *out_model, int64_t *out_last_used,
@@ -4667,11 +4501,7 @@ try {
     info->space_to_fill = h.space_to_fill;
     info->cutoff = h.cutoff;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_proactive_plan_subset");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_proactive_plan_subset", e.what());
-}
+} MMP_CATCH(c, "mmp_proactive_plan_subset")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
@@ -4770,11 +4600,7 @@ int mmp_scaleup_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, cons
                      mmp_scaleup_out *outs, uint8_t *overloaded_out, int32_t *skipped)
 try {
     return scaleup_plan_impl(c, "mmp_scaleup_plan", entries, nullptr, n, p, nullptr, outs, nullptr, overloaded_out, skipped, nullptr);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_scaleup_plan");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_scaleup_plan", e.what());
-}
+} MMP_CATCH(c, "mmp_scaleup_plan")
 
 int mmp_scaleup_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
                           const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs, mmp_conc_out *conc_outs,
@@ -4782,11 +4608,7 @@ int mmp_scaleup_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_
 try {
     if (!cp) return fail(c, MMP_EINVAL, "mmp_scaleup_plan_conc: conc_params is null");
     return scaleup_plan_impl(c, "mmp_scaleup_plan_conc", entries, conc, n, p, cp, outs, conc_outs, overloaded_out, skipped, result);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_scaleup_plan_conc");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_scaleup_plan_conc", e.what());
-}
+} MMP_CATCH(c, "mmp_scaleup_plan_conc")
 
 // the janitor's scale-down: the one body of mmp_scaledown_plan (conc == null) and mmp_scaledown_plan_conc
 static int scaledown_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
@@ -4847,22 +4669,14 @@ int mmp_scaledown_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, co
                        uint8_t *removed_out)
 try {
     return scaledown_plan_impl(c, "mmp_scaledown_plan", entries, nullptr, n, p, 0, removed_out);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_scaledown_plan");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_scaledown_plan", e.what());
-}
+} MMP_CATCH(c, "mmp_scaledown_plan")
 
 int mmp_scaledown_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
                             const mmp_scaledown_params *p, int64_t dynamic_rpm_scale_constant, uint8_t *removed_out)
 try {
     if (n > 0 && !conc) return fail(c, MMP_EINVAL, "mmp_scaledown_plan_conc: conc is null");
     return scaledown_plan_impl(c, "mmp_scaledown_plan_conc", entries, conc, n, p, dynamic_rpm_scale_constant, removed_out);
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_scaledown_plan_conc");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_scaledown_plan_conc", e.what());
-}
+} MMP_CATCH(c, "mmp_scaledown_plan_conc")
 
 int mmp_migration_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, int32_t self_pod, int64_t now,
                        int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out)
@@ -4892,11 +4706,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_migration_plan");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_migration_plan", e.what());
-}
+} MMP_CATCH(c, "mmp_migration_plan")
 
 /* ---- stateful keyed caches (a12 + a13) ------------------------------------- */
 
@@ -4952,11 +4762,7 @@ try {
     }
     c->k_caches = n_caches;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_caches_load_keyed");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_caches_load_keyed", e.what());
-}
+} MMP_CATCH(c, "mmp_caches_load_keyed")
 
 int mmp_cache_replay(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, int64_t now, mmp_cache_op_out *outs,
                      int32_t *evicted_keys, int32_t max_evicted, int32_t *n_evicted_slots)
@@ -5076,11 +4882,7 @@ try {
     c->ks_cur = 1 - c->ks_cur;
     *n_evicted_slots = ev_off[NC];
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_cache_replay");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_cache_replay", e.what());
-}
+} MMP_CATCH(c, "mmp_cache_replay")
 
 int mmp_cache_read(mmp_ctx *c, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *key,
                    int32_t *n_out, int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm)
@@ -5106,11 +4908,7 @@ try {
     if (weighted_size) HIP_TRY(c, copy_sync(c, weighted_size, c->k_wsize.as<int64_t>() + cache, 8, hipMemcpyDeviceToHost));
     if (ubm) HIP_TRY(c, copy_sync(c, ubm, c->k_ubm.as<mmp_ubm_state>() + cache, sizeof(mmp_ubm_state), hipMemcpyDeviceToHost));
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_cache_read");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_cache_read", e.what());
-}
+} MMP_CATCH(c, "mmp_cache_read")
 
 int mmp_caches_load(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used,
                     const int32_t *weight, const int64_t *capacity)
@@ -5138,11 +4936,7 @@ try {
     c->n_caches = n_caches;
     c->cache_entries = E;
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_caches_load");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_caches_load", e.what());
-}
+} MMP_CATCH(c, "mmp_caches_load")
 
 namespace {
 // eight lanes per evaluation while the deques are short, sixteen otherwise (aux_kernels.hpp)
@@ -5215,10 +5009,6 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     return MMP_OK;
-} catch (const std::bad_alloc &) {
-    return fail(c, MMP_ENOMEM, "%s: out of host memory", "mmp_evict_batch");
-} catch (const std::exception &e) {
-    return fail(c, MMP_EHIP, "%s: %s", "mmp_evict_batch", e.what());
-}
+} MMP_CATCH(c, "mmp_evict_batch")
 
 }  // extern "C"
