@@ -656,6 +656,79 @@ int mmp_proactive_plan_subset(mmp_ctx *ctx, int32_t partition, const int32_t *sk
                               int32_t default_model_size_units, int64_t now_ms, int32_t max_out, int32_t *out_model,
                               int64_t *out_last_used, mmp_proactive_info *info);
 
+/* The reaper's FIRST half: pruneModelRegistry (MM.java:6524-6609) with pruneMissingInstances (:6752-6784) and
+ * repairLastUsedTimeIfNeeded (:6837-6850) — one full pass over the resident registry at one clock value now_ms (> 0).  The
+ * reference runs it before triggerProactiveLoadsForInstanceSubset in every reaper run (:6459-6488): a model whose only copies
+ * sat on instances that are gone becomes a proactive-load candidate (`insts.isEmpty() && failInsts.size() < 2`, :6574) only once
+ * this pass has taken those registrations out.  So: mmp_registry_prune(MMP_PRUNE_APPLY), then mmp_proactive_plan.
+ *
+ * For every model in registry order, its loaded entries first and then its failed entries, each list in entry (TreeMap) order:
+ *   - an entry is EXAMINED unless now - time < gone_after_ms (:6761, strict) or its pod is self_pod (:6765);
+ *   - an examined entry whose pod index is < 0 or >= the pod count is UNRESOLVED (the JSON ingest's "id not in the pod table"):
+ *     never pruned, never marked, counted in n_unresolved;
+ *   - an examined entry's pod is MISSING when its slot of the instance table is a tombstone (MMP_POD_TOMBSTONE; a shutting-down
+ *     row is still in instanceInfo and therefore present, :6769-6770);
+ *   - missings.putIfAbsent(pod, now) (:6776): a pod first seen missing in this run gets since = now and nothing of it is removed;
+ *     an entry is REMOVED iff it is examined, its pod is missing, the pod had a mark before the run and now - since >
+ *     gone_after_ms (:6777, strict);
+ *   - after the pass (:6601-6606) every mark with now - since > gone_after_ms is dropped, and every mark whose pod is present;
+ *   - a record with last_used == INT64_MAX gets now - 3 * lastused_age_on_add_ms (:6843-6844), before the candidate rule reads it.
+ * The reference's constants: gone_after_ms = ASSUME_INSTANCE_GONE_AFTER_MS = 600 000, lastused_age_on_add_ms =
+ * LASTUSED_AGE_ON_ADD_MS, a run every REGISTRY_REAPER_FREQ_MINS = 7 minutes.
+ *
+ * The INSTANCE TABLE the pass reads is the one mmp_proactive_plan reads: the rows of the committed snapshot (the last
+ * mmp_snapshot_commit), not rows staged since.  A prune followed by a plan sees one table.  MMP_ESTATE before the first commit.
+ *
+ * An EDIT is what the Java hands to registry.conditionalSetAndGet (:6555) / conditionalSet (:6845): the record without the
+ * removed entries and with the repaired last_used.  Edits come in registry order, the removed entries of an edit in list order
+ * at removed_out[removed_off, removed_off + n_removed).  The compare-and-set retry against the KV store stays in Java.
+ *
+ * Not restated here: readOnlyMode (:6543-6550), loadFailureInfos (`secondary.remove`, :6779), the kv-error counter
+ * (:6583-6600), cleanLeaselessEtcdInstanceRecords (:6787), and the janitor's per-instance registry loop (:6014-6108), which
+ * needs the local cache joined in. */
+#define MMP_PRUNE_APPLY 1u /* rewrite the resident registry: rows in place (as mmp_models_upsert does), no commit needed */
+#define MMP_PRUNE_DRY 2u   /* compute everything, advance nothing: registry and missing map stay as they are (sizing, diagnostics) */
+#define MMP_PRUNE_EDIT_REPAIRED 1u
+typedef struct {
+    int32_t model;
+    int32_t n_loaded_after;
+    int32_t n_failed_after;
+    uint32_t flags;        /* bit0 (MMP_PRUNE_EDIT_REPAIRED): last_used was Long.MAX_VALUE */
+    int32_t removed_off;   /* this edit's entries in removed_out */
+    int32_t n_removed;
+    int64_t last_used_after;
+} mmp_prune_edit;
+typedef struct {
+    int32_t pod;
+    int32_t failed; /* 0: from instanceIds, 1: from loadFailedInstanceIds */
+    int64_t time;
+} mmp_prune_removed;
+typedef struct {
+    int32_t n_edits;        /* totals of the run, also when the buffers held only a prefix */
+    int32_t n_removed;
+    int32_t n_repaired;
+    int32_t n_unresolved;
+    int32_t n_missing_pods; /* marks held after the run (for a dry or truncated run: that it would hold) */
+    int32_t n_new_missing;  /* pods first seen missing in this run */
+    int32_t truncated;      /* 1: n_edits > max_edits or n_removed > max_removed */
+    int32_t reserved;
+} mmp_prune_info;
+/* flags = 0: the edits are computed and the missing map advances, the resident registry is left to the caller (who applies the
+ * records the KV store accepted through mmp_models_upsert); MMP_PRUNE_APPLY: the library also rewrites the resident registry —
+ * the surviving entries are appended to the entry arena on the device and the rows rewritten in place under the protocol of
+ * mmp_models_upsert, so decisions and plans see the edited records at once; MMP_PRUNE_DRY (alone).  When an output buffer is
+ * too small the prefix that fits and the totals are returned with truncated = 1 and NOTHING is applied or advanced, whatever
+ * the flags: the caller repeats the call with larger buffers.  Buffers may be NULL with a capacity of 0. */
+int mmp_registry_prune(mmp_ctx *ctx, int32_t self_pod, int64_t now_ms, int64_t gone_after_ms, int64_t lastused_age_on_add_ms,
+                       uint32_t flags, mmp_prune_edit *edits_out, int32_t max_edits, mmp_prune_removed *removed_out,
+                       int32_t max_removed, mmp_prune_info *info_out);
+/* The missing map (`missings`, MM.java:6776): since_out[p] = the time pod p was first seen missing, 0 = no mark; *n_out = pod
+ * slots the map covers.  Lifetime: the map is kept BY POD INDEX inside the context; it grows (unmarked) when pods are appended;
+ * it survives mmp_pods_load / _upsert / _remove, which keep the index space; mmp_pod_ids_load, which redefines the index space,
+ * clears it; mmp_registry_missing_reset is missings.clear() on a leader change (:6427, :6827). */
+int mmp_registry_missing_get(mmp_ctx *ctx, int64_t *since_out, int32_t max_pods, int32_t *n_out);
+int mmp_registry_missing_reset(mmp_ctx *ctx);
+
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for
  * MMP_SCALE_UP rows the caller passes those pods as extra excludes of the load-target decisions

@@ -93,6 +93,14 @@ final class MmPlace {
                                     ByteBuffer outLastUsed, ByteBuffer info);
     static native int proactivePlanSubset(long h, int partition, ByteBuffer skipModels, int nSkip, int defaultModelSizeUnits,
                                           long nowMs, int maxOut, ByteBuffer outModel, ByteBuffer outLastUsed, ByteBuffer info);
+    // pruneModelRegistry (MM.java:6524-6609) before the plan above: flags 1 = apply to the resident registry, 2 = dry run; editsOut =
+    // mmp_prune_edit rows (32 bytes: what goes to registry.conditionalSetAndGet), removedOut = mmp_prune_removed rows (16 bytes),
+    // info = one mmp_prune_info; info.truncated: nothing was applied, repeat with larger buffers.  registryMissingReset is
+    // missings.clear() on a leader change (MM.java:6827).
+    static native int registryPrune(long h, int selfPod, long nowMs, long goneAfterMs, long lastUsedAgeOnAddMs, int flags,
+                                    ByteBuffer editsOut, int maxEdits, ByteBuffer removedOut, int maxRemoved, ByteBuffer info);
+    static native int registryMissingGet(long h, ByteBuffer sinceOut, int maxPods, ByteBuffer nOut);
+    static native int registryMissingReset(long h);
     static native int scaleupPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer outs,
                                   ByteBuffer overloadedOut, ByteBuffer skipped);
     static native int scaledownPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer removedOut);

@@ -337,6 +337,34 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_proactivePlanSubset
                                            nowMs, maxOut, buf<int32_t>(env, outModel), buf<int64_t>(env, outLastUsed),
                                            buf<mmp_proactive_info>(env, info)));
 }
+// The reaper's first half (pruneModelRegistry, MM.java:6524-6609): the output buffers' capacities are checked here, the
+// library only knows maxEdits / maxRemoved.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryPrune(JNIEnv *env, jclass, jlong h, jint selfPod, jlong nowMs,
+                                                                           jlong goneAfterMs, jlong lastUsedAgeOnAddMs, jint flags,
+                                                                           jobject editsOut, jint maxEdits, jobject removedOut,
+                                                                           jint maxRemoved, jobject info)
+{
+    if (!holds<mmp_prune_edit>(env, editsOut, maxEdits, "registryPrune: editsOut shorter than maxEdits") ||
+        !holds<mmp_prune_removed>(env, removedOut, maxRemoved, "registryPrune: removedOut shorter than maxRemoved") ||
+        !holds<mmp_prune_info>(env, info, 1, "registryPrune: info shorter than one mmp_prune_info"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_registry_prune(ctx_of(h), selfPod, nowMs, goneAfterMs, lastUsedAgeOnAddMs, static_cast<uint32_t>(flags),
+                                    buf<mmp_prune_edit>(env, editsOut), maxEdits, buf<mmp_prune_removed>(env, removedOut), maxRemoved,
+                                    buf<mmp_prune_info>(env, info)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryMissingGet(JNIEnv *env, jclass, jlong h, jobject sinceOut,
+                                                                                jint maxPods, jobject nOut)
+{
+    if (!holds<int64_t>(env, sinceOut, maxPods, "registryMissingGet: sinceOut shorter than maxPods") ||
+        !holds<int32_t>(env, nOut, 1, "registryMissingGet: nOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_registry_missing_get(ctx_of(h), buf<int64_t>(env, sinceOut), maxPods, buf<int32_t>(env, nOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryMissingReset(JNIEnv *env, jclass, jlong h)
+{
+    return check(env, ctx_of(h), mmp_registry_missing_reset(ctx_of(h)));
+}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaleupPlan(JNIEnv *env, jclass, jlong h, jobject entries,
                                                                          jint n, jobject params, jobject outs,
                                                                          jobject overloadedOut, jobject skipped)

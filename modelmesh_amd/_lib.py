@@ -98,6 +98,15 @@ PROACTIVE_INFO = np.dtype(
      ("n_selected", "<i4"), ("error", "<i4"), ("space_to_fill", "<i8"), ("cutoff", "<i8")])
 assert PROACTIVE_INFO.itemsize == 40
 
+# mmp_registry_prune (pruneModelRegistry, MM.java:6524-6609)
+PRUNE_APPLY, PRUNE_DRY, PRUNE_EDIT_REPAIRED = 1, 2, 1
+PRUNE_EDIT = np.dtype([("model", "<i4"), ("n_loaded_after", "<i4"), ("n_failed_after", "<i4"), ("flags", "<u4"),
+                       ("removed_off", "<i4"), ("n_removed", "<i4"), ("last_used_after", "<i8")])
+PRUNE_REMOVED = np.dtype([("pod", "<i4"), ("failed", "<i4"), ("time", "<i8")])
+PRUNE_INFO = np.dtype([("n_edits", "<i4"), ("n_removed", "<i4"), ("n_repaired", "<i4"), ("n_unresolved", "<i4"),
+                       ("n_missing_pods", "<i4"), ("n_new_missing", "<i4"), ("truncated", "<i4"), ("reserved", "<i4")])
+assert PRUNE_EDIT.itemsize == 32 and PRUNE_REMOVED.itemsize == 16 and PRUNE_INFO.itemsize == 32
+
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
      ("last_unload_time", "<i8"), ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"),
@@ -200,6 +209,9 @@ SYMBOLS = [
     ("mmp_route_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     ("mmp_proactive_plan", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     ("mmp_proactive_plan_subset", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("mmp_registry_prune", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("mmp_registry_missing_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mmp_registry_missing_reset", C.c_int, [_P]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("mmp_scaleup_plan_conc", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),

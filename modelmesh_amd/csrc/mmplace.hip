@@ -36,6 +36,7 @@
 #include "ingest_kernels.hpp"
 #include "place_kernel.hpp"
 #include "rebalance_kernels.hpp"
+#include "registry_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -340,6 +341,10 @@ struct mmp_ctx {
     std::vector<int32_t> m_cnt;           // host shadow: entries per model (for the arena's garbage accounting)
     int64_t ent_live = 0;                 // entries still referenced by a row
     DevBuf u_idx, u_rows, u_cnt, u_offs, u_tmp;
+    // mmp_registry_prune: `missings` (MM.java:6776) by pod index — first time seen missing, 0 = no mark — for miss_n pod slots, and
+    // the call's scratch (registry_kernels.hpp).  Owned by batch_mu; only the prune kernels, on c->stream, touch them.
+    DevBuf miss_since, p_state, p_seen, p_ps, p_counts, p_edits, p_removed, p_koff;
+    int32_t miss_n = 0;
     std::vector<uint64_t> u_stamp;        // per model: (call generation, row index) of the last row naming it
     uint32_t u_gen = 0;
     // (the registry view resolved against a snapshot, place_kernel.hpp: ResolvedModel, lives in SnapSide)
@@ -1029,7 +1034,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -1411,6 +1416,83 @@ int compact_registry(mmp_ctx *c)
     HIP_TRY(c, q);
     return MMP_OK;
 }
+
+// Make room for `count` registry rows and `base + n_entries` arena entries (called with batch_mu, by mmp_models_upsert and by an
+// applied mmp_registry_prune, before they append entries at `base`).
+int registry_grow(mmp_ctx *c, int32_t count, int32_t base, int32_t n_entries)
+{
+    hipStream_t st = c->stream;
+    // A table that has to grow moves (the old allocation is freed): only then is the state lock needed this early.
+    const bool grows = (size_t)count * sizeof(mmp_model_row) > c->models.cap || (size_t)(base + n_entries) * 4 > c->ent_pod.cap ||
+                       (size_t)(base + n_entries) * 8 > c->ent_time.cap ||
+                       (cur_side(c).rmodels_ok && ((size_t)count * sizeof(ResolvedModel) > cur_side(c).rmodels.cap || (size_t)count * 4 > cur_side(c).mtw.cap));
+    if (grows) {  // copy-on-write (grow_cow): decisions are held off for the pointer swap only
+        DevBuf fm, fp, ft, fr, fw;
+        auto drop = [&] { fm.release(); fp.release(); ft.release(); fr.release(); fw.release(); };
+        int rc = grow_cow(c, c->models, (size_t)c->n_models * sizeof(mmp_model_row), (size_t)count * sizeof(mmp_model_row), fm);
+        if (rc == MMP_OK) rc = grow_cow(c, c->ent_pod, (size_t)base * 4, (size_t)(base + n_entries) * 4, fp);
+        if (rc == MMP_OK) rc = grow_cow(c, c->ent_time, (size_t)base * 8, (size_t)(base + n_entries) * 8, ft);
+        // (the unpublished side's view is rebuilt from the model table by the next commit)
+        if (rc == MMP_OK && cur_side(c).rmodels_ok)
+            rc = grow_cow(c, cur_side(c).rmodels, (size_t)c->n_models * sizeof(ResolvedModel), (size_t)count * sizeof(ResolvedModel), fr);
+        if (rc == MMP_OK && cur_side(c).rmodels_ok) rc = grow_cow(c, cur_side(c).mtw, (size_t)c->n_models * 4, (size_t)count * 4, fw);
+        if (rc == MMP_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, MMP_EHIP, "growing the registry tables failed");
+        if (rc != MMP_OK) {
+            drop();
+            return rc;
+        }
+        DevBuf olds[5];
+        {
+            std::lock_guard<std::shared_mutex> g(c->mu);
+            if (fm.p) { olds[0] = c->models; c->models = fm; }
+            if (fp.p) { olds[1] = c->ent_pod; c->ent_pod = fp; }
+            if (ft.p) { olds[2] = c->ent_time; c->ent_time = ft; }
+            if (fr.p) { olds[3] = cur_side(c).rmodels; cur_side(c).rmodels = fr; }
+            if (fw.p) { olds[4] = cur_side(c).mtw; cur_side(c).mtw = fw; }
+        }
+        const hipError_t q = quiesce_decisions(c);  // kernels that captured the old allocations
+        for (DevBuf &o : olds) o.release();
+        HIP_TRY(c, q);
+    }
+    return MMP_OK;
+}
+
+// The in-place rewrite of k registry rows staged in u_idx / u_rows, whose entries already stand in the arena (called with batch_mu):
+// afterwards the registry has `count` rows and `n_entries_after` arena entries.
+int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_after, bool bracket_open = false)
+{
+    hipStream_t st = c->stream;
+    {
+        // Rows (and their resolved positions) are rewritten in place.  Under the state lock: the decisions in flight drain, the
+        // rewrite kernel is ENQUEUED and an event recorded behind it; decisions launched from now on order themselves behind that
+        // event on the device (order_after_registry).  The lock is not held while the kernel runs.
+        std::lock_guard<std::shared_mutex> g(c->mu);
+        HIP_TRY(c, quiesce_decisions(c));
+        const bool resolved = cur_side(c).rmodels_ok && c->committed;
+        if (!bracket_open) KT_BEGIN(c, st);  // (an applied prune opened the bracket in front of its build kernel)
+        hipLaunchKernelGGL(upsert_models_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, c->snap, c->u_idx.as<int32_t>(),
+                           c->u_rows.as<mmp_model_row>(), k, c->ent_pod.as<int32_t>(), c->models.as<mmp_model_row>(),
+                           resolved ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr, resolved ? cur_side(c).mtw.as<int32_t>() : nullptr);
+        KT_END(c, st);
+        // From here on the rewrite may be running.  Nothing may leave this block with the lock released, the rewrite enqueued
+        // and no way for later decisions to order themselves behind it: a launch or event error drains the stream first, and
+        // the new counts are published only once the event stands.
+        hipError_t le = hipGetLastError();
+        if (le == hipSuccess) le = hipEventRecord(c->reg_event, st);
+        if (le != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            HIP_TRY(c, le);
+        }
+        c->reg_pending.store(true, std::memory_order_release);
+        c->n_models = count;
+        c->n_entries = n_entries_after;
+    }
+    const hipError_t se = hipStreamSynchronize(st);
+    if (se == hipSuccess) c->reg_pending.store(false, std::memory_order_release);  // (a failed wait leaves later launches ordered behind the event)
+    HIP_TRY(c, se);
+    kt_collect(c);
+    return MMP_OK;
+}
 }  // namespace
 
 int mmp_models_upsert(mmp_ctx *c, const int32_t *idx, const mmp_model_row *rows, int32_t n, const int32_t *ent_pod,
@@ -1459,38 +1541,7 @@ try {
         c->ent_live += (int64_t)(rows[i].n_loaded + rows[i].n_failed) - c->m_cnt[idx[i]];
         c->m_cnt[idx[i]] = rows[i].n_loaded + rows[i].n_failed;
     }
-    // A table that has to grow moves (the old allocation is freed): only then is the state lock needed this early.
-    const bool grows = (size_t)count * sizeof(mmp_model_row) > c->models.cap || (size_t)(base + n_entries) * 4 > c->ent_pod.cap ||
-                       (size_t)(base + n_entries) * 8 > c->ent_time.cap ||
-                       (cur_side(c).rmodels_ok && ((size_t)count * sizeof(ResolvedModel) > cur_side(c).rmodels.cap || (size_t)count * 4 > cur_side(c).mtw.cap));
-    if (grows) {  // copy-on-write (grow_cow): decisions are held off for the pointer swap only
-        DevBuf fm, fp, ft, fr, fw;
-        auto drop = [&] { fm.release(); fp.release(); ft.release(); fr.release(); fw.release(); };
-        int rc = grow_cow(c, c->models, (size_t)c->n_models * sizeof(mmp_model_row), (size_t)count * sizeof(mmp_model_row), fm);
-        if (rc == MMP_OK) rc = grow_cow(c, c->ent_pod, (size_t)base * 4, (size_t)(base + n_entries) * 4, fp);
-        if (rc == MMP_OK) rc = grow_cow(c, c->ent_time, (size_t)base * 8, (size_t)(base + n_entries) * 8, ft);
-        // (the unpublished side's view is rebuilt from the model table by the next commit)
-        if (rc == MMP_OK && cur_side(c).rmodels_ok)
-            rc = grow_cow(c, cur_side(c).rmodels, (size_t)c->n_models * sizeof(ResolvedModel), (size_t)count * sizeof(ResolvedModel), fr);
-        if (rc == MMP_OK && cur_side(c).rmodels_ok) rc = grow_cow(c, cur_side(c).mtw, (size_t)c->n_models * 4, (size_t)count * 4, fw);
-        if (rc == MMP_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_models_upsert: growing the registry tables failed");
-        if (rc != MMP_OK) {
-            drop();
-            return rc;
-        }
-        DevBuf olds[5];
-        {
-            std::lock_guard<std::shared_mutex> g(c->mu);
-            if (fm.p) { olds[0] = c->models; c->models = fm; }
-            if (fp.p) { olds[1] = c->ent_pod; c->ent_pod = fp; }
-            if (ft.p) { olds[2] = c->ent_time; c->ent_time = ft; }
-            if (fr.p) { olds[3] = cur_side(c).rmodels; cur_side(c).rmodels = fr; }
-            if (fw.p) { olds[4] = cur_side(c).mtw; cur_side(c).mtw = fw; }
-        }
-        const hipError_t q = quiesce_decisions(c);  // kernels that captured the old allocations
-        for (DevBuf &o : olds) o.release();
-        HIP_TRY(c, q);
-    }
+    if (const int rc = registry_grow(c, count, base, n_entries)) return rc;
     HIP_TRY(c, c->u_idx.ensure((size_t)k * 4));
     HIP_TRY(c, c->u_rows.ensure((size_t)k * sizeof(mmp_model_row)));
     if (n_entries) {
@@ -1500,35 +1551,7 @@ try {
     HIP_TRY(c, hipMemcpyAsync(c->u_idx.p, h_idx.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->u_rows.p, h_rows.data(), (size_t)k * sizeof(mmp_model_row), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipStreamSynchronize(st));  // the pageable sources above are this call's stack / the caller's arrays
-    {
-        // Rows (and their resolved positions) are rewritten in place.  Under the state lock: the decisions in flight drain, the
-        // rewrite kernel is ENQUEUED and an event recorded behind it; decisions launched from now on order themselves behind that
-        // event on the device (order_after_registry).  The lock is not held while the kernel runs.
-        std::lock_guard<std::shared_mutex> g(c->mu);
-        HIP_TRY(c, quiesce_decisions(c));
-        const bool resolved = cur_side(c).rmodels_ok && c->committed;
-        KT_BEGIN(c, st);
-        hipLaunchKernelGGL(upsert_models_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, c->snap, c->u_idx.as<int32_t>(),
-                           c->u_rows.as<mmp_model_row>(), k, c->ent_pod.as<int32_t>(), c->models.as<mmp_model_row>(),
-                           resolved ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr, resolved ? cur_side(c).mtw.as<int32_t>() : nullptr);
-        KT_END(c, st);
-        // From here on the rewrite may be running.  Nothing may leave this block with the lock released, the rewrite enqueued
-        // and no way for later decisions to order themselves behind it: a launch or event error drains the stream first, and
-        // the new counts are published only once the event stands.
-        hipError_t le = hipGetLastError();
-        if (le == hipSuccess) le = hipEventRecord(c->reg_event, st);
-        if (le != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            HIP_TRY(c, le);
-        }
-        c->reg_pending.store(true, std::memory_order_release);
-        c->n_models = count;
-        c->n_entries = base + n_entries;
-    }
-    const hipError_t se = hipStreamSynchronize(st);
-    if (se == hipSuccess) c->reg_pending.store(false, std::memory_order_release);  // (a failed wait leaves later launches ordered behind the event)
-    HIP_TRY(c, se);
-    kt_collect(c);
+    if (const int rc = registry_rewrite(c, k, count, base + n_entries)) return rc;
     // more garbage than live entries (and enough to matter): squeeze the arena
     if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
     return MMP_OK;
@@ -2425,6 +2448,7 @@ try {
         c->pods[i].replica_set = c->replica_set_v[i];
     }
     c->have_ids = true;
+    c->miss_n = 0;  // the index space is redefined: marks kept by pod index mean nothing any more (mmp_registry_missing_get)
     if (id_order_out && n_pods) memcpy(id_order_out, c->id_order_v.data(), (size_t)n_pods * 4);
     if (replica_set_out && n_pods) memcpy(replica_set_out, c->replica_set_v.data(), (size_t)n_pods * 4);
     return MMP_OK;
@@ -4502,6 +4526,140 @@ try {
     info->cutoff = h.cutoff;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_proactive_plan_subset")
+
+namespace {
+// the missing map covers at least n slots; new slots carry no mark (called with batch_mu)
+int missing_cover(mmp_ctx *c, int32_t n)
+{
+    if (n <= c->miss_n) return MMP_OK;
+    if (const int rc = grow_keep(c, c->miss_since, (size_t)c->miss_n * 8, (size_t)n * 8)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->miss_since.as<int64_t>() + c->miss_n, 0, (size_t)(n - c->miss_n) * 8, c->stream));
+    c->miss_n = n;
+    return MMP_OK;
+}
+}  // namespace
+
+int mmp_registry_prune(mmp_ctx *c, int32_t self_pod, int64_t now, int64_t gone_after, int64_t age_on_add, uint32_t flags,
+                       mmp_prune_edit *edits_out, int32_t max_edits, mmp_prune_removed *removed_out, int32_t max_removed,
+                       mmp_prune_info *info)
+try {
+    if (!c || !info || max_edits < 0 || max_removed < 0 || (max_edits > 0 && !edits_out) || (max_removed > 0 && !removed_out) || now <= 0 ||
+        gone_after < 0 || age_on_add < 0 || (flags & ~(MMP_PRUNE_APPLY | MMP_PRUNE_DRY)) || flags == (MMP_PRUNE_APPLY | MMP_PRUNE_DRY))
+        return fail(c, MMP_EINVAL, "mmp_registry_prune: bad argument");
+    // batch_mu owns c->stream, the scratch and the missing map for the whole call, and every writer of the state this call reads
+    // (commit, the loaders, registry events) takes it too.  The state lock is taken only by an apply, for its in-place rewrite.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_registry_prune: not available on a pod-axis shard context");
+    const bool apply = flags & MMP_PRUNE_APPLY, dry = flags & MMP_PRUNE_DRY;
+    // an apply appends at most the live entries to the arena: refused before anything advances
+    if (apply && (int64_t)c->n_entries + c->ent_live > INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_registry_prune: entry arena overflow; reload the registry");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int32_t M = c->n_models, P = c->snap.P;
+    const int nb = div_up(M, kPruneBlock);
+    const int32_t cap_e = std::min(max_edits, M), cap_r = std::min(max_removed, c->n_entries);  // (a run has no more than these)
+    if (const int rc = missing_cover(c, P)) return rc;
+    const int32_t n_map = c->miss_n;
+    HIP_TRY(c, c->p_state.ensure((size_t)std::max(P, 1)));
+    HIP_TRY(c, c->p_seen.ensure((size_t)std::max(P, 1)));
+    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->p_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
+    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_prune_edit)));
+    HIP_TRY(c, c->p_removed.ensure((size_t)std::max(cap_r, 1) * sizeof(mmp_prune_removed)));
+    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    PruneArgs A{};
+    A.self_pod = self_pod;
+    A.P = P;
+    A.now = now;
+    A.gone_after = gone_after;
+    A.repaired_last_used = (int64_t)((uint64_t)now - 3ull * (uint64_t)age_on_add);  // :6844
+    const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what mmp_proactive_plan reads
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    PruneScalars *ps = c->p_ps.as<PruneScalars>();
+    uint8_t *state = c->p_state.as<uint8_t>(), *seen = c->p_seen.as<uint8_t>();
+    int64_t *since = c->miss_since.as<int64_t>();
+    // the marks advance with the scan only when nothing can fail afterwards: always without an apply, and with an apply that
+    // finds no edit (an apply with edits advances them once the registry has been rewritten)
+    const int32_t advance = dry ? kMarksKeep : apply ? kMarksIfNoEdits : kMarksAdvance;
+    KT_BEGIN(c, st);  // device span of the scan
+    hipLaunchKernelGGL(prune_pods_kernel, dim3(std::max(div_up(P, 256), 1)), dim3(256), 0, st, pods, A, since, state, seen, ps);
+    if (nb > 0) {
+        hipLaunchKernelGGL(prune_count_kernel, dim3(nb), dim3(kPruneBlock), 0, st, models, M, c->ent_pod.as<int32_t>(),
+                           c->ent_time.as<int64_t>(), A, state, seen, c->p_counts.as<int32_t>(), ps);
+        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, max_edits, max_removed, ps);
+        hipLaunchKernelGGL(prune_scatter_kernel, dim3(nb), dim3(kPruneBlock), 0, st, models, M, c->ent_pod.as<int32_t>(),
+                           c->ent_time.as<int64_t>(), A, state, c->p_counts.as<int32_t>(), ps, c->p_edits.as<mmp_prune_edit>(), cap_e,
+                           c->p_removed.as<mmp_prune_removed>(), cap_r, c->p_koff.as<int32_t>());
+    }
+    hipLaunchKernelGGL(prune_marks_kernel, dim3(std::max(div_up(n_map, 256), 1)), dim3(256), 0, st, A, n_map, state, seen, since, advance, ps);
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    PruneScalars h{};
+    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const int32_t ne = std::min(h.n_edits, max_edits), nr = std::min(h.n_removed, max_removed);
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_prune_edit), hipMemcpyDeviceToHost));
+    if (nr > 0) HIP_TRY(c, copy_sync(c, removed_out, c->p_removed.p, (size_t)nr * sizeof(mmp_prune_removed), hipMemcpyDeviceToHost));
+    info->n_edits = h.n_edits;
+    info->n_removed = h.n_removed;
+    info->n_repaired = h.n_repaired;
+    info->n_unresolved = h.n_unresolved;
+    info->n_missing_pods = h.n_missing_pods;
+    info->n_new_missing = h.n_new_missing;
+    info->truncated = h.truncated;
+    info->reserved = 0;
+    if (!apply || h.truncated || h.n_edits == 0) return MMP_OK;
+
+    // apply: the surviving entries of the edited records are appended to the arena ON THE DEVICE, beyond anything a published row
+    // refers to; then the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
+    const double scan_ms = c->last_kernel_ms;
+    const int32_t E = h.n_edits, base = c->n_entries;
+    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(prune_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_prune_edit>(), c->p_koff.as<int32_t>(), E,
+                       c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept, A, state,
+                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
+    if (c->prof && scan_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += scan_ms;  // the call's device span: scan + apply
+    for (int32_t e = 0; e < E; e++) c->m_cnt[edits_out[e].model] -= edits_out[e].n_removed;
+    c->ent_live -= h.n_removed;
+    // the registry holds the edited records: now the marks advance
+    hipLaunchKernelGGL(prune_marks_kernel, dim3(std::max(div_up(n_map, 256), 1)), dim3(256), 0, st, A, n_map, state, seen, since, kMarksAdvance, ps);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    // more garbage than live entries (and enough to matter): squeeze the arena
+    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_prune")
+
+int mmp_registry_missing_get(mmp_ctx *c, int64_t *since_out, int32_t max_pods, int32_t *n_out)
+try {
+    if (!c || !n_out || max_pods < 0 || (max_pods > 0 && !since_out)) return fail(c, MMP_EINVAL, "mmp_registry_missing_get: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    *n_out = c->miss_n;
+    const int32_t n = std::min(c->miss_n, max_pods);
+    if (n > 0) HIP_TRY(c, copy_sync(c, since_out, c->miss_since.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_missing_get")
+
+int mmp_registry_missing_reset(mmp_ctx *c)
+try {
+    if (!c) return fail(c, MMP_EINVAL, "mmp_registry_missing_reset: null context");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (c->miss_n > 0) {
+        HIP_TRY(c, hipMemsetAsync(c->miss_since.p, 0, (size_t)c->miss_n * 8, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_missing_reset")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

@@ -559,6 +559,56 @@ class Solver:
         n = min(int(info[0]["n_selected"]), max_out)
         return om[:n].copy(), ol[:n].copy(), info[0]
 
+    def prune_registry(self, self_pod: int, now: int, gone_after_ms: int = 600_000, lastused_age_on_add_ms: int = 3_600_000,
+                       apply: bool = True, dry: bool = False, max_edits: int = 1024, max_removed: int = 4096):
+        """The reaper's first half (pruneModelRegistry, MM.java:6524-6609): (edits, removed, info).  The buffers start at
+        max_edits / max_removed and are regrown to the run's totals when it reports `truncated` (a truncated run changes nothing)."""
+        from ._lib import PRUNE_APPLY, PRUNE_DRY, PRUNE_EDIT, PRUNE_INFO, PRUNE_REMOVED
+        flags = PRUNE_DRY if dry else (PRUNE_APPLY if apply else 0)
+        info = np.zeros(1, dtype=PRUNE_INFO)
+        while True:
+            edits = np.zeros(max(max_edits, 1), dtype=PRUNE_EDIT)
+            removed = np.zeros(max(max_removed, 1), dtype=PRUNE_REMOVED)
+            self._ck(self.lib.mmp_registry_prune(self.h, int(self_pod), int(now), int(gone_after_ms), int(lastused_age_on_add_ms),
+                                                 flags, ptr(edits), int(max_edits), ptr(removed), int(max_removed), ptr(info)))
+            if not info[0]["truncated"]:
+                break
+            max_edits, max_removed = max(max_edits, int(info[0]["n_edits"])), max(max_removed, int(info[0]["n_removed"]))
+        ne, nr = int(info[0]["n_edits"]), int(info[0]["n_removed"])
+        if flags == PRUNE_APPLY and ne and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return edits[:ne].copy(), removed[:nr].copy(), info[0].copy()
+
+    def prune_registry_raw(self, self_pod, now, gone_after_ms, lastused_age_on_add_ms, flags, max_edits, max_removed):
+        """One mmp_registry_prune call with exactly these capacities: (edits prefix, removed prefix, info)."""
+        from ._lib import PRUNE_EDIT, PRUNE_INFO, PRUNE_REMOVED
+        info = np.zeros(1, dtype=PRUNE_INFO)
+        edits = np.zeros(max(max_edits, 1), dtype=PRUNE_EDIT)
+        removed = np.zeros(max(max_removed, 1), dtype=PRUNE_REMOVED)
+        self._ck(self.lib.mmp_registry_prune(self.h, int(self_pod), int(now), int(gone_after_ms), int(lastused_age_on_add_ms), int(flags),
+                                             ptr(edits) if max_edits else None, int(max_edits), ptr(removed) if max_removed else None,
+                                             int(max_removed), ptr(info)))
+        return (edits[: min(max_edits, int(info[0]["n_edits"]))].copy(), removed[: min(max_removed, int(info[0]["n_removed"]))].copy(),
+                info[0].copy())
+
+    def missing_instances(self) -> dict:
+        """`missings` (MM.java:6776) by pod index: {pod: first time seen missing}."""
+        n = C.c_int32(0)
+        self._ck(self.lib.mmp_registry_missing_get(self.h, None, 0, C.byref(n)))
+        since = np.zeros(max(n.value, 1), np.int64)
+        self._ck(self.lib.mmp_registry_missing_get(self.h, ptr(since), n.value, C.byref(n)))
+        return {int(p): int(since[p]) for p in np.nonzero(since[: n.value])[0]}
+
+    def missing_slots(self) -> int:
+        """Pod slots the missing map covers."""
+        n = C.c_int32(0)
+        self._ck(self.lib.mmp_registry_missing_get(self.h, None, 0, C.byref(n)))
+        return n.value
+
+    def reset_missing_instances(self):
+        """missings.clear() on a leader change (MM.java:6827)."""
+        self._ck(self.lib.mmp_registry_missing_reset(self.h))
+
     def scaleup_plan(self, entries, params):
         """a15: (outs, overloaded[P], skipped)"""
         from ._lib import CACHE_ENTRY, SCALEUP_OUT, SCALEUP_PARAMS
