@@ -684,8 +684,8 @@ int mmp_proactive_plan_subset(mmp_ctx *ctx, int32_t partition, const int32_t *sk
  * at removed_out[removed_off, removed_off + n_removed).  The compare-and-set retry against the KV store stays in Java.
  *
  * Not restated here: readOnlyMode (:6543-6550), loadFailureInfos (`secondary.remove`, :6779), the kv-error counter
- * (:6583-6600), cleanLeaselessEtcdInstanceRecords (:6787), and the janitor's per-instance registry loop (:6014-6108), which
- * needs the local cache joined in. */
+ * (:6583-6600) and cleanLeaselessEtcdInstanceRecords (:6787).  (The janitor's per-instance registry loop, :6014-6108, which
+ * needs the local cache joined in, is mmp_janitor_plan.) */
 #define MMP_PRUNE_APPLY 1u /* rewrite the resident registry: rows in place (as mmp_models_upsert does), no commit needed */
 #define MMP_PRUNE_DRY 2u   /* compute everything, advance nothing: registry and missing map stay as they are (sizing, diagnostics) */
 #define MMP_PRUNE_EDIT_REPAIRED 1u
@@ -728,6 +728,122 @@ int mmp_registry_prune(mmp_ctx *ctx, int32_t self_pod, int64_t now_ms, int64_t g
  * clears it; mmp_registry_missing_reset is missings.clear() on a leader change (:6427, :6827). */
 int mmp_registry_missing_get(mmp_ctx *ctx, int64_t *since_out, int32_t max_pods, int32_t *n_out);
 int mmp_registry_missing_reset(mmp_ctx *ctx);
+
+/* a16': what every instance's janitorTask does BEFORE the scale-down of copies — the CACHE LOOP (MM.java:5892-6008) and the
+ * REGISTRY LOOP (:6014-6108) — joined against the resident registry at one clock value params->now (> 0).  The output feeds
+ * mmp_scaledown_plan / _conc: the candidates are scaleCopiesCandidates (:6017) as complete mmp_cache_entry rows, oldest first.
+ *
+ * INPUT: one mmp_janitor_entry per local cache entry in runtimeCache.descendingMap() order (most recently used first), without
+ * the unload-buffer entry (:5893-5895).  A model appears in at most one row (the cache is keyed by model id); a duplicate, or a
+ * model index outside [-1, n_models), is MMP_EINVAL with nothing changed.  params->self_pod is a row of the committed instance
+ * table (its id_order places an inserted entry).  MMP_ESTATE before the first commit.
+ *
+ * CACHE LOOP, per row in order:
+ *   - skipped unless MMP_JE_DONE (:5905) and last_used > 0 (:5910);
+ *   - last_used == INT64_MAX: the entry is repaired to now - 3 * lastused_age_on_add_ms, the record too if its last_used is
+ *     INT64_MAX (:5924-5927), and THE RUN RETURNS (:5929): no later row is looked at, the registry loop does not run, there
+ *     are no candidates.  info.stopped_at is that row;
+ *   - now - last_used < janitor_freq_secs * 2000 + load_timeout_ms (strict, :5933): only the stale-lastUsed refresh
+ *     (:6165-6181: when last_used - record.last_used >= min_stale_age_ms, never for INT64_MAX; updateLastUsed only raises);
+ *   - otherwise the registry's timestamp for self_pod is compared with the entry's — loadFailedInstanceIds and
+ *     load_complete_timestamp for a MMP_JE_FAILED entry, instanceIds and load_timestamp otherwise (:5950-5953).  Equal: the
+ *     refresh, done.  Else, when model == -1, or not MMP_JE_STATE_LIVE, or age(last_unload_attempt_time) <
+ *     unload_attempt_recent_ms with age(0) == 0 (:5968-5969, :4162): the entry is REMOVED from the cache.  Else it is
+ *     REGISTERED (:5980-5982): instanceIds.put(self_pod, load_timestamp), removeLoadFailure(self_pod),
+ *     updateLastUsed(last_used); MMP_JANITOR_EDIT_TIMESTAMP_MISMATCH says a different load timestamp stood there (:5990).
+ * REGISTRY LOOP, per model in registry order, on the records AS THE CACHE LOOP LEFT THEM.  The entry it finds is the snapshot's
+ * (:5892, :6034): a row the cache loop removed is still found and its FAILED bit read, but getLastUsedTime gives -1 for it.
+ *   - remLoaded = loaded && (no row || FAILED) (:6039); updateLastUnloadTime gives 0 when at most two copies are left after
+ *     the removal, else now (ModelRecord.java:260-262) — the model row has no such field, the edit reports it;
+ *   - remFailed (:6041-6053): the entry is not FAILED, or now - failedTime > expiry (strict), expiry being
+ *     load_failure_expiry_ms / 2 when lastUsed > 0 && now - lastUsed < short_expiry_recent_use_ms, else load_failure_expiry_ms;
+ *   - updateLastUsed(lastUsed) when either holds, a row exists and lastUsed > 0 (:6066-6073);
+ *   - an expired failure record's FAILED entry also leaves the cache (:6089-6091);
+ *   - loaded && !remLoaded with lastUsed > 0 is a CANDIDATE (:6092-6099).  The TreeSet compares the time alone (VALUE_COMP,
+ *     :6875-6881): a second candidate with an equal time is dropped, the first in registry order stays (info.n_ties).
+ *
+ * WHERE A REGISTERED ENTRY GOES: instanceIds is in id order.  Where self_pod already stands its time is replaced in place;
+ * otherwise it goes in front of the first RESOLVED entry (0 <= pod < pod count) whose id_order is greater, at the end if there
+ * is none.  Entries with an unresolved pod keep their place and are never compared.
+ *
+ * OUTPUT: per input row one action byte — the LAST thing the run did to it; one EDIT per record that changes, in registry
+ * order, as registry.conditionalSetAndGet would receive it last (the compare-and-set retry against the KV store stays in
+ * Java); the candidates with the index of their input row beside them. */
+#define MMP_JE_DONE 1u       /* ce.isDone()                               */
+#define MMP_JE_FAILED 2u     /* ce.isFailed()                             */
+#define MMP_JE_STATE_LIVE 4u /* CacheEntry.LOADING <= ce.state <= ACTIVE  */
+typedef struct {
+    int32_t model;                   /* registry row, -1 if registry.get(modelId) == null */
+    int32_t weight;                  /* ce.getWeight()                                    */
+    int64_t last_used;               /* runtimeCache.getLastUsedTime(modelId); may be INT64_MAX */
+    int64_t load_timestamp;          /* ce.loadTimestamp                                  */
+    int64_t load_complete_timestamp; /* ce.loadCompleteTimestamp                          */
+    int64_t last_unload_attempt_time; /* ce.lastUnloadAttemptTime (-1: never, 0 reads as "now") */
+    int64_t interval_count;          /* these five pass through into the candidate row    */
+    int64_t last_heavy_time;
+    int64_t last_unload_time;
+    int32_t earlier_use_iteration;
+    int32_t last_used_iteration;
+    uint32_t flags;                  /* MMP_JE_*                                          */
+    int32_t reserved;
+} mmp_janitor_entry; /* 80 bytes */
+typedef struct {
+    int32_t self_pod;
+    int32_t shutting_down;              /* != 0: the run does nothing (:5880)                              */
+    int64_t now;
+    int64_t janitor_freq_secs;          /* LOCAL_JANITOR_FREQ_SECS = 360                                   */
+    int64_t load_timeout_ms;
+    int64_t min_stale_age_ms;           /* drawn once per mesh: 6 h + up to 1 h (:6162)                    */
+    int64_t load_failure_expiry_ms;     /* LOAD_FAILURE_EXPIRY_MS = 900 000; in use: half of it (:221)     */
+    int64_t short_expiry_recent_use_ms; /* SHORT_EXPIRY_RECENT_USE_TIME_MS = 180 000                       */
+    int64_t unload_attempt_recent_ms;   /* 600 000 (:1865)                                                 */
+    int64_t lastused_age_on_add_ms;     /* LASTUSED_AGE_ON_ADD_MS                                          */
+} mmp_janitor_params; /* 72 bytes */
+#define MMP_JANITOR_NONE 0       /* skipped, recently used, or not reached                     */
+#define MMP_JANITOR_REPAIRED 1   /* INT64_MAX repaired; the run stopped here                   */
+#define MMP_JANITOR_REFRESHED 2  /* the record's stale lastUsed was refreshed                  */
+#define MMP_JANITOR_IN_ORDER 3   /* timestamps equal, nothing to do                            */
+#define MMP_JANITOR_REMOVED 4    /* removed from the cache by the cache loop (:5970)           */
+#define MMP_JANITOR_REGISTERED 5 /* left in the cache, the record updated (:5980)              */
+#define MMP_JANITOR_EXPIRED 6    /* its failure record expired, removed from the cache (:6091) */
+#define MMP_JANITOR_EDIT_REGISTERED 1u
+#define MMP_JANITOR_EDIT_TIMESTAMP_MISMATCH 2u
+#define MMP_JANITOR_EDIT_REM_LOADED 4u
+#define MMP_JANITOR_EDIT_REM_FAILED 8u
+#define MMP_JANITOR_EDIT_TOUCHED 16u    /* updateLastUsed raised last_used                 */
+#define MMP_JANITOR_EDIT_REPAIRED 32u   /* the record's last_used was INT64_MAX            */
+#define MMP_JANITOR_EDIT_UNLOAD_SET 64u /* last_unload_after is to be stored               */
+typedef struct {
+    int32_t model;
+    int32_t n_loaded_after;
+    int32_t n_failed_after;
+    uint32_t flags;            /* MMP_JANITOR_EDIT_*                                                              */
+    int64_t last_used_after;
+    int64_t last_unload_after; /* with MMP_JANITOR_EDIT_UNLOAD_SET: 0 or now                                      */
+    int64_t inserted_time;     /* with MMP_JANITOR_EDIT_REGISTERED: (self_pod, load_timestamp) was put, and stands */
+    int32_t inserted_pos;      /*   at this place of instanceIds after the edit; -1: none, or taken out again     */
+    int32_t entry;             /* the model's input row, -1 if it has none                                        */
+} mmp_janitor_edit; /* 48 bytes */
+typedef struct {
+    int32_t n_edits;      /* totals of the run, also when the buffers held only a prefix */
+    int32_t n_candidates; /* after the tie drop                                          */
+    int32_t n_ties;       /* candidates dropped because an earlier one had their time    */
+    int32_t stopped_at;   /* the repaired row, -1 if the run did not stop                */
+    int32_t truncated;    /* 1: n_edits > max_edits or n_candidates > max_candidates     */
+    int32_t n_action[7];  /* input rows per action byte                                  */
+} mmp_janitor_info;
+#define MMP_JANITOR_APPLY 1u /* rewrite the resident registry: rows in place (as mmp_models_upsert does), no commit needed */
+#define MMP_JANITOR_DRY 2u   /* compute everything, change nothing: the same as flags = 0 here (the plan keeps no state of its
+                                own between runs); kept so that callers write the prune and the plan alike */
+/* actions_out holds n bytes.  flags = 0: the plan is computed, the resident registry is left to the caller (who applies the
+ * records the KV store accepted through mmp_models_upsert); MMP_JANITOR_APPLY: the library also rewrites the resident registry —
+ * the edited records' entries, the inserted one among them, are appended to the entry arena on the device and the rows
+ * rewritten in place under the protocol of mmp_models_upsert; MMP_JANITOR_DRY (alone).  When edits_out or the candidate
+ * buffers are too small the prefix that fits and the totals are returned with truncated = 1 and NOTHING is applied.  Buffers
+ * may be NULL with a capacity of 0. */
+int mmp_janitor_plan(mmp_ctx *ctx, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *params, uint32_t flags,
+                     uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *candidates_out,
+                     int32_t *candidate_rows_out, int32_t max_candidates, mmp_janitor_info *info_out);
 
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for

@@ -101,6 +101,14 @@ final class MmPlace {
                                     ByteBuffer editsOut, int maxEdits, ByteBuffer removedOut, int maxRemoved, ByteBuffer info);
     static native int registryMissingGet(long h, ByteBuffer sinceOut, int maxPods, ByteBuffer nOut);
     static native int registryMissingReset(long h);
+    // janitorTask's cache loop and registry loop (MM.java:5892-6008, :6014-6108) for this instance: entries = mmp_janitor_entry rows
+    // (80 bytes, runtimeCache.descendingMap() order without the unload-buffer entry), params = one mmp_janitor_params; flags 1 =
+    // apply to the resident registry, 2 = dry run.  actionsOut = one byte per row (4 / 6: ce.remove()), editsOut = mmp_janitor_edit
+    // rows (48 bytes: what goes to registry.conditionalSetAndGet), candidatesOut = scaleCopiesCandidates oldest first as
+    // mmp_cache_entry rows for scaledownPlan, candidateRowsOut their input rows; info.truncated: nothing was applied.
+    static native int janitorPlan(long h, ByteBuffer entries, int n, ByteBuffer params, int flags, ByteBuffer actionsOut,
+                                  ByteBuffer editsOut, int maxEdits, ByteBuffer candidatesOut, ByteBuffer candidateRowsOut,
+                                  int maxCandidates, ByteBuffer info);
     static native int scaleupPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer outs,
                                   ByteBuffer overloadedOut, ByteBuffer skipped);
     static native int scaledownPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer removedOut);

@@ -365,6 +365,27 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryMissingRese
 {
     return check(env, ctx_of(h), mmp_registry_missing_reset(ctx_of(h)));
 }
+// The janitor's cache and registry loops (MM.java:5892-6008, :6014-6108): every buffer's capacity is checked here, the library
+// only knows n / maxEdits / maxCandidates.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_janitorPlan(JNIEnv *env, jclass, jlong h, jobject entries, jint n,
+                                                                         jobject params, jint flags, jobject actionsOut,
+                                                                         jobject editsOut, jint maxEdits, jobject candidatesOut,
+                                                                         jobject candidateRowsOut, jint maxCandidates, jobject info)
+{
+    if (!holds<mmp_janitor_entry>(env, entries, n, "janitorPlan: entries shorter than n") ||
+        !holds<mmp_janitor_params>(env, params, 1, "janitorPlan: params shorter than one mmp_janitor_params") ||
+        !holds<uint8_t>(env, actionsOut, n, "janitorPlan: actionsOut shorter than n") ||
+        !holds<mmp_janitor_edit>(env, editsOut, maxEdits, "janitorPlan: editsOut shorter than maxEdits") ||
+        !holds<mmp_cache_entry>(env, candidatesOut, maxCandidates, "janitorPlan: candidatesOut shorter than maxCandidates") ||
+        !holds<int32_t>(env, candidateRowsOut, maxCandidates, "janitorPlan: candidateRowsOut shorter than maxCandidates") ||
+        !holds<mmp_janitor_info>(env, info, 1, "janitorPlan: info shorter than one mmp_janitor_info"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_janitor_plan(ctx_of(h), buf<mmp_janitor_entry>(env, entries), n, buf<mmp_janitor_params>(env, params),
+                                  static_cast<uint32_t>(flags), buf<uint8_t>(env, actionsOut), buf<mmp_janitor_edit>(env, editsOut), maxEdits,
+                                  buf<mmp_cache_entry>(env, candidatesOut), buf<int32_t>(env, candidateRowsOut), maxCandidates,
+                                  buf<mmp_janitor_info>(env, info)));
+}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaleupPlan(JNIEnv *env, jclass, jlong h, jobject entries,
                                                                          jint n, jobject params, jobject outs,
                                                                          jobject overloadedOut, jobject skipped)

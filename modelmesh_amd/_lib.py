@@ -107,6 +107,27 @@ PRUNE_INFO = np.dtype([("n_edits", "<i4"), ("n_removed", "<i4"), ("n_repaired", 
                        ("n_missing_pods", "<i4"), ("n_new_missing", "<i4"), ("truncated", "<i4"), ("reserved", "<i4")])
 assert PRUNE_EDIT.itemsize == 32 and PRUNE_REMOVED.itemsize == 16 and PRUNE_INFO.itemsize == 32
 
+# mmp_janitor_plan (janitorTask's cache and registry loops, MM.java:5892-6008, :6014-6108)
+JANITOR_APPLY, JANITOR_DRY = 1, 2
+JE_DONE, JE_FAILED, JE_STATE_LIVE = 1, 2, 4
+(JAN_NONE, JAN_REPAIRED, JAN_REFRESHED, JAN_IN_ORDER, JAN_REMOVED, JAN_REGISTERED, JAN_EXPIRED) = range(7)
+(JAN_EDIT_REGISTERED, JAN_EDIT_TIMESTAMP_MISMATCH, JAN_EDIT_REM_LOADED, JAN_EDIT_REM_FAILED, JAN_EDIT_TOUCHED, JAN_EDIT_REPAIRED,
+ JAN_EDIT_UNLOAD_SET) = (1, 2, 4, 8, 16, 32, 64)
+JANITOR_ENTRY = np.dtype(
+    [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("load_timestamp", "<i8"), ("load_complete_timestamp", "<i8"),
+     ("last_unload_attempt_time", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"), ("last_unload_time", "<i8"),
+     ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+JANITOR_PARAMS = np.dtype(
+    [("self_pod", "<i4"), ("shutting_down", "<i4"), ("now", "<i8"), ("janitor_freq_secs", "<i8"), ("load_timeout_ms", "<i8"),
+     ("min_stale_age_ms", "<i8"), ("load_failure_expiry_ms", "<i8"), ("short_expiry_recent_use_ms", "<i8"),
+     ("unload_attempt_recent_ms", "<i8"), ("lastused_age_on_add_ms", "<i8")])
+JANITOR_EDIT = np.dtype(
+    [("model", "<i4"), ("n_loaded_after", "<i4"), ("n_failed_after", "<i4"), ("flags", "<u4"), ("last_used_after", "<i8"),
+     ("last_unload_after", "<i8"), ("inserted_time", "<i8"), ("inserted_pos", "<i4"), ("entry", "<i4")])
+JANITOR_INFO = np.dtype([("n_edits", "<i4"), ("n_candidates", "<i4"), ("n_ties", "<i4"), ("stopped_at", "<i4"), ("truncated", "<i4"),
+                         ("n_action", "<i4", (7,))])
+assert JANITOR_ENTRY.itemsize == 80 and JANITOR_PARAMS.itemsize == 72 and JANITOR_EDIT.itemsize == 48 and JANITOR_INFO.itemsize == 48
+
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
      ("last_unload_time", "<i8"), ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"),
@@ -212,6 +233,7 @@ SYMBOLS = [
     ("mmp_registry_prune", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int32, _P, C.c_int32, _P]),
     ("mmp_registry_missing_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_registry_missing_reset", C.c_int, [_P]),
+    ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("mmp_scaleup_plan_conc", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),

@@ -37,6 +37,7 @@
 #include "place_kernel.hpp"
 #include "rebalance_kernels.hpp"
 #include "registry_kernels.hpp"
+#include "janitor_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -345,6 +346,10 @@ struct mmp_ctx {
     // the call's scratch (registry_kernels.hpp).  Owned by batch_mu; only the prune kernels, on c->stream, touch them.
     DevBuf miss_since, p_state, p_seen, p_ps, p_counts, p_edits, p_removed, p_koff;
     int32_t miss_n = 0;
+    // mmp_janitor_plan (janitor_kernels.hpp): the model -> cache row map, all -1 between runs over its first jn_map_n words (0: not
+    // known to be clear), the uploaded rows, the call's scalars and its row-sized scratch.  Owned by batch_mu, used on c->stream.
+    DevBuf jn_map, jn_in, jn_js, jn_tmp;
+    int32_t jn_map_n = 0;
     std::vector<uint64_t> u_stamp;        // per model: (call generation, row index) of the last row naming it
     uint32_t u_gen = 0;
     // (the registry view resolved against a snapshot, place_kernel.hpp: ResolvedModel, lives in SnapSide)
@@ -1034,7 +1039,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->jn_map, &c->jn_in, &c->jn_js, &c->jn_tmp, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -4660,6 +4665,151 @@ try {
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_registry_missing_reset")
+
+int mmp_janitor_plan(mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *p, uint32_t flags,
+                     uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *cands_out,
+                     int32_t *cand_rows_out, int32_t max_cands, mmp_janitor_info *info)
+try {
+    if (!c || !p || !info || n < 0 || max_edits < 0 || max_cands < 0 || (n > 0 && (!entries || !actions_out)) || (max_edits > 0 && !edits_out) ||
+        (max_cands > 0 && (!cands_out || !cand_rows_out)) || p->now <= 0 || p->janitor_freq_secs < 0 || p->load_timeout_ms < 0 ||
+        p->min_stale_age_ms < 0 || p->load_failure_expiry_ms < 0 || p->short_expiry_recent_use_ms < 0 || p->unload_attempt_recent_ms < 0 ||
+        p->lastused_age_on_add_ms < 0 || (flags & ~(MMP_JANITOR_APPLY | MMP_JANITOR_DRY)) || flags == (MMP_JANITOR_APPLY | MMP_JANITOR_DRY))
+        return fail(c, MMP_EINVAL, "mmp_janitor_plan: bad argument");
+    // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
+    // too.  The state lock is taken only by an apply, for its in-place rewrite.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_janitor_plan: not available on a pod-axis shard context");
+    const int32_t M = c->n_models, P = c->snap.P;
+    if (p->self_pod < 0 || p->self_pod >= P) return fail(c, MMP_EINVAL, "mmp_janitor_plan: self_pod %d of %d", p->self_pod, P);
+    {
+        // the rows index the map: range and one-row-per-model are settled here, before any kernel reads them
+        if (++c->u_gen == 0) ++c->u_gen;  // (generation 0 is what an untouched stamp carries)
+        const uint64_t gen = (uint64_t)c->u_gen << 32;
+        if (c->u_stamp.size() < (size_t)M) c->u_stamp.resize(M, 0);
+        for (int32_t r = 0; r < n; r++) {
+            const int32_t m = entries[r].model;
+            if (m < -1 || m >= M) return fail(c, MMP_EINVAL, "mmp_janitor_plan: row %d names model %d of %d", r, m, M);
+            if (m < 0) continue;
+            if ((c->u_stamp[m] & ~0xffffffffull) == gen) return fail(c, MMP_EINVAL, "mmp_janitor_plan: model %d has two rows", m);
+            c->u_stamp[m] = gen | (uint32_t)r;
+        }
+    }
+    *info = mmp_janitor_info{};
+    info->stopped_at = -1;
+    if (p->shutting_down) {  // :5880
+        if (n > 0) memset(actions_out, MMP_JANITOR_NONE, (size_t)n);
+        info->n_action[MMP_JANITOR_NONE] = n;
+        return MMP_OK;
+    }
+    const bool apply = flags & MMP_JANITOR_APPLY;
+    // an apply appends at most the live entries and one more per row to the arena: refused before anything is done
+    if (apply && (int64_t)c->n_entries + c->ent_live + n > INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_janitor_plan: entry arena overflow; reload the registry");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int nb = div_up(M, kJanBlock), n1 = std::max(n, 1);
+    const int32_t cap_e = std::min(max_edits, M);
+    // the row-sized scratch, carved from one buffer
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) {
+        const size_t at = off;
+        off = (off + bytes + 255) & ~size_t(255);
+        return at;
+    };
+    const size_t o_ctime = carve((size_t)n1 * 8), o_crow = carve((size_t)n1 * 4), o_drop = carve((size_t)n1), o_act = carve((size_t)n1),
+                 o_cands = carve((size_t)n1 * sizeof(mmp_cache_entry)), o_orow = carve((size_t)n1 * 4);
+    HIP_TRY(c, c->jn_tmp.ensure(off));
+    char *tmp = c->jn_tmp.as<char>();
+    HIP_TRY(c, c->jn_in.ensure((size_t)n1 * sizeof(mmp_janitor_entry)));
+    HIP_TRY(c, c->jn_js.ensure(sizeof(JanitorScalars)));
+    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->p_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
+    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_janitor_edit)));
+    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    if (c->jn_map_n < M || (size_t)M * 4 > c->jn_map.cap) {  // the one M-sized fill: when the map is new, grew or was left in doubt
+        HIP_TRY(c, c->jn_map.ensure((size_t)std::max(M, 1) * 4));
+        HIP_TRY(c, hipMemsetAsync(c->jn_map.p, 0xff, (size_t)std::max(M, 1) * 4, st));
+    }
+    c->jn_map_n = 0;  // in doubt until the finish kernel has been seen to complete
+    const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    const int32_t *ent_pod = c->ent_pod.as<int32_t>();
+    const int64_t *ent_time = c->ent_time.as<int64_t>();
+    const mmp_janitor_entry *d_in = c->jn_in.as<mmp_janitor_entry>();
+    int32_t *map = c->jn_map.as<int32_t>();
+    JanitorScalars *js = c->jn_js.as<JanitorScalars>();
+    PruneScalars *ps = c->p_ps.as<PruneScalars>();
+    int64_t *ctime = (int64_t *)(tmp + o_ctime);
+    int32_t *crow = (int32_t *)(tmp + o_crow), *orow = (int32_t *)(tmp + o_orow);
+    uint8_t *drop = (uint8_t *)(tmp + o_drop), *act = (uint8_t *)(tmp + o_act);
+    mmp_cache_entry *d_cands = (mmp_cache_entry *)(tmp + o_cands);
+    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->jn_in.p, entries, (size_t)n * sizeof(mmp_janitor_entry), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(js, 0, sizeof(JanitorScalars), st));
+    HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
+    KT_BEGIN(c, st);  // device span of the plan
+    const int gn = div_up(n, 256);
+    if (n > 0) hipLaunchKernelGGL(janitor_entry_kernel, dim3(gn), dim3(256), 0, st, d_in, n, map, *p, js);
+    if (nb > 0) {
+        hipLaunchKernelGGL(janitor_count_kernel, dim3(nb), dim3(kJanBlock), 0, st, models, M, ent_pod, ent_time, pods, P, map, d_in, n, *p, js,
+                           c->p_counts.as<int32_t>());
+        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
+        hipLaunchKernelGGL(janitor_scatter_kernel, dim3(nb), dim3(kJanBlock), 0, st, models, M, ent_pod, ent_time, pods, P, map, d_in, n, *p, js,
+                           c->p_counts.as<int32_t>(), ps, c->p_edits.as<mmp_janitor_edit>(), cap_e, c->p_koff.as<int32_t>(), ctime, crow);
+    }
+    if (n > 0) {
+        const int gt = div_up(n, kJanTile);
+        hipLaunchKernelGGL(janitor_tie_kernel, dim3(gt), dim3(256), 0, st, ctime, ps, drop, js);
+        hipLaunchKernelGGL(janitor_rank_kernel, dim3(gt), dim3(256), 0, st, ctime, crow, drop, ps, d_in, d_cands, orow, n);
+        hipLaunchKernelGGL(janitor_finish_kernel, dim3(gn), dim3(256), 0, st, d_in, n, models, ent_pod, ent_time, map, *p, act, js);
+    }
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    JanitorScalars hj{};
+    PruneScalars h{};
+    HIP_TRY(c, hipMemcpyAsync(&hj, js, sizeof hj, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->jn_map_n = M;
+    kt_collect(c);
+    const int32_t ne = std::min(h.n_edits, max_edits), nc = std::min(hj.n_cands, max_cands);
+    if (n > 0) HIP_TRY(c, copy_sync(c, actions_out, act, (size_t)n, hipMemcpyDeviceToHost));
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_janitor_edit), hipMemcpyDeviceToHost));
+    if (nc > 0) {
+        HIP_TRY(c, copy_sync(c, cands_out, d_cands, (size_t)nc * sizeof(mmp_cache_entry), hipMemcpyDeviceToHost));
+        HIP_TRY(c, copy_sync(c, cand_rows_out, orow, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    }
+    info->n_edits = h.n_edits;
+    info->n_candidates = hj.n_cands;
+    info->n_ties = hj.n_ties;
+    info->stopped_at = hj.stop_inv > 0 ? n - hj.stop_inv : -1;
+    info->truncated = (h.n_edits > max_edits || hj.n_cands > max_cands) ? 1 : 0;
+    for (int k = 0; k < 7; k++) info->n_action[k] = hj.n_action[k];
+    if (!apply || info->truncated || h.n_edits == 0) return MMP_OK;
+
+    // apply: the edited records are rebuilt at the end of the arena ON THE DEVICE, beyond anything a published row refers to; then
+    // the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
+    const double plan_ms = c->last_kernel_ms;
+    const int32_t E = h.n_edits, base = c->n_entries;
+    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(janitor_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_janitor_edit>(), c->p_koff.as<int32_t>(), E,
+                       c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept, p->self_pod,
+                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
+    if (c->prof && plan_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += plan_ms;  // the call's device span: plan + apply
+    for (int32_t e = 0; e < E; e++) {
+        const int32_t cnt = edits_out[e].n_loaded_after + edits_out[e].n_failed_after;
+        c->ent_live += (int64_t)cnt - c->m_cnt[edits_out[e].model];
+        c->m_cnt[edits_out[e].model] = cnt;
+    }
+    // more garbage than live entries (and enough to matter): squeeze the arena
+    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_janitor_plan")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

@@ -609,6 +609,39 @@ class Solver:
         """missings.clear() on a leader change (MM.java:6827)."""
         self._ck(self.lib.mmp_registry_missing_reset(self.h))
 
+    def janitor_plan(self, entries, params, apply: bool = True, dry: bool = False, max_edits: int = 1024, max_candidates: int = 1024):
+        """The janitor's cache and registry loops (MM.java:5892-6008, :6014-6108) for one instance: (actions, edits, candidates,
+        candidate rows, info).  The candidates go to scaledown_plan unchanged.  The buffers are regrown to the run's totals when it
+        reports `truncated` (a truncated run changes nothing)."""
+        from ._lib import JANITOR_APPLY, JANITOR_DRY
+        flags = JANITOR_DRY if dry else (JANITOR_APPLY if apply else 0)
+        while True:
+            out = self.janitor_plan_raw(entries, params, flags, max_edits, max_candidates)
+            info = out[4]
+            if not info["truncated"]:
+                break
+            max_edits, max_candidates = max(max_edits, int(info["n_edits"])), max(max_candidates, int(info["n_candidates"]))
+        if flags == JANITOR_APPLY and int(info["n_edits"]) and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return out
+
+    def janitor_plan_raw(self, entries, params, flags, max_edits, max_candidates):
+        """One mmp_janitor_plan call with exactly these capacities: (actions, edits prefix, candidates prefix, rows prefix, info)."""
+        from ._lib import CACHE_ENTRY, JANITOR_EDIT, JANITOR_ENTRY, JANITOR_INFO, JANITOR_PARAMS
+        entries = np.ascontiguousarray(entries, dtype=JANITOR_ENTRY)
+        params = np.ascontiguousarray(params, dtype=JANITOR_PARAMS).reshape(1)
+        n = len(entries)
+        info = np.zeros(1, dtype=JANITOR_INFO)
+        actions = np.zeros(max(n, 1), np.uint8)
+        edits = np.zeros(max(max_edits, 1), dtype=JANITOR_EDIT)
+        cands = np.zeros(max(max_candidates, 1), dtype=CACHE_ENTRY)
+        rows = np.zeros(max(max_candidates, 1), np.int32)
+        self._ck(self.lib.mmp_janitor_plan(self.h, ptr(entries) if n else None, n, ptr(params), int(flags), ptr(actions) if n else None,
+                                           ptr(edits) if max_edits else None, int(max_edits), ptr(cands) if max_candidates else None,
+                                           ptr(rows) if max_candidates else None, int(max_candidates), ptr(info)))
+        ne, nc = min(max_edits, int(info[0]["n_edits"])), min(max_candidates, int(info[0]["n_candidates"]))
+        return actions[:n].copy(), edits[:ne].copy(), cands[:nc].copy(), rows[:nc].copy(), info[0].copy()
+
     def scaleup_plan(self, entries, params):
         """a15: (outs, overloaded[P], skipped)"""
         from ._lib import CACHE_ENTRY, SCALEUP_OUT, SCALEUP_PARAMS
