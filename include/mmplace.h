@@ -845,6 +845,40 @@ int mmp_janitor_plan(mmp_ctx *ctx, const mmp_janitor_entry *entries, int32_t n, 
                      uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *candidates_out,
                      int32_t *candidate_rows_out, int32_t max_candidates, mmp_janitor_info *info_out);
 
+/* A census of the resident registry: what the registry listener keeps on every instance (event(), MM.java:2807-2854) and
+ * logModelCountMetrics publishes (:6852-6863).  A record is in loadedModelIds iff !instanceIds.isEmpty() (:2828) and in
+ * failedModelIds iff hasLoadFailure() (:2829, ModelRecord.java:181-183); both depend on the record alone, so the sizes of the two
+ * sets are counts over the registry as it stands.  After mmp_registry_prune / mmp_janitor_plan have rewritten rows on the device
+ * this is how a host learns them without reading the registry back.
+ *
+ * Read-only; needs no committed snapshot (the registry does not depend on one).  Pod indices are those of the STAGED instance
+ * table, as in mmp_models_upsert.  The call sees the registry between two writers, never inside one: it takes the registry the
+ * way mmp_models_upsert and the applied prune / janitor plan do, and like them it does not hold decisions off. */
+typedef struct {
+    int32_t n_models;          /* registry.getCount(), :2851, :6862                                            */
+    int32_t n_loaded;          /* records with n_loaded > 0 = loadedModelIds.size(), :2828, :2844               */
+    int32_t n_failed;          /* records with n_failed > 0 = failedModelIds.size(), :2829, :2845               */
+    int32_t n_loaded_and_failed;
+    int32_t n_unloaded_used;   /* n_loaded == 0, 0 < last_used < INT64_MAX: the population :6574 draws from     */
+    int32_t n_last_used_max;   /* last_used == INT64_MAX: what repairLastUsedTimeIfNeeded (:6837) looks for     */
+    int64_t n_entries_loaded;  /* sum of n_loaded                                                               */
+    int64_t n_entries_failed;  /* sum of n_failed                                                               */
+    int64_t n_entries_unresolved; /* entries whose pod is outside [0, pod slots): ids the table does not know   */
+    int32_t copies_hist[5];    /* records with 0, 1, 2, 3, >= 4 instanceIds (a15's second copy, a16's >= 3 rule) */
+    int32_t max_copies;        /* the largest n_loaded                                                          */
+} mmp_registry_stats;
+typedef struct {
+    int32_t n_models, n_loaded, n_failed, reserved;
+    int64_t n_entries_loaded;
+} mmp_registry_type_stats;
+/* pod_loaded_out[p] / pod_failed_out[p] = records whose instanceIds / loadFailedInstanceIds hold pod p — hasRegistration
+ * (:2856-2858) summed over the registry, per list — for every slot of the pod table, tombstoned ones included.  types_out[t] covers
+ * the loaded type table (*n_types_out = 0 without one); a record whose type lies outside it counts in the totals only.
+ * *n_pods_out / *n_types_out are always set.  The pod buffers (both or neither) and the type buffer may be NULL with a capacity
+ * of 0: that part is not returned.  A capacity that is positive and smaller than the count: MMP_EINVAL, nothing else written. */
+int mmp_registry_census(mmp_ctx *ctx, mmp_registry_stats *out, int32_t *pod_loaded_out, int32_t *pod_failed_out, int32_t max_pods,
+                        int32_t *n_pods_out, mmp_registry_type_stats *types_out, int32_t max_types, int32_t *n_types_out);
+
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for
  * MMP_SCALE_UP rows the caller passes those pods as extra excludes of the load-target decisions

@@ -101,6 +101,13 @@ final class MmPlace {
                                     ByteBuffer editsOut, int maxEdits, ByteBuffer removedOut, int maxRemoved, ByteBuffer info);
     static native int registryMissingGet(long h, ByteBuffer sinceOut, int maxPods, ByteBuffer nOut);
     static native int registryMissingReset(long h);
+    // loadedModelCount / failedModelCount / registry.getCount() (event(), MM.java:2828-2852; logModelCountMetrics, :6852-6863) over the
+    // resident registry, after registryPrune / janitorPlan have rewritten it: statsOut = one mmp_registry_stats (72 bytes: n_models,
+    // n_loaded, n_failed at offsets 0, 4, 8); podLoadedOut / podFailedOut = one int per pod slot (hasRegistration, :2856-2858, summed
+    // over the records), typesOut = mmp_registry_type_stats rows (24 bytes); nPodsOut / nTypesOut = the table sizes, always set.
+    // Buffers may be null with a capacity of 0.
+    static native int registryCensus(long h, ByteBuffer statsOut, ByteBuffer podLoadedOut, ByteBuffer podFailedOut, int maxPods,
+                                     ByteBuffer nPodsOut, ByteBuffer typesOut, int maxTypes, ByteBuffer nTypesOut);
     // janitorTask's cache loop and registry loop (MM.java:5892-6008, :6014-6108) for this instance: entries = mmp_janitor_entry rows
     // (80 bytes, runtimeCache.descendingMap() order without the unload-buffer entry), params = one mmp_janitor_params; flags 1 =
     // apply to the resident registry, 2 = dry run.  actionsOut = one byte per row (4 / 6: ce.remove()), editsOut = mmp_janitor_edit

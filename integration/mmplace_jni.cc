@@ -365,6 +365,25 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryMissingRese
 {
     return check(env, ctx_of(h), mmp_registry_missing_reset(ctx_of(h)));
 }
+// The registry listener's model counts (MM.java:2807-2854, :6852-6863): the buffers' capacities are checked here, the library only
+// knows maxPods / maxTypes.  A null buffer with a capacity of 0: that part is not returned.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryCensus(JNIEnv *env, jclass, jlong h, jobject statsOut,
+                                                                            jobject podLoadedOut, jobject podFailedOut, jint maxPods,
+                                                                            jobject nPodsOut, jobject typesOut, jint maxTypes,
+                                                                            jobject nTypesOut)
+{
+    if (!holds<mmp_registry_stats>(env, statsOut, 1, "registryCensus: statsOut shorter than one mmp_registry_stats") ||
+        !holds<int32_t>(env, podLoadedOut, maxPods, "registryCensus: podLoadedOut shorter than maxPods") ||
+        !holds<int32_t>(env, podFailedOut, maxPods, "registryCensus: podFailedOut shorter than maxPods") ||
+        !holds<int32_t>(env, nPodsOut, 1, "registryCensus: nPodsOut shorter than one int") ||
+        !holds<mmp_registry_type_stats>(env, typesOut, maxTypes, "registryCensus: typesOut shorter than maxTypes") ||
+        !holds<int32_t>(env, nTypesOut, 1, "registryCensus: nTypesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_registry_census(ctx_of(h), buf<mmp_registry_stats>(env, statsOut), buf<int32_t>(env, podLoadedOut),
+                                     buf<int32_t>(env, podFailedOut), maxPods, buf<int32_t>(env, nPodsOut),
+                                     buf<mmp_registry_type_stats>(env, typesOut), maxTypes, buf<int32_t>(env, nTypesOut)));
+}
 // The janitor's cache and registry loops (MM.java:5892-6008, :6014-6108): every buffer's capacity is checked here, the library
 // only knows n / maxEdits / maxCandidates.
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_janitorPlan(JNIEnv *env, jclass, jlong h, jobject entries, jint n,

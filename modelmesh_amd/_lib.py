@@ -128,6 +128,15 @@ JANITOR_INFO = np.dtype([("n_edits", "<i4"), ("n_candidates", "<i4"), ("n_ties",
                          ("n_action", "<i4", (7,))])
 assert JANITOR_ENTRY.itemsize == 80 and JANITOR_PARAMS.itemsize == 72 and JANITOR_EDIT.itemsize == 48 and JANITOR_INFO.itemsize == 48
 
+# mmp_registry_census (the registry listener's model counts, MM.java:2807-2854, :6852-6863)
+REGISTRY_STATS = np.dtype(
+    [("n_models", "<i4"), ("n_loaded", "<i4"), ("n_failed", "<i4"), ("n_loaded_and_failed", "<i4"), ("n_unloaded_used", "<i4"),
+     ("n_last_used_max", "<i4"), ("n_entries_loaded", "<i8"), ("n_entries_failed", "<i8"), ("n_entries_unresolved", "<i8"),
+     ("copies_hist", "<i4", (5,)), ("max_copies", "<i4")])
+REGISTRY_TYPE_STATS = np.dtype([("n_models", "<i4"), ("n_loaded", "<i4"), ("n_failed", "<i4"), ("reserved", "<i4"),
+                                ("n_entries_loaded", "<i8")])
+assert REGISTRY_STATS.itemsize == 72 and REGISTRY_TYPE_STATS.itemsize == 24
+
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
      ("last_unload_time", "<i8"), ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"),
@@ -234,6 +243,7 @@ SYMBOLS = [
     ("mmp_registry_missing_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_registry_missing_reset", C.c_int, [_P]),
     ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    ("mmp_registry_census", C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("mmp_scaleup_plan_conc", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),

@@ -38,6 +38,7 @@
 #include "rebalance_kernels.hpp"
 #include "registry_kernels.hpp"
 #include "janitor_kernels.hpp"
+#include "census_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -383,6 +384,14 @@ struct mmp_ctx {
     DevBuf s_reqs, s_outs, s_extra, s_a, s_b, s_c, s_d;
     // rebalancer scratch
     DevBuf r_ps, r_counts, r_keys, r_vals, r_keys2, r_vals2, r_tmp, r_out_model, r_out_lu;
+    // mmp_registry_census (census_kernels.hpp): the call's outputs on the device — stats | type rows | pod_loaded | pod_failed — zeroed
+    // by every call, and their host copy.  Owned by batch_mu, used on c->stream.  census_pod_lds: the dynamic LDS the walk may be
+    // launched with (beyond it the per-pod counts go to global memory; 32 KB need no grant, the first call asks for
+    // kCensusPodLdsBytes); census_cus: compute units of the device (0: not asked yet).
+    DevBuf cn_out;
+    std::vector<unsigned char> cn_host;
+    size_t census_pod_lds = 32 * 1024;
+    int32_t census_cus = 0;
 };
 
 namespace {
@@ -1039,7 +1048,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->jn_map, &c->jn_in, &c->jn_js, &c->jn_tmp, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->jn_map, &c->jn_in, &c->jn_js, &c->jn_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -4642,6 +4651,70 @@ try {
     if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
     return MMP_OK;
 } MMP_CATCH(c, "mmp_registry_prune")
+
+int mmp_registry_census(mmp_ctx *c, mmp_registry_stats *out, int32_t *pod_loaded_out, int32_t *pod_failed_out, int32_t max_pods,
+                        int32_t *n_pods_out, mmp_registry_type_stats *types_out, int32_t max_types, int32_t *n_types_out)
+try {
+    if (!c || !out || !n_pods_out || !n_types_out || max_pods < 0 || max_types < 0 || (max_pods > 0 && (!pod_loaded_out || !pod_failed_out)) ||
+        (max_types > 0 && !types_out))
+        return fail(c, MMP_EINVAL, "mmp_registry_census: bad argument");
+    // batch_mu owns c->stream and the scratch for the whole call, and every writer of what this call reads — registry events, an
+    // applied prune or janitor plan, the loaders of the registry, the instance table and the type table — takes it too and leaves
+    // with its work on c->stream finished.  The state lock is not taken: nothing decisions read is written.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t M = c->n_models, P = (int32_t)c->pods.size(), T = c->n_types;
+    *n_pods_out = P;
+    *n_types_out = T;
+    if ((max_pods > 0 && max_pods < P) || (max_types > 0 && max_types < T))
+        return fail(c, MMP_EINVAL, "mmp_registry_census: room for %d pods and %d types, the tables have %d and %d", max_pods, max_types, P, T);
+    const bool want_pods = max_pods > 0, want_types = max_types > 0;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (c->census_cus == 0) {  // the first call: the device's size, and the dynamic LDS the walk keeps its per-pod counts in
+        int cus = 0;
+        c->census_cus = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) == hipSuccess && cus > 0 ? cus : 256;
+        if (kCensusPodLdsBytes + kCensusStaticLds <= c->lds_limit &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(census_walk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kCensusPodLdsBytes) == hipSuccess)
+            c->census_pod_lds = kCensusPodLdsBytes;
+        (void)hipGetLastError();
+    }
+    hipStream_t st = c->stream;
+    const size_t o_types = 128, o_pods = o_types + (size_t)T * sizeof(mmp_registry_type_stats), total = o_pods + (size_t)P * 8;
+    static_assert(sizeof(mmp_registry_stats) <= 128, "the scalars come first");
+    HIP_TRY(c, c->cn_out.ensure(total));
+    char *d = c->cn_out.as<char>();
+    // private per-pod counts when the two arrays fit the LDS the kernel was granted; as many workgroups as stay resident with it
+    const size_t pod_lds = (size_t)P * 8;
+    const bool priv = pod_lds <= c->census_pod_lds;
+    const int nb = div_up(M, kCensusBlock);
+    const int per_cu = priv ? (int)std::min<size_t>(8, std::max<size_t>(1, kLdsPerCU / (pod_lds + kCensusStaticLds))) : 8;
+    const int grid = std::min(nb, std::min(kCensusGridMax, c->census_cus * per_cu));
+    KT_BEGIN(c, st);
+    HIP_TRY(c, hipMemsetAsync(d, 0, total, st));
+    if (nb > 0) {
+        if (priv)
+            hipLaunchKernelGGL(census_walk_kernel<true>, dim3(grid), dim3(kCensusBlock), pod_lds, st, c->models.as<mmp_model_row>(), M,
+                               c->ent_pod.as<int32_t>(), P, T, (mmp_registry_stats *)d, (mmp_registry_type_stats *)(d + o_types),
+                               (int32_t *)(d + o_pods));
+        else
+            hipLaunchKernelGGL(census_walk_kernel<false>, dim3(grid), dim3(kCensusBlock), 0, st, c->models.as<mmp_model_row>(), M,
+                               c->ent_pod.as<int32_t>(), P, T, (mmp_registry_stats *)d, (mmp_registry_type_stats *)(d + o_types),
+                               (int32_t *)(d + o_pods));
+    }
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    const size_t take = want_pods ? total : o_pods;  // (the pod arrays come last)
+    c->cn_host.resize(total);
+    HIP_TRY(c, copy_sync(c, c->cn_host.data(), d, take, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    memcpy(out, c->cn_host.data(), sizeof *out);
+    if (want_types && T > 0) memcpy(types_out, c->cn_host.data() + o_types, (size_t)T * sizeof(mmp_registry_type_stats));
+    if (want_pods && P > 0) {
+        memcpy(pod_loaded_out, c->cn_host.data() + o_pods, (size_t)P * 4);
+        memcpy(pod_failed_out, c->cn_host.data() + o_pods + (size_t)P * 4, (size_t)P * 4);
+    }
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_census")
 
 int mmp_registry_missing_get(mmp_ctx *c, int64_t *since_out, int32_t max_pods, int32_t *n_out)
 try {

@@ -642,6 +642,40 @@ class Solver:
         ne, nc = min(max_edits, int(info[0]["n_edits"])), min(max_candidates, int(info[0]["n_candidates"]))
         return actions[:n].copy(), edits[:ne].copy(), cands[:nc].copy(), rows[:nc].copy(), info[0].copy()
 
+    def registry_census(self):
+        """The registry listener's model counts (MM.java:2807-2854, :6852-6863) over the resident registry: (stats, pod_loaded,
+        pod_failed, type_stats) — one mmp_registry_stats row, per pod slot of the staged instance table the records that hold it in
+        instanceIds / in loadFailedInstanceIds, and one mmp_registry_type_stats row per row of the type table."""
+        while True:
+            n_pods, n_types = self.registry_census_sizes()
+            stats, pl, pf, ts, got_pods, got_types, rc = self.registry_census_raw(n_pods, n_types)
+            if rc == _lib.MMP_EINVAL and (got_pods, got_types) != (n_pods, n_types):
+                continue  # a table grew between the two calls
+            self._ck(rc)
+            return stats, pl, pf, ts
+
+    def registry_census_sizes(self):
+        """(pod slots, type rows) the census covers."""
+        from ._lib import REGISTRY_STATS
+        stats = np.zeros(1, dtype=REGISTRY_STATS)
+        n_pods, n_types = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mmp_registry_census(self.h, ptr(stats), None, None, 0, C.byref(n_pods), None, 0, C.byref(n_types)))
+        return n_pods.value, n_types.value
+
+    def registry_census_raw(self, max_pods, max_types, fill=0):
+        """One mmp_registry_census call with exactly these capacities (0: a NULL buffer), the arrays filled with `fill` first:
+        (stats, pod_loaded, pod_failed, type_stats, n_pods, n_types, rc).  Does not raise: rc is the return code."""
+        from ._lib import REGISTRY_STATS, REGISTRY_TYPE_STATS
+        stats = np.zeros(1, dtype=REGISTRY_STATS)
+        pl = np.full(max(max_pods, 1), fill, np.int32)
+        pf = np.full(max(max_pods, 1), fill, np.int32)
+        ts = np.zeros(max(max_types, 1), dtype=REGISTRY_TYPE_STATS)
+        ts.view(np.int32)[:] = fill
+        n_pods, n_types = C.c_int32(-1), C.c_int32(-1)
+        rc = self.lib.mmp_registry_census(self.h, ptr(stats), ptr(pl) if max_pods else None, ptr(pf) if max_pods else None, int(max_pods),
+                                          C.byref(n_pods), ptr(ts) if max_types else None, int(max_types), C.byref(n_types))
+        return stats[0].copy(), pl[:max_pods], pf[:max_pods], ts[:max_types], n_pods.value, n_types.value, rc
+
     def scaleup_plan(self, entries, params):
         """a15: (outs, overloaded[P], skipped)"""
         from ._lib import CACHE_ENTRY, SCALEUP_OUT, SCALEUP_PARAMS
