@@ -879,6 +879,94 @@ typedef struct {
 int mmp_registry_census(mmp_ctx *ctx, mmp_registry_stats *out, int32_t *pod_loaded_out, int32_t *pod_failed_out, int32_t max_pods,
                         int32_t *n_pods_out, mmp_registry_type_stats *types_out, int32_t max_types, int32_t *n_types_out);
 
+/* The edits an instance makes to ModelRecords itself, as a batch against the resident registry.  Each op names one record
+ * (`model`) and one instance (`pod` = the reference's instanceId: a slot of the instance table, present, shutting down or
+ * tombstoned); now_ms (> 0) stands for every currentTimeMillis() below.  With r the record of `model`:
+ *
+ *   MMP_ROP_REGISTER (loadLocal, MM.java:5204-5207) — always an edit (the record is always submitted):
+ *     instanceIds.put(pod, load_time): over the entry that is there, else in front of the first RESOLVED entry with a greater
+ *     id_order (at the end if there is none; unresolved entries are never compared); removeLoadFailure(pod);
+ *     updateLastUsed(last_used == 0 ? now : last_used).
+ *   MMP_ROP_LOAD_FAILED (the CacheEntry failure path, :2484-2495):
+ *     lu = last_used, or r.last_used when last_used <= 0; instanceIds.remove(pod, load_time) — key present AND time equal — or
+ *     else nothing changes; unless MMP_ROPF_SHUTTING_DOWN, loadFailedInstanceIds.put(pod, load_complete_time) (addLoadFailure,
+ *     ModelRecord.java:156-167: over the entry that is there, else in id order within that list); updateLastUsed(lu), where an
+ *     lu that is still 0 means now (ModelRecord.java:239-246).
+ *   MMP_ROP_DEREGISTER (deregisterModel, :2948-2958):
+ *     with MMP_ROPF_MATCH_TIME (loadTime != null) the loaded entry goes only if its time == load_time and the failed entry only
+ *     if its time == load_complete_time (ModelRecord.java:173-179); without it either goes if present.  Neither: nothing
+ *     changes (:2955).  Else updateLastUsed(last_used) (0 = now) and, if the loaded entry went, updateLastUnloadTime(): 0 when
+ *     instanceIds.size() <= 2 after the removal, else now (ModelRecord.java:260-262).
+ *   MMP_ROP_SCALE_DOWN (removeLocalModelCopyAsync, :6347-6365):
+ *     no loaded entry for pod, or its time != load_time: nothing changes (:6348).  Else it is removed, updateLastUnloadTime(),
+ *     updateLastUsed(last_used).  loadFailedInstanceIds is not touched.  (isLoadedElsewhere, :6357, is a remote check: the host
+ *     sends the op after it.)
+ *
+ * updateLastUsed only raises (a record at INT64_MAX stays there).  The model row has no lastUnloadTime: the edit reports it.
+ * The instance table read for id_order is the committed one, as for mmp_janitor_plan.  The compare-and-set retry against the
+ * KV store, loadFailureInfos and the CacheEntry state machine around these sites stay with the caller.
+ *
+ * MMP_EINVAL, with nothing written or changed: a model outside [0, n_models), a pod outside the instance table, an unknown op
+ * or flag bit, now_ms <= 0, two ops naming the same model (an instance has one cache entry per model; a host that needs both
+ * flushes between them).  MMP_ESTATE before the first commit.  n = 0 is a valid call with empty outputs. */
+#define MMP_ROP_REGISTER 0
+#define MMP_ROP_LOAD_FAILED 1
+#define MMP_ROP_DEREGISTER 2
+#define MMP_ROP_SCALE_DOWN 3
+#define MMP_ROPF_SHUTTING_DOWN 1u /* MMP_ROP_LOAD_FAILED: no failure record is written (:2492) */
+#define MMP_ROPF_MATCH_TIME 2u    /* MMP_ROP_DEREGISTER: loadTime != null (:2951)              */
+typedef struct {
+    int32_t model;
+    int32_t pod;
+    int32_t op;                 /* MMP_ROP_*                                                   */
+    uint32_t flags;             /* MMP_ROPF_*                                                  */
+    int64_t last_used;
+    int64_t load_time;          /* ce.loadTimestamp / loadTime                                 */
+    int64_t load_complete_time; /* loadCompleteTimestamp / loadCompletedTime                   */
+} mmp_registry_op; /* 40 bytes */
+#define MMP_ROP_UNCHANGED 0 /* the Java returned without a compare-and-set */
+#define MMP_ROP_EDITED 1
+#define MMP_ROP_EDIT_REM_LOADED 1u
+#define MMP_ROP_EDIT_REM_FAILED 2u
+#define MMP_ROP_EDIT_PUT_LOADED 4u
+#define MMP_ROP_EDIT_PUT_FAILED 8u
+#define MMP_ROP_EDIT_REPLACED 16u   /* the put found the key: its time was replaced in place */
+#define MMP_ROP_EDIT_TOUCHED 32u    /* updateLastUsed raised last_used                       */
+#define MMP_ROP_EDIT_UNLOAD_SET 64u /* last_unload_after is to be stored                     */
+typedef struct {
+    int32_t model;
+    int32_t op_index;          /* the op that made this edit                                                     */
+    int32_t n_loaded_after;
+    int32_t n_failed_after;
+    uint32_t flags;            /* MMP_ROP_EDIT_*                                                                 */
+    int32_t inserted_pos;      /* where the put entry stands in its list (instanceIds for PUT_LOADED,            */
+                               /*   loadFailedInstanceIds for PUT_FAILED) after the edit; -1: nothing was put    */
+    int64_t last_used_after;
+    int64_t last_unload_after; /* with MMP_ROP_EDIT_UNLOAD_SET: 0 or now                                         */
+} mmp_registry_op_edit; /* 40 bytes */
+typedef struct {
+    int32_t n_edits;           /* totals of the call, also when edits_out held only a prefix */
+    int32_t n_unchanged;
+    int32_t truncated;         /* 1: n_edits > max_edits                                     */
+    int32_t reserved;
+    int32_t n_edited_op[4];    /* per MMP_ROP_* kind                                         */
+    int32_t n_unchanged_op[4];
+    int32_t n_entries_added;   /* puts that found no key                                     */
+    int32_t n_entries_removed;
+} mmp_registry_ops_info; /* 56 bytes */
+#define MMP_ROPS_APPLY 1u /* rewrite the resident registry: rows in place (as mmp_models_upsert does), no commit needed */
+#define MMP_ROPS_DRY 2u   /* compute everything, change nothing: the same as flags = 0 here; kept so that callers write the
+                             prune, the janitor plan and this alike */
+/* status_out holds n bytes (MMP_ROP_UNCHANGED / MMP_ROP_EDITED); edits_out one row per edited record IN OP ORDER — the order
+ * the Java would issue its conditionalSetAndGet calls in.  flags = 0: computed only, the resident registry is left to the
+ * caller (who applies what the KV store accepted through mmp_models_upsert); MMP_ROPS_APPLY: the edited records' entries are
+ * appended to the entry arena on the device and the rows rewritten in place under the protocol of mmp_models_upsert;
+ * MMP_ROPS_DRY (alone).  When edits_out is too small the prefix that fits and the totals are returned with truncated = 1 and
+ * NOTHING is applied.  edits_out may be NULL with a capacity of 0; a NULL status_out is not
+ * returned. */
+int mmp_registry_ops(mmp_ctx *ctx, const mmp_registry_op *ops, int32_t n, int64_t now_ms, uint32_t flags, uint8_t *status_out,
+                     mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info_out);
+
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for
  * MMP_SCALE_UP rows the caller passes those pods as extra excludes of the load-target decisions

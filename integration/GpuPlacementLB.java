@@ -116,6 +116,14 @@ final class MmPlace {
     static native int janitorPlan(long h, ByteBuffer entries, int n, ByteBuffer params, int flags, ByteBuffer actionsOut,
                                   ByteBuffer editsOut, int maxEdits, ByteBuffer candidatesOut, ByteBuffer candidateRowsOut,
                                   int maxCandidates, ByteBuffer info);
+    // the edits this instance makes to ModelRecords itself: ops = mmp_registry_op rows (40 bytes: model, pod, op, flags, lastUsed,
+    // loadTime, loadCompleteTime); op 0 = loadLocal's put (MM.java:5204-5207), 1 = the load-failure path (:2484-2495; flag 1 =
+    // shuttingDown), 2 = deregisterModel (:2948-2958; flag 2 = loadTime != null), 3 = removeLocalModelCopyAsync (:6347-6365, sent
+    // after isLoadedElsewhere).  flags 1 = apply to the resident registry, 2 = dry run.  statusOut = one byte per op (1: the record
+    // changed and goes to registry.conditionalSetAndGet), editsOut = mmp_registry_op_edit rows (40 bytes) in op order, info = one
+    // mmp_registry_ops_info (56 bytes); info.truncated: nothing was applied.
+    static native int registryOps(long h, ByteBuffer ops, int n, long nowMs, int flags, ByteBuffer statusOut, ByteBuffer editsOut,
+                                  int maxEdits, ByteBuffer info);
     static native int scaleupPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer outs,
                                   ByteBuffer overloadedOut, ByteBuffer skipped);
     static native int scaledownPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer removedOut);

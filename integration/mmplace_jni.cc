@@ -405,6 +405,22 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_janitorPlan(JNIEnv 
                                   buf<mmp_cache_entry>(env, candidatesOut), buf<int32_t>(env, candidateRowsOut), maxCandidates,
                                   buf<mmp_janitor_info>(env, info)));
 }
+// loadLocal / the load-failure path / deregisterModel / removeLocalModelCopyAsync (MM.java:5204-5207, :2484-2495, :2948-2958,
+// :6347-6365) as a batch of ops: every buffer's capacity is checked here, the library only knows n / maxEdits
+// (a null statusOut is not returned).
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryOps(JNIEnv *env, jclass, jlong h, jobject ops, jint n, jlong nowMs,
+                                                                         jint flags, jobject statusOut, jobject editsOut, jint maxEdits,
+                                                                         jobject info)
+{
+    if (!holds<mmp_registry_op>(env, ops, n, "registryOps: ops shorter than n") ||
+        (statusOut && !holds<uint8_t>(env, statusOut, n, "registryOps: statusOut shorter than n")) ||
+        !holds<mmp_registry_op_edit>(env, editsOut, maxEdits, "registryOps: editsOut shorter than maxEdits") ||
+        !holds<mmp_registry_ops_info>(env, info, 1, "registryOps: info shorter than one mmp_registry_ops_info"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_registry_ops(ctx_of(h), buf<mmp_registry_op>(env, ops), n, nowMs, static_cast<uint32_t>(flags), buf<uint8_t>(env, statusOut),
+                                  buf<mmp_registry_op_edit>(env, editsOut), maxEdits, buf<mmp_registry_ops_info>(env, info)));
+}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaleupPlan(JNIEnv *env, jclass, jlong h, jobject entries,
                                                                          jint n, jobject params, jobject outs,
                                                                          jobject overloadedOut, jobject skipped)

@@ -128,6 +128,24 @@ JANITOR_INFO = np.dtype([("n_edits", "<i4"), ("n_candidates", "<i4"), ("n_ties",
                          ("n_action", "<i4", (7,))])
 assert JANITOR_ENTRY.itemsize == 80 and JANITOR_PARAMS.itemsize == 72 and JANITOR_EDIT.itemsize == 48 and JANITOR_INFO.itemsize == 48
 
+# mmp_registry_ops (loadLocal MM.java:5204-5207, the load-failure path :2484-2495, deregisterModel :2948-2958,
+# removeLocalModelCopyAsync :6347-6365)
+ROPS_APPLY, ROPS_DRY = 1, 2
+ROPS_BLOCK = 256  # ops per workgroup of the device pass (csrc/registry_ops_kernels.hpp: kRopsBlock)
+(ROP_REGISTER, ROP_LOAD_FAILED, ROP_DEREGISTER, ROP_SCALE_DOWN) = range(4)
+ROPF_SHUTTING_DOWN, ROPF_MATCH_TIME = 1, 2
+ROP_UNCHANGED, ROP_EDITED = 0, 1
+(ROP_EDIT_REM_LOADED, ROP_EDIT_REM_FAILED, ROP_EDIT_PUT_LOADED, ROP_EDIT_PUT_FAILED, ROP_EDIT_REPLACED, ROP_EDIT_TOUCHED,
+ ROP_EDIT_UNLOAD_SET) = (1, 2, 4, 8, 16, 32, 64)
+REGISTRY_OP = np.dtype([("model", "<i4"), ("pod", "<i4"), ("op", "<i4"), ("flags", "<u4"), ("last_used", "<i8"), ("load_time", "<i8"),
+                        ("load_complete_time", "<i8")])
+REGISTRY_OP_EDIT = np.dtype([("model", "<i4"), ("op_index", "<i4"), ("n_loaded_after", "<i4"), ("n_failed_after", "<i4"), ("flags", "<u4"),
+                             ("inserted_pos", "<i4"), ("last_used_after", "<i8"), ("last_unload_after", "<i8")])
+REGISTRY_OPS_INFO = np.dtype([("n_edits", "<i4"), ("n_unchanged", "<i4"), ("truncated", "<i4"), ("reserved", "<i4"),
+                              ("n_edited_op", "<i4", (4,)), ("n_unchanged_op", "<i4", (4,)), ("n_entries_added", "<i4"),
+                              ("n_entries_removed", "<i4")])
+assert REGISTRY_OP.itemsize == 40 and REGISTRY_OP_EDIT.itemsize == 40 and REGISTRY_OPS_INFO.itemsize == 56
+
 # mmp_registry_census (the registry listener's model counts, MM.java:2807-2854, :6852-6863)
 REGISTRY_STATS = np.dtype(
     [("n_models", "<i4"), ("n_loaded", "<i4"), ("n_failed", "<i4"), ("n_loaded_and_failed", "<i4"), ("n_unloaded_used", "<i4"),
@@ -243,6 +261,7 @@ SYMBOLS = [
     ("mmp_registry_missing_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_registry_missing_reset", C.c_int, [_P]),
     ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    ("mmp_registry_ops", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint32, _P, _P, C.c_int32, _P]),
     ("mmp_registry_census", C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),

@@ -38,6 +38,7 @@
 #include "rebalance_kernels.hpp"
 #include "registry_kernels.hpp"
 #include "janitor_kernels.hpp"
+#include "registry_ops_kernels.hpp"
 #include "census_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
@@ -4739,6 +4740,21 @@ try {
     return MMP_OK;
 } MMP_CATCH(c, "mmp_registry_missing_reset")
 
+namespace {
+// The model-indexed map of mmp_janitor_plan and mmp_registry_ops covers M words, all -1 (called with batch_mu).  The one M-sized
+// fill: when the map is new, grew or was left in doubt.  It is in doubt from here on (jn_map_n = 0) until the caller has seen the
+// kernel that clears its words again complete, and says so with jn_map_n = M.
+int model_map_cover(mmp_ctx *c, int32_t M, hipStream_t st)
+{
+    if (c->jn_map_n < M || (size_t)M * 4 > c->jn_map.cap) {
+        HIP_TRY(c, c->jn_map.ensure((size_t)std::max(M, 1) * 4));
+        HIP_TRY(c, hipMemsetAsync(c->jn_map.p, 0xff, (size_t)std::max(M, 1) * 4, st));
+    }
+    c->jn_map_n = 0;
+    return MMP_OK;
+}
+}  // namespace
+
 int mmp_janitor_plan(mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *p, uint32_t flags,
                      uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *cands_out,
                      int32_t *cand_rows_out, int32_t max_cands, mmp_janitor_info *info)
@@ -4800,11 +4816,7 @@ try {
     HIP_TRY(c, c->p_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
     HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_janitor_edit)));
     HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
-    if (c->jn_map_n < M || (size_t)M * 4 > c->jn_map.cap) {  // the one M-sized fill: when the map is new, grew or was left in doubt
-        HIP_TRY(c, c->jn_map.ensure((size_t)std::max(M, 1) * 4));
-        HIP_TRY(c, hipMemsetAsync(c->jn_map.p, 0xff, (size_t)std::max(M, 1) * 4, st));
-    }
-    c->jn_map_n = 0;  // in doubt until the finish kernel has been seen to complete
+    if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the finish kernel has been seen to complete)
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows
     const mmp_model_row *models = c->models.as<mmp_model_row>();
     const int32_t *ent_pod = c->ent_pod.as<int32_t>();
@@ -4883,6 +4895,115 @@ try {
     if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
     return MMP_OK;
 } MMP_CATCH(c, "mmp_janitor_plan")
+
+int mmp_registry_ops(mmp_ctx *c, const mmp_registry_op *ops, int32_t n, int64_t now, uint32_t flags, uint8_t *status_out,
+                     mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info)
+try {
+    if (!c || !info || n < 0 || max_edits < 0 || (n > 0 && !ops) || (max_edits > 0 && !edits_out) || now <= 0 ||
+        (flags & ~(MMP_ROPS_APPLY | MMP_ROPS_DRY)) || flags == (MMP_ROPS_APPLY | MMP_ROPS_DRY))
+        return fail(c, MMP_EINVAL, "mmp_registry_ops: bad argument");
+    // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
+    // too.  The state lock is taken only by an apply, for its in-place rewrite.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_registry_ops: not available on a pod-axis shard context");
+    const int32_t M = c->n_models, P = c->snap.P;
+    // the ops index the map, the rows and the instance table: their ranges are settled here, before any kernel reads them (that
+    // no model is named twice is settled by the first kernel, on the map)
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_registry_op &o = ops[i];
+        if (o.model < 0 || o.model >= M) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d names model %d of %d", i, o.model, M);
+        if (o.pod < 0 || o.pod >= P) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d names pod %d of %d", i, o.pod, P);
+        if (o.op < MMP_ROP_REGISTER || o.op > MMP_ROP_SCALE_DOWN) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d has kind %d", i, o.op);
+        if (o.flags & ~(MMP_ROPF_SHUTTING_DOWN | MMP_ROPF_MATCH_TIME)) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d has flags %u", i, o.flags);
+    }
+    if (n == 0) {
+        *info = mmp_registry_ops_info{};
+        return MMP_OK;
+    }
+    const bool apply = flags & MMP_ROPS_APPLY;
+    // an apply appends at most the live entries and one more per op to the arena: refused before anything is done
+    if (apply && (int64_t)c->n_entries + c->ent_live + n > INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_registry_ops: entry arena overflow; reload the registry");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int nb = div_up(n, kRopsBlock);
+    const int32_t cap_e = std::min(max_edits, n);
+    // (the janitor's upload, scalar and row-sized scratch buffers serve this call too: both hold batch_mu throughout)
+    HIP_TRY(c, c->jn_in.ensure((size_t)n * sizeof(mmp_registry_op)));
+    HIP_TRY(c, c->jn_js.ensure(std::max(sizeof(RopsScalars), sizeof(JanitorScalars))));
+    HIP_TRY(c, c->jn_tmp.ensure((size_t)n));
+    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->p_counts.ensure((size_t)nb * 3 * 4));
+    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_registry_op_edit)));
+    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the scatter kernel has been seen to complete)
+    const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what the janitor's insert reads
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    const int32_t *ent_pod = c->ent_pod.as<int32_t>();
+    const int64_t *ent_time = c->ent_time.as<int64_t>();
+    const mmp_registry_op *d_ops = c->jn_in.as<mmp_registry_op>();
+    int32_t *map = c->jn_map.as<int32_t>();
+    RopsScalars *rs = c->jn_js.as<RopsScalars>();
+    PruneScalars *ps = c->p_ps.as<PruneScalars>();
+    uint8_t *d_status = c->jn_tmp.as<uint8_t>();
+    HIP_TRY(c, hipMemcpyAsync(c->jn_in.p, ops, (size_t)n * sizeof(mmp_registry_op), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(rs, 0, sizeof(RopsScalars), st));
+    HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
+    KT_BEGIN(c, st);  // device span of the evaluation
+    hipLaunchKernelGGL(rops_count_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
+                       c->p_counts.as<int32_t>());
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, max_edits, INT32_MAX, ps);
+    hipLaunchKernelGGL(rops_scatter_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
+                       c->p_counts.as<int32_t>(), c->p_edits.as<mmp_registry_op_edit>(), cap_e, c->p_koff.as<int32_t>(), d_status);
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    RopsScalars hr{};
+    PruneScalars h{};
+    HIP_TRY(c, hipMemcpyAsync(&hr, rs, sizeof hr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->jn_map_n = M;
+    kt_collect(c);
+    if (hr.n_dup != 0) return fail(c, MMP_EINVAL, "mmp_registry_ops: %d ops name a model another op of the call names", hr.n_dup);
+    const int32_t ne = std::min(h.n_edits, max_edits);
+    if (status_out) HIP_TRY(c, copy_sync(c, status_out, d_status, (size_t)n, hipMemcpyDeviceToHost));
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_registry_op_edit), hipMemcpyDeviceToHost));
+    *info = mmp_registry_ops_info{};
+    info->n_edits = h.n_edits;
+    info->n_unchanged = n - h.n_edits;
+    info->truncated = h.truncated;
+    for (int k = 0; k < 4; k++) {
+        info->n_edited_op[k] = hr.n_edited[k];
+        info->n_unchanged_op[k] = hr.n_unchanged[k];
+    }
+    info->n_entries_added = hr.n_added;
+    info->n_entries_removed = hr.n_removed;
+    if (!apply || h.truncated || h.n_edits == 0) return MMP_OK;
+
+    // apply: the edited records are rebuilt at the end of the arena ON THE DEVICE, beyond anything a published row refers to; then
+    // the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
+    const double eval_ms = c->last_kernel_ms;
+    const int32_t E = h.n_edits, base = c->n_entries;
+    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(rops_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_registry_op_edit>(), c->p_koff.as<int32_t>(), E,
+                       d_ops, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept,
+                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
+    if (c->prof && eval_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += eval_ms;  // the call's device span: evaluation + apply
+    for (int32_t e = 0; e < E; e++) {
+        const int32_t cnt = edits_out[e].n_loaded_after + edits_out[e].n_failed_after;
+        c->ent_live += (int64_t)cnt - c->m_cnt[edits_out[e].model];
+        c->m_cnt[edits_out[e].model] = cnt;
+    }
+    // more garbage than live entries (and enough to matter): squeeze the arena
+    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_ops")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

@@ -642,6 +642,36 @@ class Solver:
         ne, nc = min(max_edits, int(info[0]["n_edits"])), min(max_candidates, int(info[0]["n_candidates"]))
         return actions[:n].copy(), edits[:ne].copy(), cands[:nc].copy(), rows[:nc].copy(), info[0].copy()
 
+    def registry_ops(self, ops, now: int, apply: bool = True, dry: bool = False, max_edits: int = 1024):
+        """The edits an instance makes to ModelRecords itself (loadLocal MM.java:5204-5207, the load-failure path :2484-2495,
+        deregisterModel :2948-2958, removeLocalModelCopyAsync :6347-6365), a batch of mmp_registry_op rows: (status, edits, info),
+        the edits in op order.  The buffer is regrown to the call's total when it reports `truncated` (a truncated call changes
+        nothing)."""
+        from ._lib import ROPS_APPLY, ROPS_DRY
+        flags = ROPS_DRY if dry else (ROPS_APPLY if apply else 0)
+        while True:
+            out = self.registry_ops_raw(ops, now, flags, max_edits)
+            info = out[2]
+            if not info["truncated"]:
+                break
+            max_edits = max(max_edits, int(info["n_edits"]))
+        if flags == ROPS_APPLY and int(info["n_edits"]) and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return out
+
+    def registry_ops_raw(self, ops, now, flags, max_edits, want_status=True):
+        """One mmp_registry_ops call with exactly this capacity (0: a NULL buffer): (status, edits prefix, info)."""
+        from ._lib import REGISTRY_OP, REGISTRY_OP_EDIT, REGISTRY_OPS_INFO
+        ops = np.ascontiguousarray(ops, dtype=REGISTRY_OP)
+        n = len(ops)
+        info = np.zeros(1, dtype=REGISTRY_OPS_INFO)
+        status = np.zeros(max(n, 1), np.uint8)
+        edits = np.zeros(max(max_edits, 1), dtype=REGISTRY_OP_EDIT)
+        self._ck(self.lib.mmp_registry_ops(self.h, ptr(ops) if n else None, n, int(now), int(flags), ptr(status) if n and want_status else None,
+                                           ptr(edits) if max_edits else None, int(max_edits), ptr(info)))
+        ne = min(max_edits, int(info[0]["n_edits"]))
+        return status[:n].copy(), edits[:ne].copy(), info[0].copy()
+
     def registry_census(self):
         """The registry listener's model counts (MM.java:2807-2854, :6852-6863) over the resident registry: (stats, pod_loaded,
         pod_failed, type_stats) — one mmp_registry_stats row, per pod slot of the staged instance table the records that hold it in
