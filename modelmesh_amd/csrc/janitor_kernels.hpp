@@ -12,7 +12,7 @@
 //                           between runs), the stop index
 //   janitor_count_kernel    one lane per model: row, map word, entry walk for self_pod; a model with neither an entry for
 //                           self_pod nor a cache row ends there.  Per-workgroup counts of (edits, candidates, entries kept)
-//   prune_scan_kernel       (registry_kernels.hpp) the one-workgroup scan of those triples
+//   prune_scan_kernel       (registry_kernels.hpp) the one-workgroup scan of those triples (protocol: triple_count there)
 //   janitor_scatter_kernel  the same walk: edits in registry order, candidates (time, row) in registry order
 //   janitor_tie_kernel      a candidate is dropped when an EARLIER one (registry order) has its time       } all pairs over the
 //   janitor_rank_kernel     rank = kept candidates with a smaller time; the candidate row scattered there  } candidates, for
@@ -225,6 +225,7 @@ __device__ __forceinline__ bool janitor_model(const mmp_model_row *__restrict__ 
     return true;
 }
 
+// (its own copy of triple_count: with the helper this kernel took two more VGPRs and two more SGPRs)
 __global__ __launch_bounds__(kJanBlock) void janitor_count_kernel(const mmp_model_row *__restrict__ models, int32_t M,
                                                                   const int32_t *__restrict__ ent_pod, const int64_t *__restrict__ ent_time,
                                                                   const mmp_pod_row *__restrict__ pods, int32_t P,
@@ -280,7 +281,6 @@ __global__ __launch_bounds__(kJanBlock) void janitor_scatter_kernel(const mmp_mo
                                                                     int32_t *__restrict__ keep_off, int64_t *__restrict__ cand_time,
                                                                     int32_t *__restrict__ cand_row)
 {
-    __shared__ int32_t s_e[kJanBlock / 64], s_c[kJanBlock / 64], s_k[kJanBlock / 64];
     if (ps->n_edits == 0 && ps->n_removed == 0) return;  // (uniform: the whole grid leaves)
     const int i = blockIdx.x * kJanBlock + threadIdx.x;
     JanEval ev{};
@@ -291,24 +291,9 @@ __global__ __launch_bounds__(kJanBlock) void janitor_scatter_kernel(const mmp_mo
         cand = ev.cand;
         if (edit) kept = ev.nl + ev.nf;
     }
-    const uint64_t be = __ballot(edit), bc = __ballot(cand);
-    const int32_t ik = wave_incl_scan_i32(kept);
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    if (lane == 63) {
-        s_e[w] = __popcll(be);
-        s_c[w] = __popcll(bc);
-        s_k[w] = ik;
-    }
-    __syncthreads();
-    int32_t oe = block_off[3 * blockIdx.x + 0], oc = block_off[3 * blockIdx.x + 1], ok = block_off[3 * blockIdx.x + 2];
-    for (int x = 0; x < w; x++) {
-        oe += s_e[x];
-        oc += s_c[x];
-        ok += s_k[x];
-    }
-    const uint64_t below = (1ull << lane) - 1ull;
+    const TripleOff o = triple_offsets<kCol1Count>(edit, cand, kept, block_off);
     if (edit) {
-        const int32_t x = oe + __popcll(be & below);
+        const int32_t x = o.e;
         if (x < max_edits) {
             mmp_janitor_edit ed;
             ed.model = i;
@@ -321,11 +306,11 @@ __global__ __launch_bounds__(kJanBlock) void janitor_scatter_kernel(const mmp_mo
             ed.inserted_pos = ev.ins_pos;
             ed.entry = row;
             edits[x] = ed;
-            keep_off[x] = ok + ik - kept;
+            keep_off[x] = o.k;
         }
     }
     if (cand) {
-        const int32_t x = oc + __popcll(bc & below);
+        const int32_t x = o.r;
         if (x < n) {  // (a candidate has a cache row of its own: there are never more than n)
             cand_time[x] = ev.cand_time;
             cand_row[x] = row;

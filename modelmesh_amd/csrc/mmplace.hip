@@ -345,13 +345,19 @@ struct mmp_ctx {
     int64_t ent_live = 0;                 // entries still referenced by a row
     DevBuf u_idx, u_rows, u_cnt, u_offs, u_tmp;
     // mmp_registry_prune: `missings` (MM.java:6776) by pod index — first time seen missing, 0 = no mark — for miss_n pod slots, and
-    // the call's scratch (registry_kernels.hpp).  Owned by batch_mu; only the prune kernels, on c->stream, touch them.
-    DevBuf miss_since, p_state, p_seen, p_ps, p_counts, p_edits, p_removed, p_koff;
+    // the scratch only the prune uses (registry_kernels.hpp).  Owned by batch_mu; only the prune kernels, on c->stream, touch them.
+    DevBuf miss_since, p_state, p_seen, p_removed;
     int32_t miss_n = 0;
-    // mmp_janitor_plan (janitor_kernels.hpp): the model -> cache row map, all -1 between runs over its first jn_map_n words (0: not
-    // known to be clear), the uploaded rows, the call's scalars and its row-sized scratch.  Owned by batch_mu, used on c->stream.
-    DevBuf jn_map, jn_in, jn_js, jn_tmp;
-    int32_t jn_map_n = 0;
+    // The scratch the registry plans share (mmp_registry_prune, mmp_janitor_plan, mmp_registry_ops).  The sharing is safe by one
+    // rule: every user holds batch_mu from its first use of a buffer to its last, and uses it on c->stream only.
+    struct PlanScratch {
+        DevBuf totals, block_counts;   // PruneScalars from prune_scan_kernel; the per-workgroup triples, then offsets
+        DevBuf edits, keep_off;        // the call's edit structs in output order; where each one's kept entries start
+        DevBuf rows_in, call_scalars;  // the caller's rows (cache rows / ops); the call's own counters (JanitorScalars / RopsScalars)
+        DevBuf row_tmp;                // row-sized scratch (janitor: carved; ops: the status bytes)
+        DevBuf model_map;              // model -> row, all -1 between runs over its first model_map_n words (0: not known to be clear)
+        int32_t model_map_n = 0;
+    } plan;
     std::vector<uint64_t> u_stamp;        // per model: (call generation, row index) of the last row naming it
     uint32_t u_gen = 0;
     // (the registry view resolved against a snapshot, place_kernel.hpp: ResolvedModel, lives in SnapSide)
@@ -1049,7 +1055,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->p_ps, &c->p_counts, &c->p_edits, &c->p_removed, &c->p_koff, &c->jn_map, &c->jn_in, &c->jn_js, &c->jn_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -1433,7 +1439,7 @@ int compact_registry(mmp_ctx *c)
 }
 
 // Make room for `count` registry rows and `base + n_entries` arena entries (called with batch_mu, by mmp_models_upsert and by an
-// applied mmp_registry_prune, before they append entries at `base`).
+// applied registry plan, registry_apply_edits, before they append entries at `base`).
 int registry_grow(mmp_ctx *c, int32_t count, int32_t base, int32_t n_entries)
 {
     hipStream_t st = c->stream;
@@ -1484,7 +1490,7 @@ int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_aft
         std::lock_guard<std::shared_mutex> g(c->mu);
         HIP_TRY(c, quiesce_decisions(c));
         const bool resolved = cur_side(c).rmodels_ok && c->committed;
-        if (!bracket_open) KT_BEGIN(c, st);  // (an applied prune opened the bracket in front of its build kernel)
+        if (!bracket_open) KT_BEGIN(c, st);  // (registry_apply_edits opened the bracket in front of the plan's build kernel)
         hipLaunchKernelGGL(upsert_models_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, c->snap, c->u_idx.as<int32_t>(),
                            c->u_rows.as<mmp_model_row>(), k, c->ent_pod.as<int32_t>(), c->models.as<mmp_model_row>(),
                            resolved ? cur_side(c).rmodels.as<ResolvedModel>() : nullptr, resolved ? cur_side(c).mtw.as<int32_t>() : nullptr);
@@ -1506,6 +1512,60 @@ int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_aft
     if (se == hipSuccess) c->reg_pending.store(false, std::memory_order_release);  // (a failed wait leaves later launches ordered behind the event)
     HIP_TRY(c, se);
     kt_collect(c);
+    return MMP_OK;
+}
+
+// More garbage in the arena than live entries (and enough to matter): squeeze it (called with batch_mu, after a rewrite).
+int squeeze_if_garbage(mmp_ctx *c)
+{
+    return (int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16) ? compact_registry(c) : (int)MMP_OK;
+}
+
+// The apply of a registry plan (mmp_registry_prune, mmp_janitor_plan, mmp_registry_ops; called with batch_mu, the evaluation
+// collected): the E edited records, n_kept entries in all, are rebuilt at the end of the arena ON THE DEVICE, beyond anything a
+// published row refers to; then the rows are rewritten in place exactly as a registry event's are (registry_rewrite).
+// launch_build(base, arena_end) only enqueues the call's build kernel on c->stream, inside the bracket opened here; after_rewrite
+// runs once the registry holds the edited records, before the arena may be squeezed.  `edits`: the E edit structs, on the host.
+extern "C++" template <class Edit, class LaunchBuild>  // (a template inside the file's extern "C" block)
+int registry_apply_edits(mmp_ctx *c, int32_t E, int32_t n_kept, const Edit *edits, LaunchBuild &&launch_build,
+                         const std::function<int()> &after_rewrite = {})
+{
+    const double eval_ms = c->last_kernel_ms;
+    const int32_t M = c->n_models, base = c->n_entries;
+    if (const int rc = registry_grow(c, M, base, n_kept)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
+    KT_BEGIN(c, c->stream);
+    launch_build(base, base + n_kept);
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, E, M, base + n_kept, true)) return rc;
+    if (c->prof && eval_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += eval_ms;  // the call's device span: evaluation + apply
+    // the host shadow, from the counts the edits leave.  (The prune's edits carry n_removed as well: m_cnt[model] == n_loaded +
+    // n_failed holds before the call, so this is m_cnt[model] -= n_removed, and ent_live falls by the removed entries.)
+    for (int32_t e = 0; e < E; e++) {
+        const int32_t cnt = edits[e].n_loaded_after + edits[e].n_failed_after;
+        c->ent_live += (int64_t)cnt - c->m_cnt[edits[e].model];
+        c->m_cnt[edits[e].model] = cnt;
+    }
+    if (after_rewrite)
+        if (const int rc = after_rewrite()) return rc;
+    return squeeze_if_garbage(c);
+}
+// What the registry plans refuse before they touch the device, in the three places where each call checks it: the flag word among
+// the arguments (before batch_mu is taken), the context's state, and, behind the call's own row checks, the arena's room: an apply
+// appends at most the live entries and `extra` more (one per row of the call that can put an entry).
+constexpr uint32_t kPlanFlags = MMP_PRUNE_APPLY | MMP_PRUNE_DRY;
+static_assert(MMP_JANITOR_APPLY == MMP_PRUNE_APPLY && MMP_ROPS_APPLY == MMP_PRUNE_APPLY && MMP_JANITOR_DRY == MMP_PRUNE_DRY && MMP_ROPS_DRY == MMP_PRUNE_DRY, "");
+inline bool plan_flags_bad(uint32_t flags) { return (flags & ~kPlanFlags) || flags == kPlanFlags; }
+int plan_state_guard(mmp_ctx *c, const char *fn)
+{
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "%s: not available on a pod-axis shard context", fn);
+    return MMP_OK;
+}
+int plan_arena_guard(mmp_ctx *c, const char *fn, bool apply, int32_t extra)
+{
+    if (apply && (int64_t)c->n_entries + c->ent_live + extra > INT32_MAX) return fail(c, MMP_EINVAL, "%s: entry arena overflow; reload the registry", fn);
     return MMP_OK;
 }
 }  // namespace
@@ -1567,9 +1627,7 @@ try {
     HIP_TRY(c, hipMemcpyAsync(c->u_rows.p, h_rows.data(), (size_t)k * sizeof(mmp_model_row), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipStreamSynchronize(st));  // the pageable sources above are this call's stack / the caller's arrays
     if (const int rc = registry_rewrite(c, k, count, base + n_entries)) return rc;
-    // more garbage than live entries (and enough to matter): squeeze the arena
-    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
-    return MMP_OK;
+    return squeeze_if_garbage(c);
 } MMP_CATCH(c, "mmp_models_upsert")
 
 /* ---- commit: rank + permute + bitmaps + stats, all on the device --------- */
@@ -4559,17 +4617,14 @@ int mmp_registry_prune(mmp_ctx *c, int32_t self_pod, int64_t now, int64_t gone_a
                        mmp_prune_info *info)
 try {
     if (!c || !info || max_edits < 0 || max_removed < 0 || (max_edits > 0 && !edits_out) || (max_removed > 0 && !removed_out) || now <= 0 ||
-        gone_after < 0 || age_on_add < 0 || (flags & ~(MMP_PRUNE_APPLY | MMP_PRUNE_DRY)) || flags == (MMP_PRUNE_APPLY | MMP_PRUNE_DRY))
+        gone_after < 0 || age_on_add < 0 || plan_flags_bad(flags))
         return fail(c, MMP_EINVAL, "mmp_registry_prune: bad argument");
     // batch_mu owns c->stream, the scratch and the missing map for the whole call, and every writer of the state this call reads
     // (commit, the loaders, registry events) takes it too.  The state lock is taken only by an apply, for its in-place rewrite.
     std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_registry_prune: not available on a pod-axis shard context");
+    if (const int rc = plan_state_guard(c, "mmp_registry_prune")) return rc;
     const bool apply = flags & MMP_PRUNE_APPLY, dry = flags & MMP_PRUNE_DRY;
-    // an apply appends at most the live entries to the arena: refused before anything advances
-    if (apply && (int64_t)c->n_entries + c->ent_live > INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_registry_prune: entry arena overflow; reload the registry");
+    if (const int rc = plan_arena_guard(c, "mmp_registry_prune", apply, 0)) return rc;  // (refused before anything advances)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     const int32_t M = c->n_models, P = c->snap.P;
@@ -4579,11 +4634,11 @@ try {
     const int32_t n_map = c->miss_n;
     HIP_TRY(c, c->p_state.ensure((size_t)std::max(P, 1)));
     HIP_TRY(c, c->p_seen.ensure((size_t)std::max(P, 1)));
-    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
-    HIP_TRY(c, c->p_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
-    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_prune_edit)));
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
+    HIP_TRY(c, c->plan.edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_prune_edit)));
     HIP_TRY(c, c->p_removed.ensure((size_t)std::max(cap_r, 1) * sizeof(mmp_prune_removed)));
-    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    HIP_TRY(c, c->plan.keep_off.ensure((size_t)std::max(cap_e, 1) * 4));
     PruneArgs A{};
     A.self_pod = self_pod;
     A.P = P;
@@ -4592,7 +4647,7 @@ try {
     A.repaired_last_used = (int64_t)((uint64_t)now - 3ull * (uint64_t)age_on_add);  // :6844
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what mmp_proactive_plan reads
     const mmp_model_row *models = c->models.as<mmp_model_row>();
-    PruneScalars *ps = c->p_ps.as<PruneScalars>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
     uint8_t *state = c->p_state.as<uint8_t>(), *seen = c->p_seen.as<uint8_t>();
     int64_t *since = c->miss_since.as<int64_t>();
     // the marks advance with the scan only when nothing can fail afterwards: always without an apply, and with an apply that
@@ -4602,11 +4657,11 @@ try {
     hipLaunchKernelGGL(prune_pods_kernel, dim3(std::max(div_up(P, 256), 1)), dim3(256), 0, st, pods, A, since, state, seen, ps);
     if (nb > 0) {
         hipLaunchKernelGGL(prune_count_kernel, dim3(nb), dim3(kPruneBlock), 0, st, models, M, c->ent_pod.as<int32_t>(),
-                           c->ent_time.as<int64_t>(), A, state, seen, c->p_counts.as<int32_t>(), ps);
-        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, max_edits, max_removed, ps);
+                           c->ent_time.as<int64_t>(), A, state, seen, c->plan.block_counts.as<int32_t>(), ps);
+        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, max_edits, max_removed, ps);
         hipLaunchKernelGGL(prune_scatter_kernel, dim3(nb), dim3(kPruneBlock), 0, st, models, M, c->ent_pod.as<int32_t>(),
-                           c->ent_time.as<int64_t>(), A, state, c->p_counts.as<int32_t>(), ps, c->p_edits.as<mmp_prune_edit>(), cap_e,
-                           c->p_removed.as<mmp_prune_removed>(), cap_r, c->p_koff.as<int32_t>());
+                           c->ent_time.as<int64_t>(), A, state, c->plan.block_counts.as<int32_t>(), ps, c->plan.edits.as<mmp_prune_edit>(), cap_e,
+                           c->p_removed.as<mmp_prune_removed>(), cap_r, c->plan.keep_off.as<int32_t>());
     }
     hipLaunchKernelGGL(prune_marks_kernel, dim3(std::max(div_up(n_map, 256), 1)), dim3(256), 0, st, A, n_map, state, seen, since, advance, ps);
     KT_END(c, st);
@@ -4616,7 +4671,7 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     const int32_t ne = std::min(h.n_edits, max_edits), nr = std::min(h.n_removed, max_removed);
-    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_prune_edit), hipMemcpyDeviceToHost));
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_prune_edit), hipMemcpyDeviceToHost));
     if (nr > 0) HIP_TRY(c, copy_sync(c, removed_out, c->p_removed.p, (size_t)nr * sizeof(mmp_prune_removed), hipMemcpyDeviceToHost));
     info->n_edits = h.n_edits;
     info->n_removed = h.n_removed;
@@ -4628,29 +4683,18 @@ try {
     info->reserved = 0;
     if (!apply || h.truncated || h.n_edits == 0) return MMP_OK;
 
-    // apply: the surviving entries of the edited records are appended to the arena ON THE DEVICE, beyond anything a published row
-    // refers to; then the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
-    const double scan_ms = c->last_kernel_ms;
-    const int32_t E = h.n_edits, base = c->n_entries;
-    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
-    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
-    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(prune_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_prune_edit>(), c->p_koff.as<int32_t>(), E,
-                       c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept, A, state,
-                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
-    if (c->prof && scan_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += scan_ms;  // the call's device span: scan + apply
-    for (int32_t e = 0; e < E; e++) c->m_cnt[edits_out[e].model] -= edits_out[e].n_removed;
-    c->ent_live -= h.n_removed;
-    // the registry holds the edited records: now the marks advance
-    hipLaunchKernelGGL(prune_marks_kernel, dim3(std::max(div_up(n_map, 256), 1)), dim3(256), 0, st, A, n_map, state, seen, since, kMarksAdvance, ps);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    // more garbage than live entries (and enough to matter): squeeze the arena
-    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
-    return MMP_OK;
+    return registry_apply_edits(
+        c, h.n_edits, h.n_kept, edits_out, [&](int32_t base, int32_t arena_end) {  // the surviving entries of the edited records
+            hipLaunchKernelGGL(prune_build_kernel, dim3(div_up(h.n_edits, 256)), dim3(256), 0, st, c->plan.edits.as<mmp_prune_edit>(),
+                               c->plan.keep_off.as<int32_t>(), h.n_edits, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(),
+                               c->ent_time.as<int64_t>(), base, arena_end, A, state, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+        },
+        [&] {  // the registry holds the edited records: now the marks advance
+            hipLaunchKernelGGL(prune_marks_kernel, dim3(std::max(div_up(n_map, 256), 1)), dim3(256), 0, st, A, n_map, state, seen, since, kMarksAdvance, ps);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(st));
+            return (int)MMP_OK;
+        });
 } MMP_CATCH(c, "mmp_registry_prune")
 
 int mmp_registry_census(mmp_ctx *c, mmp_registry_stats *out, int32_t *pod_loaded_out, int32_t *pod_failed_out, int32_t max_pods,
@@ -4742,15 +4786,15 @@ try {
 
 namespace {
 // The model-indexed map of mmp_janitor_plan and mmp_registry_ops covers M words, all -1 (called with batch_mu).  The one M-sized
-// fill: when the map is new, grew or was left in doubt.  It is in doubt from here on (jn_map_n = 0) until the caller has seen the
-// kernel that clears its words again complete, and says so with jn_map_n = M.
+// fill: when the map is new, grew or was left in doubt.  It is in doubt from here on (model_map_n = 0) until the caller has seen the
+// kernel that clears its words again complete, and says so with model_map_n = M.
 int model_map_cover(mmp_ctx *c, int32_t M, hipStream_t st)
 {
-    if (c->jn_map_n < M || (size_t)M * 4 > c->jn_map.cap) {
-        HIP_TRY(c, c->jn_map.ensure((size_t)std::max(M, 1) * 4));
-        HIP_TRY(c, hipMemsetAsync(c->jn_map.p, 0xff, (size_t)std::max(M, 1) * 4, st));
+    if (c->plan.model_map_n < M || (size_t)M * 4 > c->plan.model_map.cap) {
+        HIP_TRY(c, c->plan.model_map.ensure((size_t)std::max(M, 1) * 4));
+        HIP_TRY(c, hipMemsetAsync(c->plan.model_map.p, 0xff, (size_t)std::max(M, 1) * 4, st));
     }
-    c->jn_map_n = 0;
+    c->plan.model_map_n = 0;
     return MMP_OK;
 }
 }  // namespace
@@ -4762,13 +4806,12 @@ try {
     if (!c || !p || !info || n < 0 || max_edits < 0 || max_cands < 0 || (n > 0 && (!entries || !actions_out)) || (max_edits > 0 && !edits_out) ||
         (max_cands > 0 && (!cands_out || !cand_rows_out)) || p->now <= 0 || p->janitor_freq_secs < 0 || p->load_timeout_ms < 0 ||
         p->min_stale_age_ms < 0 || p->load_failure_expiry_ms < 0 || p->short_expiry_recent_use_ms < 0 || p->unload_attempt_recent_ms < 0 ||
-        p->lastused_age_on_add_ms < 0 || (flags & ~(MMP_JANITOR_APPLY | MMP_JANITOR_DRY)) || flags == (MMP_JANITOR_APPLY | MMP_JANITOR_DRY))
+        p->lastused_age_on_add_ms < 0 || plan_flags_bad(flags))
         return fail(c, MMP_EINVAL, "mmp_janitor_plan: bad argument");
     // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
     // too.  The state lock is taken only by an apply, for its in-place rewrite.
     std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_janitor_plan: not available on a pod-axis shard context");
+    if (const int rc = plan_state_guard(c, "mmp_janitor_plan")) return rc;
     const int32_t M = c->n_models, P = c->snap.P;
     if (p->self_pod < 0 || p->self_pod >= P) return fail(c, MMP_EINVAL, "mmp_janitor_plan: self_pod %d of %d", p->self_pod, P);
     {
@@ -4792,9 +4835,7 @@ try {
         return MMP_OK;
     }
     const bool apply = flags & MMP_JANITOR_APPLY;
-    // an apply appends at most the live entries and one more per row to the arena: refused before anything is done
-    if (apply && (int64_t)c->n_entries + c->ent_live + n > INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_janitor_plan: entry arena overflow; reload the registry");
+    if (const int rc = plan_arena_guard(c, "mmp_janitor_plan", apply, n)) return rc;  // (refused before anything is done)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     const int nb = div_up(M, kJanBlock), n1 = std::max(n, 1);
@@ -4808,28 +4849,28 @@ try {
     };
     const size_t o_ctime = carve((size_t)n1 * 8), o_crow = carve((size_t)n1 * 4), o_drop = carve((size_t)n1), o_act = carve((size_t)n1),
                  o_cands = carve((size_t)n1 * sizeof(mmp_cache_entry)), o_orow = carve((size_t)n1 * 4);
-    HIP_TRY(c, c->jn_tmp.ensure(off));
-    char *tmp = c->jn_tmp.as<char>();
-    HIP_TRY(c, c->jn_in.ensure((size_t)n1 * sizeof(mmp_janitor_entry)));
-    HIP_TRY(c, c->jn_js.ensure(sizeof(JanitorScalars)));
-    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
-    HIP_TRY(c, c->p_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
-    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_janitor_edit)));
-    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    HIP_TRY(c, c->plan.row_tmp.ensure(off));
+    char *tmp = c->plan.row_tmp.as<char>();
+    HIP_TRY(c, c->plan.rows_in.ensure((size_t)n1 * sizeof(mmp_janitor_entry)));
+    HIP_TRY(c, c->plan.call_scalars.ensure(sizeof(JanitorScalars)));
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)std::max(nb, 1) * 3 * 4));
+    HIP_TRY(c, c->plan.edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_janitor_edit)));
+    HIP_TRY(c, c->plan.keep_off.ensure((size_t)std::max(cap_e, 1) * 4));
     if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the finish kernel has been seen to complete)
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows
     const mmp_model_row *models = c->models.as<mmp_model_row>();
     const int32_t *ent_pod = c->ent_pod.as<int32_t>();
     const int64_t *ent_time = c->ent_time.as<int64_t>();
-    const mmp_janitor_entry *d_in = c->jn_in.as<mmp_janitor_entry>();
-    int32_t *map = c->jn_map.as<int32_t>();
-    JanitorScalars *js = c->jn_js.as<JanitorScalars>();
-    PruneScalars *ps = c->p_ps.as<PruneScalars>();
+    const mmp_janitor_entry *d_in = c->plan.rows_in.as<mmp_janitor_entry>();
+    int32_t *map = c->plan.model_map.as<int32_t>();
+    JanitorScalars *js = c->plan.call_scalars.as<JanitorScalars>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
     int64_t *ctime = (int64_t *)(tmp + o_ctime);
     int32_t *crow = (int32_t *)(tmp + o_crow), *orow = (int32_t *)(tmp + o_orow);
     uint8_t *drop = (uint8_t *)(tmp + o_drop), *act = (uint8_t *)(tmp + o_act);
     mmp_cache_entry *d_cands = (mmp_cache_entry *)(tmp + o_cands);
-    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->jn_in.p, entries, (size_t)n * sizeof(mmp_janitor_entry), hipMemcpyHostToDevice, st));
+    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, entries, (size_t)n * sizeof(mmp_janitor_entry), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(js, 0, sizeof(JanitorScalars), st));
     HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
     KT_BEGIN(c, st);  // device span of the plan
@@ -4837,10 +4878,10 @@ try {
     if (n > 0) hipLaunchKernelGGL(janitor_entry_kernel, dim3(gn), dim3(256), 0, st, d_in, n, map, *p, js);
     if (nb > 0) {
         hipLaunchKernelGGL(janitor_count_kernel, dim3(nb), dim3(kJanBlock), 0, st, models, M, ent_pod, ent_time, pods, P, map, d_in, n, *p, js,
-                           c->p_counts.as<int32_t>());
-        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
+                           c->plan.block_counts.as<int32_t>());
+        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
         hipLaunchKernelGGL(janitor_scatter_kernel, dim3(nb), dim3(kJanBlock), 0, st, models, M, ent_pod, ent_time, pods, P, map, d_in, n, *p, js,
-                           c->p_counts.as<int32_t>(), ps, c->p_edits.as<mmp_janitor_edit>(), cap_e, c->p_koff.as<int32_t>(), ctime, crow);
+                           c->plan.block_counts.as<int32_t>(), ps, c->plan.edits.as<mmp_janitor_edit>(), cap_e, c->plan.keep_off.as<int32_t>(), ctime, crow);
     }
     if (n > 0) {
         const int gt = div_up(n, kJanTile);
@@ -4855,11 +4896,11 @@ try {
     HIP_TRY(c, hipMemcpyAsync(&hj, js, sizeof hj, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->jn_map_n = M;
+    c->plan.model_map_n = M;
     kt_collect(c);
     const int32_t ne = std::min(h.n_edits, max_edits), nc = std::min(hj.n_cands, max_cands);
     if (n > 0) HIP_TRY(c, copy_sync(c, actions_out, act, (size_t)n, hipMemcpyDeviceToHost));
-    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_janitor_edit), hipMemcpyDeviceToHost));
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_janitor_edit), hipMemcpyDeviceToHost));
     if (nc > 0) {
         HIP_TRY(c, copy_sync(c, cands_out, d_cands, (size_t)nc * sizeof(mmp_cache_entry), hipMemcpyDeviceToHost));
         HIP_TRY(c, copy_sync(c, cand_rows_out, orow, (size_t)nc * 4, hipMemcpyDeviceToHost));
@@ -4872,41 +4913,23 @@ try {
     for (int k = 0; k < 7; k++) info->n_action[k] = hj.n_action[k];
     if (!apply || info->truncated || h.n_edits == 0) return MMP_OK;
 
-    // apply: the edited records are rebuilt at the end of the arena ON THE DEVICE, beyond anything a published row refers to; then
-    // the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
-    const double plan_ms = c->last_kernel_ms;
-    const int32_t E = h.n_edits, base = c->n_entries;
-    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
-    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
-    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(janitor_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_janitor_edit>(), c->p_koff.as<int32_t>(), E,
-                       c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept, p->self_pod,
-                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
-    if (c->prof && plan_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += plan_ms;  // the call's device span: plan + apply
-    for (int32_t e = 0; e < E; e++) {
-        const int32_t cnt = edits_out[e].n_loaded_after + edits_out[e].n_failed_after;
-        c->ent_live += (int64_t)cnt - c->m_cnt[edits_out[e].model];
-        c->m_cnt[edits_out[e].model] = cnt;
-    }
-    // more garbage than live entries (and enough to matter): squeeze the arena
-    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
-    return MMP_OK;
+    return registry_apply_edits(c, h.n_edits, h.n_kept, edits_out, [&](int32_t base, int32_t arena_end) {  // the records without / with self_pod's entry
+        hipLaunchKernelGGL(janitor_build_kernel, dim3(div_up(h.n_edits, 256)), dim3(256), 0, st, c->plan.edits.as<mmp_janitor_edit>(),
+                           c->plan.keep_off.as<int32_t>(), h.n_edits, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
+                           base, arena_end, p->self_pod, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    });
 } MMP_CATCH(c, "mmp_janitor_plan")
 
 int mmp_registry_ops(mmp_ctx *c, const mmp_registry_op *ops, int32_t n, int64_t now, uint32_t flags, uint8_t *status_out,
                      mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info)
 try {
     if (!c || !info || n < 0 || max_edits < 0 || (n > 0 && !ops) || (max_edits > 0 && !edits_out) || now <= 0 ||
-        (flags & ~(MMP_ROPS_APPLY | MMP_ROPS_DRY)) || flags == (MMP_ROPS_APPLY | MMP_ROPS_DRY))
+        plan_flags_bad(flags))
         return fail(c, MMP_EINVAL, "mmp_registry_ops: bad argument");
     // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
     // too.  The state lock is taken only by an apply, for its in-place rewrite.
     std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_registry_ops: not available on a pod-axis shard context");
+    if (const int rc = plan_state_guard(c, "mmp_registry_ops")) return rc;
     const int32_t M = c->n_models, P = c->snap.P;
     // the ops index the map, the rows and the instance table: their ranges are settled here, before any kernel reads them (that
     // no model is named twice is settled by the first kernel, on the map)
@@ -4922,40 +4945,37 @@ try {
         return MMP_OK;
     }
     const bool apply = flags & MMP_ROPS_APPLY;
-    // an apply appends at most the live entries and one more per op to the arena: refused before anything is done
-    if (apply && (int64_t)c->n_entries + c->ent_live + n > INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_registry_ops: entry arena overflow; reload the registry");
+    if (const int rc = plan_arena_guard(c, "mmp_registry_ops", apply, n)) return rc;  // (refused before anything is done)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     const int nb = div_up(n, kRopsBlock);
     const int32_t cap_e = std::min(max_edits, n);
-    // (the janitor's upload, scalar and row-sized scratch buffers serve this call too: both hold batch_mu throughout)
-    HIP_TRY(c, c->jn_in.ensure((size_t)n * sizeof(mmp_registry_op)));
-    HIP_TRY(c, c->jn_js.ensure(std::max(sizeof(RopsScalars), sizeof(JanitorScalars))));
-    HIP_TRY(c, c->jn_tmp.ensure((size_t)n));
-    HIP_TRY(c, c->p_ps.ensure(sizeof(PruneScalars)));
-    HIP_TRY(c, c->p_counts.ensure((size_t)nb * 3 * 4));
-    HIP_TRY(c, c->p_edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_registry_op_edit)));
-    HIP_TRY(c, c->p_koff.ensure((size_t)std::max(cap_e, 1) * 4));
+    HIP_TRY(c, c->plan.rows_in.ensure((size_t)n * sizeof(mmp_registry_op)));
+    HIP_TRY(c, c->plan.call_scalars.ensure(std::max(sizeof(RopsScalars), sizeof(JanitorScalars))));
+    HIP_TRY(c, c->plan.row_tmp.ensure((size_t)n));
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
+    HIP_TRY(c, c->plan.edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_registry_op_edit)));
+    HIP_TRY(c, c->plan.keep_off.ensure((size_t)std::max(cap_e, 1) * 4));
     if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the scatter kernel has been seen to complete)
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what the janitor's insert reads
     const mmp_model_row *models = c->models.as<mmp_model_row>();
     const int32_t *ent_pod = c->ent_pod.as<int32_t>();
     const int64_t *ent_time = c->ent_time.as<int64_t>();
-    const mmp_registry_op *d_ops = c->jn_in.as<mmp_registry_op>();
-    int32_t *map = c->jn_map.as<int32_t>();
-    RopsScalars *rs = c->jn_js.as<RopsScalars>();
-    PruneScalars *ps = c->p_ps.as<PruneScalars>();
-    uint8_t *d_status = c->jn_tmp.as<uint8_t>();
-    HIP_TRY(c, hipMemcpyAsync(c->jn_in.p, ops, (size_t)n * sizeof(mmp_registry_op), hipMemcpyHostToDevice, st));
+    const mmp_registry_op *d_ops = c->plan.rows_in.as<mmp_registry_op>();
+    int32_t *map = c->plan.model_map.as<int32_t>();
+    RopsScalars *rs = c->plan.call_scalars.as<RopsScalars>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
+    uint8_t *d_status = c->plan.row_tmp.as<uint8_t>();
+    HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, ops, (size_t)n * sizeof(mmp_registry_op), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(rs, 0, sizeof(RopsScalars), st));
     HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
     KT_BEGIN(c, st);  // device span of the evaluation
     hipLaunchKernelGGL(rops_count_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
-                       c->p_counts.as<int32_t>());
-    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->p_counts.as<int32_t>(), nb, max_edits, INT32_MAX, ps);
+                       c->plan.block_counts.as<int32_t>());
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, max_edits, INT32_MAX, ps);
     hipLaunchKernelGGL(rops_scatter_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
-                       c->p_counts.as<int32_t>(), c->p_edits.as<mmp_registry_op_edit>(), cap_e, c->p_koff.as<int32_t>(), d_status);
+                       c->plan.block_counts.as<int32_t>(), c->plan.edits.as<mmp_registry_op_edit>(), cap_e, c->plan.keep_off.as<int32_t>(), d_status);
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     RopsScalars hr{};
@@ -4963,12 +4983,12 @@ try {
     HIP_TRY(c, hipMemcpyAsync(&hr, rs, sizeof hr, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->jn_map_n = M;
+    c->plan.model_map_n = M;
     kt_collect(c);
     if (hr.n_dup != 0) return fail(c, MMP_EINVAL, "mmp_registry_ops: %d ops name a model another op of the call names", hr.n_dup);
     const int32_t ne = std::min(h.n_edits, max_edits);
     if (status_out) HIP_TRY(c, copy_sync(c, status_out, d_status, (size_t)n, hipMemcpyDeviceToHost));
-    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->p_edits.p, (size_t)ne * sizeof(mmp_registry_op_edit), hipMemcpyDeviceToHost));
+    if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_registry_op_edit), hipMemcpyDeviceToHost));
     *info = mmp_registry_ops_info{};
     info->n_edits = h.n_edits;
     info->n_unchanged = n - h.n_edits;
@@ -4981,28 +5001,11 @@ try {
     info->n_entries_removed = hr.n_removed;
     if (!apply || h.truncated || h.n_edits == 0) return MMP_OK;
 
-    // apply: the edited records are rebuilt at the end of the arena ON THE DEVICE, beyond anything a published row refers to; then
-    // the rows are rewritten in place exactly as a registry event's are (registry_rewrite)
-    const double eval_ms = c->last_kernel_ms;
-    const int32_t E = h.n_edits, base = c->n_entries;
-    if (const int rc = registry_grow(c, M, base, h.n_kept)) return rc;
-    HIP_TRY(c, c->u_idx.ensure((size_t)E * 4));
-    HIP_TRY(c, c->u_rows.ensure((size_t)E * sizeof(mmp_model_row)));
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(rops_build_kernel, dim3(div_up(E, 256)), dim3(256), 0, st, c->p_edits.as<mmp_registry_op_edit>(), c->p_koff.as<int32_t>(), E,
-                       d_ops, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), base, base + h.n_kept,
-                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = registry_rewrite(c, E, M, base + h.n_kept, true)) return rc;
-    if (c->prof && eval_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += eval_ms;  // the call's device span: evaluation + apply
-    for (int32_t e = 0; e < E; e++) {
-        const int32_t cnt = edits_out[e].n_loaded_after + edits_out[e].n_failed_after;
-        c->ent_live += (int64_t)cnt - c->m_cnt[edits_out[e].model];
-        c->m_cnt[edits_out[e].model] = cnt;
-    }
-    // more garbage than live entries (and enough to matter): squeeze the arena
-    if ((int64_t)c->n_entries - c->ent_live > std::max<int64_t>(c->ent_live, 1 << 16)) return compact_registry(c);
-    return MMP_OK;
+    return registry_apply_edits(c, h.n_edits, h.n_kept, edits_out, [&](int32_t base, int32_t arena_end) {  // the records without / with the op's entry
+        hipLaunchKernelGGL(rops_build_kernel, dim3(div_up(h.n_edits, 256)), dim3(256), 0, st, c->plan.edits.as<mmp_registry_op_edit>(),
+                           c->plan.keep_off.as<int32_t>(), h.n_edits, d_ops, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(),
+                           c->ent_time.as<int64_t>(), base, arena_end, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    });
 } MMP_CATCH(c, "mmp_registry_ops")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc

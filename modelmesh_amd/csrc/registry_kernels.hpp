@@ -17,6 +17,8 @@
 //   prune_marks_kernel    pod-sized: new marks first, then the cleanup of :6601-6606
 //   prune_build_kernel    (apply) one lane per edit: the surviving entries appended to the arena, the edited row
 //                         staged for upsert_models_kernel
+// The count and scatter kernels here, in janitor_kernels.hpp and in registry_ops_kernels.hpp hand prune_scan_kernel one triple
+// per workgroup and take their offsets back from it by one protocol: triple_count / triple_offsets below.
 #pragma once
 #include "rebalance_kernels.hpp"
 
@@ -35,6 +37,69 @@ struct PruneArgs {
 constexpr uint8_t kPodPresent = 0, kPodMissing = 1, kPodDue = 2;
 constexpr int kPruneBlock = kCompactBlock;
 constexpr int32_t kMarksKeep = 0, kMarksAdvance = 1, kMarksIfNoEdits = 2;  // prune_marks_kernel: whether the map is written
+
+// ---- the per-workgroup triple (edits, column 1, entries the edited records keep) ----
+// A count kernel leaves block_counts[3 * b + 0..2] for its workgroup b, prune_scan_kernel turns them into exclusive offsets in place
+// (and the totals), and the scatter kernel of the same grid, its lanes contributing the same three, places its output there in lane
+// order.  Column 1 is what the call lists beside its edits: removed entries (the prune: a sum), candidates (the janitor: a count
+// of lanes), nothing (the ops: constant 0, no LDS).  Each helper holds one __syncthreads(): the whole workgroup calls it, or none.
+enum TripleCol1 { kCol1None, kCol1Count, kCol1Sum };
+struct TripleOff { int32_t e, r, k; };  // the lane's exclusive offset in each column
+// count side: thread 0 stores the workgroup's three totals
+template <TripleCol1 C1>
+__device__ __forceinline__ void triple_count(bool edit, int32_t v1, int32_t kept, int32_t *__restrict__ block_counts)
+{
+    constexpr int W = kCompactBlock / 64, K = C1 == kCol1None ? 1 : 2;
+    __shared__ int32_t s[K + 1][W];  // per wave: edits, column 1 if there is one, kept
+    const int ne = __popcll(__ballot(edit));
+    const int32_t n1 = C1 == kCol1Count ? __popcll(__ballot(v1 != 0)) : C1 == kCol1Sum ? wave_sum_i32(v1) : 0, nk = wave_sum_i32(kept);
+    const int w = threadIdx.x >> 6;
+    if (lane_id() == 0) {
+        s[0][w] = ne;
+        if (C1 != kCol1None) s[1][w] = n1;
+        s[K][w] = nk;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t e = 0, r = 0, k = 0;
+        for (int x = 0; x < W; x++) {
+            e += s[0][x];
+            if (C1 != kCol1None) r += s[1][x];
+            k += s[K][x];
+        }
+        block_counts[3 * blockIdx.x + 0] = e;
+        block_counts[3 * blockIdx.x + 1] = r;
+        block_counts[3 * blockIdx.x + 2] = k;
+    }
+}
+
+// scatter side: the workgroup's offsets from the scan, plus the preceding waves, plus the preceding lanes
+template <TripleCol1 C1>
+__device__ __forceinline__ TripleOff triple_offsets(bool edit, int32_t v1, int32_t kept, const int32_t *__restrict__ block_off)
+{
+    constexpr int W = kCompactBlock / 64, K = C1 == kCol1None ? 1 : 2;
+    __shared__ int32_t s[K + 1][W];
+    const uint64_t be = __ballot(edit), b1 = C1 == kCol1Count ? __ballot(v1 != 0) : 0;
+    const int32_t i1 = C1 == kCol1Sum ? wave_incl_scan_i32(v1) : 0, ik = wave_incl_scan_i32(kept);
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    if (lane == 63) {
+        s[0][w] = __popcll(be);
+        if (C1 != kCol1None) s[1][w] = C1 == kCol1Count ? __popcll(b1) : i1;
+        s[K][w] = ik;
+    }
+    __syncthreads();
+    TripleOff o{block_off[3 * blockIdx.x + 0], C1 != kCol1None ? block_off[3 * blockIdx.x + 1] : 0, block_off[3 * blockIdx.x + 2]};
+    for (int x = 0; x < w; x++) {
+        o.e += s[0][x];
+        if (C1 != kCol1None) o.r += s[1][x];
+        o.k += s[K][x];
+    }
+    const uint64_t below = (1ull << lane) - 1ull;
+    o.e += __popcll(be & below);
+    o.r += C1 == kCol1Count ? __popcll(b1 & below) : i1 - v1;
+    o.k += ik - kept;
+    return o;
+}
 
 // One state byte per pod slot of the instance table; `seen` is cleared for the walk.  since[] covers n_map >= P slots.
 __global__ void prune_pods_kernel(const mmp_pod_row *__restrict__ pods, PruneArgs A, const int64_t *__restrict__ since,
@@ -100,7 +165,7 @@ __global__ __launch_bounds__(kPruneBlock) void prune_count_kernel(const mmp_mode
                                                                   const uint8_t *__restrict__ state, uint8_t *__restrict__ seen,
                                                                   int32_t *__restrict__ block_counts, PruneScalars *ps)
 {
-    __shared__ int32_t s_e[kPruneBlock / 64], s_r[kPruneBlock / 64], s_k[kPruneBlock / 64], s_u[kPruneBlock / 64], s_p[kPruneBlock / 64];
+    __shared__ int32_t s_u[kPruneBlock / 64], s_p[kPruneBlock / 64];
     const int i = blockIdx.x * kPruneBlock + threadIdx.x;
     bool edit = false, repair = false;
     int32_t rm = 0, kept = 0, unres = 0;
@@ -113,29 +178,20 @@ __global__ __launch_bounds__(kPruneBlock) void prune_count_kernel(const mmp_mode
         edit = rm > 0 || repair;
         if (edit) kept = m.n_loaded + m.n_failed - rm;
     }
-    const int ne = __popcll(__ballot(edit)), np = __popcll(__ballot(repair));
-    const int32_t nr = wave_sum_i32(rm), nk = wave_sum_i32(kept), nu = wave_sum_i32(unres);
+    const int np = __popcll(__ballot(repair));
+    const int32_t nu = wave_sum_i32(unres);
     const int w = threadIdx.x >> 6;
     if (lane_id() == 0) {
-        s_e[w] = ne;
-        s_r[w] = nr;
-        s_k[w] = nk;
         s_u[w] = nu;
         s_p[w] = np;
     }
-    __syncthreads();
+    triple_count<kCol1Sum>(edit, rm, kept, block_counts);  // (its barrier covers s_u / s_p too)
     if (threadIdx.x == 0) {
-        int32_t e = 0, r = 0, k = 0, u = 0, p = 0;
+        int32_t u = 0, p = 0;
         for (int x = 0; x < kPruneBlock / 64; x++) {
-            e += s_e[x];
-            r += s_r[x];
-            k += s_k[x];
             u += s_u[x];
             p += s_p[x];
         }
-        block_counts[3 * blockIdx.x + 0] = e;
-        block_counts[3 * blockIdx.x + 1] = r;
-        block_counts[3 * blockIdx.x + 2] = k;
         if (u) atomicAdd(&ps->n_unresolved, u);
         if (p) atomicAdd(&ps->n_repaired, p);
     }
@@ -191,7 +247,6 @@ __global__ __launch_bounds__(kPruneBlock) void prune_scatter_kernel(const mmp_mo
                                                                     mmp_prune_removed *__restrict__ removed, int32_t max_removed,
                                                                     int32_t *__restrict__ keep_off)
 {
-    __shared__ int32_t s_e[kPruneBlock / 64], s_r[kPruneBlock / 64], s_k[kPruneBlock / 64];
     if (ps->n_edits == 0) return;  // (uniform: the whole grid leaves)
     const int i = blockIdx.x * kPruneBlock + threadIdx.x;
     mmp_model_row m{};
@@ -208,24 +263,9 @@ __global__ __launch_bounds__(kPruneBlock) void prune_scatter_kernel(const mmp_mo
         edit = rm > 0 || repair;
         if (edit) kept = m.n_loaded + m.n_failed - rm;
     }
-    const uint64_t b = __ballot(edit);
-    const int32_t ir = wave_incl_scan_i32(rm), ik = wave_incl_scan_i32(kept);
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    if (lane == 63) {
-        s_e[w] = __popcll(b);
-        s_r[w] = ir;
-        s_k[w] = ik;
-    }
-    __syncthreads();
-    int32_t oe = block_off[3 * blockIdx.x + 0], orm = block_off[3 * blockIdx.x + 1], ok = block_off[3 * blockIdx.x + 2];
-    for (int x = 0; x < w; x++) {
-        oe += s_e[x];
-        orm += s_r[x];
-        ok += s_k[x];
-    }
+    const TripleOff o = triple_offsets<kCol1Sum>(edit, rm, kept, block_off);
     if (!edit) return;
-    const int32_t e = oe + __popcll(b & ((1ull << lane) - 1ull));
-    const int32_t roff = orm + ir - rm;
+    const int32_t e = o.e, roff = o.r;
     if (e < max_edits) {
         mmp_prune_edit ed;
         ed.model = i;
@@ -236,7 +276,7 @@ __global__ __launch_bounds__(kPruneBlock) void prune_scatter_kernel(const mmp_mo
         ed.n_removed = rm;
         ed.last_used_after = repair ? A.repaired_last_used : m.last_used;  // :6844
         edits[e] = ed;
-        keep_off[e] = ok + ik - kept;
+        keep_off[e] = o.k;
     }
     if (rm > 0) (void)prune_walk<true>(m, ent_pod, ent_time, A, state, nullptr, removed, roff, max_removed);
 }

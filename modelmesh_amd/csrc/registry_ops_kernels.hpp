@@ -9,7 +9,7 @@
 //   rops_count_kernel    one lane per op: its model marked in the janitor's map (M int32 words, all -1 between runs) with a
 //                        compare-and-swap — a word already taken is a second op on that model, counted; the op evaluated;
 //                        per-workgroup counts of (edits, -, entries the edited records hold afterwards)
-//   prune_scan_kernel    (registry_kernels.hpp) the one-workgroup scan of those triples
+//   prune_scan_kernel    (registry_kernels.hpp) the one-workgroup scan of those triples (protocol: triple_count there)
 //   rops_scatter_kernel  the same evaluation: edits in OP order by ballot and popcount (no atomics on positions), status bytes,
 //                        the totals per op kind, and the map words back to -1 — no M-sized memset per call.  With a duplicate
 //                        it only clears the map.
@@ -129,7 +129,6 @@ __global__ __launch_bounds__(kRopsBlock) void rops_count_kernel(const mmp_regist
                                                                 int32_t P, int64_t now, int32_t *__restrict__ map, RopsScalars *rs,
                                                                 int32_t *__restrict__ block_counts)
 {
-    __shared__ int32_t s_e[kRopsBlock / 64], s_k[kRopsBlock / 64];
     const int i = blockIdx.x * kRopsBlock + threadIdx.x;
     bool edit = false, dup = false;
     int32_t kept = 0;
@@ -140,25 +139,9 @@ __global__ __launch_bounds__(kRopsBlock) void rops_count_kernel(const mmp_regist
         edit = ev.edited;
         if (edit) kept = ev.nl + ev.nf;
     }
-    const int ne = __popcll(__ballot(edit)), nd = __popcll(__ballot(dup));
-    const int32_t nk = wave_sum_i32(kept);
-    const int w = threadIdx.x >> 6;
-    if (lane_id() == 0) {
-        s_e[w] = ne;
-        s_k[w] = nk;
-        if (nd) atomicAdd(&rs->n_dup, nd);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t a = 0, c = 0;
-        for (int x = 0; x < kRopsBlock / 64; x++) {
-            a += s_e[x];
-            c += s_k[x];
-        }
-        block_counts[3 * blockIdx.x + 0] = a;
-        block_counts[3 * blockIdx.x + 1] = 0;
-        block_counts[3 * blockIdx.x + 2] = c;
-    }
+    const int nd = __popcll(__ballot(dup));
+    if (lane_id() == 0 && nd) atomicAdd(&rs->n_dup, nd);
+    triple_count<kCol1None>(edit, 0, kept, block_counts);
 }
 
 // edits in op order (bounded by max_edits: a truncated prefix), one status byte per op, the totals; every map word this call
@@ -170,7 +153,6 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
                                                                   const int32_t *__restrict__ block_off, mmp_registry_op_edit *__restrict__ edits,
                                                                   int32_t max_edits, int32_t *__restrict__ keep_off, uint8_t *__restrict__ status)
 {
-    __shared__ int32_t s_e[kRopsBlock / 64], s_k[kRopsBlock / 64];
     const int i = blockIdx.x * kRopsBlock + threadIdx.x;
     mmp_registry_op op{};
     if (i < n) {
@@ -182,22 +164,11 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
     if (i < n) ev = rops_eval(models[op.model], ent_pod, ent_time, pods, P, op, now);
     const bool edit = ev.edited;
     const int32_t kept = edit ? ev.nl + ev.nf : 0;
-    const uint64_t be = __ballot(edit);
-    const int32_t ik = wave_incl_scan_i32(kept);
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    if (lane == 63) {
-        s_e[w] = __popcll(be);
-        s_k[w] = ik;
-    }
-    __syncthreads();
-    int32_t oe = block_off[3 * blockIdx.x + 0], ok = block_off[3 * blockIdx.x + 2];
-    for (int x = 0; x < w; x++) {
-        oe += s_e[x];
-        ok += s_k[x];
-    }
+    const TripleOff o = triple_offsets<kCol1None>(edit, 0, kept, block_off);
+    const int lane = lane_id();
     if (i < n) status[i] = edit ? MMP_ROP_EDITED : MMP_ROP_UNCHANGED;
     if (edit) {
-        const int32_t x = oe + __popcll(be & ((1ull << lane) - 1ull));
+        const int32_t x = o.e;
         if (x < max_edits) {
             mmp_registry_op_edit ed;
             ed.model = op.model;
@@ -209,7 +180,7 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
             ed.last_used_after = ev.last_used;
             ed.last_unload_after = ev.last_unload;
             edits[x] = ed;
-            keep_off[x] = ok + ik - kept;
+            keep_off[x] = o.k;
         }
     }
 #pragma unroll
