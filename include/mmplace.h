@@ -1020,6 +1020,23 @@ int mmp_type_names_load(mmp_ctx *ctx, const char *names, const int32_t *name_off
  * last_unload_out[i] = "lul" (ModelRecord.lastUnloadTime, an input of the scale-down plan). */
 int mmp_models_ingest_json(mmp_ctx *ctx, const char *buf, const int64_t *off, int32_t n_models, int64_t *last_unload_out,
                            int32_t *status_out);
+/* Registry events as stored (the registry's KV listener, MM.java:628, event() :2807-2854, delivers one whole ModelRecord value per
+ * change): mmp_models_upsert with the rows parsed on the device.  Event i is the value buf[off[i], off[i+1]) for registry row
+ * model_idx[i]; indices follow mmp_models_upsert (model_idx[i] == the running model count appends, in event order).
+ * deleted[i] != 0 is ENTRY_DELETED: the value is ignored (it may be empty) and the row becomes the empty row — all fields zero, no
+ * entries — which is what mmp_models_upsert documents for a deleted record; deleted may be NULL (no event is a deletion).
+ * Grammar, field set, type-name resolution, default type and id resolution are those of mmp_models_ingest_json: an id that is not
+ * in the pod table gives an entry with pod -1, entries stay in document order, mmp_pod_ids_load is required first (MMP_ESTATE
+ * without it), the type table is optional.  status_out[i] = 1 for a malformed value.  Events apply in order and a malformed event
+ * changes nothing, so a row ends as its LAST WELL-FORMED OR DELETED event left it: an existing row whose events in this call are
+ * all malformed is untouched; an appended row whose events are all malformed becomes the empty row (its index has been handed
+ * out).  last_unload_out[i] = the event's "lul", 0 for a deleted or malformed event; it may be NULL.  Takes effect at once, no
+ * commit; locking as in mmp_models_upsert (decisions are held off only while the rows are rewritten in place).  n == 0 is valid.
+ * MMP_EINVAL, with nothing changed: a NULL required buffer, non-monotone offsets, an index < 0 or beyond the running count, entry
+ * arena overflow.  O(events + their bytes + their entries), whatever the size of the registry: the values are parsed and the
+ * winning events' entries appended to the arena on the device; only the per-event status, lul and entry counts come back. */
+int mmp_models_upsert_json(mmp_ctx *ctx, const char *buf, const int64_t *off, int32_t n, const int32_t *model_idx,
+                           const uint8_t *deleted, int64_t *last_unload_out, int32_t *status_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

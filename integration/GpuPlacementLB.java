@@ -153,6 +153,9 @@ final class MmPlace {
     static native int typeNamesLoad(long h, ByteBuffer names, ByteBuffer nameOff, int nTypes, int unknownType);
     static native int modelsIngestJson(long h, ByteBuffer json, ByteBuffer off, int nModels, ByteBuffer lastUnloadOut,
                                        ByteBuffer statusOut);
+    /** a batch of registry events as stored: value i for model modelIdx[i]; deleted (may be null) marks ENTRY_DELETED */
+    static native int modelsUpsertJson(long h, ByteBuffer json, ByteBuffer off, int n, ByteBuffer modelIdx, ByteBuffer deleted,
+                                       ByteBuffer lastUnloadOut, ByteBuffer statusOut);
     // misc
     static native long minSpaceUnits(int defaultModelSizeUnits, int loadingThreads, long capacityUnits,
                                      boolean haveUnloadManager);
@@ -171,7 +174,9 @@ final class MmPlace {
  * class of ModelMesh: the interner maps instance id <-> dense pod index (id_order == rank under String.compareTo,
  * replica_set == interned id.substring(0,6)) and model id -> dense model index; the snapshot handle is refreshed by
  * the instance-table listener (handleInstanceTableChange, ModelMesh.java:1455: podsUpsert / podsRemove + commit) and
- * by the registry listener (modelsLoad once, modelsUpsert per ModelRecord event).
+ * by the registry listener (modelsIngestJson of the stored values once, then modelsUpsertJson per batch of events with
+ * the raw byte[] of each event and the model index of its key, ENTRY_DELETED as a deleted flag; a listener that holds
+ * parsed ModelRecords uses modelsLoad / modelsUpsert instead).
  */
 interface GpuMeshBinding {
     long handle();

@@ -562,6 +562,17 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsIngestJson(JN
                  mmp_models_ingest_json(ctx_of(h), buf<char>(env, json), buf<int64_t>(env, off), nModels,
                                         buf<int64_t>(env, lastUnloadOut), buf<int32_t>(env, statusOut)));
 }
+// registry listener events as stored: the raw byte[] of each event, parsed on the device (see mmp_models_upsert_json)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsUpsertJson(JNIEnv *env, jclass, jlong h,
+                                                                              jobject json, jobject off, jint n,
+                                                                              jobject modelIdx, jobject deleted,
+                                                                              jobject lastUnloadOut, jobject statusOut)
+{
+    return check(env, ctx_of(h),
+                 mmp_models_upsert_json(ctx_of(h), buf<char>(env, json), buf<int64_t>(env, off), n,
+                                        buf<int32_t>(env, modelIdx), buf<uint8_t>(env, deleted),
+                                        buf<int64_t>(env, lastUnloadOut), buf<int32_t>(env, statusOut)));
+}
 
 // ---- misc -----------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL Java_com_ibm_watson_modelmesh_MmPlace_minSpaceUnits(JNIEnv *, jclass,

@@ -272,6 +272,7 @@ SYMBOLS = [
     ("mmp_pods_ingest_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("mmp_type_names_load", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     ("mmp_models_ingest_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    ("mmp_models_upsert_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

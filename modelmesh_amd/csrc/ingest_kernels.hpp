@@ -300,7 +300,28 @@ struct IngestModelsArgs {
     int32_t *ent_pod;      // entries of record i are parked at slot off[i] / 6 (an entry takes >= 6 bytes of JSON,
     int64_t *ent_time;     // so the slots of consecutive records never overlap) until the offsets are known
     int32_t grp;           // records per wavefront (1..kJGroup)
+    // mmp_models_upsert_json (all three NULL for the full reload, where record i IS row i): the records are EVENTS, rows / cnt /
+    // last_unload / status are per-event scratch, and event i belongs to the registry row in slot[i] of the call's distinct rows.
+    const uint8_t *deleted;  // event i is ENTRY_DELETED: its value is not read, it leaves the empty row and counts as well-formed
+    const int32_t *slot;
+    int32_t *win;            // per slot: the last event that is well-formed or deleted (-1 before the launch; atomicMax)
 };
+
+// What every path of ingest_models_kernel leaves for record i.  With the row indirection the event also stands for its row:
+// events apply in order and a malformed one changes nothing, so the row ends as its highest-numbered good event left it.
+__device__ __forceinline__ void j_publish_model(const IngestModelsArgs &A, int i, bool bad, mmp_model_row r, int64_t lul)
+{
+    if (A.deleted && A.deleted[i]) {
+        bad = false;
+        r = mmp_model_row{};
+        lul = 0;
+    }
+    A.status[i] = bad ? 1 : 0;
+    A.rows[i] = r;
+    A.cnt[i] = r.n_loaded + r.n_failed;
+    A.last_unload[i] = bad ? 0 : lul;
+    if (A.slot && !bad) atomicMax(&A.win[A.slot[i]], i);
+}
 
 // One ModelRecord value walked by ONE lane.  PASS 0: type / counts / lu / lul; PASS 1: the entries.
 template <int PASS>
@@ -803,19 +824,17 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                 r.n_loaded = r.n_failed = 0;
                 r.last_used = 0;
                 r.ent_off = 0;
-                int64_t lul, lul2;
+                int64_t lul = 0, lul2;
                 const char *b = A.buf + S.off[i - i0], *e = A.buf + S.off[i - i0 + 1];
-                bool bad = model_record_serial<0>(A, b, e, r, lul);
+                bool bad = A.deleted && A.deleted[i];  // (a deleted event's value is not walked)
+                if (!bad) bad = model_record_serial<0>(A, b, e, r, lul);
                 if (!bad) {
                     mmp_model_row w = r;
                     w.ent_off = (int32_t)(S.off[i - i0] / 6);
                     (void)model_record_serial<1>(A, b, e, w, lul2);
                 } else
                     r.n_loaded = r.n_failed = 0;
-                A.status[i] = bad ? 1 : 0;
-                A.rows[i] = r;
-                A.cnt[i] = r.n_loaded + r.n_failed;
-                A.last_unload[i] = bad ? 0 : lul;
+                j_publish_model(A, i, bad, r, lul);
             }
             i++;
             continue;
@@ -939,10 +958,7 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
             r.n_loaded = bad ? 0 : (int32_t)S.val[lane][3];
             r.n_failed = bad ? 0 : (int32_t)S.val[lane][4];
             r.last_used = bad ? 0 : S.val[lane][1];
-            A.status[i + lane] = bad ? 1 : 0;
-            A.rows[i + lane] = r;
-            A.cnt[i + lane] = r.n_loaded + r.n_failed;
-            A.last_unload[i + lane] = bad ? 0 : S.val[lane][2];
+            j_publish_model(A, i + lane, bad, r, S.val[lane][2]);
         }
         wave_sync();
         i += cnt;
@@ -966,6 +982,51 @@ __global__ void compact_entries_kernel(const int64_t *__restrict__ off, int32_t 
         ent_pod[o + e] = tmp_pod[slot + e];
         ent_time[o + e] = tmp_time[slot + e];
     }
+}
+
+// ---- mmp_models_upsert_json: from the parsed events to the rows registry_rewrite takes -----------------------------------------
+//
+// Slot j is the j-th distinct registry row the call names (slot_model[j]); win[j] is the event that decides it (see
+// j_publish_model).  Everything here is sized by the call's events and distinct rows, never by the registry.
+
+// s_cnt[j] = entries slot j appends to the arena (scanned into s_offs); s_cnt[k] = 0 so that the scan's last element is the total
+__global__ void upsert_json_counts_kernel(const int32_t *__restrict__ win, const int32_t *__restrict__ ev_cnt, int32_t k,
+                                          int32_t *__restrict__ s_cnt)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > k) return;
+    const int32_t w = j < k ? win[j] : -1;
+    s_cnt[j] = w >= 0 ? ev_cnt[w] : 0;
+}
+
+// One lane per slot (a model has 1-3 copies): the winner's parked entries to arena[base + s_offs[j] ...), which lies inside the
+// arena (the host grew it by the scan's total) and beyond anything a published row refers to; u_idx / u_rows for
+// upsert_models_kernel.  A slot without a winner saw malformed events only: an existing row (model < n_before) is staged as it
+// stands, so the rewrite leaves it as it was; an appended one becomes the empty row, because its index has been handed out.
+__global__ void upsert_json_build_kernel(const int32_t *__restrict__ win, const int32_t *__restrict__ slot_model, int32_t k,
+                                         int32_t n_before, int32_t base, const int32_t *__restrict__ s_offs,
+                                         const mmp_model_row *__restrict__ ev_rows, const int64_t *__restrict__ off,
+                                         const int32_t *__restrict__ tmp_pod, const int64_t *__restrict__ tmp_time,
+                                         const mmp_model_row *__restrict__ models, int32_t *__restrict__ ent_pod,
+                                         int64_t *__restrict__ ent_time, int32_t *__restrict__ u_idx, mmp_model_row *__restrict__ u_rows)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const int32_t w = win[j], model = slot_model[j];
+    mmp_model_row r{};
+    if (w >= 0) {
+        r = ev_rows[w];
+        const int32_t cnt = r.n_loaded + r.n_failed, o = base + s_offs[j];
+        const int64_t slot = off[w] / 6;
+        for (int32_t e = 0; e < cnt; e++) {
+            ent_pod[o + e] = tmp_pod[slot + e];
+            ent_time[o + e] = tmp_time[slot + e];
+        }
+        r.ent_off = cnt ? o : 0;
+    } else if (model < n_before)
+        r = models[model];
+    u_idx[j] = model;
+    u_rows[j] = r;
 }
 
 }  // namespace mmp

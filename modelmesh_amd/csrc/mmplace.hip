@@ -382,7 +382,7 @@ struct mmp_ctx {
     std::vector<uint32_t> id_order_v;
     std::vector<int32_t> replica_set_v;
     DevBuf idtab_hash, idtab_val, tytab_hash, tytab_val, j_buf, j_off, j_rows, j_aux, j_status, j_cnt, j_offs, j_tmp_pod, j_tmp_time,
-        j_scan_tmp;
+        j_scan_tmp, j_ev;  // j_ev: mmp_models_upsert_json's per-event / per-distinct-row words
     uint32_t idtab_mask = 0, tytab_mask = 0;
     bool have_ids = false, have_types = false;
     int32_t unknown_type = 0, default_type = 0;
@@ -1055,7 +1055,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -2687,6 +2687,128 @@ try {
     c->ent_live = total;
     return rebuild_resolved(c);
 } MMP_CATCH(c, "mmp_models_ingest_json")
+
+int mmp_models_upsert_json(mmp_ctx *c, const char *buf, const int64_t *off, int32_t n, const int32_t *model_idx,
+                           const uint8_t *deleted, int64_t *last_unload_out, int32_t *status_out)
+try {
+    if (!c || n < 0 || (n > 0 && (!off || !model_idx || !status_out)))
+        return fail(c, MMP_EINVAL, "mmp_models_upsert_json: bad argument");
+    // the locking of mmp_models_upsert: batch_mu for the call; decisions are held off only while the rows are rewritten
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_models_upsert_json: load the instance ids first (mmp_pod_ids_load)");
+    if (n == 0) return MMP_OK;
+    const int32_t M0 = c->n_models;
+    int32_t count = M0;
+    // slot = the distinct registry rows of the call in order of first appearance (found through a map sized by the events:
+    // nothing here is sized by the registry)
+    std::vector<int32_t> h_slot(n), h_model;
+    {
+        std::unordered_map<int32_t, int32_t> slot_of;
+        slot_of.reserve((size_t)n * 2);
+        for (int32_t i = 0; i < n; i++) {
+            if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: offsets not monotone at %d", i);
+            if (model_idx[i] < 0 || model_idx[i] > count)
+                return fail(c, MMP_EINVAL, "mmp_models_upsert_json: event %d names model %d of %d", i, model_idx[i], count);
+            if (model_idx[i] == count) count++;
+            const auto it = slot_of.emplace(model_idx[i], (int32_t)h_model.size());
+            if (it.second) h_model.push_back(model_idx[i]);
+            h_slot[i] = it.first->second;
+        }
+    }
+    const int64_t bytes = off[n] - off[0];
+    if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: bad argument");
+    const size_t ent_cap = (size_t)(bytes / 6 + 2);  // an entry takes >= 6 bytes of JSON
+    if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: more than 2^31 entries in one call");
+    const int32_t k = (int32_t)h_model.size();
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // j_ev, in words: slot[n] | slot_model[k] | win[k] | deleted[n bytes] (uploaded together) | s_cnt[k+1] | s_offs[k+1]
+    const size_t del_words = ((size_t)n + 3) / 4, up_words = (size_t)n + 2 * (size_t)k + del_words;
+    std::vector<int32_t> up(up_words, 0);
+    memcpy(up.data(), h_slot.data(), (size_t)n * 4);
+    memcpy(up.data() + n, h_model.data(), (size_t)k * 4);
+    std::fill(up.begin() + n + k, up.begin() + n + 2 * (size_t)k, -1);
+    if (deleted)
+        for (int32_t i = 0; i < n; i++) reinterpret_cast<uint8_t *>(up.data() + n + 2 * (size_t)k)[i] = deleted[i] ? 1 : 0;
+    HIP_TRY(c, c->j_ev.ensure((up_words + 2 * ((size_t)k + 1)) * 4));
+    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
+    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
+    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+    HIP_TRY(c, c->j_cnt.ensure((size_t)n * 4));
+    HIP_TRY(c, c->j_tmp_pod.ensure(ent_cap * 4));
+    HIP_TRY(c, c->j_tmp_time.ensure(ent_cap * 8));
+    int32_t *d_slot = c->j_ev.as<int32_t>(), *d_model = d_slot + n, *d_win = d_model + k;
+    int32_t *s_cnt = d_slot + up_words, *s_offs = s_cnt + k + 1;
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    std::vector<int64_t> rel(n + 1);
+    for (int32_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->j_ev.p, up.data(), up_words * 4, hipMemcpyHostToDevice, st));
+    IngestModelsArgs A{};
+    A.buf = c->j_buf.as<char>();
+    A.off = c->j_off.as<int64_t>();
+    A.n = n;
+    A.ids = HashTab{c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), c->idtab_mask};
+    A.types = c->have_types ? HashTab{c->tytab_hash.as<uint64_t>(), c->tytab_val.as<int32_t>(), c->tytab_mask}
+                            : HashTab{nullptr, nullptr, 0};
+    A.unknown_type = c->have_types ? c->unknown_type : 0;
+    A.default_type = c->have_types ? c->default_type : 0;
+    A.rows = c->j_rows.as<mmp_model_row>();
+    A.last_unload = c->j_aux.as<int64_t>();
+    A.status = c->j_status.as<int32_t>();
+    A.cnt = c->j_cnt.as<int32_t>();
+    A.ent_pod = c->j_tmp_pod.as<int32_t>();
+    A.ent_time = c->j_tmp_time.as<int64_t>();
+    A.grp = ingest_group(n);
+    A.deleted = deleted ? reinterpret_cast<const uint8_t *>(d_win + k) : nullptr;
+    A.slot = d_slot;
+    A.win = d_win;
+    // parse the events (entries parked in scratch), pick each row's winner, and size what the winners append
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * A.grp)), dim3(kJBlock), 0, st, A);
+    hipLaunchKernelGGL(upsert_json_counts_kernel, dim3(div_up(k + 1, 256)), dim3(256), 0, st, d_win, A.cnt, k, s_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    // back to the host: the winners and the per-event counts (for the host shadow) and the arena room needed; no entry, no row
+    std::vector<int32_t> h_win(k), h_cnt(n);
+    int32_t total = 0;
+    HIP_TRY(c, hipMemcpyAsync(h_win.data(), d_win, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h_cnt.data(), A.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&total, s_offs + k, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const double parse_ms = c->last_kernel_ms;
+    const int32_t base = c->n_entries;
+    if ((int64_t)base + total > INT32_MAX)  // (nothing but scratch has been written so far)
+        return fail(c, MMP_EINVAL, "mmp_models_upsert_json: entry arena overflow; reload the registry");
+    if (const int rc = registry_grow(c, count, base, total)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)k * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)k * sizeof(mmp_model_row)));
+    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (last_unload_out) HIP_TRY(c, hipMemcpyAsync(last_unload_out, c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(upsert_json_build_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, d_win, d_model, k, M0, base, s_offs, A.rows, A.off,
+                       A.ent_pod, A.ent_time, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
+                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, k, count, base + total, true)) return rc;
+    if (c->prof && parse_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += parse_ms;  // the call's device span: parse + apply
+    // the host shadow: a slot without a winner keeps its count (an existing row) or has none (an appended one)
+    c->m_cnt.resize(count, 0);
+    for (int32_t j = 0; j < k; j++) {
+        if (h_win[j] < 0) continue;
+        const int32_t cnt = h_cnt[h_win[j]];
+        c->ent_live += (int64_t)cnt - c->m_cnt[h_model[j]];
+        c->m_cnt[h_model[j]] = cnt;
+    }
+    return squeeze_if_garbage(c);
+} MMP_CATCH(c, "mmp_models_upsert_json")
 
 int mmp_pods_get(mmp_ctx *c, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out)
 try {

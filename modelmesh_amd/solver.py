@@ -199,6 +199,21 @@ class Solver:
         self._models = self._ent_pod = None  # (the registry now lives on the device only: serve_counters needs load_models / upsert_models)
         return status[:n], lul[:n]
 
+    def upsert_models_json(self, values, idx, deleted=None):
+        """Registry events as stored: values[i] (ModelRecord JSON, bytes/str) replaces model idx[i]; deleted[i] marks
+        ENTRY_DELETED (the value is ignored).  Returns (status, last_unload_time)."""
+        blob, off = self._pack(values)
+        n = len(values)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        deleted = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+        lul = np.zeros(max(n, 1), np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        self._ck(self.lib.mmp_models_upsert_json(self.h, blob, ptr(off), n, ptr(idx), ptr(deleted), ptr(lul), ptr(status)))
+        if n:
+            self.n_models = max(getattr(self, "n_models", 0), int(idx.max()) + 1)
+            self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
+        return status[:n], lul[:n]
+
     def get_pods(self) -> np.ndarray:
         n = C.c_int32(0)
         self._ck(self.lib.mmp_pods_get(self.h, None, 0, C.byref(n)))

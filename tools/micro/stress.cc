@@ -5,7 +5,8 @@
 //   R request threads   single requests and small batches through the latency slots (mmp_place_batch n = 1 / 2 with exclusions / 300,
 //                       mmp_gate_batch, mmp_serve_batch, mmp_miss_batch, mmp_route_batch), half the run with the resident kernel on
 //   1 committer         a few InstanceRecords rewritten, then mmp_snapshot_commit (delta and full commits)
-//   1 registry thread   mmp_models_upsert of a few ModelRecords (arena growth and squeezes)
+//   1 registry thread   mmp_models_upsert of a few ModelRecords (arena growth and squeezes), every other round the same kind of events
+//                       as stored JSON values through mmp_models_upsert_json (a deletion and a malformed value among them)
 //   1 batch thread      mmp_place_batch with 6000 host-pointer requests; device-pointer batches of 300 000 (split: two launches) on two
 //                       streams of its own through mmp_issue_threads(4) + mmp_issue_flush
 // Every return code must be MMP_OK and every result row plausible (a pod index, MMP_NONE or MMP_SELF).  No oracle here: the parity
@@ -24,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -87,6 +89,19 @@ int main(int argc, char **argv)
             ep.push_back((int32_t)((m * 7919 + k * 104729) % P));
             et.push_back(NOW - 60000);
         }
+    }
+    // instance ids "p00000".."p02999" (index order == String.compareTo order; six characters: no replica set), for the JSON events
+    std::string ids;
+    std::vector<int32_t> id_off(P + 1, 0);
+    for (int p = 0; p < P; p++) {
+        char b[16];
+        snprintf(b, sizeof b, "p%05d", p);
+        ids += b;
+        id_off[p + 1] = (int32_t)ids.size();
+    }
+    if (mmp_pod_ids_load(c, ids.data(), id_off.data(), P, nullptr, nullptr)) {
+        fprintf(stderr, "ids: %s\n", mmp_last_error(c));
+        return 1;
     }
     if (mmp_pods_load(c, pods.data(), P) || mmp_models_load(c, models.data(), M, ep.data(), et.data(), (int32_t)ep.size()) || mmp_snapshot_commit(c)) {
         fprintf(stderr, "load: %s\n", mmp_last_error(c));
@@ -194,10 +209,44 @@ int main(int argc, char **argv)
             std::this_thread::sleep_for(std::chrono::microseconds(500 + rng() % 2000));
         }
     };
+    // k registry events as the KV store holds them; about one in eight is a deletion, one in eight malformed (truncated)
+    auto json_events = [&](std::mt19937 &rng, int k) {
+        std::string buf;
+        std::vector<int64_t> off(1, 0), lul(k);
+        std::vector<int32_t> idx(k), status(k);
+        std::vector<uint8_t> del(k);
+        for (int i = 0; i < k; i++) {
+            idx[i] = (int32_t)(rng() % M);
+            del[i] = (rng() % 8) == 0;
+            if (!del[i] || (rng() & 1)) {
+                std::string v = "{\"type\":\"t\",\"instanceIds\":{";
+                const int nl = (int)(rng() % 4), first = (int)(rng() % P);
+                for (int j = 0; j < nl; j++) {
+                    char b[48];
+                    snprintf(b, sizeof b, "%s\"p%05d\":%lld", j ? "," : "", (first + 37 * j) % P, (long long)(NOW - 1000));
+                    v += b;
+                }
+                v += "},\"lu\":" + std::to_string(NOW - (int64_t)(rng() % 3600000)) + "}";
+                if ((rng() % 8) == 0) v.resize(v.size() / 2);
+                buf += v;
+            }
+            off.push_back((int64_t)buf.size());
+        }
+        const int rc = mmp_models_upsert_json(c, buf.data(), off.data(), k, idx.data(), (rng() % 4) ? del.data() : nullptr, lul.data(), status.data());
+        for (int i = 0; i < k && rc == MMP_OK; i++)
+            if (status[i] != 0 && status[i] != 1) g_fail++;
+        return rc;
+    };
     auto registry = [&]() {
         std::mt19937 rng(9);
-        while (!g_stop.load(std::memory_order_relaxed)) {
+        for (int round = 0; !g_stop.load(std::memory_order_relaxed); round++) {
             const int k = 1 + (int)(rng() % 16);
+            if (round & 1) {
+                CK(c, json_events(rng, k));
+                g_calls[2]++;
+                std::this_thread::sleep_for(std::chrono::microseconds(300 + rng() % 1500));
+                continue;
+            }
             std::vector<int32_t> idx(k), e_pod;
             std::vector<int64_t> e_time;
             std::vector<mmp_model_row> rows(k);
@@ -326,6 +375,18 @@ int main(int argc, char **argv)
                 int32_t e_pod[2] = {w32(), w32()};
                 int64_t e_time[2] = {w64(), w64()};
                 rc = mmp_models_upsert(c, idx, rows, 2, e_pod, e_time, 2);
+            } else if (kind == 7) {  // registry events as JSON: rows beyond the table, offsets that run backwards, buffers that are not there
+                static const char val[] = "{\"instanceIds\":{\"p00001\":5}}{}";
+                int64_t off[3] = {0, (int64_t)sizeof val - 3, (int64_t)sizeof val - 1};
+                int32_t idx[2] = {(int32_t)(rng() % M), (rng() & 1) ? w32() : (int32_t)(rng() % M)};
+                if (idx[1] == M) idx[1] = M + 1;  // (index == the model count APPENDS — legal, and the table would grow call by call)
+                uint8_t del[2] = {0, (uint8_t)(rng() & 1)};
+                int64_t lul[2];
+                int32_t status[2];
+                const unsigned how = rng() % 6;
+                if (how == 0) off[1] = w64() | 1;  // (odd: never the monotone value it had)
+                rc = mmp_models_upsert_json(c, how == 1 ? nullptr : val, how == 2 ? nullptr : off, how == 3 ? -2 : 2, how == 4 ? nullptr : idx,
+                                            del, lul, how == 5 ? nullptr : status);
             } else {
                 rc = mmp_place_batch(c, rq.data(), n, pool.data(), 32, (rng() & 7) ? NOW : w64(), out.data());
                 if (rc == MMP_OK) {
