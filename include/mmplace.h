@@ -967,6 +967,58 @@ typedef struct {
 int mmp_registry_ops(mmp_ctx *ctx, const mmp_registry_op *ops, int32_t n, int64_t now_ms, uint32_t flags, uint8_t *status_out,
                      mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info_out);
 
+/* getStatus (MM.java:3247) answered from the resident registry, a batch of questions at a time: the status class of
+ * invokeModel's "getStatus case" (:3760-3768) and the copy list makeStatusInfo builds for the reply (:3013-3058).  Each answer
+ * is a pure function of the record, so after an applied prune, janitor plan or mmp_registry_ops a host asks here instead of
+ * reading the registry back.
+ *
+ * A request names a registry row (`model`; -1: no record, mr == null, :3257 — both lists empty) and optionally the instance
+ * whose local load failed (`fail_pod` = the pod of mle.getInstanceId(); -1: no mle).  An all-zero row — what a deleted record
+ * leaves behind — is an ordinary record without copies: the library cannot tell it from a live one, and a host that deletes
+ * records sends -1 for them.
+ *
+ *   The failure overlay (:3017-3026).  fail_pod >= 0 and NOT among the record's loadFailedInstanceIds: it is put there with time
+ *   now_ms, where mmp_registry_ops puts a new key — in front of the first RESOLVED entry (0 <= pod < pod count) with a greater
+ *   id_order in the committed instance table, at the end if there is none; unresolved entries are never compared — and its
+ *   entry in instanceIds, if any, is removed.  fail_pod already among the failed entries: nothing changes, and its loaded entry
+ *   stays too (that is what the Java does).  The registry is not written.
+ *
+ *   The class, from the lists after the overlay: model -1: MMP_MST_NOT_FOUND; else loaded entries and no MMP_MSTF_MISS:
+ *   MMP_MST_ASK; else fail_pod >= 0 or any failed entry: MMP_MST_LOADING_FAILED (:3764); else MMP_MST_NOT_LOADED.
+ *
+ *   The copies (:3029-3057): the loaded entries in list order as MMP_COPY_NOT_CHECKED, then the failed entries in list order as
+ *   MMP_COPY_LOADING_FAILED, then Collections.sort with Long.compare(o.time, time): a STABLE sort by signed time, descending —
+ *   equal times keep the concatenation order; times are arbitrary int64 values.  `pod` is reported as stored (an unresolved
+ *   entry keeps its -1 or out-of-table value).  The MMP_COPY_LOADING_FAILED rows, read in output order, are also the order of
+ *   the reply's message list (:3043-3045); the messages themselves (loadFailureInfos) stay with the caller, as in
+ *   mmp_registry_ops.
+ *
+ * rows_out[i].copy_off is the exclusive prefix sum of the counts in request order; the copies of request i are
+ * copies_out[copy_off, copy_off + n_not_checked + n_failed).  *n_copies_out is always the total.  copies_out == NULL with
+ * max_copies == 0 returns the rows and the total only.  A positive max_copies below the total returns every copy whose global
+ * index is below max_copies, the complete rows and the total, and still 0.  The answers are identical from run to run.
+ *
+ * Requests may repeat a model; n == 0 is valid.  Read-only: the call sees the registry between two writers, never inside one
+ * (it takes it the way mmp_registry_census does) and does not hold decisions off.  MMP_EINVAL, with nothing written: a model
+ * outside [-1, n_models), a fail_pod outside [-1, pod slots of the committed instance table), an unknown flag bit or a non-zero
+ * `reserved`, now_ms <= 0 while a request carries a fail_pod, a NULL required buffer, more than INT32_MAX copies in all.
+ * MMP_ESTATE when a request carries a fail_pod >= 0 before the first commit (the overlay needs id_order); without a fail_pod no
+ * commit is needed. */
+#define MMP_MST_NOT_FOUND 0      /* mr == null (:3257)                                             */
+#define MMP_MST_NOT_LOADED 1     /* SI_NOT_LOADED (:3767)                                          */
+#define MMP_MST_LOADING_FAILED 2 /* :3765 / :3981                                                  */
+#define MMP_MST_ASK 3            /* the record has copies and the cache-hit loop has not been run: */
+                                 /* the host asks a copy (mmp_serve_batch / mmp_route_batch); on   */
+                                 /* LOADED / LOADING the list below is updateWithModelCopyInfo's   */
+#define MMP_MSTF_MISS 1u         /* the cache-hit loop is exhausted: global cache miss, :3760      */
+#define MMP_COPY_NOT_CHECKED 0
+#define MMP_COPY_LOADING_FAILED 1
+typedef struct { int32_t model; int32_t fail_pod; uint32_t flags; uint32_t reserved; } mmp_status_req;   /* 16 bytes */
+typedef struct { int32_t cls; int32_t copy_off; int32_t n_not_checked; int32_t n_failed; } mmp_status_row; /* 16 bytes */
+typedef struct { int32_t pod; int32_t status; int64_t time; } mmp_status_copy;                            /* 16 bytes */
+int mmp_models_status(mmp_ctx *ctx, const mmp_status_req *reqs, int32_t n, int64_t now_ms, mmp_status_row *rows_out,
+                      mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out);
+
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for
  * MMP_SCALE_UP rows the caller passes those pods as extra excludes of the load-target decisions

@@ -124,6 +124,13 @@ final class MmPlace {
     // mmp_registry_ops_info (56 bytes); info.truncated: nothing was applied.
     static native int registryOps(long h, ByteBuffer ops, int n, long nowMs, int flags, ByteBuffer statusOut, ByteBuffer editsOut,
                                   int maxEdits, ByteBuffer info);
+    // getStatus (MM.java:3247) from the resident registry: reqs = mmp_status_req rows (16 bytes: model or -1 for mr == null, failPod =
+    // the pod of mle.getInstanceId() or -1, flags 1 = the cache-hit loop is exhausted, 0).  rowsOut = mmp_status_row rows (16 bytes:
+    // class 0 NOT_FOUND / 1 NOT_LOADED / 2 LOADING_FAILED / 3 ask a copy, copyOff, nNotChecked, nFailed), copiesOut = mmp_status_copy
+    // rows (16 bytes: pod, 0 NOT_CHECKED / 1 LOADING_FAILED, time) in makeStatusInfo's sorted order (:3013-3058), request i's at
+    // copyOff; nCopiesOut = the total, also when copiesOut (null with maxCopies 0: sizes only) held a prefix.
+    static native int modelsStatus(long h, ByteBuffer reqs, int n, long nowMs, ByteBuffer rowsOut, ByteBuffer copiesOut, int maxCopies,
+                                   ByteBuffer nCopiesOut);
     static native int scaleupPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer outs,
                                   ByteBuffer overloadedOut, ByteBuffer skipped);
     static native int scaledownPlan(long h, ByteBuffer entries, int n, ByteBuffer params, ByteBuffer removedOut);

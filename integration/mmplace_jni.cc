@@ -421,6 +421,21 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryOps(JNIEnv 
                  mmp_registry_ops(ctx_of(h), buf<mmp_registry_op>(env, ops), n, nowMs, static_cast<uint32_t>(flags), buf<uint8_t>(env, statusOut),
                                   buf<mmp_registry_op_edit>(env, editsOut), maxEdits, buf<mmp_registry_ops_info>(env, info)));
 }
+// getStatus answers from the resident registry (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058): every
+// buffer's capacity is checked here, the library only knows n / maxCopies.  A null copiesOut with maxCopies = 0: the sizes only.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsStatus(JNIEnv *env, jclass, jlong h, jobject reqs, jint n, jlong nowMs,
+                                                                          jobject rowsOut, jobject copiesOut, jint maxCopies,
+                                                                          jobject nCopiesOut)
+{
+    if (!holds<mmp_status_req>(env, reqs, n, "modelsStatus: reqs shorter than n") ||
+        !holds<mmp_status_row>(env, rowsOut, n, "modelsStatus: rowsOut shorter than n") ||
+        !holds<mmp_status_copy>(env, copiesOut, maxCopies, "modelsStatus: copiesOut shorter than maxCopies") ||
+        !holds<int32_t>(env, nCopiesOut, 1, "modelsStatus: nCopiesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_status(ctx_of(h), buf<mmp_status_req>(env, reqs), n, nowMs, buf<mmp_status_row>(env, rowsOut),
+                                   buf<mmp_status_copy>(env, copiesOut), maxCopies, buf<int32_t>(env, nCopiesOut)));
+}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaleupPlan(JNIEnv *env, jclass, jlong h, jobject entries,
                                                                          jint n, jobject params, jobject outs,
                                                                          jobject overloadedOut, jobject skipped)

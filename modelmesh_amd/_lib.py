@@ -146,6 +146,18 @@ REGISTRY_OPS_INFO = np.dtype([("n_edits", "<i4"), ("n_unchanged", "<i4"), ("trun
                               ("n_entries_removed", "<i4")])
 assert REGISTRY_OP.itemsize == 40 and REGISTRY_OP_EDIT.itemsize == 40 and REGISTRY_OPS_INFO.itemsize == 56
 
+# mmp_models_status (getStatus MM.java:3247: the class of :3760-3768, the copy list of makeStatusInfo :3013-3058)
+(MST_NOT_FOUND, MST_NOT_LOADED, MST_LOADING_FAILED, MST_ASK) = range(4)
+MSTF_MISS = 1
+COPY_NOT_CHECKED, COPY_LOADING_FAILED = 0, 1
+STATUS_BLOCK = 256       # requests / output entries per workgroup (csrc/status_kernels.hpp: kStatusBlock)
+STATUS_WAVE_ROW = 64     # copies a packed lane still ranks on its own (kStatusWaveRow); longer rows take the workgroup path
+STATUS_TILE = 1024       # times of one long row staged in LDS at once (kStatusTile)
+STATUS_REQ = np.dtype([("model", "<i4"), ("fail_pod", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
+STATUS_ROW = np.dtype([("cls", "<i4"), ("copy_off", "<i4"), ("n_not_checked", "<i4"), ("n_failed", "<i4")])
+STATUS_COPY = np.dtype([("pod", "<i4"), ("status", "<i4"), ("time", "<i8")])
+assert STATUS_REQ.itemsize == 16 and STATUS_ROW.itemsize == 16 and STATUS_COPY.itemsize == 16
+
 # mmp_registry_census (the registry listener's model counts, MM.java:2807-2854, :6852-6863)
 REGISTRY_STATS = np.dtype(
     [("n_models", "<i4"), ("n_loaded", "<i4"), ("n_failed", "<i4"), ("n_loaded_and_failed", "<i4"), ("n_unloaded_used", "<i4"),
@@ -262,6 +274,7 @@ SYMBOLS = [
     ("mmp_registry_missing_reset", C.c_int, [_P]),
     ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("mmp_registry_ops", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint32, _P, _P, C.c_int32, _P]),
+    ("mmp_models_status", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_registry_census", C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),

@@ -39,6 +39,7 @@
 #include "registry_kernels.hpp"
 #include "janitor_kernels.hpp"
 #include "registry_ops_kernels.hpp"
+#include "status_kernels.hpp"
 #include "census_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
@@ -399,6 +400,9 @@ struct mmp_ctx {
     std::vector<unsigned char> cn_host;
     size_t census_pod_lds = 32 * 1024;
     int32_t census_cus = 0;
+    // mmp_models_status (status_kernels.hpp): the call's copy list on the device.  Owned by batch_mu, used on c->stream; its other
+    // scratch is the registry plans' (plan).
+    DevBuf st_copies;
 };
 
 namespace {
@@ -1055,7 +1059,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -5129,6 +5133,96 @@ try {
                            c->ent_time.as<int64_t>(), base, arena_end, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
     });
 } MMP_CATCH(c, "mmp_registry_ops")
+
+int mmp_models_status(mmp_ctx *c, const mmp_status_req *reqs, int32_t n, int64_t now, mmp_status_row *rows_out,
+                      mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out)
+try {
+    if (!c || !n_copies_out || n < 0 || max_copies < 0 || (n > 0 && (!reqs || !rows_out)) || (max_copies > 0 && !copies_out))
+        return fail(c, MMP_EINVAL, "mmp_models_status: bad argument");
+    // batch_mu owns c->stream and the scratch for the whole call, and every writer of what this call reads — registry events, an
+    // applied prune, janitor plan or batch of ops, the loaders of the registry, a commit — takes it too and leaves with its work
+    // on c->stream finished.  The state lock is not taken: nothing decisions read is written.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t M = c->n_models;
+    // the requests index the rows and the instance table: their ranges are settled here, before any kernel reads them
+    bool overlay = false;
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_status_req &q = reqs[i];
+        if (q.model < -1 || q.model >= M) return fail(c, MMP_EINVAL, "mmp_models_status: request %d names model %d of %d", i, q.model, M);
+        if (q.fail_pod < -1) return fail(c, MMP_EINVAL, "mmp_models_status: request %d names pod %d", i, q.fail_pod);
+        if ((q.flags & ~MMP_MSTF_MISS) || q.reserved) return fail(c, MMP_EINVAL, "mmp_models_status: request %d has flags %u, reserved %u", i, q.flags, q.reserved);
+        overlay |= q.fail_pod >= 0;
+    }
+    int32_t P = 0;
+    const mmp_pod_row *pods = nullptr;  // the committed rows, read for id_order by the overlay alone
+    if (overlay) {
+        if (now <= 0) return fail(c, MMP_EINVAL, "mmp_models_status: now_ms = %lld with a fail_pod", (long long)now);
+        if (const int rc = plan_state_guard(c, "mmp_models_status")) return rc;
+        P = c->snap.P;
+        pods = c->sb[c->cur].pods.as<mmp_pod_row>();
+        for (int32_t i = 0; i < n; i++)
+            if (reqs[i].fail_pod >= P) return fail(c, MMP_EINVAL, "mmp_models_status: request %d names pod %d of %d", i, reqs[i].fail_pod, P);
+    }
+    if (n == 0) {
+        *n_copies_out = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int nb = div_up(n, kStatusBlock);
+    HIP_TRY(c, c->plan.rows_in.ensure((size_t)n * sizeof(mmp_status_req)));
+    HIP_TRY(c, c->plan.edits.ensure((size_t)n * sizeof(mmp_status_row)));
+    HIP_TRY(c, c->plan.keep_off.ensure((size_t)n * sizeof(StatusAux)));
+    HIP_TRY(c, c->plan.row_tmp.ensure((size_t)n * 4));
+    HIP_TRY(c, c->plan.call_scalars.ensure(std::max(sizeof(StatusScalars), std::max(sizeof(RopsScalars), sizeof(JanitorScalars)))));
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    const int32_t *ent_pod = c->ent_pod.as<int32_t>();
+    const int64_t *ent_time = c->ent_time.as<int64_t>();
+    const mmp_status_req *d_reqs = c->plan.rows_in.as<mmp_status_req>();
+    mmp_status_row *d_rows = c->plan.edits.as<mmp_status_row>();
+    StatusAux *d_aux = c->plan.keep_off.as<StatusAux>();
+    int32_t *d_long = c->plan.row_tmp.as<int32_t>();
+    StatusScalars *ss = c->plan.call_scalars.as<StatusScalars>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
+    HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, reqs, (size_t)n * sizeof(mmp_status_req), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(ss, 0, sizeof(StatusScalars), st));
+    HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
+    KT_BEGIN(c, st);  // device span: count, scan, offsets — and, behind the one read-back of the sizes, the two emit kernels
+    hipLaunchKernelGGL(status_count_kernel, dim3(nb), dim3(kStatusBlock), 0, st, d_reqs, n, models, ent_pod, pods, P, d_rows, d_aux,
+                       c->plan.block_counts.as<int32_t>(), ss);
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
+    hipLaunchKernelGGL(status_rows_kernel, dim3(nb), dim3(kStatusBlock), 0, st, n, d_rows, c->plan.block_counts.as<int32_t>(), d_long);
+    HIP_TRY(c, hipGetLastError());
+    StatusScalars hs{};
+    PruneScalars h{};
+    HIP_TRY(c, hipMemcpyAsync(&hs, ss, sizeof hs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (hs.n_copies > (unsigned long long)INT32_MAX) {
+        c->prof_armed = false;
+        return fail(c, MMP_EINVAL, "mmp_models_status: %llu copies in all; split the batch", hs.n_copies);
+    }
+    const int32_t total = h.n_kept, n_long = h.n_edits, take = std::min(total, max_copies);
+    if (take > 0) {
+        HIP_TRY(c, c->st_copies.ensure((size_t)take * sizeof(mmp_status_copy)));
+        mmp_status_copy *d_copies = c->st_copies.as<mmp_status_copy>();
+        hipLaunchKernelGGL(status_emit_kernel, dim3(div_up(total, kStatusBlock)), dim3(kStatusBlock), 0, st, d_reqs, n, total, models, ent_pod,
+                           ent_time, now, d_rows, d_aux, d_copies, take);
+        if (n_long > 0)
+            hipLaunchKernelGGL(status_long_kernel, dim3(n_long), dim3(kStatusLongBlock), 0, st, d_reqs, d_long, models, ent_pod, ent_time, now,
+                               d_rows, d_aux, d_copies, take);
+    }
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    // every word of copies[0, take) has exactly one writer above: the ranks of a segment are a permutation of its indices
+    if (take > 0) HIP_TRY(c, copy_sync(c, copies_out, c->st_copies.p, (size_t)take * sizeof(mmp_status_copy), hipMemcpyDeviceToHost));
+    HIP_TRY(c, copy_sync(c, rows_out, d_rows, (size_t)n * sizeof(mmp_status_row), hipMemcpyDeviceToHost));
+    kt_collect(c);
+    *n_copies_out = total;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_models_status")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

@@ -687,6 +687,36 @@ class Solver:
         ne = min(max_edits, int(info[0]["n_edits"]))
         return status[:n].copy(), edits[:ne].copy(), info[0].copy()
 
+    def models_status(self, reqs, now: int):
+        """getStatus answers (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058) for a batch of mmp_status_req
+        rows from the resident registry: (rows, copies) — one mmp_status_row per request, and the copies of request i, latest
+        first, at copies[rows[i].copy_off : ... + n_not_checked + n_failed].  Two calls: the sizes, then the list; repeated if
+        the registry changed in between."""
+        max_copies = self.models_status_raw(reqs, now, 0)[2]
+        while True:
+            rows, copies, total, rc = self.models_status_raw(reqs, now, max_copies)
+            self._ck(rc)
+            if total <= max_copies:
+                return rows, copies
+            max_copies = total
+
+    def models_status_raw(self, reqs, now, max_copies, fill=0, null_out=False):
+        """One mmp_models_status call with exactly this capacity (0: a NULL copies buffer), the outputs filled with the byte
+        `fill` first: (rows, copies[:min(total, max_copies)] — all max_copies rows when the call fails —, total, rc).  Does not
+        raise: rc is the return code (total is -1 where the library did not set it).  null_out: NULL rows_out and n_copies_out."""
+        from ._lib import STATUS_COPY, STATUS_REQ, STATUS_ROW
+        reqs = np.ascontiguousarray(reqs, dtype=STATUS_REQ)
+        n = len(reqs)
+        rows = np.zeros(max(n, 1), dtype=STATUS_ROW)
+        copies = np.zeros(max(max_copies, 1), dtype=STATUS_COPY)
+        rows.view(np.uint8)[:] = fill
+        copies.view(np.uint8)[:] = fill
+        total = C.c_int32(-1)
+        rc = self.lib.mmp_models_status(self.h, ptr(reqs) if n else None, n, int(now), None if null_out else ptr(rows),
+                                        ptr(copies) if max_copies else None, int(max_copies), None if null_out else C.byref(total))
+        got = max_copies if rc != 0 else min(max_copies, max(total.value, 0))
+        return rows[:n].copy(), copies[:got].copy(), total.value, rc
+
     def registry_census(self):
         """The registry listener's model counts (MM.java:2807-2854, :6852-6863) over the resident registry: (stats, pod_loaded,
         pod_failed, type_stats) — one mmp_registry_stats row, per pod slot of the staged instance table the records that hold it in
