@@ -17,10 +17,19 @@
 //
 // Pure byte / integer work: no MFMA, bound by the bytes of JSON read once.
 //
-// Malformed values (status 1, row untouched): truncated or unbalanced nesting / strings, a value that
-// does not start with '{', a known field or a map entry whose value has the wrong type, missing ',' or
-// ':' separators.  The grammar INSIDE values that are skipped (unknown fields, loc / zone / labels,
-// fails) is not validated beyond balanced nesting.
+// Malformed values (status 1, row untouched): empty or blank values, truncated or unbalanced nesting / strings, a value
+// that does not start with '{', bytes other than blanks behind its closing brace, a known field or a map entry whose
+// value has the wrong type, missing, doubled or trailing ',' or ':' separators.  Both parsers give the same verdict and
+// the same row for such a value and for every well-formed one, whatever its length; a later duplicate of a field wins,
+// the maps included (the row holds the entries of the last instanceIds / failedIn only), also a `"type":null` or a
+// `"shutdown":false` behind an earlier one; an EARLIER duplicate is held to its type all the same (the entries of a
+// map that lost are walked, not written).  A rejected ModelRecord of a full reload leaves the empty row of the default
+// type.  A map key may be empty: `"":1,`
+// is the shortest entry, five bytes, which is what the parking rule of the entries rests on (kJEntryBytes below).
+// UNSPECIFIED — the two parsers may differ, tests/ingest_model.py names the class and no test relies on it: a value that
+// is invalid only INSIDE a value that is skipped (unknown fields, loc / zone / labels, fails: the wave path checks
+// balanced nesting there and nothing else, the serial walk a little more), leading zeros, integers outside int64 / int32,
+// a `type` that is neither a string nor null, and backslash escapes in the names and keys the parsers hash.
 #pragma once
 #include "snapshot.hpp"
 
@@ -64,6 +73,14 @@ __device__ __forceinline__ bool j_eat(JCur &c, char ch)
         return true;
     }
     return false;
+}
+
+// at the record's closing brace: nothing but blanks may follow it (the wave path: zero_pos == R.g)
+__device__ __forceinline__ void j_end_of_value(JCur &c)
+{
+    c.p++;
+    j_ws(c);
+    if (c.p < c.e) c.bad = true;
 }
 
 // at the opening quote: hash the raw bytes up to the closing quote (escapes are hashed verbatim)
@@ -183,7 +200,10 @@ __device__ __forceinline__ bool pod_record_serial(const char *b, const char *e, 
     bool first = true;
     while (!c.bad) {
         j_ws(c);
-        if (c.p < c.e && *c.p == '}') break;
+        if (c.p < c.e && *c.p == '}') {
+            j_end_of_value(c);
+            break;
+        }
         if (!first && !j_eat(c, ',')) {
             c.bad = true;
             break;
@@ -212,8 +232,8 @@ __device__ __forceinline__ bool pod_record_serial(const char *b, const char *e, 
             r.loading_in_progress = (int32_t)j_int(c);
         else if (KEY_IS(h, klen, kp, "rpm"))
             r.rpm = (int32_t)j_int(c);
-        else if (KEY_IS(h, klen, kp, "shutdown")) {
-            if (j_bool(c)) r.flags |= MMP_POD_SHUTTING_DOWN;
+        else if (KEY_IS(h, klen, kp, "shutdown")) {  // (set or CLEARED: a later duplicate wins)
+            r.flags = j_bool(c) ? (r.flags | MMP_POD_SHUTTING_DOWN) : (r.flags & ~MMP_POD_SHUTTING_DOWN);
         } else if (KEY_IS(h, klen, kp, "startTime"))
             st = j_int(c);
         else if (KEY_IS(h, klen, kp, "vers"))
@@ -286,6 +306,15 @@ __device__ __forceinline__ int32_t j_id_map(JCur &c, const HashTab &ids, int32_t
     return n;
 }
 
+// The parking rule.  The shortest map entry is `"":1,` — an empty key is a key — so n entries of one record take at least
+// 5n + 1 bytes of its JSON (5n - 1 for the entries, the map's braces), and record i may park its entries at slot
+// off[i] / kJEntryBytes + e: off[i + 1] >= off[i] + 5n + 1 puts the next record's first slot behind them, and the last
+// record's behind bytes / kJEntryBytes.  The host sizes the parking arrays as bytes / kJEntryBytes + 2 (mmplace.hip).  The
+// wave path refuses a map whose separators announce more entries than its bytes can hold BEFORE any entry is parked: the
+// entry lanes write independently, and a lane with a well-formed entry behind malformed two-byte ones would otherwise park
+// it beyond the record's slots.
+constexpr int kJEntryBytes = 5;
+
 struct IngestModelsArgs {
     const char *buf;
     const int64_t *off;
@@ -297,8 +326,8 @@ struct IngestModelsArgs {
     int64_t *last_unload;
     int32_t *status;
     int32_t *cnt;          // n_loaded + n_failed per record (scanned into the CSR offsets)
-    int32_t *ent_pod;      // entries of record i are parked at slot off[i] / 6 (an entry takes >= 6 bytes of JSON,
-    int64_t *ent_time;     // so the slots of consecutive records never overlap) until the offsets are known
+    int32_t *ent_pod;      // entries of record i are parked at slot off[i] / kJEntryBytes (so the slots of consecutive
+    int64_t *ent_time;     // records never overlap) until the offsets are known
     int32_t grp;           // records per wavefront (1..kJGroup)
     // mmp_models_upsert_json (all three NULL for the full reload, where record i IS row i): the records are EVENTS, rows / cnt /
     // last_unload / status are per-event scratch, and event i belongs to the registry row in slot[i] of the call's distinct rows.
@@ -323,18 +352,24 @@ __device__ __forceinline__ void j_publish_model(const IngestModelsArgs &A, int i
     if (A.slot && !bad) atomicMax(&A.win[A.slot[i]], i);
 }
 
-// One ModelRecord value walked by ONE lane.  PASS 0: type / counts / lu / lul; PASS 1: the entries.
+// One ModelRecord value walked by ONE lane.  PASS 0: type / counts / lu / lul, and in mapf[] the index of the field that set
+// each map's count (the last duplicate: the one that wins); PASS 1: the entries, of those two fields only — an earlier duplicate
+// is walked but not written, so the row holds exactly the winner's entries, as on the wave path.
 template <int PASS>
 __device__ __forceinline__ bool model_record_serial(const IngestModelsArgs &A, const char *b, const char *e,
-                                                    mmp_model_row &r, int64_t &lul)
+                                                    mmp_model_row &r, int64_t &lul, int32_t (&mapf)[2])
 {
     JCur c{b, e, false};
     lul = 0;
+    int32_t f = -1;  // index of the field being read
     if (!j_eat(c, '{')) c.bad = true;
     bool first = true;
     while (!c.bad) {
         j_ws(c);
-        if (c.p < c.e && *c.p == '}') break;
+        if (c.p < c.e && *c.p == '}') {
+            j_end_of_value(c);
+            break;
+        }
         if (!first && !j_eat(c, ',')) {
             c.bad = true;
             break;
@@ -349,19 +384,33 @@ __device__ __forceinline__ bool model_record_serial(const IngestModelsArgs &A, c
             c.bad = true;
             break;
         }
+        f++;
         if (KEY_IS(h, klen, kp, "instanceIds")) {
-            const int32_t k = j_id_map(c, A.ids, PASS ? A.ent_pod + r.ent_off : nullptr, PASS ? A.ent_time + r.ent_off : nullptr);
-            if (PASS == 0) r.n_loaded = k;
+            const bool wr = PASS && f == mapf[0];
+            const int32_t k = j_id_map(c, A.ids, wr ? A.ent_pod + r.ent_off : nullptr, wr ? A.ent_time + r.ent_off : nullptr);
+            if (PASS == 0) {
+                r.n_loaded = k;
+                mapf[0] = f;
+            }
         } else if (KEY_IS(h, klen, kp, "failedIn")) {
-            const int32_t k = j_id_map(c, A.ids, PASS ? A.ent_pod + r.ent_off + r.n_loaded : nullptr,
-                                       PASS ? A.ent_time + r.ent_off + r.n_loaded : nullptr);
-            if (PASS == 0) r.n_failed = k;
+            const bool wr = PASS && f == mapf[1];
+            const int32_t k = j_id_map(c, A.ids, wr ? A.ent_pod + r.ent_off + r.n_loaded : nullptr,
+                                       wr ? A.ent_time + r.ent_off + r.n_loaded : nullptr);
+            if (PASS == 0) {
+                r.n_failed = k;
+                mapf[1] = f;
+            }
         } else if (PASS == 0 && KEY_IS(h, klen, kp, "type")) {
             j_ws(c);
             if (c.p < c.e && *c.p == '"')
                 r.type = tab_find(A.types, j_string_hash(c), A.unknown_type);
-            else
-                j_skip_value(c);  // null -> DEFAULT_TYPE (ModelRecord.java:121)
+            else {  // null -> DEFAULT_TYPE (ModelRecord.java:121), also behind an earlier duplicate that named a type
+                // (exactly `null`, as on the wave path; anything else that is not a string is skipped)
+                if (c.e - c.p >= 4 && c.p[0] == 'n' && c.p[1] == 'u' && c.p[2] == 'l' && c.p[3] == 'l' &&
+                    (c.e - c.p == 4 || c.p[4] == ',' || c.p[4] == '}' || c.p[4] == ' ' || c.p[4] == '\n' || c.p[4] == '\t' || c.p[4] == '\r'))
+                    r.type = A.default_type;
+                j_skip_value(c);
+            }
         } else if (PASS == 0 && KEY_IS(h, klen, kp, "lu"))
             r.last_used = j_int(c);
         else if (PASS == 0 && KEY_IS(h, klen, kp, "lul"))
@@ -801,7 +850,7 @@ __global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__rest
 
 // ModelRecord values, A.grp per WAVEFRONT, one pass: type / n_loaded / n_failed / last_used, the status
 // (the whole value is validated, entries included) and the entries themselves, parked at slot
-// off[i] / 6 + e of ent_pod / ent_time until compact_entries_kernel moves them to their CSR position.
+// off[i] / kJEntryBytes + e of ent_pod / ent_time until compact_entries_kernel moves them to their CSR position.
 // Slots: 0 type, 1 lu, 2 lul, 3 instanceIds, 4 failedIn (value = entry count), 5..8 = the two maps'
 // opener / closer positions.
 __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs A)
@@ -825,15 +874,19 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                 r.last_used = 0;
                 r.ent_off = 0;
                 int64_t lul = 0, lul2;
+                int32_t mapf[2] = {-1, -1};
                 const char *b = A.buf + S.off[i - i0], *e = A.buf + S.off[i - i0 + 1];
                 bool bad = A.deleted && A.deleted[i];  // (a deleted event's value is not walked)
-                if (!bad) bad = model_record_serial<0>(A, b, e, r, lul);
+                if (!bad) bad = model_record_serial<0>(A, b, e, r, lul, mapf);
                 if (!bad) {
                     mmp_model_row w = r;
-                    w.ent_off = (int32_t)(S.off[i - i0] / 6);
-                    (void)model_record_serial<1>(A, b, e, w, lul2);
-                } else
+                    w.ent_off = (int32_t)(S.off[i - i0] / kJEntryBytes);
+                    (void)model_record_serial<1>(A, b, e, w, lul2, mapf);
+                } else {  // the row a rejected record gets on the wave path
+                    r.type = A.default_type;
                     r.n_loaded = r.n_failed = 0;
+                    r.last_used = 0;
+                }
                 j_publish_model(A, i, bad, r, lul);
             }
             i++;
@@ -874,8 +927,11 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                             for (int k = v + 1; k < ve; k++) th = (th ^ (uint64_t)R.by[k]) * 0x100000001b3ull;
                             val = tab_find(A.types, th, A.unknown_type);
                             if (!j_term(R, ve + 1, R.m1, R.g, last)) lbad = true;
+                        } else if (j_lit_at(R, v, "null", 4) && j_term(R, v + 4, R.m1, R.g, last)) {
+                            val = A.default_type;  // null -> DEFAULT_TYPE (ModelRecord.java:121); claimed, so that it also
+                                                   // wins over an earlier duplicate that named a type
                         } else {
-                            fid = -1;  // null (or a non-string) -> DEFAULT_TYPE (ModelRecord.java:121)
+                            fid = -1;  // not a string: the field is skipped
                         }
                     } else if (fid == 1 || fid == 2) {
                         if (!j_int_at(R, v, val) || !j_term(R, v, R.m1, R.g, last)) lbad = true;
@@ -891,6 +947,7 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                                 vclose = ce;
                                 val = j_count(R.c2, v, ce);
                                 if (j_count(R.m2, v, ce) != (val > 0 ? val - 1 : 0)) lbad = true;
+                                if (val * kJEntryBytes > ce - v) lbad = true;  // more entries than bytes: see kJEntryBytes
                                 if (val == 0) {
                                     int q = v + 1;
                                     while (q < ce && j_is_ws(R.by[q])) q++;
@@ -906,12 +963,33 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                 if (fid >= 0 && !lbad) j_claim(S, r, fid, j);
             }
             wave_sync();
-            if (fid >= 0 && !lbad && S.win[r][fid] == j) {
-                S.val[r][fid] = val;
-                if (fid >= 3) {
-                    S.val[r][5 + 2 * (fid - 3)] = vopen;
-                    S.val[r][6 + 2 * (fid - 3)] = vclose;
+            // A map that loses to a later duplicate is read by no entry lane, so it is walked here (the serial parser's map
+            // grammar, nothing written): a malformed entry rejects the record wherever it stands.  S.win is final only for
+            // the fields of the rounds run so far, so there are two kinds of loser: a map of THIS round that lost its claim
+            // walks itself; a map that won an EARLIER round is still in S.val (its opener is > 0; 0 = none yet, -1 = null)
+            // and is walked by the lane that now replaces it.
+            int lost_open = -1, lost_close = -1;
+            if (fid >= 0 && !lbad) {
+                if (S.win[r][fid] == j) {
+                    S.val[r][fid] = val;
+                    if (fid >= 3) {
+                        if (S.val[r][5 + 2 * (fid - 3)] > 0) {
+                            lost_open = (int)S.val[r][5 + 2 * (fid - 3)];
+                            lost_close = (int)S.val[r][6 + 2 * (fid - 3)];
+                        }
+                        S.val[r][5 + 2 * (fid - 3)] = vopen;
+                        S.val[r][6 + 2 * (fid - 3)] = vclose;
+                    }
+                } else if (fid >= 3) {
+                    lost_open = vopen;
+                    lost_close = vclose;
                 }
+            }
+            if (lost_open >= 0) {
+                const JView R = j_view(S, r);
+                JCur c{reinterpret_cast<const char *>(R.by) + lost_open, reinterpret_cast<const char *>(R.by) + lost_close + 1, false};
+                (void)j_id_map(c, A.ids, nullptr, nullptr);
+                if (c.bad) S.rec[r].bad = 1;
             }
             wave_sync();
         }
@@ -943,7 +1021,7 @@ __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs
                 if (lbad)
                     S.rec[r].bad = 1;
                 else {
-                    const int64_t slot = S.off[i - i0 + r] / 6 + e;
+                    const int64_t slot = S.off[i - i0 + r] / kJEntryBytes + e;
                     A.ent_pod[slot] = tab_find(A.ids, h, -1);
                     A.ent_time[slot] = tm;
                 }
@@ -976,7 +1054,7 @@ __global__ void compact_entries_kernel(const int64_t *__restrict__ off, int32_t 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t k = cnt[i], o = offs[i];
-    const int64_t slot = off[i] / 6;
+    const int64_t slot = off[i] / kJEntryBytes;
     rows[i].ent_off = o;
     for (int32_t e = 0; e < k; e++) {
         ent_pod[o + e] = tmp_pod[slot + e];
@@ -1017,7 +1095,7 @@ __global__ void upsert_json_build_kernel(const int32_t *__restrict__ win, const 
     if (w >= 0) {
         r = ev_rows[w];
         const int32_t cnt = r.n_loaded + r.n_failed, o = base + s_offs[j];
-        const int64_t slot = off[w] / 6;
+        const int64_t slot = off[w] / kJEntryBytes;
         for (int32_t e = 0; e < cnt; e++) {
             ent_pod[o + e] = tmp_pod[slot + e];
             ent_time[o + e] = tmp_time[slot + e];

@@ -2652,9 +2652,9 @@ try {
     A.rows = c->models.as<mmp_model_row>();
     A.last_unload = c->j_aux.as<int64_t>();
     A.status = c->j_status.as<int32_t>();
-    // one pass: every record's entries are parked at slot off / 6 (an entry takes >= 6 bytes of JSON), the
-    // counts are scanned, and the entries move to their CSR position — no host round trip in between
-    const size_t ent_cap = (size_t)(bytes / 6 + 2);
+    // one pass: every record's entries are parked at slot off / kJEntryBytes (ingest_kernels.hpp: n entries take >= 5n + 1
+    // bytes of JSON), the counts are scanned, and the entries move to their CSR position — no host round trip in between
+    const size_t ent_cap = (size_t)(bytes / kJEntryBytes + 2);
     HIP_TRY(c, c->j_tmp_pod.ensure(ent_cap * 4));
     HIP_TRY(c, c->j_tmp_time.ensure(ent_cap * 8));
     HIP_TRY(c, c->ent_pod.ensure(ent_cap * 4));
@@ -2721,7 +2721,7 @@ try {
     }
     const int64_t bytes = off[n] - off[0];
     if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: bad argument");
-    const size_t ent_cap = (size_t)(bytes / 6 + 2);  // an entry takes >= 6 bytes of JSON
+    const size_t ent_cap = (size_t)(bytes / kJEntryBytes + 2);  // n entries take >= 5n + 1 bytes of JSON
     if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: more than 2^31 entries in one call");
     const int32_t k = (int32_t)h_model.size();
     HIP_TRY(c, hipSetDevice(c->cfg.device));

@@ -20,7 +20,7 @@ for ln in p.stderr.split("\n"):
         cur = {"name": re.sub(r"\(.*", "", name).replace("mmp::", "")}
         rows.append(cur)
         continue
-    m = re.search(r"remark: .*?\s+(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", ln)
+    m = re.search(r"remark: .*?\s+(?:Total)?(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", ln)
     if m and cur is not None:
         cur[m.group(1).split(" [")[0]] = int(m.group(2))
 cols = ["VGPRs", "SGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize", "Occupancy", "LDS Size"]
