@@ -2,31 +2,36 @@
 //
 // ModelMesh keeps InstanceRecord and ModelRecord values as Jackson JSON in etcd / ZooKeeper
 // (MM.java:346 INST_REC_SERIALIZER, :628 registry view).  These kernels parse the raw values on the
-// device: one WAVEFRONT per record (j_scan: the record is staged into LDS with coalesced dword loads and
-// classified 64 bytes at a time with ballots — unescaped quotes, string interiors by prefix-xor, nesting
-// depth by popcounts — after which every field / map entry of the record is parsed by its own lane);
-// records longer than the LDS tile are walked by one lane (the serial parser below, which is also the
-// readable statement of the grammar).  Either way the parser matches the @JsonProperty names
-// (InstanceRecord.java:37-69: lruTime,count,cap,used,lThreads,lInProg,rpm,shutdown,startTime,vers,
-// loc,zone,labels; ModelRecord.java:61-114: type,encKey,mPath,instanceIds,failedIn,fails,refs,
-// autoDel,lu,lul — `instanceIds` has no @JsonProperty and serialises under its bean name) by
-// length + FNV-1a hash, and writes the packed row.  Fields Jackson omits because they hold the
-// default value come out as 0 / false, exactly like the bean's defaults.  Instance ids inside a
-// ModelRecord (the keys of instanceIds / failedIn) are resolved to pod indices through an
+// device.  A WAVEFRONT takes a group of up to kJGroup consecutive records (j_ingest_wave, the frame of both
+// kernels).  The records of the group that fit the LDS tile together are staged into it with coalesced
+// dword loads and classified 64 bytes at a time with ballots (j_scan: unescaped quotes, string interiors by
+// prefix-xor, nesting depth by popcounts), after which every field / map entry of every such record is
+// parsed by its own lane; a record longer than the tile is walked by one lane.  Both routes leave the
+// values of the known fields in the wavefront's slots (JWaveLds::val), and one publish turns the slots into
+// the packed row.
+//
+// ONE GRAMMAR, stated once.  What an object is — braces, members, separators — is j_members for the lane
+// that walks and j_scan + j_member_at for the lanes of the tile.  What a record holds is stated per record
+// type, for both routes: the slots (PodSlot, ModelSlot), the @JsonProperty name of each slot, matched by
+// length + FNV-1a hash and then byte for byte (pod_slot_of, model_slot_of — InstanceRecord.java:37-69,
+// ModelRecord.java:61-114; `instanceIds` has no @JsonProperty and serialises under its bean name), and the
+// row made of the slots (pod_row_from_slots, the publish of ingest_models_kernel).  Fields Jackson omits
+// because they hold the default value come out as 0 / false, exactly like the bean's defaults.  Instance
+// ids inside a ModelRecord (the keys of instanceIds / failedIn) are resolved to pod indices through an
 // open-addressing table of id hashes built when the ids are loaded.
 //
 // Pure byte / integer work: no MFMA, bound by the bytes of JSON read once.
 //
 // Malformed values (status 1, row untouched): empty or blank values, truncated or unbalanced nesting / strings, a value
 // that does not start with '{', bytes other than blanks behind its closing brace, a known field or a map entry whose
-// value has the wrong type, missing, doubled or trailing ',' or ':' separators.  Both parsers give the same verdict and
+// value has the wrong type, missing, doubled or trailing ',' or ':' separators.  Both routes give the same verdict and
 // the same row for such a value and for every well-formed one, whatever its length; a later duplicate of a field wins,
 // the maps included (the row holds the entries of the last instanceIds / failedIn only), also a `"type":null` or a
 // `"shutdown":false` behind an earlier one; an EARLIER duplicate is held to its type all the same (the entries of a
 // map that lost are walked, not written).  A rejected ModelRecord of a full reload leaves the empty row of the default
 // type.  A map key may be empty: `"":1,`
 // is the shortest entry, five bytes, which is what the parking rule of the entries rests on (kJEntryBytes below).
-// UNSPECIFIED — the two parsers may differ, tests/ingest_model.py names the class and no test relies on it: a value that
+// UNSPECIFIED — the two routes may differ, tests/ingest_model.py names the class and no test relies on it: a value that
 // is invalid only INSIDE a value that is skipped (unknown fields, loc / zone / labels, fails: the wave path checks
 // balanced nesting there and nothing else, the serial walk a little more), leading zeros, integers outside int64 / int32,
 // a `type` that is neither a string nor null, and backslash escapes in the names and keys the parsers hash.
@@ -35,25 +40,31 @@
 
 namespace mmp {
 
-__host__ __device__ constexpr uint64_t fnv1a(const char *s, int n)
+constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull;
+__host__ __device__ constexpr uint64_t fnv1a_step(uint64_t h, uint64_t byte) { return (h ^ byte) * 0x100000001b3ull; }
+
+template <class B>
+__host__ __device__ constexpr uint64_t fnv1a(const B *s, int n)
 {
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (int i = 0; i < n; i++) h = (h ^ (uint64_t)(unsigned char)s[i]) * 0x100000001b3ull;
+    uint64_t h = kFnvBasis;
+    for (int i = 0; i < n; i++) h = fnv1a_step(h, (unsigned char)s[i]);
     return h;
 }
 #define MMP_KEY(lit) fnv1a(lit, (int)sizeof(lit) - 1)
+template <class B>
+__device__ __forceinline__ bool bytes_equal(const B *p, const char *lit, int n)
+{
+    for (int i = 0; i < n; i++)
+        if ((unsigned char)p[i] != (unsigned char)lit[i]) return false;
+    return true;
+}
 // A field name is recognised by hash + length and then CONFIRMED byte for byte (kp = its first byte): an unknown
 // field whose name collides on both (FNV-1a is not collision resistant against a chosen name) is skipped like any
 // other unknown field instead of being parsed as the known one.
-template <class B>
-__device__ __forceinline__ bool key_bytes_equal(const B *kp, const char *lit, int n)
-{
-    for (int i = 0; i < n; i++)
-        if ((unsigned char)kp[i] != (unsigned char)lit[i]) return false;
-    return true;
-}
 #define KEY_IS(h, klen, kp, lit) \
-    ((h) == MMP_KEY(lit) && (klen) == (int)sizeof(lit) - 1 && key_bytes_equal((kp), lit, (int)sizeof(lit) - 1))
+    ((h) == MMP_KEY(lit) && (klen) == (int)sizeof(lit) - 1 && bytes_equal((kp), lit, (int)sizeof(lit) - 1))
+
+__device__ __forceinline__ bool j_is_ws(uint32_t c) { return c == ' ' || c == '\n' || c == '\t' || c == '\r'; }
 
 struct JCur {
     const char *p, *e;
@@ -62,7 +73,7 @@ struct JCur {
 
 __device__ __forceinline__ void j_ws(JCur &c)
 {
-    while (c.p < c.e && (*c.p == ' ' || *c.p == '\n' || *c.p == '\t' || *c.p == '\r')) c.p++;
+    while (c.p < c.e && j_is_ws(*c.p)) c.p++;
 }
 
 __device__ __forceinline__ bool j_eat(JCur &c, char ch)
@@ -75,18 +86,18 @@ __device__ __forceinline__ bool j_eat(JCur &c, char ch)
     return false;
 }
 
-// at the record's closing brace: nothing but blanks may follow it (the wave path: zero_pos == R.g)
-__device__ __forceinline__ void j_end_of_value(JCur &c)
+// the literal at the cursor, taken if it is there
+__device__ __forceinline__ bool j_lit(JCur &c, const char *lit, int n)
 {
-    c.p++;
-    j_ws(c);
-    if (c.p < c.e) c.bad = true;
+    if (c.e - c.p < n || !bytes_equal(c.p, lit, n)) return false;
+    c.p += n;
+    return true;
 }
 
 // at the opening quote: hash the raw bytes up to the closing quote (escapes are hashed verbatim)
 __device__ __forceinline__ uint64_t j_string_hash(JCur &c)
 {
-    uint64_t h = 0xcbf29ce484222325ull;
+    uint64_t h = kFnvBasis;
     if (c.p >= c.e || *c.p != '"') {
         c.bad = true;
         return 0;
@@ -94,11 +105,11 @@ __device__ __forceinline__ uint64_t j_string_hash(JCur &c)
     c.p++;
     while (c.p < c.e && *c.p != '"') {
         if (*c.p == '\\') {
-            h = (h ^ (uint64_t)(unsigned char)*c.p) * 0x100000001b3ull;
+            h = fnv1a_step(h, (unsigned char)*c.p);
             c.p++;
             if (c.p >= c.e) break;
         }
-        h = (h ^ (uint64_t)(unsigned char)*c.p) * 0x100000001b3ull;
+        h = fnv1a_step(h, (unsigned char)*c.p);
         c.p++;
     }
     if (c.p >= c.e) {
@@ -143,9 +154,7 @@ __device__ __forceinline__ void j_skip_value(JCur &c)
         return;
     }
     // number / true / false / null
-    while (c.p < c.e && *c.p != ',' && *c.p != '}' && *c.p != ']' && *c.p != ' ' && *c.p != '\n' && *c.p != '\t' &&
-           *c.p != '\r')
-        c.p++;
+    while (c.p < c.e && *c.p != ',' && *c.p != '}' && *c.p != ']' && !j_is_ws(*c.p)) c.p++;
 }
 
 // a Java long / int written by Jackson: optional '-', digits (wraps like Long.parseLong would not — a
@@ -174,34 +183,28 @@ __device__ __forceinline__ int64_t j_int(JCur &c)
 __device__ __forceinline__ bool j_bool(JCur &c)
 {
     j_ws(c);
-    if (c.e - c.p >= 4 && c.p[0] == 't' && c.p[1] == 'r' && c.p[2] == 'u' && c.p[3] == 'e') {
-        c.p += 4;
-        return true;
-    }
-    if (c.e - c.p >= 5 && c.p[0] == 'f' && c.p[1] == 'a' && c.p[2] == 'l' && c.p[3] == 's' && c.p[4] == 'e') {
-        c.p += 5;
-        return false;
-    }
-    c.bad = true;
+    if (j_lit(c, "true", 4)) return true;
+    if (!j_lit(c, "false", 5)) c.bad = true;
     return false;
 }
 
-// One InstanceRecord value, walked by ONE lane (records longer than the LDS tile of the wave path).
-// `r` arrives with id_order / replica_set / flags(LIVE) set by the host; every numeric field is
-// (re)written from the JSON.  Returns true when the value is malformed.
-__device__ __forceinline__ bool pod_record_serial(const char *b, const char *e, mmp_pod_row &r, int64_t &st)
+// The members of the object at the cursor, the serial statement of what j_scan + j_member_at check on the tile: '{', members
+// `"key" : value` separated by exactly one ',', '}'.  member(h, klen, kp) gets the key's hash, length and first byte with the
+// cursor behind the ':' and consumes the value.  whole_value: the object is the record, and nothing but blanks may follow
+// its closing brace (the wave path: zero_pos == R.g).
+template <class F>
+__device__ __forceinline__ void j_members(JCur &c, bool whole_value, F &&member)
 {
-    JCur c{b, e, false};
-    r.lru_time = r.capacity = r.used = r.version = 0;
-    r.count = r.loading_threads = r.loading_in_progress = r.rpm = 0;
-    r.flags &= ~MMP_POD_SHUTTING_DOWN;
-    st = 0;
     if (!j_eat(c, '{')) c.bad = true;
     bool first = true;
     while (!c.bad) {
         j_ws(c);
         if (c.p < c.e && *c.p == '}') {
-            j_end_of_value(c);
+            c.p++;
+            if (whole_value) {
+                j_ws(c);
+                if (c.p < c.e) c.bad = true;
+            }
             break;
         }
         if (!first && !j_eat(c, ',')) {
@@ -210,37 +213,65 @@ __device__ __forceinline__ bool pod_record_serial(const char *b, const char *e, 
         }
         first = false;
         j_ws(c);
-        const char *k0 = c.p;
+        const char *kp = c.p + 1;
         const uint64_t h = j_string_hash(c);
-        const int klen = (int)(c.p - k0) - 2;
-        const char *kp = k0 + 1;
+        const int klen = (int)(c.p - kp) - 1;
         if (c.bad || !j_eat(c, ':')) {
             c.bad = true;
             break;
         }
-        if (KEY_IS(h, klen, kp, "lruTime"))
-            r.lru_time = j_int(c);
-        else if (KEY_IS(h, klen, kp, "count"))
-            r.count = (int32_t)j_int(c);
-        else if (KEY_IS(h, klen, kp, "cap"))
-            r.capacity = j_int(c);
-        else if (KEY_IS(h, klen, kp, "used"))
-            r.used = j_int(c);
-        else if (KEY_IS(h, klen, kp, "lThreads"))
-            r.loading_threads = (int32_t)j_int(c);
-        else if (KEY_IS(h, klen, kp, "lInProg"))
-            r.loading_in_progress = (int32_t)j_int(c);
-        else if (KEY_IS(h, klen, kp, "rpm"))
-            r.rpm = (int32_t)j_int(c);
-        else if (KEY_IS(h, klen, kp, "shutdown")) {  // (set or CLEARED: a later duplicate wins)
-            r.flags = j_bool(c) ? (r.flags | MMP_POD_SHUTTING_DOWN) : (r.flags & ~MMP_POD_SHUTTING_DOWN);
-        } else if (KEY_IS(h, klen, kp, "startTime"))
-            st = j_int(c);
-        else if (KEY_IS(h, klen, kp, "vers"))
-            r.version = j_int(c);
-        else
-            j_skip_value(c);  // loc, zone, labels (interned on the host), anything newer
+        member(h, klen, kp);
     }
+}
+
+// ---- InstanceRecord: its slots, the name of each, the row they make -------------------------------------------------------------
+
+enum PodSlot { kPodLruTime, kPodCount, kPodCap, kPodUsed, kPodLThreads, kPodLInProg, kPodRpm, kPodShutdown, kPodStartTime, kPodVers, kPodSlots };
+
+// the slot of a field name, -1 for loc, zone, labels (interned on the host) and anything newer
+template <class B>
+__device__ __forceinline__ int pod_slot_of(uint64_t h, int klen, const B *kp)
+{
+    if (KEY_IS(h, klen, kp, "lruTime")) return kPodLruTime;
+    if (KEY_IS(h, klen, kp, "count")) return kPodCount;
+    if (KEY_IS(h, klen, kp, "cap")) return kPodCap;
+    if (KEY_IS(h, klen, kp, "used")) return kPodUsed;
+    if (KEY_IS(h, klen, kp, "lThreads")) return kPodLThreads;
+    if (KEY_IS(h, klen, kp, "lInProg")) return kPodLInProg;
+    if (KEY_IS(h, klen, kp, "rpm")) return kPodRpm;
+    if (KEY_IS(h, klen, kp, "shutdown")) return kPodShutdown;
+    if (KEY_IS(h, klen, kp, "startTime")) return kPodStartTime;
+    if (KEY_IS(h, klen, kp, "vers")) return kPodVers;
+    return -1;
+}
+
+// `r` arrives with id_order / replica_set / flags(LIVE) set by the host; every numeric field is (re)written from the slots
+__device__ __forceinline__ void pod_row_from_slots(mmp_pod_row &r, const int64_t *fv, int64_t &start_time)
+{
+    r.lru_time = fv[kPodLruTime];
+    r.count = (int32_t)fv[kPodCount];
+    r.capacity = fv[kPodCap];
+    r.used = fv[kPodUsed];
+    r.loading_threads = (int32_t)fv[kPodLThreads];
+    r.loading_in_progress = (int32_t)fv[kPodLInProg];
+    r.rpm = (int32_t)fv[kPodRpm];
+    r.flags = fv[kPodShutdown] ? (r.flags | MMP_POD_SHUTTING_DOWN) : (r.flags & ~MMP_POD_SHUTTING_DOWN);
+    r.version = fv[kPodVers];
+    start_time = fv[kPodStartTime];
+}
+
+// One InstanceRecord value walked by ONE lane (longer than the LDS tile of the wave path) into the cleared slots fv[]: a later
+// duplicate wins by program order.  Returns true when the value is malformed.
+__device__ __forceinline__ bool pod_record_serial(const char *b, const char *e, int64_t *fv)
+{
+    JCur c{b, e, false};
+    j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
+        const int s = pod_slot_of(h, klen, kp);
+        if (s < 0)
+            j_skip_value(c);
+        else
+            fv[s] = s == kPodShutdown ? (int64_t)j_bool(c) : j_int(c);
+    });
     return c.bad;
 }
 
@@ -264,45 +295,21 @@ __device__ __forceinline__ int32_t tab_find(const HashTab &t, uint64_t h, int32_
     return missing;
 }
 
-// at '{' of an id -> long map (instanceIds / failedIn): count the entries, and when out_pod != nullptr
-// write them in document order (a TreeMap serialises in key order, which is what the paths expect)
+// at an id -> long map (instanceIds / failedIn; Jackson writes a null map as `null`): count the entries, and when
+// out_pod != nullptr write them in document order (a TreeMap serialises in key order, which is what the paths expect)
 __device__ __forceinline__ int32_t j_id_map(JCur &c, const HashTab &ids, int32_t *out_pod, int64_t *out_time)
 {
     int32_t n = 0;
     j_ws(c);
-    if (c.e - c.p >= 4 && c.p[0] == 'n' && c.p[1] == 'u' && c.p[2] == 'l' && c.p[3] == 'l') {
-        c.p += 4;
-        return 0;
-    }
-    if (!j_eat(c, '{')) {
-        c.bad = true;
-        return 0;
-    }
-    bool first = true;
-    while (!c.bad) {
-        j_ws(c);
-        if (c.p < c.e && *c.p == '}') {
-            c.p++;
-            break;
-        }
-        if (!first && !j_eat(c, ',')) {
-            c.bad = true;
-            break;
-        }
-        first = false;
-        j_ws(c);
-        const uint64_t h = j_string_hash(c);
-        if (c.bad || !j_eat(c, ':')) {
-            c.bad = true;
-            break;
-        }
+    if (j_lit(c, "null", 4)) return 0;
+    j_members(c, false, [&](uint64_t h, int, const char *) {
         const int64_t t = j_int(c);
         if (out_pod) {
             out_pod[n] = tab_find(ids, h, -1);
             out_time[n] = t;
         }
         n++;
-    }
+    });
     return n;
 }
 
@@ -336,94 +343,70 @@ struct IngestModelsArgs {
     int32_t *win;            // per slot: the last event that is well-formed or deleted (-1 before the launch; atomicMax)
 };
 
-// What every path of ingest_models_kernel leaves for record i.  With the row indirection the event also stands for its row:
-// events apply in order and a malformed one changes nothing, so the row ends as its highest-numbered good event left it.
-__device__ __forceinline__ void j_publish_model(const IngestModelsArgs &A, int i, bool bad, mmp_model_row r, int64_t lul)
+// ---- ModelRecord: its slots and the name of each ---------------------------------------------------------------------------------
+//
+// The two maps take three slots each: the entry count, and on the tile the positions of the map's opener and closer (0 = no
+// map yet, -1 = null).
+enum ModelSlot { kModType, kModLu, kModLul, kModLoaded, kModFailed, kModLoadedOpen, kModLoadedClose, kModFailedOpen, kModFailedClose, kModSlots };
+// map m (0 instanceIds, 1 failedIn): its count in slot kModLoaded + m, its opener in slot j_map_open(m), its closer in the next
+__device__ __forceinline__ int j_map_open(int m) { return kModLoadedOpen + 2 * m; }
+static_assert(kModFailed == kModLoaded + 1 && kModLoadedClose == kModLoadedOpen + 1 && kModFailedOpen == kModLoadedOpen + 2 &&
+                  kModFailedClose == kModFailedOpen + 1, "the slots of the two maps are laid out alike");
+
+// the slot of a field name (kModType .. kModFailed), -1 for every other field
+template <class B>
+__device__ __forceinline__ int model_slot_of(uint64_t h, int klen, const B *kp)
 {
-    if (A.deleted && A.deleted[i]) {
-        bad = false;
-        r = mmp_model_row{};
-        lul = 0;
-    }
-    A.status[i] = bad ? 1 : 0;
-    A.rows[i] = r;
-    A.cnt[i] = r.n_loaded + r.n_failed;
-    A.last_unload[i] = bad ? 0 : lul;
-    if (A.slot && !bad) atomicMax(&A.win[A.slot[i]], i);
+    if (KEY_IS(h, klen, kp, "type")) return kModType;
+    if (KEY_IS(h, klen, kp, "lu")) return kModLu;
+    if (KEY_IS(h, klen, kp, "lul")) return kModLul;
+    if (KEY_IS(h, klen, kp, "instanceIds")) return kModLoaded;
+    if (KEY_IS(h, klen, kp, "failedIn")) return kModFailed;
+    return -1;
 }
 
-// One ModelRecord value walked by ONE lane.  PASS 0: type / counts / lu / lul, and in mapf[] the index of the field that set
-// each map's count (the last duplicate: the one that wins); PASS 1: the entries, of those two fields only — an earlier duplicate
-// is walked but not written, so the row holds exactly the winner's entries, as on the wave path.
+// One ModelRecord value walked by ONE lane into the slots fv[] / win[] (cleared, fv[kModType] = the default type).  PASS 0: type,
+// lu, lul, the maps' counts, and in win[] the index of the field that set each map's count (the last duplicate: the one that
+// wins); PASS 1: the entries, of those two fields only, parked from slot `park` on — an earlier duplicate is walked but not
+// written, so the row holds exactly the winner's entries, as on the wave path.
 template <int PASS>
-__device__ __forceinline__ bool model_record_serial(const IngestModelsArgs &A, const char *b, const char *e,
-                                                    mmp_model_row &r, int64_t &lul, int32_t (&mapf)[2])
+__device__ __forceinline__ bool model_record_serial(const IngestModelsArgs &A, const char *b, const char *e, int64_t *fv,
+                                                    int32_t *win, int64_t park)
 {
     JCur c{b, e, false};
-    lul = 0;
     int32_t f = -1;  // index of the field being read
-    if (!j_eat(c, '{')) c.bad = true;
-    bool first = true;
-    while (!c.bad) {
-        j_ws(c);
-        if (c.p < c.e && *c.p == '}') {
-            j_end_of_value(c);
-            break;
-        }
-        if (!first && !j_eat(c, ',')) {
-            c.bad = true;
-            break;
-        }
-        first = false;
-        j_ws(c);
-        const char *k0 = c.p;
-        const uint64_t h = j_string_hash(c);
-        const int klen = (int)(c.p - k0) - 2;
-        const char *kp = k0 + 1;
-        if (c.bad || !j_eat(c, ':')) {
-            c.bad = true;
-            break;
-        }
+    j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
         f++;
-        if (KEY_IS(h, klen, kp, "instanceIds")) {
-            const bool wr = PASS && f == mapf[0];
-            const int32_t k = j_id_map(c, A.ids, wr ? A.ent_pod + r.ent_off : nullptr, wr ? A.ent_time + r.ent_off : nullptr);
+        const int s = model_slot_of(h, klen, kp);
+        if (s >= kModLoaded) {
+            const bool wr = PASS && f == win[s];
+            const int64_t at = park + (s == kModFailed ? fv[kModLoaded] : 0);
+            const int32_t k = j_id_map(c, A.ids, wr ? A.ent_pod + at : nullptr, wr ? A.ent_time + at : nullptr);
             if (PASS == 0) {
-                r.n_loaded = k;
-                mapf[0] = f;
+                fv[s] = k;
+                win[s] = f;
             }
-        } else if (KEY_IS(h, klen, kp, "failedIn")) {
-            const bool wr = PASS && f == mapf[1];
-            const int32_t k = j_id_map(c, A.ids, wr ? A.ent_pod + r.ent_off + r.n_loaded : nullptr,
-                                       wr ? A.ent_time + r.ent_off + r.n_loaded : nullptr);
-            if (PASS == 0) {
-                r.n_failed = k;
-                mapf[1] = f;
-            }
-        } else if (PASS == 0 && KEY_IS(h, klen, kp, "type")) {
+        } else if (PASS == 0 && s == kModType) {
             j_ws(c);
             if (c.p < c.e && *c.p == '"')
-                r.type = tab_find(A.types, j_string_hash(c), A.unknown_type);
+                fv[s] = tab_find(A.types, j_string_hash(c), A.unknown_type);
             else {  // null -> DEFAULT_TYPE (ModelRecord.java:121), also behind an earlier duplicate that named a type
                 // (exactly `null`, as on the wave path; anything else that is not a string is skipped)
-                if (c.e - c.p >= 4 && c.p[0] == 'n' && c.p[1] == 'u' && c.p[2] == 'l' && c.p[3] == 'l' &&
-                    (c.e - c.p == 4 || c.p[4] == ',' || c.p[4] == '}' || c.p[4] == ' ' || c.p[4] == '\n' || c.p[4] == '\t' || c.p[4] == '\r'))
-                    r.type = A.default_type;
+                JCur v = c;
+                if (j_lit(v, "null", 4) && (v.p == v.e || *v.p == ',' || *v.p == '}' || j_is_ws(*v.p))) fv[s] = A.default_type;
                 j_skip_value(c);
             }
-        } else if (PASS == 0 && KEY_IS(h, klen, kp, "lu"))
-            r.last_used = j_int(c);
-        else if (PASS == 0 && KEY_IS(h, klen, kp, "lul"))
-            lul = j_int(c);
+        } else if (PASS == 0 && s >= 0)
+            fv[s] = j_int(c);  // lu, lul
         else
             j_skip_value(c);
-    }
+    });
     return c.bad;
 }
 
 // ---- the wave path ----------------------------------------------------------------------------------------
 //
-// A wavefront takes kJGroup consecutive records.  Their bytes are contiguous in the value buffer, so the
+// A wavefront takes up to kJGroup consecutive records.  Their bytes are contiguous in the value buffer, so the
 // whole group is staged into an LDS tile with coalesced dword loads.  Then, per record, j_scan classifies
 // the bytes 64 at a time, one byte per lane, with ballots (the masks are wave-uniform 64-bit scalars):
 //   unescaped quotes   = '"' & ~escaped, `escaped` from the odd-length-backslash-run carry arithmetic
@@ -440,7 +423,8 @@ constexpr int kJGroup = 8;           // records per wavefront
 constexpr int kJTileBytes = 2048;    // LDS tile of one wavefront; a record longer than this: serial path
 constexpr int kJTileChunks = kJTileBytes / 64 + kJGroup;
 constexpr int kJBlock = kJWaves * 64;
-constexpr int kJSlots = 10;          // known fields per record (InstanceRecord has 10, ModelRecord 5 + 6 map words)
+constexpr int kJSlots = 10;          // slots per record
+static_assert(kPodSlots <= kJSlots && kModSlots <= kJSlots, "JWaveLds::val / win hold every slot of either record type");
 
 struct JRecInfo {  // one record of the tile
     int32_t base;  // first byte inside the tile
@@ -490,8 +474,6 @@ __device__ __forceinline__ JView j_view(const JWaveLds &S, int r)
     V.n1 = I.n1;
     return V;
 }
-
-__device__ __forceinline__ bool j_is_ws(uint32_t c) { return c == ' ' || c == '\n' || c == '\t' || c == '\r'; }
 
 __device__ __forceinline__ uint64_t j_prefix_xor(uint64_t x)
 {
@@ -638,8 +620,7 @@ __device__ __forceinline__ bool j_key(const JView &R, int p, const uint64_t *com
     if (sp < 0 || (first ? sp != open_pos : !j_bit(commas, sp))) return false;
     klen = q - ks - 1;
     kp = R.by + ks + 1;
-    h = 0xcbf29ce484222325ull;
-    for (int i = ks + 1; i < q; i++) h = (h ^ (uint64_t)R.by[i]) * 0x100000001b3ull;
+    h = fnv1a(kp, klen);
     return true;
 }
 
@@ -670,10 +651,7 @@ __device__ __forceinline__ bool j_int_at(const JView &R, int &p, int64_t &out)
 
 __device__ __forceinline__ bool j_lit_at(const JView &R, int p, const char *lit, int n)
 {
-    if (p + n > R.L) return false;
-    for (int i = 0; i < n; i++)
-        if (R.by[p + i] != (uint8_t)lit[i]) return false;
-    return true;
+    return p + n <= R.L && bytes_equal(R.by + p, lit, n);
 }
 
 // The byte offsets of the wavefront's records, fetched with one load (S.off[k] = off[i0 + k]).
@@ -693,6 +671,16 @@ __device__ __forceinline__ int j_group_len(const JWaveLds &S, int k, int k1)
     return c;
 }
 
+// the slots of records [0, cnt) of the tile: no value, no field that set one
+__device__ __forceinline__ void j_clear_slots(JWaveLds &S, int cnt)
+{
+    for (int q = lane_id(); q < cnt * kJSlots; q += 64) {
+        (&S.val[0][0])[q] = 0;
+        (&S.win[0][0])[q] = -1;
+    }
+    wave_sync();
+}
+
 // Stage records [k, k+cnt) of the wavefront into the tile and scan them; fills S.rec[0..cnt).
 __device__ __forceinline__ void j_stage_and_scan(const char *buf, int k, int cnt, JWaveLds &S)
 {
@@ -710,11 +698,7 @@ __device__ __forceinline__ void j_stage_and_scan(const char *buf, int k, int cnt
         if (lane == 0) S.rec[r] = R;
         mb += R.nch;
     }
-    for (int q = lane; q < cnt * kJSlots; q += 64) {
-        (&S.val[0][0])[q] = 0;
-        (&S.win[0][0])[q] = -1;
-    }
-    wave_sync();
+    j_clear_slots(S, cnt);
 }
 
 // pf[0..cnt] = exclusive prefix sums of the per-record item counts held by lanes 0..cnt-1; returns the total
@@ -739,16 +723,66 @@ __device__ __forceinline__ int j_item_record(const JWaveLds &S, int cnt, int t, 
     return r;
 }
 
-// a known field's value: the field with the highest index wins (Jackson keeps the last duplicate)
-__device__ __forceinline__ void j_claim(JWaveLds &S, int r, int fid, int j) { atomicMax(&S.win[r][fid], j); }
-
-// One InstanceRecord value per lane-group, kJGroup records per WAVEFRONT.  rows[] arrive with id_order /
-// replica_set / flags(LIVE) set by the host; every numeric field is (re)written from the JSON.
-__global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__restrict__ buf, const int64_t *__restrict__ off,
-                                                              int32_t n, int32_t grp, mmp_pod_row *__restrict__ rows,
-                                                              int64_t *__restrict__ start_time, int32_t *__restrict__ status)
+// the group's fields as items: records the scan rejected have none
+__device__ __forceinline__ int j_prefix_fields(JWaveLds &S, int cnt)
 {
-    __shared__ JWaveLds lds[kJWaves];
+    const int lane = lane_id();
+    return j_prefix_items(S, cnt, lane < cnt && !S.rec[lane].bad ? S.rec[lane].n1 : 0);
+}
+
+// Member k of the container opened at byte `open` of the record, `colons` / `commas` being the masks of its level.
+struct JMember {
+    uint64_t h;  // the key: FNV-1a, length, first byte
+    int klen;
+    const uint8_t *kp;
+    int p, v;    // the ':' and the first byte of the value
+};
+
+__device__ __forceinline__ bool j_member_at(const JView &R, const uint64_t *colons, const uint64_t *commas, int open, int k, JMember &M)
+{
+    M.p = j_nth_after(colons, R.nch, open, k);
+    if (M.p < 0 || !j_key(R, M.p, commas, open, k == 0, M.h, M.klen, M.kp)) return false;
+    M.v = M.p + 1;
+    while (M.v < R.L && j_is_ws(R.by[M.v])) M.v++;
+    return true;
+}
+
+// The head of a field round: item t of the group's fields is field j of record r (the j-th ':' directly inside the record object).
+struct JField {
+    int r, j;
+    bool last;  // the record's last field: its value ends at the closing brace, not at a ','
+    JMember m;
+};
+
+__device__ __forceinline__ bool j_field_at(const JWaveLds &S, int cnt, int t, JView &R, JField &F)
+{
+    F.r = j_item_record(S, cnt, t, F.j);
+    R = j_view(S, F.r);
+    F.last = F.j == R.n1 - 1;
+    return j_member_at(R, R.c1, R.m1, R.f, F.j, F.m);
+}
+
+// The claims of a field round, by every lane of the wavefront: a malformed field rejects its record; the value of a known field
+// (fid >= 0) claims the slot, where the field with the highest index wins (Jackson keeps the last duplicate).  True for a lane
+// that claimed: once this returns S.win[r][fid] == j tells it whether it won.  The caller stores what the winners hold and ends
+// the round with a wave_sync.
+__device__ __forceinline__ bool j_claim(JWaveLds &S, const JField &F, int fid, bool lbad)
+{
+    if (lbad) S.rec[F.r].bad = 1;
+    const bool claims = fid >= 0 && !lbad;
+    if (claims) atomicMax(&S.win[F.r][fid], F.j);
+    wave_sync();
+    return claims;
+}
+
+// The frame of both kernels, by every wavefront: grp consecutive records, taken in groups that fit the LDS tile together.
+// tile(S, k, cnt) parses the staged and scanned records [k, k + cnt) of the wavefront, every lane at work; a record longer than
+// the tile is a group of one that lane 0 walks: walk(S, i, b, e) -> malformed.  Both leave the values in S.val and the verdict
+// in S.rec[].bad, and publish(i, bad, fv) writes record i from its slots.
+template <class Walk, class Tile, class Publish>
+__device__ __forceinline__ void j_ingest_wave(JWaveLds *lds, const char *buf, const int64_t *off, int32_t n, int32_t grp, Walk &&walk,
+                                              Tile &&tile, Publish &&publish)
+{
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = lane_id();
     JWaveLds &S = lds[wave];
@@ -758,53 +792,44 @@ __global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__rest
     j_load_offsets(off, i0, i1, S);
     int i = i0;
     while (i < i1) {
-        const int cnt = j_group_len(S, i - i0, i1 - i0);
-        if (cnt == 0) {  // does not fit the LDS tile: one lane walks it
-            if (lane == 0) {
-                mmp_pod_row r = rows[i];
-                int64_t st;
-                const bool bad = pod_record_serial(buf + off[i], buf + off[i + 1], r, st);
-                status[i] = bad ? 1 : 0;
-                if (!bad) {
-                    rows[i] = r;
-                    start_time[i] = st;
-                }
-            }
-            i++;
-            continue;
+        const int k = i - i0;
+        int cnt = j_group_len(S, k, i1 - i0);
+        if (cnt == 0) {
+            j_clear_slots(S, cnt = 1);
+            if (lane == 0) S.rec[0].bad = walk(S, i, buf + S.off[k], buf + S.off[k + 1]) ? 1 : 0;
+            wave_sync();
+        } else {
+            j_stage_and_scan(buf, k, cnt, S);
+            tile(S, k, cnt);
         }
-        j_stage_and_scan(buf, i - i0, cnt, S);
-        const int total = j_prefix_items(S, cnt, lane < cnt ? (S.rec[lane].bad ? 0 : S.rec[lane].n1) : 0);
-        // every field of every record of the group on its own lane
-        for (int base = 0; base < total; base += 64) {
-            const int t = base + lane;
-            int fid = -1, r = 0, j = 0;
-            int64_t val = 0;
-            bool lbad = false;
-            if (t < total) {
-                r = j_item_record(S, cnt, t, j);
-                const JView R = j_view(S, r);
-                const int p = j_nth_after(R.c1, R.nch, -1, j);
-                uint64_t h;
-                int klen;
-                const uint8_t *kp = nullptr;
-                if (!j_key(R, p, R.m1, R.f, j == 0, h, klen, kp))
-                    lbad = true;
-                else {
-                    if (KEY_IS(h, klen, kp, "lruTime")) fid = 0;
-                    else if (KEY_IS(h, klen, kp, "count")) fid = 1;
-                    else if (KEY_IS(h, klen, kp, "cap")) fid = 2;
-                    else if (KEY_IS(h, klen, kp, "used")) fid = 3;
-                    else if (KEY_IS(h, klen, kp, "lThreads")) fid = 4;
-                    else if (KEY_IS(h, klen, kp, "lInProg")) fid = 5;
-                    else if (KEY_IS(h, klen, kp, "rpm")) fid = 6;
-                    else if (KEY_IS(h, klen, kp, "shutdown")) fid = 7;
-                    else if (KEY_IS(h, klen, kp, "startTime")) fid = 8;
-                    else if (KEY_IS(h, klen, kp, "vers")) fid = 9;
-                    if (fid >= 0) {
-                        int v = p + 1;
-                        while (v < R.L && j_is_ws(R.by[v])) v++;
-                        if (fid == 7) {
+        if (lane < cnt) publish(i + lane, S.rec[lane].bad != 0, S.val[lane]);
+        wave_sync();
+        i += cnt;
+    }
+}
+
+// InstanceRecord values, grp per WAVEFRONT.
+__global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__restrict__ buf, const int64_t *__restrict__ off,
+                                                              int32_t n, int32_t grp, mmp_pod_row *__restrict__ rows,
+                                                              int64_t *__restrict__ start_time, int32_t *__restrict__ status)
+{
+    __shared__ JWaveLds lds[kJWaves];
+    const int lane = lane_id();
+    j_ingest_wave(
+        lds, buf, off, n, grp, [&](JWaveLds &S, int, const char *b, const char *e) { return pod_record_serial(b, e, S.val[0]); },
+        [&](JWaveLds &S, int, int cnt) {  // every field of every record of the group on its own lane
+            const int total = j_prefix_fields(S, cnt);
+            for (int base = 0; base < total; base += 64) {
+                JField F{};
+                int fid = -1;
+                int64_t val = 0;
+                bool lbad = false;
+                if (base + lane < total) {
+                    JView R;
+                    lbad = !j_field_at(S, cnt, base + lane, R, F);
+                    if (!lbad && (fid = pod_slot_of(F.m.h, F.m.klen, F.m.kp)) >= 0) {
+                        int v = F.m.v;
+                        if (fid == kPodShutdown) {
                             if (j_lit_at(R, v, "true", 4)) {
                                 val = 1;
                                 v += 4;
@@ -814,233 +839,182 @@ __global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__rest
                                 lbad = true;
                         } else if (!j_int_at(R, v, val))
                             lbad = true;
-                        if (!lbad && !j_term(R, v, R.m1, R.g, j == R.n1 - 1)) lbad = true;
+                        if (!lbad && !j_term(R, v, R.m1, R.g, F.last)) lbad = true;
                     }
                 }
-                if (lbad) S.rec[r].bad = 1;
-                if (fid >= 0 && !lbad) j_claim(S, r, fid, j);
+                if (j_claim(S, F, fid, lbad) && S.win[F.r][fid] == F.j) S.val[F.r][fid] = val;
+                wave_sync();
             }
-            wave_sync();
-            if (fid >= 0 && !lbad && S.win[r][fid] == j) S.val[r][fid] = val;
-            wave_sync();
-        }
-        if (lane < cnt) {
-            const bool bad = S.rec[lane].bad != 0;
-            status[i + lane] = bad ? 1 : 0;
+        },
+        [&](int i, bool bad, const int64_t *fv) {
+            status[i] = bad ? 1 : 0;
             if (!bad) {
-                const int64_t *fv = S.val[lane];
-                mmp_pod_row r = rows[i + lane];
-                r.lru_time = fv[0];
-                r.count = (int32_t)fv[1];
-                r.capacity = fv[2];
-                r.used = fv[3];
-                r.loading_threads = (int32_t)fv[4];
-                r.loading_in_progress = (int32_t)fv[5];
-                r.rpm = (int32_t)fv[6];
-                r.flags = fv[7] ? (r.flags | MMP_POD_SHUTTING_DOWN) : (r.flags & ~MMP_POD_SHUTTING_DOWN);
-                r.version = fv[9];
-                rows[i + lane] = r;
-                start_time[i + lane] = fv[8];
+                mmp_pod_row r = rows[i];
+                pod_row_from_slots(r, fv, start_time[i]);
+                rows[i] = r;
             }
-        }
-        wave_sync();
-        i += cnt;
-    }
+        });
 }
 
 // ModelRecord values, A.grp per WAVEFRONT, one pass: type / n_loaded / n_failed / last_used, the status
 // (the whole value is validated, entries included) and the entries themselves, parked at slot
 // off[i] / kJEntryBytes + e of ent_pod / ent_time until compact_entries_kernel moves them to their CSR position.
-// Slots: 0 type, 1 lu, 2 lul, 3 instanceIds, 4 failedIn (value = entry count), 5..8 = the two maps'
-// opener / closer positions.
 __global__ __launch_bounds__(kJBlock) void ingest_models_kernel(IngestModelsArgs A)
 {
     __shared__ JWaveLds lds[kJWaves];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = lane_id();
-    JWaveLds &S = lds[wave];
-    const int i0 = (blockIdx.x * kJWaves + wave) * A.grp;
-    if (i0 >= A.n) return;
-    const int i1 = i0 + A.grp < A.n ? i0 + A.grp : A.n;
-    j_load_offsets(A.off, i0, i1, S);
-    int i = i0;
-    while (i < i1) {
-        const int cnt = j_group_len(S, i - i0, i1 - i0);
-        if (cnt == 0) {  // longer than the tile: one lane walks it, a second time to write the entries
-            if (lane == 0) {
-                mmp_model_row r;
-                r.type = A.default_type;
-                r.n_loaded = r.n_failed = 0;
-                r.last_used = 0;
-                r.ent_off = 0;
-                int64_t lul = 0, lul2;
-                int32_t mapf[2] = {-1, -1};
-                const char *b = A.buf + S.off[i - i0], *e = A.buf + S.off[i - i0 + 1];
-                bool bad = A.deleted && A.deleted[i];  // (a deleted event's value is not walked)
-                if (!bad) bad = model_record_serial<0>(A, b, e, r, lul, mapf);
-                if (!bad) {
-                    mmp_model_row w = r;
-                    w.ent_off = (int32_t)(S.off[i - i0] / kJEntryBytes);
-                    (void)model_record_serial<1>(A, b, e, w, lul2, mapf);
-                } else {  // the row a rejected record gets on the wave path
-                    r.type = A.default_type;
-                    r.n_loaded = r.n_failed = 0;
-                    r.last_used = 0;
-                }
-                j_publish_model(A, i, bad, r, lul);
-            }
-            i++;
-            continue;
-        }
-        j_stage_and_scan(A.buf, i - i0, cnt, S);
-        if (lane < cnt) S.val[lane][0] = A.default_type;
-        wave_sync();
-        int total = j_prefix_items(S, cnt, lane < cnt ? (S.rec[lane].bad ? 0 : S.rec[lane].n1) : 0);
-        for (int base = 0; base < total; base += 64) {
-            const int t = base + lane;
-            int fid = -1, r = 0, j = 0;
-            int64_t val = 0;
-            int vopen = -1, vclose = -1;
-            bool lbad = false;
-            if (t < total) {
-                r = j_item_record(S, cnt, t, j);
-                const JView R = j_view(S, r);
-                const int p = j_nth_after(R.c1, R.nch, -1, j);
-                uint64_t h;
-                int klen;
-                const uint8_t *kp = nullptr;
-                if (!j_key(R, p, R.m1, R.f, j == 0, h, klen, kp))
-                    lbad = true;
-                else {
-                    if (KEY_IS(h, klen, kp, "type")) fid = 0;
-                    else if (KEY_IS(h, klen, kp, "lu")) fid = 1;
-                    else if (KEY_IS(h, klen, kp, "lul")) fid = 2;
-                    else if (KEY_IS(h, klen, kp, "instanceIds")) fid = 3;
-                    else if (KEY_IS(h, klen, kp, "failedIn")) fid = 4;
-                    int v = p + 1;
-                    while (v < R.L && j_is_ws(R.by[v])) v++;
-                    const bool last = j == R.n1 - 1;
-                    if (fid == 0) {
-                        if (v < R.L && j_bit(R.rq, v)) {
-                            const int ve = j_nth_after(R.rq, R.nch, v, 0);  // closing quote (strings are balanced)
-                            uint64_t th = 0xcbf29ce484222325ull;
-                            for (int k = v + 1; k < ve; k++) th = (th ^ (uint64_t)R.by[k]) * 0x100000001b3ull;
-                            val = tab_find(A.types, th, A.unknown_type);
-                            if (!j_term(R, ve + 1, R.m1, R.g, last)) lbad = true;
-                        } else if (j_lit_at(R, v, "null", 4) && j_term(R, v + 4, R.m1, R.g, last)) {
-                            val = A.default_type;  // null -> DEFAULT_TYPE (ModelRecord.java:121); claimed, so that it also
-                                                   // wins over an earlier duplicate that named a type
-                        } else {
-                            fid = -1;  // not a string: the field is skipped
-                        }
-                    } else if (fid == 1 || fid == 2) {
-                        if (!j_int_at(R, v, val) || !j_term(R, v, R.m1, R.g, last)) lbad = true;
-                    } else if (fid >= 3) {
-                        if (j_lit_at(R, v, "null", 4)) {
-                            if (!j_term(R, v + 4, R.m1, R.g, last)) lbad = true;
-                        } else if (v < R.L && R.by[v] == '{') {
-                            const int ce = j_nth_after(R.e2, R.nch, v, 0);
-                            if (ce < 0 || R.by[ce] != '}')
-                                lbad = true;
-                            else {
-                                vopen = v;
-                                vclose = ce;
-                                val = j_count(R.c2, v, ce);
-                                if (j_count(R.m2, v, ce) != (val > 0 ? val - 1 : 0)) lbad = true;
-                                if (val * kJEntryBytes > ce - v) lbad = true;  // more entries than bytes: see kJEntryBytes
-                                if (val == 0) {
-                                    int q = v + 1;
-                                    while (q < ce && j_is_ws(R.by[q])) q++;
-                                    if (q != ce) lbad = true;
-                                }
-                                if (!j_term(R, ce + 1, R.m1, R.g, last)) lbad = true;
-                            }
-                        } else
-                            lbad = true;
-                    }
-                }
-                if (lbad) S.rec[r].bad = 1;
-                if (fid >= 0 && !lbad) j_claim(S, r, fid, j);
-            }
+    j_ingest_wave(
+        lds, A.buf, A.off, A.n, A.grp,
+        [&](JWaveLds &S, int i, const char *b, const char *e) {  // a second walk writes the entries
+            if (A.deleted && A.deleted[i]) return true;           // (a deleted event's value is not walked)
+            S.val[0][kModType] = A.default_type;
+            const int64_t park = (b - A.buf) / kJEntryBytes;
+            if (model_record_serial<0>(A, b, e, S.val[0], S.win[0], park)) return true;
+            (void)model_record_serial<1>(A, b, e, S.val[0], S.win[0], park);
+            return false;
+        },
+        [&](JWaveLds &S, int k0, int cnt) {
+            if (lane < cnt) S.val[lane][kModType] = A.default_type;
             wave_sync();
-            // A map that loses to a later duplicate is read by no entry lane, so it is walked here (the serial parser's map
-            // grammar, nothing written): a malformed entry rejects the record wherever it stands.  S.win is final only for
-            // the fields of the rounds run so far, so there are two kinds of loser: a map of THIS round that lost its claim
-            // walks itself; a map that won an EARLIER round is still in S.val (its opener is > 0; 0 = none yet, -1 = null)
-            // and is walked by the lane that now replaces it.
-            int lost_open = -1, lost_close = -1;
-            if (fid >= 0 && !lbad) {
-                if (S.win[r][fid] == j) {
-                    S.val[r][fid] = val;
-                    if (fid >= 3) {
-                        if (S.val[r][5 + 2 * (fid - 3)] > 0) {
-                            lost_open = (int)S.val[r][5 + 2 * (fid - 3)];
-                            lost_close = (int)S.val[r][6 + 2 * (fid - 3)];
-                        }
-                        S.val[r][5 + 2 * (fid - 3)] = vopen;
-                        S.val[r][6 + 2 * (fid - 3)] = vclose;
-                    }
-                } else if (fid >= 3) {
-                    lost_open = vopen;
-                    lost_close = vclose;
-                }
-            }
-            if (lost_open >= 0) {
-                const JView R = j_view(S, r);
-                JCur c{reinterpret_cast<const char *>(R.by) + lost_open, reinterpret_cast<const char *>(R.by) + lost_close + 1, false};
-                (void)j_id_map(c, A.ids, nullptr, nullptr);
-                if (c.bad) S.rec[r].bad = 1;
-            }
-            wave_sync();
-        }
-        // the entries of both maps of every record, one lane each: instanceIds first, then failedIn (CSR layout)
-        total = j_prefix_items(S, cnt, lane < cnt && !S.rec[lane].bad ? (int)(S.val[lane][3] + S.val[lane][4]) : 0);
-        for (int base = 0; base < total; base += 64) {
-            const int t = base + lane;
-            if (t < total) {
-                int e;
-                const int r = j_item_record(S, cnt, t, e);
-                const JView R = j_view(S, r);
-                const int nl = (int)S.val[r][3], nfl = (int)S.val[r][4];
-                const int which = e < nl ? 0 : 1;
-                const int k = which ? e - nl : e, kcnt = which ? nfl : nl;
-                const int open = (int)S.val[r][5 + 2 * which], close = (int)S.val[r][6 + 2 * which];
-                const int p = j_nth_after(R.c2, R.nch, open, k);
-                uint64_t h = 0;
-                int klen;
-                int64_t tm = 0;
+            int total = j_prefix_fields(S, cnt);
+            for (int base = 0; base < total; base += 64) {
+                JField F{};
+                int fid = -1;
+                int64_t val = 0;
+                int vopen = -1, vclose = -1;
                 bool lbad = false;
-                const uint8_t *kp = nullptr;
-                if (p < 0 || p > close || !j_key(R, p, R.m2, open, k == 0, h, klen, kp))
-                    lbad = true;
-                else {
-                    int v = p + 1;
-                    while (v < R.L && j_is_ws(R.by[v])) v++;
-                    if (!j_int_at(R, v, tm) || !j_term(R, v, R.m2, close, k == kcnt - 1)) lbad = true;
+                if (base + lane < total) {
+                    JView R;
+                    if (!j_field_at(S, cnt, base + lane, R, F))
+                        lbad = true;
+                    else {
+                        fid = model_slot_of(F.m.h, F.m.klen, F.m.kp);
+                        int v = F.m.v;
+                        const bool last = F.last;
+                        if (fid == kModType) {
+                            if (v < R.L && j_bit(R.rq, v)) {
+                                const int ve = j_nth_after(R.rq, R.nch, v, 0);  // closing quote (strings are balanced)
+                                val = tab_find(A.types, fnv1a(R.by + v + 1, ve - v - 1), A.unknown_type);
+                                if (!j_term(R, ve + 1, R.m1, R.g, last)) lbad = true;
+                            } else if (j_lit_at(R, v, "null", 4) && j_term(R, v + 4, R.m1, R.g, last)) {
+                                val = A.default_type;  // null -> DEFAULT_TYPE (ModelRecord.java:121); claimed, so that it also
+                                                       // wins over an earlier duplicate that named a type
+                            } else {
+                                fid = -1;  // not a string: the field is skipped
+                            }
+                        } else if (fid == kModLu || fid == kModLul) {
+                            if (!j_int_at(R, v, val) || !j_term(R, v, R.m1, R.g, last)) lbad = true;
+                        } else if (fid >= kModLoaded) {
+                            if (j_lit_at(R, v, "null", 4)) {
+                                if (!j_term(R, v + 4, R.m1, R.g, last)) lbad = true;
+                            } else if (v < R.L && R.by[v] == '{') {
+                                const int ce = j_nth_after(R.e2, R.nch, v, 0);
+                                if (ce < 0 || R.by[ce] != '}')
+                                    lbad = true;
+                                else {
+                                    vopen = v;
+                                    vclose = ce;
+                                    val = j_count(R.c2, v, ce);
+                                    if (j_count(R.m2, v, ce) != (val > 0 ? val - 1 : 0)) lbad = true;
+                                    if (val * kJEntryBytes > ce - v) lbad = true;  // more entries than bytes: see kJEntryBytes
+                                    if (val == 0) {
+                                        int q = v + 1;
+                                        while (q < ce && j_is_ws(R.by[q])) q++;
+                                        if (q != ce) lbad = true;
+                                    }
+                                    if (!j_term(R, ce + 1, R.m1, R.g, last)) lbad = true;
+                                }
+                            } else
+                                lbad = true;
+                        }
+                    }
                 }
-                if (lbad)
-                    S.rec[r].bad = 1;
-                else {
-                    const int64_t slot = S.off[i - i0 + r] / kJEntryBytes + e;
-                    A.ent_pod[slot] = tab_find(A.ids, h, -1);
-                    A.ent_time[slot] = tm;
+                const int r = F.r;
+                const bool claims = j_claim(S, F, fid, lbad);
+                // A map that loses to a later duplicate is read by no entry lane, so it is walked here (the serial walk's map
+                // grammar, nothing written): a malformed entry rejects the record wherever it stands.  S.win is final only for
+                // the fields of the rounds run so far, so there are two kinds of loser: a map of THIS round that lost its claim
+                // walks itself; a map that won an EARLIER round is still in S.val (its opener is > 0; 0 = none yet, -1 = null)
+                // and is walked by the lane that now replaces it.
+                int lost_open = -1, lost_close = -1;
+                if (claims) {
+                    if (S.win[r][fid] == F.j) {
+                        S.val[r][fid] = val;
+                        if (fid >= kModLoaded) {
+                            int64_t *span = &S.val[r][j_map_open(fid - kModLoaded)];  // opener, closer
+                            if (span[0] > 0) {
+                                lost_open = (int)span[0];
+                                lost_close = (int)span[1];
+                            }
+                            span[0] = vopen;
+                            span[1] = vclose;
+                        }
+                    } else if (fid >= kModLoaded) {
+                        lost_open = vopen;
+                        lost_close = vclose;
+                    }
+                }
+                if (lost_open >= 0) {
+                    const JView R = j_view(S, r);
+                    JCur c{reinterpret_cast<const char *>(R.by) + lost_open, reinterpret_cast<const char *>(R.by) + lost_close + 1, false};
+                    (void)j_id_map(c, A.ids, nullptr, nullptr);
+                    if (c.bad) S.rec[r].bad = 1;
+                }
+                wave_sync();
+            }
+            // the entries of both maps of every record, one lane each: instanceIds first, then failedIn (CSR layout)
+            total = j_prefix_items(S, cnt, lane < cnt && !S.rec[lane].bad ? (int)(S.val[lane][kModLoaded] + S.val[lane][kModFailed]) : 0);
+            for (int base = 0; base < total; base += 64) {
+                const int t = base + lane;
+                if (t < total) {
+                    int e;
+                    const int r = j_item_record(S, cnt, t, e);
+                    const JView R = j_view(S, r);
+                    const int64_t *fv = S.val[r];
+                    const int nl = (int)fv[kModLoaded];
+                    const int m = e < nl ? 0 : 1;  // which map
+                    const int k = m ? e - nl : e, kcnt = (int)fv[kModLoaded + m];
+                    const int open = (int)fv[j_map_open(m)], close = (int)fv[j_map_open(m) + 1];
+                    JMember M;
+                    int64_t tm = 0;
+                    bool ok = j_member_at(R, R.c2, R.m2, open, k, M) && M.p <= close;
+                    if (ok) {
+                        int v = M.v;
+                        ok = j_int_at(R, v, tm) && j_term(R, v, R.m2, close, k == kcnt - 1);
+                    }
+                    if (!ok)
+                        S.rec[r].bad = 1;
+                    else {
+                        const int64_t slot = S.off[k0 + r] / kJEntryBytes + e;
+                        A.ent_pod[slot] = tab_find(A.ids, M.h, -1);
+                        A.ent_time[slot] = tm;
+                    }
                 }
             }
-        }
-        wave_sync();
-        if (lane < cnt) {
-            const bool bad = S.rec[lane].bad != 0;
-            mmp_model_row r;
-            r.type = bad ? A.default_type : (int32_t)S.val[lane][0];
-            r.ent_off = 0;
-            r.n_loaded = bad ? 0 : (int32_t)S.val[lane][3];
-            r.n_failed = bad ? 0 : (int32_t)S.val[lane][4];
-            r.last_used = bad ? 0 : S.val[lane][1];
-            j_publish_model(A, i + lane, bad, r, S.val[lane][2]);
-        }
-        wave_sync();
-        i += cnt;
-    }
+            wave_sync();
+        },
+        // What every route leaves for record i.  With the row indirection the event also stands for its row: events apply in
+        // order and a malformed one changes nothing, so the row ends as its highest-numbered good event left it.
+        [&](int i, bool bad, const int64_t *fv) {
+            mmp_model_row r{};
+            int64_t lul = 0;
+            if (A.deleted && A.deleted[i])
+                bad = false;  // ENTRY_DELETED: whatever the value, the empty row, and it counts as well-formed
+            else if (bad)
+                r.type = A.default_type;
+            else {
+                r.type = (int32_t)fv[kModType];
+                r.n_loaded = (int32_t)fv[kModLoaded];
+                r.n_failed = (int32_t)fv[kModFailed];
+                r.last_used = fv[kModLu];
+                lul = fv[kModLul];
+            }
+            A.status[i] = bad ? 1 : 0;
+            A.rows[i] = r;
+            A.cnt[i] = r.n_loaded + r.n_failed;
+            A.last_unload[i] = lul;
+            if (A.slot && !bad) atomicMax(&A.win[A.slot[i]], i);
+        });
 }
 
 // offs = exclusive scan of cnt (rocPRIM): move every record's entries from their parking slots to
@@ -1065,7 +1039,7 @@ __global__ void compact_entries_kernel(const int64_t *__restrict__ off, int32_t 
 // ---- mmp_models_upsert_json: from the parsed events to the rows registry_rewrite takes -----------------------------------------
 //
 // Slot j is the j-th distinct registry row the call names (slot_model[j]); win[j] is the event that decides it (see
-// j_publish_model).  Everything here is sized by the call's events and distinct rows, never by the registry.
+// the publish of ingest_models_kernel).  Everything here is sized by the call's events and distinct rows, never by the registry.
 
 // s_cnt[j] = entries slot j appends to the arena (scanned into s_offs); s_cnt[k] = 0 so that the scan's last element is the total
 __global__ void upsert_json_counts_kernel(const int32_t *__restrict__ win, const int32_t *__restrict__ ev_cnt, int32_t k,

@@ -2482,6 +2482,55 @@ int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n
     mask_out = cap - 1;
     return MMP_OK;
 }
+
+// The values of a wire-format call onto the device (the device is set, batch_mu held): off[0 .. n] must not decrease; j_buf gets
+// the bytes [off[0], off[n]) — none needs no buf —, j_off the offsets rebased to off[0].  Both uploads are enqueued on c->stream;
+// `rel` is what j_off is uploaded from and stays with the caller until it has synchronised.
+int stage_values(mmp_ctx *c, const char *fn, const char *buf, const int64_t *off, int32_t n, std::vector<int64_t> &rel, int64_t &bytes)
+{
+    rel.assign((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; i++) {
+        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: offsets not monotone at %d", fn, i);
+        rel[i + 1] = off[i + 1] - off[0];
+    }
+    bytes = rel[n];
+    if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
+    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    return MMP_OK;
+}
+
+// What ingest_models_kernel is given by either caller, for n staged values of `bytes` bytes: the tables, the per-record status /
+// lul / count words, and the parking arrays: ent_cap slots (ingest_kernels.hpp, the parking rule: n entries take >= 5n + 1 bytes
+// of JSON).  The rows and the event members are the caller's to set.
+int ingest_models_args(mmp_ctx *c, int32_t n, int64_t bytes, IngestModelsArgs &A, size_t &ent_cap)
+{
+    ent_cap = (size_t)(bytes / kJEntryBytes + 2);
+    HIP_TRY(c, c->j_aux.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+    HIP_TRY(c, c->j_cnt.ensure((size_t)(n + 1) * 4));
+    HIP_TRY(c, c->j_tmp_pod.ensure(ent_cap * 4));
+    HIP_TRY(c, c->j_tmp_time.ensure(ent_cap * 8));
+    A = IngestModelsArgs{};
+    A.buf = c->j_buf.as<char>();
+    A.off = c->j_off.as<int64_t>();
+    A.n = n;
+    A.ids = HashTab{c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), c->idtab_mask};
+    if (c->have_types) {
+        A.types = HashTab{c->tytab_hash.as<uint64_t>(), c->tytab_val.as<int32_t>(), c->tytab_mask};
+        A.unknown_type = c->unknown_type;
+        A.default_type = c->default_type;
+    }
+    A.last_unload = c->j_aux.as<int64_t>();
+    A.status = c->j_status.as<int32_t>();
+    A.cnt = c->j_cnt.as<int32_t>();
+    A.ent_pod = c->j_tmp_pod.as<int32_t>();
+    A.ent_time = c->j_tmp_time.as<int64_t>();
+    A.grp = ingest_group(n);
+    return MMP_OK;
+}
 }  // namespace
 
 int mmp_pod_ids_load(mmp_ctx *c, const char *ids, const int32_t *id_off, int32_t n_pods, uint32_t *id_order_out,
@@ -2545,25 +2594,20 @@ try {
     for (int32_t i = 0; i < n; i++) {
         const int32_t k = pod_idx[i];
         if (k < 0 || k >= P) return fail(c, MMP_EINVAL, "mmp_pods_ingest_json: record %d names pod %d", i, k);
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_pods_ingest_json: offsets not monotone at %d", i);
         mmp_pod_row r{};
         r.id_order = c->id_order_v[k];
         r.replica_set = c->replica_set_v[k];
         r.flags = (!live || live[i]) ? MMP_POD_LIVE : 0u;
         rows[i] = r;
     }
-    const int64_t bytes = off[n] - off[0];
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
-    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
+    std::vector<int64_t> rel;
+    int64_t bytes;
+    if (const int rc = stage_values(c, "mmp_pods_ingest_json", buf, off, n, rel, bytes)) return rc;
     HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_pod_row)));
     HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
     HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
-    std::vector<int64_t> rel(n + 1);
-    for (int32_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
     KT_BEGIN(c, st);
@@ -2627,49 +2671,25 @@ try {
         c->m_cnt.clear();
         return MMP_OK;
     }
-    for (int32_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_models_ingest_json: offsets not monotone at %d", i);
-    const int64_t bytes = off[n] - off[0];
-    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
-    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
-    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8 + 8));
-    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+    std::vector<int64_t> rel;
+    int64_t bytes;
+    if (const int rc = stage_values(c, "mmp_models_ingest_json", buf, off, n, rel, bytes)) return rc;
+    // one pass: every record's entries are parked, the counts are scanned, and the entries move to their CSR position — no host
+    // round trip in between
+    IngestModelsArgs A;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
     HIP_TRY(c, c->models.ensure((size_t)n * sizeof(mmp_model_row)));
-    std::vector<int64_t> rel(n + 1);
-    for (int32_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->models.p, 0, (size_t)n * sizeof(mmp_model_row), st));
-    IngestModelsArgs A{};
-    A.buf = c->j_buf.as<char>();
-    A.off = c->j_off.as<int64_t>();
-    A.n = n;
-    A.ids = HashTab{c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), c->idtab_mask};
-    A.types = c->have_types ? HashTab{c->tytab_hash.as<uint64_t>(), c->tytab_val.as<int32_t>(), c->tytab_mask}
-                            : HashTab{nullptr, nullptr, 0};
-    A.unknown_type = c->have_types ? c->unknown_type : 0;
-    A.default_type = c->have_types ? c->default_type : 0;
     A.rows = c->models.as<mmp_model_row>();
-    A.last_unload = c->j_aux.as<int64_t>();
-    A.status = c->j_status.as<int32_t>();
-    // one pass: every record's entries are parked at slot off / kJEntryBytes (ingest_kernels.hpp: n entries take >= 5n + 1
-    // bytes of JSON), the counts are scanned, and the entries move to their CSR position — no host round trip in between
-    const size_t ent_cap = (size_t)(bytes / kJEntryBytes + 2);
-    HIP_TRY(c, c->j_tmp_pod.ensure(ent_cap * 4));
-    HIP_TRY(c, c->j_tmp_time.ensure(ent_cap * 8));
     HIP_TRY(c, c->ent_pod.ensure(ent_cap * 4));
     HIP_TRY(c, c->ent_time.ensure(ent_cap * 8));
-    HIP_TRY(c, c->j_cnt.ensure((size_t)(n + 1) * 4));
     HIP_TRY(c, c->j_offs.ensure((size_t)(n + 1) * 4));
     size_t scan_bytes = 0;
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->j_cnt.as<int32_t>(), c->j_offs.as<int32_t>(), (int32_t)0,
                                        (size_t)n + 1, rocprim::plus<int32_t>(), st));
     HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
     HIP_TRY(c, hipMemsetAsync(c->j_cnt.as<int32_t>() + n, 0, 4, st));
-    A.cnt = c->j_cnt.as<int32_t>();
-    A.ent_pod = c->j_tmp_pod.as<int32_t>();
-    A.ent_time = c->j_tmp_time.as<int64_t>();
-    A.grp = ingest_group(n);
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * A.grp)), dim3(kJBlock), 0, st, A);
     HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, c->j_cnt.as<int32_t>(), c->j_offs.as<int32_t>(), (int32_t)0,
@@ -2710,7 +2730,6 @@ try {
         std::unordered_map<int32_t, int32_t> slot_of;
         slot_of.reserve((size_t)n * 2);
         for (int32_t i = 0; i < n; i++) {
-            if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: offsets not monotone at %d", i);
             if (model_idx[i] < 0 || model_idx[i] > count)
                 return fail(c, MMP_EINVAL, "mmp_models_upsert_json: event %d names model %d of %d", i, model_idx[i], count);
             if (model_idx[i] == count) count++;
@@ -2719,13 +2738,16 @@ try {
             h_slot[i] = it.first->second;
         }
     }
-    const int64_t bytes = off[n] - off[0];
-    if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: bad argument");
-    const size_t ent_cap = (size_t)(bytes / kJEntryBytes + 2);  // n entries take >= 5n + 1 bytes of JSON
-    if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: more than 2^31 entries in one call");
     const int32_t k = (int32_t)h_model.size();
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
+    std::vector<int64_t> rel;
+    int64_t bytes;
+    if (const int rc = stage_values(c, "mmp_models_upsert_json", buf, off, n, rel, bytes)) return rc;
+    IngestModelsArgs A;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
+    if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: more than 2^31 entries in one call");
     // j_ev, in words: slot[n] | slot_model[k] | win[k] | deleted[n bytes] (uploaded together) | s_cnt[k+1] | s_offs[k+1]
     const size_t del_words = ((size_t)n + 3) / 4, up_words = (size_t)n + 2 * (size_t)k + del_words;
     std::vector<int32_t> up(up_words, 0);
@@ -2735,40 +2757,14 @@ try {
     if (deleted)
         for (int32_t i = 0; i < n; i++) reinterpret_cast<uint8_t *>(up.data() + n + 2 * (size_t)k)[i] = deleted[i] ? 1 : 0;
     HIP_TRY(c, c->j_ev.ensure((up_words + 2 * ((size_t)k + 1)) * 4));
-    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
-    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
-    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
-    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
     HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
-    HIP_TRY(c, c->j_cnt.ensure((size_t)n * 4));
-    HIP_TRY(c, c->j_tmp_pod.ensure(ent_cap * 4));
-    HIP_TRY(c, c->j_tmp_time.ensure(ent_cap * 8));
     int32_t *d_slot = c->j_ev.as<int32_t>(), *d_model = d_slot + n, *d_win = d_model + k;
     int32_t *s_cnt = d_slot + up_words, *s_offs = s_cnt + k + 1;
     size_t scan_bytes = 0;
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
     HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-    std::vector<int64_t> rel(n + 1);
-    for (int32_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->j_ev.p, up.data(), up_words * 4, hipMemcpyHostToDevice, st));
-    IngestModelsArgs A{};
-    A.buf = c->j_buf.as<char>();
-    A.off = c->j_off.as<int64_t>();
-    A.n = n;
-    A.ids = HashTab{c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), c->idtab_mask};
-    A.types = c->have_types ? HashTab{c->tytab_hash.as<uint64_t>(), c->tytab_val.as<int32_t>(), c->tytab_mask}
-                            : HashTab{nullptr, nullptr, 0};
-    A.unknown_type = c->have_types ? c->unknown_type : 0;
-    A.default_type = c->have_types ? c->default_type : 0;
     A.rows = c->j_rows.as<mmp_model_row>();
-    A.last_unload = c->j_aux.as<int64_t>();
-    A.status = c->j_status.as<int32_t>();
-    A.cnt = c->j_cnt.as<int32_t>();
-    A.ent_pod = c->j_tmp_pod.as<int32_t>();
-    A.ent_time = c->j_tmp_time.as<int64_t>();
-    A.grp = ingest_group(n);
     A.deleted = deleted ? reinterpret_cast<const uint8_t *>(d_win + k) : nullptr;
     A.slot = d_slot;
     A.win = d_win;

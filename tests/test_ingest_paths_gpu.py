@@ -162,10 +162,11 @@ def test_grouped_path_planted_pods():
 
 # ---- 5. group sizes the host never picks by itself -----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("grp", [3, 7])
+@pytest.mark.parametrize("grp", [3, 7, 8])
 def test_odd_group_sizes(grp):
-    """MMP_JGROUP is read once per process: a fresh child ingests the first 4 096 records of the planted batches with 3 and with 7
-    records per wavefront.  A child that ends by a signal or runs into its time limit fails the test; it is not started again."""
+    """MMP_JGROUP is read once per process: a fresh child ingests the first 4 096 records of the planted batches with 3, 7 and 8
+    records per wavefront (4 096 records never reach 8 by the host's own choice), then sends the ModelRecords as registry events, which
+    must give what the reload gave.  A child that ends by a signal or runs into its time limit fails the test; it is not started again."""
     r = subprocess.run([sys.executable, "-m", "tests.ingest_group_child"], cwd=ROOT, env=dict(os.environ, MMP_JGROUP=str(grp)),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
