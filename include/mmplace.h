@@ -1089,6 +1089,55 @@ int mmp_models_ingest_json(mmp_ctx *ctx, const char *buf, const int64_t *off, in
  * winning events' entries appended to the arena on the device; only the per-event status, lul and entry counts come back. */
 int mmp_models_upsert_json(mmp_ctx *ctx, const char *buf, const int64_t *off, int32_t n, const int32_t *model_idx,
                            const uint8_t *deleted, int64_t *last_unload_out, int32_t *status_out);
+/* New instances join the index space: the n_new ids get the pod indices P .. P + n_new - 1 (P = the pod count at the call), their
+ * rows are appended as tombstones — what mmp_pod_ids_load leaves for a row it has not seen ingested — and the id -> pod table
+ * learns them.  id_order is recomputed for all P + n_new ids (rank under String.compareTo, as the load); replica_set of the new
+ * ids continues the load's interning: a six-character prefix seen before keeps its number, a new one gets the next, |id| < 7
+ * gives -1.  Both outputs are optional and cover ALL P + n_new pods; with either, max_pods >= P + n_new is required.
+ * Unlike a second mmp_pod_ids_load the call keeps the `missings` marks of mmp_registry_prune (the map grows by zero marks for
+ * the new slots), re-sorts only the new ids, extends the device table on the device (copy-on-write: a copy, or a rehash of the
+ * stored hashes when it outgrows its capacity, then an atomic insert per new id and a verifying lookup; swapped in on success)
+ * and does not quiesce decisions: nothing a decision kernel reads is rewritten.  (The call holds the state lock like the load, so
+ * a decision issued meanwhile waits for it to return.)  The next mmp_snapshot_commit RANKS FROM SCRATCH, as after mmp_pod_ids_load: a join moves
+ * the id_order of other rows, so it is not eligible for the insertion commit.  To the type tables the appended pods are what
+ * pods appended through mmp_pods_upsert are.  Records that named one of the ids before it joined: mmp_registry_unresolved.
+ * MMP_EINVAL with NOTHING changed (table, rows, marks, ids): a NULL required buffer, non-monotone offsets, an id equal to an
+ * existing id or to another new one or colliding with one under FNV-1a (the rule of the load), an output with max_pods too
+ * small.  MMP_ESTATE before the first mmp_pod_ids_load (a load of 0 ids is a valid start) and when mmp_pods_load /
+ * mmp_pods_upsert have resized the table since.  n_new == 0 is valid and changes nothing. */
+int mmp_pod_ids_append(mmp_ctx *ctx, const char *ids, const int32_t *id_off, int32_t n_new, uint32_t *id_order_out,
+                       int32_t *replica_set_out, int32_t max_pods);
+/* Instance-table events as stored (handleInstanceTableChange, MM.java:1455): event i is the instance id
+ * keys[key_off[i], key_off[i+1]) — the raw ASCII bytes of the KV key, not JSON-escaped — with the InstanceRecord value
+ * buf[off[i], off[i+1]).  The keys are resolved against the id table on the device.  deleted[i] != 0: the effect of
+ * mmp_pods_remove on that pod; the value is ignored and may be empty.  Otherwise the value goes through the parser of
+ * mmp_pods_ingest_json (live as there).  status_out[i]: 0 applied, 1 malformed value (the row is left as it was), 2 unknown id
+ * (nothing changes; pod_idx_out[i] = -1).  An id the table does not know: with MMP_PEV_APPEND in flags the distinct unknown ids
+ * of NON-DELETED events join through mmp_pod_ids_append, in order of first appearance, whether or not their values turn out
+ * well-formed (the index has been handed out, the row stays a tombstone: the rule of mmp_models_upsert_json for appended rows);
+ * without the flag such an event is status 2.  A deletion never appends: of an id that is unknown when the event is reached —
+ * the table and the events before it — it is status 2.  Events apply in order: a pod ends as its LAST WELL-FORMED OR DELETED event
+ * left it.  pod_idx_out[i] = the resolved index (mmp_upgrade_instance_added and the serve counters need it);
+ * start_time_out[i] = InstanceRecord.startTime of an applied value, else 0; *n_appended_out = ids that joined.  deleted, live,
+ * start_time_out, n_appended_out may be NULL.  After a join the next commit ranks from scratch (mmp_pod_ids_append).
+ * MMP_EINVAL with nothing changed: a NULL required buffer, non-monotone offsets of either kind, unknown flags, two new ids that
+ * collide under FNV-1a.  MMP_ESTATE, with nothing changed: before mmp_pod_ids_load, and when mmp_pods_load / mmp_pods_upsert
+ * have resized the instance table since (its rows and the ids no longer cover the same indices; checked for every call, with or
+ * without a join).  Locking as mmp_pod_ids_append.  n == 0 is valid. */
+#define MMP_PEV_APPEND 1u
+int mmp_pods_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                         const uint8_t *deleted, const uint8_t *live, uint32_t flags, int32_t *pod_idx_out, int64_t *start_time_out,
+                         int32_t *status_out, int32_t *n_appended_out);
+/* Which records name an id the table does not know: the registry rows that hold at least one entry (loaded or failed) whose pod
+ * is outside [0, pod slots of the staged table), in ascending row order.  *n_models_out / *n_entries_out are always the full
+ * counts (*n_entries_out = mmp_registry_stats.n_entries_unresolved); at most max_models rows are written, lowest rows first;
+ * model_out == NULL with max_models == 0 asks for the sizes only.  Read-only, locking as mmp_registry_census, no commit needed;
+ * two runs over the same registry are byte-identical.
+ * The intended loop: (1) an instance joins (mmp_pod_ids_append / mmp_pods_events_json); (2) the host asks here; (3) it sends
+ * the stored values of those records through mmp_models_upsert_json again — the registry listener has them.  The library cannot
+ * do step 3 by itself: the registry keeps neither the bytes nor the hash of an id it could not resolve, only pod -1.  Until
+ * then such an entry still counts as a copy but excludes nobody in a decision. */
+int mmp_registry_unresolved(mmp_ctx *ctx, int32_t *model_out, int32_t max_models, int32_t *n_models_out, int64_t *n_entries_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -163,6 +163,21 @@ final class MmPlace {
     /** a batch of registry events as stored: value i for model modelIdx[i]; deleted (may be null) marks ENTRY_DELETED */
     static native int modelsUpsertJson(long h, ByteBuffer json, ByteBuffer off, int n, ByteBuffer modelIdx, ByteBuffer deleted,
                                        ByteBuffer lastUnloadOut, ByteBuffer statusOut);
+    // instances join after podIdsLoad: the nNew ids get the indices P .. P + nNew - 1; idOrderOut / replicaSetOut (may be null)
+    // cover ALL P + nNew pods and need maxPods >= P + nNew.  The missings marks of registryPrune are kept (a second podIdsLoad
+    // clears them); the next commit ranks from scratch.
+    static native int podIdsAppend(long h, ByteBuffer ids, ByteBuffer idOff, int nNew, ByteBuffer idOrderOut,
+                                   ByteBuffer replicaSetOut, int maxPods);
+    /** handleInstanceTableChange (MM.java:1455) as stored: event i = the raw key bytes keys[keyOff[i], keyOff[i+1]) (the instance
+     *  id) with the raw value json[off[i], off[i+1]); deleted (may be null) marks a deletion; flags 1 = unknown ids join.
+     *  podIdxOut = the pod of each event (-1 with status 2), statusOut 0 applied / 1 malformed / 2 unknown id; nAppendedOut =
+     *  ids that joined (one int, may be null). */
+    static native int podsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
+                                     ByteBuffer deleted, ByteBuffer live, int flags, ByteBuffer podIdxOut,
+                                     ByteBuffer startTimeOut, ByteBuffer statusOut, ByteBuffer nAppendedOut);
+    // the registry rows holding an entry whose instance id the table does not know, ascending; after a join the listener sends
+    // their stored values through modelsUpsertJson again.  nModelsOut (int) / nEntriesOut (long) are the full counts.
+    static native int registryUnresolved(long h, ByteBuffer modelOut, int maxModels, ByteBuffer nModelsOut, ByteBuffer nEntriesOut);
     // misc
     static native long minSpaceUnits(int defaultModelSizeUnits, int loadingThreads, long capacityUnits,
                                      boolean haveUnloadManager);
@@ -180,7 +195,8 @@ final class MmPlace {
  * What the GPU load balancers need from the enclosing ModelMesh instance.  The patch implements it as an inner
  * class of ModelMesh: the interner maps instance id <-> dense pod index (id_order == rank under String.compareTo,
  * replica_set == interned id.substring(0,6)) and model id -> dense model index; the snapshot handle is refreshed by
- * the instance-table listener (handleInstanceTableChange, ModelMesh.java:1455: podsUpsert / podsRemove + commit) and
+ * the instance-table listener (handleInstanceTableChange, ModelMesh.java:1455: podsEventsJson with the raw key and value
+ * of each event + commit, registryUnresolved + modelsUpsertJson after a join; or podsUpsert / podsRemove with parsed rows) and
  * by the registry listener (modelsIngestJson of the stored values once, then modelsUpsertJson per batch of events with
  * the raw byte[] of each event and the model index of its key, ENTRY_DELETED as a deleted flag; a listener that holds
  * parsed ModelRecords uses modelsLoad / modelsUpsert instead).

@@ -589,6 +589,59 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsUpsertJson(JN
                                         buf<int64_t>(env, lastUnloadOut), buf<int32_t>(env, statusOut)));
 }
 
+// Instances join after podIdsLoad (see mmp_pod_ids_append).  The capacities are checked here — the offsets, the id bytes up to the
+// last offset, the outputs — the library only knows nNew / maxPods.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podIdsAppend(JNIEnv *env, jclass, jlong h, jobject ids,
+                                                                          jobject idOff, jint nNew, jobject idOrderOut,
+                                                                          jobject replicaSetOut, jint maxPods)
+{
+    if (!holds<int32_t>(env, idOff, (jlong)nNew + 1, "podIdsAppend: idOff shorter than nNew + 1") ||
+        (nNew > 0 && !holds<char>(env, ids, buf<int32_t>(env, idOff)[nNew], "podIdsAppend: ids shorter than idOff[nNew]")) ||
+        (idOrderOut && !holds<uint32_t>(env, idOrderOut, maxPods, "podIdsAppend: idOrderOut shorter than maxPods")) ||
+        (replicaSetOut && !holds<int32_t>(env, replicaSetOut, maxPods, "podIdsAppend: replicaSetOut shorter than maxPods")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_pod_ids_append(ctx_of(h), buf<char>(env, ids), buf<int32_t>(env, idOff), nNew,
+                                    buf<uint32_t>(env, idOrderOut), buf<int32_t>(env, replicaSetOut), maxPods));
+}
+// instance-table events as stored: the raw key and value bytes of each event (see mmp_pods_events_json)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podsEventsJson(JNIEnv *env, jclass, jlong h, jobject keys,
+                                                                            jobject keyOff, jobject json, jobject off, jint n,
+                                                                            jobject deleted, jobject live, jint flags,
+                                                                            jobject podIdxOut, jobject startTimeOut,
+                                                                            jobject statusOut, jobject nAppendedOut)
+{
+    if (!holds<int32_t>(env, keyOff, (jlong)n + 1, "podsEventsJson: keyOff shorter than n + 1") ||
+        !holds<int64_t>(env, off, (jlong)n + 1, "podsEventsJson: off shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "podsEventsJson: keys shorter than keyOff[n]")) ||
+        (n > 0 && !holds<char>(env, json, buf<int64_t>(env, off)[n], "podsEventsJson: json shorter than off[n]")) ||
+        (deleted && !holds<uint8_t>(env, deleted, n, "podsEventsJson: deleted shorter than n")) ||
+        (live && !holds<uint8_t>(env, live, n, "podsEventsJson: live shorter than n")) ||
+        !holds<int32_t>(env, podIdxOut, n, "podsEventsJson: podIdxOut shorter than n") ||
+        (startTimeOut && !holds<int64_t>(env, startTimeOut, n, "podsEventsJson: startTimeOut shorter than n")) ||
+        !holds<int32_t>(env, statusOut, n, "podsEventsJson: statusOut shorter than n") ||
+        (nAppendedOut && !holds<int32_t>(env, nAppendedOut, 1, "podsEventsJson: nAppendedOut shorter than one int")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_pods_events_json(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), buf<char>(env, json),
+                                      buf<int64_t>(env, off), n, buf<uint8_t>(env, deleted), buf<uint8_t>(env, live),
+                                      static_cast<uint32_t>(flags), buf<int32_t>(env, podIdxOut), buf<int64_t>(env, startTimeOut),
+                                      buf<int32_t>(env, statusOut), buf<int32_t>(env, nAppendedOut)));
+}
+// which records name an id the table does not know (see mmp_registry_unresolved); a null modelOut with maxModels 0: sizes only
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryUnresolved(JNIEnv *env, jclass, jlong h, jobject modelOut,
+                                                                                jint maxModels, jobject nModelsOut,
+                                                                                jobject nEntriesOut)
+{
+    if (!holds<int32_t>(env, modelOut, maxModels, "registryUnresolved: modelOut shorter than maxModels") ||
+        !holds<int32_t>(env, nModelsOut, 1, "registryUnresolved: nModelsOut shorter than one int") ||
+        !holds<int64_t>(env, nEntriesOut, 1, "registryUnresolved: nEntriesOut shorter than one long"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_registry_unresolved(ctx_of(h), buf<int32_t>(env, modelOut), maxModels, buf<int32_t>(env, nModelsOut),
+                                         buf<int64_t>(env, nEntriesOut)));
+}
+
 // ---- misc -----------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL Java_com_ibm_watson_modelmesh_MmPlace_minSpaceUnits(JNIEnv *, jclass,
                                                                             jint defaultModelSizeUnits,

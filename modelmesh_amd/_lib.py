@@ -167,6 +167,10 @@ REGISTRY_TYPE_STATS = np.dtype([("n_models", "<i4"), ("n_loaded", "<i4"), ("n_fa
                                 ("n_entries_loaded", "<i8")])
 assert REGISTRY_STATS.itemsize == 72 and REGISTRY_TYPE_STATS.itemsize == 24
 
+# mmp_pods_events_json (instance-table events by key, handleInstanceTableChange MM.java:1455)
+PEV_APPEND = 1
+PEV_APPLIED, PEV_MALFORMED, PEV_UNKNOWN = 0, 1, 2  # status_out
+
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
      ("last_unload_time", "<i8"), ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"),
@@ -286,6 +290,9 @@ SYMBOLS = [
     ("mmp_type_names_load", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     ("mmp_models_ingest_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     ("mmp_models_upsert_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("mmp_pod_ids_append", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32]),
+    ("mmp_pods_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
+    ("mmp_registry_unresolved", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -282,10 +282,13 @@ struct HashTab {
     uint32_t mask;  // capacity - 1 (power of two); 0 with hash == nullptr means "empty table"
 };
 
+// where the probe sequence of hash h starts (the host's build_hash_table and the device's inserts start there too)
+__host__ __device__ constexpr uint32_t tab_home(uint64_t h, uint32_t mask) { return (uint32_t)(h ^ (h >> 32)) & mask; }
+
 __device__ __forceinline__ int32_t tab_find(const HashTab &t, uint64_t h, int32_t missing)
 {
     if (!t.hash) return missing;
-    uint32_t s = (uint32_t)(h ^ (h >> 32)) & t.mask;
+    uint32_t s = tab_home(h, t.mask);
     for (uint32_t probe = 0; probe <= t.mask; probe++) {
         const int32_t v = t.val[s];
         if (v == INT32_MIN) return missing;  // empty slot

@@ -41,6 +41,7 @@
 #include "registry_ops_kernels.hpp"
 #include "status_kernels.hpp"
 #include "census_kernels.hpp"
+#include "pod_events_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -387,6 +388,14 @@ struct mmp_ctx {
     uint32_t idtab_mask = 0, tytab_mask = 0;
     bool have_ids = false, have_types = false;
     int32_t unknown_type = 0, default_type = 0;
+    // what mmp_pod_ids_append continues from the load: the id bytes (id i = id_bytes[id_offs[i], id_offs[i + 1])), the pods in id
+    // order, and the replica-set interning.  idtab_next_*: the table built beside the published one (swapped in when the call
+    // succeeds); ida_*: the new ids / event keys of one call on the device — bytes, offsets, hashes, what tab_find answered.
+    std::string id_bytes;
+    std::vector<int32_t> id_offs{0}, id_sorted;
+    std::unordered_map<std::string, int32_t> rs_intern;
+    DevBuf idtab_next_hash, idtab_next_val, ida_bytes, ida_off, ida_hash, ida_found;
+    DevBuf unres_list;  // mmp_registry_unresolved: the listed rows (its other scratch is the registry plans')
 
     // per-call scratch for the host-pointer entry points
     DevBuf s_reqs, s_outs, s_extra, s_a, s_b, s_c, s_d;
@@ -1059,7 +1068,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -2467,7 +2476,7 @@ int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n
     for (int32_t i = 0; i < n; i++) {
         if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: offsets not monotone at %d", what, i);
         const uint64_t h = fnv1a(strs + off[i], off[i + 1] - off[i]);
-        uint32_t s = (uint32_t)(h ^ (h >> 32)) & (cap - 1);
+        uint32_t s = tab_home(h, cap - 1);
         while (vs[s] != INT32_MIN) {
             if (hs[s] == h) return fail(c, MMP_EINVAL, "%s: entries %d and %d are equal or collide under FNV-1a", what, vs[s], i);
             s = (s + 1) & (cap - 1);
@@ -2531,6 +2540,20 @@ int ingest_models_args(mmp_ctx *c, int32_t n, int64_t bytes, IngestModelsArgs &A
     A.grp = ingest_group(n);
     return MMP_OK;
 }
+// String.compareTo on ASCII ids == bytewise comparison, shorter prefix first (ids a and b of the context's id store)
+bool id_less(const mmp_ctx *c, int32_t a, int32_t b)
+{
+    const int la = c->id_offs[a + 1] - c->id_offs[a], lb = c->id_offs[b + 1] - c->id_offs[b];
+    const int m = memcmp(c->id_bytes.data() + c->id_offs[a], c->id_bytes.data() + c->id_offs[b], (size_t)std::min(la, lb));
+    return m != 0 ? m < 0 : la < lb;
+}
+
+// interned id.substring(0, 6) of stored id i: a prefix seen before keeps its number, a new one gets the next
+int32_t intern_replica_set(mmp_ctx *c, int32_t i)
+{
+    if (c->id_offs[i + 1] - c->id_offs[i] < 7) return -1;  // MM.java:4769: iid.length() > 6
+    return c->rs_intern.emplace(std::string(c->id_bytes.data() + c->id_offs[i], 6), (int32_t)c->rs_intern.size()).first->second;
+}
 }  // namespace
 
 int mmp_pod_ids_load(mmp_ctx *c, const char *ids, const int32_t *id_off, int32_t n_pods, uint32_t *id_order_out,
@@ -2543,25 +2566,18 @@ try {
     HIP_TRY(c, quiesce_decisions(c));
     int rc = build_hash_table(c, ids, id_off, n_pods, c->idtab_hash, c->idtab_val, c->idtab_mask, "mmp_pod_ids_load");
     if (rc != MMP_OK) return rc;
-    // String.compareTo on ASCII ids == bytewise comparison, shorter prefix first
-    std::vector<int32_t> perm(n_pods);
-    for (int32_t i = 0; i < n_pods; i++) perm[i] = i;
-    auto less = [&](int32_t a, int32_t b) {
-        const int la = id_off[a + 1] - id_off[a], lb = id_off[b + 1] - id_off[b];
-        const int m = memcmp(ids + id_off[a], ids + id_off[b], (size_t)std::min(la, lb));
-        return m != 0 ? m < 0 : la < lb;
-    };
-    std::sort(perm.begin(), perm.end(), less);
+    // the ids, their order and the interning stay with the context: mmp_pod_ids_append continues all three
+    c->id_bytes.assign(n_pods ? ids + id_off[0] : "", n_pods ? (size_t)(id_off[n_pods] - id_off[0]) : 0);
+    c->id_offs.resize((size_t)n_pods + 1);
+    for (int32_t i = 0; i <= n_pods; i++) c->id_offs[i] = id_off[i] - id_off[0];
+    c->id_sorted.resize(n_pods);
+    for (int32_t i = 0; i < n_pods; i++) c->id_sorted[i] = i;
+    std::sort(c->id_sorted.begin(), c->id_sorted.end(), [c](int32_t a, int32_t b) { return id_less(c, a, b); });
     c->id_order_v.assign(n_pods, 0);
-    for (int32_t r = 0; r < n_pods; r++) c->id_order_v[perm[r]] = (uint32_t)r;
-    std::unordered_map<std::string, int32_t> rs_intern;
+    for (int32_t r = 0; r < n_pods; r++) c->id_order_v[c->id_sorted[r]] = (uint32_t)r;
+    c->rs_intern.clear();
     c->replica_set_v.assign(n_pods, -1);
-    for (int32_t i = 0; i < n_pods; i++) {
-        const int len = id_off[i + 1] - id_off[i];
-        if (len < 7) continue;  // MM.java:4769: iid.length() > 6
-        auto it = rs_intern.emplace(std::string(ids + id_off[i], 6), (int32_t)rs_intern.size());
-        c->replica_set_v[i] = it.first->second;
-    }
+    for (int32_t i = 0; i < n_pods; i++) c->replica_set_v[i] = intern_replica_set(c, i);
     const size_t old = c->pods.size();
     c->pods.resize(n_pods);
     c->dirty_all = true;
@@ -2631,6 +2647,256 @@ try {
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_pods_ingest_json")
+
+namespace {
+int missing_cover(mmp_ctx *c, int32_t n);  // (defined with the prune below)
+
+// n ids or event keys onto the device (batch_mu held, the device set): off[0 .. n] must not decrease; ida_bytes gets the bytes
+// [off[0], off[n]), ida_off the offsets rebased to off[0].  Both uploads are enqueued on c->stream; `rel` stays with the caller
+// until it has synchronised.
+int stage_ids(mmp_ctx *c, const char *fn, const char *what, const char *ids, const int32_t *off, int32_t n, std::vector<int32_t> &rel)
+{
+    rel.assign((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; i++) {
+        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: %s offsets not monotone at %d", fn, what, i);
+        rel[i + 1] = off[i + 1] - off[0];
+    }
+    if (rel[n] > 0 && !ids) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    HIP_TRY(c, c->ida_bytes.ensure((size_t)rel[n] + 16));
+    HIP_TRY(c, c->ida_off.ensure((size_t)(n + 1) * 4));
+    if (rel[n]) HIP_TRY(c, hipMemcpyAsync(c->ida_bytes.p, ids + off[0], (size_t)rel[n], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->ida_off.p, rel.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    return MMP_OK;
+}
+
+// The staged instance table and the id store cover the same indices: mmp_pods_load / mmp_pods_upsert resize the table without
+// telling the id store, and an index of one space must not be used in the other.
+int id_space_guard(mmp_ctx *c, const char *fn)
+{
+    if (c->pods.size() + 1 == c->id_offs.size()) return MMP_OK;
+    return fail(c, MMP_ESTATE, "%s: the instance table has %d rows for %d loaded ids (mmp_pods_load / mmp_pods_upsert resized it)", fn,
+                (int32_t)c->pods.size(), (int32_t)c->id_offs.size() - 1);
+}
+
+// The body of mmp_pod_ids_append (batch_mu and the state lock held, the device set, c->have_ids, n_new > 0, the offsets checked):
+// the next table is built beside the published one and everything is swapped in only once the new ids have verified.
+int pod_ids_append_locked(mmp_ctx *c, const char *fn, const char *ids, const int32_t *id_off, int32_t n_new)
+{
+    const int32_t P = (int32_t)c->pods.size();
+    if (const int rc = id_space_guard(c, fn)) return rc;
+    if ((int64_t)P + n_new > INT32_MAX / 4) return fail(c, MMP_EINVAL, "%s: %d + %d ids", fn, P, n_new);
+    hipStream_t st = c->stream;
+    std::vector<int32_t> rel;
+    if (const int rc = stage_ids(c, fn, "id", ids, id_off, n_new, rel)) return rc;
+    const uint32_t cap0 = c->idtab_mask + 1;
+    uint32_t cap = 16;  // the capacity build_hash_table would choose for P + n_new ids
+    while (cap < (uint32_t)(P + n_new) * 2u) cap <<= 1;
+    cap = std::max(cap, cap0);
+    HIP_TRY(c, c->idtab_next_hash.ensure((size_t)cap * 8));
+    HIP_TRY(c, c->idtab_next_val.ensure((size_t)cap * 4));
+    HIP_TRY(c, c->ida_hash.ensure((size_t)n_new * 8));
+    HIP_TRY(c, c->ida_found.ensure((size_t)n_new * 4));
+    const HashTabW nt{c->idtab_next_hash.as<uint64_t>(), c->idtab_next_val.as<int32_t>(), cap - 1};
+    KT_BEGIN(c, st);
+    if (cap == cap0) {  // room for the new ids: the slots as they are
+        HIP_TRY(c, hipMemcpyAsync(nt.hash, c->idtab_hash.p, (size_t)cap * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(nt.val, c->idtab_val.p, (size_t)cap * 4, hipMemcpyDeviceToDevice, st));
+    } else {  // the stored hashes into the larger table
+        HIP_TRY(c, hipMemsetAsync(nt.hash, 0, (size_t)cap * 8, st));
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nt.val), INT32_MIN, cap, st));
+        hipLaunchKernelGGL(idtab_rehash_kernel, dim3(div_up((int)cap0, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->idtab_hash.as<uint64_t>(),
+                           c->idtab_val.as<int32_t>(), cap0, nt);
+    }
+    hipLaunchKernelGGL(idtab_insert_kernel, dim3(div_up(n_new, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_bytes.as<char>(),
+                       c->ida_off.as<int32_t>(), n_new, P, nt, c->ida_hash.as<uint64_t>());
+    hipLaunchKernelGGL(idtab_verify_kernel, dim3(div_up(n_new, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_hash.as<uint64_t>(), n_new,
+                       HashTab{nt.hash, nt.val, nt.mask}, c->ida_found.as<int32_t>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> found(n_new);
+    HIP_TRY(c, copy_sync(c, found.data(), c->ida_found.p, (size_t)n_new * 4, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    for (int32_t i = 0; i < n_new; i++) {
+        if (found[i] == P + i) continue;
+        if (found[i] < 0) return fail(c, MMP_EHIP, "%s: id %d was not inserted", fn, P + i);
+        // (whichever of two new ids claimed its slot first: the pair is reported lower index first, as the load does)
+        return fail(c, MMP_EINVAL, "%s: entries %d and %d are equal or collide under FNV-1a", fn, std::min(found[i], P + i),
+                    std::max(found[i], P + i));
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (const int rc = missing_cover(c, P + n_new)) return rc;  // the marks stay, the new slots carry none (the last step that can fail)
+    // nothing fails from here on: the table, the id store, the order, the interning and the rows change together
+    std::swap(c->idtab_hash, c->idtab_next_hash);
+    std::swap(c->idtab_val, c->idtab_next_val);
+    c->idtab_mask = cap - 1;
+    const int32_t base = c->id_offs[P];
+    c->id_bytes.append(ids + id_off[0], (size_t)rel[n_new]);
+    for (int32_t i = 1; i <= n_new; i++) c->id_offs.push_back(base + rel[i]);
+    std::vector<int32_t> fresh(n_new), merged((size_t)P + n_new);
+    for (int32_t i = 0; i < n_new; i++) fresh[i] = P + i;
+    const auto less = [c](int32_t a, int32_t b) { return id_less(c, a, b); };
+    std::sort(fresh.begin(), fresh.end(), less);
+    std::merge(c->id_sorted.begin(), c->id_sorted.end(), fresh.begin(), fresh.end(), merged.begin(), less);
+    c->id_sorted.swap(merged);
+    c->id_order_v.resize((size_t)P + n_new);
+    for (int32_t r = 0; r < P + n_new; r++) c->id_order_v[c->id_sorted[r]] = (uint32_t)r;
+    c->replica_set_v.resize((size_t)P + n_new, -1);
+    for (int32_t i = P; i < P + n_new; i++) c->replica_set_v[i] = intern_replica_set(c, i);
+    c->pods.resize((size_t)P + n_new);
+    for (int32_t i = 0; i < P + n_new; i++) {
+        if (i >= P) {
+            c->pods[i] = mmp_pod_row{};
+            c->pods[i].flags = MMP_POD_TOMBSTONE;
+            c->pods[i].replica_set = c->replica_set_v[i];
+        }
+        c->pods[i].id_order = c->id_order_v[i];
+    }
+    c->dirty_all = true;  // every row's id_order may have moved: the next commit ranks from scratch
+    c->dirty.clear();
+    return MMP_OK;
+}
+}  // namespace
+
+int mmp_pod_ids_append(mmp_ctx *c, const char *ids, const int32_t *id_off, int32_t n_new, uint32_t *id_order_out,
+                       int32_t *replica_set_out, int32_t max_pods)
+try {
+    if (!c || n_new < 0 || !id_off || (n_new > 0 && !ids) || max_pods < 0) return fail(c, MMP_EINVAL, "mmp_pod_ids_append: bad argument");
+    // the locks of the load.  The id table is read by the ingest kernels alone, which run under batch_mu: no quiesce_decisions (a
+    // decision still waits for the state lock while this call holds it)
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_pod_ids_append: load the instance ids first (mmp_pod_ids_load)");
+    for (int32_t i = 0; i < n_new; i++)
+        if (id_off[i + 1] < id_off[i]) return fail(c, MMP_EINVAL, "mmp_pod_ids_append: id offsets not monotone at %d", i);
+    const int64_t total = (int64_t)c->pods.size() + n_new;
+    if ((id_order_out || replica_set_out) && max_pods < total)
+        return fail(c, MMP_EINVAL, "mmp_pod_ids_append: room for %d pods, the table will have %lld", max_pods, (long long)total);
+    if (n_new > 0) {
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        if (const int rc = pod_ids_append_locked(c, "mmp_pod_ids_append", ids, id_off, n_new)) return rc;
+    }
+    const size_t n = std::min(c->id_order_v.size(), c->pods.size());
+    if (id_order_out && n) memcpy(id_order_out, c->id_order_v.data(), n * 4);
+    if (replica_set_out && n) memcpy(replica_set_out, c->replica_set_v.data(), n * 4);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_pod_ids_append")
+
+int mmp_pods_events_json(mmp_ctx *c, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                         const uint8_t *deleted, const uint8_t *live, uint32_t flags, int32_t *pod_idx_out, int64_t *start_time_out,
+                         int32_t *status_out, int32_t *n_appended_out)
+try {
+    if (!c || n < 0 || (flags & ~MMP_PEV_APPEND) || (n > 0 && (!keys || !key_off || !off || !pod_idx_out || !status_out)))
+        return fail(c, MMP_EINVAL, "mmp_pods_events_json: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_pods_events_json: load the instance ids first (mmp_pod_ids_load)");
+    // a key resolves to an index of the id space, and step 4 writes the staged row of that index: the two must be one space
+    if (const int rc = id_space_guard(c, "mmp_pods_events_json")) return rc;
+    if (n_appended_out) *n_appended_out = 0;
+    if (n == 0) return MMP_OK;
+    for (int32_t i = 0; i < n; i++)  // (both kinds, before anything is staged: a refused call changes nothing)
+        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_pods_events_json: offsets not monotone at %d", i);
+    if (off[n] > off[0] && !buf) return fail(c, MMP_EINVAL, "mmp_pods_events_json: bad argument");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // 1. the keys against the id table, a lane per event
+    std::vector<int32_t> krel, idx(n);
+    if (const int rc = stage_ids(c, "mmp_pods_events_json", "key", keys, key_off, n, krel)) return rc;
+    HIP_TRY(c, c->ida_found.ensure((size_t)n * 4));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(resolve_keys_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_bytes.as<char>(),
+                       c->ida_off.as<int32_t>(), n, HashTab{c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), c->idtab_mask},
+                       c->ida_found.as<int32_t>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, copy_sync(c, idx.data(), c->ida_found.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    double span_ms = c->last_kernel_ms;
+    // 2. the ids nobody knows: with MMP_PEV_APPEND the distinct ones of non-deleted events join, in order of first appearance (a
+    // map sized by the unknown keys of the call).  A deletion resolves to such an id only behind the event that made it join.
+    const int32_t P0 = (int32_t)c->pods.size();
+    const bool append = flags & MMP_PEV_APPEND;
+    std::string join_bytes;
+    std::vector<int32_t> join_off{0};
+    {
+        std::unordered_map<std::string, int32_t> joined;
+        for (int32_t i = 0; i < n; i++) {
+            if (idx[i] >= 0) continue;
+            const bool del = deleted && deleted[i];
+            if (!append && !del) continue;
+            std::string key(keys + key_off[i], (size_t)(key_off[i + 1] - key_off[i]));
+            if (del) {
+                const auto it = joined.find(key);
+                if (it != joined.end()) idx[i] = it->second;
+                continue;
+            }
+            const auto it = joined.emplace(std::move(key), P0 + (int32_t)join_off.size() - 1);
+            if (it.second) {
+                join_bytes.append(it.first->first);
+                join_off.push_back((int32_t)join_bytes.size());
+            }
+            idx[i] = it.first->second;
+        }
+    }
+    const int32_t n_join = (int32_t)join_off.size() - 1;
+    if (n_join > 0) {
+        if (const int rc = pod_ids_append_locked(c, "mmp_pods_events_json", join_bytes.data(), join_off.data(), n_join)) return rc;
+        if (c->prof && span_ms >= 0 && c->last_kernel_ms >= 0) span_ms += c->last_kernel_ms;
+    }
+    // 3. the values through the parser of mmp_pods_ingest_json, every event into a row of its own
+    std::vector<mmp_pod_row> rows(n);
+    for (int32_t i = 0; i < n; i++) {
+        mmp_pod_row r{};
+        if (idx[i] >= 0) {
+            r.id_order = c->id_order_v[idx[i]];
+            r.replica_set = c->replica_set_v[idx[i]];
+        }
+        r.flags = (!live || live[i]) ? MMP_POD_LIVE : 0u;
+        rows[i] = r;
+    }
+    std::vector<int64_t> rel;
+    int64_t bytes;
+    if (const int rc = stage_values(c, "mmp_pods_events_json", buf, off, n, rel, bytes)) return rc;
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_pod_row)));
+    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
+    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+    HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
+    KT_BEGIN(c, st);
+    const int grp = ingest_group(n);
+    hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(), c->j_off.as<int64_t>(), n,
+                       grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int64_t> stt(n);
+    HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(stt.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    if (c->prof && span_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += span_ms;  // the call's device span: resolve + join + parse
+    // 4. the events in order: a pod ends as its last well-formed or deleted event left it
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t k = idx[i];
+        pod_idx_out[i] = k;
+        int64_t started = 0;
+        if (k < 0) {
+            status_out[i] = 2;
+        } else if (deleted && deleted[i]) {  // mmp_pods_remove
+            status_out[i] = 0;
+            c->pods[k].flags |= MMP_POD_TOMBSTONE;
+            c->pods[k].flags &= ~MMP_POD_LIVE;
+            note_dirty(c, k);
+        } else if (status_out[i] == 0) {
+            c->pods[k] = rows[i];
+            note_dirty(c, k);
+            started = stt[i];
+        }
+        if (start_time_out) start_time_out[i] = started;
+    }
+    if (n_appended_out) *n_appended_out = n_join;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_pods_events_json")
 
 int mmp_type_names_load(mmp_ctx *c, const char *names, const int32_t *name_off, int32_t n_types, int32_t unknown_type)
 try {
@@ -4882,6 +5148,45 @@ try {
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_registry_census")
+
+int mmp_registry_unresolved(mmp_ctx *c, int32_t *model_out, int32_t max_models, int32_t *n_models_out, int64_t *n_entries_out)
+try {
+    if (!c || !n_models_out || !n_entries_out || max_models < 0 || (max_models > 0 && !model_out))
+        return fail(c, MMP_EINVAL, "mmp_registry_unresolved: bad argument");
+    // read-only, the locking of the census: batch_mu owns c->stream and the plans' scratch, every writer of the registry and of the
+    // instance table takes it too; nothing decisions read is written
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t M = c->n_models, P = (int32_t)c->pods.size();
+    *n_models_out = 0;
+    *n_entries_out = 0;
+    if (M == 0) return MMP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int nb = div_up(M, kUnresolvedBlock);
+    const int32_t cap = std::min(max_models, M);
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
+    HIP_TRY(c, c->unres_list.ensure((size_t)std::max(cap, 1) * 4));
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    int32_t *counts = c->plan.block_counts.as<int32_t>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(unresolved_count_kernel, dim3(nb), dim3(kUnresolvedBlock), 0, st, models, M, c->ent_pod.as<int32_t>(), P, counts);
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, counts, nb, INT32_MAX, INT32_MAX, ps);
+    if (cap > 0)
+        hipLaunchKernelGGL(unresolved_list_kernel, dim3(nb), dim3(kUnresolvedBlock), 0, st, models, M, c->ent_pod.as<int32_t>(), P, counts,
+                           c->unres_list.as<int32_t>(), cap);
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    PruneScalars h{};
+    HIP_TRY(c, copy_sync(c, &h, ps, sizeof h, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    const int32_t take = std::min(h.n_edits, cap);
+    if (take > 0) HIP_TRY(c, copy_sync(c, model_out, c->unres_list.p, (size_t)take * 4, hipMemcpyDeviceToHost));
+    *n_models_out = h.n_edits;
+    *n_entries_out = h.n_kept;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_registry_unresolved")
 
 int mmp_registry_missing_get(mmp_ctx *c, int64_t *since_out, int32_t max_pods, int32_t *n_out)
 try {

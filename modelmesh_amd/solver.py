@@ -183,6 +183,65 @@ class Solver:
             self._live = mirror
         return status[:n], st[:n]
 
+    def append_pod_ids(self, ids):
+        """New instances join the index space (mmp_pod_ids_append): ids get the indices n_pods .. n_pods + len(ids) - 1; returns
+        (id_order, replica_set) of ALL pods."""
+        blob, off = self._pack(ids)
+        off32 = off.astype(np.int32)
+        total = self.n_pods + len(ids)
+        io = np.zeros(max(total, 1), np.uint32)
+        rs = np.zeros(max(total, 1), np.int32)
+        self._ck(self.lib.mmp_pod_ids_append(self.h, blob, ptr(off32), len(ids), ptr(io), ptr(rs), total))
+        self._grow_live(total)
+        self.n_pods = total
+        return io[:total], rs[:total]
+
+    def _grow_live(self, n):
+        """the host mirror serve_counters reads covers n pods (new slots: not live)"""
+        mirror = getattr(self, "_live", None)
+        if mirror is not None and n > len(mirror):
+            self._live = np.concatenate([mirror, np.zeros(n - len(mirror), bool)])
+
+    def pods_events_json(self, keys, values, deleted=None, live=None, append=True):
+        """Instance-table events by key (mmp_pods_events_json): keys[i] is the instance id, values[i] its InstanceRecord JSON,
+        deleted[i] marks a deletion.  Returns (status, pod_idx, start_time, n_appended)."""
+        kblob, koff = self._pack(keys)
+        koff32 = koff.astype(np.int32)
+        blob, off = self._pack(values)
+        n = len(keys)
+        assert len(values) == n
+        deleted = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+        live = None if live is None else np.ascontiguousarray(live, dtype=np.uint8)
+        st = np.zeros(max(n, 1), np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        idx = np.full(max(n, 1), -1, np.int32)
+        n_app = C.c_int32(0)
+        self._ck(self.lib.mmp_pods_events_json(self.h, kblob, ptr(koff32), blob, ptr(off), n, ptr(deleted), ptr(live),
+                                               _lib.PEV_APPEND if append else 0, ptr(idx), ptr(st), ptr(status), C.byref(n_app)))
+        self.n_pods += n_app.value
+        self._grow_live(self.n_pods)
+        mirror = getattr(self, "_live", None)
+        if mirror is not None:
+            for i in range(n):  # in event order, as the library applies them
+                if status[i] != 0:
+                    continue
+                if deleted is not None and deleted[i]:
+                    mirror[idx[i]] = False
+                else:
+                    mirror[idx[i]] = True if live is None else bool(live[i])
+        return status[:n], idx[:n], st[:n], n_app.value
+
+    def registry_unresolved(self, max_models=None):
+        """The registry rows holding an entry whose id the instance table does not know (mmp_registry_unresolved), ascending.
+        Returns (rows, n_models, n_entries); max_models=None asks for all of them."""
+        nm, ne = C.c_int32(0), C.c_int64(0)
+        if max_models is None:
+            self._ck(self.lib.mmp_registry_unresolved(self.h, None, 0, C.byref(nm), C.byref(ne)))
+            max_models = nm.value
+        out = np.full(max(max_models, 1), -1, np.int32)
+        self._ck(self.lib.mmp_registry_unresolved(self.h, ptr(out) if max_models else None, int(max_models), C.byref(nm), C.byref(ne)))
+        return out[: min(max_models, nm.value)], nm.value, ne.value
+
     def load_type_names(self, names, unknown_type):
         blob, off = self._pack(names)
         off32 = off.astype(np.int32)
