@@ -172,6 +172,73 @@ struct FastSlot {
     std::atomic<uint32_t> seq{0};
 };
 
+// ---- the slot layout table: what each request call puts where in a slot's three buffers -----------------------------------------
+// A call rides a slot while every count it brings is within its row here (k*: the crossover thresholds — they decide latency);
+// beyond them it is staged through device scratch on the context's batch stream (seam_run).  A region is a byte range of `reqs`
+// (kSlotReq), `extra` (kSlotPool) or `outs` (kSlotOut); slot_after puts one behind another, 16-byte aligned, so regions of one row
+// cannot overlap; slot_fits says of EVERY region of a row that it is aligned and ends inside its buffer.
+enum SlotBuf { kSlotReq, kSlotPool, kSlotOut };
+constexpr size_t kSlotBufBytes[3] = {kFastN * sizeof(mmp_place_req), kFastExtra * sizeof(int32_t), kFastN * sizeof(mmp_place_out)};
+struct SlotRegion {
+    SlotBuf buf;
+    size_t off, bytes;
+};
+constexpr SlotRegion kStagedOnly{kSlotReq, 0, 0};  // an array of a call that never rides a slot
+constexpr SlotRegion slot_first(SlotBuf buf, size_t count, size_t elem) { return {buf, 0, count * elem}; }
+constexpr SlotRegion slot_after(SlotRegion prev, size_t count, size_t elem)
+{
+    return {prev.buf, (prev.off + prev.bytes + 15) & ~size_t(15), count * elem};
+}
+constexpr bool slot_fits(std::initializer_list<SlotRegion> regions)
+{
+    for (const SlotRegion &r : regions)
+        if (r.off % 16 != 0 || r.off + r.bytes > kSlotBufBytes[r.buf]) return false;
+    return true;
+}
+struct PlaceSlot {  // mmp_place_batch; mmp_place_batch_c writes calls of this size out as mmp_place_req rows
+    static constexpr int kN = kFastN, kExtra = kFastExtra;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), extra = slot_first(kSlotPool, kExtra, 4),
+                                outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out));
+    static_assert(slot_fits({reqs, extra, outs}), "place slot layout");
+};
+struct ServeSlot {  // mmp_serve_batch: everything a call brings is O(copies), 48 B + 16 B per listed copy
+    static constexpr int kN = 1024, kCounters = 8192, kExcl = 4096;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_serve_req)),
+                                counters = slot_after(reqs, kCounters, sizeof(mmp_serve_counter)),
+                                excl_pod = slot_first(kSlotPool, kExcl, 4), excl_time = slot_after(excl_pod, kExcl, 8),
+                                outs = slot_first(kSlotOut, kN, sizeof(mmp_serve_out));
+    static_assert(slot_fits({reqs, counters, excl_pod, excl_time, outs}), "serve slot layout");
+};
+struct GateSlot {  // mmp_gate_batch: as many 144-byte requests as the request buffer holds (1820; their 8-byte results fit with room)
+    static constexpr int kN = (int)(kSlotBufBytes[kSlotReq] / sizeof(mmp_gate_req)), kExcl = 4096, kExplicit = 4096;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_gate_req)), excl_pod = slot_first(kSlotPool, kExcl, 4),
+                                explicit_pool = slot_after(excl_pod, kExplicit, 4), excl_time = slot_after(explicit_pool, kExcl, 8),
+                                outs = slot_first(kSlotOut, kN, sizeof(mmp_gate_out));
+    static_assert(slot_fits({reqs, excl_pod, explicit_pool, excl_time, outs}), "gate slot layout");
+};
+struct MissSlot {  // mmp_miss_batch: the load-target half where mmp_place_batch has it, the guards' half behind
+    static constexpr int kN = 256, kPool = 2048;  // kPool: each of extras, exclusion pairs, explicit
+    static constexpr SlotRegion preqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), greqs = slot_after(preqs, kN, sizeof(mmp_gate_req)),
+                                extra = slot_first(kSlotPool, kPool, 4), excl_pod = slot_after(extra, kPool, 4),
+                                explicit_pool = slot_after(excl_pod, kPool, 4), excl_time = slot_after(explicit_pool, kPool, 8),
+                                pouts = slot_first(kSlotOut, kN, sizeof(mmp_place_out)), gouts = slot_after(pouts, kN, sizeof(mmp_gate_out));
+    static_assert(slot_fits({preqs, greqs, extra, excl_pod, explicit_pool, excl_time, pouts, gouts}), "miss slot layout");
+};
+struct RouteSlot {  // mmp_route_batch: the serve half shares the guards' exclusion pairs
+    static constexpr int kN = 256, kCounters = 4096, kExcl = 4096, kExplicit = 4096;
+    static constexpr SlotRegion greqs = slot_first(kSlotReq, kN, sizeof(mmp_gate_req)), sreqs = slot_after(greqs, kN, sizeof(mmp_serve_req)),
+                                counters = slot_after(sreqs, kCounters, sizeof(mmp_serve_counter)),
+                                excl_pod = slot_first(kSlotPool, kExcl, 4), explicit_pool = slot_after(excl_pod, kExplicit, 4),
+                                excl_time = slot_after(explicit_pool, kExcl, 8),
+                                gouts = slot_first(kSlotOut, kN, sizeof(mmp_gate_out)), souts = slot_after(gouts, kN, sizeof(mmp_serve_out));
+    static_assert(slot_fits({greqs, sreqs, counters, excl_pod, explicit_pool, excl_time, gouts, souts}), "route slot layout");
+};
+struct EvictSlot {  // mmp_evict_batch: as many 32-byte result rows as the result buffer holds (2048); their 16-byte requests fit
+    static constexpr int kN = (int)(kSlotBufBytes[kSlotOut] / sizeof(mmp_evict_out));
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_evict_req)), outs = slot_first(kSlotOut, kN, sizeof(mmp_evict_out));
+    static_assert(slot_fits({reqs, outs}), "evict slot layout");
+};
+
 // The environment switches (all MMP_*), read once per context at mmp_create (read_tuning).  The defaults are the product's routes;
 // the switches force routes for the tests and for comparison runs.
 struct Tuning {
@@ -728,13 +795,13 @@ struct PlaceCall {
     const mmp_gate_req *fused_greq = nullptr;
 };
 
-// the latency path's launch on slot `f` (called with the state lock held: the sequence number is bumped here)
-PlaceCall slot_call(FastSlot *f, const mmp_place_req *inline_req)
+// a place launch that announces completion through `done` (seam_run: a slot's flag and this launch's sequence number, or none)
+PlaceCall slot_call(const DoneFlag &done, const mmp_place_req *inline_req)
 {
     PlaceCall o;
-    o.done_flag = f->done;
-    o.done_seq = ++f->seq;
-    o.done_blocks = f->blocks;
+    o.done_flag = done.flag;
+    o.done_seq = done.seq;
+    o.done_blocks = done.blocks;
     o.inline_req = inline_req;
     return o;
 }
@@ -923,6 +990,213 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     HIP_TRY(c, hipGetLastError());
     if (is_split(r)) c->n_split.fetch_add(1, std::memory_order_relaxed);
     return MMP_OK;
+}
+
+// ---- the request seam: what the seven host-pointer request calls share (mmp_place_batch, _place_batch_c, _serve_batch, _gate_batch,
+// _miss_batch, _route_batch, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
+
+// [off, off + n) lies inside a pool of `len` entries (int64: off + n may pass INT32_MAX)
+inline bool in_pool(int32_t off, int32_t n, int32_t len) { return off >= 0 && n >= 0 && (int64_t)off + n <= len; }
+int bad_range(mmp_ctx *c, const char *call, int32_t i, const char *pool, int32_t off, int32_t n, int32_t len)
+{
+    return fail(c, MMP_EINVAL, "%s: request %d %s range [%d, +%d) outside the pool of %d", call, i, pool, off, n, len);
+}
+// The pool ranges of one request of each request struct, refused before any state is looked at.  Each entry point walks its requests
+// once and asks these of request i (inline: a request in range costs the comparisons alone).
+template <class Req>  // mmp_place_req, mmp_place_req_c
+inline int check_place_req(mmp_ctx *c, const char *call, int32_t i, const Req &r, int32_t n_extra)
+{
+    return in_pool(r.extra_off, r.n_extra, n_extra) ? MMP_OK : bad_range(c, call, i, "extra", r.extra_off, r.n_extra, n_extra);
+}
+inline int check_gate_req(mmp_ctx *c, const char *call, int32_t i, const mmp_gate_req &r, int32_t n_excl, int32_t n_explicit)
+{
+    if (!in_pool(r.excl_off, r.n_excl, n_excl)) return bad_range(c, call, i, "exclude", r.excl_off, r.n_excl, n_excl);
+    if (!in_pool(r.explicit_off, r.n_explicit, n_explicit)) return bad_range(c, call, i, "explicit", r.explicit_off, r.n_explicit, n_explicit);
+    return MMP_OK;
+}
+inline int check_serve_req(mmp_ctx *c, const char *call, int32_t i, const mmp_serve_req &r, int32_t n_excl, int32_t n_counters)
+{
+    if (!in_pool(r.excl_off, r.n_excl, n_excl)) return bad_range(c, call, i, "exclude", r.excl_off, r.n_excl, n_excl);
+    if (!in_pool(r.cnt_off, r.n_cnt, n_counters)) return bad_range(c, call, i, "counter", r.cnt_off, r.n_cnt, n_counters);
+    return MMP_OK;
+}
+// the two halves of one request (mmp_miss_batch, mmp_route_batch) name one model
+inline int check_same_model(mmp_ctx *c, const char *call, int32_t i, int32_t gate_model, int32_t other_model)
+{
+    return gate_model == other_model ? MMP_OK : fail(c, MMP_EINVAL, "%s: request %d names two models", call, i);
+}
+
+// The state a decision call reads, looked at under the lock it launches under (seam_run).  whole_table: not on a pod-axis shard
+// context, whose snapshot holds a slice of the instances only (the load targets go through mmp_shard_place_phase_dev there).
+int need_snapshot(mmp_ctx *c, bool whole_table)
+{
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (whole_table && c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard (the mmp_shard_* calls decide there)");
+    return MMP_OK;
+}
+
+// The kernels' argument blocks as far as the context fills them; the caller binds its own arrays and the completion flag.
+GateArgs gate_args(mmp_ctx *c, int32_t n, int64_t now, int64_t in_use_expiry)
+{
+    GateArgs A{};
+    A.models = c->models.as<mmp_model_row>();
+    A.ent_pod = c->ent_pod.as<int32_t>();
+    A.ent_time = c->ent_time.as<int64_t>();
+    A.pods = c->sb[c->cur].pods.as<mmp_pod_row>();
+    A.allowed = cur_side(c).d_allowed.as<uint64_t>();
+    A.has_allowed = cur_side(c).d_has_allowed.as<uint8_t>();
+    A.stats = cur_side(c).stats_acc.as<StatsAcc>();
+    A.tstats = cur_side(c).tstats.as<StatsAcc>();
+    A.T_rows = std::max(c->n_types, 1);
+    A.n = n;
+    A.n_models = c->n_models;
+    A.P = c->snap.P;
+    A.W = c->snap.W;
+    A.T = c->n_types;
+    A.now = now;
+    A.in_use_expiry = in_use_expiry;
+    A.min_space = c->cfg.min_space_units;
+    A.min_churn = c->cfg.min_churn_age_ms;
+    A.done = DoneFlag{nullptr, nullptr, 0};
+    return A;
+}
+ServeArgs serve_args(mmp_ctx *c, int32_t n, int64_t now)
+{
+    ServeArgs A{};
+    A.models = c->models.as<mmp_model_row>();
+    A.ent_pod = c->ent_pod.as<int32_t>();
+    A.ent_time = c->ent_time.as<int64_t>();
+    A.n = n;
+    A.n_models = c->n_models;
+    A.P = c->snap.P;
+    A.now = now;
+    A.done = DoneFlag{nullptr, nullptr, 0};
+    return A;
+}
+EvictArgs evict_args(mmp_ctx *c, int32_t n, int64_t now)
+{
+    EvictArgs A;  // (every field is set: the arrays and the flag by the caller)
+    A.seg_off = c->c_seg.as<int32_t>();
+    A.last_used = c->c_lu.as<int64_t>();
+    A.weight = c->c_wt.as<int32_t>();
+    A.capacity = c->c_cap.as<int64_t>();
+    A.n = n;
+    A.n_caches = c->n_caches;
+    A.now = now;
+    A.done = DoneFlag{nullptr, nullptr, 0};
+    return A;
+}
+// eight lanes per evaluation while the deques are short, sixteen otherwise (aux_kernels.hpp)
+void evict_launch(mmp_ctx *c, const EvictArgs &A, int32_t n, hipStream_t st)
+{
+    if (c->cache_entries <= (int64_t)24 * std::max(c->n_caches, 1))
+        hipLaunchKernelGGL(evict_batch_kernel<8>, dim3(div_up(n, kEvBlock / 8)), dim3(kEvBlock), 0, st, A);
+    else
+        hipLaunchKernelGGL(evict_batch_kernel<16>, dim3(div_up(n, kEvBlock / 16)), dim3(kEvBlock), 0, st, A);
+}
+
+// One input or output array of a request call: the caller's array, its region of a slot (the layout table beside FastSlot), and the
+// scratch buffer that stages it when the call does not ride a slot.
+struct SeamIo {
+    void *host;  // (an input is only read)
+    size_t bytes;
+    SlotRegion at;
+    DevBuf *stage;
+    void *dev = nullptr;  // where the kernels find it: seam_run sets it before the launch body runs
+    template <class T>
+    T *as() const { return static_cast<T *>(dev); }
+};
+template <class T>
+SeamIo seam_io(const T *host, int32_t count, const SlotRegion &at, DevBuf &stage)
+{
+    return SeamIo{const_cast<T *>(host), (size_t)count * sizeof(T), at, &stage};
+}
+template <class T>  // an array of a call that always rides a slot
+SeamIo seam_io(const T *host, int32_t count, const SlotRegion &at)
+{
+    return SeamIo{const_cast<T *>(host), (size_t)count * sizeof(T), at, nullptr};
+}
+inline void *slot_ptr(FastSlot *f, const SlotRegion &r)
+{
+    char *base = r.buf == kSlotReq ? reinterpret_cast<char *>(f->reqs) : r.buf == kSlotPool ? reinterpret_cast<char *>(f->extra) : reinterpret_cast<char *>(f->outs);
+    return base + r.off;
+}
+
+// The two paths of a request call.  `check()` refuses the call when the state it needs is not there; `launch(stream, done, on_slot)`
+// binds the arrays' device addresses (SeamIo::dev) and enqueues the kernels, the last of them announcing `done`; on_slot is
+// std::true_type on the latency path, so what a body does there only costs nothing elsewhere.
+
+// The latency path (slot_acquire): the arrays are copied into the slot's pinned, device-mapped buffers, the kernels run on the slot's
+// own stream and the host spins on the slot's completion flag: no staging copies, no batch lock, no kernel timing.  The state lock is
+// held SHARED over check, the sequence number's bump and the enqueue — quiesce_decisions relies on that.  The number is bumped before
+// the body runs: a body that fails leaves it ahead of every kernel, which costs the next quiescer a stream synchronisation (slot_wait's
+// fallback) and never hides a kernel in flight.  Inlined into each entry point: the array lists are unrolled and the regions' addresses
+// folded there.
+template <class Check, class Launch>
+__attribute__((always_inline)) inline int seam_slot(mmp_ctx *c, std::initializer_list<SeamIo *> ins, std::initializer_list<SeamIo *> outs,
+                                                    Check &check, Launch &launch)
+{
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    std::unique_lock<std::mutex> fl;
+    FastSlot *f = slot_acquire(c, fl);
+    for (SeamIo *io : ins) {
+        io->dev = slot_ptr(f, io->at);
+        if (io->bytes) memcpy(io->dev, io->host, io->bytes);
+    }
+    for (SeamIo *io : outs) io->dev = slot_ptr(f, io->at);
+    {
+        std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published state + enqueue
+        if (const int rc = check()) return rc;
+        if (const int rc = launch(f->stream, DoneFlag{f->done, f->blocks, ++f->seq}, std::true_type{})) return rc;
+    }
+    HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
+    for (SeamIo *io : outs) memcpy(io->host, io->dev, io->bytes);
+    return MMP_OK;
+}
+
+// The staged path, n == 0 included: batch_mu owns c->stream and the scratch for the whole call, and every writer of the state the
+// call reads (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath, so the state is
+// checked first.  The state lock c->mu is NOT held, so that latency-path calls keep flowing — except by the place calls
+// (kLaunchExcl; they answer n == 0 themselves), which hold it exclusive over their check and place_launch.  Kernel time (KT_*)
+// brackets the launches alone, not the copies.
+template <bool kLaunchExcl, class Check, class Launch>
+__attribute__((noinline)) int seam_staged(mmp_ctx *c, int32_t n, std::initializer_list<SeamIo *> ins, std::initializer_list<SeamIo *> outs,
+                                          Check &check, Launch &launch)
+{
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if constexpr (!kLaunchExcl)
+        if (const int rc = check()) return rc;
+    if (n == 0) return MMP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    for (const auto &side : {ins, outs})
+        for (SeamIo *io : side) {
+            HIP_TRY(c, io->stage->ensure(std::max<size_t>(io->bytes, 1)));  // (an empty pool still gets an address)
+            io->dev = io->stage->p;
+        }
+    for (SeamIo *io : ins)
+        if (io->bytes) HIP_TRY(c, hipMemcpyAsync(io->dev, io->host, io->bytes, hipMemcpyHostToDevice, st));
+    {
+        std::unique_lock<std::shared_mutex> g(c->mu, std::defer_lock);
+        if constexpr (kLaunchExcl) {
+            g.lock();
+            if (const int rc = check()) return rc;
+        }
+        KT_BEGIN(c, st);
+        if (const int rc = launch(st, DoneFlag{nullptr, nullptr, 0}, std::false_type{})) return rc;
+        KT_END(c, st);
+    }
+    for (SeamIo *io : outs) HIP_TRY(c, hipMemcpyAsync(io->host, io->dev, io->bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    return MMP_OK;
+}
+
+template <bool kLaunchExcl, class Check, class Launch>
+__attribute__((always_inline)) inline int seam_run(mmp_ctx *c, int32_t n, bool rides_slot, std::initializer_list<SeamIo *> ins,
+                                                   std::initializer_list<SeamIo *> outs, Check &&check, Launch &&launch)
+{
+    return rides_slot ? seam_slot(c, ins, outs, check, launch) : seam_staged<kLaunchExcl>(c, n, ins, outs, check, launch);
 }
 
 }  // namespace
@@ -4304,9 +4578,8 @@ try {
     if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
         return fail(c, MMP_EINVAL, "mmp_place_batch_c: bad argument");
     for (int32_t i = 0; i < n; i++)
-        if (reqs[i].n_extra < 0 || reqs[i].extra_off < 0 || (int64_t)reqs[i].extra_off + reqs[i].n_extra > n_extra)
-            return fail(c, MMP_EINVAL, "mmp_place_batch_c: request %d extra range out of bounds", i);
-    if (n <= kFastN && n_extra <= kFastExtra) {
+        if (const int rc = check_place_req(c, "mmp_place_batch_c", i, reqs[i], n_extra)) return rc;
+    if (n <= PlaceSlot::kN && n_extra <= PlaceSlot::kExtra) {
         // a handful of requests: the latency path of mmp_place_batch (slots, the single-decision kernels, the resident kernel) on
         // the same decisions written out as mmp_place_req rows
         std::vector<mmp_place_req> full((size_t)n);
@@ -4327,29 +4600,14 @@ try {
         }
         return mmp_place_batch(c, full.data(), n, extra_pool, n_extra, now, outs);
     }
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_place_req_c)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_place_out)));
-    HIP_TRY(c, c->s_extra.ensure((size_t)std::max(n_extra, 1) * 4));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, reqs, (size_t)n * sizeof(mmp_place_req_c), hipMemcpyHostToDevice, st));
-    if (n_extra) HIP_TRY(c, hipMemcpyAsync(c->s_extra.p, extra_pool, (size_t)n_extra * 4, hipMemcpyHostToDevice, st));
-    {
-        std::lock_guard<std::shared_mutex> g(c->mu);
-        if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-        if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-        PlaceCall o;
-        o.caller = caller;
-        KT_BEGIN(c, st);
-        const int rc = place_launch(c, c->s_reqs.p, n, c->s_extra.p, now, c->s_outs.p, st, o);
-        if (rc != MMP_OK) return rc;
-        KT_END(c, st);
-    }
-    HIP_TRY(c, hipMemcpyAsync(outs, c->s_outs.p, (size_t)n * sizeof(mmp_place_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
+    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs), x = seam_io(extra_pool, n_extra, kStagedOnly, c->s_extra),
+           o = seam_io(outs, n, kStagedOnly, c->s_outs);
+    return seam_run<true>(c, n, false, {&q, &x}, {&o}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &, auto) {
+                        PlaceCall call;
+                        call.caller = caller;
+                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
+                    });
 } MMP_CATCH(c, "mmp_place_batch_c")
 
 int mmp_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
@@ -4358,186 +4616,56 @@ try {
     if (!c || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
         return fail(c, MMP_EINVAL, "mmp_place_batch: bad argument");
     for (int32_t i = 0; i < n; i++)
-        if (reqs[i].n_extra < 0 || reqs[i].extra_off < 0 || (int64_t)reqs[i].extra_off + reqs[i].n_extra > n_extra)
-            return fail(c, MMP_EINVAL, "mmp_place_batch: request %d extra range out of bounds", i);
+        if (const int rc = check_place_req(c, "mmp_place_batch", i, reqs[i], n_extra)) return rc;
     if (n == 0) {
         std::lock_guard<std::shared_mutex> g(c->mu);
-        if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-        if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-        return MMP_OK;
+        return need_snapshot(c, true);
     }
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-
-    if (n == 1 && reqs[0].n_extra == 0 && c->res.enabled && now >= 0 && (now >> kResidentNowBits) == 0) {
-        // a single request without exclusions of its own: the resident kernel, no launch at all
+    const bool lone = n == 1 && reqs[0].n_extra == 0;  // a single request without exclusions of its own
+    if (lone && c->res.enabled && now >= 0 && (now >> kResidentNowBits) == 0) {
+        // the resident kernel, no launch at all
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
         const int rc = resident_place(c, reqs[0], now, outs);
         if (rc != kResidentFallback) return rc;
     }
-    if (n <= kFastN && n_extra <= kFastExtra) {
-        // latency path: the kernel reads the requests from, and writes the results to, pinned host
-        // memory over the fabric — no staging copies, no contention with batches on c->stream
-        std::unique_lock<std::mutex> fl;
-        FastSlot *f = slot_acquire(c, fl);
-        memcpy(f->reqs, reqs, (size_t)n * sizeof(mmp_place_req));
-        if (n_extra) memcpy(f->extra, extra_pool, (size_t)n_extra * sizeof(int32_t));
-        {
-            std::shared_lock<std::shared_mutex> g(c->mu);
-            if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-            if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-            const int rc = place_launch(c, f->reqs, n, f->extra, now, f->outs, f->stream,
-                                        slot_call(f, (n == 1 && reqs[0].n_extra == 0) ? &reqs[0] : nullptr));
-            if (rc != MMP_OK) return rc;
-        }
-        HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-        memcpy(outs, f->outs, (size_t)n * sizeof(mmp_place_out));
-        return MMP_OK;
-    }
-
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_place_req)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_place_out)));
-    HIP_TRY(c, c->s_extra.ensure((size_t)std::max(n_extra, 1) * 4));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, reqs, (size_t)n * sizeof(mmp_place_req), hipMemcpyHostToDevice, st));
-    if (n_extra) HIP_TRY(c, hipMemcpyAsync(c->s_extra.p, extra_pool, (size_t)n_extra * 4, hipMemcpyHostToDevice, st));
-    {
-        std::lock_guard<std::shared_mutex> g(c->mu);
-        if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-        if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard: use mmp_shard_place_phase_dev");
-        KT_BEGIN(c, st);
-        const int rc = place_launch(c, c->s_reqs.p, n, c->s_extra.p, now, c->s_outs.p, st);
-        if (rc != MMP_OK) return rc;
-        KT_END(c, st);
-    }
-    HIP_TRY(c, hipMemcpyAsync(outs, c->s_outs.p, (size_t)n * sizeof(mmp_place_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
+    SeamIo q = seam_io(reqs, n, PlaceSlot::reqs, c->s_reqs), x = seam_io(extra_pool, n_extra, PlaceSlot::extra, c->s_extra),
+           o = seam_io(outs, n, PlaceSlot::outs, c->s_outs);
+    return seam_run<true>(c, n, n <= PlaceSlot::kN && n_extra <= PlaceSlot::kExtra, {&q, &x}, {&o}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        // (on a slot a lone request rides in the kernel arguments)
+                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, on_slot && lone ? &reqs[0] : nullptr));
+                    });
 } MMP_CATCH(c, "mmp_place_batch")
 
+// What the LB's one call per request (MM.java:4315) needs: on a slot, one launch and the completion flag.
 int mmp_serve_batch(mmp_ctx *c, const mmp_serve_req *reqs, int32_t n, const mmp_serve_counter *counters, int32_t n_counters,
                     const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, int64_t now, mmp_serve_out *outs)
 try {
     if (!c || n < 0 || n_excl < 0 || n_counters < 0 || (n > 0 && (!reqs || !outs)) || (n_counters > 0 && !counters) ||
         (n_excl > 0 && (!excl_pod || !excl_time)))
         return fail(c, MMP_EINVAL, "mmp_serve_batch: bad argument");
-    for (int32_t i = 0; i < n; i++) {
-        if (reqs[i].n_excl < 0 || reqs[i].excl_off < 0 || (int64_t)reqs[i].excl_off + reqs[i].n_excl > n_excl)
-            return fail(c, MMP_EINVAL, "mmp_serve_batch: request %d exclude range out of bounds", i);
-        if (reqs[i].n_cnt < 0 || reqs[i].cnt_off < 0 || (int64_t)reqs[i].cnt_off + reqs[i].n_cnt > n_counters)
-            return fail(c, MMP_EINVAL, "mmp_serve_batch: request %d counter range out of bounds", i);
-    }
-    auto args = [&](int32_t cnt) {
-        ServeArgs A{};
-        A.models = c->models.as<mmp_model_row>();
-        A.ent_pod = c->ent_pod.as<int32_t>();
-        A.ent_time = c->ent_time.as<int64_t>();
-        A.n = cnt;
-        A.n_models = c->n_models;
-        A.P = c->snap.P;
-        A.now = now;
-        A.done = DoneFlag{nullptr, nullptr, 0};
-        return A;
-    };
-    // latency path (see slot_acquire): the slot's pinned buffers take the requests, the counters behind them, and the
-    // exclusion pairs in the int pool; one launch + the completion flag, no staging copies — what the LB's one call per
-    // request (MM.java:4315) needs.  Everything a call brings is O(copies): 48 B + 16 B per listed copy.
-    constexpr int kSlotReqs = 1024, kSlotCounters = 8192, kSlotExcl = kFastExtra / 4;
-    static_assert((size_t)kSlotReqs * sizeof(mmp_serve_req) + (size_t)kSlotCounters * sizeof(mmp_serve_counter) <= (size_t)kFastN * sizeof(mmp_place_req),
-                  "requests + counters fit the slot's request buffer");
-    static_assert((size_t)kSlotReqs * sizeof(mmp_serve_out) <= (size_t)kFastN * sizeof(mmp_place_out), "results fit the slot's result buffer");
-    if (n > 0 && n <= kSlotReqs && n_counters <= kSlotCounters && n_excl <= kSlotExcl) {
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        std::unique_lock<std::mutex> fl;
-        FastSlot *f = slot_acquire(c, fl);
-        char *rb = reinterpret_cast<char *>(f->reqs);
-        memcpy(rb, reqs, (size_t)n * sizeof(mmp_serve_req));
-        mmp_serve_counter *cb = reinterpret_cast<mmp_serve_counter *>(rb + (size_t)kSlotReqs * sizeof(mmp_serve_req));
-        if (n_counters) memcpy(cb, counters, (size_t)n_counters * sizeof(mmp_serve_counter));
-        int32_t *pool = f->extra;
-        if (n_excl) {
-            memcpy(pool, excl_pod, (size_t)n_excl * 4);
-            memcpy(pool + 2 * kSlotExcl, excl_time, (size_t)n_excl * 8);
-        }
-        {
-            std::shared_lock<std::shared_mutex> g(c->mu);  // capture the registry view + enqueue
-            if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-            ServeArgs A = args(n);
-            A.reqs = reinterpret_cast<const mmp_serve_req *>(rb);
-            A.counters = cb;
-            A.excl_pod = pool;
-            A.excl_time = reinterpret_cast<const int64_t *>(pool + 2 * kSlotExcl);
-            A.outs = reinterpret_cast<mmp_serve_out *>(f->outs);
-            A.done = DoneFlag{f->done, f->blocks, ++f->seq};
-            HIP_TRY(c, order_after_registry(c, f->stream));
-            hipLaunchKernelGGL(serve_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, f->stream, A);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-        memcpy(outs, f->outs, (size_t)n * sizeof(mmp_serve_out));
-        return MMP_OK;
-    }
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (n == 0) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_serve_req)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_serve_out)));
-    HIP_TRY(c, c->s_a.ensure((size_t)std::max(n_counters, 1) * sizeof(mmp_serve_counter)));
-    HIP_TRY(c, c->s_c.ensure((size_t)std::max(n_excl, 1) * 4));
-    HIP_TRY(c, c->s_d.ensure((size_t)std::max(n_excl, 1) * 8));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, reqs, (size_t)n * sizeof(mmp_serve_req), hipMemcpyHostToDevice, st));
-    if (n_counters) HIP_TRY(c, hipMemcpyAsync(c->s_a.p, counters, (size_t)n_counters * sizeof(mmp_serve_counter), hipMemcpyHostToDevice, st));
-    if (n_excl) {
-        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, excl_pod, (size_t)n_excl * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->s_d.p, excl_time, (size_t)n_excl * 8, hipMemcpyHostToDevice, st));
-    }
-    ServeArgs A = args(n);
-    A.reqs = c->s_reqs.as<mmp_serve_req>();
-    A.counters = c->s_a.as<mmp_serve_counter>();
-    A.excl_pod = c->s_c.as<int32_t>();
-    A.excl_time = c->s_d.as<int64_t>();
-    A.outs = c->s_outs.as<mmp_serve_out>();
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(serve_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(outs, c->s_outs.p, (size_t)n * sizeof(mmp_serve_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
+    for (int32_t i = 0; i < n; i++)
+        if (const int rc = check_serve_req(c, "mmp_serve_batch", i, reqs[i], n_excl, n_counters)) return rc;
+    using L = ServeSlot;
+    SeamIo q = seam_io(reqs, n, L::reqs, c->s_reqs), cnt = seam_io(counters, n_counters, L::counters, c->s_a),
+           xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c), xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d),
+           o = seam_io(outs, n, L::outs, c->s_outs);
+    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_counters <= L::kCounters && n_excl <= L::kExcl, {&q, &cnt, &xp, &xt}, {&o},
+                    [&] { return need_snapshot(c, false); },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        ServeArgs A = serve_args(c, n, now);
+                        A.reqs = q.as<mmp_serve_req>();
+                        A.counters = cnt.as<mmp_serve_counter>();
+                        A.excl_pod = xp.as<int32_t>();
+                        A.excl_time = xt.as<int64_t>();
+                        A.outs = o.as<mmp_serve_out>();
+                        A.done = done;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(serve_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
 } MMP_CATCH(c, "mmp_serve_batch")
-
-namespace {
-GateArgs gate_args(mmp_ctx *c, int32_t n, int64_t now, int64_t in_use_expiry)
-{
-    GateArgs A{};
-    A.models = c->models.as<mmp_model_row>();
-    A.ent_pod = c->ent_pod.as<int32_t>();
-    A.ent_time = c->ent_time.as<int64_t>();
-    A.pods = c->sb[c->cur].pods.as<mmp_pod_row>();
-    A.allowed = cur_side(c).d_allowed.as<uint64_t>();
-    A.has_allowed = cur_side(c).d_has_allowed.as<uint8_t>();
-    A.stats = cur_side(c).stats_acc.as<StatsAcc>();
-    A.tstats = cur_side(c).tstats.as<StatsAcc>();
-    A.T_rows = std::max(c->n_types, 1);
-    A.n = n;
-    A.n_models = c->n_models;
-    A.P = c->snap.P;
-    A.W = c->snap.W;
-    A.T = c->n_types;
-    A.now = now;
-    A.in_use_expiry = in_use_expiry;
-    A.min_space = c->cfg.min_space_units;
-    A.min_churn = c->cfg.min_churn_age_ms;
-    A.done = DoneFlag{nullptr, nullptr, 0};
-    return A;
-}
-}  // namespace
 
 int mmp_gate_batch(mmp_ctx *c, const mmp_gate_req *reqs, int32_t n, const int32_t *excl_pod, const int64_t *excl_time,
                    int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
@@ -4546,77 +4674,27 @@ try {
     if (!c || n < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!reqs || !outs)) ||
         (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
         return fail(c, MMP_EINVAL, "mmp_gate_batch: bad argument");
-    for (int32_t i = 0; i < n; i++) {
-        const mmp_gate_req &r = reqs[i];
-        if (r.n_excl < 0 || r.excl_off < 0 || (int64_t)r.excl_off + r.n_excl > n_excl || r.n_explicit < 0 ||
-            r.explicit_off < 0 || (int64_t)r.explicit_off + r.n_explicit > n_explicit)
-            return fail(c, MMP_EINVAL, "mmp_gate_batch: request %d pool range out of bounds", i);
-    }
-    constexpr int kGatePool = kFastExtra / 4;  // the slot's int pool holds excl_pod | explicit | excl_time (as int64)
-    if (n > 0 && (size_t)n * sizeof(mmp_gate_req) <= kFastN * sizeof(mmp_place_req) &&
-        (size_t)n * sizeof(mmp_gate_out) <= kFastN * sizeof(mmp_place_out) && n_excl <= kGatePool && n_explicit <= kGatePool) {
-        // latency path (see slot_acquire)
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        std::unique_lock<std::mutex> fl;
-        FastSlot *f = slot_acquire(c, fl);
-        memcpy(f->reqs, reqs, (size_t)n * sizeof(mmp_gate_req));
-        int32_t *pool = f->extra;
-        if (n_excl) {
-            memcpy(pool, excl_pod, (size_t)n_excl * 4);
-            memcpy(pool + 2 * kGatePool, excl_time, (size_t)n_excl * 8);
-        }
-        if (n_explicit) memcpy(pool + kGatePool, explicit_pool, (size_t)n_explicit * 4);
-        {
-            std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published snapshot + enqueue
-            if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-            GateArgs A = gate_args(c, n, now, in_use_expiry);
-            A.reqs = reinterpret_cast<const mmp_gate_req *>(f->reqs);
-            A.excl_pod = pool;
-            A.explicit_pool = pool + kGatePool;
-            A.excl_time = reinterpret_cast<const int64_t *>(pool + 2 * kGatePool);
-            A.outs = reinterpret_cast<mmp_gate_out *>(f->outs);
-            A.done = DoneFlag{f->done, f->blocks, ++f->seq};
-            HIP_TRY(c, order_after_registry(c, f->stream));
-            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, f->stream, A);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-        memcpy(outs, f->outs, (size_t)n * sizeof(mmp_gate_out));
-        return MMP_OK;
-    }
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (n == 0) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_gate_req)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_gate_out)));
-    HIP_TRY(c, c->s_a.ensure((size_t)std::max(n_explicit, 1) * 4));
-    HIP_TRY(c, c->s_c.ensure((size_t)std::max(n_excl, 1) * 4));
-    HIP_TRY(c, c->s_d.ensure((size_t)std::max(n_excl, 1) * 8));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, reqs, (size_t)n * sizeof(mmp_gate_req), hipMemcpyHostToDevice, st));
-    if (n_explicit) HIP_TRY(c, hipMemcpyAsync(c->s_a.p, explicit_pool, (size_t)n_explicit * 4, hipMemcpyHostToDevice, st));
-    if (n_excl) {
-        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, excl_pod, (size_t)n_excl * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->s_d.p, excl_time, (size_t)n_excl * 8, hipMemcpyHostToDevice, st));
-    }
-    GateArgs A = gate_args(c, n, now, in_use_expiry);
-    A.reqs = c->s_reqs.as<mmp_gate_req>();
-    A.excl_pod = c->s_c.as<int32_t>();
-    A.excl_time = c->s_d.as<int64_t>();
-    A.explicit_pool = c->s_a.as<int32_t>();
-    A.outs = c->s_outs.as<mmp_gate_out>();
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(outs, c->s_outs.p, (size_t)n * sizeof(mmp_gate_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
+    for (int32_t i = 0; i < n; i++)
+        if (const int rc = check_gate_req(c, "mmp_gate_batch", i, reqs[i], n_excl, n_explicit)) return rc;
+    using L = GateSlot;
+    SeamIo q = seam_io(reqs, n, L::reqs, c->s_reqs), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           o = seam_io(outs, n, L::outs, c->s_outs);
+    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_excl <= L::kExcl && n_explicit <= L::kExplicit, {&q, &xp, &xt, &ex}, {&o},
+                    [&] { return need_snapshot(c, false); },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        GateArgs A = gate_args(c, n, now, in_use_expiry);
+                        A.reqs = q.as<mmp_gate_req>();
+                        A.excl_pod = xp.as<int32_t>();
+                        A.excl_time = xt.as<int64_t>();
+                        A.explicit_pool = ex.as<int32_t>();
+                        A.outs = o.as<mmp_gate_out>();
+                        A.done = done;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
 } MMP_CATCH(c, "mmp_gate_batch")
 
 int mmp_miss_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_place_req *preqs, int32_t n, const int32_t *excl_pod,
@@ -4627,72 +4705,44 @@ try {
         (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
         return fail(c, MMP_EINVAL, "mmp_miss_batch: bad argument");
     for (int32_t i = 0; i < n; i++) {
-        const mmp_gate_req &g = greqs[i];
-        const mmp_place_req &r = preqs[i];
-        if (g.n_excl < 0 || g.excl_off < 0 || (int64_t)g.excl_off + g.n_excl > n_excl || g.n_explicit < 0 || g.explicit_off < 0 ||
-            (int64_t)g.explicit_off + g.n_explicit > n_explicit)
-            return fail(c, MMP_EINVAL, "mmp_miss_batch: request %d pool range out of bounds", i);
-        if (r.n_extra < 0 || r.extra_off < 0 || (int64_t)r.extra_off + r.n_extra > n_extra)
-            return fail(c, MMP_EINVAL, "mmp_miss_batch: request %d extra range [%d, +%d) outside the pool of %d", i, r.extra_off, r.n_extra, n_extra);
-        if (g.model != r.model) return fail(c, MMP_EINVAL, "mmp_miss_batch: request %d names two models", i);
+        if (const int rc = check_gate_req(c, "mmp_miss_batch", i, greqs[i], n_excl, n_explicit)) return rc;
+        if (const int rc = check_place_req(c, "mmp_miss_batch", i, preqs[i], n_extra)) return rc;
+        if (const int rc = check_same_model(c, "mmp_miss_batch", i, greqs[i].model, preqs[i].model)) return rc;
     }
     if (n == 0) return MMP_OK;
-    // One latency slot, TWO launches on its stream (the guards, then the load targets: in stream order, so the second kernel's
-    // completion flag covers both), ONE wait: what two calls did in two launch-wait-return round trips.
-    constexpr int kMissN = 256, kMissPool = kFastExtra / 8;  // place extras | gate excl_pod | gate explicit | gate excl_time (2 ints each)
-    constexpr size_t kMissGreqOff = (size_t)kMissN * sizeof(mmp_place_req), kMissGoutOff = (size_t)kMissN * sizeof(mmp_place_out);
-    static_assert(kMissGreqOff + (size_t)kMissN * sizeof(mmp_gate_req) <= (size_t)kFastN * sizeof(mmp_place_req), "miss slot layout");
-    static_assert(kMissGoutOff + (size_t)kMissN * sizeof(mmp_gate_out) <= (size_t)kFastN * sizeof(mmp_place_out), "miss slot results");
-    if (n > kMissN || n_extra > kMissPool || n_excl > kMissPool || n_explicit > kMissPool) {  // large batches: the two calls
+    using L = MissSlot;
+    if (n > L::kN || n_extra > L::kPool || n_excl > L::kPool || n_explicit > L::kPool) {  // large batches: the two calls
         const int rc = mmp_gate_batch(c, greqs, n, excl_pod, excl_time, n_excl, explicit_pool, n_explicit, now, in_use_expiry, gouts);
         return rc != MMP_OK ? rc : mmp_place_batch(c, preqs, n, extra_pool, n_extra, now, pouts);
     }
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    std::unique_lock<std::mutex> fl;
-    FastSlot *f = slot_acquire(c, fl);
-    char *base = reinterpret_cast<char *>(f->reqs), *obase = reinterpret_cast<char *>(f->outs);
-    memcpy(base, preqs, (size_t)n * sizeof(mmp_place_req));
-    memcpy(base + kMissGreqOff, greqs, (size_t)n * sizeof(mmp_gate_req));
-    int32_t *pool = f->extra;
-    if (n_extra) memcpy(pool, extra_pool, (size_t)n_extra * 4);
-    if (n_excl) {
-        memcpy(pool + kMissPool, excl_pod, (size_t)n_excl * 4);
-        memcpy(pool + 3 * kMissPool, excl_time, (size_t)n_excl * 8);
-    }
-    if (n_explicit) memcpy(pool + 2 * kMissPool, explicit_pool, (size_t)n_explicit * 4);
-    {
-        std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published snapshot + enqueue
-        if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-        if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard");
-        GateArgs G = gate_args(c, n, now, in_use_expiry);
-        G.reqs = reinterpret_cast<const mmp_gate_req *>(base + kMissGreqOff);
-        G.excl_pod = pool + kMissPool;
-        G.explicit_pool = pool + 2 * kMissPool;
-        G.excl_time = reinterpret_cast<const int64_t *>(pool + 3 * kMissPool);
-        G.outs = reinterpret_cast<mmp_gate_out *>(obase + kMissGoutOff);
-        G.done = DoneFlag{nullptr, nullptr, 0};
-        const bool one = n == 1 && preqs[0].n_extra == 0;
-        if (one) {  // ONE launch: both requests in the kernel arguments, guards and load target on two wavefronts
-            PlaceCall o = slot_call(f, &preqs[0]);
-            o.fused_gate = &G;
-            o.fused_greq = &greqs[0];
-            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream, o);
-            if (rc != MMP_OK) return rc;
-        } else {
-            HIP_TRY(c, order_after_registry(c, f->stream));
-            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, f->stream, G);
-            HIP_TRY(c, hipGetLastError());
-            const int rc = place_launch(c, f->reqs, n, pool, now, f->outs, f->stream,
-                                        slot_call(f, (n == 1 && preqs[0].n_extra == 0) ? &preqs[0] : nullptr));
-            if (rc != MMP_OK) return rc;
-        }
-    }
-    HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-    memcpy(pouts, obase, (size_t)n * sizeof(mmp_place_out));
-    memcpy(gouts, obase + kMissGoutOff, (size_t)n * sizeof(mmp_gate_out));
-    return MMP_OK;
+    // One latency slot, TWO launches on its stream (the guards, then the load targets: in stream order, so the second kernel's
+    // completion flag covers both), ONE wait: what two calls did in two launch-wait-return round trips.  Always on a slot: the staged
+    // path is the two calls above.
+    SeamIo pq = seam_io(preqs, n, L::preqs), gq = seam_io(greqs, n, L::greqs), x = seam_io(extra_pool, n_extra, L::extra),
+           xp = seam_io(excl_pod, n_excl, L::excl_pod), xt = seam_io(excl_time, n_excl, L::excl_time),
+           ex = seam_io(explicit_pool, n_explicit, L::explicit_pool), po = seam_io(pouts, n, L::pouts), go = seam_io(gouts, n, L::gouts);
+    return seam_run<false>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex}, {&po, &go}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        GateArgs G = gate_args(c, n, now, in_use_expiry);
+                        G.reqs = gq.as<mmp_gate_req>();
+                        G.excl_pod = xp.as<int32_t>();
+                        G.excl_time = xt.as<int64_t>();
+                        G.explicit_pool = ex.as<int32_t>();
+                        G.outs = go.as<mmp_gate_out>();
+                        if (n == 1 && preqs[0].n_extra == 0) {  // ONE launch: both requests in the kernel arguments, guards and load target on two wavefronts
+                            PlaceCall call = slot_call(done, &preqs[0]);
+                            call.fused_gate = &G;
+                            call.fused_greq = &greqs[0];
+                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
+                        }
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
+                        HIP_TRY(c, hipGetLastError());
+                        return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
+                    });
 } MMP_CATCH(c, "mmp_miss_batch")
 
+// The per-request seam (invokeModel asks for ONE route at a time): the guards and the serve target of every request in one launch.
 int mmp_route_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_serve_req *sreqs, int32_t n, const mmp_serve_counter *counters,
                     int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
                     const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts,
@@ -4702,130 +4752,63 @@ try {
         (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
         return fail(c, MMP_EINVAL, "mmp_route_batch: bad argument");
     for (int32_t i = 0; i < n; i++) {
-        const mmp_gate_req &g = greqs[i];
-        const mmp_serve_req &r = sreqs[i];
-        if (g.n_excl < 0 || g.excl_off < 0 || (int64_t)g.excl_off + g.n_excl > n_excl || g.n_explicit < 0 || g.explicit_off < 0 ||
-            (int64_t)g.explicit_off + g.n_explicit > n_explicit || r.n_excl < 0 || r.excl_off < 0 ||
-            (int64_t)r.excl_off + r.n_excl > n_excl || r.n_cnt < 0 || r.cnt_off < 0 || (int64_t)r.cnt_off + r.n_cnt > n_counters)
-            return fail(c, MMP_EINVAL, "mmp_route_batch: request %d pool range out of bounds", i);
-        if (g.model != r.model) return fail(c, MMP_EINVAL, "mmp_route_batch: request %d names two models", i);
+        if (const int rc = check_gate_req(c, "mmp_route_batch", i, greqs[i], n_excl, n_explicit)) return rc;
+        if (const int rc = check_serve_req(c, "mmp_route_batch", i, sreqs[i], n_excl, n_counters)) return rc;
+        if (const int rc = check_same_model(c, "mmp_route_batch", i, greqs[i].model, sreqs[i].model)) return rc;
     }
-    // The per-request seam (invokeModel asks for ONE route at a time): a latency slot, as mmp_gate_batch / mmp_serve_batch take
-    // for small calls — pinned, device-mapped buffers on the slot's own stream, one launch, completion through the pinned flag;
-    // nothing is staged and the call never queues behind a commit or a large batch.
-    constexpr int kRouteN = 256, kRouteCnt = 4096, kRoutePool = kFastExtra / 4;
-    constexpr size_t kRouteSreqOff = (size_t)kRouteN * sizeof(mmp_gate_req), kRouteCntOff = kRouteSreqOff + (size_t)kRouteN * sizeof(mmp_serve_req),
-                     kRouteSoutOff = (((size_t)kRouteN * sizeof(mmp_gate_out)) + 15) & ~(size_t)15;
-    static_assert(kRouteCntOff + (size_t)kRouteCnt * sizeof(mmp_serve_counter) <= (size_t)kFastN * sizeof(mmp_place_req), "route slot layout");
-    static_assert(kRouteSoutOff + (size_t)kRouteN * sizeof(mmp_serve_out) <= (size_t)kFastN * sizeof(mmp_place_out), "route slot results");
-    static_assert(kRouteSreqOff % 16 == 0 && kRouteCntOff % 16 == 0, "route slot alignment");
-    if (n > 0 && n <= kRouteN && n_counters <= kRouteCnt && n_excl <= kRoutePool && n_explicit <= kRoutePool) {
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        std::unique_lock<std::mutex> fl;
-        FastSlot *f = slot_acquire(c, fl);
-        char *base = reinterpret_cast<char *>(f->reqs);
-        memcpy(base, greqs, (size_t)n * sizeof(mmp_gate_req));
-        memcpy(base + kRouteSreqOff, sreqs, (size_t)n * sizeof(mmp_serve_req));
-        if (n_counters) memcpy(base + kRouteCntOff, counters, (size_t)n_counters * sizeof(mmp_serve_counter));
-        int32_t *pool = f->extra;
-        if (n_excl) {
-            memcpy(pool, excl_pod, (size_t)n_excl * 4);
-            memcpy(pool + 2 * kRoutePool, excl_time, (size_t)n_excl * 8);
-        }
-        if (n_explicit) memcpy(pool + kRoutePool, explicit_pool, (size_t)n_explicit * 4);
-        char *obase = reinterpret_cast<char *>(f->outs);
-        {
-            std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published snapshot + enqueue
-            if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-            if (c->n_shards > 0) return fail(c, MMP_ESTATE, "context is a pod-axis shard");
-            GateArgs G = gate_args(c, n, now, in_use_expiry);
-            G.reqs = reinterpret_cast<const mmp_gate_req *>(base);
-            G.excl_pod = pool;
-            G.explicit_pool = pool + kRoutePool;
-            G.excl_time = reinterpret_cast<const int64_t *>(pool + 2 * kRoutePool);
-            G.outs = reinterpret_cast<mmp_gate_out *>(obase);
-            G.done = DoneFlag{f->done, f->blocks, ++f->seq};
-            ServeArgs S{};
-            S.reqs = reinterpret_cast<const mmp_serve_req *>(base + kRouteSreqOff);
-            S.models = c->models.as<mmp_model_row>();
-            S.ent_pod = c->ent_pod.as<int32_t>();
-            S.ent_time = c->ent_time.as<int64_t>();
-            S.counters = reinterpret_cast<const mmp_serve_counter *>(base + kRouteCntOff);
-            S.excl_pod = G.excl_pod;
-            S.excl_time = G.excl_time;
-            S.outs = reinterpret_cast<mmp_serve_out *>(obase + kRouteSoutOff);
-            S.n = n;
-            S.n_models = c->n_models;
-            S.P = c->snap.P;
-            S.now = now;
-            S.done = DoneFlag{nullptr, nullptr, 0};
-            HIP_TRY(c, order_after_registry(c, f->stream));
-            if (n == 1 && n_counters <= kRouteInlineCnt && sreqs[0].n_cnt <= kRouteInlineCnt) {  // ONE route: the requests ride in the kernel arguments
-                RouteInline R{};
-                R.g = greqs[0];
-                R.s = sreqs[0];
-                for (int32_t j = 0; j < sreqs[0].n_cnt; j++) R.cnt[j] = counters[sreqs[0].cnt_off + j];
-                hipLaunchKernelGGL(route_single_kernel, dim3(1), dim3(128), 0, f->stream, G, S, R);
-            } else
-                hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, f->stream, G, S);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-        memcpy(gouts, obase, (size_t)n * sizeof(mmp_gate_out));
-        memcpy(souts, obase + kRouteSoutOff, (size_t)n * sizeof(mmp_serve_out));
-        return MMP_OK;
-    }
-    std::lock_guard<std::mutex> gb(c->batch_mu);  // (as mmp_gate_batch's batch path: owns c->stream and the scratch)
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (n == 0) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_gate_req)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_gate_out)));
-    HIP_TRY(c, c->rt_sreqs.ensure((size_t)n * sizeof(mmp_serve_req)));
-    HIP_TRY(c, c->rt_souts.ensure((size_t)n * sizeof(mmp_serve_out)));
-    HIP_TRY(c, c->rt_cnt.ensure((size_t)std::max(n_counters, 1) * sizeof(mmp_serve_counter)));
-    HIP_TRY(c, c->s_a.ensure((size_t)std::max(n_explicit, 1) * 4));
-    HIP_TRY(c, c->s_c.ensure((size_t)std::max(n_excl, 1) * 4));
-    HIP_TRY(c, c->s_d.ensure((size_t)std::max(n_excl, 1) * 8));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, greqs, (size_t)n * sizeof(mmp_gate_req), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->rt_sreqs.p, sreqs, (size_t)n * sizeof(mmp_serve_req), hipMemcpyHostToDevice, st));
-    if (n_counters) HIP_TRY(c, hipMemcpyAsync(c->rt_cnt.p, counters, (size_t)n_counters * sizeof(mmp_serve_counter), hipMemcpyHostToDevice, st));
-    if (n_explicit) HIP_TRY(c, hipMemcpyAsync(c->s_a.p, explicit_pool, (size_t)n_explicit * 4, hipMemcpyHostToDevice, st));
-    if (n_excl) {
-        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, excl_pod, (size_t)n_excl * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->s_d.p, excl_time, (size_t)n_excl * 8, hipMemcpyHostToDevice, st));
-    }
-    GateArgs G = gate_args(c, n, now, in_use_expiry);
-    G.reqs = c->s_reqs.as<mmp_gate_req>();
-    G.excl_pod = c->s_c.as<int32_t>();
-    G.excl_time = c->s_d.as<int64_t>();
-    G.explicit_pool = c->s_a.as<int32_t>();
-    G.outs = c->s_outs.as<mmp_gate_out>();
-    ServeArgs S{};
-    S.reqs = c->rt_sreqs.as<mmp_serve_req>();
-    S.models = c->models.as<mmp_model_row>();
-    S.ent_pod = c->ent_pod.as<int32_t>();
-    S.ent_time = c->ent_time.as<int64_t>();
-    S.counters = c->rt_cnt.as<mmp_serve_counter>();
-    S.excl_pod = c->s_c.as<int32_t>();
-    S.excl_time = c->s_d.as<int64_t>();
-    S.outs = c->rt_souts.as<mmp_serve_out>();
-    S.n = n;
-    S.n_models = c->n_models;
-    S.P = c->snap.P;
-    S.now = now;
-    S.done = DoneFlag{nullptr, nullptr, 0};
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(gouts, c->s_outs.p, (size_t)n * sizeof(mmp_gate_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(souts, c->rt_souts.p, (size_t)n * sizeof(mmp_serve_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
+    using L = RouteSlot;
+    // (staged, the gate half takes the scratch mmp_gate_batch takes, the serve half buffers of its own)
+    SeamIo gq = seam_io(greqs, n, L::greqs, c->s_reqs), sq = seam_io(sreqs, n, L::sreqs, c->rt_sreqs),
+           cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
+    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit,
+                    {&gq, &sq, &cnt, &xp, &xt, &ex}, {&go, &so}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        GateArgs G = gate_args(c, n, now, in_use_expiry);
+                        G.reqs = gq.as<mmp_gate_req>();
+                        G.excl_pod = xp.as<int32_t>();
+                        G.excl_time = xt.as<int64_t>();
+                        G.explicit_pool = ex.as<int32_t>();
+                        G.outs = go.as<mmp_gate_out>();
+                        G.done = done;
+                        ServeArgs S = serve_args(c, n, now);
+                        S.reqs = sq.as<mmp_serve_req>();
+                        S.counters = cnt.as<mmp_serve_counter>();
+                        S.excl_pod = G.excl_pod;
+                        S.excl_time = G.excl_time;
+                        S.outs = so.as<mmp_serve_out>();
+                        HIP_TRY(c, order_after_registry(c, st));
+                        if (on_slot && n == 1 && n_counters <= kRouteInlineCnt && sreqs[0].n_cnt <= kRouteInlineCnt) {
+                            // ONE route on a slot: the requests ride in the kernel arguments
+                            RouteInline R{};
+                            R.g = greqs[0];
+                            R.s = sreqs[0];
+                            for (int32_t j = 0; j < sreqs[0].n_cnt; j++) R.cnt[j] = counters[sreqs[0].cnt_off + j];
+                            hipLaunchKernelGGL(route_single_kernel, dim3(1), dim3(128), 0, st, G, S, R);
+                        } else
+                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
 } MMP_CATCH(c, "mmp_route_batch")
+
+int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
+try {
+    if (!c || n < 0 || (n > 0 && (!reqs || !outs))) return fail(c, MMP_EINVAL, "mmp_evict_batch: bad argument");
+    SeamIo q = seam_io(reqs, n, EvictSlot::reqs, c->s_reqs), o = seam_io(outs, n, EvictSlot::outs, c->s_outs);
+    return seam_run<false>(c, n, n > 0 && n <= EvictSlot::kN, {&q}, {&o},
+                    [&] { return n > 0 && c->n_caches <= 0 ? fail(c, MMP_ESTATE, "no caches loaded") : MMP_OK; },
+                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
+                        EvictArgs A = evict_args(c, n, now);
+                        A.reqs = q.as<mmp_evict_req>();
+                        A.outs = o.as<mmp_evict_out>();
+                        A.done = done;
+                        evict_launch(c, A, n, st);
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
+} MMP_CATCH(c, "mmp_evict_batch")
 
 int mmp_proactive_plan(mmp_ctx *c, int32_t default_units, int64_t now, int32_t max_out, int32_t *out_model,
                        int64_t *out_last_used, mmp_proactive_info *info)
@@ -5959,78 +5942,5 @@ try {
     c->cache_entries = E;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_caches_load")
-
-namespace {
-// eight lanes per evaluation while the deques are short, sixteen otherwise (aux_kernels.hpp)
-void evict_launch(mmp_ctx *c, const EvictArgs &A, int32_t n, hipStream_t st)
-{
-    if (c->cache_entries <= (int64_t)24 * std::max(c->n_caches, 1))
-        hipLaunchKernelGGL(evict_batch_kernel<8>, dim3(div_up(n, kEvBlock / 8)), dim3(kEvBlock), 0, st, A);
-    else
-        hipLaunchKernelGGL(evict_batch_kernel<16>, dim3(div_up(n, kEvBlock / 16)), dim3(kEvBlock), 0, st, A);
-}
-}  // namespace
-
-int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
-try {
-    if (!c || n < 0 || (n > 0 && (!reqs || !outs))) return fail(c, MMP_EINVAL, "mmp_evict_batch: bad argument");
-    if (n > 0 && (size_t)n * sizeof(mmp_evict_out) <= kFastN * sizeof(mmp_place_out)) {
-        // latency path (see slot_acquire): one launch on a slot stream, no staging copies, no batch lock
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        std::unique_lock<std::mutex> fl;
-        FastSlot *f = slot_acquire(c, fl);
-        memcpy(f->reqs, reqs, (size_t)n * sizeof(mmp_evict_req));
-        {
-            std::shared_lock<std::shared_mutex> g(c->mu);  // capture the cache tables + enqueue
-            if (c->n_caches <= 0) return fail(c, MMP_ESTATE, "no caches loaded");
-            EvictArgs A;
-            A.reqs = reinterpret_cast<const mmp_evict_req *>(f->reqs);
-            A.seg_off = c->c_seg.as<int32_t>();
-            A.last_used = c->c_lu.as<int64_t>();
-            A.weight = c->c_wt.as<int32_t>();
-            A.capacity = c->c_cap.as<int64_t>();
-            A.outs = reinterpret_cast<mmp_evict_out *>(f->outs);
-            A.n = n;
-            A.n_caches = c->n_caches;
-            A.now = now;
-            A.done = DoneFlag{f->done, f->blocks, ++f->seq};
-            evict_launch(c, A, n, f->stream);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
-        memcpy(outs, f->outs, (size_t)n * sizeof(mmp_evict_out));
-        return MMP_OK;
-    }
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (c->n_caches <= 0 && n > 0) return fail(c, MMP_ESTATE, "no caches loaded");
-    if (n == 0) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_evict_req)));
-    HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_evict_out)));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, reqs, (size_t)n * sizeof(mmp_evict_req), hipMemcpyHostToDevice, st));
-    EvictArgs A;
-    A.reqs = c->s_reqs.as<mmp_evict_req>();
-    A.seg_off = c->c_seg.as<int32_t>();
-    A.last_used = c->c_lu.as<int64_t>();
-    A.weight = c->c_wt.as<int32_t>();
-    A.capacity = c->c_cap.as<int64_t>();
-    A.outs = c->s_outs.as<mmp_evict_out>();
-    A.n = n;
-    A.n_caches = c->n_caches;
-    A.now = now;
-    A.done = DoneFlag{nullptr, nullptr, 0};
-    KT_BEGIN(c, st);
-    evict_launch(c, A, n, st);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(outs, c->s_outs.p, (size_t)n * sizeof(mmp_evict_out), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    return MMP_OK;
-} MMP_CATCH(c, "mmp_evict_batch")
 
 }  // extern "C"
