@@ -1138,6 +1138,51 @@ int mmp_pods_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off,
  * do step 3 by itself: the registry keeps neither the bytes nor the hash of an id it could not resolve, only pod -1.  Until
  * then such an entry still counts as a copy but excludes nobody in a decision. */
 int mmp_registry_unresolved(mmp_ctx *ctx, int32_t *model_out, int32_t max_models, int32_t *n_models_out, int64_t *n_entries_out);
+/* ---- registry events by key: the model-id table (model_ids_kernels.hpp) --------------------------------------------------------
+ * The registry's rows are numbered; its listener (MM.java:628, event() :2807-2854) gets a key and a value.  The context keeps the
+ * id -> row map on the device — open addressing like the instance table's, but a model id is an arbitrary user string (raw key
+ * bytes, any UTF-8, no ASCII rule: nothing orders them), so a slot is matched on its 64-bit FNV-1a hash AND its bytes, which the
+ * context keeps in a device arena.  Ids that collide coexist; nothing is refused for colliding.  The table has no deletion.
+ * MMP_MODEL_ID_HASH_BITS=b (read with the other MMP_* switches, per context at mmp_create) masks every model-id hash to its low b
+ * bits, 0: all equal — a diagnostic that makes the collision path testable. */
+/* Name the registry's rows 0 .. n_models-1: id i = ids[id_off[i], id_off[i+1]).  The table is built on the device and replaces
+ * the loaded one.  MMP_ESTATE unless n_models equals the registry's row count (load the registry first; 0 ids over an empty
+ * registry is a valid start, every id then joins through mmp_models_events_json).  MMP_EINVAL with nothing changed: a NULL
+ * required buffer, non-monotone offsets, two equal ids. */
+int mmp_model_ids_load(mmp_ctx *ctx, const char *ids, const int32_t *id_off, int32_t n_models);
+/* model_idx_out[i] = the registry row of key i = keys[key_off[i], key_off[i+1]), -1 for an id the table does not know.
+ * Read-only: this is how a host asks mmp_models_status / mmp_registry_ops / a request row by id.  MMP_ESTATE before
+ * mmp_model_ids_load and when the registry has been resized by index since (see mmp_models_events_json).  n == 0 is valid. */
+int mmp_model_ids_resolve(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, int32_t *model_idx_out);
+/* The way back: the ids of rows [first_row, first_row + n_rows) — the prune, janitor, unresolved and status calls answer in rows.
+ * *n_bytes_out = their bytes, always; off_out (n_rows + 1 words, rebased to 0) is written when it is not NULL; the bytes are
+ * written when max_bytes >= *n_bytes_out.  bytes_out == NULL with max_bytes == 0 asks for the sizes only.  MMP_EINVAL for a range
+ * outside the table; MMP_ESTATE as mmp_model_ids_resolve. */
+int mmp_model_ids_get(mmp_ctx *ctx, int32_t first_row, int32_t n_rows, char *bytes_out, int32_t max_bytes, int32_t *off_out,
+                      int32_t *n_bytes_out);
+/* Registry events as the listener gets them: event i is the model id keys[key_off[i], key_off[i+1]) — the raw bytes of the KV
+ * key — with the ModelRecord value buf[off[i], off[i+1]).  The keys are resolved, deduplicated and numbered on the device;
+ * everything behind the resolution is mmp_models_upsert_json (same parser, same winner rule, same arena append — both calls run
+ * one pipeline).  deleted[i] != 0 is ENTRY_DELETED: the value is ignored and the row becomes the empty row; it KEEPS its id and
+ * its number, and an id that is registered again gets its old row back (reclaiming rows is out of scope).
+ * status_out[i]: 0 applied, 1 malformed value, 2 unknown id (nothing changes; model_idx_out[i] = -1).  An id the table does not
+ * know: with MMP_MEV_APPEND in flags the distinct unknown ids of NON-DELETED events join as rows M0, M0+1, ... (M0 = the row count
+ * at the call) in order of first appearance, whether or not their values turn out well-formed (the appended-row rule of
+ * mmp_models_upsert_json: a joined row whose events are all malformed is the empty row); without the flag such an event is
+ * status 2.  A deletion never appends: of an id that is unknown when the event is reached — the table and the events before
+ * it — it is status 2; behind the event that made the id join, it applies.  Events apply in order: a row ends as its LAST
+ * WELL-FORMED OR DELETED event left it.  model_idx_out[i] = the resolved row; last_unload_out[i] = "lul" of an applied value,
+ * else 0; *n_appended_out = ids that joined.  deleted, last_unload_out, n_appended_out may be NULL.
+ * Only O(events) words come back to the host; two runs over the same state and events are byte-identical, whichever lanes raced.
+ * MMP_EINVAL with nothing changed (table, id arena, registry): a NULL required buffer, non-monotone offsets of either kind,
+ * unknown flags, entry arena overflow.  MMP_ESTATE with nothing changed: before mmp_model_ids_load or mmp_pod_ids_load, and when
+ * the registry's row count no longer equals the id count — mmp_models_load, mmp_models_ingest_json or an append by index
+ * (mmp_models_upsert / mmp_models_upsert_json) resized one space without the other; load the ids again.  Locking as
+ * mmp_models_upsert_json.  n == 0 is valid. */
+#define MMP_MEV_APPEND 1u
+int mmp_models_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                           const uint8_t *deleted, uint32_t flags, int32_t *model_idx_out, int64_t *last_unload_out,
+                           int32_t *status_out, int32_t *n_appended_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

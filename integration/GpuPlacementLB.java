@@ -178,6 +178,21 @@ final class MmPlace {
     // the registry rows holding an entry whose instance id the table does not know, ascending; after a join the listener sends
     // their stored values through modelsUpsertJson again.  nModelsOut (int) / nEntriesOut (long) are the full counts.
     static native int registryUnresolved(long h, ByteBuffer modelOut, int maxModels, ByteBuffer nModelsOut, ByteBuffer nEntriesOut);
+    // registry events by key: the model-id table lives on the device.  modelIdsLoad names rows 0 .. nModels-1 (nModels must be
+    // the registry's row count; 0 ids over an empty registry is a valid start); modelIdsResolve gives the row of each key, -1 for
+    // an unknown id (modelsStatus / registryOps / a request row by id); modelIdsGet gives the ids of a row range back (a null
+    // bytesOut with maxBytes 0: nBytesOut only; offOut, may be null, holds nRows + 1 ints).
+    static native int modelIdsLoad(long h, ByteBuffer ids, ByteBuffer idOff, int nModels);
+    static native int modelIdsResolve(long h, ByteBuffer keys, ByteBuffer keyOff, int n, ByteBuffer modelIdxOut);
+    static native int modelIdsGet(long h, int firstRow, int nRows, ByteBuffer bytesOut, int maxBytes, ByteBuffer offOut,
+                                  ByteBuffer nBytesOut);
+    /** the registry listener (MM.java:628, event() :2807-2854) as it is called: event i = the raw key bytes keys[keyOff[i],
+     *  keyOff[i+1]) (the model id, any UTF-8) with the raw value json[off[i], off[i+1]); deleted (may be null) marks
+     *  ENTRY_DELETED; flags 1 = unknown ids join as new rows.  modelIdxOut = the row of each event (-1 with status 2), statusOut
+     *  0 applied / 1 malformed / 2 unknown id; lastUnloadOut (may be null); nAppendedOut = ids that joined (one int, may be null). */
+    static native int modelsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
+                                       ByteBuffer deleted, int flags, ByteBuffer modelIdxOut, ByteBuffer lastUnloadOut,
+                                       ByteBuffer statusOut, ByteBuffer nAppendedOut);
     // misc
     static native long minSpaceUnits(int defaultModelSizeUnits, int loadingThreads, long capacityUnits,
                                      boolean haveUnloadManager);
@@ -197,9 +212,10 @@ final class MmPlace {
  * replica_set == interned id.substring(0,6)) and model id -> dense model index; the snapshot handle is refreshed by
  * the instance-table listener (handleInstanceTableChange, ModelMesh.java:1455: podsEventsJson with the raw key and value
  * of each event + commit, registryUnresolved + modelsUpsertJson after a join; or podsUpsert / podsRemove with parsed rows) and
- * by the registry listener (modelsIngestJson of the stored values once, then modelsUpsertJson per batch of events with
- * the raw byte[] of each event and the model index of its key, ENTRY_DELETED as a deleted flag; a listener that holds
- * parsed ModelRecords uses modelsLoad / modelsUpsert instead).
+ * by the registry listener (modelsIngestJson of the stored values and modelIdsLoad of their keys once, then modelsEventsJson
+ * per batch of events with the raw key and the raw byte[] of each event, ENTRY_DELETED as a deleted flag: the listener keeps no
+ * id map, modelIndexOf is modelIdsResolve; a listener that numbers its rows itself uses modelsUpsertJson by index, one that holds
+ * parsed ModelRecords modelsLoad / modelsUpsert).
  */
 interface GpuMeshBinding {
     long handle();

@@ -642,6 +642,63 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryUnresolved(
                                          buf<int64_t>(env, nEntriesOut)));
 }
 
+// ---- registry events by key: the model-id table on the device (see mmp_model_ids_load ... mmp_models_events_json) -----------
+// The capacities are checked here, as for the instance calls: the library only knows n.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelIdsLoad(JNIEnv *env, jclass, jlong h, jobject ids, jobject idOff,
+                                                                          jint nModels)
+{
+    if (nModels < 0 || !holds<int32_t>(env, idOff, (jlong)nModels + 1, "modelIdsLoad: idOff shorter than nModels + 1") ||
+        (nModels > 0 && !holds<char>(env, ids, buf<int32_t>(env, idOff)[nModels], "modelIdsLoad: ids shorter than idOff[nModels]")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_model_ids_load(ctx_of(h), buf<char>(env, ids), buf<int32_t>(env, idOff), nModels));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelIdsResolve(JNIEnv *env, jclass, jlong h, jobject keys,
+                                                                             jobject keyOff, jint n, jobject modelIdxOut)
+{
+    if (n < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "modelIdsResolve: keyOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "modelIdsResolve: keys shorter than keyOff[n]")) ||
+        !holds<int32_t>(env, modelIdxOut, n, "modelIdsResolve: modelIdxOut shorter than n"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_model_ids_resolve(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), n, buf<int32_t>(env, modelIdxOut)));
+}
+// a null bytesOut with maxBytes 0: sizes only; offOut (may be null) holds nRows + 1 ints
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelIdsGet(JNIEnv *env, jclass, jlong h, jint firstRow, jint nRows,
+                                                                         jobject bytesOut, jint maxBytes, jobject offOut,
+                                                                         jobject nBytesOut)
+{
+    if (nRows < 0 || maxBytes < 0 || !holds<char>(env, bytesOut, maxBytes, "modelIdsGet: bytesOut shorter than maxBytes") ||
+        (offOut && !holds<int32_t>(env, offOut, (jlong)nRows + 1, "modelIdsGet: offOut shorter than nRows + 1")) ||
+        !holds<int32_t>(env, nBytesOut, 1, "modelIdsGet: nBytesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_model_ids_get(ctx_of(h), firstRow, nRows, buf<char>(env, bytesOut), maxBytes, buf<int32_t>(env, offOut),
+                                   buf<int32_t>(env, nBytesOut)));
+}
+// registry listener events as the listener gets them: the raw key and value bytes of each event (see mmp_models_events_json)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsEventsJson(JNIEnv *env, jclass, jlong h, jobject keys,
+                                                                              jobject keyOff, jobject json, jobject off, jint n,
+                                                                              jobject deleted, jint flags, jobject modelIdxOut,
+                                                                              jobject lastUnloadOut, jobject statusOut,
+                                                                              jobject nAppendedOut)
+{
+    if (n < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "modelsEventsJson: keyOff shorter than n + 1") ||
+        !holds<int64_t>(env, off, (jlong)n + 1, "modelsEventsJson: off shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "modelsEventsJson: keys shorter than keyOff[n]")) ||
+        (n > 0 && !holds<char>(env, json, buf<int64_t>(env, off)[n], "modelsEventsJson: json shorter than off[n]")) ||
+        (deleted && !holds<uint8_t>(env, deleted, n, "modelsEventsJson: deleted shorter than n")) ||
+        !holds<int32_t>(env, modelIdxOut, n, "modelsEventsJson: modelIdxOut shorter than n") ||
+        (lastUnloadOut && !holds<int64_t>(env, lastUnloadOut, n, "modelsEventsJson: lastUnloadOut shorter than n")) ||
+        !holds<int32_t>(env, statusOut, n, "modelsEventsJson: statusOut shorter than n") ||
+        (nAppendedOut && !holds<int32_t>(env, nAppendedOut, 1, "modelsEventsJson: nAppendedOut shorter than one int")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_events_json(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), buf<char>(env, json),
+                                        buf<int64_t>(env, off), n, buf<uint8_t>(env, deleted), static_cast<uint32_t>(flags),
+                                        buf<int32_t>(env, modelIdxOut), buf<int64_t>(env, lastUnloadOut), buf<int32_t>(env, statusOut),
+                                        buf<int32_t>(env, nAppendedOut)));
+}
+
 // ---- misc -----------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL Java_com_ibm_watson_modelmesh_MmPlace_minSpaceUnits(JNIEnv *, jclass,
                                                                             jint defaultModelSizeUnits,

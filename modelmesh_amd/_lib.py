@@ -171,6 +171,9 @@ assert REGISTRY_STATS.itemsize == 72 and REGISTRY_TYPE_STATS.itemsize == 24
 PEV_APPEND = 1
 PEV_APPLIED, PEV_MALFORMED, PEV_UNKNOWN = 0, 1, 2  # status_out
 
+# mmp_models_events_json (registry events by key, the registry listener MM.java:628): the status values are those above
+MEV_APPEND = 1
+
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
      ("last_unload_time", "<i8"), ("earlier_use_iteration", "<i4"), ("last_used_iteration", "<i4"), ("flags", "<u4"),
@@ -293,6 +296,10 @@ SYMBOLS = [
     ("mmp_pod_ids_append", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32]),
     ("mmp_pods_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_registry_unresolved", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    ("mmp_model_ids_load", C.c_int, [_P, _P, _P, C.c_int32]),
+    ("mmp_model_ids_resolve", C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    ("mmp_model_ids_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    ("mmp_models_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -42,6 +42,7 @@
 #include "status_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
+#include "model_ids_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -260,6 +261,7 @@ struct Tuning {
     int32_t plan_sorted = 0;     // MMP_PLAN_SORTED=1: mmp_proactive_plan takes its sorted (fallback) path on every input; 2: never (tests)
     int32_t plan_fused = 1;      // MMP_PLAN_FUSED=0: the plan as its eight dependent launches (comparison; the one-launch form is the default)
     int32_t resident = 0;        // MMP_RESIDENT=1: mmp_create turns the resident decision kernel on (mmp_resident)
+    int32_t model_id_hash_bits = 64;  // MMP_MODEL_ID_HASH_BITS=b: every model-id hash is masked to its low b bits, 0: all equal (tests: ids that collide)
 };
 
 struct mmp_ctx {
@@ -463,6 +465,16 @@ struct mmp_ctx {
     std::unordered_map<std::string, int32_t> rs_intern;
     DevBuf idtab_next_hash, idtab_next_val, ida_bytes, ida_off, ida_hash, ida_found;
     DevBuf unres_list;  // mmp_registry_unresolved: the listed rows (its other scratch is the registry plans')
+    // The model-id table (model_ids_kernels.hpp), read and written under batch_mu only: mid_hash / mid_val / mid_mask the published
+    // table, mid_bytes / mid_off the id arena (row r = mid_bytes[mid_off[r], mid_off[r + 1]); mid_n rows, mid_nbytes bytes);
+    // mid_next_*: the table built beside the published one.  me_*: one call's keys on the device — hashes, resolved rows, dedupe
+    // slots, the call-local table (owner | first | first_nd), the flags and their scan, model_idx, the joining events, what the
+    // verify found, the deleted bytes.
+    DevBuf mid_hash, mid_val, mid_next_hash, mid_next_val, mid_bytes, mid_off;
+    DevBuf me_hash, me_row, me_slot, me_tab, me_cnt, me_pos, me_idx, me_join, me_found, me_del;
+    uint32_t mid_mask = 0;
+    int32_t mid_n = 0, mid_nbytes = 0;
+    bool have_model_ids = false;
 
     // per-call scratch for the host-pointer entry points
     DevBuf s_reqs, s_outs, s_extra, s_a, s_b, s_c, s_d;
@@ -758,6 +770,8 @@ Tuning read_tuning()
     num("MMP_RANK_MODE", t.rank_mode), flag("MMP_NO_DELTA", t.no_delta);
     num("MMP_PLAN_SORTED", t.plan_sorted), num("MMP_PLAN_FUSED", t.plan_fused);
     flag("MMP_RESIDENT", t.resident);
+    num("MMP_MODEL_ID_HASH_BITS", t.model_id_hash_bits);
+    t.model_id_hash_bits = std::max(0, std::min(t.model_id_hash_bits, 64));
     return t;
 }
 
@@ -1342,7 +1356,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->me_del, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -3252,6 +3266,91 @@ try {
     return rebuild_resolved(c);
 } MMP_CATCH(c, "mmp_models_ingest_json")
 
+namespace {
+// What mmp_models_upsert_json and mmp_models_events_json hand to the pipeline they share, all of it on the device: the one resolves
+// the events' rows on the host from indices, the other on the device from keys (model_ids_kernels.hpp).
+struct UpsertJsonEvents {
+    int32_t *slot;            // [n] event -> its row's position among the call's distinct rows in order of first appearance; k for an
+                              // event without a row (an unknown id of mmp_models_events_json)
+    int32_t *slot_model;      // [k] the registry row of each slot
+    int32_t *win;             // [k + 1] -1; win[k] takes the events without a row and is never read
+    const uint8_t *deleted;   // [n], or nullptr: no event is a deletion
+    int32_t *s_cnt, *s_offs;  // [k + 1] each
+    int32_t k, count;         // distinct rows (> 0); the registry's rows after the call
+};
+
+// From the events' slots on the device to the rewritten registry (batch_mu held, the device set, n > 0, E.k > 0): the values are
+// staged and parsed, each slot's winner picked, the winners' entries appended to the arena and the rows rewritten in place.
+// h_model: the rows of the slots on the host, for the m_cnt shadow; given empty it is read back from E.slot_model.  Nothing but
+// scratch is written before the last refusal (entry arena overflow).  The caller squeezes the arena afterwards.
+int models_upsert_json_run(mmp_ctx *c, const char *fn, const char *buf, const int64_t *off, int32_t n, const UpsertJsonEvents &E,
+                           std::vector<int32_t> &h_model, int64_t *last_unload_out, int32_t *status_out)
+{
+    const int32_t k = E.k, count = E.count, M0 = c->n_models;
+    hipStream_t st = c->stream;
+    std::vector<int64_t> rel;
+    int64_t bytes;
+    if (const int rc = stage_values(c, fn, buf, off, n, rel, bytes)) return rc;
+    IngestModelsArgs A;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
+    if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "%s: more than 2^31 entries in one call", fn);
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+    int32_t *d_win = E.win, *d_model = E.slot_model, *s_cnt = E.s_cnt, *s_offs = E.s_offs;
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    A.rows = c->j_rows.as<mmp_model_row>();
+    A.deleted = E.deleted;
+    A.slot = E.slot;
+    A.win = d_win;
+    // parse the events (entries parked in scratch), pick each row's winner, and size what the winners append
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * A.grp)), dim3(kJBlock), 0, st, A);
+    hipLaunchKernelGGL(upsert_json_counts_kernel, dim3(div_up(k + 1, 256)), dim3(256), 0, st, d_win, A.cnt, k, s_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    // back to the host: the winners and the per-event counts (for the host shadow) and the arena room needed; no entry, no row
+    std::vector<int32_t> h_win(k), h_cnt(n);
+    int32_t total = 0;
+    HIP_TRY(c, hipMemcpyAsync(h_win.data(), d_win, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h_cnt.data(), A.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&total, s_offs + k, 4, hipMemcpyDeviceToHost, st));
+    if (h_model.empty()) {
+        h_model.resize(k);
+        HIP_TRY(c, hipMemcpyAsync(h_model.data(), d_model, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const double parse_ms = c->last_kernel_ms;
+    const int32_t base = c->n_entries;
+    if ((int64_t)base + total > INT32_MAX)  // (nothing but scratch has been written so far)
+        return fail(c, MMP_EINVAL, "%s: entry arena overflow; reload the registry", fn);
+    if (const int rc = registry_grow(c, count, base, total)) return rc;
+    HIP_TRY(c, c->u_idx.ensure((size_t)k * 4));
+    HIP_TRY(c, c->u_rows.ensure((size_t)k * sizeof(mmp_model_row)));
+    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (last_unload_out) HIP_TRY(c, hipMemcpyAsync(last_unload_out, c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(upsert_json_build_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, d_win, d_model, k, M0, base, s_offs, A.rows, A.off,
+                       A.ent_pod, A.ent_time, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
+                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = registry_rewrite(c, k, count, base + total, true)) return rc;
+    if (c->prof && parse_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += parse_ms;  // the call's device span: parse + apply
+    // the host shadow: a slot without a winner keeps its count (an existing row) or has none (an appended one)
+    c->m_cnt.resize(count, 0);
+    for (int32_t j = 0; j < k; j++) {
+        if (h_win[j] < 0) continue;
+        const int32_t cnt = h_cnt[h_win[j]];
+        c->ent_live += (int64_t)cnt - c->m_cnt[h_model[j]];
+        c->m_cnt[h_model[j]] = cnt;
+    }
+    return MMP_OK;
+}
+}  // namespace
+
 int mmp_models_upsert_json(mmp_ctx *c, const char *buf, const int64_t *off, int32_t n, const int32_t *model_idx,
                            const uint8_t *deleted, int64_t *last_unload_out, int32_t *status_out)
 try {
@@ -3281,74 +3380,329 @@ try {
     const int32_t k = (int32_t)h_model.size();
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    std::vector<int64_t> rel;
-    int64_t bytes;
-    if (const int rc = stage_values(c, "mmp_models_upsert_json", buf, off, n, rel, bytes)) return rc;
-    IngestModelsArgs A;
-    size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
-    if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_models_upsert_json: more than 2^31 entries in one call");
-    // j_ev, in words: slot[n] | slot_model[k] | win[k] | deleted[n bytes] (uploaded together) | s_cnt[k+1] | s_offs[k+1]
-    const size_t del_words = ((size_t)n + 3) / 4, up_words = (size_t)n + 2 * (size_t)k + del_words;
+    // j_ev, in words: slot[n] | slot_model[k] | win[k + 1] | deleted[n bytes] (uploaded together) | s_cnt[k+1] | s_offs[k+1]
+    const size_t del_words = ((size_t)n + 3) / 4, up_words = (size_t)n + 2 * (size_t)k + 1 + del_words;
     std::vector<int32_t> up(up_words, 0);
     memcpy(up.data(), h_slot.data(), (size_t)n * 4);
     memcpy(up.data() + n, h_model.data(), (size_t)k * 4);
-    std::fill(up.begin() + n + k, up.begin() + n + 2 * (size_t)k, -1);
+    std::fill(up.begin() + n + k, up.begin() + n + 2 * (size_t)k + 1, -1);
     if (deleted)
-        for (int32_t i = 0; i < n; i++) reinterpret_cast<uint8_t *>(up.data() + n + 2 * (size_t)k)[i] = deleted[i] ? 1 : 0;
+        for (int32_t i = 0; i < n; i++) reinterpret_cast<uint8_t *>(up.data() + n + 2 * (size_t)k + 1)[i] = deleted[i] ? 1 : 0;
     HIP_TRY(c, c->j_ev.ensure((up_words + 2 * ((size_t)k + 1)) * 4));
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
-    int32_t *d_slot = c->j_ev.as<int32_t>(), *d_model = d_slot + n, *d_win = d_model + k;
-    int32_t *s_cnt = d_slot + up_words, *s_offs = s_cnt + k + 1;
-    size_t scan_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
-    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    UpsertJsonEvents E{};
+    E.slot = c->j_ev.as<int32_t>();
+    E.slot_model = E.slot + n;
+    E.win = E.slot_model + k;
+    E.deleted = deleted ? reinterpret_cast<const uint8_t *>(E.win + k + 1) : nullptr;
+    E.s_cnt = E.slot + up_words;
+    E.s_offs = E.s_cnt + k + 1;
+    E.k = k;
+    E.count = count;
     HIP_TRY(c, hipMemcpyAsync(c->j_ev.p, up.data(), up_words * 4, hipMemcpyHostToDevice, st));
-    A.rows = c->j_rows.as<mmp_model_row>();
-    A.deleted = deleted ? reinterpret_cast<const uint8_t *>(d_win + k) : nullptr;
-    A.slot = d_slot;
-    A.win = d_win;
-    // parse the events (entries parked in scratch), pick each row's winner, and size what the winners append
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * A.grp)), dim3(kJBlock), 0, st, A);
-    hipLaunchKernelGGL(upsert_json_counts_kernel, dim3(div_up(k + 1, 256)), dim3(256), 0, st, d_win, A.cnt, k, s_cnt);
-    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, s_cnt, s_offs, (int32_t)0, (size_t)k + 1, rocprim::plus<int32_t>(), st));
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    // back to the host: the winners and the per-event counts (for the host shadow) and the arena room needed; no entry, no row
-    std::vector<int32_t> h_win(k), h_cnt(n);
-    int32_t total = 0;
-    HIP_TRY(c, hipMemcpyAsync(h_win.data(), d_win, (size_t)k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_cnt.data(), A.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&total, s_offs + k, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    const double parse_ms = c->last_kernel_ms;
-    const int32_t base = c->n_entries;
-    if ((int64_t)base + total > INT32_MAX)  // (nothing but scratch has been written so far)
-        return fail(c, MMP_EINVAL, "mmp_models_upsert_json: entry arena overflow; reload the registry");
-    if (const int rc = registry_grow(c, count, base, total)) return rc;
-    HIP_TRY(c, c->u_idx.ensure((size_t)k * 4));
-    HIP_TRY(c, c->u_rows.ensure((size_t)k * sizeof(mmp_model_row)));
-    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (last_unload_out) HIP_TRY(c, hipMemcpyAsync(last_unload_out, c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(upsert_json_build_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, d_win, d_model, k, M0, base, s_offs, A.rows, A.off,
-                       A.ent_pod, A.ent_time, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
-                       c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = registry_rewrite(c, k, count, base + total, true)) return rc;
-    if (c->prof && parse_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += parse_ms;  // the call's device span: parse + apply
-    // the host shadow: a slot without a winner keeps its count (an existing row) or has none (an appended one)
-    c->m_cnt.resize(count, 0);
-    for (int32_t j = 0; j < k; j++) {
-        if (h_win[j] < 0) continue;
-        const int32_t cnt = h_cnt[h_win[j]];
-        c->ent_live += (int64_t)cnt - c->m_cnt[h_model[j]];
-        c->m_cnt[h_model[j]] = cnt;
-    }
+    if (const int rc = models_upsert_json_run(c, "mmp_models_upsert_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
     return squeeze_if_garbage(c);
 } MMP_CATCH(c, "mmp_models_upsert_json")
+
+namespace {
+// One call's keys resolved, deduplicated and numbered on the device, and the table / arena that would hold the joining ids built
+// beside the published ones.  Nothing of the context's published state has changed until model_ids_publish.
+struct ModelIdsPlan {
+    int32_t k = 0, n_join = 0, join_bytes = 0;  // distinct applicable rows; ids that join; their bytes
+    int32_t n_before = 0, bytes_before = 0;
+    uint32_t cap = 0;                // capacity of the table built in mid_next_* (0: none was needed)
+    DevBuf fresh_bytes, fresh_off;   // the arena, where it had to move (or is replaced)
+    std::vector<int32_t> idx;        // model_idx per event
+    double ms = 0;                   // device span (profiling)
+    ~ModelIdsPlan()
+    {
+        fresh_bytes.release();
+        fresh_off.release();
+    }
+};
+
+// the j_ev layout of the by-key call, in words, every part sized for k == n: slot[n] | slot_model[n] | win[n+1] | s_cnt[n+1] | s_offs[n+1]
+size_t mid_ev_words(int32_t n) { return 5 * (size_t)n + 3; }
+
+int mid_empty_table(mmp_ctx *c, const HashTabW &nt)
+{
+    HIP_TRY(c, hipMemsetAsync(nt.hash, 0, ((size_t)nt.mask + 1) * 8, c->stream));
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nt.val), INT32_MIN, (size_t)nt.mask + 1, c->stream));
+    return MMP_OK;
+}
+
+// batch_mu held, the device set, n > 0, the key offsets monotone.  replace: the keys are a whole id space (mmp_model_ids_load) —
+// resolved against no table, numbered from row 0, table and arena built fresh.  deleted: host bytes or nullptr.
+int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, int32_t n, const uint8_t *deleted, bool append,
+                   bool replace, ModelIdsPlan &P)
+{
+    if (n > INT32_MAX / 8) return fail(c, MMP_EINVAL, "%s: %d keys in one call", fn, n);
+    hipStream_t st = c->stream;
+    const int32_t M0 = P.n_before = replace ? 0 : c->mid_n, B0 = P.bytes_before = replace ? 0 : c->mid_nbytes;
+    std::vector<int32_t> krel;
+    if (const int rc = stage_ids(c, fn, "key", keys, key_off, n, krel)) return rc;
+    uint32_t bcap = 16;  // the call-local table: twice the events
+    while (bcap < (uint32_t)n * 2u) bcap <<= 1;
+    HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
+    HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    HIP_TRY(c, c->me_slot.ensure((size_t)n * 4));
+    HIP_TRY(c, c->me_tab.ensure((size_t)bcap * 3 * 4));
+    HIP_TRY(c, c->me_cnt.ensure(((size_t)n + 1) * sizeof(MidCount)));
+    HIP_TRY(c, c->me_pos.ensure(((size_t)n + 1) * sizeof(MidCount)));
+    HIP_TRY(c, c->me_idx.ensure((size_t)n * 4));
+    HIP_TRY(c, c->me_join.ensure((size_t)n * 4));
+    HIP_TRY(c, c->me_found.ensure((size_t)n * 4));
+    HIP_TRY(c, c->me_del.ensure((size_t)n));
+    HIP_TRY(c, c->j_ev.ensure(mid_ev_words(n) * 4));
+    const MidBatch B{c->me_tab.as<int32_t>(), c->me_tab.as<int32_t>() + bcap, c->me_tab.as<int32_t>() + 2 * (size_t)bcap, bcap - 1};
+    const char *d_keys = c->ida_bytes.as<char>();
+    const int32_t *d_off = c->ida_off.as<int32_t>();
+    const uint64_t *d_hash = c->me_hash.as<uint64_t>();
+    const uint8_t *d_del = deleted ? c->me_del.as<uint8_t>() : nullptr;
+    MidCount *d_cnt = c->me_cnt.as<MidCount>(), *d_pos = c->me_pos.as<MidCount>();
+    const int bits = c->tune.model_id_hash_bits;
+    const uint64_t hmask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+    const ModelIdTab cur{replace ? nullptr : c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
+                         c->mid_off.as<int32_t>()};
+    if (deleted) HIP_TRY(c, hipMemcpyAsync(c->me_del.p, deleted, (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(B.owner, 0xff, (size_t)bcap * 4, st));
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.first), INT32_MAX, (size_t)bcap * 2, st));
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, MidCount{0, 0, 0}, (size_t)n + 1, MidPlus(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
+    // 1. hash once; the rows the table knows; the call's own duplicates; the flags and their scan
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, st, d_keys, d_off, n, hmask, c->me_hash.as<uint64_t>());
+    hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, st, d_keys, d_off, n, d_hash, cur, c->me_row.as<int32_t>());
+    hipLaunchKernelGGL(mid_dedupe_kernel, grid, block, 0, st, d_keys, d_off, n, d_hash, d_del, B, c->me_slot.as<int32_t>());
+    hipLaunchKernelGGL(mid_flags_kernel, dim3(div_up(n + 1, kIdTabBlock)), block, 0, st, n, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B,
+                       d_off, append ? 1 : 0, d_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, MidCount{0, 0, 0}, (size_t)n + 1, MidPlus(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    MidCount tot{};
+    HIP_TRY(c, copy_sync(c, &tot, d_pos + n, sizeof tot, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    P.ms = c->last_kernel_ms;
+    P.k = tot.slot;
+    P.n_join = tot.join;
+    P.join_bytes = tot.bytes;
+    if ((int64_t)M0 + P.n_join > INT32_MAX / 4) return fail(c, MMP_EINVAL, "%s: %d + %d ids", fn, M0, P.n_join);
+    if ((int64_t)B0 + P.join_bytes > INT32_MAX) return fail(c, MMP_EINVAL, "%s: more than 2^31 id bytes", fn);
+    // 2. the arena the joining ids are appended to: in place beyond the published rows, or moved when it has to grow
+    if (replace) {
+        HIP_TRY(c, P.fresh_bytes.ensure((size_t)P.join_bytes + 16));
+        HIP_TRY(c, P.fresh_off.ensure(((size_t)P.n_join + 1) * 4));
+        HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, st));
+    } else {
+        if (const int rc = grow_cow(c, c->mid_bytes, (size_t)B0, (size_t)B0 + P.join_bytes, P.fresh_bytes)) return rc;
+        if (const int rc = grow_cow(c, c->mid_off, ((size_t)M0 + 1) * 4, ((size_t)M0 + P.n_join + 1) * 4, P.fresh_off)) return rc;
+    }
+    char *a_bytes = P.fresh_bytes.p ? P.fresh_bytes.as<char>() : c->mid_bytes.as<char>();
+    int32_t *a_off = P.fresh_off.p ? P.fresh_off.as<int32_t>() : c->mid_off.as<int32_t>();
+    int32_t *d_slot = c->j_ev.as<int32_t>(), *d_model = d_slot + n;
+    // 3. number the events; 4. the next table, copy-on-write, and a verifying lookup in a launch of its own
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(mid_number_kernel, grid, block, 0, st, n, M0, P.k, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B, append ? 1 : 0,
+                       d_pos, d_keys, d_off, B0, c->me_idx.as<int32_t>(), d_slot, d_model, c->me_join.as<int32_t>(), a_bytes, a_off);
+    if (P.n_join > 0 || replace) {
+        const uint32_t cap0 = replace ? 0u : c->mid_mask + 1;
+        uint32_t cap = 16;
+        while (cap < (uint32_t)(M0 + P.n_join) * 2u) cap <<= 1;
+        cap = std::max(cap, cap0);
+        HIP_TRY(c, c->mid_next_hash.ensure((size_t)cap * 8));
+        HIP_TRY(c, c->mid_next_val.ensure((size_t)cap * 4));
+        const HashTabW nt{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), cap - 1};
+        if (cap == cap0) {  // room for the new ids: the slots as they are
+            HIP_TRY(c, hipMemcpyAsync(nt.hash, c->mid_hash.p, (size_t)cap * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(nt.val, c->mid_val.p, (size_t)cap * 4, hipMemcpyDeviceToDevice, st));
+        } else {  // the stored hashes into the larger table
+            if (const int rc = mid_empty_table(c, nt)) return rc;
+            if (cap0)
+                hipLaunchKernelGGL(idtab_rehash_kernel, dim3(div_up((int)cap0, kIdTabBlock)), block, 0, st, c->mid_hash.as<uint64_t>(),
+                                   c->mid_val.as<int32_t>(), cap0, nt);
+        }
+        if (P.n_join > 0) {
+            const dim3 jgrid(div_up(P.n_join, kIdTabBlock));
+            hipLaunchKernelGGL(mid_insert_kernel, jgrid, block, 0, st, P.n_join, c->me_join.as<int32_t>(), d_hash, M0, nt);
+            hipLaunchKernelGGL(mid_verify_kernel, jgrid, block, 0, st, P.n_join, c->me_join.as<int32_t>(), d_hash, d_keys, d_off,
+                               ModelIdTab{nt.hash, nt.val, nt.mask, a_bytes, a_off}, c->me_found.as<int32_t>());
+        }
+        P.cap = cap;
+    }
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    P.idx.resize(n);
+    std::vector<int32_t> found(P.n_join);
+    HIP_TRY(c, hipMemcpyAsync(P.idx.data(), c->me_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (P.n_join > 0) HIP_TRY(c, hipMemcpyAsync(found.data(), c->me_found.p, (size_t)P.n_join * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    if (c->prof && P.ms >= 0 && c->last_kernel_ms >= 0) P.ms += c->last_kernel_ms;
+    for (int32_t r = 0; r < P.n_join; r++)
+        if (found[r] != M0 + r) return fail(c, MMP_EHIP, "%s: id %d was not inserted (the lookup answered %d)", fn, M0 + r, found[r]);
+    return MMP_OK;
+}
+
+// nothing fails from here on: the table, the arena and the counts change together (batch_mu held, the stream idle)
+void model_ids_publish(mmp_ctx *c, ModelIdsPlan &P)
+{
+    if (P.cap) {
+        std::swap(c->mid_hash, c->mid_next_hash);
+        std::swap(c->mid_val, c->mid_next_val);
+        c->mid_mask = P.cap - 1;
+    }
+    if (P.fresh_bytes.p) {
+        c->mid_bytes.release();
+        c->mid_bytes = P.fresh_bytes;
+        P.fresh_bytes = DevBuf{};
+    }
+    if (P.fresh_off.p) {
+        c->mid_off.release();
+        c->mid_off = P.fresh_off;
+        P.fresh_off = DevBuf{};
+    }
+    c->mid_n = P.n_before + P.n_join;
+    c->mid_nbytes = P.bytes_before + P.join_bytes;
+}
+
+// The registry and the id table cover the same rows: mmp_models_load, mmp_models_ingest_json and an append by index
+// (mmp_models_upsert / mmp_models_upsert_json) resize the registry without telling the id table (the rule of id_space_guard).
+int model_id_space_guard(mmp_ctx *c, const char *fn)
+{
+    if (!c->have_model_ids) return fail(c, MMP_ESTATE, "%s: load the model ids first (mmp_model_ids_load)", fn);
+    if (c->mid_n == c->n_models) return MMP_OK;
+    return fail(c, MMP_ESTATE, "%s: the registry has %d rows for %d loaded model ids (resized by index since mmp_model_ids_load)", fn,
+                c->n_models, c->mid_n);
+}
+}  // namespace
+
+int mmp_model_ids_load(mmp_ctx *c, const char *ids, const int32_t *id_off, int32_t n_models)
+try {
+    if (!c || n_models < 0 || (n_models > 0 && !id_off)) return fail(c, MMP_EINVAL, "mmp_model_ids_load: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (n_models != c->n_models)
+        return fail(c, MMP_ESTATE, "mmp_model_ids_load: %d ids for a registry of %d rows", n_models, c->n_models);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    ModelIdsPlan P;
+    if (n_models == 0) {  // a valid start: the empty table, every id joins through mmp_models_events_json
+        P.cap = 16;
+        HIP_TRY(c, c->mid_next_hash.ensure((size_t)P.cap * 8));
+        HIP_TRY(c, c->mid_next_val.ensure((size_t)P.cap * 4));
+        HIP_TRY(c, P.fresh_bytes.ensure(16));
+        HIP_TRY(c, P.fresh_off.ensure(4));
+        if (const int rc = mid_empty_table(c, HashTabW{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), P.cap - 1})) return rc;
+        HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        if (const int rc = model_ids_plan(c, "mmp_model_ids_load", ids, id_off, n_models, nullptr, true, true, P)) return rc;
+        if (P.n_join != n_models) {  // up to the first repeat an id's row is its index
+            int32_t i = 0;
+            while (i < n_models && P.idx[i] == i) i++;
+            return fail(c, MMP_EINVAL, "mmp_model_ids_load: ids %d and %d are equal", i < n_models ? P.idx[i] : -1, i);
+        }
+    }
+    model_ids_publish(c, P);
+    c->have_model_ids = true;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_model_ids_load")
+
+int mmp_model_ids_resolve(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, int32_t *model_idx_out)
+try {
+    if (!c || n < 0 || (n > 0 && (!key_off || !model_idx_out))) return fail(c, MMP_EINVAL, "mmp_model_ids_resolve: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, "mmp_model_ids_resolve")) return rc;
+    if (n == 0) return MMP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel;
+    if (const int rc = stage_ids(c, "mmp_model_ids_resolve", "key", keys, key_off, n, krel)) return rc;
+    HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
+    HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    const int bits = c->tune.model_id_hash_bits;
+    const uint64_t hmask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+    const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, st, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hmask, c->me_hash.as<uint64_t>());
+    hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, st, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, c->me_hash.as<uint64_t>(),
+                       ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(), c->mid_off.as<int32_t>()},
+                       c->me_row.as<int32_t>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_model_ids_resolve")
+
+int mmp_model_ids_get(mmp_ctx *c, int32_t first_row, int32_t n_rows, char *bytes_out, int32_t max_bytes, int32_t *off_out,
+                      int32_t *n_bytes_out)
+try {
+    if (!c || first_row < 0 || n_rows < 0 || !n_bytes_out || max_bytes < 0 || (max_bytes > 0 && !bytes_out))
+        return fail(c, MMP_EINVAL, "mmp_model_ids_get: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, "mmp_model_ids_get")) return rc;
+    if ((int64_t)first_row + n_rows > c->mid_n)
+        return fail(c, MMP_EINVAL, "mmp_model_ids_get: rows [%d, %d + %d) of %d", first_row, first_row, n_rows, c->mid_n);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    std::vector<int32_t> offs((size_t)n_rows + 1);
+    HIP_TRY(c, copy_sync(c, offs.data(), c->mid_off.as<int32_t>() + first_row, ((size_t)n_rows + 1) * 4, hipMemcpyDeviceToHost));
+    const int32_t nb = offs[n_rows] - offs[0];
+    *n_bytes_out = nb;
+    if (off_out)
+        for (int32_t r = 0; r <= n_rows; r++) off_out[r] = offs[r] - offs[0];
+    if (nb > 0 && max_bytes >= nb) HIP_TRY(c, copy_sync(c, bytes_out, c->mid_bytes.as<char>() + offs[0], (size_t)nb, hipMemcpyDeviceToHost));
+    if (c->prof) c->last_kernel_ms = -1;  // two copies, no kernel
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_model_ids_get")
+
+int mmp_models_events_json(mmp_ctx *c, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                           const uint8_t *deleted, uint32_t flags, int32_t *model_idx_out, int64_t *last_unload_out, int32_t *status_out,
+                           int32_t *n_appended_out)
+try {
+    if (!c || n < 0 || (flags & ~MMP_MEV_APPEND) || (n > 0 && (!key_off || !off || !model_idx_out || !status_out)))
+        return fail(c, MMP_EINVAL, "mmp_models_events_json: bad argument");
+    // the locking of mmp_models_upsert_json; the id table is read and written under batch_mu only
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_models_events_json: load the instance ids first (mmp_pod_ids_load)");
+    // a key resolves to a row of the id space and the pipeline rewrites the registry row of that number: the two must be one space
+    if (const int rc = model_id_space_guard(c, "mmp_models_events_json")) return rc;
+    if (n_appended_out) *n_appended_out = 0;
+    if (n == 0) return MMP_OK;
+    for (int32_t i = 0; i < n; i++)  // (both kinds, before anything is staged: a refused call changes nothing)
+        if (off[i + 1] < off[i] || key_off[i + 1] < key_off[i])
+            return fail(c, MMP_EINVAL, "mmp_models_events_json: offsets not monotone at %d", i);
+    if ((off[n] > off[0] && !buf) || (key_off[n] > key_off[0] && !keys)) return fail(c, MMP_EINVAL, "mmp_models_events_json: bad argument");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    ModelIdsPlan P;
+    if (const int rc = model_ids_plan(c, "mmp_models_events_json", keys, key_off, n, deleted, flags & MMP_MEV_APPEND, false, P)) return rc;
+    if (P.k > 0) {
+        // everything behind the resolution is mmp_models_upsert_json: slot / slot_model are on the device already
+        UpsertJsonEvents E{};
+        E.slot = c->j_ev.as<int32_t>();
+        E.slot_model = E.slot + n;
+        E.win = E.slot_model + n;
+        E.s_cnt = E.win + n + 1;
+        E.s_offs = E.s_cnt + n + 1;
+        E.deleted = deleted ? c->me_del.as<uint8_t>() : nullptr;
+        E.k = P.k;
+        E.count = P.n_before + P.n_join;
+        HIP_TRY(c, hipMemsetAsync(E.win, 0xff, ((size_t)P.k + 1) * 4, st));
+        std::vector<int32_t> h_model;
+        if (const int rc = models_upsert_json_run(c, "mmp_models_events_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
+        if (c->prof && P.ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += P.ms;  // the call's device span: resolve + parse + apply
+        model_ids_publish(c, P);
+    } else if (c->prof)
+        c->last_kernel_ms = P.ms;
+    for (int32_t i = 0; i < n; i++) {
+        model_idx_out[i] = P.idx[i];
+        if (P.idx[i] >= 0) continue;
+        status_out[i] = 2;  // an unknown id: nothing was read, nothing changes
+        if (last_unload_out) last_unload_out[i] = 0;
+    }
+    if (n_appended_out) *n_appended_out = P.n_join;
+    return P.k > 0 ? squeeze_if_garbage(c) : (int)MMP_OK;
+} MMP_CATCH(c, "mmp_models_events_json")
 
 int mmp_pods_get(mmp_ctx *c, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out)
 try {

@@ -273,6 +273,53 @@ class Solver:
             self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
         return status[:n], lul[:n]
 
+    def model_ids_load(self, ids):
+        """Name the registry's rows (mmp_model_ids_load): ids[i] (bytes/str) is the id of row i; len(ids) must equal the row count."""
+        blob, off = self._pack(ids)
+        off32 = off.astype(np.int32)
+        self._ck(self.lib.mmp_model_ids_load(self.h, blob, ptr(off32), len(ids)))
+
+    def model_ids_resolve(self, keys):
+        """The registry row of every key, -1 for an unknown id (mmp_model_ids_resolve)."""
+        blob, off = self._pack(keys)
+        off32 = off.astype(np.int32)
+        n = len(keys)
+        out = np.full(max(n, 1), -1, np.int32)
+        self._ck(self.lib.mmp_model_ids_resolve(self.h, blob, ptr(off32), n, ptr(out)))
+        return out[:n]
+
+    def model_ids_get(self, first_row=0, n_rows=None):
+        """The ids (bytes) of rows [first_row, first_row + n_rows) (mmp_model_ids_get); n_rows=None: up to the last row."""
+        if n_rows is None:
+            n_rows = self.n_models - first_row
+        nb = C.c_int32(0)
+        self._ck(self.lib.mmp_model_ids_get(self.h, int(first_row), int(n_rows), None, 0, None, C.byref(nb)))
+        buf = np.zeros(max(nb.value, 1), np.uint8)
+        off = np.zeros(n_rows + 1, np.int32)
+        self._ck(self.lib.mmp_model_ids_get(self.h, int(first_row), int(n_rows), ptr(buf), nb.value, ptr(off), C.byref(nb)))
+        raw = buf.tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(n_rows)]
+
+    def models_events_json(self, keys, values, deleted=None, append=True):
+        """Registry events by key (mmp_models_events_json): keys[i] is the model id (bytes/str), values[i] its ModelRecord JSON,
+        deleted[i] marks ENTRY_DELETED.  Returns (status, model_idx, last_unload, n_appended)."""
+        kblob, koff = self._pack(keys)
+        koff32 = koff.astype(np.int32)
+        blob, off = self._pack(values)
+        n = len(keys)
+        assert len(values) == n
+        deleted = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+        lul = np.zeros(max(n, 1), np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        idx = np.full(max(n, 1), -1, np.int32)
+        n_app = C.c_int32(0)
+        self._ck(self.lib.mmp_models_events_json(self.h, kblob, ptr(koff32), blob, ptr(off), n, ptr(deleted),
+                                                 _lib.MEV_APPEND if append else 0, ptr(idx), ptr(lul), ptr(status), C.byref(n_app)))
+        if n:
+            self.n_models = getattr(self, "n_models", 0) + n_app.value
+            self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
+        return status[:n], idx[:n], lul[:n], n_app.value
+
     def get_pods(self) -> np.ndarray:
         n = C.c_int32(0)
         self._ck(self.lib.mmp_pods_get(self.h, None, 0, C.byref(n)))
