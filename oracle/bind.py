@@ -476,7 +476,7 @@ def subset_stats(fleet, mask, global_stats):
     out["total_capacity"] = int(pods["capacity"][sel].sum())
     out["total_free"] = int(rem[sel & (rem >= fleet.min_space_units)].sum())
     out["instance_count"] = int(sel.sum())
-    out["model_copy_count"] = int(pods["count"][sel].sum())
+    out["model_copy_count"] = (int(pods["count"][sel].sum(dtype=np.int64)) + 2**31) % 2**32 - 2**31  # a Java int: it wraps
     out["global_lru"] = int(global_stats["global_lru"]) if sel.any() else 2**63 - 1
     return out
 

@@ -6,7 +6,8 @@ reference tree and only reads the committed file).
 Per load-target case: the clusterState iteration order, and per request (chosen, candidates.size(), survivors of the rpm
 filter, audit hash of the shortlist).  Per serve-target case: (chosen, chosenTimeStamp).  Per guard case: (MMP_GATE_* bits,
 loadLocal's initial size).  Plus a digest of each case's inputs.
-usage: python oracle/ref_harness/make_ref_vectors.py"""
+tests/golden/ref_gate_edges.npz: the guard cases at the edges of their value domain (gate_edge_vectors below).
+usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges]"""
 import os
 import subprocess
 import sys
@@ -22,6 +23,7 @@ from tests import ref_fleets as rf  # noqa: E402
 # touching the committed vectors
 HARNESS = os.environ.get("MMP_REF_HARNESS") or os.path.join(ROOT, "oracle", "_ref", "ref_harness")
 OUT = os.environ.get("MMP_REF_OUT") or os.path.join(ROOT, "tests", "golden", "ref_getnext.npz")
+EDGE_OUT = os.environ.get("MMP_REF_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_gate_edges.npz")
 
 
 def proactive_inputs(fleet, units, partitioned):
@@ -129,9 +131,74 @@ def run(blob: bytes, n_place: int, n_serve: int, n_gate: int = 0, n_scale: int =
     return order, place, serve, gate, scale, called, ov
 
 
+GUARDS = ["goLocal", "failures", "locations", "notAllowed", "churn", "earlyReject", "reload", "publish"]
+
+
+def gate_edge_vectors():
+    """tests/golden/ref_gate_edges.npz: the guards at the edges of their value domain (tests/ref_fleets.py:gate_edge_cases).  A case
+    that does not hold what it is there for is REFUSED: the assertions below read the inputs and the reference's own outputs."""
+    from oracle import bind as ob
+    out, names = {}, []
+    tier_bits, tier_rows, tier_sizing = {}, {}, {}
+    for name, fleet, ids, reqs, xp, xt, expl, expiry in rf.gate_edge_cases():
+        tier = rf.gate_edge_tier(name)
+        assert tier in rf.GATE_EDGE_TIERS and fleet.n_pods in (8, 24, 64, 65) and fleet.n_models <= 60 and len(reqs) <= 2000, name
+        tstats = np.ascontiguousarray(ob.type_set_stats(fleet))
+        blob = rf.input_blob(fleet, ids, gates=(reqs, xp, xt, expl, expiry, tstats))
+        _, _, _, gate = run(blob, 0, 0, len(reqs))
+        assert np.array_equal(run(blob, 0, 0, len(reqs), env={"MMP_REF_EXC_CONTEXT": "1"})[3], gate), name
+        bits = gate[:, 0].astype(np.uint32)
+        sized = (bits & 32) == 0
+        assert sized.mean() >= 0.5, (name, "the initial size is observable in fewer than half of the rows", sized.mean())
+        if tier == "timed":
+            want = {(x, e, k) for x in (False, True) for e in (False, True) for k in ("equal", "off", "any")}
+            assert rf.timed_combinations(fleet, reqs, xp, xt) == want, name
+            # ... and they decide: the same rows with every exclusion's time erased (a key exclude) go another way somewhere
+            any_time = np.full(len(xt), rf._lib.ANY_TIME, np.int64)
+            g2 = run(rf.input_blob(fleet, ids, gates=(reqs, xp, any_time, expl, expiry, tstats)), 0, 0, len(reqs))[3]
+            assert ((g2[:, 0] ^ gate[:, 0]) & 1).sum() >= 20, (name, "the exclusions' times decide too few rows")
+        outcome = rf.sizing_outcomes(fleet, reqs, tstats)
+        seen = tier_sizing.setdefault(tier, {})
+        for i in np.nonzero(sized)[0]:
+            q, o, v = reqs[i], outcome[i], int(gate[i, 1])
+            if o is None:
+                assert v == q["loader_predicted"], (name, i)
+                continue
+            ok = {"hint": v == q["size_hint"], "negative estimate": v < -1, "positive estimate": v > 0, "estimate -1": v == -1,
+                  "estimate 0: loader_predicted": v == q["loader_predicted"]}[o]
+            assert ok, (name, int(i), o, v)
+            seen[o] = seen.get(o, 0) + 1
+        if tier == "totals":
+            eng = [int(s["total_capacity"] - s["total_free"]) for s in tstats[1:10]]
+            c = int(tstats[1]["model_copy_count"])
+            assert eng == [2**31 - 1, 2**31, 2**31 + 5, 2**32 - 2 * c, 2**32 - c - 1, 2**32 - 1, 2**32, 2**32 + 99, 10**10], (name, eng)
+            assert all(int(s["model_copy_count"]) == c for s in tstats[1:]), name
+            assert [int(s["instance_count"]) for s in tstats[10:13]] == [1, 2, 2], name
+            assert 20 * int(tstats[10]["total_free"]) == int(tstats[10]["total_capacity"]), name
+            assert 20 * int(tstats[11]["total_free"]) == int(tstats[11]["total_capacity"]), name
+            assert 20 * int(tstats[12]["total_free"]) == int(tstats[12]["total_capacity"]) - 1, name
+        tier_bits.setdefault(tier, []).append(bits)
+        tier_rows[tier] = tier_rows.get(tier, 0) + len(reqs)
+        out[f"{name}/gate"] = gate
+        out[f"{name}/digest"] = np.frombuffer(rf.digest(blob).encode(), np.uint8)
+        names.append(name)
+        print(f"{name}: {len(reqs)} guard evaluations, {100 * sized.mean():.0f} % sized; fired: " +
+              " ".join(f"{b}:{int(((bits >> k) & 1).sum())}" for k, b in enumerate(GUARDS)))
+    for tier in rf.GATE_EDGE_TIERS:
+        bits = np.concatenate(tier_bits[tier])
+        assert int(np.bitwise_or.reduce(bits)) == 255 and int(np.bitwise_and.reduce(bits)) == 0, (tier, "a guard bit is never set or never clear")
+        print(f"tier {tier}: {tier_rows[tier]} rows; sizing outcomes among the sized rows: {tier_sizing[tier]}")
+    assert all(tier_sizing["totals"].get(o, 0) > 0 for o in rf.SIZING_OUTCOMES), tier_sizing["totals"]
+    out["names"] = np.array(names)
+    np.savez_compressed(EDGE_OUT, **out)
+    print(f"wrote {EDGE_OUT}: {os.path.getsize(EDGE_OUT) / 1e6:.2f} MB, {len(names)} cases")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
+    if "--gate-edges" in sys.argv[1:]:  # only the guard edge cases: ref_getnext.npz stays as it is
+        return gate_edge_vectors()
     out = {}
     names = []
     for name, fleet, ids, reqs, extra in rf.place_cases():
@@ -295,6 +362,7 @@ def main():
     out["manifest"] = np.array(open(os.path.join(ROOT, "oracle", "_ref", "gen", "MANIFEST.txt")).read())
     np.savez_compressed(OUT, **out)
     print(f"wrote {OUT}: {os.path.getsize(OUT) / 1e6:.2f} MB, {len(names)} cases")
+    gate_edge_vectors()
 
 
 if __name__ == "__main__":

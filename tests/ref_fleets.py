@@ -1,4 +1,4 @@
-"""Fleets and requests of the reference-text vectors (tests/golden/ref_getnext.npz): built here, deterministically from
+"""Fleets and requests of the reference-text vectors (tests/golden/ref_getnext.npz, ref_gate_edges.npz): built here, deterministically from
 seeds, so that the generator (oracle/ref_harness/make_ref_vectors.py — needs /root/reference) and the tests that consume
 the committed vectors (CPU: the oracle; GPU: the HIP path) construct byte-identical inputs.  A digest of the inputs is stored
 with the vectors and checked by the tests.
@@ -245,6 +245,578 @@ def gate_cases():
         r["explicit_off"], r["n_explicit"] = xoff[:-1], nx
         explicit = rng.integers(0, P, int(xoff[-1])).astype(np.int32)
         yield f"gates_{seed}", fleet, ids, r, excl_pod, excl_time, explicit, 450_000
+
+
+INT_MIN, INT_MAX, LONG_MIN, LONG_MAX = -(2**31), 2**31 - 1, -(2**63), 2**63 - 1
+GATE_EDGE_TIERS = ("timed", "totals", "thresholds", "wrap")
+GATE_EXPIRY = 450_000
+GATE_CUTOFF = 10  # weight_predict_cutoff of the engineered rows
+N_TOTALS_PLAIN = 300  # ordinary rows behind the engineered ones of a gate_totals case
+
+
+def _edge_fleet(P, seed, groups=()):
+    """An orderly fleet (one version, every instance live and present, nothing full) that the tiers below then bend where they
+    need to.  groups: type t + 1 may only be placed on the instances groups[t]; type 0 is unconstrained."""
+    rng = np.random.default_rng(0xE06E + seed)
+    now = wl.NOW_MS
+    rows = np.zeros(P, dtype=_lib.POD_ROW)
+    rows["capacity"] = 1_000_000
+    rows["used"] = rng.choice([200_000, 500_000, 900_000], P)
+    rows["count"] = rng.integers(1, 30, P)
+    rows["lru_time"] = now - rng.integers(400_000, 9_000_000, P)
+    rows["rpm"] = rng.choice([0, 50, 500, 5000], P)
+    rows["loading_threads"] = 8
+    rows["loading_in_progress"] = rng.integers(0, 3, P)
+    rows["version"] = 7
+    rows["id_order"] = rng.permutation(P)
+    rows["replica_set"] = rng.integers(0, 3, P)
+    rows["flags"] = _lib_flag_live()
+    fleet = wl.Fleet(pods=rows, models=np.zeros(0, _lib.MODEL_ROW), ent_pod=np.zeros(0, np.int32), ent_time=np.zeros(0, np.int64),
+                     min_space_units=6553, min_churn_age_ms=600_000, now=now)
+    if groups:
+        T = len(groups) + 1
+        al = np.zeros((T, P), bool)
+        al[0] = True
+        for t, g in enumerate(groups):
+            al[t + 1, list(g)] = True
+        fleet.n_types = T
+        fleet.allowed, fleet.prefer = wl.bitmap_from_bool(al), wl.bitmap_from_bool(np.zeros((T, P), bool))
+        fleet.has_allowed, fleet.has_prefer = np.array([0] + [1] * len(groups), np.uint8), np.zeros(T, np.uint8)
+    return fleet, rng
+
+
+def _set_models(fleet, specs):
+    """specs: [(type, copies, failed)] -> the registry, each list in instance-id order (as instanceIds / loadFailedInstanceIds
+    iterate; string_ids has run, so id_order IS that order).  Times are set by the caller, by POSITION."""
+    rank = fleet.pods["id_order"]
+    rows = np.zeros(len(specs), dtype=_lib.MODEL_ROW)
+    ent = []
+    for i, (ty, lp, fp) in enumerate(specs):
+        lp = sorted((int(p) for p in lp), key=lambda p: rank[p])
+        fp = sorted((int(p) for p in fp), key=lambda p: rank[p])
+        rows[i] = (ty, len(ent), len(lp), len(fp), fleet.now - 5_000)
+        ent += lp + fp
+    fleet.models = rows
+    fleet.ent_pod = np.array(ent, np.int32)
+    fleet.ent_time = np.full(len(ent), fleet.now - 3_000_000, np.int64)
+
+
+def _copies(fleet, i):
+    m = fleet.models[i]
+    a, k, f = int(m["ent_off"]), int(m["n_loaded"]), int(m["n_failed"])
+    return fleet.ent_pod[a:a + k], fleet.ent_time[a:a + k], fleet.ent_pod[a + k:a + k + f], fleet.ent_time[a + k:a + k + f]
+
+
+def _count_specs(rng, P, n_types):
+    """A few models with enough copies / failure records for the two caps (the tiers that are about something else still have to
+    see every guard both ways)."""
+    out = []
+    for k, f in ((5, 3), (6, 0), (2, 5), (4, 2)):
+        pods = rng.choice(P, size=min(k + f, P), replace=False)
+        out.append((int(rng.integers(0, max(n_types, 1))), list(pods[:min(k, P)]), list(pods[min(k, P):])))
+    return out
+
+
+def _edge_rows(fleet, rng, model, self_pod):
+    """Ordinary values in every field of a guard request (as gate_cases draws them), no exclusions; the tiers overwrite what
+    they are about."""
+    n, now = len(model), fleet.now
+    r = np.zeros(n, dtype=_lib.GATE_REQ)
+    r["model"], r["self_pod"] = model, self_pod
+    r["flags"] = rng.integers(0, 512, n)
+    r["size_hint"] = rng.choice([0, 1, 6400, 2_000_000], n)
+    r["last_used_time"] = rng.choice([0, now - 5_000, now - 4_000_000], n)
+    r["cache_capacity"] = rng.choice([131072, 1_000_000], n)
+    r["cache_weighted_size"] = (r["cache_capacity"] * rng.choice([0.1, 0.96, 0.999, 1.0], n)).astype(np.int64)
+    r["cache_oldest_time"] = rng.choice([-1, LONG_MAX, now - 1_000, now - 4_500_000, now - 700_000], n)
+    r["loader_predicted"] = rng.choice([6400, 1, 200_000], n)
+    r["loading_count"] = rng.integers(0, 20, n)
+    r["weight_predict_cutoff"] = GATE_CUTOFF
+    r["loaded_time"] = rng.choice([-1, now - 1_000, now - 200_000, now - 5_000_000], n)
+    r["load_timeout_ms"] = rng.choice([90_000, 720_000], n)
+    cur = fleet.pods[r["self_pod"]]
+    near = rng.random(n) < 0.6
+    r["fresh_lru"] = np.where(near, cur["lru_time"], cur["lru_time"] - rng.choice([0, 10_000, 30_000], n))
+    r["fresh_capacity"] = np.where(near, cur["capacity"], cur["capacity"] - rng.choice([0, 100, 50_000], n))
+    r["fresh_used"] = np.where(near, cur["used"], (cur["used"] * rng.choice([1.0, 1.1, 1.3], n)).astype(np.int64))
+    r["fresh_count"] = cur["count"] + rng.choice([0, 0, 1, 2, 10], n)
+    r["fresh_loading_threads"] = np.where(rng.random(n) < 0.9, cur["loading_threads"], 3)
+    r["fresh_in_progress"] = cur["loading_in_progress"] + rng.choice([0, 0, 1, 3], n)
+    r["fresh_rpm"] = cur["rpm"] + rng.choice([0, 0, 5, 99, 100, 1000], n)
+    r["last_published"] = now - rng.choice([500, 2_500, 38_000, 39_500, 100_000, 170_000], n)
+    return r
+
+
+def _publish_row(fleet, rng, p, lp=50_000, flags=0, **over):
+    """One row of caller p whose fresh record EQUALS the table's (published lp ms ago: checked, not old, nothing to publish), with
+    the fields in `over` moved: that field alone decides publishInstanceRecord."""
+    q = _edge_rows(fleet, rng, np.array([0]), np.array([p]))
+    cur = fleet.pods[p]
+    q["flags"] = (q["flags"] & np.uint32(63)) | flags | (256 if cur["flags"] & 1 else 0)
+    q["fresh_lru"], q["fresh_capacity"], q["fresh_used"], q["fresh_count"] = cur["lru_time"], cur["capacity"], cur["used"], cur["count"]
+    q["fresh_loading_threads"], q["fresh_in_progress"], q["fresh_rpm"] = cur["loading_threads"], cur["loading_in_progress"], cur["rpm"]
+    q["last_published"] = fleet.now - lp
+    for k, v in over.items():
+        q[k] = v
+    return q
+
+
+def _i32(x):
+    return (int(x) + 2**31) % 2**32 - 2**31
+
+
+def _i64(x):
+    return (int(x) + 2**63) % 2**64 - 2**63
+
+
+def _random_rows(fleet, rng, n):
+    """n ordinary rows: the caller is one of the model's copies more often than not; short lists of key excludes and explicit
+    excludes on some."""
+    P = fleet.n_pods
+    model = rng.integers(0, fleet.n_models, n)
+    self_pod = rng.integers(0, P, n)
+    for i in range(n):
+        lp = _copies(fleet, model[i])[0]
+        if len(lp) and rng.random() < 0.6:
+            self_pod[i] = lp[rng.integers(0, len(lp))]
+    r = _edge_rows(fleet, rng, model, self_pod)
+    excl = [[(int(rng.integers(0, P)), _lib.ANY_TIME) for _ in range(int(rng.integers(1, 8)))] if rng.random() < 0.3 else [] for _ in range(n)]
+    expl = [[int(x) for x in rng.integers(0, P, int(rng.integers(1, 8)))] if rng.random() < 0.4 else [] for _ in range(n)]
+    return r, excl, expl
+
+
+def _with_lists(r, excl, expl):
+    """excl: per row [(instance, time)]; expl: per row [instance] -> (rows with the offsets set, excl_pod, excl_time, explicit)."""
+    r = r.copy()
+    ne, nx = np.array([len(x) for x in excl], np.int64), np.array([len(x) for x in expl], np.int64)
+    r["excl_off"], r["n_excl"] = np.cumsum(ne) - ne, ne
+    r["explicit_off"], r["n_explicit"] = np.cumsum(nx) - nx, nx
+    excl_pod = np.array([p for x in excl for p, _ in x], np.int32)
+    excl_time = np.array([t for x in excl for _, t in x], np.int64)
+    explicit = np.array([p for x in expl for p in x], np.int32)
+    return r, excl_pod, excl_time, explicit
+
+
+def _cat(parts):
+    rows = np.concatenate([p[0] for p in parts])
+    return rows, [x for p in parts for x in p[1]], [x for p in parts for x in p[2]]
+
+
+def timed_combinations(fleet, r, excl_pod, excl_time):
+    """{(exclusion at index >= 4, copy at index >= 4, 'equal' | 'off' | 'any')}: which pairs of an exclusion and a copy of the
+    same instance a set of rows holds ('off': the exclusion's time is the copy's + 1, so it must NOT filter)."""
+    seen = set()
+    for q in r:
+        lp, lt, _, _ = _copies(fleet, q["model"])
+        for x in range(q["n_excl"]):
+            p, t = excl_pod[q["excl_off"] + x], excl_time[q["excl_off"] + x]
+            for e in np.nonzero(lp == p)[0]:
+                kind = "any" if t == _lib.ANY_TIME else "equal" if t == lt[e] else "off" if t == lt[e] + 1 else None
+                if kind:
+                    seen.add((x >= 4, bool(e >= 4), kind))
+    return seen
+
+
+def _timed_case(P, seed, typed):
+    fleet, rng = _edge_fleet(P, seed, [range(0, P, 2), range(P // 2, P)] if typed else ())
+    ids = string_ids(fleet, 300 + seed)
+    now = fleet.now
+    specs = []
+    for k in range(1, 9):
+        for j in range(6):
+            pods = rng.choice(P, size=k, replace=False)
+            if P > 64 and j < 3 and P - 1 not in pods:
+                pods[0] = P - 1  # the caller of the second bitmap word holds copies too
+            specs.append((int(rng.integers(0, fleet.n_types)) if typed else 0, list(pods), []))
+    specs += _count_specs(rng, P, fleet.n_types)
+    _set_models(fleet, specs)
+    fleet.ent_time[:] = now - rng.choice([0, 1499, 1500, 50_000], len(fleet.ent_time))
+    model, self_pod, flags, excl = [], [], [], []
+    lo, hi = [(1, 0), (4, 3), (9, 0), (3, 1)], [(5, 4), (9, 8), (7, 5), (9, 4)]  # (list length, index of the pair that matters)
+    c = 0
+
+    def filler(lp, lt, others):
+        if len(others) and rng.random() < 0.5:
+            return int(rng.choice(others)), _lib.ANY_TIME  # not a copy of the model
+        q = int(rng.integers(0, len(lp)))
+        return int(lp[q]), int(lt[q]) + 1 + int(rng.integers(0, 2))  # a copy, at another time: filters nothing
+    for i in range(48):
+        lp, lt, _, _ = _copies(fleet, i)
+        k = len(lp)
+        others = np.setdiff1d(np.arange(P), lp)
+        for e in range(k):
+            for kind in range(3):
+                for where in (lo, hi):
+                    L, x = where[c % 4]
+                    lst = [filler(lp, lt, others) for _ in range(L)]
+                    lst[x] = (int(lp[e]), [_lib.ANY_TIME, int(lt[e]), int(lt[e]) + 1][kind])
+                    model.append(i)
+                    self_pod.append(int([lp[e], lp[(e + 1) % k], rng.integers(0, P)][c % 3]))  # its own copy excluded: has_local flips
+                    flags.append(3 if c % 2 == 0 else int(rng.integers(0, 8)))
+                    excl.append(lst)
+                    c += 1
+        for keep in (0, k - 1) if k >= 2 else ():  # every copy but one excluded: filteredCount == 1
+            lst = [(int(lp[e]), _lib.ANY_TIME if (e + c) % 2 else int(lt[e])) for e in range(k) if e != keep]
+            model.append(i)
+            self_pod.append(int(lp[keep] if c % 2 else lp[(keep + 1) % k]))
+            flags.append(int(rng.integers(0, 8)))
+            excl.append([lst[j] for j in rng.permutation(len(lst))])
+            c += 1
+    r = _edge_rows(fleet, rng, np.array(model), np.array(self_pod))
+    r["flags"] = (r["flags"] & ~np.uint32(7)) | np.array(flags, np.uint32)
+    expl = [[int(x) for x in rng.integers(0, P, int(rng.integers(1, 8)))] if rng.random() < 0.3 else [] for _ in range(len(r))]
+    rows, excl, expl = _cat([(r, excl, expl), _random_rows(fleet, rng, 200)])
+    return (fleet, ids) + _with_lists(rows, excl, expl) + (GATE_EXPIRY,)
+
+
+def estimate_of(total_capacity, total_free, copy_count):
+    """loadLocal's -(1 + (int) (totalCapacity - totalFree) / copyCount) in Java's arithmetic (MM.java:5170-5175) — used to AIM
+    the engineered rows (cache sizes on either side of |initialSize|) and to name the sizing outcome of a row; the expected
+    outputs come from the reference."""
+    d = (total_capacity - total_free) & 0xFFFFFFFF
+    d -= (d >> 31) << 32
+    q = abs(d) // copy_count * (1 if d >= 0 else -1)
+    e = (-(1 + q)) & 0xFFFFFFFF
+    return e - ((e >> 31) << 32)
+
+
+def totals_plan(P, c):
+    """The instance groups of a gate_totals fleet: [(instances, capacity - free or None, copies, what)]; type t + 1 <-> group t."""
+    used = [2**31 - 1, 2**31, 2**31 + 5, 2**32 - 2 * c, 2**32 - c - 1, 2**32 - 1, 2**32, 2**32 + 99]
+    plan = [(list(range(5 * i, 5 * i + 5)), d, c, "used") for i, d in enumerate(used)]
+    plan.append((list(range(40, 52)), 10**10, c, "used"))
+    plan.append(([52], None, c, "one instance, 20 * free == capacity"))
+    plan.append(([53, 54], None, c, "20 * free == capacity"))
+    plan.append(([55, P - 1], None, c, "20 * free == capacity - 1"))
+    return plan
+
+
+def _totals_case(P, c, seed):
+    plan = totals_plan(P, c)
+    fleet, rng = _edge_fleet(P, seed, [g for g, _, _, _ in plan])
+    ids = string_ids(fleet, 320 + seed)
+    now, pods = fleet.now, fleet.pods
+    for g, d, copies, what in plan:
+        k = len(g)
+        pods["count"][g] = copies // k
+        pods["count"][g[0]] += copies - copies // k * k
+        if d is not None:  # nothing full: capacity - free = the sum of `used`
+            pods["capacity"][g] = 2**29 if d // k < 2**29 - 2**20 else 2**30
+            pods["used"][g] = d // k
+            pods["used"][g[0]] += d - d // k * k
+        else:
+            free = [6_710_886, 13_421_772][:k] if k == 2 else [6_710_886]
+            for p, f in zip(g, free):
+                pods["capacity"][p], pods["used"][p] = 20 * f, 19 * f
+            if what.endswith("- 1"):
+                pods["capacity"][g[1]] += 1
+                pods["used"][g[1]] += 1
+    T = fleet.n_types
+    specs = []
+    for t in range(T):
+        g = plan[t - 1][0] if t else list(range(P))
+        specs += [(t, [], []), (t, [g[0]], []), (t, list(g[:2]), [g[-1]] if len(g) > 2 else [])]
+    specs += [(T + 3, [56], []), (-1, [57, 58], [])]  # no such type row: answered from row 0
+    specs += _count_specs(rng, P, T)
+    _set_models(fleet, specs)
+    fleet.ent_time[:] = now - rng.choice([100, 449_000, 451_000, 3_000_000], len(fleet.ent_time))
+    n_eng = len(specs) - 4
+    model = np.repeat(np.arange(n_eng), 27)
+    lc, hint, pred = (np.tile(a.reshape(-1), n_eng) for a in np.meshgrid([GATE_CUTOFF - 1, GATE_CUTOFF, GATE_CUTOFF + 1], [0, 1, 2], [0, 1, 6400],
+                                                                         indexing="ij"))
+    n = len(model)
+    self_pod = np.where(np.arange(n) % 4 == 0, P - 1, rng.integers(0, P, n))
+    r = _edge_rows(fleet, rng, model, self_pod)
+    r["loading_count"], r["loader_predicted"] = lc, pred
+    r["flags"] = np.where(hint > 0, r["flags"] | 32, r["flags"] & ~np.uint32(32))
+    r["size_hint"] = np.where(hint == 1, 0, 6400)
+    # the early reject on either side of equality: |initialSize| against the cache's capacity, then against its free space
+    pods_present = (pods["flags"] & 5) == 0
+    rem = np.maximum(pods["capacity"] - pods["used"], 0)
+    al = np.ones((max(T, 1), P), bool)
+    for t, (g, _, _, _) in enumerate(plan):
+        al[t + 1] = np.isin(np.arange(P), g)
+    for i in range(n):
+        ty = int(fleet.models["type"][model[i]])
+        sel = al[ty if 0 <= ty < T else 0] & pods_present
+        cap, free = int(pods["capacity"][sel].sum()), int(rem[sel & (rem >= fleet.min_space_units)].sum())
+        copies = int(pods["count"][sel].sum())
+        size = 6400 if hint[i] == 2 else 0
+        if not hint[i] and lc[i] > GATE_CUTOFF and copies >= 10:
+            size = estimate_of(cap, free, copies)
+        size = abs(size or int(pred[i]))
+        how, d = int(rng.integers(0, 3)), int(rng.integers(-1, 2))
+        r["flags"][i] = (r["flags"][i] & ~np.uint32(8)) | (8 if how else 0)
+        if how == 1:
+            r["cache_capacity"][i], r["cache_weighted_size"][i] = size + d, 0
+        elif how == 2:
+            r["cache_capacity"][i], r["cache_weighted_size"][i] = 2**40, 2**40 - (size + d)
+            r["last_used_time"][i], r["cache_oldest_time"][i] = now - 5_000, now - 1_000
+        # onEviction: now - loadedTime against 2 * loadTimeoutMs, around equality
+        r["flags"][i] &= ~np.uint32(16)
+        r["load_timeout_ms"][i], r["loaded_time"][i] = 90_000, now - (180_000 + int(rng.integers(-1, 2)))
+    excl, expl = [[] for _ in range(n)], [[] for _ in range(n)]
+    rows, excl, expl = _cat([(r, excl, expl), _random_rows(fleet, rng, N_TOTALS_PLAIN)])
+    return (fleet, ids) + _with_lists(rows, excl, expl) + (GATE_EXPIRY,)
+
+
+def _thresholds_case(P, seed, typed):
+    # three small groups that are about 20 * free / capacity (onEviction), as in the totals fleets
+    plan = [([52], "one instance"), ([53, 54], "20 * free == capacity"), ([55, 56], "20 * free == capacity - 1")] if typed else []
+    fleet, rng = _edge_fleet(P, seed, [g for g, _ in plan])
+    ids = string_ids(fleet, 340 + seed)
+    now, pods, msu = fleet.now, fleet.pods, fleet.min_space_units
+    for g, what in plan:
+        for p, f in zip(g, [6_710_886, 13_421_772]):
+            pods["capacity"][p], pods["used"][p] = 20 * f, 19 * f
+        if what.endswith("- 1"):
+            pods["capacity"][g[1]] += 1
+            pods["used"][g[1]] += 1
+    byrank = np.argsort(pods["id_order"])
+    mid = P // 2 + (byrank[P // 2] == P - 1)
+    tomb = int(byrank[mid])  # a tombstone in the middle of the id order: a copy list can hold it at any position
+    A, B, Cc, Dd, Fs = [p for p in (P - 1, 1, 2, 3, 4, 6, 7, 5) if p != tomb][:5]  # A = the last instance: the second bitmap word of 65
+    for p, (used, count, age, rpm, inprog) in ((A, (500_000, 40, 5_000_000, 5000, 5)), (B, (500_000, 1000, 160_000, 500, 8)),
+                                               (Dd, (1_000_000 - msu, 20, 3_000_000, 50, 1)), (Fs, (500_000, 10, 3_000_000, 50, 1))):
+        pods["capacity"][p], pods["used"][p], pods["count"][p], pods["lru_time"][p] = 1_000_000, used, count, now - age
+        pods["rpm"][p], pods["loading_in_progress"][p], pods["loading_threads"][p] = rpm, inprog, 8
+    pods["capacity"][Cc], pods["used"][Cc], pods["count"][Cc], pods["lru_time"][Cc] = 1_000_000, 0, 0, LONG_MAX  # an empty cache
+    pods["rpm"][Cc], pods["loading_in_progress"][Cc] = 0, 0
+    pods["flags"][tomb] = 4
+    pods["flags"][Fs] = 3  # announced its shutdown, still in the table
+    lower = [int(p) for p in byrank[:mid] if p != Fs]
+    upper = [int(p) for p in byrank[mid + 1:] if p != Fs]
+    r_, e_, o_ = now - GATE_EXPIRY + 1, now - GATE_EXPIRY, now - GATE_EXPIRY - 1  # failure times: > cutoff, at it, before it
+    fail_pat = [[r_, r_, r_], [r_, r_, e_, r_], [r_, e_, r_, o_, r_], [r_, r_, e_, o_, e_], [r_, r_, o_], [e_, e_, e_], [r_, o_, r_, e_, o_, r_],
+                [e_, o_, r_, r_, r_], [o_, o_, o_, o_, r_, r_]]
+    # copy lists by position: L an instance of the table, T the tombstone, X an instance the request excludes explicitly
+    loc_pat = ["LLLL", "LLLLL", "TLLLL", "TLLLLL", "LLLLT", "LLLLTL", "LLXLL", "LLXLLL", "LLLLXL", "LLLLLX", "LLTLXLL", "XLLLL"]
+    specs, loc_x = [], []
+    for times in fail_pat:
+        specs.append((0, [], list(rng.choice(P, size=len(times), replace=False))))
+    for pat in loc_pat:
+        t_at = pat.find("T")
+        if t_at >= 0:
+            cp = lower[:t_at] + [tomb] + upper[:len(pat) - t_at - 1]
+        else:
+            cp = upper[:len(pat)]
+        specs.append((0, cp, []))
+    go_times = [[100, 1499], [100, 1500], [1499, 100], [1500, 100], [1499, 1499, 100], [1500, 3000, 100], [0, 1500], [100, 100]]
+    for times in go_times:
+        specs.append((0, list(rng.choice(upper, size=len(times), replace=False)), []))
+    n_spec = len(specs)
+    specs += [(t + 1, [g[0]], []) for t, (g, _) in enumerate(plan)]
+    specs += _count_specs(rng, P, fleet.n_types)
+    _set_models(fleet, specs)
+    for i, times in enumerate(fail_pat):
+        m = fleet.models[i]
+        fleet.ent_time[m["ent_off"]: m["ent_off"] + m["n_failed"]] = times
+    for i, times in enumerate(go_times):
+        m = fleet.models[len(fail_pat) + len(loc_pat) + i]
+        fleet.ent_time[m["ent_off"]: m["ent_off"] + m["n_loaded"]] = now - np.array(times)
+    parts = []
+    # ---- the caps and goLocal's 1500 ms, by every caller kind
+    model, self_pod, expl = [], [], []
+    for i in range(n_spec):
+        lp = _copies(fleet, i)[0]
+        pat = loc_pat[i - len(fail_pat)] if len(fail_pat) <= i < len(fail_pat) + len(loc_pat) else ""
+        for rep in range(4):
+            model.append(i)
+            self_pod.append(int(lp[rep % len(lp)]) if len(lp) and rep < 3 else A)
+            x = [int(lp[j]) for j, ch in enumerate(pat) if ch == "X"]
+            pad = [int(p) for p in lower[:6] if p not in lp]
+            # the excluded copy sits before / after the explicit list's fourth entry
+            expl.append((pad[:rep + 2] + x + pad[rep + 2:rep + 3]) if x else (pad[:rep] if rep % 2 else []))
+    r = _edge_rows(fleet, rng, np.array(model), np.array(self_pod))
+    r["flags"] = (r["flags"] & ~np.uint32(7)) | 3  # favourSelfForHits, a cache entry that is not done: oldest() decides
+    parts.append((r, [[] for _ in range(len(r))], expl))
+
+    # ---- publishInstanceRecord: a fresh record equal to the table's, one field moved to just inside / outside its threshold
+    prow = []
+
+    def pub(p, lp=50_000, flags=0, **over):
+        prow.append(_publish_row(fleet, rng, p, lp, flags, **over))
+    cap, lru = 1_000_000, int(pods["lru_time"][A])
+    d_in = max(d for d in range(19_000, 21_000) if d < (cap - d) // 50)  # |cur - cap| < cap / 50, cap being the FRESH capacity
+    u_in = max(d for d in range(19_000, 21_000) if d < (cap + d) // 50)
+    for p in (A, B, Cc, Dd, Fs):
+        for lp, flags in ((1_999, 64), (2_000, 64), (38_999, 0), (39_000, 0), (1_999, 128), (500, 64 | 128)):
+            pub(p, lp, flags, fresh_count=int(pods["count"][p]) + 20)
+        for lp in (160_000, 160_001):
+            pub(p, lp, fresh_in_progress=int(pods["loading_in_progress"][p]) + 1 if p in (A, Cc) else int(pods["loading_in_progress"][p]))
+            pub(p, lp, fresh_used=int(pods["used"][p]) + 1)
+        pub(p, fresh_loading_threads=7)
+        pub(p, flags=256)
+        pub(p)
+    for d in (d_in, d_in + 1):
+        pub(A, fresh_capacity=cap - d)
+    for d in (u_in, u_in + 1):
+        pub(A, fresh_capacity=cap + d)
+    for d in (19_999, 20_000, -19_999, -20_000):
+        pub(A, fresh_lru=lru - d)
+    for d in (9_999, 10_000, -9_999, -10_000):  # (now - lruTime) / 16 = 10 000 for B
+        pub(B, fresh_lru=int(pods["lru_time"][B]) - d)
+    for cnt in (45, 46, 35, 34, 49, 50):  # 15 % of 40, then the ten copies
+        pub(A, fresh_count=cnt)
+    for cnt in (1009, 1010, 991, 990):
+        pub(B, fresh_count=cnt)
+    for used in (599_999, 600_000, 400_001, 400_000):
+        pub(A, fresh_used=used)
+    for rpm in (5099, 5100, 4901, 4900):
+        pub(A, fresh_rpm=rpm)
+    for rpm in (554, 555, 446, 445, 599, 600):  # 10 % of 500
+        pub(B, fresh_rpm=rpm)
+    for rpm in (0, 1):
+        pub(Cc, fresh_rpm=rpm)
+    for ip in (7, 8, 3, 2, 9):  # +-3 loads; 9 also crosses loadingThreads
+        pub(A, fresh_in_progress=ip)
+    for ip in (9, 7, 11, 5):
+        pub(B, fresh_in_progress=ip)
+    for ip in (0, 2, 3, 4):
+        pub(Dd, fresh_in_progress=ip)
+    for ip in (0, 1, 3):
+        pub(Cc, fresh_in_progress=ip)
+    for used in (1_000_000 - msu, 1_000_000 - msu + 1, 1_000_000 - msu - 1):  # isFull on either side
+        pub(Dd, fresh_used=used)
+    for lp in (50_000, 200_000):  # an empty cache: oldestTime() == -1 is Long.MAX_VALUE, the table's value
+        for fl in (-1, LONG_MAX, now - 1_000, 0):
+            pub(Cc, lp, fresh_lru=fl)
+        pub(A, lp, fresh_lru=-1)
+    for lp, flags in ((50_000, 0), (50_000, 256), (1_000, 256), (200_000, 256), (200_000, 0), (1_000, 128), (1_000, 128 | 256)):
+        pub(tomb, lp, flags)  # no record of the caller in the table: created unless it is shutting down
+    pr = np.concatenate(prow)
+    parts.append((pr, [[] for _ in range(len(pr))], [[] for _ in range(len(pr))]))
+
+    # ---- the churn guard and onEviction
+    n_c = 0
+    crow = []
+    for space in (msu - 1, msu, msu + 1):
+        for oldest in (now - fleet.min_churn_age_ms + 1, now - fleet.min_churn_age_ms, now - fleet.min_churn_age_ms - 1, now, -1, 0, 1, LONG_MAX,
+                       LONG_MAX - 1):
+            q = _edge_rows(fleet, rng, np.array([n_c % n_spec]), np.array([A]))
+            q["cache_capacity"], q["cache_weighted_size"], q["cache_oldest_time"] = 1_000_000, 1_000_000 - space, oldest
+            crow.append(q)
+            n_c += 1
+    ev_models = [n_spec + j for j in range(len(plan))]  # the engineered groups' models
+    for mi in ev_models + [0, len(fail_pat)]:
+        for timeout in (90_000, 720_000):
+            for d in (-1, 0, 1):
+                for failed, lt in ((0, now - 2 * timeout - d), (16, now - 2 * timeout - 1), (0, -1), (0, 0)):
+                    q = _edge_rows(fleet, rng, np.array([mi]), np.array([B]))
+                    q["flags"] = (q["flags"] & ~np.uint32(16)) | failed
+                    q["load_timeout_ms"], q["loaded_time"] = timeout, lt
+                    crow.append(q)
+    cr = np.concatenate(crow)
+    parts.append((cr, [[] for _ in range(len(cr))], [[] for _ in range(len(cr))]))
+    parts.append(_random_rows(fleet, rng, 300))
+    rows, excl, expl = _cat(parts)
+    return (fleet, ids) + _with_lists(rows, excl, expl) + (GATE_EXPIRY,)
+
+
+def _wrap_case(P, seed, typed):
+    """HOSTILE values: no mesh produces them.  What is pinned is that the device, like Java, wraps."""
+    fleet, rng = _edge_fleet(P, seed, [range(0, P, 3), range(1, P), [5, 7]] if typed else ())
+    ids = string_ids(fleet, 360 + seed)
+    now, pods = fleet.now, fleet.pods
+    if typed:  # two instances whose free space times 20 leaves 64 bits (onEviction's 20 * totalFree): only type 1 keeps small totals
+        pods["capacity"][[5, 7]], pods["used"][[5, 7]] = 2**61, 0
+    i32 = [0, 1, -1, 99, 100, 101, 2**30, INT_MAX, INT_MIN, INT_MIN + 1]
+    i64 = [0, 1, -1, now, 2**62, -(2**62), LONG_MAX, LONG_MIN, LONG_MIN + 1]
+    # the table's rows keep to the non-negative values in most places; `count` in all: PLACEMENT_ORDER subtracts counts
+    # (MM.java:4676), negative ones would make it no order at all, and the instance order is not what is tested here
+    odd = rng.random(P) < 0.5
+    for f in ("count", "rpm", "loading_threads", "loading_in_progress"):
+        pods[f] = np.where(odd, rng.choice([0, 1, 99, 100, 101, 2**30, INT_MAX], P), pods[f])
+    neg = [1, 2, 3, 4, 6, P - 1]  # rows whose rpm / loads in progress / loading threads are negative (compared, never subtracted, by the order)
+    pods["rpm"][neg[:3]] = [-1, INT_MIN, INT_MIN + 1]
+    pods["loading_in_progress"][neg[3:]] = [-1, INT_MIN, INT_MIN + 1]
+    pods["loading_threads"][neg[4]] = -1
+    pods["lru_time"] = np.where(rng.random(P) < 0.3, rng.choice([1, now, 2**62, LONG_MAX], P), pods["lru_time"])
+    specs = []
+    for _ in range(50):
+        k, f = int(rng.integers(0, min(8, P) + 1)), int(rng.integers(0, 7))
+        f = min(f, P - k)
+        ps = rng.choice(P, size=k + f, replace=False)
+        specs.append((int(rng.integers(0, max(fleet.n_types, 1))), list(ps[:k]), list(ps[k:])))
+    specs += _count_specs(rng, P, fleet.n_types)
+    _set_models(fleet, specs)
+    fleet.ent_time[:] = np.where(rng.random(len(fleet.ent_time)) < 0.5, rng.choice(i64, len(fleet.ent_time)),
+                                 now - rng.choice([100, 1499, 1500, 449_999, 450_000, 450_001], len(fleet.ent_time)))
+    n = 1300
+    r, _, expl = _random_rows(fleet, rng, n)
+    for f in ("size_hint", "loader_predicted", "loading_count", "weight_predict_cutoff", "fresh_count", "fresh_loading_threads",
+              "fresh_in_progress", "fresh_rpm"):
+        r[f] = rng.choice(i32, n)
+    for f in ("last_used_time", "cache_capacity", "cache_weighted_size", "cache_oldest_time", "loaded_time", "load_timeout_ms", "fresh_lru",
+              "fresh_capacity", "fresh_used", "last_published"):
+        r[f] = rng.choice(i64, n)
+    excl = []
+    for i in range(n):
+        lp, lt, _, _ = _copies(fleet, r["model"][i])
+        lst = []
+        for _ in range(int(rng.integers(0, 10)) if rng.random() < 0.5 else 0):
+            if len(lp) and rng.random() < 0.7:
+                e = int(rng.integers(0, len(lp)))
+                lst.append((int(lp[e]), int(rng.choice([int(lt[e]), int(lt[e]), LONG_MIN] + i64))))
+            else:
+                lst.append((int(rng.integers(0, P)), int(rng.choice(i64))))
+        excl.append(lst)
+    # a difference of exactly MIN_VALUE, whose Math.abs stays negative and passes every "<": one field at a time, the rest of the
+    # fresh record equal to the table's; and |difference| * 100 leaving 64 bits
+    aimed = []
+    for p in range(P):
+        cur = pods[p]
+        for over in (dict(fresh_count=_i32(int(cur["count"]) + INT_MIN)), dict(fresh_rpm=_i32(int(cur["rpm"]) + INT_MIN)),
+                     dict(fresh_in_progress=_i32(int(cur["loading_in_progress"]) + INT_MIN)), dict(fresh_lru=_i64(int(cur["lru_time"]) + LONG_MIN)),
+                     dict(fresh_used=_i64(int(cur["used"]) - 2**62)), dict(fresh_used=_i64(int(cur["used"]) + LONG_MIN)),
+                     dict(fresh_capacity=_i64(int(cur["capacity"]) + LONG_MIN)), dict(fresh_count=_i32(int(cur["count"]) + INT_MIN + 1)),
+                     dict(fresh_used=_i64(int(cur["used"]) - 2**62 + 1)), dict(fresh_rpm=INT_MAX), dict(fresh_rpm=INT_MAX - 1), dict(fresh_rpm=0),
+                     dict(fresh_in_progress=INT_MAX), dict(fresh_in_progress=0))[(0 if P <= 8 or p in neg else p % 3)::1 if P <= 8 or p in neg else 3]:
+            aimed.append(_publish_row(fleet, rng, p, **over))
+    aimed = np.concatenate(aimed)
+    none = [[] for _ in range(len(aimed))]
+    rows, excl, expl = _cat([(r, excl, expl), (aimed, none, none), _random_rows(fleet, rng, 200)])
+    return (fleet, ids) + _with_lists(rows, excl, expl) + (GATE_EXPIRY,)
+
+
+def gate_edge_cases():
+    """(name, fleet, ids, reqs, excl_pod, excl_time, explicit, in_use_expiry) as gate_cases, at the EDGES of the guards' value
+    domain; name = gate_<tier>_<case>.  timed: (instance, loadStart) exclusions as a cache-hit retry leaves them, matching and
+    off by one, before and behind the device's four-entry prefetch.  totals: fleets whose per-type totalCapacity - totalFree is
+    engineered around 2^31 and 2^32 (loadLocal's estimate narrows it to int first), 20 * totalFree at totalCapacity.  thresholds:
+    one row just inside, one just outside every threshold of the publish / reload / churn / cap rules.  wrap: hostile values."""
+    for P, typed in ((8, False), (24, True), (64, False), (65, True)):
+        yield (f"gate_timed_{P}",) + _timed_case(P, P, typed)
+    for P, c in ((64, 9), (65, 10), (64, 12), (65, 300)):
+        yield (f"gate_totals_c{c}",) + _totals_case(P, c, c)
+    for P, typed in ((24, False), (65, True)):
+        yield (f"gate_thresholds_{P}",) + _thresholds_case(P, P, typed)
+    for P, typed in ((8, False), (65, True)):
+        yield (f"gate_wrap_{P}",) + _wrap_case(P, P, typed)
+
+
+def gate_edge_tier(name):
+    return name.split("_")[1]
+
+
+SIZING_OUTCOMES = ("hint", "negative estimate", "positive estimate", "estimate -1", "estimate 0: loader_predicted")
+
+
+def sizing_outcomes(fleet, r, tstats):
+    """Per row, which way loadLocal's sizing goes (MM.java:5159-5178) — one of SIZING_OUTCOMES, or None where neither a hint nor
+    the estimate applies (or the hint is 0).  tstats: typeSetStats per type row."""
+    out = []
+    for q in r:
+        ty = int(fleet.models["type"][q["model"]])
+        st = tstats[ty if 0 <= ty < len(tstats) else 0]
+        what = None
+        if q["flags"] & 32:
+            what = "hint" if q["size_hint"] else None
+        elif q["loading_count"] > q["weight_predict_cutoff"] and st["model_copy_count"] >= 10:
+            e = estimate_of(int(st["total_capacity"]), int(st["total_free"]), int(st["model_copy_count"]))
+            what = SIZING_OUTCOMES[1] if e < -1 else SIZING_OUTCOMES[2] if e > 0 else SIZING_OUTCOMES[3] if e == -1 else SIZING_OUTCOMES[4]
+        out.append(what)
+    return out
 
 
 def _rebalance_fleet(seed, pods, models, used):

@@ -2,21 +2,15 @@
 a14, a20): goLocal MM.java:3603-3626, checkLoadFailureCount :4607-4627, checkLoadLocationCount
 :4590-4604, throwIfLocalLoadNotAllowed :4003-4042, churn guard :3870-3884, loadLocal size prediction
 and early reject :5158-5197, onEviction reload rule :2886-2920, publish hysteresis :5397-5468."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from modelmesh_amd import _lib
 from modelmesh_amd import workload as wl
 from modelmesh_amd.solver import Solver
-from oracle import bind as ob
+from tests.gate_helpers import oracle_gates
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if len(a) else None
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -88,68 +82,10 @@ def test_gates_match_oracle(seed):
     finally:
         s.close()
 
-    lib = ob.load()
-    orc = ob.OracleFleet(fleet)
-    # typeSetStats(mr.getType()): the stats of the instances the model's type may be placed on (MM.java:5169, :2918)
-    tstats = np.ascontiguousarray(ob.type_set_stats(fleet))
-    in_table = np.ascontiguousarray(((fleet.pods["flags"] & 4) == 0).astype(np.uint8))
-    al = ob.unpack_bitmap(fleet.allowed, P) if fleet.n_types else None
-    opods = orc.pods
-    seen = 0
-    for i in range(n):
-        q = r[i]
-        mr = m[q["model"]]
-        lp = fleet.ent_pod[mr["ent_off"]: mr["ent_off"] + mr["n_loaded"]]
-        lt = fleet.ent_time[mr["ent_off"]: mr["ent_off"] + mr["n_loaded"]]
-        fp = fleet.ent_pod[mr["ent_off"] + mr["n_loaded"]: mr["ent_off"] + mr["n_loaded"] + mr["n_failed"]]
-        ft = fleet.ent_time[mr["ent_off"] + mr["n_loaded"]: mr["ent_off"] + mr["n_loaded"] + mr["n_failed"]]
-        keep = np.ones(len(lp), bool)
-        for j in range(q["n_excl"]):
-            keep &= lp != excl_pod[q["excl_off"] + j]
-        ex = np.ascontiguousarray(explicit[q["explicit_off"]: q["explicit_off"] + q["n_explicit"]])
-        fl = int(q["flags"])
-        ty = int(mr["type"])
-        stats = tstats[(0 if ty < 0 or ty >= len(tstats) else ty): ][:1]
-        want = 0
-        cp, ct = np.ascontiguousarray(lp[keep]), np.ascontiguousarray(lt[keep])
-        if lib.orc_go_local(_p(cp), _p(ct), len(cp), int(q["self_pod"]), fl & 1, (fl >> 1) & 1, (fl >> 2) & 1, now):
-            want |= 1
-        ftc = np.ascontiguousarray(ft)
-        if lib.orc_load_failures_breached(_p(ftc), len(ftc), now, 450_000):
-            want |= 2
-        lpc = np.ascontiguousarray(lp)
-        if lib.orc_load_locations_breached(_p(lpc), len(lpc), _p(ex), len(ex), _p(in_table)):
-            want |= 4
-        local_filtered = (q["self_pod"] in ex) or (q["self_pod"] in lp) or (q["self_pod"] in fp)
-        blocked = bool(fleet.n_types and fleet.has_allowed[mr["type"]] and not al[mr["type"]][q["self_pod"]])
-        if local_filtered or blocked:
-            want |= 8
-        if lib.orc_churn_reject(fleet.min_churn_age_ms, fleet.min_space_units, int(q["cache_capacity"]),
-                                int(q["cache_weighted_size"]), int(q["cache_oldest_time"]), now):
-            want |= 16
-        rej = C.c_int(0)
-        init = lib.orc_load_local_initial_size((fl >> 5) & 1, int(q["size_hint"]), int(q["loading_count"]),
-                                               int(q["weight_predict_cutoff"]), int(q["loader_predicted"]),
-                                               stats.ctypes.data_as(C.c_void_p), (fl >> 3) & 1,
-                                               int(q["last_used_time"]), int(q["cache_capacity"]),
-                                               int(q["cache_weighted_size"]), int(q["cache_oldest_time"]), C.byref(rej))
-        if rej.value:
-            want |= 32
-        if lib.orc_reload_elsewhere((fl >> 4) & 1, int(q["loaded_time"]), int(q["load_timeout_ms"]), now,
-                                    stats.ctypes.data_as(C.c_void_p)):
-            want |= 64
-        fresh = np.zeros(1, dtype=ob.ORC_POD)
-        fresh["lru_time"], fresh["capacity"], fresh["used"] = q["fresh_lru"], q["fresh_capacity"], q["fresh_used"]
-        fresh["count"], fresh["loading_threads"] = q["fresh_count"], q["fresh_loading_threads"]
-        fresh["loading_in_progress"], fresh["rpm"] = q["fresh_in_progress"], q["fresh_rpm"]
-        fresh["shutting_down"] = (fl >> 8) & 1
-        curp = np.ascontiguousarray(opods[q["self_pod"]: q["self_pod"] + 1]).copy()
-        tomb = bool(fleet.pods["flags"][q["self_pod"]] & 4)
-        curp["shutting_down"] = bool(fleet.pods["flags"][q["self_pod"]] & 1)
-        if lib.orc_should_publish(None if tomb else curp.ctypes.data_as(C.c_void_p), fresh.ctypes.data_as(C.c_void_p),
-                                  now, int(q["last_published"]), (fl >> 6) & 1, (fl >> 7) & 1, fleet.min_space_units):
-            want |= 128
-        assert got[i]["bits"] == want, (i, bin(got[i]["bits"]), bin(want), q)
-        assert got[i]["initial_size"] == init, (i, got[i], init)
-        seen |= want
+    want = oracle_gates(fleet, r, excl_pod, excl_time, explicit, 450_000)  # the C restatement, request by request
+    bad = np.nonzero(got["bits"] != want[:, 0])[0]
+    assert len(bad) == 0, [(int(i), bin(got[i]["bits"]), bin(want[i, 0]), r[i]) for i in bad[:3]]
+    bad = np.nonzero(got["initial_size"] != want[:, 1])[0]
+    assert len(bad) == 0, [(int(i), got[i], int(want[i, 1])) for i in bad[:3]]
+    seen = int(np.bitwise_or.reduce(want[:, 0]))
     assert seen == 255, f"some gate never fired in the sample: {seen:#x}"

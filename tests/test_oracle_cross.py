@@ -351,6 +351,68 @@ def test_request_guards_c_vs_python(seed):
     assert all(v == {False, True} for v in seen.values()), seen
 
 
+def py_gates_rows(fleet, r, excl_pod, excl_time, explicit, in_use_expiry):
+    """oracle/py_gates.py over guard requests (the shape of tests/ref_fleets.py:gate_cases) -> (bits, initial size) per row."""
+    from oracle import py_gates as pg
+    P, now, msu = fleet.n_pods, int(fleet.now), int(fleet.min_space_units)
+    tstats = ob.type_set_stats(fleet)
+    al = ob.unpack_bitmap(fleet.allowed, P) if fleet.n_types else None
+    in_table = [not (int(f) & 4) for f in fleet.pods["flags"]]
+    out = np.zeros((len(r), 2), np.int64)
+    for i, q in enumerate(r):
+        mr = fleet.models[q["model"]]
+        a, k, f = int(mr["ent_off"]), int(mr["n_loaded"]), int(mr["n_failed"])
+        lp, lt = [int(x) for x in fleet.ent_pod[a:a + k]], [int(x) for x in fleet.ent_time[a:a + k]]
+        fp, ft = [int(x) for x in fleet.ent_pod[a + k:a + k + f]], [int(x) for x in fleet.ent_time[a + k:a + k + f]]
+        xs = [(int(excl_pod[q["excl_off"] + j]), int(excl_time[q["excl_off"] + j])) for j in range(q["n_excl"])]
+        copies = [(p, t) for p, t in zip(lp, lt) if not any(xp == p and (xt == -(1 << 63) or xt == t) for xp, xt in xs)]  # MapFilteringSet.apply
+        ex = set(int(x) for x in explicit[q["explicit_off"]: q["explicit_off"] + q["n_explicit"]])
+        fl, ty, sp = int(q["flags"]), int(mr["type"]), int(q["self_pod"])
+        st = tstats[ty if 0 <= ty < len(tstats) else 0]
+        sd = {n: int(st[n]) for n in st.dtype.names}
+        ty = ty if 0 <= ty < fleet.n_types else 0
+        bits = 0
+        if pg.go_local(copies, sp, fl & 1, fl & 2, fl & 4, now):
+            bits |= 1
+        if pg.load_failures_breached(ft, now, in_use_expiry):
+            bits |= 2
+        if pg.load_locations_breached(lp, ex, in_table):
+            bits |= 4
+        if sp in ex or sp in lp or sp in fp or bool(fleet.n_types and fleet.has_allowed[ty] and not al[ty][sp]):
+            bits |= 8
+        if pg.churn_reject(int(fleet.min_churn_age_ms), msu, int(q["cache_capacity"]), int(q["cache_weighted_size"]), int(q["cache_oldest_time"]), now):
+            bits |= 16
+        init, rej = pg.load_local_initial_size(fl & 32, int(q["size_hint"]), int(q["loading_count"]), int(q["weight_predict_cutoff"]),
+                                               int(q["loader_predicted"]), sd, fl & 8, int(q["last_used_time"]), int(q["cache_capacity"]),
+                                               int(q["cache_weighted_size"]), int(q["cache_oldest_time"]))
+        if rej:
+            bits |= 32
+        if pg.reload_elsewhere(fl & 16, int(q["loaded_time"]), int(q["load_timeout_ms"]), now, sd):
+            bits |= 64
+        fresh = dict(lru_time=int(q["fresh_lru"]), capacity=int(q["fresh_capacity"]), used=int(q["fresh_used"]), count=int(q["fresh_count"]),
+                     loading_threads=int(q["fresh_loading_threads"]), loading_in_progress=int(q["fresh_in_progress"]), rpm=int(q["fresh_rpm"]),
+                     shutting_down=(fl >> 8) & 1)
+        row = fleet.pods[sp]
+        cur = None if int(row["flags"]) & 4 else dict(lru_time=int(row["lru_time"]), capacity=int(row["capacity"]), used=int(row["used"]),
+                                                       count=int(row["count"]), loading_threads=int(row["loading_threads"]),
+                                                       loading_in_progress=int(row["loading_in_progress"]), rpm=int(row["rpm"]),
+                                                       shutting_down=int(row["flags"]) & 1)
+        if pg.should_publish(cur, fresh, now, int(q["last_published"]), fl & 64, fl & 128, msu):
+            bits |= 128
+        out[i] = bits, init
+    return out
+
+
+def test_request_guard_edges_python_vs_the_reference_text():
+    """The Python restatement on the rows of tests/ref_fleets.py:gate_edge_cases, against what the reference's own text decided
+    (tests/golden/ref_gate_edges.npz; the C restatement on the same rows: tests/test_ref_vectors.py)."""
+    from tests.gate_helpers import GOLDEN_GATE_EDGES, check_gates, gate_edge_inputs
+    edges = np.load(GOLDEN_GATE_EDGES)
+    for name, fleet, ids, r, xp, xt, expl, expiry, _ in gate_edge_inputs(edges):
+        got = py_gates_rows(fleet, r, xp, xt, expl, expiry)
+        check_gates(name, got[:, 0], got[:, 1], edges[f"{name}/gate"], all_fire=False)
+
+
 @pytest.mark.parametrize("seed,pods,used", [(0, 12, 0.5), (1, 200, 0.97), (2, 200, 0.2), (3, 1, 0.5), (4, 60, 0.99)])
 def test_rebalancers_c_vs_python(seed, pods, used):
     """rateTrackingTask's scale-up (MM.java:5636-5856), the janitor's scale-down (:6110-6335) and preShutdown's
