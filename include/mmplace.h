@@ -1128,6 +1128,43 @@ int mmp_pod_ids_append(mmp_ctx *ctx, const char *ids, const int32_t *id_off, int
 int mmp_pods_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
                          const uint8_t *deleted, const uint8_t *live, uint32_t flags, int32_t *pod_idx_out, int64_t *start_time_out,
                          int32_t *status_out, int32_t *n_appended_out);
+/* ---- instance labels from the stored value ---------------------------------------------------------------------------------
+ * InstanceRecord.labels (InstanceRecord.java:68-92: a String[]; null, absent and an empty array are all NO_LABELS) kept inside the
+ * context, one label word and one element count per staged instance, as long as the staged instance table.  Only the labels some
+ * type names can matter (TypeConstraintManager.java:478-486, instanceMatches), so the host loads those names once and hands every
+ * instance event over as stored.
+ *
+ * mmp_label_names_load: label name i = names[name_off[i], name_off[i+1]) owns bit i of a label word; 0 <= n_labels <= 64 (one
+ * uint64 per instance, the width mmp_types_from_labels fixes).  Names match by bytes against the RAW bytes between the quotes of an
+ * element; an empty name and non-ASCII UTF-8 names are allowed.  A successful load clears every resident label word and count (the
+ * bits change meaning); n_labels == 0 unloads the table (names / name_off may then be NULL).  MMP_EINVAL with nothing changed:
+ * more than 64 names, two equal names, non-monotone offsets, a name holding '"', '\' or a byte below 0x20 (none can stand raw
+ * inside a JSON string, and Jackson writes no escapes for any other character).
+ *
+ * While a table is loaded, mmp_pods_ingest_json and mmp_pods_events_json read `labels` as a known field of type "null or array
+ * of strings" with a second kernel over the staged values (mmp_last_kernel_ms covers it); without one they behave and launch
+ * exactly as before.  Every occurrence is held to its type — a number, a string, an object, true, an element that is not a
+ * string, a leading / doubled / trailing comma, two strings without a comma, an unterminated array: status 1, neither the row nor
+ * the labels change — and the LAST occurrence decides the set.  Every applied non-deleted event sets word and count of its pod
+ * (0 / 0 when the field is absent, null or []); a deleted event leaves them.  An element whose raw bytes hold a backslash matches
+ * no name and counts as an unknown label; a repeated label sets its bit once and counts twice.  Unspecified: a raw control byte
+ * inside a label string.
+ *
+ * State: mmp_pod_ids_append and a join inside mmp_pods_events_json add zero words; mmp_pods_load keeps the words of the indices
+ * that remain and zeroes new ones; mmp_pod_ids_load clears all (a new index space, as for the `missings` marks); mmp_pods_upsert
+ * and mmp_pods_remove leave them alone (an appended row starts with none). */
+int mmp_label_names_load(mmp_ctx *ctx, const char *names, const int32_t *name_off, int32_t n_labels);
+/* For hosts that feed rows (mmp_pods_upsert) instead of JSON: word and count of the staged pods idx[0..n), all of the call or
+ * none of it on an index outside the staged table (MMP_EINVAL; also a negative count, a NULL buffer).  Needs no name table. */
+int mmp_pod_labels_set(mmp_ctx *ctx, const int32_t *idx, const uint64_t *words, const int32_t *counts, int32_t n);
+/* words_out[p] = the known-label bits of pod p, counts_out[p] = the number of elements of its `labels` array, unknown and
+ * repeated ones included: 0 means NO_LABELS, which is what a host passes as labels_key == 0 (mmp_upgrade_instance_added).
+ * *n_out = the staged pod count, always; at most max_pods entries are written.  Either output may be NULL. */
+int mmp_pod_labels_get(mmp_ctx *ctx, uint64_t *words_out, int32_t *counts_out, int32_t max_pods, int32_t *n_out);
+/* mmp_types_from_labels with the resident label words in place of pod_labels: from raw instance events to the type sets of the
+ * next commit without the host decoding a record.  required[t] / preferred[t] are bitsets over the loaded name order. */
+int mmp_types_from_pod_labels(mmp_ctx *ctx, int32_t n_types, const uint64_t *required, const uint64_t *preferred,
+                              uint64_t *allowed_out, uint64_t *prefer_out, uint8_t *has_allowed_out, uint8_t *has_prefer_out);
 /* Which records name an id the table does not know: the registry rows that hold at least one entry (loaded or failed) whose pod
  * is outside [0, pod slots of the staged table), in ascending row order.  *n_models_out / *n_entries_out are always the full
  * counts (*n_entries_out = mmp_registry_stats.n_entries_unresolved); at most max_models rows are written, lowest rows first;

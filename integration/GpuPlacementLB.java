@@ -175,6 +175,16 @@ final class MmPlace {
     static native int podsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
                                      ByteBuffer deleted, ByteBuffer live, int flags, ByteBuffer podIdxOut,
                                      ByteBuffer startTimeOut, ByteBuffer statusOut, ByteBuffer nAppendedOut);
+    // Instance labels kept in the context.  labelNamesLoad: the label names some type constraint mentions, name i = bit i of a
+    // label word (at most 64; nLabels 0 unloads; clears every resident word).  While names are loaded podsIngestJson and
+    // podsEventsJson read `labels` from the stored value, so the listener decodes no InstanceRecord: podLabelsGet gives words
+    // and element counts back (count 0 = NO_LABELS = labelsKey 0 of upgradeInstanceAdded; either buffer may be null, nOut = the
+    // pod count), typesFromPodLabels is typesFromLabels over the resident words, podLabelsSet is for hosts that upsert rows.
+    static native int labelNamesLoad(long h, ByteBuffer names, ByteBuffer nameOff, int nLabels);
+    static native int podLabelsSet(long h, ByteBuffer idx, ByteBuffer words, ByteBuffer counts, int n);
+    static native int podLabelsGet(long h, ByteBuffer wordsOut, ByteBuffer countsOut, int maxPods, ByteBuffer nOut);
+    static native int typesFromPodLabels(long h, int nTypes, ByteBuffer required, ByteBuffer preferred, ByteBuffer allowedOut,
+                                         ByteBuffer preferOut, ByteBuffer hasAllowedOut, ByteBuffer hasPreferOut);
     // the registry rows holding an entry whose instance id the table does not know, ascending; after a join the listener sends
     // their stored values through modelsUpsertJson again.  nModelsOut (int) / nEntriesOut (long) are the full counts.
     static native int registryUnresolved(long h, ByteBuffer modelOut, int maxModels, ByteBuffer nModelsOut, ByteBuffer nEntriesOut);

@@ -604,6 +604,39 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podIdsAppend(JNIEnv
                  mmp_pod_ids_append(ctx_of(h), buf<char>(env, ids), buf<int32_t>(env, idOff), nNew,
                                     buf<uint32_t>(env, idOrderOut), buf<int32_t>(env, replicaSetOut), maxPods));
 }
+// instance labels kept in the context: the names some type constraint mentions (name i = bit i), then `labels` is read from the
+// stored values by podsIngestJson / podsEventsJson (see mmp_label_names_load)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_labelNamesLoad(JNIEnv *env, jclass, jlong h, jobject names, jobject nameOff, jint nLabels)
+{
+    if (nLabels > 0 && (!holds<int32_t>(env, nameOff, (jlong)nLabels + 1, "labelNamesLoad: nameOff shorter than nLabels + 1") ||
+                        !holds<char>(env, names, buf<int32_t>(env, nameOff)[nLabels], "labelNamesLoad: names shorter than nameOff[nLabels]")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_label_names_load(ctx_of(h), buf<char>(env, names), buf<int32_t>(env, nameOff), nLabels));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podLabelsSet(JNIEnv *env, jclass, jlong h, jobject idx, jobject words, jobject counts, jint n)
+{
+    if (!holds<int32_t>(env, idx, n, "podLabelsSet: idx shorter than n") || !holds<uint64_t>(env, words, n, "podLabelsSet: words shorter than n") ||
+        !holds<int32_t>(env, counts, n, "podLabelsSet: counts shorter than n"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_pod_labels_set(ctx_of(h), buf<int32_t>(env, idx), buf<uint64_t>(env, words), buf<int32_t>(env, counts), n));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podLabelsGet(JNIEnv *env, jclass, jlong h, jobject wordsOut, jobject countsOut, jint maxPods, jobject nOut)
+{
+    if ((wordsOut && !holds<uint64_t>(env, wordsOut, maxPods, "podLabelsGet: wordsOut shorter than maxPods")) ||
+        (countsOut && !holds<int32_t>(env, countsOut, maxPods, "podLabelsGet: countsOut shorter than maxPods")) ||
+        !holds<int32_t>(env, nOut, 1, "podLabelsGet: nOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_pod_labels_get(ctx_of(h), buf<uint64_t>(env, wordsOut), buf<int32_t>(env, countsOut), maxPods, buf<int32_t>(env, nOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_typesFromPodLabels(JNIEnv *env, jclass, jlong h, jint nTypes, jobject required, jobject preferred,
+                                              jobject allowedOut, jobject preferOut, jobject hasAllowedOut, jobject hasPreferOut)
+{
+    return check(env, ctx_of(h),
+                 mmp_types_from_pod_labels(ctx_of(h), nTypes, buf<uint64_t>(env, required), buf<uint64_t>(env, preferred),
+                                           buf<uint64_t>(env, allowedOut), buf<uint64_t>(env, preferOut), buf<uint8_t>(env, hasAllowedOut),
+                                           buf<uint8_t>(env, hasPreferOut)));
+}
 // instance-table events as stored: the raw key and value bytes of each event (see mmp_pods_events_json)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podsEventsJson(JNIEnv *env, jclass, jlong h, jobject keys,
                                                                             jobject keyOff, jobject json, jobject off, jint n,

@@ -296,6 +296,10 @@ SYMBOLS = [
     ("mmp_pod_ids_append", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32]),
     ("mmp_pods_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_registry_unresolved", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    ("mmp_label_names_load", C.c_int, [_P, _P, _P, C.c_int32]),
+    ("mmp_pod_labels_set", C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    ("mmp_pod_labels_get", C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mmp_types_from_pod_labels", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("mmp_model_ids_load", C.c_int, [_P, _P, _P, C.c_int32]),
     ("mmp_model_ids_resolve", C.c_int, [_P, _P, _P, C.c_int32, _P]),
     ("mmp_model_ids_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),

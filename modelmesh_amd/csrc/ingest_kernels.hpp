@@ -18,7 +18,9 @@
 // row made of the slots (pod_row_from_slots, the publish of ingest_models_kernel).  Fields Jackson omits
 // because they hold the default value come out as 0 / false, exactly like the bean's defaults.  Instance
 // ids inside a ModelRecord (the keys of instanceIds / failedIn) are resolved to pod indices through an
-// open-addressing table of id hashes built when the ids are loaded.
+// open-addressing table of id hashes built when the ids are loaded.  The `labels` of an InstanceRecord are no slot of the
+// pod parser: once label names are loaded (mmp_label_names_load) a second kernel over the same staged values,
+// ingest_pod_labels_kernel, turns the array into a 64-bit word of known-label bits and an element count.
 //
 // Pure byte / integer work: no MFMA, bound by the bytes of JSON read once.
 //
@@ -32,8 +34,9 @@
 // type.  A map key may be empty: `"":1,`
 // is the shortest entry, five bytes, which is what the parking rule of the entries rests on (kJEntryBytes below).
 // UNSPECIFIED — the two routes may differ, tests/ingest_model.py names the class and no test relies on it: a value that
-// is invalid only INSIDE a value that is skipped (unknown fields, loc / zone / labels, fails: the wave path checks
-// balanced nesting there and nothing else, the serial walk a little more), leading zeros, integers outside int64 / int32,
+// is invalid only INSIDE a value that is skipped (unknown fields, loc / zone, fails, and labels while no label names are loaded:
+// the wave path checks balanced nesting there and nothing else, the serial walk a little more), a raw control byte inside
+// a label string, leading zeros, integers outside int64 / int32,
 // a `type` that is neither a string nor null, and backslash escapes in the names and keys the parsers hash.
 #pragma once
 #include "snapshot.hpp"
@@ -228,7 +231,7 @@ __device__ __forceinline__ void j_members(JCur &c, bool whole_value, F &&member)
 
 enum PodSlot { kPodLruTime, kPodCount, kPodCap, kPodUsed, kPodLThreads, kPodLInProg, kPodRpm, kPodShutdown, kPodStartTime, kPodVers, kPodSlots };
 
-// the slot of a field name, -1 for loc, zone, labels (interned on the host) and anything newer
+// the slot of a field name, -1 for loc, zone (interned on the host), labels (ingest_pod_labels_kernel) and anything newer
 template <class B>
 __device__ __forceinline__ int pod_slot_of(uint64_t h, int klen, const B *kp)
 {
@@ -296,6 +299,63 @@ __device__ __forceinline__ int32_t tab_find(const HashTab &t, uint64_t h, int32_
         s = (s + 1) & t.mask;
     }
     return missing;
+}
+
+// The label names of mmp_label_names_load: name i owns bit i of a label word.  `tab` maps the masked hash of a name to i and,
+// unlike the id tables, may hold EQUAL hashes (MMP_LABEL_HASH_BITS masks them down to provoke that): a probe goes on past an
+// entry whose bytes differ.  At most 64 names in a table of >= 128 slots, so every probe sequence meets an empty slot.
+struct LabelTab {
+    HashTab tab;
+    const int32_t *name_off;  // name i = arena[name_off[i], name_off[i + 1])
+    const char *arena;
+    uint64_t hmask;  // the hash bits that count
+};
+
+// the bit of the label whose raw bytes are p[0, len) with FNV-1a hash h; -1 for a label no type can name
+template <class B>
+__device__ __forceinline__ int32_t label_find(const LabelTab &T, uint64_t h, int len, const B *p)
+{
+    h &= T.hmask;
+    uint32_t s = tab_home(h, T.tab.mask);
+    for (uint32_t probe = 0; probe <= T.tab.mask; probe++) {
+        const int32_t v = T.tab.val[s];
+        if (v == INT32_MIN) return -1;  // empty slot
+        if (T.tab.hash[s] == h) {       // hash first, then the length, then the bytes
+            const int32_t o = T.name_off[v];
+            if (T.name_off[v + 1] - o == len && bytes_equal(p, T.arena + o, len)) return v;
+        }
+        s = (s + 1) & T.tab.mask;
+    }
+    return -1;
+}
+
+// At the value of a `labels` member (InstanceRecord.java:68-92: a String[], null and [] alike NO_LABELS), the serial statement
+// of what the element round of ingest_pod_labels_kernel checks on the tile: `null`, or '[', strings separated by exactly one
+// ',', ']'.  word = the bits of the known labels (T == nullptr: the grammar alone), count = the elements, unknown and repeated
+// ones included.  A string is matched by its raw bytes, so one that holds a backslash escape matches no name.
+__device__ __forceinline__ void j_labels(JCur &c, const LabelTab *T, uint64_t &word, int32_t &count)
+{
+    word = 0;
+    count = 0;
+    j_ws(c);
+    if (j_lit(c, "null", 4)) return;
+    if (!j_eat(c, '[')) {
+        c.bad = true;
+        return;
+    }
+    if (j_eat(c, ']')) return;
+    for (;;) {
+        j_ws(c);
+        const char *kp = c.p + 1;
+        const uint64_t h = j_string_hash(c);
+        if (c.bad) return;
+        const int32_t b = T ? label_find(*T, h, (int)(c.p - kp) - 1, kp) : -1;
+        if (b >= 0) word |= 1ull << b;
+        count++;
+        if (j_eat(c, ',')) continue;
+        if (!j_eat(c, ']')) c.bad = true;
+        return;
+    }
 }
 
 // at an id -> long map (instanceIds / failedIn; Jackson writes a null map as `null`): count the entries, and when
@@ -856,6 +916,147 @@ __global__ __launch_bounds__(kJBlock) void ingest_pods_kernel(const char *__rest
                 pod_row_from_slots(r, fv, start_time[i]);
                 rows[i] = r;
             }
+        });
+}
+
+// The `labels` of InstanceRecord values, grp per WAVEFRONT: a second launch over the values ingest_pods_kernel has parsed, made
+// only while label names are loaded (ingest_pods_kernel has no slot left, and one more would change the LDS layout of both record
+// types).  word[i] / count[i] = the known-label bits and the element count of the LAST `labels` member of value i (absent, null
+// and [] alike 0 / 0); status[i] = 1 when the value is malformed as a whole or ANY of its `labels` members is not null or an
+// array of strings, which the host ORs into the parser's status.
+enum LabelSlot { kLabWord, kLabCount, kLabOpen, kLabClose, kLabSlots };  // kLabOpen / kLabClose: the winning array's brackets on the tile
+static_assert(kLabSlots <= kJSlots, "JWaveLds::val / win hold every slot");
+
+__global__ __launch_bounds__(kJBlock) void ingest_pod_labels_kernel(const char *__restrict__ buf, const int64_t *__restrict__ off,
+                                                                    int32_t n, int32_t grp, LabelTab T, uint64_t *__restrict__ word,
+                                                                    int32_t *__restrict__ count, int32_t *__restrict__ status)
+{
+    __shared__ JWaveLds lds[kJWaves];
+    const int lane = lane_id();
+    j_ingest_wave(
+        lds, buf, off, n, grp,
+        [&](JWaveLds &S, int, const char *b, const char *e) {  // a later duplicate wins by program order
+            JCur c{b, e, false};
+            j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
+                if (KEY_IS(h, klen, kp, "labels")) {
+                    uint64_t w;
+                    int32_t k;
+                    j_labels(c, &T, w, k);
+                    S.val[0][kLabWord] = (int64_t)w;
+                    S.val[0][kLabCount] = k;
+                } else
+                    j_skip_value(c);
+            });
+            return c.bad;
+        },
+        [&](JWaveLds &S, int, int cnt) {
+            // the `labels` members of every record of the group: the last one claims kLabCount and leaves its brackets
+            int total = j_prefix_fields(S, cnt);
+            for (int base = 0; base < total; base += 64) {
+                JField F{};
+                int fid = -1;
+                int64_t val = 0;
+                int vopen = -1, vclose = -1;
+                bool lbad = false;
+                if (base + lane < total) {
+                    JView R;
+                    if (!j_field_at(S, cnt, base + lane, R, F))
+                        lbad = true;
+                    else if (KEY_IS(F.m.h, F.m.klen, F.m.kp, "labels")) {
+                        fid = kLabCount;
+                        const int v = F.m.v;
+                        if (j_lit_at(R, v, "null", 4)) {
+                            if (!j_term(R, v + 4, R.m1, R.g, F.last)) lbad = true;
+                        } else if (v < R.L && R.by[v] == '[') {
+                            const int ce = j_nth_after(R.e2, R.nch, v, 0);
+                            if (ce < 0 || R.by[ce] != ']')
+                                lbad = true;
+                            else {
+                                vopen = v;
+                                vclose = ce;
+                                val = j_count(R.m2, v, ce) + 1;  // the elements are the m2 commas between the brackets, plus one
+                                if (val == 1) {                  // ... unless nothing but blanks stands there
+                                    int q = v + 1;
+                                    while (q < ce && j_is_ws(R.by[q])) q++;
+                                    if (q == ce) val = 0;
+                                }
+                                if (!j_term(R, ce + 1, R.m1, R.g, F.last)) lbad = true;
+                            }
+                        } else
+                            lbad = true;
+                    }
+                }
+                const int r = F.r;
+                const bool claims = j_claim(S, F, fid, lbad);
+                // An array that loses to a later duplicate is read by no element lane, so it is walked here, as the lost maps of
+                // ingest_models_kernel are: one of THIS round that lost its claim walks itself, the winner of an EARLIER round
+                // (its opener is > 0; -1 = null) is walked by the lane that replaces it.
+                int lost_open = -1, lost_close = -1;
+                if (claims) {
+                    if (S.win[r][fid] == F.j) {
+                        int64_t *fv = S.val[r];
+                        if (fv[kLabOpen] > 0) {
+                            lost_open = (int)fv[kLabOpen];
+                            lost_close = (int)fv[kLabClose];
+                        }
+                        fv[kLabCount] = val;
+                        fv[kLabOpen] = vopen;
+                        fv[kLabClose] = vclose;
+                    } else {
+                        lost_open = vopen;
+                        lost_close = vclose;
+                    }
+                }
+                if (lost_open >= 0) {
+                    const JView R = j_view(S, r);
+                    JCur c{reinterpret_cast<const char *>(R.by) + lost_open, reinterpret_cast<const char *>(R.by) + lost_close + 1, false};
+                    uint64_t w;
+                    int32_t k;
+                    j_labels(c, nullptr, w, k);
+                    if (c.bad) S.rec[r].bad = 1;
+                }
+                wave_sync();
+            }
+            // the elements of the winning arrays of all records, one lane each: element e stands between separator e - 1 (the
+            // opener for the first) and separator e (the closer for the last)
+            total = j_prefix_items(S, cnt, lane < cnt && !S.rec[lane].bad ? (int)S.val[lane][kLabCount] : 0);
+            for (int base = 0; base < total; base += 64) {
+                const int t = base + lane;
+                if (t < total) {
+                    int e;
+                    const int r = j_item_record(S, cnt, t, e);
+                    const JView R = j_view(S, r);
+                    const int64_t *fv = S.val[r];
+                    const int open = (int)fv[kLabOpen], close = (int)fv[kLabClose], kcnt = (int)fv[kLabCount];
+                    const int lo = e == 0 ? open : j_nth_after(R.m2, R.nch, open, e - 1);
+                    const int hi = e == kcnt - 1 ? close : j_nth_after(R.m2, R.nch, open, e);
+                    int p = lo + 1, q = -1;
+                    while (p < hi && j_is_ws(R.by[p])) p++;
+                    bool ok = lo >= 0 && p < hi && R.by[p] == '"';  // one string ...
+                    if (ok) {
+                        q = j_nth_after(R.rq, R.nch, p, 0);  // its closing quote
+                        ok = q > p && q < hi;
+                    }
+                    if (ok) {  // ... with nothing but blanks behind it
+                        int z = q + 1;
+                        while (z < hi && j_is_ws(R.by[z])) z++;
+                        ok = z == hi;
+                    }
+                    if (!ok)
+                        S.rec[r].bad = 1;
+                    else {
+                        const int len = q - p - 1;
+                        const int32_t b = label_find(T, fnv1a(R.by + p + 1, len), len, R.by + p + 1);
+                        if (b >= 0) atomicOr(reinterpret_cast<unsigned long long *>(&S.val[r][kLabWord]), 1ull << b);
+                    }
+                }
+            }
+            wave_sync();
+        },
+        [&](int i, bool bad, const int64_t *fv) {
+            status[i] = bad ? 1 : 0;
+            word[i] = bad ? 0ull : (uint64_t)fv[kLabWord];
+            count[i] = bad ? 0 : (int32_t)fv[kLabCount];
         });
 }
 

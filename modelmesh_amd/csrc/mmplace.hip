@@ -261,6 +261,7 @@ struct Tuning {
     int32_t plan_sorted = 0;     // MMP_PLAN_SORTED=1: mmp_proactive_plan takes its sorted (fallback) path on every input; 2: never (tests)
     int32_t plan_fused = 1;      // MMP_PLAN_FUSED=0: the plan as its eight dependent launches (comparison; the one-launch form is the default)
     int32_t resident = 0;        // MMP_RESIDENT=1: mmp_create turns the resident decision kernel on (mmp_resident)
+    int32_t label_hash_bits = 64;     // MMP_LABEL_HASH_BITS=b: the same for the label-name hashes (tests: the byte comparison of label_find)
     int32_t model_id_hash_bits = 64;  // MMP_MODEL_ID_HASH_BITS=b: every model-id hash is masked to its low b bits, 0: all equal (tests: ids that collide)
 };
 
@@ -464,6 +465,16 @@ struct mmp_ctx {
     std::vector<int32_t> id_offs{0}, id_sorted;
     std::unordered_map<std::string, int32_t> rs_intern;
     DevBuf idtab_next_hash, idtab_next_val, ida_bytes, ida_off, ida_hash, ida_found;
+    // The instance labels.  pod_label_word / pod_label_count sit beside c->pods under the same locks and are as long as it
+    // (labels_cover): the known-label bits of each staged instance and the element count of its `labels` array (0 = NO_LABELS).
+    // lbtab_* / lb_arena / lb_off: the label names on the device (ingest_kernels.hpp: LabelTab), read under batch_mu by
+    // ingest_pod_labels_kernel alone; j_lab: one call's words | counts | statuses.
+    std::vector<uint64_t> pod_label_word;
+    std::vector<int32_t> pod_label_count;
+    DevBuf lbtab_hash, lbtab_val, lb_arena, lb_off, j_lab;
+    uint32_t lbtab_mask = 0;
+    uint64_t lb_hmask = ~0ull;
+    bool have_labels = false;
     DevBuf unres_list;  // mmp_registry_unresolved: the listed rows (its other scratch is the registry plans')
     // The model-id table (model_ids_kernels.hpp), read and written under batch_mu only: mid_hash / mid_val / mid_mask the published
     // table, mid_bytes / mid_off the id arena (row r = mid_bytes[mid_off[r], mid_off[r + 1]); mid_n rows, mid_nbytes bytes);
@@ -772,6 +783,8 @@ Tuning read_tuning()
     flag("MMP_RESIDENT", t.resident);
     num("MMP_MODEL_ID_HASH_BITS", t.model_id_hash_bits);
     t.model_id_hash_bits = std::max(0, std::min(t.model_id_hash_bits, 64));
+    num("MMP_LABEL_HASH_BITS", t.label_hash_bits);
+    t.label_hash_bits = std::max(0, std::min(t.label_hash_bits, 64));
     return t;
 }
 
@@ -1404,6 +1417,13 @@ inline void note_dirty(mmp_ctx *c, int32_t k)
     }
     c->dirty.push_back(k);
 }
+
+// the label state is as long as the staged instance table: indices that remain keep their word, new ones carry none
+inline void labels_cover(mmp_ctx *c)
+{
+    c->pod_label_word.resize(c->pods.size(), 0);
+    c->pod_label_count.resize(c->pods.size(), 0);
+}
 }  // namespace
 
 int mmp_pods_load(mmp_ctx *c, const mmp_pod_row *rows, int32_t n)
@@ -1412,6 +1432,7 @@ try {
     std::lock_guard<std::mutex> gb(c->batch_mu);
     std::lock_guard<std::shared_mutex> g(c->mu);
     c->pods.assign(rows, rows + n);
+    labels_cover(c);
     c->dirty_all = true;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_pods_load")
@@ -1432,6 +1453,7 @@ try {
         const int32_t k = idx[i];
         if (k == (int32_t)c->pods.size()) {
             c->pods.push_back(rows[i]);
+            labels_cover(c);
             c->dirty_all = true;
         } else {
             c->pods[k] = rows[i];
@@ -1488,16 +1510,14 @@ try {
     return MMP_OK;
 } MMP_CATCH(c, "mmp_types_load")
 
-int mmp_types_from_labels(mmp_ctx *c, int32_t n_types, const uint64_t *required, const uint64_t *preferred,
-                          const uint64_t *pod_labels, uint64_t *allowed_out, uint64_t *prefer_out,
-                          uint8_t *has_allowed_out, uint8_t *has_prefer_out)
-try {
-    if (!c || n_types < 0 || (n_types > 0 && (!required || !preferred)))
-        return fail(c, MMP_EINVAL, "mmp_types_from_labels: bad argument");
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    std::lock_guard<std::shared_mutex> g(c->mu);
+namespace {
+// The body of mmp_types_from_labels and mmp_types_from_pod_labels (batch_mu and the state lock held): pod_labels[P] is the
+// caller's array or the resident words.
+int types_from_labels_locked(mmp_ctx *c, int32_t n_types, const uint64_t *required, const uint64_t *preferred,
+                             const uint64_t *pod_labels, uint64_t *allowed_out, uint64_t *prefer_out, uint8_t *has_allowed_out,
+                             uint8_t *has_prefer_out)
+{
     const int32_t P = (int32_t)c->pods.size();
-    if (P > 0 && !pod_labels) return fail(c, MMP_EINVAL, "mmp_types_from_labels: pod_labels is null");
     const int32_t W = div_up(P, 64), T = n_types, R = T + 1;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
@@ -1548,7 +1568,62 @@ try {
     if (has_allowed_out) memcpy(has_allowed_out, c->has_allowed.data(), R);
     if (has_prefer_out) memcpy(has_prefer_out, c->has_prefer.data(), R);
     return MMP_OK;
+}
+}  // namespace
+
+int mmp_types_from_labels(mmp_ctx *c, int32_t n_types, const uint64_t *required, const uint64_t *preferred,
+                          const uint64_t *pod_labels, uint64_t *allowed_out, uint64_t *prefer_out,
+                          uint8_t *has_allowed_out, uint8_t *has_prefer_out)
+try {
+    if (!c || n_types < 0 || (n_types > 0 && (!required || !preferred)))
+        return fail(c, MMP_EINVAL, "mmp_types_from_labels: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (!c->pods.empty() && !pod_labels) return fail(c, MMP_EINVAL, "mmp_types_from_labels: pod_labels is null");
+    return types_from_labels_locked(c, n_types, required, preferred, pod_labels, allowed_out, prefer_out, has_allowed_out, has_prefer_out);
 } MMP_CATCH(c, "mmp_types_from_labels")
+
+int mmp_types_from_pod_labels(mmp_ctx *c, int32_t n_types, const uint64_t *required, const uint64_t *preferred, uint64_t *allowed_out,
+                              uint64_t *prefer_out, uint8_t *has_allowed_out, uint8_t *has_prefer_out)
+try {
+    if (!c || n_types < 0 || (n_types > 0 && (!required || !preferred)))
+        return fail(c, MMP_EINVAL, "mmp_types_from_pod_labels: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    labels_cover(c);
+    return types_from_labels_locked(c, n_types, required, preferred, c->pod_label_word.data(), allowed_out, prefer_out, has_allowed_out,
+                                    has_prefer_out);
+} MMP_CATCH(c, "mmp_types_from_pod_labels")
+
+int mmp_pod_labels_set(mmp_ctx *c, const int32_t *idx, const uint64_t *words, const int32_t *counts, int32_t n)
+try {
+    if (!c || n < 0 || (n > 0 && (!idx || !words || !counts))) return fail(c, MMP_EINVAL, "mmp_pod_labels_set: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    labels_cover(c);
+    for (int32_t i = 0; i < n; i++) {  // (all of the call or none of it)
+        if (idx[i] < 0 || idx[i] >= (int32_t)c->pods.size()) return fail(c, MMP_EINVAL, "mmp_pod_labels_set: index %d out of range", idx[i]);
+        if (counts[i] < 0) return fail(c, MMP_EINVAL, "mmp_pod_labels_set: count %d of entry %d", counts[i], i);
+    }
+    for (int32_t i = 0; i < n; i++) {
+        c->pod_label_word[idx[i]] = words[i];
+        c->pod_label_count[idx[i]] = counts[i];
+    }
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_pod_labels_set")
+
+int mmp_pod_labels_get(mmp_ctx *c, uint64_t *words_out, int32_t *counts_out, int32_t max_pods, int32_t *n_out)
+try {
+    if (!c || !n_out || max_pods < 0) return fail(c, MMP_EINVAL, "mmp_pod_labels_get: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    labels_cover(c);
+    *n_out = (int32_t)c->pods.size();
+    const int32_t m = std::min(*n_out, max_pods);
+    if (words_out && m > 0) memcpy(words_out, c->pod_label_word.data(), (size_t)m * 8);
+    if (counts_out && m > 0) memcpy(counts_out, c->pod_label_count.data(), (size_t)m * 4);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_pod_labels_get")
 
 int mmp_replaced_rs_load(mmp_ctx *c, const int32_t *rs, int32_t n)
 try {
@@ -2754,8 +2829,10 @@ int ingest_group(int32_t n)
 }
 
 // host side of the open-addressing table the device probes (ingest_kernels.hpp: tab_find)
+// (hmask / equal_ok: the label names, whose hashes may be masked down until they are equal — the device then tells them apart by
+// their bytes, ingest_kernels.hpp: label_find; the caller has refused equal names)
 int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n, DevBuf &d_hash, DevBuf &d_val,
-                     uint32_t &mask_out, const char *what)
+                     uint32_t &mask_out, const char *what, uint64_t hmask = ~0ull, bool equal_ok = false)
 {
     uint32_t cap = 16;
     while (cap < (uint32_t)n * 2u) cap <<= 1;
@@ -2763,10 +2840,10 @@ int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n
     std::vector<int32_t> vs(cap, INT32_MIN);
     for (int32_t i = 0; i < n; i++) {
         if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: offsets not monotone at %d", what, i);
-        const uint64_t h = fnv1a(strs + off[i], off[i + 1] - off[i]);
+        const uint64_t h = fnv1a(strs + off[i], off[i + 1] - off[i]) & hmask;
         uint32_t s = tab_home(h, cap - 1);
         while (vs[s] != INT32_MIN) {
-            if (hs[s] == h) return fail(c, MMP_EINVAL, "%s: entries %d and %d are equal or collide under FNV-1a", what, vs[s], i);
+            if (hs[s] == h && !equal_ok) return fail(c, MMP_EINVAL, "%s: entries %d and %d are equal or collide under FNV-1a", what, vs[s], i);
             s = (s + 1) & (cap - 1);
         }
         hs[s] = h;
@@ -2868,6 +2945,8 @@ try {
     for (int32_t i = 0; i < n_pods; i++) c->replica_set_v[i] = intern_replica_set(c, i);
     const size_t old = c->pods.size();
     c->pods.resize(n_pods);
+    c->pod_label_word.assign(n_pods, 0);  // a new index space: the labels of the old one mean nothing in it (as the marks below)
+    c->pod_label_count.assign(n_pods, 0);
     c->dirty_all = true;
     for (size_t i = 0; i < (size_t)n_pods; i++) {
         if (i >= old) {
@@ -2883,6 +2962,97 @@ try {
     if (replica_set_out && n_pods) memcpy(replica_set_out, c->replica_set_v.data(), (size_t)n_pods * 4);
     return MMP_OK;
 } MMP_CATCH(c, "mmp_pod_ids_load")
+
+namespace {
+// The label side of the two instance JSON calls, a no-op from end to end while no label names are loaded: the second launch over
+// the staged values (inside the caller's kernel-time bracket), its words / counts / statuses back on the host, the status the
+// caller ORs into the parser's, and the word and count of an applied event.
+struct PodLabelsOut {
+    bool on = false;
+    std::vector<uint64_t> word;
+    std::vector<int32_t> count, status;
+    int prepare(mmp_ctx *c, int32_t n)
+    {
+        on = c->have_labels;
+        labels_cover(c);
+        if (on) HIP_TRY(c, c->j_lab.ensure((size_t)n * 16));
+        return MMP_OK;
+    }
+    uint64_t *d_word(mmp_ctx *c) const { return c->j_lab.as<uint64_t>(); }
+    int32_t *d_count(mmp_ctx *c, int32_t n) const { return reinterpret_cast<int32_t *>(d_word(c) + n); }
+    void launch(mmp_ctx *c, int32_t n, int grp) const
+    {
+        if (!on) return;
+        const LabelTab T{HashTab{c->lbtab_hash.as<uint64_t>(), c->lbtab_val.as<int32_t>(), c->lbtab_mask}, c->lb_off.as<int32_t>(),
+                         c->lb_arena.as<char>(), c->lb_hmask};
+        hipLaunchKernelGGL(ingest_pod_labels_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, c->stream, c->j_buf.as<char>(),
+                           c->j_off.as<int64_t>(), n, grp, T, d_word(c), d_count(c, n), d_count(c, n) + n);
+    }
+    int fetch(mmp_ctx *c, int32_t n)  // enqueued; the caller synchronises the stream
+    {
+        if (!on) return MMP_OK;
+        word.resize(n), count.resize(n), status.resize(n);
+        HIP_TRY(c, hipMemcpyAsync(word.data(), d_word(c), (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(count.data(), d_count(c, n), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(status.data(), d_count(c, n) + n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        return MMP_OK;
+    }
+    void merge_status(int32_t *status_out, int32_t n) const
+    {
+        if (!on) return;
+        for (int32_t i = 0; i < n; i++) status_out[i] |= status[i];
+    }
+    void apply(mmp_ctx *c, int32_t i, int32_t pod) const
+    {
+        if (!on) return;
+        c->pod_label_word[pod] = word[i];
+        c->pod_label_count[pod] = count[i];
+    }
+};
+}  // namespace
+
+int mmp_label_names_load(mmp_ctx *c, const char *names, const int32_t *name_off, int32_t n_labels)
+try {
+    if (!c || n_labels < 0 || n_labels > 64 || (n_labels > 0 && !name_off))
+        return fail(c, MMP_EINVAL, "mmp_label_names_load: bad argument (0 to 64 names)");
+    for (int32_t i = 0; i < n_labels; i++)
+        if (name_off[i + 1] < name_off[i]) return fail(c, MMP_EINVAL, "mmp_label_names_load: offsets not monotone at %d", i);
+    const int32_t nbytes = n_labels ? name_off[n_labels] - name_off[0] : 0;
+    if (nbytes > 0 && !names) return fail(c, MMP_EINVAL, "mmp_label_names_load: bad argument");
+    for (int32_t i = 0; i < n_labels; i++) {
+        const char *a = names + name_off[i];
+        const int32_t la = name_off[i + 1] - name_off[i];
+        for (int32_t q = 0; q < la; q++)  // what cannot stand raw inside a JSON string
+            if (a[q] == '"' || a[q] == '\\' || (unsigned char)a[q] < 0x20)
+                return fail(c, MMP_EINVAL, "mmp_label_names_load: name %d holds a byte that JSON escapes (0x%02x)", i, (unsigned char)a[q]);
+        for (int32_t j = 0; j < i; j++)
+            if (name_off[j + 1] - name_off[j] == la && memcmp(names + name_off[j], a, (size_t)la) == 0)
+                return fail(c, MMP_EINVAL, "mmp_label_names_load: names %d and %d are equal", j, i);
+    }
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n_labels > 0) {
+        const int bits = c->tune.label_hash_bits;
+        const uint64_t hmask = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
+        std::vector<int32_t> rel((size_t)n_labels + 1);
+        for (int32_t i = 0; i <= n_labels; i++) rel[i] = name_off[i] - name_off[0];
+        HIP_TRY(c, c->lb_arena.ensure((size_t)nbytes + 16));
+        HIP_TRY(c, c->lb_off.ensure((size_t)(n_labels + 1) * 4));
+        c->have_labels = false;  // (a HIP failure below leaves no half-built table in use)
+        if (const int rc = build_hash_table(c, names, name_off, n_labels, c->lbtab_hash, c->lbtab_val, c->lbtab_mask, "mmp_label_names_load",
+                                            hmask, true))
+            return rc;
+        if (nbytes) HIP_TRY(c, copy_sync(c, c->lb_arena.p, names + name_off[0], (size_t)nbytes, hipMemcpyHostToDevice));
+        HIP_TRY(c, copy_sync(c, c->lb_off.p, rel.data(), (size_t)(n_labels + 1) * 4, hipMemcpyHostToDevice));
+        c->lb_hmask = hmask;
+    }
+    c->have_labels = n_labels > 0;
+    c->pod_label_word.assign(c->pods.size(), 0);  // the bits change meaning
+    c->pod_label_count.assign(c->pods.size(), 0);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_label_names_load")
 
 int mmp_pods_ingest_json(mmp_ctx *c, const char *buf, const int64_t *off, int32_t n, const int32_t *pod_idx,
                          const uint8_t *live, int64_t *start_time_out, int32_t *status_out)
@@ -2914,24 +3084,30 @@ try {
     HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
     HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
+    PodLabelsOut lab;
+    if (const int rc = lab.prepare(c, n)) return rc;
     KT_BEGIN(c, st);
     const int grp = ingest_group(n);
     hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(), c->j_off.as<int64_t>(), n,
                        grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
+    lab.launch(c, n, grp);
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
+    if (const int rc = lab.fetch(c, n)) return rc;
     std::vector<int64_t> stt(n);
     HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(stt.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
+    lab.merge_status(status_out, n);
     for (int32_t i = 0; i < n; i++) {
         if (status_out[i] == 0) {
             c->pods[pod_idx[i]] = rows[i];
             note_dirty(c, pod_idx[i]);
+            lab.apply(c, i, pod_idx[i]);
         }
-        if (start_time_out) start_time_out[i] = stt[i];
+        if (start_time_out) start_time_out[i] = status_out[i] == 0 ? stt[i] : 0;  // (the parser leaves 0 for a value IT rejects)
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_pods_ingest_json")
@@ -3031,6 +3207,7 @@ int pod_ids_append_locked(mmp_ctx *c, const char *fn, const char *ids, const int
     c->replica_set_v.resize((size_t)P + n_new, -1);
     for (int32_t i = P; i < P + n_new; i++) c->replica_set_v[i] = intern_replica_set(c, i);
     c->pods.resize((size_t)P + n_new);
+    labels_cover(c);
     for (int32_t i = 0; i < P + n_new; i++) {
         if (i >= P) {
             c->pods[i] = mmp_pod_row{};
@@ -3150,12 +3327,16 @@ try {
     HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
     HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
+    PodLabelsOut lab;
+    if (const int rc = lab.prepare(c, n)) return rc;
     KT_BEGIN(c, st);
     const int grp = ingest_group(n);
     hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(), c->j_off.as<int64_t>(), n,
                        grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
+    lab.launch(c, n, grp);
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
+    if (const int rc = lab.fetch(c, n)) return rc;
     std::vector<int64_t> stt(n);
     HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(stt.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -3163,7 +3344,8 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     if (c->prof && span_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += span_ms;  // the call's device span: resolve + join + parse
-    // 4. the events in order: a pod ends as its last well-formed or deleted event left it
+    // 4. the events in order: a pod ends as its last well-formed or deleted event left it, labels included
+    lab.merge_status(status_out, n);
     for (int32_t i = 0; i < n; i++) {
         const int32_t k = idx[i];
         pod_idx_out[i] = k;
@@ -3178,6 +3360,7 @@ try {
         } else if (status_out[i] == 0) {
             c->pods[k] = rows[i];
             note_dirty(c, k);
+            lab.apply(c, i, k);
             started = stt[i];
         }
         if (start_time_out) start_time_out[i] = started;

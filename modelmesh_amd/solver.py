@@ -231,6 +231,43 @@ class Solver:
                     mirror[idx[i]] = True if live is None else bool(live[i])
         return status[:n], idx[:n], st[:n], n_app.value
 
+    # ---- instance labels kept in the context ------------------------------------------------------
+    def label_names_load(self, names):
+        """Label name i owns bit i of a label word (mmp_label_names_load); at most 64 names, [] unloads the table.  While a
+        table is loaded the two instance JSON calls read `labels` from the stored value.  Clears every resident word."""
+        blob, off = self._pack(names)
+        off32 = off.astype(np.int32)
+        self._ck(self.lib.mmp_label_names_load(self.h, blob, ptr(off32), len(names)))
+
+    def pod_labels_set(self, idx, words, counts):
+        """Word and count of staged pods by index (mmp_pod_labels_set), for hosts that feed rows instead of JSON."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        assert len(words) == len(idx) == len(counts)
+        self._ck(self.lib.mmp_pod_labels_set(self.h, ptr(idx), ptr(words), ptr(counts), len(idx)))
+
+    def pod_labels_get(self):
+        """-> (words[P], counts[P]): the known-label bits and the `labels` element count of every staged pod."""
+        n = C.c_int32(0)
+        self._ck(self.lib.mmp_pod_labels_get(self.h, None, None, 0, C.byref(n)))
+        words, counts = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.int32)
+        self._ck(self.lib.mmp_pod_labels_get(self.h, ptr(words), ptr(counts), n.value, C.byref(n)))
+        return words[:n.value], counts[:n.value]
+
+    def types_from_pod_labels(self, required, preferred):
+        """types_from_labels with the resident label words (mmp_types_from_pod_labels)."""
+        required = np.ascontiguousarray(required, dtype=np.uint64)
+        preferred = np.ascontiguousarray(preferred, dtype=np.uint64)
+        T, W = len(required), (self.n_pods + 63) // 64
+        al = np.zeros((T + 1, max(W, 1)), np.uint64)
+        pf = np.zeros((T + 1, max(W, 1)), np.uint64)
+        ha = np.zeros(T + 1, np.uint8)
+        hp = np.zeros(T + 1, np.uint8)
+        self._ck(self.lib.mmp_types_from_pod_labels(self.h, T, ptr(required) if T else None, ptr(preferred) if T else None,
+                                                    ptr(al), ptr(pf), ptr(ha), ptr(hp)))
+        return al[:, :W], pf[:, :W], ha, hp
+
     def registry_unresolved(self, max_models=None):
         """The registry rows holding an entry whose id the instance table does not know (mmp_registry_unresolved), ascending.
         Returns (rows, n_models, n_entries); max_models=None asks for all of them."""
