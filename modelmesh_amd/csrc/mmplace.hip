@@ -454,7 +454,7 @@ struct mmp_ctx {
     std::vector<uint32_t> id_order_v;
     std::vector<int32_t> replica_set_v;
     DevBuf idtab_hash, idtab_val, tytab_hash, tytab_val, j_buf, j_off, j_rows, j_aux, j_status, j_cnt, j_offs, j_tmp_pod, j_tmp_time,
-        j_scan_tmp, j_ev;  // j_ev: mmp_models_upsert_json's per-event / per-distinct-row words
+        j_scan_tmp, j_ev;  // j_ev: the per-event / per-distinct-row words of the registry event calls (UpsertJsonEvents, carve)
     uint32_t idtab_mask = 0, tytab_mask = 0;
     bool have_ids = false, have_types = false;
     int32_t unknown_type = 0, default_type = 0;
@@ -480,9 +480,9 @@ struct mmp_ctx {
     // table, mid_bytes / mid_off the id arena (row r = mid_bytes[mid_off[r], mid_off[r + 1]); mid_n rows, mid_nbytes bytes);
     // mid_next_*: the table built beside the published one.  me_*: one call's keys on the device — hashes, resolved rows, dedupe
     // slots, the call-local table (owner | first | first_nd), the flags and their scan, model_idx, the joining events, what the
-    // verify found, the deleted bytes.
+    // verify found.  (slot / slot_model and the deleted bytes are written where the pipeline reads them: j_ev.)
     DevBuf mid_hash, mid_val, mid_next_hash, mid_next_val, mid_bytes, mid_off;
-    DevBuf me_hash, me_row, me_slot, me_tab, me_cnt, me_pos, me_idx, me_join, me_found, me_del;
+    DevBuf me_hash, me_row, me_slot, me_tab, me_cnt, me_pos, me_idx, me_join, me_found;
     uint32_t mid_mask = 0;
     int32_t mid_n = 0, mid_nbytes = 0;
     bool have_model_ids = false;
@@ -567,6 +567,13 @@ inline void kt_collect(mmp_ctx *c)
     c->last_kernel_ms = ms;
     c->prof_armed = false;
 }
+// The device span of a call is the sum of its brackets: kt_add behind the last kt_collect adds what an earlier bracket collected.
+// Where either span is unknown (negative), or profiling is off, the later one stands.  kt_sum: the rule as a value (a_ms stands).
+inline void kt_add(mmp_ctx *c, double earlier_ms)
+{
+    if (c->prof && earlier_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += earlier_ms;
+}
+inline double kt_sum(const mmp_ctx *c, double a_ms, double b_ms) { return c->prof && a_ms >= 0 && b_ms >= 0 ? a_ms + b_ms : a_ms; }
 
 // Called with c->mu held, before device state that decisions read is overwritten: every decision
 // kernel was enqueued under c->mu, so once the streams are idle nothing reads the old state.
@@ -1369,7 +1376,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->me_del, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -1915,7 +1922,7 @@ int registry_apply_edits(mmp_ctx *c, int32_t E, int32_t n_kept, const Edit *edit
     launch_build(base, base + n_kept);
     HIP_TRY(c, hipGetLastError());
     if (const int rc = registry_rewrite(c, E, M, base + n_kept, true)) return rc;
-    if (c->prof && eval_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += eval_ms;  // the call's device span: evaluation + apply
+    kt_add(c, eval_ms);  // the call's device span: evaluation + apply
     // the host shadow, from the counts the edits leave.  (The prune's edits carry n_removed as well: m_cnt[model] == n_loaded +
     // n_failed holds before the call, so this is m_cnt[model] -= n_removed, and ent_live falls by the removed entries.)
     for (int32_t e = 0; e < E; e++) {
@@ -2828,18 +2835,59 @@ int ingest_group(int32_t n)
     return g;
 }
 
+// What every table of this section takes for n keys: a power of two, at least 16 and at least twice the keys
+uint32_t tab_capacity(int32_t n)
+{
+    uint32_t cap = 16;
+    while (cap < (uint32_t)n * 2u) cap <<= 1;
+    return cap;
+}
+
+// MMP_LABEL_HASH_BITS / MMP_MODEL_ID_HASH_BITS: the hashes of a table masked to their low `bits` bits, so that they collide
+uint64_t hash_mask(int bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1ull; }
+
+// off[0 .. n] must not decrease (nor off2[0 .. n], where a call brings two kinds: the first index at which either does is named).
+// On its own where a call must refuse before anything is staged; `what`: "", "key " or "id ".
+extern "C++" template <class Off, class Off2 = Off>  // (a template inside the file's extern "C" block)
+int check_offsets(mmp_ctx *c, const char *fn, const char *what, const Off *off, int32_t n, const Off2 *off2 = nullptr)
+{
+    for (int32_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i] || (off2 && off2[i + 1] < off2[i]))
+            return fail(c, MMP_EINVAL, "%s: %soffsets not monotone at %d", fn, what, i);
+    return MMP_OK;
+}
+
+// n strings of a call onto the device (the device is set, batch_mu held) — the values into j_buf / j_off, ids and event keys
+// into ida_bytes / ida_off: off[0 .. n] must not decrease; d_bytes gets the bytes [off[0], off[n]) — none needs no buf —, d_off
+// the offsets rebased to off[0].  Both uploads are enqueued on c->stream; `rel` is what d_off is uploaded from (rel[n]: the
+// bytes) and stays with the caller until it has synchronised.
+extern "C++" template <class Off>
+int stage_strings(mmp_ctx *c, const char *fn, const char *what, const char *buf, const Off *off, int32_t n, DevBuf &d_bytes,
+                  DevBuf &d_off, std::vector<Off> &rel)
+{
+    if (const int rc = check_offsets(c, fn, what, off, n)) return rc;
+    rel.assign((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; i++) rel[i + 1] = off[i + 1] - off[0];
+    const size_t bytes = (size_t)rel[n];
+    if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    HIP_TRY(c, d_bytes.ensure(bytes + 16));  // the wave path stages whole dwords
+    HIP_TRY(c, d_off.ensure((size_t)(n + 1) * sizeof(Off)));
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(d_bytes.p, buf + off[0], bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_off.p, rel.data(), (size_t)(n + 1) * sizeof(Off), hipMemcpyHostToDevice, c->stream));
+    return MMP_OK;
+}
+
 // host side of the open-addressing table the device probes (ingest_kernels.hpp: tab_find)
 // (hmask / equal_ok: the label names, whose hashes may be masked down until they are equal — the device then tells them apart by
 // their bytes, ingest_kernels.hpp: label_find; the caller has refused equal names)
 int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n, DevBuf &d_hash, DevBuf &d_val,
                      uint32_t &mask_out, const char *what, uint64_t hmask = ~0ull, bool equal_ok = false)
 {
-    uint32_t cap = 16;
-    while (cap < (uint32_t)n * 2u) cap <<= 1;
+    if (const int rc = check_offsets(c, what, "", off, n)) return rc;
+    const uint32_t cap = tab_capacity(n);
     std::vector<uint64_t> hs(cap, 0);
     std::vector<int32_t> vs(cap, INT32_MIN);
     for (int32_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: offsets not monotone at %d", what, i);
         const uint64_t h = fnv1a(strs + off[i], off[i + 1] - off[i]) & hmask;
         uint32_t s = tab_home(h, cap - 1);
         while (vs[s] != INT32_MIN) {
@@ -2857,22 +2905,40 @@ int build_hash_table(mmp_ctx *c, const char *strs, const int32_t *off, int32_t n
     return MMP_OK;
 }
 
-// The values of a wire-format call onto the device (the device is set, batch_mu held): off[0 .. n] must not decrease; j_buf gets
-// the bytes [off[0], off[n]) — none needs no buf —, j_off the offsets rebased to off[0].  Both uploads are enqueued on c->stream;
-// `rel` is what j_off is uploaded from and stays with the caller until it has synchronised.
-int stage_values(mmp_ctx *c, const char *fn, const char *buf, const int64_t *off, int32_t n, std::vector<int64_t> &rel, int64_t &bytes)
+// An open-addressing table with no key in it (enqueued on c->stream)
+int empty_table(mmp_ctx *c, const HashTabW &nt)
 {
-    rel.assign((size_t)n + 1, 0);
-    for (int32_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: offsets not monotone at %d", fn, i);
-        rel[i + 1] = off[i + 1] - off[0];
+    HIP_TRY(c, hipMemsetAsync(nt.hash, 0, ((size_t)nt.mask + 1) * 8, c->stream));
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nt.val), INT32_MIN, (size_t)nt.mask + 1, c->stream));
+    return MMP_OK;
+}
+
+// The table a call builds beside the published one (cap0 slots; cap0 == 0: there is none), in two steps.  next_table_room: the
+// capacity for n_keys keys in all, never below the published one, and next_hash / next_val that large: `nt`.  next_table, inside
+// the caller's bracket, enqueued on c->stream: room for the new keys — the slots of hash / val as they are; else the stored
+// hashes go into the larger, emptied table (idtab_rehash_kernel reads no key).  `nt` is then ready for the claims of the
+// joining keys; the caller swaps the buffers in once they have verified.
+int next_table_room(mmp_ctx *c, uint32_t cap0, int32_t n_keys, DevBuf &next_hash, DevBuf &next_val, HashTabW &nt)
+{
+    const uint32_t cap = std::max(tab_capacity(n_keys), cap0);
+    HIP_TRY(c, next_hash.ensure((size_t)cap * 8));
+    HIP_TRY(c, next_val.ensure((size_t)cap * 4));
+    nt = HashTabW{next_hash.as<uint64_t>(), next_val.as<int32_t>(), cap - 1};
+    return MMP_OK;
+}
+int next_table(mmp_ctx *c, const DevBuf &hash, const DevBuf &val, uint32_t cap0, const HashTabW &nt)
+{
+    hipStream_t st = c->stream;
+    const size_t cap = (size_t)nt.mask + 1;
+    if (cap == cap0) {
+        HIP_TRY(c, hipMemcpyAsync(nt.hash, hash.p, cap * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(nt.val, val.p, cap * 4, hipMemcpyDeviceToDevice, st));
+        return MMP_OK;
     }
-    bytes = rel[n];
-    if (bytes > 0 && !buf) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    HIP_TRY(c, c->j_buf.ensure((size_t)bytes + 16));  // the wave path stages whole dwords
-    HIP_TRY(c, c->j_off.ensure((size_t)(n + 1) * 8));
-    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->j_buf.p, buf + off[0], (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->j_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = empty_table(c, nt)) return rc;
+    if (cap0)
+        hipLaunchKernelGGL(idtab_rehash_kernel, dim3(div_up((int)cap0, kIdTabBlock)), dim3(kIdTabBlock), 0, st, hash.as<uint64_t>(),
+                           val.as<int32_t>(), cap0, nt);
     return MMP_OK;
 }
 
@@ -2964,50 +3030,78 @@ try {
 } MMP_CATCH(c, "mmp_pod_ids_load")
 
 namespace {
-// The label side of the two instance JSON calls, a no-op from end to end while no label names are loaded: the second launch over
-// the staged values (inside the caller's kernel-time bracket), its words / counts / statuses back on the host, the status the
-// caller ORs into the parser's, and the word and count of an applied event.
-struct PodLabelsOut {
-    bool on = false;
-    std::vector<uint64_t> word;
-    std::vector<int32_t> count, status;
-    int prepare(mmp_ctx *c, int32_t n)
+// The parse stage of the two instance JSON calls (batch_mu and the state lock held, the device set, n > 0): event i's row starts
+// from the id attributes of pod src[i] — a negative src[i] leaves them zero: an event nobody applies — and `live`, the values
+// are staged and go through ingest_pods_kernel, every event into a row of its own.  Left on the host: the parsed rows, the start
+// times, and in status_out the parser's verdict ORed with the labels'.  The caller applies the events; the two differ on purpose.
+// The label side is a no-op from end to end while no label names are loaded: the second launch over the staged values (inside
+// the same kernel-time bracket), its words / counts / statuses back on the host, and the word and count of an applied event.
+struct PodParse {
+    std::vector<mmp_pod_row> rows;
+    std::vector<int64_t> start;
+    int run(mmp_ctx *c, const char *fn, const char *buf, const int64_t *off, int32_t n, const int32_t *src, const uint8_t *live,
+            int32_t *status_out)
     {
-        on = c->have_labels;
+        hipStream_t st = c->stream;
+        rows.assign(n, mmp_pod_row{});
+        for (int32_t i = 0; i < n; i++) {
+            if (src[i] >= 0) {
+                rows[i].id_order = c->id_order_v[src[i]];
+                rows[i].replica_set = c->replica_set_v[src[i]];
+            }
+            rows[i].flags = (!live || live[i]) ? MMP_POD_LIVE : 0u;
+        }
+        std::vector<int64_t> rel;
+        if (const int rc = stage_strings(c, fn, "", buf, off, n, c->j_buf, c->j_off, rel)) return rc;
+        HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_pod_row)));
+        HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
+        HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
+        labels = c->have_labels;
         labels_cover(c);
-        if (on) HIP_TRY(c, c->j_lab.ensure((size_t)n * 16));
+        if (labels) HIP_TRY(c, c->j_lab.ensure((size_t)n * 16));
+        KT_BEGIN(c, st);
+        const int grp = ingest_group(n);
+        hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(),
+                           c->j_off.as<int64_t>(), n, grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
+        uint64_t *d_word = labels ? c->j_lab.as<uint64_t>() : nullptr;  // j_lab: words | counts | statuses
+        int32_t *d_count = labels ? reinterpret_cast<int32_t *>(d_word + n) : nullptr;
+        if (labels) {
+            const LabelTab T{HashTab{c->lbtab_hash.as<uint64_t>(), c->lbtab_val.as<int32_t>(), c->lbtab_mask}, c->lb_off.as<int32_t>(),
+                             c->lb_arena.as<char>(), c->lb_hmask};
+            hipLaunchKernelGGL(ingest_pod_labels_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(),
+                               c->j_off.as<int64_t>(), n, grp, T, d_word, d_count, d_count + n);
+        }
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        if (labels) {
+            word.resize(n), count.resize(n), status.resize(n);
+            HIP_TRY(c, hipMemcpyAsync(word.data(), d_word, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(count.data(), d_count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(status.data(), d_count + n, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        }
+        start.resize(n);
+        HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(start.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        kt_collect(c);
+        if (labels)
+            for (int32_t i = 0; i < n; i++) status_out[i] |= status[i];
         return MMP_OK;
     }
-    uint64_t *d_word(mmp_ctx *c) const { return c->j_lab.as<uint64_t>(); }
-    int32_t *d_count(mmp_ctx *c, int32_t n) const { return reinterpret_cast<int32_t *>(d_word(c) + n); }
-    void launch(mmp_ctx *c, int32_t n, int grp) const
+    void apply_labels(mmp_ctx *c, int32_t i, int32_t pod) const  // of an applied event i
     {
-        if (!on) return;
-        const LabelTab T{HashTab{c->lbtab_hash.as<uint64_t>(), c->lbtab_val.as<int32_t>(), c->lbtab_mask}, c->lb_off.as<int32_t>(),
-                         c->lb_arena.as<char>(), c->lb_hmask};
-        hipLaunchKernelGGL(ingest_pod_labels_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, c->stream, c->j_buf.as<char>(),
-                           c->j_off.as<int64_t>(), n, grp, T, d_word(c), d_count(c, n), d_count(c, n) + n);
-    }
-    int fetch(mmp_ctx *c, int32_t n)  // enqueued; the caller synchronises the stream
-    {
-        if (!on) return MMP_OK;
-        word.resize(n), count.resize(n), status.resize(n);
-        HIP_TRY(c, hipMemcpyAsync(word.data(), d_word(c), (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(count.data(), d_count(c, n), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(status.data(), d_count(c, n) + n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        return MMP_OK;
-    }
-    void merge_status(int32_t *status_out, int32_t n) const
-    {
-        if (!on) return;
-        for (int32_t i = 0; i < n; i++) status_out[i] |= status[i];
-    }
-    void apply(mmp_ctx *c, int32_t i, int32_t pod) const
-    {
-        if (!on) return;
+        if (!labels) return;
         c->pod_label_word[pod] = word[i];
         c->pod_label_count[pod] = count[i];
     }
+
+private:
+    bool labels = false;
+    std::vector<uint64_t> word;
+    std::vector<int32_t> count, status;
 };
 }  // namespace
 
@@ -3015,8 +3109,7 @@ int mmp_label_names_load(mmp_ctx *c, const char *names, const int32_t *name_off,
 try {
     if (!c || n_labels < 0 || n_labels > 64 || (n_labels > 0 && !name_off))
         return fail(c, MMP_EINVAL, "mmp_label_names_load: bad argument (0 to 64 names)");
-    for (int32_t i = 0; i < n_labels; i++)
-        if (name_off[i + 1] < name_off[i]) return fail(c, MMP_EINVAL, "mmp_label_names_load: offsets not monotone at %d", i);
+    if (const int rc = check_offsets(c, "mmp_label_names_load", "", name_off, n_labels)) return rc;
     const int32_t nbytes = n_labels ? name_off[n_labels] - name_off[0] : 0;
     if (nbytes > 0 && !names) return fail(c, MMP_EINVAL, "mmp_label_names_load: bad argument");
     for (int32_t i = 0; i < n_labels; i++) {
@@ -3034,8 +3127,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (n_labels > 0) {
-        const int bits = c->tune.label_hash_bits;
-        const uint64_t hmask = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
+        const uint64_t hmask = hash_mask(c->tune.label_hash_bits);
         std::vector<int32_t> rel((size_t)n_labels + 1);
         for (int32_t i = 0; i <= n_labels; i++) rel[i] = name_off[i] - name_off[0];
         HIP_TRY(c, c->lb_arena.ensure((size_t)nbytes + 16));
@@ -3064,74 +3156,24 @@ try {
     if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_pods_ingest_json: load the instance ids first (mmp_pod_ids_load)");
     if (n == 0) return MMP_OK;
     const int32_t P = (int32_t)c->pods.size();
-    std::vector<mmp_pod_row> rows(n);
-    for (int32_t i = 0; i < n; i++) {
-        const int32_t k = pod_idx[i];
-        if (k < 0 || k >= P) return fail(c, MMP_EINVAL, "mmp_pods_ingest_json: record %d names pod %d", i, k);
-        mmp_pod_row r{};
-        r.id_order = c->id_order_v[k];
-        r.replica_set = c->replica_set_v[k];
-        r.flags = (!live || live[i]) ? MMP_POD_LIVE : 0u;
-        rows[i] = r;
-    }
+    for (int32_t i = 0; i < n; i++)
+        if (pod_idx[i] < 0 || pod_idx[i] >= P) return fail(c, MMP_EINVAL, "mmp_pods_ingest_json: record %d names pod %d", i, pod_idx[i]);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    std::vector<int64_t> rel;
-    int64_t bytes;
-    if (const int rc = stage_values(c, "mmp_pods_ingest_json", buf, off, n, rel, bytes)) return rc;
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_pod_row)));
-    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
-    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
-    HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
-    PodLabelsOut lab;
-    if (const int rc = lab.prepare(c, n)) return rc;
-    KT_BEGIN(c, st);
-    const int grp = ingest_group(n);
-    hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(), c->j_off.as<int64_t>(), n,
-                       grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
-    lab.launch(c, n, grp);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = lab.fetch(c, n)) return rc;
-    std::vector<int64_t> stt(n);
-    HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(stt.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    lab.merge_status(status_out, n);
+    PodParse parse;
+    if (const int rc = parse.run(c, "mmp_pods_ingest_json", buf, off, n, pod_idx, live, status_out)) return rc;
     for (int32_t i = 0; i < n; i++) {
         if (status_out[i] == 0) {
-            c->pods[pod_idx[i]] = rows[i];
+            c->pods[pod_idx[i]] = parse.rows[i];
             note_dirty(c, pod_idx[i]);
-            lab.apply(c, i, pod_idx[i]);
+            parse.apply_labels(c, i, pod_idx[i]);
         }
-        if (start_time_out) start_time_out[i] = status_out[i] == 0 ? stt[i] : 0;  // (the parser leaves 0 for a value IT rejects)
+        if (start_time_out) start_time_out[i] = status_out[i] == 0 ? parse.start[i] : 0;  // (the parser leaves 0 for a value IT rejects)
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_pods_ingest_json")
 
 namespace {
 int missing_cover(mmp_ctx *c, int32_t n);  // (defined with the prune below)
-
-// n ids or event keys onto the device (batch_mu held, the device set): off[0 .. n] must not decrease; ida_bytes gets the bytes
-// [off[0], off[n]), ida_off the offsets rebased to off[0].  Both uploads are enqueued on c->stream; `rel` stays with the caller
-// until it has synchronised.
-int stage_ids(mmp_ctx *c, const char *fn, const char *what, const char *ids, const int32_t *off, int32_t n, std::vector<int32_t> &rel)
-{
-    rel.assign((size_t)n + 1, 0);
-    for (int32_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "%s: %s offsets not monotone at %d", fn, what, i);
-        rel[i + 1] = off[i + 1] - off[0];
-    }
-    if (rel[n] > 0 && !ids) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    HIP_TRY(c, c->ida_bytes.ensure((size_t)rel[n] + 16));
-    HIP_TRY(c, c->ida_off.ensure((size_t)(n + 1) * 4));
-    if (rel[n]) HIP_TRY(c, hipMemcpyAsync(c->ida_bytes.p, ids + off[0], (size_t)rel[n], hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->ida_off.p, rel.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    return MMP_OK;
-}
 
 // The staged instance table and the id store cover the same indices: mmp_pods_load / mmp_pods_upsert resize the table without
 // telling the id store, and an index of one space must not be used in the other.
@@ -3151,26 +3193,14 @@ int pod_ids_append_locked(mmp_ctx *c, const char *fn, const char *ids, const int
     if ((int64_t)P + n_new > INT32_MAX / 4) return fail(c, MMP_EINVAL, "%s: %d + %d ids", fn, P, n_new);
     hipStream_t st = c->stream;
     std::vector<int32_t> rel;
-    if (const int rc = stage_ids(c, fn, "id", ids, id_off, n_new, rel)) return rc;
+    if (const int rc = stage_strings(c, fn, "id ", ids, id_off, n_new, c->ida_bytes, c->ida_off, rel)) return rc;
     const uint32_t cap0 = c->idtab_mask + 1;
-    uint32_t cap = 16;  // the capacity build_hash_table would choose for P + n_new ids
-    while (cap < (uint32_t)(P + n_new) * 2u) cap <<= 1;
-    cap = std::max(cap, cap0);
-    HIP_TRY(c, c->idtab_next_hash.ensure((size_t)cap * 8));
-    HIP_TRY(c, c->idtab_next_val.ensure((size_t)cap * 4));
+    HashTabW nt;
+    if (const int rc = next_table_room(c, cap0, P + n_new, c->idtab_next_hash, c->idtab_next_val, nt)) return rc;
     HIP_TRY(c, c->ida_hash.ensure((size_t)n_new * 8));
     HIP_TRY(c, c->ida_found.ensure((size_t)n_new * 4));
-    const HashTabW nt{c->idtab_next_hash.as<uint64_t>(), c->idtab_next_val.as<int32_t>(), cap - 1};
     KT_BEGIN(c, st);
-    if (cap == cap0) {  // room for the new ids: the slots as they are
-        HIP_TRY(c, hipMemcpyAsync(nt.hash, c->idtab_hash.p, (size_t)cap * 8, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(nt.val, c->idtab_val.p, (size_t)cap * 4, hipMemcpyDeviceToDevice, st));
-    } else {  // the stored hashes into the larger table
-        HIP_TRY(c, hipMemsetAsync(nt.hash, 0, (size_t)cap * 8, st));
-        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nt.val), INT32_MIN, cap, st));
-        hipLaunchKernelGGL(idtab_rehash_kernel, dim3(div_up((int)cap0, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->idtab_hash.as<uint64_t>(),
-                           c->idtab_val.as<int32_t>(), cap0, nt);
-    }
+    if (const int rc = next_table(c, c->idtab_hash, c->idtab_val, cap0, nt)) return rc;
     hipLaunchKernelGGL(idtab_insert_kernel, dim3(div_up(n_new, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_bytes.as<char>(),
                        c->ida_off.as<int32_t>(), n_new, P, nt, c->ida_hash.as<uint64_t>());
     hipLaunchKernelGGL(idtab_verify_kernel, dim3(div_up(n_new, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_hash.as<uint64_t>(), n_new,
@@ -3192,7 +3222,7 @@ int pod_ids_append_locked(mmp_ctx *c, const char *fn, const char *ids, const int
     // nothing fails from here on: the table, the id store, the order, the interning and the rows change together
     std::swap(c->idtab_hash, c->idtab_next_hash);
     std::swap(c->idtab_val, c->idtab_next_val);
-    c->idtab_mask = cap - 1;
+    c->idtab_mask = nt.mask;
     const int32_t base = c->id_offs[P];
     c->id_bytes.append(ids + id_off[0], (size_t)rel[n_new]);
     for (int32_t i = 1; i <= n_new; i++) c->id_offs.push_back(base + rel[i]);
@@ -3231,8 +3261,7 @@ try {
     std::lock_guard<std::mutex> gb(c->batch_mu);
     std::lock_guard<std::shared_mutex> g(c->mu);
     if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_pod_ids_append: load the instance ids first (mmp_pod_ids_load)");
-    for (int32_t i = 0; i < n_new; i++)
-        if (id_off[i + 1] < id_off[i]) return fail(c, MMP_EINVAL, "mmp_pod_ids_append: id offsets not monotone at %d", i);
+    if (const int rc = check_offsets(c, "mmp_pod_ids_append", "id ", id_off, n_new)) return rc;
     const int64_t total = (int64_t)c->pods.size() + n_new;
     if ((id_order_out || replica_set_out) && max_pods < total)
         return fail(c, MMP_EINVAL, "mmp_pod_ids_append: room for %d pods, the table will have %lld", max_pods, (long long)total);
@@ -3259,14 +3288,14 @@ try {
     if (const int rc = id_space_guard(c, "mmp_pods_events_json")) return rc;
     if (n_appended_out) *n_appended_out = 0;
     if (n == 0) return MMP_OK;
-    for (int32_t i = 0; i < n; i++)  // (both kinds, before anything is staged: a refused call changes nothing)
-        if (off[i + 1] < off[i]) return fail(c, MMP_EINVAL, "mmp_pods_events_json: offsets not monotone at %d", i);
+    // (both kinds, before anything is staged: a refused call changes nothing)
+    if (const int rc = check_offsets(c, "mmp_pods_events_json", "", off, n)) return rc;
     if (off[n] > off[0] && !buf) return fail(c, MMP_EINVAL, "mmp_pods_events_json: bad argument");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     // 1. the keys against the id table, a lane per event
     std::vector<int32_t> krel, idx(n);
-    if (const int rc = stage_ids(c, "mmp_pods_events_json", "key", keys, key_off, n, krel)) return rc;
+    if (const int rc = stage_strings(c, "mmp_pods_events_json", "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
     HIP_TRY(c, c->ida_found.ensure((size_t)n * 4));
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(resolve_keys_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_bytes.as<char>(),
@@ -3306,46 +3335,13 @@ try {
     const int32_t n_join = (int32_t)join_off.size() - 1;
     if (n_join > 0) {
         if (const int rc = pod_ids_append_locked(c, "mmp_pods_events_json", join_bytes.data(), join_off.data(), n_join)) return rc;
-        if (c->prof && span_ms >= 0 && c->last_kernel_ms >= 0) span_ms += c->last_kernel_ms;
+        span_ms = kt_sum(c, span_ms, c->last_kernel_ms);
     }
     // 3. the values through the parser of mmp_pods_ingest_json, every event into a row of its own
-    std::vector<mmp_pod_row> rows(n);
-    for (int32_t i = 0; i < n; i++) {
-        mmp_pod_row r{};
-        if (idx[i] >= 0) {
-            r.id_order = c->id_order_v[idx[i]];
-            r.replica_set = c->replica_set_v[idx[i]];
-        }
-        r.flags = (!live || live[i]) ? MMP_POD_LIVE : 0u;
-        rows[i] = r;
-    }
-    std::vector<int64_t> rel;
-    int64_t bytes;
-    if (const int rc = stage_values(c, "mmp_pods_events_json", buf, off, n, rel, bytes)) return rc;
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_pod_row)));
-    HIP_TRY(c, c->j_aux.ensure((size_t)n * 8));
-    HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
-    HIP_TRY(c, hipMemcpyAsync(c->j_rows.p, rows.data(), (size_t)n * sizeof(mmp_pod_row), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->j_aux.p, 0, (size_t)n * 8, st));
-    PodLabelsOut lab;
-    if (const int rc = lab.prepare(c, n)) return rc;
-    KT_BEGIN(c, st);
-    const int grp = ingest_group(n);
-    hipLaunchKernelGGL(ingest_pods_kernel, dim3(div_up(n, kJWaves * grp)), dim3(kJBlock), 0, st, c->j_buf.as<char>(), c->j_off.as<int64_t>(), n,
-                       grp, c->j_rows.as<mmp_pod_row>(), c->j_aux.as<int64_t>(), c->j_status.as<int32_t>());
-    lab.launch(c, n, grp);
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    if (const int rc = lab.fetch(c, n)) return rc;
-    std::vector<int64_t> stt(n);
-    HIP_TRY(c, hipMemcpyAsync(rows.data(), c->j_rows.p, (size_t)n * sizeof(mmp_pod_row), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(stt.data(), c->j_aux.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    if (c->prof && span_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += span_ms;  // the call's device span: resolve + join + parse
+    PodParse parse;
+    if (const int rc = parse.run(c, "mmp_pods_events_json", buf, off, n, idx.data(), live, status_out)) return rc;
+    kt_add(c, span_ms);  // the call's device span: resolve + join + parse
     // 4. the events in order: a pod ends as its last well-formed or deleted event left it, labels included
-    lab.merge_status(status_out, n);
     for (int32_t i = 0; i < n; i++) {
         const int32_t k = idx[i];
         pod_idx_out[i] = k;
@@ -3358,10 +3354,10 @@ try {
             c->pods[k].flags &= ~MMP_POD_LIVE;
             note_dirty(c, k);
         } else if (status_out[i] == 0) {
-            c->pods[k] = rows[i];
+            c->pods[k] = parse.rows[i];
             note_dirty(c, k);
-            lab.apply(c, i, k);
-            started = stt[i];
+            parse.apply_labels(c, i, k);
+            started = parse.start[i];
         }
         if (start_time_out) start_time_out[i] = started;
     }
@@ -3409,13 +3405,12 @@ try {
         return MMP_OK;
     }
     std::vector<int64_t> rel;
-    int64_t bytes;
-    if (const int rc = stage_values(c, "mmp_models_ingest_json", buf, off, n, rel, bytes)) return rc;
+    if (const int rc = stage_strings(c, "mmp_models_ingest_json", "", buf, off, n, c->j_buf, c->j_off, rel)) return rc;
     // one pass: every record's entries are parked, the counts are scanned, and the entries move to their CSR position — no host
     // round trip in between
     IngestModelsArgs A;
     size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
+    if (const int rc = ingest_models_args(c, n, rel[n], A, ent_cap)) return rc;
     HIP_TRY(c, c->models.ensure((size_t)n * sizeof(mmp_model_row)));
     HIP_TRY(c, hipMemsetAsync(c->models.p, 0, (size_t)n * sizeof(mmp_model_row), st));
     A.rows = c->models.as<mmp_model_row>();
@@ -3457,10 +3452,30 @@ struct UpsertJsonEvents {
                               // event without a row (an unknown id of mmp_models_events_json)
     int32_t *slot_model;      // [k] the registry row of each slot
     int32_t *win;             // [k + 1] -1; win[k] takes the events without a row and is never read
-    const uint8_t *deleted;   // [n], or nullptr: no event is a deletion
+    uint8_t *deleted;         // [n], or nullptr: no event is a deletion
     int32_t *s_cnt, *s_offs;  // [k + 1] each
     int32_t k, count;         // distinct rows (> 0); the registry's rows after the call
 };
+
+// j_ev, in words, for n events and room for kcap distinct rows (by index the k of the call, by key n: k is known on the device
+// first): slot[n] | slot_model[kcap] | win[kcap + 1] | deleted[n bytes, padded to a word] | s_cnt[kcap + 1] | s_offs[kcap + 1].
+// slot .. deleted are what the by-index call uploads in one copy: ev_upload_words of ev_words.  deleted, k and count are the
+// caller's to set (deleted to nullptr where no event is a deletion).
+size_t ev_upload_words(int32_t n, int32_t kcap) { return (size_t)n + 2 * (size_t)kcap + 1 + ((size_t)n + 3) / 4; }
+size_t ev_words(int32_t n, int32_t kcap) { return ev_upload_words(n, kcap) + 2 * ((size_t)kcap + 1); }
+UpsertJsonEvents carve(int32_t *base, int32_t n, int32_t kcap, bool scan_words = true)  // (false: base holds the uploaded part only)
+{
+    UpsertJsonEvents E{};
+    E.slot = base;
+    E.slot_model = E.slot + n;
+    E.win = E.slot_model + kcap;
+    E.deleted = reinterpret_cast<uint8_t *>(E.win + kcap + 1);
+    if (scan_words) {
+        E.s_cnt = base + ev_upload_words(n, kcap);
+        E.s_offs = E.s_cnt + kcap + 1;
+    }
+    return E;
+}
 
 // From the events' slots on the device to the rewritten registry (batch_mu held, the device set, n > 0, E.k > 0): the values are
 // staged and parsed, each slot's winner picked, the winners' entries appended to the arena and the rows rewritten in place.
@@ -3472,11 +3487,10 @@ int models_upsert_json_run(mmp_ctx *c, const char *fn, const char *buf, const in
     const int32_t k = E.k, count = E.count, M0 = c->n_models;
     hipStream_t st = c->stream;
     std::vector<int64_t> rel;
-    int64_t bytes;
-    if (const int rc = stage_values(c, fn, buf, off, n, rel, bytes)) return rc;
+    if (const int rc = stage_strings(c, fn, "", buf, off, n, c->j_buf, c->j_off, rel)) return rc;
     IngestModelsArgs A;
     size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, bytes, A, ent_cap)) return rc;
+    if (const int rc = ingest_models_args(c, n, rel[n], A, ent_cap)) return rc;
     if ((int64_t)ent_cap > INT32_MAX) return fail(c, MMP_EINVAL, "%s: more than 2^31 entries in one call", fn);
     HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
     int32_t *d_win = E.win, *d_model = E.slot_model, *s_cnt = E.s_cnt, *s_offs = E.s_offs;
@@ -3521,7 +3535,7 @@ int models_upsert_json_run(mmp_ctx *c, const char *fn, const char *buf, const in
                        c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
     HIP_TRY(c, hipGetLastError());
     if (const int rc = registry_rewrite(c, k, count, base + total, true)) return rc;
-    if (c->prof && parse_ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += parse_ms;  // the call's device span: parse + apply
+    kt_add(c, parse_ms);  // the call's device span: parse + apply
     // the host shadow: a slot without a winner keeps its count (an existing row) or has none (an appended one)
     c->m_cnt.resize(count, 0);
     for (int32_t j = 0; j < k; j++) {
@@ -3563,25 +3577,20 @@ try {
     const int32_t k = (int32_t)h_model.size();
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    // j_ev, in words: slot[n] | slot_model[k] | win[k + 1] | deleted[n bytes] (uploaded together) | s_cnt[k+1] | s_offs[k+1]
-    const size_t del_words = ((size_t)n + 3) / 4, up_words = (size_t)n + 2 * (size_t)k + 1 + del_words;
-    std::vector<int32_t> up(up_words, 0);
-    memcpy(up.data(), h_slot.data(), (size_t)n * 4);
-    memcpy(up.data() + n, h_model.data(), (size_t)k * 4);
-    std::fill(up.begin() + n + k, up.begin() + n + 2 * (size_t)k + 1, -1);
+    // what the call uploads of j_ev, carved on the host as it is on the device
+    std::vector<int32_t> up(ev_upload_words(n, k), 0);
+    const UpsertJsonEvents H = carve(up.data(), n, k, false);
+    memcpy(H.slot, h_slot.data(), (size_t)n * 4);
+    memcpy(H.slot_model, h_model.data(), (size_t)k * 4);
+    std::fill(H.win, H.win + k + 1, -1);
     if (deleted)
-        for (int32_t i = 0; i < n; i++) reinterpret_cast<uint8_t *>(up.data() + n + 2 * (size_t)k + 1)[i] = deleted[i] ? 1 : 0;
-    HIP_TRY(c, c->j_ev.ensure((up_words + 2 * ((size_t)k + 1)) * 4));
-    UpsertJsonEvents E{};
-    E.slot = c->j_ev.as<int32_t>();
-    E.slot_model = E.slot + n;
-    E.win = E.slot_model + k;
-    E.deleted = deleted ? reinterpret_cast<const uint8_t *>(E.win + k + 1) : nullptr;
-    E.s_cnt = E.slot + up_words;
-    E.s_offs = E.s_cnt + k + 1;
+        for (int32_t i = 0; i < n; i++) H.deleted[i] = deleted[i] ? 1 : 0;
+    HIP_TRY(c, c->j_ev.ensure(ev_words(n, k) * 4));
+    UpsertJsonEvents E = carve(c->j_ev.as<int32_t>(), n, k);
+    if (!deleted) E.deleted = nullptr;
     E.k = k;
     E.count = count;
-    HIP_TRY(c, hipMemcpyAsync(c->j_ev.p, up.data(), up_words * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->j_ev.p, up.data(), up.size() * 4, hipMemcpyHostToDevice, st));
     if (const int rc = models_upsert_json_run(c, "mmp_models_upsert_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
     return squeeze_if_garbage(c);
 } MMP_CATCH(c, "mmp_models_upsert_json")
@@ -3603,14 +3612,14 @@ struct ModelIdsPlan {
     }
 };
 
-// the j_ev layout of the by-key call, in words, every part sized for k == n: slot[n] | slot_model[n] | win[n+1] | s_cnt[n+1] | s_offs[n+1]
-size_t mid_ev_words(int32_t n) { return 5 * (size_t)n + 3; }
-
-int mid_empty_table(mmp_ctx *c, const HashTabW &nt)
+// The staged keys (ida_*) hashed once into me_hash and looked up in `tab` into me_row (enqueued inside the caller's bracket)
+void mid_resolve_launch(mmp_ctx *c, int32_t n, const ModelIdTab &tab)
 {
-    HIP_TRY(c, hipMemsetAsync(nt.hash, 0, ((size_t)nt.mask + 1) * 8, c->stream));
-    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nt.val), INT32_MIN, (size_t)nt.mask + 1, c->stream));
-    return MMP_OK;
+    const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
+    hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, c->stream, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n,
+                       hash_mask(c->tune.model_id_hash_bits), c->me_hash.as<uint64_t>());
+    hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, c->stream, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n,
+                       c->me_hash.as<uint64_t>(), tab, c->me_row.as<int32_t>());
 }
 
 // batch_mu held, the device set, n > 0, the key offsets monotone.  replace: the keys are a whole id space (mmp_model_ids_load) —
@@ -3622,9 +3631,8 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     hipStream_t st = c->stream;
     const int32_t M0 = P.n_before = replace ? 0 : c->mid_n, B0 = P.bytes_before = replace ? 0 : c->mid_nbytes;
     std::vector<int32_t> krel;
-    if (const int rc = stage_ids(c, fn, "key", keys, key_off, n, krel)) return rc;
-    uint32_t bcap = 16;  // the call-local table: twice the events
-    while (bcap < (uint32_t)n * 2u) bcap <<= 1;
+    if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+    const uint32_t bcap = tab_capacity(n);  // the call-local table: twice the events
     HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
     HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
     HIP_TRY(c, c->me_slot.ensure((size_t)n * 4));
@@ -3634,19 +3642,17 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     HIP_TRY(c, c->me_idx.ensure((size_t)n * 4));
     HIP_TRY(c, c->me_join.ensure((size_t)n * 4));
     HIP_TRY(c, c->me_found.ensure((size_t)n * 4));
-    HIP_TRY(c, c->me_del.ensure((size_t)n));
-    HIP_TRY(c, c->j_ev.ensure(mid_ev_words(n) * 4));
+    HIP_TRY(c, c->j_ev.ensure(ev_words(n, n) * 4));
+    const UpsertJsonEvents E = carve(c->j_ev.as<int32_t>(), n, n);  // (k is known on the device first)
     const MidBatch B{c->me_tab.as<int32_t>(), c->me_tab.as<int32_t>() + bcap, c->me_tab.as<int32_t>() + 2 * (size_t)bcap, bcap - 1};
     const char *d_keys = c->ida_bytes.as<char>();
     const int32_t *d_off = c->ida_off.as<int32_t>();
     const uint64_t *d_hash = c->me_hash.as<uint64_t>();
-    const uint8_t *d_del = deleted ? c->me_del.as<uint8_t>() : nullptr;
+    const uint8_t *d_del = deleted ? E.deleted : nullptr;
     MidCount *d_cnt = c->me_cnt.as<MidCount>(), *d_pos = c->me_pos.as<MidCount>();
-    const int bits = c->tune.model_id_hash_bits;
-    const uint64_t hmask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
     const ModelIdTab cur{replace ? nullptr : c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
                          c->mid_off.as<int32_t>()};
-    if (deleted) HIP_TRY(c, hipMemcpyAsync(c->me_del.p, deleted, (size_t)n, hipMemcpyHostToDevice, st));
+    if (deleted) HIP_TRY(c, hipMemcpyAsync(E.deleted, deleted, (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(B.owner, 0xff, (size_t)bcap * 4, st));
     HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.first), INT32_MAX, (size_t)bcap * 2, st));
     size_t scan_bytes = 0;
@@ -3655,8 +3661,7 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
     // 1. hash once; the rows the table knows; the call's own duplicates; the flags and their scan
     KT_BEGIN(c, st);
-    hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, st, d_keys, d_off, n, hmask, c->me_hash.as<uint64_t>());
-    hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, st, d_keys, d_off, n, d_hash, cur, c->me_row.as<int32_t>());
+    mid_resolve_launch(c, n, cur);
     hipLaunchKernelGGL(mid_dedupe_kernel, grid, block, 0, st, d_keys, d_off, n, d_hash, d_del, B, c->me_slot.as<int32_t>());
     hipLaunchKernelGGL(mid_flags_kernel, dim3(div_up(n + 1, kIdTabBlock)), block, 0, st, n, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B,
                        d_off, append ? 1 : 0, d_cnt);
@@ -3683,35 +3688,22 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     }
     char *a_bytes = P.fresh_bytes.p ? P.fresh_bytes.as<char>() : c->mid_bytes.as<char>();
     int32_t *a_off = P.fresh_off.p ? P.fresh_off.as<int32_t>() : c->mid_off.as<int32_t>();
-    int32_t *d_slot = c->j_ev.as<int32_t>(), *d_model = d_slot + n;
     // 3. number the events; 4. the next table, copy-on-write, and a verifying lookup in a launch of its own
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(mid_number_kernel, grid, block, 0, st, n, M0, P.k, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B, append ? 1 : 0,
-                       d_pos, d_keys, d_off, B0, c->me_idx.as<int32_t>(), d_slot, d_model, c->me_join.as<int32_t>(), a_bytes, a_off);
+                       d_pos, d_keys, d_off, B0, c->me_idx.as<int32_t>(), E.slot, E.slot_model, c->me_join.as<int32_t>(), a_bytes, a_off);
     if (P.n_join > 0 || replace) {
         const uint32_t cap0 = replace ? 0u : c->mid_mask + 1;
-        uint32_t cap = 16;
-        while (cap < (uint32_t)(M0 + P.n_join) * 2u) cap <<= 1;
-        cap = std::max(cap, cap0);
-        HIP_TRY(c, c->mid_next_hash.ensure((size_t)cap * 8));
-        HIP_TRY(c, c->mid_next_val.ensure((size_t)cap * 4));
-        const HashTabW nt{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), cap - 1};
-        if (cap == cap0) {  // room for the new ids: the slots as they are
-            HIP_TRY(c, hipMemcpyAsync(nt.hash, c->mid_hash.p, (size_t)cap * 8, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync(nt.val, c->mid_val.p, (size_t)cap * 4, hipMemcpyDeviceToDevice, st));
-        } else {  // the stored hashes into the larger table
-            if (const int rc = mid_empty_table(c, nt)) return rc;
-            if (cap0)
-                hipLaunchKernelGGL(idtab_rehash_kernel, dim3(div_up((int)cap0, kIdTabBlock)), block, 0, st, c->mid_hash.as<uint64_t>(),
-                                   c->mid_val.as<int32_t>(), cap0, nt);
-        }
+        HashTabW nt;
+        if (const int rc = next_table_room(c, cap0, M0 + P.n_join, c->mid_next_hash, c->mid_next_val, nt)) return rc;
+        if (const int rc = next_table(c, c->mid_hash, c->mid_val, cap0, nt)) return rc;
         if (P.n_join > 0) {
             const dim3 jgrid(div_up(P.n_join, kIdTabBlock));
             hipLaunchKernelGGL(mid_insert_kernel, jgrid, block, 0, st, P.n_join, c->me_join.as<int32_t>(), d_hash, M0, nt);
             hipLaunchKernelGGL(mid_verify_kernel, jgrid, block, 0, st, P.n_join, c->me_join.as<int32_t>(), d_hash, d_keys, d_off,
                                ModelIdTab{nt.hash, nt.val, nt.mask, a_bytes, a_off}, c->me_found.as<int32_t>());
         }
-        P.cap = cap;
+        P.cap = nt.mask + 1;
     }
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
@@ -3721,7 +3713,7 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     if (P.n_join > 0) HIP_TRY(c, hipMemcpyAsync(found.data(), c->me_found.p, (size_t)P.n_join * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
-    if (c->prof && P.ms >= 0 && c->last_kernel_ms >= 0) P.ms += c->last_kernel_ms;
+    P.ms = kt_sum(c, P.ms, c->last_kernel_ms);
     for (int32_t r = 0; r < P.n_join; r++)
         if (found[r] != M0 + r) return fail(c, MMP_EHIP, "%s: id %d was not inserted (the lookup answered %d)", fn, M0 + r, found[r]);
     return MMP_OK;
@@ -3769,12 +3761,12 @@ try {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     ModelIdsPlan P;
     if (n_models == 0) {  // a valid start: the empty table, every id joins through mmp_models_events_json
-        P.cap = 16;
-        HIP_TRY(c, c->mid_next_hash.ensure((size_t)P.cap * 8));
-        HIP_TRY(c, c->mid_next_val.ensure((size_t)P.cap * 4));
+        HashTabW nt;
+        if (const int rc = next_table_room(c, 0, 0, c->mid_next_hash, c->mid_next_val, nt)) return rc;
+        P.cap = nt.mask + 1;
         HIP_TRY(c, P.fresh_bytes.ensure(16));
         HIP_TRY(c, P.fresh_off.ensure(4));
-        if (const int rc = mid_empty_table(c, HashTabW{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), P.cap - 1})) return rc;
+        if (const int rc = next_table(c, c->mid_hash, c->mid_val, 0, nt)) return rc;
         HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
@@ -3799,17 +3791,12 @@ try {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     std::vector<int32_t> krel;
-    if (const int rc = stage_ids(c, "mmp_model_ids_resolve", "key", keys, key_off, n, krel)) return rc;
+    if (const int rc = stage_strings(c, "mmp_model_ids_resolve", "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
     HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
     HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
-    const int bits = c->tune.model_id_hash_bits;
-    const uint64_t hmask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
-    const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
     KT_BEGIN(c, st);
-    hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, st, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hmask, c->me_hash.as<uint64_t>());
-    hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, st, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, c->me_hash.as<uint64_t>(),
-                       ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(), c->mid_off.as<int32_t>()},
-                       c->me_row.as<int32_t>());
+    mid_resolve_launch(c, n, ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
+                                        c->mid_off.as<int32_t>()});
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -3851,9 +3838,8 @@ try {
     if (const int rc = model_id_space_guard(c, "mmp_models_events_json")) return rc;
     if (n_appended_out) *n_appended_out = 0;
     if (n == 0) return MMP_OK;
-    for (int32_t i = 0; i < n; i++)  // (both kinds, before anything is staged: a refused call changes nothing)
-        if (off[i + 1] < off[i] || key_off[i + 1] < key_off[i])
-            return fail(c, MMP_EINVAL, "mmp_models_events_json: offsets not monotone at %d", i);
+    // (both kinds, before anything is staged: a refused call changes nothing)
+    if (const int rc = check_offsets(c, "mmp_models_events_json", "", off, n, key_off)) return rc;
     if ((off[n] > off[0] && !buf) || (key_off[n] > key_off[0] && !keys)) return fail(c, MMP_EINVAL, "mmp_models_events_json: bad argument");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
@@ -3861,19 +3847,14 @@ try {
     if (const int rc = model_ids_plan(c, "mmp_models_events_json", keys, key_off, n, deleted, flags & MMP_MEV_APPEND, false, P)) return rc;
     if (P.k > 0) {
         // everything behind the resolution is mmp_models_upsert_json: slot / slot_model are on the device already
-        UpsertJsonEvents E{};
-        E.slot = c->j_ev.as<int32_t>();
-        E.slot_model = E.slot + n;
-        E.win = E.slot_model + n;
-        E.s_cnt = E.win + n + 1;
-        E.s_offs = E.s_cnt + n + 1;
-        E.deleted = deleted ? c->me_del.as<uint8_t>() : nullptr;
+        UpsertJsonEvents E = carve(c->j_ev.as<int32_t>(), n, n);  // as model_ids_plan carved it
+        if (!deleted) E.deleted = nullptr;
         E.k = P.k;
         E.count = P.n_before + P.n_join;
         HIP_TRY(c, hipMemsetAsync(E.win, 0xff, ((size_t)P.k + 1) * 4, st));
         std::vector<int32_t> h_model;
         if (const int rc = models_upsert_json_run(c, "mmp_models_events_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
-        if (c->prof && P.ms >= 0 && c->last_kernel_ms >= 0) c->last_kernel_ms += P.ms;  // the call's device span: resolve + parse + apply
+        kt_add(c, P.ms);  // the call's device span: resolve + parse + apply
         model_ids_publish(c, P);
     } else if (c->prof)
         c->last_kernel_ms = P.ms;
