@@ -1179,7 +1179,8 @@ int mmp_registry_unresolved(mmp_ctx *ctx, int32_t *model_out, int32_t max_models
  * The registry's rows are numbered; its listener (MM.java:628, event() :2807-2854) gets a key and a value.  The context keeps the
  * id -> row map on the device — open addressing like the instance table's, but a model id is an arbitrary user string (raw key
  * bytes, any UTF-8, no ASCII rule: nothing orders them), so a slot is matched on its 64-bit FNV-1a hash AND its bytes, which the
- * context keeps in a device arena.  Ids that collide coexist; nothing is refused for colliding.  The table has no deletion.
+ * context keeps in a device arena.  Ids that collide coexist; nothing is refused for colliding.  A slot is never deleted in
+ * place: ids leave only through mmp_models_retire, which builds the next table without them.
  * MMP_MODEL_ID_HASH_BITS=b (read with the other MMP_* switches, per context at mmp_create) masks every model-id hash to its low b
  * bits, 0: all equal — a diagnostic that makes the collision path testable. */
 /* Name the registry's rows 0 .. n_models-1: id i = ids[id_off[i], id_off[i+1]).  The table is built on the device and replaces
@@ -1201,7 +1202,8 @@ int mmp_model_ids_get(mmp_ctx *ctx, int32_t first_row, int32_t n_rows, char *byt
  * key — with the ModelRecord value buf[off[i], off[i+1]).  The keys are resolved, deduplicated and numbered on the device;
  * everything behind the resolution is mmp_models_upsert_json (same parser, same winner rule, same arena append — both calls run
  * one pipeline).  deleted[i] != 0 is ENTRY_DELETED: the value is ignored and the row becomes the empty row; it KEEPS its id and
- * its number, and an id that is registered again gets its old row back (reclaiming rows is out of scope).
+ * its number, and an id that is registered again gets its old row back — until the host hands the row back through
+ * mmp_models_retire, after which the id is unknown again.
  * status_out[i]: 0 applied, 1 malformed value, 2 unknown id (nothing changes; model_idx_out[i] = -1).  An id the table does not
  * know: with MMP_MEV_APPEND in flags the distinct unknown ids of NON-DELETED events join as rows M0, M0+1, ... (M0 = the row count
  * at the call) in order of first appearance, whether or not their values turn out well-formed (the appended-row rule of
@@ -1220,6 +1222,34 @@ int mmp_model_ids_get(mmp_ctx *ctx, int32_t first_row, int32_t n_rows, char *byt
 int mmp_models_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
                            const uint8_t *deleted, uint32_t flags, int32_t *model_idx_out, int64_t *last_unload_out,
                            int32_t *status_out, int32_t *n_appended_out);
+/* Retire registry rows: the named rows leave the index space, and the registry, its entry arena, the id arena and the model-id
+ * table are compacted on the device (retire_kernels.hpp).  rows[0 .. n) are registry rows in [0, M0), M0 = the row count at the
+ * call, in any order; a row named twice is retired once.  The survivors keep their relative order and move down: a survivor's
+ * new row is its old row minus the number of retired rows below it.  remap_out (may be NULL; else max_models >= M0 words):
+ * remap_out[old] = the new row, -1 for a retired one, for all M0 old rows.  *n_models_after_out (may be NULL) = the new count.
+ * Registry: the survivors' records are unchanged — type, last_used, the loaded and failed entries in their order; the retired
+ * rows' entries are dropped, and the call leaves the entry arena squeezed (ent_off = the exclusive prefix of the survivors'
+ * counts, no garbage).  Model-id table, when one is loaded: the retired ids leave the table and the arena,
+ * mmp_model_ids_resolve of a retired id gives -1, mmp_model_ids_get returns the survivors' ids under their new rows, the table
+ * has the capacity of a fresh load of the survivors (no id is hashed again: MMP_MODEL_ID_HASH_BITS still holds), and a retired
+ * id that arrives again through mmp_models_events_json with MMP_MEV_APPEND joins as a new row at the end, like any unknown id.
+ * Both spaces shrink together, so the by-key calls go on without a reload.  Without an id table only the registry is compacted.
+ * MMP_RETIRE_EMPTY_ONLY guards the intended loop — (1) deletion events arrive, (2) the host collects their model_idx, (3) it
+ * retires them later: every named row must then be the empty row (all fields zero, no entries: what a deletion leaves), checked
+ * on the device rows; if one is not — its id was registered again in between, with or without copies — the call is MMP_EINVAL
+ * with nothing changed and mmp_last_error names the lowest such row.
+ * Decisions: the compacted tables are built beside the published ones; the pointers and counts are swapped under the state lock
+ * once the decisions in flight have drained, and the resolved view is rebuilt as in mmp_models_load — a decision sees the whole
+ * old registry or the whole new one, and decisions after the call are right without a commit.  Row numbers the HOST holds —
+ * request rows in flight, the keys of the keyed caches, its own maps — are the host's to renumber from remap_out.
+ * MMP_EINVAL with nothing changed: NULL rows with n > 0, a row outside [0, M0), an unknown flag bit, remap_out with
+ * max_models < M0, a non-empty row under MMP_RETIRE_EMPTY_ONLY.  MMP_ESTATE with nothing changed: an id table is loaded and its
+ * row count no longer equals the registry's (as mmp_model_ids_resolve).  n == 0 is valid and changes nothing: remap_out is the
+ * identity, *n_models_after_out = M0.  No commit is needed before or after.  The work is O(registry), as a reload is — the host
+ * decides how often to call; two runs over the same state and list are byte-identical.  Locking: batch_mu throughout. */
+#define MMP_RETIRE_EMPTY_ONLY 1u
+int mmp_models_retire(mmp_ctx *ctx, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_models,
+                      int32_t *n_models_after_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -203,6 +203,12 @@ final class MmPlace {
     static native int modelsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
                                        ByteBuffer deleted, int flags, ByteBuffer modelIdxOut, ByteBuffer lastUnloadOut,
                                        ByteBuffer statusOut, ByteBuffer nAppendedOut);
+    /** hand registry rows back (mmp_models_retire): rows = n ints, the rows whose deletion the listener has seen; flags 1 = every
+     *  named row must still be the empty row a deletion leaves (else MMP_EINVAL, nothing changed: the id was registered again).
+     *  The survivors move down in order; remapOut (maxModels >= the row count at the call, may be null) gives old row -> new row,
+     *  -1 for a retired one — every row number the Java side holds is renumbered from it; nModelsAfterOut (one int, may be null). */
+    static native int modelsRetire(long h, ByteBuffer rows, int n, int flags, ByteBuffer remapOut, int maxModels,
+                                   ByteBuffer nModelsAfterOut);
     // misc
     static native long minSpaceUnits(int defaultModelSizeUnits, int loadingThreads, long capacityUnits,
                                      boolean haveUnloadManager);

@@ -732,6 +732,19 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsEventsJson(JN
                                         buf<int32_t>(env, nAppendedOut)));
 }
 
+// rows: n ints; remapOut (may be null) holds maxModels ints, nModelsAfterOut (may be null) one (see mmp_models_retire)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRetire(JNIEnv *env, jclass, jlong h, jobject rows, jint n, jint flags,
+                                                                          jobject remapOut, jint maxModels, jobject nModelsAfterOut)
+{
+    if (n < 0 || maxModels < 0 || !holds<int32_t>(env, rows, n, "modelsRetire: rows shorter than n") ||
+        (remapOut && !holds<int32_t>(env, remapOut, maxModels, "modelsRetire: remapOut shorter than maxModels")) ||
+        (nModelsAfterOut && !holds<int32_t>(env, nModelsAfterOut, 1, "modelsRetire: nModelsAfterOut shorter than one int")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_retire(ctx_of(h), buf<int32_t>(env, rows), n, static_cast<uint32_t>(flags), buf<int32_t>(env, remapOut),
+                                   maxModels, buf<int32_t>(env, nModelsAfterOut)));
+}
+
 // ---- misc -----------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL Java_com_ibm_watson_modelmesh_MmPlace_minSpaceUnits(JNIEnv *, jclass,
                                                                             jint defaultModelSizeUnits,

@@ -43,6 +43,7 @@
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
+#include "retire_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -486,6 +487,10 @@ struct mmp_ctx {
     uint32_t mid_mask = 0;
     int32_t mid_n = 0, mid_nbytes = 0;
     bool have_model_ids = false;
+    // mmp_models_retire (retire_kernels.hpp): the caller's list, keep[row], remap[row] and the two atomicMin words (the lowest
+    // non-empty row | the lowest row the verify lost).  Owned by batch_mu, used on c->stream; the triples and their scan are me_cnt /
+    // me_pos / j_scan_tmp.
+    DevBuf ret_rows, ret_keep, ret_remap, ret_word;
 
     // per-call scratch for the host-pointer entry points
     DevBuf s_reqs, s_outs, s_extra, s_a, s_b, s_c, s_d;
@@ -1376,7 +1381,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -3867,6 +3872,158 @@ try {
     if (n_appended_out) *n_appended_out = P.n_join;
     return P.k > 0 ? squeeze_if_garbage(c) : (int)MMP_OK;
 } MMP_CATCH(c, "mmp_models_events_json")
+
+int mmp_models_retire(mmp_ctx *c, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_models,
+                      int32_t *n_models_after_out)
+try {
+    if (!c || n < 0 || (n > 0 && !rows) || (flags & ~MMP_RETIRE_EMPTY_ONLY) || max_models < 0)
+        return fail(c, MMP_EINVAL, "mmp_models_retire: bad argument");
+    // batch_mu keeps every other writer of the registry and the id table away while the compacted tables are built BESIDE the
+    // published ones (decisions go on reading those); the state lock is taken for the swap and the re-resolution only.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t M0 = c->n_models;
+    const bool ids = c->have_model_ids;
+    if (ids && c->mid_n != M0)
+        return fail(c, MMP_ESTATE, "mmp_models_retire: the registry has %d rows for %d loaded model ids (resized by index since mmp_model_ids_load)",
+                    M0, c->mid_n);
+    if (remap_out && max_models < M0) return fail(c, MMP_EINVAL, "mmp_models_retire: room for %d rows in remap_out, the registry has %d", max_models, M0);
+    for (int32_t i = 0; i < n; i++)
+        if (rows[i] < 0 || rows[i] >= M0) return fail(c, MMP_EINVAL, "mmp_models_retire: rows[%d] names row %d of %d", i, rows[i], M0);
+    if (n == 0) {
+        if (remap_out)
+            for (int32_t r = 0; r < M0; r++) remap_out[r] = r;
+        if (n_models_after_out) *n_models_after_out = M0;
+        if (c->prof) c->last_kernel_ms = -1;  // no kernel
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->ret_rows.ensure((size_t)n * 4));
+    HIP_TRY(c, c->ret_keep.ensure((size_t)M0 * 4));
+    HIP_TRY(c, c->ret_remap.ensure((size_t)M0 * 4));
+    HIP_TRY(c, c->ret_word.ensure(8));
+    HIP_TRY(c, c->me_cnt.ensure(((size_t)M0 + 1) * sizeof(RetireCount)));
+    HIP_TRY(c, c->me_pos.ensure(((size_t)M0 + 1) * sizeof(RetireCount)));
+    RetireCount *d_cnt = c->me_cnt.as<RetireCount>(), *d_pos = c->me_pos.as<RetireCount>();
+    int32_t *d_keep = c->ret_keep.as<int32_t>(), *d_remap = c->ret_remap.as<int32_t>(), *d_word = c->ret_word.as<int32_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, RetireCount{0, 0, 0}, (size_t)M0 + 1, RetirePlus(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    HIP_TRY(c, hipMemcpyAsync(c->ret_rows.p, rows, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_keep), 1, (size_t)M0, st));
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
+    const dim3 block(kRetireBlock);
+    const int32_t *old_off = ids ? c->mid_off.as<int32_t>() : nullptr;
+    // 1. mark, and with the flag the lowest named row that is not empty; the triples and their scan
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, c->ret_rows.as<int32_t>(), n, c->models.as<mmp_model_row>(),
+                       (flags & MMP_RETIRE_EMPTY_ONLY) ? 1 : 0, d_keep, d_word);
+    hipLaunchKernelGGL(retire_flags_kernel, dim3(div_up(M0 + 1, kRetireBlock)), block, 0, st, M0, d_keep, c->models.as<mmp_model_row>(), old_off, d_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, RetireCount{0, 0, 0}, (size_t)M0 + 1, RetirePlus(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    int32_t word[2] = {INT32_MAX, INT32_MAX};
+    RetireCount tot{};
+    HIP_TRY(c, hipMemcpyAsync(word, d_word, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, copy_sync(c, &tot, d_pos + M0, sizeof tot, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    const double mark_ms = c->last_kernel_ms;
+    if (word[0] != INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_models_retire: row %d is not empty (registered again since its deletion?); nothing was retired", word[0]);
+    const int32_t M1 = tot.row, B1 = tot.bytes, E1 = tot.ents;
+    // 2. the compacted registry, id arena and table, beside the published ones
+    DevBuf nm, np, nt, nb, no;
+    auto drop = [&] { nm.release(); np.release(); nt.release(); nb.release(); no.release(); };
+    const size_t ecap = (size_t)std::max<int64_t>((int64_t)E1 + E1 / 2, 1024);
+    bool room = nm.ensure((size_t)std::max(M1, 1) * sizeof(mmp_model_row)) == hipSuccess && np.ensure(ecap * 4) == hipSuccess &&
+                nt.ensure(ecap * 8) == hipSuccess;
+    const uint32_t cap0 = ids ? c->mid_mask + 1 : 0u, cap1 = tab_capacity(M1);
+    HashTabW next{};
+    if (room && ids)
+        room = nb.ensure((size_t)B1 + 16) == hipSuccess && no.ensure(((size_t)M1 + 1) * 4) == hipSuccess &&
+               c->mid_next_hash.ensure((size_t)cap1 * 8) == hipSuccess && c->mid_next_val.ensure((size_t)cap1 * 4) == hipSuccess;
+    if (!room) {
+        drop();
+        return fail(c, MMP_ENOMEM, "mmp_models_retire: out of device memory");
+    }
+    int rc = MMP_OK;
+    if (ids) {
+        next = HashTabW{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), cap1 - 1};
+        rc = empty_table(c, next);
+        if (rc == MMP_OK && hipMemsetAsync(no.p, 0, 4, st) != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_models_retire: hipMemsetAsync failed");
+    }
+    std::vector<int32_t> remap((size_t)M0);
+    if (rc == MMP_OK) {
+        const RetireMove A{c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
+                           ids ? c->mid_bytes.as<char>() : nullptr, old_off, nm.as<mmp_model_row>(), np.as<int32_t>(), nt.as<int64_t>(),
+                           nb.as<char>(), no.as<int32_t>()};
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(retire_move_kernel, dim3(div_up(M0, kRetireBlock)), block, 0, st, M0, d_keep, d_pos, A, d_remap);
+        if (ids) {
+            // 3. the stored hashes of the survivors into the emptied next table; 4. a verifying lookup in a launch of its own
+            const dim3 sgrid(div_up((int)cap0, kRetireBlock));
+            hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), cap0, d_remap, next);
+            hipLaunchKernelGGL(retire_verify_kernel, sgrid, block, 0, st, c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), cap0, d_remap,
+                               ModelIdTab{next.hash, next.val, next.mask, nb.as<char>(), no.as<int32_t>()}, d_word + 1);
+        }
+        KT_END(c, st);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(remap.data(), d_remap, (size_t)M0 * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(word + 1, d_word + 1, 4, hipMemcpyDeviceToHost, st);
+        const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
+        if (e == hipSuccess) e = se;
+        if (e != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_models_retire: %s", hipGetErrorString(e));
+    } else
+        (void)hipStreamSynchronize(st);
+    if (rc == MMP_OK && word[1] != INT32_MAX)
+        rc = fail(c, MMP_EHIP, "mmp_models_retire: the id of new row %d was not found in the compacted table", word[1]);
+    if (rc != MMP_OK) {
+        drop();
+        return rc;
+    }
+    kt_collect(c);
+    kt_add(c, mark_ms);  // the call's device span: mark + scan + move + table + verify
+    // 3. nothing fails from here on but the drain and the re-resolution: registry, arena, table and counts change together
+    DevBuf om, op, ot;
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);
+        const hipError_t q = quiesce_decisions(c);  // kernels that captured the old tables; the resolved view is rewritten in place
+        if (q != hipSuccess) {
+            drop();
+            HIP_TRY(c, q);
+        }
+        om = c->models, op = c->ent_pod, ot = c->ent_time;
+        c->models = nm, c->ent_pod = np, c->ent_time = nt;
+        c->n_models = M1;
+        c->n_entries = E1;
+        c->ent_live = E1;
+        c->m_cnt.resize(M0, 0);
+        for (int32_t r = 0; r < M0; r++)  // (remap[r] <= r: in place)
+            if (remap[r] >= 0) c->m_cnt[remap[r]] = c->m_cnt[r];
+        c->m_cnt.resize(M1);
+        c->u_stamp.assign(std::min<size_t>(c->u_stamp.size(), (size_t)M1), 0);  // (stamps name a call generation: zero = none)
+        c->plan.model_map_n = std::min(c->plan.model_map_n, M1);
+        if (ids) {
+            std::swap(c->mid_hash, c->mid_next_hash);
+            std::swap(c->mid_val, c->mid_next_val);
+            c->mid_mask = cap1 - 1;
+            c->mid_bytes.release();
+            c->mid_off.release();
+            c->mid_bytes = nb, c->mid_off = no;
+            c->mid_n = M1;
+            c->mid_nbytes = B1;
+        }
+        om.release();
+        op.release();
+        ot.release();
+        c->side[0].rmodels_ok = c->side[1].rmodels_ok = false;
+        split_reset(c);
+        if (const int rr = rebuild_resolved(c)) return rr;
+    }
+    if (remap_out) memcpy(remap_out, remap.data(), (size_t)M0 * 4);
+    if (n_models_after_out) *n_models_after_out = M1;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_models_retire")
 
 int mmp_pods_get(mmp_ctx *c, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out)
 try {

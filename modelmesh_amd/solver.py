@@ -357,6 +357,20 @@ class Solver:
             self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
         return status[:n], idx[:n], lul[:n], n_app.value
 
+    def models_retire(self, rows, empty_only=False):
+        """Retire registry rows (mmp_models_retire): the rows leave the index space, registry and id table are compacted on the
+        device.  Returns remap, int32[M0]: the new row of every old row, -1 for a retired one."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        m0 = getattr(self, "n_models", 0)
+        remap = np.full(max(m0, 1), -1, np.int32)
+        after = C.c_int32(0)
+        self._ck(self.lib.mmp_models_retire(self.h, ptr(rows) if len(rows) else None, len(rows),
+                                            _lib.RETIRE_EMPTY_ONLY if empty_only else 0, ptr(remap), m0, C.byref(after)))
+        self.n_models = after.value
+        if len(rows):
+            self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
+        return remap[:m0]
+
     def get_pods(self) -> np.ndarray:
         n = C.c_int32(0)
         self._ck(self.lib.mmp_pods_get(self.h, None, 0, C.byref(n)))
