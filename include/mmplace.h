@@ -1250,6 +1250,49 @@ int mmp_models_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_of
 #define MMP_RETIRE_EMPTY_ONLY 1u
 int mmp_models_retire(mmp_ctx *ctx, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_models,
                       int32_t *n_models_after_out);
+/* Retire instance rows: the named instances leave the index space, the other index space of the wire-format path and the one
+ * that churns (every rolling update replaces every instance by one with a new id, and a tombstone keeps its index).  pods[0 .. n)
+ * are staged instance indices in [0, P0), P0 = the staged count at the call, in any order; an index named twice is retired once.
+ * The survivors keep their relative order and move down: a survivor's new index is its old index minus the number of retired
+ * indices below it.  remap_out (may be NULL; else max_pods >= P0 words): remap_out[old] = the new index, -1 for a retired one,
+ * for all P0 old indices.  *n_pods_after_out (may be NULL) = the new count P1.  *n_entries_unresolved_out (may be NULL) = the
+ * registry entries the call turned into pod -1.
+ * Staged table, label words and counts: compacted.  With an id table loaded the survivors' id_order becomes their rank among the
+ * surviving ids — what a fresh mmp_pod_ids_load of the survivors gives; replica_set numbers and the interning are NOT renumbered
+ * (mmp_replaced_rs_load and the upgrade tracker hold them, and an id prefix seen before keeps its number when it comes back).
+ * Without an id table the rows keep the id_order the host supplied.  Instance-id table and id store: the retired ids leave both;
+ * the table gets the capacity of a fresh load of the survivors, built from the stored hashes (no id is hashed again) and verified
+ * in a launch of its own.  A retired id is unknown afterwards: mmp_pods_events_json answers status 2 for it, and with
+ * MMP_PEV_APPEND it joins as a new index at the end.  Type table: the retired instances' bits are squeezed out of the allowed /
+ * prefer rows, whichever call loaded them — no reload is needed.  `missings` marks: the survivors' marks move with them;
+ * mmp_registry_missing_get returns the old map read through remap.  Registry: rows, times and offsets are untouched and the entry
+ * arena is NOT squeezed; an entry naming a survivor gets its new index, an entry naming a retired instance becomes -1 (it still
+ * counts as a copy and excludes nobody: mmp_registry_unresolved), an entry outside [0, P0) is copied as it is.
+ * MMP_PODS_RETIRE_GONE_ONLY: every named row must be a tombstone in the staged table (MMP_POD_TOMBSTONE set, MMP_POD_LIVE clear) —
+ * the guard against an id that came back between its deletion and the retire; otherwise MMP_EINVAL, mmp_last_error names the
+ * lowest such index.  MMP_PODS_RETIRE_UNREFERENCED: no entry a registry row references, loaded or failed, may name a retired
+ * instance (checked on the device registry; the arena's garbage is not looked at); otherwise MMP_EINVAL naming the lowest such
+ * instance.  The intended loop: a deletion event tombstones the row, mmp_registry_prune removes its registrations after
+ * gone_after_ms, then both guards hold and the index is handed back.
+ * Decisions: this call changes what the published snapshot is indexed by, so it ENDS IN A COMMIT.  Everything above is built
+ * beside the published state; then the state lock is taken exclusively, the decisions in flight drain, the inputs are swapped and
+ * the stages of mmp_snapshot_commit run from scratch and publish — with the state lock held, which is accepted for this call:
+ * decisions issued meanwhile wait, a decision sees the whole old index space or the whole new one, and every answer after the
+ * call is in the new numbering.  If the commit stage fails (MMP_EORDER when the staged table carries other edits) the old inputs
+ * are put back and nothing has changed.  A context without a published snapshot only has its inputs compacted.
+ * Everything numbered by instance that the HOST holds — request rows, exclusion lists, serve counters, self_pod, fail_pod — is
+ * the host's to renumber from remap_out.  Cache numbers (mmp_caches_load*) are the host's own index space and are not touched.
+ * MMP_EINVAL with nothing changed (rows, ids, table, labels, types, marks, registry, snapshot): NULL pods with n > 0, an index
+ * outside [0, P0), an unknown flag bit, remap_out with max_pods < P0, either guard.  MMP_ESTATE with nothing changed: an id table
+ * is loaded and no longer covers the staged rows (the rule of mmp_pod_ids_append); a type table is loaded whose word count is not
+ * that of the P0 staged rows (the table a commit refuses: it could not be squeezed, and must not pass the commit's check once the
+ * count crosses the word edge back — reload the types first); the context is a pod-axis shard (out of scope: reload the shards).  n == 0 is valid and changes nothing: remap_out is the identity and no commit is run.  The work is
+ * O(P0 + table slots + entry arena + registry rows) plus the commit; two runs over the same state and list are byte-identical.
+ * Locking: batch_mu throughout, the state lock from the swap to the publication. */
+#define MMP_PODS_RETIRE_GONE_ONLY 1u
+#define MMP_PODS_RETIRE_UNREFERENCED 2u
+int mmp_pods_retire(mmp_ctx *ctx, const int32_t *pods, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_pods,
+                    int32_t *n_pods_after_out, int64_t *n_entries_unresolved_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -209,6 +209,14 @@ final class MmPlace {
      *  -1 for a retired one — every row number the Java side holds is renumbered from it; nModelsAfterOut (one int, may be null). */
     static native int modelsRetire(long h, ByteBuffer rows, int n, int flags, ByteBuffer remapOut, int maxModels,
                                    ByteBuffer nModelsAfterOut);
+    /** hand instance indices back (mmp_pods_retire): pods = n ints, the instances whose deletion the instance listener has seen
+     *  and whose registrations the reaper has pruned; flags 1 = every named row must still be a tombstone (else MMP_EINVAL,
+     *  nothing changed: the id came back), 2 = no registry record may still name one.  The survivors move down in order and the
+     *  call commits; remapOut (maxPods >= the instance count at the call, may be null) gives old index -> new index, -1 for a
+     *  retired one — every instance number the Java side holds (request rows, exclusions, serve counters, selfPod) is renumbered
+     *  from it; nPodsAfterOut (one int) and nEntriesUnresolvedOut (one long, the entries that now name nobody) may be null. */
+    static native int podsRetire(long h, ByteBuffer pods, int n, int flags, ByteBuffer remapOut, int maxPods,
+                                 ByteBuffer nPodsAfterOut, ByteBuffer nEntriesUnresolvedOut);
     // misc
     static native long minSpaceUnits(int defaultModelSizeUnits, int loadingThreads, long capacityUnits,
                                      boolean haveUnloadManager);

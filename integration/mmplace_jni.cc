@@ -745,6 +745,22 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRetire(JNIEnv
                                    maxModels, buf<int32_t>(env, nModelsAfterOut)));
 }
 
+// pods: n ints; remapOut (may be null) holds maxPods ints, nPodsAfterOut (may be null) one int, nEntriesUnresolvedOut (may be null)
+// one long (see mmp_pods_retire)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_podsRetire(JNIEnv *env, jclass, jlong h, jobject pods, jint n, jint flags,
+                                                                        jobject remapOut, jint maxPods, jobject nPodsAfterOut,
+                                                                        jobject nEntriesUnresolvedOut)
+{
+    if (n < 0 || maxPods < 0 || !holds<int32_t>(env, pods, n, "podsRetire: pods shorter than n") ||
+        (remapOut && !holds<int32_t>(env, remapOut, maxPods, "podsRetire: remapOut shorter than maxPods")) ||
+        (nPodsAfterOut && !holds<int32_t>(env, nPodsAfterOut, 1, "podsRetire: nPodsAfterOut shorter than one int")) ||
+        (nEntriesUnresolvedOut && !holds<int64_t>(env, nEntriesUnresolvedOut, 1, "podsRetire: nEntriesUnresolvedOut shorter than one long")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_pods_retire(ctx_of(h), buf<int32_t>(env, pods), n, static_cast<uint32_t>(flags), buf<int32_t>(env, remapOut), maxPods,
+                                 buf<int32_t>(env, nPodsAfterOut), buf<int64_t>(env, nEntriesUnresolvedOut)));
+}
+
 // ---- misc -----------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL Java_com_ibm_watson_modelmesh_MmPlace_minSpaceUnits(JNIEnv *, jclass,
                                                                             jint defaultModelSizeUnits,

@@ -175,6 +175,9 @@ PEV_APPLIED, PEV_MALFORMED, PEV_UNKNOWN = 0, 1, 2  # status_out
 MEV_APPEND = 1
 # mmp_models_retire: every named row must be the empty row a deletion leaves
 RETIRE_EMPTY_ONLY = 1
+# mmp_pods_retire: every named row must be a tombstone / no referenced registry entry may name a retired instance
+PODS_RETIRE_GONE_ONLY = 1
+PODS_RETIRE_UNREFERENCED = 2
 
 CACHE_ENTRY = np.dtype(
     [("model", "<i4"), ("weight", "<i4"), ("last_used", "<i8"), ("interval_count", "<i8"), ("last_heavy_time", "<i8"),
@@ -307,6 +310,7 @@ SYMBOLS = [
     ("mmp_model_ids_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),
     ("mmp_models_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_models_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mmp_pods_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

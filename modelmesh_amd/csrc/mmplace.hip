@@ -43,7 +43,7 @@
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
-#include "retire_kernels.hpp"
+#include "pods_retire_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -489,7 +489,8 @@ struct mmp_ctx {
     bool have_model_ids = false;
     // mmp_models_retire (retire_kernels.hpp): the caller's list, keep[row], remap[row] and the two atomicMin words (the lowest
     // non-empty row | the lowest row the verify lost).  Owned by batch_mu, used on c->stream; the triples and their scan are me_cnt /
-    // me_pos / j_scan_tmp.
+    // me_pos / j_scan_tmp.  mmp_pods_retire (pods_retire_kernels.hpp) keeps its remap[instance] in ret_remap and its PodsRetireWords
+    // in ret_word, under the same rule.
     DevBuf ret_rows, ret_keep, ret_remap, ret_word;
 
     // per-call scratch for the host-pointer entry points
@@ -2572,17 +2573,16 @@ void publish_cluster_stats(mmp_ctx *c, const StatsAcc &acc)
     c->stats.instance_count = acc.instance_count;
     c->stats.model_copy_count = acc.model_copy_count;
 }
-}  // namespace
 
-int mmp_snapshot_commit(mmp_ctx *c)
-try {
-    if (!c) return MMP_EINVAL;
+// The commit itself (mmp_snapshot_commit below; the caller holds batch_mu).  state_locked: the caller holds the state lock as well
+// and keeps it — mmp_pods_retire, whose swapped inputs and the snapshot built from them must become visible together.
+int commit_staged(mmp_ctx *c, bool state_locked)
+{
     // Wait-free for decisions (SURVEY.md §8b "Threading"): the whole build runs with batch_mu only.  batch_mu keeps
     // the inputs still — every loader of the instance table, the type table, the registry and the replica-set list
     // takes it, and so does any other commit — and it owns c->stream and the commit scratch.  Everything a decision
     // reads is double-buffered (SnapBufs + SnapSide): the build fills the set that is NOT published, decisions keep
     // capturing the published one under c->mu, and c->mu is taken only for the pointer swap at the end.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
     if (c->n_shards > 0)
         return fail(c, MMP_ESTATE, "context is a pod-axis shard: commit with mmp_shard_rank_dev + mmp_shard_commit_dev");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -2668,7 +2668,8 @@ try {
     // long variant carries the prefix-table jump that finds it without the wave path
     if (c->tune.long_mode < 0 && acc.sparse_types) next_long = true;
     // publish: the only part of a commit a decision can ever wait for
-    std::lock_guard<std::shared_mutex> g(c->mu);
+    std::unique_lock<std::shared_mutex> g(c->mu, std::defer_lock);
+    if (!state_locked) g.lock();
     resident_stop(c);  // it answers for the snapshot it was launched with; the next single request starts one on the new
     c->order_total = oc.sort_legal;
     if (delta) {
@@ -2687,6 +2688,14 @@ try {
     split_reset(c);
     publish_cluster_stats(c, acc);
     return MMP_OK;
+}
+}  // namespace
+
+int mmp_snapshot_commit(mmp_ctx *c)
+try {
+    if (!c) return MMP_EINVAL;
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    return commit_staged(c, false);
 } MMP_CATCH(c, "mmp_snapshot_commit")
 
 int mmp_delta_commits(mmp_ctx *c, int64_t *n_out)
@@ -4024,6 +4033,234 @@ try {
     if (n_models_after_out) *n_models_after_out = M1;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_models_retire")
+
+int mmp_pods_retire(mmp_ctx *c, const int32_t *pods, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_pods,
+                    int32_t *n_pods_after_out, int64_t *n_entries_unresolved_out)
+try {
+    if (!c || n < 0 || (n > 0 && !pods) || (flags & ~(MMP_PODS_RETIRE_GONE_ONLY | MMP_PODS_RETIRE_UNREFERENCED)) || max_pods < 0)
+        return fail(c, MMP_EINVAL, "mmp_pods_retire: bad argument");
+    // batch_mu keeps every other writer of the commit's inputs, the registry and the id table away while the compacted state is
+    // built BESIDE the published one (decisions go on reading that); the state lock is taken for the swap and held across the commit.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_pods_retire: not available on a pod-axis shard context");
+    const int32_t P0 = (int32_t)c->pods.size();
+    const bool ids = c->have_ids;
+    if (ids)
+        if (const int rc = id_space_guard(c, "mmp_pods_retire")) return rc;
+    // Type rows loaded for another word count are stale, and a commit refuses them.  They must stay refused: squeezing is impossible
+    // (their bits belong to no numbering of these rows) and leaving them would let the check pass once P crosses the word edge back.
+    if (c->n_types > 0 && c->types_w != div_up(P0, 64))
+        return fail(c, MMP_ESTATE, "mmp_pods_retire: the type bitmaps were loaded for a different pod count (%d words for %d pods); reload them first",
+                    c->types_w, P0);
+    if (remap_out && max_pods < P0) return fail(c, MMP_EINVAL, "mmp_pods_retire: room for %d pods in remap_out, the table has %d", max_pods, P0);
+    for (int32_t i = 0; i < n; i++)
+        if (pods[i] < 0 || pods[i] >= P0) return fail(c, MMP_EINVAL, "mmp_pods_retire: pods[%d] names instance %d of %d", i, pods[i], P0);
+    if (n == 0) {
+        if (remap_out)
+            for (int32_t p = 0; p < P0; p++) remap_out[p] = p;
+        if (n_pods_after_out) *n_pods_after_out = P0;
+        if (n_entries_unresolved_out) *n_entries_unresolved_out = 0;
+        if (c->prof) c->last_kernel_ms = -1;  // no kernel
+        return MMP_OK;
+    }
+    // 1. the remap, on the host: P0 words from the caller's list
+    std::vector<int32_t> remap((size_t)P0, 0);
+    for (int32_t i = 0; i < n; i++) remap[pods[i]] = -1;
+    int32_t P1 = 0;
+    for (int32_t p = 0; p < P0; p++) {
+        if (remap[p] == 0) {
+            remap[p] = P1++;
+            continue;
+        }
+        if ((flags & MMP_PODS_RETIRE_GONE_ONLY) && ((c->pods[p].flags & MMP_POD_LIVE) || !(c->pods[p].flags & MMP_POD_TOMBSTONE)))
+            return fail(c, MMP_EINVAL, "mmp_pods_retire: instance %d is not a tombstone (its id came back since the deletion?); nothing was retired", p);
+    }
+    // 2. what the device holds by instance index, beside the published state: the entry arena's pods, the marks, the id table
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int32_t M = c->n_models, E = c->n_entries, miss0 = std::min(c->miss_n, P0);
+    int32_t miss1 = 0;
+    for (int32_t p = 0; p < miss0; p++) miss1 += remap[p] >= 0;
+    HIP_TRY(c, c->ret_remap.ensure((size_t)P0 * 4));
+    HIP_TRY(c, c->ret_word.ensure(sizeof(PodsRetireWords)));
+    const int32_t *d_remap = c->ret_remap.as<int32_t>();
+    PodsRetireWords *d_words = c->ret_word.as<PodsRetireWords>();
+    PodsRetireWords words{0ull, INT32_MAX, INT32_MAX};
+    // the new arena and marks, after the swap the old ones: freed on every way out, an exception of step 3 included
+    struct Beside {
+        DevBuf np, nmiss;
+        ~Beside() { np.release(), nmiss.release(); }
+    } beside;
+    DevBuf &np = beside.np, &nmiss = beside.nmiss;
+    auto drop = [&] { np.release(); nmiss.release(); };
+    const uint32_t cap0 = ids ? c->idtab_mask + 1 : 0u;
+    HashTabW next{};
+    bool room = (!c->ent_pod.p || np.ensure(c->ent_pod.cap) == hipSuccess) && (miss1 == 0 || nmiss.ensure((size_t)miss1 * 8) == hipSuccess);
+    if (room && ids) room = next_table_room(c, 0, P1, c->idtab_next_hash, c->idtab_next_val, next) == MMP_OK;  // tab_capacity(P1): the table shrinks
+    if (!room) {
+        drop();
+        return fail(c, MMP_ENOMEM, "mmp_pods_retire: out of device memory");
+    }
+    const dim3 block(kRetireBlock);
+    hipError_t e = hipMemcpyAsync(c->ret_remap.p, remap.data(), (size_t)P0 * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_words, &words, sizeof words, hipMemcpyHostToDevice, st);
+    int rc = MMP_OK;
+    KT_BEGIN(c, st);
+    if (e == hipSuccess) {
+        if (E > 0)
+            hipLaunchKernelGGL(pods_retire_entries_kernel, dim3(div_up(E, kRetireBlock)), block, 0, st, c->ent_pod.as<int32_t>(), E, d_remap, P0,
+                               np.as<int32_t>());
+        if (M > 0)
+            hipLaunchKernelGGL(pods_retire_count_kernel, dim3(div_up(M, kRetireBlock)), block, 0, st, c->models.as<mmp_model_row>(), M,
+                               c->ent_pod.as<int32_t>(), d_remap, P0, d_words);
+        if (miss0 > 0 && miss1 > 0)
+            hipLaunchKernelGGL(pods_retire_marks_kernel, dim3(div_up(miss0, kRetireBlock)), block, 0, st, c->miss_since.as<int64_t>(), miss0,
+                               d_remap, nmiss.as<int64_t>());
+        if (ids) {
+            // the stored hashes of the survivors into the emptied next table; a verifying lookup in a launch of its own
+            rc = empty_table(c, next);
+            if (rc == MMP_OK) {
+                const dim3 sgrid(div_up((int)cap0, kRetireBlock));
+                hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), cap0, d_remap, next);
+                hipLaunchKernelGGL(pods_retire_verify_kernel, sgrid, block, 0, st, c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), cap0,
+                                   d_remap, P0, HashTab{next.hash, next.val, next.mask}, d_words);
+            }
+        }
+    }
+    KT_END(c, st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&words, d_words, sizeof words, hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
+    if (e == hipSuccess) e = se;
+    if (rc == MMP_OK && e != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_pods_retire: %s", hipGetErrorString(e));
+    if (rc == MMP_OK && (flags & MMP_PODS_RETIRE_UNREFERENCED) && words.n_turned > 0)
+        rc = fail(c, MMP_EINVAL, "mmp_pods_retire: instance %d is still named by a registry entry (prune the registry first); nothing was retired",
+                  words.lowest_named);
+    if (rc == MMP_OK && words.lost != INT32_MAX)
+        rc = fail(c, MMP_EHIP, "mmp_pods_retire: the id of new instance %d was not found in the compacted table", words.lost);
+    if (rc != MMP_OK) {
+        drop();
+        return rc;
+    }
+    kt_collect(c);
+    const double build_ms = c->last_kernel_ms;
+    // 3. what the host holds by instance index: rows, labels, type bit rows, the id store
+    struct HostSide {
+        std::vector<mmp_pod_row> pods;
+        std::vector<uint64_t> label_word, allowed, prefer;
+        std::vector<int32_t> label_count, id_offs, id_sorted, replica_set_v, dirty;
+        std::vector<uint32_t> id_order_v;
+        std::string id_bytes;
+        int32_t types_w = 0;
+    } H;
+    H.pods.resize((size_t)P1);
+    H.label_word.assign((size_t)P1, 0);
+    H.label_count.assign((size_t)P1, 0);
+    const bool labels = c->pod_label_word.size() == (size_t)P0 && c->pod_label_count.size() == (size_t)P0;
+    for (int32_t p = 0; p < P0; p++) {
+        const int32_t q = remap[p];
+        if (q < 0) continue;
+        H.pods[q] = c->pods[p];
+        if (labels) H.label_word[q] = c->pod_label_word[p], H.label_count[q] = c->pod_label_count[p];
+    }
+    if (ids) {
+        // the ranks of the survivors among the surviving ids: id_sorted filtered, not sorted again
+        H.id_offs.assign(1, 0);
+        H.id_order_v.assign((size_t)P1, 0);
+        H.replica_set_v.assign((size_t)P1, -1);
+        for (int32_t p = 0; p < P0; p++) {
+            if (remap[p] < 0) continue;
+            H.id_bytes.append(c->id_bytes, (size_t)c->id_offs[p], (size_t)(c->id_offs[p + 1] - c->id_offs[p]));
+            H.id_offs.push_back((int32_t)H.id_bytes.size());
+            H.replica_set_v[remap[p]] = c->replica_set_v[p];
+        }
+        H.id_sorted.reserve((size_t)P1);
+        for (const int32_t p : c->id_sorted)
+            if (remap[p] >= 0) {
+                H.id_order_v[remap[p]] = (uint32_t)H.id_sorted.size();
+                H.id_sorted.push_back(remap[p]);
+            }
+        for (int32_t q = 0; q < P1; q++) H.pods[q].id_order = H.id_order_v[q];
+    }
+    const bool types = c->n_types > 0;  // (they cover P0: checked on the way in)
+    if (types) {
+        const int32_t W0 = c->types_w, W1 = div_up(P1, 64);
+        H.types_w = W1;
+        H.allowed.assign((size_t)c->n_types * W1, 0);
+        H.prefer.assign((size_t)c->n_types * W1, 0);
+        for (int32_t t = 0; t < c->n_types; t++) {
+            const uint64_t *a0 = c->allowed.data() + (size_t)t * W0, *f0 = c->prefer.data() + (size_t)t * W0;
+            uint64_t *a1 = H.allowed.data() + (size_t)t * W1, *f1 = H.prefer.data() + (size_t)t * W1;
+            for (int32_t p = 0; p < P0; p++) {
+                const int32_t q = remap[p];
+                if (q < 0) continue;
+                a1[q >> 6] |= ((a0[p >> 6] >> (p & 63)) & 1ull) << (q & 63);
+                f1[q >> 6] |= ((f0[p >> 6] >> (p & 63)) & 1ull) << (q & 63);
+            }
+        }
+    }
+    // 4. the swap and the commit, under the state lock: a decision sees the whole old index space or the whole new one
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);
+        const hipError_t q = quiesce_decisions(c);
+        if (q != hipSuccess) {
+            drop();
+            HIP_TRY(c, q);
+        }
+        const bool dirty_all0 = c->dirty_all;
+        const int32_t miss_n0 = c->miss_n;
+        const uint32_t mask0 = c->idtab_mask;
+        const auto swap_inputs = [&] {  // (its own inverse)
+            c->pods.swap(H.pods);
+            c->pod_label_word.swap(H.label_word);
+            c->pod_label_count.swap(H.label_count);
+            c->dirty.swap(H.dirty);
+            if (types) {
+                c->allowed.swap(H.allowed);
+                c->prefer.swap(H.prefer);
+                std::swap(c->types_w, H.types_w);
+                c->types_gen++;  // (never back to a generation a device copy may carry)
+                c->sig_valid = false;
+            }
+            if (ids) {
+                c->id_bytes.swap(H.id_bytes);
+                c->id_offs.swap(H.id_offs);
+                c->id_sorted.swap(H.id_sorted);
+                c->id_order_v.swap(H.id_order_v);
+                c->replica_set_v.swap(H.replica_set_v);
+                std::swap(c->idtab_hash, c->idtab_next_hash);
+                std::swap(c->idtab_val, c->idtab_next_val);
+            }
+            std::swap(c->ent_pod, np);
+            std::swap(c->miss_since, nmiss);
+        };
+        swap_inputs();
+        c->idtab_mask = ids ? next.mask : mask0;
+        c->miss_n = miss1;
+        c->dirty_all = true;
+        const bool commit = c->committed;
+        try {
+            if (commit) rc = commit_staged(c, true);
+        } catch (const std::exception &ex) {
+            rc = fail(c, MMP_ENOMEM, "mmp_pods_retire: %s in the commit stage", ex.what());
+        }
+        if (rc != MMP_OK) {  // nothing was published: the old inputs go back
+            (void)hipStreamSynchronize(st);
+            swap_inputs();
+            c->idtab_mask = mask0;
+            c->miss_n = miss_n0;
+            c->dirty_all = dirty_all0;
+            drop();
+            return rc;
+        }
+        if (commit) kt_add(c, build_ms);  // the call's device span: remap + count + marks + table + verify, and the commit's
+    }
+    drop();  // the old arena and marks
+    if (remap_out) memcpy(remap_out, remap.data(), (size_t)P0 * 4);
+    if (n_pods_after_out) *n_pods_after_out = P1;
+    if (n_entries_unresolved_out) *n_entries_unresolved_out = (int64_t)words.n_turned;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_pods_retire")
 
 int mmp_pods_get(mmp_ctx *c, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out)
 try {

@@ -371,6 +371,32 @@ class Solver:
             self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
         return remap[:m0]
 
+    def pods_retire(self, pods, gone_only=False, unreferenced=False):
+        """Retire instance rows (mmp_pods_retire): the instances leave the index space; the staged table, the id table, the type
+        rows, the marks and the registry's entries are renumbered and, with a published snapshot, committed.  Returns
+        (remap, n_entries_unresolved): remap is int32[P0], the new index of every old index, -1 for a retired one."""
+        pods = np.ascontiguousarray(pods, dtype=np.int32).reshape(-1)
+        p0 = self.n_pods
+        remap = np.full(max(p0, 1), -1, np.int32)
+        after, turned = C.c_int32(0), C.c_int64(0)
+        flags = (_lib.PODS_RETIRE_GONE_ONLY if gone_only else 0) | (_lib.PODS_RETIRE_UNREFERENCED if unreferenced else 0)
+        self._ck(self.lib.mmp_pods_retire(self.h, ptr(pods) if len(pods) else None, len(pods), flags, ptr(remap), p0,
+                                          C.byref(after), C.byref(turned)))
+        remap = remap[:p0]
+        self.n_pods = after.value
+        # the wrapper's own per-instance mirrors follow the renumbering: the live flags and the registry copy serve_counters reads
+        mirror = getattr(self, "_live", None)
+        if mirror is not None:
+            self._grow_live(p0)
+            self._live = self._live[:p0][remap >= 0]
+        ent = getattr(self, "_ent_pod", None)
+        if ent is not None and len(pods):
+            ent = np.array(ent, dtype=np.int32)
+            known = (ent >= 0) & (ent < p0)
+            ent[known] = remap[ent[known]]
+            self._ent_pod = ent
+        return remap, turned.value
+
     def get_pods(self) -> np.ndarray:
         n = C.c_int32(0)
         self._ck(self.lib.mmp_pods_get(self.h, None, 0, C.byref(n)))
