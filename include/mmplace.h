@@ -1293,6 +1293,61 @@ int mmp_models_retire(mmp_ctx *ctx, const int32_t *rows, int32_t n, uint32_t fla
 #define MMP_PODS_RETIRE_UNREFERENCED 2u
 int mmp_pods_retire(mmp_ctx *ctx, const int32_t *pods, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_pods,
                     int32_t *n_pods_after_out, int64_t *n_entries_unresolved_out);
+/* ---- the write side of the wire format (rewrite_kernels.hpp) ---------------------------------------------------------------------
+ * Every edit of the registry ends, in the reference, in a compare-and-set that writes a WHOLE serialised ModelRecord back to the
+ * KV store (ModelMesh.java: 13 conditionalSet / conditionalSetAndGet sites, 12 of them on the registry).  The library answers an edit with edit rows
+ * (mmp_registry_op_edit, mmp_prune_edit, mmp_janitor_edit); this call turns the stored value of a record, plus the record as the
+ * device now holds it, into the value to store next — so that the host decodes no ModelRecord on the way out either.  The device
+ * does not hold type, mPath, encKey, refs, autoDel, the failure texts or any future field: those pass through BYTE FOR BYTE from
+ * the old value.  It renders what the mesh owns, from the resident row: instanceIds, failedIn, lu, optionally lul, and the key set
+ * of fails.
+ *
+ * Value i: the old value old_buf[old_off[i], old_off[i+1]) of registry row rows[i]; a row may appear more than once.  With the
+ * OWNED names instanceIds, failedIn, fails, lu — and lul when last_unload != NULL — the new value is
+ *     { kept members , owned members }
+ * joined by single commas with no other whitespace.
+ * Kept members: every top-level member of the old value whose name is not an owned name, in document order, every occurrence of
+ * a duplicate included, each copied verbatim from the opening quote of its key to the last byte of its value (whitespace inside
+ * that span stays, whitespace around it goes).  Names match as the parser matches them: raw bytes, so an escaped spelling of an
+ * owned name is an unknown member and is kept.  The owned members come last, so under any reader for which a later duplicate wins
+ * the owned ones win.  With last_unload == NULL, lul is an ordinary kept member.
+ * Owned members, in this order, each omitted when it holds the bean's default, as Jackson omits it:
+ *   1. "instanceIds":{"<id>":<time>,...}   the row's loaded entries in resident order; omitted when there are none
+ *   2. "failedIn":{...}                    the failed entries likewise
+ *   3. "fails":{...}                       start from the LAST top-level fails member of the old value that is an object (null or
+ *        absent: none); keep, verbatim and in order, the members whose raw key bytes equal the id of an instance in the row's
+ *        failed list; if fail_pod[i] >= 0, drop those keyed by that instance's id and, if its message
+ *        fail_msg[fail_msg_off[i], fail_msg_off[i+1]) is not empty and the instance is in the failed list, append
+ *        "<id>":{"msg":"<escaped message>"} — addLoadFailure / removeLoadFailure (ModelRecord.java:156-179) and the
+ *        secondary.remove of the prune.  Escaping: '"' becomes \", '\' becomes \\, a byte below 0x20 becomes \u00xx in
+ *        lower-case hex, everything else is verbatim.  Omitted when it ends up empty
+ *   4. "lu":<last_used>                    omitted when 0
+ *   5. "lul":<last_unload[i]>              only when last_unload is given; omitted when 0
+ * Times are int64 in plain decimal, Long.MIN_VALUE included.  A row the registry holds as empty (a deleted record) renders like
+ * any other: its kept members and no owned ones.
+ *
+ * status_out[i]: MMP_MRW_OK; MMP_MRW_MALFORMED exactly when mmp_models_upsert_json gives status 1 for the old value as a
+ * non-deleted event (the parser itself runs over the old values: the write side accepts what the read side accepts, and what is
+ * unspecified there stays unspecified here); MMP_MRW_HOST when the value is well-formed but the device cannot name what it must
+ * render — an entry whose pod is outside [0, pod slots) (an unresolved id: its bytes are gone), or an id among the rendered entries
+ * that holds a byte needing JSON escaping ('"', '\', below 0x20, above 0x7e).  Both give length 0; the host renders the latter.
+ *
+ * Output: new value i = out_buf[out_off[i], out_off[i+1]), out_off has n + 1 words; *n_bytes_out = the bytes of all rendered
+ * values.  out_off, status_out and *n_bytes_out are always complete; NO byte of out_buf is written when out_buf is NULL or out_cap
+ * is smaller than the total, and the call still returns MMP_OK: the caller repeats it with a larger buffer.  The device makes a
+ * size pass, scans the sizes, the host reads the total back once, and a write pass follows if there is room.
+ * Read-only: no commit, locking as mmp_models_status without a fail_pod.  flags must be 0.  last_unload may be NULL; fail_pod,
+ * fail_msg, fail_msg_off may be NULL all three.  n == 0 is valid.  MMP_EINVAL with nothing written: a NULL required buffer,
+ * non-monotone offsets of either kind, a row outside [0, models), a fail_pod outside [-1, pod slots), fail_pod without the two
+ * message arrays, flags != 0.  MMP_ESTATE before mmp_pod_ids_load and when the id store and the instance table no longer cover
+ * the same indices (the check of mmp_pods_events_json).  Two runs over the same state are byte-identical. */
+#define MMP_MRW_OK 0        /* rendered */
+#define MMP_MRW_MALFORMED 1 /* the old value is malformed: length 0 in the output */
+#define MMP_MRW_HOST 2      /* well-formed, but the device cannot render it: length 0, the host renders this one */
+int mmp_models_rewrite_json(mmp_ctx *ctx, const int32_t *rows, int32_t n, const char *old_buf, const int64_t *old_off,
+                            const int64_t *last_unload, const int32_t *fail_pod, const char *fail_msg, const int32_t *fail_msg_off,
+                            uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off, int32_t *status_out,
+                            int64_t *n_bytes_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -203,6 +203,16 @@ final class MmPlace {
     static native int modelsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
                                        ByteBuffer deleted, int flags, ByteBuffer modelIdxOut, ByteBuffer lastUnloadOut,
                                        ByteBuffer statusOut, ByteBuffer nAppendedOut);
+    /** the write side of the wire format (mmp_models_rewrite_json), for the 13 conditionalSet / conditionalSetAndGet sites of
+     *  ModelMesh.java: value i = the stored bytes oldJson[oldOff[i], oldOff[i+1]) of registry row rows[i]; the answer is the value to
+     *  store next — what the device does not own copied byte for byte, instanceIds / failedIn / fails / lu (and lul from lastUnload,
+     *  may be null) rendered from the resident row; failPod / failMsg / failMsgOff (all three may be null) are addLoadFailure /
+     *  removeLoadFailure of one instance per value.  New value i = outBuf[outOff[i], outOff[i+1]); statusOut 0 rendered / 1 the
+     *  old value is malformed / 2 the host renders this one (an unresolved or unprintable id); nBytesOut (one long) = the bytes of
+     *  all values.  Nothing is written to outBuf when it is null or outCap is smaller than that: call again with room.  flags 0. */
+    static native int modelsRewriteJson(long h, ByteBuffer rows, int n, ByteBuffer oldJson, ByteBuffer oldOff, ByteBuffer lastUnload,
+                                        ByteBuffer failPod, ByteBuffer failMsg, ByteBuffer failMsgOff, int flags, ByteBuffer outBuf,
+                                        long outCap, ByteBuffer outOff, ByteBuffer statusOut, ByteBuffer nBytesOut);
     /** hand registry rows back (mmp_models_retire): rows = n ints, the rows whose deletion the listener has seen; flags 1 = every
      *  named row must still be the empty row a deletion leaves (else MMP_EINVAL, nothing changed: the id was registered again).
      *  The survivors move down in order; remapOut (maxModels >= the row count at the call, may be null) gives old row -> new row,

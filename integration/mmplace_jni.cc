@@ -732,6 +732,34 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsEventsJson(JN
                                         buf<int32_t>(env, nAppendedOut)));
 }
 
+// the write side of the wire format: the stored value of each edited record and the record as the device holds it give the value
+// to store next (see mmp_models_rewrite_json).  The capacities are checked here; outCap is what outBuf holds (0 with null: sizes).
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRewriteJson(JNIEnv *env, jclass, jlong h, jobject rows, jint n,
+                                                                               jobject oldJson, jobject oldOff, jobject lastUnload,
+                                                                               jobject failPod, jobject failMsg, jobject failMsgOff,
+                                                                               jint flags, jobject outBuf, jlong outCap, jobject outOff,
+                                                                               jobject statusOut, jobject nBytesOut)
+{
+    if (n < 0 || outCap < 0 || !holds<int32_t>(env, rows, n, "modelsRewriteJson: rows shorter than n") ||
+        !holds<int64_t>(env, oldOff, (jlong)n + 1, "modelsRewriteJson: oldOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, oldJson, buf<int64_t>(env, oldOff)[n], "modelsRewriteJson: oldJson shorter than oldOff[n]")) ||
+        (lastUnload && !holds<int64_t>(env, lastUnload, n, "modelsRewriteJson: lastUnload shorter than n")) ||
+        (failPod && !holds<int32_t>(env, failPod, n, "modelsRewriteJson: failPod shorter than n")) ||
+        (failMsgOff && !holds<int32_t>(env, failMsgOff, (jlong)n + 1, "modelsRewriteJson: failMsgOff shorter than n + 1")) ||
+        (failMsg && failMsgOff && n > 0 &&
+         !holds<char>(env, failMsg, buf<int32_t>(env, failMsgOff)[n], "modelsRewriteJson: failMsg shorter than failMsgOff[n]")) ||
+        (outBuf && !holds<char>(env, outBuf, outCap, "modelsRewriteJson: outBuf shorter than outCap")) ||
+        !holds<int64_t>(env, outOff, (jlong)n + 1, "modelsRewriteJson: outOff shorter than n + 1") ||
+        !holds<int32_t>(env, statusOut, n, "modelsRewriteJson: statusOut shorter than n") ||
+        !holds<int64_t>(env, nBytesOut, 1, "modelsRewriteJson: nBytesOut shorter than one long"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_rewrite_json(ctx_of(h), buf<int32_t>(env, rows), n, buf<char>(env, oldJson), buf<int64_t>(env, oldOff),
+                                         buf<int64_t>(env, lastUnload), buf<int32_t>(env, failPod), buf<char>(env, failMsg),
+                                         buf<int32_t>(env, failMsgOff), static_cast<uint32_t>(flags), buf<char>(env, outBuf), outCap,
+                                         buf<int64_t>(env, outOff), buf<int32_t>(env, statusOut), buf<int64_t>(env, nBytesOut)));
+}
+
 // rows: n ints; remapOut (may be null) holds maxModels ints, nModelsAfterOut (may be null) one (see mmp_models_retire)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRetire(JNIEnv *env, jclass, jlong h, jobject rows, jint n, jint flags,
                                                                           jobject remapOut, jint maxModels, jobject nModelsAfterOut)

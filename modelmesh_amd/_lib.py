@@ -173,6 +173,8 @@ PEV_APPLIED, PEV_MALFORMED, PEV_UNKNOWN = 0, 1, 2  # status_out
 
 # mmp_models_events_json (registry events by key, the registry listener MM.java:628): the status values are those above
 MEV_APPEND = 1
+# mmp_models_rewrite_json (the write side of the wire format): status_out
+MRW_OK, MRW_MALFORMED, MRW_HOST = 0, 1, 2
 # mmp_models_retire: every named row must be the empty row a deletion leaves
 RETIRE_EMPTY_ONLY = 1
 # mmp_pods_retire: every named row must be a tombstone / no referenced registry entry may name a retired instance
@@ -311,6 +313,8 @@ SYMBOLS = [
     ("mmp_models_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_models_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_pods_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    ("mmp_models_rewrite_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_int64, _P, _P,
+                                          C.POINTER(C.c_int64)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -44,6 +44,7 @@
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
 #include "pods_retire_kernels.hpp"
+#include "rewrite_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -508,6 +509,12 @@ struct mmp_ctx {
     // mmp_models_status (status_kernels.hpp): the call's copy list on the device.  Owned by batch_mu, used on c->stream; its other
     // scratch is the registry plans' (plan).
     DevBuf st_copies;
+    // mmp_models_rewrite_json (rewrite_kernels.hpp).  idd_bytes / idd_off: the device copy of the instance id store (id_bytes /
+    // id_offs), uploaded lazily: every writer of the host store bumps id_gen, the call uploads when idd_gen differs.  rw_*: one
+    // call's rows, last_unload, fail_pod, messages and their offsets, sizes, offsets, statuses and rendered bytes.  Owned by
+    // batch_mu, used on c->stream; the parser's scratch is the j_* of the registry event calls.
+    DevBuf idd_bytes, idd_off, rw_rows, rw_lul, rw_fpod, rw_fmsg, rw_fmoff, rw_len, rw_off, rw_status, rw_out;
+    uint64_t id_gen = 1, idd_gen = 0;
 };
 
 namespace {
@@ -1381,7 +1388,8 @@ void mmp_destroy(mmp_ctx *c)
                       &c->s_c, &c->s_d, &c->r_ps, &c->r_counts, &c->r_keys, &c->r_vals, &c->r_keys2, &c->r_vals2,
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
-                      &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod,
+                      &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
+                      &c->rw_off, &c->rw_status, &c->rw_out,
                       &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
@@ -3013,6 +3021,7 @@ try {
     if (rc != MMP_OK) return rc;
     // the ids, their order and the interning stay with the context: mmp_pod_ids_append continues all three
     c->id_bytes.assign(n_pods ? ids + id_off[0] : "", n_pods ? (size_t)(id_off[n_pods] - id_off[0]) : 0);
+    c->id_gen++;
     c->id_offs.resize((size_t)n_pods + 1);
     for (int32_t i = 0; i <= n_pods; i++) c->id_offs[i] = id_off[i] - id_off[0];
     c->id_sorted.resize(n_pods);
@@ -3239,6 +3248,7 @@ int pod_ids_append_locked(mmp_ctx *c, const char *fn, const char *ids, const int
     c->idtab_mask = nt.mask;
     const int32_t base = c->id_offs[P];
     c->id_bytes.append(ids + id_off[0], (size_t)rel[n_new]);
+    c->id_gen++;
     for (int32_t i = 1; i <= n_new; i++) c->id_offs.push_back(base + rel[i]);
     std::vector<int32_t> fresh(n_new), merged((size_t)P + n_new);
     for (int32_t i = 0; i < n_new; i++) fresh[i] = P + i;
@@ -4224,6 +4234,7 @@ try {
             }
             if (ids) {
                 c->id_bytes.swap(H.id_bytes);
+                c->id_gen++;
                 c->id_offs.swap(H.id_offs);
                 c->id_sorted.swap(H.id_sorted);
                 c->id_order_v.swap(H.id_order_v);
@@ -6419,6 +6430,125 @@ try {
     *n_copies_out = total;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_models_status")
+
+int mmp_models_rewrite_json(mmp_ctx *c, const int32_t *rows, int32_t n, const char *old_buf, const int64_t *old_off,
+                            const int64_t *last_unload, const int32_t *fail_pod, const char *fail_msg, const int32_t *fail_msg_off,
+                            uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off, int32_t *status_out, int64_t *n_bytes_out)
+try {
+    if (!c || n < 0 || flags || out_cap < 0 || !out_off || !n_bytes_out || (n > 0 && (!rows || !old_off || !status_out)) ||
+        (fail_pod && (!fail_msg || !fail_msg_off)))
+        return fail(c, MMP_EINVAL, "mmp_models_rewrite_json: bad argument");
+    // read-only: the locking of mmp_models_status without a fail_pod (batch_mu owns the stream, the scratch, the registry's
+    // writers and the id store's)
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_models_rewrite_json: load the instance ids first (mmp_pod_ids_load)");
+    if (const int rc = id_space_guard(c, "mmp_models_rewrite_json")) return rc;
+    const int32_t M = c->n_models, P = (int32_t)c->pods.size();
+    if (const int rc = check_offsets(c, "mmp_models_rewrite_json", "", old_off, n)) return rc;
+    if (fail_pod)
+        if (const int rc = check_offsets(c, "mmp_models_rewrite_json", "message ", fail_msg_off, n)) return rc;
+    for (int32_t i = 0; i < n; i++) {
+        if (rows[i] < 0 || rows[i] >= M) return fail(c, MMP_EINVAL, "mmp_models_rewrite_json: value %d names model %d of %d", i, rows[i], M);
+        if (fail_pod && (fail_pod[i] < -1 || fail_pod[i] >= P))
+            return fail(c, MMP_EINVAL, "mmp_models_rewrite_json: value %d names pod %d of %d", i, fail_pod[i], P);
+    }
+    if (n > 0 && old_off[n] > old_off[0] && !old_buf) return fail(c, MMP_EINVAL, "mmp_models_rewrite_json: bad argument");
+    if (n == 0) {
+        out_off[0] = 0;
+        *n_bytes_out = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // the old values where the parser reads them, and its verdict on each as a non-deleted event (rows and entries into scratch)
+    std::vector<int64_t> rel;
+    if (const int rc = stage_strings(c, "mmp_models_rewrite_json", "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
+    IngestModelsArgs J;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+    J.rows = c->j_rows.as<mmp_model_row>();
+    // the call's own inputs
+    std::vector<int32_t> mrel;
+    HIP_TRY(c, c->rw_rows.ensure((size_t)n * 4));
+    HIP_TRY(c, hipMemcpyAsync(c->rw_rows.p, rows, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (last_unload) {
+        HIP_TRY(c, c->rw_lul.ensure((size_t)n * 8));
+        HIP_TRY(c, hipMemcpyAsync(c->rw_lul.p, last_unload, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    }
+    if (fail_pod) {
+        HIP_TRY(c, c->rw_fpod.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->rw_fpod.p, fail_pod, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        if (const int rc = stage_strings(c, "mmp_models_rewrite_json", "message ", fail_msg, fail_msg_off, n, c->rw_fmsg, c->rw_fmoff, mrel))
+            return rc;
+    }
+    if (c->idd_gen != c->id_gen) {  // the id store moved since the last call: its device copy follows
+        HIP_TRY(c, c->idd_bytes.ensure(c->id_bytes.size() + 16));
+        HIP_TRY(c, c->idd_off.ensure(c->id_offs.size() * 4));
+        if (!c->id_bytes.empty())
+            HIP_TRY(c, hipMemcpyAsync(c->idd_bytes.p, c->id_bytes.data(), c->id_bytes.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->idd_off.p, c->id_offs.data(), c->id_offs.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipStreamSynchronize(st));  // (the host store may change once batch_mu is released)
+        c->idd_gen = c->id_gen;
+    }
+    HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->rw_status.ensure((size_t)n * 4));
+    int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
+    RewriteArgs A{};
+    A.buf = J.buf;
+    A.off = J.off;
+    A.n = n;
+    A.rows = c->rw_rows.as<int32_t>();
+    A.pstatus = J.status;
+    A.models = c->models.as<mmp_model_row>();
+    A.ent_pod = c->ent_pod.as<int32_t>();
+    A.ent_time = c->ent_time.as<int64_t>();
+    A.id_bytes = c->idd_bytes.as<char>();
+    A.id_off = c->idd_off.as<int32_t>();
+    A.n_pods = P;
+    A.last_unload = last_unload ? c->rw_lul.as<int64_t>() : nullptr;
+    A.fail_pod = fail_pod ? c->rw_fpod.as<int32_t>() : nullptr;
+    A.fail_msg = fail_pod ? c->rw_fmsg.as<char>() : nullptr;
+    A.fail_msg_off = fail_pod ? c->rw_fmoff.as<int32_t>() : nullptr;
+    A.len = d_len;
+    A.out_off = d_off;
+    A.status = c->rw_status.as<int32_t>();
+    // the size pass, the scan of the sizes, and the one read-back that decides whether anything is written
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
+    hipLaunchKernelGGL(models_rewrite_kernel<false>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int64_t> h_off((size_t)n + 1);
+    std::vector<int32_t> h_status(n);
+    HIP_TRY(c, hipMemcpyAsync(h_off.data(), d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h_status.data(), c->rw_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const double size_ms = c->last_kernel_ms;
+    const int64_t total = h_off[n];
+    if (out_buf && out_cap >= total && total > 0) {
+        HIP_TRY(c, c->rw_out.ensure((size_t)total));
+        A.out = c->rw_out.as<char>();
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(models_rewrite_kernel<true>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, copy_sync(c, out_buf, c->rw_out.p, (size_t)total, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        kt_add(c, size_ms);  // the call's device span: size + write
+    }
+    memcpy(out_off, h_off.data(), (size_t)(n + 1) * 8);
+    memcpy(status_out, h_status.data(), (size_t)n * 4);
+    *n_bytes_out = total;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_models_rewrite_json")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

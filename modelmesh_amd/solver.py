@@ -310,6 +310,50 @@ class Solver:
             self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
         return status[:n], lul[:n]
 
+    def models_rewrite_json(self, rows, old_values, last_unload=None, fail=None):
+        """The write side of the wire format (mmp_models_rewrite_json): old_values[i] (bytes/str) is the stored value of registry
+        row rows[i]; the answer is the value to store next — what the device does not own copied byte for byte, instanceIds /
+        failedIn / fails / lu (and lul from last_unload[i], when given) rendered from the resident row.  fail = (fail_pod,
+        messages): addLoadFailure / removeLoadFailure of instance fail_pod[i] (-1: none) with messages[i] (bytes/str, empty:
+        remove).  Returns (values, status): values[i] is bytes, or None where status[i] is MRW_MALFORMED / MRW_HOST.  Two calls:
+        the sizes, then the bytes."""
+        total = self.models_rewrite_json_raw(rows, old_values, last_unload, fail, 0)[3]
+        out, off, status, total2, rc = self.models_rewrite_json_raw(rows, old_values, last_unload, fail, total)
+        self._ck(rc)
+        assert total2 == total  # (read-only over a registry nobody edited in between)
+        vals = [bytes(out[off[i]:off[i + 1]]) if status[i] == 0 else None for i in range(len(status))]
+        return vals, status
+
+    def models_rewrite_json_raw(self, rows, old_values, last_unload, fail, out_cap, fill=0, null_out=False, flags=0, old_off=None,
+                                msg_off=None, no_msgs=False):
+        """One mmp_models_rewrite_json call with exactly this capacity (null_out: a NULL out_buf), the outputs filled with the
+        byte `fill` first: (out bytes as uint8[out_cap], out_off[n + 1], status[n], total, rc).  Raises on rc only through the
+        caller: rc is returned (total is -1 where the library did not set it).  old_off / msg_off: these offsets instead of the packed
+        ones; no_msgs: fail_pod without the two message arrays."""
+        blob, off = self._pack(old_values)
+        n = len(old_values)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        lul = None if last_unload is None else np.ascontiguousarray(last_unload, dtype=np.int64)
+        fpod = fmsg = fmoff = None
+        if fail is not None:
+            fpod = np.ascontiguousarray(fail[0], dtype=np.int32)
+            fmsg, fmoff64 = self._pack(fail[1])
+            fmoff = fmoff64.astype(np.int32) if msg_off is None else np.ascontiguousarray(msg_off, dtype=np.int32)
+            if no_msgs:
+                fmsg = fmoff = None
+        if old_off is not None:
+            off = np.ascontiguousarray(old_off, dtype=np.int64)
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        out_off = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        for a in (out, out_off, status):
+            a.view(np.uint8)[:] = fill
+        total = C.c_int64(-1)
+        rc = self.lib.mmp_models_rewrite_json(self.h, ptr(rows), n, blob, ptr(off), ptr(lul), ptr(fpod), fmsg, ptr(fmoff), flags,
+                                              None if null_out else ptr(out), int(out_cap), ptr(out_off), ptr(status),
+                                              C.byref(total))
+        return out[:int(out_cap)], out_off, status[:n], total.value, rc
+
     def model_ids_load(self, ids):
         """Name the registry's rows (mmp_model_ids_load): ids[i] (bytes/str) is the id of row i; len(ids) must equal the row count."""
         blob, off = self._pack(ids)
