@@ -639,6 +639,73 @@ int mmp_route_batch(mmp_ctx *ctx, const mmp_gate_req *gate_reqs, const mmp_serve
                     int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now_ms,
                     int64_t in_use_failure_expiry_ms, mmp_gate_out *gate_outs, mmp_serve_out *serve_outs);
 
+/* The single-caller forms of the two routes.  About two thirds of a mmp_gate_req + mmp_serve_req (or + mmp_place_req) describe the
+ * CALLING INSTANCE, not the request — self, the local cache's capacity / weighted size / oldest time, loadingCount and its cutoff,
+ * loadTimeoutMs, getFreshInstanceRecord(), lastPublished, localInvokesInFlight, lastInvokeTime — and a batch is what ONE instance's
+ * request threads hand over together.  That side travels once per call (mmp_seam_caller, 112 bytes); a route request is 48 + 24
+ * bytes instead of 144 + 48, a miss request 48 + 24 instead of 144 + 64.
+ *
+ * THE RULE: request i of a call is decided exactly as the existing call decides these rows —
+ *   gate row   {model = g.model, caller.self_pod, flags = caller.gate_flags | g.flags, g.excl_off, g.n_excl, g.explicit_off,
+ *               g.n_explicit, g.size_hint, g.last_used_time, caller.cache_capacity, caller.cache_weighted_size,
+ *               caller.cache_oldest_time, g.loader_predicted, caller.loading_count, caller.weight_predict_cutoff, reserved = 0,
+ *               g.loaded_time, caller.load_timeout_ms, caller.fresh_*, caller.last_published}
+ *   serve row  {g.model, caller.self_pod, s.flags, caller.local_in_flight, caller.last_invoke_time, s.assume_completed_ms,
+ *               g.excl_off, g.n_excl, s.cnt_off, s.n_cnt}     (the serve half reads the GATE row's exclusion range: the two
+ *               selections share one MapFilteringSet, MM.java:3634, :4316)
+ *   place row  as mmp_place_batch_c defines it from place_caller and place_reqs[i]
+ * (g = gate_reqs[i], s = serve_reqs[i]), and the results are those rows' results, byte for byte.  Validation is that of the
+ * expanded rows: the MMP_EINVAL cases of mmp_route_batch / mmp_miss_batch (null arguments, negative counts, ranges outside the
+ * pools, gate_reqs[i].model != place_reqs[i].model), a NULL caller or place_caller as well, all with the outputs untouched;
+ * MMP_ESTATE as for the existing calls; n = 0 is a valid call.  `caller` / `place_caller` are host memory (they ride in the
+ * kernels' arguments).  Calls within the existing calls' latency-slot sizes (256 requests, their pool limits) are written out as
+ * full rows and take that path; larger ones stage the compact rows as they are and run kernels of their own on them
+ * (csrc/seam_caller_kernels.hpp). */
+typedef struct {                 /* the calling instance's side of a batch of route / miss requests — 112 bytes */
+    int32_t  self_pod;
+    uint32_t gate_flags;         /* MMP_GATE_* bits ORed into every request's flags */
+    int32_t  loading_count;
+    int32_t  weight_predict_cutoff;
+    int64_t  cache_capacity, cache_weighted_size, cache_oldest_time;
+    int64_t  load_timeout_ms;
+    int64_t  fresh_lru, fresh_capacity, fresh_used;
+    int32_t  fresh_count, fresh_loading_threads, fresh_in_progress, fresh_rpm;
+    int64_t  last_published;
+    int32_t  local_in_flight;    /* serve half: localInvokesInFlight (MM.java:4303) */
+    int32_t  reserved;
+    int64_t  last_invoke_time;   /* serve half: lastInvokeTime (MM.java:4304) */
+} mmp_seam_caller;
+
+typedef struct {                 /* the request's own side of mmp_gate_req — 48 bytes */
+    int32_t  model;
+    uint32_t flags;              /* MMP_GATE_*; the request's flags are caller.gate_flags | flags */
+    int32_t  excl_off, n_excl;
+    int32_t  explicit_off, n_explicit;
+    int32_t  size_hint;
+    int32_t  loader_predicted;
+    int64_t  last_used_time;
+    int64_t  loaded_time;
+} mmp_gate_req_c;
+
+typedef struct {                 /* the request's own side of mmp_serve_req — 24 bytes */
+    uint32_t flags;              /* MMP_SERVE_* */
+    int32_t  cnt_off, n_cnt;
+    int32_t  reserved;
+    int64_t  assume_completed_ms;
+} mmp_serve_req_c;
+
+int mmp_route_batch_c(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_gate_req_c *gate_reqs,
+                      const mmp_serve_req_c *serve_reqs, int32_t n, const mmp_serve_counter *counters, int32_t n_counters,
+                      const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool,
+                      int32_t n_explicit, int64_t now_ms, int64_t in_use_expiry_ms, mmp_gate_out *gate_outs,
+                      mmp_serve_out *serve_outs);
+
+int mmp_miss_batch_c(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_place_caller *place_caller,
+                     const mmp_gate_req_c *gate_reqs, const mmp_place_req_c *place_reqs, int32_t n,
+                     const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool,
+                     int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now_ms,
+                     int64_t in_use_expiry_ms, mmp_gate_out *gate_outs, mmp_place_out *place_outs);
+
 /* triggerProactiveLoadsForInstanceSubset (MM.java:6616-6747, excludeTypes == null) over the
  * committed snapshot and the loaded model table (models in registry iteration order): which
  * unloaded models the leader would proactively load, most recently used first. The caller then

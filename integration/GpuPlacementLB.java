@@ -89,6 +89,18 @@ final class MmPlace {
     static native int routeBatch(long h, ByteBuffer gateReqs, ByteBuffer serveReqs, int n, ByteBuffer counters, int nCounters,
                                  ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool, int nExplicit,
                                  long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts, ByteBuffer serveOuts);
+    /** the single-caller forms of the two routes: caller = one mmp_seam_caller (112 bytes: this instance's index, the flags every
+     *  request of the batch shares, loadingCount and its cutoff, runtimeCache capacity / weightedSize / oldestTime, loadTimeoutMs,
+     *  getFreshInstanceRecord(), lastPublished, localInvokesInFlight, lastInvokeTime), filled ONCE per batch; gateReqs = n
+     *  mmp_gate_req_c rows of 48 bytes, serveReqs = n mmp_serve_req_c rows of 24 bytes, placeReqs = n mmp_place_req_c rows.  A batch
+     *  is what one instance's request threads hand over together. */
+    static native int routeBatchCaller(long h, ByteBuffer caller, ByteBuffer gateReqs, ByteBuffer serveReqs, int n, ByteBuffer counters,
+                                       int nCounters, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool,
+                                       int nExplicit, long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts, ByteBuffer serveOuts);
+    static native int missBatchCaller(long h, ByteBuffer caller, ByteBuffer placeCaller, ByteBuffer gateReqs, ByteBuffer placeReqs, int n,
+                                      ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool, int nExplicit,
+                                      ByteBuffer extraPool, int nExtra, long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts,
+                                      ByteBuffer placeOuts);
     static native int proactivePlan(long h, int defaultModelSizeUnits, long nowMs, int maxOut, ByteBuffer outModel,
                                     ByteBuffer outLastUsed, ByteBuffer info);
     static native int proactivePlanSubset(long h, int partition, ByteBuffer skipModels, int nSkip, int defaultModelSizeUnits,

@@ -315,6 +315,49 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_routeBatch(JNIEnv *
                                  buf<int64_t>(env, exclTime), nExcl, buf<int32_t>(env, explicitPool), nExplicit, nowMs,
                                  inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_serve_out>(env, serveOuts)));
 }
+// ---- the single-caller forms of the two routes: the calling instance's side (mmp_seam_caller, 112 bytes) once per batch, 48-byte
+// gate rows and 24-byte serve / load-target rows (include/mmplace.h: mmp_route_batch_c, mmp_miss_batch_c)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_routeBatchCaller(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                              jobject gateReqs, jobject serveReqs, jint n,
+                                                                              jobject counters, jint nCounters, jobject exclPod,
+                                                                              jobject exclTime, jint nExcl, jobject explicitPool,
+                                                                              jint nExplicit, jlong nowMs, jlong inUseFailureExpiryMs,
+                                                                              jobject gateOuts, jobject serveOuts)
+{
+    if (!holds<mmp_seam_caller>(env, caller, 1, "routeBatchCaller: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "routeBatchCaller: gateReqs shorter than n requests") ||
+        !holds<mmp_serve_req_c>(env, serveReqs, n, "routeBatchCaller: serveReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "routeBatchCaller: gateOuts shorter than n results") ||
+        !holds<mmp_serve_out>(env, serveOuts, n, "routeBatchCaller: serveOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_route_batch_c(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_gate_req_c>(env, gateReqs),
+                                   buf<mmp_serve_req_c>(env, serveReqs), n, buf<mmp_serve_counter>(env, counters), nCounters,
+                                   buf<int32_t>(env, exclPod), buf<int64_t>(env, exclTime), nExcl, buf<int32_t>(env, explicitPool),
+                                   nExplicit, nowMs, inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts),
+                                   buf<mmp_serve_out>(env, serveOuts)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_missBatchCaller(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                             jobject placeCaller, jobject gateReqs, jobject placeReqs,
+                                                                             jint n, jobject exclPod, jobject exclTime, jint nExcl,
+                                                                             jobject explicitPool, jint nExplicit, jobject extraPool,
+                                                                             jint nExtra, jlong nowMs, jlong inUseFailureExpiryMs,
+                                                                             jobject gateOuts, jobject placeOuts)
+{
+    if (!holds<mmp_seam_caller>(env, caller, 1, "missBatchCaller: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_place_caller>(env, placeCaller, 1, "missBatchCaller: placeCaller shorter than one mmp_place_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "missBatchCaller: gateReqs shorter than n requests") ||
+        !holds<mmp_place_req_c>(env, placeReqs, n, "missBatchCaller: placeReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "missBatchCaller: gateOuts shorter than n results") ||
+        !holds<mmp_place_out>(env, placeOuts, n, "missBatchCaller: placeOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_miss_batch_c(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_place_caller>(env, placeCaller),
+                                  buf<mmp_gate_req_c>(env, gateReqs), buf<mmp_place_req_c>(env, placeReqs), n,
+                                  buf<int32_t>(env, exclPod), buf<int64_t>(env, exclTime), nExcl, buf<int32_t>(env, explicitPool),
+                                  nExplicit, buf<int32_t>(env, extraPool), nExtra, nowMs, inUseFailureExpiryMs,
+                                  buf<mmp_gate_out>(env, gateOuts), buf<mmp_place_out>(env, placeOuts)));
+}
 
 // ---- rebalancers (MM.java:5636-5871, 6110-6335, 6616-6747, 6959-7147) ---------------------------------
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_proactivePlan(JNIEnv *env, jclass, jlong h,

@@ -90,6 +90,19 @@ GATE_REQ = np.dtype(
      ("fresh_rpm", "<i4"), ("last_published", "<i8")])
 GATE_OUT = np.dtype([("bits", "<u4"), ("initial_size", "<i4")])
 assert GATE_REQ.itemsize == 144 and GATE_OUT.itemsize == 8
+# the single-caller forms of the route and miss seams (mmp_route_batch_c / mmp_miss_batch_c): the calling instance's side once per
+# call, 48 + 24 bytes per route request instead of 144 + 48
+SEAM_CALLER = np.dtype(
+    [("self_pod", "<i4"), ("gate_flags", "<u4"), ("loading_count", "<i4"), ("weight_predict_cutoff", "<i4"),
+     ("cache_capacity", "<i8"), ("cache_weighted_size", "<i8"), ("cache_oldest_time", "<i8"), ("load_timeout_ms", "<i8"),
+     ("fresh_lru", "<i8"), ("fresh_capacity", "<i8"), ("fresh_used", "<i8"), ("fresh_count", "<i4"),
+     ("fresh_loading_threads", "<i4"), ("fresh_in_progress", "<i4"), ("fresh_rpm", "<i4"), ("last_published", "<i8"),
+     ("local_in_flight", "<i4"), ("reserved", "<i4"), ("last_invoke_time", "<i8")])
+GATE_REQ_C = np.dtype(
+    [("model", "<i4"), ("flags", "<u4"), ("excl_off", "<i4"), ("n_excl", "<i4"), ("explicit_off", "<i4"), ("n_explicit", "<i4"),
+     ("size_hint", "<i4"), ("loader_predicted", "<i4"), ("last_used_time", "<i8"), ("loaded_time", "<i8")])
+SERVE_REQ_C = np.dtype([("flags", "<u4"), ("cnt_off", "<i4"), ("n_cnt", "<i4"), ("reserved", "<i4"), ("assume_completed_ms", "<i8")])
+assert SEAM_CALLER.itemsize == 112 and GATE_REQ_C.itemsize == 48 and SERVE_REQ_C.itemsize == 24
 GATE_GO_LOCAL, GATE_FAILURES_BREACHED, GATE_LOCATIONS_BREACHED, GATE_LOCAL_NOT_ALLOWED = 1, 2, 4, 8
 GATE_CHURN_REJECT, GATE_EARLY_REJECT, GATE_RELOAD_ELSEWHERE, GATE_SHOULD_PUBLISH = 16, 32, 64, 128
 
@@ -281,6 +294,10 @@ SYMBOLS = [
     ("mmp_gate_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),
     ("mmp_miss_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     ("mmp_route_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    ("mmp_route_batch_c", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64,
+                                    _P, _P]),
+    ("mmp_miss_batch_c", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64,
+                                   C.c_int64, _P, _P]),
     ("mmp_proactive_plan", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     ("mmp_proactive_plan_subset", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     ("mmp_registry_prune", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int32, _P, C.c_int32, _P]),

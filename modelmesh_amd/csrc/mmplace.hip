@@ -33,6 +33,7 @@
 #include "aux_kernels.hpp"
 #include "cache_kernels.hpp"
 #include "gate_kernel.hpp"
+#include "seam_caller_kernels.hpp"
 #include "ingest_kernels.hpp"
 #include "place_kernel.hpp"
 #include "rebalance_kernels.hpp"
@@ -1039,8 +1040,8 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     return MMP_OK;
 }
 
-// ---- the request seam: what the seven host-pointer request calls share (mmp_place_batch, _place_batch_c, _serve_batch, _gate_batch,
-// _miss_batch, _route_batch, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
+// ---- the request seam: what the nine host-pointer request calls share (mmp_place_batch, _place_batch_c, _serve_batch, _gate_batch,
+// _miss_batch, _miss_batch_c, _route_batch, _route_batch_c, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
 
 // [off, off + n) lies inside a pool of `len` entries (int64: off + n may pass INT32_MAX)
 inline bool in_pool(int32_t off, int32_t n, int32_t len) { return off >= 0 && n >= 0 && (int64_t)off + n <= len; }
@@ -1055,7 +1056,8 @@ inline int check_place_req(mmp_ctx *c, const char *call, int32_t i, const Req &r
 {
     return in_pool(r.extra_off, r.n_extra, n_extra) ? MMP_OK : bad_range(c, call, i, "extra", r.extra_off, r.n_extra, n_extra);
 }
-inline int check_gate_req(mmp_ctx *c, const char *call, int32_t i, const mmp_gate_req &r, int32_t n_excl, int32_t n_explicit)
+template <class Req>  // mmp_gate_req, mmp_gate_req_c
+inline int check_gate_req(mmp_ctx *c, const char *call, int32_t i, const Req &r, int32_t n_excl, int32_t n_explicit)
 {
     if (!in_pool(r.excl_off, r.n_excl, n_excl)) return bad_range(c, call, i, "exclude", r.excl_off, r.n_excl, n_excl);
     if (!in_pool(r.explicit_off, r.n_explicit, n_explicit)) return bad_range(c, call, i, "explicit", r.explicit_off, r.n_explicit, n_explicit);
@@ -5715,6 +5717,149 @@ try {
                         return MMP_OK;
                     });
 } MMP_CATCH(c, "mmp_route_batch")
+
+// ---- the single-caller forms of the two routes (include/mmplace.h: THE RULE; kernels: seam_caller_kernels.hpp) ----------------
+namespace {
+// (the gate and serve rows of the header's rule: expand_gate / expand_serve, seam_caller_kernels.hpp — one statement for host and device)
+mmp_place_req full_place_row(const mmp_place_caller &c, const mmp_place_req_c &q)
+{
+    mmp_place_req r;
+    r.model = q.model;
+    r.self_pod = c.self_pod;
+    r.flags = c.flags;
+    r.pick = q.pick;
+    r.last_used = q.last_used;
+    r.extra_off = q.extra_off;
+    r.n_extra = q.n_extra;
+    r.fresh_lru = c.fresh_lru;
+    r.fresh_capacity = c.fresh_capacity;
+    r.fresh_used = c.fresh_used;
+    r.fresh_count = c.fresh_count;
+    r.fresh_rpm = c.fresh_rpm;
+    return r;
+}
+SeamCArgs seam_c_args(const mmp_seam_caller &caller, const SeamIo &gq, const SeamIo *sq, int32_t n)
+{
+    SeamCArgs R;
+    R.greqs = gq.as<mmp_gate_req_c>();
+    R.sreqs = sq ? sq->as<mmp_serve_req_c>() : nullptr;
+    R.n = n;
+    R.caller = caller;
+    return R;
+}
+}  // namespace
+
+int mmp_route_batch_c(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
+                      const mmp_serve_counter *counters, int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time,
+                      int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
+                      mmp_gate_out *gouts, mmp_serve_out *souts)
+try {
+    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
+        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
+        return fail(c, MMP_EINVAL, "mmp_route_batch_c: bad argument");
+    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges: the serve row's exclusion range IS the gate row's
+        if (const int rc = check_gate_req(c, "mmp_route_batch_c", i, greqs[i], n_excl, n_explicit)) return rc;
+        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
+            return bad_range(c, "mmp_route_batch_c", i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
+    }
+    using L = RouteSlot;
+    if (n <= L::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit) {
+        // within the latency slots' sizes (and n = 0): mmp_route_batch — its slots, its n = 1 kernel — on the rows written out
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_serve_req> fs((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
+        }
+        return mmp_route_batch(c, n ? fg.data() : nullptr, n ? fs.data() : nullptr, n, counters, n_counters, excl_pod, excl_time, n_excl,
+                               explicit_pool, n_explicit, now, in_use_expiry, gouts, souts);
+    }
+    // (the scratch mmp_route_batch stages through: the two calls never overlap, batch_mu owns it for a call)
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs),
+           cnt = seam_io(counters, n_counters, kStagedOnly, c->rt_cnt), xp = seam_io(excl_pod, n_excl, kStagedOnly, c->s_c),
+           xt = seam_io(excl_time, n_excl, kStagedOnly, c->s_d), ex = seam_io(explicit_pool, n_explicit, kStagedOnly, c->s_a),
+           go = seam_io(gouts, n, kStagedOnly, c->s_outs), so = seam_io(souts, n, kStagedOnly, c->rt_souts);
+    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex}, {&go, &so}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        GateArgs G = gate_args(c, n, now, in_use_expiry);
+                        G.excl_pod = xp.as<int32_t>();
+                        G.excl_time = xt.as<int64_t>();
+                        G.explicit_pool = ex.as<int32_t>();
+                        G.outs = go.as<mmp_gate_out>();
+                        G.done = done;
+                        ServeArgs S = serve_args(c, n, now);
+                        S.counters = cnt.as<mmp_serve_counter>();
+                        S.excl_pod = G.excl_pod;
+                        S.excl_time = G.excl_time;
+                        S.outs = so.as<mmp_serve_out>();
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
+                                           seam_c_args(*caller, gq, &sq, n));
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
+} MMP_CATCH(c, "mmp_route_batch_c")
+
+int mmp_miss_batch_c(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
+                     const mmp_place_req_c *preqs, int32_t n, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
+                     const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now,
+                     int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts)
+try {
+    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
+        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
+        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "mmp_miss_batch_c: bad argument");
+    for (int32_t i = 0; i < n; i++) {
+        if (const int rc = check_gate_req(c, "mmp_miss_batch_c", i, greqs[i], n_excl, n_explicit)) return rc;
+        if (const int rc = check_place_req(c, "mmp_miss_batch_c", i, preqs[i], n_extra)) return rc;
+        if (const int rc = check_same_model(c, "mmp_miss_batch_c", i, greqs[i].model, preqs[i].model)) return rc;
+    }
+    using L = MissSlot;
+    if (n <= L::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool) {
+        // within the latency slot's sizes (and n = 0): mmp_miss_batch on the rows written out
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_place_req> fp((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
+        }
+        return mmp_miss_batch(c, n ? fg.data() : nullptr, n ? fp.data() : nullptr, n, excl_pod, excl_time, n_excl, explicit_pool,
+                              n_explicit, extra_pool, n_extra, now, in_use_expiry, gouts, pouts);
+    }
+    // a large batch is two calls, as mmp_miss_batch's is: the guards on the compact rows, then the load targets where
+    // mmp_place_batch_c has them
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), xp = seam_io(excl_pod, n_excl, kStagedOnly, c->s_c),
+           xt = seam_io(excl_time, n_excl, kStagedOnly, c->s_d), ex = seam_io(explicit_pool, n_explicit, kStagedOnly, c->s_a),
+           go = seam_io(gouts, n, kStagedOnly, c->s_outs);
+    const int rc = seam_run<false>(c, n, false, {&gq, &xp, &xt, &ex}, {&go}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        GateArgs A = gate_args(c, n, now, in_use_expiry);
+                        A.excl_pod = xp.as<int32_t>();
+                        A.excl_time = xt.as<int64_t>();
+                        A.explicit_pool = ex.as<int32_t>();
+                        A.outs = go.as<mmp_gate_out>();
+                        A.done = done;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, A,
+                                           seam_c_args(*caller, gq, nullptr, n));
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
+    if (rc != MMP_OK) return rc;
+    // (profiling: the call's device span is the sum of its two brackets; a load-target half that rides a slot leaves none.
+    // last_kernel_ms belongs to batch_mu)
+    double gate_ms = -1.0;
+    {
+        std::lock_guard<std::mutex> gb(c->batch_mu);
+        if (c->prof) std::swap(gate_ms, c->last_kernel_ms);
+    }
+    const int rc2 = mmp_place_batch_c(c, pcaller, preqs, n, extra_pool, n_extra, now, pouts);
+    if (gate_ms >= 0) {
+        std::lock_guard<std::mutex> gb(c->batch_mu);
+        if (c->prof) c->last_kernel_ms = c->last_kernel_ms >= 0 ? c->last_kernel_ms + gate_ms : gate_ms;
+    }
+    return rc2;
+} MMP_CATCH(c, "mmp_miss_batch_c")
 
 int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
 try {

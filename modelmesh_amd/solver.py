@@ -787,6 +787,54 @@ class Solver:
                                          ptr(gouts) if n else None, ptr(pouts) if n else None))
         return gouts, pouts
 
+    def route_c(self, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time, explicit_pool, now,
+                in_use_failure_expiry_ms=450_000):
+        """The single-caller form of route (mmp_route_batch_c): caller = 1 SEAM_CALLER row, GATE_REQ_C / SERVE_REQ_C rows
+        -> (gate outs, serve outs)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
+        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        souts = np.zeros(n, dtype=SERVE_OUT)
+        self._ck(self.lib.mmp_route_batch_c(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
+                                            ptr(counters) if len(counters) else None, len(counters),
+                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                            ptr(gouts) if n else None, ptr(souts) if n else None))
+        return gouts, souts
+
+    def miss_c(self, caller, place_caller, gate_reqs_c, place_reqs_c, excl_pod, excl_time, explicit_pool, extra_pool, now,
+               in_use_failure_expiry_ms=450_000):
+        """The single-caller form of miss (mmp_miss_batch_c): caller = 1 SEAM_CALLER row, place_caller = 1 PLACE_CALLER row,
+        GATE_REQ_C / PLACE_REQ_C rows -> (gate outs, place outs)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_OUT, PLACE_REQ_C, SEAM_CALLER
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        pouts = np.zeros(n, dtype=PLACE_OUT)
+        self._ck(self.lib.mmp_miss_batch_c(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
+                                           ptr(place_reqs_c) if n else None, n,
+                                           ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                           len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                           ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
+                                           C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                           ptr(gouts) if n else None, ptr(pouts) if n else None))
+        return gouts, pouts
+
     def proactive_plan(self, default_model_size_units: int, now: int, max_out: int, partition: int = -1, skip_models=None):
         """a17: (models, last_used, info) the leader would proactively load, MRU first; partition >= 0: for that
         ProhibitedTypeSet partition only (one reaper call per partition when type constraints exist)."""
