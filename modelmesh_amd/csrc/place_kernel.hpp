@@ -808,6 +808,9 @@ struct RpmRule {
                ((ago < -1000LL && rpm > m11) || (ago < 5000LL && rpm > m15) ||
                 (ago < 12LL * 60 * 1000 && rpm > m3) || (ago < 24LL * 3600 * 1000 && rpm > m4));
     }
+    // Where 3x / 4x wrap below the minimum itself (min_load >= 2^29) the rule nulls EVERY entry, and the reference's loop stops at one
+    // survivor (:4975-4977): the entry it never reached, the list's LAST.  A decision whose filter leaves nothing therefore answers with
+    // entry ccount - 1 of the unfiltered list and remaining = 1 (`last_only` below; the lean checks hand such a request on).
     // The same rule as ONE threshold: the age clauses are nested (-1 s < 5 s < 12 min < 1 day), so the clauses that
     // apply to this request are a suffix of the list and "some applicable clause has rpm > m_i" is rpm > the
     // smallest applicable m_i (taken explicitly: 3x / 4x wrap like the Java's int products, so the m_i need not
@@ -1442,7 +1445,10 @@ __device__ __forceinline__ int lane_case_b(const Snap &S, const ResolvedReq &r, 
         removed_surv += (int)(bit & (sw_[i] >> (e & 63)));
     }
     const int remaining = pcc[whi + 1] - p0c - removed_surv;
-    if (remaining <= 0) return kLaneWave;  // (cannot happen: the instance with the smallest rpm is never filtered)
+    // The instance with the smallest rpm is never filtered as long as no limit has wrapped below the minimum, and 3x / 4x min_load
+    // wrap from 2^29 on: the `L.min_load > 500000000` test at the top sends those windows to the wave path, which stops at one
+    // survivor as the reference does (see RpmRule).  Keep that test: without it this line would answer for them.
+    if (remaining <= 0) return kLaneWave;
     const int index = remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
     int t = index;
 #pragma unroll
@@ -1736,7 +1742,7 @@ __device__ __forceinline__ int lane_decide_r(const Snap &S, const PlaceArgs &A, 
         }
         PHASE(4);  // count + hash
         int remaining = ccount;
-        bool null0 = false, null_s = false, null_o = false;
+        bool null0 = false, null_s = false, null_o = false, last_only = false;
         if (ccount >= 2) {  // rpm filter, :4951-4980 (quirks B#2/B#3: three rpm classes)
             const int n_others = ccount - 1 - (self_in_c ? 1 : 0);
             int32_t mn = b_rpm;
@@ -1748,9 +1754,14 @@ __device__ __forceinline__ int lane_decide_r(const Snap &S, const PlaceArgs &A, 
             null_s = self_in_c && rule.nulls(e_rpm);
             null_o = n_others > 0 && rule.nulls(f_rpm);
             remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+            if (remaining == 0) {  // the filter stops at one survivor, the list's last entry (see RpmRule)
+                null0 = null_s = null_o = false;
+                remaining = 1;
+                last_only = true;
+            }
         }
         PHASE(5);  // rpm rule
-        const int index = remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
+        const int index = last_only ? ccount - 1 : remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
         int cpos = kNoPos;
         if (remaining >= 1) {
             const int bw = bestpos >> 6, sw = self_in_c ? (selfpos >> 6) : -1;
@@ -2052,7 +2063,7 @@ __device__ __forceinline__ int lane_decide_win(const Snap &S, const PlaceArgs &A
     }
     PHASE(4);
     int remaining = ccount;
-    bool null0 = false, null_s = false, null_o = false;
+    bool null0 = false, null_s = false, null_o = false, last_only = false;
     if (ccount >= 2) {  // rpm filter, :4951-4980 (quirks B#2/B#3: three rpm classes)
         const int n_others = ccount - 1 - (self_in_c ? 1 : 0);
         int32_t mn = b_rpm;
@@ -2065,9 +2076,14 @@ __device__ __forceinline__ int lane_decide_win(const Snap &S, const PlaceArgs &A
         null_s = self_in_c && e_rpm >= 100 && e_rpm > lim;
         null_o = n_others > 0 && f_rpm >= 100 && f_rpm > lim;
         remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+        if (remaining == 0) {  // the filter stops at one survivor, the list's last entry (see RpmRule)
+            null0 = null_s = null_o = false;
+            remaining = 1;
+            last_only = true;
+        }
     }
     PHASE(5);  // rpm rule
-    const int index = remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
+    const int index = last_only ? ccount - 1 : remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
     int cpos = kNoPos;
     if (remaining >= 1) {
         const int sw = self_in_c ? (selfpos >> 6) : -1;
@@ -2188,6 +2204,7 @@ __device__ __forceinline__ void place_one(const Snap &S, const PlaceArgs &A, int
     uint64_t hsum;
     RpmRule rule;
     int remaining;
+    bool last_only = false;  // the filter stopped at one survivor, the list's last entry (see RpmRule)
 
     if (mode_b) {
         // only preferred pods inside the age window are candidates; best0 is not (:4867-4877)
@@ -2238,6 +2255,14 @@ __device__ __forceinline__ void place_one(const Snap &S, const PlaceArgs &A, int
                     }
                 }
                 remaining = ccount - wave_sum_i32(nulled);
+                if (remaining == 0) {  // fw holds the whole list again
+                    for (int base = wlo; base <= whi; base += 64) {
+                        const int w = base + lane;
+                        if (w <= whi) fw[w] = clip_word(ew[w] & Pm[w], w, start, limit);
+                    }
+                    remaining = 1;
+                    last_only = true;
+                }
             }
         }
         wave_sync();
@@ -2334,8 +2359,11 @@ __device__ __forceinline__ void place_one(const Snap &S, const PlaceArgs &A, int
             const bool null0 = rule.nulls(b_rpm);
             const bool null_s = self_in_c && rule.nulls(e_rpm);
             const bool null_o = n_others > 0 && rule.nulls(f_rpm);
-            if (null0 || null_s || null_o) {
-                remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+            if (null0 || null_s || null_o) remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+            if (remaining == 0) {  // fw keeps the whole list
+                remaining = 1;
+                last_only = true;
+            } else if (null0 || null_s || null_o) {
                 const int bw = bestpos >> 6, sw = self_in_c ? (selfpos >> 6) : -1;
                 for (int base = wlo; base <= whi; base += 64) {
                     const int w = base + lane;
@@ -2362,7 +2390,7 @@ __device__ __forceinline__ void place_one(const Snap &S, const PlaceArgs &A, int
     }
     const uint32_t hash = (uint32_t)(hsum ^ (hsum >> 32)) ^ ((uint32_t)remaining * 0x9E3779B1u);
     // :4981-4986 — index-th non-null candidate
-    const int index = remaining <= 1 ? 0 : (int)(((uint64_t)rq.pick * (uint64_t)(uint32_t)remaining) >> 32);
+    const int index = last_only ? ccount - 1 : remaining <= 1 ? 0 : (int)(((uint64_t)rq.pick * (uint64_t)(uint32_t)remaining) >> 32);
     const int cpos = remaining >= 1 ? select_in_range(fw, wlo, whi, index) : kNoPos;
     int32_t chosen = MMP_NONE;
     if (cpos != kNoPos) {
@@ -2595,6 +2623,7 @@ __device__ __forceinline__ bool memo_try(const Snap &S, const PlaceArgs &A, cons
     const bool null_s = ccount >= 2 && self_in && e_rpm >= 100 && e_rpm > lim;
     const bool null_o = ccount >= 2 && n_others > 0 && f_rpm >= 100 && f_rpm > lim;
     const int remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+    if (ccount >= 2 && remaining == 0) return false;  // every entry over the limit (see RpmRule): the ordinary path decides
     const int index = remaining <= 1 ? 0 : (int)(((uint64_t)rq.pick * (uint64_t)(uint32_t)remaining) >> 32);
     // candidate number of the index-th survivor
     int k;
@@ -2767,7 +2796,7 @@ __device__ __forceinline__ bool long_memo_try(const Snap &S, const PlaceArgs &A,
     }
     const int ccount = vh.z - __popc(xmask);
     int remaining = ccount;
-    bool null0 = false, null_s = false, null_o = false;
+    bool null0 = false, null_s = false, null_o = false, last_only = false;
     int n_others = 0;
     if (ccount >= 2) {  // rpm filter, :4951-4980 (quirks B#2/B#3: three rpm classes)
         n_others = ccount - 1 - (self_in_c ? 1 : 0);
@@ -2780,8 +2809,13 @@ __device__ __forceinline__ bool long_memo_try(const Snap &S, const PlaceArgs &A,
         null_s = self_in_c && rule.nulls(e_rpm);
         null_o = n_others > 0 && rule.nulls(f_rpm);
         remaining = ccount - (null0 ? 1 : 0) - (null_s ? 1 : 0) - (null_o ? n_others : 0);
+        if (remaining == 0) {  // the filter stops at one survivor, the list's last entry (see RpmRule)
+            null0 = null_s = null_o = false;
+            remaining = 1;
+            last_only = true;
+        }
     }
-    const int index = remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
+    const int index = last_only ? ccount - 1 : remaining <= 1 ? 0 : (int)(((uint64_t)r.pick * (uint64_t)(uint32_t)remaining) >> 32);
     int cpos = kNoPos;
     if (remaining >= 1) {
         if (null_o) {  // only the best and the self entry can be left, in that order

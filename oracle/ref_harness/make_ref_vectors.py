@@ -7,7 +7,8 @@ Per load-target case: the clusterState iteration order, and per request (chosen,
 filter, audit hash of the shortlist).  Per serve-target case: (chosen, chosenTimeStamp).  Per guard case: (MMP_GATE_* bits,
 loadLocal's initial size).  Plus a digest of each case's inputs.
 tests/golden/ref_gate_edges.npz: the guard cases at the edges of their value domain (gate_edge_vectors below).
-usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges]"""
+tests/golden/ref_place_edges.npz: the load-target cases at the edges of theirs (place_edge_vectors below).
+usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges]"""
 import os
 import subprocess
 import sys
@@ -24,6 +25,7 @@ from tests import ref_fleets as rf  # noqa: E402
 HARNESS = os.environ.get("MMP_REF_HARNESS") or os.path.join(ROOT, "oracle", "_ref", "ref_harness")
 OUT = os.environ.get("MMP_REF_OUT") or os.path.join(ROOT, "tests", "golden", "ref_getnext.npz")
 EDGE_OUT = os.environ.get("MMP_REF_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_gate_edges.npz")
+PLACE_EDGE_OUT = os.environ.get("MMP_REF_PLACE_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_place_edges.npz")
 
 
 def proactive_inputs(fleet, units, partitioned):
@@ -194,11 +196,79 @@ def gate_edge_vectors():
     print(f"wrote {EDGE_OUT}: {os.path.getsize(EDGE_OUT) / 1e6:.2f} MB, {len(names)} cases")
 
 
+def place_edge_vectors():
+    """tests/golden/ref_place_edges.npz: getNext at the edges of its value domain (tests/ref_fleets.py:place_edge_cases).  As above, a
+    case that does not hold what it is there for is REFUSED, on the evidence of the inputs and the reference's own outputs."""
+    out, names = {}, []
+    seen = {t: dict(rows=0, pairs=0, outcomes=set(), sizes=set(), kinds=set(), rpm={}) for t in rf.PLACE_EDGE_TIERS}
+    orders = {}
+    for name, fleet, ids, reqs, extra in rf.place_edge_cases():
+        tier, meta = rf.place_edge_tier(name), rf.place_edge_meta(name)
+        assert tier in rf.PLACE_EDGE_TIERS and fleet.n_pods in (8, 64, 65, 200, 700) and 0 < len(reqs) <= 3000, name
+        blob = rf.input_blob(fleet, ids, reqs, extra)
+        order, place, _, _ = run(blob, len(reqs), 0)
+        for a, b, off in meta["pairs"]:  # one row inside, one outside a threshold: the reference must decide them differently
+            if off == 0:  # the same first instance: the same walk but for the threshold
+                assert not np.array_equal(place[a, :3], place[b, :3]), (name, "the reference decides a pair alike", a, b, place[a], place[b], reqs[a], reqs[b])
+            else:  # first instances `off` positions apart: lists of different length anyway — they must END at different instances
+                assert place[a, 1] > 0 and place[b, 1] > 0 and place[a, 1] != place[b, 1] + off, \
+                    (name, "the two lists of a pair end at the same instance", a, b, off, place[a], place[b])
+        if meta["caller"]:
+            for f in rf._lib.PLACE_CALLER.names:
+                assert np.all(reqs[f] == reqs[f][0]), (name, "not one caller's batch", f)
+            assert len(meta["pairs"]) > 0 or tier == "order", name  # (the order tier is about the table: it has no pairs)
+        st = seen[tier]
+        st["rows"] += len(reqs)
+        st["pairs"] += len(meta["pairs"])
+        st["outcomes"] |= {"remote" if c >= 0 else "self" if c == -2 else "none" for c in place[:, 0]}
+        st["sizes"] |= set(int(n) for n in place[:, 1])
+        st["kinds"] |= set(rf.place_row_kinds(fleet, order, reqs, extra))
+        for i in np.nonzero(place[:, 1] >= 2)[0]:
+            gone = int(place[i, 1] - place[i, 2])
+            how = "0" if gone == 0 else "all but one" if gone == place[i, 1] - 1 else "some"
+            st["rpm"].setdefault(rf.rpm_class(fleet, int(reqs["last_used"][i])), {}).setdefault(how, 0)
+            st["rpm"][rf.rpm_class(fleet, int(reqs["last_used"][i]))][how] += 1
+        orders[name] = order
+        out[f"{name}/order"], out[f"{name}/place"] = order, place
+        out[f"{name}/digest"] = np.frombuffer(rf.digest(blob).encode(), np.uint8)
+        names.append(name)
+        print(f"{name}: {len(order)} instances, {len(reqs)} decisions, {len(meta['pairs'])} pairs: "
+              f"{int((place[:, 0] >= 0).sum())} remote, {int((place[:, 0] == -2).sum())} self, {int((place[:, 0] == -1).sum())} none; "
+              f"shortlists {int(place[:, 1].min())} ... {int(place[:, 1].max())}")
+    assert len(names) <= 16
+    for tier in rf.PLACE_EDGE_TIERS:
+        assert any(rf.place_edge_meta(n)["caller"] for n in names if rf.place_edge_tier(n) == tier), (tier, "no one-caller case")
+    for name in names:
+        after = rf.place_edge_meta(name)["after"]
+        if after is not None:
+            assert not np.array_equal(orders[name], orders[after]), (name, "the changed rows do not move in the order")
+    for tier in rf.PLACE_EDGE_TIERS:
+        st = seen[tier]
+        assert st["outcomes"] == {"remote", "self", "none"}, (tier, st["outcomes"])
+        print(f"tier {tier}: {st['rows']} rows, {st['pairs']} pairs; kinds " + ", ".join(sorted(f"{k}{' (full)' if f else ''}" for k, f in st["kinds"])) +
+              f"; shortlists of 1: {1 in st['sizes']}, of >= 65: {max(st['sizes']) >= 65}; filtered by rpm class: " +
+              "; ".join(f"{c} {st['rpm'].get(c, {})}" for c in rf.RPM_CLASSES))
+    sizes = set().union(*(seen[t]["sizes"] for t in rf.PLACE_EDGE_TIERS))
+    assert 1 in sizes and max(sizes) >= 65, sizes
+    # case (a) exists only with a first instance that is not full and case (b) only with a full one (:4828); the simple case in both
+    assert seen["breaks"]["kinds"] >= {("simple", False), ("simple", True), ("a found", False), ("a replay", False), ("b found", True),
+                                       ("b replay", True), ("none", False)}, seen["breaks"]["kinds"]
+    assert {("simple", True), ("b found", True)} <= seen["rpm"]["kinds"], seen["rpm"]["kinds"]
+    for c in rf.RPM_CLASSES[:4]:  # beyond a day no clause applies (:4972): class `none` filters nothing
+        assert set(seen["rpm"]["rpm"].get(c, {})) == {"0", "some", "all but one"}, (c, seen["rpm"]["rpm"].get(c))
+    assert set(seen["rpm"]["rpm"]["none"]) == {"0"}, seen["rpm"]["rpm"]["none"]
+    out["names"] = np.array(names)
+    np.savez_compressed(PLACE_EDGE_OUT, **out)
+    print(f"wrote {PLACE_EDGE_OUT}: {os.path.getsize(PLACE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
     if "--gate-edges" in sys.argv[1:]:  # only the guard edge cases: ref_getnext.npz stays as it is
         return gate_edge_vectors()
+    if "--place-edges" in sys.argv[1:]:  # only the load-target edge cases
+        return place_edge_vectors()
     out = {}
     names = []
     for name, fleet, ids, reqs, extra in rf.place_cases():
@@ -363,6 +433,7 @@ def main():
     np.savez_compressed(OUT, **out)
     print(f"wrote {OUT}: {os.path.getsize(OUT) / 1e6:.2f} MB, {len(names)} cases")
     gate_edge_vectors()
+    place_edge_vectors()
 
 
 if __name__ == "__main__":

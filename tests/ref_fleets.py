@@ -10,6 +10,7 @@ and derives the replica set from id.substring(0, 6) (MM.java:4770).  The fuzz fl
 the registry entries (instanceIds / loadFailedInstanceIds iterate in id order) are re-sorted accordingly."""
 from __future__ import annotations
 
+import functools
 import hashlib
 import struct
 
@@ -819,6 +820,560 @@ def sizing_outcomes(fleet, r, tstats):
     return out
 
 
+PLACE_EDGE_TIERS = ("breaks", "rpm", "order")
+RPM_CLASSES = ("m11", "m15", "m3", "m4", "none")  # the strictest clause of :4966-4972 that applies to a request's lastUsedAgo
+
+
+def place_edge_tier(name):
+    return name.split("_")[1]
+
+
+def place_edge_meta(name):
+    """What a place-edge case was built for: pairs [(row inside, row outside, offset)] of requests on either side of one threshold
+    — offset 0: the two rows walk from the same first instance; else the outside row's first instance stands that many eligible
+    positions behind (negative: in front of) the inside row's, and what must differ is where the two lists END —, caller (the case
+    is one caller's batch), after (the name of the case that holds the same table after a few rows changed)."""
+    return _place_edge_all()[name][4]
+
+
+def rpm_class(fleet, last_used):
+    ago = 0 if last_used == 0 else fleet.now - int(last_used)
+    return "m11" if ago < -1000 else "m15" if ago < 5000 else "m3" if ago < 720_000 else "m4" if ago < 86_400_000 else "none"
+
+
+def cluster_order(fleet):
+    """The instances in PLACEMENT_ORDER, by the Python restatement: used to AIM the engineered rows (which instance is a model's
+    first candidate); the expected outputs come from the reference."""
+    from oracle import py_oracle as po
+    return po.Mesh(fleet.min_space_units, fleet.min_churn_age_ms, fleet.now).sorted_cluster_state(py_pods(fleet))
+
+
+def py_pods(fleet):
+    """The instance table as oracle/py_oracle.py takes it."""
+    return [dict(lru_time=int(r["lru_time"]), capacity=int(r["capacity"]), used=int(r["used"]), version=int(r["version"]), count=int(r["count"]),
+                 loading_threads=int(r["loading_threads"]), loading_in_progress=int(r["loading_in_progress"]), rpm=int(r["rpm"]),
+                 id_order=int(r["id_order"]), replica_set=int(r["replica_set"]), shutting_down=bool(r["flags"] & 5)) for r in fleet.pods]
+
+
+def _set_types(fleet, allowed, prefer):
+    """Per type row the instances it may be placed on / prefers (None: no such set)."""
+    T, P = len(allowed), fleet.n_pods
+    al, pf = np.ones((T, P), bool), np.zeros((T, P), bool)
+    for t in range(T):
+        if allowed[t] is not None:
+            al[t] = np.isin(np.arange(P), list(allowed[t]))
+        if prefer[t] is not None:
+            pf[t] = np.isin(np.arange(P), list(prefer[t]))
+    fleet.n_types = T
+    fleet.allowed, fleet.prefer = wl.bitmap_from_bool(al), wl.bitmap_from_bool(pf)
+    fleet.has_allowed = np.array([a is not None for a in allowed], np.uint8)
+    fleet.has_prefer = np.array([p is not None for p in prefer], np.uint8)
+
+
+class _PlaceRows:
+    """Load-target requests of one case.  A row's fresh record is the table's row of its caller (a stand-in for a caller that is
+    not in the table) unless the keywords lru / capacity / used / count / rpm move a field; ago: lastUsedAgo (a day and more by
+    default: the rpm rule filters nothing)."""
+
+    def __init__(self, fleet, seed):
+        self.fleet, self.rng = fleet, np.random.default_rng(0x91ACE + seed)
+        self.rows, self.extra, self.pairs = [], [], []
+
+    def add(self, model, self_pod=-1, favour=0, pick=None, ago=100_000_000, last_used=None, extra=(), **fresh):
+        f = self.fleet
+        q = np.zeros(1, dtype=_lib.PLACE_REQ)
+        q["model"], q["self_pod"], q["flags"] = model, self_pod, favour
+        q["pick"] = int(self.rng.integers(0, 2**32)) if pick is None else pick
+        q["last_used"] = f.now - ago if last_used is None else last_used
+        q["extra_off"], q["n_extra"] = len(self.extra), len(extra)
+        self.extra += [int(p) for p in extra]
+        if self_pod >= 0:
+            cur = f.pods[self_pod]
+            vals = dict(lru=cur["lru_time"], capacity=cur["capacity"], used=cur["used"], count=cur["count"], rpm=cur["rpm"])
+        else:
+            vals = dict(lru=f.now - 1_000_000, capacity=1_000_000, used=500_000, count=5, rpm=0)
+        vals.update(fresh)
+        q["fresh_lru"], q["fresh_capacity"], q["fresh_used"] = vals["lru"], vals["capacity"], vals["used"]
+        q["fresh_count"], q["fresh_rpm"] = vals["count"], vals["rpm"]
+        self.rows.append(q)
+        return len(self.rows) - 1
+
+    def pair(self, inside, outside, offset=0):
+        self.pairs.append((inside, outside, offset))
+
+    def done(self):
+        return np.concatenate(self.rows), np.array(self.extra, np.int32)
+
+
+def _one_caller(rows, self_pod, **fresh):
+    """The same requests as ONE instance's batch: every row carries this caller and its fresh record."""
+    for q in rows.rows:
+        q["self_pod"], q["flags"] = self_pod, 0
+        q["fresh_lru"], q["fresh_capacity"], q["fresh_used"] = fresh["lru"], fresh["capacity"], fresh["used"]
+        q["fresh_count"], q["fresh_rpm"] = fresh["count"], fresh["rpm"]
+
+
+def _age(now, t):
+    return 0 if t == 0 else now - t
+
+
+def _tdiv(a, b):
+    return abs(a) // b * (1 if a >= 0 else -1)  # Java's '/': toward zero
+
+
+def _breaks_full_case(P, seed, typed, future=False, zero_oldest=False, caller=False, mixed=False):
+    """Every instance full: the LRU break (:4913-4917) and case (b)'s window (:4864).  Instances are named by their role; a model
+    whose copies are the instances in front of X in the order has X as its first candidate.  mixed: a sixth of the instances are
+    NOT full and no type may use them — the same walks, on a table that is no full cluster (the device picks its kernels by that)."""
+    fleet, rng = _edge_fleet(P, seed)
+    now = fleet.now
+    pods = fleet.pods
+    pods["used"] = pods["capacity"] - rng.integers(0, fleet.min_space_units, P)
+    perm = [int(p) for p in rng.permutation(P)]
+    Y = now - 440_000  # age / 10 and age / 4 below 45 000 and 120 000 from here on
+    lru = [now - 3_000_007, now - 3_000_007 + 1_001, now - 3_000_007 + 2_002, Y, Y + 1_000, Y + 1_001]
+    O0, O1, O2, Y5, Y6, Y7 = perm[:6]
+    k = 6
+    gaps = []
+    if typed:  # instances exactly at, and one millisecond behind, the end of case (b)'s window of Y5 and of O1
+        q = _tdiv(now - lru[1], 4)
+        assert q > 120_000 and (now - lru[1]) % 4
+        lru += [Y + 120_000, Y + 120_001, lru[1] + q, lru[1] + q + 1]
+        gaps = perm[6:10]
+        k = 10
+    step = max(1, 100_000 // P)
+    lru += [Y + 2_000 + i * step for i in range(P - k)]
+    pods["lru_time"][perm] = lru
+    if zero_oldest:
+        pods["lru_time"][O0] = 0  # age(0) is 0 (:4162-4164)
+    if future:  # the call's `now` lies before every lruTime: negative ages
+        fleet.now = now = int(pods["lru_time"].min()) - 95
+    open_pods = set(p for p in perm[k + 5::6] if p != perm[-1]) if mixed else set()
+    pods["used"][sorted(open_pods)] = 500_000
+    # counts that do not decrease along the order (full instances stand in lruTime order): the device keeps its per-type head
+    # windows, and the shortlists it records from them at commit, only for such a table
+    pods["count"][np.argsort(pods["lru_time"], kind="stable")] = 40 + np.arange(P) // 4
+    pods["count"][sorted(open_pods)] = 1 + np.arange(len(open_pods))
+    ids = string_ids(fleet, 400 + seed)
+    order = cluster_order(fleet)
+    assert set(order[:len(open_pods)]) == open_pods
+    order = order[len(open_pods):]  # the full instances: all a type may use
+    pos = {p: i for i, p in enumerate(order)}
+    assert [pos[p] for p in (O0, O1, O2)] == [0, 1, 2] and pos[Y5] < pos[Y6] < pos[Y7] == pos[Y6] + 1
+    far = order[-1]
+    firsts = [O0, O1, O2, Y5, Y6, Y7] + ([order[pos[Y7] + 1]] if P > 8 else [])
+    allowed, prefer = [None], [None]
+    if typed:
+        sub = sorted((set(firsts) | set(gaps) | {far} | set(int(p) for p in rng.choice(P, P // 2, replace=False))) - open_pods)
+        if mixed:
+            allowed, every = [list(order)], list(order)
+        else:
+            every = None
+        # (the last two: types whose FIRST instance is Y6 / Y7 — what the device records per type at commit starts there)
+        allowed += [sub, every, every, every, every, [order[-2], order[-3]], order[pos[Y6]:], order[pos[Y7]:]]
+        prefer += [None, [gaps[0]], [gaps[1]], [gaps[2]], [gaps[3]], None, None, None]
+        _set_types(fleet, allowed, prefer)
+    specs, first_of, kind = [], [], []
+    for t in range(2 if typed else 1):
+        for b in firsts:
+            specs.append((t, order[:pos[b]], []))
+            first_of.append(b)
+            kind.append("simple")
+    if typed:
+        for t, b in ((2, Y5), (3, Y5), (4, O1), (5, O1)):
+            specs.append((t, order[:pos[b]], []))
+            first_of.append(b)
+            kind.append("b")
+        specs.append((6, [order[-2]], [order[-3]]))  # every instance of its type holds or failed it: no candidate
+        first_of.append(None)
+        kind.append("none")
+        for t, b in ((7, Y6), (8, Y7)):
+            specs.append((t, [], []))
+            first_of.append(b)
+            kind.append("simple")
+    _set_models(fleet, specs)
+    rows = _PlaceRows(fleet, seed)
+    T_of = {}
+    for m, b in enumerate(first_of):
+        if b is None:
+            rows.add(m)
+            rows.add(m, self_pod=far, favour=1)
+            continue
+        oldest = int(pods["lru_time"][b])
+        T_of[m] = thr = max(45_000, _tdiv(_age(now, oldest), 10))
+        elig = [p for p in order[pos[b] + 1:] if allowed[specs[m][0]] is None or p in allowed[specs[m][0]]]
+        assert len(elig) >= 2 and elig[-1] == far
+        if kind[m] == "b":
+            rows.add(m, lru=oldest)
+            rows.add(m, lru=oldest + thr + 1)
+            rows.add(m, self_pod=gaps[specs[m][0] - 2], favour=1)
+            rows.add(m, self_pod=gaps[specs[m][0] - 2], favour=0)
+            continue
+        for sp in (-1, far, elig[0]):
+            for fav in (0, 1):
+                i = [rows.add(m, self_pod=sp, favour=fav, lru=oldest + thr + d) for d in (-1, 0, 1)]
+                if fav == 0:
+                    rows.pair(i[1], i[2])
+        rows.add(m, self_pod=b, favour=1)
+        rows.add(m, self_pod=b, favour=0, lru=oldest + 50_000)
+        rows.add(m, self_pod=b, favour=0, lru=oldest - 50_000, extra=[elig[0]])
+    if typed:  # case (b): the preferred instance at the window's last millisecond / one behind it
+        nb = len(firsts) * 2
+        base = {m: None for m in range(nb, nb + 4)}
+        for i, q in enumerate(rows.rows):
+            m = int(q["model"][0])
+            if m in base and base[m] is None:
+                base[m] = i  # the model's first row: no caller, the fresh row at `oldest`
+        rows.pair(base[nb], base[nb + 1])
+        rows.pair(base[nb + 2], base[nb + 3])
+    if caller:  # one caller: the fresh lruTime 45 001 ms behind Y6's and 45 000 behind Y7's
+        for m in range(len(first_of)):
+            if first_of[m] is not None:
+                for _ in range(3):
+                    rows.add(m)
+        cur = pods[far]
+        _one_caller(rows, far, lru=int(pods["lru_time"][Y6]) + 45_001, capacity=cur["capacity"], used=cur["used"], count=cur["count"], rpm=0)
+        assert T_of[firsts.index(Y6)] == T_of[firsts.index(Y7)] == 45_000
+        rows.pairs = []
+        for t in range(2 if typed else 1):
+            a, b = (t * len(firsts) + firsts.index(x) for x in (Y7, Y6))
+            ia, ib = (next(i for i, q in enumerate(rows.rows) if q["model"][0] == m) for m in (a, b))
+            rows.pair(ia, ib, -1)
+        if typed:  # ... and as their types' first instances, nothing excluded
+            ia, ib = (next(i for i, q in enumerate(rows.rows) if q["model"][0] == m) for m in (len(specs) - 1, len(specs) - 2))
+            rows.pair(ia, ib, -1)
+    return fleet, ids, rows
+
+
+OPEN_COUNTS = (7, 8, 9, 10, 10, 11, 11, 11, 12, 12, 40, 50, 51, 52, 62, 63, 64, 65, 66)
+FRESH_COUNTS = (7, 8, 9, 10, 40, 41, 50, 51, 52, 1_717_986_918, 1_717_986_919, INT_MAX)
+
+
+def _breaks_open_case(P, seed, typed, caller=False):
+    """Nothing full in front: the remaining-space break (:4922), the count break (:4926) inside and beyond the device's table of
+    thresholds, case (a) with the caller behind the preferred instance (its row is judged by the FIRST entry's record, :4909)."""
+    fleet, rng = _edge_fleet(P, seed)
+    now, pods, msu = fleet.now, fleet.pods, fleet.min_space_units
+    perm = [int(p) for p in rng.permutation(P)]
+    role = {}
+
+    def put(name, count, rem):
+        p = perm[len(role)]
+        role[name] = p
+        pods["capacity"][p], pods["used"][p], pods["count"][p] = 1_000_000, 1_000_000 - rem, count
+        return p
+    put("S1", 1, 20_000)  # a quarter of their space lies below min_space: the full rule decides
+    put("S2", 2, 20_001)
+    for j in range(5):
+        put(f"Q{j}", 3, 400_000 + j)  # remaining % 4 = 0 ... 3, and the next multiple
+    for j, c in enumerate(OPEN_COUNTS):
+        put(f"C{c}_{j}", c, 300_000 - j)
+    put("Bp", 13, 80_004)
+    for c in (14, 15, 16, 17):
+        put(f"P{c}", c, 300_000)
+    n_role = len(role)
+    for p in perm[n_role:]:
+        pods["capacity"][p], pods["count"][p] = 1_000_000, int(rng.integers(18, 40))
+        pods["used"][p] = 1_000_000 - int(rng.integers(250_000, 350_000))
+    # behind them: a full instance, and one whose `used` exceeds its capacity (getRemaining clamps to 0)
+    pods["used"][perm[-1]] = pods["capacity"][perm[-1]] + 7
+    pods["used"][perm[-2]] = pods["capacity"][perm[-2]] - msu + 1
+    pods["count"][perm[-2:]] = 100  # (counts do not decrease along the order: the device keeps its head windows for such a table)
+    ids = string_ids(fleet, 420 + seed)
+    order = cluster_order(fleet)
+    pos = {p: i for i, p in enumerate(order)}
+    assert set(order[-2:]) == set(perm[-2:]) and [pos[role[x]] for x in ("S1", "S2")] == [0, 1]
+    assert [order[2 + j] for j in range(5)] == [role[f"Q{4 - j}"] for j in range(5)]
+    pref = [role[x] for x in ("Bp", "P14", "P15", "P16", "P17")]
+    allowed, prefer = [None], [None]
+    if typed:
+        sub = sorted(set(role.values()) | set(int(p) for p in rng.choice(P, P // 2, replace=False)))
+        # (the last two: types whose FIRST instance is Q4 / Q3 — what the device records per type at commit starts there)
+        allowed += [sub, None, [perm[-3], perm[-4]], order[pos[role["Q4"]]:], order[pos[role["Q3"]]:]]
+        prefer += [None, pref, None, None, None]
+        _set_types(fleet, allowed, prefer)
+    firsts = ["S1", "S2", "Q4", "Q3", "Q2", "Q1", "Q0"] + [f"C{c}_{j}" for j, c in enumerate(OPEN_COUNTS) if c not in OPEN_COUNTS[:j]][:10]
+    specs, first_of = [], []
+    for t in range(2 if typed else 1):
+        for x in firsts:
+            specs.append((t, order[:pos[role[x]]], []))
+            first_of.append(x)
+    if typed:
+        specs += [(2, [], []), (2, [role["S1"]], []), (3, [perm[-3]], [perm[-4]]), (2, pref, [])]  # the last: no preferred instance left
+        first_of += ["a:S1", "a:S2", None, "S1"]
+        specs += [(4, [], []), (5, [], [])]
+        first_of += ["Q4", "Q3"]
+    _set_models(fleet, specs)
+    rows = _PlaceRows(fleet, seed)
+    far = order[-3]
+    by_first = {}
+    for m, x in enumerate(first_of):
+        if x is None:
+            rows.add(m)
+            rows.add(m, self_pod=far, favour=1)
+            continue
+        if x.startswith("a:"):  # case (a): Bp becomes the best instance
+            q = max(msu, (1_000_000 - int(pods["used"][role["Bp"]])) >> 2)
+            i = [rows.add(m, self_pod=role["P15"], favour=0, used=1_000_000 - 300_000) for _ in range(2)]
+            by_first[x] = i[0]
+            j = [rows.add(m, used=1_000_000 - (q + d)) for d in (-1, 0, 1)]
+            rows.pair(j[1], j[0])
+            rows.add(m, self_pod=role["Bp"], favour=1)
+            rows.add(m, self_pod=role["P16"], favour=1)
+            continue
+        b = role[x]
+        b_rem = 1_000_000 - int(pods["used"][b])
+        q = max(msu, b_rem >> 2)
+        for sp in (-1, far):
+            i = [rows.add(m, self_pod=sp, used=1_000_000 - (q + d)) for d in (-1, 0, 1)]
+            rows.pair(i[1], i[0])
+        i = [rows.add(m, used=1_000_000 - msu), rows.add(m, used=1_000_000 + 5), rows.add(m, used=LONG_MAX)]
+        if q == msu:
+            rows.pair(i[0], i[1])  # capacity - used <= 0: clamped to 0, full
+        by_first.setdefault(x.split("_")[0], rows.add(m, used=500_000))
+        rows.add(m, self_pod=b, favour=1)
+        rows.add(m, self_pod=far, favour=1, used=500_000)
+        if x.startswith("C"):  # the caller is the first candidate: firstCount is its FRESH count
+            i = [rows.add(m, self_pod=b, count=c) for c in FRESH_COUNTS]
+            if x == "C7_0":
+                for a, o in zip(i[:-2], i[1:-1]):  # (the last two both wrap)
+                    rows.pair(a, o)
+    for a, o in ((7, 8), (8, 9), (9, 10), (50, 51), (51, 52)):  # ... and through the table's rows
+        rows.pair(by_first[f"C{a}"], by_first[f"C{o}"], 1)  # (the next first instance stands one position behind)
+    if typed:
+        rows.pair(by_first["a:S2"], by_first["a:S1"])  # the caller behind Bp breaks on S1's remaining space, not on S2's
+    if caller:  # one caller with 100 000 units left: a quarter of Q3's space, one short of a quarter of Q4's
+        for m in range(len(first_of)):
+            for _ in range(3):
+                rows.add(m)
+        cur = pods[far]
+        _one_caller(rows, far, lru=cur["lru_time"], capacity=1_000_000, used=900_000, count=cur["count"], rpm=0)
+        rows.pairs = []
+        for t in range(2 if typed else 1):
+            a, b = (t * len(firsts) + firsts.index(x) for x in ("Q3", "Q4"))
+            ia, ib = (next(i for i, q in enumerate(rows.rows) if q["model"][0] == m) for m in (a, b))
+            rows.pair(ia, ib, -1)
+        if typed:  # ... and as their types' first instances, nothing excluded
+            ia, ib = (next(i for i, q in enumerate(rows.rows) if q["model"][0] == m) for m in (len(specs) - 1, len(specs) - 2))
+            rows.pair(ia, ib, -1)
+    return fleet, ids, rows
+
+
+AGO_EDGES = (-1_001, -1_000, 4_999, 5_000, 719_999, 720_000, 86_399_999, 86_400_000, 431_999_999, 432_000_000)
+MIN_LOADS = (50, 101, 109, 110, 1_000)  # the table's rpm of the first candidate: min_load 100 (from below), 101, ...
+WRAP_LOADS = (2**29 - 1, 2**29, 715_827_882, 715_827_883, 2**30 - 1, 2**30, INT_MAX)
+B_RPMS = (100, 111, 151, 301, 401, 99, 100, 101)  # case (b)'s candidates carry their own (:4875)
+CLASS_AGO = (-5_000, 0, 10_000, 1_000_000)  # one lastUsedAgo per clause: m11, m15, 3 * min, 4 * min is the strictest that applies
+
+
+def _rpm_thresholds(min_load):
+    m = max(100, min_load)
+    return [min(m + m // 10, INT_MAX), min(m + m // 2, INT_MAX), _i32(m * 3), _i32(m * 4)]
+
+
+def _rpm_case(P, seed, typed, caller=False):
+    """Every instance full and as old as the first: the shortlist is everything eligible, and the rpm rule (:4951-4986) decides.  In
+    the simple case the list is [the first candidate's rpm, the caller's fresh rpm, ...] (:4909, :4936)."""
+    fleet, rng = _edge_fleet(P, seed)
+    now, pods = fleet.now, fleet.pods
+    pods["used"] = pods["capacity"] - rng.integers(0, fleet.min_space_units, P)
+    perm = [int(p) for p in rng.permutation(P)]
+    pods["lru_time"][perm] = now - 400_000 + 10 * np.arange(P)
+    pods["count"][perm] = 5 + np.arange(P) // 4  # (not decreasing along the order: the device keeps its head windows for such a table)
+    head = list(MIN_LOADS) + list(WRAP_LOADS)
+    pods["rpm"][perm[:len(head)]] = head
+    bp = perm[len(head)]
+    Pb = perm[len(head) + 1: len(head) + 1 + len(B_RPMS)]
+    pods["rpm"][Pb] = B_RPMS
+    Pw = perm[len(head) + 9: len(head) + 13]
+    pods["rpm"][Pw] = [2**30, 2**30, 2**30 + 5, 2**30]
+    rest = perm[len(head) + 13:]
+    ids = string_ids(fleet, 440 + seed)
+    order = cluster_order(fleet)
+    assert order == perm
+    sizes = [n for n in (2, 3, 63, 64, 65) if n <= len(rest)] + ([len(rest)] if len(rest) < 63 else [])
+    allowed, prefer = [None], [None]
+    if typed:
+        allowed += [None, None] + [rest[:n] for n in sizes] + [rest[:2]]
+        prefer += [Pb, Pw] + [None] * len(sizes) + [None]
+        _set_types(fleet, allowed, prefer)
+    specs = [(0, perm[:k], []) for k in range(len(head))]
+    if typed:
+        specs += [(1, perm[:len(head)], []), (2, perm[:len(head)], [])]
+        specs += [(3 + j, [], []) for j in range(len(sizes))]
+        specs.append((3 + len(sizes), rest[:1], rest[1:2]))
+    _set_models(fleet, specs)
+    rows = _PlaceRows(fleet, seed)
+    far = perm[-1]
+
+    def lru_of(m):
+        return int(pods["lru_time"][perm[m]])
+    # lastUsedAgo on either side of every clause's limit; the fresh rpm such that this clause alone decides (min_load 100)
+    for f in (111, 200, 350, 401, 100):
+        i = [rows.add(0, ago=a, lru=lru_of(0), rpm=f) for a in AGO_EDGES]
+        for a, o in ((1, 0), (3, 2), (5, 4), (7, 6)):
+            if f == (111, 200, 350, 401)[a // 2]:
+                rows.pair(i[a], i[o])
+        z = rows.add(0, last_used=0, lru=lru_of(0), rpm=f)  # never used: age(0) == 0, within the 5 s clause
+        if f == 200:
+            rows.pair(i[3], z)
+    # the fresh rpm below, at and above each clause's limit, per min_load
+    for m in range(len(MIN_LOADS)):
+        th = _rpm_thresholds(MIN_LOADS[m])
+        for c in range(4):
+            for sp in (-1, far):
+                i = [rows.add(m, self_pod=sp, ago=CLASS_AGO[c], lru=lru_of(m), rpm=th[c] + d) for d in (-1, 0, 1)]
+                rows.pair(i[1], i[2])
+        for f in (99, 100, 101):
+            rows.add(m, ago=0, lru=lru_of(m), rpm=f)
+        rows.add(m, self_pod=perm[m], favour=1)
+        for c in range(4):  # the first candidate alone is filtered
+            rows.add(m, ago=CLASS_AGO[c], lru=lru_of(m), rpm=100)
+    # min_load where 3 * min and 4 * min wrap and 1.1 * min, 1.5 * min saturate
+    wi = {}
+    for j, w in enumerate(WRAP_LOADS):
+        m = len(MIN_LOADS) + j
+        th = _rpm_thresholds(w)
+        for c in range(4):
+            for f in sorted({w, INT_MAX} | {min(max(t, w), INT_MAX) for t in (th[c] - 1, th[c], th[c] + 1)}):
+                wi[(w, c, f)] = rows.add(m, ago=CLASS_AGO[c], lru=lru_of(m), rpm=f, pick=[0, 1, 2**31, 2**32 - 1][(j + c) % 4])
+        rows.add(m, ago=90_000_000, lru=lru_of(m), rpm=INT_MAX)
+    rows.pair(wi[(2**29 - 1, 3, 2**29 - 1)], wi[(2**29, 3, 2**29)])  # 4 * 2^29 wraps to MIN_VALUE: everything is filtered
+    # (3 * min wraps from 715 827 883 on; 4 * min has wrapped by then and applies whenever 3 * min does: those rows are not a pair)
+    if typed:
+        mb = len(head)
+        # case (b): the candidates' own rpm against every lastUsedAgo
+        for sp, fav in ((-1, 0), (far, 0), (Pb[2], 0), (Pb[2], 1)):
+            i = [rows.add(mb, self_pod=sp, favour=fav, ago=a) for a in AGO_EDGES]
+            z = rows.add(mb, self_pod=sp, favour=fav, last_used=0)
+            if sp == -1:
+                for a, o in ((1, 0), (3, 2), (5, 4), (7, 6)):
+                    rows.pair(i[a], i[o])
+                rows.pair(i[3], z)
+        for a in AGO_EDGES + (-5_000, 0, 10_000):
+            for pk in (0, 1, 2**31, 2**32 - 1):
+                rows.add(mb + 1, ago=a, pick=pk)  # min_load 2^30: 3 * min wraps, the filter stops at one survivor in mid-list
+        for j in range(len(sizes)):  # pick against 2, 3, 63, 64, 65 survivors
+            for pk in (0, 1, 2**31, 2**32 - 1):
+                first = int(pods["lru_time"][rest[0]])
+                rows.add(mb + 2 + j, pick=pk, lru=first, rpm=0)
+                rows.add(mb + 2 + j, pick=pk, lru=first, rpm=500, ago=0)
+                rows.add(mb + 2 + j, self_pod=rest[1], pick=pk, lru=first, rpm=0)
+        rows.add(mb + 2 + len(sizes))
+    if caller:  # one caller, fresh rpm 151: the 5 s clause's limit + 1 at min_load 100; lastUsedAgo varies by request
+        rows.rows, rows.extra, rows.pairs = [], [], []
+        for m in range(len(specs)):
+            i = [rows.add(m, ago=a, pick=pk) for a in AGO_EDGES + (0,) for pk in (0, 2**31, 2**32 - 1)]
+            z = rows.add(m, last_used=0)
+            if m == 0 or (typed and m == len(head)):
+                rows.pair(i[3 * 3], i[2 * 3])
+                rows.pair(i[3 * 3], z)
+        cur = pods[far]
+        _one_caller(rows, far, lru=lru_of(0), capacity=cur["capacity"], used=cur["used"], count=cur["count"], rpm=151)
+    return fleet, ids, rows
+
+
+def _order_case(P, seed, after=False, caller=False):
+    """PLACEMENT_ORDER's own thresholds (:4649-4701): instances that differ in one key, down to the id; two versions, every full
+    instance of which is older than 2 * minChurnAge (the comparator's precondition).  after: the same table with a few rows moved
+    across a threshold — what a delta commit re-ranks by insertion.  The counts are laid out per (version, full) band — version 8
+    not full 0 ... 19, full 20; version 7 not full 30 ... 49, full 100 — so that they do not decrease along the order: the device
+    records its per-type shortlists at commit only for such a table, and the delta commit must rebuild them.  caller: the
+    requests are one instance's batch."""
+    fleet, rng = _edge_fleet(P, seed)
+    now, pods, msu, mc = fleet.now, fleet.pods, fleet.min_space_units, fleet.min_churn_age_ms
+    perm = [int(p) for p in rng.permutation(P)]
+    pods["version"] = np.where(rng.random(P) < 0.5, 8, 7)
+    pods["count"] = 1 + pods["count"] % 19  # the band's offset is added below
+    it = iter(perm)
+
+    def put(**kw):
+        p = next(it)
+        pods["capacity"][p], pods["used"][p], pods["count"][p], pods["lru_time"][p] = 1_000_000, 600_000, 12, now - 2_000_000
+        pods["loading_threads"][p], pods["loading_in_progress"][p], pods["rpm"][p], pods["version"][p] = 8, 1, 50, 7
+        for k, v in kw.items():
+            pods[k][p] = v
+        return p
+    eng = []
+    for v in (7, 8):
+        eng += [put(version=v, used=1_000_000 - msu), put(version=v, used=1_000_000 - msu + 1), put(version=v, used=1_000_000 - msu - 1)]
+        eng += [put(version=v, used=1_000_000 - msu + 1, lru_time=2 * mc + 1), put(version=v, used=1_000_000 - msu, lru_time=2 * mc),
+                put(version=v, used=1_000_000 - msu, lru_time=2 * mc + 1), put(version=v, used=1_000_007), put(version=v, used=1_000_000, count=0)]
+        eng += [put(version=v) for _ in range(3)]  # equal in every key: the id decides
+        eng += [put(version=v, loading_threads=INT_MAX, loading_in_progress=-1), put(version=v, loading_threads=INT_MIN, loading_in_progress=1),
+                put(version=v, loading_threads=0, loading_in_progress=0), put(version=v, loading_threads=INT_MIN + 5, loading_in_progress=INT_MIN),
+                put(version=v, loading_threads=INT_MIN + 4, loading_in_progress=INT_MAX)]
+        eng += [put(version=v, loading_threads=7, loading_in_progress=0, rpm=r) for r in (INT_MIN, -1, 0, INT_MAX)]
+        eng += [put(version=v, capacity=1_000_001, used=600_001), put(version=v, count=11), put(version=v, count=13),
+                put(version=v, lru_time=now - 2_000_001)]
+    assert len(eng) <= P
+    if after:  # a few rows cross a threshold, take another's place, or swap the key that separated them
+        a, b, c, d, e = eng[0], eng[1], eng[8], eng[11], eng[16]
+        pods["used"][a] += 1
+        pods["used"][b] -= 1
+        pods["rpm"][c] = INT_MAX
+        pods["loading_in_progress"][d] = INT_MAX
+        pods["count"][e] = 0
+        pods["lru_time"][eng[26]] = 2 * mc + 2
+    rem = np.maximum(pods["capacity"] - pods["used"], 0)
+    v7 = pods["version"] == 7
+    pods["count"] = np.where(rem < msu, np.where(v7, 100, 20), pods["count"] + np.where(v7, 30, 0))
+    ids = string_ids(fleet, 460 + seed)
+    specs = []
+    for _ in range(40):
+        k, f = int(rng.integers(0, 4)), int(rng.integers(0, 3))
+        ps = rng.choice(P, size=k + f, replace=False)
+        specs.append((0, list(ps[:k]), list(ps[k:])))
+    specs.append((0, perm[:P // 2], perm[P // 2:]))  # every instance holds or failed it
+    _set_models(fleet, specs)
+    rows = _PlaceRows(fleet, seed)
+    for m in range(len(specs)):
+        for sp in (-1, eng[m % len(eng)], perm[-1 - m % 5]):
+            for fav in (0, 1):
+                rows.add(m, self_pod=sp, favour=fav, ago=[0, 100_000_000][m % 2])
+    if caller:  # one caller, not in any list's way; its fresh row has room before the rows move and min_space - 1 after: either recorded list
+        _one_caller(rows, perm[-1], lru=now - 2_000_000, capacity=1_000_000, used=1_000_000 - msu + 1 if after else 600_000, count=12, rpm=50)
+    return fleet, ids, rows
+
+
+def _place_edge_cases():
+    """(name, fleet, ids, _PlaceRows, caller, after)"""
+    yield ("edge_breaks_full8",) + _breaks_full_case(8, 1, False, future=True) + (False, None)
+    yield ("edge_breaks_full65",) + _breaks_full_case(65, 2, True, zero_oldest=True) + (False, None)
+    yield ("edge_breaks_full200c",) + _breaks_full_case(200, 3, True, caller=True) + (True, None)
+    yield ("edge_breaks_full700",) + _breaks_full_case(700, 4, True) + (False, None)
+    yield ("edge_breaks_mixed200",) + _breaks_full_case(200, 11, True, mixed=True) + (False, None)
+    yield ("edge_breaks_open64",) + _breaks_open_case(64, 5, False) + (False, None)
+    yield ("edge_breaks_open200",) + _breaks_open_case(200, 6, True) + (False, None)
+    yield ("edge_breaks_open65c",) + _breaks_open_case(65, 7, True, caller=True) + (True, None)
+    yield ("edge_rpm_64",) + _rpm_case(64, 8, False) + (False, None)
+    yield ("edge_rpm_200",) + _rpm_case(200, 9, True) + (False, None)
+    yield ("edge_rpm_65c",) + _rpm_case(65, 10, True, caller=True) + (True, None)
+    for P, seed, c in ((65, 12, True), (200, 14, False)):
+        tag = f"{P}c" if c else f"{P}"
+        yield (f"edge_order_{tag}",) + _order_case(P, seed, caller=c) + (c, f"edge_order_{tag}after")
+        yield (f"edge_order_{tag}after",) + _order_case(P, seed, after=True, caller=c) + (c, None)
+
+
+@functools.lru_cache(maxsize=None)
+def _place_edge_all():
+    """{name: (fleet, ids, reqs, extra, meta)}, built once; the consumers do not write into it."""
+    out = {}
+    for name, fleet, ids, rows, caller, after in _place_edge_cases():
+        reqs, extra = rows.done()
+        out[name] = (fleet, ids, reqs, extra, dict(pairs=list(rows.pairs), caller=caller, after=after))
+    return out
+
+
+def place_edge_cases():
+    """(name, fleet, ids, reqs, extra) like place_cases, at the EDGES of getNext's value domain (MM.java:4777-5003); name =
+    edge_<tier>_<case>.  breaks: the shortlist's break thresholds one unit inside, on and outside, best full and not full, through the
+    caller's fresh row and through the table's rows.  rpm: the filter's age classes, its limits (wrapping and saturating ones
+    included), the stop at one survivor, the pick.  order: PLACEMENT_ORDER's thresholds, each table once more after a few rows moved."""
+    for name, (fleet, ids, reqs, extra, _) in _place_edge_all().items():
+        yield name, fleet, ids, reqs, extra
+
+
 def _rebalance_fleet(seed, pods, models, used):
     """Fleet where many models have 1-4 copies, often including self_pod = 0 (as tests/test_rebalance_gpu.py builds it)."""
     rng = np.random.default_rng(8000 + seed)
@@ -1348,3 +1903,55 @@ def input_blob(fleet, ids, reqs=None, extra=None, serve=None, gates=None, scaleu
 
 def digest(blob: bytes) -> str:
     return hashlib.sha256(blob).hexdigest()[:16]
+
+
+def place_row_kinds(fleet, order, reqs, extra):
+    """Per load-target request, from the inputs and the reference's instance order alone: (kind, full) with kind one of 'none',
+    'simple', 'a found', 'a replay', 'b found', 'b replay' (MM.java:4822-4887) and full = isFull(best) as :4811 takes it."""
+    P, T = fleet.n_pods, fleet.n_types
+    al = [None] * max(T, 1)
+    pf = [None] * max(T, 1)
+    for t in range(T):
+        bits = lambda bm: set(int(p) for p in range(P) if (int(bm[t][p >> 6]) >> (p & 63)) & 1)  # noqa: E731
+        al[t] = bits(fleet.allowed) if fleet.has_allowed[t] else None
+        pf[t] = bits(fleet.prefer) if fleet.has_prefer[t] else None
+    live = (fleet.pods["flags"] & 2) != 0
+    rem = np.maximum(fleet.pods["capacity"] - fleet.pods["used"], 0)
+    out = []
+    for q in reqs:
+        m = fleet.models[q["model"]]
+        t = int(m["type"]) if T else 0
+        ex = set(int(p) for p in fleet.ent_pod[m["ent_off"]: m["ent_off"] + m["n_loaded"] + m["n_failed"]])
+        ex |= set(int(p) for p in extra[q["extra_off"]: q["extra_off"] + q["n_extra"]])
+        el = [int(p) for p in order if live[p] and p not in ex and (al[t] is None or p in al[t])]
+        if not el:
+            out.append(("none", False))
+            continue
+        b = el[0]
+        us = b == q["self_pod"]
+        b_rem = max(int(q["fresh_capacity"]) - int(q["fresh_used"]), 0) if us else int(rem[b])
+        b_lru = int(q["fresh_lru"]) if us else int(fleet.pods["lru_time"][b])
+        full = b_rem < fleet.min_space_units
+        if pf[t] is None or b in pf[t]:
+            out.append(("simple", full))
+        elif not full:
+            kind = "a replay"
+            for p in el[1:]:
+                if p in pf[t]:
+                    kind = "a found"
+                    break
+                if rem[p] < fleet.min_space_units:
+                    break
+            out.append((kind, full))
+        else:
+            kind = "b replay"
+            quarter = _tdiv(_age(fleet.now, b_lru), 4)
+            for p in el[1:]:
+                d = int(fleet.pods["lru_time"][p]) - b_lru
+                if d > 120_000 and d > quarter:
+                    break
+                if p in pf[t]:
+                    kind = "b found"
+                    break
+            out.append((kind, full))
+    return out
