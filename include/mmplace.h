@@ -1415,6 +1415,80 @@ int mmp_models_rewrite_json(mmp_ctx *ctx, const int32_t *rows, int32_t n, const 
                             const int64_t *last_unload, const int32_t *fail_pod, const char *fail_msg, const int32_t *fail_msg_off,
                             uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off, int32_t *status_out,
                             int64_t *n_bytes_out);
+/* ---- registerModel / deleteModel (register_kernels.hpp) ------------------------------------------------------------------------------
+ * The management API's own registry writers: registerModel's touch of an existing record (ModelMesh.java:3120-3127), its creation of
+ * a new one (:3135-3142) and deleteModel's conditionalDelete (:3181-3203).  A batch of such questions; each answer is a pure function
+ * of the request, the stored value the host's listener holds for that key, now_ms and lastused_age_on_add_ms
+ * (LASTUSED_AGE_ON_ADD_MS).  The host parses no stored value and serialises no ModelRecord; the compare-and-set itself, its retry
+ * loop (call again with the value the store answered) and readOnlyMode stay in Java.
+ *
+ * Request i: reqs[i]; its type, encKey and mPath are the spans 3i, 3i + 1, 3i + 2 of info / info_off (3n + 1 offsets).  An EMPTY
+ * encKey or mPath span is null — the Java maps "" to null before it compares (:3094-3095); an empty type span on a request that is
+ * not a delete is MMP_EINVAL.  The stored value is old_buf[old_off[i], old_off[i+1]); an EMPTY span is registry.get() == null.  A
+ * delete reads nothing of its three strings and its timestamp.
+ *
+ * last_used_out[i] = lastUsedTimestamp of :3098-3101,
+ *     ts = ict >= now ? now : (ict > 0 ? ict : now - age * (loadNow ? 1 : 6))
+ * in Java long arithmetic (the product and the difference wrap); 0 for a delete.  The host passes it on to ensureLoaded (:3158).
+ *
+ * The stored value is read as the parser reads it: the top-level member walk, names matched as raw bytes, a later duplicate wins.
+ *     type            a string; absent or null reads as "NLCLASSIFIER" (ModelRecord.java:122)
+ *     encKey, mPath   a string, or null / absent
+ *     lu              long, absent = 0 (the parser's own reading)        refs   int, absent = 0
+ *
+ * class_out[i], in this order of precedence:
+ *   register or delete, old span empty    MMP_MREG_CREATED with the value below / MMP_MREG_ABSENT (:3187, fine if not found)
+ *   MMP_MREG_MALFORMED   exactly where mmp_models_upsert_json gives status 1 for the old value as a non-deleted event (the parser
+ *                        itself runs over the old values first, as in mmp_models_rewrite_json)
+ *   MMP_MREG_HOST        the value is well-formed but the device will not decide it, the host decides this one: the deciding
+ *                        (last) occurrence of a member the request compares — type, encKey, mPath for a register, refs for a
+ *                        delete — is a type / encKey / mPath string that holds a backslash, a type / encKey / mPath that is
+ *                        neither a string nor null, or a refs that is not an integer in int32
+ *   delete               refs > 0: MMP_MREG_REFERENCED (:3188-3191); otherwise MMP_MREG_DELETABLE: the host issues
+ *                        conditionalDelete with the old value (:3198)
+ *   MMP_MREG_CONFLICT    register, any of the three attributes unequal (:3111-3118): raw bytes of the escape-free stored string
+ *                        against the request's bytes, null against null; a stored "" does not equal the request's null
+ *   MMP_MREG_TOUCHED     register, attributes equal, !loadNow && ts > lu + age (the sum wraps as in Java), :3120.  The value is
+ *                        every top-level member of the old value whose name is not lu, verbatim and in document order as
+ *                        mmp_models_rewrite_json keeps members, then "lu":<lu'>, omitted at 0, with lu' = updateLastUsed(ts)
+ *                        (ModelRecord.java:239-246): a ts of 0 means now_ms, and the value is only raised.  The class is TOUCHED
+ *                        and a value is rendered even when lu' == lu: the Java submits the record all the same
+ *   MMP_MREG_EXISTS      register otherwise: no compare-and-set, weCreated = false (:3129)
+ * The CREATED value is {"type":"<t>","encKey":"<k>","mPath":"<p>","lu":<ts>}, each of the last three omitted at null / 0, the
+ * strings escaped by the rule of mmp_models_rewrite_json ('"' and '\' behind a backslash, a byte below 0x20 as \u00xx, everything
+ * else verbatim).  Every class but CREATED and TOUCHED has length 0.
+ *
+ * model_idx_out (may be NULL): the row of key i = keys[key_off[i], key_off[i+1]) in the resident model-id table, -1 for an unknown
+ * id, from the stage mmp_model_ids_resolve uses — the host goes straight on to mmp_models_status / mmp_place_batch_c.  MMP_ESTATE
+ * under that call's conditions.  With model_idx_out == NULL, keys / key_off may be NULL and no id table is needed.
+ *
+ * Output and sizing as mmp_models_rewrite_json: value i = out_buf[out_off[i], out_off[i+1]); out_off (n + 1 words), class_out,
+ * last_used_out, model_idx_out and *n_bytes_out are always complete; NO byte of out_buf is written when out_buf is NULL or out_cap
+ * is smaller than the total, and the call still returns MMP_OK.  Read-only: no commit, locking as mmp_models_status without a
+ * fail_pod.  n == 0 is valid.  MMP_EINVAL with nothing written: a NULL required buffer, non-monotone offsets of any of the three
+ * kinds, unknown request flag bits or a non-zero reserved word, flags != 0, now_ms <= 0, lastused_age_on_add_ms < 0, an empty type
+ * on a register.  MMP_ESTATE before mmp_pod_ids_load (the parser's condition).  Two runs over the same state are byte-identical. */
+typedef struct {
+    uint32_t flags;
+    int32_t reserved;
+    int64_t initial_cache_timestamp; /* 0: not specified */
+} mmp_register_req;             /* 16 bytes */
+#define MMP_MREG_LOAD_NOW 1u    /* registerModel(loadNow = true) */
+#define MMP_MREG_DELETE 2u      /* deleteModel: the three strings and the timestamp are ignored */
+/* class_out */
+#define MMP_MREG_CREATED 0      /* no stored value: the new record is rendered */
+#define MMP_MREG_TOUCHED 1      /* the same model, lu raised: the next value is rendered */
+#define MMP_MREG_EXISTS 2       /* the same model, nothing to write */
+#define MMP_MREG_CONFLICT 3     /* "Model already exists with different attribute values" */
+#define MMP_MREG_ABSENT 4       /* delete of a model that is not there */
+#define MMP_MREG_REFERENCED 5   /* delete refused: the model has referents */
+#define MMP_MREG_DELETABLE 6    /* delete: conditionalDelete with the old value */
+#define MMP_MREG_MALFORMED 7    /* the old value is malformed */
+#define MMP_MREG_HOST 8         /* well-formed, but the host decides this one */
+int mmp_models_register_json(mmp_ctx *ctx, const mmp_register_req *reqs, int32_t n, const char *keys, const int32_t *key_off,
+                             const char *info, const int32_t *info_off, const char *old_buf, const int64_t *old_off, int64_t now_ms,
+                             int64_t lastused_age_on_add_ms, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off,
+                             int32_t *class_out, int64_t *last_used_out, int32_t *model_idx_out, int64_t *n_bytes_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

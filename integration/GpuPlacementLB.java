@@ -225,6 +225,18 @@ final class MmPlace {
     static native int modelsRewriteJson(long h, ByteBuffer rows, int n, ByteBuffer oldJson, ByteBuffer oldOff, ByteBuffer lastUnload,
                                         ByteBuffer failPod, ByteBuffer failMsg, ByteBuffer failMsgOff, int flags, ByteBuffer outBuf,
                                         long outCap, ByteBuffer outOff, ByteBuffer statusOut, ByteBuffer nBytesOut);
+    /** registerModel / deleteModel (ModelMesh.java:3088-3147, :3181-3203) as a batch of questions (mmp_models_register_json):
+     *  request i = reqs[i] (16 bytes: int flags 1 = loadNow / 2 = delete, int reserved, long initialCacheTimestamp), its type, encKey
+     *  and mPath the spans 3i .. 3i + 2 of info / infoOff (an empty encKey / mPath span is null), and the stored value
+     *  oldJson[oldOff[i], oldOff[i+1]) the registry listener holds for that id (empty: registry.get() == null).  classOut 0 created /
+     *  1 touched (both: the value to conditionalSet is outBuf[outOff[i], outOff[i+1])) / 2 exists / 3 different attributes / 4 absent /
+     *  5 has referents / 6 conditionalDelete the old value / 7 malformed / 8 the host decides; lastUsedOut = lastUsedTimestamp of
+     *  :3098-3101.  modelIdxOut (may be null, then keys / keyOff too) = the row of each id, -1 unknown.  Sizing as modelsRewriteJson:
+     *  nothing is written to outBuf when it is null or outCap is smaller than nBytesOut.  flags 0. */
+    static native int modelsRegisterJson(long h, ByteBuffer reqs, int n, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer info,
+                                         ByteBuffer infoOff, ByteBuffer oldJson, ByteBuffer oldOff, long nowMs, long lastUsedAgeOnAddMs,
+                                         int flags, ByteBuffer outBuf, long outCap, ByteBuffer outOff, ByteBuffer classOut,
+                                         ByteBuffer lastUsedOut, ByteBuffer modelIdxOut, ByteBuffer nBytesOut);
     /** hand registry rows back (mmp_models_retire): rows = n ints, the rows whose deletion the listener has seen; flags 1 = every
      *  named row must still be the empty row a deletion leaves (else MMP_EINVAL, nothing changed: the id was registered again).
      *  The survivors move down in order; remapOut (maxModels >= the row count at the call, may be null) gives old row -> new row,

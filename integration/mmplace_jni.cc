@@ -803,6 +803,39 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRewriteJson(J
                                          buf<int64_t>(env, outOff), buf<int32_t>(env, statusOut), buf<int64_t>(env, nBytesOut)));
 }
 
+// registerModel / deleteModel as a batch of questions about the stored values (see mmp_models_register_json): reqs = n
+// mmp_register_req, infoOff 3n + 1 ints, keys / keyOff / modelIdxOut may be null all three.  The capacities are checked here.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRegisterJson(JNIEnv *env, jclass, jlong h, jobject reqs, jint n,
+                                                                                jobject keys, jobject keyOff, jobject info,
+                                                                                jobject infoOff, jobject oldJson, jobject oldOff,
+                                                                                jlong nowMs, jlong lastUsedAgeOnAddMs, jint flags,
+                                                                                jobject outBuf, jlong outCap, jobject outOff,
+                                                                                jobject classOut, jobject lastUsedOut,
+                                                                                jobject modelIdxOut, jobject nBytesOut)
+{
+    if (n < 0 || n > INT32_MAX / 3 - 1 || outCap < 0 ||
+        !holds<mmp_register_req>(env, reqs, n, "modelsRegisterJson: reqs shorter than n") ||
+        !holds<int32_t>(env, infoOff, 3 * (jlong)n + 1, "modelsRegisterJson: infoOff shorter than 3n + 1") ||
+        !holds<int64_t>(env, oldOff, (jlong)n + 1, "modelsRegisterJson: oldOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, info, buf<int32_t>(env, infoOff)[3 * n], "modelsRegisterJson: info shorter than infoOff[3n]")) ||
+        (n > 0 && !holds<char>(env, oldJson, buf<int64_t>(env, oldOff)[n], "modelsRegisterJson: oldJson shorter than oldOff[n]")) ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "modelsRegisterJson: modelIdxOut shorter than n")) ||
+        (modelIdxOut && !holds<int32_t>(env, keyOff, (jlong)n + 1, "modelsRegisterJson: keyOff shorter than n + 1")) ||
+        (modelIdxOut && n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "modelsRegisterJson: keys shorter than keyOff[n]")) ||
+        (outBuf && !holds<char>(env, outBuf, outCap, "modelsRegisterJson: outBuf shorter than outCap")) ||
+        !holds<int64_t>(env, outOff, (jlong)n + 1, "modelsRegisterJson: outOff shorter than n + 1") ||
+        !holds<int32_t>(env, classOut, n, "modelsRegisterJson: classOut shorter than n") ||
+        !holds<int64_t>(env, lastUsedOut, n, "modelsRegisterJson: lastUsedOut shorter than n") ||
+        !holds<int64_t>(env, nBytesOut, 1, "modelsRegisterJson: nBytesOut shorter than one long"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_register_json(ctx_of(h), buf<mmp_register_req>(env, reqs), n, buf<char>(env, keys), buf<int32_t>(env, keyOff),
+                                          buf<char>(env, info), buf<int32_t>(env, infoOff), buf<char>(env, oldJson),
+                                          buf<int64_t>(env, oldOff), nowMs, lastUsedAgeOnAddMs, static_cast<uint32_t>(flags),
+                                          buf<char>(env, outBuf), outCap, buf<int64_t>(env, outOff), buf<int32_t>(env, classOut),
+                                          buf<int64_t>(env, lastUsedOut), buf<int32_t>(env, modelIdxOut), buf<int64_t>(env, nBytesOut)));
+}
+
 // rows: n ints; remapOut (may be null) holds maxModels ints, nModelsAfterOut (may be null) one (see mmp_models_retire)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRetire(JNIEnv *env, jclass, jlong h, jobject rows, jint n, jint flags,
                                                                           jobject remapOut, jint maxModels, jobject nModelsAfterOut)

@@ -188,6 +188,12 @@ PEV_APPLIED, PEV_MALFORMED, PEV_UNKNOWN = 0, 1, 2  # status_out
 MEV_APPEND = 1
 # mmp_models_rewrite_json (the write side of the wire format): status_out
 MRW_OK, MRW_MALFORMED, MRW_HOST = 0, 1, 2
+# mmp_models_register_json (registerModel / deleteModel): request flags, class_out
+REGISTER_REQ = np.dtype([("flags", "<u4"), ("reserved", "<i4"), ("initial_cache_timestamp", "<i8")])
+assert REGISTER_REQ.itemsize == 16
+MREG_LOAD_NOW, MREG_DELETE = 1, 2
+(MREG_CREATED, MREG_TOUCHED, MREG_EXISTS, MREG_CONFLICT, MREG_ABSENT, MREG_REFERENCED, MREG_DELETABLE, MREG_MALFORMED,
+ MREG_HOST) = range(9)
 # mmp_models_retire: every named row must be the empty row a deletion leaves
 RETIRE_EMPTY_ONLY = 1
 # mmp_pods_retire: every named row must be a tombstone / no referenced registry entry may name a retired instance
@@ -332,6 +338,8 @@ SYMBOLS = [
     ("mmp_pods_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("mmp_models_rewrite_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_int64, _P, _P,
                                           C.POINTER(C.c_int64)]),
+    ("mmp_models_register_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int64,
+                                           _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -46,6 +46,7 @@
 #include "model_ids_kernels.hpp"
 #include "pods_retire_kernels.hpp"
 #include "rewrite_kernels.hpp"
+#include "register_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -515,6 +516,9 @@ struct mmp_ctx {
     // call's rows, last_unload, fail_pod, messages and their offsets, sizes, offsets, statuses and rendered bytes.  Owned by
     // batch_mu, used on c->stream; the parser's scratch is the j_* of the registry event calls.
     DevBuf idd_bytes, idd_off, rw_rows, rw_lul, rw_fpod, rw_fmsg, rw_fmoff, rw_len, rw_off, rw_status, rw_out;
+    // mmp_models_register_json (register_kernels.hpp): one call's requests, their three strings and offsets, classes and
+    // last_used; sizes, offsets and rendered bytes are rw_len / rw_off / rw_out.  Owned by batch_mu, used on c->stream.
+    DevBuf rg_reqs, rg_info, rg_ioff, rg_cls, rg_lu;
     uint64_t id_gen = 1, idd_gen = 0;
 };
 
@@ -1391,7 +1395,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
-                      &c->rw_off, &c->rw_status, &c->rw_out,
+                      &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu,
                       &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
@@ -6694,6 +6698,128 @@ try {
     *n_bytes_out = total;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_models_rewrite_json")
+
+int mmp_models_register_json(mmp_ctx *c, const mmp_register_req *reqs, int32_t n, const char *keys, const int32_t *key_off,
+                             const char *info, const int32_t *info_off, const char *old_buf, const int64_t *old_off, int64_t now_ms,
+                             int64_t lastused_age_on_add_ms, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off,
+                             int32_t *class_out, int64_t *last_used_out, int32_t *model_idx_out, int64_t *n_bytes_out)
+try {
+    const char *fn = "mmp_models_register_json";
+    if (!c || n < 0 || n > INT32_MAX / 3 - 1 || flags || out_cap < 0 || !out_off || !n_bytes_out ||
+        (n > 0 && (!reqs || !info_off || !old_off || !class_out || !last_used_out || (model_idx_out && !key_off))))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (now_ms <= 0 || lastused_age_on_add_ms < 0)
+        return fail(c, MMP_EINVAL, "%s: now_ms = %lld, lastused_age_on_add_ms = %lld", fn, (long long)now_ms, (long long)lastused_age_on_add_ms);
+    // read-only: the locking of mmp_models_status without a fail_pod (batch_mu owns the stream, the scratch, and the writers of the
+    // id tables the two by-key stages read)
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "%s: load the instance ids first (mmp_pod_ids_load)", fn);
+    if (model_idx_out)
+        if (const int rc = model_id_space_guard(c, fn)) return rc;
+    // every refusal stands before anything is staged or written: the three kinds of offsets, then the requests
+    if (const int rc = check_offsets(c, fn, "", old_off, n)) return rc;
+    if (const int rc = check_offsets(c, fn, "info ", info_off, 3 * n)) return rc;
+    if (model_idx_out)
+        if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_register_req &q = reqs[i];
+        if ((q.flags & ~(MMP_MREG_LOAD_NOW | MMP_MREG_DELETE)) || q.reserved)
+            return fail(c, MMP_EINVAL, "%s: request %d has flags %u, reserved %d", fn, i, q.flags, q.reserved);
+        if (!(q.flags & MMP_MREG_DELETE) && info_off[3 * i + 1] == info_off[3 * i])
+            return fail(c, MMP_EINVAL, "%s: request %d registers an empty type", fn, i);
+        if (old_off[i + 1] - old_off[i] >= INT32_MAX) return fail(c, MMP_EINVAL, "%s: value %d holds 2^31 bytes or more", fn, i);
+    }
+    if (n > 0 && ((old_off[n] > old_off[0] && !old_buf) || (info_off[3 * n] > info_off[0] && !info) ||
+                  (model_idx_out && key_off[n] > key_off[0] && !keys)))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (n == 0) {
+        out_off[0] = 0;
+        *n_bytes_out = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // stage_strings, three times: the stored values where the parser reads them, the requests' strings, the keys where the by-key
+    // stage reads them
+    std::vector<int64_t> rel;
+    std::vector<int32_t> irel, krel;
+    if (const int rc = stage_strings(c, fn, "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
+    if (const int rc = stage_strings(c, fn, "info ", info, info_off, 3 * n, c->rg_info, c->rg_ioff, irel)) return rc;
+    if (model_idx_out) {
+        if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+        HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
+        HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    }
+    // the parser's verdict on each stored value as a non-deleted event, and the lu it read (rows and entries into scratch)
+    IngestModelsArgs J;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+    J.rows = c->j_rows.as<mmp_model_row>();
+    HIP_TRY(c, c->rg_reqs.ensure((size_t)n * sizeof(mmp_register_req)));
+    HIP_TRY(c, hipMemcpyAsync(c->rg_reqs.p, reqs, (size_t)n * sizeof(mmp_register_req), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, c->rg_cls.ensure((size_t)n * 4));
+    HIP_TRY(c, c->rg_lu.ensure((size_t)n * 8));
+    HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
+    int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
+    RegisterArgs A{};
+    A.buf = J.buf;
+    A.off = J.off;
+    A.n = n;
+    A.reqs = c->rg_reqs.as<mmp_register_req>();
+    A.info = c->rg_info.as<char>();
+    A.info_off = c->rg_ioff.as<int32_t>();
+    A.pstatus = J.status;
+    A.prow = J.rows;
+    A.now = now_ms;
+    A.age = lastused_age_on_add_ms;
+    A.len = d_len;
+    A.out_off = d_off;
+    A.cls = c->rg_cls.as<int32_t>();
+    A.last_used = c->rg_lu.as<int64_t>();
+    // the by-key stage, the parser, the size pass, the scan of the sizes, and the one read-back that decides whether anything is written
+    KT_BEGIN(c, st);
+    if (model_idx_out)
+        mid_resolve_launch(c, n, ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
+                                            c->mid_off.as<int32_t>()});
+    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
+    hipLaunchKernelGGL(models_register_kernel<false>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int64_t> h_off((size_t)n + 1), h_lu(n);
+    std::vector<int32_t> h_cls(n), h_idx(model_idx_out ? n : 0);
+    HIP_TRY(c, hipMemcpyAsync(h_off.data(), d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h_cls.data(), c->rg_cls.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h_lu.data(), c->rg_lu.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (model_idx_out) HIP_TRY(c, hipMemcpyAsync(h_idx.data(), c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const double size_ms = c->last_kernel_ms;
+    const int64_t total = h_off[n];
+    if (out_buf && out_cap >= total && total > 0) {
+        HIP_TRY(c, c->rw_out.ensure((size_t)total));
+        A.out = c->rw_out.as<char>();
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(models_register_kernel<true>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, copy_sync(c, out_buf, c->rw_out.p, (size_t)total, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        kt_add(c, size_ms);  // the call's device span: size + write
+    }
+    memcpy(out_off, h_off.data(), (size_t)(n + 1) * 8);
+    memcpy(class_out, h_cls.data(), (size_t)n * 4);
+    memcpy(last_used_out, h_lu.data(), (size_t)n * 8);
+    if (model_idx_out) memcpy(model_idx_out, h_idx.data(), (size_t)n * 4);
+    *n_bytes_out = total;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_models_register_json")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

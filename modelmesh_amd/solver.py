@@ -354,6 +354,52 @@ class Solver:
                                               C.byref(total))
         return out[:int(out_cap)], out_off, status[:n], total.value, rc
 
+    def models_register_json(self, reqs, infos, old_values, now_ms, lastused_age_on_add_ms, keys=None):
+        """registerModel / deleteModel as a batch of questions (mmp_models_register_json): reqs is a REGISTER_REQ array, infos[i] =
+        (type, encKey, mPath) as bytes/str with "" or None for null, old_values[i] the stored value (empty: registry.get() == null),
+        keys the model ids (None: no rows are asked for).  Returns (values, classes, last_used, rows): values[i] is bytes where
+        classes[i] is MREG_CREATED / MREG_TOUCHED and None elsewhere, rows is None without keys.  Two calls: the sizes, then the
+        bytes."""
+        args = (reqs, infos, old_values, now_ms, lastused_age_on_add_ms, keys)
+        r = self.models_register_json_raw(*args, 0)
+        self._ck(r[6])
+        out, off, cls, lu, rows, total, rc = self.models_register_json_raw(*args, r[5])
+        self._ck(rc)
+        assert total == r[5]  # (a pure function of the arguments, and of the id table for the rows)
+        rendered = (_lib.MREG_CREATED, _lib.MREG_TOUCHED)
+        vals = [bytes(out[off[i]:off[i + 1]]) if cls[i] in rendered else None for i in range(len(cls))]
+        return vals, cls, lu, rows
+
+    def models_register_json_raw(self, reqs, infos, old_values, now_ms, lastused_age_on_add_ms, keys, out_cap, fill=0, null_out=False,
+                                 flags=0, old_off=None, info_off=None, key_off=None):
+        """One mmp_models_register_json call with exactly this capacity (null_out: a NULL out_buf), the outputs filled with the byte
+        `fill` first: (out bytes as uint8[out_cap], out_off[n + 1], classes[n], last_used[n], rows[n] or None, total, rc); total is
+        -1 where the library did not set it.  old_off / info_off / key_off: these offsets instead of the packed ones."""
+        reqs = np.ascontiguousarray(reqs, dtype=_lib.REGISTER_REQ)
+        n = len(reqs)
+        assert len(infos) == n and len(old_values) == n and (keys is None or len(keys) == n)
+        iblob, ioff = self._pack([x if x is not None else b"" for t in infos for x in t])
+        ioff = ioff.astype(np.int32) if info_off is None else np.ascontiguousarray(info_off, dtype=np.int32)
+        blob, off = self._pack(old_values)
+        if old_off is not None:
+            off = np.ascontiguousarray(old_off, dtype=np.int64)
+        kblob = koff = rows = None
+        if keys is not None:
+            kblob, koff64 = self._pack(keys)
+            koff = koff64.astype(np.int32) if key_off is None else np.ascontiguousarray(key_off, dtype=np.int32)
+            rows = np.zeros(max(n, 1), np.int32)
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        out_off = np.zeros(n + 1, np.int64)
+        cls = np.zeros(max(n, 1), np.int32)
+        lu = np.zeros(max(n, 1), np.int64)
+        for a in (out, out_off, cls, lu) + (() if rows is None else (rows,)):
+            a.view(np.uint8)[:] = fill
+        total = C.c_int64(-1)
+        rc = self.lib.mmp_models_register_json(self.h, ptr(reqs), n, kblob, ptr(koff), iblob, ptr(ioff), blob, ptr(off), int(now_ms),
+                                               int(lastused_age_on_add_ms), flags, None if null_out else ptr(out), int(out_cap),
+                                               ptr(out_off), ptr(cls), ptr(lu), ptr(rows), C.byref(total))
+        return out[:int(out_cap)], out_off, cls[:n], lu[:n], None if rows is None else rows[:n], total.value, rc
+
     def model_ids_load(self, ids):
         """Name the registry's rows (mmp_model_ids_load): ids[i] (bytes/str) is the id of row i; len(ids) must equal the row count."""
         blob, off = self._pack(ids)
