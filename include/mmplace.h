@@ -1489,6 +1489,152 @@ int mmp_models_register_json(mmp_ctx *ctx, const mmp_register_req *reqs, int32_t
                              const char *info, const int32_t *info_off, const char *old_buf, const int64_t *old_off, int64_t now_ms,
                              int64_t lastused_age_on_add_ms, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off,
                              int32_t *class_out, int64_t *last_used_out, int32_t *model_idx_out, int64_t *n_bytes_out);
+/* ---- the vmodel table on the device (vmodel_kernels.hpp) ------------------------------------------------------------------------
+ * VModelManager.java:101-110 watches a second table: vmodel id -> VModelRecord {o, amid, tmid, failed} (VModelRecord.java:26-41).
+ * The context keeps it on the device like the registry: an id -> row map with the open addressing of the model-id table (a slot is
+ * matched on the 64-bit FNV-1a hash AND the bytes, ids that collide coexist, a slot is never deleted in place) and one row per
+ * vmodel holding the raw bytes of amid, tmid and o in a string arena, the model-id hashes of amid and tmid, and the MMP_VMF_* flags.
+ * NO registry row is stored in a vmodel row: amid and tmid are looked up in the model-id table when a question is asked, so a model
+ * that joins later, or one mmp_models_retire renumbered, is found without any vmodel call in between.  The state exists only once
+ * the first vmodel call has been made; the table starts empty at mmp_create, and start-up is one mmp_vmodels_events_json batch
+ * with MMP_VMEV_APPEND — there is no separate load call.  The string arena grows by append: an applied event leaves its
+ * predecessor's strings as garbage, which is squeezed out when it exceeds the live bytes.
+ * MMP_VMODEL_ID_HASH_BITS=b (read with the other MMP_* switches, per context at mmp_create) masks every vmodel-id hash to its low b
+ * bits, 0: all equal — the diagnostic of MMP_MODEL_ID_HASH_BITS for this table.
+ * Writes stay with the host: updateVModel / deleteVModel are multi-key KV transactions. */
+#define MMP_VMF_FAILED 1u      /* `failed` as stored                                                 */
+#define MMP_VMF_ABSENT 2u      /* never set, or deleted                                              */
+#define MMP_VMF_ACTIVE_NULL 4u /* amid absent or null                                                */
+#define MMP_VMF_TARGET_NULL 8u /* tmid absent or null                                                */
+#define MMP_VMF_OWNER_NULL 16u /* o absent or null                                                   */
+#define MMP_VMF_HOST 32u       /* one of the three strings holds a backslash escape: the host decodes this one record */
+/* The listener's events as it gets them: event i is the vmodel id keys[key_off[i], key_off[i+1]) — the raw bytes of the KV key —
+ * with the VModelRecord value buf[off[i], off[i+1]).  The contract is that of mmp_models_events_json, clause for clause: the keys
+ * are resolved, deduplicated and numbered on the device by the same kernels; deleted[i] != 0 is ENTRY_DELETED: the value is
+ * ignored and the row becomes ABSENT; it KEEPS its id and its number, and an id that is set again gets its old row back.
+ * status_out[i]: 0 applied, 1 malformed value, 2 unknown id (nothing changes; vmodel_idx_out[i] = -1).  An id the table does not
+ * know: with MMP_VMEV_APPEND in flags the distinct unknown ids of NON-DELETED events join as rows V0, V0+1, ... (V0 = the row count
+ * at the call) in order of first appearance, whether or not their values turn out well-formed (a joined row whose events are all
+ * malformed is ABSENT); without the flag such an event is status 2.  A deletion never appends: of an id that is unknown when the
+ * event is reached — the table and the events before it — it is status 2; behind the event that made the id join, it applies.
+ * Events apply in order: a row ends as its LAST WELL-FORMED OR DELETED event left it.
+ * The value: amid, tmid and o are each a string or null, failed is true / false; every occurrence of one of the four is held to
+ * its type, a later duplicate wins (a later null included), any other member is skipped whatever its type (JsonExtensible), and
+ * nothing but blanks may follow the closing brace — the grammar and the verdicts of mmp_models_upsert_json.  A value of 2^30
+ * bytes or more is refused.  The strings are kept as their raw bytes between the quotes; one that holds a backslash flags the row
+ * MMP_VMF_HOST.
+ * vmodel_idx_out[i] = the resolved row; *n_appended_out = ids that joined.  deleted, n_appended_out may be NULL.
+ * Only O(events) words come back to the host; two runs over the same state and events are byte-identical, whichever lanes raced.
+ * MMP_EINVAL with nothing changed (table, id arena, rows, string arena): a NULL required buffer, non-monotone offsets of either
+ * kind, unknown flags, a value of 2^30 bytes or more, more than 2^31 arena bytes.  The call needs neither mmp_model_ids_load nor
+ * mmp_pod_ids_load: the hashes of amid / tmid are computed from the bytes.  Locking: batch_mu for the call, which every
+ * reader of the vmodel state holds too; the id table, and the id arena, string arena and row array where they have to grow, are
+ * built beside the published ones and swapped together with the counts under the state lock; rows of known ids are rewritten
+ * behind the last refusal.  n == 0 is valid. */
+#define MMP_VMEV_APPEND 1u
+int mmp_vmodels_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                            const uint8_t *deleted, uint32_t flags, int32_t *vmodel_idx_out, int32_t *status_out,
+                            int32_t *n_appended_out);
+/* resolveVModelId (VModelManager.java:569-597, from ModelMeshApi.callModel :457-476) and the classes getVModelStatus needs
+ * (:505-528, :537-559), one question per request, one lane per question: key i = keys[key_off[i], key_off[i+1]) is the vmodel id,
+ * nf i = nf_keys[nf_off[i], nf_off[i+1]) the notFoundModelId and owner i = owners[owner_off[i], owner_off[i+1]) the owner; an empty
+ * span is Java null, and nf_keys / nf_off, owners / owner_off and req_flags may each be NULL (all null / 0).  Strings compare on
+ * bytes; a stored null equals nothing (String.equals(null)).
+ * rows_out[i].cls:
+ *   MMP_VMR_NOT_FOUND         the id is unknown or the row is ABSENT (:570-573); also when an owner is given and differs from the
+ *                             stored one byte for byte (absentOrOwnerMismatch, :530-532; a row with OWNER_NULL mismatches any owner)
+ *   MMP_VMR_HOST              the row is flagged MMP_VMF_HOST: the host decodes the record (mmp_vmodels_get) and decides
+ *   MMP_VMR_OK                `which` (MMP_VMW_ACTIVE / MMP_VMW_TARGET) names the id resolveVModelId returns; MMP_VMRF_NULL_ID in
+ *                             flags when that id is null (the Java returns null), model = -1 then
+ *   MMP_VMR_STRONG_READ       nf equals the active id as held (:575 fails): the host performs vModels.getStrong (:582), sends that
+ *                             value through mmp_vmodels_events_json and asks again with MMP_VMRQ_AFTER_STRONG in req_flags[i]
+ *   MMP_VMR_TARGET_NOT_FOUND  with MMP_VMRQ_AFTER_STRONG (:587-596): active if it differs from nf, else target if it differs, else
+ *                             this — the Java throws INTERNAL "Target model ... not found".  An empty nf answers active in
+ *                             either phase
+ * vmodel = the row (-1 for NOT_FOUND); model = the registry row of the answered id in the model-id table, -1 when the table does
+ * not know it (or the class answers none); target_model likewise for tmid; vstatus = MMP_VMS_DEFINED / _TRANSITIONING /
+ * _TRANSITION_FAILED (:555-556; inTransition() is !Objects.equals(amid, tmid) on bytes, null-aware); target_status = 0 when not in
+ * transition, otherwise (:537-549) MMP_VMT_LOADING_FAILED when `failed` is set and the target's resident row has n_failed > 0 and
+ * n_loaded == 0, MMP_VMT_NOT_FOUND when the target's row is unknown or is the empty row, MMP_VMT_LOADING otherwise;
+ * mmp_models_status fills in the rest.  (The Java would throw a NullPointerException at :544 for `failed` with a missing target
+ * record; the device answers MMP_VMT_NOT_FOUND there.)  For NOT_FOUND and HOST every other field is -1 / 0.
+ * Read-only, no commit.  MMP_ESTATE under the conditions of mmp_model_ids_resolve (no model-id table, or the registry resized by
+ * index since).  MMP_EINVAL with nothing written: a NULL required buffer, non-monotone offsets of any of the three kinds, unknown
+ * request flag bits.  Locking as mmp_model_ids_resolve: the model-id table is owned by batch_mu, so the call holds it and is
+ * serialised with the event calls (it sees the state before or after one, never a mix); it does not take the state lock
+ * exclusive, so the request calls go on beside it.  n == 0 is valid.  Two runs over the same state are byte-identical. */
+#define MMP_VMRQ_AFTER_STRONG 1u
+#define MMP_VMR_NOT_FOUND 0
+#define MMP_VMR_OK 1
+#define MMP_VMR_STRONG_READ 2
+#define MMP_VMR_TARGET_NOT_FOUND 3
+#define MMP_VMR_HOST 4
+#define MMP_VMW_ACTIVE 0
+#define MMP_VMW_TARGET 1
+#define MMP_VMRF_NULL_ID 1u
+#define MMP_VMS_DEFINED 0
+#define MMP_VMS_TRANSITIONING 1
+#define MMP_VMS_TRANSITION_FAILED 2
+#define MMP_VMT_NONE 0
+#define MMP_VMT_LOADING 1
+#define MMP_VMT_LOADING_FAILED 2
+#define MMP_VMT_NOT_FOUND 3
+typedef struct {
+    int32_t cls, which;
+    int32_t vmodel, model, target_model;
+    int32_t vstatus, target_status;
+    uint32_t flags;
+} mmp_vmodel_answer; /* 32 bytes */
+int mmp_vmodels_resolve(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, const char *nf_keys, const int32_t *nf_off,
+                        const char *owners, const int32_t *owner_off, const uint32_t *req_flags, mmp_vmodel_answer *rows_out);
+/* The leader's transition pass: processVModels (:617-634), the filter of processVModel (:639-643) and the prologue of
+ * PendingTransition.run (:701-708) as one scan over all rows in row order.  Listed: every row that is not ABSENT, not HOST and
+ * in transition.  Per listed row: vmodel; from_model / to_model = the registry rows of amid / tmid, -1 for null or unknown;
+ * target_count = curActive.getInstanceIds().size() — the resident row's n_loaded, unresolved entries included, 0 when from_model
+ * is -1; cls = MMP_VMX_PROMOTE when target_count == 0 (:703 is skipped, the host goes straight to the record update at :749), else
+ * MMP_VMX_ENSURE_LOADED with last_used = the row's last_used, or now_ms - lastused_age_on_add_ms in Java long arithmetic when that
+ * is 0 (:705-708); last_used is 0 for PROMOTE.  flags: MMP_VMXF_FAILED as stored, MMP_VMXF_FROM_EMPTY / _TO_EMPTY when that registry
+ * row is the empty row (what a deletion leaves: the definition of MMP_RETIRE_EMPTY_ONLY).
+ * Sizing and truncation as mmp_registry_unresolved: *n_out = the listed rows, always; rows_out receives the first
+ * min(*n_out, max_rows) of them in row order, rows_out may be NULL with max_rows == 0.  info_out (may be NULL): counts per class,
+ * the HOST rows skipped, truncated = *n_out > max_rows.  No atomic decides a position: two runs are byte-identical.
+ * What stays with the host: the pendingTransitions de-duplication (:644-652), the status switch after ensureLoadedInternal
+ * (:716-747, which asks mmp_models_status), stuckTransitions / processModelChange, and the transaction.
+ * Read-only, locking and MMP_ESTATE as mmp_vmodels_resolve.  MMP_EINVAL with nothing written: a NULL n_out, max_rows < 0, max_rows
+ * > 0 without rows_out.  An empty vmodel table lists nothing. */
+#define MMP_VMX_PROMOTE 0
+#define MMP_VMX_ENSURE_LOADED 1
+#define MMP_VMXF_FAILED 1u
+#define MMP_VMXF_FROM_EMPTY 2u
+#define MMP_VMXF_TO_EMPTY 4u
+typedef struct {
+    int32_t vmodel, from_model, to_model, target_count;
+    int32_t cls;
+    uint32_t flags;
+    int64_t last_used;
+} mmp_vmodel_transition; /* 32 bytes */
+typedef struct {
+    int32_t n_listed, n_promote, n_ensure_loaded, n_host_skipped, truncated, reserved;
+} mmp_vmodel_transitions_info; /* 24 bytes */
+int mmp_vmodels_transitions(mmp_ctx *ctx, int64_t now_ms, int64_t lastused_age_on_add_ms, mmp_vmodel_transition *rows_out,
+                            int32_t max_rows, int32_t *n_out, mmp_vmodel_transitions_info *info_out);
+/* The way back: rows [first_row, first_row + n_rows).  Their ids as mmp_model_ids_get gives model ids: *n_id_bytes_out always,
+ * id_off_out (n_rows + 1 words, rebased to 0) when not NULL, the bytes when max_id_bytes >= *n_id_bytes_out.  flags_out (n_rows
+ * words, may be NULL) = MMP_VMF_*.  The three strings of row r are spans 3r (amid), 3r + 1 (tmid), 3r + 2 (o) of str_bytes_out /
+ * str_off_out (3 * n_rows + 1 words, rebased to 0, may be NULL), raw bytes as stored, a null string an empty span (the flags tell
+ * it from ""): *n_str_bytes_out always, the bytes when max_str_bytes >= *n_str_bytes_out.  Copies only, no kernel.  MMP_EINVAL
+ * with nothing written for a range outside the table or a NULL required buffer.  Locking: batch_mu. */
+int mmp_vmodels_get(mmp_ctx *ctx, int32_t first_row, int32_t n_rows, char *id_bytes_out, int32_t max_id_bytes, int32_t *id_off_out,
+                    int32_t *n_id_bytes_out, uint32_t *flags_out, char *str_bytes_out, int32_t max_str_bytes, int32_t *str_off_out,
+                    int32_t *n_str_bytes_out);
+/* For tests and operators: rows, rows that are not ABSENT, the string arena's bytes and those a row refers to, the id table's
+ * capacity (0 before the first vmodel call).  No kernel.  Locking: batch_mu. */
+typedef struct {
+    int32_t n_rows, n_live;
+    int64_t arena_bytes, live_bytes;
+    int32_t capacity, reserved;
+} mmp_vmodels_stats; /* 32 bytes */
+int mmp_vmodels_info(mmp_ctx *ctx, mmp_vmodels_stats *out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -215,6 +215,29 @@ final class MmPlace {
     static native int modelsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
                                        ByteBuffer deleted, int flags, ByteBuffer modelIdxOut, ByteBuffer lastUnloadOut,
                                        ByteBuffer statusOut, ByteBuffer nAppendedOut);
+    /** the vmodel table (VModelManager.java:101-110) on the device.  vmodelsEventsJson takes the vmodel listener's events as
+     *  modelsEventsJson takes the registry's: raw key bytes, raw VModelRecord value, deleted (may be null), flags 1 = unknown ids
+     *  join as new rows; there is no load call, start-up is one batch with flags 1.  statusOut 0 applied / 1 malformed / 2 unknown. */
+    static native int vmodelsEventsJson(long h, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer json, ByteBuffer off, int n,
+                                        ByteBuffer deleted, int flags, ByteBuffer vmodelIdxOut, ByteBuffer statusOut,
+                                        ByteBuffer nAppendedOut);
+    /** resolveVModelId (:569-597) and the classes of getVModelStatus (:505-559), one 32-byte answer per key: cls (0 not found / 1 ok /
+     *  2 strong read wanted / 3 target not found / 4 the host decodes), which (0 active / 1 target), vmodel, model, target_model,
+     *  vstatus, target_status, flags.  nfKeys / nfOff (notFoundModelId), owners / ownerOff and reqFlags (1 = after the strong read)
+     *  may each be null; an empty span is null.  model goes straight into a request row. */
+    static native int vmodelsResolve(long h, ByteBuffer keys, ByteBuffer keyOff, int n, ByteBuffer nfKeys, ByteBuffer nfOff,
+                                     ByteBuffer owners, ByteBuffer ownerOff, ByteBuffer reqFlags, ByteBuffer rowsOut);
+    /** processVModels (:617-634) with the prologue of PendingTransition.run (:701-708): the rows in transition, 32 bytes each —
+     *  vmodel, from_model, to_model, target_count, cls (0 promote / 1 ensureLoaded), flags, last_used.  nOut = the full count;
+     *  a null rowsOut with maxRows 0 sizes.  infoOut (24 bytes, may be null). */
+    static native int vmodelsTransitions(long h, long nowMs, long lastUsedAgeOnAddMs, ByteBuffer rowsOut, int maxRows, ByteBuffer nOut,
+                                         ByteBuffer infoOut);
+    /** the way back: ids, flags and the three raw strings (amid, tmid, o: spans 3r .. 3r + 2) of a row range; sizes first. */
+    static native int vmodelsGet(long h, int firstRow, int nRows, ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut,
+                                 ByteBuffer nIdBytesOut, ByteBuffer flagsOut, ByteBuffer strBytesOut, int maxStrBytes,
+                                 ByteBuffer strOffOut, ByteBuffer nStrBytesOut);
+    /** rows, live rows, arena bytes, live bytes, table capacity (32 bytes). */
+    static native int vmodelsInfo(long h, ByteBuffer out);
     /** the write side of the wire format (mmp_models_rewrite_json), for the 13 conditionalSet / conditionalSetAndGet sites of
      *  ModelMesh.java: value i = the stored bytes oldJson[oldOff[i], oldOff[i+1]) of registry row rows[i]; the answer is the value to
      *  store next — what the device does not own copied byte for byte, instanceIds / failedIn / fails / lu (and lul from lastUnload,

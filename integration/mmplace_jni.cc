@@ -775,6 +775,86 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsEventsJson(JN
                                         buf<int32_t>(env, nAppendedOut)));
 }
 
+// ---- the vmodel table on the device (see mmp_vmodels_events_json ... mmp_vmodels_info) -------------------------------------
+// The capacities are checked here, as for the registry calls: the library only knows n.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsEventsJson(JNIEnv *env, jclass, jlong h, jobject keys,
+                                                                               jobject keyOff, jobject json, jobject off, jint n,
+                                                                               jobject deleted, jint flags, jobject vmodelIdxOut,
+                                                                               jobject statusOut, jobject nAppendedOut)
+{
+    if (n < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "vmodelsEventsJson: keyOff shorter than n + 1") ||
+        !holds<int64_t>(env, off, (jlong)n + 1, "vmodelsEventsJson: off shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "vmodelsEventsJson: keys shorter than keyOff[n]")) ||
+        (n > 0 && !holds<char>(env, json, buf<int64_t>(env, off)[n], "vmodelsEventsJson: json shorter than off[n]")) ||
+        (deleted && !holds<uint8_t>(env, deleted, n, "vmodelsEventsJson: deleted shorter than n")) ||
+        !holds<int32_t>(env, vmodelIdxOut, n, "vmodelsEventsJson: vmodelIdxOut shorter than n") ||
+        !holds<int32_t>(env, statusOut, n, "vmodelsEventsJson: statusOut shorter than n") ||
+        (nAppendedOut && !holds<int32_t>(env, nAppendedOut, 1, "vmodelsEventsJson: nAppendedOut shorter than one int")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_events_json(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), buf<char>(env, json),
+                                         buf<int64_t>(env, off), n, buf<uint8_t>(env, deleted), static_cast<uint32_t>(flags),
+                                         buf<int32_t>(env, vmodelIdxOut), buf<int32_t>(env, statusOut), buf<int32_t>(env, nAppendedOut)));
+}
+// nfKeys / nfOff, owners / ownerOff and reqFlags may each be null; rowsOut holds n mmp_vmodel_answer structs
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsResolve(JNIEnv *env, jclass, jlong h, jobject keys, jobject keyOff,
+                                                                            jint n, jobject nfKeys, jobject nfOff, jobject owners,
+                                                                            jobject ownerOff, jobject reqFlags, jobject rowsOut)
+{
+    if (n < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "vmodelsResolve: keyOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "vmodelsResolve: keys shorter than keyOff[n]")) ||
+        (nfOff && !holds<int32_t>(env, nfOff, (jlong)n + 1, "vmodelsResolve: nfOff shorter than n + 1")) ||
+        (nfOff && n > 0 && !holds<char>(env, nfKeys, buf<int32_t>(env, nfOff)[n], "vmodelsResolve: nfKeys shorter than nfOff[n]")) ||
+        (ownerOff && !holds<int32_t>(env, ownerOff, (jlong)n + 1, "vmodelsResolve: ownerOff shorter than n + 1")) ||
+        (ownerOff && n > 0 && !holds<char>(env, owners, buf<int32_t>(env, ownerOff)[n], "vmodelsResolve: owners shorter than ownerOff[n]")) ||
+        (reqFlags && !holds<uint32_t>(env, reqFlags, n, "vmodelsResolve: reqFlags shorter than n")) ||
+        !holds<mmp_vmodel_answer>(env, rowsOut, n, "vmodelsResolve: rowsOut shorter than n answers"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_resolve(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), n, buf<char>(env, nfKeys),
+                                     buf<int32_t>(env, nfOff), buf<char>(env, owners), buf<int32_t>(env, ownerOff),
+                                     buf<uint32_t>(env, reqFlags), buf<mmp_vmodel_answer>(env, rowsOut)));
+}
+// a null rowsOut with maxRows 0: nOut and infoOut only; infoOut (may be null) holds one mmp_vmodel_transitions_info
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsTransitions(JNIEnv *env, jclass, jlong h, jlong nowMs,
+                                                                                jlong lastUsedAgeOnAddMs, jobject rowsOut, jint maxRows,
+                                                                                jobject nOut, jobject infoOut)
+{
+    if (maxRows < 0 || !holds<mmp_vmodel_transition>(env, rowsOut, maxRows, "vmodelsTransitions: rowsOut shorter than maxRows") ||
+        !holds<int32_t>(env, nOut, 1, "vmodelsTransitions: nOut shorter than one int") ||
+        (infoOut && !holds<mmp_vmodel_transitions_info>(env, infoOut, 1, "vmodelsTransitions: infoOut shorter than one info")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_transitions(ctx_of(h), nowMs, lastUsedAgeOnAddMs, buf<mmp_vmodel_transition>(env, rowsOut), maxRows,
+                                         buf<int32_t>(env, nOut), buf<mmp_vmodel_transitions_info>(env, infoOut)));
+}
+// sizes first: null byte buffers with capacities 0 give nIdBytesOut / nStrBytesOut; idOffOut (nRows + 1 ints), flagsOut (nRows ints)
+// and strOffOut (3 nRows + 1 ints) may be null
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsGet(JNIEnv *env, jclass, jlong h, jint firstRow, jint nRows,
+                                                                        jobject idBytesOut, jint maxIdBytes, jobject idOffOut,
+                                                                        jobject nIdBytesOut, jobject flagsOut, jobject strBytesOut,
+                                                                        jint maxStrBytes, jobject strOffOut, jobject nStrBytesOut)
+{
+    if (nRows < 0 || maxIdBytes < 0 || maxStrBytes < 0 ||
+        !holds<char>(env, idBytesOut, maxIdBytes, "vmodelsGet: idBytesOut shorter than maxIdBytes") ||
+        (idOffOut && !holds<int32_t>(env, idOffOut, (jlong)nRows + 1, "vmodelsGet: idOffOut shorter than nRows + 1")) ||
+        !holds<int32_t>(env, nIdBytesOut, 1, "vmodelsGet: nIdBytesOut shorter than one int") ||
+        (flagsOut && !holds<uint32_t>(env, flagsOut, nRows, "vmodelsGet: flagsOut shorter than nRows")) ||
+        !holds<char>(env, strBytesOut, maxStrBytes, "vmodelsGet: strBytesOut shorter than maxStrBytes") ||
+        (strOffOut && !holds<int32_t>(env, strOffOut, 3 * (jlong)nRows + 1, "vmodelsGet: strOffOut shorter than 3 nRows + 1")) ||
+        !holds<int32_t>(env, nStrBytesOut, 1, "vmodelsGet: nStrBytesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_get(ctx_of(h), firstRow, nRows, buf<char>(env, idBytesOut), maxIdBytes, buf<int32_t>(env, idOffOut),
+                                 buf<int32_t>(env, nIdBytesOut), buf<uint32_t>(env, flagsOut), buf<char>(env, strBytesOut), maxStrBytes,
+                                 buf<int32_t>(env, strOffOut), buf<int32_t>(env, nStrBytesOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsInfo(JNIEnv *env, jclass, jlong h, jobject out)
+{
+    if (!holds<mmp_vmodels_stats>(env, out, 1, "vmodelsInfo: out shorter than one mmp_vmodels_stats")) return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_vmodels_info(ctx_of(h), buf<mmp_vmodels_stats>(env, out)));
+}
+
 // the write side of the wire format: the stored value of each edited record and the record as the device holds it give the value
 // to store next (see mmp_models_rewrite_json).  The capacities are checked here; outCap is what outBuf holds (0 with null: sizes).
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRewriteJson(JNIEnv *env, jclass, jlong h, jobject rows, jint n,

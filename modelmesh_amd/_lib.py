@@ -194,6 +194,27 @@ assert REGISTER_REQ.itemsize == 16
 MREG_LOAD_NOW, MREG_DELETE = 1, 2
 (MREG_CREATED, MREG_TOUCHED, MREG_EXISTS, MREG_CONFLICT, MREG_ABSENT, MREG_REFERENCED, MREG_DELETABLE, MREG_MALFORMED,
  MREG_HOST) = range(9)
+# the vmodel table (VModelManager.java:101-110): mmp_vmodels_events_json / _resolve / _transitions / _get / _info
+VMEV_APPEND = 1
+(VMF_FAILED, VMF_ABSENT, VMF_ACTIVE_NULL, VMF_TARGET_NULL, VMF_OWNER_NULL, VMF_HOST) = (1, 2, 4, 8, 16, 32)
+VMRQ_AFTER_STRONG = 1
+(VMR_NOT_FOUND, VMR_OK, VMR_STRONG_READ, VMR_TARGET_NOT_FOUND, VMR_HOST) = range(5)
+VMW_ACTIVE, VMW_TARGET = 0, 1
+VMRF_NULL_ID = 1
+VMS_DEFINED, VMS_TRANSITIONING, VMS_TRANSITION_FAILED = range(3)
+VMT_NONE, VMT_LOADING, VMT_LOADING_FAILED, VMT_NOT_FOUND = range(4)
+VMX_PROMOTE, VMX_ENSURE_LOADED = 0, 1
+VMXF_FAILED, VMXF_FROM_EMPTY, VMXF_TO_EMPTY = 1, 2, 4
+VMODEL_ANSWER = np.dtype([("cls", "<i4"), ("which", "<i4"), ("vmodel", "<i4"), ("model", "<i4"), ("target_model", "<i4"),
+                          ("vstatus", "<i4"), ("target_status", "<i4"), ("flags", "<u4")])
+VMODEL_TRANSITION = np.dtype([("vmodel", "<i4"), ("from_model", "<i4"), ("to_model", "<i4"), ("target_count", "<i4"), ("cls", "<i4"),
+                              ("flags", "<u4"), ("last_used", "<i8")])
+VMODEL_TRANSITIONS_INFO = np.dtype([("n_listed", "<i4"), ("n_promote", "<i4"), ("n_ensure_loaded", "<i4"), ("n_host_skipped", "<i4"),
+                                    ("truncated", "<i4"), ("reserved", "<i4")])
+VMODELS_STATS = np.dtype([("n_rows", "<i4"), ("n_live", "<i4"), ("arena_bytes", "<i8"), ("live_bytes", "<i8"), ("capacity", "<i4"),
+                          ("reserved", "<i4")])
+assert VMODEL_ANSWER.itemsize == 32 and VMODEL_TRANSITION.itemsize == 32 and VMODEL_TRANSITIONS_INFO.itemsize == 24
+assert VMODELS_STATS.itemsize == 32
 # mmp_models_retire: every named row must be the empty row a deletion leaves
 RETIRE_EMPTY_ONLY = 1
 # mmp_pods_retire: every named row must be a tombstone / no referenced registry entry may name a retired instance
@@ -340,6 +361,12 @@ SYMBOLS = [
                                           C.POINTER(C.c_int64)]),
     ("mmp_models_register_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int64,
                                            _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    ("mmp_vmodels_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.POINTER(C.c_int32)]),
+    ("mmp_vmodels_resolve", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("mmp_vmodels_transitions", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.POINTER(C.c_int32), _P]),
+    ("mmp_vmodels_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
+                                  C.POINTER(C.c_int32)]),
+    ("mmp_vmodels_info", C.c_int, [_P, _P]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

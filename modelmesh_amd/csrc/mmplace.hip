@@ -47,6 +47,7 @@
 #include "pods_retire_kernels.hpp"
 #include "rewrite_kernels.hpp"
 #include "register_kernels.hpp"
+#include "vmodel_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -267,6 +268,7 @@ struct Tuning {
     int32_t resident = 0;        // MMP_RESIDENT=1: mmp_create turns the resident decision kernel on (mmp_resident)
     int32_t label_hash_bits = 64;     // MMP_LABEL_HASH_BITS=b: the same for the label-name hashes (tests: the byte comparison of label_find)
     int32_t model_id_hash_bits = 64;  // MMP_MODEL_ID_HASH_BITS=b: every model-id hash is masked to its low b bits, 0: all equal (tests: ids that collide)
+    int32_t vmodel_id_hash_bits = 64;  // MMP_VMODEL_ID_HASH_BITS=b: the same for the vmodel-id hashes
 };
 
 struct mmp_ctx {
@@ -520,6 +522,17 @@ struct mmp_ctx {
     // last_used; sizes, offsets and rendered bytes are rw_len / rw_off / rw_out.  Owned by batch_mu, used on c->stream.
     DevBuf rg_reqs, rg_info, rg_ioff, rg_cls, rg_lu;
     uint64_t id_gen = 1, idd_gen = 0;
+    // The vmodel table (vmodel_kernels.hpp), nothing of it allocated before the first vmodel call.  vid_*: its id table, the fields
+    // of the model-id table over again (both are driven through IdTabRef).  vm_rows: one VmRow per vmodel; vm_arena: the strings,
+    // vm_arena_bytes of them used, vm_live_bytes referred to by a row; vm_live_rows: rows that are not ABSENT.  vm_ev / vm_cnt /
+    // vm_pos: one event call's parsed events, byte counts and their scan; vm_nf_* / vm_ow_* / vm_rflags / vm_ans: one resolve's
+    // staged strings, flags and answers; vm_list: the transition scan's rows.  Read and written under batch_mu, used on c->stream.
+    DevBuf vid_hash, vid_val, vid_next_hash, vid_next_val, vid_bytes, vid_off;
+    DevBuf vm_rows, vm_arena, vm_ev, vm_cnt, vm_pos, vm_nf_bytes, vm_nf_off, vm_ow_bytes, vm_ow_off, vm_rflags, vm_ans, vm_list;
+    uint32_t vid_mask = 0;
+    int32_t vid_n = 0, vid_nbytes = 0, vm_arena_bytes = 0, vm_live_rows = 0;
+    int64_t vm_live_bytes = 0;
+    bool have_vmodels = false;
 };
 
 namespace {
@@ -808,6 +821,8 @@ Tuning read_tuning()
     flag("MMP_RESIDENT", t.resident);
     num("MMP_MODEL_ID_HASH_BITS", t.model_id_hash_bits);
     t.model_id_hash_bits = std::max(0, std::min(t.model_id_hash_bits, 64));
+    num("MMP_VMODEL_ID_HASH_BITS", t.vmodel_id_hash_bits);
+    t.vmodel_id_hash_bits = std::max(0, std::min(t.vmodel_id_hash_bits, 64));
     num("MMP_LABEL_HASH_BITS", t.label_hash_bits);
     t.label_hash_bits = std::max(0, std::min(t.label_hash_bits, 64));
     return t;
@@ -1396,6 +1411,9 @@ void mmp_destroy(mmp_ctx *c)
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
                       &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu,
+                      &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_arena,
+                      &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
+                      &c->vm_ans, &c->vm_list,
                       &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
@@ -3626,6 +3644,26 @@ try {
 } MMP_CATCH(c, "mmp_models_upsert_json")
 
 namespace {
+// An id table of the context as the by-key sequence below sees it: the model-id table (mid_*) or the vmodel-id table (vid_*).
+// Both are one ModelIdTab on the device, so one host sequence drives the kernels of model_ids_kernels.hpp for either.
+struct IdTabRef {
+    DevBuf &hash, &val, &next_hash, &next_val, &bytes, &off;
+    uint32_t &mask;
+    int32_t &n, &nbytes;
+    int32_t hash_bits;
+    ModelIdTab published() const { return ModelIdTab{hash.as<uint64_t>(), val.as<int32_t>(), mask, bytes.as<char>(), off.as<int32_t>()}; }
+};
+extern "C++" IdTabRef model_id_tab(mmp_ctx *c)  // (references: no C linkage inside the file's extern "C" block)
+{
+    return IdTabRef{c->mid_hash, c->mid_val, c->mid_next_hash, c->mid_next_val, c->mid_bytes, c->mid_off, c->mid_mask, c->mid_n, c->mid_nbytes,
+                    c->tune.model_id_hash_bits};
+}
+extern "C++" IdTabRef vmodel_id_tab(mmp_ctx *c)
+{
+    return IdTabRef{c->vid_hash, c->vid_val, c->vid_next_hash, c->vid_next_val, c->vid_bytes, c->vid_off, c->vid_mask, c->vid_n, c->vid_nbytes,
+                    c->tune.vmodel_id_hash_bits};
+}
+
 // One call's keys resolved, deduplicated and numbered on the device, and the table / arena that would hold the joining ids built
 // beside the published ones.  Nothing of the context's published state has changed until model_ids_publish.
 struct ModelIdsPlan {
@@ -3643,23 +3681,24 @@ struct ModelIdsPlan {
 };
 
 // The staged keys (ida_*) hashed once into me_hash and looked up in `tab` into me_row (enqueued inside the caller's bracket)
-void mid_resolve_launch(mmp_ctx *c, int32_t n, const ModelIdTab &tab)
+void mid_resolve_launch(mmp_ctx *c, int32_t n, const ModelIdTab &tab, int32_t hash_bits)
 {
     const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
     hipLaunchKernelGGL(mid_hash_kernel, grid, block, 0, c->stream, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n,
-                       hash_mask(c->tune.model_id_hash_bits), c->me_hash.as<uint64_t>());
+                       hash_mask(hash_bits), c->me_hash.as<uint64_t>());
     hipLaunchKernelGGL(mid_resolve_kernel, grid, block, 0, c->stream, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n,
                        c->me_hash.as<uint64_t>(), tab, c->me_row.as<int32_t>());
 }
 
-// batch_mu held, the device set, n > 0, the key offsets monotone.  replace: the keys are a whole id space (mmp_model_ids_load) —
-// resolved against no table, numbered from row 0, table and arena built fresh.  deleted: host bytes or nullptr.
-int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, int32_t n, const uint8_t *deleted, bool append,
-                   bool replace, ModelIdsPlan &P)
+// batch_mu held, the device set, n > 0, the key offsets monotone.  T: the table the keys belong to.  replace: the keys are a whole
+// id space (mmp_model_ids_load) or the table's first (the vmodel table's first call) — resolved against no table, numbered from
+// row 0, table and arena built fresh.  deleted: host bytes or nullptr.
+int model_ids_plan(mmp_ctx *c, const IdTabRef &T, const char *fn, const char *keys, const int32_t *key_off, int32_t n,
+                   const uint8_t *deleted, bool append, bool replace, ModelIdsPlan &P)
 {
     if (n > INT32_MAX / 8) return fail(c, MMP_EINVAL, "%s: %d keys in one call", fn, n);
     hipStream_t st = c->stream;
-    const int32_t M0 = P.n_before = replace ? 0 : c->mid_n, B0 = P.bytes_before = replace ? 0 : c->mid_nbytes;
+    const int32_t M0 = P.n_before = replace ? 0 : T.n, B0 = P.bytes_before = replace ? 0 : T.nbytes;
     std::vector<int32_t> krel;
     if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
     const uint32_t bcap = tab_capacity(n);  // the call-local table: twice the events
@@ -3680,8 +3719,8 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     const uint64_t *d_hash = c->me_hash.as<uint64_t>();
     const uint8_t *d_del = deleted ? E.deleted : nullptr;
     MidCount *d_cnt = c->me_cnt.as<MidCount>(), *d_pos = c->me_pos.as<MidCount>();
-    const ModelIdTab cur{replace ? nullptr : c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
-                         c->mid_off.as<int32_t>()};
+    ModelIdTab cur = T.published();
+    if (replace) cur.hash = nullptr;
     if (deleted) HIP_TRY(c, hipMemcpyAsync(E.deleted, deleted, (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(B.owner, 0xff, (size_t)bcap * 4, st));
     HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.first), INT32_MAX, (size_t)bcap * 2, st));
@@ -3691,7 +3730,7 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
     const dim3 grid(div_up(n, kIdTabBlock)), block(kIdTabBlock);
     // 1. hash once; the rows the table knows; the call's own duplicates; the flags and their scan
     KT_BEGIN(c, st);
-    mid_resolve_launch(c, n, cur);
+    mid_resolve_launch(c, n, cur, T.hash_bits);
     hipLaunchKernelGGL(mid_dedupe_kernel, grid, block, 0, st, d_keys, d_off, n, d_hash, d_del, B, c->me_slot.as<int32_t>());
     hipLaunchKernelGGL(mid_flags_kernel, dim3(div_up(n + 1, kIdTabBlock)), block, 0, st, n, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B,
                        d_off, append ? 1 : 0, d_cnt);
@@ -3713,20 +3752,20 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
         HIP_TRY(c, P.fresh_off.ensure(((size_t)P.n_join + 1) * 4));
         HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, st));
     } else {
-        if (const int rc = grow_cow(c, c->mid_bytes, (size_t)B0, (size_t)B0 + P.join_bytes, P.fresh_bytes)) return rc;
-        if (const int rc = grow_cow(c, c->mid_off, ((size_t)M0 + 1) * 4, ((size_t)M0 + P.n_join + 1) * 4, P.fresh_off)) return rc;
+        if (const int rc = grow_cow(c, T.bytes, (size_t)B0, (size_t)B0 + P.join_bytes, P.fresh_bytes)) return rc;
+        if (const int rc = grow_cow(c, T.off, ((size_t)M0 + 1) * 4, ((size_t)M0 + P.n_join + 1) * 4, P.fresh_off)) return rc;
     }
-    char *a_bytes = P.fresh_bytes.p ? P.fresh_bytes.as<char>() : c->mid_bytes.as<char>();
-    int32_t *a_off = P.fresh_off.p ? P.fresh_off.as<int32_t>() : c->mid_off.as<int32_t>();
+    char *a_bytes = P.fresh_bytes.p ? P.fresh_bytes.as<char>() : T.bytes.as<char>();
+    int32_t *a_off = P.fresh_off.p ? P.fresh_off.as<int32_t>() : T.off.as<int32_t>();
     // 3. number the events; 4. the next table, copy-on-write, and a verifying lookup in a launch of its own
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(mid_number_kernel, grid, block, 0, st, n, M0, P.k, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B, append ? 1 : 0,
                        d_pos, d_keys, d_off, B0, c->me_idx.as<int32_t>(), E.slot, E.slot_model, c->me_join.as<int32_t>(), a_bytes, a_off);
     if (P.n_join > 0 || replace) {
-        const uint32_t cap0 = replace ? 0u : c->mid_mask + 1;
+        const uint32_t cap0 = replace ? 0u : T.mask + 1;
         HashTabW nt;
-        if (const int rc = next_table_room(c, cap0, M0 + P.n_join, c->mid_next_hash, c->mid_next_val, nt)) return rc;
-        if (const int rc = next_table(c, c->mid_hash, c->mid_val, cap0, nt)) return rc;
+        if (const int rc = next_table_room(c, cap0, M0 + P.n_join, T.next_hash, T.next_val, nt)) return rc;
+        if (const int rc = next_table(c, T.hash, T.val, cap0, nt)) return rc;
         if (P.n_join > 0) {
             const dim3 jgrid(div_up(P.n_join, kIdTabBlock));
             hipLaunchKernelGGL(mid_insert_kernel, jgrid, block, 0, st, P.n_join, c->me_join.as<int32_t>(), d_hash, M0, nt);
@@ -3750,25 +3789,25 @@ int model_ids_plan(mmp_ctx *c, const char *fn, const char *keys, const int32_t *
 }
 
 // nothing fails from here on: the table, the arena and the counts change together (batch_mu held, the stream idle)
-void model_ids_publish(mmp_ctx *c, ModelIdsPlan &P)
+void model_ids_publish(const IdTabRef &T, ModelIdsPlan &P)
 {
     if (P.cap) {
-        std::swap(c->mid_hash, c->mid_next_hash);
-        std::swap(c->mid_val, c->mid_next_val);
-        c->mid_mask = P.cap - 1;
+        std::swap(T.hash, T.next_hash);
+        std::swap(T.val, T.next_val);
+        T.mask = P.cap - 1;
     }
     if (P.fresh_bytes.p) {
-        c->mid_bytes.release();
-        c->mid_bytes = P.fresh_bytes;
+        T.bytes.release();
+        T.bytes = P.fresh_bytes;
         P.fresh_bytes = DevBuf{};
     }
     if (P.fresh_off.p) {
-        c->mid_off.release();
-        c->mid_off = P.fresh_off;
+        T.off.release();
+        T.off = P.fresh_off;
         P.fresh_off = DevBuf{};
     }
-    c->mid_n = P.n_before + P.n_join;
-    c->mid_nbytes = P.bytes_before + P.join_bytes;
+    T.n = P.n_before + P.n_join;
+    T.nbytes = P.bytes_before + P.join_bytes;
 }
 
 // The registry and the id table cover the same rows: mmp_models_load, mmp_models_ingest_json and an append by index
@@ -3800,14 +3839,14 @@ try {
         HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
-        if (const int rc = model_ids_plan(c, "mmp_model_ids_load", ids, id_off, n_models, nullptr, true, true, P)) return rc;
+        if (const int rc = model_ids_plan(c, model_id_tab(c), "mmp_model_ids_load", ids, id_off, n_models, nullptr, true, true, P)) return rc;
         if (P.n_join != n_models) {  // up to the first repeat an id's row is its index
             int32_t i = 0;
             while (i < n_models && P.idx[i] == i) i++;
             return fail(c, MMP_EINVAL, "mmp_model_ids_load: ids %d and %d are equal", i < n_models ? P.idx[i] : -1, i);
         }
     }
-    model_ids_publish(c, P);
+    model_ids_publish(model_id_tab(c), P);
     c->have_model_ids = true;
     return MMP_OK;
 } MMP_CATCH(c, "mmp_model_ids_load")
@@ -3825,8 +3864,7 @@ try {
     HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
     HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
     KT_BEGIN(c, st);
-    mid_resolve_launch(c, n, ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
-                                        c->mid_off.as<int32_t>()});
+    mid_resolve_launch(c, n, model_id_tab(c).published(), c->tune.model_id_hash_bits);
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -3874,7 +3912,8 @@ try {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     ModelIdsPlan P;
-    if (const int rc = model_ids_plan(c, "mmp_models_events_json", keys, key_off, n, deleted, flags & MMP_MEV_APPEND, false, P)) return rc;
+    if (const int rc = model_ids_plan(c, model_id_tab(c), "mmp_models_events_json", keys, key_off, n, deleted, flags & MMP_MEV_APPEND, false, P))
+        return rc;
     if (P.k > 0) {
         // everything behind the resolution is mmp_models_upsert_json: slot / slot_model are on the device already
         UpsertJsonEvents E = carve(c->j_ev.as<int32_t>(), n, n);  // as model_ids_plan carved it
@@ -3885,7 +3924,7 @@ try {
         std::vector<int32_t> h_model;
         if (const int rc = models_upsert_json_run(c, "mmp_models_events_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
         kt_add(c, P.ms);  // the call's device span: resolve + parse + apply
-        model_ids_publish(c, P);
+        model_ids_publish(model_id_tab(c), P);
     } else if (c->prof)
         c->last_kernel_ms = P.ms;
     for (int32_t i = 0; i < n; i++) {
@@ -3897,6 +3936,305 @@ try {
     if (n_appended_out) *n_appended_out = P.n_join;
     return P.k > 0 ? squeeze_if_garbage(c) : (int)MMP_OK;
 } MMP_CATCH(c, "mmp_models_events_json")
+
+namespace {
+// (a DevBuf that is released unless it has been handed over)
+struct ScopedDevBuf {
+    DevBuf b;
+    ~ScopedDevBuf() { b.release(); }
+    void move_into(DevBuf &dst)
+    {
+        if (!b.p) return;
+        dst.release();
+        dst = b;
+        b = DevBuf{};
+    }
+};
+
+VmTab vmodel_tab(mmp_ctx *c)
+{
+    VmTab V{};
+    if (c->have_vmodels) V = VmTab{vmodel_id_tab(c).published(), c->vm_rows.as<VmRow>(), c->vm_arena.as<char>(), c->vid_n};
+    return V;
+}
+VmModels vmodel_models(mmp_ctx *c) { return VmModels{model_id_tab(c).published(), c->models.as<mmp_model_row>(), c->n_models}; }
+
+// The vmodel string arena's garbage (batch_mu held, the device set): as squeeze_if_garbage for the entry arena — when the bytes no
+// row refers to exceed the live ones, the rows with their new offsets and the squeezed arena are built beside the published ones
+// and swapped in under the state lock.
+int vmodels_squeeze_if_garbage(mmp_ctx *c)
+{
+    const int32_t V = c->vid_n;
+    if ((int64_t)c->vm_arena_bytes - c->vm_live_bytes <= c->vm_live_bytes) return MMP_OK;
+    hipStream_t st = c->stream;
+    ScopedDevBuf rows, arena;
+    HIP_TRY(c, rows.b.ensure(std::max<size_t>(c->vm_rows.cap, 16)));
+    HIP_TRY(c, arena.b.ensure(std::max<size_t>((size_t)c->vm_live_bytes * 2, 16)));
+    HIP_TRY(c, c->j_cnt.ensure(((size_t)V + 1) * 4));
+    HIP_TRY(c, c->j_offs.ensure(((size_t)V + 1) * 4));
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->j_cnt.as<int32_t>(), c->j_offs.as<int32_t>(), (int32_t)0, (size_t)V + 1,
+                                       rocprim::plus<int32_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    const double events_ms = c->last_kernel_ms;
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(vm_squeeze_len_kernel, dim3(div_up(V + 1, 256)), dim3(256), 0, st, c->vm_rows.as<VmRow>(), V, c->j_cnt.as<int32_t>());
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, c->j_cnt.as<int32_t>(), c->j_offs.as<int32_t>(), (int32_t)0,
+                                       (size_t)V + 1, rocprim::plus<int32_t>(), st));
+    if (V > 0)
+        hipLaunchKernelGGL(vm_squeeze_copy_kernel, dim3(div_up(V, 256)), dim3(256), 0, st, c->vm_rows.as<VmRow>(), V, c->j_offs.as<int32_t>(),
+                           c->vm_arena.as<char>(), rows.b.as<VmRow>(), arena.b.as<char>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    int32_t live = 0;
+    HIP_TRY(c, copy_sync(c, &live, c->j_offs.as<int32_t>() + V, 4, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    kt_add(c, events_ms);
+    if (live != c->vm_live_bytes) return fail(c, MMP_EHIP, "vmodel arena: %d live bytes on the device, %lld accounted", live, (long long)c->vm_live_bytes);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    rows.move_into(c->vm_rows);
+    arena.move_into(c->vm_arena);
+    c->vm_arena_bytes = live;
+    return MMP_OK;
+}
+}  // namespace
+
+int mmp_vmodels_events_json(mmp_ctx *c, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
+                            const uint8_t *deleted, uint32_t flags, int32_t *vmodel_idx_out, int32_t *status_out, int32_t *n_appended_out)
+try {
+    if (!c || n < 0 || (flags & ~MMP_VMEV_APPEND) || (n > 0 && (!key_off || !off || !vmodel_idx_out || !status_out)))
+        return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: bad argument");
+    // the vmodel state is read and written under batch_mu; the state lock is taken for the swap only
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (n_appended_out) *n_appended_out = 0;
+    if (n == 0) return MMP_OK;
+    // (both kinds, before anything is staged: a refused call changes nothing)
+    if (const int rc = check_offsets(c, "mmp_vmodels_events_json", "", off, n, key_off)) return rc;
+    if ((off[n] > off[0] && !buf) || (key_off[n] > key_off[0] && !keys)) return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: bad argument");
+    for (int32_t i = 0; i < n; i++)
+        if (off[i + 1] - off[i] >= kVmMaxValue) return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: value %d has 2^30 bytes or more", i);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const IdTabRef T = vmodel_id_tab(c);
+    ModelIdsPlan P;
+    if (const int rc = model_ids_plan(c, T, "mmp_vmodels_events_json", keys, key_off, n, deleted, flags & MMP_VMEV_APPEND, !c->have_vmodels, P))
+        return rc;
+    const int32_t V0 = P.n_before, V1 = V0 + P.n_join, k = P.k;
+    ScopedDevBuf fresh_rows, fresh_arena;
+    VmBytes tot{0, 0, 0};
+    double ms = P.ms;
+    if (k > 0) {
+        // slot / slot_model are on the device already, as model_ids_plan carved them: the winner rule of mmp_models_upsert_json
+        UpsertJsonEvents E = carve(c->j_ev.as<int32_t>(), n, n);
+        HIP_TRY(c, hipMemsetAsync(E.win, 0xff, ((size_t)k + 1) * 4, st));
+        std::vector<int64_t> rel;
+        if (const int rc = stage_strings(c, "mmp_vmodels_events_json", "", buf, off, n, c->j_buf, c->j_off, rel)) return rc;
+        HIP_TRY(c, c->vm_ev.ensure((size_t)n * sizeof(VmEvent)));
+        HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+        HIP_TRY(c, c->vm_cnt.ensure(((size_t)k + 1) * sizeof(VmBytes)));
+        HIP_TRY(c, c->vm_pos.ensure(((size_t)k + 1) * sizeof(VmBytes)));
+        if (const int rc = grow_cow(c, c->vm_rows, (size_t)V0 * sizeof(VmRow), (size_t)V1 * sizeof(VmRow), fresh_rows.b)) return rc;
+        VmBytes *d_cnt = c->vm_cnt.as<VmBytes>(), *d_pos = c->vm_pos.as<VmBytes>();
+        size_t scan_bytes = 0;
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, VmBytes{0, 0, 0}, (size_t)k + 1, VmBytesPlus(), st));
+        HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+        VmParseArgs A{c->j_buf.as<char>(), c->j_off.as<int64_t>(), n, ingest_group(n), deleted ? E.deleted : nullptr, E.slot, E.win,
+                      c->vm_ev.as<VmEvent>(), c->j_status.as<int32_t>()};
+        // parse the events, pick each row's winner, and size what the winners append
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(vm_parse_kernel, dim3(div_up(n, kJWaves * A.grp)), dim3(kJBlock), 0, st, A);
+        hipLaunchKernelGGL(vm_counts_kernel, dim3(div_up(k + 1, 256)), dim3(256), 0, st, E.win, A.ev, k, E.slot_model, V0, c->vm_rows.as<VmRow>(),
+                           d_cnt);
+        HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, VmBytes{0, 0, 0}, (size_t)k + 1, VmBytesPlus(), st));
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, copy_sync(c, &tot, d_pos + k, sizeof tot, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        ms = kt_sum(c, ms, c->last_kernel_ms);
+        const int32_t base = c->vm_arena_bytes;
+        if ((int64_t)base + tot.add > INT32_MAX)  // (nothing but scratch has been written so far)
+            return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: more than 2^31 bytes in the string arena");
+        if (const int rc = grow_cow(c, c->vm_arena, (size_t)base, (size_t)base + tot.add + 16, fresh_arena.b)) return rc;
+        VmRow *rows = fresh_rows.b.p ? fresh_rows.b.as<VmRow>() : c->vm_rows.as<VmRow>();
+        char *arena = fresh_arena.b.p ? fresh_arena.b.as<char>() : c->vm_arena.as<char>();
+        // nothing is refused from here on: the winners' strings behind the published bytes, the rows rewritten
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(vm_build_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, E.win, E.slot_model, k, V0, base, d_pos, A.ev, A.buf, A.off,
+                           hash_mask(c->tune.model_id_hash_bits), rows, arena);
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(status_out, c->j_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        kt_collect(c);
+        ms = kt_sum(c, ms, c->last_kernel_ms);
+    }
+    if (c->prof) c->last_kernel_ms = ms;
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);  // table, arenas and counts change together
+        model_ids_publish(T, P);
+        fresh_rows.move_into(c->vm_rows);
+        fresh_arena.move_into(c->vm_arena);
+        c->vm_arena_bytes += tot.add;
+        c->vm_live_bytes += (int64_t)tot.add - tot.sub;
+        c->vm_live_rows += tot.live;
+        c->have_vmodels = true;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        vmodel_idx_out[i] = P.idx[i];
+        if (P.idx[i] < 0) status_out[i] = 2;  // an unknown id: nothing was read, nothing changes
+    }
+    if (n_appended_out) *n_appended_out = P.n_join;
+    return vmodels_squeeze_if_garbage(c);
+} MMP_CATCH(c, "mmp_vmodels_events_json")
+
+int mmp_vmodels_resolve(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, const char *nf_keys, const int32_t *nf_off,
+                        const char *owners, const int32_t *owner_off, const uint32_t *req_flags, mmp_vmodel_answer *rows_out)
+try {
+    if (!c || n < 0 || (n > 0 && (!key_off || !rows_out))) return fail(c, MMP_EINVAL, "mmp_vmodels_resolve: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, "mmp_vmodels_resolve")) return rc;
+    if (n == 0) return MMP_OK;
+    // (all three kinds and the flags, before anything is staged)
+    if (const int rc = check_offsets(c, "mmp_vmodels_resolve", "key ", key_off, n)) return rc;
+    if (nf_off)
+        if (const int rc = check_offsets(c, "mmp_vmodels_resolve", "nf ", nf_off, n)) return rc;
+    if (owner_off)
+        if (const int rc = check_offsets(c, "mmp_vmodels_resolve", "owner ", owner_off, n)) return rc;
+    if ((key_off[n] > key_off[0] && !keys) || (nf_off && nf_off[n] > nf_off[0] && !nf_keys) || (owner_off && owner_off[n] > owner_off[0] && !owners))
+        return fail(c, MMP_EINVAL, "mmp_vmodels_resolve: bad argument");
+    if (req_flags)
+        for (int32_t i = 0; i < n; i++)
+            if (req_flags[i] & ~MMP_VMRQ_AFTER_STRONG) return fail(c, MMP_EINVAL, "mmp_vmodels_resolve: request %d has unknown flag bits", i);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel, nrel, orel;
+    if (const int rc = stage_strings(c, "mmp_vmodels_resolve", "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+    if (nf_off)
+        if (const int rc = stage_strings(c, "mmp_vmodels_resolve", "nf ", nf_keys, nf_off, n, c->vm_nf_bytes, c->vm_nf_off, nrel)) return rc;
+    if (owner_off)
+        if (const int rc = stage_strings(c, "mmp_vmodels_resolve", "owner ", owners, owner_off, n, c->vm_ow_bytes, c->vm_ow_off, orel)) return rc;
+    if (req_flags) {
+        HIP_TRY(c, c->vm_rflags.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->vm_rflags.p, req_flags, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(c, c->vm_ans.ensure((size_t)n * sizeof(mmp_vmodel_answer)));
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(vm_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(),
+                       n, hash_mask(c->tune.vmodel_id_hash_bits), nf_off ? c->vm_nf_bytes.as<char>() : nullptr,
+                       nf_off ? c->vm_nf_off.as<int32_t>() : nullptr, owner_off ? c->vm_ow_bytes.as<char>() : nullptr,
+                       owner_off ? c->vm_ow_off.as<int32_t>() : nullptr, req_flags ? c->vm_rflags.as<uint32_t>() : nullptr, vmodel_tab(c),
+                       vmodel_models(c), c->vm_ans.as<mmp_vmodel_answer>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, copy_sync(c, rows_out, c->vm_ans.p, (size_t)n * sizeof(mmp_vmodel_answer), hipMemcpyDeviceToHost));
+    kt_collect(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_resolve")
+
+int mmp_vmodels_transitions(mmp_ctx *c, int64_t now_ms, int64_t lastused_age_on_add_ms, mmp_vmodel_transition *rows_out, int32_t max_rows,
+                            int32_t *n_out, mmp_vmodel_transitions_info *info_out)
+try {
+    if (!c || !n_out || max_rows < 0 || (max_rows > 0 && !rows_out)) return fail(c, MMP_EINVAL, "mmp_vmodels_transitions: bad argument");
+    // read-only, the locking of mmp_registry_unresolved: batch_mu owns c->stream and the plans' scratch
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, "mmp_vmodels_transitions")) return rc;
+    *n_out = 0;
+    if (info_out) *info_out = mmp_vmodel_transitions_info{};
+    const int32_t V = c->have_vmodels ? c->vid_n : 0;
+    if (V == 0) return MMP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const int nb = div_up(V, kVmBlock);
+    const int32_t cap = std::min(max_rows, V);
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
+    HIP_TRY(c, c->vm_list.ensure((size_t)std::max(cap, 1) * sizeof(mmp_vmodel_transition)));
+    int32_t *counts = c->plan.block_counts.as<int32_t>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
+    const VmTransArgs A{vmodel_tab(c), vmodel_models(c), now_ms, lastused_age_on_add_ms};
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(vm_trans_count_kernel, dim3(nb), dim3(kVmBlock), 0, st, A, counts);
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, counts, nb, INT32_MAX, INT32_MAX, ps);
+    if (cap > 0) hipLaunchKernelGGL(vm_trans_list_kernel, dim3(nb), dim3(kVmBlock), 0, st, A, counts, c->vm_list.as<mmp_vmodel_transition>(), cap);
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    PruneScalars h{};
+    HIP_TRY(c, copy_sync(c, &h, ps, sizeof h, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    const int32_t take = std::min(h.n_edits, cap);
+    if (take > 0) HIP_TRY(c, copy_sync(c, rows_out, c->vm_list.p, (size_t)take * sizeof(mmp_vmodel_transition), hipMemcpyDeviceToHost));
+    *n_out = h.n_edits;
+    if (info_out) {
+        info_out->n_listed = h.n_edits;
+        info_out->n_promote = h.n_removed;
+        info_out->n_ensure_loaded = h.n_edits - h.n_removed;
+        info_out->n_host_skipped = h.n_kept;
+        info_out->truncated = h.n_edits > max_rows ? 1 : 0;
+    }
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_transitions")
+
+int mmp_vmodels_get(mmp_ctx *c, int32_t first_row, int32_t n_rows, char *id_bytes_out, int32_t max_id_bytes, int32_t *id_off_out,
+                    int32_t *n_id_bytes_out, uint32_t *flags_out, char *str_bytes_out, int32_t max_str_bytes, int32_t *str_off_out,
+                    int32_t *n_str_bytes_out)
+try {
+    if (!c || first_row < 0 || n_rows < 0 || !n_id_bytes_out || !n_str_bytes_out || max_id_bytes < 0 || max_str_bytes < 0 ||
+        (max_id_bytes > 0 && !id_bytes_out) || (max_str_bytes > 0 && !str_bytes_out))
+        return fail(c, MMP_EINVAL, "mmp_vmodels_get: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t V = c->have_vmodels ? c->vid_n : 0;
+    if ((int64_t)first_row + n_rows > V)
+        return fail(c, MMP_EINVAL, "mmp_vmodels_get: rows [%d, %d + %d) of %d", first_row, first_row, n_rows, V);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    std::vector<int32_t> offs((size_t)n_rows + 1, 0);
+    std::vector<VmRow> rows((size_t)n_rows);
+    std::vector<char> arena;
+    if (n_rows > 0) {
+        HIP_TRY(c, copy_sync(c, offs.data(), c->vid_off.as<int32_t>() + first_row, ((size_t)n_rows + 1) * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, copy_sync(c, rows.data(), c->vm_rows.as<VmRow>() + first_row, (size_t)n_rows * sizeof(VmRow), hipMemcpyDeviceToHost));
+    }
+    int64_t sb = 0;
+    for (const VmRow &r : rows) sb += (int64_t)r.len[0] + r.len[1] + r.len[2];
+    if (sb > INT32_MAX) return fail(c, MMP_EINVAL, "mmp_vmodels_get: more than 2^31 string bytes; ask for fewer rows");
+    const int32_t nb = offs[n_rows] - offs[0];
+    const bool want_str = sb > 0 && max_str_bytes >= sb;
+    if (want_str) {  // the rows' strings lie anywhere in the arena: one copy of it, sliced here
+        arena.resize((size_t)c->vm_arena_bytes);
+        HIP_TRY(c, copy_sync(c, arena.data(), c->vm_arena.p, arena.size(), hipMemcpyDeviceToHost));
+    }
+    if (nb > 0 && max_id_bytes >= nb)
+        HIP_TRY(c, copy_sync(c, id_bytes_out, c->vid_bytes.as<char>() + offs[0], (size_t)nb, hipMemcpyDeviceToHost));
+    *n_id_bytes_out = nb;
+    *n_str_bytes_out = (int32_t)sb;
+    if (id_off_out)
+        for (int32_t r = 0; r <= n_rows; r++) id_off_out[r] = offs[r] - offs[0];
+    int32_t o = 0;
+    for (int32_t r = 0; r < n_rows; r++) {
+        if (flags_out) flags_out[r] = rows[r].flags;
+        for (int s = 0; s < 3; s++) {
+            if (str_off_out) str_off_out[3 * r + s] = o;
+            if (want_str && rows[r].len[s]) memcpy(str_bytes_out + o, arena.data() + rows[r].off[s], (size_t)rows[r].len[s]);
+            o += rows[r].len[s];
+        }
+    }
+    if (str_off_out) str_off_out[3 * (size_t)n_rows] = o;
+    if (c->prof) c->last_kernel_ms = -1;  // copies, no kernel
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_get")
+
+int mmp_vmodels_info(mmp_ctx *c, mmp_vmodels_stats *out)
+try {
+    if (!c || !out) return fail(c, MMP_EINVAL, "mmp_vmodels_info: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    *out = mmp_vmodels_stats{};
+    if (!c->have_vmodels) return MMP_OK;
+    out->n_rows = c->vid_n;
+    out->n_live = c->vm_live_rows;
+    out->arena_bytes = c->vm_arena_bytes;
+    out->live_bytes = c->vm_live_bytes;
+    out->capacity = (int32_t)(c->vid_mask + 1);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_info")
 
 int mmp_models_retire(mmp_ctx *c, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_models,
                       int32_t *n_models_after_out)
@@ -6785,8 +7123,7 @@ try {
     // the by-key stage, the parser, the size pass, the scan of the sizes, and the one read-back that decides whether anything is written
     KT_BEGIN(c, st);
     if (model_idx_out)
-        mid_resolve_launch(c, n, ModelIdTab{c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), c->mid_mask, c->mid_bytes.as<char>(),
-                                            c->mid_off.as<int32_t>()});
+        mid_resolve_launch(c, n, model_id_tab(c).published(), c->tune.model_id_hash_bits);
     hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
     hipLaunchKernelGGL(models_register_kernel<false>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
     HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));

@@ -447,6 +447,109 @@ class Solver:
             self._models = self._ent_pod = None  # (the registry now lives on the device only, as after ingest_models_json)
         return status[:n], idx[:n], lul[:n], n_app.value
 
+    # ---- the vmodel table (VModelManager.java:101-110) ----
+
+    def vmodels_events_json_raw(self, keys, values, deleted=None, flags=_lib.VMEV_APPEND, key_off=None, off=None, fill=0,
+                                null_idx=False, null_status=False):
+        """mmp_vmodels_events_json without the error check (tests: refusals): the outputs are pre-filled with `fill`, key_off /
+        off replace the packed offsets.  Returns (status, vmodel_idx, n_appended, rc)."""
+        kblob, koff = self._pack(keys)
+        koff32 = koff.astype(np.int32) if key_off is None else np.ascontiguousarray(key_off, dtype=np.int32)
+        blob, voff = self._pack(values)
+        if off is not None:
+            voff = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(keys)
+        assert len(values) == n
+        deleted = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+        status = np.zeros(max(n, 1), np.int32)
+        idx = np.zeros(max(n, 1), np.int32)
+        status.view(np.uint8)[:] = fill
+        idx.view(np.uint8)[:] = fill
+        n_app = C.c_int32(-1)
+        rc = self.lib.mmp_vmodels_events_json(self.h, kblob, ptr(koff32), blob, ptr(voff), n, ptr(deleted), flags,
+                                              None if null_idx else ptr(idx), None if null_status else ptr(status), C.byref(n_app))
+        return status[:n], idx[:n], n_app.value, rc
+
+    def vmodels_events_json(self, keys, values, deleted=None, append=True):
+        """The vmodel listener's events by key (mmp_vmodels_events_json): keys[i] is the vmodel id (bytes/str), values[i] its
+        VModelRecord JSON, deleted[i] marks ENTRY_DELETED.  Returns (status, vmodel_idx, n_appended)."""
+        status, idx, n_app, rc = self.vmodels_events_json_raw(keys, values, deleted, _lib.VMEV_APPEND if append else 0)
+        self._ck(rc)
+        return status, idx, n_app
+
+    def vmodels_resolve_raw(self, keys, nf=None, owners=None, req_flags=None, fill=0, key_off=None, null_out=False):
+        """mmp_vmodels_resolve without the error check: nf / owners are lists of bytes/str/None (None and b"" are Java null), or
+        None for a NULL buffer.  Returns (answers as VMODEL_ANSWER, rc)."""
+        n = len(keys)
+        kblob, koff = self._pack(keys)
+        koff32 = koff.astype(np.int32) if key_off is None else np.ascontiguousarray(key_off, dtype=np.int32)
+        nblob = noff = oblob = ooff = None
+        if nf is not None:
+            nblob, noff = self._pack([x if x is not None else b"" for x in nf])
+            noff = noff.astype(np.int32)
+        if owners is not None:
+            oblob, ooff = self._pack([x if x is not None else b"" for x in owners])
+            ooff = ooff.astype(np.int32)
+        rf = None if req_flags is None else np.ascontiguousarray(req_flags, dtype=np.uint32)
+        out = np.zeros(max(n, 1), _lib.VMODEL_ANSWER)
+        out.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_vmodels_resolve(self.h, kblob, ptr(koff32), n, nblob, ptr(noff), oblob, ptr(ooff), ptr(rf),
+                                          None if null_out else ptr(out))
+        return out[:n], rc
+
+    def vmodels_resolve(self, keys, nf=None, owners=None, req_flags=None):
+        """resolveVModelId and the classes of getVModelStatus, one answer per key (mmp_vmodels_resolve)."""
+        out, rc = self.vmodels_resolve_raw(keys, nf, owners, req_flags)
+        self._ck(rc)
+        return out
+
+    def vmodels_transitions_raw(self, now_ms, lastused_age_on_add_ms, max_rows, fill=0, null_rows=False):
+        """mmp_vmodels_transitions without the error check.  Returns (rows buffer of max_rows, n, info, rc)."""
+        rows = np.zeros(max(int(max_rows), 1), _lib.VMODEL_TRANSITION)
+        info = np.zeros(1, _lib.VMODEL_TRANSITIONS_INFO)
+        rows.view(np.uint8)[:] = fill
+        info.view(np.uint8)[:] = fill
+        n = C.c_int32(-1)
+        rc = self.lib.mmp_vmodels_transitions(self.h, int(now_ms), int(lastused_age_on_add_ms), None if null_rows else ptr(rows),
+                                              int(max_rows), C.byref(n), ptr(info))
+        return rows[:max(int(max_rows), 0)], n.value, info[0], rc
+
+    def vmodels_transitions(self, now_ms, lastused_age_on_add_ms):
+        """The leader's transition pass (mmp_vmodels_transitions): sizes first, then the rows.  Returns (rows, info)."""
+        _, n, _, rc = self.vmodels_transitions_raw(now_ms, lastused_age_on_add_ms, 0, null_rows=True)
+        self._ck(rc)
+        rows, n2, info, rc = self.vmodels_transitions_raw(now_ms, lastused_age_on_add_ms, n)
+        self._ck(rc)
+        assert n2 == n
+        return rows[:n], info
+
+    def vmodels_info(self):
+        """Rows, live rows, arena bytes, live arena bytes and table capacity of the vmodel table (mmp_vmodels_info)."""
+        out = np.zeros(1, _lib.VMODELS_STATS)
+        self._ck(self.lib.mmp_vmodels_info(self.h, ptr(out)))
+        return out[0]
+
+    def vmodels_get(self, first_row=0, n_rows=None):
+        """Rows [first_row, first_row + n_rows) of the vmodel table (mmp_vmodels_get); n_rows=None: up to the last row.  Returns
+        (ids, flags, strings): strings[r] = (amid, tmid, o) as bytes, None where the flags say null."""
+        if n_rows is None:
+            n_rows = int(self.vmodels_info()["n_rows"]) - first_row
+        nid, nstr = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mmp_vmodels_get(self.h, int(first_row), int(n_rows), None, 0, None, C.byref(nid), None, None, 0, None,
+                                          C.byref(nstr)))
+        ids = np.zeros(max(nid.value, 1), np.uint8)
+        ioff = np.zeros(n_rows + 1, np.int32)
+        flags = np.zeros(max(n_rows, 1), np.uint32)
+        sb = np.zeros(max(nstr.value, 1), np.uint8)
+        soff = np.zeros(3 * n_rows + 1, np.int32)
+        self._ck(self.lib.mmp_vmodels_get(self.h, int(first_row), int(n_rows), ptr(ids), nid.value, ptr(ioff), C.byref(nid), ptr(flags),
+                                          ptr(sb), nstr.value, ptr(soff), C.byref(nstr)))
+        iraw, sraw = ids.tobytes(), sb.tobytes()
+        null = (_lib.VMF_ACTIVE_NULL, _lib.VMF_TARGET_NULL, _lib.VMF_OWNER_NULL)
+        strings = [tuple(None if flags[r] & null[k] else sraw[soff[3 * r + k]:soff[3 * r + k + 1]] for k in range(3))
+                   for r in range(n_rows)]
+        return [iraw[ioff[r]:ioff[r + 1]] for r in range(n_rows)], flags[:n_rows].copy(), strings
+
     def models_retire(self, rows, empty_only=False):
         """Retire registry rows (mmp_models_retire): the rows leave the index space, registry and id table are compacted on the
         device.  Returns remap, int32[M0]: the new row of every old row, -1 for a retired one."""
