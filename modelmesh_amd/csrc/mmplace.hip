@@ -6918,6 +6918,82 @@ try {
     return MMP_OK;
 } MMP_CATCH(c, "mmp_models_status")
 
+// THE TWO-PASS FRAME of the "next stored value" calls (rewrite_kernels.hpp, register_kernels.hpp): stored values in, rendered
+// values out.  The caller (owner of batch_mu, the device set, every refusal behind it) has staged its own inputs and filled its
+// own members of A; the frame stages the stored values where the parser reads them and fills StoredArgs.  Size bracket: `front`
+// (launches in front of the parser), ingest_models_kernel as over non-deleted events (rows and entries into scratch), the size
+// pass, the scan of the sizes; then the ONE read-back — the offsets and every array of `back` — that decides whether anything is
+// written; write bracket: the write pass and the copy of the bytes, where out_buf holds them.  Nothing reaches the caller's
+// arrays before the last step that can fail, and the call's device span is the sum of the two brackets.
+struct RenderBack {
+    void *host;  // the caller's array (nullptr with 0 bytes: not asked for)
+    const DevBuf *dev;
+    size_t bytes;
+};
+extern "C++" template <class Args, class Front>
+int render_stored_values(mmp_ctx *c, const char *fn, const char *old_buf, const int64_t *old_off, int32_t n, Args &A, void (*size_pass)(Args),
+                         void (*write_pass)(Args), Front &&front, std::initializer_list<RenderBack> back, char *out_buf, int64_t out_cap,
+                         int64_t *out_off, int64_t *n_bytes_out)
+{
+    hipStream_t st = c->stream;
+    std::vector<int64_t> rel;
+    if (const int rc = stage_strings(c, fn, "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
+    IngestModelsArgs J;
+    size_t ent_cap;
+    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
+    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+    J.rows = c->j_rows.as<mmp_model_row>();
+    HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
+    HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
+    int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
+    A.buf = J.buf;
+    A.off = J.off;
+    A.n = n;
+    A.pstatus = J.status;
+    A.prow = J.rows;
+    A.len = d_len;
+    A.out_off = d_off;
+    const dim3 grid(div_up(n, kJWaves)), block(kJBlock);
+    KT_BEGIN(c, st);
+    front();
+    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), block, 0, st, J);
+    hipLaunchKernelGGL(size_pass, grid, block, 0, st, A);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int64_t> h_off((size_t)n + 1);
+    std::vector<std::vector<char>> h_back;
+    HIP_TRY(c, hipMemcpyAsync(h_off.data(), d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    for (const RenderBack &b : back) {
+        h_back.emplace_back(b.bytes);
+        if (b.bytes) HIP_TRY(c, hipMemcpyAsync(h_back.back().data(), b.dev->p, b.bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    const double size_ms = c->last_kernel_ms;
+    const int64_t total = h_off[n];
+    if (out_buf && out_cap >= total && total > 0) {
+        HIP_TRY(c, c->rw_out.ensure((size_t)total));
+        A.out = c->rw_out.as<char>();
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(write_pass, grid, block, 0, st, A);
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, copy_sync(c, out_buf, c->rw_out.p, (size_t)total, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        kt_add(c, size_ms);  // the call's device span: size + write
+    }
+    memcpy(out_off, h_off.data(), (size_t)(n + 1) * 8);
+    for (size_t k = 0; k < back.size(); k++)
+        if (back.begin()[k].bytes) memcpy(back.begin()[k].host, h_back[k].data(), back.begin()[k].bytes);
+    *n_bytes_out = total;
+    return MMP_OK;
+}
+
 int mmp_models_rewrite_json(mmp_ctx *c, const int32_t *rows, int32_t n, const char *old_buf, const int64_t *old_off,
                             const int64_t *last_unload, const int32_t *fail_pod, const char *fail_msg, const int32_t *fail_msg_off,
                             uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off, int32_t *status_out, int64_t *n_bytes_out)
@@ -6947,14 +7023,6 @@ try {
     }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    // the old values where the parser reads them, and its verdict on each as a non-deleted event (rows and entries into scratch)
-    std::vector<int64_t> rel;
-    if (const int rc = stage_strings(c, "mmp_models_rewrite_json", "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
-    IngestModelsArgs J;
-    size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
-    J.rows = c->j_rows.as<mmp_model_row>();
     // the call's own inputs
     std::vector<int32_t> mrel;
     HIP_TRY(c, c->rw_rows.ensure((size_t)n * 4));
@@ -6978,20 +7046,9 @@ try {
         HIP_TRY(c, hipStreamSynchronize(st));  // (the host store may change once batch_mu is released)
         c->idd_gen = c->id_gen;
     }
-    HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
-    HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
     HIP_TRY(c, c->rw_status.ensure((size_t)n * 4));
-    int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
-    size_t scan_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
-    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-    HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
     RewriteArgs A{};
-    A.buf = J.buf;
-    A.off = J.off;
-    A.n = n;
     A.rows = c->rw_rows.as<int32_t>();
-    A.pstatus = J.status;
     A.models = c->models.as<mmp_model_row>();
     A.ent_pod = c->ent_pod.as<int32_t>();
     A.ent_time = c->ent_time.as<int64_t>();
@@ -7002,39 +7059,9 @@ try {
     A.fail_pod = fail_pod ? c->rw_fpod.as<int32_t>() : nullptr;
     A.fail_msg = fail_pod ? c->rw_fmsg.as<char>() : nullptr;
     A.fail_msg_off = fail_pod ? c->rw_fmoff.as<int32_t>() : nullptr;
-    A.len = d_len;
-    A.out_off = d_off;
     A.status = c->rw_status.as<int32_t>();
-    // the size pass, the scan of the sizes, and the one read-back that decides whether anything is written
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
-    hipLaunchKernelGGL(models_rewrite_kernel<false>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
-    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<int64_t> h_off((size_t)n + 1);
-    std::vector<int32_t> h_status(n);
-    HIP_TRY(c, hipMemcpyAsync(h_off.data(), d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_status.data(), c->rw_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    const double size_ms = c->last_kernel_ms;
-    const int64_t total = h_off[n];
-    if (out_buf && out_cap >= total && total > 0) {
-        HIP_TRY(c, c->rw_out.ensure((size_t)total));
-        A.out = c->rw_out.as<char>();
-        KT_BEGIN(c, st);
-        hipLaunchKernelGGL(models_rewrite_kernel<true>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
-        KT_END(c, st);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, copy_sync(c, out_buf, c->rw_out.p, (size_t)total, hipMemcpyDeviceToHost));
-        kt_collect(c);
-        kt_add(c, size_ms);  // the call's device span: size + write
-    }
-    memcpy(out_off, h_off.data(), (size_t)(n + 1) * 8);
-    memcpy(status_out, h_status.data(), (size_t)n * 4);
-    *n_bytes_out = total;
-    return MMP_OK;
+    return render_stored_values(c, "mmp_models_rewrite_json", old_buf, old_off, n, A, models_rewrite_kernel<false>, models_rewrite_kernel<true>,
+                                [] {}, {{status_out, &c->rw_status, (size_t)n * 4}}, out_buf, out_cap, out_off, n_bytes_out);
 } MMP_CATCH(c, "mmp_models_rewrite_json")
 
 int mmp_models_register_json(mmp_ctx *c, const mmp_register_req *reqs, int32_t n, const char *keys, const int32_t *key_off,
@@ -7077,85 +7104,34 @@ try {
     }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    // stage_strings, three times: the stored values where the parser reads them, the requests' strings, the keys where the by-key
-    // stage reads them
-    std::vector<int64_t> rel;
+    // the requests, their strings, and the keys where the by-key stage reads them
     std::vector<int32_t> irel, krel;
-    if (const int rc = stage_strings(c, fn, "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
     if (const int rc = stage_strings(c, fn, "info ", info, info_off, 3 * n, c->rg_info, c->rg_ioff, irel)) return rc;
     if (model_idx_out) {
         if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
         HIP_TRY(c, c->me_hash.ensure((size_t)n * 8));
         HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
     }
-    // the parser's verdict on each stored value as a non-deleted event, and the lu it read (rows and entries into scratch)
-    IngestModelsArgs J;
-    size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
-    J.rows = c->j_rows.as<mmp_model_row>();
     HIP_TRY(c, c->rg_reqs.ensure((size_t)n * sizeof(mmp_register_req)));
     HIP_TRY(c, hipMemcpyAsync(c->rg_reqs.p, reqs, (size_t)n * sizeof(mmp_register_req), hipMemcpyHostToDevice, st));
     HIP_TRY(c, c->rg_cls.ensure((size_t)n * 4));
     HIP_TRY(c, c->rg_lu.ensure((size_t)n * 8));
-    HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
-    HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
-    int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
-    size_t scan_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
-    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-    HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
     RegisterArgs A{};
-    A.buf = J.buf;
-    A.off = J.off;
-    A.n = n;
     A.reqs = c->rg_reqs.as<mmp_register_req>();
     A.info = c->rg_info.as<char>();
     A.info_off = c->rg_ioff.as<int32_t>();
-    A.pstatus = J.status;
-    A.prow = J.rows;
     A.now = now_ms;
     A.age = lastused_age_on_add_ms;
-    A.len = d_len;
-    A.out_off = d_off;
     A.cls = c->rg_cls.as<int32_t>();
     A.last_used = c->rg_lu.as<int64_t>();
-    // the by-key stage, the parser, the size pass, the scan of the sizes, and the one read-back that decides whether anything is written
-    KT_BEGIN(c, st);
-    if (model_idx_out)
-        mid_resolve_launch(c, n, model_id_tab(c).published(), c->tune.model_id_hash_bits);
-    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
-    hipLaunchKernelGGL(models_register_kernel<false>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
-    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<int64_t> h_off((size_t)n + 1), h_lu(n);
-    std::vector<int32_t> h_cls(n), h_idx(model_idx_out ? n : 0);
-    HIP_TRY(c, hipMemcpyAsync(h_off.data(), d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_cls.data(), c->rg_cls.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_lu.data(), c->rg_lu.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (model_idx_out) HIP_TRY(c, hipMemcpyAsync(h_idx.data(), c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    kt_collect(c);
-    const double size_ms = c->last_kernel_ms;
-    const int64_t total = h_off[n];
-    if (out_buf && out_cap >= total && total > 0) {
-        HIP_TRY(c, c->rw_out.ensure((size_t)total));
-        A.out = c->rw_out.as<char>();
-        KT_BEGIN(c, st);
-        hipLaunchKernelGGL(models_register_kernel<true>, dim3(div_up(n, kJWaves)), dim3(kJBlock), 0, st, A);
-        KT_END(c, st);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, copy_sync(c, out_buf, c->rw_out.p, (size_t)total, hipMemcpyDeviceToHost));
-        kt_collect(c);
-        kt_add(c, size_ms);  // the call's device span: size + write
-    }
-    memcpy(out_off, h_off.data(), (size_t)(n + 1) * 8);
-    memcpy(class_out, h_cls.data(), (size_t)n * 4);
-    memcpy(last_used_out, h_lu.data(), (size_t)n * 8);
-    if (model_idx_out) memcpy(model_idx_out, h_idx.data(), (size_t)n * 4);
-    *n_bytes_out = total;
-    return MMP_OK;
+    const auto by_key = [&] {  // the rows of the keys, in front of the parser
+        if (model_idx_out) mid_resolve_launch(c, n, model_id_tab(c).published(), c->tune.model_id_hash_bits);
+    };
+    return render_stored_values(c, fn, old_buf, old_off, n, A, models_register_kernel<false>, models_register_kernel<true>, by_key,
+                                {{class_out, &c->rg_cls, (size_t)n * 4},
+                                 {last_used_out, &c->rg_lu, (size_t)n * 8},
+                                 {model_idx_out, &c->me_row, model_idx_out ? (size_t)n * 4 : 0}},
+                                out_buf, out_cap, out_off, n_bytes_out);
 } MMP_CATCH(c, "mmp_models_register_json")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc

@@ -15,10 +15,9 @@
 //   MALFORMED the parser's own verdict on the stored value;  HOST  a compared member the device will not decide (an escape in a
 //            compared string, an encKey / mPath / type of another kind, a refs that is no int32)
 //
-// ONE GRAMMAR, as in rewrite_kernels.hpp: a value that fits the LDS tile is staged and classified by j_scan, lanes take members
-// (64 per round), the last occurrence of each compared name is the wave max of its member index, and the string comparison is
-// spread over the lanes; a longer value is walked by lane 0 through j_members, which leaves the same four value spans.  The verdict
-// is ingest_models_kernel's, which has run over the same staged values and also leaves lu.
+// ONE GRAMMAR and ONE WALK, rewrite_kernels.hpp's rw_walk: it keeps every member not named lu and notes the value span of the last
+// occurrence of each compared name, on the tile or, for a longer value, by lane 0; the string comparison is spread over the
+// lanes.  The verdict is ingest_models_kernel's, which has run over the same staged values and also leaves lu.
 //
 // One kernel body, two instantiations: the size pass settles class, last_used and the bytes a value takes, the write pass runs
 // the same code with the stores switched on.  A wavefront takes one request (measured beside the rewrite).
@@ -27,21 +26,13 @@
 
 namespace mmp {
 
-struct RegisterArgs {
-    const char *buf;  // the staged stored values (what the parser has just read); an empty span: registry.get() == null
-    const int64_t *off;
-    int32_t n;
+struct RegisterArgs : StoredArgs {  // (an empty span of buf: registry.get() == null; prow[i].last_used = lu)
     const mmp_register_req *reqs;
     const char *info;  // type, encKey, mPath of request i = spans 3i, 3i + 1, 3i + 2
     const int32_t *info_off;
-    const int32_t *pstatus;      // the parser's verdict on value i
-    const mmp_model_row *prow;   // ... and the row it read: last_used = lu
     int64_t now, age;
-    int64_t *len;            // size pass: bytes of value i
-    const int64_t *out_off;  // write pass: exclusive scan of len
     int32_t *cls;
     int64_t *last_used;
-    char *out;
 };
 
 enum RegSlot { kRegType, kRegEncKey, kRegMPath, kRegRefs, kRegCompared, kRegLu = kRegCompared };
@@ -134,8 +125,7 @@ __device__ __forceinline__ int32_t reg_decide(RwOut &E, const RegisterArgs &A, c
     if (load_now || !(ts > (int64_t)((uint64_t)lu + (uint64_t)A.age))) return MMP_MREG_EXISTS;  // :3120, :3129
     const int64_t t = ts == 0 ? A.now : ts;  // updateLastUsed, ModelRecord.java:239-246: 0 means now, and only upwards
     rw_long<WRITE>(E, "\"lu\":", 5, t > lu ? t : lu);
-    if (E.units == 0) rw_close<WRITE>(E, '{');
-    rw_close<WRITE>(E, '}');
+    rw_close_record<WRITE>(E);
     return MMP_MREG_TOUCHED;
 }
 
@@ -163,17 +153,9 @@ __global__ __launch_bounds__(kJBlock) void models_register_kernel(RegisterArgs A
                                           : ict > 0 ? ict : (int64_t)((uint64_t)A.now - (uint64_t)A.age * (load_now ? 1ull : 6ull));
     const int32_t o0 = A.info_off[3 * i], o1 = A.info_off[3 * i + 1], o2 = A.info_off[3 * i + 2], o3 = A.info_off[3 * i + 3];
 
-    RwOut E{A.out, 0, 0, 0};
-    if (WRITE) {
-        E.pos = A.out_off[i];
-        E.end = A.out_off[i + 1];
-    }
-    const int64_t start = E.pos;
+    RwOut E = rw_open<WRITE>(A, i);
     int32_t cls;
-
-    j_load_offsets(A.off, i, i + 1, S);
-    const char *b = A.buf + S.off[0], *e = A.buf + S.off[1];
-    if (b == e) {  // registry.get() == null
+    if (A.off[i + 1] == A.off[i]) {  // registry.get() == null
         if (del)
             cls = MMP_MREG_ABSENT;  // :3187: fine if not found
         else {  // new ModelRecord(type, encKey, mPath, false) + setLastUsed, :3135-3137, as Jackson writes it (defaults omitted)
@@ -181,90 +163,29 @@ __global__ __launch_bounds__(kJBlock) void models_register_kernel(RegisterArgs A
             if (o2 > o1) reg_string<WRITE>(E, "\"encKey\":\"", 10, A.info + o1, o2 - o1);
             if (o3 > o2) reg_string<WRITE>(E, "\"mPath\":\"", 9, A.info + o2, o3 - o2);
             rw_long<WRITE>(E, "\"lu\":", 5, ts);
-            rw_close<WRITE>(E, '}');
+            rw_close_record<WRITE>(E);
             cls = MMP_MREG_CREATED;
         }
     } else if (A.pstatus[i] != 0)
         cls = MMP_MREG_MALFORMED;
     else {
-        const int64_t lu = A.prow[i].last_used;
-        int vs[kRegCompared] = {-1, -1, -1, -1}, ve[kRegCompared] = {-1, -1, -1, -1};
-        if (j_group_len(S, 0, 1) == 1) {
-            // ---- the tile: one lane per member, 64 members a round; members other than lu are the units of a touched value
-            j_stage_and_scan(A.buf, 0, 1, S);
-            const JView R = j_view(S, 0);
-            int last[kRegCompared] = {-1, -1, -1, -1};  // member index of the last occurrence of each compared name
-            for (int base = 0; base < R.n1; base += 64) {
-                const int j = base + lane;
-                int len = -1, soff = 0, slot = -1;
-                JMember M;
-                if (j < R.n1 && j_member_at(R, R.c1, R.m1, R.f, j, M)) {
-                    slot = reg_slot_of(M.h, M.klen, M.kp);
-                    if (slot != kRegLu) {
-                        int ce = j == R.n1 - 1 ? R.g : j_nth_after(R.m1, R.nch, R.f, j);
-                        if (ce >= 0) {
-                            while (ce > M.v && j_is_ws(R.by[ce - 1])) ce--;
-                            soff = (int)(M.kp - R.by) - 1;
-                            len = ce - soff;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < kRegCompared; s++) {  // the wave max of the member index: the highest lane of the round that holds the name
-                    const uint64_t m = __ballot(slot == s);
-                    if (m) last[s] = base + 63 - __clzll((unsigned long long)m);
-                }
-                rw_put_spans<WRITE>(E, E.units, R.by, soff, len);
-            }
-#pragma unroll
-            for (int s = 0; s < kRegCompared; s++) {
-                JMember M;
-                if (last[s] >= 0 && j_member_at(R, R.c1, R.m1, R.f, last[s], M)) {
-                    int ce = last[s] == R.n1 - 1 ? R.g : j_nth_after(R.m1, R.nch, R.f, last[s]);
-                    if (ce >= 0) {
-                        while (ce > M.v && j_is_ws(R.by[ce - 1])) ce--;
-                        vs[s] = M.v;
-                        ve[s] = ce;
-                    }
-                }
-            }
-            cls = reg_decide<WRITE>(E, A, R.by, vs, ve, del, load_now, ts, lu, A.info, o0, o1, o2, o3);
-        } else {
-            // ---- the same by lane 0 through j_members; the spans are offsets into the value
-            if (lane == 0) {
-                JCur c{b, e, false};
-                j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
-                    j_ws(c);
-                    const char *v = c.p;
-                    j_skip_value(c);
-                    if (c.bad) return;
-                    const int slot = reg_slot_of(h, klen, kp);
-                    if (slot == kRegLu) return;
-#pragma unroll
-                    for (int s = 0; s < kRegCompared; s++)
-                        if (slot == s) {
-                            vs[s] = (int)(v - b);
-                            ve[s] = (int)(c.p - b);
-                        }
-                    rw_putc<WRITE>(E, E.pos++, E.units++ == 0 ? '{' : ',');
-                    for (const char *p = kp - 1; p < c.p; p++) rw_putc<WRITE>(E, E.pos++, (unsigned char)*p);
-                });
-            }
-            E.pos = (int64_t)shfl_u64((uint64_t)E.pos, 0);
-            E.units = shfl_i32(E.units, 0);
-#pragma unroll
-            for (int s = 0; s < kRegCompared; s++) {
-                vs[s] = shfl_i32(vs[s], 0);
-                ve[s] = shfl_i32(ve[s], 0);
-            }
-            cls = reg_decide<WRITE>(E, A, b, vs, ve, del, load_now, ts, lu, A.info, o0, o1, o2, o3);
-        }
+        // ---- every member not named lu is a unit of a touched value; noted: the last occurrence of each compared name
+        int vs[kRegCompared], ve[kRegCompared];
+        const bool tile = rw_walk<WRITE>(A, i, S, E, [](uint64_t h, int klen, const auto *kp, uint32_t) {
+            const int slot = reg_slot_of(h, klen, kp);
+            return RwMember{slot != kRegLu, slot < kRegCompared ? slot : -1};
+        }, vs, ve);
+        const auto decide = [&](const auto *by) {  // (the spans are offsets into what the walk ran over)
+            return reg_decide<WRITE>(E, A, by, vs, ve, del, load_now, ts, A.prow[i].last_used, A.info, o0, o1, o2, o3);
+        };
+        cls = tile ? decide(j_view(S, 0).by) : decide(A.buf + S.off[0]);
     }
     if (!WRITE && lane == 0) {
         A.cls[i] = cls;
         A.last_used[i] = ts;
-        A.len[i] = cls == MMP_MREG_CREATED || cls == MMP_MREG_TOUCHED ? E.pos - start : 0;
+        A.len[i] = cls == MMP_MREG_CREATED || cls == MMP_MREG_TOUCHED ? E.pos : 0;
     }
 }
 
 }  // namespace mmp
+

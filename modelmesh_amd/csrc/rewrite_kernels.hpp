@@ -15,7 +15,8 @@
 //
 // ONE GRAMMAR: nothing here restates what an object is.  A value that fits the LDS tile is staged and classified by j_scan; the
 // level-1 ':' / ',' masks give the spans of its members, the level-2 masks the members of `fails`, and lanes are spread over
-// members, entries and copy bytes.  A longer value is walked by lane 0 through j_members.  The verdict (status 1) is the parser's
+// members, entries and copy bytes.  A longer value is walked by lane 0 through j_members.  Both routes over the top-level members
+// are ONE WALK, rw_walk, which register_kernels.hpp calls too: a kernel brings a classifier.  The verdict (status 1) is the parser's
 // own: ingest_models_kernel runs over the same staged values first, so the write side accepts exactly what the read side accepts.
 // What ingest_kernels.hpp leaves UNSPECIFIED (a value invalid only inside a skipped value) stays unspecified here.
 //
@@ -27,12 +28,20 @@
 
 namespace mmp {
 
-struct RewriteArgs {
-    const char *buf;      // the staged old values (the buffers the parser has just read)
+// What every "next stored value" kernel is given alike, and what the host's two-pass frame fills in (mmplace.hip, render_stored_values).
+struct StoredArgs {
+    const char *buf;  // the staged stored values (the buffers the parser has just read)
     const int64_t *off;
     int32_t n;
-    const int32_t *rows;     // registry row of value i
-    const int32_t *pstatus;  // the parser's verdict on value i
+    const int32_t *pstatus;     // the parser's verdict on value i
+    const mmp_model_row *prow;  // ... and the row it read
+    int64_t *len;               // size pass: bytes of value i
+    const int64_t *out_off;     // write pass: exclusive scan of len, out_off[n] = the total
+    char *out;
+};
+
+struct RewriteArgs : StoredArgs {
+    const int32_t *rows;  // registry row of value i
     const mmp_model_row *models;
     const int32_t *ent_pod;
     const int64_t *ent_time;
@@ -43,10 +52,7 @@ struct RewriteArgs {
     const int32_t *fail_pod;     // nullptr: no row has one
     const char *fail_msg;
     const int32_t *fail_msg_off;
-    int64_t *len;            // size pass: bytes of record i
-    const int64_t *out_off;  // write pass: exclusive scan of len, out_off[n] = the total
     int32_t *status;
-    char *out;
 };
 
 // Where a record's bytes go.  Everything is laid out as UNITS: a separator byte and what follows it, the separator being the
@@ -58,20 +64,22 @@ struct RwOut {
     int32_t units;  // units of the record object so far
 };
 
+// The record of value i: nowhere in the size pass (pos counts its bytes from 0), at the offset the scan gave it in the write pass.
+template <bool WRITE>
+__device__ __forceinline__ RwOut rw_open(const StoredArgs &A, int i)
+{
+    RwOut E{A.out, 0, 0, 0};
+    if (WRITE) {
+        E.pos = A.out_off[i];
+        E.end = A.out_off[i + 1];
+    }
+    return E;
+}
+
 template <bool WRITE>
 __device__ __forceinline__ void rw_putc(const RwOut &E, int64_t p, uint32_t ch)
 {
     if (WRITE && p < E.end) E.out[p] = (char)ch;  // (end: a record never writes into its neighbour)
-}
-
-__device__ __forceinline__ int32_t rw_wave_max(int32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int32_t t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
 }
 
 // a Java long in plain decimal, Long.MIN_VALUE included
@@ -119,6 +127,14 @@ __device__ __forceinline__ void rw_close(RwOut &E, uint32_t ch)
     E.pos++;
 }
 
+// the close of the record object; one without units is '{}'
+template <bool WRITE>
+__device__ __forceinline__ void rw_close_record(RwOut &E)
+{
+    if (E.units == 0) rw_close<WRITE>(E, '{');
+    rw_close<WRITE>(E, '}');
+}
+
 // Every lane may bring one span of `by` (len < 0: none): the spans become units behind E.pos in lane order, and every span is
 // copied by all lanes together.
 template <bool WRITE, class B>
@@ -142,6 +158,102 @@ __device__ __forceinline__ void rw_put_spans(RwOut &E, int32_t &units, const B *
     }
     E.pos += readlane_i32(incl, 63);
     units += readlane_i32(cincl, 63);
+}
+
+// The same by ONE lane, for a value longer than the tile: the separator, then the bytes [s, e) verbatim.
+template <bool WRITE>
+__device__ __forceinline__ void rw_put_serial(RwOut &E, int32_t &units, const char *s, const char *e)
+{
+    rw_putc<WRITE>(E, E.pos++, units++ == 0 ? '{' : ',');
+    for (; s < e; s++) rw_putc<WRITE>(E, E.pos++, (unsigned char)*s);
+}
+
+// The unit of member M, the j-th of the n members of the container by[open .. close] (`commas`: the mask of its level): by[soff, end),
+// from the opening quote of its key to the byte before its ',' (the closer behind the last member), blanks trimmed.
+__device__ __forceinline__ bool rw_member_span(const JView &R, const uint64_t *commas, int open, int close, int n, int j, const JMember &M,
+                                               int &soff, int &end)
+{
+    end = j == n - 1 ? close : j_nth_after(commas, R.nch, open, j);
+    if (end < 0) return false;
+    while (end > M.v && j_is_ws(R.by[end - 1])) end--;
+    soff = (int)(M.kp - R.by) - 1;
+    return true;
+}
+
+// What a caller of rw_walk says of a member: whether it stays, and the note slot it belongs to (-1: none).
+struct RwMember {
+    bool keep;
+    int note;
+};
+
+// THE MEMBER WALK of both "next stored value" kernels, by the whole wavefront over value i: every top-level member that
+// classify(hash, key length, key bytes, first byte of the value) keeps becomes a unit of the record object behind E.pos, in
+// document order, and [vs[s], ve[s]) is the value of the LAST member classified into note slot s (-1: none).  True: the value
+// fits the tile, which is staged and scanned (j_view(S, 0)) — one lane per member, 64 a round, the spans offsets into R.by.
+// False: lane 0 has walked it through j_members, the spans are offsets into the value at A.buf + S.off[0], and a member whose
+// value j_skip_value could not skip is neither kept nor noted.  E.pos, E.units and the spans are wave-uniform either way.
+template <bool WRITE, int NOTES, class Off, class C>
+__device__ __forceinline__ bool rw_walk(const StoredArgs &A, int i, JWaveLds &S, RwOut &E, const C &classify, Off (&vs)[NOTES],
+                                        Off (&ve)[NOTES])
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int s = 0; s < NOTES; s++) vs[s] = ve[s] = -1;
+    j_load_offsets(A.off, i, i + 1, S);
+    if (j_group_len(S, 0, 1) == 1) {
+        j_stage_and_scan(A.buf, 0, 1, S);
+        const JView R = j_view(S, 0);
+        for (int base = 0; base < R.n1; base += 64) {
+            const int j = base + lane;
+            int len = -1, soff = 0, end = -1, v = -1, note = -1;
+            JMember M;
+            if (j < R.n1 && j_member_at(R, R.c1, R.m1, R.f, j, M)) {
+                const RwMember k = classify(M.h, M.klen, M.kp, M.v < R.L ? (uint32_t)R.by[M.v] : 0u);
+                if ((k.keep || k.note >= 0) && rw_member_span(R, R.m1, R.f, R.g, R.n1, j, M, soff, end)) {
+                    v = M.v;
+                    note = k.note;
+                    if (k.keep) len = end - soff;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NOTES; s++) {  // the last member of the round in slot s: the highest lane that holds one
+                const uint64_t m = __ballot(note == s);
+                if (m) {
+                    const int l = 63 - __clzll((unsigned long long)m);
+                    vs[s] = readlane_i32(v, l);
+                    ve[s] = readlane_i32(end, l);
+                }
+            }
+            rw_put_spans<WRITE>(E, E.units, R.by, soff, len);
+        }
+        return true;
+    }
+    if (lane == 0) {
+        const char *b = A.buf + S.off[0];
+        JCur c{b, A.buf + S.off[1], false};
+        j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
+            j_ws(c);
+            const char *v = c.p;
+            j_skip_value(c);
+            if (c.bad) return;
+            const RwMember k = classify(h, klen, kp, v < c.e ? (uint32_t)(unsigned char)*v : 0u);
+#pragma unroll
+            for (int s = 0; s < NOTES; s++)
+                if (k.note == s) {
+                    vs[s] = (Off)(v - b);
+                    ve[s] = (Off)(c.p - b);
+                }
+            if (k.keep) rw_put_serial<WRITE>(E, E.units, kp - 1, c.p);
+        });
+    }
+    E.pos = (int64_t)shfl_u64((uint64_t)E.pos, 0);
+    E.units = shfl_i32(E.units, 0);
+#pragma unroll
+    for (int s = 0; s < NOTES; s++) {
+        vs[s] = __shfl(vs[s], 0, 64);
+        ve[s] = __shfl(ve[s], 0, 64);
+    }
+    return false;
 }
 
 // the owned names (matched as the parser matches names: raw bytes)
@@ -269,53 +381,46 @@ __device__ __forceinline__ bool rw_fails_keep(const RewriteArgs &A, const RwFail
     return false;
 }
 
-// The members of the `fails` object at tile byte `open` that stay, by the whole wavefront, one lane per member: counted
-// (EMIT false; returns how many) or put as the units of the new object.
+// The members that stay of the `fails` object the walk noted at byte `at`, by the route the walk took — the tile: one lane per
+// member, spans from the level-2 masks; else lane 0 through j_members: counted (EMIT false) or put as the units of the new
+// object.  Returns how many.
 template <bool WRITE, bool EMIT>
-__device__ __forceinline__ int32_t rw_fails_tile(RwOut &E, int32_t &funits, const RewriteArgs &A, const RwFails &F, const JView &R,
-                                                 int open)
+__device__ __forceinline__ int32_t rw_fails_members(RwOut &E, int32_t &funits, const RewriteArgs &A, const RwFails &F, const JWaveLds &S,
+                                                    bool tile, int64_t at)
 {
     const int lane = lane_id();
-    const int close = j_nth_after(R.e2, R.nch, open, 0);
-    if (close < 0) return 0;
-    const int nm = j_count(R.c2, open, close);
     int32_t kept = 0;
-    for (int base = 0; base < nm; base += 64) {
-        const int k = base + lane;
-        int len = -1, soff = 0;
-        JMember M;
-        if (k < nm && j_member_at(R, R.c2, R.m2, open, k, M) && M.p < close && rw_fails_keep(A, F, M.kp, M.klen)) {
-            int e = j_nth_after(R.m2, R.nch, M.p, 0);  // the ',' behind the value, or the closer behind the last one
-            if (e < 0 || e > close) e = close;
-            while (e > M.v && j_is_ws(R.by[e - 1])) e--;
-            soff = (int)(M.kp - R.by) - 1;
-            len = e - soff;
+    if (tile) {
+        const JView R = j_view(S, 0);
+        const int open = (int)at, close = j_nth_after(R.e2, R.nch, open, 0);
+        if (close < 0) return 0;
+        const int nm = j_count(R.c2, open, close);
+        for (int base = 0; base < nm; base += 64) {
+            const int k = base + lane;
+            int len = -1, soff = 0, end;
+            JMember M;
+            if (k < nm && j_member_at(R, R.c2, R.m2, open, k, M) && rw_fails_keep(A, F, M.kp, M.klen) &&
+                rw_member_span(R, R.m2, open, close, nm, k, M, soff, end))
+                len = end - soff;
+            if (EMIT)
+                rw_put_spans<WRITE>(E, funits, R.by, soff, len);
+            else
+                kept += __popcll((unsigned long long)__ballot(len >= 0));
         }
-        if (EMIT)
-            rw_put_spans<WRITE>(E, funits, R.by, soff, len);
-        else
-            kept += __popcll((unsigned long long)__ballot(len >= 0));
+        return kept;
     }
-    return kept;
-}
-
-// The same by ONE lane, for a value longer than the tile: the object at b[at], walked through j_members.
-template <bool WRITE, bool EMIT>
-__device__ __forceinline__ int32_t rw_fails_serial(RwOut &E, int32_t &funits, const RewriteArgs &A, const RwFails &F, const char *b,
-                                                   const char *e, int64_t at)
-{
-    JCur c{b + at, e, false};
-    int32_t kept = 0;
-    j_members(c, false, [&](uint64_t, int klen, const char *kp) {
-        j_skip_value(c);
-        if (c.bad || !rw_fails_keep(A, F, kp, klen)) return;
-        kept++;
-        if (EMIT) {
-            rw_putc<WRITE>(E, E.pos++, funits++ == 0 ? '{' : ',');
-            for (const char *q = kp - 1; q < c.p; q++) rw_putc<WRITE>(E, E.pos++, (unsigned char)*q);
-        }
-    });
-    return kept;
+    if (lane == 0) {
+        JCur c{A.buf + S.off[0] + at, A.buf + S.off[1], false};
+        j_members(c, false, [&](uint64_t, int klen, const char *kp) {
+            j_skip_value(c);
+            if (c.bad || !rw_fails_keep(A, F, kp, klen)) return;
+            kept++;
+            if (EMIT) rw_put_serial<WRITE>(E, funits, kp - 1, c.p);
+        });
+    }
+    E.pos = (int64_t)shfl_u64((uint64_t)E.pos, 0);
+    funits = shfl_i32(funits, 0);
+    return shfl_i32(kept, 0);
 }
 
 // One record per wavefront.  WRITE false: len[i] and status[i]; WRITE true: the bytes of every status-0 record at out_off[i].
@@ -362,91 +467,22 @@ __global__ __launch_bounds__(kJBlock) void models_rewrite_kernel(RewriteArgs A)
     const bool append = F.fp >= 0 && msg_len > 0 && fp_failed;
     const bool lul = A.last_unload != nullptr;
 
-    RwOut E{A.out, 0, 0, 0};
-    if (WRITE) {
-        E.pos = A.out_off[i];
-        E.end = A.out_off[i + 1];
-    }
-    const int64_t start = E.pos;
-
-    j_load_offsets(A.off, i, i + 1, S);
-    const char *b = A.buf + S.off[0], *e = A.buf + S.off[1];
-    const bool tile = j_group_len(S, 0, 1) == 1;
-    int64_t fails_at = -1;  // the '{' of the last `fails` member that is an object: tile byte / value byte
-    if (tile) {
-        // ---- the kept members: one lane per member of the record object, spans from the level-1 masks
-        j_stage_and_scan(A.buf, 0, 1, S);
-        const JView R = j_view(S, 0);
-        int32_t fails_j = -1;
-        for (int base = 0; base < R.n1; base += 64) {
-            const int j = base + lane;
-            int len = -1, soff = 0, cand = -1;
-            JMember M;
-            if (j < R.n1 && j_member_at(R, R.c1, R.m1, R.f, j, M)) {
-                if (rw_owned(M.h, M.klen, M.kp, lul)) {
-                    if (rw_is_fails(M.h, M.klen, M.kp) && M.v < R.L && R.by[M.v] == '{') cand = j;
-                } else {
-                    int ce = j == R.n1 - 1 ? R.g : j_nth_after(R.m1, R.nch, R.f, j);
-                    if (ce >= 0) {
-                        while (ce > M.v && j_is_ws(R.by[ce - 1])) ce--;
-                        soff = (int)(M.kp - R.by) - 1;
-                        len = ce - soff;
-                    }
-                }
-            }
-            fails_j = max(fails_j, rw_wave_max(cand));
-            rw_put_spans<WRITE>(E, E.units, R.by, soff, len);
-        }
-        if (fails_j >= 0) {
-            JMember M;
-            if (j_member_at(R, R.c1, R.m1, R.f, fails_j, M)) fails_at = M.v;
-        }
-    } else {
-        // ---- the same by lane 0 through j_members
-        if (lane == 0) {
-            JCur c{b, e, false};
-            j_members(c, true, [&](uint64_t h, int klen, const char *kp) {
-                j_ws(c);
-                const char *v = c.p;
-                j_skip_value(c);
-                if (c.bad) return;
-                if (rw_owned(h, klen, kp, lul)) {
-                    if (rw_is_fails(h, klen, kp) && v < e && *v == '{') fails_at = v - b;
-                    return;
-                }
-                rw_putc<WRITE>(E, E.pos++, E.units++ == 0 ? '{' : ',');
-                for (const char *q = kp - 1; q < c.p; q++) rw_putc<WRITE>(E, E.pos++, (unsigned char)*q);
-            });
-        }
-        E.pos = (int64_t)shfl_u64((uint64_t)E.pos, 0);
-        E.units = shfl_i32(E.units, 0);
-        fails_at = (int64_t)shfl_u64((uint64_t)fails_at, 0);
-    }
+    // ---- the kept members; noted: the '{' of the last `fails` member that is an object (one that is not is neither)
+    RwOut E = rw_open<WRITE>(A, i);
+    int64_t fails_at[1], fails_end[1];
+    const bool tile = rw_walk<WRITE>(A, i, S, E, [lul](uint64_t h, int klen, const auto *kp, uint32_t v0) {
+        return RwMember{!rw_owned(h, klen, kp, lul), rw_is_fails(h, klen, kp) && v0 == '{' ? 0 : -1};
+    }, fails_at, fails_end);
 
     // ---- the owned members, from the resident row
     rw_id_map<WRITE>(E, A, "\"instanceIds\":", 14, eo, nl);
     rw_id_map<WRITE>(E, A, "\"failedIn\":", 11, eo + nl, nf);
     {
-        int32_t kept = 0, funits = 0;
-        if (fails_at >= 0 && nf > 0) {
-            if (tile)
-                kept = rw_fails_tile<WRITE, false>(E, funits, A, F, j_view(S, 0), (int)fails_at);
-            else {
-                if (lane == 0) kept = rw_fails_serial<WRITE, false>(E, funits, A, F, b, e, fails_at);
-                kept = shfl_i32(kept, 0);
-            }
-        }
+        int32_t funits = 0;
+        const int32_t kept = fails_at[0] >= 0 && nf > 0 ? rw_fails_members<WRITE, false>(E, funits, A, F, S, tile, fails_at[0]) : 0;
         if (kept > 0 || append) {
             rw_head<WRITE>(E, E.units, "\"fails\":", 8);
-            if (kept > 0) {
-                if (tile)
-                    (void)rw_fails_tile<WRITE, true>(E, funits, A, F, j_view(S, 0), (int)fails_at);
-                else {
-                    if (lane == 0) (void)rw_fails_serial<WRITE, true>(E, funits, A, F, b, e, fails_at);
-                    E.pos = (int64_t)shfl_u64((uint64_t)E.pos, 0);
-                    funits = shfl_i32(funits, 0);
-                }
-            }
+            if (kept > 0) (void)rw_fails_members<WRITE, true>(E, funits, A, F, S, tile, fails_at[0]);
             if (append) {  // "<id>":{"msg":"<escaped message>"}
                 if (lane == 0) {
                     int64_t p = E.pos;
@@ -470,12 +506,12 @@ __global__ __launch_bounds__(kJBlock) void models_rewrite_kernel(RewriteArgs A)
     }
     rw_long<WRITE>(E, "\"lu\":", 5, row.last_used);
     if (lul) rw_long<WRITE>(E, "\"lul\":", 6, A.last_unload[i]);
-    if (E.units == 0) rw_close<WRITE>(E, '{');
-    rw_close<WRITE>(E, '}');
+    rw_close_record<WRITE>(E);
     if (!WRITE && lane == 0) {
         A.status[i] = 0;
-        A.len[i] = E.pos - start;
+        A.len[i] = E.pos;
     }
 }
 
 }  // namespace mmp
+

@@ -173,22 +173,44 @@ def string_batch():
 MEMBER_COUNTS = (63, 64, 65, 130)
 
 
-def member_batch():
-    """Values of 63, 64, 65 and 130 top-level members, the compared members (and lu) first and last, and as a losing first
-    occurrence with the deciding one last."""
-    items = head()
+def member_layouts():
+    """[(n, k, members)]: values of 63, 64, 65 and 130 top-level members, the compared members (and lu) first, last, around the
+    others, and as a losing first occurrence with the deciding one last, and the other way round."""
     want = [(b"type", s(b"type-2")), (b"encKey", s(b"ek")), (b"mPath", s(b"/p")), (b"refs", b"1"), (b"lu", b"9")]
     lose = [(b"type", s(b"type-1")), (b"encKey", b"null"), (b"mPath", s(b"/q")), (b"refs", b"0"), (b"lu", b"%d" % NOW)]
+    out = []
     for n in MEMBER_COUNTS:
         fill = [(b"f%d" % i, b"%d" % i) for i in range(n - len(want))]
         short = [(b"f%d" % i, b"%d" % i) for i in range(n - 2 * len(want))]
         for k, members in enumerate((want + fill, fill + want, want[:2] + fill + want[2:], lose + short + want, want + short + lose)):
             assert len(members) == n
-            old = obj(members, k % 3)
-            assert len(old) <= TILE
-            items.append((0, 0, (b"type-2", b"ek", b"/p"), old, b"m%d" % n))
-            items.append((mm.DELETE, 0, (b"", b"", b""), old, b"m%d" % n))
+            out.append((n, k, members))
+    return out
+
+
+def _member_items(value_of):
+    """head(), then each layout's value once as a touch and once as a delete."""
+    items = head()
+    for n, k, members in member_layouts():
+        old = value_of(n, k, members)
+        items.append((0, 0, (b"type-2", b"ek", b"/p"), old, b"m%d" % n))
+        items.append((mm.DELETE, 0, (b"", b"", b""), old, b"m%d" % n))
     return to_batch(items)
+
+
+def member_batch():
+    """The member layouts on the tile, in the three separator styles."""
+    def value_of(n, k, members):
+        old = obj(members, k % 3)
+        assert len(old) <= TILE
+        return old
+    return _member_items(value_of)
+
+
+def padded_member_batch():
+    """The same layouts padded past the tile (the pad in front, in the middle, at the end in turn): the serial walk sees a
+    repeated compared name, and the compared members behind 64 and more others."""
+    return _member_items(lambda n, k, members: padded(members, TILE + 1 + 13 * k, (0, n // 2, n)[k % 3]))
 
 
 def padded(members, total, pad_at):
@@ -248,7 +270,7 @@ def corpus_batch(values):
 
 def every_batch(corpus_values=()):
     """Every batch of nine requests or more that the GPU test sends."""
-    out = [sized_batch(n) for n in SIZES if n >= 9] + [string_batch(), member_batch(), tile_edge_batch(), escape_batch()]
+    out = [sized_batch(n) for n in SIZES if n >= 9] + [string_batch(), member_batch(), padded_member_batch(), tile_edge_batch(), escape_batch()]
     if corpus_values:
         out.append(corpus_batch(corpus_values))
     return out

@@ -182,6 +182,61 @@ def entry_batch(ids, stored, recs):
     return to_batch(items)
 
 
+MEMBER_COUNTS = (63, 64, 65, 130)
+NON_OBJECTS = (b"3", b"null", b'"x"')
+PAD = b',"pad":"' + b"p" * TILE + b'"'  # a kept string member behind the others: the value takes the serial route
+
+
+def fails_object(w, tag):
+    """A `fails` object for row 1 (failed: pods 0 and 2) whose kept members name their object: "<tag>-0", "<tag>-2"."""
+    p0, p2 = w.pod_ids[0].encode(), w.pod_ids[2].encode()
+    return b'{"%s":{"msg":"%s-0"},"stale":{"msg":"s"},"%s":{"msg":"%s-2"}}' % (p0, tag, p2, tag)
+
+
+def member_layouts(w):
+    """[(name, n, {member index: the value of a `fails` member there})]: one `fails` object at member 0, 63, 64 and last of
+    values of 63 .. 130 members (the highest lane of a 64-member round and the lanes on both sides of it), and two `fails`
+    members inside one round (10, 20) and across a round (10, 70): object then object, object then each kind of non-object, and
+    non-objects only."""
+    out = []
+    for n in MEMBER_COUNTS:
+        for at in sorted({0, 63, 64, n - 1}):
+            if at < n:
+                out.append(("one-%d-%d" % (n, at), n, {at: fails_object(w, b"only")}))
+    for a, b in ((10, 20), (10, 70)):
+        out.append(("obj-obj-%d" % b, 130, {a: fails_object(w, b"first"), b: fails_object(w, b"second")}))
+        for v in NON_OBJECTS:
+            out.append(("obj-%s-%d" % (v.decode(), b), 130, {a: fails_object(w, b"first"), b: v}))
+        out.append(("non-%d" % b, 130, {a: NON_OBJECTS[0], b: NON_OBJECTS[2]}))
+        out.append(("non-msg-%d" % b, 130, {a: NON_OBJECTS[1], b: NON_OBJECTS[0]}))
+    return out
+
+
+def member_value(n, fails_at, sep=0):
+    comma, colon = (x.encode() for x in SEPS[sep])
+    return b"{" + comma.join(b'"fails"%s%s' % (colon, fails_at[j]) if j in fails_at else b'"f%d"%s%d' % (j, colon, j)
+                             for j in range(n)) + b"}"
+
+
+def member_items(w, pad):
+    """One item of row 1 per layout, in the order of member_layouts: the values of up to 65 members in the three separator
+    styles in turn; a "-msg" layout brings a message for pod 0, every third one with an object replaces the entry of pod 2."""
+    items = []
+    for k, (name, n, at) in enumerate(member_layouts(w)):
+        old = member_value(n, at, k % 3 if n < 130 else 0)
+        assert len(old) <= TILE
+        if pad:
+            old = old[:-1] + PAD + b"}"
+        fp, msg = (0, b"late") if "-msg" in name else (2, b"again") if k % 3 == 2 and name[:3] != "non" else (-1, b"")
+        items.append((1, old, k, fp, msg))
+    return items
+
+
+def member_batches(w):
+    """HEAD and the member layouts: [on the tile, padded past it]."""
+    return [to_batch(head(w) + member_items(w, pad)) for pad in (False, True)]
+
+
 def run_model(batch, recs, pod_ids, lul=True):
     return mrm.rewrite_batch(batch.olds, recs, batch.rows, pod_ids, batch.last_unload if lul else None, (batch.fail_pod, batch.msgs))
 

@@ -187,3 +187,19 @@ def test_every_batch_the_gpu_test_sends_holds_all_nine_classes():
     assert {fx.TILE - 2, fx.TILE - 1, fx.TILE, fx.TILE + 1, fx.TILE + 2} <= set(lens)
     classes = fx.run_model(fx.string_batch())[1]
     assert classes.count(mm.CONFLICT) > 40 and classes.count(mm.TOUCHED) == 3 * (len(fx.STRING_LENGTHS) - 1) + 1  # (length 0: a stored "" equals nothing)
+
+
+def test_the_padded_member_layouts_answer_as_the_tile_sized_ones():
+    """The same class and last_used from either, on every class a layout is meant to reach, and values equal up to the pad."""
+    tile, padded = fx.member_batch(), fx.padded_member_batch()
+    (tv, tc, tl), (pv, pc, pl) = fx.run_model(tile), fx.run_model(padded)
+    assert (tc, tl) == (pc, pl) and len(tc) == 9 + 2 * 5 * len(fx.MEMBER_COUNTS)
+    assert {c for c in tc[9:]} == {mm.TOUCHED, mm.CONFLICT, mm.REFERENCED, mm.DELETABLE}
+    for i in range(9, len(tc)):
+        told, pold = tile.olds[i], padded.olds[i]
+        assert len(told) <= fx.TILE < len(pold)
+        drop_pad = lambda v: [(k, x) for k, x in json.loads(v, object_pairs_hook=list) if k != "pad"]  # noqa: E731
+        assert drop_pad(pold) == json.loads(told, object_pairs_hook=list)
+        assert (tv[i] is None) == (pv[i] is None) == (tc[i] != mm.TOUCHED)
+        if tv[i] is not None:
+            assert drop_pad(pv[i]) == json.loads(tv[i], object_pairs_hook=list), i

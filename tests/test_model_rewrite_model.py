@@ -186,7 +186,7 @@ def test_the_entry_point_refuses_a_null_context():
 
 def test_every_gpu_batch_meets_the_fixture_conditions():
     w, recs = _worlds()
-    batches = [fx.sized_batch(w, recs, n) for n in fx.SIZES if n >= 2] + [fx.same_row_batch(w)] + fx.tile_edge_batches(w)
+    batches = [fx.sized_batch(w, recs, n) for n in fx.SIZES if n >= 2] + [fx.same_row_batch(w)] + fx.tile_edge_batches(w) + fx.member_batches(w)
     for b in batches:
         fx.check_conditions(*fx.run_model(b, recs, w.pod_ids))
     # (n = 0 and n = 1 cannot hold three statuses: n = 1 runs once per status instead)
@@ -203,3 +203,38 @@ def test_the_tile_edge_values_have_their_sizes_and_alignments():
         assert sizes == [2046, 2047, 2048, 2049, 2050], sizes
         for v in b.olds[1:-8]:
             assert {k for k, _, _, _ in members(v, 0)} >= {b"type", b"fails", b"x", b"zz"}
+
+
+def test_the_member_layouts_reach_what_they_are_meant_to_reach():
+    """From the model alone: the last `fails` OBJECT decides wherever it stands, a `fails` that is no object is dropped and
+    decides nothing, every value parses, and the padded value of a layout is the tile-sized one up to the pad."""
+    w, recs = _worlds()
+    p0, p2 = w.pod_ids[0], w.pod_ids[2]
+    assert [p for p, _ in recs[1][3]] == [0, 2]
+    layouts = fx.member_layouts(w)
+    tile, padded = fx.member_batches(w)
+    (tv, ts), (pv, ps) = (fx.run_model(b, recs, w.pod_ids) for b in (tile, padded))
+    assert ts == ps and not any(ts[8:]) and len(tv) == 8 + len(layouts)
+    assert {n for _, n, _ in layouts} == set(fx.MEMBER_COUNTS) and {0, 62, 63, 64, 129} <= {a for _, _, at in layouts for a in at}
+    for (name, n, at), told, pold, t, p, fp, msg in zip(layouts, tile.olds[8:], padded.olds[8:], tv[8:], pv[8:], tile.fail_pod[8:],
+                                                         tile.msgs[8:]):
+        assert len(told) <= fx.TILE < len(pold) and len(members(told, 0)) == n and len(members(pold, 0)) == n + 1
+        assert p.replace(fx.PAD, b"") == t and fx.PAD in p, name
+        doc, old = json.loads(t), json.loads(told)
+        assert json.loads(p)["pad"] == "p" * fx.TILE
+        kept = [k for k in doc if k not in ("failedIn", "fails", "lul")]
+        assert kept == [k for k in old if k != "fails"] and len(kept) == n - len(at), name  # no `fails` is ever kept
+        objs = [v for _, v in sorted(at.items()) if v[:1] == b"{"]
+        want = {}
+        if objs:
+            tag = json.loads(objs[-1])[p0]["msg"][:-2]
+            assert tag == ("second" if name.startswith("obj-obj") else "first" if name.startswith("obj-") else "only")
+            want = {p0: {"msg": tag + "-0"}, p2: {"msg": tag + "-2"}}
+        if fp >= 0:
+            want.pop(w.pod_ids[fp], None)
+            want[w.pod_ids[fp]] = {"msg": msg.decode()}
+        assert doc.get("fails", {}) == want, name
+        assert ("fails" in doc) == (bool(objs) or fp >= 0) and (fp >= 0) == ("-msg" in name or (bool(objs) and fp == 2)), name
+    names = [name for name, _, _ in layouts]  # non-objects only: no `fails` without a message, one for the message alone
+    assert all("fails" not in json.loads(tv[8 + names.index(x)]) for x in ("non-20", "non-70"))
+    assert all(list(json.loads(tv[8 + names.index(x)])["fails"]) == [p0] for x in ("non-msg-20", "non-msg-70"))

@@ -96,6 +96,12 @@ def test_values_of_63_to_130_members(ctx):
     check(s, fx.member_batch())
 
 
+def test_the_member_layouts_padded_past_the_tile(ctx):
+    """The serial walk over 63 .. 130 members with a repeated compared name, each value as a touch and as a delete."""
+    _, s, _ = ctx
+    check(s, fx.padded_member_batch())
+
+
 def test_request_strings_that_need_every_escape(ctx):
     _, s, _ = ctx
     vals, _ = check(s, fx.escape_batch())

@@ -100,6 +100,14 @@ def test_one_row_64_times_under_different_fail_pods(ctx):
     same_registry(rp.compact(*s.get_models()), to_arrays(recs), "read-only")
 
 
+def test_fails_members_around_the_64_member_round_on_both_routes(ctx):
+    """`fails` at member 0, 63, 64 and last of 63 .. 130 members, two `fails` inside and across a round, objects and not: on the
+    tile, and padded past it."""
+    w, s, _, recs = ctx
+    for b in fx.member_batches(w):
+        check(s, b, recs, w.pod_ids)
+
+
 def test_rows_of_0_to_130_entries():
     ids, stored, recs = fx.entry_world()
     s = Solver(1, 1)
