@@ -1635,6 +1635,44 @@ typedef struct {
     int32_t capacity, reserved;
 } mmp_vmodels_stats; /* 32 bytes */
 int mmp_vmodels_info(mmp_ctx *ctx, mmp_vmodels_stats *out);
+/* Retire vmodel rows: the named rows leave the index space, and the vmodel rows, the string arena, the vmodel-id arena and the
+ * vmodel-id table are compacted on the device (vmodel_retire_kernels.hpp) — the counterpart of mmp_models_retire for the third
+ * resident table.  rows[0 .. n) are vmodel rows in [0, V0), V0 = the row count at the call, in any order; a row named twice is
+ * retired once.  The survivors keep their relative order and move down: a survivor's new row is its old row minus the number of
+ * retired rows below it.  remap_out (may be NULL; else max_vmodels >= V0 words): remap_out[old] = the new row, -1 for a retired
+ * one, for all V0 old rows.  *n_vmodels_after_out (may be NULL) = the new count V1.
+ * Rows: a survivor keeps its flags (MMP_VMF_*, HOST included), the raw bytes of amid, tmid and o (a null stays null and "" stays
+ * "": the flags tell them apart) and its two model-id hashes as stored; the retired rows' strings are dropped, and the call leaves
+ * the string arena squeezed (arena_bytes == live_bytes in mmp_vmodels_info; n_live and live_bytes follow).  Vmodel-id table: the
+ * retired ids leave the table and the id arena, mmp_vmodels_resolve of a retired id answers MMP_VMR_NOT_FOUND with vmodel == -1,
+ * mmp_vmodels_get returns the survivors' ids under their new rows, the table has the capacity a fresh context reports after one
+ * MMP_VMEV_APPEND batch of V1 ids — 0 when no row is left: the state before the first vmodel call — (no string is hashed again:
+ * MMP_MODEL_ID_HASH_BITS and MMP_VMODEL_ID_HASH_BITS still hold), and a retired id that arrives again through
+ * mmp_vmodels_events_json with MMP_VMEV_APPEND joins as a new row at the end, like any unknown id; without the flag, and for a
+ * deletion, it is status 2.  A vmodel row stores ids and never registry rows: nothing on the model side is touched.
+ * MMP_VMRETIRE_ABSENT_ONLY guards the intended loop — (1) deletion events arrive, (2) the host collects their vmodel_idx, (3) it
+ * retires them later: every named row must then carry MMP_VMF_ABSENT, checked on the device rows; if one does not — its id was
+ * set again in between — the call is MMP_EINVAL with nothing changed and mmp_last_error names the lowest such row.
+ * MMP_VMRETIRE_ALL_ABSENT: the device chooses — every row flagged MMP_VMF_ABSENT at the call is retired; n must be 0 (a list
+ * beside the flag is MMP_EINVAL).  The form for a host that keeps no id map.  MMP_VMRETIRE_ABSENT_ONLY beside it is accepted and
+ * adds nothing.
+ * Readers: no decision kernel reads vmodel state, and every reader of it (mmp_vmodels_resolve, _transitions, _get, _info) holds
+ * batch_mu, which this call holds throughout — a reader sees the table before the retire or after it; no decision is drained and
+ * no resolved view rebuilt.  The new rows, arenas and table are built beside the published ones and swapped together with the
+ * counts under the state lock, as mmp_vmodels_events_json swaps what it grew; everything that can fail — allocation, a HIP error,
+ * an id the verifying lookup does not find (MMP_EHIP) — fails before the swap, with nothing published.  Row numbers the HOST holds
+ * — answers of mmp_vmodels_resolve and _transitions — are the host's to renumber from remap_out.
+ * MMP_EINVAL with nothing changed and every output untouched: NULL rows with n > 0, a row outside [0, V0), an unknown flag bit,
+ * max_vmodels < 0, remap_out with max_vmodels < V0, a row that is not ABSENT under MMP_VMRETIRE_ABSENT_ONLY,
+ * MMP_VMRETIRE_ALL_ABSENT with n > 0.  No MMP_ESTATE: the call needs neither mmp_model_ids_load nor mmp_pod_ids_load.  n == 0
+ * without MMP_VMRETIRE_ALL_ABSENT — and that flag where no row is ABSENT — is valid and changes nothing (no squeeze, no launch):
+ * remap_out is the identity, *n_vmodels_after_out = V0; also before the first vmodel call, where V0 == 0.  No commit is needed
+ * before or after.  The work is O(table), as a rebuild from the survivors is — the host decides how often to call; two runs over
+ * the same state and list are byte-identical.  Locking: batch_mu throughout. */
+#define MMP_VMRETIRE_ABSENT_ONLY  1u
+#define MMP_VMRETIRE_ALL_ABSENT   2u
+int mmp_vmodels_retire(mmp_ctx *ctx, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_vmodels,
+                       int32_t *n_vmodels_after_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

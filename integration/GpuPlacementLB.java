@@ -238,6 +238,13 @@ final class MmPlace {
                                  ByteBuffer strOffOut, ByteBuffer nStrBytesOut);
     /** rows, live rows, arena bytes, live bytes, table capacity (32 bytes). */
     static native int vmodelsInfo(long h, ByteBuffer out);
+    /** hand vmodel rows back (mmp_vmodels_retire): rows = n ints, the rows whose deletion the vmodel listener has seen; flags 1 =
+     *  every named row must still be ABSENT (else MMP_EINVAL, nothing changed: the id was set again), 2 = no list (n 0), the device
+     *  retires every ABSENT row.  The survivors move down in order; remapOut (maxVmodels >= the row count at the call, may be null)
+     *  gives old row -> new row, -1 for a retired one — row numbers the Java side holds from vmodelsResolve / vmodelsTransitions are
+     *  renumbered from it; nVmodelsAfterOut (one int, may be null). */
+    static native int vmodelsRetire(long h, ByteBuffer rows, int n, int flags, ByteBuffer remapOut, int maxVmodels,
+                                    ByteBuffer nVmodelsAfterOut);
     /** the write side of the wire format (mmp_models_rewrite_json), for the 13 conditionalSet / conditionalSetAndGet sites of
      *  ModelMesh.java: value i = the stored bytes oldJson[oldOff[i], oldOff[i+1]) of registry row rows[i]; the answer is the value to
      *  store next — what the device does not own copied byte for byte, instanceIds / failedIn / fails / lu (and lul from lastUnload,

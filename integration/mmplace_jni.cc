@@ -854,6 +854,19 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsInfo(JNIEnv 
     if (!holds<mmp_vmodels_stats>(env, out, 1, "vmodelsInfo: out shorter than one mmp_vmodels_stats")) return MMP_EINVAL;
     return check(env, ctx_of(h), mmp_vmodels_info(ctx_of(h), buf<mmp_vmodels_stats>(env, out)));
 }
+// rows: n ints (may be null with n == 0); remapOut (may be null) holds maxVmodels ints, nVmodelsAfterOut (may be null) one (see
+// mmp_vmodels_retire)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsRetire(JNIEnv *env, jclass, jlong h, jobject rows, jint n, jint flags,
+                                                                           jobject remapOut, jint maxVmodels, jobject nVmodelsAfterOut)
+{
+    if (n < 0 || maxVmodels < 0 || !holds<int32_t>(env, rows, n, "vmodelsRetire: rows shorter than n") ||
+        (remapOut && !holds<int32_t>(env, remapOut, maxVmodels, "vmodelsRetire: remapOut shorter than maxVmodels")) ||
+        (nVmodelsAfterOut && !holds<int32_t>(env, nVmodelsAfterOut, 1, "vmodelsRetire: nVmodelsAfterOut shorter than one int")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_retire(ctx_of(h), buf<int32_t>(env, rows), n, static_cast<uint32_t>(flags), buf<int32_t>(env, remapOut),
+                                    maxVmodels, buf<int32_t>(env, nVmodelsAfterOut)));
+}
 
 // the write side of the wire format: the stored value of each edited record and the record as the device holds it give the value
 // to store next (see mmp_models_rewrite_json).  The capacities are checked here; outCap is what outBuf holds (0 with null: sizes).

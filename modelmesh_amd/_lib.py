@@ -215,6 +215,9 @@ VMODELS_STATS = np.dtype([("n_rows", "<i4"), ("n_live", "<i4"), ("arena_bytes", 
                           ("reserved", "<i4")])
 assert VMODEL_ANSWER.itemsize == 32 and VMODEL_TRANSITION.itemsize == 32 and VMODEL_TRANSITIONS_INFO.itemsize == 24
 assert VMODELS_STATS.itemsize == 32
+# mmp_vmodels_retire: every named row must be ABSENT / the device retires every ABSENT row (no list)
+VMRETIRE_ABSENT_ONLY = 1
+VMRETIRE_ALL_ABSENT = 2
 # mmp_models_retire: every named row must be the empty row a deletion leaves
 RETIRE_EMPTY_ONLY = 1
 # mmp_pods_retire: every named row must be a tombstone / no referenced registry entry may name a retired instance
@@ -367,6 +370,7 @@ SYMBOLS = [
     ("mmp_vmodels_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),
     ("mmp_vmodels_info", C.c_int, [_P, _P]),
+    ("mmp_vmodels_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -48,6 +48,7 @@
 #include "rewrite_kernels.hpp"
 #include "register_kernels.hpp"
 #include "vmodel_kernels.hpp"
+#include "vmodel_retire_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -527,6 +528,7 @@ struct mmp_ctx {
     // vm_arena_bytes of them used, vm_live_bytes referred to by a row; vm_live_rows: rows that are not ABSENT.  vm_ev / vm_cnt /
     // vm_pos: one event call's parsed events, byte counts and their scan; vm_nf_* / vm_ow_* / vm_rflags / vm_ans: one resolve's
     // staged strings, flags and answers; vm_list: the transition scan's rows.  Read and written under batch_mu, used on c->stream.
+    // mmp_vmodels_retire (vmodel_retire_kernels.hpp) takes its scratch from mmp_models_retire: ret_*, me_cnt / me_pos / j_scan_tmp.
     DevBuf vid_hash, vid_val, vid_next_hash, vid_next_val, vid_bytes, vid_off;
     DevBuf vm_rows, vm_arena, vm_ev, vm_cnt, vm_pos, vm_nf_bytes, vm_nf_off, vm_ow_bytes, vm_ow_off, vm_rflags, vm_ans, vm_list;
     uint32_t vid_mask = 0;
@@ -4235,6 +4237,129 @@ try {
     out->capacity = (int32_t)(c->vid_mask + 1);
     return MMP_OK;
 } MMP_CATCH(c, "mmp_vmodels_info")
+
+int mmp_vmodels_retire(mmp_ctx *c, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_vmodels,
+                       int32_t *n_vmodels_after_out)
+try {
+    const bool all = flags & MMP_VMRETIRE_ALL_ABSENT;
+    if (!c || n < 0 || (n > 0 && !rows) || (flags & ~(MMP_VMRETIRE_ABSENT_ONLY | MMP_VMRETIRE_ALL_ABSENT)) || max_vmodels < 0)
+        return fail(c, MMP_EINVAL, "mmp_vmodels_retire: bad argument");
+    if (all && n > 0) return fail(c, MMP_EINVAL, "mmp_vmodels_retire: MMP_VMRETIRE_ALL_ABSENT takes no list (n = %d)", n);
+    // The vmodel state is read and written under batch_mu only (vmodel_tab: mmp_vmodels_resolve and _transitions hold it, and no
+    // decision kernel is handed a vmodel pointer), so nothing reads it while the compacted rows, arenas and table are built BESIDE
+    // the published ones: no quiesce, no rebuild_resolved.  The state lock is taken for the swap only, as in mmp_vmodels_events_json.
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    const int32_t V0 = c->have_vmodels ? c->vid_n : 0;
+    if (remap_out && max_vmodels < V0)
+        return fail(c, MMP_EINVAL, "mmp_vmodels_retire: room for %d rows in remap_out, the table has %d", max_vmodels, V0);
+    for (int32_t i = 0; i < n; i++)
+        if (rows[i] < 0 || rows[i] >= V0) return fail(c, MMP_EINVAL, "mmp_vmodels_retire: rows[%d] names row %d of %d", i, rows[i], V0);
+    auto unchanged = [&] {
+        if (remap_out)
+            for (int32_t r = 0; r < V0; r++) remap_out[r] = r;
+        if (n_vmodels_after_out) *n_vmodels_after_out = V0;
+        return (int)MMP_OK;
+    };
+    if (all ? c->vm_live_rows == V0 : n == 0) {  // nothing leaves: no squeeze, no launch
+        if (c->prof) c->last_kernel_ms = -1;
+        return unchanged();
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->ret_rows.ensure((size_t)std::max(n, 1) * 4));
+    HIP_TRY(c, c->ret_keep.ensure((size_t)V0 * 4));
+    HIP_TRY(c, c->ret_remap.ensure((size_t)V0 * 4));
+    HIP_TRY(c, c->ret_word.ensure(8));
+    HIP_TRY(c, c->me_cnt.ensure(((size_t)V0 + 1) * sizeof(VmRetireCount)));
+    HIP_TRY(c, c->me_pos.ensure(((size_t)V0 + 1) * sizeof(VmRetireCount)));
+    VmRetireCount *d_cnt = c->me_cnt.as<VmRetireCount>(), *d_pos = c->me_pos.as<VmRetireCount>();
+    int32_t *d_keep = c->ret_keep.as<int32_t>(), *d_remap = c->ret_remap.as<int32_t>(), *d_word = c->ret_word.as<int32_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, VmRetireCount{0, 0, 0, 0}, (size_t)V0 + 1, VmRetirePlus(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    if (!all) {
+        HIP_TRY(c, hipMemcpyAsync(c->ret_rows.p, rows, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_keep), 1, (size_t)V0, st));
+    }
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
+    const dim3 block(kRetireBlock), vgrid(div_up(V0, kRetireBlock));
+    const VmRow *old_rows = c->vm_rows.as<VmRow>();
+    const int32_t *old_off = c->vid_off.as<int32_t>();
+    // 1. mark — the list, and with ABSENT_ONLY the lowest named row that is not ABSENT, or every ABSENT row; the counts and their scan
+    KT_BEGIN(c, st);
+    if (all)
+        hipLaunchKernelGGL(vm_retire_absent_kernel, vgrid, block, 0, st, V0, old_rows, d_keep);
+    else
+        hipLaunchKernelGGL(vm_retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, c->ret_rows.as<int32_t>(), n, old_rows,
+                           (flags & MMP_VMRETIRE_ABSENT_ONLY) ? 1 : 0, d_keep, d_word);
+    hipLaunchKernelGGL(vm_retire_count_kernel, dim3(div_up(V0 + 1, kRetireBlock)), block, 0, st, V0, d_keep, old_rows, old_off, d_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, VmRetireCount{0, 0, 0, 0}, (size_t)V0 + 1, VmRetirePlus(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    int32_t word[2] = {INT32_MAX, INT32_MAX};
+    VmRetireCount tot{};
+    HIP_TRY(c, hipMemcpyAsync(word, d_word, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, copy_sync(c, &tot, d_pos + V0, sizeof tot, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    const double mark_ms = c->last_kernel_ms;
+    if (word[0] != INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_vmodels_retire: row %d is not ABSENT (set again since its deletion?); nothing was retired", word[0]);
+    const int32_t V1 = tot.row, B1 = tot.bytes, S1 = tot.strs;
+    // 2. the compacted rows, string arena, id arena and table, beside the published ones
+    ScopedDevBuf nr, na, nb, no;
+    const uint32_t cap0 = c->vid_mask + 1, cap1 = tab_capacity(V1);
+    if (nr.b.ensure((size_t)std::max(V1, 1) * sizeof(VmRow)) != hipSuccess || na.b.ensure((size_t)S1 + 16) != hipSuccess ||
+        nb.b.ensure((size_t)B1 + 16) != hipSuccess || no.b.ensure(((size_t)V1 + 1) * 4) != hipSuccess ||
+        c->vid_next_hash.ensure((size_t)cap1 * 8) != hipSuccess || c->vid_next_val.ensure((size_t)cap1 * 4) != hipSuccess)
+        return fail(c, MMP_ENOMEM, "mmp_vmodels_retire: out of device memory");
+    const HashTabW next{c->vid_next_hash.as<uint64_t>(), c->vid_next_val.as<int32_t>(), cap1 - 1};
+    int rc = empty_table(c, next);
+    if (rc == MMP_OK && hipMemsetAsync(no.b.p, 0, 4, st) != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: hipMemsetAsync failed");
+    std::vector<int32_t> remap((size_t)V0);
+    if (rc == MMP_OK) {
+        const VmRetireMove A{old_rows, c->vm_arena.as<char>(), c->vid_bytes.as<char>(), old_off, nr.b.as<VmRow>(), na.b.as<char>(),
+                             nb.b.as<char>(), no.b.as<int32_t>()};
+        // 3. the stored hashes of the survivors into the emptied next table; 4. a verifying lookup in a launch of its own
+        const dim3 sgrid(div_up((int)cap0, kRetireBlock));
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(vm_retire_move_kernel, vgrid, block, 0, st, V0, d_keep, d_pos, A, d_remap);
+        hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->vid_hash.as<uint64_t>(), c->vid_val.as<int32_t>(), cap0, d_remap, next);
+        hipLaunchKernelGGL(retire_verify_kernel, sgrid, block, 0, st, c->vid_hash.as<uint64_t>(), c->vid_val.as<int32_t>(), cap0, d_remap,
+                           ModelIdTab{next.hash, next.val, next.mask, nb.b.as<char>(), no.b.as<int32_t>()}, d_word + 1);
+        KT_END(c, st);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(remap.data(), d_remap, (size_t)V0 * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(word + 1, d_word + 1, 4, hipMemcpyDeviceToHost, st);
+        const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
+        if (e == hipSuccess) e = se;
+        if (e != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: %s", hipGetErrorString(e));
+    } else
+        (void)hipStreamSynchronize(st);
+    if (rc == MMP_OK && word[1] != INT32_MAX)
+        rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: the id of new row %d was not found in the compacted table", word[1]);
+    if (rc != MMP_OK) return rc;
+    kt_collect(c);
+    kt_add(c, mark_ms);  // the call's device span: mark + scan + move + table + verify
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);  // nothing fails from here on: rows, arenas, table and counts change together
+        nr.move_into(c->vm_rows);
+        na.move_into(c->vm_arena);
+        nb.move_into(c->vid_bytes);
+        no.move_into(c->vid_off);
+        std::swap(c->vid_hash, c->vid_next_hash);
+        std::swap(c->vid_val, c->vid_next_val);
+        c->vid_mask = cap1 - 1;
+        c->vid_n = V1;
+        c->vid_nbytes = B1;
+        c->vm_arena_bytes = S1;
+        c->vm_live_bytes = S1;
+        c->vm_live_rows = tot.live;
+        c->have_vmodels = V1 > 0;  // (no row: the state before the first vmodel call, which the next event batch starts from)
+    }
+    if (remap_out) memcpy(remap_out, remap.data(), (size_t)V0 * 4);
+    if (n_vmodels_after_out) *n_vmodels_after_out = V1;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_retire")
 
 int mmp_models_retire(mmp_ctx *c, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_models,
                       int32_t *n_models_after_out)

@@ -550,6 +550,31 @@ class Solver:
                    for r in range(n_rows)]
         return [iraw[ioff[r]:ioff[r + 1]] for r in range(n_rows)], flags[:n_rows].copy(), strings
 
+    def vmodels_retire_raw(self, rows=None, flags=0, fill=0, null_remap=False, max_vmodels=None, n=None):
+        """mmp_vmodels_retire without the error check (tests: refusals): remap and n_after are pre-filled with `fill`; max_vmodels
+        replaces the row count as remap's stated room, n the list's length, rows=None is a NULL list.  Returns (remap, n_after, rc)."""
+        v0 = int(self.vmodels_info()["n_rows"])
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        room = v0 if max_vmodels is None else int(max_vmodels)
+        remap = np.zeros(max(v0, room, 1), np.int32)
+        after = np.zeros(1, np.int32)
+        remap.view(np.uint8)[:] = fill
+        after.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_vmodels_retire(self.h, ptr(rows) if rows is not None and len(rows) else None,
+                                         (0 if rows is None else len(rows)) if n is None else int(n), int(flags),
+                                         None if null_remap else ptr(remap), room, after.ctypes.data_as(C.POINTER(C.c_int32)))
+        return remap[:v0], int(after[0]), rc
+
+    def vmodels_retire(self, rows=None, absent_only=False, all_absent=False):
+        """Retire vmodel rows (mmp_vmodels_retire): the rows leave the index space; rows, string arena and id table are compacted on
+        the device.  all_absent: the device retires every ABSENT row (no list).  Returns (remap, n_after): remap is int32[V0], the
+        new row of every old row, -1 for a retired one."""
+        flags = (_lib.VMRETIRE_ABSENT_ONLY if absent_only else 0) | (_lib.VMRETIRE_ALL_ABSENT if all_absent else 0)
+        remap, after, rc = self.vmodels_retire_raw(rows, flags)
+        self._ck(rc)
+        return remap, after
+
     def models_retire(self, rows, empty_only=False):
         """Retire registry rows (mmp_models_retire): the rows leave the index space, registry and id table are compacted on the
         device.  Returns remap, int32[M0]: the new row of every old row, -1 for a retired one."""
