@@ -274,7 +274,14 @@ __device__ __forceinline__ void derive5(const ShardSnap &S, const mmp_place_req 
             D.remaining = cc - (D.null0 ? 1 : 0) - (D.null_s ? 1 : 0) - (D.null_o ? n_others : 0);
         }
     }
-    D.index = D.remaining <= 1 ? 0 : (int)(((uint64_t)rq.pick * (uint64_t)(uint32_t)D.remaining) >> 32);
+    // the filter stops at one survivor, the list's last entry (see RpmRule): phase 6 selects from the unfiltered words, the owner
+    // prefix below runs over the unfiltered counts
+    const bool last_only = cc >= 2 && D.remaining == 0;
+    if (last_only) {
+        D.null0 = D.null_s = D.null_o = D.apply_b = false;
+        D.remaining = 1;
+    }
+    D.index = last_only ? cc - 1 : D.remaining <= 1 ? 0 : (int)(((uint64_t)rq.pick * (uint64_t)(uint32_t)D.remaining) >> 32);
     D.sel_shard = -1;
     D.sel_prefix = 0;
     if (D.remaining >= 1) {

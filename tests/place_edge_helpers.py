@@ -1,5 +1,6 @@
-"""Shared by tests/test_place_edges.py (CPU) and tests/test_place_edges_gpu.py: the committed vectors of the load-target edge cases
-(tests/golden/ref_place_edges.npz) and the Python restatement's decisions in the device's output format."""
+"""Shared by tests/test_place_edges.py (CPU), tests/test_place_edges_gpu.py and the pod-axis pair tests/test_shard_edges_premise.py
+(CPU) / tests/test_shard_edges_gpu.py: the committed vectors of the load-target edge cases (tests/golden/ref_place_edges.npz), the
+Python restatement's decisions in the device's output format, and the sharded commit's slice rule."""
 import os
 
 import numpy as np
@@ -31,6 +32,32 @@ def audit_hash(order, shortlist, remaining):
     for w, b in words.items():
         h = (h + b * mul(w)) & M64
     return ((h ^ (h >> 32)) & 0xFFFFFFFF) ^ ((remaining * 0x9E3779B1) & 0xFFFFFFFF)
+
+
+def n_words(fleet):
+    """W: the 64-bit words of a rank-ordered bitmap of the fleet's table."""
+    return max(-(-fleet.n_pods // 64), 1)
+
+
+def slice_owner(fleet, G):
+    """The sharded commit's slice rule (mmp_shard_commit_dev): Wl = ceil(W / G) words per shard, position p belongs to (p >> 6) // Wl."""
+    wl = -(-n_words(fleet) // G)
+    return lambda p: (p >> 6) // wl
+
+
+def shard_counts(fleet):
+    """The shard counts the pod-axis edge tests run a case at: one word has nothing to cut (1 and 2 — more shards only add empty
+    slices); otherwise 1, 2, 3, 8 (which leaves trailing slices empty up to 7 words) and one shard per word."""
+    W = n_words(fleet)
+    return [1, 2] if W == 1 else sorted({1, 2, 3, 8, W})
+
+
+def excluded_pods(fleet, r, extra):
+    """The instances of the table that request row r already excludes: its own exclusions first, then its model's entries."""
+    m = fleet.models[r["model"]]
+    own = [int(x) for x in extra[r["extra_off"]: r["extra_off"] + r["n_extra"]]]
+    ents = [int(x) for x in fleet.ent_pod[m["ent_off"]: m["ent_off"] + m["n_loaded"] + m["n_failed"]]]
+    return [p for p in own + ents if 0 <= p < fleet.n_pods]
 
 
 def py_place(fleet, reqs, extra):
