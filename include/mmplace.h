@@ -1673,6 +1673,187 @@ int mmp_vmodels_info(mmp_ctx *ctx, mmp_vmodels_stats *out);
 #define MMP_VMRETIRE_ALL_ABSENT   2u
 int mmp_vmodels_retire(mmp_ctx *ctx, const int32_t *rows, int32_t n, uint32_t flags, int32_t *remap_out, int32_t max_vmodels,
                        int32_t *n_vmodels_after_out);
+/* ---- incRefCount / decRefCount on stored ModelRecord values (refs_kernels.hpp) -----------------------------------------------------
+ * The write side of the vmodel transactions, the ModelRecord half: updateVModel (VModelManager.java:137-385), deleteVModel
+ * (:416-470) and the tail of PendingTransition.run (:716-767) each change `refs` on up to three ModelRecords — the new target gains
+ * a referent and a lastUsed (:299-302), a model the vmodel lets go loses one and is deleted with it when it was created for it
+ * (decModelRefsInTxn :475-489).  A batch of such steps; the next bytes of a record are a pure function of the request and of the
+ * stored value the host holds for that id.  The host parses no stored value and serialises no ModelRecord; the transaction, its
+ * retry loop (call again with the values the store answered) and readOnlyMode stay in Java.
+ *
+ * Request i: reqs[i], on the stored value old_buf[old_off[i], old_off[i+1]); an EMPTY span is mr == null.  With MMP_MREF_INC the
+ * request is setLastUsed(last_used) + incRefCount() (:301-302), without it decModelRefsInTxn, which reads nothing else of the
+ * request.  info / info_off (3n + 1 offsets; both may be NULL: every span empty) bring type, encKey and mPath as the spans 3i,
+ * 3i + 1, 3i + 2, as in mmp_models_register_json; they are read only by an INC onto no stored value, as is MMP_MREF_AUTO_DELETE
+ * (the autoDelete of the record :294 creates).
+ *
+ * The stored value is read as mmp_models_register_json reads it: the top-level member walk, names matched as raw bytes, a later
+ * duplicate wins.
+ *     refs      int, absent = 0; what that call's delete guard refuses (not an integer in int32) is MMP_MREFC_HOST
+ *     autoDel   the literal true or false, absent = false; anything else is MMP_MREFC_HOST.  Read only by a DEC
+ * A DEC (ModelRecord.java:213-215, refCount > 0 ? --refCount : 0): the FIELD becomes refs > 0 ? refs - 1 : refs — a stored -1
+ * stays -1 — and the RETURN value is refs > 0 ? refs - 1 : 0.  An INC (:220-222): both are refs + 1 as a Java int, 2^31 - 1 wraps
+ * to -2^31; setLastUsed sets unconditionally.
+ *
+ * class_out[i], in this order of precedence:
+ *   DEC, old span empty                   MMP_MREFC_ENSURE_ABSENT (:485-487, txn.ensureAbsent).  Length 0
+ *   INC, old span empty, type not empty   MMP_MREFC_CREATED with the value
+ *                                         {"type":"<t>","encKey":"<k>","mPath":"<p>","refs":1,"autoDel":true,"lu":<last_used>},
+ *                                         encKey / mPath omitted at an empty span, autoDel without MMP_MREF_AUTO_DELETE, lu at 0; the
+ *                                         strings escaped by the rule of mmp_models_rewrite_json (:294, :301-302)
+ *   INC, old span empty, type empty       MMP_MREFC_NOT_FOUND (:203-205, "Target model not found"); also with info_off == NULL
+ *   MMP_MREFC_MALFORMED   exactly where mmp_models_upsert_json gives status 1 for the old value as a non-deleted event (the parser
+ *                         itself runs over the old values first, as in the other two calls)
+ *   MMP_MREFC_HOST        the value is well-formed but the device will not decide it, by the refs / autoDel rules above
+ *   DEC, return == 0 && autoDel           MMP_MREFC_DELETE (:478-480).  Length 0: the host deletes with the old value.  A stored
+ *                                         refs of 0 or -1 with autoDel is a DELETE too: the return value decides
+ *   DEC otherwise                         MMP_MREFC_SET: every top-level member of the old value not named refs, verbatim and in
+ *                                         document order as mmp_models_rewrite_json keeps members, then "refs":<field>, omitted at 0
+ *   INC, stored value present             MMP_MREFC_SET: every member not named refs or lu, then "refs":<refs + 1>, omitted at 0,
+ *                                         then "lu":<last_used>, omitted at 0
+ * refs_out[i] = the count the Java method returns (1 for CREATED); 0 for the classes that compute none.  Numbers are plain decimal,
+ * Long.MIN_VALUE included.  Every class but SET and CREATED has length 0.
+ *
+ * Output and sizing as mmp_models_rewrite_json: value i = out_buf[out_off[i], out_off[i+1]); out_off (n + 1 words), class_out,
+ * refs_out and *n_bytes_out are always complete; NO byte of out_buf is written when out_buf is NULL or out_cap is smaller than the
+ * total, and the call still returns MMP_OK.  Read-only: no commit, locking as mmp_models_register_json.  n == 0 is valid.
+ * MMP_EINVAL with every output untouched: a NULL required buffer (info and info_off may be NULL), non-monotone offsets of either
+ * kind, unknown request flag bits or a non-zero reserved word, flags != 0, out_cap < 0, a value of 2^31 bytes or more.  MMP_ESTATE
+ * before mmp_pod_ids_load (the parser's condition).  Two runs are byte-identical. */
+typedef struct {
+    uint32_t flags;
+    int32_t reserved;
+    int64_t last_used; /* an INC: the record's next lu (newLastUsedTime, :299-300) */
+} mmp_refs_req;                      /* 16 bytes */
+#define MMP_MREF_INC 1u              /* setLastUsed(last_used) + incRefCount(); without it: decModelRefsInTxn */
+#define MMP_MREF_AUTO_DELETE 2u      /* read only by an INC onto no stored value: autoDelete of the created record */
+/* class_out */
+#define MMP_MREFC_SET 0              /* txn.set: the next value is rendered */
+#define MMP_MREFC_CREATED 1          /* no stored value, an INC with a type: the new record is rendered */
+#define MMP_MREFC_DELETE 2           /* a DEC to 0 of an autoDel record: txn.delete with the old value */
+#define MMP_MREFC_ENSURE_ABSENT 3    /* a DEC of no stored value: txn.ensureAbsent */
+#define MMP_MREFC_NOT_FOUND 4        /* an INC of no stored value and no type */
+#define MMP_MREFC_MALFORMED 5        /* the old value is malformed */
+#define MMP_MREFC_HOST 6             /* well-formed, but the host decides this one */
+int mmp_models_refs_json(mmp_ctx *ctx, const mmp_refs_req *reqs, int32_t n, const char *info, const int32_t *info_off,
+                         const char *old_buf, const int64_t *old_off, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off,
+                         int32_t *class_out, int32_t *refs_out, int64_t *n_bytes_out);
+/* ---- the record step of the three vmodel writers (vmodel_write_kernels.hpp) ----------------------------------------------------------
+ * updateVModel (VModelManager.java:137-385), deleteVModel (:416-470) and the tail of PendingTransition.run (:716-767) each read the
+ * stored VModelRecord, decide, render the next one and name up to two models that lose a referent.  A batch of such steps; each
+ * answer is a pure function of the request, the stored value, now_ms, lastused_age_on_add_ms (LASTUSED_AGE_ON_ADD_MS) and two facts
+ * of the resident registry — the loaded copies of the previous active model (:248, :261) and its lastUsed (:299).  The transaction,
+ * its retry loop (call again with the values the store answered), the waiters and readOnlyMode stay in Java; the ModelRecord half
+ * of a transaction is mmp_models_refs_json.  The resident vmodel table is not read and need not exist.
+ *
+ * Request i: reqs[i]; its strings are the spans 3i (id_a), 3i + 1 (id_b), 3i + 2 (owner) of strs / str_off (3n + 1 offsets); an EMPTY
+ * span is Java null.  The stored value is old_buf[old_off[i], old_off[i+1]); an EMPTY span is vmr == null.  It is read by the grammar
+ * and the verdicts of mmp_vmodels_events_json (the parser itself runs over the old values first): a malformed value is
+ * MMP_VWC_MALFORMED; amid, tmid and o are strings or null (absent = null), failed a boolean (absent = false), a later duplicate
+ * wins; strings compare on raw bytes, a stored null equals nothing.  MMP_VWC_HOST: the value is well-formed but the stored amid or
+ * tmid (every op but FAIL_FLAG) or, where a SET or DELETE brings an owner, the stored o holds a backslash.  default_owner
+ * (default_owner_len bytes, 0: none) is DEFAULT_OWNER of :282.
+ *
+ * Rendering.  The next value is every top-level member of the old value not named amid / tmid / failed, verbatim and in document
+ * order as mmp_models_rewrite_json keeps members, duplicates included, o among them (it is final in the bean); then "amid":"..",
+ * "tmid":"..", "failed":true, each omitted at null / false.  A string that stays is copied raw from the stored value; one the
+ * request brings is escaped by the rule of mmp_models_rewrite_json.  A CREATED value is {"o":"<owner>","amid":"<id_a>",
+ * "tmid":"<id_a>"}, the owner the request's, else default_owner, else omitted.  Only CREATED and UPDATED have a length.
+ *
+ * MMP_VW_SET (updateVModel :174-189, :216-284): id_a = targetModelId (empty: MMP_EINVAL), id_b = expectedTargetModelId.
+ *   no stored value, in this order (the strong read of :174-179 stands in front of the loop):
+ *     id_b given and != id_a            MMP_VWC_PRECONDITION (:178, :280)
+ *     MMP_VWQ_UPDATE_ONLY               MMP_VWC_NOT_FOUND (:277)
+ *     otherwise                         MMP_VWC_CREATED
+ *   stored value present, in this order:
+ *     1. owner given and != stored o    MMP_VWC_OWNER_MISMATCH (:181, :222)
+ *     2. id_b given, != stored tmid, and id_a != stored tmid       MMP_VWC_PRECONDITION (:184, :232)
+ *     3. id_a == stored tmid and == stored amid                     MMP_VWC_UNCHANGED (:243)
+ *     4. id_a == stored tmid and no MMP_VWQ_FORCE                   MMP_VWC_UNCHANGED, target_copy_count from the previous active
+ *                                       model when that id is not null (:246-250), looked up as in 5
+ *     5. otherwise tmid := id_a where it differed, and dec[0] = the previous target when it is not null and differs from the
+ *        previous active id (:237-239).  When id_a != stored amid: a null previous active gives amid := id_a (:258); else the
+ *        previous active id is looked up in the model-id table and target_copy_count = the resident row's n_loaded (unresolved
+ *        entries included, as in mmp_vmodels_transitions), 0 for an unknown id or the empty row, which sets
+ *        MMP_VWF_PREV_ACTIVE_UNKNOWN.  The active model switches — amid := id_a, dec[1] = the previous active id,
+ *        MMP_VWF_ACTIVE_SWITCHED — under MMP_VWQ_FORCE, or at a count of 0, or at a count of 1 with MMP_VWQ_TARGET_EXISTS and
+ *        MMP_VWQ_TARGET_LOADED (:262-270).  At a count of 1 with TARGET_EXISTS, without FORCE and with neither status flag the class
+ *        is MMP_VWC_NEEDS_TARGET_STATUS: nothing is rendered, target_copy_count is 1; the host asks getStatus(target) and calls
+ *        again with the answer, as MMP_VMR_STRONG_READ works.  Then failed := false (:273), class MMP_VWC_UPDATED
+ *   request flags: MMP_VWQ_TARGET_EXISTS = the host holds a stored value for the target (targetModel != null, :264);
+ *   MMP_VWQ_TARGET_LOADED / _NOT_LOADED = the answer to getStatus(target) == LOADED (both: MMP_EINVAL).
+ *   last_used (CREATED / UPDATED, :299-300; the host passes it to the INC of mmp_models_refs_json) = the previous active row's
+ *   last_used where step 5 looked that row up, it is known and > 0; otherwise now_ms - age * (LOAD_NOW ? 1 : 6) in Java long
+ *   arithmetic (:168-170).  model (CREATED / UPDATED / UNCHANGED / NEEDS_TARGET_STATUS) = the registry row of id_a, -1 unknown.
+ * MMP_VW_DELETE (:416-470): owner = span 2.  No stored value, or an owner given that != stored o: MMP_VWC_NOOP (:419, :457).
+ *   Otherwise MMP_VWC_DELETE: dec[0] = the active id when not null (:438), dec[1] = the target id when it is not null and not equal
+ *   to the active one (:441).  Nothing is rendered: the host deletes with the old value.
+ * MMP_VW_COMPLETE (:750-766): id_a = toId (empty: MMP_EINVAL), id_b = fromId.  No stored value, stored amid != id_b or stored tmid !=
+ *   id_a: MMP_VWC_CHANGED (:762-764; the first attempt, with origVmr, satisfies the guard by construction).  Otherwise amid := id_a,
+ *   failed := false, dec[0] = the stored amid, class MMP_VWC_UPDATED.  An empty id_b matches only a stored null amid — where the
+ *   Java would throw at :762 — and then names no dec.
+ * MMP_VW_FAIL_FLAG (:725-742): MMP_VWQ_FAILED is the new value.  No stored value: MMP_VWC_NOOP; equal to the stored flag:
+ *   MMP_VWC_UNCHANGED; otherwise MMP_VWC_UPDATED with failed set.
+ * MMP_VWF_IN_TRANSITION (UPDATED / UNCHANGED): !Objects.equals(amid, tmid) of the record as it stands after the step, for
+ *   UNCHANGED as stored (:344).
+ * dec: dec_off[k] / dec_len[k] name the id as a span of raw bytes INSIDE old value i (dec_len -1: none, dec_off then 0), so the
+ * host needs no parse to key the transaction; dec_model[k] = its registry row, -1 unknown.  Every field a class does not define is
+ * 0, the three row numbers -1, dec_len -1.
+ *
+ * Output and sizing as mmp_models_rewrite_json: value i = out_buf[out_off[i], out_off[i+1]); out_off (n + 1 words), rows_out and
+ * *n_bytes_out are always complete; NO byte of out_buf is written when out_buf is NULL or out_cap is smaller than the total, and the
+ * call still returns MMP_OK.  Read-only: no commit; locking as mmp_vmodels_resolve.  n == 0 is valid.  MMP_EINVAL with every output
+ * untouched: an unknown op or flag bits, a NULL required buffer, non-monotone offsets of either kind, now_ms <= 0,
+ * lastused_age_on_add_ms < 0, flags != 0, out_cap < 0, default_owner_len < 0, a value of 2^30 bytes or more, an empty id_a on SET /
+ * COMPLETE, both status flags.  MMP_ESTATE under the conditions of mmp_model_ids_resolve.  Two runs over the same state are
+ * byte-identical. */
+typedef struct {
+    uint32_t op;    /* MMP_VW_* */
+    uint32_t flags; /* MMP_VWQ_* */
+} mmp_vmodel_write_req;              /* 8 bytes */
+typedef struct {
+    int32_t cls;               /* MMP_VWC_* */
+    uint32_t flags;            /* MMP_VWF_* */
+    int32_t model;             /* SET: the registry row of id_a, -1 unknown */
+    int32_t target_copy_count; /* SET: loaded copies of the previous active model (:248, :261) */
+    int32_t dec_model[2];      /* the registry rows of the ids that lose a referent, -1 unknown or none */
+    int32_t dec_off[2];        /* ... and the ids as spans of old value i */
+    int32_t dec_len[2];        /* -1: none */
+    int64_t last_used;         /* SET, CREATED / UPDATED: newLastUsedTime (:299-300) */
+} mmp_vmodel_write_row;              /* 48 bytes */
+#define MMP_VW_SET 0                 /* updateVModel */
+#define MMP_VW_DELETE 1              /* deleteVModel */
+#define MMP_VW_COMPLETE 2            /* the tail of PendingTransition.run */
+#define MMP_VW_FAIL_FLAG 3           /* setTargetLoadFailed (:736-738) */
+/* request flags */
+#define MMP_VWQ_UPDATE_ONLY 1u
+#define MMP_VWQ_FORCE 2u
+#define MMP_VWQ_LOAD_NOW 4u
+#define MMP_VWQ_TARGET_EXISTS 8u
+#define MMP_VWQ_TARGET_LOADED 16u
+#define MMP_VWQ_TARGET_NOT_LOADED 32u
+#define MMP_VWQ_FAILED 64u           /* FAIL_FLAG: the new value */
+/* cls */
+#define MMP_VWC_CREATED 0            /* the new record is rendered */
+#define MMP_VWC_UPDATED 1            /* the next record is rendered */
+#define MMP_VWC_UNCHANGED 2          /* no record updates needed */
+#define MMP_VWC_NOT_FOUND 3          /* updateOnly and no vmodel */
+#define MMP_VWC_PRECONDITION 4       /* FAILED_PRECONDITION */
+#define MMP_VWC_OWNER_MISMATCH 5     /* ALREADY_EXISTS with a different owner */
+#define MMP_VWC_NEEDS_TARGET_STATUS 6 /* call again with MMP_VWQ_TARGET_LOADED or _NOT_LOADED */
+#define MMP_VWC_NOOP 7               /* nothing to do: absent, or another owner's */
+#define MMP_VWC_DELETE 8             /* delete with the old value */
+#define MMP_VWC_CHANGED 9            /* COMPLETE: things changed, give up */
+#define MMP_VWC_MALFORMED 10         /* the old value is malformed */
+#define MMP_VWC_HOST 11              /* well-formed, but the host decides this one */
+/* row flags */
+#define MMP_VWF_IN_TRANSITION 1u
+#define MMP_VWF_ACTIVE_SWITCHED 2u
+#define MMP_VWF_PREV_ACTIVE_UNKNOWN 4u
+int mmp_vmodels_write_json(mmp_ctx *ctx, const mmp_vmodel_write_req *reqs, int32_t n, const char *strs, const int32_t *str_off,
+                           const char *default_owner, int32_t default_owner_len, const char *old_buf, const int64_t *old_off,
+                           int64_t now_ms, int64_t lastused_age_on_add_ms, uint32_t flags, char *out_buf, int64_t out_cap,
+                           int64_t *out_off, mmp_vmodel_write_row *rows_out, int64_t *n_bytes_out);
 /* Read the staged instance table / the loaded registry view back (tests, diagnostics). */
 int mmp_pods_get(mmp_ctx *ctx, mmp_pod_row *rows_out, int32_t max_rows, int32_t *n_out);
 int mmp_models_get(mmp_ctx *ctx, mmp_model_row *rows_out, int32_t max_models, int32_t *ent_pod_out, int64_t *ent_time_out,

@@ -267,6 +267,30 @@ final class MmPlace {
                                          ByteBuffer infoOff, ByteBuffer oldJson, ByteBuffer oldOff, long nowMs, long lastUsedAgeOnAddMs,
                                          int flags, ByteBuffer outBuf, long outCap, ByteBuffer outOff, ByteBuffer classOut,
                                          ByteBuffer lastUsedOut, ByteBuffer modelIdxOut, ByteBuffer nBytesOut);
+    /** the ModelRecord half of the vmodel transactions (VModelManager.java:299-302, decModelRefsInTxn :475-489) as a batch of steps
+     *  (mmp_models_refs_json): request i = reqs[i] (16 bytes: int flags 1 = setLastUsed + incRefCount, else decModelRefsInTxn / 2 =
+     *  autoDelete of a created record, int reserved, long lastUsed) on the stored value oldJson[oldOff[i], oldOff[i+1]) (empty: mr ==
+     *  null); info / infoOff (may be null both) bring type, encKey, mPath for a record the INC creates.  classOut 0 txn.set / 1
+     *  created (both: the value is outBuf[outOff[i], outOff[i+1])) / 2 txn.delete with the old value / 3 txn.ensureAbsent / 4 target
+     *  model not found / 5 malformed / 6 the host decides; refsOut = what incRefCount / decRefCount return.  Sizing as
+     *  modelsRewriteJson: nothing is written to outBuf when it is null or outCap is smaller than nBytesOut.  flags 0. */
+    static native int modelsRefsJson(long h, ByteBuffer reqs, int n, ByteBuffer info, ByteBuffer infoOff, ByteBuffer oldJson,
+                                     ByteBuffer oldOff, int flags, ByteBuffer outBuf, long outCap, ByteBuffer outOff,
+                                     ByteBuffer classOut, ByteBuffer refsOut, ByteBuffer nBytesOut);
+    /** the record step of updateVModel (VModelManager.java:174-189, :216-284), deleteVModel (:416-470) and the tail of
+     *  PendingTransition.run (:725-766) as a batch (mmp_vmodels_write_json): request i = reqs[i] (8 bytes: int op 0 set / 1 delete /
+     *  2 complete / 3 fail flag, int flags 1 updateOnly / 2 force / 4 loadNow / 8 the target has a stored value / 16, 32 getStatus(target)
+     *  is / is not LOADED / 64 the new failed flag), its id_a, id_b and owner the spans 3i .. 3i + 2 of strs / strOff (empty: null),
+     *  on the stored VModelRecord oldJson[oldOff[i], oldOff[i+1]) (empty: vmr == null).  rowsOut[i] (48 bytes: int cls, int flags,
+     *  int model, int targetCopyCount, int[2] decModel, int[2] decOff, int[2] decLen, long lastUsed): cls 0 created / 1 updated (both:
+     *  the value to set is outBuf[outOff[i], outOff[i+1])) / 2 unchanged / 3 not found / 4 failed precondition / 5 another owner /
+     *  6 call again with 16 or 32 / 7 nothing to do / 8 delete with the old value / 9 things changed / 10 malformed / 11 the host
+     *  decides; decOff / decLen name the ids whose refs go down (modelsRefsJson) inside the old value.  Sizing as modelsRewriteJson.
+     *  flags 0. */
+    static native int vmodelsWriteJson(long h, ByteBuffer reqs, int n, ByteBuffer strs, ByteBuffer strOff, ByteBuffer defaultOwner,
+                                       int defaultOwnerLen, ByteBuffer oldJson, ByteBuffer oldOff, long nowMs, long lastUsedAgeOnAddMs,
+                                       int flags, ByteBuffer outBuf, long outCap, ByteBuffer outOff, ByteBuffer rowsOut,
+                                       ByteBuffer nBytesOut);
     /** hand registry rows back (mmp_models_retire): rows = n ints, the rows whose deletion the listener has seen; flags 1 = every
      *  named row must still be the empty row a deletion leaves (else MMP_EINVAL, nothing changed: the id was registered again).
      *  The survivors move down in order; remapOut (maxModels >= the row count at the call, may be null) gives old row -> new row,

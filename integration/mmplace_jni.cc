@@ -929,6 +929,60 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRegisterJson(
                                           buf<int64_t>(env, lastUsedOut), buf<int32_t>(env, modelIdxOut), buf<int64_t>(env, nBytesOut)));
 }
 
+// incRefCount / decRefCount of the vmodel transactions as a batch of steps on stored values (see mmp_models_refs_json): reqs = n
+// mmp_refs_req, info / infoOff (3n + 1 ints) may be null both.  The capacities are checked here.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRefsJson(JNIEnv *env, jclass, jlong h, jobject reqs, jint n, jobject info,
+                                                                            jobject infoOff, jobject oldJson, jobject oldOff, jint flags,
+                                                                            jobject outBuf, jlong outCap, jobject outOff, jobject classOut,
+                                                                            jobject refsOut, jobject nBytesOut)
+{
+    if (n < 0 || n > INT32_MAX / 3 - 1 || outCap < 0 || !holds<mmp_refs_req>(env, reqs, n, "modelsRefsJson: reqs shorter than n") ||
+        (infoOff && !holds<int32_t>(env, infoOff, 3 * (jlong)n + 1, "modelsRefsJson: infoOff shorter than 3n + 1")) ||
+        !holds<int64_t>(env, oldOff, (jlong)n + 1, "modelsRefsJson: oldOff shorter than n + 1") ||
+        (infoOff && n > 0 && !holds<char>(env, info, buf<int32_t>(env, infoOff)[3 * n], "modelsRefsJson: info shorter than infoOff[3n]")) ||
+        (n > 0 && !holds<char>(env, oldJson, buf<int64_t>(env, oldOff)[n], "modelsRefsJson: oldJson shorter than oldOff[n]")) ||
+        (outBuf && !holds<char>(env, outBuf, outCap, "modelsRefsJson: outBuf shorter than outCap")) ||
+        !holds<int64_t>(env, outOff, (jlong)n + 1, "modelsRefsJson: outOff shorter than n + 1") ||
+        !holds<int32_t>(env, classOut, n, "modelsRefsJson: classOut shorter than n") ||
+        !holds<int32_t>(env, refsOut, n, "modelsRefsJson: refsOut shorter than n") ||
+        !holds<int64_t>(env, nBytesOut, 1, "modelsRefsJson: nBytesOut shorter than one long"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_refs_json(ctx_of(h), buf<mmp_refs_req>(env, reqs), n, buf<char>(env, info), buf<int32_t>(env, infoOff),
+                                      buf<char>(env, oldJson), buf<int64_t>(env, oldOff), static_cast<uint32_t>(flags),
+                                      buf<char>(env, outBuf), outCap, buf<int64_t>(env, outOff), buf<int32_t>(env, classOut),
+                                      buf<int32_t>(env, refsOut), buf<int64_t>(env, nBytesOut)));
+}
+
+// the record step of updateVModel / deleteVModel / PendingTransition.run as a batch (see mmp_vmodels_write_json): reqs = n
+// mmp_vmodel_write_req, strOff 3n + 1 ints, rowsOut n mmp_vmodel_write_row; defaultOwner may be null with length 0.  The capacities
+// are checked here.
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsWriteJson(JNIEnv *env, jclass, jlong h, jobject reqs, jint n, jobject strs,
+                                                                              jobject strOff, jobject defaultOwner, jint defaultOwnerLen,
+                                                                              jobject oldJson, jobject oldOff, jlong nowMs,
+                                                                              jlong lastUsedAgeOnAddMs, jint flags, jobject outBuf,
+                                                                              jlong outCap, jobject outOff, jobject rowsOut,
+                                                                              jobject nBytesOut)
+{
+    if (n < 0 || n > INT32_MAX / 3 - 1 || outCap < 0 || defaultOwnerLen < 0 ||
+        !holds<mmp_vmodel_write_req>(env, reqs, n, "vmodelsWriteJson: reqs shorter than n") ||
+        !holds<int32_t>(env, strOff, 3 * (jlong)n + 1, "vmodelsWriteJson: strOff shorter than 3n + 1") ||
+        !holds<int64_t>(env, oldOff, (jlong)n + 1, "vmodelsWriteJson: oldOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, strs, buf<int32_t>(env, strOff)[3 * n], "vmodelsWriteJson: strs shorter than strOff[3n]")) ||
+        (n > 0 && !holds<char>(env, oldJson, buf<int64_t>(env, oldOff)[n], "vmodelsWriteJson: oldJson shorter than oldOff[n]")) ||
+        (defaultOwnerLen > 0 && !holds<char>(env, defaultOwner, defaultOwnerLen, "vmodelsWriteJson: defaultOwner shorter than its length")) ||
+        (outBuf && !holds<char>(env, outBuf, outCap, "vmodelsWriteJson: outBuf shorter than outCap")) ||
+        !holds<int64_t>(env, outOff, (jlong)n + 1, "vmodelsWriteJson: outOff shorter than n + 1") ||
+        !holds<mmp_vmodel_write_row>(env, rowsOut, n, "vmodelsWriteJson: rowsOut shorter than n") ||
+        !holds<int64_t>(env, nBytesOut, 1, "vmodelsWriteJson: nBytesOut shorter than one long"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_write_json(ctx_of(h), buf<mmp_vmodel_write_req>(env, reqs), n, buf<char>(env, strs), buf<int32_t>(env, strOff),
+                                        buf<char>(env, defaultOwner), defaultOwnerLen, buf<char>(env, oldJson), buf<int64_t>(env, oldOff),
+                                        nowMs, lastUsedAgeOnAddMs, static_cast<uint32_t>(flags), buf<char>(env, outBuf), outCap,
+                                        buf<int64_t>(env, outOff), buf<mmp_vmodel_write_row>(env, rowsOut), buf<int64_t>(env, nBytesOut)));
+}
+
 // rows: n ints; remapOut (may be null) holds maxModels ints, nModelsAfterOut (may be null) one (see mmp_models_retire)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsRetire(JNIEnv *env, jclass, jlong h, jobject rows, jint n, jint flags,
                                                                           jobject remapOut, jint maxModels, jobject nModelsAfterOut)

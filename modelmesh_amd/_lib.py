@@ -194,6 +194,21 @@ assert REGISTER_REQ.itemsize == 16
 MREG_LOAD_NOW, MREG_DELETE = 1, 2
 (MREG_CREATED, MREG_TOUCHED, MREG_EXISTS, MREG_CONFLICT, MREG_ABSENT, MREG_REFERENCED, MREG_DELETABLE, MREG_MALFORMED,
  MREG_HOST) = range(9)
+# mmp_models_refs_json (incRefCount / decRefCount on stored ModelRecord values): request flags, class_out
+REFS_REQ = np.dtype([("flags", "<u4"), ("reserved", "<i4"), ("last_used", "<i8")])
+assert REFS_REQ.itemsize == 16
+MREF_INC, MREF_AUTO_DELETE = 1, 2
+(MREFC_SET, MREFC_CREATED, MREFC_DELETE, MREFC_ENSURE_ABSENT, MREFC_NOT_FOUND, MREFC_MALFORMED, MREFC_HOST) = range(7)
+# mmp_vmodels_write_json (the record step of updateVModel / deleteVModel / PendingTransition.run): ops, request flags, classes, row flags
+VMODEL_WRITE_REQ = np.dtype([("op", "<u4"), ("flags", "<u4")])
+VMODEL_WRITE_ROW = np.dtype([("cls", "<i4"), ("flags", "<u4"), ("model", "<i4"), ("target_copy_count", "<i4"), ("dec_model", "<i4", (2,)),
+                             ("dec_off", "<i4", (2,)), ("dec_len", "<i4", (2,)), ("last_used", "<i8")])
+assert VMODEL_WRITE_REQ.itemsize == 8 and VMODEL_WRITE_ROW.itemsize == 48
+VW_SET, VW_DELETE, VW_COMPLETE, VW_FAIL_FLAG = range(4)
+(VWQ_UPDATE_ONLY, VWQ_FORCE, VWQ_LOAD_NOW, VWQ_TARGET_EXISTS, VWQ_TARGET_LOADED, VWQ_TARGET_NOT_LOADED, VWQ_FAILED) = (1, 2, 4, 8, 16, 32, 64)
+(VWC_CREATED, VWC_UPDATED, VWC_UNCHANGED, VWC_NOT_FOUND, VWC_PRECONDITION, VWC_OWNER_MISMATCH, VWC_NEEDS_TARGET_STATUS, VWC_NOOP,
+ VWC_DELETE, VWC_CHANGED, VWC_MALFORMED, VWC_HOST) = range(12)
+VWF_IN_TRANSITION, VWF_ACTIVE_SWITCHED, VWF_PREV_ACTIVE_UNKNOWN = 1, 2, 4
 # the vmodel table (VModelManager.java:101-110): mmp_vmodels_events_json / _resolve / _transitions / _get / _info
 VMEV_APPEND = 1
 (VMF_FAILED, VMF_ABSENT, VMF_ACTIVE_NULL, VMF_TARGET_NULL, VMF_OWNER_NULL, VMF_HOST) = (1, 2, 4, 8, 16, 32)
@@ -371,6 +386,10 @@ SYMBOLS = [
                                   C.POINTER(C.c_int32)]),
     ("mmp_vmodels_info", C.c_int, [_P, _P]),
     ("mmp_vmodels_retire", C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mmp_models_refs_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_uint32, _P, C.c_int64, _P, _P, _P,
+                                       C.POINTER(C.c_int64)]),
+    ("mmp_vmodels_write_json", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int64,
+                                         _P, _P, C.POINTER(C.c_int64)]),
     ("mmp_pods_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_models_get", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mmp_shard_configure", C.c_int, [_P, C.c_int32, C.c_int32]),

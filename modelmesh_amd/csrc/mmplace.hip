@@ -47,8 +47,10 @@
 #include "pods_retire_kernels.hpp"
 #include "rewrite_kernels.hpp"
 #include "register_kernels.hpp"
+#include "refs_kernels.hpp"
 #include "vmodel_kernels.hpp"
 #include "vmodel_retire_kernels.hpp"
+#include "vmodel_write_kernels.hpp"
 #include "shard_kernels.hpp"
 #include "multi_kernel.hpp"
 #include "rank_sample.hpp"
@@ -522,6 +524,12 @@ struct mmp_ctx {
     // mmp_models_register_json (register_kernels.hpp): one call's requests, their three strings and offsets, classes and
     // last_used; sizes, offsets and rendered bytes are rw_len / rw_off / rw_out.  Owned by batch_mu, used on c->stream.
     DevBuf rg_reqs, rg_info, rg_ioff, rg_cls, rg_lu;
+    // mmp_models_refs_json (refs_kernels.hpp): one call's requests, strings, offsets and classes are the rg_* above (both request
+    // structs take 16 bytes); rf_refs: its counts.  Owned by batch_mu, used on c->stream.
+    DevBuf rf_refs;
+    // mmp_vmodels_write_json (vmodel_write_kernels.hpp): one call's requests, their strings (the default owner behind them) and
+    // offsets, and the answers; the parser's scratch is vm_ev / j_ev / j_status.  Owned by batch_mu, used on c->stream.
+    DevBuf vw_reqs, vw_strs, vw_soff, vw_rows;
     uint64_t id_gen = 1, idd_gen = 0;
     // The vmodel table (vmodel_kernels.hpp), nothing of it allocated before the first vmodel call.  vid_*: its id table, the fields
     // of the model-id table over again (both are driven through IdTabRef).  vm_rows: one VmRow per vmodel; vm_arena: the strings,
@@ -1412,7 +1420,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
-                      &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu,
+                      &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu, &c->rf_refs, &c->vw_reqs, &c->vw_strs, &c->vw_soff, &c->vw_rows,
                       &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_arena,
                       &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
                       &c->vm_ans, &c->vm_list,
@@ -7046,7 +7054,7 @@ try {
 // THE TWO-PASS FRAME of the "next stored value" calls (rewrite_kernels.hpp, register_kernels.hpp): stored values in, rendered
 // values out.  The caller (owner of batch_mu, the device set, every refusal behind it) has staged its own inputs and filled its
 // own members of A; the frame stages the stored values where the parser reads them and fills StoredArgs.  Size bracket: `front`
-// (launches in front of the parser), ingest_models_kernel as over non-deleted events (rows and entries into scratch), the size
+// (launches in front of the parser), the parser stage the caller names (ModelValueParser / VModelValueParser below), the size
 // pass, the scan of the sizes; then the ONE read-back — the offsets and every array of `back` — that decides whether anything is
 // written; write bracket: the write pass and the copy of the bytes, where out_buf holds them.  Nothing reaches the caller's
 // arrays before the last step that can fail, and the call's device span is the sum of the two brackets.
@@ -7055,19 +7063,57 @@ struct RenderBack {
     const DevBuf *dev;
     size_t bytes;
 };
-extern "C++" template <class Args, class Front>
-int render_stored_values(mmp_ctx *c, const char *fn, const char *old_buf, const int64_t *old_off, int32_t n, Args &A, void (*size_pass)(Args),
-                         void (*write_pass)(Args), Front &&front, std::initializer_list<RenderBack> back, char *out_buf, int64_t out_cap,
+// The parser stage over ModelRecord values: ingest_models_kernel as over non-deleted events (rows and entries into scratch).
+struct ModelValueParser {
+    IngestModelsArgs J;
+    int prepare(mmp_ctx *c, int32_t n, int64_t bytes, StoredArgs &A)
+    {
+        size_t ent_cap;
+        if (const int rc = ingest_models_args(c, n, bytes, J, ent_cap)) return rc;
+        HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
+        J.rows = c->j_rows.as<mmp_model_row>();
+        A.buf = J.buf;
+        A.off = J.off;
+        A.pstatus = J.status;
+        A.prow = J.rows;
+        return MMP_OK;
+    }
+    void launch(int32_t n, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J);
+    }
+};
+// The parser stage over VModelRecord values: vm_parse_kernel as over non-deleted events, every event on the one slot of a table
+// nobody reads (the winner rule has nothing to decide here).
+struct VModelValueParser {
+    VmParseArgs J;
+    int prepare(mmp_ctx *c, int32_t n, int64_t, StoredArgs &A)
+    {
+        HIP_TRY(c, c->j_ev.ensure(((size_t)n + 1) * 4));
+        HIP_TRY(c, c->vm_ev.ensure((size_t)n * sizeof(VmEvent)));
+        HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
+        int32_t *slot = c->j_ev.as<int32_t>();
+        HIP_TRY(c, hipMemsetAsync(slot, 0, (size_t)n * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(slot + n, 0xff, 4, c->stream));
+        J = VmParseArgs{c->j_buf.as<char>(), c->j_off.as<int64_t>(), n, ingest_group(n), nullptr, slot, slot + n, c->vm_ev.as<VmEvent>(),
+                        c->j_status.as<int32_t>()};
+        A.buf = J.buf;
+        A.off = J.off;
+        A.pstatus = J.status;
+        A.pev = J.ev;
+        return MMP_OK;
+    }
+    void launch(int32_t n, hipStream_t st) const { hipLaunchKernelGGL(vm_parse_kernel, dim3(div_up(n, kJWaves * J.grp)), dim3(kJBlock), 0, st, J); }
+};
+extern "C++" template <class Args, class Parser, class Front>
+int render_stored_values(mmp_ctx *c, const char *fn, const char *old_buf, const int64_t *old_off, int32_t n, Args &A, Parser &&parser,
+                         void (*size_pass)(Args), void (*write_pass)(Args), Front &&front, std::initializer_list<RenderBack> back, char *out_buf, int64_t out_cap,
                          int64_t *out_off, int64_t *n_bytes_out)
 {
     hipStream_t st = c->stream;
     std::vector<int64_t> rel;
     if (const int rc = stage_strings(c, fn, "", old_buf, old_off, n, c->j_buf, c->j_off, rel)) return rc;
-    IngestModelsArgs J;
-    size_t ent_cap;
-    if (const int rc = ingest_models_args(c, n, rel[n], J, ent_cap)) return rc;
-    HIP_TRY(c, c->j_rows.ensure((size_t)n * sizeof(mmp_model_row)));
-    J.rows = c->j_rows.as<mmp_model_row>();
+    if (const int rc = parser.prepare(c, n, rel[n], A)) return rc;
     HIP_TRY(c, c->rw_len.ensure((size_t)(n + 1) * 8));
     HIP_TRY(c, c->rw_off.ensure((size_t)(n + 1) * 8));
     int64_t *d_len = c->rw_len.as<int64_t>(), *d_off = c->rw_off.as<int64_t>();
@@ -7075,17 +7121,13 @@ int render_stored_values(mmp_ctx *c, const char *fn, const char *old_buf, const 
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
     HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
     HIP_TRY(c, hipMemsetAsync(d_len + n, 0, 8, st));
-    A.buf = J.buf;
-    A.off = J.off;
     A.n = n;
-    A.pstatus = J.status;
-    A.prow = J.rows;
     A.len = d_len;
     A.out_off = d_off;
     const dim3 grid(div_up(n, kJWaves)), block(kJBlock);
     KT_BEGIN(c, st);
     front();
-    hipLaunchKernelGGL(ingest_models_kernel, dim3(div_up(n, kJWaves * J.grp)), block, 0, st, J);
+    parser.launch(n, st);
     hipLaunchKernelGGL(size_pass, grid, block, 0, st, A);
     HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_off, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
     KT_END(c, st);
@@ -7185,7 +7227,8 @@ try {
     A.fail_msg = fail_pod ? c->rw_fmsg.as<char>() : nullptr;
     A.fail_msg_off = fail_pod ? c->rw_fmoff.as<int32_t>() : nullptr;
     A.status = c->rw_status.as<int32_t>();
-    return render_stored_values(c, "mmp_models_rewrite_json", old_buf, old_off, n, A, models_rewrite_kernel<false>, models_rewrite_kernel<true>,
+    return render_stored_values(c, "mmp_models_rewrite_json", old_buf, old_off, n, A, ModelValueParser(), models_rewrite_kernel<false>,
+                                models_rewrite_kernel<true>,
                                 [] {}, {{status_out, &c->rw_status, (size_t)n * 4}}, out_buf, out_cap, out_off, n_bytes_out);
 } MMP_CATCH(c, "mmp_models_rewrite_json")
 
@@ -7252,12 +7295,128 @@ try {
     const auto by_key = [&] {  // the rows of the keys, in front of the parser
         if (model_idx_out) mid_resolve_launch(c, n, model_id_tab(c).published(), c->tune.model_id_hash_bits);
     };
-    return render_stored_values(c, fn, old_buf, old_off, n, A, models_register_kernel<false>, models_register_kernel<true>, by_key,
+    return render_stored_values(c, fn, old_buf, old_off, n, A, ModelValueParser(), models_register_kernel<false>,
+                                models_register_kernel<true>, by_key,
                                 {{class_out, &c->rg_cls, (size_t)n * 4},
                                  {last_used_out, &c->rg_lu, (size_t)n * 8},
                                  {model_idx_out, &c->me_row, model_idx_out ? (size_t)n * 4 : 0}},
                                 out_buf, out_cap, out_off, n_bytes_out);
 } MMP_CATCH(c, "mmp_models_register_json")
+
+int mmp_models_refs_json(mmp_ctx *c, const mmp_refs_req *reqs, int32_t n, const char *info, const int32_t *info_off, const char *old_buf,
+                         const int64_t *old_off, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off, int32_t *class_out,
+                         int32_t *refs_out, int64_t *n_bytes_out)
+try {
+    const char *fn = "mmp_models_refs_json";
+    if (!c || n < 0 || n > INT32_MAX / 3 - 1 || flags || out_cap < 0 || !out_off || !n_bytes_out ||
+        (n > 0 && (!reqs || !old_off || !class_out || !refs_out)))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    // read-only: the locking of mmp_models_register_json
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!c->have_ids) return fail(c, MMP_ESTATE, "%s: load the instance ids first (mmp_pod_ids_load)", fn);
+    // every refusal stands before anything is staged or written: the two kinds of offsets, then the requests
+    if (const int rc = check_offsets(c, fn, "", old_off, n)) return rc;
+    if (info_off)
+        if (const int rc = check_offsets(c, fn, "info ", info_off, 3 * n)) return rc;
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_refs_req &q = reqs[i];
+        if ((q.flags & ~(MMP_MREF_INC | MMP_MREF_AUTO_DELETE)) || q.reserved)
+            return fail(c, MMP_EINVAL, "%s: request %d has flags %u, reserved %d", fn, i, q.flags, q.reserved);
+        if (old_off[i + 1] - old_off[i] >= INT32_MAX) return fail(c, MMP_EINVAL, "%s: value %d holds 2^31 bytes or more", fn, i);
+    }
+    if (n > 0 && ((old_off[n] > old_off[0] && !old_buf) || (info_off && info_off[3 * n] > info_off[0] && !info)))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (n == 0) {
+        out_off[0] = 0;
+        *n_bytes_out = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // the requests and their strings (no info: 3n empty spans)
+    std::vector<int32_t> irel, none;
+    if (!info_off) none.assign((size_t)3 * n + 1, 0);
+    if (const int rc = stage_strings(c, fn, "info ", info, info_off ? info_off : none.data(), 3 * n, c->rg_info, c->rg_ioff, irel)) return rc;
+    HIP_TRY(c, c->rg_reqs.ensure((size_t)n * sizeof(mmp_refs_req)));
+    HIP_TRY(c, hipMemcpyAsync(c->rg_reqs.p, reqs, (size_t)n * sizeof(mmp_refs_req), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, c->rg_cls.ensure((size_t)n * 4));
+    HIP_TRY(c, c->rf_refs.ensure((size_t)n * 4));
+    RefsArgs A{};
+    A.reqs = c->rg_reqs.as<mmp_refs_req>();
+    A.info = c->rg_info.as<char>();
+    A.info_off = c->rg_ioff.as<int32_t>();
+    A.cls = c->rg_cls.as<int32_t>();
+    A.refs = c->rf_refs.as<int32_t>();
+    return render_stored_values(c, fn, old_buf, old_off, n, A, ModelValueParser(), models_refs_kernel<false>,
+                                models_refs_kernel<true>, [] {},
+                                {{class_out, &c->rg_cls, (size_t)n * 4}, {refs_out, &c->rf_refs, (size_t)n * 4}}, out_buf, out_cap,
+                                out_off, n_bytes_out);
+} MMP_CATCH(c, "mmp_models_refs_json")
+
+int mmp_vmodels_write_json(mmp_ctx *c, const mmp_vmodel_write_req *reqs, int32_t n, const char *strs, const int32_t *str_off,
+                           const char *default_owner, int32_t default_owner_len, const char *old_buf, const int64_t *old_off, int64_t now_ms,
+                           int64_t lastused_age_on_add_ms, uint32_t flags, char *out_buf, int64_t out_cap, int64_t *out_off,
+                           mmp_vmodel_write_row *rows_out, int64_t *n_bytes_out)
+try {
+    const char *fn = "mmp_vmodels_write_json";
+    if (!c || n < 0 || n > INT32_MAX / 3 - 1 || flags || out_cap < 0 || !out_off || !n_bytes_out || default_owner_len < 0 ||
+        (default_owner_len > 0 && !default_owner) || (n > 0 && (!reqs || !str_off || !old_off || !rows_out)))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (now_ms <= 0 || lastused_age_on_add_ms < 0)
+        return fail(c, MMP_EINVAL, "%s: now_ms = %lld, lastused_age_on_add_ms = %lld", fn, (long long)now_ms, (long long)lastused_age_on_add_ms);
+    // read-only: the locking of mmp_vmodels_resolve (batch_mu owns the stream, the scratch, and the writers of the model-id table
+    // and the registry this call reads)
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, fn)) return rc;
+    // every refusal stands before anything is staged or written: the two kinds of offsets, then the requests
+    if (const int rc = check_offsets(c, fn, "", old_off, n)) return rc;
+    if (const int rc = check_offsets(c, fn, "string ", str_off, 3 * n)) return rc;
+    constexpr uint32_t kSetFlags = MMP_VWQ_UPDATE_ONLY | MMP_VWQ_FORCE | MMP_VWQ_LOAD_NOW | MMP_VWQ_TARGET_EXISTS | MMP_VWQ_TARGET_LOADED |
+                                   MMP_VWQ_TARGET_NOT_LOADED | MMP_VWQ_FAILED;
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_vmodel_write_req &q = reqs[i];
+        if (q.op > MMP_VW_FAIL_FLAG || (q.flags & ~kSetFlags))
+            return fail(c, MMP_EINVAL, "%s: request %d has op %u, flags %u", fn, i, q.op, q.flags);
+        if ((q.flags & MMP_VWQ_TARGET_LOADED) && (q.flags & MMP_VWQ_TARGET_NOT_LOADED))
+            return fail(c, MMP_EINVAL, "%s: request %d says the target is loaded and not loaded", fn, i);
+        if ((q.op == MMP_VW_SET || q.op == MMP_VW_COMPLETE) && str_off[3 * i + 1] == str_off[3 * i])
+            return fail(c, MMP_EINVAL, "%s: request %d brings no id_a", fn, i);
+        if (old_off[i + 1] - old_off[i] >= kVmMaxValue) return fail(c, MMP_EINVAL, "%s: value %d has 2^30 bytes or more", fn, i);
+    }
+    if (n > 0 && ((old_off[n] > old_off[0] && !old_buf) || (str_off[3 * n] > str_off[0] && !strs))) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (n == 0) {
+        out_off[0] = 0;
+        *n_bytes_out = 0;
+        return MMP_OK;
+    }
+    if ((int64_t)str_off[3 * n] - str_off[0] + default_owner_len > INT32_MAX) return fail(c, MMP_EINVAL, "%s: 2^31 string bytes or more", fn);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    // the requests and their strings; the default owner rides behind them as span 3n
+    const int32_t s0 = str_off[0], sbytes = str_off[3 * n] - s0;
+    std::vector<char> blob((size_t)sbytes + default_owner_len);
+    if (sbytes) memcpy(blob.data(), strs + s0, (size_t)sbytes);
+    if (default_owner_len) memcpy(blob.data() + sbytes, default_owner, (size_t)default_owner_len);
+    std::vector<int32_t> soff((size_t)3 * n + 2), srel;
+    for (int32_t k = 0; k <= 3 * n; k++) soff[k] = str_off[k] - s0;
+    soff[(size_t)3 * n + 1] = sbytes + default_owner_len;
+    if (const int rc = stage_strings(c, fn, "string ", blob.data(), soff.data(), 3 * n + 1, c->vw_strs, c->vw_soff, srel)) return rc;
+    HIP_TRY(c, c->vw_reqs.ensure((size_t)n * sizeof(mmp_vmodel_write_req)));
+    HIP_TRY(c, hipMemcpyAsync(c->vw_reqs.p, reqs, (size_t)n * sizeof(mmp_vmodel_write_req), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, c->vw_rows.ensure((size_t)n * sizeof(mmp_vmodel_write_row)));
+    VmWriteArgs A{};
+    A.reqs = c->vw_reqs.as<mmp_vmodel_write_req>();
+    A.strs = c->vw_strs.as<char>();
+    A.str_off = c->vw_soff.as<int32_t>();
+    A.M = vmodel_models(c);
+    A.model_hmask = hash_mask(c->tune.model_id_hash_bits);
+    A.now = now_ms;
+    A.age = lastused_age_on_add_ms;
+    A.rows = c->vw_rows.as<mmp_vmodel_write_row>();
+    return render_stored_values(c, fn, old_buf, old_off, n, A, VModelValueParser(), vmodels_write_kernel<false>, vmodels_write_kernel<true>,
+                                [] {}, {{rows_out, &c->vw_rows, (size_t)n * sizeof(mmp_vmodel_write_row)}}, out_buf, out_cap, out_off,
+                                n_bytes_out);
+} MMP_CATCH(c, "mmp_vmodels_write_json")
 
 // rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
 static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,

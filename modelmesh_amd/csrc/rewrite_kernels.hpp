@@ -28,13 +28,16 @@
 
 namespace mmp {
 
+struct VmEvent;  // (vmodel_kernels.hpp)
+
 // What every "next stored value" kernel is given alike, and what the host's two-pass frame fills in (mmplace.hip, render_stored_values).
 struct StoredArgs {
     const char *buf;  // the staged stored values (the buffers the parser has just read)
     const int64_t *off;
     int32_t n;
     const int32_t *pstatus;     // the parser's verdict on value i
-    const mmp_model_row *prow;  // ... and the row it read
+    const mmp_model_row *prow;  // ... and the row it read (ModelRecord values: ingest_models_kernel)
+    const VmEvent *pev;         // ... or the slots it read (VModelRecord values: vm_parse_kernel)
     int64_t *len;               // size pass: bytes of value i
     const int64_t *out_off;     // write pass: exclusive scan of len, out_off[n] = the total
     char *out;

@@ -400,6 +400,86 @@ class Solver:
                                                ptr(out_off), ptr(cls), ptr(lu), ptr(rows), C.byref(total))
         return out[:int(out_cap)], out_off, cls[:n], lu[:n], None if rows is None else rows[:n], total.value, rc
 
+    def models_refs_json(self, reqs, old_values, infos=None):
+        """incRefCount / decRefCount on stored ModelRecord values (mmp_models_refs_json): reqs is a REFS_REQ array, old_values[i]
+        the stored value (empty: mr == null), infos[i] = (type, encKey, mPath) as bytes/str with "" or None for null (None: no
+        request brings one).  Returns (values, classes, refs): values[i] is bytes where classes[i] is MREFC_SET / MREFC_CREATED and
+        None elsewhere, refs[i] the count the Java method returns.  Two calls: the sizes, then the bytes."""
+        r = self.models_refs_json_raw(reqs, old_values, infos, 0)
+        self._ck(r[5])
+        out, off, cls, refs, total, rc = self.models_refs_json_raw(reqs, old_values, infos, r[4])
+        self._ck(rc)
+        assert total == r[4]  # (a pure function of the arguments)
+        rendered = (_lib.MREFC_SET, _lib.MREFC_CREATED)
+        vals = [bytes(out[off[i]:off[i + 1]]) if cls[i] in rendered else None for i in range(len(cls))]
+        return vals, cls, refs
+
+    def models_refs_json_raw(self, reqs, old_values, infos, out_cap, fill=0, null_out=False, flags=0, old_off=None, info_off=None):
+        """One mmp_models_refs_json call with exactly this capacity (null_out: a NULL out_buf), the outputs filled with the byte
+        `fill` first: (out bytes as uint8[out_cap], out_off[n + 1], classes[n], refs[n], total, rc); total is -1 where the library
+        did not set it.  old_off / info_off: these offsets instead of the packed ones."""
+        reqs = np.ascontiguousarray(reqs, dtype=_lib.REFS_REQ)
+        n = len(reqs)
+        assert len(old_values) == n and (infos is None or len(infos) == n)
+        iblob = ioff = None
+        if infos is not None:
+            iblob, ioff = self._pack([x if x is not None else b"" for t in infos for x in t])
+            ioff = ioff.astype(np.int32) if info_off is None else np.ascontiguousarray(info_off, dtype=np.int32)
+        blob, off = self._pack(old_values)
+        if old_off is not None:
+            off = np.ascontiguousarray(old_off, dtype=np.int64)
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        out_off = np.zeros(n + 1, np.int64)
+        cls = np.zeros(max(n, 1), np.int32)
+        refs = np.zeros(max(n, 1), np.int32)
+        for a in (out, out_off, cls, refs):
+            a.view(np.uint8)[:] = fill
+        total = C.c_int64(-1)
+        rc = self.lib.mmp_models_refs_json(self.h, ptr(reqs), n, iblob, ptr(ioff), blob, ptr(off), flags,
+                                           None if null_out else ptr(out), int(out_cap), ptr(out_off), ptr(cls), ptr(refs),
+                                           C.byref(total))
+        return out[:int(out_cap)], out_off, cls[:n], refs[:n], total.value, rc
+
+    def vmodels_write_json(self, reqs, strs, old_values, now_ms, lastused_age_on_add_ms, default_owner=b""):
+        """The record step of the three vmodel writers (mmp_vmodels_write_json): reqs is a VMODEL_WRITE_REQ array, strs[i] =
+        (id_a, id_b, owner) as bytes/str with "" or None for null, old_values[i] the stored VModelRecord value (empty: vmr == null).
+        Returns (values, rows): values[i] is bytes where rows["cls"][i] is VWC_CREATED / VWC_UPDATED and None elsewhere, rows a
+        VMODEL_WRITE_ROW array.  Two calls: the sizes, then the bytes."""
+        args = (reqs, strs, old_values, now_ms, lastused_age_on_add_ms, default_owner)
+        r = self.vmodels_write_json_raw(*args, 0)
+        self._ck(r[4])
+        out, off, rows, total, rc = self.vmodels_write_json_raw(*args, r[3])
+        self._ck(rc)
+        assert total == r[3]  # (read-only over a registry nobody edited in between)
+        rendered = (_lib.VWC_CREATED, _lib.VWC_UPDATED)
+        vals = [bytes(out[off[i]:off[i + 1]]) if rows["cls"][i] in rendered else None for i in range(len(rows))]
+        return vals, rows
+
+    def vmodels_write_json_raw(self, reqs, strs, old_values, now_ms, lastused_age_on_add_ms, default_owner, out_cap, fill=0,
+                               null_out=False, flags=0, old_off=None, str_off=None):
+        """One mmp_vmodels_write_json call with exactly this capacity (null_out: a NULL out_buf), the outputs filled with the byte
+        `fill` first: (out bytes as uint8[out_cap], out_off[n + 1], rows[n], total, rc); total is -1 where the library did not set
+        it.  old_off / str_off: these offsets instead of the packed ones."""
+        reqs = np.ascontiguousarray(reqs, dtype=_lib.VMODEL_WRITE_REQ)
+        n = len(reqs)
+        assert len(strs) == n and len(old_values) == n
+        sblob, soff = self._pack([x if x is not None else b"" for t in strs for x in t])
+        soff = soff.astype(np.int32) if str_off is None else np.ascontiguousarray(str_off, dtype=np.int32)
+        blob, off = self._pack(old_values)
+        if old_off is not None:
+            off = np.ascontiguousarray(old_off, dtype=np.int64)
+        owner = default_owner.encode() if isinstance(default_owner, str) else bytes(default_owner or b"")
+        out = np.zeros(max(int(out_cap), 1), np.uint8)
+        out_off = np.zeros(n + 1, np.int64)
+        rows = np.zeros(max(n, 1), _lib.VMODEL_WRITE_ROW)
+        for a in (out, out_off, rows):
+            a.view(np.uint8)[:] = fill
+        total = C.c_int64(-1)
+        rc = self.lib.mmp_vmodels_write_json(self.h, ptr(reqs), n, sblob, ptr(soff), owner or None, len(owner), blob, ptr(off),
+                                             int(now_ms), int(lastused_age_on_add_ms), flags, None if null_out else ptr(out),
+                                             int(out_cap), ptr(out_off), ptr(rows), C.byref(total))
+        return out[:int(out_cap)], out_off, rows[:n], total.value, rc
+
     def model_ids_load(self, ids):
         """Name the registry's rows (mmp_model_ids_load): ids[i] (bytes/str) is the id of row i; len(ids) must equal the row count."""
         blob, off = self._pack(ids)
