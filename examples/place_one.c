@@ -55,7 +55,31 @@ int main(void)
         return 1;
     }
     printf("chosen=%d best=%d candidates=%d\n", out.chosen, out.best, out.n_candidates);
+    /* The same request with the model named by its id: the registry's rows are named once (mmp_model_ids_load), then a request
+     * brings the id's bytes and the library resolves them on the device inside the call (mmp_place_batch_ck). */
+    const char ids[] = "my-model";
+    const int32_t id_off[2] = {0, (int32_t)sizeof ids - 1};
+    mmp_place_caller caller;
+    memset(&caller, 0, sizeof caller);
+    caller.self_pod = rq.self_pod;
+    caller.fresh_lru = rq.fresh_lru;
+    caller.fresh_capacity = rq.fresh_capacity;
+    caller.fresh_used = rq.fresh_used;
+    caller.fresh_count = rq.fresh_count;
+    mmp_place_req_c rc_row;
+    memset(&rc_row, 0, sizeof rc_row);
+    rc_row.model = -1; /* ignored: the key names the model */
+    mmp_place_out keyed;
+    int32_t row = -2;
+    if ((rc = mmp_model_ids_load(ctx, ids, id_off, 1)) ||
+        (rc = mmp_place_batch_ck(ctx, &caller, &rc_row, 1, ids, id_off, NULL, 0, now, &keyed, &row))) {
+        fprintf(stderr, "libmmplace: %d (%s)\n", rc, mmp_last_error(ctx));
+        mmp_destroy(ctx);
+        return 1;
+    }
+    printf("by id: row=%d chosen=%d best=%d candidates=%d\n", row, keyed.chosen, keyed.best, keyed.n_candidates);
     mmp_destroy(ctx);
-    /* pod 0 holds the model, so the most desirable eligible pod is pod 1 */
+    /* pod 0 holds the model, so the most desirable eligible pod is pod 1; the id names row 0 and decides the same */
+    if (row != 0 || memcmp(&keyed, &out, sizeof out) != 0) return 3;
     return out.best == 1 ? 0 : 2;
 }

@@ -706,6 +706,42 @@ int mmp_miss_batch_c(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_plac
                      int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now_ms,
                      int64_t in_use_expiry_ms, mmp_gate_out *gate_outs, mmp_place_out *place_outs);
 
+/* The single-caller forms BY MODEL ID.  The three calls above name a request's model by registry row, and a caller that keeps no id
+ * map (the id table lives on the device: mmp_model_ids_load, below) would first ask mmp_model_ids_resolve — a call that takes the
+ * batch lock and queues behind every large batch.  These forms take the model's KEY instead (the raw bytes of the model id, as the
+ * registry listener hands them to mmp_models_events_json) and resolve it on the device inside the same call: one latency slot, one
+ * stream, one wait, no batch lock (csrc/keyed_kernels.hpp).
+ *
+ * Key i is keys[key_off[i], key_off[i + 1]): n + 1 monotone offsets, under the conventions of mmp_model_ids_resolve.  The `model`
+ * field of the request rows is IGNORED on input, and the caller's arrays are never written (mmp_miss_batch_c's "names two models"
+ * check has no counterpart: both halves take the key's row).  model_idx_out (n words, may be NULL) receives the row each key
+ * resolved to, or -1.
+ *
+ * THE RULE BY KEY: request i is decided exactly as the existing _c call decides the same rows with model = r, where r is the row
+ * mmp_model_ids_resolve answers for key i against the id table as published at the moment the call captured it; an unknown id is
+ * r = -1, which every decision treats as "no such model", as it treats any model outside [0, n_models).  The result rows are those
+ * rows' results byte for byte, and model_idx_out[i] = r.  A registry event batch (mmp_models_events_json) publishes the ids that
+ * join together with their registry rows: a call sees a batch before or after, never an id whose row the registry does not have.
+ *
+ * MMP_EINVAL, every output untouched: everything the _c forms refuse; a NULL key_off with n > 0; offsets that are not monotone; NULL
+ * keys with key bytes present.  MMP_ESTATE: as the _c forms (no commit yet, a pod-axis shard context), and under the conditions of
+ * the id table's guard — no mmp_model_ids_load yet, or the registry was resized by index since.  n = 0 is a valid call.  Up to 256
+ * requests with up to 16384 key bytes (and the pools of the _c forms' latency path; the load targets' extra pool up to 2048) ride a
+ * latency slot; larger calls are staged under the batch lock like every large call. */
+int mmp_place_batch_ck(mmp_ctx *ctx, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
+                       const int32_t *key_off, const int32_t *extra_pool, int32_t n_extra, int64_t now_ms, mmp_place_out *outs,
+                       int32_t *model_idx_out);
+int mmp_route_batch_ck(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_gate_req_c *gate_reqs,
+                       const mmp_serve_req_c *serve_reqs, int32_t n, const char *keys, const int32_t *key_off,
+                       const mmp_serve_counter *counters, int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time,
+                       int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now_ms, int64_t in_use_expiry_ms,
+                       mmp_gate_out *gate_outs, mmp_serve_out *serve_outs, int32_t *model_idx_out);
+int mmp_miss_batch_ck(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_place_caller *place_caller,
+                      const mmp_gate_req_c *gate_reqs, const mmp_place_req_c *place_reqs, int32_t n, const char *keys,
+                      const int32_t *key_off, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
+                      const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now_ms,
+                      int64_t in_use_expiry_ms, mmp_gate_out *gate_outs, mmp_place_out *place_outs, int32_t *model_idx_out);
+
 /* triggerProactiveLoadsForInstanceSubset (MM.java:6616-6747, excludeTypes == null) over the
  * committed snapshot and the loaded model table (models in registry iteration order): which
  * unloaded models the leader would proactively load, most recently used first. The caller then

@@ -101,6 +101,20 @@ final class MmPlace {
                                       ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool, int nExplicit,
                                       ByteBuffer extraPool, int nExtra, long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts,
                                       ByteBuffer placeOuts);
+    /** the single-caller forms BY MODEL ID (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck): request i names its model by
+     *  keys[keyOff[i], keyOff[i + 1]) — the model id's UTF-8 bytes, keyOff = n + 1 ints — and the library resolves it on the device
+     *  inside the call (one latency slot, one wait, no batch lock: no modelIdsResolve in front).  The rows' model field is ignored;
+     *  modelIdxOut (n ints, may be null) receives the row of each key, -1 for an unknown id. */
+    static native int placeBatchKeyed(long h, ByteBuffer caller, ByteBuffer reqs, int n, ByteBuffer keys, ByteBuffer keyOff,
+                                      ByteBuffer extraPool, int nExtra, long nowMs, ByteBuffer outs, ByteBuffer modelIdxOut);
+    static native int routeBatchKeyed(long h, ByteBuffer caller, ByteBuffer gateReqs, ByteBuffer serveReqs, int n, ByteBuffer keys,
+                                      ByteBuffer keyOff, ByteBuffer counters, int nCounters, ByteBuffer exclPod, ByteBuffer exclTime,
+                                      int nExcl, ByteBuffer explicitPool, int nExplicit, long nowMs, long inUseFailureExpiryMs,
+                                      ByteBuffer gateOuts, ByteBuffer serveOuts, ByteBuffer modelIdxOut);
+    static native int missBatchKeyed(long h, ByteBuffer caller, ByteBuffer placeCaller, ByteBuffer gateReqs, ByteBuffer placeReqs, int n,
+                                     ByteBuffer keys, ByteBuffer keyOff, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl,
+                                     ByteBuffer explicitPool, int nExplicit, ByteBuffer extraPool, int nExtra, long nowMs,
+                                     long inUseFailureExpiryMs, ByteBuffer gateOuts, ByteBuffer placeOuts, ByteBuffer modelIdxOut);
     static native int proactivePlan(long h, int defaultModelSizeUnits, long nowMs, int maxOut, ByteBuffer outModel,
                                     ByteBuffer outLastUsed, ByteBuffer info);
     static native int proactivePlanSubset(long h, int partition, ByteBuffer skipModels, int nSkip, int defaultModelSizeUnits,
@@ -316,6 +330,28 @@ final class MmPlace {
     static final int NONE = -1, SELF = -2;
 
     static ByteBuffer direct(int bytes) { return ByteBuffer.allocateDirect(bytes).order(ByteOrder.LITTLE_ENDIAN); }
+    /** bytes [off, off + len) of a direct buffer as a direct buffer of its own (the natives read a buffer from its address) */
+    static ByteBuffer slice(ByteBuffer b, int off, int len) {
+        ByteBuffer d = b.duplicate();
+        d.position(off).limit(off + len);
+        return d.slice().order(ByteOrder.LITTLE_ENDIAN);
+    }
+}
+
+/** One model id as the keyed natives take it: { the id's UTF-8 bytes, keyOff = {0, length} }, in per-thread direct buffers. */
+final class ModelKey {
+    private static final ThreadLocal<ByteBuffer[]> BUF = ThreadLocal.withInitial(() -> new ByteBuffer[] { MmPlace.direct(256), MmPlace.direct(8) });
+
+    static ByteBuffer[] of(String modelId) {
+        final byte[] utf8 = modelId.getBytes(java.nio.charset.StandardCharsets.UTF_8);
+        ByteBuffer[] b = BUF.get();
+        if (b[0].capacity() < utf8.length) b[0] = MmPlace.direct(Math.max(utf8.length, 2 * b[0].capacity()));
+        b[0].clear();
+        b[0].put(utf8);
+        b[1].putInt(0, 0);
+        b[1].putInt(4, utf8.length);
+        return b;
+    }
 }
 
 /**
@@ -328,6 +364,10 @@ final class MmPlace {
  * per batch of events with the raw key and the raw byte[] of each event, ENTRY_DELETED as a deleted flag: the listener keeps no
  * id map, modelIndexOf is modelIdsResolve; a listener that numbers its rows itself uses modelsUpsertJson by index, one that holds
  * parsed ModelRecords modelsLoad / modelsUpsert).
+ *
+ * The REQUEST PATH of a binding without an id map (modelIdsResident() == true) never calls modelIndexOf: modelIdsResolve takes the
+ * library's batch lock and would queue every getNext behind the large batches.  The load balancers below hand the model id's UTF-8
+ * bytes to placeBatchKeyed / routeBatchKeyed instead, which resolve the id on the device inside the one call on a latency slot.
  */
 interface GpuMeshBinding {
     long handle();
@@ -335,6 +375,7 @@ interface GpuMeshBinding {
     int podIndexOf(String instanceId);      // -1 if unknown
     String instanceIdOf(int podIndex);
     int modelIndexOf(String modelId);       // -1 if unknown
+    boolean modelIdsResident();             // the id -> row map lives in the library alone (modelIdsLoad + modelsEventsJson)
     String selfInstanceId();
     boolean sendDestinationId();            // ModelMesh.sendDestinationId
     InstanceRecord freshSelf();             // getFreshInstanceRecord(), ModelMesh.java:5369
@@ -391,6 +432,7 @@ class GpuCacheMissLB extends ModelMesh.IdBasedLoadBalancer {
             for (String iid : exclude.explicit) { int p = mesh.podIndexOf(iid); if (p >= 0) { x.putInt(p); nExtra++; } }
         for (String iid : notLive) { int p = mesh.podIndexOf(iid); if (p >= 0) { x.putInt(p); nExtra++; } }
 
+        if (mesh.modelIdsResident()) return decideKeyed(exclude, fresh, x, nExtra, pick, nowMs);
         ByteBuffer q = REQ.get(); q.clear();               // mmp_place_req, 64 bytes (include/mmplace.h)
         q.putInt(mesh.modelIndexOf(mesh.currentModelId())); // model
         q.putInt(mesh.podIndexOf(mesh.selfInstanceId()));   // self_pod
@@ -406,6 +448,30 @@ class GpuCacheMissLB extends ModelMesh.IdBasedLoadBalancer {
         final int[] last = LAST_OUT.get();
         for (int i = 0; i < 4; i++) last[i] = o.getInt(4 * i);        // chosen, best, n_candidates, hash
         return o.getInt(0);  // read from this thread's own OUT buffer, never from shared state
+    }
+
+    private static final ThreadLocal<ByteBuffer> CALLER = ThreadLocal.withInitial(() -> MmPlace.direct(40));
+    private static final ThreadLocal<ByteBuffer> REQ_C = ThreadLocal.withInitial(() -> MmPlace.direct(24));
+
+    /** The same decision with the model named by its id: mmp_place_caller (40 bytes) + one mmp_place_req_c (24 bytes) + the id's
+     *  UTF-8 bytes; the library resolves the id on the device inside the call (no modelIndexOf, no batch lock). */
+    private int decideKeyed(ModelMesh.CacheMissExcludeSet exclude, InstanceRecord fresh, ByteBuffer x, int nExtra, int pick, long nowMs) {
+        ByteBuffer c = CALLER.get(); c.clear();
+        c.putInt(mesh.podIndexOf(mesh.selfInstanceId()));   // self_pod
+        c.putInt(exclude.favourSelf ? 1 : 0);               // flags (MMP_REQ_FAVOUR_SELF)
+        c.putLong(fresh.getLruTime()); c.putLong(fresh.getCapacity()); c.putLong(fresh.getUsed());
+        c.putInt(fresh.getCount()); c.putInt(fresh.getReqsPerMinute());
+        ByteBuffer q = REQ_C.get(); q.clear();
+        q.putInt(-1);                                       // model: ignored, the key names it
+        q.putInt(pick);
+        q.putLong(exclude.lastUsedTime);
+        q.putInt(0); q.putInt(nExtra);                      // extra_off, n_extra
+        final ByteBuffer[] key = ModelKey.of(mesh.currentModelId());
+        ByteBuffer o = OUT.get();
+        MmPlace.placeBatchKeyed(mesh.handle(), c, q, 1, key[0], key[1], x, nExtra, nowMs, o, null);
+        final int[] last = LAST_OUT.get();
+        for (int i = 0; i < 4; i++) last[i] = o.getInt(4 * i);
+        return o.getInt(0);
     }
 
     @SuppressWarnings("unchecked")
@@ -497,6 +563,7 @@ class GpuForwardingLB extends ModelMesh.IdBasedLoadBalancer {
             int p = mesh.podIndexOf(tried.getKey());
             if (p >= 0) { ep.putInt(4 * nExcl, p); et.putLong(8 * nExcl, tried.getValue()); nExcl++; }
         }
+        if (mesh.modelIdsResident()) return decideKeyed(filtered, cnt, nCnt, ep, et, nExcl, nowMs);
         ByteBuffer q = REQ.get(); q.clear();            // mmp_serve_req, 48 bytes
         q.putInt(mesh.modelIndexOf(mesh.currentModelId()));
         q.putInt(mesh.podIndexOf(mesh.selfInstanceId()));
@@ -508,6 +575,38 @@ class GpuForwardingLB extends ModelMesh.IdBasedLoadBalancer {
         q.putInt(0); q.putInt(nCnt);                    // cnt_off, n_cnt
         ByteBuffer o = OUT.get();
         MmPlace.serveBatch(mesh.handle(), q, 1, cnt, nCnt, ep, et, nExcl, nowMs, o);
+        final long[] last = LAST_OUT.get();
+        last[0] = o.getInt(0);
+        last[1] = o.getLong(8);
+        return o.getInt(0);
+    }
+
+    private static final ThreadLocal<ByteBuffer> CALLER = ThreadLocal.withInitial(() -> MmPlace.direct(112));
+    private static final ThreadLocal<ByteBuffer> ROWS_C = ThreadLocal.withInitial(() -> MmPlace.direct(48 + 24 + 8));
+
+    /** The same selection with the model named by its id, through the keyed route seam (there is no keyed serve-only call: the
+     *  per-request seam of invokeModel is guards + serve target).  The serve row is the one decide() fills — the library builds it
+     *  from mmp_seam_caller {self_pod, local_in_flight, last_invoke_time}, the gate row's exclusion range and the mmp_serve_req_c
+     *  row (include/mmplace.h, THE RULE) — and the guards' half, evaluated on a row that carries that range alone, is not read. */
+    private int decideKeyed(ModelMesh.MapFilteringSet<String, Long> filtered, ByteBuffer cnt, int nCnt, ByteBuffer ep, ByteBuffer et,
+                            int nExcl, long nowMs) {
+        ByteBuffer c = CALLER.get();
+        for (int i = 0; i < 112; i += 8) c.putLong(i, 0L);
+        c.putInt(0, mesh.podIndexOf(mesh.selfInstanceId()));   // self_pod
+        c.putInt(96, mesh.localInvokesInFlight());             // local_in_flight
+        c.putLong(104, mesh.lastInvokeTime());                 // last_invoke_time
+        ByteBuffer r = ROWS_C.get();
+        for (int i = 0; i < 80; i += 8) r.putLong(i, 0L);
+        r.putInt(0, -1);                                       // gate row: model (ignored, the key names it)
+        r.putInt(8, 0); r.putInt(12, nExcl);                   // gate row: excl_off, n_excl — the range the serve half reads
+        r.putInt(48, (filtered.excludeSelf ? 1 : 0) | (filtered.preferSelf ? 2 : 0)); // serve row: flags
+        r.putInt(52, 0); r.putInt(56, nCnt);                   // cnt_off, n_cnt
+        r.putLong(64, mesh.assumeCompletedAfterMillis(filtered.modelType));
+        final ByteBuffer gate = MmPlace.slice(r, 0, 48), serve = MmPlace.slice(r, 48, 24), gateOut = MmPlace.slice(r, 72, 8);
+        final ByteBuffer[] key = ModelKey.of(mesh.currentModelId());
+        ByteBuffer o = OUT.get();
+        MmPlace.routeBatchKeyed(mesh.handle(), c, gate, serve, 1, key[0], key[1], cnt, nCnt, ep, et, nExcl, null, 0, nowMs,
+                                ModelMesh.IN_USE_LOAD_FAILURE_EXPIRY_MS, gateOut, o, null);
         final long[] last = LAST_OUT.get();
         last[0] = o.getInt(0);
         last[1] = o.getLong(8);

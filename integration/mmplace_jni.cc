@@ -358,6 +358,78 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_missBatchCaller(JNI
                                   nExplicit, buf<int32_t>(env, extraPool), nExtra, nowMs, inUseFailureExpiryMs,
                                   buf<mmp_gate_out>(env, gateOuts), buf<mmp_place_out>(env, placeOuts)));
 }
+// ---- the single-caller forms BY MODEL ID: request i names its model by keys[keyOff[i], keyOff[i + 1]) (the model id's UTF-8 bytes),
+// resolved on the device inside the call; modelIdxOut (n ints, may be null) receives the rows (include/mmplace.h: THE RULE BY KEY)
+static bool holds_keys(JNIEnv *env, const char *who, jobject keys, jobject keyOff, jint n, jobject modelIdxOut)
+{
+    if (n < 0) return false;
+    if (n == 0) return true;  // (a valid call without keys)
+    if (!holds<int32_t>(env, keyOff, (jlong)n + 1, who)) return false;
+    if (!holds<char>(env, keys, (jlong)buf<int32_t>(env, keyOff)[n], who)) return false;
+    return !modelIdxOut || holds<int32_t>(env, modelIdxOut, n, who);
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_placeBatchKeyed(JNIEnv *env, jclass, jlong h, jobject caller, jobject reqs,
+                                                                             jint n, jobject keys, jobject keyOff, jobject extraPool,
+                                                                             jint nExtra, jlong nowMs, jobject outs, jobject modelIdxOut)
+{
+    if (!holds_keys(env, "placeBatchKeyed: keyOff / keys / modelIdxOut shorter than the call's n", keys, keyOff, n, modelIdxOut) ||
+        !holds<mmp_place_caller>(env, caller, 1, "placeBatchKeyed: caller shorter than one mmp_place_caller") ||
+        !holds<mmp_place_req_c>(env, reqs, n, "placeBatchKeyed: reqs shorter than n requests") ||
+        !holds<int32_t>(env, extraPool, nExtra, "placeBatchKeyed: extraPool shorter than nExtra entries") ||
+        !holds<mmp_place_out>(env, outs, n, "placeBatchKeyed: outs shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_place_batch_ck(ctx_of(h), buf<mmp_place_caller>(env, caller), buf<mmp_place_req_c>(env, reqs), n, buf<char>(env, keys),
+                                    buf<int32_t>(env, keyOff), buf<int32_t>(env, extraPool), nExtra, nowMs, buf<mmp_place_out>(env, outs),
+                                    buf<int32_t>(env, modelIdxOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_routeBatchKeyed(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                             jobject gateReqs, jobject serveReqs, jint n, jobject keys,
+                                                                             jobject keyOff, jobject counters, jint nCounters,
+                                                                             jobject exclPod, jobject exclTime, jint nExcl,
+                                                                             jobject explicitPool, jint nExplicit, jlong nowMs,
+                                                                             jlong inUseFailureExpiryMs, jobject gateOuts, jobject serveOuts,
+                                                                             jobject modelIdxOut)
+{
+    if (!holds_keys(env, "routeBatchKeyed: keyOff / keys / modelIdxOut shorter than the call's n", keys, keyOff, n, modelIdxOut) ||
+        !holds<mmp_seam_caller>(env, caller, 1, "routeBatchKeyed: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "routeBatchKeyed: gateReqs shorter than n requests") ||
+        !holds<mmp_serve_req_c>(env, serveReqs, n, "routeBatchKeyed: serveReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "routeBatchKeyed: gateOuts shorter than n results") ||
+        !holds<mmp_serve_out>(env, serveOuts, n, "routeBatchKeyed: serveOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_route_batch_ck(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_gate_req_c>(env, gateReqs),
+                                    buf<mmp_serve_req_c>(env, serveReqs), n, buf<char>(env, keys), buf<int32_t>(env, keyOff),
+                                    buf<mmp_serve_counter>(env, counters), nCounters, buf<int32_t>(env, exclPod),
+                                    buf<int64_t>(env, exclTime), nExcl, buf<int32_t>(env, explicitPool), nExplicit, nowMs,
+                                    inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_serve_out>(env, serveOuts),
+                                    buf<int32_t>(env, modelIdxOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_missBatchKeyed(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                            jobject placeCaller, jobject gateReqs, jobject placeReqs,
+                                                                            jint n, jobject keys, jobject keyOff, jobject exclPod,
+                                                                            jobject exclTime, jint nExcl, jobject explicitPool,
+                                                                            jint nExplicit, jobject extraPool, jint nExtra, jlong nowMs,
+                                                                            jlong inUseFailureExpiryMs, jobject gateOuts, jobject placeOuts,
+                                                                            jobject modelIdxOut)
+{
+    if (!holds_keys(env, "missBatchKeyed: keyOff / keys / modelIdxOut shorter than the call's n", keys, keyOff, n, modelIdxOut) ||
+        !holds<mmp_seam_caller>(env, caller, 1, "missBatchKeyed: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_place_caller>(env, placeCaller, 1, "missBatchKeyed: placeCaller shorter than one mmp_place_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "missBatchKeyed: gateReqs shorter than n requests") ||
+        !holds<mmp_place_req_c>(env, placeReqs, n, "missBatchKeyed: placeReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "missBatchKeyed: gateOuts shorter than n results") ||
+        !holds<mmp_place_out>(env, placeOuts, n, "missBatchKeyed: placeOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_miss_batch_ck(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_place_caller>(env, placeCaller),
+                                   buf<mmp_gate_req_c>(env, gateReqs), buf<mmp_place_req_c>(env, placeReqs), n, buf<char>(env, keys),
+                                   buf<int32_t>(env, keyOff), buf<int32_t>(env, exclPod), buf<int64_t>(env, exclTime), nExcl,
+                                   buf<int32_t>(env, explicitPool), nExplicit, buf<int32_t>(env, extraPool), nExtra, nowMs,
+                                   inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_place_out>(env, placeOuts),
+                                   buf<int32_t>(env, modelIdxOut)));
+}
 
 // ---- rebalancers (MM.java:5636-5871, 6110-6335, 6616-6747, 6959-7147) ---------------------------------
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_proactivePlan(JNIEnv *env, jclass, jlong h,

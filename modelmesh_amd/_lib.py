@@ -343,7 +343,13 @@ SYMBOLS = [
                                     _P, _P]),
     ("mmp_miss_batch_c", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64,
                                    C.c_int64, _P, _P]),
-    ("mmp_proactive_plan", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
+    # the same three by model id: keys / key_off behind n, model_idx_out last
+    ("mmp_place_batch_ck", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P]),
+    ("mmp_route_batch_ck", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64,
+                                     C.c_int64, _P, _P, _P]),
+    ("mmp_miss_batch_ck", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32,
+                                    C.c_int64, C.c_int64, _P, _P, _P]),
+    ("mmp_proactive_plan",C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     ("mmp_proactive_plan_subset", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     ("mmp_registry_prune", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _P, C.c_int32, _P, C.c_int32, _P]),
     ("mmp_registry_missing_get", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),

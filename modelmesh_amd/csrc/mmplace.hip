@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -44,6 +45,7 @@
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
+#include "keyed_kernels.hpp"
 #include "pods_retire_kernels.hpp"
 #include "rewrite_kernels.hpp"
 #include "register_kernels.hpp"
@@ -241,6 +243,33 @@ struct RouteSlot {  // mmp_route_batch: the serve half shares the guards' exclus
                                 excl_time = slot_after(explicit_pool, kExcl, 8),
                                 gouts = slot_first(kSlotOut, kN, sizeof(mmp_gate_out)), souts = slot_after(gouts, kN, sizeof(mmp_serve_out));
     static_assert(slot_fits({greqs, sreqs, counters, excl_pod, explicit_pool, excl_time, gouts, souts}), "route slot layout");
+};
+// The request calls by model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck; keyed_kernels.hpp): the layout of the call they
+// resolve in front of, with the key bytes (kKeyedPad readable bytes behind them) and the n + 1 key offsets behind its requests and
+// the resolved rows behind its results.  kKeyBytes: the key bytes a call may bring onto a slot.
+constexpr int kKeyedN = 256, kKeyedKeyBytes = kKeyedLdsBytes;
+struct KeyedPlaceSlot {  // a 256-request layout of its own: PlaceSlot fills its buffers
+    static constexpr int kN = kKeyedN, kExtra = MissSlot::kPool, kKeyBytes = kKeyedKeyBytes;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), keys = slot_after(reqs, kKeyBytes + kKeyedPad, 1),
+                                key_off = slot_after(keys, kN + 1, 4), extra = slot_first(kSlotPool, kExtra, 4),
+                                outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out)), idx = slot_after(outs, kN, 4);
+    static_assert(slot_fits({reqs, keys, key_off, extra, outs, idx}), "keyed place slot layout");
+};
+struct KeyedMissSlot {
+    using L = MissSlot;
+    static constexpr int kN = kKeyedN, kKeyBytes = kKeyedKeyBytes;
+    static constexpr SlotRegion keys = slot_after(L::greqs, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
+                                idx = slot_after(L::gouts, kN, 4);
+    static_assert(kN <= L::kN && slot_fits({L::preqs, L::greqs, keys, key_off, L::extra, L::excl_pod, L::explicit_pool, L::excl_time, L::pouts, L::gouts, idx}),
+                  "keyed miss slot layout");
+};
+struct KeyedRouteSlot {
+    using L = RouteSlot;
+    static constexpr int kN = kKeyedN, kKeyBytes = kKeyedKeyBytes;
+    static constexpr SlotRegion keys = slot_after(L::counters, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
+                                idx = slot_after(L::souts, kN, 4);
+    static_assert(kN <= L::kN && slot_fits({L::greqs, L::sreqs, L::counters, keys, key_off, L::excl_pod, L::explicit_pool, L::excl_time, L::gouts, L::souts, idx}),
+                  "keyed route slot layout");
 };
 struct EvictSlot {  // mmp_evict_batch: as many 32-byte result rows as the result buffer holds (2048); their 16-byte requests fit
     static constexpr int kN = (int)(kSlotBufBytes[kSlotOut] / sizeof(mmp_evict_out));
@@ -485,13 +514,22 @@ struct mmp_ctx {
     uint64_t lb_hmask = ~0ull;
     bool have_labels = false;
     DevBuf unres_list;  // mmp_registry_unresolved: the listed rows (its other scratch is the registry plans')
-    // The model-id table (model_ids_kernels.hpp), read and written under batch_mu only: mid_hash / mid_val / mid_mask the published
-    // table, mid_bytes / mid_off the id arena (row r = mid_bytes[mid_off[r], mid_off[r + 1]); mid_n rows, mid_nbytes bytes);
-    // mid_next_*: the table built beside the published one.  me_*: one call's keys on the device — hashes, resolved rows, dedupe
+    // The model-id table (model_ids_kernels.hpp): mid_hash / mid_val / mid_mask the published table, mid_bytes / mid_off the id arena
+    // (row r = mid_bytes[mid_off[r], mid_off[r + 1]); mid_n rows, mid_nbytes bytes); mid_next_*: the table built beside the published
+    // one.  OWNERSHIP: every writer holds batch_mu for its whole call, and builds beside the published table (the arena's append
+    // lands beyond the rows the published table lists).  The published fields (the six above without mid_next_*, and
+    // have_model_ids) change under the state lock held EXCLUSIVE, in the same hold that publishes the registry's row count
+    // (n_models); readers hold batch_mu, or — the request calls by model id on a latency slot — the state lock SHARED while they
+    // capture the fields and enqueue.  A buffer a swap retires (the old table, which becomes mid_next_*; an arena or offset array
+    // that moved) is neither rewritten nor released before quiesce_decisions has run behind the swap (model_ids_retired_drain).
+    // me_*: one call's keys on the device — hashes, resolved rows, dedupe
     // slots, the call-local table (owner | first | first_nd), the flags and their scan, model_idx, the joining events, what the
     // verify found.  (slot / slot_model and the deleted bytes are written where the pipeline reads them: j_ev.)
     DevBuf mid_hash, mid_val, mid_next_hash, mid_next_val, mid_bytes, mid_off;
     DevBuf me_hash, me_row, me_slot, me_tab, me_cnt, me_pos, me_idx, me_join, me_found;
+    // the staged path of the request calls by model id: the key bytes, their offsets, the resolved rows, and the load-target half of
+    // mmp_miss_batch_ck (its guards' half takes the scratch of mmp_gate_batch).  Owned by batch_mu, used on c->stream.
+    DevBuf kq_keys, kq_off, kq_idx, kq_preqs, kq_pouts;
     uint32_t mid_mask = 0;
     int32_t mid_n = 0, mid_nbytes = 0;
     bool have_model_ids = false;
@@ -1069,8 +1107,8 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     return MMP_OK;
 }
 
-// ---- the request seam: what the nine host-pointer request calls share (mmp_place_batch, _place_batch_c, _serve_batch, _gate_batch,
-// _miss_batch, _miss_batch_c, _route_batch, _route_batch_c, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
+// ---- the request seam: what the twelve host-pointer request calls share (mmp_place_batch, _place_batch_c, _place_batch_ck, _serve_batch,
+// _gate_batch, _miss_batch, _miss_batch_c, _miss_batch_ck, _route_batch, _route_batch_c, _route_batch_ck, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
 
 // [off, off + n) lies inside a pool of `len` entries (int64: off + n may pass INT32_MAX)
 inline bool in_pool(int32_t off, int32_t n, int32_t len) { return off >= 0 && n >= 0 && (int64_t)off + n <= len; }
@@ -1424,7 +1462,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_arena,
                       &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
                       &c->vm_ans, &c->vm_list,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->kq_keys, &c->kq_off, &c->kq_idx, &c->kq_preqs, &c->kq_pouts, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -1910,8 +1948,10 @@ int registry_grow(mmp_ctx *c, int32_t count, int32_t base, int32_t n_entries)
 }
 
 // The in-place rewrite of k registry rows staged in u_idx / u_rows, whose entries already stand in the arena (called with batch_mu):
-// afterwards the registry has `count` rows and `n_entries_after` arena entries.
-int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_after, bool bracket_open = false)
+// afterwards the registry has `count` rows and `n_entries_after` arena entries.  with_count: what else the call publishes in the hold
+// of the state lock that publishes the new row count (a by-key event batch: the model-id table that names the new rows).
+int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_after, bool bracket_open = false,
+                     const std::function<void()> &with_count = {})
 {
     hipStream_t st = c->stream;
     {
@@ -1938,6 +1978,7 @@ int registry_rewrite(mmp_ctx *c, int32_t k, int32_t count, int32_t n_entries_aft
         c->reg_pending.store(true, std::memory_order_release);
         c->n_models = count;
         c->n_entries = n_entries_after;
+        if (with_count) with_count();
     }
     const hipError_t se = hipStreamSynchronize(st);
     if (se == hipSuccess) c->reg_pending.store(false, std::memory_order_release);  // (a failed wait leaves later launches ordered behind the event)
@@ -3538,9 +3579,11 @@ UpsertJsonEvents carve(int32_t *base, int32_t n, int32_t kcap, bool scan_words =
 // From the events' slots on the device to the rewritten registry (batch_mu held, the device set, n > 0, E.k > 0): the values are
 // staged and parsed, each slot's winner picked, the winners' entries appended to the arena and the rows rewritten in place.
 // h_model: the rows of the slots on the host, for the m_cnt shadow; given empty it is read back from E.slot_model.  Nothing but
-// scratch is written before the last refusal (entry arena overflow).  The caller squeezes the arena afterwards.
+// scratch is written before the last refusal (entry arena overflow).  The caller squeezes the arena afterwards.  with_count: see
+// registry_rewrite (it has run, once, exactly when the registry's counts were published).
 int models_upsert_json_run(mmp_ctx *c, const char *fn, const char *buf, const int64_t *off, int32_t n, const UpsertJsonEvents &E,
-                           std::vector<int32_t> &h_model, int64_t *last_unload_out, int32_t *status_out)
+                           std::vector<int32_t> &h_model, int64_t *last_unload_out, int32_t *status_out,
+                           const std::function<void()> &with_count = {})
 {
     const int32_t k = E.k, count = E.count, M0 = c->n_models;
     hipStream_t st = c->stream;
@@ -3592,7 +3635,7 @@ int models_upsert_json_run(mmp_ctx *c, const char *fn, const char *buf, const in
                        A.ent_pod, A.ent_time, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
                        c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
     HIP_TRY(c, hipGetLastError());
-    if (const int rc = registry_rewrite(c, k, count, base + total, true)) return rc;
+    if (const int rc = registry_rewrite(c, k, count, base + total, true, with_count)) return rc;
     kt_add(c, parse_ms);  // the call's device span: parse + apply
     // the host shadow: a slot without a winner keeps its count (an existing row) or has none (an appended one)
     c->m_cnt.resize(count, 0);
@@ -3681,12 +3724,13 @@ struct ModelIdsPlan {
     int32_t n_before = 0, bytes_before = 0;
     uint32_t cap = 0;                // capacity of the table built in mid_next_* (0: none was needed)
     DevBuf fresh_bytes, fresh_off;   // the arena, where it had to move (or is replaced)
+    DevBuf old_bytes, old_off;       // after model_ids_publish: the arena it replaced (released with the plan)
+    bool swapped = false;            // ... and whether the publish retired anything a captured ModelIdTab may name
     std::vector<int32_t> idx;        // model_idx per event
     double ms = 0;                   // device span (profiling)
     ~ModelIdsPlan()
     {
-        fresh_bytes.release();
-        fresh_off.release();
+        for (DevBuf *b : {&fresh_bytes, &fresh_off, &old_bytes, &old_off}) b->release();
     }
 };
 
@@ -3798,7 +3842,10 @@ int model_ids_plan(mmp_ctx *c, const IdTabRef &T, const char *fn, const char *ke
     return MMP_OK;
 }
 
-// nothing fails from here on: the table, the arena and the counts change together (batch_mu held, the stream idle)
+// nothing fails from here on: the table, the arena and the counts change together (batch_mu held, the stream idle; for the
+// model-id table the state lock held exclusive as well: the ownership rule at mmp_ctx::mid_hash).  What the swap retires stays
+// allocated and unwritten: the old table is mid_next_* now, the old arena goes to the plan, which releases it when it ends —
+// for the model-id table only behind model_ids_retired_drain.
 void model_ids_publish(const IdTabRef &T, ModelIdsPlan &P)
 {
     if (P.cap) {
@@ -3807,18 +3854,25 @@ void model_ids_publish(const IdTabRef &T, ModelIdsPlan &P)
         T.mask = P.cap - 1;
     }
     if (P.fresh_bytes.p) {
-        T.bytes.release();
+        P.old_bytes = T.bytes;
         T.bytes = P.fresh_bytes;
         P.fresh_bytes = DevBuf{};
     }
     if (P.fresh_off.p) {
-        T.off.release();
+        P.old_off = T.off;
         T.off = P.fresh_off;
         P.fresh_off = DevBuf{};
     }
+    P.swapped = P.cap || P.old_bytes.p || P.old_off.p;
     T.n = P.n_before + P.n_join;
     T.nbytes = P.bytes_before + P.join_bytes;
 }
+
+// Behind a publish of the MODEL-id table, with batch_mu and without the state lock: a request call by model id that captured the
+// table before the swap may still be running on a latency slot.  It was enqueued under the state lock, so quiesce_decisions sees
+// it; once it has drained the retired table may be rewritten (by the next joining call, which finds it as mid_next_*) and the
+// retired arena released (by the plan).  Nothing to wait for when the publish swapped nothing (no id joined).
+hipError_t model_ids_retired_drain(mmp_ctx *c, const ModelIdsPlan &P) { return P.swapped ? quiesce_decisions(c) : hipSuccess; }
 
 // The registry and the id table cover the same rows: mmp_models_load, mmp_models_ingest_json and an append by index
 // (mmp_models_upsert / mmp_models_upsert_json) resize the registry without telling the id table (the rule of id_space_guard).
@@ -3856,8 +3910,12 @@ try {
             return fail(c, MMP_EINVAL, "mmp_model_ids_load: ids %d and %d are equal", i < n_models ? P.idx[i] : -1, i);
         }
     }
-    model_ids_publish(model_id_tab(c), P);
-    c->have_model_ids = true;
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);  // the swap (the ownership rule at mmp_ctx::mid_hash)
+        model_ids_publish(model_id_tab(c), P);
+        c->have_model_ids = true;
+    }
+    HIP_TRY(c, model_ids_retired_drain(c, P));  // request calls by model id that captured the replaced table
     return MMP_OK;
 } MMP_CATCH(c, "mmp_model_ids_load")
 
@@ -3909,7 +3967,9 @@ int mmp_models_events_json(mmp_ctx *c, const char *keys, const int32_t *key_off,
 try {
     if (!c || n < 0 || (flags & ~MMP_MEV_APPEND) || (n > 0 && (!key_off || !off || !model_idx_out || !status_out)))
         return fail(c, MMP_EINVAL, "mmp_models_events_json: bad argument");
-    // the locking of mmp_models_upsert_json; the id table is read and written under batch_mu only
+    // the locking of mmp_models_upsert_json.  The id table: built beside the published one under batch_mu, published under the state
+    // lock in the hold that publishes the registry's row count, what the swap retired drained before it is reused (the ownership
+    // rule at mmp_ctx::mid_hash) — a request call by model id sees this batch before or after, never an id without its row
     std::lock_guard<std::mutex> gb(c->batch_mu);
     if (!c->have_ids) return fail(c, MMP_ESTATE, "mmp_models_events_json: load the instance ids first (mmp_pod_ids_load)");
     // a key resolves to a row of the id space and the pipeline rewrites the registry row of that number: the two must be one space
@@ -3932,9 +3992,13 @@ try {
         E.count = P.n_before + P.n_join;
         HIP_TRY(c, hipMemsetAsync(E.win, 0xff, ((size_t)P.k + 1) * 4, st));
         std::vector<int32_t> h_model;
-        if (const int rc = models_upsert_json_run(c, "mmp_models_events_json", buf, off, n, E, h_model, last_unload_out, status_out)) return rc;
+        const int rc = models_upsert_json_run(c, "mmp_models_events_json", buf, off, n, E, h_model, last_unload_out, status_out,
+                                              [&] { model_ids_publish(model_id_tab(c), P); });
+        // (whether or not the rest of the run succeeded: a table that was swapped out is drained before this call lets go of it)
+        const hipError_t q = model_ids_retired_drain(c, P);
+        if (rc != MMP_OK) return rc;
+        HIP_TRY(c, q);
         kt_add(c, P.ms);  // the call's device span: resolve + parse + apply
-        model_ids_publish(model_id_tab(c), P);
     } else if (c->prof)
         c->last_kernel_ms = P.ms;
     for (int32_t i = 0; i < n; i++) {
@@ -4500,6 +4564,8 @@ try {
         c->u_stamp.assign(std::min<size_t>(c->u_stamp.size(), (size_t)M1), 0);  // (stamps name a call generation: zero = none)
         c->plan.model_map_n = std::min(c->plan.model_map_n, M1);
         if (ids) {
+            // (the id table's ownership rule, mmp_ctx::mid_hash: the drain above ran inside this exclusive hold, so no request call
+            // by model id holds the table swapped out here or the arena released here)
             std::swap(c->mid_hash, c->mid_next_hash);
             std::swap(c->mid_val, c->mid_next_val);
             c->mid_mask = cap1 - 1;
@@ -6335,6 +6401,269 @@ try {
     }
     return rc2;
 } MMP_CATCH(c, "mmp_miss_batch_c")
+
+// ---- the request calls by model id (include/mmplace.h: THE RULE BY KEY; kernel: keyed_kernels.hpp) ------------------------------
+// The key is resolved on the device inside the call: keyed_resolve_kernel is enqueued in front of the unchanged decision kernels on
+// the same stream and writes each request's row into the call's OWN copy of the request rows (its slot region, or its staged
+// scratch), so the call waits once.  On a slot the state lock is held shared over the guard, the capture of the published id table
+// and both enqueues (seam_slot), and batch_mu is never taken: the ownership rule at mmp_ctx::mid_hash is what makes that capture
+// safe.  Beyond the slot sizes the call is staged under batch_mu like every large call, on the compact rows.
+namespace {
+int keyed_check_keys(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, int32_t n, int32_t &key_bytes)
+{
+    key_bytes = 0;
+    if (n == 0) return MMP_OK;
+    if (!key_off) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
+    const int64_t bytes = (int64_t)key_off[n] - key_off[0];
+    if (bytes > INT32_MAX - kKeyedPad) return fail(c, MMP_EINVAL, "%s: more than 2^31 key bytes", fn);
+    if (bytes > 0 && !keys) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    key_bytes = (int32_t)bytes;
+    return MMP_OK;
+}
+// the state the three calls need, looked at under the lock they launch under
+int keyed_state(mmp_ctx *c, const char *fn)
+{
+    if (const int rc = need_snapshot(c, true)) return rc;
+    return model_id_space_guard(c, fn);
+}
+int keyed_empty(mmp_ctx *c, const char *fn)  // n == 0
+{
+    std::shared_lock<std::shared_mutex> g(c->mu);
+    return keyed_state(c, fn);
+}
+// The three arrays a keyed call adds to the call it resolves in front of: the key bytes, their offsets as the caller gave them,
+// and the resolved rows.  On a slot the bytes are copied as they are (the layouts leave kKeyedPad bytes behind them); staged, from
+// a copy that carries the padding.  A NULL model_idx_out gets a sink: the kernel writes the rows either way.
+struct KeyedIo {
+    std::vector<char> padded;
+    std::vector<int32_t> sink;
+    SeamIo kb, ko, ix;
+    KeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, int32_t *model_idx_out, bool on_slot,
+            const SlotRegion &keys_at, const SlotRegion &off_at, const SlotRegion &idx_at)
+    {
+        const char *first = key_bytes > 0 ? keys + key_off[0] : nullptr;
+        if (!on_slot) {
+            padded.assign((size_t)key_bytes + kKeyedPad, 0);
+            if (key_bytes > 0) memcpy(padded.data(), first, (size_t)key_bytes);
+            kb = seam_io(padded.data(), key_bytes + kKeyedPad, keys_at, c->kq_keys);
+        } else
+            kb = seam_io(first, key_bytes, keys_at, c->kq_keys);
+        ko = seam_io(key_off, n + 1, off_at, c->kq_off);
+        if (!model_idx_out) {
+            sink.resize((size_t)n);
+            model_idx_out = sink.data();
+        }
+        ix = seam_io(model_idx_out, n, idx_at, c->kq_idx);
+    }
+};
+extern "C++" template <class Row>  // the `model` field of an array of Row as the call holds it
+KeyedPatch keyed_patch_of(const SeamIo &rows)
+{
+    return KeyedPatch{rows.as<char>(), (int32_t)sizeof(Row), (int32_t)offsetof(Row, model)};
+}
+// (called with the state lock held, or by the owner of batch_mu under which no writer of the id table runs)
+int keyed_launch(mmp_ctx *c, hipStream_t st, const KeyedIo &K, int32_t n, const KeyedPatch &a, const KeyedPatch &b)
+{
+    KeyedArgs A;
+    A.keys = K.kb.as<char>();
+    A.off = K.ko.as<int32_t>();
+    A.n = n;
+    A.hmask = hash_mask(c->tune.model_id_hash_bits);
+    A.tab = model_id_tab(c).published();
+    A.model_idx = K.ix.as<int32_t>();
+    A.a = a;
+    A.b = b;
+    hipLaunchKernelGGL(keyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+constexpr KeyedPatch kNoPatch{nullptr, 0, 0};
+}  // namespace
+
+int mmp_place_batch_ck(mmp_ctx *c, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
+                       const int32_t *key_off, const int32_t *extra_pool, int32_t n_extra, int64_t now, mmp_place_out *outs,
+                       int32_t *model_idx_out)
+try {
+    const char *fn = "mmp_place_batch_ck";
+    if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++)
+        if (const int rc = check_place_req(c, fn, i, reqs[i], n_extra)) return rc;
+    int32_t key_bytes;
+    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = KeyedPlaceSlot;
+    const bool on_slot = n <= L::kN && n_extra <= L::kExtra && key_bytes <= L::kKeyBytes;
+    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, L::keys, L::key_off, L::idx);
+    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), o = seam_io(outs, n, L::outs, c->s_outs);
+    if (on_slot) {  // the rows written out in full, as mmp_place_batch_c does; a lone request takes the row path too (its model is not known at launch)
+        std::vector<mmp_place_req> full((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            full[(size_t)i] = full_place_row(*caller, reqs[i]);
+            full[(size_t)i].model = -1;
+        }
+        SeamIo q = seam_io(full.data(), n, L::reqs);
+        return seam_run<true>(c, n, true, {&q, &x, &K.kb, &K.ko}, {&o, &K.ix}, [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req>(q), kNoPatch)) return rc;
+                            return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, nullptr));
+                        });
+    }
+    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs);
+    return seam_run<true>(c, n, false, {&q, &x, &K.kb, &K.ko}, {&o, &K.ix}, [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &, auto) {
+                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req_c>(q), kNoPatch)) return rc;
+                        PlaceCall call;
+                        call.caller = caller;
+                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
+                    });
+} MMP_CATCH(c, "mmp_place_batch_ck")
+
+int mmp_route_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
+                       const char *keys, const int32_t *key_off, const mmp_serve_counter *counters, int32_t n_counters,
+                       const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit,
+                       int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_serve_out *souts, int32_t *model_idx_out)
+try {
+    const char *fn = "mmp_route_batch_ck";
+    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
+        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges, as mmp_route_batch_c checks them
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
+        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
+            return bad_range(c, fn, i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
+    }
+    int32_t key_bytes;
+    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = RouteSlot;
+    using KL = KeyedRouteSlot;
+    const bool on_slot = n <= KL::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit && key_bytes <= KL::kKeyBytes;
+    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, KL::keys, KL::key_off, KL::idx);
+    SeamIo cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
+    auto bind = [&](GateArgs &G, ServeArgs &S, const DoneFlag &done) {
+        G.excl_pod = xp.as<int32_t>();
+        G.excl_time = xt.as<int64_t>();
+        G.explicit_pool = ex.as<int32_t>();
+        G.outs = go.as<mmp_gate_out>();
+        G.done = done;
+        S.counters = cnt.as<mmp_serve_counter>();
+        S.excl_pod = G.excl_pod;
+        S.excl_time = G.excl_time;
+        S.outs = so.as<mmp_serve_out>();
+    };
+    if (on_slot) {  // the rows written out in full, as mmp_route_batch_c does; one route takes the row kernel too
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_serve_req> fs((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
+            fg[(size_t)i].model = fs[(size_t)i].model = -1;
+        }
+        SeamIo gq = seam_io(fg.data(), n, L::greqs), sq = seam_io(fs.data(), n, L::sreqs);
+        return seam_run<false>(c, n, true, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.kb, &K.ko}, {&go, &so, &K.ix}, [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            GateArgs G = gate_args(c, n, now, in_use_expiry);
+                            ServeArgs S = serve_args(c, n, now);
+                            bind(G, S, done);
+                            G.reqs = gq.as<mmp_gate_req>();
+                            S.reqs = sq.as<mmp_serve_req>();
+                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_serve_req>(sq))) return rc;
+                            HIP_TRY(c, order_after_registry(c, st));
+                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
+                            HIP_TRY(c, hipGetLastError());
+                            return MMP_OK;
+                        });
+    }
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs);
+    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.kb, &K.ko}, {&go, &so, &K.ix}, [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        GateArgs G = gate_args(c, n, now, in_use_expiry);
+                        ServeArgs S = serve_args(c, n, now);
+                        bind(G, S, done);
+                        // (the compact serve row has no model of its own: the serve half reads the gate row's)
+                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), kNoPatch)) return rc;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
+                                           seam_c_args(*caller, gq, &sq, n));
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
+} MMP_CATCH(c, "mmp_route_batch_ck")
+
+int mmp_miss_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
+                      const mmp_place_req_c *preqs, int32_t n, const char *keys, const int32_t *key_off, const int32_t *excl_pod,
+                      const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool,
+                      int32_t n_extra, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts, int32_t *model_idx_out)
+try {
+    const char *fn = "mmp_miss_batch_ck";
+    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
+        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
+        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {  // (both halves take the key's row: no "names two models" here)
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
+        if (const int rc = check_place_req(c, fn, i, preqs[i], n_extra)) return rc;
+    }
+    int32_t key_bytes;
+    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = MissSlot;
+    using KL = KeyedMissSlot;
+    const bool on_slot = n <= KL::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool && key_bytes <= KL::kKeyBytes;
+    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, KL::keys, KL::key_off, KL::idx);
+    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           po = seam_io(pouts, n, L::pouts, c->kq_pouts), go = seam_io(gouts, n, L::gouts, c->s_outs);
+    auto gate = [&](const DoneFlag &done) {
+        GateArgs G = gate_args(c, n, now, in_use_expiry);
+        G.excl_pod = xp.as<int32_t>();
+        G.excl_time = xt.as<int64_t>();
+        G.explicit_pool = ex.as<int32_t>();
+        G.outs = go.as<mmp_gate_out>();
+        G.done = done;
+        return G;
+    };
+    if (on_slot) {
+        // the rows written out in full, as mmp_miss_batch_c does: one slot, THREE launches on its stream (the keys, the guards, the
+        // load targets: the last one's completion flag covers all), one wait.  A lone request takes the row path too.
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_place_req> fp((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
+            fg[(size_t)i].model = fp[(size_t)i].model = -1;
+        }
+        SeamIo pq = seam_io(fp.data(), n, L::preqs), gq = seam_io(fg.data(), n, L::greqs);
+        return seam_run<true>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex, &K.kb, &K.ko}, {&po, &go, &K.ix}, [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            GateArgs G = gate(DoneFlag{nullptr, nullptr, 0});
+                            G.reqs = gq.as<mmp_gate_req>();
+                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_place_req>(pq))) return rc;
+                            HIP_TRY(c, order_after_registry(c, st));
+                            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
+                            HIP_TRY(c, hipGetLastError());
+                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
+                        });
+    }
+    // a large batch: both halves staged in ONE hold of batch_mu (one resolution names both halves' rows), on the compact rows
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), pq = seam_io(preqs, n, kStagedOnly, c->kq_preqs);
+    return seam_run<true>(c, n, false, {&pq, &gq, &x, &xp, &xt, &ex, &K.kb, &K.ko}, {&po, &go, &K.ix}, [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate(done);
+                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), keyed_patch_of<mmp_place_req_c>(pq))) return rc;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G,
+                                           seam_c_args(*caller, gq, nullptr, n));
+                        HIP_TRY(c, hipGetLastError());
+                        PlaceCall call;
+                        call.caller = pcaller;
+                        return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
+                    });
+} MMP_CATCH(c, "mmp_miss_batch_ck")
 
 int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
 try {

@@ -24,6 +24,16 @@
 // claimed it.  Which lane claims a slot, and under equal hashes which slot a key gets, depends on the race; no output does — all
 // are functions of the two minima, so two runs are byte-identical.
 //
+// Ownership of the MODEL-id table (the vmodel-id table, driven by the same kernels, is read and written under batch_mu alone).
+// Writers hold batch_mu for the call and build beside the published table: the next table in mid_next_*, the arena where it has to
+// move, and an append in place only beyond the rows the published table lists — a captured ModelIdTab cannot reach rows it does
+// not list.  The swap happens under the state lock held exclusive, in the hold that publishes the registry's new row count.  Readers
+// hold batch_mu (mmp_model_ids_resolve / _get, the registry calls that resolve), or the state lock SHARED: the request calls by
+// model id (keyed_kernels.hpp) capture the published ModelIdTab there and enqueue on a latency slot's stream, without batch_mu.  So
+// whatever a swap retires — the old table, which the NEXT joining call rewrites as mid_next_*; an arena or offset array that moved
+// — is neither rewritten nor released until quiesce_decisions has run behind the swap (mmplace.hip: model_ids_retired_drain;
+// mmp_models_retire drains in front of its swap, inside the exclusive hold).
+//
 // Model ids are tens of bytes (as resolve_keys_kernel assumes for instance ids): a key is a loop of its lane.  With the hash masked
 // probes run as long as the table is full and lanes of a wavefront diverge for that long; that mode is a diagnostic.
 #pragma once

@@ -1089,6 +1089,83 @@ class Solver:
                                            ptr(gouts) if n else None, ptr(pouts) if n else None))
         return gouts, pouts
 
+    # ---- the single-caller forms by model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck) ----
+    @staticmethod
+    def pack_keys(keys):
+        """keys (a list of bytes / str, str as UTF-8) as the by-key calls take them, packed as model_ids_resolve packs them:
+        (the bytes joined, n + 1 int32 offsets)."""
+        blob, off = Solver._pack(keys)
+        return blob, off.astype(np.int32)
+
+    def place_batch_ck(self, caller, reqs_c, keys, extra_pool, now, want_idx=True):
+        """mmp_place_batch_c with request i's model named by keys[i]: -> (outs, model_idx); the `model` field of reqs_c is
+        ignored.  want_idx=False passes a NULL model_idx_out and returns None for it."""
+        from ._lib import PLACE_CALLER, PLACE_REQ_C
+        caller = np.ascontiguousarray(caller, dtype=PLACE_CALLER).reshape(1)
+        reqs_c = np.ascontiguousarray(reqs_c, dtype=PLACE_REQ_C)
+        extra = np.zeros(0, np.int32) if extra_pool is None else np.ascontiguousarray(extra_pool, dtype=np.int32)
+        n = len(reqs_c)
+        assert len(keys) == n
+        blob, off = self.pack_keys(keys)
+        outs = np.zeros(n, dtype=PLACE_OUT)
+        idx = np.full(max(n, 1), -2, np.int32)
+        self._ck(self.lib.mmp_place_batch_ck(self.h, ptr(caller), ptr(reqs_c) if n else None, n, blob, ptr(off),
+                                             ptr(extra) if len(extra) else None, len(extra), C.c_int64(int(now)),
+                                             ptr(outs) if n else None, ptr(idx) if want_idx else None))
+        return outs, (idx[:n] if want_idx else None)
+
+    def route_batch_ck(self, caller, gate_reqs_c, serve_reqs_c, keys, counters, excl_pod, excl_time, explicit_pool, now,
+                       in_use_failure_expiry_ms=450_000, want_idx=True):
+        """mmp_route_batch_c with request i's model named by keys[i]: -> (gate outs, serve outs, model_idx)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
+        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        assert len(keys) == n and len(serve_reqs_c) == n
+        blob, off = self.pack_keys(keys)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        souts = np.zeros(n, dtype=SERVE_OUT)
+        idx = np.full(max(n, 1), -2, np.int32)
+        self._ck(self.lib.mmp_route_batch_ck(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
+                                             blob, ptr(off), ptr(counters) if len(counters) else None, len(counters),
+                                             ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                             len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                             C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                             ptr(gouts) if n else None, ptr(souts) if n else None, ptr(idx) if want_idx else None))
+        return gouts, souts, (idx[:n] if want_idx else None)
+
+    def miss_batch_ck(self, caller, place_caller, gate_reqs_c, place_reqs_c, keys, excl_pod, excl_time, explicit_pool, extra_pool, now,
+                      in_use_failure_expiry_ms=450_000, want_idx=True):
+        """mmp_miss_batch_c with request i's model named by keys[i]: -> (gate outs, place outs, model_idx)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_REQ_C, SEAM_CALLER
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        assert len(keys) == n and len(place_reqs_c) == n
+        blob, off = self.pack_keys(keys)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        pouts = np.zeros(n, dtype=PLACE_OUT)
+        idx = np.full(max(n, 1), -2, np.int32)
+        self._ck(self.lib.mmp_miss_batch_ck(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
+                                            ptr(place_reqs_c) if n else None, n, blob, ptr(off),
+                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                            ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
+                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                            ptr(gouts) if n else None, ptr(pouts) if n else None, ptr(idx) if want_idx else None))
+        return gouts, pouts, (idx[:n] if want_idx else None)
+
     def proactive_plan(self, default_model_size_units: int, now: int, max_out: int, partition: int = -1, skip_models=None):
         """a17: (models, last_used, info) the leader would proactively load, MRU first; partition >= 0: for that
         ProhibitedTypeSet partition only (one reaper call per partition when type constraints exist)."""
