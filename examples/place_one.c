@@ -78,8 +78,30 @@ int main(void)
         return 1;
     }
     printf("by id: row=%d chosen=%d best=%d candidates=%d\n", row, keyed.chosen, keyed.best, keyed.n_candidates);
+    /* And with the request naming a VMODEL: the vmodel listener's one event makes "my-vmodel" point at "my-model"; a request brings
+     * the vmodel id's bytes, resolveVModelId runs on the device inside the call (mmp_place_batch_cv), and the host reads the class
+     * of the answer before it believes the decision. */
+    const char vids[] = "my-vmodel";
+    const int32_t vid_off[2] = {0, (int32_t)sizeof vids - 1};
+    const char record[] = "{\"amid\":\"my-model\",\"tmid\":\"my-model\"}";
+    const int64_t rec_off[2] = {0, (int64_t)sizeof record - 1};
+    int32_t vrow = -2, vstatus = -2;
+    mmp_place_out by_vmodel;
+    mmp_vseam_row vm;
+    if ((rc = mmp_vmodels_events_json(ctx, vids, vid_off, record, rec_off, 1, NULL, MMP_VMEV_APPEND, &vrow, &vstatus, NULL)) ||
+        (rc = mmp_place_batch_cv(ctx, &caller, &rc_row, 1, vids, vid_off, NULL, NULL, NULL, NULL, 0, now, &by_vmodel, &vm))) {
+        fprintf(stderr, "libmmplace: %d (%s)\n", rc, mmp_last_error(ctx));
+        mmp_destroy(ctx);
+        return 1;
+    }
+    printf("by vmodel id: class=%d vmodel=%d model=%d chosen=%d best=%d candidates=%d\n", vm.cls, vm.vmodel, vm.model, by_vmodel.chosen,
+           by_vmodel.best, by_vmodel.n_candidates);
     mmp_destroy(ctx);
-    /* pod 0 holds the model, so the most desirable eligible pod is pod 1; the id names row 0 and decides the same */
+    /* pod 0 holds the model, so the most desirable eligible pod is pod 1; the id names row 0 and decides the same, and so does the
+     * vmodel whose active model it is */
     if (row != 0 || memcmp(&keyed, &out, sizeof out) != 0) return 3;
+    if (vm.cls != MMP_VMR_OK || vm.which != MMP_VMW_ACTIVE || vm.vmodel != 0 || vm.model != 0 || vm.flags != 0 ||
+        memcmp(&by_vmodel, &out, sizeof out) != 0)
+        return 4;
     return out.best == 1 ? 0 : 2;
 }

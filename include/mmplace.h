@@ -1564,9 +1564,11 @@ int mmp_models_register_json(mmp_ctx *ctx, const mmp_register_req *reqs, int32_t
  * MMP_EINVAL with nothing changed (table, id arena, rows, string arena): a NULL required buffer, non-monotone offsets of either
  * kind, unknown flags, a value of 2^30 bytes or more, more than 2^31 arena bytes.  The call needs neither mmp_model_ids_load nor
  * mmp_pod_ids_load: the hashes of amid / tmid are computed from the bytes.  Locking: batch_mu for the call, which every
- * reader of the vmodel state holds too; the id table, and the id arena, string arena and row array where they have to grow, are
- * built beside the published ones and swapped together with the counts under the state lock; rows of known ids are rewritten
- * behind the last refusal.  n == 0 is valid. */
+ * reader of the vmodel state holds too except the request calls by vmodel id on a latency slot (mmp_*_batch_cv), which capture
+ * the published table under the state lock.  So the id table, the id arena and string arena where they have to grow, and the row
+ * array whenever a row of a known id is rewritten or it has to grow, are built beside the published ones and swapped together
+ * with the counts under the state lock, and what the swap retired is neither reused nor released before the latency slots have
+ * drained behind it.  n == 0 is valid. */
 #define MMP_VMEV_APPEND 1u
 int mmp_vmodels_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_off, const char *buf, const int64_t *off, int32_t n,
                             const uint8_t *deleted, uint32_t flags, int32_t *vmodel_idx_out, int32_t *status_out,
@@ -1623,6 +1625,55 @@ typedef struct {
 } mmp_vmodel_answer; /* 32 bytes */
 int mmp_vmodels_resolve(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, const char *nf_keys, const int32_t *nf_off,
                         const char *owners, const int32_t *owner_off, const uint32_t *req_flags, mmp_vmodel_answer *rows_out);
+/* The single-caller request forms BY VMODEL ID: ModelMeshApi.callModel (:452-476) for a request that names a vmodel — first
+ * resolveVModelId(vModelId, notFoundModelId), then invokeModel's seams on the model id it returned.  With mmp_vmodels_resolve (a
+ * staged call under the batch lock, which answers a registry ROW) in front of a _c call that is two calls and one batch lock on the
+ * request path.  These are the _ck forms (mmp_place_batch_ck ...) with the resolution of the VMODEL id inside the call: one latency
+ * slot, one stream, one wait, no batch lock (csrc/vkeyed_kernels.hpp).  Against the _ck signatures:
+ *   keys / key_off     key i is the VMODEL id of request i
+ *   nf_keys / nf_off   behind them: the notFoundModelId spans under the conventions of mmp_vmodels_resolve — both may be NULL, an
+ *                      empty span is Java null
+ *   req_flags          n words, may be NULL; the only bit is MMP_VMRQ_AFTER_STRONG.  There are no owners: resolveVModelId on the
+ *                      request path takes none
+ *   vm_out             n rows in place of model_idx_out, may be NULL; `reserved` is written 0.  cls is MMP_VMR_*, which MMP_VMW_*,
+ *                      flags MMP_VMRF_NULL_ID
+ *
+ * THE RULE BY VMODEL KEY: vm_out[i] equals, field by field, what mmp_vmodels_resolve answers for (key i, nf i, no owner, flags i)
+ * against the vmodel table, the model-id table and the registry row count as published at the moment the call captured them.
+ * Request i is decided exactly as the _c call decides the same rows with model = r, where r = vm_out[i].model when cls ==
+ * MMP_VMR_OK and MMP_VMRF_NULL_ID is clear, and r = -1 otherwise: NOT_FOUND, HOST, STRONG_READ, TARGET_NOT_FOUND, a null id, or an
+ * id the model-id table does not know.  The result rows are those rows' results byte for byte.  The caller's arrays are never
+ * written, and the `model` fields of the request rows are ignored on input.  The host reads cls before it believes a decision; on
+ * MMP_VMR_STRONG_READ it does what mmp_vmodels_resolve asks for (getStrong, the value through mmp_vmodels_events_json, the call
+ * again with MMP_VMRQ_AFTER_STRONG).  A vmodel event batch, mmp_vmodels_retire (which renumbers vmodel rows) and the registry's
+ * event batches and retirements are each seen before or after, never as a mix.
+ *
+ * MMP_EINVAL, every output untouched: everything the _ck forms refuse; nf_off that is not monotone; NULL nf_keys with nf bytes
+ * present; unknown request flag bits.  MMP_ESTATE as the _ck forms.  A context that never had a vmodel call has an empty vmodel
+ * table: a valid call, every request answers MMP_VMR_NOT_FOUND.  n = 0 is a valid call.  Up to 256 requests with up to 8192 key
+ * bytes and up to 8192 nf bytes (and the pools of the _ck forms' latency path) ride a latency slot; larger calls are staged under
+ * the batch lock on the compact rows, as the _ck forms are. */
+typedef struct {
+    int32_t cls, which;
+    int32_t vmodel, model;
+    uint32_t flags;
+    int32_t reserved;
+} mmp_vseam_row; /* 24 bytes */
+int mmp_place_batch_cv(mmp_ctx *ctx, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
+                       const int32_t *key_off, const char *nf_keys, const int32_t *nf_off, const uint32_t *req_flags,
+                       const int32_t *extra_pool, int32_t n_extra, int64_t now_ms, mmp_place_out *outs, mmp_vseam_row *vm_out);
+int mmp_route_batch_cv(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_gate_req_c *gate_reqs,
+                       const mmp_serve_req_c *serve_reqs, int32_t n, const char *keys, const int32_t *key_off, const char *nf_keys,
+                       const int32_t *nf_off, const uint32_t *req_flags, const mmp_serve_counter *counters, int32_t n_counters,
+                       const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool,
+                       int32_t n_explicit, int64_t now_ms, int64_t in_use_expiry_ms, mmp_gate_out *gate_outs,
+                       mmp_serve_out *serve_outs, mmp_vseam_row *vm_out);
+int mmp_miss_batch_cv(mmp_ctx *ctx, const mmp_seam_caller *caller, const mmp_place_caller *place_caller,
+                      const mmp_gate_req_c *gate_reqs, const mmp_place_req_c *place_reqs, int32_t n, const char *keys,
+                      const int32_t *key_off, const char *nf_keys, const int32_t *nf_off, const uint32_t *req_flags,
+                      const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool,
+                      int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now_ms, int64_t in_use_expiry_ms,
+                      mmp_gate_out *gate_outs, mmp_place_out *place_outs, mmp_vseam_row *vm_out);
 /* The leader's transition pass: processVModels (:617-634), the filter of processVModel (:639-643) and the prologue of
  * PendingTransition.run (:701-708) as one scan over all rows in row order.  Listed: every row that is not ABSENT, not HOST and
  * in transition.  Per listed row: vmodel; from_model / to_model = the registry rows of amid / tmid, -1 for null or unknown;
@@ -1692,10 +1743,11 @@ int mmp_vmodels_info(mmp_ctx *ctx, mmp_vmodels_stats *out);
  * MMP_VMRETIRE_ALL_ABSENT: the device chooses — every row flagged MMP_VMF_ABSENT at the call is retired; n must be 0 (a list
  * beside the flag is MMP_EINVAL).  The form for a host that keeps no id map.  MMP_VMRETIRE_ABSENT_ONLY beside it is accepted and
  * adds nothing.
- * Readers: no decision kernel reads vmodel state, and every reader of it (mmp_vmodels_resolve, _transitions, _get, _info) holds
- * batch_mu, which this call holds throughout — a reader sees the table before the retire or after it; no decision is drained and
- * no resolved view rebuilt.  The new rows, arenas and table are built beside the published ones and swapped together with the
- * counts under the state lock, as mmp_vmodels_events_json swaps what it grew; everything that can fail — allocation, a HIP error,
+ * Readers: no decision kernel reads vmodel state; mmp_vmodels_resolve, _transitions, _get and _info hold batch_mu, which this
+ * call holds throughout, and the request calls by vmodel id (mmp_*_batch_cv) capture the table under the state lock — either kind
+ * sees the numbering before the retire or after it, never a mix; no resolved view is rebuilt.  The new rows, arenas and table are
+ * built beside the published ones and swapped together with the counts under the state lock, as mmp_vmodels_events_json swaps
+ * what it built, and the latency slots are drained behind the swap before what it retired is released; everything that can fail — allocation, a HIP error,
  * an id the verifying lookup does not find (MMP_EHIP) — fails before the swap, with nothing published.  Row numbers the HOST holds
  * — answers of mmp_vmodels_resolve and _transitions — are the host's to renumber from remap_out.
  * MMP_EINVAL with nothing changed and every output untouched: NULL rows with n > 0, a row outside [0, V0), an unknown flag bit,

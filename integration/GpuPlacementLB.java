@@ -115,6 +115,26 @@ final class MmPlace {
                                      ByteBuffer keys, ByteBuffer keyOff, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl,
                                      ByteBuffer explicitPool, int nExplicit, ByteBuffer extraPool, int nExtra, long nowMs,
                                      long inUseFailureExpiryMs, ByteBuffer gateOuts, ByteBuffer placeOuts, ByteBuffer modelIdxOut);
+    /** the single-caller forms BY VMODEL ID (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv): keys name VMODELS, and
+     *  resolveVModelId (VModelManager.java:569-597) runs on the device inside the call — no vmodelsResolve (a staged call under the
+     *  batch lock) in front.  nfKeys / nfOff (both may be null): the notFoundModelId spans, an empty span is null; reqFlags (n ints,
+     *  may be null): 1 = the question is asked again after vModels.getStrong.  vmOut (n rows of 24 bytes, may be null): int cls (0 not
+     *  found / 1 ok / 2 strong read wanted / 3 target not found / 4 the host decides), int which (0 active / 1 target), int vmodel,
+     *  int model, int flags (1 = the answered id is null), int reserved.  The decision is the one for vmOut.model when cls is 1 and
+     *  flags is 0, and the one for "no such model" otherwise: READ cls BEFORE BELIEVING THE DECISION (VModelCall below). */
+    static native int placeBatchVKeyed(long h, ByteBuffer caller, ByteBuffer reqs, int n, ByteBuffer keys, ByteBuffer keyOff,
+                                       ByteBuffer nfKeys, ByteBuffer nfOff, ByteBuffer reqFlags, ByteBuffer extraPool, int nExtra,
+                                       long nowMs, ByteBuffer outs, ByteBuffer vmOut);
+    static native int routeBatchVKeyed(long h, ByteBuffer caller, ByteBuffer gateReqs, ByteBuffer serveReqs, int n, ByteBuffer keys,
+                                       ByteBuffer keyOff, ByteBuffer nfKeys, ByteBuffer nfOff, ByteBuffer reqFlags, ByteBuffer counters,
+                                       int nCounters, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool,
+                                       int nExplicit, long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts, ByteBuffer serveOuts,
+                                       ByteBuffer vmOut);
+    static native int missBatchVKeyed(long h, ByteBuffer caller, ByteBuffer placeCaller, ByteBuffer gateReqs, ByteBuffer placeReqs, int n,
+                                      ByteBuffer keys, ByteBuffer keyOff, ByteBuffer nfKeys, ByteBuffer nfOff, ByteBuffer reqFlags,
+                                      ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, ByteBuffer explicitPool, int nExplicit,
+                                      ByteBuffer extraPool, int nExtra, long nowMs, long inUseFailureExpiryMs, ByteBuffer gateOuts,
+                                      ByteBuffer placeOuts, ByteBuffer vmOut);
     static native int proactivePlan(long h, int defaultModelSizeUnits, long nowMs, int maxOut, ByteBuffer outModel,
                                     ByteBuffer outLastUsed, ByteBuffer info);
     static native int proactivePlanSubset(long h, int partition, ByteBuffer skipModels, int nSkip, int defaultModelSizeUnits,
@@ -351,6 +371,75 @@ final class ModelKey {
         b[1].putInt(0, 0);
         b[1].putInt(4, utf8.length);
         return b;
+    }
+}
+
+/**
+ * ModelMeshApi.callModel (:452-476) for a request that names a VMODEL, on a binding whose vmodel table is resident on the device
+ * (vmodelsEventsJson): resolveVModelId and the route seam of invokeModel are ONE call on a latency slot (routeBatchVKeyed) instead of
+ * vmodelsResolve — which takes the library's batch lock — followed by routeBatchCaller on the row it answered.
+ *
+ *   first attempt      nf = null: the active model is answered (cls 1, which 0)
+ *   MODEL_NOT_FOUND    the invocation came back with "model not found" for that id: the second attempt passes it as nf (:466-470).
+ *                      cls 2 (the stored active id IS nf): vModels.getStrong(vModelId) (:582), its value through vmodelsEventsJson
+ *                      — so that the device holds what the strong read saw — and the call again with reqFlags = 1; then cls 1 with
+ *                      which = 1 (the target) or cls 3 (:594, INTERNAL "Target model ... not found")
+ *   cls 0 / 4          NOT_FOUND to the client (:570-573) / a record with an escaped string: the host resolves it from the KV value
+ * The gate and serve rows are the caller's to fill, as for routeBatchKeyed; only the answer's class is interpreted here.
+ */
+final class VModelCall {
+    static final int NOT_FOUND = 0, OK = 1, STRONG_READ = 2, TARGET_NOT_FOUND = 3, HOST = 4;
+    static final int AFTER_STRONG = 1, NULL_ID = 1;
+
+    /** what the strong read needs from the enclosing instance: vModels.getStrong(id) as the raw stored bytes, null for absent */
+    interface StrongReader { byte[] getStrong(String vModelId) throws Exception; }
+
+    private static final ThreadLocal<ByteBuffer> VM_OUT = ThreadLocal.withInitial(() -> MmPlace.direct(24));
+    private static final ThreadLocal<ByteBuffer> FLAGS = ThreadLocal.withInitial(() -> MmPlace.direct(4));
+    private static final ThreadLocal<ByteBuffer[]> NF = ThreadLocal.withInitial(() -> new ByteBuffer[] { MmPlace.direct(256), MmPlace.direct(8) });
+    private static final ThreadLocal<ByteBuffer> ONE_OFF = ThreadLocal.withInitial(() -> MmPlace.direct(32));
+
+    private static ByteBuffer[] span(ThreadLocal<ByteBuffer[]> tl, byte[] utf8) {
+        ByteBuffer[] b = tl.get();
+        if (b[0].capacity() < utf8.length) b[0] = MmPlace.direct(Math.max(utf8.length, 2 * b[0].capacity()));
+        b[0].clear();
+        b[0].put(utf8);
+        b[1].putInt(0, 0);
+        b[1].putInt(4, utf8.length);
+        return b;
+    }
+
+    /**
+     * One route of a vmodel request: { cls, which, vmodel row, model row, flags } of the answer the decision in gateOut / serveOut
+     * belongs to.  notFoundModelId == null: the first attempt.  The caller invokes on serveOut only when cls is OK and flags is 0.
+     */
+    static int[] route(GpuMeshBinding mesh, StrongReader kv, String vModelId, String notFoundModelId, ByteBuffer caller, ByteBuffer gate,
+                       ByteBuffer serve, ByteBuffer counters, int nCounters, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl, long nowMs,
+                       ByteBuffer gateOut, ByteBuffer serveOut) throws Exception {
+        final ByteBuffer[] key = ModelKey.of(vModelId);
+        final ByteBuffer[] nf = notFoundModelId == null ? null
+                : span(NF, notFoundModelId.getBytes(java.nio.charset.StandardCharsets.UTF_8));
+        final ByteBuffer vm = VM_OUT.get(), flags = FLAGS.get();
+        flags.putInt(0, 0);
+        for (int attempt = 0; ; attempt++) {
+            MmPlace.routeBatchVKeyed(mesh.handle(), caller, gate, serve, 1, key[0], key[1], nf != null ? nf[0] : null,
+                                     nf != null ? nf[1] : null, flags, counters, nCounters, exclPod, exclTime, nExcl, null, 0, nowMs,
+                                     ModelMesh.IN_USE_LOAD_FAILURE_EXPIRY_MS, gateOut, serveOut, vm);
+            final int cls = vm.getInt(0);
+            if (cls != STRONG_READ || attempt > 0) break;       // (after the strong read the device never answers STRONG_READ)
+            // :582 — the strong read, and its value to the device before the question is asked again
+            final byte[] fresh = kv.getStrong(vModelId);
+            final byte[] value = fresh != null ? fresh : new byte[0];
+            final ByteBuffer json = MmPlace.direct(Math.max(value.length, 1));
+            json.put(value);
+            final ByteBuffer off = ONE_OFF.get();
+            off.putLong(0, 0L); off.putLong(8, value.length);
+            final ByteBuffer deleted = MmPlace.slice(off, 16, 1), idx = MmPlace.slice(off, 20, 4), status = MmPlace.slice(off, 24, 4);
+            deleted.put(0, (byte) (fresh == null ? 1 : 0));
+            MmPlace.vmodelsEventsJson(mesh.handle(), key[0], key[1], json, MmPlace.slice(off, 0, 16), 1, deleted, 1, idx, status, null);
+            flags.putInt(0, AFTER_STRONG);
+        }
+        return new int[] { vm.getInt(0), vm.getInt(4), vm.getInt(8), vm.getInt(12), vm.getInt(16) };
     }
 }
 

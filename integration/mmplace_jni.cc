@@ -430,6 +430,90 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_missBatchKeyed(JNIE
                                    inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_place_out>(env, placeOuts),
                                    buf<int32_t>(env, modelIdxOut)));
 }
+// ---- the single-caller forms BY VMODEL ID: keys name VMODELS, nfKeys / nfOff (both may be null) the notFoundModelId spans, reqFlags
+// (n ints, may be null) MMP_VMRQ_AFTER_STRONG; resolveVModelId runs on the device inside the call and vmOut (n mmp_vseam_row, may be
+// null) says what it answered (include/mmplace.h: THE RULE BY VMODEL KEY)
+static bool holds_vkeys(JNIEnv *env, const char *who, jobject keys, jobject keyOff, jobject nfKeys, jobject nfOff, jobject reqFlags, jint n,
+                        jobject vmOut)
+{
+    if (!holds_keys(env, who, keys, keyOff, n, nullptr)) return false;
+    if (n == 0) return true;
+    if (nfOff && (!holds<int32_t>(env, nfOff, (jlong)n + 1, who) || !holds<char>(env, nfKeys, (jlong)buf<int32_t>(env, nfOff)[n], who)))
+        return false;
+    if (reqFlags && !holds<uint32_t>(env, reqFlags, n, who)) return false;
+    return !vmOut || holds<mmp_vseam_row>(env, vmOut, n, who);
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_placeBatchVKeyed(JNIEnv *env, jclass, jlong h, jobject caller, jobject reqs,
+                                                                              jint n, jobject keys, jobject keyOff, jobject nfKeys,
+                                                                              jobject nfOff, jobject reqFlags, jobject extraPool,
+                                                                              jint nExtra, jlong nowMs, jobject outs, jobject vmOut)
+{
+    if (!holds_vkeys(env, "placeBatchVKeyed: keyOff / keys / nfOff / nfKeys / reqFlags / vmOut shorter than the call's n", keys, keyOff, nfKeys,
+                     nfOff, reqFlags, n, vmOut) ||
+        !holds<mmp_place_caller>(env, caller, 1, "placeBatchVKeyed: caller shorter than one mmp_place_caller") ||
+        !holds<mmp_place_req_c>(env, reqs, n, "placeBatchVKeyed: reqs shorter than n requests") ||
+        !holds<int32_t>(env, extraPool, nExtra, "placeBatchVKeyed: extraPool shorter than nExtra entries") ||
+        !holds<mmp_place_out>(env, outs, n, "placeBatchVKeyed: outs shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_place_batch_cv(ctx_of(h), buf<mmp_place_caller>(env, caller), buf<mmp_place_req_c>(env, reqs), n, buf<char>(env, keys),
+                                    buf<int32_t>(env, keyOff), buf<char>(env, nfKeys), buf<int32_t>(env, nfOff), buf<uint32_t>(env, reqFlags),
+                                    buf<int32_t>(env, extraPool), nExtra, nowMs, buf<mmp_place_out>(env, outs),
+                                    buf<mmp_vseam_row>(env, vmOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_routeBatchVKeyed(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                              jobject gateReqs, jobject serveReqs, jint n, jobject keys,
+                                                                              jobject keyOff, jobject nfKeys, jobject nfOff,
+                                                                              jobject reqFlags, jobject counters, jint nCounters,
+                                                                              jobject exclPod, jobject exclTime, jint nExcl,
+                                                                              jobject explicitPool, jint nExplicit, jlong nowMs,
+                                                                              jlong inUseFailureExpiryMs, jobject gateOuts,
+                                                                              jobject serveOuts, jobject vmOut)
+{
+    if (!holds_vkeys(env, "routeBatchVKeyed: keyOff / keys / nfOff / nfKeys / reqFlags / vmOut shorter than the call's n", keys, keyOff, nfKeys,
+                     nfOff, reqFlags, n, vmOut) ||
+        !holds<mmp_seam_caller>(env, caller, 1, "routeBatchVKeyed: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "routeBatchVKeyed: gateReqs shorter than n requests") ||
+        !holds<mmp_serve_req_c>(env, serveReqs, n, "routeBatchVKeyed: serveReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "routeBatchVKeyed: gateOuts shorter than n results") ||
+        !holds<mmp_serve_out>(env, serveOuts, n, "routeBatchVKeyed: serveOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_route_batch_cv(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_gate_req_c>(env, gateReqs),
+                                    buf<mmp_serve_req_c>(env, serveReqs), n, buf<char>(env, keys), buf<int32_t>(env, keyOff),
+                                    buf<char>(env, nfKeys), buf<int32_t>(env, nfOff), buf<uint32_t>(env, reqFlags),
+                                    buf<mmp_serve_counter>(env, counters), nCounters, buf<int32_t>(env, exclPod),
+                                    buf<int64_t>(env, exclTime), nExcl, buf<int32_t>(env, explicitPool), nExplicit, nowMs,
+                                    inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_serve_out>(env, serveOuts),
+                                    buf<mmp_vseam_row>(env, vmOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_missBatchVKeyed(JNIEnv *env, jclass, jlong h, jobject caller,
+                                                                             jobject placeCaller, jobject gateReqs, jobject placeReqs,
+                                                                             jint n, jobject keys, jobject keyOff, jobject nfKeys,
+                                                                             jobject nfOff, jobject reqFlags, jobject exclPod,
+                                                                             jobject exclTime, jint nExcl, jobject explicitPool,
+                                                                             jint nExplicit, jobject extraPool, jint nExtra, jlong nowMs,
+                                                                             jlong inUseFailureExpiryMs, jobject gateOuts, jobject placeOuts,
+                                                                             jobject vmOut)
+{
+    if (!holds_vkeys(env, "missBatchVKeyed: keyOff / keys / nfOff / nfKeys / reqFlags / vmOut shorter than the call's n", keys, keyOff, nfKeys,
+                     nfOff, reqFlags, n, vmOut) ||
+        !holds<mmp_seam_caller>(env, caller, 1, "missBatchVKeyed: caller shorter than one mmp_seam_caller") ||
+        !holds<mmp_place_caller>(env, placeCaller, 1, "missBatchVKeyed: placeCaller shorter than one mmp_place_caller") ||
+        !holds<mmp_gate_req_c>(env, gateReqs, n, "missBatchVKeyed: gateReqs shorter than n requests") ||
+        !holds<mmp_place_req_c>(env, placeReqs, n, "missBatchVKeyed: placeReqs shorter than n requests") ||
+        !holds<mmp_gate_out>(env, gateOuts, n, "missBatchVKeyed: gateOuts shorter than n results") ||
+        !holds<mmp_place_out>(env, placeOuts, n, "missBatchVKeyed: placeOuts shorter than n results"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_miss_batch_cv(ctx_of(h), buf<mmp_seam_caller>(env, caller), buf<mmp_place_caller>(env, placeCaller),
+                                   buf<mmp_gate_req_c>(env, gateReqs), buf<mmp_place_req_c>(env, placeReqs), n, buf<char>(env, keys),
+                                   buf<int32_t>(env, keyOff), buf<char>(env, nfKeys), buf<int32_t>(env, nfOff),
+                                   buf<uint32_t>(env, reqFlags), buf<int32_t>(env, exclPod), buf<int64_t>(env, exclTime), nExcl,
+                                   buf<int32_t>(env, explicitPool), nExplicit, buf<int32_t>(env, extraPool), nExtra, nowMs,
+                                   inUseFailureExpiryMs, buf<mmp_gate_out>(env, gateOuts), buf<mmp_place_out>(env, placeOuts),
+                                   buf<mmp_vseam_row>(env, vmOut)));
+}
 
 // ---- rebalancers (MM.java:5636-5871, 6110-6335, 6616-6747, 6959-7147) ---------------------------------
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_proactivePlan(JNIEnv *env, jclass, jlong h,

@@ -229,6 +229,9 @@ VMODEL_TRANSITIONS_INFO = np.dtype([("n_listed", "<i4"), ("n_promote", "<i4"), (
 VMODELS_STATS = np.dtype([("n_rows", "<i4"), ("n_live", "<i4"), ("arena_bytes", "<i8"), ("live_bytes", "<i8"), ("capacity", "<i4"),
                           ("reserved", "<i4")])
 assert VMODEL_ANSWER.itemsize == 32 and VMODEL_TRANSITION.itemsize == 32 and VMODEL_TRANSITIONS_INFO.itemsize == 24
+# mmp_vseam_row: what the request calls by vmodel id answer per request (the shared fields of VMODEL_ANSWER)
+VSEAM_ROW = np.dtype([("cls", "<i4"), ("which", "<i4"), ("vmodel", "<i4"), ("model", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert VSEAM_ROW.itemsize == 24
 assert VMODELS_STATS.itemsize == 32
 # mmp_vmodels_retire: every named row must be ABSENT / the device retires every ABSENT row (no list)
 VMRETIRE_ABSENT_ONLY = 1
@@ -387,6 +390,12 @@ SYMBOLS = [
                                            _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     ("mmp_vmodels_events_json", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_vmodels_resolve", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    # the request calls by vmodel id: the _ck signatures with nf_keys / nf_off / req_flags behind key_off, vm_out last
+    ("mmp_place_batch_cv", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P]),
+    ("mmp_route_batch_cv", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32,
+                                     C.c_int64, C.c_int64, _P, _P, _P]),
+    ("mmp_miss_batch_cv", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32,
+                                    C.c_int64, C.c_int64, _P, _P, _P]),
     ("mmp_vmodels_transitions", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.POINTER(C.c_int32), _P]),
     ("mmp_vmodels_get", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
                                   C.POINTER(C.c_int32)]),

@@ -51,6 +51,7 @@
 #include "register_kernels.hpp"
 #include "refs_kernels.hpp"
 #include "vmodel_kernels.hpp"
+#include "vkeyed_kernels.hpp"
 #include "vmodel_retire_kernels.hpp"
 #include "vmodel_write_kernels.hpp"
 #include "shard_kernels.hpp"
@@ -270,6 +271,41 @@ struct KeyedRouteSlot {
                                 idx = slot_after(L::souts, kN, 4);
     static_assert(kN <= L::kN && slot_fits({L::greqs, L::sreqs, L::counters, keys, key_off, L::excl_pod, L::explicit_pool, L::excl_time, L::gouts, L::souts, idx}),
                   "keyed route slot layout");
+};
+// The request calls by VMODEL id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv; vkeyed_kernels.hpp): again the layout of the
+// call they resolve in front of; behind its requests the vmodel key bytes, the n + 1 key offsets, the notFoundModelId bytes (each
+// byte region with kKeyedPad readable bytes behind it), their n + 1 offsets and the n flag words; behind its results the n
+// mmp_vseam_row.  kKeyBytes / kNfBytes: what a call may bring onto a slot of each — what vkeyed_resolve_kernel stages in LDS of each.
+constexpr int kVKeyedKeyBytes = kVKeyedLdsBytes, kVKeyedNfBytes = kVKeyedLdsBytes;
+static_assert(sizeof(mmp_vseam_row) == 24, "mmp_vseam_row is 24 bytes");
+struct VKeyedPlaceSlot {
+    static constexpr int kN = kKeyedN, kExtra = MissSlot::kPool, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), keys = slot_after(reqs, kKeyBytes + kKeyedPad, 1),
+                                key_off = slot_after(keys, kN + 1, 4), nf = slot_after(key_off, kNfBytes + kKeyedPad, 1),
+                                nf_off = slot_after(nf, kN + 1, 4), flags = slot_after(nf_off, kN, 4),
+                                extra = slot_first(kSlotPool, kExtra, 4), outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out)),
+                                vm = slot_after(outs, kN, sizeof(mmp_vseam_row));
+    static_assert(slot_fits({reqs, keys, key_off, nf, nf_off, flags, extra, outs, vm}), "vmodel-keyed place slot layout");
+};
+struct VKeyedMissSlot {
+    using L = MissSlot;
+    static constexpr int kN = kKeyedN, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
+    static constexpr SlotRegion keys = slot_after(L::greqs, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
+                                nf = slot_after(key_off, kNfBytes + kKeyedPad, 1), nf_off = slot_after(nf, kN + 1, 4),
+                                flags = slot_after(nf_off, kN, 4), vm = slot_after(L::gouts, kN, sizeof(mmp_vseam_row));
+    static_assert(kN <= L::kN && slot_fits({L::preqs, L::greqs, keys, key_off, nf, nf_off, flags, L::extra, L::excl_pod, L::explicit_pool,
+                                            L::excl_time, L::pouts, L::gouts, vm}),
+                  "vmodel-keyed miss slot layout");
+};
+struct VKeyedRouteSlot {
+    using L = RouteSlot;
+    static constexpr int kN = kKeyedN, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
+    static constexpr SlotRegion keys = slot_after(L::counters, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
+                                nf = slot_after(key_off, kNfBytes + kKeyedPad, 1), nf_off = slot_after(nf, kN + 1, 4),
+                                flags = slot_after(nf_off, kN, 4), vm = slot_after(L::souts, kN, sizeof(mmp_vseam_row));
+    static_assert(kN <= L::kN && slot_fits({L::greqs, L::sreqs, L::counters, keys, key_off, nf, nf_off, flags, L::excl_pod, L::explicit_pool,
+                                            L::excl_time, L::gouts, L::souts, vm}),
+                  "vmodel-keyed route slot layout");
 };
 struct EvictSlot {  // mmp_evict_batch: as many 32-byte result rows as the result buffer holds (2048); their 16-byte requests fit
     static constexpr int kN = (int)(kSlotBufBytes[kSlotOut] / sizeof(mmp_evict_out));
@@ -573,10 +609,23 @@ struct mmp_ctx {
     // of the model-id table over again (both are driven through IdTabRef).  vm_rows: one VmRow per vmodel; vm_arena: the strings,
     // vm_arena_bytes of them used, vm_live_bytes referred to by a row; vm_live_rows: rows that are not ABSENT.  vm_ev / vm_cnt /
     // vm_pos: one event call's parsed events, byte counts and their scan; vm_nf_* / vm_ow_* / vm_rflags / vm_ans: one resolve's
-    // staged strings, flags and answers; vm_list: the transition scan's rows.  Read and written under batch_mu, used on c->stream.
+    // staged strings, flags and answers; vm_list: the transition scan's rows.  The scratch is owned by batch_mu, used on c->stream.
     // mmp_vmodels_retire (vmodel_retire_kernels.hpp) takes its scratch from mmp_models_retire: ret_*, me_cnt / me_pos / j_scan_tmp.
+    // OWNERSHIP of the table itself — vid_hash / vid_val / vid_mask / vid_bytes / vid_off / vid_n / vid_nbytes, vm_rows, vm_arena,
+    // vm_arena_bytes and have_vmodels — is the rule written at mid_hash: every writer (mmp_vmodels_events_json, its squeeze,
+    // mmp_vmodels_retire) holds batch_mu for its whole call and builds beside what is published: the next id table in vid_next_*,
+    // the row array in vm_rows_next whenever a row of a known id is rewritten or the array has to grow (a ping-pong pair, as
+    // mid_next_* is), the arenas where they have to move; in place it only appends — id bytes and rows beyond vid_n, strings beyond
+    // vm_arena_bytes, which nothing a captured table lists refers to.  The published fields change under the state lock held
+    // EXCLUSIVE, all in one hold.  Readers hold batch_mu (mmp_vmodels_resolve, _transitions, _get, _info, _write_json), or — the
+    // request calls by vmodel id on a latency slot — the state lock SHARED while they capture the fields and enqueue.  What a swap
+    // retires (the old id table, now vid_next_*; the old rows, now vm_rows_next; an arena that moved) is neither rewritten nor
+    // released before quiesce_decisions has run behind the swap (vmodels_retired_drain).
+    // vq_*: the staged path of the request calls by vmodel id — the nf bytes, their offsets, the flags, the mmp_vseam_row (the keys
+    // and the load-target half take kq_*).  Owned by batch_mu, used on c->stream.
     DevBuf vid_hash, vid_val, vid_next_hash, vid_next_val, vid_bytes, vid_off;
-    DevBuf vm_rows, vm_arena, vm_ev, vm_cnt, vm_pos, vm_nf_bytes, vm_nf_off, vm_ow_bytes, vm_ow_off, vm_rflags, vm_ans, vm_list;
+    DevBuf vm_rows, vm_rows_next, vm_arena, vm_ev, vm_cnt, vm_pos, vm_nf_bytes, vm_nf_off, vm_ow_bytes, vm_ow_off, vm_rflags, vm_ans, vm_list;
+    DevBuf vq_nf, vq_nf_off, vq_flags, vq_out;
     uint32_t vid_mask = 0;
     int32_t vid_n = 0, vid_nbytes = 0, vm_arena_bytes = 0, vm_live_rows = 0;
     int64_t vm_live_bytes = 0;
@@ -1107,8 +1156,9 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     return MMP_OK;
 }
 
-// ---- the request seam: what the twelve host-pointer request calls share (mmp_place_batch, _place_batch_c, _place_batch_ck, _serve_batch,
-// _gate_batch, _miss_batch, _miss_batch_c, _miss_batch_ck, _route_batch, _route_batch_c, _route_batch_ck, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
+// ---- the request seam: what the fifteen host-pointer request calls share (mmp_place_batch, _place_batch_c, _place_batch_ck, _place_batch_cv,
+// _serve_batch, _gate_batch, _miss_batch, _miss_batch_c, _miss_batch_ck, _miss_batch_cv, _route_batch, _route_batch_c, _route_batch_ck,
+// _route_batch_cv, _evict_batch) — the range checks, the kernels' argument blocks, and the driver of their two paths ----------
 
 // [off, off + n) lies inside a pool of `len` entries (int64: off + n may pass INT32_MAX)
 inline bool in_pool(int32_t off, int32_t n, int32_t len) { return off >= 0 && n >= 0 && (int64_t)off + n <= len; }
@@ -1459,7 +1509,8 @@ void mmp_destroy(mmp_ctx *c)
                       &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
                       &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu, &c->rf_refs, &c->vw_reqs, &c->vw_strs, &c->vw_soff, &c->vw_rows,
-                      &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_arena,
+                      &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_rows_next, &c->vm_arena,
+                      &c->vq_nf, &c->vq_nf_off, &c->vq_flags, &c->vq_out,
                       &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
                       &c->vm_ans, &c->vm_list,
                       &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->kq_keys, &c->kq_off, &c->kq_idx, &c->kq_preqs, &c->kq_pouts, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
@@ -4012,18 +4063,23 @@ try {
 } MMP_CATCH(c, "mmp_models_events_json")
 
 namespace {
-// (a DevBuf that is released unless it has been handed over)
+// A DevBuf built beside a published one.  move_into (under the state lock held exclusive) publishes it and takes what it replaced,
+// which stays allocated and unwritten until this object ends: its owner declares it ahead of the work and runs
+// vmodels_retired_drain between the swap and its own return (the ownership rule at mmp_ctx::vid_hash).  Never handed over: released.
 struct ScopedDevBuf {
     DevBuf b;
     ~ScopedDevBuf() { b.release(); }
     void move_into(DevBuf &dst)
     {
-        if (!b.p) return;
-        dst.release();
-        dst = b;
-        b = DevBuf{};
+        if (b.p) std::swap(dst, b);
     }
 };
+
+// Behind a swap of the vmodel table, with batch_mu and without the state lock (model_ids_retired_drain for the vmodel side): a
+// request call by vmodel id that captured the table before the swap may still be running on a latency slot; it was enqueued under
+// the state lock, so quiesce_decisions sees it.  Only then may what the swap retired be rewritten (vid_next_*, vm_rows_next: by the
+// next event call) or released (the ScopedDevBufs and the plan, when their owner returns).
+hipError_t vmodels_retired_drain(mmp_ctx *c, bool swapped) { return swapped ? quiesce_decisions(c) : hipSuccess; }
 
 VmTab vmodel_tab(mmp_ctx *c)
 {
@@ -4065,10 +4121,13 @@ int vmodels_squeeze_if_garbage(mmp_ctx *c)
     kt_collect(c);
     kt_add(c, events_ms);
     if (live != c->vm_live_bytes) return fail(c, MMP_EHIP, "vmodel arena: %d live bytes on the device, %lld accounted", live, (long long)c->vm_live_bytes);
-    std::lock_guard<std::shared_mutex> g(c->mu);
-    rows.move_into(c->vm_rows);
-    arena.move_into(c->vm_arena);
-    c->vm_arena_bytes = live;
+    {
+        std::lock_guard<std::shared_mutex> g(c->mu);
+        rows.move_into(c->vm_rows);
+        arena.move_into(c->vm_arena);
+        c->vm_arena_bytes = live;
+    }
+    HIP_TRY(c, vmodels_retired_drain(c, true));  // the replaced rows and arena are released behind it, when `rows` / `arena` end
     return MMP_OK;
 }
 }  // namespace
@@ -4078,7 +4137,8 @@ int mmp_vmodels_events_json(mmp_ctx *c, const char *keys, const int32_t *key_off
 try {
     if (!c || n < 0 || (flags & ~MMP_VMEV_APPEND) || (n > 0 && (!key_off || !off || !vmodel_idx_out || !status_out)))
         return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: bad argument");
-    // the vmodel state is read and written under batch_mu; the state lock is taken for the swap only
+    // batch_mu for the call; the table is built beside the published one and swapped under the state lock, and what the swap retired
+    // is drained before this call lets go of it (the ownership rule at mmp_ctx::vid_hash)
     std::lock_guard<std::mutex> gb(c->batch_mu);
     if (n_appended_out) *n_appended_out = 0;
     if (n == 0) return MMP_OK;
@@ -4094,7 +4154,8 @@ try {
     if (const int rc = model_ids_plan(c, T, "mmp_vmodels_events_json", keys, key_off, n, deleted, flags & MMP_VMEV_APPEND, !c->have_vmodels, P))
         return rc;
     const int32_t V0 = P.n_before, V1 = V0 + P.n_join, k = P.k;
-    ScopedDevBuf fresh_rows, fresh_arena;
+    ScopedDevBuf fresh_arena;
+    bool rows_beside = false;
     VmBytes tot{0, 0, 0};
     double ms = P.ms;
     if (k > 0) {
@@ -4107,7 +4168,16 @@ try {
         HIP_TRY(c, c->j_status.ensure((size_t)n * 4));
         HIP_TRY(c, c->vm_cnt.ensure(((size_t)k + 1) * sizeof(VmBytes)));
         HIP_TRY(c, c->vm_pos.ensure(((size_t)k + 1) * sizeof(VmBytes)));
-        if (const int rc = grow_cow(c, c->vm_rows, (size_t)V0 * sizeof(VmRow), (size_t)V1 * sizeof(VmRow), fresh_rows.b)) return rc;
+        // The rows.  A call whose distinct rows all join only appends: in place, beyond the vid_n rows a captured table lists.  One
+        // that rewrites a row of a known id, or outgrows the array, builds in vm_rows_next — the published rows copied there first —
+        // and the publish swaps the two: a ping-pong pair as mid_next_* is (not a forced grow_cow: no allocation per call), which
+        // the drain behind the swap makes free for the next call.
+        const size_t rows_want = (size_t)V1 * sizeof(VmRow);
+        rows_beside = k > P.n_join || rows_want > c->vm_rows.cap;
+        if (rows_beside) {  // (an array that has to grow doubles, as grow_cow's do)
+            HIP_TRY(c, c->vm_rows_next.ensure(rows_want > c->vm_rows.cap ? std::max(rows_want, c->vm_rows.cap * 2) : rows_want));
+            if (V0 > 0) HIP_TRY(c, hipMemcpyAsync(c->vm_rows_next.p, c->vm_rows.p, (size_t)V0 * sizeof(VmRow), hipMemcpyDeviceToDevice, st));
+        }
         VmBytes *d_cnt = c->vm_cnt.as<VmBytes>(), *d_pos = c->vm_pos.as<VmBytes>();
         size_t scan_bytes = 0;
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, VmBytes{0, 0, 0}, (size_t)k + 1, VmBytesPlus(), st));
@@ -4129,9 +4199,9 @@ try {
         if ((int64_t)base + tot.add > INT32_MAX)  // (nothing but scratch has been written so far)
             return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: more than 2^31 bytes in the string arena");
         if (const int rc = grow_cow(c, c->vm_arena, (size_t)base, (size_t)base + tot.add + 16, fresh_arena.b)) return rc;
-        VmRow *rows = fresh_rows.b.p ? fresh_rows.b.as<VmRow>() : c->vm_rows.as<VmRow>();
+        VmRow *rows = rows_beside ? c->vm_rows_next.as<VmRow>() : c->vm_rows.as<VmRow>();
         char *arena = fresh_arena.b.p ? fresh_arena.b.as<char>() : c->vm_arena.as<char>();
-        // nothing is refused from here on: the winners' strings behind the published bytes, the rows rewritten
+        // nothing is refused from here on: the winners' strings behind the published bytes, the rows beside the published ones
         KT_BEGIN(c, st);
         hipLaunchKernelGGL(vm_build_kernel, dim3(div_up(k, 256)), dim3(256), 0, st, E.win, E.slot_model, k, V0, base, d_pos, A.ev, A.buf, A.off,
                            hash_mask(c->tune.model_id_hash_bits), rows, arena);
@@ -4146,13 +4216,16 @@ try {
     {
         std::lock_guard<std::shared_mutex> g(c->mu);  // table, arenas and counts change together
         model_ids_publish(T, P);
-        fresh_rows.move_into(c->vm_rows);
+        if (rows_beside) std::swap(c->vm_rows, c->vm_rows_next);
         fresh_arena.move_into(c->vm_arena);
         c->vm_arena_bytes += tot.add;
         c->vm_live_bytes += (int64_t)tot.add - tot.sub;
         c->vm_live_rows += tot.live;
         c->have_vmodels = true;
     }
+    // request calls by vmodel id that captured what the swap retired: the id table (rewritten by the next joining call), the rows
+    // (by the next call that rewrites one), the arenas (released when this call returns)
+    HIP_TRY(c, vmodels_retired_drain(c, P.swapped || rows_beside || fresh_arena.b.p != nullptr));
     for (int32_t i = 0; i < n; i++) {
         vmodel_idx_out[i] = P.idx[i];
         if (P.idx[i] < 0) status_out[i] = 2;  // an unknown id: nothing was read, nothing changes
@@ -4317,9 +4390,9 @@ try {
     if (!c || n < 0 || (n > 0 && !rows) || (flags & ~(MMP_VMRETIRE_ABSENT_ONLY | MMP_VMRETIRE_ALL_ABSENT)) || max_vmodels < 0)
         return fail(c, MMP_EINVAL, "mmp_vmodels_retire: bad argument");
     if (all && n > 0) return fail(c, MMP_EINVAL, "mmp_vmodels_retire: MMP_VMRETIRE_ALL_ABSENT takes no list (n = %d)", n);
-    // The vmodel state is read and written under batch_mu only (vmodel_tab: mmp_vmodels_resolve and _transitions hold it, and no
-    // decision kernel is handed a vmodel pointer), so nothing reads it while the compacted rows, arenas and table are built BESIDE
-    // the published ones: no quiesce, no rebuild_resolved.  The state lock is taken for the swap only, as in mmp_vmodels_events_json.
+    // The ownership rule at mmp_ctx::vid_hash: batch_mu for the call, the compacted rows, arenas and table built BESIDE the published
+    // ones (the request calls by vmodel id go on reading those from the latency slots), the state lock exclusive for the swap only,
+    // and the drain behind it before anything the swap retired is released.  No decision kernel reads a vmodel row: no rebuild_resolved.
     std::lock_guard<std::mutex> gb(c->batch_mu);
     const int32_t V0 = c->have_vmodels ? c->vid_n : 0;
     if (remap_out && max_vmodels < V0)
@@ -4428,6 +4501,9 @@ try {
         c->vm_live_rows = tot.live;
         c->have_vmodels = V1 > 0;  // (no row: the state before the first vmodel call, which the next event batch starts from)
     }
+    // a request call by vmodel id saw the numbering before the swap or sees the one after it; the ones that captured the old rows,
+    // arenas and table are drained before nr / na / nb / no release those and the next event call rewrites vid_next_*
+    HIP_TRY(c, vmodels_retired_drain(c, true));
     if (remap_out) memcpy(remap_out, remap.data(), (size_t)V0 * 4);
     if (n_vmodels_after_out) *n_vmodels_after_out = V1;
     return MMP_OK;
@@ -6432,24 +6508,33 @@ int keyed_empty(mmp_ctx *c, const char *fn)  // n == 0
     std::shared_lock<std::shared_mutex> g(c->mu);
     return keyed_state(c, fn);
 }
-// The three arrays a keyed call adds to the call it resolves in front of: the key bytes, their offsets as the caller gave them,
-// and the resolved rows.  On a slot the bytes are copied as they are (the layouts leave kKeyedPad bytes behind them); staged, from
-// a copy that carries the padding.  A NULL model_idx_out gets a sink: the kernel writes the rows either way.
-struct KeyedIo {
+// n byte spans of a call as the resolving kernels take them: the bytes and their n + 1 offsets as the caller gave them.  On a slot
+// the bytes are copied as they are (the layouts leave kKeyedPad bytes behind them); staged, from a copy that carries the padding.
+struct KeyedSpans {
     std::vector<char> padded;
-    std::vector<int32_t> sink;
-    SeamIo kb, ko, ix;
-    KeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, int32_t *model_idx_out, bool on_slot,
-            const SlotRegion &keys_at, const SlotRegion &off_at, const SlotRegion &idx_at)
+    SeamIo kb, ko;
+    void bind(const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, bool on_slot, const SlotRegion &keys_at,
+              const SlotRegion &off_at, DevBuf &bytes_stage, DevBuf &off_stage)
     {
         const char *first = key_bytes > 0 ? keys + key_off[0] : nullptr;
         if (!on_slot) {
             padded.assign((size_t)key_bytes + kKeyedPad, 0);
             if (key_bytes > 0) memcpy(padded.data(), first, (size_t)key_bytes);
-            kb = seam_io(padded.data(), key_bytes + kKeyedPad, keys_at, c->kq_keys);
+            kb = seam_io(padded.data(), key_bytes + kKeyedPad, keys_at, bytes_stage);
         } else
-            kb = seam_io(first, key_bytes, keys_at, c->kq_keys);
-        ko = seam_io(key_off, n + 1, off_at, c->kq_off);
+            kb = seam_io(first, key_bytes, keys_at, bytes_stage);
+        ko = seam_io(key_off, n + 1, off_at, off_stage);
+    }
+};
+// The three arrays a keyed call adds to the call it resolves in front of: the key bytes, their offsets, and the resolved rows.  A
+// NULL model_idx_out gets a sink: the kernel writes the rows either way.
+struct KeyedIo : KeyedSpans {
+    std::vector<int32_t> sink;
+    SeamIo ix;
+    KeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, int32_t *model_idx_out, bool on_slot,
+            const SlotRegion &keys_at, const SlotRegion &off_at, const SlotRegion &idx_at)
+    {
+        bind(keys, key_off, n, key_bytes, on_slot, keys_at, off_at, c->kq_keys, c->kq_off);
         if (!model_idx_out) {
             sink.resize((size_t)n);
             model_idx_out = sink.data();
@@ -6664,6 +6749,281 @@ try {
                         return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
                     });
 } MMP_CATCH(c, "mmp_miss_batch_ck")
+
+// ---- the request calls by vmodel id (include/mmplace.h: THE RULE BY VMODEL KEY; kernel: vkeyed_kernels.hpp) -----------------------
+// The frame of the calls by model id above, with vkeyed_resolve_kernel in the place of keyed_resolve_kernel: resolveVModelId and the
+// lookup of the id it returns happen on the device in front of the unchanged decision kernels, on the same stream.  On a slot the
+// state lock is held shared over the guard, the capture of the published vmodel table, model-id table and registry row count, and
+// every enqueue (seam_slot); batch_mu is never taken: the ownership rules at mmp_ctx::vid_hash and ::mid_hash make that capture safe.
+namespace {
+// The arrays a call by vmodel id adds: the vmodel keys and the notFoundModelId spans (bytes + offsets each), the flags, and the
+// mmp_vseam_row per request.  The kernel takes all of them, so what the caller left out is supplied here: no nf is n + 1 equal
+// offsets, no flags n zero words, a NULL vm_out a sink.
+struct VKeyedIo {
+    std::vector<int32_t> no_nf;
+    std::vector<uint32_t> no_flags;
+    std::vector<mmp_vseam_row> sink;
+    KeyedSpans key, nf;
+    SeamIo fl, vo;
+    VKeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t key_bytes, const char *nf_keys, const int32_t *nf_off,
+             int32_t nf_bytes, const uint32_t *req_flags, int32_t n, mmp_vseam_row *vm_out, bool on_slot, const SlotRegion &keys_at,
+             const SlotRegion &off_at, const SlotRegion &nf_at, const SlotRegion &nf_off_at, const SlotRegion &flags_at, const SlotRegion &vm_at)
+    {
+        key.bind(keys, key_off, n, key_bytes, on_slot, keys_at, off_at, c->kq_keys, c->kq_off);
+        if (!nf_off) {
+            no_nf.assign((size_t)n + 1, 0);
+            nf_off = no_nf.data();
+        }
+        nf.bind(nf_keys, nf_off, n, nf_bytes, on_slot, nf_at, nf_off_at, c->vq_nf, c->vq_nf_off);
+        if (!req_flags) {
+            no_flags.assign((size_t)n, 0u);
+            req_flags = no_flags.data();
+        }
+        fl = seam_io(req_flags, n, flags_at, c->vq_flags);
+        if (!vm_out) {
+            sink.resize((size_t)n);
+            vm_out = sink.data();
+        }
+        vo = seam_io(vm_out, n, vm_at, c->vq_out);
+    }
+};
+// what the _cv forms refuse beyond the _ck forms: the nf spans and the flags
+int vkeyed_check(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, const char *nf_keys, const int32_t *nf_off,
+                 const uint32_t *req_flags, int32_t n, int32_t &key_bytes, int32_t &nf_bytes)
+{
+    nf_bytes = 0;
+    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
+    if (n > 0 && nf_off) {
+        if (const int rc = check_offsets(c, fn, "nf ", nf_off, n)) return rc;
+        const int64_t bytes = (int64_t)nf_off[n] - nf_off[0];
+        if (bytes > INT32_MAX - kKeyedPad) return fail(c, MMP_EINVAL, "%s: more than 2^31 nf bytes", fn);
+        if (bytes > 0 && !nf_keys) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+        nf_bytes = (int32_t)bytes;
+    }
+    if (req_flags)
+        for (int32_t i = 0; i < n; i++)
+            if (req_flags[i] & ~MMP_VMRQ_AFTER_STRONG) return fail(c, MMP_EINVAL, "%s: request %d has unknown flag bits", fn, i);
+    return MMP_OK;
+}
+// (called with the state lock held, or by the owner of batch_mu under which no writer of either table runs)
+int vkeyed_launch(mmp_ctx *c, hipStream_t st, const VKeyedIo &K, int32_t n, const KeyedPatch &a, const KeyedPatch &b)
+{
+    VKeyedArgs A;
+    A.keys = K.key.kb.as<char>();
+    A.off = K.key.ko.as<int32_t>();
+    A.nf = K.nf.kb.as<char>();
+    A.nf_off = K.nf.ko.as<int32_t>();
+    A.flags = K.fl.as<uint32_t>();
+    A.n = n;
+    A.hmask = hash_mask(c->tune.vmodel_id_hash_bits);
+    A.V = vmodel_tab(c);
+    A.models = model_id_tab(c).published();
+    A.n_models = c->n_models;
+    A.out = K.vo.as<mmp_vseam_row>();
+    A.a = a;
+    A.b = b;
+    hipLaunchKernelGGL(vkeyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+}  // namespace
+
+int mmp_place_batch_cv(mmp_ctx *c, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
+                       const int32_t *key_off, const char *nf_keys, const int32_t *nf_off, const uint32_t *req_flags,
+                       const int32_t *extra_pool, int32_t n_extra, int64_t now, mmp_place_out *outs, mmp_vseam_row *vm_out)
+try {
+    const char *fn = "mmp_place_batch_cv";
+    if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++)
+        if (const int rc = check_place_req(c, fn, i, reqs[i], n_extra)) return rc;
+    int32_t key_bytes, nf_bytes;
+    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = VKeyedPlaceSlot;
+    const bool on_slot = n <= L::kN && n_extra <= L::kExtra && key_bytes <= L::kKeyBytes && nf_bytes <= L::kNfBytes;
+    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, L::keys, L::key_off, L::nf, L::nf_off,
+               L::flags, L::vm);
+    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), o = seam_io(outs, n, L::outs, c->s_outs);
+    if (on_slot) {  // the rows written out in full with model = -1, as mmp_place_batch_ck does; a lone request takes the row path too
+        std::vector<mmp_place_req> full((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            full[(size_t)i] = full_place_row(*caller, reqs[i]);
+            full[(size_t)i].model = -1;
+        }
+        SeamIo q = seam_io(full.data(), n, L::reqs);
+        return seam_run<true>(c, n, true, {&q, &x, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&o, &K.vo},
+                        [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req>(q), kNoPatch)) return rc;
+                            return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, nullptr));
+                        });
+    }
+    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs);
+    return seam_run<true>(c, n, false, {&q, &x, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&o, &K.vo},
+                    [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &, auto) {
+                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req_c>(q), kNoPatch)) return rc;
+                        PlaceCall call;
+                        call.caller = caller;
+                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
+                    });
+} MMP_CATCH(c, "mmp_place_batch_cv")
+
+int mmp_route_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
+                       const char *keys, const int32_t *key_off, const char *nf_keys, const int32_t *nf_off, const uint32_t *req_flags,
+                       const mmp_serve_counter *counters, int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time,
+                       int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
+                       mmp_gate_out *gouts, mmp_serve_out *souts, mmp_vseam_row *vm_out)
+try {
+    const char *fn = "mmp_route_batch_cv";
+    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
+        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges, as mmp_route_batch_c checks them
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
+        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
+            return bad_range(c, fn, i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
+    }
+    int32_t key_bytes, nf_bytes;
+    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = RouteSlot;
+    using KL = VKeyedRouteSlot;
+    const bool on_slot = n <= KL::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit &&
+                         key_bytes <= KL::kKeyBytes && nf_bytes <= KL::kNfBytes;
+    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, KL::keys, KL::key_off, KL::nf,
+               KL::nf_off, KL::flags, KL::vm);
+    SeamIo cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
+    auto bind = [&](GateArgs &G, ServeArgs &S, const DoneFlag &done) {
+        G.excl_pod = xp.as<int32_t>();
+        G.excl_time = xt.as<int64_t>();
+        G.explicit_pool = ex.as<int32_t>();
+        G.outs = go.as<mmp_gate_out>();
+        G.done = done;
+        S.counters = cnt.as<mmp_serve_counter>();
+        S.excl_pod = G.excl_pod;
+        S.excl_time = G.excl_time;
+        S.outs = so.as<mmp_serve_out>();
+    };
+    if (on_slot) {  // the rows written out in full with model = -1, as mmp_route_batch_ck does; one route takes the row kernel too
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_serve_req> fs((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
+            fg[(size_t)i].model = fs[(size_t)i].model = -1;
+        }
+        SeamIo gq = seam_io(fg.data(), n, L::greqs), sq = seam_io(fs.data(), n, L::sreqs);
+        return seam_run<false>(c, n, true, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&go, &so, &K.vo},
+                        [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            GateArgs G = gate_args(c, n, now, in_use_expiry);
+                            ServeArgs S = serve_args(c, n, now);
+                            bind(G, S, done);
+                            G.reqs = gq.as<mmp_gate_req>();
+                            S.reqs = sq.as<mmp_serve_req>();
+                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_serve_req>(sq))) return rc;
+                            HIP_TRY(c, order_after_registry(c, st));
+                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
+                            HIP_TRY(c, hipGetLastError());
+                            return MMP_OK;
+                        });
+    }
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs);
+    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&go, &so, &K.vo},
+                    [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        GateArgs G = gate_args(c, n, now, in_use_expiry);
+                        ServeArgs S = serve_args(c, n, now);
+                        bind(G, S, done);
+                        // (the compact serve row has no model of its own: the serve half reads the gate row's)
+                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), kNoPatch)) return rc;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
+                                           seam_c_args(*caller, gq, &sq, n));
+                        HIP_TRY(c, hipGetLastError());
+                        return MMP_OK;
+                    });
+} MMP_CATCH(c, "mmp_route_batch_cv")
+
+int mmp_miss_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
+                      const mmp_place_req_c *preqs, int32_t n, const char *keys, const int32_t *key_off, const char *nf_keys,
+                      const int32_t *nf_off, const uint32_t *req_flags, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
+                      const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now,
+                      int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts, mmp_vseam_row *vm_out)
+try {
+    const char *fn = "mmp_miss_batch_cv";
+    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
+        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
+        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {  // (both halves take the row the vmodel resolves to: no "names two models" here)
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
+        if (const int rc = check_place_req(c, fn, i, preqs[i], n_extra)) return rc;
+    }
+    int32_t key_bytes, nf_bytes;
+    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = MissSlot;
+    using KL = VKeyedMissSlot;
+    const bool on_slot = n <= KL::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool && key_bytes <= KL::kKeyBytes &&
+                         nf_bytes <= KL::kNfBytes;
+    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, KL::keys, KL::key_off, KL::nf,
+               KL::nf_off, KL::flags, KL::vm);
+    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
+           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
+           po = seam_io(pouts, n, L::pouts, c->kq_pouts), go = seam_io(gouts, n, L::gouts, c->s_outs);
+    auto gate = [&](const DoneFlag &done) {
+        GateArgs G = gate_args(c, n, now, in_use_expiry);
+        G.excl_pod = xp.as<int32_t>();
+        G.excl_time = xt.as<int64_t>();
+        G.explicit_pool = ex.as<int32_t>();
+        G.outs = go.as<mmp_gate_out>();
+        G.done = done;
+        return G;
+    };
+    if (on_slot) {
+        // as mmp_miss_batch_ck: one slot, three launches on its stream (the resolution, the guards, the load targets: the last
+        // one's completion flag covers all), one wait.  A lone request takes the row path too.
+        std::vector<mmp_gate_req> fg((size_t)n);
+        std::vector<mmp_place_req> fp((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
+            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
+            fg[(size_t)i].model = fp[(size_t)i].model = -1;
+        }
+        SeamIo pq = seam_io(fp.data(), n, L::preqs), gq = seam_io(fg.data(), n, L::greqs);
+        return seam_run<true>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&po, &go, &K.vo},
+                        [&] { return keyed_state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            GateArgs G = gate(DoneFlag{nullptr, nullptr, 0});
+                            G.reqs = gq.as<mmp_gate_req>();
+                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_place_req>(pq))) return rc;
+                            HIP_TRY(c, order_after_registry(c, st));
+                            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
+                            HIP_TRY(c, hipGetLastError());
+                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
+                        });
+    }
+    // a large batch: both halves staged in ONE hold of batch_mu (one resolution names both halves' rows), on the compact rows
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), pq = seam_io(preqs, n, kStagedOnly, c->kq_preqs);
+    return seam_run<true>(c, n, false, {&pq, &gq, &x, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&po, &go, &K.vo},
+                    [&] { return keyed_state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate(done);
+                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), keyed_patch_of<mmp_place_req_c>(pq))) return rc;
+                        HIP_TRY(c, order_after_registry(c, st));
+                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G,
+                                           seam_c_args(*caller, gq, nullptr, n));
+                        HIP_TRY(c, hipGetLastError());
+                        PlaceCall call;
+                        call.caller = pcaller;
+                        return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
+                    });
+} MMP_CATCH(c, "mmp_miss_batch_cv")
 
 int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
 try {

@@ -24,7 +24,8 @@
 // claimed it.  Which lane claims a slot, and under equal hashes which slot a key gets, depends on the race; no output does — all
 // are functions of the two minima, so two runs are byte-identical.
 //
-// Ownership of the MODEL-id table (the vmodel-id table, driven by the same kernels, is read and written under batch_mu alone).
+// Ownership of the MODEL-id table (the vmodel-id table, driven by the same kernels, has the same rule for the request calls by
+// vmodel id: mmp_ctx::vid_hash in mmplace.hip, vkeyed_kernels.hpp).
 // Writers hold batch_mu for the call and build beside the published table: the next table in mid_next_*, the arena where it has to
 // move, and an append in place only beyond the rows the published table lists — a captured ModelIdTab cannot reach rows it does
 // not list.  The swap happens under the state lock held exclusive, in the hold that publishes the registry's new row count.  Readers

@@ -307,7 +307,26 @@ __device__ __forceinline__ bool vm_in_transition(const VmTab &V, const VmRow &r)
 
 __device__ __forceinline__ bool vm_model_empty(const mmp_model_row &m) { return retire_row_empty(m); }
 
-// resolveVModelId (VModelManager.java:569-597) in both phases, absentOrOwnerMismatch (:530-532), the class of statusFromRecord
+// THE CHOICE of resolveVModelId (VModelManager.java:569-597) in both phases, behind absentOrOwnerMismatch (:530-532), stated once for
+// vm_resolve_kernel and vkeyed_resolve_kernel (vkeyed_kernels.hpp).  [owner, owner + olen) and [np, np + nlen) are the owner and the
+// notFoundModelId, an empty span Java null; after: the question is asked again behind the strong read.  which = -1 unless cls is
+// MMP_VMR_OK.  For MMP_VMR_NOT_FOUND and MMP_VMR_HOST nothing else of the row is answered.
+struct VmChoice {
+    int32_t cls, which;
+};
+__device__ __forceinline__ VmChoice vm_choose(const VmTab &V, const VmRow &r, const char *owner, int32_t olen, const char *np, int32_t nlen,
+                                              bool after)
+{
+    if (r.flags & kVmfAbsent) return VmChoice{MMP_VMR_NOT_FOUND, -1};  // :570-573
+    if (r.flags & kVmfHost) return VmChoice{MMP_VMR_HOST, -1};
+    if (olen > 0 && !vm_str_is(V, r, 2, owner, olen)) return VmChoice{MMP_VMR_NOT_FOUND, -1};  // :530-532, an owner is given and differs
+    if (nlen == 0 || !vm_str_is(V, r, 0, np, nlen)) return VmChoice{MMP_VMR_OK, MMP_VMW_ACTIVE};  // :575, and :587 after the strong read
+    if (!after) return VmChoice{MMP_VMR_STRONG_READ, -1};  // :582
+    if (!vm_str_is(V, r, 1, np, nlen)) return VmChoice{MMP_VMR_OK, MMP_VMW_TARGET};  // :591
+    return VmChoice{MMP_VMR_TARGET_NOT_FOUND, -1};  // :594
+}
+
+// resolveVModelId and absentOrOwnerMismatch (vm_choose), the class of statusFromRecord
 // (:555-556) and of resolveTargetModelStatusInfo (:537-549).  Spans: key i, and where given nf i and owner i; an empty span is
 // Java null.
 __global__ __launch_bounds__(kIdTabBlock) void vm_resolve_kernel(const char *__restrict__ keys, const int32_t *__restrict__ key_off,
@@ -326,29 +345,14 @@ __global__ __launch_bounds__(kIdTabBlock) void vm_resolve_kernel(const char *__r
     const int32_t klen = key_off[i + 1] - key_off[i];
     const int32_t v = mid_find(V.ids, fnv1a(key, klen) & vm_hmask, key, klen);
     const VmRow r = v >= 0 && v < V.n_rows ? V.rows[v] : vm_absent_row();
-    const int32_t olen = owner_off ? owner_off[i + 1] - owner_off[i] : 0;
-    if (r.flags & kVmfAbsent) {
-        // :570-573
-    } else if (r.flags & kVmfHost) {
-        a.cls = MMP_VMR_HOST;
+    const int32_t olen = owner_off ? owner_off[i + 1] - owner_off[i] : 0, nlen = nf_off ? nf_off[i + 1] - nf_off[i] : 0;
+    const VmChoice ch = vm_choose(V, r, olen > 0 ? owners + owner_off[i] : nullptr, olen, nlen > 0 ? nf + nf_off[i] : nullptr, nlen,
+                                  req_flags && (req_flags[i] & MMP_VMRQ_AFTER_STRONG));
+    a.cls = ch.cls;
+    if (ch.cls == MMP_VMR_HOST)
         a.vmodel = v;
-    } else if (olen > 0 && !vm_str_is(V, r, 2, owners + owner_off[i], olen)) {
-        // :530-532, an owner is given and differs
-    } else {
-        const int32_t nlen = nf_off ? nf_off[i + 1] - nf_off[i] : 0;
-        const char *np = nlen > 0 ? nf + nf_off[i] : nullptr;
-        const bool after = req_flags && (req_flags[i] & MMP_VMRQ_AFTER_STRONG);
-        int which = -1;
-        if (nlen == 0 || !vm_str_is(V, r, 0, np, nlen)) {  // :575, and :587 after the strong read
-            a.cls = MMP_VMR_OK;
-            which = 0;
-        } else if (!after)
-            a.cls = MMP_VMR_STRONG_READ;  // :582
-        else if (!vm_str_is(V, r, 1, np, nlen)) {  // :591
-            a.cls = MMP_VMR_OK;
-            which = 1;
-        } else
-            a.cls = MMP_VMR_TARGET_NOT_FOUND;  // :594
+    else if (ch.cls != MMP_VMR_NOT_FOUND) {
+        const int which = ch.which;
         a.vmodel = v;
         a.target_model = vm_model_of(V, M, r, 1);
         if (which >= 0) {

@@ -1166,6 +1166,89 @@ class Solver:
                                             ptr(gouts) if n else None, ptr(pouts) if n else None, ptr(idx) if want_idx else None))
         return gouts, pouts, (idx[:n] if want_idx else None)
 
+    # ---- the single-caller forms by vmodel id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv) ----
+    def _vkey_args(self, n, keys, nf, req_flags, want_vm):
+        """What the _cv calls add: (key blob, key offsets, nf blob, nf offsets, flags, vm_out).  nf is a list of
+        bytes/str/None (None and b"" are Java null) or None for NULL buffers; req_flags n words or None."""
+        assert len(keys) == n
+        blob, off = self.pack_keys(keys)
+        nblob = noff = None
+        if nf is not None:
+            assert len(nf) == n
+            nblob, noff = self.pack_keys([x if x is not None else b"" for x in nf])
+        rf = None if req_flags is None else np.ascontiguousarray(req_flags, dtype=np.uint32)
+        assert rf is None or len(rf) == n
+        vm = np.zeros(max(n, 1), _lib.VSEAM_ROW)
+        vm.view(np.uint8)[:] = 0xEE
+        return blob, off, nblob, noff, rf, (vm if want_vm else None)
+
+    def place_batch_cv(self, caller, reqs_c, keys, extra_pool, now, nf=None, req_flags=None, want_vm=True):
+        """mmp_place_batch_c with request i's model named by the VMODEL id keys[i], resolved (resolveVModelId with nf[i] and
+        req_flags[i]) inside the call: -> (outs, vm rows as VSEAM_ROW); the `model` field of reqs_c is ignored.  want_vm=False
+        passes a NULL vm_out and returns None for it."""
+        from ._lib import PLACE_CALLER, PLACE_REQ_C
+        caller = np.ascontiguousarray(caller, dtype=PLACE_CALLER).reshape(1)
+        reqs_c = np.ascontiguousarray(reqs_c, dtype=PLACE_REQ_C)
+        extra = np.zeros(0, np.int32) if extra_pool is None else np.ascontiguousarray(extra_pool, dtype=np.int32)
+        n = len(reqs_c)
+        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
+        outs = np.zeros(n, dtype=PLACE_OUT)
+        self._ck(self.lib.mmp_place_batch_cv(self.h, ptr(caller), ptr(reqs_c) if n else None, n, blob, ptr(off), nblob, ptr(noff),
+                                             ptr(rf), ptr(extra) if len(extra) else None, len(extra), C.c_int64(int(now)),
+                                             ptr(outs) if n else None, ptr(vm)))
+        return outs, (vm[:n] if want_vm else None)
+
+    def route_batch_cv(self, caller, gate_reqs_c, serve_reqs_c, keys, counters, excl_pod, excl_time, explicit_pool, now,
+                       in_use_failure_expiry_ms=450_000, nf=None, req_flags=None, want_vm=True):
+        """mmp_route_batch_c with request i's model named by the VMODEL id keys[i]: -> (gate outs, serve outs, vm rows)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
+        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        assert len(serve_reqs_c) == n
+        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        souts = np.zeros(n, dtype=SERVE_OUT)
+        self._ck(self.lib.mmp_route_batch_cv(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
+                                             blob, ptr(off), nblob, ptr(noff), ptr(rf),
+                                             ptr(counters) if len(counters) else None, len(counters),
+                                             ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                             len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                             C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                             ptr(gouts) if n else None, ptr(souts) if n else None, ptr(vm)))
+        return gouts, souts, (vm[:n] if want_vm else None)
+
+    def miss_batch_cv(self, caller, place_caller, gate_reqs_c, place_reqs_c, keys, excl_pod, excl_time, explicit_pool, extra_pool, now,
+                      in_use_failure_expiry_ms=450_000, nf=None, req_flags=None, want_vm=True):
+        """mmp_miss_batch_c with request i's model named by the VMODEL id keys[i]: -> (gate outs, place outs, vm rows)."""
+        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_REQ_C, SEAM_CALLER
+        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
+        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
+        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
+        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
+        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
+        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
+        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
+        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
+        n = len(gate_reqs_c)
+        assert len(place_reqs_c) == n
+        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
+        gouts = np.zeros(n, dtype=GATE_OUT)
+        pouts = np.zeros(n, dtype=PLACE_OUT)
+        self._ck(self.lib.mmp_miss_batch_cv(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
+                                            ptr(place_reqs_c) if n else None, n, blob, ptr(off), nblob, ptr(noff), ptr(rf),
+                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
+                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
+                                            ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
+                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
+                                            ptr(gouts) if n else None, ptr(pouts) if n else None, ptr(vm)))
+        return gouts, pouts, (vm[:n] if want_vm else None)
+
     def proactive_plan(self, default_model_size_units: int, now: int, max_out: int, partition: int = -1, skip_models=None):
         """a17: (models, last_used, info) the leader would proactively load, MRU first; partition >= 0: for that
         ProhibitedTypeSet partition only (one reaper call per partition when type constraints exist)."""
