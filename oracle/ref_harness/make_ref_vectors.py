@@ -8,7 +8,9 @@ filter, audit hash of the shortlist).  Per serve-target case: (chosen, chosenTim
 loadLocal's initial size).  Plus a digest of each case's inputs.
 tests/golden/ref_gate_edges.npz: the guard cases at the edges of their value domain (gate_edge_vectors below).
 tests/golden/ref_place_edges.npz: the load-target cases at the edges of theirs (place_edge_vectors below).
-usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges]"""
+tests/golden/ref_rebalance_edges.npz: the rate task, the janitor's scale-down and the reaper's proactive loads at the edges of theirs
+(rebalance_edge_vectors below).
+usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges | --rebalance-edges]"""
 import os
 import subprocess
 import sys
@@ -26,6 +28,7 @@ HARNESS = os.environ.get("MMP_REF_HARNESS") or os.path.join(ROOT, "oracle", "_re
 OUT = os.environ.get("MMP_REF_OUT") or os.path.join(ROOT, "tests", "golden", "ref_getnext.npz")
 EDGE_OUT = os.environ.get("MMP_REF_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_gate_edges.npz")
 PLACE_EDGE_OUT = os.environ.get("MMP_REF_PLACE_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_place_edges.npz")
+REBALANCE_EDGE_OUT = os.environ.get("MMP_REF_REBALANCE_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_rebalance_edges.npz")
 
 
 def proactive_inputs(fleet, units, partitioned):
@@ -262,6 +265,147 @@ def place_edge_vectors():
     print(f"wrote {PLACE_EDGE_OUT}: {os.path.getsize(PLACE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
 
 
+def run_rebalance(tier, case, blob):
+    """One rebalance edge case through the harness -> {field: array}: rate: scale (action, copies, timestamp, i1, i2, heavy per entry),
+    overloaded, exclude_set_built, with MaxConcCacheEntry rows also conc + average_model_parallelism; janitor: removed; plan: proactive."""
+    fleet = case[0]
+    if tier == "rate":
+        n, latency = len(case[2]), case[3] is not None
+        got = run(blob, 0, 0, 0, n, fleet.n_pods, conc=latency)
+        out = dict(scale=got[4], exclude_set_built=np.array([got[5]]), overloaded=got[6])
+        if latency:
+            out["conc"], out["average_model_parallelism"] = got[7], got[8]
+        return out
+    if tier == "janitor":
+        return dict(removed=run(blob, 0, 0, 0, -1, 0, len(case[2])))
+    return dict(proactive=run(blob, 0, 0, proactive=True))
+
+
+def rebalance_answer(tier, out, row):
+    """What the reference answered for one row of a case (row -1: for the run as a whole)."""
+    if tier == "rate":
+        a = out["scale"] if row < 0 else out["scale"][row]
+        if "conc" in out:
+            a = np.concatenate([np.ravel(a), np.ravel(out["conc"] if row < 0 else out["conc"][row])])
+        return np.ravel(a)
+    if tier == "janitor":
+        return np.ravel(out["removed"] if row < 0 else out["removed"][row])
+    calls = out["proactive"]
+    return np.ravel(calls[:, :2]) if row < 0 else np.array([int(np.any(calls[:, 0] == row))])
+
+
+def rebalance_throws(tier, case):
+    """The rows on which the Java would throw, from the inputs alone (the harness is C++ and traps there): a reason, or None."""
+    from oracle import bind as ob
+    fleet = case[0]
+    if tier == "rate":
+        sp = case[4]
+        if int(sp["now"][0]) == int(sp["last_check_time"][0]):
+            return "timeDelta == 0"
+        if case[3] is None and int(sp["scale_up_rpm_threshold"][0]) == 0:
+            return "scaleUpRpms == 0"
+        rows = list(ob.type_set_stats(fleet)) + [ob.OracleFleet(fleet).stats()]
+        if any(int(s["instance_count"]) >= 2 and int(s["total_capacity"]) == 0 for s in rows):
+            return "totalCapacity == 0 at the fullness clause"
+        return None
+    if tier == "janitor":
+        dp = case[4]
+        return "timeSinceLastCheck == 0" if int(dp["now"][0]) == int(dp["last_check_time"][0]) else None
+    units, partitioned = case[2], case[3]
+    stats = list(ob.partition_stats(fleet)[2]) if partitioned else [ob.OracleFleet(fleet).stats()]
+    for s in stats:
+        tc, tf, c = int(s["total_capacity"]), int(s["total_free"]), int(s["model_copy_count"])
+        if tc > 0 and tf > 0 and c >= 3:
+            avg = rf._tdiv(rf._i32(tc - tf), c)
+            if (avg if c > 10 else rf._tdiv(rf._i32(avg + units), 2)) == 0:
+                return "sizeEstimate == 0"
+        if tc > 0 and tf > 0 and c < 3 and units == 0:
+            return "sizeEstimate == 0"
+    return None
+
+
+def rebalance_edge_vectors():
+    """tests/golden/ref_rebalance_edges.npz: the rate task, the janitor's scale-down and the reaper's proactive loads at the edges of
+    their value domain (tests/ref_fleets.py:rebalance_edge_cases).  A case that does not hold what it is there for is REFUSED, on
+    the evidence of the inputs and the reference's own outputs: both rows of every pair must be answered differently."""
+    out, names, outs, tiers = {}, [], {}, {}
+    seen = {t: dict(cases=0, rows=0, pairs=0, run_pairs=0, sizes=set(), lens=set(), what={}) for t in rf.REBALANCE_EDGE_TIERS}
+
+    def count(tier, what, n=1):
+        if n:
+            seen[tier]["what"][what] = seen[tier]["what"].get(what, 0) + int(n)
+
+    for name, tier, case in rf.rebalance_edge_cases():
+        fleet, meta = case[0], case[-1]
+        assert tier == rf.rebalance_edge_tier(name) and fleet.n_pods in (8, 64, 65) and fleet.n_models <= 600, name
+        assert rebalance_throws(tier, case) is None, (name, rebalance_throws(tier, case))
+        blob = rf.rebalance_blob(tier, case)
+        got = run_rebalance(tier, case, blob)
+        n_rows = fleet.n_models if tier == "plan" else len(case[2])
+        assert 0 < n_rows <= 600, name
+        for a, b, what in meta["pairs"]:
+            assert not np.array_equal(rebalance_answer(tier, got, a), rebalance_answer(tier, got, b)), \
+                (name, "the reference answers a pair alike", a, b, what, rebalance_answer(tier, got, a))
+        st = seen[tier]
+        st["cases"], st["rows"], st["pairs"] = st["cases"] + 1, st["rows"] + n_rows, st["pairs"] + len(meta["pairs"])
+        st["sizes"].add(fleet.n_pods)
+        st["lens"].add(n_rows)
+        if tier == "rate":
+            sc, sp = got["scale"], case[4]
+            early = int(sp["now"][0] - sp["last_check_time"][0]) * 5 < int(sp["rate_check_interval_ms"][0]) * 3
+            few = int((fleet.pods["flags"] & 5 == 0).sum()) < 2
+            assert (early or few) == (not sc[:, 0].any() and np.array_equal(sc[:, 3:5], np.stack(
+                [case[2]["earlier_use_iteration"], case[2]["last_used_iteration"]], 1))), (name, "an early return that leaves no trace")
+            count(tier, "exit: timeDelta too short", early)
+            count(tier, "exit: fewer than two instances", few and not early)
+            for k, a in enumerate(("none", "second copy", "scale-up")):
+                count(tier, a, (sc[:, 0] == k).sum())
+            count(tier, "heavy", sc[:, 5].sum())
+            count(tier, "markers moved", (sc[:, 4] != case[2]["last_used_iteration"]).sum())
+            count(tier, "overloaded instances", got["overloaded"].sum())
+            if "overloaded" in meta:
+                assert sorted(np.flatnonzero(got["overloaded"])) == sorted(meta["overloaded"]), (name, np.flatnonzero(got["overloaded"]))
+            if "conc" in got:
+                count(tier, "counter resets", got["conc"][:, 1].sum())
+                assert not np.any((got["conc"][:, 0] == 0) & (sc[:, 0] == 2)), (name, "scaleUpRpms == 0 reached")
+        elif tier == "janitor":
+            count(tier, "removed", got["removed"].sum())
+            count(tier, "kept", (got["removed"] == 0).sum())
+            count(tier, "exit: shutting down", int(case[4]["shutting_down"][0]))
+        else:
+            count(tier, "loads", len(got["proactive"]))
+            count(tier, "runs without a load", len(got["proactive"]) == 0)
+        for k, v in got.items():
+            out[f"{name}/{k}"] = v
+        out[f"{name}/pairs"] = np.array([(a, b) for a, b, _ in meta["pairs"]], np.int32).reshape(-1, 2)
+        out[f"{name}/digest"] = np.frombuffer(rf.digest(blob).encode(), np.uint8)
+        names.append(name)
+        outs[name], tiers[name] = got, tier
+        print(f"{name}: {fleet.n_pods} instances, {n_rows} rows, {len(meta['pairs'])} pairs")
+    for a, ra, b, rb in rf.rebalance_run_pairs():  # the same row of two runs one unit apart
+        assert tiers[a] == tiers[b] and not np.array_equal(rebalance_answer(tiers[a], outs[a], ra), rebalance_answer(tiers[b], outs[b], rb)), \
+            ("the reference answers a pair of runs alike", a, ra, b, rb)
+        seen[tiers[a]]["run_pairs"] += 1
+    for tier in rf.REBALANCE_EDGE_TIERS:
+        st = seen[tier]
+        assert st["sizes"] >= ({8, 64, 65} if tier != "plan" else {8, 64}), (tier, st["sizes"])
+        if tier != "plan":
+            assert st["lens"] >= {255, 256, 257}, (tier, sorted(st["lens"]))
+        print(f"tier {tier}: {st['cases']} cases, {st['rows']} rows, {st['pairs']} pairs of rows, {st['run_pairs']} pairs of runs; " +
+              ", ".join(f"{k}: {v}" for k, v in sorted(st["what"].items())))
+    w = seen["rate"]["what"]
+    assert all(w.get(k, 0) > 0 for k in ("none", "second copy", "scale-up", "heavy", "exit: timeDelta too short", "exit: fewer than two instances",
+                                         "overloaded instances", "counter resets")), w
+    w = seen["janitor"]["what"]
+    assert all(w.get(k, 0) > 0 for k in ("removed", "kept", "exit: shutting down")), w
+    w = seen["plan"]["what"]
+    assert all(w.get(k, 0) > 0 for k in ("loads", "runs without a load")), w
+    out["names"] = np.array(names)
+    out["run_pairs"] = np.array([f"{a}:{ra}:{b}:{rb}" for a, ra, b, rb in rf.rebalance_run_pairs()])
+    np.savez_compressed(REBALANCE_EDGE_OUT, **out)
+    print(f"wrote {REBALANCE_EDGE_OUT}: {os.path.getsize(REBALANCE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
@@ -269,6 +413,8 @@ def main():
         return gate_edge_vectors()
     if "--place-edges" in sys.argv[1:]:  # only the load-target edge cases
         return place_edge_vectors()
+    if "--rebalance-edges" in sys.argv[1:]:  # only the rebalancers' edge cases
+        return rebalance_edge_vectors()
     out = {}
     names = []
     for name, fleet, ids, reqs, extra in rf.place_cases():
@@ -434,6 +580,7 @@ def main():
     print(f"wrote {OUT}: {os.path.getsize(OUT) / 1e6:.2f} MB, {len(names)} cases")
     gate_edge_vectors()
     place_edge_vectors()
+    rebalance_edge_vectors()
 
 
 if __name__ == "__main__":

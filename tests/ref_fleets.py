@@ -1,4 +1,5 @@
-"""Fleets and requests of the reference-text vectors (tests/golden/ref_getnext.npz, ref_gate_edges.npz): built here, deterministically from
+"""Fleets and requests of the reference-text vectors (tests/golden/ref_getnext.npz, ref_gate_edges.npz, ref_place_edges.npz,
+ref_rebalance_edges.npz): built here, deterministically from
 seeds, so that the generator (oracle/ref_harness/make_ref_vectors.py — needs /root/reference) and the tests that consume
 the committed vectors (CPU: the oracle; GPU: the HIP path) construct byte-identical inputs.  A digest of the inputs is stored
 with the vectors and checked by the tests.
@@ -1624,6 +1625,772 @@ def proactive_cases():
             fleet.has_allowed, fleet.has_prefer = np.array([0, 1, 1], np.uint8), np.zeros(3, np.uint8)
             fleet.models["type"] = rng.integers(0, 3, fleet.n_models)
         yield f"proactive_parts_{seed}", fleet, string_ids(fleet, 95 + seed), 6400, True
+
+
+REBALANCE_EDGE_TIERS = ("rate", "janitor", "plan")
+LOAD_AGO = 45_000_000  # a copy loaded long ago (older than every cutoff of the rebalancers)
+ITER, MAX_AGE_ITERS, MIN_AGE_ITERS = 1000, 240, 42  # lower = 760, upper = 958: inside the entries' range
+RATE_THR = 2001  # * 3 is no multiple of 4: heavy = 1500
+
+
+class _RebRows:
+    """The cache entries of one run with the registry behind them: a registry row per entry unless `model=` names an earlier one.
+    loaded / failed: instances or (instance, time) pairs; the lists are stored in instance-id order, each time with its instance.
+    pairs: [(row a, row b, the engineered field or None)]: the reference must answer the two rows differently."""
+
+    def __init__(self, fleet):
+        self.fleet, self.models, self.ent, self.rows, self.conc, self.pairs = fleet, [], [], [], [], []
+
+    def model(self, loaded, failed=(), type=0, last_used=None):
+        rank, old = self.fleet.pods["id_order"], self.fleet.now - LOAD_AGO
+        norm = lambda xs: sorted(((int(x), old) if np.ndim(x) == 0 else (int(x[0]), int(x[1])) for x in xs), key=lambda x: rank[x[0]])  # noqa: E731
+        lp, fp = norm(loaded), norm(failed)
+        assert len({p for p, _ in lp}) == len(lp) and len({p for p, _ in fp}) == len(fp)
+        self.models.append((type, len(self.ent), len(lp), len(fp), self.fleet.now - 5_000 if last_used is None else last_used))
+        self.ent += lp + fp
+        return len(self.models) - 1
+
+    def add(self, loaded=(), failed=(), type=0, model=None, conc=None, **fields):
+        e = np.zeros(1, dtype=_lib.CACHE_ENTRY)
+        e["model"] = self.model(loaded, failed, type) if model is None else model
+        e["weight"], e["last_used"] = 6400, self.fleet.now - 4_000_000
+        for k, v in fields.items():
+            e[k] = v
+        c = np.zeros(1, dtype=_lib.CONC_ENTRY)
+        c["max_conc"] = 1
+        for k, v in (conc or {}).items():
+            c[k] = v
+        self.rows.append(e)
+        self.conc.append(c)
+        return len(self.rows) - 1
+
+    def both(self, field, a, b, **kw):
+        """Two rows that differ in `field` alone (a, then b), as a pair."""
+        i = self.add(**{**kw, field: a})
+        j = self.add(**{**kw, field: b})
+        self.pairs.append((i, j, field))
+        return i, j
+
+    def both_conc(self, field, a, b, conc, **kw):
+        i = self.add(conc={**conc, field: a}, **kw)
+        j = self.add(conc={**conc, field: b}, **kw)
+        self.pairs.append((i, j, "conc." + field))
+        return i, j
+
+    def pad(self, n, **kw):
+        """Plain rows up to n entries on the first registry rows (the 256-thread blocks of the per-entry kernels)."""
+        k = 0
+        while len(self.rows) < n:
+            self.add(model=k % len(self.models), interval_count=k % 7, **kw)
+            k += 1
+        assert len(self.rows) == n and len(self.models) <= 600
+
+    def done(self):
+        f = self.fleet
+        f.models = np.array(self.models, dtype=_lib.MODEL_ROW) if self.models else np.zeros(0, _lib.MODEL_ROW)
+        f.ent_pod = np.array([p for p, _ in self.ent], np.int32)
+        f.ent_time = np.array([t for _, t in self.ent], np.int64)
+        return np.concatenate(self.rows), np.concatenate(self.conc)
+
+
+def _scaleup_params(fleet, thr=RATE_THR, our_rpm=0, delta=60_000, lru_thr=72_000_000, self_pod=0):
+    """One run of the rate task: timeDelta 60 000 makes an entry's rpm its interval count."""
+    sp = np.zeros(1, dtype=_lib.SCALEUP_PARAMS)
+    sp["self_pod"], sp["iteration_counter"] = self_pod, ITER
+    sp["second_copy_max_age_iters"], sp["second_copy_min_age_iters"] = MAX_AGE_ITERS, MIN_AGE_ITERS
+    sp["scale_up_rpm_threshold"], sp["our_rpm"] = thr, our_rpm
+    sp["now"], sp["last_check_time"], sp["rate_check_interval_ms"] = fleet.now, fleet.now - delta, 10_000
+    sp["second_copy_lru_threshold_ms"], sp["assume_completed_ms"] = lru_thr, 30_000
+    return sp
+
+
+def _conc_params(dyn=540_000, avg=1.0):
+    cp = np.zeros(1, dtype=_lib.CONC_PARAMS)
+    cp["dynamic_rpm_scale_constant"], cp["average_model_parallelism"] = dyn, avg
+    return cp
+
+
+def _roomy(fleet):
+    """Every instance half empty, old and quiet: the second-copy rule's fullness clause holds, nobody is overloaded."""
+    p = fleet.pods
+    p["capacity"], p["used"], p["rpm"] = 1_000_000, 500_000, 0
+    p["lru_time"] = fleet.now - 3_000_000
+
+
+def _window_rows(R, others, type=0, **kw):
+    """The second-copy window (:5737-5744) on models with one copy, here: every edge of i1 / i2 against lower / upper."""
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    one = dict(loaded=[0], type=type, **kw)
+    R.both("last_used_iteration", lo - 1, lo, earlier_use_iteration=lo - 5, **one)
+    R.both("earlier_use_iteration", up, up + 1, last_used_iteration=up + 3, **one)
+    R.both("earlier_use_iteration", lo - 1, lo, last_used_iteration=up + 3, **one)
+    R.both("last_used_iteration", up, up + 1, earlier_use_iteration=lo - 5, **one)
+    combos = [R.add(earlier_use_iteration=a, last_used_iteration=b, **one) for a in (lo + 1, lo - 1) for b in (up - 1, up + 1)]
+    R.pairs += [(combos[0], combos[3], None), (combos[1], combos[3], None), (combos[2], combos[3], None), (combos[0], combos[1], None)]
+    # two copies: the rule is not applied, the markers stay
+    two = R.add(loaded=[0, others[0]], type=type, earlier_use_iteration=lo + 1, last_used_iteration=up - 1, **kw)
+    R.pairs.append((combos[0], two, None))
+    return combos
+
+
+def _rpm_rows(R, others, thr, type=0, **kw):
+    """heavy, scaleUp and the copies asked for, on models with two old copies (the second-copy rule is not reached)."""
+    heavy = _i32(thr * 3) // 4
+    two = dict(loaded=[0, others[0]], type=type, **kw)
+    R.both("interval_count", heavy, heavy + 1, **two)
+    R.both("interval_count", thr - 1, thr, **two)
+    R.both("interval_count", 2 * thr - 1, 2 * thr, **two)  # rpm / scaleUp 1 / 2 against many candidates
+    # ... against exactly two candidates: one below, equal, one above (equal and above are decided alike: no pair)
+    n = int(((R.fleet.pods["flags"] & 5) == 0).sum())
+    few = dict(loaded=[0, others[0]], failed=others[1:n - 3], type=type, **kw)
+    if n >= 6 and not type:
+        R.both("interval_count", 2 * thr - 1, 2 * thr, **few)
+        R.add(interval_count=3 * thr, **few)
+
+
+def _loaded_since_rows(R, others, sp, thr):
+    """loadedSince (:5860-5871) under the scale-up rule: the newest load on either side of recentLoadCutoff."""
+    now = int(sp["now"][0])
+    cut = now - (now - int(sp["last_check_time"][0]) + int(sp["rate_check_interval_ms"][0]) + 2 * int(sp["assume_completed_ms"][0]))
+    hot = dict(interval_count=thr)
+    a = R.add(loaded=[0, (others[0], cut)], **hot)
+    b = R.add(loaded=[0, (others[0], cut + 1)], **hot)
+    R.pairs.append((a, b, "ent_time"))
+    own = R.add(loaded=[(0, cut + 1), others[0]], **hot)  # the caller's own load is ignored
+    R.pairs.append((own, b, None))
+    fl = R.add(loaded=[0, others[0]], failed=[(others[1], cut + 1)], **hot)  # the failed list is not looked at
+    R.pairs.append((fl, b, None))
+    if len(others) >= 6:  # a list position >= 4
+        last = max(others[:5], key=lambda p: R.fleet.pods["id_order"][p])
+        rest = [p for p in others[:5] if p != last]
+        assert sum(R.fleet.pods["id_order"][p] < R.fleet.pods["id_order"][last] for p in [0] + rest) >= 4
+        a = R.add(loaded=[0] + rest + [(last, cut)], **hot)
+        b = R.add(loaded=[0] + rest + [(last, cut + 1)], **hot)
+        R.pairs.append((a, b, "ent_time"))
+
+
+def _rate_plain(P, seed, n_entries, latency=False):
+    """No type constraints: window, candidate count, rpm and loadedSince rows on a roomy cluster."""
+    fleet, rng = _edge_fleet(P, seed)
+    ids = string_ids(fleet, 500 + seed)
+    _roomy(fleet)
+    others = [int(p) for p in np.argsort(fleet.pods["id_order"]) if p != 0]
+    sp = _scaleup_params(fleet)
+    R = _RebRows(fleet)
+    _window_rows(R, others)
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    # candidateInstCount 0 / 1: suitable - (loaded + failed)
+    a = R.add(loaded=[0], failed=others[:P - 1], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    b = R.add(loaded=[0], failed=others[:P - 2], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    R.pairs.append((a, b, None))
+    R.add(model=-1, interval_count=RATE_THR)  # no registry record: heavy only
+    R.add(loaded=[], failed=[others[0]], interval_count=RATE_THR)  # no copy anywhere
+    _rpm_rows(R, others, RATE_THR)
+    _loaded_since_rows(R, others, sp, RATE_THR)
+    R.pad(n_entries)
+    entries, conc = R.done()
+    return fleet, ids, entries, (conc if latency else None), sp, (_conc_params() if latency else None), dict(pairs=R.pairs)
+
+
+# per-type stats of the fullness / lru case: (instances, what); type t + 1 <-> group t
+def _fullness_groups(P):
+    return [([1, 2], "10 * tf == tc"), ([3, 4], "10 * tf == tc - 1"), ([5], "one instance"), ([6, 7], "two instances"),
+            (list(range(8, 20)), "roomy"), (list(range(20, P)), "full")]
+
+
+def _rate_typed(P, seed, n_entries, lru_off, latency=False):
+    """Type constraints: the fullness clause 10 * tf / tc >= 1 on either side per type, the lru clause on either side per RUN
+    (lru_off: secondCopyLruThresholdMillis - (now - globalLru)), a type confined to one instance, a type row outside the table."""
+    groups = _fullness_groups(P)
+    fleet, rng = _edge_fleet(P, seed, [g for g, _ in groups])
+    ids = string_ids(fleet, 510 + seed)
+    pods, now = fleet.pods, fleet.now
+    pods["capacity"], pods["used"], pods["rpm"] = 1_000_000, 1_000_000, 0  # full everywhere but where a group says otherwise
+    pods["lru_time"] = now - rng.integers(400_000, 9_000_000, P)
+    pods["lru_time"][9] = now - 10_000_000  # globalLru
+    pods["used"][[1, 2]] = 900_000           # tc 2 000 000, tf 200 000
+    pods["capacity"][4] = 1_000_001          # tc 2 000 001, tf 200 000
+    pods["used"][3], pods["used"][4] = 900_000, 900_001
+    pods["used"][5], pods["used"][[6, 7]] = 500_000, 500_000
+    pods["used"][8:20] = 500_000
+    pods["used"][0] = 500_000
+    others = [int(p) for p in np.argsort(pods["id_order"]) if p != 0]
+    sp = _scaleup_params(fleet, lru_thr=10_000_000 + lru_off)
+    R = _RebRows(fleet)
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    inside = dict(loaded=[0], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    row = {what: R.add(type=t + 1, **inside) for t, (_, what) in enumerate(groups)}
+    if lru_off >= 0:  # (past the lru threshold every type gets its second copy)
+        R.pairs.append((row["10 * tf == tc"], row["10 * tf == tc - 1"], None))
+    R.pairs.append((row["one instance"], row["two instances"], None))
+    R.pairs.append((row["roomy"], row["full"], None) if lru_off >= 0 else (row["roomy"], row["one instance"], None))
+    R.add(type=len(groups) + 5, **inside)  # no such type row: the stats of row 0
+    R.add(type=-1, **inside)
+    R.add(type=0, **inside)
+    _window_rows(R, others, type=5)
+    _rpm_rows(R, others, RATE_THR, type=5)
+    R.pad(n_entries)
+    entries, conc = R.done()
+    return fleet, ids, entries, (conc if latency else None), sp, (_conc_params() if latency else None), \
+        dict(pairs=R.pairs, lru_rows=[row["10 * tf == tc - 1"], row["full"]])
+
+
+def _rate_suitable(P, seed, n_entries):
+    """copiesToLoad 2 / 3 against suitable / 3 for suitable 6 ... 12 (types confined to groups of that many instances)."""
+    sizes, groups, a = list(range(6, 13)), [], 1
+    for k in sizes:
+        groups.append(list(range(a, a + k)))
+        a += k
+    assert a <= P
+    fleet, rng = _edge_fleet(P, seed, groups)
+    ids = string_ids(fleet, 520 + seed)
+    _roomy(fleet)
+    sp = _scaleup_params(fleet)
+    R = _RebRows(fleet)
+    three = {}
+    for t, g in enumerate(groups):
+        R.add(loaded=[0, g[0]], type=t + 1, interval_count=2 * RATE_THR)
+        three[len(g)] = R.add(loaded=[0, g[0]], type=t + 1, interval_count=3 * RATE_THR)
+        R.add(loaded=[0, g[0]], type=t + 1, interval_count=5 * RATE_THR)
+    R.pairs.append((three[8], three[9], None))  # at 8 three copies become two
+    R.pad(n_entries)
+    entries, conc = R.done()
+    return fleet, ids, entries, None, sp, None, dict(pairs=R.pairs, suitable=sizes)
+
+
+WRAP_DELTAS = (6_000, 10_000, 12_345)
+
+
+def _rate_wrap(delta, seed=3):
+    """count * 60000 / timeDelta on either side of 2^31 (the narrowing turns it negative) at three timeDeltas; 5 999 ms: the run
+    returns before it looks at an entry (timeDelta * 5 < interval * 3)."""
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 530)
+    _roomy(fleet)
+    others = [int(p) for p in np.argsort(fleet.pods["id_order"]) if p != 0]
+    sp = _scaleup_params(fleet, delta=delta)
+    R = _RebRows(fleet)
+    for d in WRAP_DELTAS:
+        c = (2**31 * d - 1) // 60_000  # the largest count whose rpm stays below 2^31
+        assert c * 60_000 // d < 2**31 <= (c + 1) * 60_000 // d
+        R.both("interval_count", c, c + 1, loaded=[0, others[0]])
+        if d != delta:
+            R.pairs.pop()
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    R.add(loaded=[0], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    R.add(loaded=[0, others[0]], interval_count=RATE_THR * delta // 60_000 + 1)
+    entries, conc = R.done()
+    return fleet, ids, entries, None, sp, None, dict(pairs=R.pairs if delta != 5_999 else [])
+
+
+def _rate_exclude(P, which, seed=4):
+    """getExcludeSet (:5835-5856): instances at maxRpm and one above it, where 4 * thr is the larger term (a), where ourRpm - 2 * thr is
+    (b), where they are equal (c); the caller and a shutting-down instance far above; models whose candidates it leaves 0 / 1 of."""
+    thr, our = 100, dict(a=0, b=1_000, c=600)[which]
+    max_rpm = max(4 * thr, our - 2 * thr)
+    fleet, rng = _edge_fleet(P, seed)
+    ids = string_ids(fleet, 540 + P)
+    _roomy(fleet)
+    pods = fleet.pods
+    at, over = [1] + ([62] if P > 8 else []), [2] + ([63] if P > 8 else []) + ([64] if P > 64 else [])
+    pods["rpm"][at], pods["rpm"][over] = max_rpm, max_rpm + 1
+    pods["rpm"][0], pods["rpm"][3], pods["flags"][3] = 10**9, 10**9, 1
+    S, k = P - 1, len(over)
+    free = [p for p in range(4, P) if p not in at + over]
+    sp = _scaleup_params(fleet, thr=thr, our_rpm=our)
+    R = _RebRows(fleet)
+    hot = dict(interval_count=thr)
+    # the excluded instances in neither list: candidates - k - k
+    a = R.add(loaded=[0, free[0]], failed=free[1:1 + S - 2 - 2 * k], **hot)
+    b = R.add(loaded=[0, free[0]], failed=free[1:1 + S - 2 - 2 * k - 1], **hot)
+    R.pairs.append((a, b, None))
+    # in the loaded list, in the failed list: candidates - k
+    for where in ("loaded", "failed"):
+        n_fail = S - 1 - k - k  # candidates before: k
+        lists = dict(loaded=[0] + over, failed=free[:n_fail]) if where == "loaded" else dict(loaded=[0], failed=over + free[:n_fail])
+        a = R.add(**lists, last_used_iteration=1, **hot)
+        lists["failed"] = lists["failed"][:-1]
+        b = R.add(**lists, last_used_iteration=1, **hot)
+        R.pairs.append((a, b, None))
+    R.add(loaded=[0, free[0]], interval_count=3 * thr)
+    entries, conc = R.done()
+    return fleet, ids, entries, None, sp, None, dict(pairs=R.pairs, overloaded=over)
+
+
+def _rate_count(n_live, seed=5):
+    """clusterStats.instanceCount 1 / 2 (:5658): the run with one instance returns early."""
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 550)
+    _roomy(fleet)
+    fleet.pods["flags"][n_live:] = 1
+    R = _RebRows(fleet)
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    R.add(loaded=[0], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    R.add(loaded=[0], interval_count=RATE_THR, last_used_iteration=1)
+    entries, conc = R.done()
+    return fleet, ids, entries, None, _scaleup_params(fleet), None, dict(pairs=[])
+
+
+def _rate_nolru(with_lru, seed=9):
+    """A full cluster (10 * tf < tc) in which no instance has an lru: globalLru is Long.MAX_VALUE and now - globalLru wraps negative, so the
+    lru clause does not fire either; the same table with one instance 80 000 000 ms old: it does."""
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 555)
+    p = fleet.pods
+    p["capacity"], p["used"], p["rpm"], p["lru_time"] = 1_000_000, 1_000_000, 0, 0
+    if with_lru:
+        p["lru_time"][1] = fleet.now - 80_000_000
+    R = _RebRows(fleet)
+    lo, up = ITER - MAX_AGE_ITERS, ITER - MIN_AGE_ITERS
+    R.add(loaded=[0], earlier_use_iteration=lo + 1, last_used_iteration=up - 1)
+    R.add(loaded=[0, 1], interval_count=RATE_THR)
+    entries, conc = R.done()
+    return fleet, ids, entries, None, _scaleup_params(fleet), None, dict(pairs=[])
+
+
+def _cts(count, per_call=100):
+    return (count * per_call) * (1 << _lib.CONC_COUNT_BITS) + count
+
+
+def _rate_conc(seed=6):
+    """getRpmScaleThreshold(true) (:2766-2796): counts 63 / 64 and 7 / 8 with priorCount 0, 1, -1; timeSum 0 (Integer.MAX_VALUE, whose
+    * 3 wraps to a heavy limit of 536 870 911); rpm on either side of a computed threshold."""
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 560)
+    _roomy(fleet)
+    others = [int(p) for p in np.argsort(fleet.pods["id_order"]) if p != 0]
+    R = _RebRows(fleet)
+    two = dict(loaded=[0, others[0]])
+    for pc, ps in ((0, 0), (1, 7), (-1, 7)):
+        for lo_c, hi_c in ((63, 64), (7, 8)):
+            i = R.add(conc=dict(count_and_time_sum=_cts(lo_c), prior_count=pc, prior_sum=ps), interval_count=3_000, **two)
+            j = R.add(conc=dict(count_and_time_sum=_cts(hi_c), prior_count=pc, prior_sum=ps), interval_count=3_000, **two)
+            R.pairs.append((i, j, "conc.count_and_time_sum"))
+    R.both("interval_count", 536_870_911, 536_870_912, conc=dict(count_and_time_sum=64), **two)
+    R.both("interval_count", 536_870_911, 536_870_912, conc=dict(count_and_time_sum=3, prior_count=9), **two)
+    # 64 calls of 10 ms, one at a time: 64 * 540 000 / 6 400 = 5 400
+    R.both("interval_count", 5_399, 5_400, conc=dict(count_and_time_sum=_cts(64)), **two)
+    R.both("interval_count", 4_050, 4_051, conc=dict(count_and_time_sum=_cts(64)), **two)  # its heavy limit
+    R.both("interval_count", 21_599, 21_600, conc=dict(count_and_time_sum=_cts(64), max_conc=4), **two)
+    entries, conc = R.done()
+    return fleet, ids, entries, conc, _scaleup_params(fleet), _conc_params(), dict(pairs=R.pairs)
+
+
+def _rate_conc_wrap(seed=7):
+    """A threshold's quotient on either side of 2^31: 64 * 2^26 / timeSum at timeSum 2 (2^31: the narrowing gives Integer.MIN_VALUE) and 3."""
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 570)
+    _roomy(fleet)
+    others = [int(p) for p in np.argsort(fleet.pods["id_order"]) if p != 0]
+    R = _RebRows(fleet)
+    for cnt in (10, 3_000):
+        i = R.add(loaded=[0, others[0]], interval_count=cnt, conc=dict(count_and_time_sum=(2 << _lib.CONC_COUNT_BITS) + 64))
+        j = R.add(loaded=[0, others[0]], interval_count=cnt, conc=dict(count_and_time_sum=(3 << _lib.CONC_COUNT_BITS) + 64))
+        R.pairs.append((i, j, "conc.count_and_time_sum"))
+    entries, conc = R.done()
+    return fleet, ids, entries, conc, _scaleup_params(fleet), _conc_params(dyn=2**26), dict(pairs=R.pairs)
+
+
+AVG_BELOW, AVG_AT, AVG_BEYOND = 2147483646.5 / 900.0, 2147483647.5 / 900.0, 1.0e7
+
+
+def _rate_conc_avg(avg, seed=8):
+    """getExcludeSet's own threshold (int) (900.0 * averageModelParallelism) (:5836) at 2^31 - 2, saturated at 2^31 - 1, and far beyond:
+    maxRpm is ourRpm + 4 / ourRpm + 2, an instance at ourRpm + 3 is excluded or not.  Every entry's maxConc is 0: the run's new
+    averageModelParallelism is max(1.0, 0 / n) = 1.0."""
+    assert int(900.0 * AVG_BELOW) == 2**31 - 2 and 900.0 * AVG_AT >= 2147483647.0
+    our = 1_000
+    fleet, rng = _edge_fleet(8, seed)
+    ids = string_ids(fleet, 580)
+    _roomy(fleet)
+    fleet.pods["rpm"][[1, 2, 3]] = [our + 2, our + 3, our + 5]
+    R = _RebRows(fleet)
+    hot = dict(interval_count=100, conc=dict(max_conc=0))
+    # 8 instances: candidates before 4 and 3; excluded {3} or {2, 3}, none of them held
+    R.add(loaded=[0, 4], failed=[5, 6], **hot)
+    R.add(loaded=[0, 4], failed=[5, 6, 7], **hot)
+    R.add(loaded=[0, 4], **hot)
+    entries, conc = R.done()
+    return fleet, ids, entries, conc, _scaleup_params(fleet, thr=100, our_rpm=our), _conc_params(avg=avg), dict(pairs=[])
+
+
+@functools.lru_cache(maxsize=None)
+def _rate_edge_all():
+    out = {}
+    out["edge_rate_plain_8"] = _rate_plain(8, 0, 255)
+    out["edge_rate_plain_64"] = _rate_plain(64, 1, 256)
+    out["edge_rate_plainconc_65"] = _rate_plain(65, 2, 257, latency=True)
+    out["edge_rate_typed_65_at"] = _rate_typed(65, 0, 257, 0)
+    out["edge_rate_typed_65_over"] = _rate_typed(65, 0, 257, -1)
+    out["edge_rate_typedconc_64_at"] = _rate_typed(64, 1, 120, 0, latency=True)
+    out["edge_rate_suitable_64"] = _rate_suitable(64, 2, 256)
+    for d in (5_999,) + WRAP_DELTAS:
+        out[f"edge_rate_wrap_8_{d}"] = _rate_wrap(d)
+    out["edge_rate_exclude_8_a"] = _rate_exclude(8, "a")
+    out["edge_rate_exclude_64_b"] = _rate_exclude(64, "b")
+    out["edge_rate_exclude_65_c"] = _rate_exclude(65, "c")
+    out["edge_rate_count_8_1"], out["edge_rate_count_8_2"] = _rate_count(1), _rate_count(2)
+    out["edge_rate_nolru_8_none"], out["edge_rate_nolru_8_old"] = _rate_nolru(False), _rate_nolru(True)
+    out["edge_rate_conc_8"] = _rate_conc()
+    out["edge_rate_concwrap_8"] = _rate_conc_wrap()
+    for k, avg in (("below", AVG_BELOW), ("at", AVG_AT), ("beyond", AVG_BEYOND)):
+        out[f"edge_rate_concavg_8_{k}"] = _rate_conc_avg(avg)
+    return out
+
+
+# pairs of RUNS: (case a, row a, case b, row b): the same row of two runs that differ in one parameter or one table value by one unit
+# (row -1: the whole run — one of the two returns early)
+def rate_run_pairs():
+    c = _rate_edge_all()
+    out = [("edge_rate_typed_65_at", r, "edge_rate_typed_65_over", r) for r in c["edge_rate_typed_65_at"][6]["lru_rows"]]
+    out += [("edge_rate_wrap_8_5999", -1, "edge_rate_wrap_8_6000", -1), ("edge_rate_count_8_1", -1, "edge_rate_count_8_2", -1)]
+    out += [("edge_rate_concavg_8_below", 0, "edge_rate_concavg_8_at", 0)]
+    out += [("edge_rate_nolru_8_none", 0, "edge_rate_nolru_8_old", 0)]
+    return out
+
+
+def _scaledown_params(fleet, self_pod, thr=2000, cap=10**9, since=60_000, sd=0):
+    """One janitor pass: timeSinceLastCheck 60 000 makes a candidate's rpm its interval count."""
+    dp = np.zeros(1, dtype=_lib.SCALEDOWN_PARAMS)
+    dp["self_pod"], dp["shutting_down"], dp["now"] = self_pod, sd, fleet.now
+    dp["last_check_time"], dp["rate_check_interval_ms"] = fleet.now - since, 10_000
+    dp["adjusted_cache_capacity"], dp["scale_up_rpm_threshold"] = cap, thr
+    return dp
+
+
+def _janitor_fleet(P, seed, glru, now=None):
+    """A full cluster (tf == 0: the janitor goes on) whose oldest lru is glru; the caller in the middle of PLACEMENT_ORDER, a live
+    instance before and one behind it, one shutting down and one gone.  -> (fleet, ids, caller, before, behind, down, gone)"""
+    fleet, rng = _edge_fleet(P, seed)
+    if now is not None:
+        fleet.now = now
+    ids = string_ids(fleet, 600 + seed)
+    p = fleet.pods
+    p["capacity"], p["used"], p["rpm"] = 1_000_000, 1_000_000, 0
+    p["lru_time"] = glru + rng.permutation(P) * 1_000 + 1_000
+    p["lru_time"][2] = glru
+    down, gone = P - 1, P - 2
+    p["flags"][down], p["flags"][gone] = 1, 4
+    order = [int(x) for x in cluster_order(fleet)]
+    assert len(order) == P - 2
+    return fleet, ids, order[len(order) // 2], order[0], order[-1], down, gone
+
+
+def _two_copy_rows(R, now, cache_age, S, before):
+    """removeSecondModelCopy's age (:6240-6262): cacheAge / 10, capped at ten hours when the model was not heavy lately."""
+    sda_u, fifth = cache_age // 10, cache_age // 5
+    sda_c = min(36_000_000, sda_u)
+    two = dict(loaded=[S, before])
+    out = []
+    for lh in (0, now - (fifth - 1)):  # the cap applies
+        out.append(R.both("last_used", now - sda_c, now - (sda_c + 1), last_heavy_time=lh, **two))
+    out.append(R.both("last_used", now - sda_u, now - (sda_u + 1), last_heavy_time=now - fifth, **two))  # ... and does not
+    if sda_u > sda_c:
+        R.both("last_heavy_time", now - fifth, now - (fifth - 1), last_used=now - (sda_c + 1), **two)
+    return out
+
+
+def _janitor_two(P, seed, cache_age, n_entries=0, self_flags=2):
+    fleet, ids, S, before, behind, down, gone = _janitor_fleet(P, seed, wl.NOW_MS - cache_age)
+    now = fleet.now
+    R = _RebRows(fleet)
+    _two_copy_rows(R, now, cache_age, S, before)
+    old = dict(last_used=now - cache_age)
+    a = R.add(loaded=[S, before], **old)   # the other copy before the caller in the order: ours goes
+    b = R.add(loaded=[S, behind], **old)   # ... behind it: ours stays
+    R.pairs.append((a, b, None))
+    for other in (down, gone):             # no other live copy
+        R.pairs.append((a, R.add(loaded=[S, other], **old), None))
+    R.add(loaded=[S], **old)
+    R.add(loaded=[S, before], last_used=0)
+    R.add(model=-1, **old)
+    R.add(loaded=[behind, before, S], **old)  # three copies: the other rule
+    R.pad(n_entries or len(R.rows), last_used=now - 1_000)
+    fleet.pods["flags"][S] = self_flags
+    entries, conc = R.done()
+    return fleet, ids, entries, None, _scaledown_params(fleet, S), 0, \
+        dict(pairs=R.pairs if self_flags == 2 else [], cache_age=cache_age, order_row=a)
+
+
+def min_age_of(glru):
+    """minAgeMs as removeModelCopies computes it (:6277-6283: the ABSOLUTE lru, quirk B#13) -> (the quotient, the clamped value)"""
+    q = _tdiv(_i64(_i64(3 * glru) + 10_400_000), 100)
+    return q, min(max(q, 600_000), 18_000_000)
+
+
+# globalLru values near the epoch, by the quotient (3 * globalLru + 10 400 000) / 100 they give
+MIN_AGE_LRUS = {"599999": 16_533_333, "600000": 16_533_334, "600001": 16_533_367, "mid": 100_000_000, "17999999": 596_533_333,
+                "18000000": 596_533_334, "18000001": 596_533_367}
+JANITOR_COUNTS = (0, 1, 2, 3, 66, 67, 1333, 1334, 3600, 3601)
+
+
+def _janitor_three(P, seed, glru, thr=2000, since=60_000, latency=False, n_entries=0):
+    """Three copies (:6264-6306) under a clock near the epoch: lastUnloadTime, a recent load, minAgeMs in its three bands, the rpm rule."""
+    fleet, ids, S, before, behind, down, gone = _janitor_fleet(P, seed, glru, now=glru + 50_000_000)
+    now = fleet.now
+    q, m = min_age_of(glru)
+    R = _RebRows(fleet)
+    three = dict(loaded=[S, before, behind])
+    R.both("last_heavy_time", now - (m - 1), now - m, **three)
+    R.add(last_heavy_time=0, **three)
+    R.both("last_unload_time", now - 79_999, now - 80_000, **three)
+    a = R.add(loaded=[S, (before, now - 1_800_000), behind])
+    b = R.add(loaded=[S, (before, now - 1_800_000 + 1), behind])
+    R.pairs.append((a, b, "ent_time"))
+    R.pairs.append((a, R.add(loaded=[(S, now - 1_800_000 + 1), before, behind]), None))  # the caller's own load counts
+    rows = {c: R.add(interval_count=c, **three) for c in JANITOR_COUNTS}
+    lim = (thr * 2) // 3
+    if since == 60_000 and not latency:
+        R.pairs.append((rows[lim], rows[lim + 1], "interval_count"))
+    if latency:  # 64 calls of 10 ms: 5 400, two thirds of it 3 600; no samples: scaleUpRpmThreshold
+        busy = dict(count_and_time_sum=_cts(64))
+        R.both("interval_count", 3_600, 3_601, conc=busy, **three)
+        R.both("interval_count", lim, lim + 1, conc=dict(count_and_time_sum=7), **three)
+        R.both_conc("queued_requests", 1, 2, {}, **three)
+    R.pad(n_entries or len(R.rows), last_used=now - 1_000)
+    entries, conc = R.done()
+    return fleet, ids, entries, (conc if latency else None), _scaledown_params(fleet, S, thr=thr, since=since), 540_000, \
+        dict(pairs=R.pairs if since >= 1_000 else [], min_age=(q, m), go_row=2)  # (a sample period too short refuses every row)
+
+
+def _janitor_budget(entries_spec, cap, sd=0, pairs=()):
+    """The serial allowance (:6117-6135) over two-copy candidates that removeModelCopies takes (True) or refuses (False)."""
+    cache_age = 100_000_000
+    fleet, ids, S, before, behind, down, gone = _janitor_fleet(8, 9, wl.NOW_MS - cache_age)
+    R = _RebRows(fleet)
+    for i, (w, takes) in enumerate(entries_spec):  # oldest first, no two alike: as scaleCopiesCandidates hands them over; refused: the other
+        # copy stands behind the caller in the order
+        R.add(loaded=[S, before if takes else behind], weight=w, last_used=fleet.now - cache_age - 1_000 * (len(entries_spec) - i))
+    entries, conc = R.done()
+    return fleet, ids, entries, None, _scaledown_params(fleet, S, cap=cap, sd=sd), 0, dict(pairs=list(pairs))
+
+
+BUDGET_EXACT = ((60_000, True), (40_001, True), (30_000, False), (40_000, True), (1, True))  # allowance 100 000: rows 0 and 3 go
+BUDGET_NEGATIVE = ((100_001, True), (1, True), (0, True))  # the first goes whatever it weighs; the allowance is then -1
+BUDGET_SMALL = ((1, True), (0, True), (1, True))  # allowance 0 / 1 / 1 / 2 at capacities 19 / 20 / 39 / 40
+
+
+def _janitor_full(extra, tf):
+    """instanceSetStats() on either side of tf * 100 / tc > 5 (:6229): tc = 8 000 000 + extra over six live instances, all of tf on one."""
+    fleet, ids, S, before, behind, down, gone = _janitor_fleet(8, 10, wl.NOW_MS - 100_000_000)
+    p = fleet.pods
+    live = [i for i in range(8) if i not in (down, gone)]
+    p["capacity"][live] = [1_333_334, 1_333_334, 1_333_333, 1_333_333, 1_333_333, 1_333_333]
+    p["used"][live] = p["capacity"][live]
+    p["capacity"][live[0]] += extra
+    p["used"][live[0]] = p["capacity"][live[0]] - tf
+    assert int(p["capacity"][live].sum()) == 8_000_000 + extra
+    order = [int(x) for x in cluster_order(fleet)]  # (the instance with room moves in the order)
+    S, before, behind = order[len(order) // 2], order[0], order[-1]
+    R = _RebRows(fleet)
+    R.add(loaded=[S, before], last_used=fleet.now - 100_000_000)
+    R.add(loaded=[S, before, behind])
+    entries, conc = R.done()
+    return fleet, ids, entries, None, _scaledown_params(fleet, S), 0, dict(pairs=[], totals=(8_000_000 + extra, tf))
+
+
+@functools.lru_cache(maxsize=None)
+def _janitor_edge_all():
+    out = {}
+    out["edge_janitor_two_8_low"] = _janitor_two(8, 0, 100_000_000, 255)
+    out["edge_janitor_two_64_at"] = _janitor_two(64, 1, 360_000_000, 256)
+    out["edge_janitor_two_65_at1"] = _janitor_two(65, 2, 360_000_010, 257)
+    out["edge_janitor_two_8_far"] = _janitor_two(8, 3, 2_000_000_000)
+    out["edge_janitor_two_8_selfdown"] = _janitor_two(8, 0, 100_000_000, 255, self_flags=1)
+    out["edge_janitor_two_8_selfgone"] = _janitor_two(8, 0, 100_000_000, 255, self_flags=4)
+    for k, g in MIN_AGE_LRUS.items():
+        out[f"edge_janitor_three_8_{k}"] = _janitor_three(8, 4, g)
+    out["edge_janitor_three_65_mid"] = _janitor_three(65, 5, MIN_AGE_LRUS["mid"], n_entries=257)
+    for thr in (1, 2, 3, 100):
+        out[f"edge_janitor_thr_8_{thr}"] = _janitor_three(8, 4, MIN_AGE_LRUS["mid"], thr=thr)
+    for since in (999, 1_000):
+        out[f"edge_janitor_since_8_{since}"] = _janitor_three(8, 4, MIN_AGE_LRUS["mid"], since=since)
+    out["edge_janitor_conc_8"] = _janitor_three(8, 4, MIN_AGE_LRUS["mid"], latency=True)
+    out["edge_janitor_budget_8_exact"] = _janitor_budget(BUDGET_EXACT, 2_000_000, pairs=[(1, 3, "weight")])
+    out["edge_janitor_budget_8_down"] = _janitor_budget(BUDGET_EXACT, 2_000_000, sd=1)
+    out["edge_janitor_budget_8_negative"] = _janitor_budget(BUDGET_NEGATIVE, 2_000_000, pairs=[(0, 1, None)])
+    for cap in (19, 20, 39, 40):
+        out[f"edge_janitor_budget_8_{cap}"] = _janitor_budget(BUDGET_SMALL, cap)
+    # 6 * tc - 1 is odd and tf * 100 even: the nearest a table can come from below is 6 * tc - 2 (tc = 8 000 017)
+    out["edge_janitor_full_8_below"] = _janitor_full(17, 480_001)   # tf * 100 == 6 * tc - 2: goes on
+    out["edge_janitor_full_8_above"] = _janitor_full(17, 480_002)   # one unit more: refuses everything
+    out["edge_janitor_full_8_under"] = _janitor_full(0, 479_999)    # tf * 100 == 6 * tc - 100: goes on
+    out["edge_janitor_full_8_equal"] = _janitor_full(0, 480_000)    # tf * 100 == 6 * tc: refuses everything
+    return out
+
+
+def janitor_run_pairs():
+    j = "edge_janitor_"
+    r = _janitor_edge_all()[j + "two_8_low"][6]["order_row"]
+    out = [(j + "two_8_low", r, j + "two_8_" + k, r) for k in ("selfdown", "selfgone")]  # the caller shutting down / not in the table
+    out += [(j + "since_8_999", 2, j + "since_8_1000", 2), (j + "budget_8_exact", 0, j + "budget_8_down", 0)]
+    out += [(j + "budget_8_19", 1, j + "budget_8_20", 1), (j + "budget_8_39", 2, j + "budget_8_40", 2)]
+    out += [(j + "full_8_below", r, j + "full_8_above", r) for r in (0, 1)] + [(j + "full_8_under", r, j + "full_8_equal", r) for r in (0, 1)]
+    return out
+
+
+def plan_cutoff(now, lru_age):
+    """proactiveLastUsedCutoff (:6657-6664) of a cluster whose globalLru is now - lru_age (None: no lru)"""
+    return 0 if lru_age is None else now - lru_age + max(lru_age // 3, 1_200_000)
+
+
+def _plan_case(seed, units, pods, copies, lru_age, models, groups=(), types=None, pairs=()):
+    """pods: per instance (capacity, used, loadingThreads, loadingInProgress); copies: modelCopyCount, on the first instance (of every
+    group); lru_age: now - globalLru (None: no instance has an lru); models: [(lastUsed, n_failed)], unloaded, in registry order.
+    minSpaceUnits is 1, so that a single free unit counts into totalFree."""
+    P = len(pods)
+    fleet, rng = _edge_fleet(P, seed, groups)
+    fleet.min_space_units = 1
+    ids = string_ids(fleet, 700 + seed)
+    p, now = fleet.pods, fleet.now
+    for i, (c, u, t, ip) in enumerate(pods):
+        p["capacity"][i], p["used"][i], p["loading_threads"][i], p["loading_in_progress"][i] = c, u, t, ip
+    p["count"] = 0
+    for g in (groups or [range(P)]):
+        p["count"][list(g)[0]] = copies
+    p["lru_time"] = 2**63 - 1 if lru_age is None else now - lru_age + 1_000 + np.arange(P) * 1_000
+    if lru_age is not None:
+        p["lru_time"][0] = now - lru_age
+    rows = np.zeros(len(models), dtype=_lib.MODEL_ROW)
+    ent = []
+    for i, (lu, nf) in enumerate(models):
+        rows[i] = (0 if types is None else types[i], len(ent), 0, nf, lu)
+        ent += sorted(range(nf), key=lambda q: p["id_order"][q])
+    fleet.models, fleet.ent_pod = rows, np.array(ent, np.int32)
+    fleet.ent_time = np.full(len(ent), now - 3_000_000, np.int64)
+    return fleet, ids, units, bool(groups), dict(pairs=list(pairs))
+
+
+QUIET = (1_000_000, 500_000, 0, 0)  # room, but no loading thread: it adds nothing to spaceToFill
+TINY = (8, 8, 0, 0)
+NARROW_A = (2**30, 7 * 2**27 - 7, 8, 0)  # avail 7
+
+
+def _narrow_pods(total_used):
+    """Eight instances of 2^30 units whose `used` sums to total_used (nothing full but exactly-full ones: tc - tf == total_used); only the
+    first can load."""
+    rest, out = total_used - NARROW_A[1], [NARROW_A]
+    for _ in range(7):
+        u = min(rest, 2**30)
+        out.append((2**30, u, 0, 0))
+        rest -= u
+    assert rest == 0
+    return out
+
+
+def _below(now, lru_age, n):
+    """n distinct candidates older than the cutoff: loaded only as far as freeSpaceProactiveLoadCount reaches"""
+    return [(plan_cutoff(now, lru_age) - 1_000_000 - 1_000 * i, 0) for i in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def _plan_edge_all():
+    now, age = wl.NOW_MS, 9_000_000
+    cut = plan_cutoff(now, age)
+    out = {}
+    # sizeEstimate: modelCopyCount 2 / 3 and 10 / 11 (tc - tf = 4 000 000)
+    a_pods = [(4_000_000, 2_000_000, 8, 0)] + [QUIET] * 4 + [(1_000_000, 0, 0, 0)] * 3
+    for c in (2, 3, 10, 11):
+        out[f"edge_plan_copies_8_{c}"] = _plan_case(0, 6400, a_pods, c, age, _below(now, age, 130))
+    # (int) (tc - tf) binds before the division
+    for name, used, c, units in (("2p31m1", 2**31 - 1, 11, 6400), ("2p31", 2**31, 11, 6400), ("2p32m1", 2**32 - 1, 5, 6401), ("2p32", 2**32, 5, 6401),
+                                 ("2p32p4", 2**32 + 4, 5, 3), ("2p32p5", 2**32 + 5, 5, 3)):
+        out[f"edge_plan_narrow_8_{name}"] = _plan_case(1, units, _narrow_pods(used), c, age, _below(now, age, 12))
+    # spaceToFill at sizeEstimate 1: the first instance gives k, the second the engineered term
+    sp = lambda k, v: [(1_000_000, 0, 1, 50 - k), v] + [QUIET] * 6  # noqa: E731
+    odd = 1_000_003  # / 8 = 125 000
+    for name, k, v, units in (("maxloads0", 1, (1_000_000, 0, 1, 50), 1), ("maxloads1", 1, (1_000_000, 0, 1, 49), 1),
+                              ("avail0", 3, (odd, odd - 125_000, 8, 0), 1), ("avail1", 3, (odd, odd - 125_001, 8, 0), 1),
+                              ("over", 3, (odd, odd + 5, 8, 0), 1),
+                              ("by2", 3, (odd, odd - 125_002, 1, 47), 1), ("by3", 3, (odd, odd - 125_003, 1, 47), 1),
+                              ("by4", 3, (odd, odd - 125_004, 1, 47), 1),
+                              ("wrap1", 3, (1_000_000, 0, 1, 49), 2**30), ("wrap2", 3, (1_000_000, 0, 1, 48), 2**30)):
+        out[f"edge_plan_space_8_{name}"] = _plan_case(2, units, sp(k, v), 2, age, _below(now, age, 12))
+    # freeSpaceProactiveLoadCount below, at and above totalCapacity / (20 * sizeEstimate) = 10
+    for avail in (19, 20, 21, 22):
+        out[f"edge_plan_count_8_{avail}"] = _plan_case(3, 1, [(160, 140 - avail, 8, 0)] + [TINY] * 7, 2, age, _below(now, age, 14))
+    # the gate: totalFree 0 / 1, totalCapacity 0 / 1
+    full = (1_000_000, 1_000_000, 0, 0)
+    gate_models = [(cut + 5, 0), (now - age, 1), (now - age + 1, 1), (now - age + 1, 2)]  # the registry rule lastUsed > globalLru
+    out["edge_plan_gate_8_tf0"] = _plan_case(4, 100, [full] * 8, 2, age, gate_models)
+    out["edge_plan_gate_8_tf1"] = _plan_case(4, 100, [(1_000_000, 999_999, 0, 0)] + [full] * 7, 2, age, gate_models)
+    out["edge_plan_gate_8_tc0"] = _plan_case(4, 100, [(0, 0, 0, 0)] * 8, 2, age, gate_models)
+    out["edge_plan_gate_8_tc1"] = _plan_case(4, 100, [(1, 0, 0, 0)] + [(0, 0, 0, 0)] * 7, 2, age, gate_models)
+    # the cutoff: age / 3 on either side of 1 200 000, no lru at all; candidates at cutoff - 1, cutoff, cutoff + 1
+    for name, a in (("1199999", 3_599_999), ("1200000", 3_600_000), ("1200001", 3_600_003), ("nolru", None)):
+        c = plan_cutoff(now, a)
+        ms = [(c - 1, 0), (c, 0), (c + 1, 0), (c + 5, 1), (c + 6, 2)]
+        out[f"edge_plan_cutoff_8_{name}"] = _plan_case(5, 6400, [QUIET] * 8, 2, a, ms, pairs=[(1, 2, "last_used"), (3, 4, None)])  # (3, 4): one / two failures
+    # ... with one free-space load: the first is taken whatever its age, the second must be >= cutoff
+    out["edge_plan_cutoff_8_free1"] = _plan_case(5, 6400, [QUIET, (1_000_000, 0, 1, 48)] + [QUIET] * 6, 2, age,
+                                                 [(cut - 1, 0), (cut + 1, 0), (cut, 0)], pairs=[(2, 0, "last_used")])
+    # the TreeSet: exactly totalProactiveLoadCount (3) distinct candidates, and one more; ties are dropped, set full or not
+    x = cut + 10
+    set3 = [(x + 3, 0), (x + 2, 0), (x + 2, 0), (x + 1, 0)]
+    small = [(600, 0, 0, 0)] + [TINY] * 7
+    out["edge_plan_set_8_3"] = _plan_case(6, 10, small, 2, age, set3, pairs=[(1, 2, None)])
+    out["edge_plan_set_8_4"] = _plan_case(6, 10, small, 2, age, set3 + [(x + 1, 0), (x, 0)], pairs=[(1, 2, None), (3, 4, None), (3, 5, "last_used")])
+    # per partition: eight groups of eight instances, each one of the tables above; its models carry the group's type
+    blocks = [a_pods, a_pods, sp(1, (1_000_000, 0, 1, 49)), sp(3, (odd, odd - 125_003, 1, 47)), [QUIET, (1_000_000, 0, 1, 48)] + [QUIET] * 6,
+              small, [(160, 120, 8, 0)] + [TINY] * 7, [QUIET] * 8]
+    pods = [r for b in blocks for r in b]
+    models, types = [], []
+    for k in range(8):
+        models += [(cut - 5 + i, i % 3 == 2 and 2 or 0) for i in range(20)] + [(cut - 2_000_000 - 1_000 * i - k, 0) for i in range(20)]
+        types += [k + 1] * 40
+    models += [(cut + 100 + i, 0) for i in range(5)]
+    types += [0, 99, -1, 0, 0]
+    out["edge_plan_parts_64"] = _plan_case(7, 6400, pods, 3, age, models, groups=[list(range(8 * k, 8 * k + 8)) for k in range(8)], types=types)
+    return out
+
+
+def plan_run_pairs():
+    p = "edge_plan_"
+    names = [("copies_8_2", "copies_8_3"), ("copies_8_10", "copies_8_11"), ("narrow_8_2p31m1", "narrow_8_2p31"), ("narrow_8_2p32p4", "narrow_8_2p32p5"),
+             ("space_8_maxloads0", "space_8_maxloads1"), ("space_8_avail0", "space_8_avail1"), ("space_8_by2", "space_8_by3"),
+             ("count_8_19", "count_8_20"), ("count_8_21", "count_8_22"), ("gate_8_tf0", "gate_8_tf1"),
+             ("cutoff_8_1199999", "cutoff_8_1200000")]
+    return [(p + a, -1, p + b, -1) for a, b in names]
+
+
+def rebalance_edge_tier(name):
+    return name.split("_")[1]
+
+
+def rebalance_edge_cases():
+    """(name, tier, case): the rebalancers at the edges of their value domain, names edge_<tier>_<case>.
+    rate: (fleet, ids, entries, conc | None, scaleup params, conc params | None, meta) — the rate-tracking task (:5636-5856);
+    janitor: (fleet, ids, entries, conc | None, scaledown params, dynamicRpmScaleConstant, meta) — the scale-down (:6110-6335);
+    plan: (fleet, ids, defaultModelSizeUnits, partitioned, meta) — the reaper's proactive loads (:6616-6747).
+    meta["pairs"]: two rows (cache entries; registry rows for the plan) on either side of one threshold, (a, b, engineered field or None)."""
+    for tier, cases in (("rate", _rate_edge_all()), ("janitor", _janitor_edge_all()), ("plan", _plan_edge_all())):
+        for name, case in cases.items():
+            yield name, tier, case
+
+
+def rebalance_run_pairs():
+    """(case a, row a, case b, row b): the same row of two RUNS that differ by one unit in one parameter or one table value (row -1: the
+    run as a whole — an early return, or the plan's call list)."""
+    return rate_run_pairs() + janitor_run_pairs() + plan_run_pairs()
+
+
+def rebalance_blob(tier, case):
+    """The harness' input for one case: the stats it is GIVEN are what oracle.bind computes from the fleet."""
+    from oracle import bind as ob
+    fleet, ids = case[0], case[1]
+    if tier == "rate":
+        _, _, entries, conc, sp, cp, _ = case
+        cstats = np.zeros(1, dtype=ob.ORC_STATS)
+        cstats[0] = ob.OracleFleet(fleet).stats()
+        return input_blob(fleet, ids, scaleup=(entries, sp, cstats, np.ascontiguousarray(ob.type_set_stats(fleet))),
+                          conc=None if conc is None else (conc, cp))
+    if tier == "janitor":
+        _, _, entries, conc, dp, dyn, _ = case
+        cp = _conc_params(dyn=dyn)
+        return input_blob(fleet, ids, scaledown=(entries, dp, ob.instance_set_stats(fleet, int(dp["self_pod"][0]))),
+                          conc=None if conc is None else (conc, cp))
+    from oracle.ref_harness.make_ref_vectors import proactive_inputs
+    return input_blob(fleet, ids, proactive=proactive_inputs(fleet, case[2], case[3]))
 
 
 TABLE_EVENT = np.dtype([("type", "<i4"), ("pod", "<i4"), ("row", _lib.POD_ROW)])  # type: 0 ENTRY_ADDED, 1 ENTRY_UPDATED, 2 ENTRY_DELETED
