@@ -96,7 +96,25 @@ int main(void)
     }
     printf("by vmodel id: class=%d vmodel=%d model=%d chosen=%d best=%d candidates=%d\n", vm.cls, vm.vmodel, vm.model, by_vmodel.chosen,
            by_vmodel.best, by_vmodel.n_candidates);
+    /* The management path by id: getVModelStatus of "my-vmodel" in one call (mmp_vmodels_status) — the vmodel's row, the status of
+     * its active and target model with their copies, and the three strings of the reply, all of one state. */
+    mmp_vstatus_row vs;
+    mmp_status_row st_rows[2];
+    mmp_status_copy st_copies[4];
+    char strs[64];
+    int32_t str_off[4], n_copies = -1, n_str = -1;
+    if ((rc = mmp_vmodels_status(ctx, vids, vid_off, 1, NULL, NULL, NULL, now, &vs, st_rows, st_copies, 4, &n_copies, strs, (int32_t)sizeof strs,
+                                 str_off, &n_str))) {
+        fprintf(stderr, "libmmplace: %d (%s)\n", rc, mmp_last_error(ctx));
+        mmp_destroy(ctx);
+        return 1;
+    }
+    printf("status by vmodel id: class=%d vstatus=%d active: class=%d copies=%d, active id \"%.*s\"\n", vs.cls, vs.vstatus, st_rows[0].cls,
+           st_rows[0].n_not_checked + st_rows[0].n_failed, (int)(str_off[1] - str_off[0]), strs + str_off[0]);
     mmp_destroy(ctx);
+    if (vs.cls != MMP_VMR_OK || vs.model != 0 || vs.vstatus != MMP_VMS_DEFINED || st_rows[0].cls != MMP_MST_ASK || n_copies != 1 ||
+        st_rows[1].cls != MMP_MST_NOT_FOUND || n_str != 16 || memcmp(strs, "my-modelmy-model", 16) != 0)
+        return 5;
     /* pod 0 holds the model, so the most desirable eligible pod is pod 1; the id names row 0 and decides the same, and so does the
      * vmodel whose active model it is */
     if (row != 0 || memcmp(&keyed, &out, sizeof out) != 0) return 3;

@@ -1121,6 +1121,30 @@ typedef struct { int32_t cls; int32_t copy_off; int32_t n_not_checked; int32_t n
 typedef struct { int32_t pod; int32_t status; int64_t time; } mmp_status_copy;                            /* 16 bytes */
 int mmp_models_status(mmp_ctx *ctx, const mmp_status_req *reqs, int32_t n, int64_t now_ms, mmp_status_row *rows_out,
                       mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out);
+/* getStatus BY MODEL ID (MM.java:3247-3263): mmp_model_ids_resolve and mmp_models_status as ONE staged call under one hold of the
+ * batch lock, so that no registry event batch and no mmp_models_retire can land between the row and its copy list
+ * (csrc/status_keyed_kernels.hpp: one launch in front of the unchanged status kernels).
+ *   keys / key_off     n keys, raw id bytes, under the conventions of mmp_model_ids_resolve
+ *   fail_pod           int32[n], may be NULL (all -1)
+ *   flags              uint32[n], may be NULL (all 0); the only bit is MMP_MSTF_MISS
+ *   model_idx_out      n words, may be NULL
+ *   rows_out, copies_out, max_copies, n_copies_out: exactly as mmp_models_status (sizes only with max_copies == 0, truncation)
+ *
+ * THE RULE BY KEY: model_idx_out[i] is what mmp_model_ids_resolve answers for key i.  Request i is answered exactly as
+ * mmp_models_status answers {model = r, fail_pod[i], flags[i], 0}, where r is the row model_idx_out[i] names, and r = -1 when the
+ * id is unknown OR that row is the empty row — the all-zero row a deleted record leaves, the definition of MMP_RETIRE_EMPTY_ONLY
+ * and what mmp_vmodels_resolve treats as "not found" for a target: a deleted record's getStatus is SI_NOT_FOUND (:3257).  So a
+ * host that keeps no id map does not have to "send -1" for deleted records; model_idx_out still carries the table's row, which
+ * tells the two cases apart.
+ *
+ * MMP_EINVAL, with nothing written: key offsets that are not monotone, a NULL required buffer (NULL keys with key bytes present
+ * included), a fail_pod outside [-1, pod slots of the committed instance table), an unknown flag bit, now_ms <= 0 while a
+ * fail_pod is present, more than INT32_MAX copies in all.  MMP_ESTATE under the conditions of mmp_model_ids_resolve, and before
+ * the first commit when a fail_pod >= 0 is present.  Read-only, locking as mmp_models_status; n == 0 is valid; two runs over the
+ * same state are byte-identical. */
+int mmp_models_status_k(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, const int32_t *fail_pod,
+                        const uint32_t *flags, int64_t now_ms, int32_t *model_idx_out, mmp_status_row *rows_out,
+                        mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out);
 
 /* a15: entries = usedSinceLastRun (runtimeCache.descendingMapWithCutoff(lastTime)) in iteration order.
  * overloaded_out has one byte per pod = membership in getExcludeSet() (MM.java:5835-5856); for
@@ -1625,6 +1649,50 @@ typedef struct {
 } mmp_vmodel_answer; /* 32 bytes */
 int mmp_vmodels_resolve(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, const char *nf_keys, const int32_t *nf_off,
                         const char *owners, const int32_t *owner_off, const uint32_t *req_flags, mmp_vmodel_answer *rows_out);
+/* getVModelStatus IN FULL (VModelManager.java:505-559) as ONE staged call under one hold of the batch lock: what a host otherwise
+ * stitches from mmp_vmodels_resolve, mmp_models_status on two rows per vmodel and mmp_vmodels_get per row — with an event batch or
+ * a retirement free to land between any two of them (csrc/status_keyed_kernels.hpp).
+ *   keys / key_off       n vmodel ids
+ *   owners / owner_off   may be NULL; an empty span is Java null (emptyToNull, :506)
+ *   req_flags            n words, may be NULL; the only bit is MMP_VMRQ_AFTER_STRONG
+ *   vrows_out            n rows (below)
+ *   rows_out             2n mmp_status_row: row 2i is the active model's answer, row 2i + 1 the target's; copy_off is the
+ *                        exclusive prefix sum over the 2n rows in that order
+ *   copies_out / max_copies / n_copies_out   as mmp_models_status
+ *   str_off_out          3n + 1 words, rebased to 0, may be NULL: span 3i is amid, 3i + 1 tmid, 3i + 2 o
+ *   str_bytes_out / max_str_bytes / n_str_bytes_out   under the conventions of mmp_vmodels_get: the total always, the offsets
+ *                        always, the bytes only when max_str_bytes >= the total; raw bytes as stored, a null string is an empty
+ *                        span and vrows_out[i].flags tells it from ""
+ *
+ * THE RULE.  Let a be what mmp_vmodels_resolve answers for (key i, no nf, owner i, req_flags i) against the state the call
+ * captured.  cls, vmodel, target_model, vstatus and target_status are a's; `model` is the row of amid as the model-id table knows
+ * it, else -1; flags = the row's MMP_VMF_FAILED / _ACTIVE_NULL / _TARGET_NULL / _OWNER_NULL as stored.  The active request (row 2i)
+ * is {m, -1, 0, 0}: m = model, or -1 when amid is null, unknown or names the empty row (:513).  The target request (row 2i + 1) is
+ * {t, -1, 0, 0}: t = target_model when the vmodel is in transition and that row is known and not empty, else -1 (:538, :548; the
+ * device keeps answering MMP_VMT_NOT_FOUND where the Java would throw at :544).  Rows 2i, 2i + 1 and their copies are byte for
+ * byte what mmp_models_status answers for those two requests.
+ *   The strong read (:514-525): cls becomes MMP_VMR_STRONG_READ when a.cls is MMP_VMR_OK, the active answer's class is
+ *   MMP_MST_NOT_FOUND and MMP_VMRQ_AFTER_STRONG is clear.  Every other field is still filled in.  The host performs getStrong,
+ *   sends the value through mmp_vmodels_events_json and asks again with the flag; with the flag the answer stands as it is.
+ *   MMP_VMR_NOT_FOUND (absent row, unknown id, owner mismatch) and MMP_VMR_HOST: both status rows are the -1 request's answer,
+ *   all three spans are empty, flags is 0, the ids are -1 (except vmodel for HOST).  An owner mismatch says nothing of the record:
+ *   the Java returns the default instance.
+ *
+ * MMP_EINVAL, every output untouched: what mmp_vmodels_resolve refuses (a NULL required buffer, offsets of either kind that are
+ * not monotone, unknown request flag bits), what mmp_models_status refuses of its buffers, more than INT32_MAX copies or string
+ * bytes in all.  MMP_ESTATE as mmp_vmodels_resolve.  Read-only, no commit; a context that never had a vmodel call answers
+ * MMP_VMR_NOT_FOUND for everything.  n == 0 is valid.  Two runs over the same state are byte-identical. */
+typedef struct {
+    int32_t cls;                  /* MMP_VMR_NOT_FOUND / _OK / _STRONG_READ / _HOST */
+    int32_t vmodel, model, target_model;
+    int32_t vstatus, target_status; /* MMP_VMS_*, MMP_VMT_* */
+    uint32_t flags;               /* MMP_VMF_FAILED | _ACTIVE_NULL | _TARGET_NULL | _OWNER_NULL */
+    int32_t reserved;             /* 0 */
+} mmp_vstatus_row; /* 32 bytes */
+int mmp_vmodels_status(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, const char *owners,
+                       const int32_t *owner_off, const uint32_t *req_flags, int64_t now_ms, mmp_vstatus_row *vrows_out,
+                       mmp_status_row *rows_out, mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out,
+                       char *str_bytes_out, int32_t max_str_bytes, int32_t *str_off_out, int32_t *n_str_bytes_out);
 /* The single-caller request forms BY VMODEL ID: ModelMeshApi.callModel (:452-476) for a request that names a vmodel — first
  * resolveVModelId(vModelId, notFoundModelId), then invokeModel's seams on the model id it returned.  With mmp_vmodels_resolve (a
  * staged call under the batch lock, which answers a registry ROW) in front of a _c call that is two calls and one batch lock on the

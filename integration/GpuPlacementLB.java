@@ -270,6 +270,23 @@ final class MmPlace {
     static native int vmodelsGet(long h, int firstRow, int nRows, ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut,
                                  ByteBuffer nIdBytesOut, ByteBuffer flagsOut, ByteBuffer strBytesOut, int maxStrBytes,
                                  ByteBuffer strOffOut, ByteBuffer nStrBytesOut);
+    /** getStatus BY MODEL ID (MM.java:3247-3263) in one call under one hold of the library's batch lock — modelIdsResolve and
+     *  modelsStatus with nothing able to land between them.  failPod / flags (n ints each) and modelIdxOut (n ints) may be null; an
+     *  unknown id AND the empty row a deleted record leaves answer class 0 (NOT_FOUND), modelIdxOut tells them apart.  Sizes and
+     *  truncation as modelsStatus. */
+    static native int modelsStatusKeyed(long h, ByteBuffer keys, ByteBuffer keyOff, int n, ByteBuffer failPod, ByteBuffer flags, long nowMs,
+                                        ByteBuffer modelIdxOut, ByteBuffer rowsOut, ByteBuffer copiesOut, int maxCopies,
+                                        ByteBuffer nCopiesOut);
+    /** getVModelStatus IN FULL (VModelManager.java:505-559) in one call: vrowsOut = n rows of 32 bytes (cls 0 not found / 1 ok /
+     *  2 strong read wanted / 4 the host decodes, vmodel, model, target_model, vstatus, target_status, flags 1 failed | 4 amid null |
+     *  8 tmid null | 16 o null, 0); rowsOut = 2 n mmp_status_row (2 i the active model's, 2 i + 1 the target's) with their copies in
+     *  copiesOut; the reply's three strings of key i are spans 3 i (amid), 3 i + 1 (tmid), 3 i + 2 (o) of strBytesOut / strOffOut.
+     *  owners / ownerOff, reqFlags (1 = after the strong read) and strOffOut may be null; null copiesOut / strBytesOut with
+     *  capacities 0 give nCopiesOut / nStrBytesOut only. */
+    static native int vmodelsStatus(long h, ByteBuffer keys, ByteBuffer keyOff, int n, ByteBuffer owners, ByteBuffer ownerOff,
+                                    ByteBuffer reqFlags, long nowMs, ByteBuffer vrowsOut, ByteBuffer rowsOut, ByteBuffer copiesOut,
+                                    int maxCopies, ByteBuffer nCopiesOut, ByteBuffer strBytesOut, int maxStrBytes, ByteBuffer strOffOut,
+                                    ByteBuffer nStrBytesOut);
     /** rows, live rows, arena bytes, live bytes, table capacity (32 bytes). */
     static native int vmodelsInfo(long h, ByteBuffer out);
     /** hand vmodel rows back (mmp_vmodels_retire): rows = n ints, the rows whose deletion the vmodel listener has seen; flags 1 =
@@ -440,6 +457,106 @@ final class VModelCall {
             flags.putInt(0, AFTER_STRONG);
         }
         return new int[] { vm.getInt(0), vm.getInt(4), vm.getInt(8), vm.getInt(12), vm.getInt(16) };
+    }
+}
+
+/**
+ * The management path's two status RPCs answered by id, one library call each instead of the sequence modelIdsResolve + modelsStatus
+ * (getModelStatus) and vmodelsResolve + modelsStatus + vmodelsGet per row (getVModelStatus): every part of an answer comes from ONE
+ * state of the registry and the vmodel table, whatever event batch or retirement the listeners send meanwhile.
+ */
+final class StatusById {
+    /** one answered status: class (0 NOT_FOUND / 1 NOT_LOADED / 2 LOADING_FAILED / 3 ask a copy) and the copies, latest first */
+    static final class Status {
+        int cls, row;             // row: the registry row the id table names (-1 unknown; a deleted record keeps its row)
+        int[] pod, copyStatus;    // 0 NOT_CHECKED / 1 LOADING_FAILED
+        long[] time;
+    }
+    /** getVModelStatus's reply: cls as VModelCall (0 NOT_FOUND: the default instance; 4 HOST: decode the KV value instead) */
+    static final class VStatus {
+        int cls, vstatus, targetStatus;
+        String activeModelId, targetModelId, owner;   // null where the record holds null
+        Status active, target;                        // target: class 0 and no copies when not in transition
+    }
+
+    private static Status status(ByteBuffer rows, int i, ByteBuffer copies, int row) {
+        final Status s = new Status();
+        s.cls = rows.getInt(16 * i);
+        s.row = row;
+        final int off = rows.getInt(16 * i + 4), n = rows.getInt(16 * i + 8) + rows.getInt(16 * i + 12);
+        s.pod = new int[n]; s.copyStatus = new int[n]; s.time = new long[n];
+        for (int k = 0; k < n; k++) {
+            s.pod[k] = copies.getInt(16 * (off + k));
+            s.copyStatus[k] = copies.getInt(16 * (off + k) + 4);
+            s.time[k] = copies.getLong(16 * (off + k) + 8);
+        }
+        return s;
+    }
+
+    /** getStatus(modelId), MM.java:3247-3263: sizes first, then the list (again if the record grew in between) */
+    static Status getModelStatus(GpuMeshBinding mesh, String modelId, long nowMs) {
+        final ByteBuffer[] key = ModelKey.of(modelId);
+        final ByteBuffer rows = MmPlace.direct(16), idx = MmPlace.direct(4), total = MmPlace.direct(4);
+        MmPlace.modelsStatusKeyed(mesh.handle(), key[0], key[1], 1, null, null, nowMs, idx, rows, null, 0, total);
+        for (;;) {
+            final int cap = total.getInt(0);
+            final ByteBuffer copies = MmPlace.direct(Math.max(16 * cap, 16));
+            MmPlace.modelsStatusKeyed(mesh.handle(), key[0], key[1], 1, null, null, nowMs, idx, rows, cap > 0 ? copies : null, cap, total);
+            if (total.getInt(0) <= cap) return status(rows, 0, copies, idx.getInt(0));
+        }
+    }
+
+    private static String str(ByteBuffer bytes, ByteBuffer off, int span, boolean isNull) {
+        if (isNull) return null;
+        final byte[] b = new byte[off.getInt(4 * (span + 1)) - off.getInt(4 * span)];
+        for (int k = 0; k < b.length; k++) b[k] = bytes.get(off.getInt(4 * span) + k);
+        return new String(b, java.nio.charset.StandardCharsets.UTF_8);
+    }
+
+    /** getVModelStatus(vmid, owner), VModelManager.java:505-559, the strong read of :514-525 included */
+    static VStatus getVModelStatus(GpuMeshBinding mesh, VModelCall.StrongReader kv, String vModelId, String owner, long nowMs)
+            throws Exception {
+        final ByteBuffer[] key = ModelKey.of(vModelId);
+        final ByteBuffer[] own = owner == null || owner.isEmpty() ? null : ModelKey.of(owner);   // :506 emptyToNull
+        final ByteBuffer vrow = MmPlace.direct(32), rows = MmPlace.direct(32), flags = MmPlace.direct(4), strOff = MmPlace.direct(16);
+        final ByteBuffer nCopies = MmPlace.direct(4), nStr = MmPlace.direct(4);
+        flags.putInt(0, 0);
+        int capCopies = 0, capStr = 0;
+        ByteBuffer copies = MmPlace.direct(16), strs = MmPlace.direct(16);
+        for (boolean strong = false; ; ) {
+            MmPlace.vmodelsStatus(mesh.handle(), key[0], key[1], 1, own != null ? own[0] : null, own != null ? own[1] : null, flags, nowMs,
+                                  vrow, rows, capCopies > 0 ? copies : null, capCopies, nCopies, capStr > 0 ? strs : null, capStr, strOff, nStr);
+            if (vrow.getInt(0) == VModelCall.STRONG_READ && !strong) {   // :515 vModels.getStrong, its value to the device, again
+                final byte[] fresh = kv.getStrong(vModelId);
+                final byte[] value = fresh != null ? fresh : new byte[0];
+                final ByteBuffer json = MmPlace.direct(Math.max(value.length, 1)), off = MmPlace.direct(32);
+                json.put(value);
+                off.putLong(0, 0L); off.putLong(8, value.length);
+                final ByteBuffer deleted = MmPlace.slice(off, 16, 1), idx = MmPlace.slice(off, 20, 4), status = MmPlace.slice(off, 24, 4);
+                deleted.put(0, (byte) (fresh == null ? 1 : 0));
+                MmPlace.vmodelsEventsJson(mesh.handle(), key[0], key[1], json, MmPlace.slice(off, 0, 16), 1, deleted, 1, idx, status, null);
+                flags.putInt(0, VModelCall.AFTER_STRONG);
+                strong = true;
+                continue;
+            }
+            if (nCopies.getInt(0) <= capCopies && nStr.getInt(0) <= capStr) break;
+            capCopies = Math.max(capCopies, nCopies.getInt(0));   // the sizes are known: the same question with room for the lists
+            capStr = Math.max(capStr, nStr.getInt(0));
+            copies = MmPlace.direct(Math.max(16 * capCopies, 16));
+            strs = MmPlace.direct(Math.max(capStr, 16));
+        }
+        final VStatus v = new VStatus();
+        v.cls = vrow.getInt(0);
+        v.vstatus = vrow.getInt(16);
+        v.targetStatus = vrow.getInt(20);
+        final int f = vrow.getInt(24);
+        final boolean found = v.cls == VModelCall.OK || v.cls == VModelCall.STRONG_READ;
+        v.activeModelId = str(strs, strOff, 0, !found || (f & 4) != 0);
+        v.targetModelId = str(strs, strOff, 1, !found || (f & 8) != 0);
+        v.owner = str(strs, strOff, 2, !found || (f & 16) != 0);
+        v.active = status(rows, 0, copies, vrow.getInt(8));
+        v.target = status(rows, 1, copies, vrow.getInt(12));
+        return v;
     }
 }
 

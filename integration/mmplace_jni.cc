@@ -1005,6 +1005,55 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsGet(JNIEnv *
                                  buf<int32_t>(env, nIdBytesOut), buf<uint32_t>(env, flagsOut), buf<char>(env, strBytesOut), maxStrBytes,
                                  buf<int32_t>(env, strOffOut), buf<int32_t>(env, nStrBytesOut)));
 }
+// getStatus by model id (mmp_models_status_k): failPod / flags (n ints each) and modelIdxOut (n ints) may be null; a null copiesOut
+// with maxCopies 0 gives the sizes only
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsStatusKeyed(JNIEnv *env, jclass, jlong h, jobject keys, jobject keyOff,
+                                                                               jint n, jobject failPod, jobject flags, jlong nowMs,
+                                                                               jobject modelIdxOut, jobject rowsOut, jobject copiesOut,
+                                                                               jint maxCopies, jobject nCopiesOut)
+{
+    if (n < 0 || maxCopies < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "modelsStatusKeyed: keyOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "modelsStatusKeyed: keys shorter than keyOff[n]")) ||
+        (failPod && !holds<int32_t>(env, failPod, n, "modelsStatusKeyed: failPod shorter than n")) ||
+        (flags && !holds<uint32_t>(env, flags, n, "modelsStatusKeyed: flags shorter than n")) ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "modelsStatusKeyed: modelIdxOut shorter than n")) ||
+        !holds<mmp_status_row>(env, rowsOut, n, "modelsStatusKeyed: rowsOut shorter than n") ||
+        !holds<mmp_status_copy>(env, copiesOut, maxCopies, "modelsStatusKeyed: copiesOut shorter than maxCopies") ||
+        !holds<int32_t>(env, nCopiesOut, 1, "modelsStatusKeyed: nCopiesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_models_status_k(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), n, buf<int32_t>(env, failPod),
+                                     buf<uint32_t>(env, flags), nowMs, buf<int32_t>(env, modelIdxOut), buf<mmp_status_row>(env, rowsOut),
+                                     buf<mmp_status_copy>(env, copiesOut), maxCopies, buf<int32_t>(env, nCopiesOut)));
+}
+// getVModelStatus in full (mmp_vmodels_status): owners / ownerOff, reqFlags and strOffOut (3 n + 1 ints) may be null; vrowsOut holds n
+// mmp_vstatus_row structs, rowsOut 2 n mmp_status_row structs; null copiesOut / strBytesOut with capacities 0 give the sizes only
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsStatus(JNIEnv *env, jclass, jlong h, jobject keys, jobject keyOff, jint n,
+                                                                           jobject owners, jobject ownerOff, jobject reqFlags, jlong nowMs,
+                                                                           jobject vrowsOut, jobject rowsOut, jobject copiesOut,
+                                                                           jint maxCopies, jobject nCopiesOut, jobject strBytesOut,
+                                                                           jint maxStrBytes, jobject strOffOut, jobject nStrBytesOut)
+{
+    if (n < 0 || maxCopies < 0 || maxStrBytes < 0 || !holds<int32_t>(env, keyOff, (jlong)n + 1, "vmodelsStatus: keyOff shorter than n + 1") ||
+        (n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "vmodelsStatus: keys shorter than keyOff[n]")) ||
+        (ownerOff && !holds<int32_t>(env, ownerOff, (jlong)n + 1, "vmodelsStatus: ownerOff shorter than n + 1")) ||
+        (ownerOff && n > 0 && !holds<char>(env, owners, buf<int32_t>(env, ownerOff)[n], "vmodelsStatus: owners shorter than ownerOff[n]")) ||
+        (reqFlags && !holds<uint32_t>(env, reqFlags, n, "vmodelsStatus: reqFlags shorter than n")) ||
+        !holds<mmp_vstatus_row>(env, vrowsOut, n, "vmodelsStatus: vrowsOut shorter than n rows") ||
+        !holds<mmp_status_row>(env, rowsOut, 2 * (jlong)n, "vmodelsStatus: rowsOut shorter than 2 n rows") ||
+        !holds<mmp_status_copy>(env, copiesOut, maxCopies, "vmodelsStatus: copiesOut shorter than maxCopies") ||
+        !holds<int32_t>(env, nCopiesOut, 1, "vmodelsStatus: nCopiesOut shorter than one int") ||
+        !holds<char>(env, strBytesOut, maxStrBytes, "vmodelsStatus: strBytesOut shorter than maxStrBytes") ||
+        (strOffOut && !holds<int32_t>(env, strOffOut, 3 * (jlong)n + 1, "vmodelsStatus: strOffOut shorter than 3 n + 1")) ||
+        !holds<int32_t>(env, nStrBytesOut, 1, "vmodelsStatus: nStrBytesOut shorter than one int"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_vmodels_status(ctx_of(h), buf<char>(env, keys), buf<int32_t>(env, keyOff), n, buf<char>(env, owners),
+                                    buf<int32_t>(env, ownerOff), buf<uint32_t>(env, reqFlags), nowMs, buf<mmp_vstatus_row>(env, vrowsOut),
+                                    buf<mmp_status_row>(env, rowsOut), buf<mmp_status_copy>(env, copiesOut), maxCopies,
+                                    buf<int32_t>(env, nCopiesOut), buf<char>(env, strBytesOut), maxStrBytes, buf<int32_t>(env, strOffOut),
+                                    buf<int32_t>(env, nStrBytesOut)));
+}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_vmodelsInfo(JNIEnv *env, jclass, jlong h, jobject out)
 {
     if (!holds<mmp_vmodels_stats>(env, out, 1, "vmodelsInfo: out shorter than one mmp_vmodels_stats")) return MMP_EINVAL;

@@ -229,6 +229,11 @@ VMODEL_TRANSITIONS_INFO = np.dtype([("n_listed", "<i4"), ("n_promote", "<i4"), (
 VMODELS_STATS = np.dtype([("n_rows", "<i4"), ("n_live", "<i4"), ("arena_bytes", "<i8"), ("live_bytes", "<i8"), ("capacity", "<i4"),
                           ("reserved", "<i4")])
 assert VMODEL_ANSWER.itemsize == 32 and VMODEL_TRANSITION.itemsize == 32 and VMODEL_TRANSITIONS_INFO.itemsize == 24
+# mmp_vstatus_row: what mmp_vmodels_status answers per vmodel (getVModelStatus, VModelManager.java:505-559); flags = VMF_REPLY bits
+VSTATUS_ROW = np.dtype([("cls", "<i4"), ("vmodel", "<i4"), ("model", "<i4"), ("target_model", "<i4"), ("vstatus", "<i4"),
+                        ("target_status", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert VSTATUS_ROW.itemsize == 32
+VMF_REPLY = VMF_FAILED | VMF_ACTIVE_NULL | VMF_TARGET_NULL | VMF_OWNER_NULL
 # mmp_vseam_row: what the request calls by vmodel id answer per request (the shared fields of VMODEL_ANSWER)
 VSEAM_ROW = np.dtype([("cls", "<i4"), ("which", "<i4"), ("vmodel", "<i4"), ("model", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
 assert VSEAM_ROW.itemsize == 24
@@ -360,6 +365,11 @@ SYMBOLS = [
     ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("mmp_registry_ops", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint32, _P, _P, C.c_int32, _P]),
     ("mmp_models_status", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    # the same by model id: keys / key_off / n, fail_pod[n], flags[n], now, model_idx_out, then the outputs of mmp_models_status
+    ("mmp_models_status_k", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    # getVModelStatus: keys / key_off / n, owners / owner_off, req_flags, now, vrows, rows[2n], copies, strings
+    ("mmp_vmodels_status", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P,
+                                     C.c_int32, _P, C.POINTER(C.c_int32)]),
     ("mmp_registry_census", C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_scaleup_plan", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("mmp_scaledown_plan", C.c_int, [_P, _P, C.c_int32, _P, _P]),

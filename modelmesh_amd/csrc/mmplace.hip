@@ -42,6 +42,7 @@
 #include "janitor_kernels.hpp"
 #include "registry_ops_kernels.hpp"
 #include "status_kernels.hpp"
+#include "status_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
@@ -590,6 +591,11 @@ struct mmp_ctx {
     // mmp_models_status (status_kernels.hpp): the call's copy list on the device.  Owned by batch_mu, used on c->stream; its other
     // scratch is the registry plans' (plan).
     DevBuf st_copies;
+    // mmp_models_status_k / mmp_vmodels_status (status_keyed_kernels.hpp): one call's fail_pod and flags words, the 64-bit total of
+    // the reply's string bytes, and the strings on the device.  The keys are ida_*, the owners vm_ow_*, the request flags vm_rflags,
+    // the resolved rows me_row, the vrows vm_ans, the lengths and their scan j_cnt / j_offs / j_scan_tmp.  Owned by batch_mu, used on
+    // c->stream.
+    DevBuf sk_fpod, sk_flags, sk_sc, sk_str;
     // mmp_models_rewrite_json (rewrite_kernels.hpp).  idd_bytes / idd_off: the device copy of the instance id store (id_bytes /
     // id_offs), uploaded lazily: every writer of the host store bumps id_gen, the call uploads when idd_gen differs.  rw_*: one
     // call's rows, last_unload, fail_pod, messages and their offsets, sizes, offsets, statuses and rendered bytes.  Owned by
@@ -1513,7 +1519,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->vq_nf, &c->vq_nf_off, &c->vq_flags, &c->vq_out,
                       &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
                       &c->vm_ans, &c->vm_list,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->kq_keys, &c->kq_off, &c->kq_idx, &c->kq_preqs, &c->kq_pouts, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
+                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->sk_fpod, &c->sk_flags, &c->sk_sc, &c->sk_str, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->kq_keys, &c->kq_off, &c->kq_idx, &c->kq_preqs, &c->kq_pouts, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
                       &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
                       &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
         b->release();
@@ -7650,6 +7656,89 @@ try {
     });
 } MMP_CATCH(c, "mmp_registry_ops")
 
+namespace {
+// What a caller of status_drive adds around the pipeline; each defaults to nothing.
+struct StatusNoHook {
+    int operator()() const { return MMP_OK; }
+};
+
+// THE STATUS PIPELINE over device-resident requests (status_kernels.hpp): mmp_models_status behind its host-side validation, shared
+// with the calls that write the requests on the device (status_keyed_kernels.hpp).  The caller owns batch_mu, has set the device,
+// has refused what it refuses of the requests, and has n > 0 mmp_status_req rows in (or on their way into) c->plan.rows_in — staged
+// by a copy it enqueued on c->stream, or written by the kernels `front` launches.  pods / P: the committed rows for the overlay,
+// nullptr / 0 when no request carries a fail_pod.  The hooks, all on c->stream:
+//   front   launches in front of the count kernel, inside the device span
+//   back    further read-backs enqueued beside the pipeline's own, in front of the ONE synchronisation on the sizes
+//   sized   the sizes are on the host: what the caller refuses of its own, and the room for what `tail` writes
+//   tail    launches behind the emit kernels, inside the device span
+// Nothing reaches rows_out / copies_out / n_copies_out before the last step that refuses.
+extern "C++" template <class Front = StatusNoHook, class Back = StatusNoHook, class Sized = StatusNoHook, class Tail = StatusNoHook>
+int status_drive(mmp_ctx *c, const char *fn, int32_t n, int64_t now, const mmp_pod_row *pods, int32_t P, mmp_status_row *rows_out,
+                 mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out, Front front = Front(), Back back = Back(),
+                 Sized sized = Sized(), Tail tail = Tail())
+{
+    hipStream_t st = c->stream;
+    const int nb = div_up(n, kStatusBlock);
+    HIP_TRY(c, c->plan.edits.ensure((size_t)n * sizeof(mmp_status_row)));
+    HIP_TRY(c, c->plan.keep_off.ensure((size_t)n * sizeof(StatusAux)));
+    HIP_TRY(c, c->plan.row_tmp.ensure((size_t)n * 4));
+    HIP_TRY(c, c->plan.call_scalars.ensure(std::max(sizeof(StatusScalars), std::max(sizeof(RopsScalars), sizeof(JanitorScalars)))));
+    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
+    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
+    const mmp_model_row *models = c->models.as<mmp_model_row>();
+    const int32_t *ent_pod = c->ent_pod.as<int32_t>();
+    const int64_t *ent_time = c->ent_time.as<int64_t>();
+    const mmp_status_req *d_reqs = c->plan.rows_in.as<mmp_status_req>();
+    mmp_status_row *d_rows = c->plan.edits.as<mmp_status_row>();
+    StatusAux *d_aux = c->plan.keep_off.as<StatusAux>();
+    int32_t *d_long = c->plan.row_tmp.as<int32_t>();
+    StatusScalars *ss = c->plan.call_scalars.as<StatusScalars>();
+    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
+    HIP_TRY(c, hipMemsetAsync(ss, 0, sizeof(StatusScalars), st));
+    HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
+    KT_BEGIN(c, st);  // device span: count, scan, offsets — and, behind the one read-back of the sizes, the two emit kernels
+    if (const int rc = front()) return rc;
+    hipLaunchKernelGGL(status_count_kernel, dim3(nb), dim3(kStatusBlock), 0, st, d_reqs, n, models, ent_pod, pods, P, d_rows, d_aux,
+                       c->plan.block_counts.as<int32_t>(), ss);
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
+    hipLaunchKernelGGL(status_rows_kernel, dim3(nb), dim3(kStatusBlock), 0, st, n, d_rows, c->plan.block_counts.as<int32_t>(), d_long);
+    HIP_TRY(c, hipGetLastError());
+    StatusScalars hs{};
+    PruneScalars h{};
+    HIP_TRY(c, hipMemcpyAsync(&hs, ss, sizeof hs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
+    if (const int rc = back()) return rc;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (hs.n_copies > (unsigned long long)INT32_MAX) {
+        c->prof_armed = false;
+        return fail(c, MMP_EINVAL, "%s: %llu copies in all; split the batch", fn, hs.n_copies);
+    }
+    if (const int rc = sized()) {
+        c->prof_armed = false;
+        return rc;
+    }
+    const int32_t total = h.n_kept, n_long = h.n_edits, take = std::min(total, max_copies);
+    if (take > 0) {
+        HIP_TRY(c, c->st_copies.ensure((size_t)take * sizeof(mmp_status_copy)));
+        mmp_status_copy *d_copies = c->st_copies.as<mmp_status_copy>();
+        hipLaunchKernelGGL(status_emit_kernel, dim3(div_up(total, kStatusBlock)), dim3(kStatusBlock), 0, st, d_reqs, n, total, models, ent_pod,
+                           ent_time, now, d_rows, d_aux, d_copies, take);
+        if (n_long > 0)
+            hipLaunchKernelGGL(status_long_kernel, dim3(n_long), dim3(kStatusLongBlock), 0, st, d_reqs, d_long, models, ent_pod, ent_time, now,
+                               d_rows, d_aux, d_copies, take);
+    }
+    if (const int rc = tail()) return rc;
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    // every word of copies[0, take) has exactly one writer above: the ranks of a segment are a permutation of its indices
+    if (take > 0) HIP_TRY(c, copy_sync(c, copies_out, c->st_copies.p, (size_t)take * sizeof(mmp_status_copy), hipMemcpyDeviceToHost));
+    HIP_TRY(c, copy_sync(c, rows_out, d_rows, (size_t)n * sizeof(mmp_status_row), hipMemcpyDeviceToHost));
+    kt_collect(c);
+    *n_copies_out = total;
+    return MMP_OK;
+}
+}  // namespace
+
 int mmp_models_status(mmp_ctx *c, const mmp_status_req *reqs, int32_t n, int64_t now, mmp_status_row *rows_out,
                       mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out)
 try {
@@ -7684,61 +7773,159 @@ try {
         return MMP_OK;
     }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    const int nb = div_up(n, kStatusBlock);
     HIP_TRY(c, c->plan.rows_in.ensure((size_t)n * sizeof(mmp_status_req)));
-    HIP_TRY(c, c->plan.edits.ensure((size_t)n * sizeof(mmp_status_row)));
-    HIP_TRY(c, c->plan.keep_off.ensure((size_t)n * sizeof(StatusAux)));
-    HIP_TRY(c, c->plan.row_tmp.ensure((size_t)n * 4));
-    HIP_TRY(c, c->plan.call_scalars.ensure(std::max(sizeof(StatusScalars), std::max(sizeof(RopsScalars), sizeof(JanitorScalars)))));
-    HIP_TRY(c, c->plan.totals.ensure(sizeof(PruneScalars)));
-    HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
-    const mmp_model_row *models = c->models.as<mmp_model_row>();
-    const int32_t *ent_pod = c->ent_pod.as<int32_t>();
-    const int64_t *ent_time = c->ent_time.as<int64_t>();
-    const mmp_status_req *d_reqs = c->plan.rows_in.as<mmp_status_req>();
-    mmp_status_row *d_rows = c->plan.edits.as<mmp_status_row>();
-    StatusAux *d_aux = c->plan.keep_off.as<StatusAux>();
-    int32_t *d_long = c->plan.row_tmp.as<int32_t>();
-    StatusScalars *ss = c->plan.call_scalars.as<StatusScalars>();
-    PruneScalars *ps = c->plan.totals.as<PruneScalars>();
-    HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, reqs, (size_t)n * sizeof(mmp_status_req), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(ss, 0, sizeof(StatusScalars), st));
-    HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
-    KT_BEGIN(c, st);  // device span: count, scan, offsets — and, behind the one read-back of the sizes, the two emit kernels
-    hipLaunchKernelGGL(status_count_kernel, dim3(nb), dim3(kStatusBlock), 0, st, d_reqs, n, models, ent_pod, pods, P, d_rows, d_aux,
-                       c->plan.block_counts.as<int32_t>(), ss);
-    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, INT32_MAX, INT32_MAX, ps);
-    hipLaunchKernelGGL(status_rows_kernel, dim3(nb), dim3(kStatusBlock), 0, st, n, d_rows, c->plan.block_counts.as<int32_t>(), d_long);
-    HIP_TRY(c, hipGetLastError());
-    StatusScalars hs{};
-    PruneScalars h{};
-    HIP_TRY(c, hipMemcpyAsync(&hs, ss, sizeof hs, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&h, ps, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (hs.n_copies > (unsigned long long)INT32_MAX) {
-        c->prof_armed = false;
-        return fail(c, MMP_EINVAL, "mmp_models_status: %llu copies in all; split the batch", hs.n_copies);
-    }
-    const int32_t total = h.n_kept, n_long = h.n_edits, take = std::min(total, max_copies);
-    if (take > 0) {
-        HIP_TRY(c, c->st_copies.ensure((size_t)take * sizeof(mmp_status_copy)));
-        mmp_status_copy *d_copies = c->st_copies.as<mmp_status_copy>();
-        hipLaunchKernelGGL(status_emit_kernel, dim3(div_up(total, kStatusBlock)), dim3(kStatusBlock), 0, st, d_reqs, n, total, models, ent_pod,
-                           ent_time, now, d_rows, d_aux, d_copies, take);
-        if (n_long > 0)
-            hipLaunchKernelGGL(status_long_kernel, dim3(n_long), dim3(kStatusLongBlock), 0, st, d_reqs, d_long, models, ent_pod, ent_time, now,
-                               d_rows, d_aux, d_copies, take);
-    }
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    // every word of copies[0, take) has exactly one writer above: the ranks of a segment are a permutation of its indices
-    if (take > 0) HIP_TRY(c, copy_sync(c, copies_out, c->st_copies.p, (size_t)take * sizeof(mmp_status_copy), hipMemcpyDeviceToHost));
-    HIP_TRY(c, copy_sync(c, rows_out, d_rows, (size_t)n * sizeof(mmp_status_row), hipMemcpyDeviceToHost));
-    kt_collect(c);
-    *n_copies_out = total;
-    return MMP_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, reqs, (size_t)n * sizeof(mmp_status_req), hipMemcpyHostToDevice, c->stream));
+    return status_drive(c, "mmp_models_status", n, now, pods, P, rows_out, copies_out, max_copies, n_copies_out);
 } MMP_CATCH(c, "mmp_models_status")
+
+// getStatus by model id: the keys resolved and the requests written on the device, in front of the pipeline (status_keyed_kernel).
+int mmp_models_status_k(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, const int32_t *fail_pod, const uint32_t *flags,
+                        int64_t now, int32_t *model_idx_out, mmp_status_row *rows_out, mmp_status_copy *copies_out, int32_t max_copies,
+                        int32_t *n_copies_out)
+try {
+    if (!c || !n_copies_out || n < 0 || max_copies < 0 || (n > 0 && (!key_off || !rows_out)) || (max_copies > 0 && !copies_out))
+        return fail(c, MMP_EINVAL, "mmp_models_status_k: bad argument");
+    // the locking of mmp_models_status; the model-id table is batch_mu's as well (mmp_model_ids_resolve)
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (const int rc = model_id_space_guard(c, "mmp_models_status_k")) return rc;
+    // (everything that is refused, before anything is staged)
+    if (const int rc = check_offsets(c, "mmp_models_status_k", "key ", key_off, n)) return rc;
+    if (n > 0 && key_off[n] > key_off[0] && !keys) return fail(c, MMP_EINVAL, "mmp_models_status_k: bad argument");
+    bool overlay = false;
+    for (int32_t i = 0; i < n; i++) {
+        if (fail_pod && fail_pod[i] < -1) return fail(c, MMP_EINVAL, "mmp_models_status_k: request %d names pod %d", i, fail_pod[i]);
+        if (flags && (flags[i] & ~MMP_MSTF_MISS)) return fail(c, MMP_EINVAL, "mmp_models_status_k: request %d has flags %u", i, flags[i]);
+        overlay |= fail_pod && fail_pod[i] >= 0;
+    }
+    int32_t P = 0;
+    const mmp_pod_row *pods = nullptr;  // the committed rows, read for id_order by the overlay alone
+    if (overlay) {
+        if (now <= 0) return fail(c, MMP_EINVAL, "mmp_models_status_k: now_ms = %lld with a fail_pod", (long long)now);
+        if (const int rc = plan_state_guard(c, "mmp_models_status_k")) return rc;
+        P = c->snap.P;
+        pods = c->sb[c->cur].pods.as<mmp_pod_row>();
+        for (int32_t i = 0; i < n; i++)
+            if (fail_pod[i] >= P) return fail(c, MMP_EINVAL, "mmp_models_status_k: request %d names pod %d of %d", i, fail_pod[i], P);
+    }
+    if (n == 0) {
+        *n_copies_out = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel;
+    if (const int rc = stage_strings(c, "mmp_models_status_k", "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+    HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    HIP_TRY(c, c->plan.rows_in.ensure((size_t)n * sizeof(mmp_status_req)));
+    if (fail_pod) {
+        HIP_TRY(c, c->sk_fpod.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->sk_fpod.p, fail_pod, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (flags) {
+        HIP_TRY(c, c->sk_flags.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->sk_flags.p, flags, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    // (the staged copy keeps keyed_resolve_kernel's contract: the buffer is an allocation of its own with 16 bytes behind the keys)
+    const StKeyArgs A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                      fail_pod ? c->sk_fpod.as<int32_t>() : nullptr, flags ? c->sk_flags.as<uint32_t>() : nullptr, c->me_row.as<int32_t>(),
+                      c->plan.rows_in.as<mmp_status_req>()};
+    const int rc = status_drive(c, "mmp_models_status_k", n, now, pods, P, rows_out, copies_out, max_copies, n_copies_out, [&]() -> int {
+        hipLaunchKernelGGL(status_keyed_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+        return MMP_OK;
+    });
+    if (rc) return rc;
+    if (model_idx_out) HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_models_status_k")
+
+// getVModelStatus in full: the vmodel keys resolved, the vrows, both requests per vmodel and the string lengths written on the
+// device in front of the pipeline (vstatus_keyed_kernel); the strings copied behind its one read-back of the sizes.
+int mmp_vmodels_status(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, const char *owners, const int32_t *owner_off,
+                       const uint32_t *req_flags, int64_t now, mmp_vstatus_row *vrows_out, mmp_status_row *rows_out,
+                       mmp_status_copy *copies_out, int32_t max_copies, int32_t *n_copies_out, char *str_bytes_out, int32_t max_str_bytes,
+                       int32_t *str_off_out, int32_t *n_str_bytes_out)
+try {
+    if (!c || !n_copies_out || !n_str_bytes_out || n < 0 || max_copies < 0 || max_str_bytes < 0 ||
+        (n > 0 && (!key_off || !vrows_out || !rows_out)) || (max_copies > 0 && !copies_out) || (max_str_bytes > 0 && !str_bytes_out))
+        return fail(c, MMP_EINVAL, "mmp_vmodels_status: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);  // the locking of mmp_vmodels_resolve and mmp_models_status: one hold for the whole answer
+    if (const int rc = model_id_space_guard(c, "mmp_vmodels_status")) return rc;
+    if (n > INT32_MAX / 8) return fail(c, MMP_EINVAL, "mmp_vmodels_status: %d keys in one call", n);
+    // (both kinds and the flags, before anything is staged)
+    if (const int rc = check_offsets(c, "mmp_vmodels_status", "key ", key_off, n)) return rc;
+    if (owner_off)
+        if (const int rc = check_offsets(c, "mmp_vmodels_status", "owner ", owner_off, n)) return rc;
+    if (n > 0 && ((key_off[n] > key_off[0] && !keys) || (owner_off && owner_off[n] > owner_off[0] && !owners)))
+        return fail(c, MMP_EINVAL, "mmp_vmodels_status: bad argument");
+    if (req_flags)
+        for (int32_t i = 0; i < n; i++)
+            if (req_flags[i] & ~MMP_VMRQ_AFTER_STRONG) return fail(c, MMP_EINVAL, "mmp_vmodels_status: request %d has unknown flag bits", i);
+    if (n == 0) {
+        *n_copies_out = 0;
+        *n_str_bytes_out = 0;
+        if (str_off_out) str_off_out[0] = 0;
+        return MMP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel, orel;
+    if (const int rc = stage_strings(c, "mmp_vmodels_status", "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+    if (owner_off)
+        if (const int rc = stage_strings(c, "mmp_vmodels_status", "owner ", owners, owner_off, n, c->vm_ow_bytes, c->vm_ow_off, orel)) return rc;
+    if (req_flags) {
+        HIP_TRY(c, c->vm_rflags.ensure((size_t)n * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->vm_rflags.p, req_flags, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    const size_t n_str = 3 * (size_t)n;
+    HIP_TRY(c, c->vm_ans.ensure((size_t)n * sizeof(mmp_vstatus_row)));
+    HIP_TRY(c, c->plan.rows_in.ensure(2 * (size_t)n * sizeof(mmp_status_req)));
+    HIP_TRY(c, c->j_cnt.ensure((n_str + 1) * 4));
+    HIP_TRY(c, c->j_offs.ensure((n_str + 1) * 4));
+    HIP_TRY(c, c->sk_sc.ensure(sizeof(VStKeyScalars)));
+    int32_t *d_len = c->j_cnt.as<int32_t>(), *d_pos = c->j_offs.as<int32_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_len, d_pos, (int32_t)0, n_str + 1, rocprim::plus<int32_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    HIP_TRY(c, hipMemsetAsync(c->sk_sc.p, 0, sizeof(VStKeyScalars), st));
+    const VmTab V = vmodel_tab(c);
+    const VStKeyArgs A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), owner_off ? c->vm_ow_bytes.as<char>() : nullptr,
+                       owner_off ? c->vm_ow_off.as<int32_t>() : nullptr, req_flags ? c->vm_rflags.as<uint32_t>() : nullptr, n,
+                       hash_mask(c->tune.vmodel_id_hash_bits), V, vmodel_models(c), c->vm_ans.as<mmp_vstatus_row>(),
+                       c->plan.rows_in.as<mmp_status_req>(), d_len, c->sk_sc.as<VStKeyScalars>()};
+    VStKeyScalars hv{};
+    bool want_str = false;
+    const int rc = status_drive(
+        c, "mmp_vmodels_status", 2 * n, now, nullptr, 0, rows_out, copies_out, max_copies, n_copies_out,
+        [&]() -> int {  // the requests, and the strings' lengths scanned
+            hipLaunchKernelGGL(vstatus_keyed_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+            HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_len, d_pos, (int32_t)0, n_str + 1, rocprim::plus<int32_t>(), st));
+            return MMP_OK;
+        },
+        [&]() -> int {  // the strings' total, read back with the copy total
+            HIP_TRY(c, hipMemcpyAsync(&hv, c->sk_sc.p, sizeof hv, hipMemcpyDeviceToHost, st));
+            return MMP_OK;
+        },
+        [&]() -> int {
+            if (hv.n_str_bytes > (unsigned long long)INT32_MAX)
+                return fail(c, MMP_EINVAL, "mmp_vmodels_status: %llu string bytes in all; split the batch", hv.n_str_bytes);
+            want_str = hv.n_str_bytes > 0 && (unsigned long long)max_str_bytes >= hv.n_str_bytes;
+            if (want_str) HIP_TRY(c, c->sk_str.ensure((size_t)hv.n_str_bytes));
+            return MMP_OK;
+        },
+        [&]() -> int {
+            if (want_str)
+                hipLaunchKernelGGL(vstatus_strings_kernel, dim3(div_up((int)n_str, 256)), dim3(256), 0, st, A.vrows, (int32_t)n_str, d_pos, V,
+                                   c->sk_str.as<char>());
+            return MMP_OK;
+        });
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(vrows_out, c->vm_ans.p, (size_t)n * sizeof(mmp_vstatus_row), hipMemcpyDeviceToHost, st));
+    if (str_off_out) HIP_TRY(c, hipMemcpyAsync(str_off_out, d_pos, (n_str + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (want_str) HIP_TRY(c, hipMemcpyAsync(str_bytes_out, c->sk_str.p, (size_t)hv.n_str_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *n_str_bytes_out = (int32_t)hv.n_str_bytes;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_vmodels_status")
 
 // THE TWO-PASS FRAME of the "next stored value" calls (rewrite_kernels.hpp, register_kernels.hpp): stored values in, rendered
 // values out.  The caller (owner of batch_mu, the device set, every refusal behind it) has staged its own inputs and filled its

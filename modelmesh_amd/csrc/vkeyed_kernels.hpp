@@ -10,7 +10,7 @@
 //
 // What the host did in two calls (mmp_vmodels_resolve under the batch lock, then a _c call on the row it answered) is one launch in
 // front of the decision.  The kernel reads the vmodel rows, the string arena and the two id tables — never the registry rows: the
-// target's status stays with mmp_vmodels_resolve (getVModelStatus is not on the request path).  There are no owners here either:
+// target's status is the management path's (getVModelStatus is not on the request path: mmp_vmodels_status, status_keyed_kernels.hpp).  There are no owners here either:
 // resolveVModelId on the request path takes none.
 //
 // The bytes.  On a slot the vmodel keys and the notFoundModelId spans lie in pinned host memory; a workgroup's keys are contiguous

@@ -326,6 +326,24 @@ __device__ __forceinline__ VmChoice vm_choose(const VmTab &V, const VmRow &r, co
     return VmChoice{MMP_VMR_TARGET_NOT_FOUND, -1};  // :594
 }
 
+// The class of statusFromRecord (:555-556) and of resolveTargetModelStatusInfo (:537-549) for a row whose tmid resolved to the
+// registry row target_model (-1: null or unknown), stated once for vm_resolve_kernel and vstatus_keyed_kernel
+// (status_keyed_kernels.hpp).  Not in transition: DEFINED / NONE.
+struct VmStatus {
+    int32_t vstatus, target_status;
+};
+__device__ __forceinline__ VmStatus vm_status_of(const VmTab &V, const VmModels &M, const VmRow &r, int32_t target_model)
+{
+    if (!vm_in_transition(V, r)) return VmStatus{MMP_VMS_DEFINED, MMP_VMT_NONE};
+    const bool failed = r.flags & kVmfFailed;
+    VmStatus s{failed ? MMP_VMS_TRANSITION_FAILED : MMP_VMS_TRANSITIONING, MMP_VMT_NOT_FOUND};
+    if (target_model >= 0) {
+        const mmp_model_row t = M.rows[target_model];
+        if (!vm_model_empty(t)) s.target_status = failed && t.n_failed > 0 && t.n_loaded == 0 ? MMP_VMT_LOADING_FAILED : MMP_VMT_LOADING;
+    }
+    return s;
+}
+
 // resolveVModelId and absentOrOwnerMismatch (vm_choose), the class of statusFromRecord
 // (:555-556) and of resolveTargetModelStatusInfo (:537-549).  Spans: key i, and where given nf i and owner i; an empty span is
 // Java null.
@@ -360,16 +378,9 @@ __global__ __launch_bounds__(kIdTabBlock) void vm_resolve_kernel(const char *__r
             a.model = which ? a.target_model : vm_model_of(V, M, r, 0);
             if (r.flags & (kVmfActiveNull << which)) a.flags |= MMP_VMRF_NULL_ID;
         }
-        if (vm_in_transition(V, r)) {
-            const bool failed = r.flags & kVmfFailed;
-            a.vstatus = failed ? MMP_VMS_TRANSITION_FAILED : MMP_VMS_TRANSITIONING;
-            a.target_status = MMP_VMT_NOT_FOUND;
-            if (a.target_model >= 0) {
-                const mmp_model_row t = M.rows[a.target_model];
-                if (!vm_model_empty(t))
-                    a.target_status = failed && t.n_failed > 0 && t.n_loaded == 0 ? MMP_VMT_LOADING_FAILED : MMP_VMT_LOADING;
-            }
-        }
+        const VmStatus vs = vm_status_of(V, M, r, a.target_model);
+        a.vstatus = vs.vstatus;
+        a.target_status = vs.target_status;
     }
     out[i] = a;
 }

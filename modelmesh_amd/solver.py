@@ -1406,6 +1406,95 @@ class Solver:
         got = max_copies if rc != 0 else min(max_copies, max(total.value, 0))
         return rows[:n].copy(), copies[:got].copy(), total.value, rc
 
+    def models_status_k_raw(self, keys, now, max_copies, fail_pod=None, flags=None, fill=0, key_off=None, null_out=False,
+                            null_idx=False):
+        """One mmp_models_status_k call with exactly this capacity (0: a NULL copies buffer), the outputs filled with the byte `fill`
+        first: (model_idx, rows, copies[:min(total, max_copies)] — all max_copies rows when the call fails —, total, rc).  Does not
+        raise.  fail_pod / flags: n words or None (NULL); key_off replaces the packed offsets; null_out: NULL rows_out and
+        n_copies_out; null_idx: NULL model_idx_out."""
+        from ._lib import STATUS_COPY, STATUS_ROW
+        n = len(keys)
+        blob, off = self._pack(keys)
+        off32 = off.astype(np.int32) if key_off is None else np.ascontiguousarray(key_off, dtype=np.int32)
+        fp = None if fail_pod is None else np.ascontiguousarray(fail_pod, dtype=np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint32)
+        idx = np.zeros(max(n, 1), np.int32)
+        rows = np.zeros(max(n, 1), dtype=STATUS_ROW)
+        copies = np.zeros(max(max_copies, 1), dtype=STATUS_COPY)
+        for a in (idx, rows, copies):
+            a.view(np.uint8)[:] = fill
+        total = C.c_int32(-1)
+        rc = self.lib.mmp_models_status_k(self.h, blob, ptr(off32), n, ptr(fp), ptr(fl), int(now), None if null_idx else ptr(idx),
+                                          None if null_out else ptr(rows), ptr(copies) if max_copies else None, int(max_copies),
+                                          None if null_out else C.byref(total))
+        got = max_copies if rc != 0 else min(max_copies, max(total.value, 0))
+        return idx[:n].copy(), rows[:n].copy(), copies[:got].copy(), total.value, rc
+
+    def models_status_k(self, keys, now: int, fail_pod=None, flags=None):
+        """getStatus by model id (mmp_models_status_k): (model_idx, rows, copies) — what model_ids_resolve and models_status answer,
+        from one call under one hold of the batch lock; an unknown id and the empty row a deletion leaves answer MST_NOT_FOUND.  Two
+        calls: the sizes, then the list; repeated if the registry changed in between."""
+        max_copies = self.models_status_k_raw(keys, now, 0, fail_pod, flags)[3]
+        while True:
+            idx, rows, copies, total, rc = self.models_status_k_raw(keys, now, max(max_copies, 0), fail_pod, flags)
+            self._ck(rc)
+            if total <= max_copies:
+                return idx, rows, copies
+            max_copies = total
+
+    def vmodels_status_raw(self, keys, now, max_copies, max_str_bytes, owners=None, req_flags=None, fill=0, key_off=None,
+                           owner_off=None, null_out=False, null_str_off=False):
+        """One mmp_vmodels_status call with exactly these capacities (0: a NULL buffer), the outputs filled with the byte `fill`
+        first.  owners: a list of bytes/str/None (None and b"" are Java null), or None for NULL buffers.  Returns a dict: vrows,
+        rows (2n), copies (the part written; all of it when the call fails), n_copies, str_off (3n + 1), str_bytes (the whole
+        buffer), n_str_bytes, rc.  Does not raise."""
+        from ._lib import STATUS_COPY, STATUS_ROW, VSTATUS_ROW
+        n = len(keys)
+        kblob, koff = self._pack(keys)
+        koff32 = koff.astype(np.int32) if key_off is None else np.ascontiguousarray(key_off, dtype=np.int32)
+        oblob = ooff = None
+        if owners is not None:
+            oblob, ooff = self._pack([x if x is not None else b"" for x in owners])
+            ooff = ooff.astype(np.int32) if owner_off is None else np.ascontiguousarray(owner_off, dtype=np.int32)
+        rf = None if req_flags is None else np.ascontiguousarray(req_flags, dtype=np.uint32)
+        vrows = np.zeros(max(n, 1), VSTATUS_ROW)
+        rows = np.zeros(max(2 * n, 1), STATUS_ROW)
+        copies = np.zeros(max(max_copies, 1), STATUS_COPY)
+        soff = np.zeros(3 * n + 1, np.int32)
+        sbytes = np.zeros(max(max_str_bytes, 1), np.uint8)
+        for a in (vrows, rows, copies, soff, sbytes):
+            a.view(np.uint8)[:] = fill
+        nc, ns = C.c_int32(-1), C.c_int32(-1)
+        rc = self.lib.mmp_vmodels_status(self.h, kblob, ptr(koff32), n, oblob, ptr(ooff), ptr(rf), int(now),
+                                         None if null_out else ptr(vrows), None if null_out else ptr(rows),
+                                         ptr(copies) if max_copies else None, int(max_copies), None if null_out else C.byref(nc),
+                                         ptr(sbytes) if max_str_bytes else None, int(max_str_bytes), None if null_str_off else ptr(soff),
+                                         C.byref(ns))
+        got = max_copies if rc != 0 else min(max_copies, max(nc.value, 0))
+        return dict(vrows=vrows[:n].copy(), rows=rows[:2 * n].copy(), copies=copies[:got].copy(), n_copies=nc.value, str_off=soff,
+                    str_bytes=sbytes[:max_str_bytes].copy(), n_str_bytes=ns.value, rc=rc)
+
+    def vmodels_status(self, keys, now: int, owners=None, req_flags=None):
+        """getVModelStatus in full (mmp_vmodels_status): (vrows, rows, copies, strings) — one mmp_vstatus_row per key, the active
+        model's status row at rows[2i] and the target's at rows[2i + 1] with their copies, and strings[i] = (amid, tmid, o) as bytes,
+        None where the row's flags say null.  Every part of one answer is of one state.  Two calls: the sizes, then the lists;
+        repeated if the state changed in between."""
+        r = self.vmodels_status_raw(keys, now, 0, 0, owners, req_flags)
+        self._ck(r["rc"])
+        mc, ms = r["n_copies"], r["n_str_bytes"]
+        while True:
+            r = self.vmodels_status_raw(keys, now, mc, ms, owners, req_flags)
+            self._ck(r["rc"])
+            if r["n_copies"] <= mc and r["n_str_bytes"] <= ms:
+                break
+            mc, ms = max(mc, r["n_copies"]), max(ms, r["n_str_bytes"])
+        raw, soff, vrows = r["str_bytes"].tobytes(), r["str_off"], r["vrows"]
+        null = (_lib.VMF_ACTIVE_NULL, _lib.VMF_TARGET_NULL, _lib.VMF_OWNER_NULL)
+        found = [int(v["cls"]) in (_lib.VMR_OK, _lib.VMR_STRONG_READ) for v in vrows]
+        strings = [tuple(None if (not found[i] or vrows[i]["flags"] & null[k]) else raw[soff[3 * i + k]:soff[3 * i + k + 1]]
+                         for k in range(3)) for i in range(len(keys))]
+        return vrows, r["rows"], r["copies"], strings
+
     def registry_census(self):
         """The registry listener's model counts (MM.java:2807-2854, :6852-6863) over the resident registry: (stats, pod_loaded,
         pod_failed, type_stats) — one mmp_registry_stats row, per pod slot of the staged instance table the records that hold it in
