@@ -1066,9 +1066,51 @@ typedef struct {
  * appended to the entry arena on the device and the rows rewritten in place under the protocol of mmp_models_upsert;
  * MMP_ROPS_DRY (alone).  When edits_out is too small the prefix that fits and the totals are returned with truncated = 1 and
  * NOTHING is applied.  edits_out may be NULL with a capacity of 0; a NULL status_out is not
- * returned. */
+ * returned.
+ *
+ * This call is by registry row and keeps its 56-byte info and its four kinds: it refuses MMP_ROP_DROP_LOCAL (kind 4) and never
+ * answers MMP_ROP_NO_RECORD.  The fifth kind, and all five by model id, are mmp_registry_ops_k below. */
 int mmp_registry_ops(mmp_ctx *ctx, const mmp_registry_op *ops, int32_t n, int64_t now_ms, uint32_t flags, uint8_t *status_out,
                      mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info_out);
+/* The same edits BY MODEL ID, and the fifth kind: mmp_model_ids_resolve and mmp_registry_ops as ONE staged call under one hold of
+ * the batch lock, so that no registry event batch and no mmp_models_retire can land between the row a key names and the edit of
+ * that row (csrc/registry_ops_keyed_kernels.hpp: one launch in front of the unchanged evaluation).
+ *   ops                n ops; with keys the `model` field is ignored
+ *   keys / key_off     n keys, raw id bytes, under the conventions of mmp_model_ids_resolve; BOTH NULL: the by-row form
+ *   model_idx_out      n words, may be NULL (by row: ops[i].model again)
+ *   status_out, edits_out, max_edits, flags: exactly as mmp_registry_ops (truncation, MMP_ROPS_APPLY / MMP_ROPS_DRY / 0, NULLs)
+ *
+ *   MMP_ROP_DROP_LOCAL (invokeModel's cache-hit loop: goLocal and getFromCache == null, MM.java:3682-3687) — always an edit (the
+ *     record is always submitted, as for MMP_ROP_REGISTER): instanceIds.remove(pod), whether or not the key is there and whatever
+ *     its time; updateLastUsed(last_used) (0 = now).  There is NO updateLastUnloadTime — MMP_ROP_EDIT_UNLOAD_SET is never set,
+ *     the difference from MMP_ROP_DEREGISTER and MMP_ROP_SCALE_DOWN — and loadFailedInstanceIds is not touched.  No MMP_ROPF_*
+ *     bit is valid; load_time / load_complete_time are not read.  The edit's flags: MMP_ROP_EDIT_REM_LOADED if the entry went,
+ *     MMP_ROP_EDIT_TOUCHED if last_used rose; inserted_pos is -1.  refreshAfterUpdatedModelRecord and the KV-error branch
+ *     (:3693-3709, whose failed placeholder entry is an op of mmp_cache_replay) stay with the caller.
+ *
+ * THE RULE BY KEY: model_idx_out[i] is what mmp_model_ids_resolve answers for key i.  Op i is evaluated exactly as
+ * mmp_registry_ops evaluates it with `model` set to the row model_idx_out[i] names.  When the id is unknown OR that row is the
+ * empty row — the all-zero row a deleted record leaves, the definition of MMP_RETIRE_EMPTY_ONLY and the rule of
+ * mmp_models_status_k — the op is MMP_ROP_NO_RECORD (registry.get / getOrStrongIfAbsent == null, the Java returns, :2481,
+ * :2945): it makes no edit, counts in n_no_record and in no per-kind total, and touches nothing.  Resolution, evaluation and
+ * apply run under one hold of the batch lock.  By row an empty row is an ordinary record, as in mmp_registry_ops.
+ *
+ * MMP_EINVAL, with nothing written or changed: everything mmp_registry_ops refuses, with the kinds 0..4 valid (by key there is no
+ * model range to refuse); a flag bit on a MMP_ROP_DROP_LOCAL op; key offsets that are not monotone; keys without key_off or
+ * key_off without keys; two ops whose keys resolve to the same live row (two MMP_ROP_NO_RECORD ops under one unknown key are
+ * not duplicates).  MMP_ESTATE before the first commit and, with keys, under the conditions of mmp_model_ids_resolve.  n == 0 is
+ * valid; two runs over the same state with flags 0 are byte-identical. */
+#define MMP_ROP_DROP_LOCAL 4 /* invokeModel's cache-hit loop: goLocal, getFromCache == null (MM.java:3682-3687) */
+#define MMP_ROP_NO_RECORD 2  /* status byte: the key is unknown or names the empty row a deleted record leaves —
+                                registry.get / getOrStrongIfAbsent == null, the Java returns (:2481, :2945) */
+typedef struct {
+    int32_t n_edits, n_unchanged, n_no_record, truncated; /* n_edits + n_unchanged + n_no_record == n */
+    int32_t n_edited_op[8], n_unchanged_op[8];            /* per MMP_ROP_* kind, 5 used */
+    int32_t n_entries_added, n_entries_removed;
+} mmp_registry_ops_info_k; /* 88 bytes */
+int mmp_registry_ops_k(mmp_ctx *ctx, const mmp_registry_op *ops, int32_t n, const char *keys, const int32_t *key_off,
+                       int64_t now_ms, uint32_t flags, int32_t *model_idx_out, uint8_t *status_out,
+                       mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info_k *info_out);
 
 /* getStatus (MM.java:3247) answered from the resident registry, a batch of questions at a time: the status class of
  * invokeModel's "getStatus case" (:3760-3768) and the copy list makeStatusInfo builds for the reply (:3013-3058).  Each answer
@@ -1316,7 +1358,9 @@ int mmp_registry_unresolved(mmp_ctx *ctx, int32_t *model_out, int32_t max_models
  * required buffer, non-monotone offsets, two equal ids. */
 int mmp_model_ids_load(mmp_ctx *ctx, const char *ids, const int32_t *id_off, int32_t n_models);
 /* model_idx_out[i] = the registry row of key i = keys[key_off[i], key_off[i+1]), -1 for an id the table does not know.
- * Read-only: this is how a host asks mmp_models_status / mmp_registry_ops / a request row by id.  MMP_ESTATE before
+ * Read-only: this is how a host that keeps the row map itself (and renumbers it after mmp_models_retire) learns a row.  A host
+ * without a map does not resolve and then call — a retirement could land between the two: it asks by id in one call
+ * (mmp_models_status_k, mmp_registry_ops_k, the _ck / _cv request seams).  MMP_ESTATE before
  * mmp_model_ids_load and when the registry has been resized by index since (see mmp_models_events_json).  n == 0 is valid. */
 int mmp_model_ids_resolve(mmp_ctx *ctx, const char *keys, const int32_t *key_off, int32_t n, int32_t *model_idx_out);
 /* The way back: the ids of rows [first_row, first_row + n_rows) — the prune, janitor, unresolved and status calls answer in rows.

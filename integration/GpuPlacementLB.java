@@ -170,6 +170,14 @@ final class MmPlace {
     // mmp_registry_ops_info (56 bytes); info.truncated: nothing was applied.
     static native int registryOps(long h, ByteBuffer ops, int n, long nowMs, int flags, ByteBuffer statusOut, ByteBuffer editsOut,
                                   int maxEdits, ByteBuffer info);
+    // the same BY MODEL ID (mmp_registry_ops_k): keys / keyOff name the record of op i (the op's model field is ignored; both null:
+    // by row), resolved, evaluated and applied under ONE hold of the batch lock — no event batch or modelsRetire can land between
+    // the row and its edit.  op 4 = the cache-hit loop dropping its own copy (:3682-3687; always an edit, no lastUnloadTime, no
+    // flag bit).  statusOut 2 = no record (unknown id, or deleted: registry.get == null, the Java returns); modelIdxOut = n ints (may
+    // be null); info = one mmp_registry_ops_info_k (88 bytes: nEdits, nUnchanged, nNoRecord, truncated, int[8] edited per kind,
+    // int[8] unchanged per kind, entries added, entries removed).
+    static native int registryOpsKeyed(long h, ByteBuffer ops, int n, ByteBuffer keys, ByteBuffer keyOff, long nowMs, int flags,
+                                       ByteBuffer modelIdxOut, ByteBuffer statusOut, ByteBuffer editsOut, int maxEdits, ByteBuffer info);
     // getStatus (MM.java:3247) from the resident registry: reqs = mmp_status_req rows (16 bytes: model or -1 for mr == null, failPod =
     // the pod of mle.getInstanceId() or -1, flags 1 = the cache-hit loop is exhausted, 0).  rowsOut = mmp_status_row rows (16 bytes:
     // class 0 NOT_FOUND / 1 NOT_LOADED / 2 LOADING_FAILED / 3 ask a copy, copyOff, nNotChecked, nFailed), copiesOut = mmp_status_copy
@@ -457,6 +465,67 @@ final class VModelCall {
             flags.putInt(0, AFTER_STRONG);
         }
         return new int[] { vm.getInt(0), vm.getInt(4), vm.getInt(8), vm.getInt(12), vm.getInt(16) };
+    }
+}
+
+/**
+ * The five sites at which an instance edits a ModelRecord itself, for a binding without an id map (modelIdsResident() == true): ONE
+ * registryOpsKeyed call per site instead of modelIdsResolve + registryOps, so that the row and its edit are of one state of the
+ * registry.  Each method answers the edit (null: the Java returns without a compare-and-set — nothing changed, or there is no
+ * record); the caller submits the record through registry.conditionalSetAndGet as before and keeps the retry loop, loadFailureInfos
+ * and refreshAfterUpdatedModelRecord.
+ */
+final class RegistryOpsById {
+    static final int REGISTER = 0, LOAD_FAILED = 1, DEREGISTER = 2, SCALE_DOWN = 3, DROP_LOCAL = 4;
+    static final int SHUTTING_DOWN = 1, MATCH_TIME = 2;         // op flags
+    static final int UNCHANGED = 0, EDITED = 1, NO_RECORD = 2;  // status bytes
+    static final int APPLY = 1;
+
+    /** one edit: the mmp_registry_op_edit row */
+    static final class Edit {
+        int row, nLoadedAfter, nFailedAfter, flags, insertedPos;   // flags: 1 rem loaded, 2 rem failed, 4 put loaded, 8 put failed,
+        long lastUsedAfter, lastUnloadAfter;                       //   16 replaced, 32 lastUsed raised, 64 lastUnloadAfter is to be stored
+    }
+
+    private static Edit one(GpuMeshBinding mesh, String modelId, int pod, int op, int flags, long lastUsed, long loadTime,
+                            long loadCompleteTime, long nowMs) {
+        if (!mesh.modelIdsResident()) throw new IllegalStateException("a binding with an id map sends rows: MmPlace.registryOps");
+        final ByteBuffer[] key = ModelKey.of(modelId);
+        final ByteBuffer row = MmPlace.direct(40), status = MmPlace.direct(1), edit = MmPlace.direct(40), info = MmPlace.direct(88);
+        row.putInt(0, -1); row.putInt(4, pod); row.putInt(8, op); row.putInt(12, flags);
+        row.putLong(16, lastUsed); row.putLong(24, loadTime); row.putLong(32, loadCompleteTime);
+        MmPlace.registryOpsKeyed(mesh.handle(), row, 1, key[0], key[1], nowMs, APPLY, null, status, edit, 1, info);
+        if (status.get(0) != EDITED) return null;               // UNCHANGED, or NO_RECORD: mr == null (:2481, :2945)
+        final Edit e = new Edit();
+        e.row = edit.getInt(0); e.nLoadedAfter = edit.getInt(8); e.nFailedAfter = edit.getInt(12);
+        e.flags = edit.getInt(16); e.insertedPos = edit.getInt(20);
+        e.lastUsedAfter = edit.getLong(24); e.lastUnloadAfter = edit.getLong(32);
+        return e;
+    }
+
+    /** loadLocal's put, MM.java:5204-5207 */
+    static Edit registered(GpuMeshBinding mesh, String modelId, int self, long lastUsed, long loadTime, long nowMs) {
+        return one(mesh, modelId, self, REGISTER, 0, lastUsed, loadTime, 0L, nowMs);
+    }
+    /** the CacheEntry failure path, :2484-2495 */
+    static Edit loadFailed(GpuMeshBinding mesh, String modelId, int self, boolean shuttingDown, long lastUsed, long loadTime,
+                           long loadCompleteTime, long nowMs) {
+        return one(mesh, modelId, self, LOAD_FAILED, shuttingDown ? SHUTTING_DOWN : 0, lastUsed, loadTime, loadCompleteTime, nowMs);
+    }
+    /** deregisterModel, :2948-2958; loadTime null: either entry goes if present */
+    static Edit deregistered(GpuMeshBinding mesh, String modelId, int self, long lastUsed, Long loadTime, long loadCompletedTime,
+                             long nowMs) {
+        return one(mesh, modelId, self, DEREGISTER, loadTime != null ? MATCH_TIME : 0, lastUsed, loadTime != null ? loadTime : 0L,
+                   loadCompletedTime, nowMs);
+    }
+    /** removeLocalModelCopyAsync, :6347-6365, sent after isLoadedElsewhere */
+    static Edit scaledDown(GpuMeshBinding mesh, String modelId, int self, long lastUsed, long loadTime, long nowMs) {
+        return one(mesh, modelId, self, SCALE_DOWN, 0, lastUsed, loadTime, 0L, nowMs);
+    }
+    /** invokeModel's cache-hit loop: goLocal and getFromCache == null, :3682-3687 — always an edit when the record exists; the
+     *  KV-error branch (:3693-3709) stays with the caller */
+    static Edit droppedLocal(GpuMeshBinding mesh, String modelId, int self, long lastUsed, long nowMs) {
+        return one(mesh, modelId, self, DROP_LOCAL, 0, lastUsed, 0L, 0L, nowMs);
     }
 }
 

@@ -620,6 +620,26 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryOps(JNIEnv 
                  mmp_registry_ops(ctx_of(h), buf<mmp_registry_op>(env, ops), n, nowMs, static_cast<uint32_t>(flags), buf<uint8_t>(env, statusOut),
                                   buf<mmp_registry_op_edit>(env, editsOut), maxEdits, buf<mmp_registry_ops_info>(env, info)));
 }
+// the same BY MODEL ID, with the fifth kind (the cache-hit loop's drop of its own copy, MM.java:3682-3687): the keys resolved, the
+// ops evaluated and the edits applied under one hold of the batch lock (mmp_registry_ops_k).  keys and keyOff both null: by row.
+// modelIdxOut and statusOut may be null; info holds one mmp_registry_ops_info_k (88 bytes).
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryOpsKeyed(JNIEnv *env, jclass, jlong h, jobject ops, jint n, jobject keys,
+                                                                              jobject keyOff, jlong nowMs, jint flags, jobject modelIdxOut,
+                                                                              jobject statusOut, jobject editsOut, jint maxEdits, jobject info)
+{
+    if (n < 0 || maxEdits < 0 || !holds<mmp_registry_op>(env, ops, n, "registryOpsKeyed: ops shorter than n") ||
+        (keyOff && !holds<int32_t>(env, keyOff, (jlong)n + 1, "registryOpsKeyed: keyOff shorter than n + 1")) ||
+        (keyOff && keys && n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "registryOpsKeyed: keys shorter than keyOff[n]")) ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "registryOpsKeyed: modelIdxOut shorter than n")) ||
+        (statusOut && !holds<uint8_t>(env, statusOut, n, "registryOpsKeyed: statusOut shorter than n")) ||
+        !holds<mmp_registry_op_edit>(env, editsOut, maxEdits, "registryOpsKeyed: editsOut shorter than maxEdits") ||
+        !holds<mmp_registry_ops_info_k>(env, info, 1, "registryOpsKeyed: info shorter than one mmp_registry_ops_info_k"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_registry_ops_k(ctx_of(h), buf<mmp_registry_op>(env, ops), n, buf<char>(env, keys), buf<int32_t>(env, keyOff), nowMs,
+                                    static_cast<uint32_t>(flags), buf<int32_t>(env, modelIdxOut), buf<uint8_t>(env, statusOut),
+                                    buf<mmp_registry_op_edit>(env, editsOut), maxEdits, buf<mmp_registry_ops_info_k>(env, info)));
+}
 // getStatus answers from the resident registry (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058): every
 // buffer's capacity is checked here, the library only knows n / maxCopies.  A null copiesOut with maxCopies = 0: the sizes only.
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_modelsStatus(JNIEnv *env, jclass, jlong h, jobject reqs, jint n, jlong nowMs,

@@ -158,6 +158,13 @@ REGISTRY_OPS_INFO = np.dtype([("n_edits", "<i4"), ("n_unchanged", "<i4"), ("trun
                               ("n_edited_op", "<i4", (4,)), ("n_unchanged_op", "<i4", (4,)), ("n_entries_added", "<i4"),
                               ("n_entries_removed", "<i4")])
 assert REGISTRY_OP.itemsize == 40 and REGISTRY_OP_EDIT.itemsize == 40 and REGISTRY_OPS_INFO.itemsize == 56
+# mmp_registry_ops_k: the same by model id, and the fifth kind (the cache-hit loop's drop of its own copy, MM.java:3682-3687)
+ROP_DROP_LOCAL = 4
+ROP_NO_RECORD = 2  # status byte: the key is unknown or names the empty row (registry.get == null, :2481 / :2945)
+REGISTRY_OPS_INFO_K = np.dtype([("n_edits", "<i4"), ("n_unchanged", "<i4"), ("n_no_record", "<i4"), ("truncated", "<i4"),
+                                ("n_edited_op", "<i4", (8,)), ("n_unchanged_op", "<i4", (8,)), ("n_entries_added", "<i4"),
+                                ("n_entries_removed", "<i4")])
+assert REGISTRY_OPS_INFO_K.itemsize == 88
 
 # mmp_models_status (getStatus MM.java:3247: the class of :3760-3768, the copy list of makeStatusInfo :3013-3058)
 (MST_NOT_FOUND, MST_NOT_LOADED, MST_LOADING_FAILED, MST_ASK) = range(4)
@@ -364,6 +371,8 @@ SYMBOLS = [
     ("mmp_registry_missing_reset", C.c_int, [_P]),
     ("mmp_janitor_plan", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     ("mmp_registry_ops", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint32, _P, _P, C.c_int32, _P]),
+    # the same by model id: ops / n, keys / key_off, now, flags, model_idx_out, status_out, edits_out, max_edits, info_out
+    ("mmp_registry_ops_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, C.c_int32, _P]),
     ("mmp_models_status", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     # the same by model id: keys / key_off / n, fail_pod[n], flags[n], now, model_idx_out, then the outputs of mmp_models_status
     ("mmp_models_status_k", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),

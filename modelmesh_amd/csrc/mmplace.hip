@@ -43,6 +43,7 @@
 #include "registry_ops_kernels.hpp"
 #include "status_kernels.hpp"
 #include "status_keyed_kernels.hpp"
+#include "registry_ops_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
@@ -7568,32 +7569,43 @@ try {
     });
 } MMP_CATCH(c, "mmp_janitor_plan")
 
-int mmp_registry_ops(mmp_ctx *c, const mmp_registry_op *ops, int32_t n, int64_t now, uint32_t flags, uint8_t *status_out,
-                     mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info)
-try {
-    if (!c || !info || n < 0 || max_edits < 0 || (n > 0 && !ops) || (max_edits > 0 && !edits_out) || now <= 0 ||
-        plan_flags_bad(flags))
-        return fail(c, MMP_EINVAL, "mmp_registry_ops: bad argument");
-    // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
-    // too.  The state lock is taken only by an apply, for its in-place rewrite.
+namespace {
+// THE REGISTRY-OPS PIPELINE (registry_ops_kernels.hpp), stated once for mmp_registry_ops and mmp_registry_ops_k: the caller has
+// refused its NULL arguments; this takes batch_mu, refuses everything else BEFORE anything is staged, stages the ops, resolves
+// the keys in front of the evaluation when there are any (rops_keyed_kernel: `model` of the staged op is then the device's, the
+// caller's is never read), evaluates, reads back and applies.  max_kind: the last MMP_ROP_* kind the entry point admits.
+// keys / key_off both NULL: by row, `model` range-checked here.  *info is written only by a call that answers MMP_OK.
+int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_op *ops, int32_t n, const char *keys, const int32_t *key_off,
+               int64_t now, uint32_t flags, int32_t *model_idx_out, uint8_t *status_out, mmp_registry_op_edit *edits_out, int32_t max_edits,
+               mmp_registry_ops_info_k *info)
+{
+    const bool keyed = keys || key_off;
+    // batch_mu owns c->stream, the scratch, the map and the model-id table for the whole call, and every writer of the state this
+    // call reads takes it too: the row a key resolves to and the edit of that row see ONE state.  The state lock is taken only by
+    // an apply, for its in-place rewrite.
     std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (const int rc = plan_state_guard(c, "mmp_registry_ops")) return rc;
+    if (const int rc = plan_state_guard(c, fn)) return rc;
+    if (keyed)
+        if (const int rc = model_id_space_guard(c, fn)) return rc;
     const int32_t M = c->n_models, P = c->snap.P;
     // the ops index the map, the rows and the instance table: their ranges are settled here, before any kernel reads them (that
-    // no model is named twice is settled by the first kernel, on the map)
+    // no model is named twice is settled by the first kernel, on the map; by key the row is the device's own and lies in [-1, M))
     for (int32_t i = 0; i < n; i++) {
         const mmp_registry_op &o = ops[i];
-        if (o.model < 0 || o.model >= M) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d names model %d of %d", i, o.model, M);
-        if (o.pod < 0 || o.pod >= P) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d names pod %d of %d", i, o.pod, P);
-        if (o.op < MMP_ROP_REGISTER || o.op > MMP_ROP_SCALE_DOWN) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d has kind %d", i, o.op);
-        if (o.flags & ~(MMP_ROPF_SHUTTING_DOWN | MMP_ROPF_MATCH_TIME)) return fail(c, MMP_EINVAL, "mmp_registry_ops: op %d has flags %u", i, o.flags);
+        if (!keyed && (o.model < 0 || o.model >= M)) return fail(c, MMP_EINVAL, "%s: op %d names model %d of %d", fn, i, o.model, M);
+        if (o.pod < 0 || o.pod >= P) return fail(c, MMP_EINVAL, "%s: op %d names pod %d of %d", fn, i, o.pod, P);
+        if (o.op < MMP_ROP_REGISTER || o.op > max_kind) return fail(c, MMP_EINVAL, "%s: op %d has kind %d", fn, i, o.op);
+        if ((o.flags & ~(MMP_ROPF_SHUTTING_DOWN | MMP_ROPF_MATCH_TIME)) || (o.op == MMP_ROP_DROP_LOCAL && o.flags))
+            return fail(c, MMP_EINVAL, "%s: op %d has flags %u", fn, i, o.flags);
     }
+    if (keyed)
+        if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
     if (n == 0) {
-        *info = mmp_registry_ops_info{};
+        *info = mmp_registry_ops_info_k{};
         return MMP_OK;
     }
     const bool apply = flags & MMP_ROPS_APPLY;
-    if (const int rc = plan_arena_guard(c, "mmp_registry_ops", apply, n)) return rc;  // (refused before anything is done)
+    if (const int rc = plan_arena_guard(c, fn, apply, n)) return rc;  // (refused before anything is done)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
     const int nb = div_up(n, kRopsBlock);
@@ -7605,12 +7617,17 @@ try {
     HIP_TRY(c, c->plan.block_counts.ensure((size_t)nb * 3 * 4));
     HIP_TRY(c, c->plan.edits.ensure((size_t)std::max(cap_e, 1) * sizeof(mmp_registry_op_edit)));
     HIP_TRY(c, c->plan.keep_off.ensure((size_t)std::max(cap_e, 1) * 4));
+    std::vector<int32_t> krel;  // (what the staged offsets are uploaded from: lives until the synchronisation below)
+    if (keyed) {
+        if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+        HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    }
     if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the scatter kernel has been seen to complete)
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what the janitor's insert reads
     const mmp_model_row *models = c->models.as<mmp_model_row>();
     const int32_t *ent_pod = c->ent_pod.as<int32_t>();
     const int64_t *ent_time = c->ent_time.as<int64_t>();
-    const mmp_registry_op *d_ops = c->plan.rows_in.as<mmp_registry_op>();
+    mmp_registry_op *d_ops = c->plan.rows_in.as<mmp_registry_op>();
     int32_t *map = c->plan.model_map.as<int32_t>();
     RopsScalars *rs = c->plan.call_scalars.as<RopsScalars>();
     PruneScalars *ps = c->plan.totals.as<PruneScalars>();
@@ -7619,6 +7636,12 @@ try {
     HIP_TRY(c, hipMemsetAsync(rs, 0, sizeof(RopsScalars), st));
     HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
     KT_BEGIN(c, st);  // device span of the evaluation
+    if (keyed) {
+        // (the staged copy keeps keyed_resolve_kernel's contract: the buffer is an allocation of its own with 16 bytes behind the keys)
+        const RopsKeyArgs A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                            c->me_row.as<int32_t>(), d_ops};
+        hipLaunchKernelGGL(rops_keyed_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+    }
     hipLaunchKernelGGL(rops_count_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
                        c->plan.block_counts.as<int32_t>());
     hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(256), 0, st, c->plan.block_counts.as<int32_t>(), nb, max_edits, INT32_MAX, ps);
@@ -7633,15 +7656,22 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     c->plan.model_map_n = M;
     kt_collect(c);
-    if (hr.n_dup != 0) return fail(c, MMP_EINVAL, "mmp_registry_ops: %d ops name a model another op of the call names", hr.n_dup);
+    if (hr.n_dup != 0) return fail(c, MMP_EINVAL, "%s: %d ops name a model another op of the call names", fn, hr.n_dup);
     const int32_t ne = std::min(h.n_edits, max_edits);
+    if (model_idx_out) {
+        if (keyed)
+            HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        else
+            for (int32_t i = 0; i < n; i++) model_idx_out[i] = ops[i].model;
+    }
     if (status_out) HIP_TRY(c, copy_sync(c, status_out, d_status, (size_t)n, hipMemcpyDeviceToHost));
     if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_registry_op_edit), hipMemcpyDeviceToHost));
-    *info = mmp_registry_ops_info{};
+    *info = mmp_registry_ops_info_k{};
     info->n_edits = h.n_edits;
-    info->n_unchanged = n - h.n_edits;
+    info->n_unchanged = n - h.n_edits - hr.n_no_record;
+    info->n_no_record = hr.n_no_record;
     info->truncated = h.truncated;
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < kRopKinds; k++) {
         info->n_edited_op[k] = hr.n_edited[k];
         info->n_unchanged_op[k] = hr.n_unchanged[k];
     }
@@ -7654,7 +7684,44 @@ try {
                            c->plan.keep_off.as<int32_t>(), h.n_edits, d_ops, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(),
                            c->ent_time.as<int64_t>(), base, arena_end, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
     });
+}
+}  // namespace
+
+// by row, kinds 0..3, its own 56-byte info: unchanged since ABI 3 (MMP_ROP_DROP_LOCAL is refused here: mmp_registry_ops_k)
+int mmp_registry_ops(mmp_ctx *c, const mmp_registry_op *ops, int32_t n, int64_t now, uint32_t flags, uint8_t *status_out,
+                     mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info *info)
+try {
+    if (!c || !info || n < 0 || max_edits < 0 || (n > 0 && !ops) || (max_edits > 0 && !edits_out) || now <= 0 ||
+        plan_flags_bad(flags))
+        return fail(c, MMP_EINVAL, "mmp_registry_ops: bad argument");
+    mmp_registry_ops_info_k k{};
+    if (const int rc = rops_drive(c, "mmp_registry_ops", MMP_ROP_SCALE_DOWN, ops, n, nullptr, nullptr, now, flags, nullptr, status_out,
+                                  edits_out, max_edits, &k))
+        return rc;
+    *info = mmp_registry_ops_info{};
+    info->n_edits = k.n_edits;
+    info->n_unchanged = k.n_unchanged;
+    info->truncated = k.truncated;
+    for (int q = 0; q < 4; q++) {
+        info->n_edited_op[q] = k.n_edited_op[q];
+        info->n_unchanged_op[q] = k.n_unchanged_op[q];
+    }
+    info->n_entries_added = k.n_entries_added;
+    info->n_entries_removed = k.n_entries_removed;
+    return MMP_OK;
 } MMP_CATCH(c, "mmp_registry_ops")
+
+// by model id (or by row with keys == key_off == NULL), kinds 0..4
+int mmp_registry_ops_k(mmp_ctx *c, const mmp_registry_op *ops, int32_t n, const char *keys, const int32_t *key_off, int64_t now,
+                       uint32_t flags, int32_t *model_idx_out, uint8_t *status_out, mmp_registry_op_edit *edits_out, int32_t max_edits,
+                       mmp_registry_ops_info_k *info)
+try {
+    if (!c || !info || n < 0 || max_edits < 0 || (n > 0 && !ops) || (max_edits > 0 && !edits_out) || now <= 0 ||
+        plan_flags_bad(flags) || (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "mmp_registry_ops_k: bad argument");
+    return rops_drive(c, "mmp_registry_ops_k", MMP_ROP_DROP_LOCAL, ops, n, keys, key_off, now, flags, model_idx_out, status_out, edits_out,
+                      max_edits, info);
+} MMP_CATCH(c, "mmp_registry_ops_k")
 
 namespace {
 // What a caller of status_drive adds around the pipeline; each defaults to nothing.

@@ -1,10 +1,14 @@
 // registry_ops_kernels.hpp — the edits an instance makes to ModelRecords itself, a batch of them against the resident registry:
 // a load completes (loadLocal, MM.java:5204-5207), a load fails (the CacheEntry failure path, :2484-2495), a copy is evicted or
-// dropped (deregisterModel, :2948-2958) and a scale-down removes the local copy (removeLocalModelCopyAsync, :6347-6365), with
+// dropped (deregisterModel, :2948-2958), a scale-down removes the local copy (removeLocalModelCopyAsync, :6347-6365) and the
+// cache-hit loop drops its own copy when getFromCache finds nothing (invokeModel, :3682-3687; mmp_registry_ops_k only), with
 // ModelRecord.addLoadFailure / removeLoadFailure / updateLastUsed / updateLastUnloadTime (ModelRecord.java:156-179, :239-262).
 //
 // An op names one record and one instance, and a call names a record at most once, so every op is decided from its own row and
-// entries (rops_eval).  The work is O(ops + entries of the records they name): nothing here walks the M rows.
+// entries (rops_eval).  The work is O(ops + entries of the records they name): nothing here walks the M rows.  An op whose
+// `model` is negative names NO record (registry.get == null, :2481 / :2945 — written by rops_keyed_kernel,
+// registry_ops_keyed_kernels.hpp, for an unknown id or the empty row; a host-checked call never carries one): it takes no map
+// word, is no edit, gets the status MMP_ROP_NO_RECORD and is counted in n_no_record; nothing is indexed with it.
 //
 //   rops_count_kernel    one lane per op: its model marked in the janitor's map (M int32 words, all -1 between runs) with a
 //                        compare-and-swap — a word already taken is a second op on that model, counted; the op evaluated;
@@ -22,9 +26,12 @@ namespace mmp {
 
 struct RopsScalars {
     int32_t n_dup;  // ops whose model an earlier-arriving op of the call had taken
-    int32_t n_edited[4], n_unchanged[4];
+    int32_t n_edited[8], n_unchanged[8];  // per MMP_ROP_* kind, kRopKinds used
     int32_t n_added, n_removed;
+    int32_t n_no_record;  // ops with model < 0
 };
+
+constexpr int kRopKinds = 5;
 
 constexpr int kRopsBlock = kCompactBlock;
 
@@ -110,7 +117,7 @@ __device__ __forceinline__ RopEval rops_eval(const mmp_model_row &m, const int32
             update_last_used(op.last_used);                     // :2956
             if (was) update_last_unload();                      // :2957
         }
-    } else {  // MMP_ROP_SCALE_DOWN
+    } else if (op.op == MMP_ROP_SCALE_DOWN) {
         if (s.li >= 0 && s.lt == op.load_time) {                // :6347-6348
             r.edited = true;
             r.flags |= MMP_ROP_EDIT_REM_LOADED;                 // :6363
@@ -118,11 +125,18 @@ __device__ __forceinline__ RopEval rops_eval(const mmp_model_row &m, const int32
             update_last_unload();                               // :6364
             update_last_used(op.last_used);                     // :6365
         }
+    } else {  // MMP_ROP_DROP_LOCAL
+        r.edited = true;  // (the record is always submitted, :3687)
+        if (s.li >= 0) {                                        // :3685 instanceIds.remove(pod), whatever its time
+            r.flags |= MMP_ROP_EDIT_REM_LOADED;
+            r.nl--;
+        }
+        update_last_used(op.last_used);                         // :3686; no updateLastUnloadTime on this path
     }
     return r;
 }
 
-// (the host checked model, pod, op and flags of every op before anything was launched)
+// (the host checked pod, op and flags of every op before anything was launched, and model < M; model < 0: no record)
 __global__ __launch_bounds__(kRopsBlock) void rops_count_kernel(const mmp_registry_op *__restrict__ ops, int32_t n,
                                                                 const mmp_model_row *__restrict__ models, const int32_t *__restrict__ ent_pod,
                                                                 const int64_t *__restrict__ ent_time, const mmp_pod_row *__restrict__ pods,
@@ -134,10 +148,12 @@ __global__ __launch_bounds__(kRopsBlock) void rops_count_kernel(const mmp_regist
     int32_t kept = 0;
     if (i < n) {
         const mmp_registry_op op = ops[i];
-        dup = atomicCAS(&map[op.model], -1, i) != -1;
-        const RopEval ev = rops_eval(models[op.model], ent_pod, ent_time, pods, P, op, now);
-        edit = ev.edited;
-        if (edit) kept = ev.nl + ev.nf;
+        if (op.model >= 0) {
+            dup = atomicCAS(&map[op.model], -1, i) != -1;
+            const RopEval ev = rops_eval(models[op.model], ent_pod, ent_time, pods, P, op, now);
+            edit = ev.edited;
+            if (edit) kept = ev.nl + ev.nf;
+        }
     }
     const int nd = __popcll(__ballot(dup));
     if (lane_id() == 0 && nd) atomicAdd(&rs->n_dup, nd);
@@ -155,18 +171,20 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
 {
     const int i = blockIdx.x * kRopsBlock + threadIdx.x;
     mmp_registry_op op{};
+    bool rec = false;  // the op names a record
     if (i < n) {
         op = ops[i];
-        map[op.model] = -1;  // (every op of a model stores the same word)
+        rec = op.model >= 0;
+        if (rec) map[op.model] = -1;  // (every op of a model stores the same word)
     }
     if (rs->n_dup != 0) return;  // (uniform: the whole grid leaves; the call is refused)
     RopEval ev{};
-    if (i < n) ev = rops_eval(models[op.model], ent_pod, ent_time, pods, P, op, now);
+    if (rec) ev = rops_eval(models[op.model], ent_pod, ent_time, pods, P, op, now);
     const bool edit = ev.edited;
     const int32_t kept = edit ? ev.nl + ev.nf : 0;
     const TripleOff o = triple_offsets<kCol1None>(edit, 0, kept, block_off);
     const int lane = lane_id();
-    if (i < n) status[i] = edit ? MMP_ROP_EDITED : MMP_ROP_UNCHANGED;
+    if (i < n) status[i] = !rec ? MMP_ROP_NO_RECORD : edit ? MMP_ROP_EDITED : MMP_ROP_UNCHANGED;
     if (edit) {
         const int32_t x = o.e;
         if (x < max_edits) {
@@ -184,8 +202,8 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
         }
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int ce = __popcll(__ballot(i < n && op.op == k && edit)), cu = __popcll(__ballot(i < n && op.op == k && !edit));
+    for (int k = 0; k < kRopKinds; k++) {
+        const int ce = __popcll(__ballot(rec && op.op == k && edit)), cu = __popcll(__ballot(rec && op.op == k && !edit));
         if (lane == 0) {
             if (ce) atomicAdd(&rs->n_edited[k], ce);
             if (cu) atomicAdd(&rs->n_unchanged[k], cu);
@@ -194,9 +212,11 @@ __global__ __launch_bounds__(kRopsBlock) void rops_scatter_kernel(const mmp_regi
     const bool put_new = (ev.flags & (MMP_ROP_EDIT_PUT_LOADED | MMP_ROP_EDIT_PUT_FAILED)) && !(ev.flags & MMP_ROP_EDIT_REPLACED);
     const int na = __popcll(__ballot(put_new));
     const int nr = __popcll(__ballot(ev.flags & MMP_ROP_EDIT_REM_LOADED)) + __popcll(__ballot(ev.flags & MMP_ROP_EDIT_REM_FAILED));
+    const int nn = __popcll(__ballot(i < n && !rec));
     if (lane == 0) {
         if (na) atomicAdd(&rs->n_added, na);
         if (nr) atomicAdd(&rs->n_removed, nr);
+        if (nn) atomicAdd(&rs->n_no_record, nn);
     }
 }
 

@@ -1,7 +1,8 @@
 // rewrite_kernels.hpp — the write side of the wire format: the next stored value of a ModelRecord (mmp_models_rewrite_json).
 //
 // Every edit of the registry ends, in the reference, in a compare-and-set that writes a whole serialised ModelRecord back
-// (ModelMesh.java: 13 conditionalSet / conditionalSetAndGet sites, 12 of them on the registry).  The device holds what the mesh
+// (ModelMesh.java: 13 conditionalSet / conditionalSetAndGet sites, 12 of them on the registry, every one of the 12 with a device
+// edit call: the last, :3687, is MMP_ROP_DROP_LOCAL of mmp_registry_ops_k).  The device holds what the mesh
 // owns of a record — the two id maps and lu — and nothing of the rest (type, mPath, encKey, refs, autoDel, the failure texts,
 // any future field), so the new value is made of two halves: the members of the OLD value the device does not own, copied byte
 // for byte, and the owned members rendered from the resident row.  The rule (include/mmplace.h states it for callers, tests/model_rewrite_model.py as a program):

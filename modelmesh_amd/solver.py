@@ -1376,6 +1376,53 @@ class Solver:
         ne = min(max_edits, int(info[0]["n_edits"]))
         return status[:n].copy(), edits[:ne].copy(), info[0].copy()
 
+    def registry_ops_k(self, ops, keys, now: int, apply: bool = True, dry: bool = False, max_edits: int = 1024):
+        """registry_ops BY MODEL ID, with the fifth kind ROP_DROP_LOCAL (the cache-hit loop's drop of its own copy, MM.java:3682-3687):
+        (model_idx, status, edits, info) from one mmp_registry_ops_k call — the key resolved, the op evaluated and the edit applied
+        under one hold of the batch lock; an unknown id and the empty row a deletion leaves answer ROP_NO_RECORD.  keys=None: by row
+        (ops["model"]).  The buffer is regrown to the call's total when it reports `truncated` (a truncated call changes nothing)."""
+        from ._lib import ROPS_APPLY, ROPS_DRY
+        flags = ROPS_DRY if dry else (ROPS_APPLY if apply else 0)
+        while True:
+            idx, status, edits, info, rc = self.registry_ops_k_raw(ops, keys, now, flags, max_edits)
+            self._ck(rc)
+            if not info["truncated"]:
+                break
+            max_edits = max(max_edits, int(info["n_edits"]))
+        if flags == ROPS_APPLY and int(info["n_edits"]) and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return idx, status, edits, info
+
+    def registry_ops_k_raw(self, ops, keys, now, flags, max_edits, fill=0, key_off=None, blob=None, null_keys=False, null_off=False,
+                           null_status=False, null_idx=False, null_info=False, null_ops=False):
+        """One mmp_registry_ops_k call with exactly this capacity (0: a NULL edits buffer), the outputs filled with the byte `fill`
+        first: (model_idx, status, edits[:min(n_edits, max_edits)] — all max_edits rows when the call fails —, info, rc).  Does not
+        raise.  keys: a list of bytes/str, or None for the by-row form (both key pointers NULL); key_off / blob replace the packed
+        offsets / bytes; the null_* switches pass NULL for that one argument."""
+        from ._lib import REGISTRY_OP, REGISTRY_OP_EDIT, REGISTRY_OPS_INFO_K
+        ops = np.ascontiguousarray(ops, dtype=REGISTRY_OP)
+        n = len(ops)
+        kblob, off32 = None, None
+        if keys is not None:
+            kblob, off = self._pack(keys)
+            off32 = off.astype(np.int32)
+        if blob is not None:
+            kblob = blob
+        if key_off is not None:
+            off32 = np.ascontiguousarray(key_off, dtype=np.int32)
+        info = np.zeros(1, dtype=REGISTRY_OPS_INFO_K)
+        idx = np.zeros(max(n, 1), np.int32)
+        status = np.zeros(max(n, 1), np.uint8)
+        edits = np.zeros(max(max_edits, 1), dtype=REGISTRY_OP_EDIT)
+        for a in (info, idx, status, edits):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_registry_ops_k(self.h, None if null_ops or not n else ptr(ops), n, None if null_keys else kblob,
+                                         None if null_off or off32 is None else ptr(off32), int(now), int(flags),
+                                         None if null_idx else ptr(idx), None if null_status else ptr(status),
+                                         ptr(edits) if max_edits else None, int(max_edits), None if null_info else ptr(info))
+        ne = max_edits if rc != 0 else min(max_edits, int(info[0]["n_edits"]))
+        return idx[:n].copy(), status[:n].copy(), edits[:ne].copy(), info[0].copy(), rc
+
     def models_status(self, reqs, now: int):
         """getStatus answers (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058) for a batch of mmp_status_req
         rows from the resident registry: (rows, copies) — one mmp_status_row per request, and the copies of request i, latest
