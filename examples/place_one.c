@@ -111,7 +111,23 @@ int main(void)
     }
     printf("status by vmodel id: class=%d vstatus=%d active: class=%d copies=%d, active id \"%.*s\"\n", vs.cls, vs.vstatus, st_rows[0].cls,
            st_rows[0].n_not_checked + st_rows[0].n_failed, (int)(str_off[1] - str_off[0]), strs + str_off[0]);
+    /* A periodic task by id: preShutdown asks, for the one entry of this instance's cache, whether a copy is to be triggered
+     * elsewhere (mmp_migration_plan_k) — the cache holds ids, so the entry's model field stays -1 and the id's bytes name it. */
+    mmp_cache_entry ce;
+    memset(&ce, 0, sizeof ce);
+    ce.model = -1; /* ignored: the key names the model */
+    ce.weight = 100;
+    ce.last_used = now - 1000;
+    uint8_t mig_action = 9, mig_wait = 9;
+    int32_t mig_row = -2;
+    if ((rc = mmp_migration_plan_k(ctx, &ce, 1, ids, id_off, 0, now, 3600000, &mig_action, &mig_wait, &mig_row))) {
+        fprintf(stderr, "libmmplace: %d (%s)\n", rc, mmp_last_error(ctx));
+        mmp_destroy(ctx);
+        return 1;
+    }
+    printf("migration by id: row=%d action=%d wait=%d\n", mig_row, mig_action, mig_wait);
     mmp_destroy(ctx);
+    if (mig_row != 0 || mig_action > 1 || mig_wait > 1) return 6;
     if (vs.cls != MMP_VMR_OK || vs.model != 0 || vs.vstatus != MMP_VMS_DEFINED || st_rows[0].cls != MMP_MST_ASK || n_copies != 1 ||
         st_rows[1].cls != MMP_MST_NOT_FOUND || n_str != 16 || memcmp(strs, "my-modelmy-model", 16) != 0)
         return 5;

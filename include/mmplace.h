@@ -1216,6 +1216,61 @@ int mmp_scaledown_plan_conc(mmp_ctx *ctx, const mmp_cache_entry *entries, const 
 int mmp_migration_plan(mmp_ctx *ctx, const mmp_cache_entry *entries, int32_t n, int32_t self_pod, int64_t now_ms,
                        int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out);
 
+/* THE PERIODIC TASKS BY MODEL ID.  The rate task (MM.java:5672-5690), the janitor's cache loop (:5896-5903) and preShutdown's
+ * migration (:6998-7010) iterate runtimeCache, whose keys are model ids, and begin each entry with registry.get(modelId): an
+ * instance holds ids, never registry rows.  Each call below keeps the argument list of its by-row call and adds
+ *   keys / key_off     n keys, raw id bytes, n + 1 offsets that need not start at 0 (the conventions of mmp_model_ids_resolve)
+ *   model_idx_out      n words, may be NULL: what mmp_model_ids_resolve answers for key i
+ * and resolves the keys on the device under THE SAME hold of the batch lock that evaluates (and, for the janitor, applies): no
+ * registry event batch that deletes and re-registers an id, and no mmp_models_retire, can move a row between its resolution and
+ * its use (csrc/tasks_keyed_kernels.hpp: one launch in front of the unchanged plan kernels).
+ *
+ * THE RULE BY KEY: entry i is evaluated exactly as the by-row call evaluates it with `model` set to the row model_idx_out[i]
+ * names, and to -1 — "registry.get(modelId) == null", what every one of these structs already says -1 means — when the id is
+ * unknown OR that row is the empty row a deleted record leaves (the definition of MMP_RETIRE_EMPTY_ONLY, the rule of
+ * mmp_models_status_k and mmp_registry_ops_k).  The `model` field the caller sent is never read.  With keys == key_off == NULL
+ * each call IS its by-row call (model_idx_out then repeats the entries' `model`); one of the two NULL is MMP_EINVAL.  Key offsets
+ * that are not monotone are MMP_EINVAL; MMP_ESTATE before the first commit and, with keys, under the conditions of
+ * mmp_model_ids_resolve; a refused call writes nothing.  n == 0 is valid; two runs over one state are byte-identical.
+ *
+ * mmp_scaleup_plan_k: mmp_scaleup_plan when conc_params is NULL (conc, conc_outs and result are then NULL too:
+ * limitModelConcurrency == false), mmp_scaleup_plan_conc otherwise.  A run that is skipped (*skipped = 1) still answers
+ * model_idx_out.  mmp_scaledown_plan_k: mmp_scaledown_plan when conc is NULL, mmp_scaledown_plan_conc otherwise. */
+int mmp_scaleup_plan_k(mmp_ctx *ctx, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n, const char *keys,
+                       const int32_t *key_off, const mmp_scaleup_params *params, const mmp_conc_params *conc_params,
+                       mmp_scaleup_out *outs, mmp_conc_out *conc_outs, uint8_t *overloaded_out, int32_t *skipped,
+                       mmp_conc_result *result, int32_t *model_idx_out);
+int mmp_scaledown_plan_k(mmp_ctx *ctx, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n, const char *keys,
+                         const int32_t *key_off, const mmp_scaledown_params *params, int64_t dynamic_rpm_scale_constant,
+                         uint8_t *removed_out, int32_t *model_idx_out);
+int mmp_migration_plan_k(mmp_ctx *ctx, const mmp_cache_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                         int32_t self_pod, int64_t now_ms, int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out,
+                         int32_t *model_idx_out);
+/* janitorTask (MM.java:5876-6145) as ONE call: mmp_janitor_plan by model id, and — with `scaledown` — the scale-down of the
+ * candidates it found (:6110-6145, removeModelCopies :6197-6310) in the same hold, where today the candidates travel to the host
+ * as rows and come back into mmp_scaledown_plan in another call.
+ *
+ * NO MODEL HAS TWO ROWS is settled on the device by key: two entries whose keys resolve to the same live row are MMP_EINVAL, with
+ * nothing written, nothing applied and the library's scratch as it was (a by-row call that follows is not disturbed).  Two equal
+ * keys that resolve to NO record both become -1 and are NOT detected — the by-row call accepts several -1 rows as well, and each
+ * is removed by the cache loop on its own (:5968).  A run that is shutting down (:5880) still resolves and still refuses.
+ *
+ * THE SCALE-DOWN IN THE SAME CALL (scaledown != NULL; also by row).  The answer is DEFINED as that of mmp_janitor_plan with
+ * MMP_JANITOR_APPLY followed by mmp_scaledown_plan (conc == NULL) / mmp_scaledown_plan_conc on the candidates it returned:
+ *   scaledown                    the scale-down's parameters; scaledown->self_pod must equal params->self_pod
+ *   conc                         n MaxConcCacheEntry rows in INPUT-row order (conc[r] belongs to entries[r]; the candidate that came
+ *                                from input row candidate_rows_out[j] is decided on conc[candidate_rows_out[j]]); NULL: not
+ *                                latency-based, dynamic_rpm_scale_constant is then not read
+ *   removed_out                  one byte per candidate, aligned with candidates_out: n_candidates bytes are written
+ * The scale-down reads the registry as the two loops left it, so it needs MMP_JANITOR_APPLY (MMP_EINVAL otherwise).  On a
+ * truncated plan nothing is applied, as in mmp_janitor_plan, and removed_out is not written.  A run that stopped at a repaired row
+ * (stopped_at >= 0) or that is shutting down has no candidates: nothing is decided.  conc without scaledown is MMP_EINVAL. */
+int mmp_janitor_plan_k(mmp_ctx *ctx, const mmp_janitor_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                       const mmp_janitor_params *params, uint32_t flags, const mmp_scaledown_params *scaledown,
+                       const mmp_conc_entry *conc, int64_t dynamic_rpm_scale_constant, int32_t *model_idx_out, uint8_t *actions_out,
+                       mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *candidates_out,
+                       int32_t *candidate_rows_out, int32_t max_candidates, uint8_t *removed_out, mmp_janitor_info *info_out);
+
 /* ---- ingestion of the KV-store wire format ---------------------------------------
  * The instance table and the registry live in etcd / ZooKeeper as Jackson JSON values
  * (MM.java:346 INST_REC_SERIALIZER, :628 registry view; InstanceRecord.java:37-69,

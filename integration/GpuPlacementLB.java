@@ -198,6 +198,27 @@ final class MmPlace {
                                         long dynamicRpmScaleConstant, ByteBuffer removedOut);
     static native int migrationPlan(long h, ByteBuffer entries, int n, int selfPod, long nowMs, long cutoffAgeMs,
                                     ByteBuffer actionOut, ByteBuffer waitOut);
+    // THE PERIODIC TASKS BY MODEL ID (mmp_scaleup_plan_k, mmp_scaledown_plan_k, mmp_migration_plan_k, mmp_janitor_plan_k): the
+    // loops iterate runtimeCache, whose keys are ids (MM.java:5672-5690, :5896-5903, :6998-7010), so keys / keyOff (TaskKeys.of)
+    // name the record of entry i — the entry's model field is ignored; both null: by row — and are resolved under the hold of the
+    // batch lock that evaluates: no event batch or modelsRetire can land between the row and its use.  An unknown id and a deleted
+    // record are model -1 (registry.get == null).  modelIdxOut = n ints (may be null).  conc / concParams / concOuts / result null:
+    // limitModelConcurrency == false.
+    static native int scaleupPlanKeyed(long h, ByteBuffer entries, ByteBuffer conc, int n, ByteBuffer keys, ByteBuffer keyOff,
+                                       ByteBuffer params, ByteBuffer concParams, ByteBuffer outs, ByteBuffer concOuts,
+                                       ByteBuffer overloadedOut, ByteBuffer skipped, ByteBuffer result, ByteBuffer modelIdxOut);
+    static native int scaledownPlanKeyed(long h, ByteBuffer entries, ByteBuffer conc, int n, ByteBuffer keys, ByteBuffer keyOff,
+                                         ByteBuffer params, long dynamicRpmScaleConstant, ByteBuffer removedOut, ByteBuffer modelIdxOut);
+    static native int migrationPlanKeyed(long h, ByteBuffer entries, int n, ByteBuffer keys, ByteBuffer keyOff, int selfPod, long nowMs,
+                                         long cutoffAgeMs, ByteBuffer actionOut, ByteBuffer waitOut, ByteBuffer modelIdxOut);
+    // janitorTask as ONE call (:5876-6145): janitorPlan by id — two entries of one record are refused — and, with scaledown (one
+    // mmp_scaledown_params of the same selfPod; flags must be 1 = apply), the scale-down of its candidates in the same hold:
+    // conc = n mmp_conc_entry rows in INPUT-row order (null: not latency-based), removedOut = one byte per candidate, aligned with
+    // candidatesOut.  info.truncated: nothing was applied and removedOut was not written.
+    static native int janitorPlanKeyed(long h, ByteBuffer entries, int n, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer params, int flags,
+                                       ByteBuffer scaledown, ByteBuffer conc, long dynamicRpmScaleConstant, ByteBuffer modelIdxOut,
+                                       ByteBuffer actionsOut, ByteBuffer editsOut, int maxEdits, ByteBuffer candidatesOut,
+                                       ByteBuffer candidateRowsOut, int maxCandidates, ByteBuffer removedOut, ByteBuffer info);
     // type constraints, upgrade tracker
     static native int typesFromLabels(long h, int nTypes, ByteBuffer required, ByteBuffer preferred, ByteBuffer podLabels,
                                       ByteBuffer allowedOut, ByteBuffer preferOut, ByteBuffer hasAllowedOut,
@@ -396,6 +417,31 @@ final class ModelKey {
         b[1].putInt(0, 0);
         b[1].putInt(4, utf8.length);
         return b;
+    }
+}
+
+/**
+ * The ids of a periodic task's entries as the keyed natives take them: { the ids' UTF-8 bytes back to back, keyOff = n + 1 ints },
+ * in iteration order.  The rate task, the janitor and preShutdown iterate runtimeCache (descendingMapWithCutoff, descendingMap,
+ * descendingLruMap: MM.java:5672, :5892, :6998), whose keys are model ids: a binding without an id map (modelIdsResident() == true)
+ * fills the entry rows' model field with -1 and hands the keys over here, ONE scaleupPlanKeyed / janitorPlanKeyed /
+ * migrationPlanKeyed call per run instead of modelIdsResolve + the by-row call.
+ */
+final class TaskKeys {
+    static ByteBuffer[] of(java.util.Collection<String> modelIds) {
+        final byte[][] utf8 = new byte[modelIds.size()][];
+        int total = 0, i = 0;
+        for (String id : modelIds) {
+            utf8[i] = id.getBytes(java.nio.charset.StandardCharsets.UTF_8);
+            total = Math.addExact(total, utf8[i++].length);
+        }
+        final ByteBuffer keys = MmPlace.direct(Math.max(total, 1)), off = MmPlace.direct(4 * (utf8.length + 1));
+        off.putInt(0, 0);
+        for (i = 0; i < utf8.length; i++) {
+            keys.put(utf8[i]);
+            off.putInt(4 * (i + 1), keys.position());
+        }
+        return new ByteBuffer[] { keys, off };
     }
 }
 

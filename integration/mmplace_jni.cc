@@ -718,6 +718,101 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_migrationPlan(JNIEn
                  mmp_migration_plan(ctx_of(h), buf<mmp_cache_entry>(env, entries), n, selfPod, nowMs, cutoffAgeMs,
                                     buf<uint8_t>(env, actionOut), buf<uint8_t>(env, waitOut)));
 }
+// THE PERIODIC TASKS BY MODEL ID (MM.java:5672-5690, :5896-5903, :6998-7010: the loops iterate runtimeCache's ids): the keys
+// resolved and the entries evaluated under one hold of the batch lock.  keys and keyOff both null: by row.  Every buffer's
+// capacity is checked here; the optional ones (conc, concParams, concOuts, result, modelIdxOut, scaledown, removedOut) may be null.
+static bool task_keys_held(JNIEnv *env, jobject keys, jobject keyOff, jint n, const char *what_off, const char *what_keys)
+{
+    return (!keyOff || holds<int32_t>(env, keyOff, (jlong)n + 1, what_off)) &&
+           (!keyOff || !keys || n <= 0 || holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], what_keys));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaleupPlanKeyed(JNIEnv *env, jclass, jlong h, jobject entries, jobject conc,
+                                                                              jint n, jobject keys, jobject keyOff, jobject params,
+                                                                              jobject concParams, jobject outs, jobject concOuts,
+                                                                              jobject overloadedOut, jobject skipped, jobject result,
+                                                                              jobject modelIdxOut)
+{
+    if (n < 0 || !holds<mmp_cache_entry>(env, entries, n, "scaleupPlanKeyed: entries shorter than n rows") ||
+        (conc && !holds<mmp_conc_entry>(env, conc, n, "scaleupPlanKeyed: conc shorter than n rows")) ||
+        !task_keys_held(env, keys, keyOff, n, "scaleupPlanKeyed: keyOff shorter than n + 1", "scaleupPlanKeyed: keys shorter than keyOff[n]") ||
+        !holds<mmp_scaleup_params>(env, params, 1, "scaleupPlanKeyed: params shorter than one mmp_scaleup_params") ||
+        (concParams && !holds<mmp_conc_params>(env, concParams, 1, "scaleupPlanKeyed: concParams shorter than one mmp_conc_params")) ||
+        !holds<mmp_scaleup_out>(env, outs, n, "scaleupPlanKeyed: outs shorter than n rows") ||
+        (concOuts && !holds<mmp_conc_out>(env, concOuts, n, "scaleupPlanKeyed: concOuts shorter than n rows")) ||
+        !holds<uint8_t>(env, overloadedOut, 1, "scaleupPlanKeyed: overloadedOut shorter than one byte") ||
+        !holds<int32_t>(env, skipped, 1, "scaleupPlanKeyed: skipped shorter than one int") ||
+        (result && !holds<mmp_conc_result>(env, result, 1, "scaleupPlanKeyed: result shorter than one mmp_conc_result")) ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "scaleupPlanKeyed: modelIdxOut shorter than n")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_scaleup_plan_k(ctx_of(h), buf<mmp_cache_entry>(env, entries), buf<mmp_conc_entry>(env, conc), n, buf<char>(env, keys),
+                                    buf<int32_t>(env, keyOff), buf<mmp_scaleup_params>(env, params), buf<mmp_conc_params>(env, concParams),
+                                    buf<mmp_scaleup_out>(env, outs), buf<mmp_conc_out>(env, concOuts), buf<uint8_t>(env, overloadedOut),
+                                    buf<int32_t>(env, skipped), buf<mmp_conc_result>(env, result), buf<int32_t>(env, modelIdxOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_scaledownPlanKeyed(JNIEnv *env, jclass, jlong h, jobject entries, jobject conc,
+                                                                                jint n, jobject keys, jobject keyOff, jobject params,
+                                                                                jlong dynamicRpmScaleConstant, jobject removedOut,
+                                                                                jobject modelIdxOut)
+{
+    if (n < 0 || !holds<mmp_cache_entry>(env, entries, n, "scaledownPlanKeyed: entries shorter than n rows") ||
+        (conc && !holds<mmp_conc_entry>(env, conc, n, "scaledownPlanKeyed: conc shorter than n rows")) ||
+        !task_keys_held(env, keys, keyOff, n, "scaledownPlanKeyed: keyOff shorter than n + 1", "scaledownPlanKeyed: keys shorter than keyOff[n]") ||
+        !holds<mmp_scaledown_params>(env, params, 1, "scaledownPlanKeyed: params shorter than one mmp_scaledown_params") ||
+        !holds<uint8_t>(env, removedOut, n, "scaledownPlanKeyed: removedOut shorter than n bytes") ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "scaledownPlanKeyed: modelIdxOut shorter than n")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_scaledown_plan_k(ctx_of(h), buf<mmp_cache_entry>(env, entries), buf<mmp_conc_entry>(env, conc), n, buf<char>(env, keys),
+                                      buf<int32_t>(env, keyOff), buf<mmp_scaledown_params>(env, params), dynamicRpmScaleConstant,
+                                      buf<uint8_t>(env, removedOut), buf<int32_t>(env, modelIdxOut)));
+}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_migrationPlanKeyed(JNIEnv *env, jclass, jlong h, jobject entries, jint n,
+                                                                                jobject keys, jobject keyOff, jint selfPod, jlong nowMs,
+                                                                                jlong cutoffAgeMs, jobject actionOut, jobject waitOut,
+                                                                                jobject modelIdxOut)
+{
+    if (n < 0 || !holds<mmp_cache_entry>(env, entries, n, "migrationPlanKeyed: entries shorter than n rows") ||
+        !task_keys_held(env, keys, keyOff, n, "migrationPlanKeyed: keyOff shorter than n + 1", "migrationPlanKeyed: keys shorter than keyOff[n]") ||
+        !holds<uint8_t>(env, actionOut, n, "migrationPlanKeyed: actionOut shorter than n bytes") ||
+        !holds<uint8_t>(env, waitOut, n, "migrationPlanKeyed: waitOut shorter than n bytes") ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "migrationPlanKeyed: modelIdxOut shorter than n")))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_migration_plan_k(ctx_of(h), buf<mmp_cache_entry>(env, entries), n, buf<char>(env, keys), buf<int32_t>(env, keyOff), selfPod,
+                                      nowMs, cutoffAgeMs, buf<uint8_t>(env, actionOut), buf<uint8_t>(env, waitOut),
+                                      buf<int32_t>(env, modelIdxOut)));
+}
+// janitorTask as one call (MM.java:5876-6145): by model id, with the scale-down of its candidates in the same hold when
+// `scaledown` is not null (removedOut: maxCandidates bytes, aligned with candidatesOut).
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_janitorPlanKeyed(JNIEnv *env, jclass, jlong h, jobject entries, jint n, jobject keys,
+                                                                              jobject keyOff, jobject params, jint flags, jobject scaledown,
+                                                                              jobject conc, jlong dynamicRpmScaleConstant, jobject modelIdxOut,
+                                                                              jobject actionsOut, jobject editsOut, jint maxEdits,
+                                                                              jobject candidatesOut, jobject candidateRowsOut, jint maxCandidates,
+                                                                              jobject removedOut, jobject info)
+{
+    if (n < 0 || maxEdits < 0 || maxCandidates < 0 || !holds<mmp_janitor_entry>(env, entries, n, "janitorPlanKeyed: entries shorter than n") ||
+        !task_keys_held(env, keys, keyOff, n, "janitorPlanKeyed: keyOff shorter than n + 1", "janitorPlanKeyed: keys shorter than keyOff[n]") ||
+        !holds<mmp_janitor_params>(env, params, 1, "janitorPlanKeyed: params shorter than one mmp_janitor_params") ||
+        (scaledown && !holds<mmp_scaledown_params>(env, scaledown, 1, "janitorPlanKeyed: scaledown shorter than one mmp_scaledown_params")) ||
+        (conc && !holds<mmp_conc_entry>(env, conc, n, "janitorPlanKeyed: conc shorter than n rows")) ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "janitorPlanKeyed: modelIdxOut shorter than n")) ||
+        !holds<uint8_t>(env, actionsOut, n, "janitorPlanKeyed: actionsOut shorter than n") ||
+        !holds<mmp_janitor_edit>(env, editsOut, maxEdits, "janitorPlanKeyed: editsOut shorter than maxEdits") ||
+        !holds<mmp_cache_entry>(env, candidatesOut, maxCandidates, "janitorPlanKeyed: candidatesOut shorter than maxCandidates") ||
+        !holds<int32_t>(env, candidateRowsOut, maxCandidates, "janitorPlanKeyed: candidateRowsOut shorter than maxCandidates") ||
+        (removedOut && !holds<uint8_t>(env, removedOut, maxCandidates, "janitorPlanKeyed: removedOut shorter than maxCandidates")) ||
+        !holds<mmp_janitor_info>(env, info, 1, "janitorPlanKeyed: info shorter than one mmp_janitor_info"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_janitor_plan_k(ctx_of(h), buf<mmp_janitor_entry>(env, entries), n, buf<char>(env, keys), buf<int32_t>(env, keyOff),
+                                    buf<mmp_janitor_params>(env, params), static_cast<uint32_t>(flags), buf<mmp_scaledown_params>(env, scaledown),
+                                    buf<mmp_conc_entry>(env, conc), dynamicRpmScaleConstant, buf<int32_t>(env, modelIdxOut),
+                                    buf<uint8_t>(env, actionsOut), buf<mmp_janitor_edit>(env, editsOut), maxEdits,
+                                    buf<mmp_cache_entry>(env, candidatesOut), buf<int32_t>(env, candidateRowsOut), maxCandidates,
+                                    buf<uint8_t>(env, removedOut), buf<mmp_janitor_info>(env, info)));
+}
 
 // ---- type constraints from labels (TypeConstraintManager.java:337-506, 680-747) ----------------------
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_typesFromLabels(JNIEnv *env, jclass, jlong h,

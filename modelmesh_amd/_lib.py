@@ -385,6 +385,17 @@ SYMBOLS = [
     ("mmp_scaleup_plan_conc", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
     ("mmp_scaledown_plan_conc", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
     ("mmp_migration_plan", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    # the periodic tasks by model id: the by-row argument lists with keys / key_off behind n and model_idx_out at the end
+    # entries, conc, n, keys, key_off, params, conc_params, outs, conc_outs, overloaded_out, skipped, result, model_idx_out
+    ("mmp_scaleup_plan_k", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P, _P]),
+    # entries, conc, n, keys, key_off, params, dynamic_rpm_scale_constant, removed_out, model_idx_out
+    ("mmp_scaledown_plan_k", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P]),
+    # entries, n, keys, key_off, self_pod, now, cutoff_age_ms, action_out, wait_out, model_idx_out
+    ("mmp_migration_plan_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    # entries, n, keys, key_off, params, flags, scaledown, conc, dynamic_rpm_scale_constant, model_idx_out, actions_out, edits_out,
+    # max_edits, candidates_out, candidate_rows_out, max_candidates, removed_out, info_out
+    ("mmp_janitor_plan_k", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P,
+                                     C.c_int32, _P, _P]),
     ("mmp_pod_ids_load", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     ("mmp_pods_ingest_json", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("mmp_type_names_load", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),

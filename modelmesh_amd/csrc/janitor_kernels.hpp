@@ -33,6 +33,7 @@ struct JanitorScalars {
     int32_t stop_inv;  // max over stopping rows of (n - row); 0 = no stop
     int32_t n_cands, n_ties;
     int32_t n_action[7];
+    int32_t n_dup;  // by key (tasks_keyed_kernels.hpp): entries whose resolved row another entry of the call had claimed
 };
 
 constexpr int kJanBlock = kCompactBlock;

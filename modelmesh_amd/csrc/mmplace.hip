@@ -44,6 +44,7 @@
 #include "status_kernels.hpp"
 #include "status_keyed_kernels.hpp"
 #include "registry_ops_keyed_kernels.hpp"
+#include "tasks_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
 #include "model_ids_kernels.hpp"
@@ -7446,47 +7447,136 @@ int model_map_cover(mmp_ctx *c, int32_t M, hipStream_t st)
     c->plan.model_map_n = 0;
     return MMP_OK;
 }
-}  // namespace
+// the scale-down's two kernels on candidates that stand on the device (defined with the rebalance calls below)
+int scaledown_enqueue(mmp_ctx *c, hipStream_t st, const mmp_cache_entry *d_entries, const mmp_conc_entry *d_conc, int32_t n,
+                      const mmp_scaledown_params *p, int64_t dyn_const);
 
-int mmp_janitor_plan(mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *p, uint32_t flags,
-                     uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *cands_out,
-                     int32_t *cand_rows_out, int32_t max_cands, mmp_janitor_info *info)
-try {
-    if (!c || !p || !info || n < 0 || max_edits < 0 || max_cands < 0 || (n > 0 && (!entries || !actions_out)) || (max_edits > 0 && !edits_out) ||
-        (max_cands > 0 && (!cands_out || !cand_rows_out)) || p->now <= 0 || p->janitor_freq_secs < 0 || p->load_timeout_ms < 0 ||
-        p->min_stale_age_ms < 0 || p->load_failure_expiry_ms < 0 || p->short_expiry_recent_use_ms < 0 || p->unload_attempt_recent_ms < 0 ||
-        p->lastused_age_on_add_ms < 0 || plan_flags_bad(flags))
-        return fail(c, MMP_EINVAL, "mmp_janitor_plan: bad argument");
-    // batch_mu owns c->stream, the scratch and the map for the whole call, and every writer of the state this call reads takes it
-    // too.  The state lock is taken only by an apply, for its in-place rewrite.
+// the keys of a periodic task (tasks_keyed_kernels.hpp), in two steps around the caller's KT_BEGIN: the staged copy — it keeps
+// keyed_resolve_kernel's contract: the buffer is an allocation of its own with 16 bytes behind the keys — and the launch that
+// writes `model` of the n staged entries and c->me_row.  `rel` stays with the caller until it has synchronised.
+int tasks_keys_stage(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, int32_t n, std::vector<int32_t> &rel)
+{
+    if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, rel)) return rc;
+    HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
+    return MMP_OK;
+}
+extern "C++" template <class Entry, class Claim>  // (a template inside the file's extern "C" block)
+void tasks_keys_launch(mmp_ctx *c, int32_t n, Entry *d_entries, const Claim &claim)
+{
+    const TasksKeyArgs<Entry> A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                                c->me_row.as<int32_t>(), d_entries};
+    hipLaunchKernelGGL((tasks_keyed_kernel<Entry, Claim>), dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, c->stream, A, claim);
+}
+// model_idx_out of a _k call: the table's rows by key, the caller's own rows by row
+extern "C++" template <class Entry>
+int tasks_model_idx(mmp_ctx *c, bool keyed, const Entry *entries, int32_t n, int32_t *model_idx_out)
+{
+    if (!model_idx_out || n == 0) return MMP_OK;
+    if (keyed) {
+        HIP_TRY(c, copy_sync(c, model_idx_out, c->me_row.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    } else
+        for (int32_t i = 0; i < n; i++) model_idx_out[i] = entries[i].model;
+    return MMP_OK;
+}
+
+// what both janitor entry points refuse before the lock is taken
+bool janitor_args_bad(const mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *p, uint32_t flags,
+                      const uint8_t *actions_out, const mmp_janitor_edit *edits_out, int32_t max_edits, const mmp_cache_entry *cands_out,
+                      const int32_t *cand_rows_out, int32_t max_cands, const mmp_janitor_info *info)
+{
+    return !c || !p || !info || n < 0 || max_edits < 0 || max_cands < 0 || (n > 0 && (!entries || !actions_out)) || (max_edits > 0 && !edits_out) ||
+           (max_cands > 0 && (!cands_out || !cand_rows_out)) || p->now <= 0 || p->janitor_freq_secs < 0 || p->load_timeout_ms < 0 ||
+           p->min_stale_age_ms < 0 || p->load_failure_expiry_ms < 0 || p->short_expiry_recent_use_ms < 0 || p->unload_attempt_recent_ms < 0 ||
+           p->lastused_age_on_add_ms < 0 || plan_flags_bad(flags);
+}
+
+// What mmp_janitor_plan_k adds to the plan: the scale-down of the candidates in the same hold (sd == nullptr: no chain)
+struct JanitorChain {
+    const mmp_scaledown_params *sd;
+    const mmp_conc_entry *conc;  // n rows in INPUT-row order; nullptr: not latency-based
+    int64_t dyn_const;
+    uint8_t *removed_out;        // one byte per candidate
+};
+
+// THE JANITOR PIPELINE (janitor_kernels.hpp), stated once for mmp_janitor_plan and mmp_janitor_plan_k: the caller has refused its
+// NULL and negative arguments; this takes batch_mu, refuses everything else BEFORE anything is staged or written, stages the
+// entries, resolves and claims by key when there are keys (tasks_keyed_kernel in the place of janitor_entry_kernel: `model` of the
+// staged entry is then the device's, the caller's is never read), evaluates, reads back, applies, and — with a chain — decides
+// the scale-down of the candidates where they lie, behind the apply.  keys / key_off both NULL: by row, range and
+// one-row-per-model checked here.
+int janitor_drive(mmp_ctx *c, const char *fn, const mmp_janitor_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                  const mmp_janitor_params *p, uint32_t flags, const JanitorChain &ch, int32_t *model_idx_out, uint8_t *actions_out,
+                  mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *cands_out, int32_t *cand_rows_out, int32_t max_cands,
+                  mmp_janitor_info *info)
+{
+    const bool keyed = keys || key_off;
+    // batch_mu owns c->stream, the scratch, the map and the model-id table for the whole call, and every writer of the state this
+    // call reads takes it too: the row a key resolves to, the edit of that row and the scale-down that reads the edited record see
+    // ONE sequence of states no other writer enters.  The state lock is taken only by an apply, for its in-place rewrite.
     std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (const int rc = plan_state_guard(c, "mmp_janitor_plan")) return rc;
+    if (const int rc = plan_state_guard(c, fn)) return rc;
+    if (keyed)
+        if (const int rc = model_id_space_guard(c, fn)) return rc;
     const int32_t M = c->n_models, P = c->snap.P;
-    if (p->self_pod < 0 || p->self_pod >= P) return fail(c, MMP_EINVAL, "mmp_janitor_plan: self_pod %d of %d", p->self_pod, P);
-    {
+    if (p->self_pod < 0 || p->self_pod >= P) return fail(c, MMP_EINVAL, "%s: self_pod %d of %d", fn, p->self_pod, P);
+    if (ch.sd && ch.sd->self_pod != p->self_pod)
+        return fail(c, MMP_EINVAL, "%s: the scale-down is self_pod %d's, the run self_pod %d's", fn, ch.sd->self_pod, p->self_pod);
+    if (keyed) {
+        // (by key the row is the device's own and lies in [-1, M); that no model has two rows is settled by the first kernel, on the map)
+        if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
+    } else {
         // the rows index the map: range and one-row-per-model are settled here, before any kernel reads them
         if (++c->u_gen == 0) ++c->u_gen;  // (generation 0 is what an untouched stamp carries)
         const uint64_t gen = (uint64_t)c->u_gen << 32;
         if (c->u_stamp.size() < (size_t)M) c->u_stamp.resize(M, 0);
         for (int32_t r = 0; r < n; r++) {
             const int32_t m = entries[r].model;
-            if (m < -1 || m >= M) return fail(c, MMP_EINVAL, "mmp_janitor_plan: row %d names model %d of %d", r, m, M);
+            if (m < -1 || m >= M) return fail(c, MMP_EINVAL, "%s: row %d names model %d of %d", fn, r, m, M);
             if (m < 0) continue;
-            if ((c->u_stamp[m] & ~0xffffffffull) == gen) return fail(c, MMP_EINVAL, "mmp_janitor_plan: model %d has two rows", m);
+            if ((c->u_stamp[m] & ~0xffffffffull) == gen) return fail(c, MMP_EINVAL, "%s: model %d has two rows", fn, m);
             c->u_stamp[m] = gen | (uint32_t)r;
         }
     }
-    *info = mmp_janitor_info{};
-    info->stopped_at = -1;
+    // (by row *info is reset here, as mmp_janitor_plan always did; by key a refused call writes nothing, and the duplicates are
+    // only known behind the first kernel: there it is reset behind that check)
+    if (!keyed) {
+        *info = mmp_janitor_info{};
+        info->stopped_at = -1;
+    }
+    const bool apply = flags & MMP_JANITOR_APPLY;
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel;  // (what the staged offsets are uploaded from: lives until the first synchronisation below)
     if (p->shutting_down) {  // :5880
+        if (keyed && n > 0) {  // nothing is evaluated; the keys are still resolved, and two entries of one record still refused
+            HIP_TRY(c, hipSetDevice(c->cfg.device));
+            if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
+            HIP_TRY(c, c->plan.rows_in.ensure((size_t)n * sizeof(mmp_janitor_entry)));
+            HIP_TRY(c, c->plan.call_scalars.ensure(sizeof(JanitorScalars)));
+            if (const int rc = model_map_cover(c, M, st)) return rc;
+            mmp_janitor_entry *d_in = c->plan.rows_in.as<mmp_janitor_entry>();
+            JanitorScalars *js = c->plan.call_scalars.as<JanitorScalars>();
+            HIP_TRY(c, hipMemcpyAsync(d_in, entries, (size_t)n * sizeof(mmp_janitor_entry), hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemsetAsync(js, 0, sizeof(JanitorScalars), st));
+            KT_BEGIN(c, st);
+            tasks_keys_launch(c, n, d_in, TasksJanitorClaim{c->plan.model_map.as<int32_t>(), js, *p, n});
+            hipLaunchKernelGGL(tasks_unclaim_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_in, n, c->plan.model_map.as<int32_t>());
+            KT_END(c, st);
+            HIP_TRY(c, hipGetLastError());
+            JanitorScalars hj{};
+            HIP_TRY(c, copy_sync(c, &hj, js, sizeof hj, hipMemcpyDeviceToHost));
+            c->plan.model_map_n = M;
+            kt_collect(c);
+            if (hj.n_dup != 0) return fail(c, MMP_EINVAL, "%s: %d entries name a model another entry of the call names", fn, hj.n_dup);
+        }
+        if (const int rc = tasks_model_idx(c, keyed, entries, n, model_idx_out)) return rc;
+        *info = mmp_janitor_info{};
+        info->stopped_at = -1;
         if (n > 0) memset(actions_out, MMP_JANITOR_NONE, (size_t)n);
         info->n_action[MMP_JANITOR_NONE] = n;
         return MMP_OK;
     }
-    const bool apply = flags & MMP_JANITOR_APPLY;
-    if (const int rc = plan_arena_guard(c, "mmp_janitor_plan", apply, n)) return rc;  // (refused before anything is done)
+    if (const int rc = plan_arena_guard(c, fn, apply, n)) return rc;  // (refused before anything is done)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
     const int nb = div_up(M, kJanBlock), n1 = std::max(n, 1);
     const int32_t cap_e = std::min(max_edits, M);
     // the row-sized scratch, carved from one buffer
@@ -7511,7 +7601,7 @@ try {
     const mmp_model_row *models = c->models.as<mmp_model_row>();
     const int32_t *ent_pod = c->ent_pod.as<int32_t>();
     const int64_t *ent_time = c->ent_time.as<int64_t>();
-    const mmp_janitor_entry *d_in = c->plan.rows_in.as<mmp_janitor_entry>();
+    mmp_janitor_entry *d_in = c->plan.rows_in.as<mmp_janitor_entry>();
     int32_t *map = c->plan.model_map.as<int32_t>();
     JanitorScalars *js = c->plan.call_scalars.as<JanitorScalars>();
     PruneScalars *ps = c->plan.totals.as<PruneScalars>();
@@ -7519,12 +7609,24 @@ try {
     int32_t *crow = (int32_t *)(tmp + o_crow), *orow = (int32_t *)(tmp + o_orow);
     uint8_t *drop = (uint8_t *)(tmp + o_drop), *act = (uint8_t *)(tmp + o_act);
     mmp_cache_entry *d_cands = (mmp_cache_entry *)(tmp + o_cands);
+    if (keyed && n > 0)
+        if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
+    if (ch.sd && ch.conc && n > 0) {  // the MaxConcCacheEntry rows in input-row order, and room for the candidates' beside them
+        HIP_TRY(c, c->s_c.ensure((size_t)n * sizeof(mmp_conc_entry)));
+        HIP_TRY(c, c->s_d.ensure((size_t)n * sizeof(mmp_conc_entry)));
+        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, ch.conc, (size_t)n * sizeof(mmp_conc_entry), hipMemcpyHostToDevice, st));
+    }
     if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, entries, (size_t)n * sizeof(mmp_janitor_entry), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(js, 0, sizeof(JanitorScalars), st));
     HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
     KT_BEGIN(c, st);  // device span of the plan
     const int gn = div_up(n, 256);
-    if (n > 0) hipLaunchKernelGGL(janitor_entry_kernel, dim3(gn), dim3(256), 0, st, d_in, n, map, *p, js);
+    if (n > 0) {
+        if (keyed)  // the row from the key, the claim of it on the map, the stop index: one launch in the entry kernel's place
+            tasks_keys_launch(c, n, d_in, TasksJanitorClaim{map, js, *p, n});
+        else
+            hipLaunchKernelGGL(janitor_entry_kernel, dim3(gn), dim3(256), 0, st, d_in, n, map, *p, js);
+    }
     if (nb > 0) {
         hipLaunchKernelGGL(janitor_count_kernel, dim3(nb), dim3(kJanBlock), 0, st, models, M, ent_pod, ent_time, pods, P, map, d_in, n, *p, js,
                            c->plan.block_counts.as<int32_t>());
@@ -7547,6 +7649,10 @@ try {
     HIP_TRY(c, hipStreamSynchronize(st));
     c->plan.model_map_n = M;
     kt_collect(c);
+    // two entries of one record: refused with nothing written (the finish kernel has put every claimed map word back to -1)
+    if (hj.n_dup != 0) return fail(c, MMP_EINVAL, "%s: %d entries name a model another entry of the call names", fn, hj.n_dup);
+    if (const int rc = tasks_model_idx(c, keyed, entries, n, model_idx_out)) return rc;
+    *info = mmp_janitor_info{};
     const int32_t ne = std::min(h.n_edits, max_edits), nc = std::min(hj.n_cands, max_cands);
     if (n > 0) HIP_TRY(c, copy_sync(c, actions_out, act, (size_t)n, hipMemcpyDeviceToHost));
     if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_janitor_edit), hipMemcpyDeviceToHost));
@@ -7560,13 +7666,44 @@ try {
     info->stopped_at = hj.stop_inv > 0 ? n - hj.stop_inv : -1;
     info->truncated = (h.n_edits > max_edits || hj.n_cands > max_cands) ? 1 : 0;
     for (int k = 0; k < 7; k++) info->n_action[k] = hj.n_action[k];
-    if (!apply || info->truncated || h.n_edits == 0) return MMP_OK;
+    if (!apply || info->truncated) return MMP_OK;
+    if (h.n_edits > 0)
+        if (const int rc = registry_apply_edits(c, h.n_edits, h.n_kept, edits_out, [&](int32_t base, int32_t arena_end) {  // the records without / with self_pod's entry
+                hipLaunchKernelGGL(janitor_build_kernel, dim3(div_up(h.n_edits, 256)), dim3(256), 0, st, c->plan.edits.as<mmp_janitor_edit>(),
+                                   c->plan.keep_off.as<int32_t>(), h.n_edits, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(),
+                                   c->ent_time.as<int64_t>(), base, arena_end, p->self_pod, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
+            }))
+            return rc;
+    // THE SCALE-DOWN IN THE SAME CALL (MM.java:6110-6145 is the tail of the one janitorTask): the candidates stand where the rank
+    // kernel put them, the registry holds what the two loops left, and nobody else has had the batch lock in between.  (A run that
+    // stopped at a repaired row has no candidates: the registry loop was never reached.)
+    if (!ch.sd || hj.n_cands == 0) return MMP_OK;
+    const int32_t nk = hj.n_cands;
+    const double before_ms = c->last_kernel_ms;
+    HIP_TRY(c, c->s_a.ensure((size_t)nk));
+    HIP_TRY(c, c->s_b.ensure((size_t)nk));
+    KT_BEGIN(c, st);
+    if (ch.conc)
+        hipLaunchKernelGGL(tasks_conc_gather_kernel, dim3(div_up(nk, 256)), dim3(256), 0, st, c->s_c.as<mmp_conc_entry>(), orow, nk,
+                           c->s_d.as<mmp_conc_entry>());
+    if (const int rc = scaledown_enqueue(c, st, d_cands, ch.conc ? c->s_d.as<mmp_conc_entry>() : nullptr, nk, ch.sd, ch.dyn_const)) return rc;
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, copy_sync(c, ch.removed_out, c->s_b.p, (size_t)nk, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    kt_add(c, before_ms);  // the call's device span: plan + apply + scale-down
+    return MMP_OK;
+}
+}  // namespace
 
-    return registry_apply_edits(c, h.n_edits, h.n_kept, edits_out, [&](int32_t base, int32_t arena_end) {  // the records without / with self_pod's entry
-        hipLaunchKernelGGL(janitor_build_kernel, dim3(div_up(h.n_edits, 256)), dim3(256), 0, st, c->plan.edits.as<mmp_janitor_edit>(),
-                           c->plan.keep_off.as<int32_t>(), h.n_edits, c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
-                           base, arena_end, p->self_pod, c->u_idx.as<int32_t>(), c->u_rows.as<mmp_model_row>());
-    });
+int mmp_janitor_plan(mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const mmp_janitor_params *p, uint32_t flags,
+                     uint8_t *actions_out, mmp_janitor_edit *edits_out, int32_t max_edits, mmp_cache_entry *cands_out,
+                     int32_t *cand_rows_out, int32_t max_cands, mmp_janitor_info *info)
+try {
+    if (janitor_args_bad(c, entries, n, p, flags, actions_out, edits_out, max_edits, cands_out, cand_rows_out, max_cands, info))
+        return fail(c, MMP_EINVAL, "mmp_janitor_plan: bad argument");
+    return janitor_drive(c, "mmp_janitor_plan", entries, n, nullptr, nullptr, p, flags, JanitorChain{}, nullptr, actions_out, edits_out, max_edits,
+                         cands_out, cand_rows_out, max_cands, info);
 } MMP_CATCH(c, "mmp_janitor_plan")
 
 namespace {
@@ -8361,21 +8498,30 @@ try {
                                 n_bytes_out);
 } MMP_CATCH(c, "mmp_vmodels_write_json")
 
-// rateTrackingTask: the one body of mmp_scaleup_plan (conc == null) and mmp_scaleup_plan_conc
-static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
-                             const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs, mmp_conc_out *conc_outs,
-                             uint8_t *overloaded_out, int32_t *skipped, mmp_conc_result *result)
+namespace {
+// What the three read-only periodic tasks refuse about their keys, behind the committed check and before anything is written or
+// staged (the order of mmp_registry_ops_k); called with batch_mu.  By row: nothing.
+int tasks_keys_guard(mmp_ctx *c, const char *fn, bool keyed, const int32_t *key_off, int32_t n)
 {
-    const bool latency = cp != nullptr;
-    if (!c || !p || !skipped || n < 0 || (n > 0 && (!entries || !outs)) || (latency && (!result || (n > 0 && (!conc || !conc_outs)))))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
+    if (!keyed) return MMP_OK;
+    if (const int rc = model_id_space_guard(c, fn)) return rc;
+    return check_offsets(c, fn, "key ", key_off, n);
+}
+
+// rateTrackingTask, the one body of mmp_scaleup_plan (conc == null), mmp_scaleup_plan_conc and mmp_scaleup_plan_k, for a caller
+// who HOLDS batch_mu (it owns c->stream and the scratch for the whole call, and every writer of the state the call reads —
+// commit, the loaders, registry events, a retirement — takes it too: the published snapshot, the registry and the model-id table
+// cannot change underneath).  keys / key_off both NULL: by row.  By key the entries' `model` is written on the device, one launch
+// in front of the plan (tasks_keyed_kernel), and the caller's is never read.
+int scaleup_locked(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const char *keys, const int32_t *key_off,
+                   const mmp_conc_entry *conc, int32_t n, const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs,
+                   mmp_conc_out *conc_outs, uint8_t *overloaded_out, int32_t *skipped, mmp_conc_result *result, int32_t *model_idx_out)
+{
+    const bool latency = cp != nullptr, keyed = keys || key_off;
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     const int32_t P = c->snap.P;
     if (P > 0 && !overloaded_out) return fail(c, MMP_EINVAL, "%s: overloaded_out is null", fn);
+    if (const int rc = tasks_keys_guard(c, fn, keyed, key_off, n)) return rc;
     if (P > 0) memset(overloaded_out, 0, (size_t)P);
     for (int32_t i = 0; i < n; i++) {
         outs[i] = mmp_scaleup_out{};
@@ -8394,9 +8540,27 @@ static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *
     // the three early returns of the task, MM.java:5646-5648, :5658-5660, :5667-5669
     const int64_t time_delta = (int64_t)((uint64_t)p->now - (uint64_t)p->last_check_time);
     *skipped = (time_delta * 5 < p->rate_check_interval_ms * 3 || c->stats.instance_count < 2 || n == 0) ? 1 : 0;
-    if (*skipped) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
+    std::vector<int32_t> krel;  // (what the staged offsets are uploaded from: lives until the synchronisation below)
+    if (*skipped) {  // the task returned before it looked at an entry: the rows of the keys are all there is to answer
+        if (keyed && n > 0 && model_idx_out) {  // the same launch as below, with no plan behind it (one resolution path)
+            HIP_TRY(c, hipSetDevice(c->cfg.device));
+            if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
+            HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_cache_entry)));
+            HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, entries, (size_t)n * sizeof(mmp_cache_entry), hipMemcpyHostToDevice, st));
+            KT_BEGIN(c, st);
+            tasks_keys_launch(c, n, c->s_reqs.as<mmp_cache_entry>(), TasksNoClaim{});
+            KT_END(c, st);
+            HIP_TRY(c, hipGetLastError());
+            const int rc = tasks_model_idx(c, true, entries, n, model_idx_out);
+            kt_collect(c);
+            return rc;
+        }
+        return tasks_model_idx(c, keyed, entries, n, model_idx_out);  // (by row: the caller's own rows; nothing else to answer)
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (keyed)
+        if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
     HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_cache_entry)));
     HIP_TRY(c, c->s_outs.ensure((size_t)n * sizeof(mmp_scaleup_out)));
     HIP_TRY(c, c->s_a.ensure((size_t)std::max(P, 1)));
@@ -8413,6 +8577,7 @@ static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *
     const int32_t b = (int32_t)((uint32_t)p->our_rpm - 2u * (uint32_t)p->scale_up_rpm_threshold);
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();
     KT_BEGIN(c, st);
+    if (keyed) tasks_keys_launch(c, n, c->s_reqs.as<mmp_cache_entry>(), TasksNoClaim{});
     if (latency)  // getExcludeSet's threshold comes from the task's averageModelParallelism (:5836)
         hipLaunchKernelGGL(conc_exclude_rpms_kernel, dim3(1), dim3(64), 0, st, cp->average_model_parallelism, p->our_rpm,
                            c->s_b.as<int32_t>() + 1, d_res);
@@ -8451,47 +8616,61 @@ static int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
-    return MMP_OK;
+    return tasks_model_idx(c, keyed, entries, n, model_idx_out);
 }
+
+// the argument check and the hold of batch_mu around scaleup_locked.  The state lock c->mu is NOT held: latency-path calls
+// (mmp_place_batch / _gate / _evict on the slots) keep flowing.
+int scaleup_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const char *keys, const int32_t *key_off,
+                      const mmp_conc_entry *conc, int32_t n, const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs,
+                      mmp_conc_out *conc_outs, uint8_t *overloaded_out, int32_t *skipped, mmp_conc_result *result, int32_t *model_idx_out)
+{
+    const bool latency = cp != nullptr;
+    if (!c || !p || !skipped || n < 0 || (n > 0 && (!entries || !outs)) || (latency && (!result || (n > 0 && (!conc || !conc_outs)))) ||
+        (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    return scaleup_locked(c, fn, entries, keys, key_off, conc, n, p, cp, outs, conc_outs, overloaded_out, skipped, result, model_idx_out);
+}
+}  // namespace
 
 int mmp_scaleup_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, const mmp_scaleup_params *p,
                      mmp_scaleup_out *outs, uint8_t *overloaded_out, int32_t *skipped)
 try {
-    return scaleup_plan_impl(c, "mmp_scaleup_plan", entries, nullptr, n, p, nullptr, outs, nullptr, overloaded_out, skipped, nullptr);
+    return scaleup_plan_impl(c, "mmp_scaleup_plan", entries, nullptr, nullptr, nullptr, n, p, nullptr, outs, nullptr, overloaded_out, skipped,
+                             nullptr, nullptr);
 } MMP_CATCH(c, "mmp_scaleup_plan")
+
+// by model id (or by row with keys == key_off == NULL); conc_params NULL: limitModelConcurrency == false
+int mmp_scaleup_plan_k(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n, const char *keys,
+                       const int32_t *key_off, const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs,
+                       mmp_conc_out *conc_outs, uint8_t *overloaded_out, int32_t *skipped, mmp_conc_result *result, int32_t *model_idx_out)
+try {
+    if (!cp && (conc || conc_outs || result))
+        return fail(c, MMP_EINVAL, "mmp_scaleup_plan_k: conc, conc_outs and result come with conc_params or not at all");
+    return scaleup_plan_impl(c, "mmp_scaleup_plan_k", entries, keys, key_off, conc, n, p, cp, outs, conc_outs, overloaded_out, skipped, result,
+                             model_idx_out);
+} MMP_CATCH(c, "mmp_scaleup_plan_k")
 
 int mmp_scaleup_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
                           const mmp_scaleup_params *p, const mmp_conc_params *cp, mmp_scaleup_out *outs, mmp_conc_out *conc_outs,
                           uint8_t *overloaded_out, int32_t *skipped, mmp_conc_result *result)
 try {
     if (!cp) return fail(c, MMP_EINVAL, "mmp_scaleup_plan_conc: conc_params is null");
-    return scaleup_plan_impl(c, "mmp_scaleup_plan_conc", entries, conc, n, p, cp, outs, conc_outs, overloaded_out, skipped, result);
+    return scaleup_plan_impl(c, "mmp_scaleup_plan_conc", entries, nullptr, nullptr, conc, n, p, cp, outs, conc_outs, overloaded_out, skipped,
+                             result, nullptr);
 } MMP_CATCH(c, "mmp_scaleup_plan_conc")
 
-// the janitor's scale-down: the one body of mmp_scaledown_plan (conc == null) and mmp_scaledown_plan_conc
-static int scaledown_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
-                               const mmp_scaledown_params *p, int64_t dyn_const, uint8_t *removed_out)
+namespace {
+// the janitor's scale-down ON THE DEVICE: the decision and the budget walk over n candidates that stand in device memory
+// (d_conc: their MaxConcCacheEntry rows beside them, or nullptr), into c->s_a (decide) and c->s_b (removed), which the caller has
+// sized.  Only enqueues, inside the caller's bracket; called with batch_mu, so that a caller who owns the lock can chain it behind
+// its own work — mmp_janitor_plan_k does, behind the apply.  The registry pointers are read HERE: an apply may have moved them.
+int scaledown_enqueue(mmp_ctx *c, hipStream_t st, const mmp_cache_entry *d_entries, const mmp_conc_entry *d_conc, int32_t n,
+                      const mmp_scaledown_params *p, int64_t dyn_const)
 {
-    if (!c || !p || n < 0 || (n > 0 && (!entries || !removed_out)))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
-    if (n == 0) return MMP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_cache_entry)));
-    HIP_TRY(c, c->s_a.ensure((size_t)n));
-    HIP_TRY(c, c->s_b.ensure((size_t)n));
-    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, entries, (size_t)n * sizeof(mmp_cache_entry), hipMemcpyHostToDevice, st));
-    if (conc) {
-        HIP_TRY(c, c->s_c.ensure((size_t)n * sizeof(mmp_conc_entry)));
-        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, conc, (size_t)n * sizeof(mmp_conc_entry), hipMemcpyHostToDevice, st));
-    }
     ScaledownArgs A;
-    A.entries = c->s_reqs.as<mmp_cache_entry>();
+    A.entries = d_entries;
     A.models = c->models.as<mmp_model_row>();
     A.ent_pod = c->ent_pod.as<int32_t>();
     A.ent_time = c->ent_time.as<int64_t>();
@@ -8510,50 +8689,83 @@ static int scaledown_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry
     A.n = n;
     A.n_models = c->n_models;
     A.P = c->snap.P;
-    A.conc = conc ? c->s_c.as<mmp_conc_entry>() : nullptr;
+    A.conc = d_conc;
     A.dyn_const = dyn_const;
-    KT_BEGIN(c, st);
     hipLaunchKernelGGL(scaledown_decide_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(scaledown_budget_kernel, dim3(1), dim3(64), 0, st, A);
+    return MMP_OK;
+}
+
+// the one body of mmp_scaledown_plan (conc == null), mmp_scaledown_plan_conc and mmp_scaledown_plan_k, for a caller who HOLDS
+// batch_mu (the ownership scaleup_locked states): the candidates staged, their keys resolved when there are any, then
+// scaledown_enqueue.  keys / key_off both NULL: by row.
+int scaledown_locked(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const char *keys, const int32_t *key_off,
+                     const mmp_conc_entry *conc, int32_t n, const mmp_scaledown_params *p, int64_t dyn_const, uint8_t *removed_out,
+                     int32_t *model_idx_out)
+{
+    const bool keyed = keys || key_off;
+    if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (const int rc = tasks_keys_guard(c, fn, keyed, key_off, n)) return rc;
+    if (n == 0) return MMP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel;  // (what the staged offsets are uploaded from: lives until the synchronisation below)
+    if (keyed)
+        if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
+    HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_cache_entry)));
+    HIP_TRY(c, c->s_a.ensure((size_t)n));
+    HIP_TRY(c, c->s_b.ensure((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, entries, (size_t)n * sizeof(mmp_cache_entry), hipMemcpyHostToDevice, st));
+    if (conc) {
+        HIP_TRY(c, c->s_c.ensure((size_t)n * sizeof(mmp_conc_entry)));
+        HIP_TRY(c, hipMemcpyAsync(c->s_c.p, conc, (size_t)n * sizeof(mmp_conc_entry), hipMemcpyHostToDevice, st));
+    }
+    KT_BEGIN(c, st);
+    if (keyed) tasks_keys_launch(c, n, c->s_reqs.as<mmp_cache_entry>(), TasksNoClaim{});
+    if (const int rc = scaledown_enqueue(c, st, c->s_reqs.as<mmp_cache_entry>(), conc ? c->s_c.as<mmp_conc_entry>() : nullptr, n, p, dyn_const))
+        return rc;
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(removed_out, c->s_b.p, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
-    return MMP_OK;
+    return tasks_model_idx(c, keyed, entries, n, model_idx_out);
 }
 
-int mmp_scaledown_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, const mmp_scaledown_params *p,
-                       uint8_t *removed_out)
-try {
-    return scaledown_plan_impl(c, "mmp_scaledown_plan", entries, nullptr, n, p, 0, removed_out);
-} MMP_CATCH(c, "mmp_scaledown_plan")
+// the argument check and the hold of batch_mu around scaledown_locked.  The state lock c->mu is NOT held: latency-path calls
+// (mmp_place_batch / _gate / _evict on the slots) keep flowing.
+int scaledown_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, const char *keys, const int32_t *key_off,
+                        const mmp_conc_entry *conc, int32_t n, const mmp_scaledown_params *p, int64_t dyn_const, uint8_t *removed_out,
+                        int32_t *model_idx_out)
+{
+    if (!c || !p || n < 0 || (n > 0 && (!entries || !removed_out)) || (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    return scaledown_locked(c, fn, entries, keys, key_off, conc, n, p, dyn_const, removed_out, model_idx_out);
+}
 
-int mmp_scaledown_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
-                            const mmp_scaledown_params *p, int64_t dynamic_rpm_scale_constant, uint8_t *removed_out)
-try {
-    if (n > 0 && !conc) return fail(c, MMP_EINVAL, "mmp_scaledown_plan_conc: conc is null");
-    return scaledown_plan_impl(c, "mmp_scaledown_plan_conc", entries, conc, n, p, dynamic_rpm_scale_constant, removed_out);
-} MMP_CATCH(c, "mmp_scaledown_plan_conc")
-
-int mmp_migration_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, int32_t self_pod, int64_t now,
-                       int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out)
-try {
-    if (!c || n < 0 || (n > 0 && (!entries || !action_out || !wait_out)))
-        return fail(c, MMP_EINVAL, "mmp_migration_plan: bad argument");
-    // batch_mu owns c->stream and the scratch for the whole call, and every writer of the state this call reads
-    // (commit, the loaders, registry events) takes it too: the published snapshot cannot change underneath.  The
-    // state lock c->mu is NOT held: latency-path calls (mmp_place_batch / _gate / _evict on the slots) keep flowing.
+// preShutdown's migration, the one body of mmp_migration_plan and mmp_migration_plan_k (the ownership scaleup_locked states)
+int migration_plan_impl(mmp_ctx *c, const char *fn, const mmp_cache_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                        int32_t self_pod, int64_t now, int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out, int32_t *model_idx_out)
+{
+    const bool keyed = keys || key_off;
+    if (!c || n < 0 || (n > 0 && (!entries || !action_out || !wait_out)) || (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
     std::lock_guard<std::mutex> gb(c->batch_mu);
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
+    if (const int rc = tasks_keys_guard(c, fn, keyed, key_off, n)) return rc;
     if (n == 0) return MMP_OK;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
+    std::vector<int32_t> krel;  // (what the staged offsets are uploaded from: lives until the synchronisation below)
+    if (keyed)
+        if (const int rc = tasks_keys_stage(c, fn, keys, key_off, n, krel)) return rc;
     HIP_TRY(c, c->s_reqs.ensure((size_t)n * sizeof(mmp_cache_entry)));
     HIP_TRY(c, c->s_a.ensure((size_t)n));
     HIP_TRY(c, c->s_b.ensure((size_t)n));
     HIP_TRY(c, hipMemcpyAsync(c->s_reqs.p, entries, (size_t)n * sizeof(mmp_cache_entry), hipMemcpyHostToDevice, st));
     KT_BEGIN(c, st);
+    if (keyed) tasks_keys_launch(c, n, c->s_reqs.as<mmp_cache_entry>(), TasksNoClaim{});
     hipLaunchKernelGGL(migration_plan_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, c->s_reqs.as<mmp_cache_entry>(), n,
                        c->models.as<mmp_model_row>(), c->n_models, c->ent_pod.as<int32_t>(), self_pod,
                        (int64_t)((uint64_t)now - (uint64_t)cutoff_age_ms), c->s_a.as<uint8_t>(), c->s_b.as<uint8_t>());
@@ -8563,8 +8775,61 @@ try {
     HIP_TRY(c, hipMemcpyAsync(wait_out, c->s_b.p, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
-    return MMP_OK;
+    return tasks_model_idx(c, keyed, entries, n, model_idx_out);
+}
+}  // namespace
+
+int mmp_scaledown_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, const mmp_scaledown_params *p,
+                       uint8_t *removed_out)
+try {
+    return scaledown_plan_impl(c, "mmp_scaledown_plan", entries, nullptr, nullptr, nullptr, n, p, 0, removed_out, nullptr);
+} MMP_CATCH(c, "mmp_scaledown_plan")
+
+int mmp_scaledown_plan_conc(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n,
+                            const mmp_scaledown_params *p, int64_t dynamic_rpm_scale_constant, uint8_t *removed_out)
+try {
+    if (n > 0 && !conc) return fail(c, MMP_EINVAL, "mmp_scaledown_plan_conc: conc is null");
+    return scaledown_plan_impl(c, "mmp_scaledown_plan_conc", entries, nullptr, nullptr, conc, n, p, dynamic_rpm_scale_constant, removed_out, nullptr);
+} MMP_CATCH(c, "mmp_scaledown_plan_conc")
+
+// by model id (or by row with keys == key_off == NULL); conc NULL: not latency-based
+int mmp_scaledown_plan_k(mmp_ctx *c, const mmp_cache_entry *entries, const mmp_conc_entry *conc, int32_t n, const char *keys,
+                         const int32_t *key_off, const mmp_scaledown_params *p, int64_t dynamic_rpm_scale_constant, uint8_t *removed_out,
+                         int32_t *model_idx_out)
+try {
+    return scaledown_plan_impl(c, "mmp_scaledown_plan_k", entries, keys, key_off, conc, n, p, conc ? dynamic_rpm_scale_constant : 0, removed_out,
+                               model_idx_out);
+} MMP_CATCH(c, "mmp_scaledown_plan_k")
+
+int mmp_migration_plan(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, int32_t self_pod, int64_t now,
+                       int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out)
+try {
+    return migration_plan_impl(c, "mmp_migration_plan", entries, n, nullptr, nullptr, self_pod, now, cutoff_age_ms, action_out, wait_out, nullptr);
 } MMP_CATCH(c, "mmp_migration_plan")
+
+int mmp_migration_plan_k(mmp_ctx *c, const mmp_cache_entry *entries, int32_t n, const char *keys, const int32_t *key_off, int32_t self_pod,
+                         int64_t now, int64_t cutoff_age_ms, uint8_t *action_out, uint8_t *wait_out, int32_t *model_idx_out)
+try {
+    return migration_plan_impl(c, "mmp_migration_plan_k", entries, n, keys, key_off, self_pod, now, cutoff_age_ms, action_out, wait_out,
+                               model_idx_out);
+} MMP_CATCH(c, "mmp_migration_plan_k")
+
+// the janitor by model id (or by row with keys == key_off == NULL), with its scale-down in the same call (scaledown != NULL)
+int mmp_janitor_plan_k(mmp_ctx *c, const mmp_janitor_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                       const mmp_janitor_params *p, uint32_t flags, const mmp_scaledown_params *scaledown, const mmp_conc_entry *conc,
+                       int64_t dynamic_rpm_scale_constant, int32_t *model_idx_out, uint8_t *actions_out, mmp_janitor_edit *edits_out,
+                       int32_t max_edits, mmp_cache_entry *cands_out, int32_t *cand_rows_out, int32_t max_cands, uint8_t *removed_out,
+                       mmp_janitor_info *info)
+try {
+    if (janitor_args_bad(c, entries, n, p, flags, actions_out, edits_out, max_edits, cands_out, cand_rows_out, max_cands, info) ||
+        (keys == nullptr) != (key_off == nullptr) || (!scaledown && conc) || (scaledown && max_cands > 0 && !removed_out))
+        return fail(c, MMP_EINVAL, "mmp_janitor_plan_k: bad argument");
+    // the scale-down reads the registry as the two loops LEFT it: only an applied run has such a registry
+    if (scaledown && !(flags & MMP_JANITOR_APPLY)) return fail(c, MMP_EINVAL, "mmp_janitor_plan_k: the scale-down needs MMP_JANITOR_APPLY");
+    return janitor_drive(c, "mmp_janitor_plan_k", entries, n, keys, key_off, p, flags,
+                         JanitorChain{scaledown, scaledown ? conc : nullptr, conc ? dynamic_rpm_scale_constant : 0, removed_out}, model_idx_out,
+                         actions_out, edits_out, max_edits, cands_out, cand_rows_out, max_cands, info);
+} MMP_CATCH(c, "mmp_janitor_plan_k")
 
 /* ---- stateful keyed caches (a12 + a13) ------------------------------------- */
 

@@ -1637,6 +1637,164 @@ class Solver:
                                              int(now), int(cutoff_age_ms), ptr(act), ptr(wait)))
         return act[: len(entries)], wait[: len(entries)]
 
+    # ---- the periodic tasks BY MODEL ID (include/mmplace.h "THE PERIODIC TASKS BY MODEL ID") ----
+    def _task_keys(self, keys, key_off, blob, null_keys, null_off):
+        """(key bytes, int32 offsets) as a _raw form passes them: keys a list of bytes/str or None (by row: both pointers NULL);
+        key_off / blob replace the packed offsets / bytes; the null_* switches pass NULL for that one argument."""
+        kblob, off32 = None, None
+        if keys is not None:
+            kblob, off = self._pack(keys)
+            off32 = off.astype(np.int32)
+        if blob is not None:
+            kblob = blob
+        if key_off is not None:
+            off32 = np.ascontiguousarray(key_off, dtype=np.int32)
+        return (None if null_keys else kblob), (None if null_off or off32 is None else off32)
+
+    def scaleup_plan_k(self, entries, keys, params, conc=None, conc_params=None):
+        """The rate task by model id: (model_idx, outs, overloaded[P], skipped) — with conc / conc_params (limitModelConcurrency ==
+        true) (model_idx, outs, conc_outs, overloaded[P], skipped, result) — from one mmp_scaleup_plan_k call: the keys resolved
+        and the entries evaluated under one hold of the batch lock; an unknown id and the empty row a deletion leaves are
+        model == -1.  keys=None: by row (entries["model"])."""
+        idx, outs, couts, ov, sk, res, rc = self.scaleup_plan_k_raw(entries, keys, params, conc, conc_params)
+        self._ck(rc)
+        return (idx, outs, ov, sk) if conc_params is None else (idx, outs, couts, ov, sk, res)
+
+    def scaleup_plan_k_raw(self, entries, keys, params, conc=None, conc_params=None, fill=0, key_off=None, blob=None, null_keys=False,
+                           null_off=False, null_idx=False, null_outs=False, null_skipped=False):
+        """One mmp_scaleup_plan_k call, the outputs filled with the byte `fill` first: (model_idx, outs, conc_outs, overloaded,
+        skipped, result, rc).  Does not raise."""
+        from ._lib import CACHE_ENTRY, CONC_ENTRY, CONC_OUT, CONC_PARAMS, CONC_RESULT, SCALEUP_OUT, SCALEUP_PARAMS
+        entries = np.ascontiguousarray(entries, dtype=CACHE_ENTRY)
+        n = len(entries)
+        params = np.ascontiguousarray(params, dtype=SCALEUP_PARAMS).reshape(1)
+        kblob, off32 = self._task_keys(keys, key_off, blob, null_keys, null_off)
+        latency = conc_params is not None
+        if latency:
+            conc = np.ascontiguousarray(conc, dtype=CONC_ENTRY)
+            assert len(conc) == n
+            cparams = np.ascontiguousarray(conc_params, dtype=CONC_PARAMS).reshape(1)
+        idx = np.zeros(max(n, 1), np.int32)
+        outs = np.zeros(max(n, 1), dtype=SCALEUP_OUT)
+        couts = np.zeros(max(n, 1), dtype=CONC_OUT)
+        res = np.zeros(1, dtype=CONC_RESULT)
+        ov = np.zeros(max(self.n_pods, 1), np.uint8)
+        sk = np.zeros(1, np.int32)
+        for a in (idx, outs, couts, res, ov, sk):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_scaleup_plan_k(self.h, ptr(entries) if n else None, ptr(conc) if latency and n else None, n, kblob,
+                                         None if off32 is None else ptr(off32), ptr(params), ptr(cparams) if latency else None,
+                                         None if null_outs or not n else ptr(outs), ptr(couts) if latency and n else None, ptr(ov),
+                                         None if null_skipped else sk.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         ptr(res) if latency else None, None if null_idx else ptr(idx))
+        return idx[:n].copy(), outs[:n].copy(), couts[:n].copy(), ov[: self.n_pods].copy(), int(sk[0]), res[0].copy(), rc
+
+    def scaledown_plan_k(self, entries, keys, params, conc=None, dynamic_rpm_scale_constant=0):
+        """The janitor's scale-down by model id: (model_idx, removed) from one mmp_scaledown_plan_k call.  keys=None: by row."""
+        idx, rem, rc = self.scaledown_plan_k_raw(entries, keys, params, conc, dynamic_rpm_scale_constant)
+        self._ck(rc)
+        return idx, rem
+
+    def scaledown_plan_k_raw(self, entries, keys, params, conc=None, dynamic_rpm_scale_constant=0, fill=0, key_off=None, blob=None,
+                             null_keys=False, null_off=False, null_idx=False, null_removed=False):
+        """One mmp_scaledown_plan_k call, the outputs filled with the byte `fill` first: (model_idx, removed, rc).  Does not raise."""
+        from ._lib import CACHE_ENTRY, CONC_ENTRY, SCALEDOWN_PARAMS
+        entries = np.ascontiguousarray(entries, dtype=CACHE_ENTRY)
+        n = len(entries)
+        params = np.ascontiguousarray(params, dtype=SCALEDOWN_PARAMS).reshape(1)
+        kblob, off32 = self._task_keys(keys, key_off, blob, null_keys, null_off)
+        if conc is not None:
+            conc = np.ascontiguousarray(conc, dtype=CONC_ENTRY)
+            assert len(conc) == n
+        idx = np.zeros(max(n, 1), np.int32)
+        rem = np.zeros(max(n, 1), np.uint8)
+        for a in (idx, rem):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_scaledown_plan_k(self.h, ptr(entries) if n else None, ptr(conc) if conc is not None and n else None, n, kblob,
+                                           None if off32 is None else ptr(off32), ptr(params), int(dynamic_rpm_scale_constant),
+                                           None if null_removed else ptr(rem), None if null_idx else ptr(idx))
+        return idx[:n].copy(), rem[:n].copy(), rc
+
+    def migration_plan_k(self, entries, keys, self_pod, now, cutoff_age_ms=3_600_000):
+        """preShutdown's migration by model id: (model_idx, action, wait) from one mmp_migration_plan_k call.  keys=None: by row."""
+        idx, act, wait, rc = self.migration_plan_k_raw(entries, keys, self_pod, now, cutoff_age_ms)
+        self._ck(rc)
+        return idx, act, wait
+
+    def migration_plan_k_raw(self, entries, keys, self_pod, now, cutoff_age_ms=3_600_000, fill=0, key_off=None, blob=None, null_keys=False,
+                             null_off=False, null_idx=False, null_action=False):
+        """One mmp_migration_plan_k call, the outputs filled with the byte `fill` first: (model_idx, action, wait, rc).  Does not raise."""
+        from ._lib import CACHE_ENTRY
+        entries = np.ascontiguousarray(entries, dtype=CACHE_ENTRY)
+        n = len(entries)
+        kblob, off32 = self._task_keys(keys, key_off, blob, null_keys, null_off)
+        idx = np.zeros(max(n, 1), np.int32)
+        act = np.zeros(max(n, 1), np.uint8)
+        wait = np.zeros(max(n, 1), np.uint8)
+        for a in (idx, act, wait):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_migration_plan_k(self.h, ptr(entries) if n else None, n, kblob, None if off32 is None else ptr(off32), int(self_pod),
+                                           int(now), int(cutoff_age_ms), None if null_action else ptr(act), ptr(wait),
+                                           None if null_idx else ptr(idx))
+        return idx[:n].copy(), act[:n].copy(), wait[:n].copy(), rc
+
+    def janitor_plan_k(self, entries, keys, params, apply: bool = True, dry: bool = False, scaledown=None, conc=None,
+                       dynamic_rpm_scale_constant=0, max_edits: int = 1024, max_candidates: int = 1024):
+        """janitorTask by model id: (model_idx, actions, edits, candidates, candidate rows, removed, info) from one
+        mmp_janitor_plan_k call — the keys resolved, the two loops evaluated and applied and, with `scaledown` (its params; conc:
+        the MaxConcCacheEntry rows in INPUT-row order), the candidates' scale-down decided under one hold of the batch lock;
+        removed is None without `scaledown`.  keys=None: by row.  The buffers are regrown to the run's totals when it reports
+        `truncated` (a truncated run changes nothing)."""
+        from ._lib import JANITOR_APPLY, JANITOR_DRY
+        flags = JANITOR_DRY if dry else (JANITOR_APPLY if apply else 0)
+        while True:
+            out = self.janitor_plan_k_raw(entries, keys, params, flags, max_edits, max_candidates, scaledown, conc, dynamic_rpm_scale_constant)
+            self._ck(out[-1])
+            info = out[6]
+            if not info["truncated"]:
+                break
+            max_edits, max_candidates = max(max_edits, int(info["n_edits"])), max(max_candidates, int(info["n_candidates"]))
+        if flags == JANITOR_APPLY and int(info["n_edits"]) and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return out[:5] + (out[5] if scaledown is not None else None,) + (info,)
+
+    def janitor_plan_k_raw(self, entries, keys, params, flags, max_edits, max_candidates, scaledown=None, conc=None,
+                           dynamic_rpm_scale_constant=0, fill=0, key_off=None, blob=None, null_keys=False, null_off=False, null_idx=False,
+                           null_removed=False, null_info=False):
+        """One mmp_janitor_plan_k call with exactly these capacities (0: NULL buffers), the outputs filled with the byte `fill`
+        first: (model_idx, actions, edits, candidates, rows, removed, info, rc) — the prefixes the call reports, every row of each
+        buffer when it fails.  Does not raise."""
+        from ._lib import CACHE_ENTRY, CONC_ENTRY, JANITOR_EDIT, JANITOR_ENTRY, JANITOR_INFO, JANITOR_PARAMS, SCALEDOWN_PARAMS
+        entries = np.ascontiguousarray(entries, dtype=JANITOR_ENTRY)
+        params = np.ascontiguousarray(params, dtype=JANITOR_PARAMS).reshape(1)
+        n = len(entries)
+        kblob, off32 = self._task_keys(keys, key_off, blob, null_keys, null_off)
+        if scaledown is not None:
+            scaledown = np.ascontiguousarray(scaledown, dtype=SCALEDOWN_PARAMS).reshape(1)
+        if conc is not None:
+            conc = np.ascontiguousarray(conc, dtype=CONC_ENTRY)
+            assert len(conc) == n
+        info = np.zeros(1, dtype=JANITOR_INFO)
+        idx = np.zeros(max(n, 1), np.int32)
+        actions = np.zeros(max(n, 1), np.uint8)
+        edits = np.zeros(max(max_edits, 1), dtype=JANITOR_EDIT)
+        cands = np.zeros(max(max_candidates, 1), dtype=CACHE_ENTRY)
+        rows = np.zeros(max(max_candidates, 1), np.int32)
+        rem = np.zeros(max(max_candidates, 1), np.uint8)
+        for a in (info, idx, actions, edits, cands, rows, rem):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_janitor_plan_k(self.h, ptr(entries) if n else None, n, kblob, None if off32 is None else ptr(off32), ptr(params),
+                                         int(flags), None if scaledown is None else ptr(scaledown),
+                                         ptr(conc) if conc is not None and n else None, int(dynamic_rpm_scale_constant),
+                                         None if null_idx else ptr(idx), ptr(actions) if n else None, ptr(edits) if max_edits else None,
+                                         int(max_edits), ptr(cands) if max_candidates else None, ptr(rows) if max_candidates else None,
+                                         int(max_candidates), None if null_removed or not max_candidates else ptr(rem),
+                                         None if null_info else ptr(info))
+        ok = rc == 0
+        ne = min(max_edits, int(info[0]["n_edits"])) if ok else max_edits
+        nc = min(max_candidates, int(info[0]["n_candidates"])) if ok else max_candidates
+        return (idx[:n].copy(), actions[:n].copy(), edits[:ne].copy(), cands[:nc].copy(), rows[:nc].copy(), rem[:nc].copy(), info[0].copy(), rc)
+
     # ---- pod-axis shard mode (include/mmplace.h "pod-axis sharding"; orchestrated by dist.py) ----
     def shard_configure(self, shard: int, n_shards: int):
         self._ck(self.lib.mmp_shard_configure(self.h, int(shard), int(n_shards)))
