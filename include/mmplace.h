@@ -202,7 +202,16 @@ typedef struct {
 /* Stateful per-pod caches (rows a12 + a13): the clhm operations and the ModelCacheUnloadBufManager
  * methods, replayed in caller order per cache by mmp_cache_replay.  Keys are interned model ids;
  * MMP_UNLOADBUF_KEY is the manager's pinned "___UNLOADBUF" pseudo-entry
- * (ModelCacheUnloadBufManager.java:42,88), which a managed cache must contain when it is loaded. */
+ * (ModelCacheUnloadBufManager.java:42,88), which a managed cache must contain when it is loaded.
+ * The eviction listener belongs to the cache (MM.java:2863-2879): what MMP_COP_PUT_IF_ABSENT or MMP_COP_UPDATE_WEIGHT evicts
+ * from a managed cache reaches entryRemoved like every other victim.  A read stamped <= 0 is a read "now" (clhm :383).
+ * Domain: the weight `arg` of MMP_COP_PUT_IF_ABSENT, _UPDATE_WEIGHT, _UBM_INSERT_NEW_ENTRY and _UBM_INSERT_FAILED_PLACEHOLDER is
+ * >= 1 (the weigher is CacheEntry.getWeight = Math.abs(weight), MM.java:1759: no caller can hand the cache a negative weight, and
+ * a weight of 0 is a node that is never linked, clhm :604); a negative or zero `arg` there is outside the domain and its
+ * outcome unspecified.  The manager's SUMS (weight + delta / + increase) may go negative or wrap: they are stored by magnitude
+ * as the weigher answers them (Integer.MIN_VALUE stays as it is, as Math.abs leaves it).
+ * MMP_COP_UBM_ADJUST_SPACE_REQUEST's `flag` (weakPrediction) is deliberately unused on the device: it negates CacheEntry.weight,
+ * a field only the weigher reads, by magnitude — nothing the cache or the manager shows depends on it. */
 #define MMP_UNLOADBUF_KEY (-1000000)
 #define MMP_COP_PUT_IF_ABSENT 0           /* clhm putIfAbsent(key, w=arg, time)  :804-834; result 1 = inserted      */
 #define MMP_COP_GET 1                     /* clhm get(key, time)                 :726-733; result = found           */

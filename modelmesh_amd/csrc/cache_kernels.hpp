@@ -264,6 +264,8 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
 template <int TW>
 __device__ __forceinline__ void ubm_set_weight_nodrain(Deque &D, int32_t k, int32_t w)
 {
+    // the weigher is CacheEntry.getWeight = Math.abs(weight) (MM.java:1759): a sum that wrapped negative weighs its magnitude
+    if (w < 0) w = (int32_t)(0u - (uint32_t)w);
     const int i = dq_find<TW>(D, k);
     if (i < 0) return;
     const int32_t diff = (int32_t)((uint32_t)w - (uint32_t)D.wt[D.head + i]);
@@ -359,14 +361,16 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         }
         D.wsize += o.arg;
         dq_insert<TW>(D, o.time == 0 ? now : o.time, o.arg, o.key);
-        dq_evict<TW>(D, false);
+        // the eviction listener is the cache's (MM.java:2863-2879): on a managed cache these victims reach entryRemoved too
+        dq_evict<TW>(D, D.reserved >= 0);
         dq_refresh_oldest(D);
+        ubm_drain<TW>(D);
         return 1;
     }
     case MMP_COP_GET: {  // clhm :726-733, applyRead :503-521
         const int i = dq_find<TW>(D, o.key);
         if (i < 0) return 0;
-        dq_touch<TW>(D, i, o.time, now);
+        dq_touch<TW>(D, i, o.time > 0 ? o.time : 0, now);  // afterRead :383: a read stamped <= 0 is a read "now"
         dq_reposition<TW>(D, i);
         dq_refresh_oldest(D);
         return 1;
@@ -389,8 +393,9 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
             dq_touch<TW>(D, i, o.time, now);
             dq_reposition<TW>(D, i);
         }
-        dq_evict<TW>(D, false);
+        dq_evict<TW>(D, D.reserved >= 0);
         dq_refresh_oldest(D);
+        ubm_drain<TW>(D);
         return 1;
     }
     case MMP_COP_REMOVE: {  // clhm :861-870, RemovalTask :614-627

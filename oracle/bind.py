@@ -124,6 +124,10 @@ def load() -> C.CDLL:
         lib.orc_ubm_buffer_weight.argtypes = [U]
         lib.orc_ubm_insert_new_entry.restype = C.c_int
         lib.orc_ubm_insert_new_entry.argtypes = [U, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+        lib.orc_ubm_put_if_absent.restype = C.c_int
+        lib.orc_ubm_put_if_absent.argtypes = [U, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+        lib.orc_ubm_update_weight.restype = C.c_int
+        lib.orc_ubm_update_weight.argtypes = [U, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
         lib.orc_ubm_adjust_new_entry_space_request.argtypes = [U, C.c_int32, C.c_int32, C.c_int64]
         lib.orc_ubm_cache_space_is_ready.restype = C.c_int
         lib.orc_ubm_cache_space_is_ready.argtypes = [U, C.c_int32]
@@ -392,7 +396,11 @@ class CCache:
         L, c, u = self.lib, C.byref(self.c), (C.byref(self.u) if self.u is not None else None)
         ev0 = self.u.n_evicted if self.u is not None else 0
         plain = None
-        if op == 0:
+        if op == 0 and self.u is not None:  # a managed cache's victims reach the listener whoever writes
+            res = L.orc_ubm_put_if_absent(u, key, arg, time, now)
+        elif op == 2 and self.u is not None:
+            res = L.orc_ubm_update_weight(u, key, arg, time, now)
+        elif op == 0:
             plain = self.put_if_absent(key, arg, time, now)
             res = 0 if plain is None else 1
         elif op == 1:

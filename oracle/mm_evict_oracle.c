@@ -137,7 +137,7 @@ int orc_cache_get(orc_cache *c, int32_t key, int64_t last_used, int64_t now)
 {
     int32_t i = orc_cache_find(c, key);
     if (i < 0) return 0;
-    touch(&c->nodes[i], last_used, now);
+    touch(&c->nodes[i], last_used > 0 ? last_used : 0, now); /* afterRead :383: a read stamped <= 0 is a read "now" */
     deque_reposition(c, i);
     refresh_oldest(c);
     return 1;
@@ -266,9 +266,11 @@ static void ubm_evict(orc_ubm *u, int64_t now)
 static void ubm_set_weight(orc_ubm *u, int32_t key, int32_t w, int64_t now)
 {
     orc_cache *c = u->cache;
+    /* the weigher is CacheEntry.getWeight = Math.abs(weight), MM.java:1759: a sum that wrapped negative weighs its magnitude */
+    if (w < 0) w = (int32_t)(0u - (uint32_t)w);
     int32_t i = orc_cache_find(c, key);
     if (i < 0) return;
-    int32_t diff = w - c->nodes[i].weight;
+    int32_t diff = (int32_t)((uint32_t)w - (uint32_t)c->nodes[i].weight);
     if (diff == 0) return;
     c->nodes[i].weight = w;
     c->weighted_size += diff;
@@ -309,17 +311,9 @@ int32_t orc_ubm_buffer_weight(const orc_ubm *u)
     return i < 0 ? 0 : u->cache->nodes[i].weight;
 }
 
-/* insertNewEntry, :130-145 */
-int orc_ubm_insert_new_entry(orc_ubm *u, int32_t key, int32_t weight, int64_t last_used, int64_t now)
+/* AddTask.run up to its evict(), clhm :602-607: the new node linked at its place */
+static void ubm_link_new(orc_cache *c, int32_t key, int32_t weight, int64_t last_used, int64_t now)
 {
-    ubm_adjust_agg(u, -weight, now);
-    orc_cache *c = u->cache;
-    if (orc_cache_find(c, key) >= 0) {
-        orc_cache_get(c, key, last_used, now);
-        ubm_adjust_agg(u, weight, now);
-        return 0;
-    }
-    /* putIfAbsent with the victims' weights captured */
     orc_node nd = {0, weight, key};
     nd.last_used = last_used == 0 ? now : last_used;
     c->weighted_size += weight;
@@ -333,7 +327,56 @@ int orc_ubm_insert_new_entry(orc_ubm *u, int32_t key, int32_t weight, int64_t la
     memmove(&c->nodes[l + 2], &c->nodes[l + 1], (size_t)(c->n - l - 1) * sizeof(orc_node));
     c->nodes[l + 1] = nd;
     c->n++;
+}
+
+/* insertNewEntry, :130-145 */
+int orc_ubm_insert_new_entry(orc_ubm *u, int32_t key, int32_t weight, int64_t last_used, int64_t now)
+{
+    ubm_adjust_agg(u, -weight, now);
+    orc_cache *c = u->cache;
+    if (orc_cache_find(c, key) >= 0) {
+        orc_cache_get(c, key, last_used, now);
+        ubm_adjust_agg(u, weight, now);
+        return 0;
+    }
+    ubm_link_new(c, key, weight, last_used, now);
     u->total_occupancy += weight;
+    ubm_evict(u, now);
+    refresh_oldest(c);
+    return 1;
+}
+
+/* putIfAbsent / put / replaceQuietly on a managed cache past the manager: the cache's eviction listener is ModelMesh whoever
+ * writes (MM.java:2863-2879), so these victims reach entryRemoved as well */
+int orc_ubm_put_if_absent(orc_ubm *u, int32_t key, int32_t weight, int64_t last_used, int64_t now)
+{
+    orc_cache *c = u->cache;
+    if (orc_cache_find(c, key) >= 0) {
+        orc_cache_get(c, key, last_used, now);
+        return 0;
+    }
+    ubm_link_new(c, key, weight, last_used, now);
+    ubm_evict(u, now);
+    refresh_oldest(c);
+    return 1;
+}
+
+int orc_ubm_update_weight(orc_ubm *u, int32_t key, int32_t new_weight, int64_t new_time, int64_t now)
+{
+    orc_cache *c = u->cache;
+    int32_t i = orc_cache_find(c, key);
+    if (i < 0) return 0;
+    int32_t diff = (int32_t)((uint32_t)new_weight - (uint32_t)c->nodes[i].weight); /* Java's int arithmetic wraps */
+    c->nodes[i].weight = new_weight;
+    if (diff == 0) {
+        if (new_time >= 0) orc_cache_get(c, key, new_time, now);
+        return 1;
+    }
+    c->weighted_size += diff;
+    if (new_time >= 0 && new_time != c->nodes[i].last_used) {
+        touch(&c->nodes[i], new_time, now);
+        deque_reposition(c, i);
+    }
     ubm_evict(u, now);
     refresh_oldest(c);
     return 1;

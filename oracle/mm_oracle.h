@@ -359,6 +359,9 @@ typedef struct {
 void orc_ubm_init(orc_ubm *u, orc_cache *cache, int32_t reserved, int64_t now);
 int32_t orc_ubm_buffer_weight(const orc_ubm *u);
 int orc_ubm_insert_new_entry(orc_ubm *u, int32_t key, int32_t weight, int64_t last_used, int64_t now);
+/* the plain writes on a managed cache: their victims reach the manager's entryRemoved as well (the listener is the cache's) */
+int orc_ubm_put_if_absent(orc_ubm *u, int32_t key, int32_t weight, int64_t last_used, int64_t now);
+int orc_ubm_update_weight(orc_ubm *u, int32_t key, int32_t new_weight, int64_t new_time, int64_t now);
 void orc_ubm_adjust_new_entry_space_request(orc_ubm *u, int32_t increase, int32_t key, int64_t now);
 int orc_ubm_cache_space_is_ready(const orc_ubm *u, int32_t required);
 int orc_ubm_claim_requested_space_if_ready(orc_ubm *u, int32_t required, int64_t now);

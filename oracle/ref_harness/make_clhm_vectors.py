@@ -4,7 +4,8 @@ from /root/reference: clhm/ConcurrentLinkedHashMap.java, clhm/LinkedDeque.java, 
 operation streams of tests/ref_clhm_cases.py — per operation: result, evicted keys in listener order, unload-buffer weight,
 weightedSize(), oldestTime(); per cache at the end: the eviction deque (key, weight, lastUsed), capacity, the manager's fields.
 Run in the build container (the GPU box has no reference tree and only reads the committed file).
-usage: python oracle/ref_harness/make_clhm_vectors.py"""
+usage: python oracle/ref_harness/make_clhm_vectors.py            (tests/golden/ref_clhm.npz)
+       python oracle/ref_harness/make_clhm_vectors.py --edges    (tests/golden/ref_clhm_edges.npz: ref_clhm_cases.edge_cases())"""
 import os
 import subprocess
 import sys
@@ -86,5 +87,47 @@ def run_case(caps, reserved, ops):
     return outs, ev, np.stack(hdr), keys, wts, lus
 
 
+def main_edges():
+    """The edge cases: the same harness on the whole case and on the prefix before every call boundary (entry counts and states
+    there are part of the vectors).  Refused: a case the domain rule would cut, a pair the reference answers alike (or one
+    marked `alike` that it does not), a tier without what it is there for."""
+    out_path = os.environ.get("MMP_CLHM_OUT") or os.path.join(ROOT, "tests", "golden", "ref_clhm_edges.npz")
+    out, names = {}, []
+    for case in rc.edge_cases():
+        name, caps, reserved, ops = case["name"], case["caps"], case["reserved"], case["ops"]
+        v = {k: case[k] for k in ("caps", "reserved", "ops", "bounds", "runs", "pairs", "tag_names", "pair_names")}
+        v["tier"] = np.array(case["tier"])
+        for j, b in enumerate(case["bounds"][1:], 1):
+            outs, ev, hdr, keys, wts, lus = run_case(caps, reserved, ops[:b])
+            for i, o in enumerate(outs):
+                if rc.UNLOADBUF_KEY in ev[o["evicted_off"]: o["evicted_off"] + o["n_evicted"]]:
+                    sys.exit(f"{name}: operation {i} {ops[i]} evicts the pinned entry: outside the domain, the case is refused")
+            v[f"b{j}/hdr"] = hdr
+            v[f"b{j}/key"] = np.concatenate(keys)
+            v[f"b{j}/weight"] = np.concatenate(wts)
+            v[f"b{j}/last_used"] = np.concatenate(lus)
+        v["outs"], v["evicted"] = outs, ev
+        assert (outs["weighted_size"] >= 0).all()
+        for p in case["pairs"]:
+            a, b = rc.run_signature(v, case, int(p["a"])), rc.run_signature(v, case, int(p["b"]))
+            if (a == b) != bool(p["alike"]):
+                sys.exit(f"{name}: pair '{case['pair_names'][p['name']]}' is answered {'alike' if a == b else 'differently'} by the reference: refused")
+        missing = [k for k, ok in rc.edge_occurrence(v, case["tier"], name).items() if not ok]
+        if missing:
+            sys.exit(f"{name}: does not occur: {missing}")
+        for k, x in v.items():
+            if k in ("ops", "outs"):  # a column per entry: the file stays a fraction of the size
+                for f in x.dtype.names:
+                    out[f"{name}/{k}.{f}"] = np.ascontiguousarray(x[f])
+            else:
+                out[f"{name}/{k}"] = x
+        names.append(name)
+        print(f"{name}: {len(caps)} runs, {len(ops)} operations, {len(case['pairs'])} pairs ({int(case['pairs']['alike'].sum())} alike), "
+              f"{int(outs['n_evicted'].sum())} evictions, boundaries {list(case['bounds'])}")
+    out["names"] = np.array(names)
+    np.savez_compressed(out_path, **out)
+    print(f"wrote {out_path}: {os.path.getsize(out_path) / 1e6:.2f} MB, {len(names)} cases")
+
+
 if __name__ == "__main__":
-    main()
+    main_edges() if "--edges" in sys.argv[1:] else main()

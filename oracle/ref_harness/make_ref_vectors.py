@@ -10,7 +10,7 @@ tests/golden/ref_gate_edges.npz: the guard cases at the edges of their value dom
 tests/golden/ref_place_edges.npz: the load-target cases at the edges of theirs (place_edge_vectors below).
 tests/golden/ref_rebalance_edges.npz: the rate task, the janitor's scale-down and the reaper's proactive loads at the edges of theirs
 (rebalance_edge_vectors below).
-usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges | --rebalance-edges]"""
+usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges | --rebalance-edges | --serve-edges]"""
 import os
 import subprocess
 import sys
@@ -406,6 +406,34 @@ def rebalance_edge_vectors():
     print(f"wrote {REBALANCE_EDGE_OUT}: {os.path.getsize(REBALANCE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
 
 
+SERVE_EDGE_OUT = os.environ.get("MMP_REF_SERVE_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_serve_edges.npz")
+
+
+def serve_edge_vectors():
+    """tests/golden/ref_serve_edges.npz: ForwardingLB.getNext on rf.serve_edge_cases().  Refused: a pair the reference decides
+    alike in chosen and chosenTimeStamp, a case without each outcome and each branch of the loop."""
+    out, names = {}, []
+    n_rows = n_pairs = 0
+    for name, fleet, ids, reqs, in_use, last_used, xp, xt, meta in rf.serve_edge_cases():
+        blob = rf.input_blob(fleet, ids, serve=(reqs, in_use, last_used, xp, xt))
+        _, _, serve, _ = run(blob, 0, len(reqs))
+        for p in meta["pairs"]:
+            if tuple(serve[p["a"]]) == tuple(serve[p["b"]]):
+                sys.exit(f"{name}: pair '{meta['pair_names'][p['name']]}' is decided alike by the reference: refused")
+        missing = [k for k, ok in rf.serve_edge_occurrence(fleet, reqs, xp, xt, serve).items() if not ok]
+        if missing:
+            sys.exit(f"{name}: does not occur: {missing}")
+        out[f"{name}/serve"] = serve
+        out[f"{name}/digest"] = np.frombuffer(rf.digest(blob).encode(), np.uint8)
+        names.append(name)
+        n_rows, n_pairs = n_rows + len(reqs), n_pairs + len(meta["pairs"])
+        print(f"{name}: {fleet.n_pods} instances, {len(reqs)} rows, {len(meta['pairs'])} pairs: {int((serve[:, 0] >= 0).sum())} remote, "
+              f"{int((serve[:, 0] == -2).sum())} self, {int((serve[:, 0] == -1).sum())} none")
+    out["names"] = np.array(names)
+    np.savez_compressed(SERVE_EDGE_OUT, **out)
+    print(f"wrote {SERVE_EDGE_OUT}: {os.path.getsize(SERVE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases, {n_rows} rows, {n_pairs} pairs")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
@@ -413,6 +441,8 @@ def main():
         return gate_edge_vectors()
     if "--place-edges" in sys.argv[1:]:  # only the load-target edge cases
         return place_edge_vectors()
+    if "--serve-edges" in sys.argv[1:]:  # only the serve choice's edge cases
+        return serve_edge_vectors()
     if "--rebalance-edges" in sys.argv[1:]:  # only the rebalancers' edge cases
         return rebalance_edge_vectors()
     out = {}

@@ -2722,3 +2722,254 @@ def place_row_kinds(fleet, order, reqs, extra):
                     break
             out.append((kind, full))
     return out
+
+
+# ---- the serve choice (ForwardingLB.getNext, MM.java:4316-4391) at the edges of its value domain: tests/golden/ref_serve_edges.npz
+# A ROW is one request on a model of its own; a copy is (inUse, lastUsed, loadStarted, listed).  The harness takes inUse /
+# lastUsed / LIVE per INSTANCE, so a case hands out instances on demand: a copy gets the first instance behind the previous
+# copy's (the entries stand in id order, and ids here are in index order) that carries its three values, else a new one; a
+# case that runs out of instances is closed and the next one begun.  A PAIR is two rows of one case whose VIEW (below) differs
+# in one value by one unit; the generator refuses a pair the reference decides alike in chosen and chosenTimeStamp.
+SERVE_EDGE_FLEETS = (8, 65)
+SERVE_NOW = wl.NOW_MS
+I32_MAX, I64_MAX, I64_MIN = 2**31 - 1, 2**63 - 1, -2**63
+SERVE_PAIR = np.dtype([("a", "<i4"), ("b", "<i4"), ("name", "<i4")])
+SERVE_CODA = 5  # rows every case ends with: remote, self, none, a still-loading pick, an unlisted copy
+
+
+class _Full(Exception):
+    pass
+
+
+class _ServeCase:
+    def __init__(self, P):
+        self.P, self.pods, self.rows, self.pairs, self.tags = P, [], [], [], []
+
+    def pod(self, attr, after):
+        for i in range(after + 1, len(self.pods)):
+            if self.pods[i] == attr:
+                return i
+        if len(self.pods) >= self.P - 2:  # (two instances stay free for the coda)
+            raise _Full()
+        self.pods.append(attr)
+        return len(self.pods) - 1
+
+    def row(self, tag, copies, self_at=None, flags=0, lif=0, lit=0, assume=3000, excl=(), model=None):
+        """copies: [(inUse, lastUsed, loadStarted[, listed])] in id order; self_at: which of them is the caller (None: the caller
+        holds no copy); excl: [(copy index or None for an instance without a copy, time or ANY_TIME)]"""
+        at, ent = -1, []
+        for c in copies:
+            at = self.pod((int(c[0]), int(c[1]), bool(c[3]) if len(c) > 3 else True), at)
+            ent.append((at, int(c[2])))
+        ex = [((ent[k][0] if k is not None else self.P - 1), int(t)) for k, t in excl]
+        self.rows.append(dict(ent=ent, self_pod=ent[self_at][0] if self_at is not None else -1, flags=flags, lif=lif, lit=lit,
+                              assume=assume, excl=ex, model=model))
+        self.tags.append(tag)
+        return len(self.rows) - 1
+
+
+def _serve_groups():
+    """[(rows: [(tag, kwargs)], pairs: [(name, a, b)] by position in rows)]: the tier, fleet by fleet the same"""
+    T = SERVE_NOW
+    done = T - 100_000  # a load long complete
+    G = []
+
+    def group(rows, pairs=()):
+        G.append((rows, list(pairs)))
+    # the cutoff (:4350-4352): loadStarted at cutoff - 1 / cutoff; a competitor that is complete and busier stands beside it
+    for assume in (0, 3000, 2**31):
+        cut = T - assume
+        for idx in (0, 3, 4, 8):
+            rows = []
+            for d in (-1, 0):
+                cp = [(5, 50, cut - 10)] * 9
+                cp[idx] = (0, 50, cut + d)
+                rows.append((f"cutoff/{assume}/{idx}/{d:+d}", dict(copies=cp, assume=assume)))
+            group(rows, [(f"loadStarted at cutoff - 1 / cutoff, assume {assume}, copy {idx}", 0, 1)])
+    # inUse against the minimum (:4354, :4358): a second copy at min - 1 / min / min + 1, less and more recently used
+    for m in (0, 1, I32_MAX - 1):
+        for lu2, what in ((50, "older"), (200, "newer")):
+            rows = [(f"inuse/{m}/{what}/{d:+d}", dict(copies=[(m, 100, done), (m + d, lu2, done)])) for d in (-1, 0, 1) if m + d <= I32_MAX]
+            pairs = [(f"inUse at min - 1 / min, min {m}, {what}", 0, 1)] if what == "newer" else []
+            if what == "older" and len(rows) == 3:
+                pairs = [(f"inUse at min / min + 1, min {m}, {what}", 1, 2)]
+            group(rows, pairs)
+    # Integer.MAX_VALUE (:4358, :4372): a complete copy at MAX_VALUE is chosen and leaves min at MAX_VALUE, so a still-loading
+    # copy BEHIND it takes its place; in front of it it does not
+    for first in ("complete", "loading"):
+        rows = []
+        for u in (I32_MAX - 1, I32_MAX):
+            q, s = (u, 50, done), (0, 50, T + 5)
+            rows.append((f"quirk/{first}-first/{u}", dict(copies=[q, s] if first == "complete" else [s, q])))
+        group(rows, [("inUse 2^31 - 2 / 2^31 - 1 on a complete copy, a loading copy behind", 0, 1)] if first == "complete" else [])
+    group([("quirk/max-and-never-used", dict(copies=[(I32_MAX, I64_MAX, done), (I32_MAX, 7, done)])),
+           ("quirk/max-alone", dict(copies=[(I32_MAX, I64_MAX, done)]))])
+    # lastUsed ties (:4362): equal / one below at equal inUse; the first in id order keeps a tie
+    for lu in (I64_MAX, I64_MAX - 1, 0, -1, I64_MIN + 1):
+        rows = [(f"tie/{lu}/{d:+d}", dict(copies=[(1, lu, done), (1, lu + d, done)])) for d in (0, -1)]
+        group(rows, [(f"lastUsed equal / one below, {lu}", 1, 0)])
+    # the caller as a copy (:4334-4342, :4356, :4360, :4381)
+    for xs in (0, 1):  # MMP_SERVE_EXCLUDE_SELF
+        for pos in (0, 1):
+            other = (1, 100, done)
+            for lu2, what in ((50, "older"), (200, "newer")):
+                rows = []
+                for lif in (0, 1, 2):
+                    cp = [(9, 9, done), other] if pos == 0 else [other, (9, 9, done)]
+                    rows.append((f"self/x{xs}/at{pos}/lif{lif}/{what}", dict(copies=cp, self_at=pos, flags=xs, lif=lif, lit=lu2)))
+                pairs = []
+                if not xs and pos == 1:
+                    pairs = [(f"local_in_flight at inUse - 1 / inUse, {what}", 0, 1)] if what == "newer" else \
+                        [(f"local_in_flight at inUse / + 1, {what}", 1, 2)]
+                group(rows, pairs)
+            rows = [(f"self/x{xs}/at{pos}/lit{d:+d}", dict(copies=[(1, 100, done), (9, 9, done)][:: 1 if pos else -1], self_at=pos,
+                                                          flags=xs, lif=1, lit=100 + d)) for d in (-1, 0, 1)]
+            group(rows, [("last_invoke_time one below / at the other's lastUsed", 0, 1)] if not xs and pos == 1 else [])
+            rows = [(f"self/x{xs}/at{pos}/prefer/{lu}", dict(copies=[(1, lu, done), (9, 9, done)][:: 1 if pos else -1], self_at=pos,
+                                                            flags=xs | 2, lif=1, lit=T)) for lu in (-1, 0, 1)]
+            group(rows, [("preferSelf against a lastUsed of 0 / 1", 1, 2)] if not xs and pos == 1 else [])
+        group([(f"self/x{xs}/alone", dict(copies=[(9, 9, done)], self_at=0, flags=xs)),
+               (f"self/x{xs}/alone-loading", dict(copies=[(9, 9, T + 1)], self_at=0, flags=xs))])
+    # still loading (:4369-4376): the earliest start, ties to the first; a complete copy in front or behind wins
+    for lead in ((), ((5, 5, done),)):
+        for trail in ((), ((5, 5, done),)):
+            rows = [(f"loading/{len(lead)}{len(trail)}/{d:+d}", dict(copies=list(lead) + [(0, 0, T + 10), (0, 0, T + 10 + d)] + list(trail)))
+                    for d in (-1, 0, 1)]
+            group(rows, [("loadStarted at firstStarted - 1 / firstStarted", 0, 1)] if not lead and not trail else [])
+    # exclusions (MapFilteringSet.apply, :4279-4283): the copy's load, one millisecond off, any load; exclusion index below 4 and
+    # from 4 on; copy index below 4 and from 4 on
+    for pad_x in (0, 4):
+        for pad_c in (0, 4):
+            front = [(7, 7, done)] * pad_c
+            rows = []
+            for t, what in ((done, "hit"), (done + 1, "miss"), (_lib.ANY_TIME, "any")):
+                rows.append((f"excl/x{pad_x}/c{pad_c}/{what}", dict(copies=front + [(0, 0, done), (5, 5, done)],
+                                                                   excl=[(None, _lib.ANY_TIME)] * pad_x + [(pad_c, t)])))
+            group(rows, [(f"exclusion at the copy's load / one millisecond off, exclusion {pad_x}, copy {pad_c}", 0, 1)])
+    group([("excl/caller", dict(copies=[(9, 9, done), (5, 5, done)], self_at=0, lif=0, excl=[(0, _lib.ANY_TIME)])),
+           ("excl/only-complete", dict(copies=[(0, 0, done), (5, 5, T + 3), (5, 5, T + 2)], excl=[(0, done)])),
+           ("excl/all-but-one", dict(copies=[(0, 0, done), (1, 1, done), (2, 2, done)], excl=[(0, done), (1, _lib.ANY_TIME)])),
+           ("excl/all", dict(copies=[(0, 0, done), (1, 1, done)], excl=[(0, done), (1, _lib.ANY_TIME)])),
+           ("excl/all-of-nine", dict(copies=[(k, k, done) for k in range(9)], excl=[(k, _lib.ANY_TIME) for k in range(9)]))])
+    # listing (:4343-4346): a copy on an instance litelinks does not list is passed over
+    group([("unlisted/copy0", dict(copies=[(0, 0, done, False), (5, 5, done)])),
+           ("unlisted/copy5", dict(copies=[(7, 7, done)] * 5 + [(0, 0, done, False), (6, 6, done)])),
+           ("unlisted/all", dict(copies=[(0, 0, done, False), (0, 0, T + 1, False)])),
+           ("unlisted/caller", dict(copies=[(0, 0, done, False), (5, 5, done)], self_at=0))])
+    group([("empty", dict(copies=[])), ("model/-1", dict(copies=[], model=-1)), ("model/past-the-end", dict(copies=[], model=10**6))])
+    return G
+
+
+def _serve_coda(c):
+    T, done = SERVE_NOW, SERVE_NOW - 100_000
+    c.P += 2  # the two instances kept free
+    c.row("coda/remote", [(0, 0, done)])
+    c.row("coda/self", [(0, 0, done)], self_at=0)
+    c.row("coda/none", [(0, 0, done)], excl=[(0, done)])
+    c.row("coda/loading", [(0, 0, T + 1)])
+    c.row("coda/unlisted", [(0, 0, done), (0, 0, done, False)])
+    c.P -= 2
+
+
+def _serve_case_arrays(name, c, seed):
+    P = c.P
+    fleet, _ = _edge_fleet(P, seed)
+    pods = c.pods + [(0, 0, True)] * (P - len(c.pods))
+    fleet.pods["id_order"] = np.arange(P)
+    fleet.pods["replica_set"] = -1
+    fleet.pods["flags"] = [_lib_flag_live() if p[2] else 0 for p in pods]
+    ids = ["s" + _b36(p, 4) for p in range(P)]
+    n = len(c.rows)
+    models = np.zeros(n, dtype=_lib.MODEL_ROW)
+    reqs = np.zeros(n, dtype=_lib.SERVE_REQ)
+    ent_pod, ent_time, xp, xt = [], [], [], []
+    for i, r in enumerate(c.rows):
+        models[i] = (0, len(ent_pod), len(r["ent"]), 0, fleet.now - 5_000)
+        ent_pod += [p for p, _ in r["ent"]]
+        ent_time += [t for _, t in r["ent"]]
+        reqs[i] = (i if r["model"] is None else r["model"], r["self_pod"], r["flags"], r["lif"], r["lit"], r["assume"], len(xp),
+                   len(r["excl"]), 0, 0)
+        xp += [p for p, _ in r["excl"]]
+        xt += [t for _, t in r["excl"]]
+    fleet.models, fleet.ent_pod, fleet.ent_time = models, np.array(ent_pod, np.int32), np.array(ent_time, np.int64)
+    in_use = np.array([p[0] for p in pods], np.int32)
+    last_used = np.array([p[1] for p in pods], np.int64)
+    tag_names = sorted(set(c.tags))
+    pair_names = sorted({p[0] for p in c.pairs})
+    meta = {"tags": np.array([tag_names.index(t) for t in c.tags], np.int32), "tag_names": np.array(tag_names),
+            "pairs": np.array([(a, b, pair_names.index(nm)) for nm, a, b in c.pairs], dtype=SERVE_PAIR),
+            "pair_names": np.array(pair_names) if pair_names else np.zeros(0, "<U1")}
+    return name, fleet, ids, reqs, in_use, last_used, np.array(xp, np.int32), np.array(xt, np.int64), meta
+
+
+@functools.lru_cache(maxsize=1)
+def _serve_edge_all():
+    out = []
+    for P in SERVE_EDGE_FLEETS:
+        cases, cur = [], _ServeCase(P)
+        for rows, pairs in _serve_groups():
+            if P == 8 and any(len(kw["copies"]) > 6 for _, kw in rows):
+                continue  # (a model of nine copies needs the larger fleet)
+            for attempt in (0, 1):
+                mark = (len(cur.pods), len(cur.rows), len(cur.pairs))
+                try:
+                    at = [cur.row(tag, **kw) for tag, kw in rows]
+                    cur.pairs += [(nm, at[a], at[b]) for nm, a, b in pairs]
+                    break
+                except _Full:
+                    assert attempt == 0, ("a group that no empty case holds", rows[0][0])
+                    del cur.pods[mark[0]:], cur.rows[mark[1]:], cur.tags[mark[1]:], cur.pairs[mark[2]:]
+                    cases.append(cur)
+                    cur = _ServeCase(P)
+        cases.append(cur)
+        for k, c in enumerate(cases):
+            _serve_coda(c)
+            out.append(_serve_case_arrays(f"serve_edges_{P}_{k}", c, 70 + k))
+    return out
+
+
+def serve_edge_cases():
+    """(name, fleet, ids, reqs, in_use, last_used, excl_pod, excl_time, meta): meta = tags, tag_names, pairs, pair_names"""
+    return _serve_edge_all()
+
+
+def serve_row_view(fleet, reqs, in_use, last_used, xp, xt, i):
+    """everything request i hands ForwardingLB.getNext, as a flat tuple of integers: per copy in id order (is the caller,
+    listed, inUse, lastUsed, loadStarted), then flags, local_in_flight, last_invoke_time, assume_completed_ms and per exclusion
+    (the copy it names or -1, any-time, time)"""
+    r = reqs[i]
+    v = []
+    pods = []
+    if 0 <= r["model"] < len(fleet.models):
+        m = fleet.models[r["model"]]
+        for e in range(int(m["ent_off"]), int(m["ent_off"] + m["n_loaded"])):
+            p = int(fleet.ent_pod[e])
+            pods.append(p)
+            v += [int(p == r["self_pod"]), int((fleet.pods["flags"][p] & 2) != 0), int(in_use[p]), int(last_used[p]), int(fleet.ent_time[e])]
+    v += [int(r["flags"]), int(r["local_in_flight"]), int(r["last_invoke_time"]), int(r["assume_completed_ms"])]
+    for k in range(int(r["excl_off"]), int(r["excl_off"] + r["n_excl"])):
+        anyt = int(xt[k]) == _lib.ANY_TIME
+        v += [pods.index(int(xp[k])) if int(xp[k]) in pods else -1, int(anyt), 0 if anyt else int(xt[k])]
+    return tuple(v)
+
+
+def serve_edge_occurrence(fleet, reqs, xp, xt, serve):
+    """{an outcome or a branch of the loop: whether some row of the case takes it}, from the inputs and the reference's answers"""
+    now = int(fleet.now)
+    occ = {"remote": bool((serve[:, 0] >= 0).any()), "self": bool((serve[:, 0] == _lib.MMP_SELF).any()),
+           "none": bool((serve[:, 0] == _lib.MMP_NONE).any()), "a complete copy chosen": False, "a still-loading copy chosen": False,
+           "a copy excluded": False, "an unlisted copy": False, "the caller among the copies": False}
+    for i, r in enumerate(reqs):
+        if not 0 <= r["model"] < len(fleet.models):
+            continue
+        m = fleet.models[r["model"]]
+        pods = fleet.ent_pod[m["ent_off"]: m["ent_off"] + m["n_loaded"]]
+        times = fleet.ent_time[m["ent_off"]: m["ent_off"] + m["n_loaded"]]
+        cutoff = now - int(r["assume_completed_ms"])
+        if serve[i, 0] != _lib.MMP_NONE:
+            occ["a complete copy chosen" if serve[i, 1] < cutoff else "a still-loading copy chosen"] = True
+        occ["an unlisted copy"] |= bool(((fleet.pods["flags"][pods] & 2) == 0).any())
+        occ["the caller among the copies"] |= bool((pods == r["self_pod"]).any())
+        for k in range(int(r["excl_off"]), int(r["excl_off"] + r["n_excl"])):
+            occ["a copy excluded"] |= bool(((pods == xp[k]) & ((xt[k] == _lib.ANY_TIME) | (times == xt[k]))).any())
+    return occ
