@@ -1111,7 +1111,7 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
         if (const int rc = grant_place_lds(c)) return rc;
     // NOBAR kernels: a region per wavefront (place_wave_lds) instead of the shared one
     const size_t lds_nobar = (size_t)kPlaceWaves * place_wave_lds(wpad);
-    rs.memo_tail_lds = lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit;
+    rs.memo_tail_lds = lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && (size_t)kPlaceWaves * memo_region_bytes(S.T) <= c->lds_limit;
     HIP_TRY(c, order_after_registry(c, st));
     // 2. the route; a split route holds the stream's buffer from here until its tail is enqueued (miss_buffer)
     const int grid = div_up(n, kPlaceBlock);
@@ -1128,7 +1128,7 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     }
     if (t.split_notail) words = nullptr;  // (diagnostics: the undecided requests are not even recorded)
     // 3. the launch
-    const size_t lds_memo = (size_t)kPlaceWaves * memo_stage_bytes(S.T);  // a copy of the types' records per wavefront
+    const size_t lds_memo = (size_t)kPlaceWaves * memo_region_bytes(S.T);  // per wavefront: a copy of the types' records / its lane scratch
     const dim3 block(kPlaceBlock), tails(t.tail_blocks);
     const bool tail = !t.split_notail;
     const mmp_place_caller C = o.caller ? *o.caller : mmp_place_caller{};

@@ -2911,6 +2911,24 @@ __device__ __forceinline__ void build_long_memo_body(int t, const Snap &S, LongM
     }
 }
 
+// The ordinary lane phase of one resolved request, as place_block's common branch and the cold branch of place_memo_body run it: the
+// type's head window first (`use_wins`, wave-uniform: there are windows — `Ws`, in LDS or global memory; `scr` = this lane's scratch
+// column, SCR lanes per column), then — WALK — lane_decide_r on the same request where the window cannot answer.  kLaneDone: `o` is
+// the result row; every other code is the caller's to route (the long phase, case (b), the general path; without WALK also
+// kLaneHeadMiss: the walk is still to do).
+template <int SCR, bool WALK = true>
+__device__ __forceinline__ int lane_phase(const Snap &S, const PlaceArgs &A, ResolvedReq &r, bool use_wins, const TypeWin *Ws, uint64_t *scr,
+                                          mmp_place_out &o, const BLds &Bt)
+{
+    int code = kLaneHeadMiss;
+    if (use_wins) code = lane_decide_win<false, false, SCR>(S, A, r, Ws, scr, o);
+    if (WALK && code == kLaneHeadMiss) {
+        merge_late_extras(r);
+        code = lane_decide_r<false>(S, A, r, o, Bt);
+    }
+    return code;
+}
+
 // NOBAR (the kernels with the shortlist check in front: place_batch_m_kernel, place_batch_c_m_kernel): no workgroup barrier at all —
 // the head windows are read from global memory (a few L1-resident rows) instead of being staged in LDS by the workgroup, and a
 // wavefront keeps the general path's list for itself.  A wavefront whose requests the shortlists all cover then neither waits for
@@ -3028,15 +3046,9 @@ __device__ __forceinline__ void place_block(const Snap &S, const PlaceArgs &A, i
             const bool rec = S.lmemo != nullptr && long_memo_try(S, A, r, o);  // (S.lmemo: wave-uniform)
             code = kLaneDone;
             if (!rec) code = lane_decide_r<false, true>(Sl, A, r, o, Bt);
-        } else {
-            if (use_wins)
-                code = NOBAR ? lane_decide_win<false, false, 64>(S, A, r, Ws, s_scr + lane_id(), o)
-                             : lane_decide_win(S, A, r, Ws, s_scr + threadIdx.x, o);
-            if (code == kLaneHeadMiss) {
-                merge_late_extras(r);
-                code = lane_decide_r<false>(S, A, r, o, Bt);
-            }
-        }
+        } else
+            code = NOBAR ? lane_phase<64>(S, A, r, use_wins, Ws, s_scr + lane_id(), o, Bt)
+                         : lane_phase<kPlaceBlock>(S, A, r, use_wins, Ws, s_scr + threadIdx.x, o, Bt);
         if (WITH_LONG && NOBAR && (code == kLaneLong || code == kLaneCaseB)) {  // the prefix-table phase at once, in this lane
             code = lane_decide<false, true, FORM>(Sl, A, d, o, Bt, C);
             if (code == kLaneDone)
@@ -3298,22 +3310,39 @@ constexpr int kSplitFromC = 8 * 1024 * 64;
 // ---- the split form (round 6): a launch that does nothing but the shortlist check, and a dense tail --------------------------------
 // place_batch_m_kernel carries the check AND the ordinary path — ~150 instructions in front of ~1000, one register allocation (72 VGPRs
 // + scratch), 25 KB of LDS per workgroup — so the requests the records cover pay for the ones they do not.  Here the two are two
-// launches.  place_memo_kernel: a lane per request, memo_try and nothing else — the records in LDS (a copy per wavefront), no barrier,
-// no scratch, 8 wavefronts per SIMD.  A wavefront with requests the check did not decide (one in sixteen, C3) reserves room for them
-// in one of kRestLists lists — wavefront w in list w mod 64: ONE returning atomic on a counter that ~1/64 of those wavefronts share
-// (a launch-wide list behind ONE counter was 16 ns per atomic in sequence, profiles/r5/shortlist_experiments v3) — and leaves their
-// indices there.  place_tail_kernel, queued right behind it on the same stream (so it runs beside the next batch's first launch, given a
-// second stream): workgroup g takes lists g, g + G, ..., reads their counts and entries — two dependent loads, no scan (summing a word
-// per first-launch wavefront took a tail workgroup 8 us) — decides them with the ordinary place_block, windows, lists, general path
-// and all (place_block<..., LIST>), and zeroes its counters for the stream's next batch.  With the check answering 99.8 % of a batch
-// of request rows (C3) the tail is a thousand requests; a batch the records do not fit (every request with a position inside its list)
-// still comes out right — the tail then loops — and the host stops splitting when a tail reports more than 1/32 of its batch
-// (mmp_ctx::split_off).
+// launches.  place_memo_kernel: a lane per request, memo_try — the records in LDS (a copy per wavefront), no barrier, no scratch, 8
+// wavefronts per SIMD — and, in the few wavefronts that hold requests the check did not decide (one in fifty on the bench's batches, one
+// in sixteen on C3 rows at large), a cold branch in which those lanes ask their type's head window (lane_phase without the walk; its
+// scratch columns lie over the wavefront's own copy of the records).  What the window does not answer either — the walk, the long
+// phase, case (b), the general path: a handful of rows per batch — gets room in one of kRestLists lists — wavefront w in list w mod 64:
+// ONE returning atomic on a counter that ~1/64 of those wavefronts share (a launch-wide list behind ONE counter was 16 ns per atomic in
+// sequence, profiles/r5/shortlist_experiments v3) — and its index there; the number of rows the CHECK left goes to a word of its own
+// in the same counter line (rest_left_word).  place_tail_kernel, queued right behind it on the same stream (so it runs beside the next
+// batch's first launch, given a second stream): workgroup g takes lists g, g + G, ...; every wavefront reads their counts, and a
+// workgroup whose lists are empty — the normal case — ends there: one level of loads, no LDS, no barrier.  Otherwise it reads the
+// entries — two dependent loads, no scan (summing a word per first-launch wavefront took a tail workgroup 8 us) — decides them with the
+// ordinary place_block, windows, lists, general path and all (place_block<..., LIST>), and zeroes its counters for the stream's next
+// batch.  Workgroup 0 reports the sum of the "left by the check" words and zeroes them.  A batch the records do not fit (every request
+// with a position inside its list) still comes out right — the cold branch, and the tail behind it, then decide all of it — and the
+// host stops splitting when a tail reports that the check left more than 1/32 of its batch (mmp_ctx::split_off).  Before the cold
+// branch the tail decided every row the check left, behind a kernel boundary and its own chain of dependent loads: where two streams
+// share a hardware queue that was a quarter of a step (profiles/split_rest: 16.3 -> 14.0 us per 800k-row call at four queues).
 constexpr int kRestLists = 64;
 constexpr int kRestCntStride = 32;  // ints between two counters: a 128-byte line each
 // ints of the stream's buffer for a first launch of n_words wavefronts: the counters, then kRestLists lists of rest_list_cap entries
 __host__ __device__ constexpr int rest_list_cap(int n_words) { return ((n_words + kRestLists - 1) / kRestLists) * 64; }
 __host__ __device__ constexpr size_t rest_buffer_ints(int n_words) { return (size_t)kRestLists * kRestCntStride + (size_t)kRestLists * rest_list_cap(n_words); }
+
+// LDS of the first launch, per wavefront: its copy of the records, later (cold) its 64 lanes' scratch columns of the lane phase
+__host__ __device__ constexpr int memo_region_bytes(int type_rows)
+{
+    return memo_stage_bytes(type_rows) > kWinWords * 64 * 8 ? memo_stage_bytes(type_rows) : kWinWords * 64 * 8;
+}
+// the "left by the check" word of the list that the wavefront of decision d appends to: second word of the list's counter line
+__device__ __forceinline__ int32_t *rest_left_word(int32_t *__restrict__ rest, int d)
+{
+    return rest + (__builtin_amdgcn_readfirstlane(d >> 6) & (kRestLists - 1)) * kRestCntStride + 1;
+}
 
 // the undecided requests of this wavefront (`todo` lanes): room in its list — ONE returning atomic — then their indices
 __device__ __forceinline__ void rest_append(int32_t *__restrict__ rest, int32_t cap, int d, bool todo)
@@ -3339,7 +3368,7 @@ __device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &
     // its candidate list and what its own positions are to the list from LDS instead of as three more dependent levels of (L1-resident)
     // global gathers — a record is 80 bytes per lane, more than the request itself.
     const int stage = memo_stage_bytes(S.T);
-    unsigned char *mine = smem + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * stage;
+    unsigned char *mine = smem + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * memo_region_bytes(S.T);
     {
         const char *src = reinterpret_cast<const char *>(S.memo);
         for (int c = 0; c < stage; c += 1024)
@@ -3364,7 +3393,31 @@ __device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &
     }
     bool todo = false;
     if (live) todo = !memo_try<FORM>(S, A, rq, d, reinterpret_cast<const TypeMemo *>(mine));
-    rest_append(rest, cap, d, todo);
+    // The rows the check leaves (COLD: one wavefront in fifty on the bench's batches).  Nearly all of them are the head window's to
+    // answer on this very lane — the caller as the best instance, the best or first eligible instance excluded, a third excluded
+    // candidate — so the wavefront that finds them decides them on the spot (lane_phase without the walk: the windows from global
+    // memory, as the barrier-free place_block reads them), and only what the window hands on goes to the tail's lists: the walk
+    // (lane_decide_r), the long phase, case (b), the general path.  The lanes' scratch columns lie over this wavefront's OWN copy of the
+    // records (memo_region_bytes), which it has read for the last time: no other wavefront's region is touched, nothing is waited for.
+    // Measured, C3, 800k rows on four streams (profiles/split_rest): with the walk in here as well the kernel takes 72 VGPRs at 7
+    // wavefronts per SIMD and 168 bytes of scratch per lane — a first launch that never enters the branch is then 0.4 us (a queue per
+    // stream) to 1.2 us (four queues) slower per call; the window alone leaves it at 58 VGPRs, 8 wavefronts, no scratch at all, and the
+    // tail's lists are as empty.  The request row stays in registers for the branch (fetching it again: +0.4 us per call).
+    const uint64_t mk = __ballot(todo);
+    if (mk) {  // (wave-uniform)
+        if (rest && lane_id() == __ffsll((unsigned long long)mk) - 1)  // what the tail reports: rows the check left (rest_left_word)
+            __hip_atomic_fetch_add(rest_left_word(rest, d), __popcll((unsigned long long)mk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        wave_sync();  // the records' last read lies before the scratch's first write
+        if (todo) {
+            ResolvedReq r = resolve_req<false, true>(S, A, rq);
+            mmp_place_out o;
+            if (lane_phase<64, false>(S, A, r, A.wins != nullptr, A.wins, reinterpret_cast<uint64_t *>(mine) + lane_id(), o, BLds{}) == kLaneDone) {
+                store_out_streaming(A.outs + d, o);
+                todo = false;
+            }
+        }
+        rest_append(rest, cap, d, todo);
+    }
 }
 __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void place_memo_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap)
 {
@@ -3393,18 +3446,26 @@ __device__ __forceinline__ void place_tail_body(const Snap &S, const PlaceArgs &
     const int G = gridDim.x, g = blockIdx.x;
     if (g >= kRestLists) return;
     const int mine = (kRestLists - g + G - 1) / G;  // lists g, g + G, ...
+    // Every wavefront reads the counts of the workgroup's lists for itself: the first launch decides on the spot what the head windows
+    // answer (place_memo_body), so the lists are normally EMPTY, and such a workgroup leaves here — one level of loads, no LDS, no barrier,
+    // no window or tile touched.  (The counts are what the first launch left: nothing writes them while the tail's workgroups start.)
+    const int lane = tid & 63;
+    const int c = lane < mine ? rest[(g + lane * G) * kRestCntStride] : 0;
+    if (g == 0 && tid < 64) {
+        // the rows the check left (rest_left_word): workgroup 0 alone reads the 64 words, reports their sum and zeroes them
+        const int lw = rest[tid * kRestCntStride + 1];
+        const int all = wave_sum_i32(lw);
+        if (report && tid == 0) {
+            __hip_atomic_store(report, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(report + 1, A.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        if (lw) rest[tid * kRestCntStride + 1] = 0;
+    }
+    if (!__ballot(c != 0)) return;  // (workgroup-uniform: every wavefront read the same words; the counters are zero already)
     if (tid < 64) {
-        const int c = tid < mine ? rest[(g + tid * G) * kRestCntStride] : 0;
         const int incl = wave_incl_scan_i32(c);
         t_cnt[tid + 1] = incl;
         if (tid == 0) t_cnt[0] = 0;
-        if (report && g == 0) {  // (every list's count: read here, at the very start — the other workgroups zero theirs at their end)
-            const int all = wave_sum_i32(rest[tid * kRestCntStride]);
-            if (tid == 0) {
-                __hip_atomic_store(report, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(report + 1, A.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
     }
     __syncthreads();
     const int total = t_cnt[mine];
