@@ -14,6 +14,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -228,8 +229,8 @@ struct GateSlot {  // mmp_gate_batch: as many 144-byte requests as the request b
     static constexpr int kN = (int)(kSlotBufBytes[kSlotReq] / sizeof(mmp_gate_req)), kExcl = 4096, kExplicit = 4096;
     static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_gate_req)), excl_pod = slot_first(kSlotPool, kExcl, 4),
                                 explicit_pool = slot_after(excl_pod, kExplicit, 4), excl_time = slot_after(explicit_pool, kExcl, 8),
-                                outs = slot_first(kSlotOut, kN, sizeof(mmp_gate_out));
-    static_assert(slot_fits({reqs, excl_pod, explicit_pool, excl_time, outs}), "gate slot layout");
+                                gouts = slot_first(kSlotOut, kN, sizeof(mmp_gate_out));
+    static_assert(slot_fits({reqs, excl_pod, explicit_pool, excl_time, gouts}), "gate slot layout");
 };
 struct MissSlot {  // mmp_miss_batch: the load-target half where mmp_place_batch has it, the guards' half behind
     static constexpr int kN = 256, kPool = 2048;  // kPool: each of extras, exclusion pairs, explicit
@@ -248,68 +249,71 @@ struct RouteSlot {  // mmp_route_batch: the serve half shares the guards' exclus
                                 gouts = slot_first(kSlotOut, kN, sizeof(mmp_gate_out)), souts = slot_after(gouts, kN, sizeof(mmp_serve_out));
     static_assert(slot_fits({greqs, sreqs, counters, excl_pod, explicit_pool, excl_time, gouts, souts}), "route slot layout");
 };
-// The request calls by model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck; keyed_kernels.hpp): the layout of the call they
-// resolve in front of, with the key bytes (kKeyedPad readable bytes behind them) and the n + 1 key offsets behind its requests and
-// the resolved rows behind its results.  kKeyBytes: the key bytes a call may bring onto a slot.
-constexpr int kKeyedN = 256, kKeyedKeyBytes = kKeyedLdsBytes;
-struct KeyedPlaceSlot {  // a 256-request layout of its own: PlaceSlot fills its buffers
-    static constexpr int kN = kKeyedN, kExtra = MissSlot::kPool, kKeyBytes = kKeyedKeyBytes;
-    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), keys = slot_after(reqs, kKeyBytes + kKeyedPad, 1),
-                                key_off = slot_after(keys, kN + 1, 4), extra = slot_first(kSlotPool, kExtra, 4),
-                                outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out)), idx = slot_after(outs, kN, 4);
-    static_assert(slot_fits({reqs, keys, key_off, extra, outs, idx}), "keyed place slot layout");
+// The request calls by id: the layout of the call they resolve in front of, with what the resolver reads behind its requests and the
+// rows it resolves behind its results.  A tail is that addition, stated once per resolver and put behind any base: `req_end` is
+// the base's last region of the request buffer, `out_end` its last region of the result buffer.  kKeyBytes / kNfBytes: the bytes
+// of each a call may bring onto a slot — what the resolving kernel stages in LDS of each.
+constexpr int kKeyedN = 256;
+// By model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck; keyed_kernels.hpp): the key bytes (kKeyedPad readable bytes
+// behind them) and the n + 1 key offsets; the n resolved rows.
+template <const SlotRegion &req_end, const SlotRegion &out_end>
+struct KeyTail {
+    static constexpr int kKeyBytes = kKeyedLdsBytes, kNfBytes = 0;
+    static constexpr SlotRegion keys = slot_after(req_end, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kKeyedN + 1, 4),
+                                idx = slot_after(out_end, kKeyedN, 4);
+    static constexpr bool fits = slot_fits({keys, key_off, idx});
 };
+// By VMODEL id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv; vkeyed_kernels.hpp): the vmodel key bytes, the n + 1 key
+// offsets, the notFoundModelId bytes (each byte region with kKeyedPad readable bytes behind it), their n + 1 offsets and the n flag
+// words; the n mmp_vseam_row.
+static_assert(sizeof(mmp_vseam_row) == 24, "mmp_vseam_row is 24 bytes");
+template <const SlotRegion &req_end, const SlotRegion &out_end>
+struct VKeyTail {
+    static constexpr int kKeyBytes = kVKeyedLdsBytes, kNfBytes = kVKeyedLdsBytes;
+    static constexpr SlotRegion keys = slot_after(req_end, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kKeyedN + 1, 4),
+                                nf = slot_after(key_off, kNfBytes + kKeyedPad, 1), nf_off = slot_after(nf, kKeyedN + 1, 4),
+                                flags = slot_after(nf_off, kKeyedN, 4), vm = slot_after(out_end, kKeyedN, sizeof(mmp_vseam_row));
+    static constexpr bool fits = slot_fits({keys, key_off, nf, nf_off, flags, vm});
+};
+template <template <const SlotRegion &, const SlotRegion &> class Tail>
+struct KeyedPlaceSlot {  // a 256-request layout of its own: PlaceSlot fills its buffers
+    static constexpr int kN = kKeyedN, kExtra = MissSlot::kPool;
+    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), extra = slot_first(kSlotPool, kExtra, 4),
+                                outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out));
+    using T = Tail<reqs, outs>;
+    static_assert(slot_fits({reqs, extra, outs}) && T::fits, "keyed place slot layout");
+};
+template <template <const SlotRegion &, const SlotRegion &> class Tail>
 struct KeyedMissSlot {
     using L = MissSlot;
-    static constexpr int kN = kKeyedN, kKeyBytes = kKeyedKeyBytes;
-    static constexpr SlotRegion keys = slot_after(L::greqs, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
-                                idx = slot_after(L::gouts, kN, 4);
-    static_assert(kN <= L::kN && slot_fits({L::preqs, L::greqs, keys, key_off, L::extra, L::excl_pod, L::explicit_pool, L::excl_time, L::pouts, L::gouts, idx}),
-                  "keyed miss slot layout");
+    static constexpr int kN = kKeyedN;
+    using T = Tail<L::greqs, L::gouts>;
+    static_assert(kN <= L::kN && T::fits, "keyed miss slot layout");
 };
+template <template <const SlotRegion &, const SlotRegion &> class Tail>
 struct KeyedRouteSlot {
     using L = RouteSlot;
-    static constexpr int kN = kKeyedN, kKeyBytes = kKeyedKeyBytes;
-    static constexpr SlotRegion keys = slot_after(L::counters, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
-                                idx = slot_after(L::souts, kN, 4);
-    static_assert(kN <= L::kN && slot_fits({L::greqs, L::sreqs, L::counters, keys, key_off, L::excl_pod, L::explicit_pool, L::excl_time, L::gouts, L::souts, idx}),
-                  "keyed route slot layout");
+    static constexpr int kN = kKeyedN;
+    using T = Tail<L::counters, L::souts>;
+    static_assert(kN <= L::kN && T::fits, "keyed route slot layout");
 };
-// The request calls by VMODEL id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv; vkeyed_kernels.hpp): again the layout of the
-// call they resolve in front of; behind its requests the vmodel key bytes, the n + 1 key offsets, the notFoundModelId bytes (each
-// byte region with kKeyedPad readable bytes behind it), their n + 1 offsets and the n flag words; behind its results the n
-// mmp_vseam_row.  kKeyBytes / kNfBytes: what a call may bring onto a slot of each — what vkeyed_resolve_kernel stages in LDS of each.
-constexpr int kVKeyedKeyBytes = kVKeyedLdsBytes, kVKeyedNfBytes = kVKeyedLdsBytes;
-static_assert(sizeof(mmp_vseam_row) == 24, "mmp_vseam_row is 24 bytes");
-struct VKeyedPlaceSlot {
-    static constexpr int kN = kKeyedN, kExtra = MissSlot::kPool, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
-    static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_place_req)), keys = slot_after(reqs, kKeyBytes + kKeyedPad, 1),
-                                key_off = slot_after(keys, kN + 1, 4), nf = slot_after(key_off, kNfBytes + kKeyedPad, 1),
-                                nf_off = slot_after(nf, kN + 1, 4), flags = slot_after(nf_off, kN, 4),
-                                extra = slot_first(kSlotPool, kExtra, 4), outs = slot_first(kSlotOut, kN, sizeof(mmp_place_out)),
-                                vm = slot_after(outs, kN, sizeof(mmp_vseam_row));
-    static_assert(slot_fits({reqs, keys, key_off, nf, nf_off, flags, extra, outs, vm}), "vmodel-keyed place slot layout");
-};
-struct VKeyedMissSlot {
-    using L = MissSlot;
-    static constexpr int kN = kKeyedN, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
-    static constexpr SlotRegion keys = slot_after(L::greqs, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
-                                nf = slot_after(key_off, kNfBytes + kKeyedPad, 1), nf_off = slot_after(nf, kN + 1, 4),
-                                flags = slot_after(nf_off, kN, 4), vm = slot_after(L::gouts, kN, sizeof(mmp_vseam_row));
-    static_assert(kN <= L::kN && slot_fits({L::preqs, L::greqs, keys, key_off, nf, nf_off, flags, L::extra, L::excl_pod, L::explicit_pool,
-                                            L::excl_time, L::pouts, L::gouts, vm}),
-                  "vmodel-keyed miss slot layout");
-};
-struct VKeyedRouteSlot {
-    using L = RouteSlot;
-    static constexpr int kN = kKeyedN, kKeyBytes = kVKeyedKeyBytes, kNfBytes = kVKeyedNfBytes;
-    static constexpr SlotRegion keys = slot_after(L::counters, kKeyBytes + kKeyedPad, 1), key_off = slot_after(keys, kN + 1, 4),
-                                nf = slot_after(key_off, kNfBytes + kKeyedPad, 1), nf_off = slot_after(nf, kN + 1, 4),
-                                flags = slot_after(nf_off, kN, 4), vm = slot_after(L::souts, kN, sizeof(mmp_vseam_row));
-    static_assert(kN <= L::kN && slot_fits({L::greqs, L::sreqs, L::counters, keys, key_off, nf, nf_off, flags, L::excl_pod, L::explicit_pool,
-                                            L::excl_time, L::gouts, L::souts, vm}),
-                  "vmodel-keyed route slot layout");
-};
+// every region where it has always been: the byte offsets of keys, key_off, (nf, nf_off, flags,) idx / vm
+template <class T>
+constexpr bool key_tail_at(size_t keys, size_t key_off, size_t idx)
+{
+    return T::keys.off == keys && T::key_off.off == key_off && T::idx.off == idx;
+}
+template <class T>
+constexpr bool vkey_tail_at(size_t keys, size_t key_off, size_t nf, size_t nf_off, size_t flags, size_t vm)
+{
+    return T::keys.off == keys && T::key_off.off == key_off && T::nf.off == nf && T::nf_off.off == nf_off && T::flags.off == flags && T::vm.off == vm;
+}
+static_assert(key_tail_at<KeyedPlaceSlot<KeyTail>::T>(16384, 32784, 4096), "keyed place slot offsets");
+static_assert(key_tail_at<KeyedMissSlot<KeyTail>::T>(53248, 69648, 6144), "keyed miss slot offsets");
+static_assert(key_tail_at<KeyedRouteSlot<KeyTail>::T>(114688, 131088, 6144), "keyed route slot offsets");
+static_assert(vkey_tail_at<KeyedPlaceSlot<VKeyTail>::T>(16384, 24592, 25632, 33840, 34880, 4096), "vmodel-keyed place slot offsets");
+static_assert(vkey_tail_at<KeyedMissSlot<VKeyTail>::T>(53248, 61456, 62496, 70704, 71744, 6144), "vmodel-keyed miss slot offsets");
+static_assert(vkey_tail_at<KeyedRouteSlot<VKeyTail>::T>(114688, 122896, 123936, 132144, 133184, 6144), "vmodel-keyed route slot offsets");
 struct EvictSlot {  // mmp_evict_batch: as many 32-byte result rows as the result buffer holds (2048); their 16-byte requests fit
     static constexpr int kN = (int)(kSlotBufBytes[kSlotOut] / sizeof(mmp_evict_out));
     static constexpr SlotRegion reqs = slot_first(kSlotReq, kN, sizeof(mmp_evict_req)), outs = slot_first(kSlotOut, kN, sizeof(mmp_evict_out));
@@ -1194,6 +1198,11 @@ inline int check_serve_req(mmp_ctx *c, const char *call, int32_t i, const mmp_se
     if (!in_pool(r.cnt_off, r.n_cnt, n_counters)) return bad_range(c, call, i, "counter", r.cnt_off, r.n_cnt, n_counters);
     return MMP_OK;
 }
+// (the compact serve row: its exclusion range IS the gate row's)
+inline int check_serve_req(mmp_ctx *c, const char *call, int32_t i, const mmp_serve_req_c &r, int32_t, int32_t n_counters)
+{
+    return in_pool(r.cnt_off, r.n_cnt, n_counters) ? MMP_OK : bad_range(c, call, i, "counter", r.cnt_off, r.n_cnt, n_counters);
+}
 // the two halves of one request (mmp_miss_batch, mmp_route_batch) name one model
 inline int check_same_model(mmp_ctx *c, const char *call, int32_t i, int32_t gate_model, int32_t other_model)
 {
@@ -1290,6 +1299,24 @@ SeamIo seam_io(const T *host, int32_t count, const SlotRegion &at)
 {
     return SeamIo{const_cast<T *>(host), (size_t)count * sizeof(T), at, nullptr};
 }
+// The input or the output arrays of a call, as seam_run takes them: a braced list, or a fixed-size array a caller put together
+// (seam_list: a seam's own arrays with a resolver's behind them).  It is a view: the list lives as long as the call's expression.
+struct SeamSpan {
+    SeamIo *const *first;
+    size_t count;
+    SeamSpan(std::initializer_list<SeamIo *> l) : first(l.begin()), count(l.size()) {}
+    template <size_t N>
+    SeamSpan(const std::array<SeamIo *, N> &a) : first(a.data()), count(N) {}
+    SeamIo *const *begin() const { return first; }
+    SeamIo *const *end() const { return first + count; }
+};
+template <size_t N, class... Io>
+std::array<SeamIo *, sizeof...(Io) + N> seam_list(const std::array<SeamIo *, N> &behind, Io *...own)
+{
+    std::array<SeamIo *, sizeof...(Io) + N> a{own...};
+    for (size_t i = 0; i < N; i++) a[sizeof...(Io) + i] = behind[i];
+    return a;
+}
 inline void *slot_ptr(FastSlot *f, const SlotRegion &r)
 {
     char *base = r.buf == kSlotReq ? reinterpret_cast<char *>(f->reqs) : r.buf == kSlotPool ? reinterpret_cast<char *>(f->extra) : reinterpret_cast<char *>(f->outs);
@@ -1307,8 +1334,7 @@ inline void *slot_ptr(FastSlot *f, const SlotRegion &r)
 // fallback) and never hides a kernel in flight.  Inlined into each entry point: the array lists are unrolled and the regions' addresses
 // folded there.
 template <class Check, class Launch>
-__attribute__((always_inline)) inline int seam_slot(mmp_ctx *c, std::initializer_list<SeamIo *> ins, std::initializer_list<SeamIo *> outs,
-                                                    Check &check, Launch &launch)
+__attribute__((always_inline)) inline int seam_slot(mmp_ctx *c, SeamSpan ins, SeamSpan outs, Check &check, Launch &launch)
 {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     std::unique_lock<std::mutex> fl;
@@ -1334,8 +1360,7 @@ __attribute__((always_inline)) inline int seam_slot(mmp_ctx *c, std::initializer
 // (kLaunchExcl; they answer n == 0 themselves), which hold it exclusive over their check and place_launch.  Kernel time (KT_*)
 // brackets the launches alone, not the copies.
 template <bool kLaunchExcl, class Check, class Launch>
-__attribute__((noinline)) int seam_staged(mmp_ctx *c, int32_t n, std::initializer_list<SeamIo *> ins, std::initializer_list<SeamIo *> outs,
-                                          Check &check, Launch &launch)
+__attribute__((noinline)) int seam_staged(mmp_ctx *c, int32_t n, SeamSpan ins, SeamSpan outs, Check &check, Launch &launch)
 {
     std::lock_guard<std::mutex> gb(c->batch_mu);
     if constexpr (!kLaunchExcl)
@@ -1367,8 +1392,8 @@ __attribute__((noinline)) int seam_staged(mmp_ctx *c, int32_t n, std::initialize
 }
 
 template <bool kLaunchExcl, class Check, class Launch>
-__attribute__((always_inline)) inline int seam_run(mmp_ctx *c, int32_t n, bool rides_slot, std::initializer_list<SeamIo *> ins,
-                                                   std::initializer_list<SeamIo *> outs, Check &&check, Launch &&launch)
+__attribute__((always_inline)) inline int seam_run(mmp_ctx *c, int32_t n, bool rides_slot, SeamSpan ins, SeamSpan outs, Check &&check,
+                                                   Launch &&launch)
 {
     return rides_slot ? seam_slot(c, ins, outs, check, launch) : seam_staged<kLaunchExcl>(c, n, ins, outs, check, launch);
 }
@@ -6122,51 +6147,580 @@ try {
 
 int mmp_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
                     int64_t now, mmp_place_out *outs);
+int mmp_miss_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_place_req *preqs, int32_t n, const int32_t *excl_pod,
+                   const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool,
+                   int32_t n_extra, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts);
+int mmp_route_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_serve_req *sreqs, int32_t n, const mmp_serve_counter *counters,
+                    int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl,
+                    const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts,
+                    mmp_serve_out *souts);
+
+// ---- the per-request seams: load target (place), cache hit (route), cache miss (miss) -----------------------------------------
+// Each seam has a form on full rows (mmp_place_batch / _route_batch / _miss_batch), a single-caller form on compact rows (_c:
+// include/mmplace.h: THE RULE; kernels: seam_caller_kernels.hpp) and the single-caller form with the model named by model id (_ck:
+// THE RULE BY KEY; keyed_kernels.hpp) or by vmodel id (_cv: THE RULE BY VMODEL KEY; vkeyed_kernels.hpp).  What all of them share is
+// stated here once: the argument test, the binding of the kernels' argument blocks, the rows written out, the staged launch bodies.
+// How a call's model gets named is a RESOLVER (NoResolver, ByModelId, ByVModelId below): the keyed seams are one body each
+// (keyed_place / keyed_route / keyed_miss) with the resolver as a parameter.
+extern "C++" {
+namespace {
+// the guards' pools as every route and miss call brings them
+struct GatePools {
+    const int32_t *excl_pod;
+    const int64_t *excl_time;
+    int32_t n_excl;
+    const int32_t *explicit_pool;
+    int32_t n_explicit;
+    bool bad() const { return n_excl < 0 || n_explicit < 0 || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool); }
+};
+
+// The argument test of each seam, `fn` the call the host made: NULL / negative arguments, then the pool ranges in request order, the
+// gate row's before the other half's.  has_callers: the caller rows the form takes are there.  same_model: the two halves carry a
+// model each and must agree (not by id: there both take the resolved row).
+template <class Req>
+__attribute__((always_inline)) inline int check_place_call(mmp_ctx *c, const char *fn, bool has_callers, const Req *reqs, int32_t n,
+                                                           const int32_t *extra_pool, int32_t n_extra, const mmp_place_out *outs)
+{
+    if (!c || !has_callers || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++)
+        if (const int rc = check_place_req(c, fn, i, reqs[i], n_extra)) return rc;
+    return MMP_OK;
+}
+template <class GReq, class SReq>
+__attribute__((always_inline)) inline int check_route_call(mmp_ctx *c, const char *fn, bool has_callers, const GReq *greqs, const SReq *sreqs,
+                                                           int32_t n, const mmp_serve_counter *counters, int32_t n_counters,
+                                                           const GatePools &P, const mmp_gate_out *gouts, const mmp_serve_out *souts)
+{
+    if (!c || !has_callers || n < 0 || n_counters < 0 || P.bad() || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
+        (n_counters > 0 && !counters))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], P.n_excl, P.n_explicit)) return rc;
+        if (const int rc = check_serve_req(c, fn, i, sreqs[i], P.n_excl, n_counters)) return rc;
+        if constexpr (std::is_same_v<SReq, mmp_serve_req>)  // (the compact serve row has no model of its own)
+            if (const int rc = check_same_model(c, fn, i, greqs[i].model, sreqs[i].model)) return rc;
+    }
+    return MMP_OK;
+}
+template <class GReq, class PReq>
+__attribute__((always_inline)) inline int check_miss_call(mmp_ctx *c, const char *fn, bool has_callers, bool same_model, const GReq *greqs,
+                                                          const PReq *preqs, int32_t n, const GatePools &P, const int32_t *extra_pool,
+                                                          int32_t n_extra, const mmp_gate_out *gouts, const mmp_place_out *pouts)
+{
+    if (!c || !has_callers || n < 0 || n_extra < 0 || P.bad() || (n > 0 && (!greqs || !preqs || !gouts || !pouts)) ||
+        (n_extra > 0 && !extra_pool))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {
+        if (const int rc = check_gate_req(c, fn, i, greqs[i], P.n_excl, P.n_explicit)) return rc;
+        if (const int rc = check_place_req(c, fn, i, preqs[i], n_extra)) return rc;
+        if (same_model)
+            if (const int rc = check_same_model(c, fn, i, greqs[i].model, preqs[i].model)) return rc;
+    }
+    return MMP_OK;
+}
+// the counts within which the route and the miss ride a slot
+inline bool route_slot_sized(int32_t n, int32_t n_counters, const GatePools &P)
+{
+    using L = RouteSlot;
+    return n <= L::kN && n_counters <= L::kCounters && P.n_excl <= L::kExcl && P.n_explicit <= L::kExplicit;
+}
+inline bool miss_slot_sized(int32_t n, int32_t n_extra, const GatePools &P)
+{
+    using L = MissSlot;
+    return n <= L::kN && n_extra <= L::kPool && P.n_excl <= L::kPool && P.n_explicit <= L::kPool;
+}
+
+// The guards' arrays of a call (all but the request rows): the pools and the results, on the regions of layout L when the call
+// rides a slot, staged through the scratch mmp_gate_batch stages them through.
+struct GateIo {
+    SeamIo xp, xt, ex, go;
+};
+struct StagedRows {  // the layout of a call that never rides a slot
+    static constexpr SlotRegion excl_pod = kStagedOnly, excl_time = kStagedOnly, explicit_pool = kStagedOnly, gouts = kStagedOnly;
+};
+template <class L>
+GateIo gate_io(mmp_ctx *c, const GatePools &P, mmp_gate_out *gouts, int32_t n)
+{
+    return GateIo{seam_io(P.excl_pod, P.n_excl, L::excl_pod, c->s_c), seam_io(P.excl_time, P.n_excl, L::excl_time, c->s_d),
+                  seam_io(P.explicit_pool, P.n_explicit, L::explicit_pool, c->s_a), seam_io(gouts, n, L::gouts, c->s_outs)};
+}
+// The guards' argument block bound to them (inside a launch body: SeamIo::dev is set).  full_rows: the mmp_gate_req rows, or null
+// where the kernel reads compact rows (SeamCArgs).  `done` is the completion flag where the guards' kernel is the call's last.
+constexpr DoneFlag kNoDone{nullptr, nullptr, 0};
+GateArgs gate_args(mmp_ctx *c, int32_t n, int64_t now, int64_t in_use_expiry, const GateIo &g, const SeamIo *full_rows, const DoneFlag &done)
+{
+    GateArgs G = gate_args(c, n, now, in_use_expiry);
+    G.reqs = full_rows ? full_rows->as<mmp_gate_req>() : nullptr;
+    G.excl_pod = g.xp.as<int32_t>();
+    G.excl_time = g.xt.as<int64_t>();
+    G.explicit_pool = g.ex.as<int32_t>();
+    G.outs = g.go.as<mmp_gate_out>();
+    G.done = done;
+    return G;
+}
+// the serve half beside them: it shares the guards' exclusion pairs
+ServeArgs serve_args(mmp_ctx *c, int32_t n, int64_t now, const GateArgs &G, const SeamIo *full_rows, const SeamIo &cnt, const SeamIo &so)
+{
+    ServeArgs S = serve_args(c, n, now);
+    S.reqs = full_rows ? full_rows->as<mmp_serve_req>() : nullptr;
+    S.counters = cnt.as<mmp_serve_counter>();
+    S.excl_pod = G.excl_pod;
+    S.excl_time = G.excl_time;
+    S.outs = so.as<mmp_serve_out>();
+    return S;
+}
+
+// Compact rows written out in full (the header's rule; gate and serve rows: expand_gate / expand_serve, seam_caller_kernels.hpp —
+// one statement for host and device).  unnamed: with model = -1, for a resolver to name on the device.
+mmp_place_req full_place_row(const mmp_place_caller &c, const mmp_place_req_c &q)
+{
+    mmp_place_req r;
+    r.model = q.model;
+    r.self_pod = c.self_pod;
+    r.flags = c.flags;
+    r.pick = q.pick;
+    r.last_used = q.last_used;
+    r.extra_off = q.extra_off;
+    r.n_extra = q.n_extra;
+    r.fresh_lru = c.fresh_lru;
+    r.fresh_capacity = c.fresh_capacity;
+    r.fresh_used = c.fresh_used;
+    r.fresh_count = c.fresh_count;
+    r.fresh_rpm = c.fresh_rpm;
+    return r;
+}
+std::vector<mmp_place_req> full_place_rows(const mmp_place_caller &caller, const mmp_place_req_c *reqs, int32_t n, bool unnamed)
+{
+    std::vector<mmp_place_req> full((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        full[(size_t)i] = full_place_row(caller, reqs[i]);
+        if (unnamed) full[(size_t)i].model = -1;
+    }
+    return full;
+}
+std::vector<mmp_gate_req> full_gate_rows(const mmp_seam_caller &caller, const mmp_gate_req_c *greqs, int32_t n, bool unnamed)
+{
+    std::vector<mmp_gate_req> full((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        full[(size_t)i] = expand_gate(caller, greqs[i]);
+        if (unnamed) full[(size_t)i].model = -1;
+    }
+    return full;
+}
+std::vector<mmp_serve_req> full_serve_rows(const mmp_seam_caller &caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
+                                           bool unnamed)
+{
+    std::vector<mmp_serve_req> full((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        full[(size_t)i] = expand_serve(caller, greqs[i], sreqs[i]);
+        if (unnamed) full[(size_t)i].model = -1;
+    }
+    return full;
+}
+
+// The launches behind the registry's writes that more than one seam makes.
+int launch_gate(mmp_ctx *c, hipStream_t st, const GateArgs &G, int32_t n)
+{
+    HIP_TRY(c, order_after_registry(c, st));
+    hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+int launch_route(mmp_ctx *c, hipStream_t st, const GateArgs &G, const ServeArgs &S, int32_t n)
+{
+    HIP_TRY(c, order_after_registry(c, st));
+    hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+// on the compact rows: gq the mmp_gate_req_c, sq the mmp_serve_req_c
+SeamCArgs seam_c_args(const mmp_seam_caller &caller, const SeamIo &gq, const SeamIo *sq, int32_t n)
+{
+    SeamCArgs R;
+    R.greqs = gq.as<mmp_gate_req_c>();
+    R.sreqs = sq ? sq->as<mmp_serve_req_c>() : nullptr;
+    R.n = n;
+    R.caller = caller;
+    return R;
+}
+int launch_gate_c(mmp_ctx *c, hipStream_t st, const GateArgs &G, const mmp_seam_caller &caller, const SeamIo &gq, int32_t n)
+{
+    HIP_TRY(c, order_after_registry(c, st));
+    hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, seam_c_args(caller, gq, nullptr, n));
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+int launch_route_c(mmp_ctx *c, hipStream_t st, const GateArgs &G, const ServeArgs &S, const mmp_seam_caller &caller, const SeamIo &gq,
+                   const SeamIo &sq, int32_t n)
+{
+    HIP_TRY(c, order_after_registry(c, st));
+    hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S, seam_c_args(caller, gq, &sq, n));
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
+}
+int place_launch_c(mmp_ctx *c, const mmp_place_caller *caller, const SeamIo &q, const SeamIo &x, const SeamIo &o, int32_t n, int64_t now,
+                   hipStream_t st)
+{
+    PlaceCall call;
+    call.caller = caller;
+    return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
+}
+
+// ---- the resolvers ---------------------------------------------------------------------------------------------------------------
+// What a call by id has beyond the call it resolves in front of.  The id is resolved on the device inside the call: the resolver's
+// kernel is enqueued in front of the unchanged decision kernels on the same stream and writes each request's row into the call's
+// OWN copy of the request rows (its slot region, or its staged scratch: a KeyedPatch each), so the call waits once.  On a slot the
+// state lock is held shared over the guard, the capture of the published tables and every enqueue (seam_slot), and batch_mu is
+// never taken: the ownership rules at mmp_ctx::mid_hash and ::vid_hash are what make that capture safe.  Beyond the slot sizes the
+// call is staged under batch_mu like every large call, on the compact rows.
+//   check(c, fn, n)       what the call refuses in its own arguments, after the ranges: keys, then nf, then flag bits
+//   fits<T>()             its byte counts are within tail T's kKeyBytes / kNfBytes
+//   bind<At>(c, n, slot)  its arrays as SeamIos, on the regions of At (a tail of the layout table, or StagedTail)
+//   ins() / outs()        those arrays, for seam_list
+//   state(c, fn)          the state the call needs, looked at under the lock it launches under
+//   launch(c, st, n, a, b) its one kernel, naming the model in up to two arrays of rows
+constexpr KeyedPatch kNoPatch{nullptr, 0, 0};
+template <class Row>  // the `model` field of an array of Row as the call holds it
+KeyedPatch keyed_patch_of(const SeamIo &rows)
+{
+    return KeyedPatch{rows.as<char>(), (int32_t)sizeof(Row), (int32_t)offsetof(Row, model)};
+}
+struct StagedTail {
+    static constexpr SlotRegion keys = kStagedOnly, key_off = kStagedOnly, nf = kStagedOnly, nf_off = kStagedOnly, flags = kStagedOnly,
+                                idx = kStagedOnly, vm = kStagedOnly;
+};
+// The rows name their model themselves (the _c forms): nothing in front.
+struct NoResolver {
+    template <class At>
+    void bind(mmp_ctx *, int32_t, bool) {}
+    std::array<SeamIo *, 0> ins() { return {}; }
+    std::array<SeamIo *, 0> outs() { return {}; }
+    int state(mmp_ctx *c, const char *) const { return need_snapshot(c, true); }
+    int launch(mmp_ctx *, hipStream_t, int32_t, const KeyedPatch &, const KeyedPatch &) const { return MMP_OK; }
+};
+int keyed_state(mmp_ctx *c, const char *fn)
+{
+    if (const int rc = need_snapshot(c, true)) return rc;
+    return model_id_space_guard(c, fn);
+}
+int keyed_empty(mmp_ctx *c, const char *fn)  // n == 0: answered from the state
+{
+    std::shared_lock<std::shared_mutex> g(c->mu);
+    return keyed_state(c, fn);
+}
+// n byte spans (`what`: "key " / "nf ") as n + 1 offsets into `bytes`: the offsets, the 2^31 bound, the bytes being there
+int check_spans(mmp_ctx *c, const char *fn, const char *what, const char *bytes, const int32_t *off, int32_t n, int32_t &n_bytes)
+{
+    if (const int rc = check_offsets(c, fn, what, off, n)) return rc;
+    const int64_t b = (int64_t)off[n] - off[0];
+    if (b > INT32_MAX - kKeyedPad) return fail(c, MMP_EINVAL, "%s: more than 2^31 %sbytes", fn, what);
+    if (b > 0 && !bytes) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    n_bytes = (int32_t)b;
+    return MMP_OK;
+}
+// n byte spans of a call as the resolving kernels take them: the bytes and their n + 1 offsets as the caller gave them.  On a slot
+// the bytes are copied as they are (the layouts leave kKeyedPad bytes behind them); staged, from a copy that carries the padding.
+struct KeyedSpans {
+    std::vector<char> padded;
+    SeamIo kb, ko;
+    void bind(const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, bool on_slot, const SlotRegion &keys_at,
+              const SlotRegion &off_at, DevBuf &bytes_stage, DevBuf &off_stage)
+    {
+        const char *first = key_bytes > 0 ? keys + key_off[0] : nullptr;
+        if (!on_slot) {
+            padded.assign((size_t)key_bytes + kKeyedPad, 0);
+            if (key_bytes > 0) memcpy(padded.data(), first, (size_t)key_bytes);
+            kb = seam_io(padded.data(), key_bytes + kKeyedPad, keys_at, bytes_stage);
+        } else
+            kb = seam_io(first, key_bytes, keys_at, bytes_stage);
+        ko = seam_io(key_off, n + 1, off_at, off_stage);
+    }
+};
+// The keys of a call by id (model ids and vmodel ids alike) as the call brings them: checked, and carried through kq_keys / kq_off.
+struct KeyArg {
+    const char *keys;
+    const int32_t *key_off;
+    int32_t bytes = 0;
+    KeyedSpans io;
+    int check(mmp_ctx *c, const char *fn, int32_t n)
+    {
+        if (n == 0) return MMP_OK;
+        if (!key_off) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+        return check_spans(c, fn, "key ", keys, key_off, n, bytes);
+    }
+    template <class At>
+    void bind(mmp_ctx *c, int32_t n, bool on_slot)
+    {
+        io.bind(keys, key_off, n, bytes, on_slot, At::keys, At::key_off, c->kq_keys, c->kq_off);
+    }
+};
+// By model id: the key bytes and their offsets in, the resolved rows out.  A NULL model_idx_out gets a sink: the kernel writes the
+// rows either way.
+struct ByModelId {
+    template <const SlotRegion &req_end, const SlotRegion &out_end>
+    using Tail = KeyTail<req_end, out_end>;
+    KeyArg key;  // (the call's arguments)
+    int32_t *model_idx_out;
+    std::vector<int32_t> sink;
+    SeamIo ix;
+    int check(mmp_ctx *c, const char *fn, int32_t n) { return key.check(c, fn, n); }
+    template <class T>
+    bool fits() const { return key.bytes <= T::kKeyBytes; }
+    template <class At>
+    void bind(mmp_ctx *c, int32_t n, bool on_slot)
+    {
+        key.template bind<At>(c, n, on_slot);
+        if (!model_idx_out) {
+            sink.resize((size_t)n);
+            model_idx_out = sink.data();
+        }
+        ix = seam_io(model_idx_out, n, At::idx, c->kq_idx);
+    }
+    std::array<SeamIo *, 2> ins() { return {&key.io.kb, &key.io.ko}; }
+    std::array<SeamIo *, 1> outs() { return {&ix}; }
+    int state(mmp_ctx *c, const char *fn) const { return keyed_state(c, fn); }
+    // (called with the state lock held, or by the owner of batch_mu under which no writer of the id table runs)
+    int launch(mmp_ctx *c, hipStream_t st, int32_t n, const KeyedPatch &a, const KeyedPatch &b) const
+    {
+        KeyedArgs A;
+        A.keys = key.io.kb.as<char>();
+        A.off = key.io.ko.as<int32_t>();
+        A.n = n;
+        A.hmask = hash_mask(c->tune.model_id_hash_bits);
+        A.tab = model_id_tab(c).published();
+        A.model_idx = ix.as<int32_t>();
+        A.a = a;
+        A.b = b;
+        hipLaunchKernelGGL(keyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+        HIP_TRY(c, hipGetLastError());
+        return MMP_OK;
+    }
+};
+// By vmodel id: resolveVModelId and the lookup of the id it returns.  Beyond the model-id form it takes the notFoundModelId spans and
+// the flags in and gives an mmp_vseam_row per request.  The kernel takes all of them, so what the caller left out is supplied here: no
+// nf is n + 1 equal offsets, no flags n zero words, a NULL vm_out a sink.
+struct ByVModelId {
+    template <const SlotRegion &req_end, const SlotRegion &out_end>
+    using Tail = VKeyTail<req_end, out_end>;
+    KeyArg key;  // (the call's arguments)
+    const char *nf_keys;
+    const int32_t *nf_off;
+    const uint32_t *req_flags;
+    mmp_vseam_row *vm_out;
+    int32_t nf_bytes = 0;
+    std::vector<int32_t> no_nf;
+    std::vector<uint32_t> no_flags;
+    std::vector<mmp_vseam_row> sink;
+    KeyedSpans nf;
+    SeamIo fl, vo;
+    int check(mmp_ctx *c, const char *fn, int32_t n)
+    {
+        if (const int rc = key.check(c, fn, n)) return rc;
+        if (n > 0 && nf_off)
+            if (const int rc = check_spans(c, fn, "nf ", nf_keys, nf_off, n, nf_bytes)) return rc;
+        if (req_flags)
+            for (int32_t i = 0; i < n; i++)
+                if (req_flags[i] & ~MMP_VMRQ_AFTER_STRONG) return fail(c, MMP_EINVAL, "%s: request %d has unknown flag bits", fn, i);
+        return MMP_OK;
+    }
+    template <class T>
+    bool fits() const { return key.bytes <= T::kKeyBytes && nf_bytes <= T::kNfBytes; }
+    template <class At>
+    void bind(mmp_ctx *c, int32_t n, bool on_slot)
+    {
+        key.template bind<At>(c, n, on_slot);
+        if (!nf_off) {
+            no_nf.assign((size_t)n + 1, 0);
+            nf_off = no_nf.data();
+        }
+        nf.bind(nf_keys, nf_off, n, nf_bytes, on_slot, At::nf, At::nf_off, c->vq_nf, c->vq_nf_off);
+        if (!req_flags) {
+            no_flags.assign((size_t)n, 0u);
+            req_flags = no_flags.data();
+        }
+        fl = seam_io(req_flags, n, At::flags, c->vq_flags);
+        if (!vm_out) {
+            sink.resize((size_t)n);
+            vm_out = sink.data();
+        }
+        vo = seam_io(vm_out, n, At::vm, c->vq_out);
+    }
+    std::array<SeamIo *, 5> ins() { return {&key.io.kb, &key.io.ko, &nf.kb, &nf.ko, &fl}; }
+    std::array<SeamIo *, 1> outs() { return {&vo}; }
+    int state(mmp_ctx *c, const char *fn) const { return keyed_state(c, fn); }
+    // (called with the state lock held, or by the owner of batch_mu under which no writer of either table runs)
+    int launch(mmp_ctx *c, hipStream_t st, int32_t n, const KeyedPatch &a, const KeyedPatch &b) const
+    {
+        VKeyedArgs A;
+        A.keys = key.io.kb.as<char>();
+        A.off = key.io.ko.as<int32_t>();
+        A.nf = nf.kb.as<char>();
+        A.nf_off = nf.ko.as<int32_t>();
+        A.flags = fl.as<uint32_t>();
+        A.n = n;
+        A.hmask = hash_mask(c->tune.vmodel_id_hash_bits);
+        A.V = vmodel_tab(c);
+        A.models = model_id_tab(c).published();
+        A.n_models = c->n_models;
+        A.out = vo.as<mmp_vseam_row>();
+        A.a = a;
+        A.b = b;
+        hipLaunchKernelGGL(vkeyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+        HIP_TRY(c, hipGetLastError());
+        return MMP_OK;
+    }
+};
+
+// ---- the seams on the compact rows, resolver K in front ----------------------------------------------------------------------------
+// The staged load target and the staged route: what mmp_place_batch_c / mmp_route_batch_c do beyond the slot sizes (NoResolver) and
+// what the forms by id do there.  The arrays stage through the scratch of the row forms: the calls never overlap, batch_mu owns it
+// for a call.
+template <class R>
+int place_c_staged(mmp_ctx *c, const char *fn, R &K, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n,
+                   const int32_t *extra_pool, int32_t n_extra, int64_t now, mmp_place_out *outs)
+{
+    K.template bind<StagedTail>(c, n, false);
+    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs), x = seam_io(extra_pool, n_extra, kStagedOnly, c->s_extra),
+           o = seam_io(outs, n, kStagedOnly, c->s_outs);
+    return seam_run<true>(c, n, false, seam_list(K.ins(), &q, &x), seam_list(K.outs(), &o), [&] { return K.state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &, auto) {
+                        if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_place_req_c>(q), kNoPatch)) return rc;
+                        return place_launch_c(c, caller, q, x, o, n, now, st);
+                    });
+}
+template <class R>
+int route_c_staged(mmp_ctx *c, const char *fn, R &K, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs,
+                   int32_t n, const mmp_serve_counter *counters, int32_t n_counters, const GatePools &P, int64_t now, int64_t in_use_expiry,
+                   mmp_gate_out *gouts, mmp_serve_out *souts)
+{
+    K.template bind<StagedTail>(c, n, false);
+    GateIo g = gate_io<StagedRows>(c, P, gouts, n);
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs),
+           cnt = seam_io(counters, n_counters, kStagedOnly, c->rt_cnt), so = seam_io(souts, n, kStagedOnly, c->rt_souts);
+    return seam_run<false>(c, n, false, seam_list(K.ins(), &gq, &sq, &cnt, &g.xp, &g.xt, &g.ex), seam_list(K.outs(), &g.go, &so),
+                    [&] { return K.state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate_args(c, n, now, in_use_expiry, g, nullptr, done);
+                        const ServeArgs S = serve_args(c, n, now, G, nullptr, cnt, so);
+                        // (the compact serve row has no model of its own: the serve half reads the gate row's)
+                        if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_gate_req_c>(gq), kNoPatch)) return rc;
+                        return launch_route_c(c, st, G, S, *caller, gq, sq, n);
+                    });
+}
+
+// The three seams by id.  Within the slot sizes: the rows written out in full with model = -1, as the _c forms write them out, the
+// resolver's launch, then the ROW kernels — a lone request takes them too, its model is not known at launch.  Beyond: staged on the
+// compact rows.  Inlined into their entry points, one instance each.
+template <class R>
+__attribute__((always_inline)) inline int keyed_place(mmp_ctx *c, const char *fn, R &K, const mmp_place_caller *caller,
+                                                      const mmp_place_req_c *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
+                                                      int64_t now, mmp_place_out *outs)
+{
+    if (const int rc = check_place_call(c, fn, caller != nullptr, reqs, n, extra_pool, n_extra, outs)) return rc;
+    if (const int rc = K.check(c, fn, n)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using L = KeyedPlaceSlot<R::template Tail>;
+    if (!(n <= L::kN && n_extra <= L::kExtra && K.template fits<typename L::T>()))
+        return place_c_staged(c, fn, K, caller, reqs, n, extra_pool, n_extra, now, outs);
+    K.template bind<typename L::T>(c, n, true);
+    const std::vector<mmp_place_req> full = full_place_rows(*caller, reqs, n, true);
+    SeamIo q = seam_io(full.data(), n, L::reqs), x = seam_io(extra_pool, n_extra, L::extra), o = seam_io(outs, n, L::outs);
+    return seam_run<true>(c, n, true, seam_list(K.ins(), &q, &x), seam_list(K.outs(), &o), [&] { return K.state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_place_req>(q), kNoPatch)) return rc;
+                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, nullptr));
+                    });
+}
+template <class R>
+__attribute__((always_inline)) inline int keyed_route(mmp_ctx *c, const char *fn, R &K, const mmp_seam_caller *caller,
+                                                      const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
+                                                      const mmp_serve_counter *counters, int32_t n_counters, const GatePools &P, int64_t now,
+                                                      int64_t in_use_expiry, mmp_gate_out *gouts, mmp_serve_out *souts)
+{
+    if (const int rc = check_route_call(c, fn, caller != nullptr, greqs, sreqs, n, counters, n_counters, P, gouts, souts)) return rc;
+    if (const int rc = K.check(c, fn, n)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using KL = KeyedRouteSlot<R::template Tail>;
+    using L = RouteSlot;
+    if (!(n <= KL::kN && route_slot_sized(n, n_counters, P) && K.template fits<typename KL::T>()))
+        return route_c_staged(c, fn, K, caller, greqs, sreqs, n, counters, n_counters, P, now, in_use_expiry, gouts, souts);
+    K.template bind<typename KL::T>(c, n, true);
+    const std::vector<mmp_gate_req> fg = full_gate_rows(*caller, greqs, n, true);
+    const std::vector<mmp_serve_req> fs = full_serve_rows(*caller, greqs, sreqs, n, true);
+    GateIo g = gate_io<L>(c, P, gouts, n);
+    SeamIo gq = seam_io(fg.data(), n, L::greqs), sq = seam_io(fs.data(), n, L::sreqs), cnt = seam_io(counters, n_counters, L::counters),
+           so = seam_io(souts, n, L::souts);
+    return seam_run<false>(c, n, true, seam_list(K.ins(), &gq, &sq, &cnt, &g.xp, &g.xt, &g.ex), seam_list(K.outs(), &g.go, &so),
+                    [&] { return K.state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate_args(c, n, now, in_use_expiry, g, &gq, done);
+                        const ServeArgs S = serve_args(c, n, now, G, &sq, cnt, so);
+                        if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_serve_req>(sq))) return rc;
+                        return launch_route(c, st, G, S, n);
+                    });
+}
+// The miss: on a slot THREE launches on its stream (the resolver, the guards, the load targets: the last one's completion flag covers
+// all), one wait; beyond, both halves staged in ONE hold of batch_mu (one resolution names both halves' rows), the load-target half
+// through buffers of its own (kq_preqs, kq_pouts).
+template <class R>
+__attribute__((always_inline)) inline int keyed_miss(mmp_ctx *c, const char *fn, R &K, const mmp_seam_caller *caller,
+                                                     const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs, const mmp_place_req_c *preqs,
+                                                     int32_t n, const GatePools &P, const int32_t *extra_pool, int32_t n_extra, int64_t now,
+                                                     int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts)
+{
+    if (const int rc = check_miss_call(c, fn, caller && pcaller, false, greqs, preqs, n, P, extra_pool, n_extra, gouts, pouts)) return rc;
+    if (const int rc = K.check(c, fn, n)) return rc;
+    if (n == 0) return keyed_empty(c, fn);
+    using KL = KeyedMissSlot<R::template Tail>;
+    using L = MissSlot;
+    GateIo g = gate_io<L>(c, P, gouts, n);
+    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), po = seam_io(pouts, n, L::pouts, c->kq_pouts);
+    if (n <= KL::kN && miss_slot_sized(n, n_extra, P) && K.template fits<typename KL::T>()) {
+        K.template bind<typename KL::T>(c, n, true);
+        const std::vector<mmp_gate_req> fg = full_gate_rows(*caller, greqs, n, true);
+        const std::vector<mmp_place_req> fp = full_place_rows(*pcaller, preqs, n, true);
+        SeamIo pq = seam_io(fp.data(), n, L::preqs), gq = seam_io(fg.data(), n, L::greqs);
+        return seam_run<true>(c, n, true, seam_list(K.ins(), &pq, &gq, &x, &g.xp, &g.xt, &g.ex), seam_list(K.outs(), &po, &g.go),
+                        [&] { return K.state(c, fn); },
+                        [&](hipStream_t st, const DoneFlag &done, auto) {
+                            const GateArgs G = gate_args(c, n, now, in_use_expiry, g, &gq, kNoDone);
+                            if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_place_req>(pq))) return rc;
+                            if (const int rc = launch_gate(c, st, G, n)) return rc;
+                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
+                        });
+    }
+    K.template bind<StagedTail>(c, n, false);
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), pq = seam_io(preqs, n, kStagedOnly, c->kq_preqs);
+    return seam_run<true>(c, n, false, seam_list(K.ins(), &pq, &gq, &x, &g.xp, &g.xt, &g.ex), seam_list(K.outs(), &po, &g.go),
+                    [&] { return K.state(c, fn); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate_args(c, n, now, in_use_expiry, g, nullptr, done);
+                        if (const int rc = K.launch(c, st, n, keyed_patch_of<mmp_gate_req_c>(gq), keyed_patch_of<mmp_place_req_c>(pq))) return rc;
+                        if (const int rc = launch_gate_c(c, st, G, *caller, gq, n)) return rc;
+                        return place_launch_c(c, pcaller, pq, x, po, n, now, st);
+                    });
+}
+}  // namespace
+}  // extern "C++"
+
 int mmp_place_batch_c(mmp_ctx *c, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const int32_t *extra_pool,
                       int32_t n_extra, int64_t now, mmp_place_out *outs)
 try {
-    if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "mmp_place_batch_c: bad argument");
-    for (int32_t i = 0; i < n; i++)
-        if (const int rc = check_place_req(c, "mmp_place_batch_c", i, reqs[i], n_extra)) return rc;
-    if (n <= PlaceSlot::kN && n_extra <= PlaceSlot::kExtra) {
-        // a handful of requests: the latency path of mmp_place_batch (slots, the single-decision kernels, the resident kernel) on
-        // the same decisions written out as mmp_place_req rows
-        std::vector<mmp_place_req> full((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            mmp_place_req &r = full[(size_t)i];
-            r.model = reqs[i].model;
-            r.self_pod = caller->self_pod;
-            r.flags = caller->flags;
-            r.pick = reqs[i].pick;
-            r.last_used = reqs[i].last_used;
-            r.extra_off = reqs[i].extra_off;
-            r.n_extra = reqs[i].n_extra;
-            r.fresh_lru = caller->fresh_lru;
-            r.fresh_capacity = caller->fresh_capacity;
-            r.fresh_used = caller->fresh_used;
-            r.fresh_count = caller->fresh_count;
-            r.fresh_rpm = caller->fresh_rpm;
-        }
-        return mmp_place_batch(c, full.data(), n, extra_pool, n_extra, now, outs);
-    }
-    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs), x = seam_io(extra_pool, n_extra, kStagedOnly, c->s_extra),
-           o = seam_io(outs, n, kStagedOnly, c->s_outs);
-    return seam_run<true>(c, n, false, {&q, &x}, {&o}, [&] { return need_snapshot(c, true); },
-                    [&](hipStream_t st, const DoneFlag &, auto) {
-                        PlaceCall call;
-                        call.caller = caller;
-                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
-                    });
+    const char *fn = "mmp_place_batch_c";
+    if (const int rc = check_place_call(c, fn, caller != nullptr, reqs, n, extra_pool, n_extra, outs)) return rc;
+    // a handful of requests: the latency path of mmp_place_batch (slots, the single-decision kernels, the resident kernel) on the same
+    // decisions written out as mmp_place_req rows
+    if (n <= PlaceSlot::kN && n_extra <= PlaceSlot::kExtra)
+        return mmp_place_batch(c, full_place_rows(*caller, reqs, n, false).data(), n, extra_pool, n_extra, now, outs);
+    NoResolver K;
+    return place_c_staged(c, fn, K, caller, reqs, n, extra_pool, n_extra, now, outs);
 } MMP_CATCH(c, "mmp_place_batch_c")
 
 int mmp_place_batch(mmp_ctx *c, const mmp_place_req *reqs, int32_t n, const int32_t *extra_pool, int32_t n_extra,
                     int64_t now, mmp_place_out *outs)
 try {
-    if (!c || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "mmp_place_batch: bad argument");
-    for (int32_t i = 0; i < n; i++)
-        if (const int rc = check_place_req(c, "mmp_place_batch", i, reqs[i], n_extra)) return rc;
+    if (const int rc = check_place_call(c, "mmp_place_batch", true, reqs, n, extra_pool, n_extra, outs)) return rc;
     if (n == 0) {
         std::lock_guard<std::shared_mutex> g(c->mu);
         return need_snapshot(c, true);
@@ -6221,29 +6775,17 @@ int mmp_gate_batch(mmp_ctx *c, const mmp_gate_req *reqs, int32_t n, const int32_
                    int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
                    mmp_gate_out *outs)
 try {
-    if (!c || n < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!reqs || !outs)) ||
-        (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
-        return fail(c, MMP_EINVAL, "mmp_gate_batch: bad argument");
+    const GatePools P{excl_pod, excl_time, n_excl, explicit_pool, n_explicit};
+    if (!c || n < 0 || P.bad() || (n > 0 && (!reqs || !outs))) return fail(c, MMP_EINVAL, "mmp_gate_batch: bad argument");
     for (int32_t i = 0; i < n; i++)
         if (const int rc = check_gate_req(c, "mmp_gate_batch", i, reqs[i], n_excl, n_explicit)) return rc;
     using L = GateSlot;
-    SeamIo q = seam_io(reqs, n, L::reqs, c->s_reqs), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           o = seam_io(outs, n, L::outs, c->s_outs);
-    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_excl <= L::kExcl && n_explicit <= L::kExplicit, {&q, &xp, &xt, &ex}, {&o},
+    GateIo g = gate_io<L>(c, P, outs, n);
+    SeamIo q = seam_io(reqs, n, L::reqs, c->s_reqs);
+    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_excl <= L::kExcl && n_explicit <= L::kExplicit, {&q, &g.xp, &g.xt, &g.ex}, {&g.go},
                     [&] { return need_snapshot(c, false); },
-                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
-                        GateArgs A = gate_args(c, n, now, in_use_expiry);
-                        A.reqs = q.as<mmp_gate_req>();
-                        A.excl_pod = xp.as<int32_t>();
-                        A.excl_time = xt.as<int64_t>();
-                        A.explicit_pool = ex.as<int32_t>();
-                        A.outs = o.as<mmp_gate_out>();
-                        A.done = done;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-                        HIP_TRY(c, hipGetLastError());
-                        return MMP_OK;
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        return launch_gate(c, st, gate_args(c, n, now, in_use_expiry, g, &q, done), n);
                     });
 } MMP_CATCH(c, "mmp_gate_batch")
 
@@ -6251,43 +6793,30 @@ int mmp_miss_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_place_req *p
                    const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool,
                    int32_t n_extra, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts)
 try {
-    if (!c || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 || (n > 0 && (!greqs || !preqs || !gouts || !pouts)) ||
-        (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "mmp_miss_batch: bad argument");
-    for (int32_t i = 0; i < n; i++) {
-        if (const int rc = check_gate_req(c, "mmp_miss_batch", i, greqs[i], n_excl, n_explicit)) return rc;
-        if (const int rc = check_place_req(c, "mmp_miss_batch", i, preqs[i], n_extra)) return rc;
-        if (const int rc = check_same_model(c, "mmp_miss_batch", i, greqs[i].model, preqs[i].model)) return rc;
-    }
+    const GatePools P{excl_pod, excl_time, n_excl, explicit_pool, n_explicit};
+    if (const int rc = check_miss_call(c, "mmp_miss_batch", true, true, greqs, preqs, n, P, extra_pool, n_extra, gouts, pouts)) return rc;
     if (n == 0) return MMP_OK;
     using L = MissSlot;
-    if (n > L::kN || n_extra > L::kPool || n_excl > L::kPool || n_explicit > L::kPool) {  // large batches: the two calls
+    if (!miss_slot_sized(n, n_extra, P)) {  // large batches: the two calls
         const int rc = mmp_gate_batch(c, greqs, n, excl_pod, excl_time, n_excl, explicit_pool, n_explicit, now, in_use_expiry, gouts);
         return rc != MMP_OK ? rc : mmp_place_batch(c, preqs, n, extra_pool, n_extra, now, pouts);
     }
     // One latency slot, TWO launches on its stream (the guards, then the load targets: in stream order, so the second kernel's
     // completion flag covers both), ONE wait: what two calls did in two launch-wait-return round trips.  Always on a slot: the staged
     // path is the two calls above.
+    GateIo g = gate_io<L>(c, P, gouts, n);
     SeamIo pq = seam_io(preqs, n, L::preqs), gq = seam_io(greqs, n, L::greqs), x = seam_io(extra_pool, n_extra, L::extra),
-           xp = seam_io(excl_pod, n_excl, L::excl_pod), xt = seam_io(excl_time, n_excl, L::excl_time),
-           ex = seam_io(explicit_pool, n_explicit, L::explicit_pool), po = seam_io(pouts, n, L::pouts), go = seam_io(gouts, n, L::gouts);
-    return seam_run<false>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex}, {&po, &go}, [&] { return need_snapshot(c, true); },
-                    [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
-                        GateArgs G = gate_args(c, n, now, in_use_expiry);
-                        G.reqs = gq.as<mmp_gate_req>();
-                        G.excl_pod = xp.as<int32_t>();
-                        G.excl_time = xt.as<int64_t>();
-                        G.explicit_pool = ex.as<int32_t>();
-                        G.outs = go.as<mmp_gate_out>();
+           po = seam_io(pouts, n, L::pouts);
+    return seam_run<false>(c, n, true, {&pq, &gq, &x, &g.xp, &g.xt, &g.ex}, {&po, &g.go}, [&] { return need_snapshot(c, true); },
+                    [&](hipStream_t st, const DoneFlag &done, auto) {
+                        const GateArgs G = gate_args(c, n, now, in_use_expiry, g, &gq, kNoDone);
                         if (n == 1 && preqs[0].n_extra == 0) {  // ONE launch: both requests in the kernel arguments, guards and load target on two wavefronts
                             PlaceCall call = slot_call(done, &preqs[0]);
                             call.fused_gate = &G;
                             call.fused_greq = &greqs[0];
                             return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
                         }
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
-                        HIP_TRY(c, hipGetLastError());
+                        if (const int rc = launch_gate(c, st, G, n)) return rc;
                         return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
                     });
 } MMP_CATCH(c, "mmp_miss_batch")
@@ -6298,131 +6827,47 @@ int mmp_route_batch(mmp_ctx *c, const mmp_gate_req *greqs, const mmp_serve_req *
                     const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts,
                     mmp_serve_out *souts)
 try {
-    if (!c || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
-        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
-        return fail(c, MMP_EINVAL, "mmp_route_batch: bad argument");
-    for (int32_t i = 0; i < n; i++) {
-        if (const int rc = check_gate_req(c, "mmp_route_batch", i, greqs[i], n_excl, n_explicit)) return rc;
-        if (const int rc = check_serve_req(c, "mmp_route_batch", i, sreqs[i], n_excl, n_counters)) return rc;
-        if (const int rc = check_same_model(c, "mmp_route_batch", i, greqs[i].model, sreqs[i].model)) return rc;
-    }
+    const GatePools P{excl_pod, excl_time, n_excl, explicit_pool, n_explicit};
+    if (const int rc = check_route_call(c, "mmp_route_batch", true, greqs, sreqs, n, counters, n_counters, P, gouts, souts)) return rc;
     using L = RouteSlot;
     // (staged, the gate half takes the scratch mmp_gate_batch takes, the serve half buffers of its own)
+    GateIo g = gate_io<L>(c, P, gouts, n);
     SeamIo gq = seam_io(greqs, n, L::greqs, c->s_reqs), sq = seam_io(sreqs, n, L::sreqs, c->rt_sreqs),
-           cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
-    return seam_run<false>(c, n, n > 0 && n <= L::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit,
-                    {&gq, &sq, &cnt, &xp, &xt, &ex}, {&go, &so}, [&] { return need_snapshot(c, true); },
+           cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), so = seam_io(souts, n, L::souts, c->rt_souts);
+    return seam_run<false>(c, n, n > 0 && route_slot_sized(n, n_counters, P), {&gq, &sq, &cnt, &g.xp, &g.xt, &g.ex}, {&g.go, &so},
+                    [&] { return need_snapshot(c, true); },
                     [&](hipStream_t st, const DoneFlag &done, auto on_slot) {
-                        GateArgs G = gate_args(c, n, now, in_use_expiry);
-                        G.reqs = gq.as<mmp_gate_req>();
-                        G.excl_pod = xp.as<int32_t>();
-                        G.excl_time = xt.as<int64_t>();
-                        G.explicit_pool = ex.as<int32_t>();
-                        G.outs = go.as<mmp_gate_out>();
-                        G.done = done;
-                        ServeArgs S = serve_args(c, n, now);
-                        S.reqs = sq.as<mmp_serve_req>();
-                        S.counters = cnt.as<mmp_serve_counter>();
-                        S.excl_pod = G.excl_pod;
-                        S.excl_time = G.excl_time;
-                        S.outs = so.as<mmp_serve_out>();
+                        const GateArgs G = gate_args(c, n, now, in_use_expiry, g, &gq, done);
+                        const ServeArgs S = serve_args(c, n, now, G, &sq, cnt, so);
+                        if (!(on_slot && n == 1 && n_counters <= kRouteInlineCnt && sreqs[0].n_cnt <= kRouteInlineCnt))
+                            return launch_route(c, st, G, S, n);
+                        // ONE route on a slot: the requests ride in the kernel arguments
+                        RouteInline R{};
+                        R.g = greqs[0];
+                        R.s = sreqs[0];
+                        for (int32_t j = 0; j < sreqs[0].n_cnt; j++) R.cnt[j] = counters[sreqs[0].cnt_off + j];
                         HIP_TRY(c, order_after_registry(c, st));
-                        if (on_slot && n == 1 && n_counters <= kRouteInlineCnt && sreqs[0].n_cnt <= kRouteInlineCnt) {
-                            // ONE route on a slot: the requests ride in the kernel arguments
-                            RouteInline R{};
-                            R.g = greqs[0];
-                            R.s = sreqs[0];
-                            for (int32_t j = 0; j < sreqs[0].n_cnt; j++) R.cnt[j] = counters[sreqs[0].cnt_off + j];
-                            hipLaunchKernelGGL(route_single_kernel, dim3(1), dim3(128), 0, st, G, S, R);
-                        } else
-                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
+                        hipLaunchKernelGGL(route_single_kernel, dim3(1), dim3(128), 0, st, G, S, R);
                         HIP_TRY(c, hipGetLastError());
                         return MMP_OK;
                     });
 } MMP_CATCH(c, "mmp_route_batch")
 
-// ---- the single-caller forms of the two routes (include/mmplace.h: THE RULE; kernels: seam_caller_kernels.hpp) ----------------
-namespace {
-// (the gate and serve rows of the header's rule: expand_gate / expand_serve, seam_caller_kernels.hpp — one statement for host and device)
-mmp_place_req full_place_row(const mmp_place_caller &c, const mmp_place_req_c &q)
-{
-    mmp_place_req r;
-    r.model = q.model;
-    r.self_pod = c.self_pod;
-    r.flags = c.flags;
-    r.pick = q.pick;
-    r.last_used = q.last_used;
-    r.extra_off = q.extra_off;
-    r.n_extra = q.n_extra;
-    r.fresh_lru = c.fresh_lru;
-    r.fresh_capacity = c.fresh_capacity;
-    r.fresh_used = c.fresh_used;
-    r.fresh_count = c.fresh_count;
-    r.fresh_rpm = c.fresh_rpm;
-    return r;
-}
-SeamCArgs seam_c_args(const mmp_seam_caller &caller, const SeamIo &gq, const SeamIo *sq, int32_t n)
-{
-    SeamCArgs R;
-    R.greqs = gq.as<mmp_gate_req_c>();
-    R.sreqs = sq ? sq->as<mmp_serve_req_c>() : nullptr;
-    R.n = n;
-    R.caller = caller;
-    return R;
-}
-}  // namespace
-
+// ---- the single-caller forms of the two routes: within the slot sizes the row forms on the rows written out ---------------------
 int mmp_route_batch_c(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
                       const mmp_serve_counter *counters, int32_t n_counters, const int32_t *excl_pod, const int64_t *excl_time,
                       int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
                       mmp_gate_out *gouts, mmp_serve_out *souts)
 try {
-    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
-        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
-        return fail(c, MMP_EINVAL, "mmp_route_batch_c: bad argument");
-    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges: the serve row's exclusion range IS the gate row's
-        if (const int rc = check_gate_req(c, "mmp_route_batch_c", i, greqs[i], n_excl, n_explicit)) return rc;
-        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
-            return bad_range(c, "mmp_route_batch_c", i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
-    }
-    using L = RouteSlot;
-    if (n <= L::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit) {
-        // within the latency slots' sizes (and n = 0): mmp_route_batch — its slots, its n = 1 kernel — on the rows written out
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_serve_req> fs((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
-        }
-        return mmp_route_batch(c, n ? fg.data() : nullptr, n ? fs.data() : nullptr, n, counters, n_counters, excl_pod, excl_time, n_excl,
-                               explicit_pool, n_explicit, now, in_use_expiry, gouts, souts);
-    }
-    // (the scratch mmp_route_batch stages through: the two calls never overlap, batch_mu owns it for a call)
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs),
-           cnt = seam_io(counters, n_counters, kStagedOnly, c->rt_cnt), xp = seam_io(excl_pod, n_excl, kStagedOnly, c->s_c),
-           xt = seam_io(excl_time, n_excl, kStagedOnly, c->s_d), ex = seam_io(explicit_pool, n_explicit, kStagedOnly, c->s_a),
-           go = seam_io(gouts, n, kStagedOnly, c->s_outs), so = seam_io(souts, n, kStagedOnly, c->rt_souts);
-    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex}, {&go, &so}, [&] { return need_snapshot(c, true); },
-                    [&](hipStream_t st, const DoneFlag &done, auto) {
-                        GateArgs G = gate_args(c, n, now, in_use_expiry);
-                        G.excl_pod = xp.as<int32_t>();
-                        G.excl_time = xt.as<int64_t>();
-                        G.explicit_pool = ex.as<int32_t>();
-                        G.outs = go.as<mmp_gate_out>();
-                        G.done = done;
-                        ServeArgs S = serve_args(c, n, now);
-                        S.counters = cnt.as<mmp_serve_counter>();
-                        S.excl_pod = G.excl_pod;
-                        S.excl_time = G.excl_time;
-                        S.outs = so.as<mmp_serve_out>();
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
-                                           seam_c_args(*caller, gq, &sq, n));
-                        HIP_TRY(c, hipGetLastError());
-                        return MMP_OK;
-                    });
+    const char *fn = "mmp_route_batch_c";
+    const GatePools P{excl_pod, excl_time, n_excl, explicit_pool, n_explicit};
+    if (const int rc = check_route_call(c, fn, caller != nullptr, greqs, sreqs, n, counters, n_counters, P, gouts, souts)) return rc;
+    // within the latency slots' sizes (and n = 0): mmp_route_batch — its slots, its n = 1 kernel — on the rows written out
+    if (route_slot_sized(n, n_counters, P))
+        return mmp_route_batch(c, full_gate_rows(*caller, greqs, n, false).data(), full_serve_rows(*caller, greqs, sreqs, n, false).data(), n,
+                               counters, n_counters, excl_pod, excl_time, n_excl, explicit_pool, n_explicit, now, in_use_expiry, gouts, souts);
+    NoResolver K;
+    return route_c_staged(c, fn, K, caller, greqs, sreqs, n, counters, n_counters, P, now, in_use_expiry, gouts, souts);
 } MMP_CATCH(c, "mmp_route_batch_c")
 
 int mmp_miss_batch_c(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
@@ -6430,45 +6875,20 @@ int mmp_miss_batch_c(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_
                      const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now,
                      int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts)
 try {
-    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
-        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
-        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "mmp_miss_batch_c: bad argument");
-    for (int32_t i = 0; i < n; i++) {
-        if (const int rc = check_gate_req(c, "mmp_miss_batch_c", i, greqs[i], n_excl, n_explicit)) return rc;
-        if (const int rc = check_place_req(c, "mmp_miss_batch_c", i, preqs[i], n_extra)) return rc;
-        if (const int rc = check_same_model(c, "mmp_miss_batch_c", i, greqs[i].model, preqs[i].model)) return rc;
-    }
-    using L = MissSlot;
-    if (n <= L::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool) {
-        // within the latency slot's sizes (and n = 0): mmp_miss_batch on the rows written out
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_place_req> fp((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
-        }
-        return mmp_miss_batch(c, n ? fg.data() : nullptr, n ? fp.data() : nullptr, n, excl_pod, excl_time, n_excl, explicit_pool,
-                              n_explicit, extra_pool, n_extra, now, in_use_expiry, gouts, pouts);
-    }
+    const char *fn = "mmp_miss_batch_c";
+    const GatePools P{excl_pod, excl_time, n_excl, explicit_pool, n_explicit};
+    if (const int rc = check_miss_call(c, fn, caller && pcaller, true, greqs, preqs, n, P, extra_pool, n_extra, gouts, pouts)) return rc;
+    // within the latency slot's sizes (and n = 0): mmp_miss_batch on the rows written out
+    if (miss_slot_sized(n, n_extra, P))
+        return mmp_miss_batch(c, full_gate_rows(*caller, greqs, n, false).data(), full_place_rows(*pcaller, preqs, n, false).data(), n,
+                              excl_pod, excl_time, n_excl, explicit_pool, n_explicit, extra_pool, n_extra, now, in_use_expiry, gouts, pouts);
     // a large batch is two calls, as mmp_miss_batch's is: the guards on the compact rows, then the load targets where
     // mmp_place_batch_c has them
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), xp = seam_io(excl_pod, n_excl, kStagedOnly, c->s_c),
-           xt = seam_io(excl_time, n_excl, kStagedOnly, c->s_d), ex = seam_io(explicit_pool, n_explicit, kStagedOnly, c->s_a),
-           go = seam_io(gouts, n, kStagedOnly, c->s_outs);
-    const int rc = seam_run<false>(c, n, false, {&gq, &xp, &xt, &ex}, {&go}, [&] { return need_snapshot(c, true); },
+    GateIo g = gate_io<StagedRows>(c, P, gouts, n);
+    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs);
+    const int rc = seam_run<false>(c, n, false, {&gq, &g.xp, &g.xt, &g.ex}, {&g.go}, [&] { return need_snapshot(c, true); },
                     [&](hipStream_t st, const DoneFlag &done, auto) {
-                        GateArgs A = gate_args(c, n, now, in_use_expiry);
-                        A.excl_pod = xp.as<int32_t>();
-                        A.excl_time = xt.as<int64_t>();
-                        A.explicit_pool = ex.as<int32_t>();
-                        A.outs = go.as<mmp_gate_out>();
-                        A.done = done;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, A,
-                                           seam_c_args(*caller, gq, nullptr, n));
-                        HIP_TRY(c, hipGetLastError());
-                        return MMP_OK;
+                        return launch_gate_c(c, st, gate_args(c, n, now, in_use_expiry, g, nullptr, done), *caller, gq, n);
                     });
     if (rc != MMP_OK) return rc;
     // (profiling: the call's device span is the sum of its two brackets; a load-target half that rides a slot leaves none.
@@ -6486,131 +6906,13 @@ try {
     return rc2;
 } MMP_CATCH(c, "mmp_miss_batch_c")
 
-// ---- the request calls by model id (include/mmplace.h: THE RULE BY KEY; kernel: keyed_kernels.hpp) ------------------------------
-// The key is resolved on the device inside the call: keyed_resolve_kernel is enqueued in front of the unchanged decision kernels on
-// the same stream and writes each request's row into the call's OWN copy of the request rows (its slot region, or its staged
-// scratch), so the call waits once.  On a slot the state lock is held shared over the guard, the capture of the published id table
-// and both enqueues (seam_slot), and batch_mu is never taken: the ownership rule at mmp_ctx::mid_hash is what makes that capture
-// safe.  Beyond the slot sizes the call is staged under batch_mu like every large call, on the compact rows.
-namespace {
-int keyed_check_keys(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, int32_t n, int32_t &key_bytes)
-{
-    key_bytes = 0;
-    if (n == 0) return MMP_OK;
-    if (!key_off) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
-    const int64_t bytes = (int64_t)key_off[n] - key_off[0];
-    if (bytes > INT32_MAX - kKeyedPad) return fail(c, MMP_EINVAL, "%s: more than 2^31 key bytes", fn);
-    if (bytes > 0 && !keys) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    key_bytes = (int32_t)bytes;
-    return MMP_OK;
-}
-// the state the three calls need, looked at under the lock they launch under
-int keyed_state(mmp_ctx *c, const char *fn)
-{
-    if (const int rc = need_snapshot(c, true)) return rc;
-    return model_id_space_guard(c, fn);
-}
-int keyed_empty(mmp_ctx *c, const char *fn)  // n == 0
-{
-    std::shared_lock<std::shared_mutex> g(c->mu);
-    return keyed_state(c, fn);
-}
-// n byte spans of a call as the resolving kernels take them: the bytes and their n + 1 offsets as the caller gave them.  On a slot
-// the bytes are copied as they are (the layouts leave kKeyedPad bytes behind them); staged, from a copy that carries the padding.
-struct KeyedSpans {
-    std::vector<char> padded;
-    SeamIo kb, ko;
-    void bind(const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, bool on_slot, const SlotRegion &keys_at,
-              const SlotRegion &off_at, DevBuf &bytes_stage, DevBuf &off_stage)
-    {
-        const char *first = key_bytes > 0 ? keys + key_off[0] : nullptr;
-        if (!on_slot) {
-            padded.assign((size_t)key_bytes + kKeyedPad, 0);
-            if (key_bytes > 0) memcpy(padded.data(), first, (size_t)key_bytes);
-            kb = seam_io(padded.data(), key_bytes + kKeyedPad, keys_at, bytes_stage);
-        } else
-            kb = seam_io(first, key_bytes, keys_at, bytes_stage);
-        ko = seam_io(key_off, n + 1, off_at, off_stage);
-    }
-};
-// The three arrays a keyed call adds to the call it resolves in front of: the key bytes, their offsets, and the resolved rows.  A
-// NULL model_idx_out gets a sink: the kernel writes the rows either way.
-struct KeyedIo : KeyedSpans {
-    std::vector<int32_t> sink;
-    SeamIo ix;
-    KeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t n, int32_t key_bytes, int32_t *model_idx_out, bool on_slot,
-            const SlotRegion &keys_at, const SlotRegion &off_at, const SlotRegion &idx_at)
-    {
-        bind(keys, key_off, n, key_bytes, on_slot, keys_at, off_at, c->kq_keys, c->kq_off);
-        if (!model_idx_out) {
-            sink.resize((size_t)n);
-            model_idx_out = sink.data();
-        }
-        ix = seam_io(model_idx_out, n, idx_at, c->kq_idx);
-    }
-};
-extern "C++" template <class Row>  // the `model` field of an array of Row as the call holds it
-KeyedPatch keyed_patch_of(const SeamIo &rows)
-{
-    return KeyedPatch{rows.as<char>(), (int32_t)sizeof(Row), (int32_t)offsetof(Row, model)};
-}
-// (called with the state lock held, or by the owner of batch_mu under which no writer of the id table runs)
-int keyed_launch(mmp_ctx *c, hipStream_t st, const KeyedIo &K, int32_t n, const KeyedPatch &a, const KeyedPatch &b)
-{
-    KeyedArgs A;
-    A.keys = K.kb.as<char>();
-    A.off = K.ko.as<int32_t>();
-    A.n = n;
-    A.hmask = hash_mask(c->tune.model_id_hash_bits);
-    A.tab = model_id_tab(c).published();
-    A.model_idx = K.ix.as<int32_t>();
-    A.a = a;
-    A.b = b;
-    hipLaunchKernelGGL(keyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
-    HIP_TRY(c, hipGetLastError());
-    return MMP_OK;
-}
-constexpr KeyedPatch kNoPatch{nullptr, 0, 0};
-}  // namespace
-
+// ---- the request calls by model id and by vmodel id: an argument pack and the seam (keyed_place / keyed_route / keyed_miss) -----
 int mmp_place_batch_ck(mmp_ctx *c, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
                        const int32_t *key_off, const int32_t *extra_pool, int32_t n_extra, int64_t now, mmp_place_out *outs,
                        int32_t *model_idx_out)
 try {
-    const char *fn = "mmp_place_batch_ck";
-    if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++)
-        if (const int rc = check_place_req(c, fn, i, reqs[i], n_extra)) return rc;
-    int32_t key_bytes;
-    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = KeyedPlaceSlot;
-    const bool on_slot = n <= L::kN && n_extra <= L::kExtra && key_bytes <= L::kKeyBytes;
-    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, L::keys, L::key_off, L::idx);
-    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), o = seam_io(outs, n, L::outs, c->s_outs);
-    if (on_slot) {  // the rows written out in full, as mmp_place_batch_c does; a lone request takes the row path too (its model is not known at launch)
-        std::vector<mmp_place_req> full((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            full[(size_t)i] = full_place_row(*caller, reqs[i]);
-            full[(size_t)i].model = -1;
-        }
-        SeamIo q = seam_io(full.data(), n, L::reqs);
-        return seam_run<true>(c, n, true, {&q, &x, &K.kb, &K.ko}, {&o, &K.ix}, [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req>(q), kNoPatch)) return rc;
-                            return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, nullptr));
-                        });
-    }
-    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs);
-    return seam_run<true>(c, n, false, {&q, &x, &K.kb, &K.ko}, {&o, &K.ix}, [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &, auto) {
-                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req_c>(q), kNoPatch)) return rc;
-                        PlaceCall call;
-                        call.caller = caller;
-                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
-                    });
+    ByModelId K{{keys, key_off}, model_idx_out};
+    return keyed_place(c, "mmp_place_batch_ck", K, caller, reqs, n, extra_pool, n_extra, now, outs);
 } MMP_CATCH(c, "mmp_place_batch_ck")
 
 int mmp_route_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
@@ -6618,73 +6920,9 @@ int mmp_route_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate
                        const int32_t *excl_pod, const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit,
                        int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_serve_out *souts, int32_t *model_idx_out)
 try {
-    const char *fn = "mmp_route_batch_ck";
-    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
-        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges, as mmp_route_batch_c checks them
-        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
-        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
-            return bad_range(c, fn, i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
-    }
-    int32_t key_bytes;
-    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = RouteSlot;
-    using KL = KeyedRouteSlot;
-    const bool on_slot = n <= KL::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit && key_bytes <= KL::kKeyBytes;
-    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, KL::keys, KL::key_off, KL::idx);
-    SeamIo cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
-    auto bind = [&](GateArgs &G, ServeArgs &S, const DoneFlag &done) {
-        G.excl_pod = xp.as<int32_t>();
-        G.excl_time = xt.as<int64_t>();
-        G.explicit_pool = ex.as<int32_t>();
-        G.outs = go.as<mmp_gate_out>();
-        G.done = done;
-        S.counters = cnt.as<mmp_serve_counter>();
-        S.excl_pod = G.excl_pod;
-        S.excl_time = G.excl_time;
-        S.outs = so.as<mmp_serve_out>();
-    };
-    if (on_slot) {  // the rows written out in full, as mmp_route_batch_c does; one route takes the row kernel too
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_serve_req> fs((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
-            fg[(size_t)i].model = fs[(size_t)i].model = -1;
-        }
-        SeamIo gq = seam_io(fg.data(), n, L::greqs), sq = seam_io(fs.data(), n, L::sreqs);
-        return seam_run<false>(c, n, true, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.kb, &K.ko}, {&go, &so, &K.ix}, [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            GateArgs G = gate_args(c, n, now, in_use_expiry);
-                            ServeArgs S = serve_args(c, n, now);
-                            bind(G, S, done);
-                            G.reqs = gq.as<mmp_gate_req>();
-                            S.reqs = sq.as<mmp_serve_req>();
-                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_serve_req>(sq))) return rc;
-                            HIP_TRY(c, order_after_registry(c, st));
-                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
-                            HIP_TRY(c, hipGetLastError());
-                            return MMP_OK;
-                        });
-    }
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs);
-    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.kb, &K.ko}, {&go, &so, &K.ix}, [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &done, auto) {
-                        GateArgs G = gate_args(c, n, now, in_use_expiry);
-                        ServeArgs S = serve_args(c, n, now);
-                        bind(G, S, done);
-                        // (the compact serve row has no model of its own: the serve half reads the gate row's)
-                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), kNoPatch)) return rc;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
-                                           seam_c_args(*caller, gq, &sq, n));
-                        HIP_TRY(c, hipGetLastError());
-                        return MMP_OK;
-                    });
+    ByModelId K{{keys, key_off}, model_idx_out};
+    return keyed_route(c, "mmp_route_batch_ck", K, caller, greqs, sreqs, n, counters, n_counters,
+                       GatePools{excl_pod, excl_time, n_excl, explicit_pool, n_explicit}, now, in_use_expiry, gouts, souts);
 } MMP_CATCH(c, "mmp_route_batch_ck")
 
 int mmp_miss_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
@@ -6692,190 +6930,17 @@ int mmp_miss_batch_ck(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place
                       const int64_t *excl_time, int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool,
                       int32_t n_extra, int64_t now, int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts, int32_t *model_idx_out)
 try {
-    const char *fn = "mmp_miss_batch_ck";
-    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
-        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
-        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++) {  // (both halves take the key's row: no "names two models" here)
-        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
-        if (const int rc = check_place_req(c, fn, i, preqs[i], n_extra)) return rc;
-    }
-    int32_t key_bytes;
-    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = MissSlot;
-    using KL = KeyedMissSlot;
-    const bool on_slot = n <= KL::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool && key_bytes <= KL::kKeyBytes;
-    KeyedIo K(c, keys, key_off, n, key_bytes, model_idx_out, on_slot, KL::keys, KL::key_off, KL::idx);
-    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           po = seam_io(pouts, n, L::pouts, c->kq_pouts), go = seam_io(gouts, n, L::gouts, c->s_outs);
-    auto gate = [&](const DoneFlag &done) {
-        GateArgs G = gate_args(c, n, now, in_use_expiry);
-        G.excl_pod = xp.as<int32_t>();
-        G.excl_time = xt.as<int64_t>();
-        G.explicit_pool = ex.as<int32_t>();
-        G.outs = go.as<mmp_gate_out>();
-        G.done = done;
-        return G;
-    };
-    if (on_slot) {
-        // the rows written out in full, as mmp_miss_batch_c does: one slot, THREE launches on its stream (the keys, the guards, the
-        // load targets: the last one's completion flag covers all), one wait.  A lone request takes the row path too.
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_place_req> fp((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
-            fg[(size_t)i].model = fp[(size_t)i].model = -1;
-        }
-        SeamIo pq = seam_io(fp.data(), n, L::preqs), gq = seam_io(fg.data(), n, L::greqs);
-        return seam_run<true>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex, &K.kb, &K.ko}, {&po, &go, &K.ix}, [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            GateArgs G = gate(DoneFlag{nullptr, nullptr, 0});
-                            G.reqs = gq.as<mmp_gate_req>();
-                            if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_place_req>(pq))) return rc;
-                            HIP_TRY(c, order_after_registry(c, st));
-                            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
-                            HIP_TRY(c, hipGetLastError());
-                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
-                        });
-    }
-    // a large batch: both halves staged in ONE hold of batch_mu (one resolution names both halves' rows), on the compact rows
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), pq = seam_io(preqs, n, kStagedOnly, c->kq_preqs);
-    return seam_run<true>(c, n, false, {&pq, &gq, &x, &xp, &xt, &ex, &K.kb, &K.ko}, {&po, &go, &K.ix}, [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &done, auto) {
-                        const GateArgs G = gate(done);
-                        if (const int rc = keyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), keyed_patch_of<mmp_place_req_c>(pq))) return rc;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G,
-                                           seam_c_args(*caller, gq, nullptr, n));
-                        HIP_TRY(c, hipGetLastError());
-                        PlaceCall call;
-                        call.caller = pcaller;
-                        return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
-                    });
+    ByModelId K{{keys, key_off}, model_idx_out};
+    return keyed_miss(c, "mmp_miss_batch_ck", K, caller, pcaller, greqs, preqs, n, GatePools{excl_pod, excl_time, n_excl, explicit_pool, n_explicit},
+                      extra_pool, n_extra, now, in_use_expiry, gouts, pouts);
 } MMP_CATCH(c, "mmp_miss_batch_ck")
-
-// ---- the request calls by vmodel id (include/mmplace.h: THE RULE BY VMODEL KEY; kernel: vkeyed_kernels.hpp) -----------------------
-// The frame of the calls by model id above, with vkeyed_resolve_kernel in the place of keyed_resolve_kernel: resolveVModelId and the
-// lookup of the id it returns happen on the device in front of the unchanged decision kernels, on the same stream.  On a slot the
-// state lock is held shared over the guard, the capture of the published vmodel table, model-id table and registry row count, and
-// every enqueue (seam_slot); batch_mu is never taken: the ownership rules at mmp_ctx::vid_hash and ::mid_hash make that capture safe.
-namespace {
-// The arrays a call by vmodel id adds: the vmodel keys and the notFoundModelId spans (bytes + offsets each), the flags, and the
-// mmp_vseam_row per request.  The kernel takes all of them, so what the caller left out is supplied here: no nf is n + 1 equal
-// offsets, no flags n zero words, a NULL vm_out a sink.
-struct VKeyedIo {
-    std::vector<int32_t> no_nf;
-    std::vector<uint32_t> no_flags;
-    std::vector<mmp_vseam_row> sink;
-    KeyedSpans key, nf;
-    SeamIo fl, vo;
-    VKeyedIo(mmp_ctx *c, const char *keys, const int32_t *key_off, int32_t key_bytes, const char *nf_keys, const int32_t *nf_off,
-             int32_t nf_bytes, const uint32_t *req_flags, int32_t n, mmp_vseam_row *vm_out, bool on_slot, const SlotRegion &keys_at,
-             const SlotRegion &off_at, const SlotRegion &nf_at, const SlotRegion &nf_off_at, const SlotRegion &flags_at, const SlotRegion &vm_at)
-    {
-        key.bind(keys, key_off, n, key_bytes, on_slot, keys_at, off_at, c->kq_keys, c->kq_off);
-        if (!nf_off) {
-            no_nf.assign((size_t)n + 1, 0);
-            nf_off = no_nf.data();
-        }
-        nf.bind(nf_keys, nf_off, n, nf_bytes, on_slot, nf_at, nf_off_at, c->vq_nf, c->vq_nf_off);
-        if (!req_flags) {
-            no_flags.assign((size_t)n, 0u);
-            req_flags = no_flags.data();
-        }
-        fl = seam_io(req_flags, n, flags_at, c->vq_flags);
-        if (!vm_out) {
-            sink.resize((size_t)n);
-            vm_out = sink.data();
-        }
-        vo = seam_io(vm_out, n, vm_at, c->vq_out);
-    }
-};
-// what the _cv forms refuse beyond the _ck forms: the nf spans and the flags
-int vkeyed_check(mmp_ctx *c, const char *fn, const char *keys, const int32_t *key_off, const char *nf_keys, const int32_t *nf_off,
-                 const uint32_t *req_flags, int32_t n, int32_t &key_bytes, int32_t &nf_bytes)
-{
-    nf_bytes = 0;
-    if (const int rc = keyed_check_keys(c, fn, keys, key_off, n, key_bytes)) return rc;
-    if (n > 0 && nf_off) {
-        if (const int rc = check_offsets(c, fn, "nf ", nf_off, n)) return rc;
-        const int64_t bytes = (int64_t)nf_off[n] - nf_off[0];
-        if (bytes > INT32_MAX - kKeyedPad) return fail(c, MMP_EINVAL, "%s: more than 2^31 nf bytes", fn);
-        if (bytes > 0 && !nf_keys) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-        nf_bytes = (int32_t)bytes;
-    }
-    if (req_flags)
-        for (int32_t i = 0; i < n; i++)
-            if (req_flags[i] & ~MMP_VMRQ_AFTER_STRONG) return fail(c, MMP_EINVAL, "%s: request %d has unknown flag bits", fn, i);
-    return MMP_OK;
-}
-// (called with the state lock held, or by the owner of batch_mu under which no writer of either table runs)
-int vkeyed_launch(mmp_ctx *c, hipStream_t st, const VKeyedIo &K, int32_t n, const KeyedPatch &a, const KeyedPatch &b)
-{
-    VKeyedArgs A;
-    A.keys = K.key.kb.as<char>();
-    A.off = K.key.ko.as<int32_t>();
-    A.nf = K.nf.kb.as<char>();
-    A.nf_off = K.nf.ko.as<int32_t>();
-    A.flags = K.fl.as<uint32_t>();
-    A.n = n;
-    A.hmask = hash_mask(c->tune.vmodel_id_hash_bits);
-    A.V = vmodel_tab(c);
-    A.models = model_id_tab(c).published();
-    A.n_models = c->n_models;
-    A.out = K.vo.as<mmp_vseam_row>();
-    A.a = a;
-    A.b = b;
-    hipLaunchKernelGGL(vkeyed_resolve_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
-    HIP_TRY(c, hipGetLastError());
-    return MMP_OK;
-}
-}  // namespace
 
 int mmp_place_batch_cv(mmp_ctx *c, const mmp_place_caller *caller, const mmp_place_req_c *reqs, int32_t n, const char *keys,
                        const int32_t *key_off, const char *nf_keys, const int32_t *nf_off, const uint32_t *req_flags,
                        const int32_t *extra_pool, int32_t n_extra, int64_t now, mmp_place_out *outs, mmp_vseam_row *vm_out)
 try {
-    const char *fn = "mmp_place_batch_cv";
-    if (!c || !caller || n < 0 || n_extra < 0 || (n > 0 && (!reqs || !outs)) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++)
-        if (const int rc = check_place_req(c, fn, i, reqs[i], n_extra)) return rc;
-    int32_t key_bytes, nf_bytes;
-    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = VKeyedPlaceSlot;
-    const bool on_slot = n <= L::kN && n_extra <= L::kExtra && key_bytes <= L::kKeyBytes && nf_bytes <= L::kNfBytes;
-    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, L::keys, L::key_off, L::nf, L::nf_off,
-               L::flags, L::vm);
-    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), o = seam_io(outs, n, L::outs, c->s_outs);
-    if (on_slot) {  // the rows written out in full with model = -1, as mmp_place_batch_ck does; a lone request takes the row path too
-        std::vector<mmp_place_req> full((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            full[(size_t)i] = full_place_row(*caller, reqs[i]);
-            full[(size_t)i].model = -1;
-        }
-        SeamIo q = seam_io(full.data(), n, L::reqs);
-        return seam_run<true>(c, n, true, {&q, &x, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&o, &K.vo},
-                        [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req>(q), kNoPatch)) return rc;
-                            return place_launch(c, q.dev, n, x.dev, now, o.dev, st, slot_call(done, nullptr));
-                        });
-    }
-    SeamIo q = seam_io(reqs, n, kStagedOnly, c->s_reqs);
-    return seam_run<true>(c, n, false, {&q, &x, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&o, &K.vo},
-                    [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &, auto) {
-                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_place_req_c>(q), kNoPatch)) return rc;
-                        PlaceCall call;
-                        call.caller = caller;
-                        return place_launch(c, q.dev, n, x.dev, now, o.dev, st, call);
-                    });
+    ByVModelId K{{keys, key_off}, nf_keys, nf_off, req_flags, vm_out};
+    return keyed_place(c, "mmp_place_batch_cv", K, caller, reqs, n, extra_pool, n_extra, now, outs);
 } MMP_CATCH(c, "mmp_place_batch_cv")
 
 int mmp_route_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate_req_c *greqs, const mmp_serve_req_c *sreqs, int32_t n,
@@ -6884,77 +6949,9 @@ int mmp_route_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_gate
                        int32_t n_excl, const int32_t *explicit_pool, int32_t n_explicit, int64_t now, int64_t in_use_expiry,
                        mmp_gate_out *gouts, mmp_serve_out *souts, mmp_vseam_row *vm_out)
 try {
-    const char *fn = "mmp_route_batch_cv";
-    if (!c || !caller || n < 0 || n_counters < 0 || n_excl < 0 || n_explicit < 0 || (n > 0 && (!greqs || !sreqs || !gouts || !souts)) ||
-        (n_counters > 0 && !counters) || (n_excl > 0 && (!excl_pod || !excl_time)) || (n_explicit > 0 && !explicit_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++) {  // the expanded rows' ranges, as mmp_route_batch_c checks them
-        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
-        if (!in_pool(sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters))
-            return bad_range(c, fn, i, "counter", sreqs[i].cnt_off, sreqs[i].n_cnt, n_counters);
-    }
-    int32_t key_bytes, nf_bytes;
-    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = RouteSlot;
-    using KL = VKeyedRouteSlot;
-    const bool on_slot = n <= KL::kN && n_counters <= L::kCounters && n_excl <= L::kExcl && n_explicit <= L::kExplicit &&
-                         key_bytes <= KL::kKeyBytes && nf_bytes <= KL::kNfBytes;
-    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, KL::keys, KL::key_off, KL::nf,
-               KL::nf_off, KL::flags, KL::vm);
-    SeamIo cnt = seam_io(counters, n_counters, L::counters, c->rt_cnt), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           go = seam_io(gouts, n, L::gouts, c->s_outs), so = seam_io(souts, n, L::souts, c->rt_souts);
-    auto bind = [&](GateArgs &G, ServeArgs &S, const DoneFlag &done) {
-        G.excl_pod = xp.as<int32_t>();
-        G.excl_time = xt.as<int64_t>();
-        G.explicit_pool = ex.as<int32_t>();
-        G.outs = go.as<mmp_gate_out>();
-        G.done = done;
-        S.counters = cnt.as<mmp_serve_counter>();
-        S.excl_pod = G.excl_pod;
-        S.excl_time = G.excl_time;
-        S.outs = so.as<mmp_serve_out>();
-    };
-    if (on_slot) {  // the rows written out in full with model = -1, as mmp_route_batch_ck does; one route takes the row kernel too
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_serve_req> fs((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fs[(size_t)i] = expand_serve(*caller, greqs[i], sreqs[i]);
-            fg[(size_t)i].model = fs[(size_t)i].model = -1;
-        }
-        SeamIo gq = seam_io(fg.data(), n, L::greqs), sq = seam_io(fs.data(), n, L::sreqs);
-        return seam_run<false>(c, n, true, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&go, &so, &K.vo},
-                        [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            GateArgs G = gate_args(c, n, now, in_use_expiry);
-                            ServeArgs S = serve_args(c, n, now);
-                            bind(G, S, done);
-                            G.reqs = gq.as<mmp_gate_req>();
-                            S.reqs = sq.as<mmp_serve_req>();
-                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_serve_req>(sq))) return rc;
-                            HIP_TRY(c, order_after_registry(c, st));
-                            hipLaunchKernelGGL(route_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G, S);
-                            HIP_TRY(c, hipGetLastError());
-                            return MMP_OK;
-                        });
-    }
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), sq = seam_io(sreqs, n, kStagedOnly, c->rt_sreqs);
-    return seam_run<false>(c, n, false, {&gq, &sq, &cnt, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&go, &so, &K.vo},
-                    [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &done, auto) {
-                        GateArgs G = gate_args(c, n, now, in_use_expiry);
-                        ServeArgs S = serve_args(c, n, now);
-                        bind(G, S, done);
-                        // (the compact serve row has no model of its own: the serve half reads the gate row's)
-                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), kNoPatch)) return rc;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(route_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G, S,
-                                           seam_c_args(*caller, gq, &sq, n));
-                        HIP_TRY(c, hipGetLastError());
-                        return MMP_OK;
-                    });
+    ByVModelId K{{keys, key_off}, nf_keys, nf_off, req_flags, vm_out};
+    return keyed_route(c, "mmp_route_batch_cv", K, caller, greqs, sreqs, n, counters, n_counters,
+                       GatePools{excl_pod, excl_time, n_excl, explicit_pool, n_explicit}, now, in_use_expiry, gouts, souts);
 } MMP_CATCH(c, "mmp_route_batch_cv")
 
 int mmp_miss_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place_caller *pcaller, const mmp_gate_req_c *greqs,
@@ -6963,75 +6960,11 @@ int mmp_miss_batch_cv(mmp_ctx *c, const mmp_seam_caller *caller, const mmp_place
                       const int32_t *explicit_pool, int32_t n_explicit, const int32_t *extra_pool, int32_t n_extra, int64_t now,
                       int64_t in_use_expiry, mmp_gate_out *gouts, mmp_place_out *pouts, mmp_vseam_row *vm_out)
 try {
-    const char *fn = "mmp_miss_batch_cv";
-    if (!c || !caller || !pcaller || n < 0 || n_excl < 0 || n_explicit < 0 || n_extra < 0 ||
-        (n > 0 && (!greqs || !preqs || !gouts || !pouts)) || (n_excl > 0 && (!excl_pod || !excl_time)) ||
-        (n_explicit > 0 && !explicit_pool) || (n_extra > 0 && !extra_pool))
-        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
-    for (int32_t i = 0; i < n; i++) {  // (both halves take the row the vmodel resolves to: no "names two models" here)
-        if (const int rc = check_gate_req(c, fn, i, greqs[i], n_excl, n_explicit)) return rc;
-        if (const int rc = check_place_req(c, fn, i, preqs[i], n_extra)) return rc;
-    }
-    int32_t key_bytes, nf_bytes;
-    if (const int rc = vkeyed_check(c, fn, keys, key_off, nf_keys, nf_off, req_flags, n, key_bytes, nf_bytes)) return rc;
-    if (n == 0) return keyed_empty(c, fn);
-    using L = MissSlot;
-    using KL = VKeyedMissSlot;
-    const bool on_slot = n <= KL::kN && n_extra <= L::kPool && n_excl <= L::kPool && n_explicit <= L::kPool && key_bytes <= KL::kKeyBytes &&
-                         nf_bytes <= KL::kNfBytes;
-    VKeyedIo K(c, keys, key_off, key_bytes, nf_keys, nf_off, nf_bytes, req_flags, n, vm_out, on_slot, KL::keys, KL::key_off, KL::nf,
-               KL::nf_off, KL::flags, KL::vm);
-    SeamIo x = seam_io(extra_pool, n_extra, L::extra, c->s_extra), xp = seam_io(excl_pod, n_excl, L::excl_pod, c->s_c),
-           xt = seam_io(excl_time, n_excl, L::excl_time, c->s_d), ex = seam_io(explicit_pool, n_explicit, L::explicit_pool, c->s_a),
-           po = seam_io(pouts, n, L::pouts, c->kq_pouts), go = seam_io(gouts, n, L::gouts, c->s_outs);
-    auto gate = [&](const DoneFlag &done) {
-        GateArgs G = gate_args(c, n, now, in_use_expiry);
-        G.excl_pod = xp.as<int32_t>();
-        G.excl_time = xt.as<int64_t>();
-        G.explicit_pool = ex.as<int32_t>();
-        G.outs = go.as<mmp_gate_out>();
-        G.done = done;
-        return G;
-    };
-    if (on_slot) {
-        // as mmp_miss_batch_ck: one slot, three launches on its stream (the resolution, the guards, the load targets: the last
-        // one's completion flag covers all), one wait.  A lone request takes the row path too.
-        std::vector<mmp_gate_req> fg((size_t)n);
-        std::vector<mmp_place_req> fp((size_t)n);
-        for (int32_t i = 0; i < n; i++) {
-            fg[(size_t)i] = expand_gate(*caller, greqs[i]);
-            fp[(size_t)i] = full_place_row(*pcaller, preqs[i]);
-            fg[(size_t)i].model = fp[(size_t)i].model = -1;
-        }
-        SeamIo pq = seam_io(fp.data(), n, L::preqs), gq = seam_io(fg.data(), n, L::greqs);
-        return seam_run<true>(c, n, true, {&pq, &gq, &x, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&po, &go, &K.vo},
-                        [&] { return keyed_state(c, fn); },
-                        [&](hipStream_t st, const DoneFlag &done, auto) {
-                            GateArgs G = gate(DoneFlag{nullptr, nullptr, 0});
-                            G.reqs = gq.as<mmp_gate_req>();
-                            if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req>(gq), keyed_patch_of<mmp_place_req>(pq))) return rc;
-                            HIP_TRY(c, order_after_registry(c, st));
-                            hipLaunchKernelGGL(gate_batch_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, G);
-                            HIP_TRY(c, hipGetLastError());
-                            return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, slot_call(done, nullptr));
-                        });
-    }
-    // a large batch: both halves staged in ONE hold of batch_mu (one resolution names both halves' rows), on the compact rows
-    SeamIo gq = seam_io(greqs, n, kStagedOnly, c->s_reqs), pq = seam_io(preqs, n, kStagedOnly, c->kq_preqs);
-    return seam_run<true>(c, n, false, {&pq, &gq, &x, &xp, &xt, &ex, &K.key.kb, &K.key.ko, &K.nf.kb, &K.nf.ko, &K.fl}, {&po, &go, &K.vo},
-                    [&] { return keyed_state(c, fn); },
-                    [&](hipStream_t st, const DoneFlag &done, auto) {
-                        const GateArgs G = gate(done);
-                        if (const int rc = vkeyed_launch(c, st, K, n, keyed_patch_of<mmp_gate_req_c>(gq), keyed_patch_of<mmp_place_req_c>(pq))) return rc;
-                        HIP_TRY(c, order_after_registry(c, st));
-                        hipLaunchKernelGGL(gate_batch_c_kernel, dim3(div_up(n, kSeamCBlock)), dim3(kSeamCBlock), 0, st, G,
-                                           seam_c_args(*caller, gq, nullptr, n));
-                        HIP_TRY(c, hipGetLastError());
-                        PlaceCall call;
-                        call.caller = pcaller;
-                        return place_launch(c, pq.dev, n, x.dev, now, po.dev, st, call);
-                    });
+    ByVModelId K{{keys, key_off}, nf_keys, nf_off, req_flags, vm_out};
+    return keyed_miss(c, "mmp_miss_batch_cv", K, caller, pcaller, greqs, preqs, n, GatePools{excl_pod, excl_time, n_excl, explicit_pool, n_explicit},
+                      extra_pool, n_extra, now, in_use_expiry, gouts, pouts);
 } MMP_CATCH(c, "mmp_miss_batch_cv")
+
 
 int mmp_evict_batch(mmp_ctx *c, const mmp_evict_req *reqs, int32_t n, int64_t now, mmp_evict_out *outs)
 try {

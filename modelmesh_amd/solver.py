@@ -857,14 +857,8 @@ class Solver:
 
     def place_c(self, caller, reqs_c, extra_pool: Optional[np.ndarray], now: int) -> np.ndarray:
         """The single-caller form (mmp_place_batch_c): caller = 1 PLACE_CALLER row, reqs_c = PLACE_REQ_C rows."""
-        from ._lib import PLACE_CALLER, PLACE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=PLACE_CALLER).reshape(1)
-        reqs_c = np.ascontiguousarray(reqs_c, dtype=PLACE_REQ_C)
-        extra = np.zeros(0, np.int32) if extra_pool is None else np.ascontiguousarray(extra_pool, dtype=np.int32)
-        outs = np.zeros(len(reqs_c), dtype=PLACE_OUT)
-        self._ck(self.lib.mmp_place_batch_c(self.h, ptr(caller), ptr(reqs_c) if len(reqs_c) else None, len(reqs_c),
-                                            ptr(extra) if len(extra) else None, len(extra), int(now), ptr(outs) if len(reqs_c) else None))
-        return outs
+        return self._seam(self.lib.mmp_place_batch_c, [(caller, _lib.PLACE_CALLER)], [(reqs_c, _lib.PLACE_REQ_C)],
+                          [[(extra_pool, np.int32)]], [now], [PLACE_OUT])[0]
 
     def place_c_dev(self, caller, d_reqs: int, n: int, d_extra: int, n_extra_pool: int, now: int, d_outs: int, stream: int = 0):
         """The single-caller form on raw device pointers (24-byte rows), no sync; `caller` is a host PLACE_CALLER row."""
@@ -1001,95 +995,35 @@ class Solver:
                                          int(now), int(in_use_failure_expiry_ms), ptr(outs)))
         return outs
 
-    def route(self, gate_reqs, serve_reqs, counters, excl_pod, excl_time, explicit_pool, now, in_use_failure_expiry_ms=450_000):
-        """The cache-hit route in one launch (mmp_route_batch): -> (gate outs, serve outs)."""
-        from ._lib import GATE_OUT, GATE_REQ, SERVE_COUNTER, SERVE_OUT, SERVE_REQ
-        gate_reqs = np.ascontiguousarray(gate_reqs, dtype=GATE_REQ)
-        serve_reqs = np.ascontiguousarray(serve_reqs, dtype=SERVE_REQ)
-        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        n = len(gate_reqs)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        souts = np.zeros(n, dtype=SERVE_OUT)
-        self._ck(self.lib.mmp_route_batch(self.h, ptr(gate_reqs) if n else None, ptr(serve_reqs) if n else None, n,
-                                          ptr(counters) if len(counters) else None, len(counters),
-                                          ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                          len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                          C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                          ptr(gouts) if n else None, ptr(souts) if n else None))
-        return gouts, souts
+    # ---- the per-request seams: route (cache hit), miss (cache miss), the load target; by row, single-caller, by id ----
+    @staticmethod
+    def _pool(a, dtype):
+        """One array of a request call as the library takes it: (the contiguous array, its pointer or None when empty, its length)."""
+        a = np.zeros(0, dtype) if a is None else np.ascontiguousarray(a, dtype=dtype)
+        return a, (ptr(a) if len(a) else None), len(a)
 
-    def miss(self, gate_reqs, place_reqs, excl_pod, excl_time, explicit_pool, extra_pool, now, in_use_failure_expiry_ms=450_000):
-        """The cache-miss route in one call (mmp_miss_batch): the request guards + the load target -> (gate outs, place outs)."""
-        from ._lib import GATE_OUT, GATE_REQ, PLACE_OUT, PLACE_REQ
-        gate_reqs = np.ascontiguousarray(gate_reqs, dtype=GATE_REQ)
-        place_reqs = np.ascontiguousarray(place_reqs, dtype=PLACE_REQ)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(gate_reqs)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        pouts = np.zeros(n, dtype=PLACE_OUT)
-        self._ck(self.lib.mmp_miss_batch(self.h, ptr(gate_reqs) if n else None, ptr(place_reqs) if n else None, n,
-                                         ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                         len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                         ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
-                                         C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                         ptr(gouts) if n else None, ptr(pouts) if n else None))
-        return gouts, pouts
+    def _seam(self, fn, callers, rows, pools, times, out_dtypes, keyed=(), row_out=None):
+        """One request-seam call, the arguments in the order every seam of include/mmplace.h has them:
+        fn(ctx, *callers, *rows, n, *keyed, *(pool.., length).., *times, *outs, row_out) -> the outs.
+        callers / rows: (array, dtype) each, n the length of the first rows; pools: groups of (array, dtype) that share one
+        length (the exclusion pods and times); keyed / row_out: what a call by id adds (_keyed)."""
+        callers = [self._pool(np.ascontiguousarray(a, dtype=dt).reshape(1), dt) for a, dt in callers]
+        rows = [self._pool(a, dt) for a, dt in rows]
+        n = rows[0][2]
+        args = [self.h] + [p for _, p, _ in callers + rows] + [n] + [ptr(k) if isinstance(k, np.ndarray) else k for k in keyed]
+        keep = [callers, rows]
+        for group in pools:
+            group = [self._pool(a, dt) for a, dt in group]
+            keep.append(group)
+            args += [p for _, p, _ in group] + [group[0][2]]
+        args += [C.c_int64(int(t)) for t in times]
+        outs = [np.zeros(n, dtype=dt) for dt in out_dtypes]
+        args += [ptr(o) if n else None for o in outs]
+        if keyed:
+            args.append(ptr(row_out))
+        self._ck(fn(*args))
+        return outs
 
-    def route_c(self, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time, explicit_pool, now,
-                in_use_failure_expiry_ms=450_000):
-        """The single-caller form of route (mmp_route_batch_c): caller = 1 SEAM_CALLER row, GATE_REQ_C / SERVE_REQ_C rows
-        -> (gate outs, serve outs)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
-        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        souts = np.zeros(n, dtype=SERVE_OUT)
-        self._ck(self.lib.mmp_route_batch_c(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
-                                            ptr(counters) if len(counters) else None, len(counters),
-                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                            ptr(gouts) if n else None, ptr(souts) if n else None))
-        return gouts, souts
-
-    def miss_c(self, caller, place_caller, gate_reqs_c, place_reqs_c, excl_pod, excl_time, explicit_pool, extra_pool, now,
-               in_use_failure_expiry_ms=450_000):
-        """The single-caller form of miss (mmp_miss_batch_c): caller = 1 SEAM_CALLER row, place_caller = 1 PLACE_CALLER row,
-        GATE_REQ_C / PLACE_REQ_C rows -> (gate outs, place outs)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_OUT, PLACE_REQ_C, SEAM_CALLER
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        pouts = np.zeros(n, dtype=PLACE_OUT)
-        self._ck(self.lib.mmp_miss_batch_c(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
-                                           ptr(place_reqs_c) if n else None, n,
-                                           ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                           len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                           ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
-                                           C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                           ptr(gouts) if n else None, ptr(pouts) if n else None))
-        return gouts, pouts
-
-    # ---- the single-caller forms by model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck) ----
     @staticmethod
     def pack_keys(keys):
         """keys (a list of bytes / str, str as UTF-8) as the by-key calls take them, packed as model_ids_resolve packs them:
@@ -1097,76 +1031,6 @@ class Solver:
         blob, off = Solver._pack(keys)
         return blob, off.astype(np.int32)
 
-    def place_batch_ck(self, caller, reqs_c, keys, extra_pool, now, want_idx=True):
-        """mmp_place_batch_c with request i's model named by keys[i]: -> (outs, model_idx); the `model` field of reqs_c is
-        ignored.  want_idx=False passes a NULL model_idx_out and returns None for it."""
-        from ._lib import PLACE_CALLER, PLACE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=PLACE_CALLER).reshape(1)
-        reqs_c = np.ascontiguousarray(reqs_c, dtype=PLACE_REQ_C)
-        extra = np.zeros(0, np.int32) if extra_pool is None else np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(reqs_c)
-        assert len(keys) == n
-        blob, off = self.pack_keys(keys)
-        outs = np.zeros(n, dtype=PLACE_OUT)
-        idx = np.full(max(n, 1), -2, np.int32)
-        self._ck(self.lib.mmp_place_batch_ck(self.h, ptr(caller), ptr(reqs_c) if n else None, n, blob, ptr(off),
-                                             ptr(extra) if len(extra) else None, len(extra), C.c_int64(int(now)),
-                                             ptr(outs) if n else None, ptr(idx) if want_idx else None))
-        return outs, (idx[:n] if want_idx else None)
-
-    def route_batch_ck(self, caller, gate_reqs_c, serve_reqs_c, keys, counters, excl_pod, excl_time, explicit_pool, now,
-                       in_use_failure_expiry_ms=450_000, want_idx=True):
-        """mmp_route_batch_c with request i's model named by keys[i]: -> (gate outs, serve outs, model_idx)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
-        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        assert len(keys) == n and len(serve_reqs_c) == n
-        blob, off = self.pack_keys(keys)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        souts = np.zeros(n, dtype=SERVE_OUT)
-        idx = np.full(max(n, 1), -2, np.int32)
-        self._ck(self.lib.mmp_route_batch_ck(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
-                                             blob, ptr(off), ptr(counters) if len(counters) else None, len(counters),
-                                             ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                             len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                             C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                             ptr(gouts) if n else None, ptr(souts) if n else None, ptr(idx) if want_idx else None))
-        return gouts, souts, (idx[:n] if want_idx else None)
-
-    def miss_batch_ck(self, caller, place_caller, gate_reqs_c, place_reqs_c, keys, excl_pod, excl_time, explicit_pool, extra_pool, now,
-                      in_use_failure_expiry_ms=450_000, want_idx=True):
-        """mmp_miss_batch_c with request i's model named by keys[i]: -> (gate outs, place outs, model_idx)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_REQ_C, SEAM_CALLER
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        assert len(keys) == n and len(place_reqs_c) == n
-        blob, off = self.pack_keys(keys)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        pouts = np.zeros(n, dtype=PLACE_OUT)
-        idx = np.full(max(n, 1), -2, np.int32)
-        self._ck(self.lib.mmp_miss_batch_ck(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
-                                            ptr(place_reqs_c) if n else None, n, blob, ptr(off),
-                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                            ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
-                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                            ptr(gouts) if n else None, ptr(pouts) if n else None, ptr(idx) if want_idx else None))
-        return gouts, pouts, (idx[:n] if want_idx else None)
-
-    # ---- the single-caller forms by vmodel id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv) ----
     def _vkey_args(self, n, keys, nf, req_flags, want_vm):
         """What the _cv calls add: (key blob, key offsets, nf blob, nf offsets, flags, vm_out).  nf is a list of
         bytes/str/None (None and b"" are Java null) or None for NULL buffers; req_flags n words or None."""
@@ -1182,72 +1046,103 @@ class Solver:
         vm.view(np.uint8)[:] = 0xEE
         return blob, off, nblob, noff, rf, (vm if want_vm else None)
 
+    def _keyed(self, rows, keys, want, vmodel=False, nf=None, req_flags=None):
+        """What a call by id adds to the call it resolves in front of, as _seam's keywords: the arguments behind n (_ck: key blob
+        and offsets; _cv: _vkey_args) and the rows it resolves (model_idx filled with -2, vm rows with 0xEE; None: a NULL output).
+        rows: the request arrays, which are as long as keys."""
+        n = len(rows[0])
+        assert all(len(r) == n for r in rows)
+        if vmodel:
+            *keyed, out = self._vkey_args(n, keys, nf, req_flags, want)
+        else:
+            assert len(keys) == n
+            keyed, out = self.pack_keys(keys), (np.full(max(n, 1), -2, np.int32) if want else None)
+        return {"keyed": tuple(keyed), "row_out": out}, (out[:n] if want else None)
+
+    def _route(self, fn, caller, gate_reqs, serve_reqs, counters, excl_pod, excl_time, explicit_pool, now, expiry, keyed=None):
+        c = caller is not None
+        return self._seam(fn, [(caller, _lib.SEAM_CALLER)] if c else [],
+                          [(gate_reqs, _lib.GATE_REQ_C if c else _lib.GATE_REQ), (serve_reqs, _lib.SERVE_REQ_C if c else SERVE_REQ)],
+                          [[(counters, SERVE_COUNTER)], [(excl_pod, np.int32), (excl_time, np.int64)], [(explicit_pool, np.int32)]],
+                          [now, expiry], [_lib.GATE_OUT, SERVE_OUT], **(keyed or {}))
+
+    def _miss(self, fn, callers, gate_reqs, place_reqs, excl_pod, excl_time, explicit_pool, extra_pool, now, expiry, keyed=None):
+        c = callers is not None
+        return self._seam(fn, [(callers[0], _lib.SEAM_CALLER), (callers[1], _lib.PLACE_CALLER)] if c else [],
+                          [(gate_reqs, _lib.GATE_REQ_C if c else _lib.GATE_REQ), (place_reqs, _lib.PLACE_REQ_C if c else PLACE_REQ)],
+                          [[(excl_pod, np.int32), (excl_time, np.int64)], [(explicit_pool, np.int32)], [(extra_pool, np.int32)]],
+                          [now, expiry], [_lib.GATE_OUT, PLACE_OUT], **(keyed or {}))
+
+    def route(self, gate_reqs, serve_reqs, counters, excl_pod, excl_time, explicit_pool, now, in_use_failure_expiry_ms=450_000):
+        """The cache-hit route in one launch (mmp_route_batch): -> (gate outs, serve outs)."""
+        return tuple(self._route(self.lib.mmp_route_batch, None, gate_reqs, serve_reqs, counters, excl_pod, excl_time, explicit_pool,
+                                 now, in_use_failure_expiry_ms))
+
+    def miss(self, gate_reqs, place_reqs, excl_pod, excl_time, explicit_pool, extra_pool, now, in_use_failure_expiry_ms=450_000):
+        """The cache-miss route in one call (mmp_miss_batch): the request guards + the load target -> (gate outs, place outs)."""
+        return tuple(self._miss(self.lib.mmp_miss_batch, None, gate_reqs, place_reqs, excl_pod, excl_time, explicit_pool, extra_pool,
+                                now, in_use_failure_expiry_ms))
+
+    def route_c(self, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time, explicit_pool, now,
+                in_use_failure_expiry_ms=450_000):
+        """The single-caller form of route (mmp_route_batch_c): caller = 1 SEAM_CALLER row, GATE_REQ_C / SERVE_REQ_C rows
+        -> (gate outs, serve outs)."""
+        return tuple(self._route(self.lib.mmp_route_batch_c, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time,
+                                 explicit_pool, now, in_use_failure_expiry_ms))
+
+    def miss_c(self, caller, place_caller, gate_reqs_c, place_reqs_c, excl_pod, excl_time, explicit_pool, extra_pool, now,
+               in_use_failure_expiry_ms=450_000):
+        """The single-caller form of miss (mmp_miss_batch_c): caller = 1 SEAM_CALLER row, place_caller = 1 PLACE_CALLER row,
+        GATE_REQ_C / PLACE_REQ_C rows -> (gate outs, place outs)."""
+        return tuple(self._miss(self.lib.mmp_miss_batch_c, (caller, place_caller), gate_reqs_c, place_reqs_c, excl_pod, excl_time,
+                                explicit_pool, extra_pool, now, in_use_failure_expiry_ms))
+
+    # ---- the single-caller forms by model id (mmp_place_batch_ck / _route_batch_ck / _miss_batch_ck) ----
+    def place_batch_ck(self, caller, reqs_c, keys, extra_pool, now, want_idx=True):
+        """mmp_place_batch_c with request i's model named by keys[i]: -> (outs, model_idx); the `model` field of reqs_c is
+        ignored.  want_idx=False passes a NULL model_idx_out and returns None for it."""
+        keyed, idx = self._keyed([reqs_c], keys, want_idx)
+        outs, = self._seam(self.lib.mmp_place_batch_ck, [(caller, _lib.PLACE_CALLER)], [(reqs_c, _lib.PLACE_REQ_C)],
+                           [[(extra_pool, np.int32)]], [now], [PLACE_OUT], **keyed)
+        return outs, idx
+
+    def route_batch_ck(self, caller, gate_reqs_c, serve_reqs_c, keys, counters, excl_pod, excl_time, explicit_pool, now,
+                       in_use_failure_expiry_ms=450_000, want_idx=True):
+        """mmp_route_batch_c with request i's model named by keys[i]: -> (gate outs, serve outs, model_idx)."""
+        keyed, idx = self._keyed([gate_reqs_c, serve_reqs_c], keys, want_idx)
+        return (*self._route(self.lib.mmp_route_batch_ck, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time,
+                             explicit_pool, now, in_use_failure_expiry_ms, keyed), idx)
+
+    def miss_batch_ck(self, caller, place_caller, gate_reqs_c, place_reqs_c, keys, excl_pod, excl_time, explicit_pool, extra_pool, now,
+                      in_use_failure_expiry_ms=450_000, want_idx=True):
+        """mmp_miss_batch_c with request i's model named by keys[i]: -> (gate outs, place outs, model_idx)."""
+        keyed, idx = self._keyed([gate_reqs_c, place_reqs_c], keys, want_idx)
+        return (*self._miss(self.lib.mmp_miss_batch_ck, (caller, place_caller), gate_reqs_c, place_reqs_c, excl_pod, excl_time,
+                            explicit_pool, extra_pool, now, in_use_failure_expiry_ms, keyed), idx)
+
+    # ---- the single-caller forms by vmodel id (mmp_place_batch_cv / _route_batch_cv / _miss_batch_cv) ----
     def place_batch_cv(self, caller, reqs_c, keys, extra_pool, now, nf=None, req_flags=None, want_vm=True):
         """mmp_place_batch_c with request i's model named by the VMODEL id keys[i], resolved (resolveVModelId with nf[i] and
         req_flags[i]) inside the call: -> (outs, vm rows as VSEAM_ROW); the `model` field of reqs_c is ignored.  want_vm=False
         passes a NULL vm_out and returns None for it."""
-        from ._lib import PLACE_CALLER, PLACE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=PLACE_CALLER).reshape(1)
-        reqs_c = np.ascontiguousarray(reqs_c, dtype=PLACE_REQ_C)
-        extra = np.zeros(0, np.int32) if extra_pool is None else np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(reqs_c)
-        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
-        outs = np.zeros(n, dtype=PLACE_OUT)
-        self._ck(self.lib.mmp_place_batch_cv(self.h, ptr(caller), ptr(reqs_c) if n else None, n, blob, ptr(off), nblob, ptr(noff),
-                                             ptr(rf), ptr(extra) if len(extra) else None, len(extra), C.c_int64(int(now)),
-                                             ptr(outs) if n else None, ptr(vm)))
-        return outs, (vm[:n] if want_vm else None)
+        keyed, vm = self._keyed([reqs_c], keys, want_vm, True, nf, req_flags)
+        outs, = self._seam(self.lib.mmp_place_batch_cv, [(caller, _lib.PLACE_CALLER)], [(reqs_c, _lib.PLACE_REQ_C)],
+                           [[(extra_pool, np.int32)]], [now], [PLACE_OUT], **keyed)
+        return outs, vm
 
     def route_batch_cv(self, caller, gate_reqs_c, serve_reqs_c, keys, counters, excl_pod, excl_time, explicit_pool, now,
                        in_use_failure_expiry_ms=450_000, nf=None, req_flags=None, want_vm=True):
         """mmp_route_batch_c with request i's model named by the VMODEL id keys[i]: -> (gate outs, serve outs, vm rows)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, SEAM_CALLER, SERVE_COUNTER, SERVE_OUT, SERVE_REQ_C
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        serve_reqs_c = np.ascontiguousarray(serve_reqs_c, dtype=SERVE_REQ_C)
-        counters = np.ascontiguousarray(counters, dtype=SERVE_COUNTER)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        assert len(serve_reqs_c) == n
-        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        souts = np.zeros(n, dtype=SERVE_OUT)
-        self._ck(self.lib.mmp_route_batch_cv(self.h, ptr(caller), ptr(gate_reqs_c) if n else None, ptr(serve_reqs_c) if n else None, n,
-                                             blob, ptr(off), nblob, ptr(noff), ptr(rf),
-                                             ptr(counters) if len(counters) else None, len(counters),
-                                             ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                             len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                             C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                             ptr(gouts) if n else None, ptr(souts) if n else None, ptr(vm)))
-        return gouts, souts, (vm[:n] if want_vm else None)
+        keyed, vm = self._keyed([gate_reqs_c, serve_reqs_c], keys, want_vm, True, nf, req_flags)
+        return (*self._route(self.lib.mmp_route_batch_cv, caller, gate_reqs_c, serve_reqs_c, counters, excl_pod, excl_time,
+                             explicit_pool, now, in_use_failure_expiry_ms, keyed), vm)
 
     def miss_batch_cv(self, caller, place_caller, gate_reqs_c, place_reqs_c, keys, excl_pod, excl_time, explicit_pool, extra_pool, now,
                       in_use_failure_expiry_ms=450_000, nf=None, req_flags=None, want_vm=True):
         """mmp_miss_batch_c with request i's model named by the VMODEL id keys[i]: -> (gate outs, place outs, vm rows)."""
-        from ._lib import GATE_OUT, GATE_REQ_C, PLACE_CALLER, PLACE_REQ_C, SEAM_CALLER
-        caller = np.ascontiguousarray(caller, dtype=SEAM_CALLER).reshape(1)
-        place_caller = np.ascontiguousarray(place_caller, dtype=PLACE_CALLER).reshape(1)
-        gate_reqs_c = np.ascontiguousarray(gate_reqs_c, dtype=GATE_REQ_C)
-        place_reqs_c = np.ascontiguousarray(place_reqs_c, dtype=PLACE_REQ_C)
-        excl_pod = np.ascontiguousarray(excl_pod, dtype=np.int32)
-        excl_time = np.ascontiguousarray(excl_time, dtype=np.int64)
-        explicit_pool = np.ascontiguousarray(explicit_pool, dtype=np.int32)
-        extra_pool = np.ascontiguousarray(extra_pool, dtype=np.int32)
-        n = len(gate_reqs_c)
-        assert len(place_reqs_c) == n
-        blob, off, nblob, noff, rf, vm = self._vkey_args(n, keys, nf, req_flags, want_vm)
-        gouts = np.zeros(n, dtype=GATE_OUT)
-        pouts = np.zeros(n, dtype=PLACE_OUT)
-        self._ck(self.lib.mmp_miss_batch_cv(self.h, ptr(caller), ptr(place_caller), ptr(gate_reqs_c) if n else None,
-                                            ptr(place_reqs_c) if n else None, n, blob, ptr(off), nblob, ptr(noff), ptr(rf),
-                                            ptr(excl_pod) if len(excl_pod) else None, ptr(excl_time) if len(excl_time) else None,
-                                            len(excl_pod), ptr(explicit_pool) if len(explicit_pool) else None, len(explicit_pool),
-                                            ptr(extra_pool) if len(extra_pool) else None, len(extra_pool),
-                                            C.c_int64(int(now)), C.c_int64(int(in_use_failure_expiry_ms)),
-                                            ptr(gouts) if n else None, ptr(pouts) if n else None, ptr(vm)))
-        return gouts, pouts, (vm[:n] if want_vm else None)
+        keyed, vm = self._keyed([gate_reqs_c, place_reqs_c], keys, want_vm, True, nf, req_flags)
+        return (*self._miss(self.lib.mmp_miss_batch_cv, (caller, place_caller), gate_reqs_c, place_reqs_c, excl_pod, excl_time,
+                            explicit_pool, extra_pool, now, in_use_failure_expiry_ms, keyed), vm)
 
     def proactive_plan(self, default_model_size_units: int, now: int, max_out: int, partition: int = -1, skip_models=None):
         """a17: (models, last_used, info) the leader would proactively load, MRU first; partition >= 0: for that
