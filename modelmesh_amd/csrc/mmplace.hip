@@ -170,7 +170,7 @@ struct SnapSide {
 constexpr unsigned int kPinnedFlags = hipHostMallocCoherent | hipHostMallocMapped;
 constexpr size_t kSelMaxBytes = (size_t)32 << 20;  // Snap::sel / ::rk are built up to this size each (per snapshot side)
 constexpr int kTailStaticLds = 512;  // what place_tail_body keeps in static LDS beside place_block's own
-constexpr int kTailBlocks = 16;    // workgroups of a split batch's tail launch (measured: see place_kernel.hpp)
+constexpr int kTailBlocks = 64;    // one-wavefront workgroups of a split batch's tail launch (measured: profiles/tail_slot)
 constexpr int kMaxMissBufs = 64;   // streams with split batches in flight that get a buffer of their own (more: those batches go unsplit)
 constexpr int kFastSlots = 4;
 constexpr int kFastN = 4096;       // decisions per fast call
@@ -329,7 +329,7 @@ struct Tuning {
     int32_t no_long_memo = 0;    // MMP_NO_LONG_MEMO=1: commit records no walks of the long shortlists (place_kernel.hpp: LongMemo)
     int32_t no_split = 0;        // MMP_NO_SPLIT=1: batches are never split (place_memo_kernel + place_tail_kernel); the one-launch kernels instead
     int32_t split_from = -1;     // MMP_SPLIT_FROM=n: decisions from which a batch is split (default kSplitFrom / kSplitFromC)
-    int32_t tail_blocks = kTailBlocks;  // MMP_TAIL_BLOCKS=n: workgroups of a split batch's tail launch (1 .. kRestLists)
+    int32_t tail_blocks = kTailBlocks;  // MMP_TAIL_BLOCKS=n: one-wavefront workgroups of a split batch's tail launch (1 .. kRestLists)
     int32_t split_notail = 0;    // MMP_SPLIT_NOTAIL=1: the tail launch is left out — the batch's results are INCOMPLETE (bench.py times the first launch alone)
     int32_t no_long_lds = 0;     // MMP_NO_LONG_LDS=1: the long path reads its per-type tables from global memory (tests, comparison)
     int32_t no_caseb = 0;        // MMP_NO_CASEB=1: case (b) decisions never use the whole-window tables (tests: the wave path decides them)
@@ -411,8 +411,9 @@ struct mmp_ctx {
         std::mutex mu;             // taken after the state lock, before miss_mu; guards words / cap
         bool used = false;         // (used, st, report: under miss_mu; a slot in use is returned only with mu held as well)
         hipStream_t st = nullptr;
-        int32_t *words = nullptr;  // place_kernel.hpp: rest_buffer_ints — counters + kRestLists lists
+        int32_t *words = nullptr;  // place_kernel.hpp: rest_buffer_ints — counters, gate line + kRestLists lists
         size_t cap = 0;            // ints
+        uint32_t calls = 0;        // split batches enqueued on `words`: its parity names the call's gate word (place_kernel.hpp, above kRestLists); under mu
         int32_t *report = nullptr;
     };
     MissBuf miss_bufs[kMaxMissBufs];
@@ -840,8 +841,10 @@ hipError_t slot_wait(FastSlot *f, uint32_t seq)
 hipError_t order_after_registry(mmp_ctx *c, hipStream_t st);
 // The buffer of a split batch on `st` (`ints`: rest_buffer_ints of its first launch) and the stream's report pair, returned with the
 // stream's slot locked in `hold` (the caller enqueues both launches before it lets go); false: none to be had (too many streams, no
-// memory) — the batch goes unsplit, nothing is held.  Also reads what the stream's last tail reported.
-bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32_t **report, std::unique_lock<std::mutex> &hold)
+// memory) — the batch goes unsplit, nothing is held.  Also reads what the stream's last tail reported.  `calls`: the slot's count of
+// split batches, which the caller advances once BOTH launches are enqueued (a count advanced for a batch that then went unsplit would
+// hand the next one the gate word its predecessor's tail has not zeroed).
+bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32_t **report, uint32_t **calls, std::unique_lock<std::mutex> &hold)
 {
     mmp_ctx::MissBuf *mb = nullptr;
     while (!mb) {
@@ -884,8 +887,9 @@ bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32
             hold.unlock();
             return false;
         }
-        // the counters start at zero (every tail leaves them so); ordered before the stream's first launch on this buffer
-        if (hipMemsetAsync(p, 0, (size_t)kRestLists * kRestCntStride * sizeof(int32_t), st) != hipSuccess) {
+        // the counters and both gate words start at zero (every tail leaves its lists' counters and the other call's gate word so);
+        // ordered before the stream's first launch on this buffer
+        if (hipMemsetAsync(p, 0, (size_t)kRestHeadInts * sizeof(int32_t), st) != hipSuccess) {
             (void)hipFree(p);
             hold.unlock();
             return false;
@@ -902,6 +906,7 @@ bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32
     if (of > 0 && (int64_t)undecided * 32 > (int64_t)of) c->split_off.store(true, std::memory_order_relaxed);
     *words = mb->words;
     *report = mb->report;
+    *calls = &mb->calls;
     return true;
 }
 // a new snapshot / registry: split batches get another chance (the reports of the old one's tails are void)
@@ -1115,16 +1120,19 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
         if (const int rc = grant_place_lds(c)) return rc;
     // NOBAR kernels: a region per wavefront (place_wave_lds) instead of the shared one
     const size_t lds_nobar = (size_t)kPlaceWaves * place_wave_lds(wpad);
-    rs.memo_tail_lds = lds + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && (size_t)kPlaceWaves * memo_region_bytes(S.T) <= c->lds_limit;
+    // the tail of a split batch: workgroups of ONE wavefront, that wavefront's region alone
+    const size_t lds_tail = (size_t)place_wave_lds(wpad);
+    rs.memo_tail_lds = lds_tail + kPlaceStaticLds + kTailStaticLds <= c->lds_limit && (size_t)kPlaceWaves * memo_region_bytes(S.T) <= c->lds_limit;
     HIP_TRY(c, order_after_registry(c, st));
     // 2. the route; a split route holds the stream's buffer from here until its tail is enqueued (miss_buffer)
     const int grid = div_up(n, kPlaceBlock);
     const int cap = rest_list_cap(grid * kPlaceWaves);  // the first launch's wavefronts share kRestLists lists
     int32_t *words = nullptr, *report = nullptr;
+    uint32_t *calls = nullptr;
     std::unique_lock<std::mutex> pair;
     rs.split_ok = !c->split_off.load(std::memory_order_relaxed);
     PlaceRoute r = place_route(t, rs, n, o);
-    if (is_split(r) && (!miss_buffer(c, st, rest_buffer_ints(grid * kPlaceWaves), &words, &report, pair) ||
+    if (is_split(r) && (!miss_buffer(c, st, rest_buffer_ints(grid * kPlaceWaves), &words, &report, &calls, pair) ||
                         c->split_off.load(std::memory_order_relaxed))) {
         if (pair) pair.unlock();
         rs.split_ok = false;
@@ -1133,17 +1141,18 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     if (t.split_notail) words = nullptr;  // (diagnostics: the undecided requests are not even recorded)
     // 3. the launch
     const size_t lds_memo = (size_t)kPlaceWaves * memo_region_bytes(S.T);  // per wavefront: a copy of the types' records / its lane scratch
-    const dim3 block(kPlaceBlock), tails(t.tail_blocks);
+    const dim3 block(kPlaceBlock), tails(t.tail_blocks), tail_block(kTailBlock);
     const bool tail = !t.split_notail;
+    const int32_t par = calls ? (int32_t)(*calls & 1u) : 0;  // the call's gate word (held: `pair`)
     const mmp_place_caller C = o.caller ? *o.caller : mmp_place_caller{};
     switch (r) {
     case PlaceRoute::memo_split:
-        hipLaunchKernelGGL(place_memo_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap);
-        if (tail) hipLaunchKernelGGL(place_tail_kernel, tails, block, lds, st, S, A, wpad, words, cap, report);
+        hipLaunchKernelGGL(place_memo_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap, par);
+        if (tail) hipLaunchKernelGGL(place_tail_kernel, tails, tail_block, lds_tail, st, S, A, wpad, words, cap, par, report);
         break;
     case PlaceRoute::memo_split_c:
-        hipLaunchKernelGGL(place_memo_c_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap, C);
-        if (tail) hipLaunchKernelGGL(place_tail_c_kernel, tails, block, lds, st, S, A, wpad, words, cap, report, C);
+        hipLaunchKernelGGL(place_memo_c_kernel, dim3(grid), block, lds_memo, st, S, A, words, cap, par, C);
+        if (tail) hipLaunchKernelGGL(place_tail_c_kernel, tails, tail_block, lds_tail, st, S, A, wpad, words, cap, par, report, C);
         break;
     case PlaceRoute::multi: hipLaunchKernelGGL(place_multi_kernel, dim3(o.seg_blocks), block, lds, st, S, A, wpad, *o.segs); break;
     case PlaceRoute::multi_m: hipLaunchKernelGGL(place_multi_m_kernel, dim3(o.seg_blocks), block, lds_nobar, st, S, A, wpad, *o.segs); break;
@@ -1164,6 +1173,7 @@ int place_launch(mmp_ctx *c, const void *d_reqs, int32_t n, const void *d_extra,
     case PlaceRoute::batch_long4_c: hipLaunchKernelGGL(place_batch_long4_c_kernel, dim3(grid), block, lds, st, S, A, wpad, C); break;
     }
     HIP_TRY(c, hipGetLastError());
+    if (is_split(r) && tail && calls) ++*calls;  // both launches are on the stream: the next split batch takes the other gate word
     if (is_split(r)) c->n_split.fetch_add(1, std::memory_order_relaxed);
     return MMP_OK;
 }

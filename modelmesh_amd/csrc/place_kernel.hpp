@@ -2935,13 +2935,15 @@ __device__ __forceinline__ int lane_phase(const Snap &S, const PlaceArgs &A, Res
 // the staging nor, at the end, for the lane phase of the workgroup's other wavefronts (with the barriers the check bought nothing
 // for request rows: 27.4 against 25.9 us; without them 24.7).  The kernels WITHOUT the check keep staging + barrier: for them the
 // windows in LDS are the faster read (800k rows: 26.0 against 26.5 us, four streams 17.75 against 18.4).
-// LIST (the tail launch of the split form, place_tail_body): the workgroup's decisions come as a list — this lane's is `d_list`
-// (-1: none) — and the function may be called again by the same workgroup (it ends behind a barrier then).
+// LIST (the tail launch of the split form, place_tail_body): the decisions come as a list — this lane's is `d_list` (-1: none) — and
+// the function may be called again by the same wavefront.  It is the barrier-free form only: a tail workgroup is ONE wavefront, and
+// everything below that counts in kPlaceWaves (the window staging, the scratch stride, the wave path's stride) belongs to the form
+// with barriers, which a launch of 64 threads must not take — the wave path would silently skip three entries in four.
 template <bool WITH_LONG, int FORM = kReq64, bool MEMO = false, bool NOBAR = false, bool LIST = false>
 __device__ __forceinline__ void place_block(const Snap &S, const PlaceArgs &A, int32_t wpad, unsigned char *smem,
                                             uint32_t *done_blocks = nullptr, const mmp_place_caller &C = mmp_place_caller{}, int d_list = -1)
 {
-    static_assert(!(LIST && NOBAR), "the list form keeps the workgroup's barriers");
+    static_assert(!LIST || NOBAR, "the list form is one wavefront's: barrier-free only");
     __shared__ int32_t fb_list[kPlaceBlock], lr_list[kPlaceBlock];
     __shared__ int32_t fb_n, lr_n;
     // The staged windows and the per-lane scratch of the lane phase, and the wave path's bitmap tiles (kPlaceWaves x 2
@@ -3120,7 +3122,6 @@ __device__ __forceinline__ void place_block(const Snap &S, const PlaceArgs &A, i
     PHASE_COUNT(11, 1);  // wavefronts
     PHASE_ABS(15);
     announce_done(DoneFlag{A.done_flag, done_blocks, A.done_seq});
-    if (LIST) __syncthreads();  // the next call resets the lists
 }
 
 // 6 wavefronts per SIMD (80 VGPRs, 100 bytes of spill per lane) instead of the 5 the unconstrained allocation (95) gives:
@@ -3316,52 +3317,75 @@ constexpr int kSplitFromC = 8 * 1024 * 64;
 // scratch columns lie over the wavefront's own copy of the records).  What the window does not answer either — the walk, the long
 // phase, case (b), the general path: a handful of rows per batch — gets room in one of kRestLists lists — wavefront w in list w mod 64:
 // ONE returning atomic on a counter that ~1/64 of those wavefronts share (a launch-wide list behind ONE counter was 16 ns per atomic in
-// sequence, profiles/r5/shortlist_experiments v3) — and its index there; the number of rows the CHECK left goes to a word of its own
-// in the same counter line (rest_left_word).  place_tail_kernel, queued right behind it on the same stream (so it runs beside the next
-// batch's first launch, given a second stream): workgroup g takes lists g, g + G, ...; every wavefront reads their counts, and a
-// workgroup whose lists are empty — the normal case — ends there: one level of loads, no LDS, no barrier.  Otherwise it reads the
-// entries — two dependent loads, no scan (summing a word per first-launch wavefront took a tail workgroup 8 us) — decides them with the
-// ordinary place_block, windows, lists, general path and all (place_block<..., LIST>), and zeroes its counters for the stream's next
-// batch.  Workgroup 0 reports the sum of the "left by the check" words and zeroes them.  A batch the records do not fit (every request
-// with a position inside its list) still comes out right — the cold branch, and the tail behind it, then decide all of it — and the
-// host stops splitting when a tail reports that the check left more than 1/32 of its batch (mmp_ctx::split_off).  Before the cold
-// branch the tail decided every row the check left, behind a kernel boundary and its own chain of dependent loads: where two streams
-// share a hardware queue that was a quarter of a step (profiles/split_rest: 16.3 -> 14.0 us per 800k-row call at four queues).
+// sequence, profiles/r5/shortlist_experiments v3) — and its index there.  The same cold wavefront adds, in ONE non-returning 64-bit
+// atomic, to the call's GATE word: how many rows the check left it (low half: what the tail reports) and how many it appended (high
+// half).  place_tail_kernel, queued right behind it on the same stream (so it runs beside the next batch's first launch, given a second
+// stream), is a launch of ONE-wavefront workgroups of at most 64 registers: eight wavefronts of another stream's first launch (58 VGPRs,
+// 64 allocated) are all 512 registers and all eight slots of a SIMD, and the slot a retiring one frees is 64 registers wide — a tail
+// wavefront takes it as any first-launch wavefront would, where a workgroup of four wavefronts of 96 needed two slots on each of a
+// compute unit's four SIMDs at once.  (Measured, profiles/tail_slot: that wait is NOT what an empty tail's 5 us beside other streams'
+// first launches are — one 64-register wavefront averages the same, and has read its gate word 0.4 us after it starts; the rest is
+// dispatch and kernel boundary.  What the form buys is 0.8 us per 800k-row call at four hardware queues, 1.5 us with a queue per
+// stream.)  Every tail wavefront reads the gate line — ONE 128-byte line for the
+// whole launch — and, nothing appended, the normal case, ends there: one load, no LDS, no barrier; workgroup 0 reports from the same
+// line.  Otherwise wavefront g takes lists g, g + G, ...: it reads their counts and their entries — two more dependent loads, no scan
+// (summing a word per first-launch wavefront took a tail workgroup 8 us) — decides them 64 at a time with the barrier-free place_block,
+// windows from global memory, general path and all (place_block<..., NOBAR, LIST>), and zeroes the counters that were not zero for the
+// stream's next batch.  A batch the records do not fit (every request with a position inside its list) still comes out right — the cold
+// branch, and the tail behind it, then decide all of it — and the host stops splitting when a tail reports that the check left more than
+// 1/32 of its batch (mmp_ctx::split_off).  Before the cold branch the tail decided every row the check left, behind a kernel boundary
+// and its own chain of dependent loads: where two streams share a hardware queue that was a quarter of a step (profiles/split_rest:
+// 16.3 -> 14.0 us per 800k-row call at four queues).
+//
+// The gate line holds TWO gate words, and a call uses the one its parity names (`par`: the count of split calls on the stream's
+// buffer, kept by the host under the slot's lock, passed to both launches).  INVARIANT: a call's gate word is zero when its first launch
+// starts, and nothing zeroes it while its tail runs.  The first launch of call k only adds to word k & 1; the tail of call k only READS
+// word k & 1 (every wavefront, in any order, as late as it likes) and its workgroup 0 zeroes word (k + 1) & 1 — the word of call k - 1,
+// whose tail, earlier on the same stream, has ended, and of call k + 1, whose first launch, later on the same stream, has not begun.
+// So no tail wavefront can see its own word zeroed before it has read it, and no reader count or second launch is needed for the
+// reset.  The buffer's head (counters and gate line) starts zeroed (miss_buffer), whichever parity comes first.
 constexpr int kRestLists = 64;
 constexpr int kRestCntStride = 32;  // ints between two counters: a 128-byte line each
-// ints of the stream's buffer for a first launch of n_words wavefronts: the counters, then kRestLists lists of rest_list_cap entries
+constexpr int kRestGate = kRestLists * kRestCntStride;          // the gate line: behind the counters' lines
+constexpr int kRestHeadInts = kRestGate + kRestCntStride;       // counters + gate line; the lists follow
+// ints of the stream's buffer for a first launch of n_words wavefronts: the head, then kRestLists lists of rest_list_cap entries
 __host__ __device__ constexpr int rest_list_cap(int n_words) { return ((n_words + kRestLists - 1) / kRestLists) * 64; }
-__host__ __device__ constexpr size_t rest_buffer_ints(int n_words) { return (size_t)kRestLists * kRestCntStride + (size_t)kRestLists * rest_list_cap(n_words); }
+__host__ __device__ constexpr size_t rest_buffer_ints(int n_words) { return (size_t)kRestHeadInts + (size_t)kRestLists * rest_list_cap(n_words); }
 
 // LDS of the first launch, per wavefront: its copy of the records, later (cold) its 64 lanes' scratch columns of the lane phase
 __host__ __device__ constexpr int memo_region_bytes(int type_rows)
 {
     return memo_stage_bytes(type_rows) > kWinWords * 64 * 8 ? memo_stage_bytes(type_rows) : kWinWords * 64 * 8;
 }
-// the "left by the check" word of the list that the wavefront of decision d appends to: second word of the list's counter line
-__device__ __forceinline__ int32_t *rest_left_word(int32_t *__restrict__ rest, int d)
+// the gate word of a call of parity `par` (8-byte aligned): low half = rows the check left, high half = entries appended
+__device__ __forceinline__ unsigned long long *rest_gate_word(int32_t *__restrict__ rest, int par)
 {
-    return rest + (__builtin_amdgcn_readfirstlane(d >> 6) & (kRestLists - 1)) * kRestCntStride + 1;
+    return reinterpret_cast<unsigned long long *>(rest + kRestGate) + (par & 1);
 }
 
-// the undecided requests of this wavefront (`todo` lanes): room in its list — ONE returning atomic — then their indices
-__device__ __forceinline__ void rest_append(int32_t *__restrict__ rest, int32_t cap, int d, bool todo)
+// the undecided requests of this wavefront (`todo` lanes): room in its list — ONE returning atomic — then their indices; and the
+// wavefront's note in the call's gate word (`left`: rows the check left this wavefront, wave-uniform) — non-returning, nothing waits
+__device__ __forceinline__ void rest_append(int32_t *__restrict__ rest, int32_t cap, int par, int d, bool todo, int left)
 {
     const uint64_t mk = __ballot(todo);
-    if (mk && rest) {  // (wave-uniform; rest == null: diagnostics, nobody will decide them)
+    if (!rest) return;  // (diagnostics: nobody will decide them)
+    const int first = __ffsll((unsigned long long)mk) - 1;
+    if (lane_id() == (mk ? first : 0))
+        (void)__hip_atomic_fetch_add(rest_gate_word(rest, par), (unsigned long long)(unsigned)left | ((unsigned long long)__popcll((unsigned long long)mk) << 32),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (mk) {  // (wave-uniform)
         const int l = __builtin_amdgcn_readfirstlane(d >> 6) & (kRestLists - 1);
-        const int first = __ffsll((unsigned long long)mk) - 1;
         int base = 0;
         if (lane_id() == first)
             base = __hip_atomic_fetch_add(rest + l * kRestCntStride, __popcll((unsigned long long)mk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         base = readlane_i32(base, first);
-        if (todo) rest[kRestLists * kRestCntStride + (size_t)l * cap + base + __popcll((unsigned long long)(mk & ((1ull << lane_id()) - 1ull)))] = d;
+        if (todo) rest[kRestHeadInts + (size_t)l * cap + base + __popcll((unsigned long long)(mk & ((1ull << lane_id()) - 1ull)))] = d;
     }
 }
 
 template <int FORM>
-__device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &A, int32_t *__restrict__ rest, int32_t cap, const mmp_place_caller &C,
-                                                unsigned char *smem)
+__device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &A, int32_t *__restrict__ rest, int32_t cap, int32_t par,
+                                                const mmp_place_caller &C, unsigned char *smem)
 {
     // The types' records (TypeMemo rows: 512 bytes a type) into LDS, a copy per WAVEFRONT — global -> LDS directly, issued before the
     // request fetch and landed when that has (loads return in order), no barrier: the check then reads its type's record, the head of
@@ -3405,8 +3429,6 @@ __device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &
     // tail's lists are as empty.  The request row stays in registers for the branch (fetching it again: +0.4 us per call).
     const uint64_t mk = __ballot(todo);
     if (mk) {  // (wave-uniform)
-        if (rest && lane_id() == __ffsll((unsigned long long)mk) - 1)  // what the tail reports: rows the check left (rest_left_word)
-            __hip_atomic_fetch_add(rest_left_word(rest, d), __popcll((unsigned long long)mk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wave_sync();  // the records' last read lies before the scratch's first write
         if (todo) {
             ResolvedReq r = resolve_req<false, true>(S, A, rq);
@@ -3416,88 +3438,95 @@ __device__ __forceinline__ void place_memo_body(const Snap &S, const PlaceArgs &
                 todo = false;
             }
         }
-        rest_append(rest, cap, d, todo);
+        rest_append(rest, cap, par, d, todo, __popcll((unsigned long long)mk));  // what the tail reports: the rows the CHECK left
     }
 }
-__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void place_memo_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap)
+__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void place_memo_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap, int32_t par)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_memo_body<kReq64>(S, A, rest, cap, mmp_place_caller{}, smem);
+    place_memo_body<kReq64>(S, A, rest, cap, par, mmp_place_caller{}, smem);
 }
 __global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void place_memo_c_kernel(Snap S, PlaceArgs A, int32_t *__restrict__ rest, int32_t cap,
-                                                                                                           mmp_place_caller C)
+                                                                                                           int32_t par, mmp_place_caller C)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_memo_body<kReqC>(S, A, rest, cap, C, smem);
+    place_memo_body<kReqC>(S, A, rest, cap, par, C, smem);
 }
 
+// A tail workgroup is ONE wavefront (see above); its dynamic LDS is that wavefront's region of the barrier-free place_block
+// (place_wave_lds(wpad): its 64 lanes' scratch columns, later its general path's two tiles).
+constexpr int kTailBlock = 64;
 // `report` (may be null): workgroup 0 leaves {undecided requests, n} there (pinned host memory: the host reads the pair some launches
 // later, never waits for it)
 template <int FORM>
 __device__ __forceinline__ void place_tail_body(const Snap &S, const PlaceArgs &A, int32_t wpad, unsigned char *smem, int32_t *__restrict__ rest, int32_t cap,
-                                                int32_t *report, const mmp_place_caller &C)
+                                                int32_t par, int32_t *report, const mmp_place_caller &C)
 {
-    __shared__ int32_t t_cnt[kRestLists + 1];  // this workgroup's lists: running totals
-    // A tail wavefront is ONE long dependent chain on a SIMD it shares with up to eight wavefronts of the next batch's first launch:
+    __shared__ int32_t t_cnt[kRestLists + 1];  // this wavefront's lists: running totals
+    // A tail wavefront is ONE long dependent chain on a SIMD it shares with up to seven wavefronts of the next batch's first launch:
     // it goes first whenever it can issue
     __builtin_amdgcn_s_setprio(3);
     PHASE_T0();
-    const int tid = threadIdx.x;
+    const int lane = threadIdx.x;  // (kTailBlock threads)
     const int G = gridDim.x, g = blockIdx.x;
     if (g >= kRestLists) return;
-    const int mine = (kRestLists - g + G - 1) / G;  // lists g, g + G, ...
-    // Every wavefront reads the counts of the workgroup's lists for itself: the first launch decides on the spot what the head windows
-    // answer (place_memo_body), so the lists are normally EMPTY, and such a workgroup leaves here — one level of loads, no LDS, no barrier,
-    // no window or tile touched.  (The counts are what the first launch left: nothing writes them while the tail's workgroups start.)
-    const int lane = tid & 63;
-    const int c = lane < mine ? rest[(g + lane * G) * kRestCntStride] : 0;
-    if (g == 0 && tid < 64) {
-        // the rows the check left (rest_left_word): workgroup 0 alone reads the 64 words, reports their sum and zeroes them
-        const int lw = rest[tid * kRestCntStride + 1];
-        const int all = wave_sum_i32(lw);
-        if (report && tid == 0) {
-            __hip_atomic_store(report, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // The gate line first — both gate words in one load, lane l reads word l & 1: the first launch decides on the spot what the head
+    // windows answer (place_memo_body), so normally NOTHING was appended, and the wavefront leaves here — one load on a line the whole
+    // launch shares, no LDS, no barrier, no counter, window or tile touched.  (The call's word is what its first launch left: nothing
+    // writes it while the tail runs — the invariant above kRestLists.)
+    const unsigned long long gw = __hip_atomic_load(rest_gate_word(rest, lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int me = par & 1;
+    const int left = readlane_i32((int32_t)(uint32_t)gw, me), appended = readlane_i32((int32_t)(uint32_t)(gw >> 32), me);
+    PHASE(13);  // (tail) the gate read
+    if (g == 0) {
+        // the rows the check left, from the same line; and the other word — the last call's, the next call's — zeroed where it is not
+        if (report && lane == 0) {
+            __hip_atomic_store(report, left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(report + 1, A.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        if (lw) rest[tid * kRestCntStride + 1] = 0;
+        if (lane == (me ^ 1) && gw != 0) *rest_gate_word(rest, lane) = 0;
     }
-    if (!__ballot(c != 0)) return;  // (workgroup-uniform: every wavefront read the same words; the counters are zero already)
-    if (tid < 64) {
+    if (appended == 0) return;  // (launch-uniform: every wavefront read the same word; the counters are zero already)
+    const int mine = (kRestLists - g + G - 1) / G;  // lists g, g + G, ...
+    const int c = lane < mine ? rest[(g + lane * G) * kRestCntStride] : 0;
+    if (!__ballot(c != 0)) return;
+    {
         const int incl = wave_incl_scan_i32(c);
-        t_cnt[tid + 1] = incl;
-        if (tid == 0) t_cnt[0] = 0;
+        t_cnt[lane + 1] = incl;
+        if (lane == 0) t_cnt[0] = 0;
     }
-    __syncthreads();
+    wave_sync();
     const int total = t_cnt[mine];
-    PHASE(13);  // (tail) the counts read
-    for (int base = 0; base < total; base += kPlaceBlock) {  // (workgroup-uniform)
+    for (int base = 0; base < total; base += kTailBlock) {  // (wave-uniform) 64 entries a pass
         int d = -1;
-        const int i = base + tid;
+        const int i = base + lane;
         if (i < total) {
             int k = 0;
-            while (t_cnt[k + 1] <= i) k++;  // (a handful of lists per workgroup)
-            d = rest[kRestLists * kRestCntStride + (size_t)(g + k * G) * cap + (i - t_cnt[k])];
+            while (t_cnt[k + 1] <= i) k++;  // (a handful of lists per wavefront)
+            d = rest[kRestHeadInts + (size_t)(g + k * G) * cap + (i - t_cnt[k])];
         }
         PHASE(14);  // (tail) this pass's entries read
-        place_block<false, FORM, false, false, true>(S, A, wpad, smem, nullptr, C, d);
+        place_block<false, FORM, false, true, true>(S, A, wpad, smem, nullptr, C, d);
     }
-    if (tid < mine) rest[(g + tid * G) * kRestCntStride] = 0;  // for the stream's next batch (ordered behind this launch)
+    if (c) rest[(g + lane * G) * kRestCntStride] = 0;  // for the stream's next batch (ordered behind this launch)
 }
-// (5 wavefronts per SIMD = 96 VGPRs: a tail wavefront then fits on a SIMD that holds eight wavefronts of another stream's first launch —
-// 8 x 48 + 96 <= 512 registers; with the 154 the compiler takes unasked, the tail's workgroups waited for a compute unit to drain)
+// (8 wavefronts per SIMD = 64 VGPRs, the width of the slot that a retiring wavefront of another stream's first launch — 58 VGPRs, 64
+// allocated, eight of them all 512 registers of a SIMD — leaves behind.  The code is cold: what does not fit 64 registers goes to
+// scratch, which costs a tail WITH rows and nothing in the normal, empty one.  It was 5 (96 VGPRs) while the first launch took 49
+// registers, 56 allocated: 8 x 56 + 64 = 512 no longer holds a 96-register wavefront since it takes 58.)
 #ifndef MMP_TAIL_EU
-#define MMP_TAIL_EU 5
+#define MMP_TAIL_EU 8
 #endif
-__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP_TAIL_EU, MMP_TAIL_EU))) void place_tail_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t *report)
+__global__ __launch_bounds__(kTailBlock) __attribute__((amdgpu_waves_per_eu(MMP_TAIL_EU, MMP_TAIL_EU))) void place_tail_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t par, int32_t *report)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_tail_body<kReq64>(S, A, wpad, smem, rest, cap, report, mmp_place_caller{});
+    place_tail_body<kReq64>(S, A, wpad, smem, rest, cap, par, report, mmp_place_caller{});
 }
-__global__ __launch_bounds__(kPlaceBlock) __attribute__((amdgpu_waves_per_eu(MMP_TAIL_EU, MMP_TAIL_EU))) void place_tail_c_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t *report,
+__global__ __launch_bounds__(kTailBlock) __attribute__((amdgpu_waves_per_eu(MMP_TAIL_EU, MMP_TAIL_EU))) void place_tail_c_kernel(Snap S, PlaceArgs A, int32_t wpad, int32_t *__restrict__ rest, int32_t cap, int32_t par, int32_t *report,
                                                                    mmp_place_caller C)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    place_tail_body<kReqC>(S, A, wpad, smem, rest, cap, report, C);
+    place_tail_body<kReqC>(S, A, wpad, smem, rest, cap, par, report, C);
 }
 
 __global__ __launch_bounds__(kPlaceBlock) void place_batch_long_c_kernel(Snap S, PlaceArgs A, int32_t wpad, mmp_place_caller C)
