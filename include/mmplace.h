@@ -622,6 +622,67 @@ int mmp_cache_replay(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n_ops, int64
 int mmp_cache_read(mmp_ctx *ctx, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *key,
                    int32_t *n_out, int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm);
 
+/* ---- the stateful caches by model id (cache_keyed_kernels.hpp) -----------------------------------------------------------------
+ * runtimeCache maps a model id to its CacheEntry (MM.java:2863-2913).  Caches loaded through mmp_caches_load_keyed_k are BOUND:
+ * the key of an entry is the registry row its model id names, the device resolves every id, and what a replay evicts comes back
+ * as ids — ready for the MMP_ROP_DEREGISTER ops of mmp_registry_ops_k that follow each eviction (onEviction -> deregisterModel).
+ * The host invents no key and keeps no map.  Caches loaded through mmp_caches_load_keyed are unbound; the plain calls above behave
+ * on both kinds exactly as they always did.  mmp_model_ids_load drops the binding (the contents stay): the _k calls then answer
+ * MMP_ESTATE until the next mmp_caches_load_keyed_k.  mmp_models_retire carries bound caches along (see there).
+ * Every _k call takes the locks of the plain cache calls, answers MMP_ESTATE as mmp_model_ids_resolve does (no id table, or the
+ * registry resized by index since) and when the caches are not bound, and takes keys as mmp_model_ids_resolve does: raw bytes,
+ * n + 1 monotone offsets that need not start at 0, the empty id an ordinary id. */
+#define MMP_COPK_RAW_KEY 1                  /* mmp_cache_op.reserved: the op keeps its `key`, which must be MMP_UNLOADBUF_KEY        */
+#define MMP_CKEY_LIVE 0                     /* key_status_out: the id names a live record                                           */
+#define MMP_CKEY_EMPTY_ROW 1                /* the row exists and its record is deleted; the op ran as usual                        */
+#define MMP_CKEY_UNKNOWN 2                  /* the table does not know the id                                                       */
+#define MMP_CACHE_KEY_UNKNOWN (-2147483647 - 1) /* the key a non-inserting op under an unknown id runs with: no cache can hold it  */
+/* mmp_caches_load_keyed with one id per entry, resolved on the device: entry e has the id keys[key_off[e], key_off[e+1]), E =
+ * seg_off[n_caches] ids in all.  is_unloadbuf (E bytes, may be NULL): a marked entry is the manager's pseudo-entry, gets
+ * MMP_UNLOADBUF_KEY and its span is not read.  An id whose row is the empty row of a deleted record is accepted (the janitor
+ * exists to remove such entries).  key_row_out (may be NULL) receives the E keys.  MMP_EINVAL with nothing changed — the caches
+ * loaded before, bound or not, stay as they were: what mmp_caches_load_keyed refuses, non-monotone key offsets, an id the table
+ * does not know (mmp_last_error names the lowest such entry). */
+int mmp_caches_load_keyed_k(mmp_ctx *ctx, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used,
+                            const int32_t *weight, const char *keys, const int32_t *key_off, const uint8_t *is_unloadbuf,
+                            const int64_t *capacity, const mmp_ubm_state *ubm, int32_t *key_row_out);
+/* mmp_cache_replay by model id.  Op i is evaluated exactly as mmp_cache_replay evaluates it with `key` = the row
+ * mmp_model_ids_resolve answers for key i (the row as the table answers it: the entry of a deleted record is still found, read and
+ * removed); the `key` the caller sent is never read.  Exceptions: an op with reserved == MMP_COPK_RAW_KEY must carry key ==
+ * MMP_UNLOADBUF_KEY and keeps it; the keyless codes (MMP_COP_UBM_SPACE_IS_READY, _CLAIM_SPACE, _UNLOAD_COMPLETE, _DISCARD_FAILED)
+ * have none; neither reads its span.  key_status_out[i] = MMP_CKEY_* (MMP_CKEY_LIVE for those two kinds); key_row_out[i] = the key
+ * the op ran with (-1 for a keyless code).  Under an UNKNOWN id a non-inserting op runs with MMP_CACHE_KEY_UNKNOWN, i.e. is
+ * answered as the reference answers an absent key (with what adjustWeightAfterLoad does to the manager's sums); an inserting op
+ * (MMP_COP_PUT_IF_ABSENT, _UBM_INSERT_NEW_ENTRY, _UBM_INSERT_FAILED_PLACEHOLDER) is NOT RUN — the mesh never loads a model without
+ * a record — and its out row carries result 0, n_evicted 0 and the cache's state as the preceding op left it; the slot sizing
+ * still counts it as a possible insert (an upper bound).
+ * outs, evicted_rows, max_evicted, n_evicted_slots: as in mmp_cache_replay, the evicted keys being rows; a slot no op used holds
+ * -1.  The ids of the evicted rows are gathered on the device in the same hold of the locks: ev_id_off_out (*n_evicted_slots + 1
+ * words; room for max_evicted + 1) are offsets into ev_id_bytes_out, an unused slot has an empty span; *n_id_bytes_out = the bytes
+ * needed, always.  With max_id_bytes below that the offsets are returned and the bytes are not — the replay is applied all the
+ * same (it is stateful and cannot be asked twice) and the context keeps the record: mmp_cache_evicted_ids returns the same offsets
+ * and bytes until the next mmp_cache_replay_k or cache load.  The record holds bytes, not rows: a mmp_models_retire in between
+ * cannot change it.  key_status_out, key_row_out, ev_id_bytes_out (with max_id_bytes 0) and ev_id_off_out may be NULL.
+ * MMP_EINVAL with nothing changed: what mmp_cache_replay refuses, keys without key_off or the reverse, neither with n_ops > 0,
+ * non-monotone offsets, reserved outside {0, MMP_COPK_RAW_KEY}, MMP_COPK_RAW_KEY with another key.  n_ops == 0 is valid (and
+ * leaves an empty record). */
+int mmp_cache_replay_k(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n_ops, const char *keys, const int32_t *key_off, int64_t now_ms,
+                       int32_t *key_status_out, int32_t *key_row_out, mmp_cache_op_out *outs, int32_t *evicted_rows, int32_t max_evicted,
+                       int32_t *n_evicted_slots, char *ev_id_bytes_out, int32_t max_id_bytes, int32_t *ev_id_off_out,
+                       int32_t *n_id_bytes_out);
+/* The eviction record of the last mmp_cache_replay_k, by the sizes-then-list protocol of mmp_model_ids_get: *n_slots_out and
+ * *n_bytes_out always; off_out (n_slots + 1 words) when it is not NULL; the bytes when max_bytes >= *n_bytes_out.  No record
+ * (none yet, or a cache load since): 0 slots. */
+int mmp_cache_evicted_ids(mmp_ctx *ctx, char *bytes_out, int32_t max_bytes, int32_t *off_out, int32_t *n_slots_out,
+                          int32_t *n_bytes_out);
+/* mmp_cache_read plus the ids of the deque's entries, gathered on the device: row_out = the keys (rows), id_off_out (min(n,
+ * max_entries) + 1 words) offsets into id_bytes_out, *n_id_bytes_out = the bytes of those entries' ids, always; the bytes are
+ * written when max_id_bytes is at least that.  The pseudo-entry has row_out == MMP_UNLOADBUF_KEY and an empty span, which tells
+ * it apart from the empty id. */
+int mmp_cache_read_k(mmp_ctx *ctx, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *row_out,
+                     char *id_bytes_out, int32_t max_id_bytes, int32_t *id_off_out, int32_t *n_out, int32_t *n_id_bytes_out,
+                     int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm);
+
 /* n guard evaluations (rows a10/a11/a14/a20). in_use_failure_expiry_ms = IN_USE_LOAD_FAILURE_EXPIRY_MS
  * (MM.java:221). excl_pod/excl_time and explicit_pool are the pools the requests index. */
 int mmp_gate_batch(mmp_ctx *ctx, const mmp_gate_req *reqs, int32_t n, const int32_t *excl_pod,
@@ -1476,9 +1537,15 @@ int mmp_models_events_json(mmp_ctx *ctx, const char *keys, const int32_t *key_of
  * Decisions: the compacted tables are built beside the published ones; the pointers and counts are swapped under the state lock
  * once the decisions in flight have drained, and the resolved view is rebuilt as in mmp_models_load — a decision sees the whole
  * old registry or the whole new one, and decisions after the call are right without a commit.  Row numbers the HOST holds —
- * request rows in flight, the keys of the keyed caches, its own maps — are the host's to renumber from remap_out.
+ * request rows in flight, the keys of UNBOUND keyed caches (mmp_caches_load_keyed), its own maps — are the host's to renumber from
+ * remap_out.  BOUND caches (mmp_caches_load_keyed_k) are carried along: a named row that is the key of a LIVE entry of any cache
+ * (a position below the cache's entry count; the slots behind it are not looked at) makes the call MMP_EINVAL with nothing
+ * changed — registry, id table and caches — and mmp_last_error names the lowest such row, checked on the device in front of the
+ * swap like MMP_RETIRE_EMPTY_ONLY (the cache's counterpart of MMP_PODS_RETIRE_UNREFERENCED; the intended loop: deletion event,
+ * the janitor's MMP_COP_REMOVE, then retire); once nothing can fail any more every live key >= 0 becomes remap[key] on the
+ * device, and MMP_UNLOADBUF_KEY stays as it is.  Without bound caches the call is what it always was.
  * MMP_EINVAL with nothing changed: NULL rows with n > 0, a row outside [0, M0), an unknown flag bit, remap_out with
- * max_models < M0, a non-empty row under MMP_RETIRE_EMPTY_ONLY.  MMP_ESTATE with nothing changed: an id table is loaded and its
+ * max_models < M0, a non-empty row under MMP_RETIRE_EMPTY_ONLY, a row that is a live key of a bound cache.  MMP_ESTATE with nothing changed: an id table is loaded and its
  * row count no longer equals the registry's (as mmp_model_ids_resolve).  n == 0 is valid and changes nothing: remap_out is the
  * identity, *n_models_after_out = M0.  No commit is needed before or after.  The work is O(registry), as a reload is — the host
  * decides how often to call; two runs over the same state and list are byte-identical.  Locking: batch_mu throughout. */

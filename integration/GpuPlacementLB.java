@@ -79,6 +79,19 @@ final class MmPlace {
                                   int maxEvicted, ByteBuffer nEvictedSlots);
     static native int cacheRead(long h, int cache, int maxEntries, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer key,
                                 ByteBuffer scalars, ByteBuffer ubm);
+    // the caches by model id (mmp_caches_load_keyed_k ...): the key of an entry is the registry row its id names, resolved on the
+    // device; what a replay evicts comes back as ids.  A thin pass-through: no Java site is moved onto these calls yet.
+    // cacheReplayK sizes = {nEvictedSlots, nIdBytes}; cacheEvictedIds sizes = {nSlots, nBytes}; cacheReadK scalars = {int n, int
+    // nIdBytes, long capacity, long weightedSize}.
+    static native int cachesLoadKeyedK(long h, int nCaches, ByteBuffer segOff, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer keys,
+                                       ByteBuffer keyOff, ByteBuffer isUnloadbuf, ByteBuffer capacity, ByteBuffer ubm,
+                                       ByteBuffer keyRowOut);
+    static native int cacheReplayK(long h, ByteBuffer ops, int nOps, ByteBuffer keys, ByteBuffer keyOff, long nowMs,
+                                   ByteBuffer keyStatusOut, ByteBuffer keyRowOut, ByteBuffer outs, ByteBuffer evictedRows,
+                                   int maxEvicted, ByteBuffer evIdBytesOut, int maxIdBytes, ByteBuffer evIdOffOut, ByteBuffer sizes);
+    static native int cacheEvictedIds(long h, ByteBuffer bytesOut, int maxBytes, ByteBuffer offOut, ByteBuffer sizes);
+    static native int cacheReadK(long h, int cache, int maxEntries, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer rowOut,
+                                 ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut, ByteBuffer scalars, ByteBuffer ubm);
     // request guards and rebalancer plans
     static native int gateBatch(long h, ByteBuffer reqs, int n, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl,
                                 ByteBuffer explicitPool, int nExplicit, long nowMs, long inUseFailureExpiryMs,

@@ -274,6 +274,55 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheRead(JNIEnv *e
                                 buf<int32_t>(env, key), &sc->n, &sc->capacity, &sc->weighted_size,
                                 buf<mmp_ubm_state>(env, ubm)));
 }
+// the caches by model id (see mmp_caches_load_keyed_k): a thin pass-through, the buffers are the caller's to size as the header says
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cachesLoadKeyedK(JNIEnv *env, jclass, jlong h, jint nCaches, jobject segOff,
+                                                                              jobject lastUsed, jobject weight, jobject keys,
+                                                                              jobject keyOff, jobject isUnloadbuf, jobject capacity,
+                                                                              jobject ubm, jobject keyRowOut)
+{
+    return check(env, ctx_of(h),
+                 mmp_caches_load_keyed_k(ctx_of(h), nCaches, buf<int32_t>(env, segOff), buf<int64_t>(env, lastUsed), buf<int32_t>(env, weight),
+                                         buf<char>(env, keys), buf<int32_t>(env, keyOff), buf<uint8_t>(env, isUnloadbuf),
+                                         buf<int64_t>(env, capacity), buf<mmp_ubm_state>(env, ubm), buf<int32_t>(env, keyRowOut)));
+}
+// sizes: direct IntBuffer of two elements {nEvictedSlots, nIdBytes}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReplayK(JNIEnv *env, jclass, jlong h, jobject ops, jint nOps, jobject keys,
+                                                                          jobject keyOff, jlong nowMs, jobject keyStatusOut,
+                                                                          jobject keyRowOut, jobject outs, jobject evictedRows,
+                                                                          jint maxEvicted, jobject evIdBytesOut, jint maxIdBytes,
+                                                                          jobject evIdOffOut, jobject sizes)
+{
+    int32_t *sz = buf<int32_t>(env, sizes);
+    if (!sz || !holds<int32_t>(env, sizes, 2, "cacheReplayK: sizes shorter than two ints")) return check(env, ctx_of(h), MMP_EINVAL);
+    return check(env, ctx_of(h),
+                 mmp_cache_replay_k(ctx_of(h), buf<mmp_cache_op>(env, ops), nOps, buf<char>(env, keys), buf<int32_t>(env, keyOff), nowMs,
+                                    buf<int32_t>(env, keyStatusOut), buf<int32_t>(env, keyRowOut), buf<mmp_cache_op_out>(env, outs),
+                                    buf<int32_t>(env, evictedRows), maxEvicted, sz, buf<char>(env, evIdBytesOut), maxIdBytes,
+                                    buf<int32_t>(env, evIdOffOut), sz + 1));
+}
+// sizes: direct IntBuffer of two elements {nSlots, nBytes}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheEvictedIds(JNIEnv *env, jclass, jlong h, jobject bytesOut, jint maxBytes,
+                                                                             jobject offOut, jobject sizes)
+{
+    int32_t *sz = buf<int32_t>(env, sizes);
+    if (!sz || !holds<int32_t>(env, sizes, 2, "cacheEvictedIds: sizes shorter than two ints")) return check(env, ctx_of(h), MMP_EINVAL);
+    return check(env, ctx_of(h), mmp_cache_evicted_ids(ctx_of(h), buf<char>(env, bytesOut), maxBytes, buf<int32_t>(env, offOut), sz, sz + 1));
+}
+// scalars: direct buffer {int32 n; int32 nIdBytes; int64 capacity; int64 weightedSize}
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReadK(JNIEnv *env, jclass, jlong h, jint cache, jint maxEntries,
+                                                                        jobject lastUsed, jobject weight, jobject rowOut, jobject idBytesOut,
+                                                                        jint maxIdBytes, jobject idOffOut, jobject scalars, jobject ubm)
+{
+    struct Scalars {
+        int32_t n, n_id_bytes;
+        int64_t capacity, weighted_size;
+    } *sc = buf<Scalars>(env, scalars);
+    if (!sc) return check(env, ctx_of(h), MMP_EINVAL);
+    return check(env, ctx_of(h),
+                 mmp_cache_read_k(ctx_of(h), cache, maxEntries, buf<int64_t>(env, lastUsed), buf<int32_t>(env, weight),
+                                  buf<int32_t>(env, rowOut), buf<char>(env, idBytesOut), maxIdBytes, buf<int32_t>(env, idOffOut), &sc->n,
+                                  &sc->n_id_bytes, &sc->capacity, &sc->weighted_size, buf<mmp_ubm_state>(env, ubm)));
+}
 
 // ---- request guards (MM.java:3603-3626, 3870-3884, 4003-4042, 4590-4627, 5158-5197, 2867-2933, 5440-5468)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_gateBatch(JNIEnv *env, jclass, jlong h, jobject reqs,

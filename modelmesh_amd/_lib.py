@@ -290,6 +290,12 @@ UNLOADBUF_KEY = -1000000
 (COP_PUT_IF_ABSENT, COP_GET, COP_UPDATE_WEIGHT, COP_REMOVE, COP_UBM_INSERT_NEW_ENTRY, COP_UBM_ADJUST_SPACE_REQUEST,
  COP_UBM_SPACE_IS_READY, COP_UBM_CLAIM_SPACE, COP_UBM_ADJUST_AFTER_LOAD, COP_UBM_UNLOAD_COMPLETE, COP_UBM_REMOVE_ENTRY,
  COP_UBM_DISCARD_FAILED, COP_UBM_INSERT_FAILED_PLACEHOLDER) = range(13)
+# the caches by model id (mmp_caches_load_keyed_k, mmp_cache_replay_k, mmp_cache_read_k)
+COPK_RAW_KEY = 1  # mmp_cache_op.reserved: the op keeps its key, which must be UNLOADBUF_KEY
+CKEY_LIVE, CKEY_EMPTY_ROW, CKEY_UNKNOWN = range(3)
+CACHE_KEY_UNKNOWN = -(2 ** 31)
+COP_KEYLESS = (COP_UBM_SPACE_IS_READY, COP_UBM_CLAIM_SPACE, COP_UBM_UNLOAD_COMPLETE, COP_UBM_DISCARD_FAILED)
+COP_INSERTING = (COP_PUT_IF_ABSENT, COP_UBM_INSERT_NEW_ENTRY, COP_UBM_INSERT_FAILED_PLACEHOLDER)
 
 assert POD_ROW.itemsize == 64 and MODEL_ROW.itemsize == 24 and PLACE_REQ.itemsize == 64
 assert PLACE_OUT.itemsize == 16 and SERVE_REQ.itemsize == 48 and SERVE_COUNTER.itemsize == 16 and SERVE_OUT.itemsize == 16
@@ -351,6 +357,12 @@ SYMBOLS = [
     ("mmp_cache_replay", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_cache_read", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                  C.POINTER(C.c_int64), _P]),
+    ("mmp_caches_load_keyed_k", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("mmp_cache_replay_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32,
+                                     _P, C.POINTER(C.c_int32)]),
+    ("mmp_cache_evicted_ids", C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("mmp_cache_read_k", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     ("mmp_gate_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),
     ("mmp_miss_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     ("mmp_route_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),

@@ -45,6 +45,7 @@
 #include "status_kernels.hpp"
 #include "status_keyed_kernels.hpp"
 #include "registry_ops_keyed_kernels.hpp"
+#include "cache_keyed_kernels.hpp"
 #include "tasks_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
@@ -531,6 +532,14 @@ struct mmp_ctx {
     DevBuf r_part;  // per-workgroup partials of the proactive plan's first pass
     DevBuf rs_split, rs_int;  // rank_sample.hpp: the sorted samples; range_of[P] | idx[P] | hist | cur | off
     DevBuf k_cap, k_wsize, k_oldest, k_ubm, k_ops, k_order, k_opoff, k_outs, k_ev, k_evoff, k_ids;  // k_ids: cache ids grouped by replay team width
+    // the caches by model id (cache_keyed_kernels.hpp).  k_bound: the keys of the current store are registry rows (set by
+    // mmp_caches_load_keyed_k; dropped by mmp_caches_load_keyed and mmp_model_ids_load).  k_slots: the deque slots of the current
+    // store, off[k_caches].  evid_*: the eviction record of the last mmp_cache_replay_k, as bytes — a retirement cannot change it.
+    bool k_bound = false;
+    int32_t k_slots = 0;
+    std::vector<char> evid_bytes;
+    std::vector<int32_t> evid_off{0};
+    DevBuf k_inv, k_kstat, k_krow, k_len, k_goff, k_gbytes;  // inverse of k_order; status / row by caller op; the id gather's lengths, offsets, bytes
 
     // wire-format ingestion: per-pod id attributes and the hash tables the parsers probe
     std::vector<uint32_t> id_order_v;
@@ -1549,7 +1558,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->c_lu, &c->c_wt, &c->c_cap, &c->s_reqs, &c->s_outs, &c->s_extra, &c->s_a, &c->s_b,
                       &c->s_c, &c->s_d, &c->r_ps, &c->r_counts, &c->r_keys, &c->r_vals, &c->r_keys2, &c->r_vals2,
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
-                      &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
+                      &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->k_inv, &c->k_kstat, &c->k_krow, &c->k_len, &c->k_goff, &c->k_gbytes, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
                       &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu, &c->rf_refs, &c->vw_reqs, &c->vw_strs, &c->vw_soff, &c->vw_rows,
                       &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_rows_next, &c->vm_arena,
@@ -2285,12 +2294,27 @@ CommitDims commit_dims(const mmp_ctx *c)
 int ensure_columns(mmp_ctx *c, SnapBufs &B, int32_t T, int32_t Wc, int32_t W)
 {
     const size_t padded = (size_t)Wc * 64;
-    HIP_TRY(c, B.lru.ensure(padded * 8));
-    HIP_TRY(c, B.rem.ensure(padded * 8));
-    HIP_TRY(c, B.cnt.ensure(padded * 4));
-    HIP_TRY(c, B.rpm.ensure(padded * 4));
-    HIP_TRY(c, B.orig.ensure(padded * 4));
-    HIP_TRY(c, B.pos_of.ensure((size_t)W * 64 * 4));
+    // A column that was (re)allocated starts as zeros.  A commit whose order is not total leaves one rank's slot of every column,
+    // and the loser's pos_of word, without a writer (scatter_pods_kernel returns on the second row of a rank), and the table
+    // kernels run on the columns before the host reads the flag and refuses with MMP_EORDER: what they find there must be an
+    // index inside the table — zero, or what an earlier commit of this context wrote — never what the allocator left behind.
+    bool fresh = false;
+    auto column = [&](DevBuf &b, size_t bytes) {
+        const size_t was = b.cap;
+        hipError_t e = b.ensure(bytes);
+        if (e == hipSuccess && b.cap != was) {
+            fresh = true;
+            e = hipMemsetAsync(b.p, 0, b.cap, c->stream);
+        }
+        return e;
+    };
+    HIP_TRY(c, column(B.lru, padded * 8));
+    HIP_TRY(c, column(B.rem, padded * 8));
+    HIP_TRY(c, column(B.cnt, padded * 4));
+    HIP_TRY(c, column(B.rpm, padded * 4));
+    HIP_TRY(c, column(B.orig, padded * 4));
+    HIP_TRY(c, column(B.pos_of, (size_t)W * 64 * 4));
+    if (fresh) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (rare: the columns only grow; whichever stream the commit builds on)
     HIP_TRY(c, B.elig.ensure((size_t)T * Wc * 8));
     HIP_TRY(c, B.elig_nors.ensure((size_t)T * Wc * 8));
     HIP_TRY(c, B.pref.ensure((size_t)T * Wc * 8));
@@ -4008,6 +4032,7 @@ try {
         std::lock_guard<std::shared_mutex> g(c->mu);  // the swap (the ownership rule at mmp_ctx::mid_hash)
         model_ids_publish(model_id_tab(c), P);
         c->have_model_ids = true;
+        c->k_bound = false;  // the keys of bound caches named rows of the replaced table: the contents stay, the binding goes
     }
     HIP_TRY(c, model_ids_retired_drain(c, P));  // request calls by model id that captured the replaced table
     return MMP_OK;
@@ -4593,22 +4618,40 @@ try {
     HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
     const dim3 block(kRetireBlock);
     const int32_t *old_off = ids ? c->mid_off.as<int32_t>() : nullptr;
+    // bound caches are carried along (cache_keyed_kernels.hpp); the cache calls hold batch_mu too, so the store stands still
+    const bool carry = c->k_bound && c->k_caches > 0 && c->k_slots > 0;
+    mmp_ctx::KeyedStore &KS = c->ks[c->ks_cur];
+    const CacheStore kstore{KS.off.as<int32_t>(), KS.lu.as<int64_t>(), KS.wt.as<int32_t>(), KS.key.as<int32_t>(), KS.n.as<int32_t>()};
+    int32_t *d_live_key = nullptr;
+    if (carry) {
+        HIP_TRY(c, c->k_len.ensure(4));
+        d_live_key = c->k_len.as<int32_t>();
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_live_key), INT32_MAX, 1, st));
+    }
     // 1. mark, and with the flag the lowest named row that is not empty; the triples and their scan
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, c->ret_rows.as<int32_t>(), n, c->models.as<mmp_model_row>(),
                        (flags & MMP_RETIRE_EMPTY_ONLY) ? 1 : 0, d_keep, d_word);
+    if (carry)  // the lowest named row that is the key of a live entry
+        hipLaunchKernelGGL(ckey_retire_check_kernel, dim3(div_up(c->k_slots, kRetireBlock)), block, 0, st, kstore, c->k_caches, c->k_slots, M0,
+                           d_keep, d_live_key);
     hipLaunchKernelGGL(retire_flags_kernel, dim3(div_up(M0 + 1, kRetireBlock)), block, 0, st, M0, d_keep, c->models.as<mmp_model_row>(), old_off, d_cnt);
     HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, RetireCount{0, 0, 0}, (size_t)M0 + 1, RetirePlus(), st));
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     int32_t word[2] = {INT32_MAX, INT32_MAX};
     RetireCount tot{};
+    int32_t live_key = INT32_MAX;
     HIP_TRY(c, hipMemcpyAsync(word, d_word, 4, hipMemcpyDeviceToHost, st));
+    if (carry) HIP_TRY(c, hipMemcpyAsync(&live_key, d_live_key, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, copy_sync(c, &tot, d_pos + M0, sizeof tot, hipMemcpyDeviceToHost));
     kt_collect(c);
     const double mark_ms = c->last_kernel_ms;
     if (word[0] != INT32_MAX)
         return fail(c, MMP_EINVAL, "mmp_models_retire: row %d is not empty (registered again since its deletion?); nothing was retired", word[0]);
+    if (live_key != INT32_MAX)
+        return fail(c, MMP_EINVAL, "mmp_models_retire: row %d is the key of a live cache entry (remove the entry first); nothing was retired",
+                    live_key);
     const int32_t M1 = tot.row, B1 = tot.bytes, E1 = tot.ents;
     // 2. the compacted registry, id arena and table, beside the published ones
     DevBuf nm, np, nt, nb, no;
@@ -4699,6 +4742,12 @@ try {
         ot.release();
         c->side[0].rmodels_ok = c->side[1].rmodels_ok = false;
         split_reset(c);
+        if (carry) {  // the keys of the bound caches follow their rows, in place (d_remap: the M0 words retire_move_kernel wrote)
+            hipLaunchKernelGGL(ckey_retire_remap_kernel, dim3(div_up(c->k_slots, kRetireBlock)), block, 0, st, kstore, c->k_caches, c->k_slots, M0,
+                               d_remap);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(st));
+        }
         if (const int rr = rebuild_resolved(c)) return rr;
     }
     if (remap_out) memcpy(remap_out, remap.data(), (size_t)M0 * 4);
@@ -8776,18 +8825,23 @@ try {
 
 /* ---- stateful keyed caches (a12 + a13) ------------------------------------- */
 
-int mmp_caches_load_keyed(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used,
-                          const int32_t *weight, const int32_t *key, const int64_t *capacity, const mmp_ubm_state *ubm)
-try {
-    if (!c || n_caches < 0 || !seg_off || (n_caches > 0 && !capacity)) return fail(c, MMP_EINVAL, "mmp_caches_load_keyed: bad argument");
-    if (seg_off[0] != 0) return fail(c, MMP_EINVAL, "mmp_caches_load_keyed: seg_off[0] must be 0");
+namespace {
+// what both loads refuse of the segments; E = seg_off[n_caches]
+int caches_keyed_segs_bad(mmp_ctx *c, const char *fn, int32_t n_caches, const int32_t *seg_off, const int64_t *capacity)
+{
+    if (!c || n_caches < 0 || !seg_off || (n_caches > 0 && !capacity)) return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    if (seg_off[0] != 0) return fail(c, MMP_EINVAL, "%s: seg_off[0] must be 0", fn);
     for (int32_t i = 0; i < n_caches; i++)
-        if (seg_off[i + 1] < seg_off[i]) return fail(c, MMP_EINVAL, "mmp_caches_load_keyed: seg_off not monotone at %d", i);
+        if (seg_off[i + 1] < seg_off[i]) return fail(c, MMP_EINVAL, "%s: seg_off not monotone at %d", fn, i);
+    return MMP_OK;
+}
+
+// The load itself, shared by mmp_caches_load_keyed and mmp_caches_load_keyed_k (bound: the keys are registry rows the device
+// resolved).  The caller holds batch_mu and the state lock, has set the device and has refused what it refuses.
+int caches_keyed_store(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used, const int32_t *weight,
+                       const int32_t *key, const int64_t *capacity, const mmp_ubm_state *ubm, bool bound)
+{
     const int32_t E = seg_off[n_caches];
-    if (E > 0 && (!last_used || !weight || !key)) return fail(c, MMP_EINVAL, "mmp_caches_load_keyed: null entry arrays");
-    std::lock_guard<std::mutex> gb(c->batch_mu);
-    std::lock_guard<std::shared_mutex> g(c->mu);
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     mmp_ctx::KeyedStore &K = c->ks[c->ks_cur];
     HIP_TRY(c, K.off.ensure((size_t)(n_caches + 1) * 4));
@@ -8827,27 +8881,154 @@ try {
         HIP_TRY(c, copy_sync(c, c->k_ubm.p, us.data(), (size_t)n_caches * sizeof(mmp_ubm_state), hipMemcpyHostToDevice));
     }
     c->k_caches = n_caches;
+    c->k_slots = E;
+    c->k_bound = bound;
+    c->evid_bytes.clear();  // the eviction record of a keyed replay ends with the store it was made on
+    c->evid_off.assign(1, 0);
     return MMP_OK;
-} MMP_CATCH(c, "mmp_caches_load_keyed")
+}
 
-int mmp_cache_replay(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, int64_t now, mmp_cache_op_out *outs,
-                     int32_t *evicted_keys, int32_t max_evicted, int32_t *n_evicted_slots)
+// THE ID GATHER, shared by the eviction record and mmp_cache_read_k (cache_keyed_kernels.hpp), in two steps around the one
+// read-back of the sizes.  ckey_gather_sizes, inside the caller's bracket: the id lengths of the n row words at d_rows and their
+// exclusive scan, n + 1 offsets into c->k_goff.  ckey_gather_bytes, once the caller has the total on the host: the bytes into
+// c->k_gbytes and on into `out`, in a bracket of its own.  The caller owns batch_mu and has seen the id space guard pass.
+int ckey_gather_sizes(mmp_ctx *c, const int32_t *d_rows, int32_t n)
+{
+    hipStream_t st = c->stream;
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, c->k_len.as<int32_t>(), c->k_goff.as<int32_t>(), 0, (size_t)n + 1, rocprim::plus<int32_t>(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    hipLaunchKernelGGL(ckey_len_kernel, dim3(div_up(n + 1, kIdTabBlock)), dim3(kIdTabBlock), 0, st, d_rows, n, c->mid_n, c->mid_off.as<int32_t>(),
+                       c->k_len.as<int32_t>());
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, c->k_len.as<int32_t>(), c->k_goff.as<int32_t>(), 0, (size_t)n + 1,
+                                       rocprim::plus<int32_t>(), st));
+    return MMP_OK;
+}
+int ckey_gather_room(mmp_ctx *c, int32_t n)
+{
+    HIP_TRY(c, c->k_len.ensure(((size_t)n + 1) * 4));
+    HIP_TRY(c, c->k_goff.ensure(((size_t)n + 1) * 4));
+    return MMP_OK;
+}
+int ckey_gather_bytes(mmp_ctx *c, const int32_t *d_rows, int32_t n, int32_t total, char *out)
+{
+    if (total <= 0) return MMP_OK;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->k_gbytes.ensure((size_t)total));
+    const double earlier = c->last_kernel_ms;
+    KT_BEGIN(c, st);
+    hipLaunchKernelGGL(ckey_gather_kernel, dim3(div_up(n, kIdTabBlock / kGatherTeam)), dim3(kIdTabBlock), 0, st, d_rows, n, c->mid_n,
+                       c->mid_off.as<int32_t>(), c->mid_bytes.as<char>(), c->k_goff.as<int32_t>(), c->k_gbytes.as<char>());
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, copy_sync(c, out, c->k_gbytes.p, (size_t)total, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    kt_add(c, earlier);
+    return MMP_OK;
+}
+
+// the caches are bound and the id table covers the registry (what every _k cache call answers MMP_ESTATE to)
+int caches_bound_guard(mmp_ctx *c, const char *fn)
+{
+    if (const int rc = model_id_space_guard(c, fn)) return rc;
+    if (!c->k_bound) return fail(c, MMP_ESTATE, "%s: the caches are not bound to model ids (mmp_caches_load_keyed_k)", fn);
+    return MMP_OK;
+}
+
+// what mmp_cache_replay_k adds to the replay
+struct ReplayKeyed {
+    const char *keys;
+    const int32_t *key_off;
+    int32_t *status_out, *row_out;
+    char *id_bytes_out;
+    int32_t max_id_bytes;
+    int32_t *id_off_out, *n_id_bytes_out;
+};
+}  // namespace
+
+int mmp_caches_load_keyed(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used,
+                          const int32_t *weight, const int32_t *key, const int64_t *capacity, const mmp_ubm_state *ubm)
 try {
-    if (!c || n_ops < 0 || max_evicted < 0 || (n_ops > 0 && (!ops || !outs)) || (max_evicted > 0 && !evicted_keys) ||
-        !n_evicted_slots)
-        return fail(c, MMP_EINVAL, "mmp_cache_replay: bad argument");
+    if (const int rc = caches_keyed_segs_bad(c, "mmp_caches_load_keyed", n_caches, seg_off, capacity)) return rc;
+    const int32_t E = seg_off[n_caches];
+    if (E > 0 && (!last_used || !weight || !key)) return fail(c, MMP_EINVAL, "mmp_caches_load_keyed: null entry arrays");
     std::lock_guard<std::mutex> gb(c->batch_mu);
     std::lock_guard<std::shared_mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    return caches_keyed_store(c, n_caches, seg_off, last_used, weight, key, capacity, ubm, false);
+} MMP_CATCH(c, "mmp_caches_load_keyed")
+
+int mmp_caches_load_keyed_k(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, const int64_t *last_used, const int32_t *weight,
+                            const char *keys, const int32_t *key_off, const uint8_t *is_unloadbuf, const int64_t *capacity,
+                            const mmp_ubm_state *ubm, int32_t *key_row_out)
+try {
+    const char *fn = "mmp_caches_load_keyed_k";
+    if (const int rc = caches_keyed_segs_bad(c, fn, n_caches, seg_off, capacity)) return rc;
+    const int32_t E = seg_off[n_caches];
+    if ((keys == nullptr) != (key_off == nullptr) || (E > 0 && (!last_used || !weight || !key_off)))
+        return fail(c, MMP_EINVAL, "%s: null entry arrays", fn);
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = model_id_space_guard(c, fn)) return rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> rows((size_t)std::max(E, 1), 0), krel;
+    if (E > 0) {
+        if (const int rc = stage_strings(c, fn, "key ", keys, key_off, E, c->ida_bytes, c->ida_off, krel)) return rc;
+        HIP_TRY(c, c->k_krow.ensure((size_t)E * 4));
+        HIP_TRY(c, c->k_len.ensure(4));
+        if (is_unloadbuf) {
+            HIP_TRY(c, c->k_kstat.ensure((size_t)E));
+            HIP_TRY(c, hipMemcpyAsync(c->k_kstat.p, is_unloadbuf, (size_t)E, hipMemcpyHostToDevice, st));
+        }
+        int32_t *d_word = c->k_len.as<int32_t>();
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 1, st));
+        const CkeyEntriesArgs A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), E, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                                is_unloadbuf ? c->k_kstat.as<uint8_t>() : nullptr, c->k_krow.as<int32_t>(), d_word};
+        KT_BEGIN(c, st);
+        hipLaunchKernelGGL(ckey_entries_kernel, dim3(div_up(E, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        int32_t lowest = INT32_MAX;
+        HIP_TRY(c, hipMemcpyAsync(&lowest, d_word, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, copy_sync(c, rows.data(), c->k_krow.p, (size_t)E * 4, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        if (lowest != INT32_MAX) return fail(c, MMP_EINVAL, "%s: entry %d names an id the table does not know; nothing was loaded", fn, lowest);
+    }
+    const double resolve_ms = c->last_kernel_ms;
+    if (const int rc = caches_keyed_store(c, n_caches, seg_off, last_used, weight, rows.data(), capacity, ubm, true)) return rc;
+    if (c->prof) c->last_kernel_ms = E > 0 ? resolve_ms : -1;
+    if (key_row_out && E > 0) memcpy(key_row_out, rows.data(), (size_t)E * 4);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_caches_load_keyed_k")
+
+namespace {
+// THE REPLAY, by key (mmp_cache_replay: kx == nullptr) or by model id.  The caller holds batch_mu and the state lock and has
+// refused NULL buffers.  Nothing of the store changes before the last step that refuses.
+int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int32_t n_ops, int64_t now, mmp_cache_op_out *outs,
+                       int32_t *evicted_keys, int32_t max_evicted, int32_t *n_evicted_slots, const ReplayKeyed *kx)
+{
     const int32_t NC = c->k_caches;
     if (NC <= 0 && n_ops > 0) return fail(c, MMP_ESTATE, "no keyed caches loaded");
     *n_evicted_slots = 0;
-    if (n_ops == 0) return MMP_OK;
+    if (n_ops == 0) {
+        if (kx) {  // a valid call: its record is the empty one
+            c->evid_bytes.clear();
+            c->evid_off.assign(1, 0);
+            *kx->n_id_bytes_out = 0;
+            if (kx->id_off_out) kx->id_off_out[0] = 0;
+            if (c->prof) c->last_kernel_ms = -1;
+        }
+        return MMP_OK;
+    }
     // group the operations by cache (stable) and size the new layout: every insert may add a slot
     std::vector<int32_t> cnt(NC + 1, 0), ins(NC, 0);
     for (int32_t i = 0; i < n_ops; i++) {
         const mmp_cache_op &o = ops[i];
-        if (o.cache < 0 || o.cache >= NC) return fail(c, MMP_EINVAL, "mmp_cache_replay: op %d names cache %d", i, o.cache);
-        if (o.op < 0 || o.op > MMP_COP_UBM_INSERT_FAILED_PLACEHOLDER) return fail(c, MMP_EINVAL, "mmp_cache_replay: op %d has code %d", i, o.op);
+        if (o.cache < 0 || o.cache >= NC) return fail(c, MMP_EINVAL, "%s: op %d names cache %d", fn, i, o.cache);
+        if (o.op < 0 || o.op > MMP_COP_UBM_INSERT_FAILED_PLACEHOLDER) return fail(c, MMP_EINVAL, "%s: op %d has code %d", fn, i, o.op);
+        if (kx && (o.reserved < 0 || o.reserved > MMP_COPK_RAW_KEY || (o.reserved == MMP_COPK_RAW_KEY && o.key != MMP_UNLOADBUF_KEY)))
+            return fail(c, MMP_EINVAL, "%s: op %d has reserved %d with key %d", fn, i, o.reserved, o.key);
         cnt[o.cache + 1]++;
         if (o.op == MMP_COP_PUT_IF_ABSENT || o.op == MMP_COP_UBM_INSERT_NEW_ENTRY || o.op == MMP_COP_UBM_INSERT_FAILED_PLACEHOLDER)
             ins[o.cache]++;
@@ -8868,8 +9049,10 @@ try {
             tiles[w] = std::max(tiles[w], slots + 1);
         }
     }
-    if (tile > kCacheTile) return fail(c, MMP_EINVAL, "mmp_cache_replay: a cache needs %d deque slots, the tile holds %d", tile, kCacheTile);
-    if (ev_off[NC] > max_evicted) return fail(c, MMP_EINVAL, "mmp_cache_replay: evicted_keys needs room for %d keys", ev_off[NC]);
+    if (tile > kCacheTile) return fail(c, MMP_EINVAL, "%s: a cache needs %d deque slots, the tile holds %d", fn, tile, kCacheTile);
+    if (ev_off[NC] > max_evicted) return fail(c, MMP_EINVAL, "%s: evicted_keys needs room for %d keys", fn, ev_off[NC]);
+    if (kx)
+        if (const int rc = check_offsets(c, fn, "key ", kx->key_off, n_ops)) return rc;
     std::vector<int32_t> order(n_ops), fill(op_off.begin(), op_off.end() - 1);
     for (int32_t i = 0; i < n_ops; i++) order[fill[ops[i].cache]++] = i;
     std::vector<mmp_cache_op> grouped((size_t)n_ops);  // the kernel reads an operation with ONE load (no index in between)
@@ -8877,6 +9060,19 @@ try {
 
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
+    const int32_t n_slots = ev_off[NC];
+    std::vector<int32_t> inv, krel;  // (what the uploads below are from: they live to the end)
+    if (kx) {
+        // the keys go up as the caller gave them, in one copy; the resolver scatters through the inverse of `order`
+        inv.resize((size_t)n_ops);
+        for (int32_t q = 0; q < n_ops; q++) inv[order[q]] = q;
+        if (const int rc = stage_strings(c, fn, "key ", kx->keys, kx->key_off, n_ops, c->ida_bytes, c->ida_off, krel)) return rc;
+        HIP_TRY(c, c->k_inv.ensure((size_t)n_ops * 4));
+        HIP_TRY(c, c->k_kstat.ensure((size_t)n_ops * 4));
+        HIP_TRY(c, c->k_krow.ensure((size_t)n_ops * 4));
+        if (const int rc = ckey_gather_room(c, n_slots)) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->k_inv.p, inv.data(), (size_t)n_ops * 4, hipMemcpyHostToDevice, st));
+    }
     mmp_ctx::KeyedStore &S = c->ks[c->ks_cur], &D = c->ks[1 - c->ks_cur];
     const int32_t Enew = new_off[NC];
     HIP_TRY(c, D.off.ensure((size_t)(NC + 1) * 4));
@@ -8919,7 +9115,15 @@ try {
         HIP_TRY(c, hipMemcpyAsync(c->k_ids.p, all.data(), (size_t)NC * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipStreamSynchronize(st));  // `all` leaves scope (the other uploads above are from vectors that live to the end)
     }
+    if (kx && n_slots)  // a slot no op used holds -1
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->k_ev.as<int32_t>()), -1, (size_t)n_slots, st));
     KT_BEGIN(c, st);
+    if (kx) {
+        // (the staged copy keeps keyed_resolve_kernel's contract: the buffer is an allocation of its own with 16 bytes behind the keys)
+        const CkeyOpsArgs K{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n_ops, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                            c->k_inv.as<int32_t>(), c->k_ops.as<mmp_cache_op>(), c->k_kstat.as<int32_t>(), c->k_krow.as<int32_t>()};
+        hipLaunchKernelGGL(ckey_ops_kernel, dim3(div_up(n_ops, kIdTabBlock)), dim3(kIdTabBlock), 0, st, K);
+    }
     const int32_t *d_ids = c->k_ids.as<int32_t>();
     for (int w = 0; w < 3; w++)
         if ((int32_t)ids[w].size() == NC) d_ids = nullptr;  // one width for every cache: the list is the identity
@@ -8938,17 +9142,129 @@ try {
         hipLaunchKernelGGL(cache_replay_kernel<64>, dim3((int)ids[2].size()), dim3(64), (size_t)tiles[2] * 24, st, A,
                            d_ids ? d_ids + ids[0].size() + ids[1].size() : nullptr, (int32_t)ids[2].size());
     }
+    if (kx && n_slots)  // the lengths of the victims' ids and their scan, in the same span
+        if (const int rc = ckey_gather_sizes(c, c->k_ev.as<int32_t>(), n_slots)) return rc;
     KT_END(c, st);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(outs, c->k_outs.p, (size_t)n_ops * sizeof(mmp_cache_op_out), hipMemcpyDeviceToHost, st));
     if (ev_off[NC]) HIP_TRY(c, hipMemcpyAsync(evicted_keys, c->k_ev.p, (size_t)ev_off[NC] * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(c->k_n.data(), D.n.p, (size_t)NC * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> id_off((size_t)n_slots + 1, 0);
+    if (kx) {
+        if (kx->status_out) HIP_TRY(c, hipMemcpyAsync(kx->status_out, c->k_kstat.p, (size_t)n_ops * 4, hipMemcpyDeviceToHost, st));
+        if (kx->row_out) HIP_TRY(c, hipMemcpyAsync(kx->row_out, c->k_krow.p, (size_t)n_ops * 4, hipMemcpyDeviceToHost, st));
+        if (n_slots) HIP_TRY(c, hipMemcpyAsync(id_off.data(), c->k_goff.p, ((size_t)n_slots + 1) * 4, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
+    // the replay is applied from here on, whatever becomes of the record: it is stateful and cannot be asked twice
     c->ks_cur = 1 - c->ks_cur;
+    c->k_slots = Enew;
     *n_evicted_slots = ev_off[NC];
+    if (!kx) return MMP_OK;
+    // the eviction record: the context keeps the bytes (a retirement between this call and mmp_cache_evicted_ids cannot change
+    // them), the caller gets them when they fit
+    const int32_t need = id_off[n_slots];
+    c->evid_off.assign(1, 0);
+    c->evid_bytes.assign((size_t)need, 0);
+    if (const int rc = ckey_gather_bytes(c, c->k_ev.as<int32_t>(), n_slots, need, c->evid_bytes.data())) {
+        c->evid_bytes.clear();
+        return rc;
+    }
+    c->evid_off = id_off;
+    *kx->n_id_bytes_out = need;
+    if (kx->id_off_out) memcpy(kx->id_off_out, id_off.data(), ((size_t)n_slots + 1) * 4);
+    if (need > 0 && kx->max_id_bytes >= need) memcpy(kx->id_bytes_out, c->evid_bytes.data(), (size_t)need);
     return MMP_OK;
+}
+}  // namespace
+
+int mmp_cache_replay(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, int64_t now, mmp_cache_op_out *outs,
+                     int32_t *evicted_keys, int32_t max_evicted, int32_t *n_evicted_slots)
+try {
+    if (!c || n_ops < 0 || max_evicted < 0 || (n_ops > 0 && (!ops || !outs)) || (max_evicted > 0 && !evicted_keys) ||
+        !n_evicted_slots)
+        return fail(c, MMP_EINVAL, "mmp_cache_replay: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    return cache_replay_drive(c, "mmp_cache_replay", ops, n_ops, now, outs, evicted_keys, max_evicted, n_evicted_slots, nullptr);
 } MMP_CATCH(c, "mmp_cache_replay")
+
+int mmp_cache_replay_k(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, const char *keys, const int32_t *key_off, int64_t now,
+                       int32_t *key_status_out, int32_t *key_row_out, mmp_cache_op_out *outs, int32_t *evicted_rows, int32_t max_evicted,
+                       int32_t *n_evicted_slots, char *ev_id_bytes_out, int32_t max_id_bytes, int32_t *ev_id_off_out, int32_t *n_id_bytes_out)
+try {
+    if (!c || n_ops < 0 || max_evicted < 0 || (n_ops > 0 && (!ops || !outs)) || (max_evicted > 0 && !evicted_rows) || !n_evicted_slots ||
+        !n_id_bytes_out || max_id_bytes < 0 || (max_id_bytes > 0 && !ev_id_bytes_out) || (keys == nullptr) != (key_off == nullptr) ||
+        (n_ops > 0 && !key_off))
+        return fail(c, MMP_EINVAL, "mmp_cache_replay_k: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, "mmp_cache_replay_k")) return rc;
+    const ReplayKeyed kx{keys, key_off, key_status_out, key_row_out, ev_id_bytes_out, max_id_bytes, ev_id_off_out, n_id_bytes_out};
+    return cache_replay_drive(c, "mmp_cache_replay_k", ops, n_ops, now, outs, evicted_rows, max_evicted, n_evicted_slots, &kx);
+} MMP_CATCH(c, "mmp_cache_replay_k")
+
+int mmp_cache_evicted_ids(mmp_ctx *c, char *bytes_out, int32_t max_bytes, int32_t *off_out, int32_t *n_slots_out, int32_t *n_bytes_out)
+try {
+    if (!c || !n_slots_out || !n_bytes_out || max_bytes < 0 || (max_bytes > 0 && !bytes_out))
+        return fail(c, MMP_EINVAL, "mmp_cache_evicted_ids: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, "mmp_cache_evicted_ids")) return rc;
+    const int32_t ns = (int32_t)c->evid_off.size() - 1, nb = c->evid_off[ns];
+    *n_slots_out = ns;
+    *n_bytes_out = nb;
+    if (off_out) memcpy(off_out, c->evid_off.data(), ((size_t)ns + 1) * 4);
+    if (nb > 0 && max_bytes >= nb) memcpy(bytes_out, c->evid_bytes.data(), (size_t)nb);
+    if (c->prof) c->last_kernel_ms = -1;  // no kernel: the record is bytes the context holds
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_cache_evicted_ids")
+
+int mmp_cache_read_k(mmp_ctx *c, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *row_out,
+                     char *id_bytes_out, int32_t max_id_bytes, int32_t *id_off_out, int32_t *n_out, int32_t *n_id_bytes_out,
+                     int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm)
+try {
+    if (!c || !n_out || !n_id_bytes_out || max_entries < 0 || max_id_bytes < 0 || (max_id_bytes > 0 && !id_bytes_out))
+        return fail(c, MMP_EINVAL, "mmp_cache_read_k: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, "mmp_cache_read_k")) return rc;
+    if (cache < 0 || cache >= c->k_caches) return fail(c, MMP_EINVAL, "mmp_cache_read_k: cache %d out of range", cache);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    mmp_ctx::KeyedStore &K = c->ks[c->ks_cur];
+    int32_t off = 0;
+    HIP_TRY(c, copy_sync(c, &off, K.off.as<int32_t>() + cache, 4, hipMemcpyDeviceToHost));
+    const int32_t n = c->k_n[cache];
+    *n_out = n;
+    const int32_t m = std::min(n, max_entries);
+    std::vector<int32_t> id_off((size_t)m + 1, 0);
+    const int32_t *d_rows = K.key.as<int32_t>() + off;
+    if (c->prof) c->last_kernel_ms = -1;
+    if (m > 0) {
+        if (const int rc = ckey_gather_room(c, m)) return rc;
+        KT_BEGIN(c, st);
+        if (const int rc = ckey_gather_sizes(c, d_rows, m)) return rc;
+        KT_END(c, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, copy_sync(c, id_off.data(), c->k_goff.p, ((size_t)m + 1) * 4, hipMemcpyDeviceToHost));
+        kt_collect(c);
+        if (last_used) HIP_TRY(c, copy_sync(c, last_used, K.lu.as<int64_t>() + off, (size_t)m * 8, hipMemcpyDeviceToHost));
+        if (weight) HIP_TRY(c, copy_sync(c, weight, K.wt.as<int32_t>() + off, (size_t)m * 4, hipMemcpyDeviceToHost));
+        if (row_out) HIP_TRY(c, copy_sync(c, row_out, d_rows, (size_t)m * 4, hipMemcpyDeviceToHost));
+    }
+    const int32_t need = id_off[m];
+    *n_id_bytes_out = need;
+    if (id_off_out) memcpy(id_off_out, id_off.data(), ((size_t)m + 1) * 4);
+    if (need > 0 && max_id_bytes >= need)
+        if (const int rc = ckey_gather_bytes(c, d_rows, m, need, id_bytes_out)) return rc;
+    if (capacity) HIP_TRY(c, copy_sync(c, capacity, c->k_cap.as<int64_t>() + cache, 8, hipMemcpyDeviceToHost));
+    if (weighted_size) HIP_TRY(c, copy_sync(c, weighted_size, c->k_wsize.as<int64_t>() + cache, 8, hipMemcpyDeviceToHost));
+    if (ubm) HIP_TRY(c, copy_sync(c, ubm, c->k_ubm.as<mmp_ubm_state>() + cache, sizeof(mmp_ubm_state), hipMemcpyDeviceToHost));
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_cache_read_k")
 
 int mmp_cache_read(mmp_ctx *c, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *key,
                    int32_t *n_out, int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm)

@@ -982,6 +982,101 @@ class Solver:
         return {"last_used": lu[:m], "weight": wt[:m], "key": key[:m], "capacity": cap.value,
                 "weighted_size": ws.value, "ubm": ubm[0]}
 
+    # ---- the stateful caches by model id: the key of an entry is the registry row its id names ----
+    @staticmethod
+    def _spans(raw, off, n):
+        return [raw[off[i]:off[i + 1]] for i in range(n)]
+
+    def load_caches_keyed_k(self, seg_off, last_used, weight, keys, capacity, ubm=None, is_unloadbuf=None, key_off=None, blob=None,
+                            want_rows=True):
+        """mmp_caches_load_keyed_k: keys[e] (bytes/str) is the model id of entry e; is_unloadbuf[e] marks the manager's
+        pseudo-entry (its key is not read).  key_off / blob: raw offsets and bytes in place of `keys`.  Returns the entries' rows."""
+        from ._lib import UBM_STATE
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int32)
+        last_used = np.ascontiguousarray(last_used, dtype=np.int64)
+        weight = np.ascontiguousarray(weight, dtype=np.int32)
+        capacity = np.ascontiguousarray(capacity, dtype=np.int64)
+        ubm = None if ubm is None else np.ascontiguousarray(ubm, dtype=UBM_STATE)
+        if blob is None:
+            blob, off = self.pack_keys(keys)
+        if key_off is not None:
+            off = np.ascontiguousarray(key_off, dtype=np.int32)
+        isu = None if is_unloadbuf is None else np.ascontiguousarray(is_unloadbuf, dtype=np.uint8)
+        E = int(seg_off[-1])
+        rows = np.full(max(E, 1), -1, np.int32)
+        self._ck(self.lib.mmp_caches_load_keyed_k(self.h, len(capacity), ptr(seg_off), ptr(last_used) if len(last_used) else None,
+                                                  ptr(weight) if len(weight) else None, blob, ptr(off), ptr(isu), ptr(capacity),
+                                                  ptr(ubm), ptr(rows) if want_rows else None))
+        self._kcache_slots = E
+        return rows[:E]
+
+    def cache_replay_k_raw(self, ops, keys, now, max_id_bytes, key_off=None, blob=None, fill=0, max_evicted=None):
+        """mmp_cache_replay_k with a caller-sized id buffer.  Returns a dict: outs, evicted_rows, status, rows, id_off, id_bytes (the
+        raw buffer, `fill` where nothing was written), need."""
+        from ._lib import CACHE_OP, CACHE_OP_OUT
+        ops = np.ascontiguousarray(ops, dtype=CACHE_OP)
+        n = len(ops)
+        if blob is None:
+            blob, off = self.pack_keys(keys)
+        if key_off is not None:
+            off = np.ascontiguousarray(key_off, dtype=np.int32)
+        outs = np.zeros(n, dtype=CACHE_OP_OUT)
+        slots = getattr(self, "_kcache_slots", 0) + n if max_evicted is None else max_evicted
+        ev = np.full(max(slots, 1), fill, np.int32)
+        status = np.full(max(n, 1), fill, np.int32)
+        rows = np.full(max(n, 1), fill, np.int32)
+        id_off = np.full(max(slots, 0) + 1, fill, np.int32)
+        buf = np.full(max(max_id_bytes, 1), fill, np.uint8)
+        used, need = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mmp_cache_replay_k(self.h, ptr(ops) if n else None, n, blob, ptr(off), int(now), ptr(status), ptr(rows),
+                                             ptr(outs) if n else None, ptr(ev), slots, C.byref(used), ptr(buf) if max_id_bytes else None,
+                                             int(max_id_bytes), ptr(id_off), C.byref(need)))
+        if max_evicted is None:
+            self._kcache_slots = slots
+        u = used.value
+        return {"outs": outs, "evicted_rows": ev[:u], "status": status[:n], "rows": rows[:n], "id_off": id_off[: u + 1],
+                "id_bytes": buf[:max_id_bytes], "need": need.value}
+
+    def cache_replay_k(self, ops, keys, now, id_bytes_hint: int = 4096):
+        """Apply cache operations by model id (mmp_cache_replay_k).  Returns (outs, evicted_rows, evicted_ids, status, rows):
+        evicted_ids[s] is the id (bytes) of evicted_rows[s], b"" for a slot no op used.  The id buffer is sized by a hint; when
+        it was short the ids come from the record the context keeps (mmp_cache_evicted_ids) — the replay itself ran once."""
+        r = self.cache_replay_k_raw(ops, keys, now, id_bytes_hint)
+        u = len(r["evicted_rows"])
+        if r["need"] <= id_bytes_hint:
+            ids = self._spans(r["id_bytes"][: r["need"]].tobytes(), r["id_off"], u)
+        else:
+            ids = self.cache_evicted_ids()
+        return r["outs"], r["evicted_rows"], ids, r["status"], r["rows"]
+
+    def cache_evicted_ids(self):
+        """The ids the last cache_replay_k evicted, one per eviction slot (mmp_cache_evicted_ids, sizes then list)."""
+        ns, nb = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mmp_cache_evicted_ids(self.h, None, 0, None, C.byref(ns), C.byref(nb)))
+        off = np.zeros(ns.value + 1, np.int32)
+        buf = np.zeros(max(nb.value, 1), np.uint8)
+        self._ck(self.lib.mmp_cache_evicted_ids(self.h, ptr(buf), nb.value, ptr(off), C.byref(ns), C.byref(nb)))
+        return self._spans(buf.tobytes(), off, ns.value)
+
+    def cache_read_k(self, cache: int, max_entries: int = 4096):
+        """mmp_cache_read plus the entries' ids (mmp_cache_read_k): "row" are the keys, "ids" their model ids (b"" for the
+        pseudo-entry, whose row is UNLOADBUF_KEY)."""
+        from ._lib import UBM_STATE
+        lu = np.zeros(max_entries, np.int64)
+        wt = np.zeros(max_entries, np.int32)
+        row = np.zeros(max_entries, np.int32)
+        off = np.zeros(max_entries + 1, np.int32)
+        n, nb, cap, ws = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        ubm = np.zeros(1, dtype=UBM_STATE)
+        self._ck(self.lib.mmp_cache_read_k(self.h, int(cache), max_entries, None, None, None, None, 0, None, C.byref(n), C.byref(nb),
+                                           None, None, None))
+        buf = np.zeros(max(nb.value, 1), np.uint8)
+        self._ck(self.lib.mmp_cache_read_k(self.h, int(cache), max_entries, ptr(lu), ptr(wt), ptr(row), ptr(buf), nb.value, ptr(off),
+                                           C.byref(n), C.byref(nb), C.byref(cap), C.byref(ws), ptr(ubm)))
+        m = min(n.value, max_entries)
+        return {"last_used": lu[:m], "weight": wt[:m], "row": row[:m], "ids": self._spans(buf.tobytes(), off, m),
+                "capacity": cap.value, "weighted_size": ws.value, "ubm": ubm[0]}
+
     def gates(self, reqs, excl_pod, excl_time, explicit_pool, now, in_use_failure_expiry_ms=450_000) -> np.ndarray:
         from ._lib import GATE_OUT, GATE_REQ
         reqs = np.ascontiguousarray(reqs, dtype=GATE_REQ)
