@@ -10,7 +10,8 @@ tests/golden/ref_gate_edges.npz: the guard cases at the edges of their value dom
 tests/golden/ref_place_edges.npz: the load-target cases at the edges of theirs (place_edge_vectors below).
 tests/golden/ref_rebalance_edges.npz: the rate task, the janitor's scale-down and the reaper's proactive loads at the edges of theirs
 (rebalance_edge_vectors below).
-usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges | --rebalance-edges | --serve-edges]"""
+tests/golden/ref_type_edges.npz: TypeConstraintManager's static computation at the edges of its value domain (type_edge_vectors below).
+usage: python oracle/ref_harness/make_ref_vectors.py [--gate-edges | --place-edges | --rebalance-edges | --serve-edges | --type-edges]"""
 import os
 import subprocess
 import sys
@@ -434,9 +435,134 @@ def serve_edge_vectors():
     print(f"wrote {SERVE_EDGE_OUT}: {os.path.getsize(SERVE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases, {n_rows} rows, {n_pairs} pairs")
 
 
+TYPE_EDGE_OUT = os.environ.get("MMP_REF_TYPE_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_type_edges.npz")
+
+
+def type_edge_vectors():
+    """tests/golden/ref_type_edges.npz: TypeConstraintManager's static computation on rf.type_edge_cases() (tests/ref_type_edges.py).
+    Refused: a pair the reference answers alike in the field it is there for (a pair marked alike: one it answers differently there), a case or a
+    tier without what it is there for — all on the evidence of the inputs and the reference's own output."""
+    import time
+    from tests import ref_type_edges as te
+    out, names, metas, not_pinned = {}, [], {}, []
+    seen = {t: dict(cases=0, rows=0, pairs=0, what=set()) for t in te.TYPE_EDGE_TIERS}
+    slowest = (0.0, None)
+    for name, fleet, ids, pod_bits, req_bits, pref_bits, meta in rf.type_edge_cases():
+        tier, P, T = meta["tier"], fleet.n_pods, len(req_bits)
+        W = (P + 63) // 64
+        blob = rf.input_blob(fleet, ids, types=(pod_bits, req_bits, pref_bits))
+        t0 = time.time()
+        rows, pod_part, part_types, part_stats, order, tstats = run(blob, 0, 0, types=(T, P))
+        slowest = max(slowest, (time.time() - t0, name))
+        out[f"{name}/rows"], out[f"{name}/pod_part"], out[f"{name}/part_stats"] = rows, pod_part, part_stats
+        out[f"{name}/part_types_len"] = np.array([len(x) for x in part_types], np.int32)
+        out[f"{name}/part_types"] = np.concatenate(part_types) if part_types else np.zeros(0, np.int64)
+        out[f"{name}/order"], out[f"{name}/tstats"] = order, tstats
+        out[f"{name}/pairs"] = np.array([f"{k}:{a}:{b}:{w}:{f}" for k, a, b, w, f in meta["pairs"]])
+        out[f"{name}/digest"] = np.frombuffer(rf.digest(blob).encode(), np.uint8)
+        names.append(name)
+        metas[name] = meta
+        st = seen[tier]
+        st["cases"], st["rows"], st["pairs"] = st["cases"] + 1, st["rows"] + T + 1, st["pairs"] + len(meta["pairs"])
+        for kind, a, b, what, field in meta["pairs"]:  # ... in the ONE field the pair is there for
+            ans = te.field_inst if kind == "inst" else te.field_type
+            if ans(out, name, a, field) == ans(out, name, b, field):
+                sys.exit(f"{name}: the reference answers pair {kind} {a} / {b} ({what}) alike in {field}: refused")
+        for kind, a, b, what, field in meta["alike"]:
+            ans = te.field_inst if kind == "inst" else te.field_type
+            if ans(out, name, a, field) != ans(out, name, b, field):
+                sys.exit(f"{name}: the reference answers pair {kind} {a} / {b} ({what}), marked alike, differently in {field}: refused")
+            not_pinned.append(f"{name}:{kind}:{a}:{b}:{what}:{field}")
+        sig = te.signatures(out, name)
+        sets = lambda t, which: te.set_of(rows[t], W, which)  # noqa: E731
+        present = [p for p in range(P) if not fleet.pods["flags"][p] & 5]
+        assert [p for p in range(P) if pod_part[p] >= 0] == present, name
+        if tier == "sets":
+            for p in meta["absent"]:  # shutting down / tombstoned, and would match type 0: in no set, in no partition
+                assert not any(te.answer_inst(out, name, p)[0]) and pod_part[p] < 0, (name, p, "an absent instance is in a set")
+            s0 = te.sets_blocks(P)[0]
+            assert {0, 62, P - 1} <= set(meta["engineered"]) and (P < 65 or {63, 64} <= set(meta["engineered"])), name
+            assert s0 + 8 in sets(5, 0) and s0 + 8 not in (sets(5, 1) or set()), (name, "required and preferred: allowed, NOT preferred")
+            assert s0 + 9 not in sets(5, 0) and s0 + 9 in sets(5, 1), (name, "preferred only: preferred and prohibited")
+            assert rows[6][0] == 0 and sets(6, 1) == sets(T, 1), (name, "a type with neither constrains nothing")
+            assert s0 + 1 not in sets(0, 0) and not any(te.answer_inst(out, name, s0 + 1)[0][0::2]), (name, "no label: allowed nowhere")
+            if meta["with_all"]:
+                assert s0 + 10 in sets(3, 0) and s0 + 11 not in sets(3, 0), name
+                st["what"].add("an instance with all 64 labels")
+            else:
+                assert rows[7][0] == 1 and sets(7, 0) == set() and sets(7, 1), (name, "nobody meets it: empty, not null; configured preference")
+                assert rows[8][0] == 1 and sets(8, 0) == set() and sets(8, 1) is None, name
+                st["what"].add("a requirement nobody meets")
+        elif tier == "infer":
+            if meta["want"] is None:
+                assert sets(meta["row"], 1) is None, (name, "the inference is not null", sets(meta["row"], 1))
+            else:
+                assert sets(meta["row"], 1) == set(meta["want"]), (name, sets(meta["row"], 1), meta["want"])
+            st["what"].add(meta["item"] + (" EMPTY non-null" if meta["want"] == [] else ""))
+            if meta["item"] == "configured":
+                assert sets(meta["twin_row"], 1) == set(meta["twin_want"]) != sets(meta["row"], 1), (name, "inference would not differ")
+                assert sets(meta["row"], 0) == sets(meta["twin_row"], 0)
+            for t in range(T):  # no requirement, a configured preference: the DEFAULT preferred set (:709-710), whatever was configured
+                if req_bits[t] == 0 and pref_bits[t] != 0:
+                    assert rows[t][0] == 0 and sets(t, 1) == sets(T, 1), (name, t)
+        else:
+            if "n_parts" in meta:
+                assert len(sig) == meta["n_parts"] == len(set(sig)), (name, len(sig))
+            if "rows" in meta:
+                assert meta["tw"] == {62: 1, 63: 1, 64: 2, 127: 2, 128: 3}[T], name
+                for r in meta["rows"]:
+                    assert frozenset([r]) in sig and frozenset() in sig, (name, "no pair of partitions that differ in row", r)
+                assert all(s <= set(meta["rows"]) for s in sig), name
+            if meta.get("variant") == "base" and "twin_of" not in meta:
+                hosts = lambda t: [k for k in range(len(sig)) if t not in sig[k]]  # noqa: E731
+                assert len(hosts(4)) == 1 and len(hosts(1)) == 0 and len(hosts(2)) == len(sig) == 4, name
+                assert tuple(tstats[1]) == (1, 0, 0, 2**63 - 1, 0, 0), (name, tstats[1])
+                by = {tuple(sorted(sig[k])): part_stats[k] for k in range(len(sig))}
+                assert by[(1, 3, 4)][1] == by[(0, 1, 4)][1] and by[(1, 3, 4)][0] != by[(0, 1, 4)][0], (name, "equal totalFree, unequal capacity")
+                assert by[(1,)][1] == te.MIN_SPACE, name
+            if meta.get("variant") == "hostile" and "twin_of" not in meta:
+                assert (part_stats[:, 0] < 0).any() and (part_stats[:, 4] < 0).any() and (tstats[:, 1] < 0).any() and (tstats[:, 5] < 0).any(), \
+                    (name, "no sum wraps")
+                assert fleet.pods["count"].min() >= 0 and fleet.pods["capacity"].min() >= 0 and fleet.pods["used"].min() >= 0
+            if meta.get("variant") == "nolru" and "twin_of" not in meta:
+                assert (part_stats[:, 2] == 2**63 - 1).all(), name
+            st["what"].add(f"{len(sig)} partitions")
+        print(f"{name}: {P} instances, {T} types, {len(sig)} partitions, {len(meta['pairs'])} pairs")
+    for name in names:  # the twins: the same case after six instances moved
+        if metas[name]["after"]:
+            assert te.answer_case(out, name) != te.answer_case(out, metas[name]["after"]), (name, "the moved instances change nothing")
+    run_pairs, alike = [], []
+    for a, b, p, what, field, same in te.type_edge_run_pairs():
+        if (te.field_case(out, a, field) == te.field_case(out, b, field)) != same:
+            sys.exit(f"{a} / {b}: instance {p} ({what}) is answered {'differently' if same else 'alike'} in {field} by the reference: refused")
+        (alike if same else run_pairs).append(f"{a}:{b}:{p}:{what}:{field}")
+        seen[metas[a]["tier"]]["pairs"] += 0 if same else 1
+    for t in te.TYPE_EDGE_TIERS:
+        print(f"tier {t}: {seen[t]['cases']} cases, {seen[t]['rows']} type rows, {seen[t]['pairs']} pairs; " + ", ".join(sorted(seen[t]["what"])))
+    assert seen["sets"]["what"] == {"an instance with all 64 labels", "a requirement nobody meets"}
+    assert {"allneg EMPTY non-null", "tie44", "single", "configured", "t0", "p1", "w256"} <= seen["infer"]["what"], seen["infer"]["what"]
+    assert {"1 partitions", "2 partitions", "512 partitions", "513 partitions", "600 partitions"} <= seen["stats"]["what"]
+    alike = not_pinned + alike
+    print(f"NOT pinned (answered alike, as they must be): {alike}")
+    print(f"slowest case: {slowest[1]} {slowest[0]:.1f} s in the harness")
+    # a preferred set that is EMPTY but present, in front of getNext (the place mode of the harness): has_prefer = 1 with a zero row
+    rows = out[f"{te.EMPTY_PREF}/rows"]
+    assert rows[-1][1] == 1 and not rows[-1][2:].any(), "the default row of the all-negative case is not empty and present"
+    f, ids, reqs = te.empty_pref_place(out)
+    blob = rf.input_blob(f, ids, reqs, None)
+    _, place, _, _ = run(blob, len(reqs), 0)
+    assert (place[:, 0] >= 0).sum() >= 10 and (place[:, 1] >= 2).any(), place
+    out["empty_pref/place"], out["empty_pref/digest"] = place, np.frombuffer(rf.digest(blob).encode(), np.uint8)
+    out["names"], out["run_pairs"], out["alike"] = np.array(names), np.array(run_pairs), np.array(alike)
+    np.savez_compressed(TYPE_EDGE_OUT, **out)
+    print(f"wrote {TYPE_EDGE_OUT}: {os.path.getsize(TYPE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
+    if "--type-edges" in sys.argv[1:]:  # only the type-constraint edge cases
+        return type_edge_vectors()
     if "--gate-edges" in sys.argv[1:]:  # only the guard edge cases: ref_getnext.npz stays as it is
         return gate_edge_vectors()
     if "--place-edges" in sys.argv[1:]:  # only the load-target edge cases

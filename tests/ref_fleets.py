@@ -2973,3 +2973,10 @@ def serve_edge_occurrence(fleet, reqs, xp, xt, serve):
         for k in range(int(r["excl_off"]), int(r["excl_off"] + r["n_excl"])):
             occ["a copy excluded"] |= bool(((pods == xp[k]) & ((xt[k] == _lib.ANY_TIME) | (times == xt[k]))).any())
     return occ
+
+
+def type_edge_cases():
+    """(name, fleet, ids, pod_bits, req_bits, pref_bits, meta): the type-constraint kernels at the edges of their value domain
+    (tests/ref_type_edges.py, tests/golden/ref_type_edges.npz)"""
+    from tests import ref_type_edges
+    return ref_type_edges.type_edge_cases()
