@@ -675,6 +675,23 @@ int mmp_cache_replay_k(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n_ops, con
  * (none yet, or a cache load since): 0 slots. */
 int mmp_cache_evicted_ids(mmp_ctx *ctx, char *bytes_out, int32_t max_bytes, int32_t *off_out, int32_t *n_slots_out,
                           int32_t *n_bytes_out);
+/* mmp_cache_replay_k with the eviction record carrying every victim's lastUsed — the value the clhm hands its listener
+ * (ConcurrentLinkedHashMap.java:578-586, node.getLastUsed() at notification), which onEviction passes to deregisterModel ->
+ * mr.updateLastUsed (MM.java:2913, :2956) and to ensureLoadedElsewhere (:2922).  It is the time the entry had when evict()
+ * unlinked it; a host cannot know it, the deque lives on the device.  Every argument and every output of mmp_cache_replay_k is as
+ * there, byte for byte; ev_last_used_out[s] is the time of slot s (room for max_evicted words), 0 for a slot no op used (row -1).
+ * ev_last_used_out may be NULL: the times are then kept in the context only.  The context keeps them with the id record, under the
+ * same lifetime: mmp_cache_evicted_times.  (The replay kernels of this call are instantiations of their own with a third column on
+ * the pending-victim stack — 32 bytes of LDS per deque slot instead of 24; mmp_cache_replay and mmp_cache_replay_k launch the
+ * kernels they always did.) */
+int mmp_cache_replay_kt(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n_ops, const char *keys, const int32_t *key_off, int64_t now_ms,
+                        int32_t *key_status_out, int32_t *key_row_out, mmp_cache_op_out *outs, int32_t *evicted_rows, int32_t max_evicted,
+                        int32_t *n_evicted_slots, char *ev_id_bytes_out, int32_t max_id_bytes, int32_t *ev_id_off_out,
+                        int32_t *n_id_bytes_out, int64_t *ev_last_used_out);
+/* The times of the last mmp_cache_replay_kt's eviction record, sizes then list: *n_slots_out always (the slots of
+ * mmp_cache_evicted_ids), the words when max_slots >= *n_slots_out.  MMP_ESTATE when the last replay recorded none: a plain
+ * mmp_cache_replay_k since, a cache load since, or no replay yet. */
+int mmp_cache_evicted_times(mmp_ctx *ctx, int64_t *out, int32_t max_slots, int32_t *n_slots_out);
 /* mmp_cache_read plus the ids of the deque's entries, gathered on the device: row_out = the keys (rows), id_off_out (min(n,
  * max_entries) + 1 words) offsets into id_bytes_out, *n_id_bytes_out = the bytes of those entries' ids, always; the bytes are
  * written when max_id_bytes is at least that.  The pseudo-entry has row_out == MMP_UNLOADBUF_KEY and an empty span, which tells
@@ -1181,6 +1198,74 @@ typedef struct {
 int mmp_registry_ops_k(mmp_ctx *ctx, const mmp_registry_op *ops, int32_t n, const char *keys, const int32_t *key_off,
                        int64_t now_ms, uint32_t flags, int32_t *model_idx_out, uint8_t *status_out,
                        mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_registry_ops_info_k *info_out);
+
+/* ---- the eviction loop by model id: onEviction's task body in one call (csrc/evictions_kernels.hpp) ---------------------------
+ * What the task of ModelMesh.onEviction does per victim (MM.java:2886-2920): read this instance's loadedTime from the record
+ * (instanceIds, else loadFailedInstanceIds), decide whether a reload elsewhere is to be attempted, and deregister — the read and
+ * the edit under ONE hold of the batch lock, so that they are of one registry state, and without a ModelRecord on the host: a
+ * host that parses no stored value has none to read loadedTime from.  With mmp_cache_replay_kt in front, the eviction loop is two
+ * calls: the record's ids are `keys`, its times are `last_used`.
+ *   entries            n victims: last_used (the record's time), load_time = ce.loadTimestamp, load_complete_time =
+ *                      ce.loadCompleteTimestamp (primitives in the Java: MMP_ROPF_MATCH_TIME always holds), weight (carried for
+ *                      the host's reload request; not read), flags = MMP_EVF_FAILED for ce.isFailed()
+ *   keys / key_off     the victims' ids, under the conventions of mmp_model_ids_resolve
+ *   params             self_pod (this instance), now, load_timeout_ms
+ *   flags              MMP_ROPS_APPLY / MMP_ROPS_DRY / 0, as in mmp_registry_ops_k
+ * Per victim, in this order:
+ *   1. the id is resolved as mmp_registry_ops_k resolves it.  Unknown, or the empty row of a deleted record: status
+ *      MMP_ROP_NO_RECORD, nothing read, nothing edited, no flag set, loaded_time -1.
+ *   2. unless MMP_EVF_FAILED (:2887): loaded_time = the time self_pod has among the row's instanceIds; if it is not there, among
+ *      its loadFailedInstanceIds (:2890-2893).  MMP_EVO_IN_REGISTRY if either list holds it (:2894); MMP_EVO_ATTEMPT_RELOAD if so
+ *      and now - loaded_time > 2 * load_timeout_ms (:2895: strict, Java long arithmetic).
+ *   3. MMP_EVO_RELOAD if MMP_EVO_ATTEMPT_RELOAD and, on the committed stats of the RECORD's type (typeSetStats, as mmp_gate_batch
+ *      reads them): totalCapacity > 0, instanceCount > 1, (20 * totalFree) / totalCapacity >= 1 (:2918-2920) — the clause that
+ *      sets MMP_GATE_RELOAD_ELSEWHERE, shared with it.
+ *   4. MMP_EVO_LOG if in the registry or failed (:2900); millis_since_last_used = now - last_used (:2899, wrapping).
+ *   5. the op {MMP_ROP_DEREGISTER, pod = self_pod, MMP_ROPF_MATCH_TIME, last_used, load_time, load_complete_time} (:2913), built on
+ *      the device, evaluated and — with MMP_ROPS_APPLY — applied by the path of mmp_registry_ops_k.  Steps 2-3 read the row BEFORE
+ *      this edit.
+ * model_idx_out, status_out, edits_out, max_edits, truncation (nothing applied), NULLs: exactly as mmp_registry_ops_k; outs[i].status
+ * repeats status_out[i].  info_out: the counts per flag and `ops`, what mmp_registry_ops_k reports of the n deregistrations.
+ * MMP_EINVAL with nothing written or changed: what mmp_registry_ops_k refuses (self_pod outside the instance table, non-monotone
+ * offsets, keys without key_off or the reverse, two victims whose ids name the same live row — the host splits the call), an entry
+ * flag other than MMP_EVF_FAILED, now <= 0.  MMP_ESTATE as mmp_registry_ops_k, which is also what mmp_gate_batch answers without
+ * a committed snapshot.  n == 0 is valid.
+ * NOT here: ensureLoadedElsewhere itself (:2922) — a victim with MMP_EVO_RELOAD goes to the _ck seams with the caller excluded
+ * and the record's last_used / weight; ce.doRemove (:2910); the metrics and log texts (:2902-2906: MMP_EVO_LOG and
+ * millis_since_last_used are their inputs); the compare-and-set retry (:2958-2960: the edits go to mmp_models_rewrite_json as
+ * ever). */
+#define MMP_EVF_FAILED 1u          /* mmp_evicted_entry.flags: ce.isFailed() */
+#define MMP_EVO_IN_REGISTRY 1u     /* mmp_evicted_out.flags */
+#define MMP_EVO_ATTEMPT_RELOAD 2u
+#define MMP_EVO_RELOAD 4u
+#define MMP_EVO_LOG 8u
+typedef struct {
+    int64_t last_used;
+    int64_t load_time;
+    int64_t load_complete_time;
+    int32_t weight;
+    uint32_t flags;
+} mmp_evicted_entry; /* 32 bytes */
+typedef struct {
+    int32_t self_pod;
+    int32_t reserved;
+    int64_t now;
+    int64_t load_timeout_ms;
+} mmp_evict_params; /* 24 bytes */
+typedef struct {
+    uint32_t flags;  /* MMP_EVO_* */
+    int32_t status;  /* MMP_ROP_UNCHANGED / MMP_ROP_EDITED / MMP_ROP_NO_RECORD of the deregistration */
+    int64_t loaded_time;             /* -1: none was read */
+    int64_t millis_since_last_used;
+} mmp_evicted_out; /* 24 bytes */
+typedef struct {
+    int32_t n_in_registry, n_attempt_reload, n_reload, n_log;
+    int32_t n_no_record, reserved;
+    mmp_registry_ops_info_k ops;
+} mmp_evictions_info; /* 112 bytes */
+int mmp_evictions_k(mmp_ctx *ctx, const mmp_evicted_entry *entries, int32_t n, const char *keys, const int32_t *key_off,
+                    const mmp_evict_params *params, uint32_t flags, int32_t *model_idx_out, mmp_evicted_out *outs,
+                    uint8_t *status_out, mmp_registry_op_edit *edits_out, int32_t max_edits, mmp_evictions_info *info_out);
 
 /* getStatus (MM.java:3247) answered from the resident registry, a batch of questions at a time: the status class of
  * invokeModel's "getStatus case" (:3760-3768) and the copy list makeStatusInfo builds for the reply (:3013-3058).  Each answer

@@ -90,6 +90,14 @@ final class MmPlace {
                                    ByteBuffer keyStatusOut, ByteBuffer keyRowOut, ByteBuffer outs, ByteBuffer evictedRows,
                                    int maxEvicted, ByteBuffer evIdBytesOut, int maxIdBytes, ByteBuffer evIdOffOut, ByteBuffer sizes);
     static native int cacheEvictedIds(long h, ByteBuffer bytesOut, int maxBytes, ByteBuffer offOut, ByteBuffer sizes);
+    // cacheReplayK with each victim's lastUsed beside its id (the value the clhm hands onEviction): evLastUsedOut = maxEvicted longs, or
+    // null — cacheEvictedTimes(out, maxSlots, nSlotsOut) reads them from the context (sizes then list; an error when the last replay
+    // recorded none)
+    static native int cacheReplayKT(long h, ByteBuffer ops, int nOps, ByteBuffer keys, ByteBuffer keyOff, long nowMs,
+                                    ByteBuffer keyStatusOut, ByteBuffer keyRowOut, ByteBuffer outs, ByteBuffer evictedRows,
+                                    int maxEvicted, ByteBuffer evIdBytesOut, int maxIdBytes, ByteBuffer evIdOffOut, ByteBuffer sizes,
+                                    ByteBuffer evLastUsedOut);
+    static native int cacheEvictedTimes(long h, ByteBuffer out, int maxSlots, ByteBuffer nSlotsOut);
     static native int cacheReadK(long h, int cache, int maxEntries, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer rowOut,
                                  ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut, ByteBuffer scalars, ByteBuffer ubm);
     // request guards and rebalancer plans
@@ -191,6 +199,13 @@ final class MmPlace {
     // int[8] unchanged per kind, entries added, entries removed).
     static native int registryOpsKeyed(long h, ByteBuffer ops, int n, ByteBuffer keys, ByteBuffer keyOff, long nowMs, int flags,
                                        ByteBuffer modelIdxOut, ByteBuffer statusOut, ByteBuffer editsOut, int maxEdits, ByteBuffer info);
+    // onEviction's task body (MM.java:2886-2920) by model id: entries = mmp_evicted_entry rows (32 bytes: lastUsed, loadTimestamp,
+    // loadCompleteTimestamp, int weight, int flags 1 = ce.isFailed()), params = {int selfPod, int 0, long now, long loadTimeoutMs},
+    // outs = mmp_evicted_out rows (24 bytes: int flags 1 in registry / 2 attempt reload / 4 reload / 8 log, int status, long
+    // loadedTime or -1, long millisSinceLastUsed), info = mmp_evictions_info (112 bytes)
+    static native int evictionsKeyed(long h, ByteBuffer entries, int n, ByteBuffer keys, ByteBuffer keyOff, ByteBuffer params, int flags,
+                                     ByteBuffer modelIdxOut, ByteBuffer outs, ByteBuffer statusOut, ByteBuffer editsOut, int maxEdits,
+                                     ByteBuffer info);
     // getStatus (MM.java:3247) from the resident registry: reqs = mmp_status_req rows (16 bytes: model or -1 for mr == null, failPod =
     // the pod of mle.getInstanceId() or -1, flags 1 = the cache-hit loop is exhausted, 0).  rowsOut = mmp_status_row rows (16 bytes:
     // class 0 NOT_FOUND / 1 NOT_LOADED / 2 LOADING_FAILED / 3 ask a copy, copyOff, nNotChecked, nFailed), copiesOut = mmp_status_copy
@@ -585,6 +600,95 @@ final class RegistryOpsById {
      *  KV-error branch (:3693-3709) stays with the caller */
     static Edit droppedLocal(GpuMeshBinding mesh, String modelId, int self, long lastUsed, long nowMs) {
         return one(mesh, modelId, self, DROP_LOCAL, 0, lastUsed, 0L, 0L, nowMs);
+    }
+}
+
+/**
+ * The eviction loop for a binding without an id map (modelIdsResident() == true), written as ModelMesh.onEviction's task body
+ * (MM.java:2886-2920) against TWO calls and nothing in between: MmPlace.cacheReplayKT — the replay that evicts; its record carries each
+ * victim's id and the lastUsed the clhm hands the listener — and MmPlace.evictionsKeyed here.  No row, no invented time and no
+ * ModelRecord on the host: loadedTime is read from the resident record, in the same hold of the library's batch lock that
+ * deregisters, so the read and the edit are of one registry state.
+ */
+final class EvictionsById {
+    static final int IN_REGISTRY = 1, ATTEMPT_RELOAD = 2, RELOAD = 4, LOG = 8;
+
+    /** one victim: the record's id and lastUsed, and what the CacheEntry holds */
+    static final class Victim {
+        String modelId;
+        long lastUsed, loadTimestamp, loadCompleteTimestamp;   // lastUsed: cacheReplayKT's evLastUsedOut
+        int weight;                                            // ce.getWeight(), for ensureLoadedElsewhere
+        boolean failed;                                        // ce.isFailed()
+    }
+    /** what the task body decided for it */
+    static final class Settled {
+        boolean inRegistry, attemptReload, reloadElsewhere, log;   // :2894, :2895, :2918-2920, :2900
+        long loadedTime, millisSinceLastUsed;                      // loadedTime -1: none was read
+        RegistryOpsById.Edit edit;                                 // null: deregisterModel returned without a compare-and-set
+    }
+
+    /** the first call: the replay that evicts.  ops / keys / outs as cacheReplayK takes them; answers one Victim per eviction slot
+     *  with its id and lastUsed filled in (null for a slot no op used).  The caller adds what its CacheEntry holds. */
+    static Victim[] replay(GpuMeshBinding mesh, ByteBuffer ops, int nOps, ByteBuffer keys, ByteBuffer keyOff, long nowMs, ByteBuffer outs,
+                           int maxEvicted, int idBytesHint) {
+        final ByteBuffer rows = MmPlace.direct(Math.max(4 * maxEvicted, 1)), off = MmPlace.direct(4 * (maxEvicted + 1)), sizes = MmPlace.direct(8),
+                         times = MmPlace.direct(Math.max(8 * maxEvicted, 1));
+        ByteBuffer bytes = MmPlace.direct(Math.max(idBytesHint, 1));
+        MmPlace.cacheReplayKT(mesh.handle(), ops, nOps, keys, keyOff, nowMs, null, null, outs, rows, maxEvicted, bytes, idBytesHint, off, sizes,
+                              times);
+        final int slots = sizes.getInt(0), need = sizes.getInt(4);
+        if (need > idBytesHint) {                                  // the replay ran once; the context kept the record
+            bytes = MmPlace.direct(need);
+            MmPlace.cacheEvictedIds(mesh.handle(), bytes, need, off, sizes);
+        }
+        final Victim[] out = new Victim[slots];
+        for (int s = 0; s < slots; s++) {
+            if (rows.getInt(4 * s) < 0) continue;
+            final byte[] id = new byte[off.getInt(4 * (s + 1)) - off.getInt(4 * s)];
+            for (int k = 0; k < id.length; k++) id[k] = bytes.get(off.getInt(4 * s) + k);
+            out[s] = new Victim();
+            out[s].modelId = new String(id, java.nio.charset.StandardCharsets.UTF_8);
+            out[s].lastUsed = times.getLong(8 * s);
+        }
+        return out;
+    }
+
+    /** the second call: victims of one replay.  Two victims that name one record (an id evicted, put back and evicted again inside
+     *  one replay) are refused with nothing changed: the caller splits the list in front of the second one. */
+    static Settled[] settle(GpuMeshBinding mesh, java.util.List<Victim> victims, int self, long nowMs, long loadTimeoutMs) {
+        if (!mesh.modelIdsResident()) throw new IllegalStateException("a binding with an id map runs onEviction on its records");
+        final int n = victims.size();
+        final java.util.List<String> ids = new java.util.ArrayList<>(n);
+        final ByteBuffer entries = MmPlace.direct(Math.max(32 * n, 1)), params = MmPlace.direct(24), outs = MmPlace.direct(Math.max(24 * n, 1)),
+                         status = MmPlace.direct(Math.max(n, 1)), edits = MmPlace.direct(Math.max(40 * n, 1)), info = MmPlace.direct(112);
+        for (int i = 0; i < n; i++) {
+            final Victim v = victims.get(i);
+            ids.add(v.modelId);
+            entries.putLong(32 * i, v.lastUsed); entries.putLong(32 * i + 8, v.loadTimestamp);
+            entries.putLong(32 * i + 16, v.loadCompleteTimestamp);
+            entries.putInt(32 * i + 24, v.weight); entries.putInt(32 * i + 28, v.failed ? 1 : 0);
+        }
+        params.putInt(0, self); params.putInt(4, 0); params.putLong(8, nowMs); params.putLong(16, loadTimeoutMs);
+        final ByteBuffer[] keys = TaskKeys.of(ids);
+        MmPlace.evictionsKeyed(mesh.handle(), entries, n, keys[0], keys[1], params, RegistryOpsById.APPLY, null, outs, status, edits, n, info);
+        final Settled[] out = new Settled[n];
+        int x = 0;                                                 // edits come in victim order
+        for (int i = 0; i < n; i++) {
+            final Settled s = out[i] = new Settled();
+            final int flags = outs.getInt(24 * i);
+            s.inRegistry = (flags & IN_REGISTRY) != 0; s.attemptReload = (flags & ATTEMPT_RELOAD) != 0;
+            s.reloadElsewhere = (flags & RELOAD) != 0; s.log = (flags & LOG) != 0;
+            s.loadedTime = outs.getLong(24 * i + 8); s.millisSinceLastUsed = outs.getLong(24 * i + 16);
+            if (status.get(i) != RegistryOpsById.EDITED) continue;
+            final RegistryOpsById.Edit e = s.edit = new RegistryOpsById.Edit();
+            e.row = edits.getInt(40 * x); e.nLoadedAfter = edits.getInt(40 * x + 8); e.nFailedAfter = edits.getInt(40 * x + 12);
+            e.flags = edits.getInt(40 * x + 16); e.insertedPos = edits.getInt(40 * x + 20);
+            e.lastUsedAfter = edits.getLong(40 * x + 24); e.lastUnloadAfter = edits.getLong(40 * x + 32);
+            x++;
+        }
+        // the caller: logs and metrics where s.log (:2902-2906), ce.doRemove (:2910), the record through conditionalSetAndGet where
+        // s.edit != null (:2958), and for s.reloadElsewhere ensureLoadedElsewhere (:2922) through the _ck seams with itself excluded
+        return out;
     }
 }
 

@@ -308,6 +308,33 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheEvictedIds(JNI
     if (!sz || !holds<int32_t>(env, sizes, 2, "cacheEvictedIds: sizes shorter than two ints")) return check(env, ctx_of(h), MMP_EINVAL);
     return check(env, ctx_of(h), mmp_cache_evicted_ids(ctx_of(h), buf<char>(env, bytesOut), maxBytes, buf<int32_t>(env, offOut), sz, sz + 1));
 }
+// cacheReplayK with the victims' lastUsed beside their ids (mmp_cache_replay_kt): evLastUsedOut holds maxEvicted longs, or is null
+// (the context keeps the times: cacheEvictedTimes)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReplayKT(JNIEnv *env, jclass, jlong h, jobject ops, jint nOps, jobject keys,
+                                                                           jobject keyOff, jlong nowMs, jobject keyStatusOut,
+                                                                           jobject keyRowOut, jobject outs, jobject evictedRows,
+                                                                           jint maxEvicted, jobject evIdBytesOut, jint maxIdBytes,
+                                                                           jobject evIdOffOut, jobject sizes, jobject evLastUsedOut)
+{
+    int32_t *sz = buf<int32_t>(env, sizes);
+    if (!sz || !holds<int32_t>(env, sizes, 2, "cacheReplayKT: sizes shorter than two ints") ||
+        (evLastUsedOut && !holds<int64_t>(env, evLastUsedOut, maxEvicted, "cacheReplayKT: evLastUsedOut shorter than maxEvicted")))
+        return check(env, ctx_of(h), MMP_EINVAL);
+    return check(env, ctx_of(h),
+                 mmp_cache_replay_kt(ctx_of(h), buf<mmp_cache_op>(env, ops), nOps, buf<char>(env, keys), buf<int32_t>(env, keyOff), nowMs,
+                                     buf<int32_t>(env, keyStatusOut), buf<int32_t>(env, keyRowOut), buf<mmp_cache_op_out>(env, outs),
+                                     buf<int32_t>(env, evictedRows), maxEvicted, sz, buf<char>(env, evIdBytesOut), maxIdBytes,
+                                     buf<int32_t>(env, evIdOffOut), sz + 1, buf<int64_t>(env, evLastUsedOut)));
+}
+// nSlotsOut: direct IntBuffer of one element; out holds maxSlots longs (null with maxSlots 0: the size only)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheEvictedTimes(JNIEnv *env, jclass, jlong h, jobject out, jint maxSlots,
+                                                                               jobject nSlotsOut)
+{
+    if (maxSlots < 0 || !holds<int32_t>(env, nSlotsOut, 1, "cacheEvictedTimes: nSlotsOut shorter than one int") ||
+        !holds<int64_t>(env, out, maxSlots, "cacheEvictedTimes: out shorter than maxSlots"))
+        return check(env, ctx_of(h), MMP_EINVAL);
+    return check(env, ctx_of(h), mmp_cache_evicted_times(ctx_of(h), buf<int64_t>(env, out), maxSlots, buf<int32_t>(env, nSlotsOut)));
+}
 // scalars: direct buffer {int32 n; int32 nIdBytes; int64 capacity; int64 weightedSize}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReadK(JNIEnv *env, jclass, jlong h, jint cache, jint maxEntries,
                                                                         jobject lastUsed, jobject weight, jobject rowOut, jobject idBytesOut,
@@ -688,6 +715,29 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_registryOpsKeyed(JN
                  mmp_registry_ops_k(ctx_of(h), buf<mmp_registry_op>(env, ops), n, buf<char>(env, keys), buf<int32_t>(env, keyOff), nowMs,
                                     static_cast<uint32_t>(flags), buf<int32_t>(env, modelIdxOut), buf<uint8_t>(env, statusOut),
                                     buf<mmp_registry_op_edit>(env, editsOut), maxEdits, buf<mmp_registry_ops_info_k>(env, info)));
+}
+// onEviction's task body by model id (mmp_evictions_k, MM.java:2886-2920): entries n x 32 bytes, params 24 bytes, outs n x 24 bytes,
+// info one mmp_evictions_info (112 bytes); modelIdxOut and statusOut may be null
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_evictionsKeyed(JNIEnv *env, jclass, jlong h, jobject entries, jint n, jobject keys,
+                                                                            jobject keyOff, jobject params, jint flags, jobject modelIdxOut,
+                                                                            jobject outs, jobject statusOut, jobject editsOut, jint maxEdits,
+                                                                            jobject info)
+{
+    if (n < 0 || maxEdits < 0 || !holds<mmp_evicted_entry>(env, entries, n, "evictionsKeyed: entries shorter than n") ||
+        (keyOff && !holds<int32_t>(env, keyOff, (jlong)n + 1, "evictionsKeyed: keyOff shorter than n + 1")) ||
+        (keyOff && keys && n > 0 && !holds<char>(env, keys, buf<int32_t>(env, keyOff)[n], "evictionsKeyed: keys shorter than keyOff[n]")) ||
+        !holds<mmp_evict_params>(env, params, 1, "evictionsKeyed: params shorter than one mmp_evict_params") ||
+        (modelIdxOut && !holds<int32_t>(env, modelIdxOut, n, "evictionsKeyed: modelIdxOut shorter than n")) ||
+        !holds<mmp_evicted_out>(env, outs, n, "evictionsKeyed: outs shorter than n") ||
+        (statusOut && !holds<uint8_t>(env, statusOut, n, "evictionsKeyed: statusOut shorter than n")) ||
+        !holds<mmp_registry_op_edit>(env, editsOut, maxEdits, "evictionsKeyed: editsOut shorter than maxEdits") ||
+        !holds<mmp_evictions_info>(env, info, 1, "evictionsKeyed: info shorter than one mmp_evictions_info"))
+        return MMP_EINVAL;
+    return check(env, ctx_of(h),
+                 mmp_evictions_k(ctx_of(h), buf<mmp_evicted_entry>(env, entries), n, buf<char>(env, keys), buf<int32_t>(env, keyOff),
+                                 buf<mmp_evict_params>(env, params), static_cast<uint32_t>(flags), buf<int32_t>(env, modelIdxOut),
+                                 buf<mmp_evicted_out>(env, outs), buf<uint8_t>(env, statusOut), buf<mmp_registry_op_edit>(env, editsOut), maxEdits,
+                                 buf<mmp_evictions_info>(env, info)));
 }
 // getStatus answers from the resident registry (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058): every
 // buffer's capacity is checked here, the library only knows n / maxCopies.  A null copiesOut with maxCopies = 0: the sizes only.

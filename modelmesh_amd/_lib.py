@@ -165,6 +165,15 @@ REGISTRY_OPS_INFO_K = np.dtype([("n_edits", "<i4"), ("n_unchanged", "<i4"), ("n_
                                 ("n_edited_op", "<i4", (8,)), ("n_unchanged_op", "<i4", (8,)), ("n_entries_added", "<i4"),
                                 ("n_entries_removed", "<i4")])
 assert REGISTRY_OPS_INFO_K.itemsize == 88
+# mmp_evictions_k: onEviction's task body by model id (MM.java:2886-2920)
+EVF_FAILED = 1
+EVO_IN_REGISTRY, EVO_ATTEMPT_RELOAD, EVO_RELOAD, EVO_LOG = 1, 2, 4, 8
+EVICTED_ENTRY = np.dtype([("last_used", "<i8"), ("load_time", "<i8"), ("load_complete_time", "<i8"), ("weight", "<i4"), ("flags", "<u4")])
+EVICT_PARAMS = np.dtype([("self_pod", "<i4"), ("reserved", "<i4"), ("now", "<i8"), ("load_timeout_ms", "<i8")])
+EVICTED_OUT = np.dtype([("flags", "<u4"), ("status", "<i4"), ("loaded_time", "<i8"), ("millis_since_last_used", "<i8")])
+EVICTIONS_INFO = np.dtype([("n_in_registry", "<i4"), ("n_attempt_reload", "<i4"), ("n_reload", "<i4"), ("n_log", "<i4"),
+                           ("n_no_record", "<i4"), ("reserved", "<i4"), ("ops", REGISTRY_OPS_INFO_K)])
+assert EVICTED_ENTRY.itemsize == 32 and EVICT_PARAMS.itemsize == 24 and EVICTED_OUT.itemsize == 24 and EVICTIONS_INFO.itemsize == 112
 
 # mmp_models_status (getStatus MM.java:3247: the class of :3760-3768, the copy list of makeStatusInfo :3013-3058)
 (MST_NOT_FOUND, MST_NOT_LOADED, MST_LOADING_FAILED, MST_ASK) = range(4)
@@ -361,6 +370,9 @@ SYMBOLS = [
     ("mmp_cache_replay_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32,
                                      _P, C.POINTER(C.c_int32)]),
     ("mmp_cache_evicted_ids", C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("mmp_cache_replay_kt", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32,
+                                      _P, C.POINTER(C.c_int32), _P]),
+    ("mmp_cache_evicted_times", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_cache_read_k", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     ("mmp_gate_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),
@@ -385,6 +397,7 @@ SYMBOLS = [
     ("mmp_registry_ops", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint32, _P, _P, C.c_int32, _P]),
     # the same by model id: ops / n, keys / key_off, now, flags, model_idx_out, status_out, edits_out, max_edits, info_out
     ("mmp_registry_ops_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, C.c_int32, _P]),
+    ("mmp_evictions_k", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_int32, _P]),
     ("mmp_models_status", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     # the same by model id: keys / key_off / n, fail_pod[n], flags[n], now, model_idx_out, then the outputs of mmp_models_status
     ("mmp_models_status_k", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),

@@ -42,6 +42,7 @@ struct ReplayArgs {
     const int32_t *op_off;     // [n_caches+1] ranges of op_order
     mmp_cache_op_out *outs;    // by caller operation index
     int32_t *evicted;          // evicted keys; cache c writes from ev_off[c]
+    int64_t *evicted_lu;       // with TIMES: every victim's lastUsed when it was unlinked, beside its key (NULL without)
     const int32_t *ev_off;     // [n_caches+1]
     int32_t n_caches;
     int32_t tile;              // LDS slots per column
@@ -65,6 +66,7 @@ struct Deque {
     int64_t *lu;
     int32_t *wt, *key;
     int32_t *stk_key, *stk_wt;  // pending victims (LIFO)
+    int64_t *stk_lu;            // with TIMES: their lastUsed, a third column that moves with the two above
     int head, n, sp;
     int64_t wsize, cap;
     int64_t oldest;  // clhm `oldestTime`: what updateOldestTime() last stored (afterWrite :444, tryToDrainBuffers :463) — setCapacity's
@@ -74,6 +76,7 @@ struct Deque {
     int64_t occ;
     // eviction record
     int32_t *ev;
+    int64_t *ev_lu;  // with TIMES
     int nev;
 };
 
@@ -207,16 +210,21 @@ __device__ __forceinline__ void dq_set_wt(Deque &D, int i, int32_t w)
 // updateOldestTime, clhm :1129-1133
 __device__ __forceinline__ void dq_refresh_oldest(Deque &D) { D.oldest = D.n ? D.lu[D.head] : -1; }
 
-template <int TW>
-__device__ __forceinline__ void record_evicted(Deque &D, int32_t k)
+// `lu` is what the clhm hands the listener: node.getLastUsed() at notification (clhm :578-586), which is the value the node
+// had when evict() unlinked it — nothing touches a dead node
+template <int TW, bool TIMES>
+__device__ __forceinline__ void record_evicted(Deque &D, int32_t k, int64_t lu)
 {
-    if (team_lane<TW>() == 0) D.ev[D.nev] = k;
+    if (team_lane<TW>() == 0) {
+        D.ev[D.nev] = k;
+        if constexpr (TIMES) D.ev_lu[D.nev] = lu;
+    }
     D.nev++;
 }
 
 // evict(), clhm :329-352 (makeDead subtracts |weight|, :566-575).  Plain caches record the victims
 // directly; with a manager they go onto the pending LIFO, oldest on top.
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
 {
     const int first = D.sp;
@@ -229,10 +237,11 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
             if (team_lane<TW>() == 0) {
                 D.stk_key[D.sp] = k;
                 D.stk_wt[D.sp] = w;
+                if constexpr (TIMES) D.stk_lu[D.sp] = ts;
             }
             D.sp++;
         } else
-            record_evicted<TW>(D, k);
+            record_evicted<TW, TIMES>(D, k, ts);
     }
     if (managed && D.sp - first > 1) {  // reverse the new run so the oldest victim is popped first
         wave_sync();
@@ -241,11 +250,16 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
             const int i = base + team_lane<TW>();
             const bool v = i < cnt / 2;
             int32_t k1 = 0, w1 = 0, k2 = 0, w2 = 0;
+            int64_t t1 = 0, t2 = 0;
             if (v) {
                 k1 = D.stk_key[first + i];
                 w1 = D.stk_wt[first + i];
                 k2 = D.stk_key[D.sp - 1 - i];
                 w2 = D.stk_wt[D.sp - 1 - i];
+                if constexpr (TIMES) {
+                    t1 = D.stk_lu[first + i];
+                    t2 = D.stk_lu[D.sp - 1 - i];
+                }
             }
             wave_sync();
             if (v) {
@@ -253,6 +267,10 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
                 D.stk_wt[first + i] = w2;
                 D.stk_key[D.sp - 1 - i] = k1;
                 D.stk_wt[D.sp - 1 - i] = w1;
+                if constexpr (TIMES) {
+                    D.stk_lu[first + i] = t2;
+                    D.stk_lu[D.sp - 1 - i] = t1;
+                }
             }
             wave_sync();
         }
@@ -261,7 +279,7 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
 }
 
 // CacheEntry.updateWeightLocked -> replaceQuietly -> UpdateTask(quiet), without running the listener
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_set_weight_nodrain(Deque &D, int32_t k, int32_t w)
 {
     // the weigher is CacheEntry.getWeight = Math.abs(weight) (MM.java:1759): a sum that wrapped negative weighs its magnitude
@@ -272,12 +290,12 @@ __device__ __forceinline__ void ubm_set_weight_nodrain(Deque &D, int32_t k, int3
     if (diff == 0) return;
     dq_set_wt<TW>(D, i, w);
     D.wsize += diff;
-    dq_evict<TW>(D, true);
+    dq_evict<TW, TIMES>(D, true);
     dq_refresh_oldest(D);  // afterWrite(UpdateTask)
 }
 
 // adjustAggregateUnloadingWeight, ModelCacheUnloadBufManager.java:375-392 (listener not yet run)
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_adjust_agg_nodrain(Deque &D, int32_t delta)
 {
     if (delta == 0) return;
@@ -289,35 +307,37 @@ __device__ __forceinline__ void ubm_adjust_agg_nodrain(Deque &D, int32_t delta)
         const int32_t cap = D.cap > INT32_MAX ? INT32_MAX : (int32_t)D.cap;
         if (cap < nw) nw = cap;
     }
-    ubm_set_weight_nodrain<TW>(D, MMP_UNLOADBUF_KEY_C, nw);
+    ubm_set_weight_nodrain<TW, TIMES>(D, MMP_UNLOADBUF_KEY_C, nw);
 }
 
 // the eviction listener: ModelMesh.onEviction -> entryRemoved (:311-316) per victim, depth first
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_drain(Deque &D)
 {
     while (D.sp > 0) {
         D.sp--;
         const int32_t k = D.stk_key[D.sp], w = D.stk_wt[D.sp];
+        int64_t lu = 0;
+        if constexpr (TIMES) lu = D.stk_lu[D.sp];
         wave_sync();
-        record_evicted<TW>(D, k);
+        record_evicted<TW, TIMES>(D, k, lu);
         D.occ -= w;
-        ubm_adjust_agg_nodrain<TW>(D, w);
+        ubm_adjust_agg_nodrain<TW, TIMES>(D, w);
     }
 }
 
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_adjust_agg(Deque &D, int32_t delta)
 {
-    ubm_adjust_agg_nodrain<TW>(D, delta);
-    ubm_drain<TW>(D);
+    ubm_adjust_agg_nodrain<TW, TIMES>(D, delta);
+    ubm_drain<TW, TIMES>(D);
 }
 
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_set_weight(Deque &D, int32_t k, int32_t w)
 {
-    ubm_set_weight_nodrain<TW>(D, k, w);
-    ubm_drain<TW>(D);
+    ubm_set_weight_nodrain<TW, TIMES>(D, k, w);
+    ubm_drain<TW, TIMES>(D);
 }
 
 // cacheSpaceIsReady, :395-402
@@ -329,7 +349,7 @@ __device__ __forceinline__ bool ubm_space_ready(const Deque &D, int32_t required
 }
 
 // payDownDeficitAndNotifyWaiters, :351-366
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ void ubm_pay_down(Deque &D, int32_t weight, bool release)
 {
     const int32_t reduction = weight < D.deficit ? weight : D.deficit;
@@ -337,7 +357,7 @@ __device__ __forceinline__ void ubm_pay_down(Deque &D, int32_t weight, bool rele
         D.deficit -= reduction;
         weight -= reduction;
     }
-    ubm_adjust_agg<TW>(D, release ? -weight : reduction);
+    ubm_adjust_agg<TW, TIMES>(D, release ? -weight : reduction);
 }
 
 // cacheRemaining, :340-342
@@ -347,7 +367,7 @@ __device__ __forceinline__ int32_t ubm_cache_remaining(const Deque &D)
     return r > INT32_MAX ? INT32_MAX : (int32_t)r;
 }
 
-template <int TW>
+template <int TW, bool TIMES>
 __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int64_t now)
 {
     switch (o.op) {
@@ -362,9 +382,9 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         D.wsize += o.arg;
         dq_insert<TW>(D, o.time == 0 ? now : o.time, o.arg, o.key);
         // the eviction listener is the cache's (MM.java:2863-2879): on a managed cache these victims reach entryRemoved too
-        dq_evict<TW>(D, D.reserved >= 0);
+        dq_evict<TW, TIMES>(D, D.reserved >= 0);
         dq_refresh_oldest(D);
-        ubm_drain<TW>(D);
+        ubm_drain<TW, TIMES>(D);
         return 1;
     }
     case MMP_COP_GET: {  // clhm :726-733, applyRead :503-521
@@ -393,9 +413,9 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
             dq_touch<TW>(D, i, o.time, now);
             dq_reposition<TW>(D, i);
         }
-        dq_evict<TW>(D, D.reserved >= 0);
+        dq_evict<TW, TIMES>(D, D.reserved >= 0);
         dq_refresh_oldest(D);
-        ubm_drain<TW>(D);
+        ubm_drain<TW, TIMES>(D);
         return 1;
     }
     case MMP_COP_REMOVE: {  // clhm :861-870, RemovalTask :614-627
@@ -409,21 +429,21 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         return 1;
     }
     case MMP_COP_UBM_INSERT_NEW_ENTRY: {  // :130-145
-        ubm_adjust_agg<TW>(D, -o.arg);
+        ubm_adjust_agg<TW, TIMES>(D, -o.arg);
         const int i = dq_find<TW>(D, o.key);
         if (i >= 0) {
             dq_touch<TW>(D, i, o.time, now);
             dq_reposition<TW>(D, i);
             dq_refresh_oldest(D);
-            ubm_adjust_agg<TW>(D, o.arg);
+            ubm_adjust_agg<TW, TIMES>(D, o.arg);
             return 0;
         }
         D.wsize += o.arg;
         dq_insert<TW>(D, o.time == 0 ? now : o.time, o.arg, o.key);
         D.occ += o.arg;
-        dq_evict<TW>(D, true);
+        dq_evict<TW, TIMES>(D, true);
         dq_refresh_oldest(D);
-        ubm_drain<TW>(D);
+        ubm_drain<TW, TIMES>(D);
         return 1;
     }
     case MMP_COP_UBM_ADJUST_SPACE_REQUEST: {  // adjustNewEntrySpaceRequest, :152-166
@@ -431,14 +451,14 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         if (i < 0) return 0;
         const int32_t nw = (int32_t)((uint32_t)D.wt[D.head + i] + (uint32_t)o.arg);
         D.occ += o.arg;
-        ubm_adjust_agg<TW>(D, -o.arg);
-        ubm_set_weight<TW>(D, o.key, nw);
+        ubm_adjust_agg<TW, TIMES>(D, -o.arg);
+        ubm_set_weight<TW, TIMES>(D, o.key, nw);
         return 1;
     }
     case MMP_COP_UBM_SPACE_IS_READY: return ubm_space_ready(D, o.arg) ? 1 : 0;
     case MMP_COP_UBM_CLAIM_SPACE: {  // claimRequestedSpaceIfReady, :190-202
         if (!ubm_space_ready(D, o.arg)) return 0;
-        ubm_adjust_agg<TW>(D, o.arg);
+        ubm_adjust_agg<TW, TIMES>(D, o.arg);
         return 1;
     }
     case MMP_COP_UBM_ADJUST_AFTER_LOAD: {  // adjustWeightAfterLoad, :224-246
@@ -447,26 +467,26 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         if (delta > 0) {
             const int32_t deficit = (int32_t)((uint32_t)delta - (uint32_t)ubm_cache_remaining(D));
             if (deficit > 0) {
-                ubm_adjust_agg<TW>(D, -deficit);
+                ubm_adjust_agg<TW, TIMES>(D, -deficit);
                 D.deficit += deficit;
             }
         }
         D.occ += delta;
         const int i = dq_find<TW>(D, o.key);
-        if (i >= 0) ubm_set_weight<TW>(D, o.key, (int32_t)((uint32_t)D.wt[D.head + i] + (uint32_t)delta));
-        if (delta < 0) ubm_pay_down<TW>(D, -delta, false);
+        if (i >= 0) ubm_set_weight<TW, TIMES>(D, o.key, (int32_t)((uint32_t)D.wt[D.head + i] + (uint32_t)delta));
+        if (delta < 0) ubm_pay_down<TW, TIMES>(D, -delta, false);
         return i >= 0 ? 1 : 0;
     }
     case MMP_COP_UBM_UNLOAD_COMPLETE: {  // :318-338
         if (o.flag) {
-            ubm_pay_down<TW>(D, o.arg, true);
+            ubm_pay_down<TW, TIMES>(D, o.arg, true);
             return 1;
         }
         const int64_t cap = D.cap;
-        ubm_adjust_agg<TW>(D, -o.arg);
+        ubm_adjust_agg<TW, TIMES>(D, -o.arg);
         D.cap = cap - o.arg > 1 ? cap - o.arg : 1;
-        dq_evict<TW>(D, true);  // setCapacity evicts and notifies under the lock, clhm :305-316 — and does NOT updateOldestTime()
-        ubm_drain<TW>(D);
+        dq_evict<TW, TIMES>(D, true);  // setCapacity evicts and notifies under the lock, clhm :305-316 — and does NOT updateOldestTime()
+        ubm_drain<TW, TIMES>(D);
         return 0;
     }
     case MMP_COP_UBM_REMOVE_ENTRY: {  // removeEntry :281-298 + entryRemoved :311-316; result = weight or -1
@@ -478,30 +498,30 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         D.wsize -= w < 0 ? -(int64_t)w : (int64_t)w;
         dq_refresh_oldest(D);
         D.occ -= w;
-        ubm_adjust_agg<TW>(D, w);
+        ubm_adjust_agg<TW, TIMES>(D, w);
         return w;
     }
     case MMP_COP_UBM_DISCARD_FAILED: {  // discardFailedEntry, :343-349
         D.occ -= o.arg;
-        ubm_pay_down<TW>(D, o.arg, false);
+        ubm_pay_down<TW, TIMES>(D, o.arg, false);
         return 1;
     }
     case MMP_COP_UBM_INSERT_FAILED_PLACEHOLDER: {  // insertFailedPlaceholderEntry, :250-274
         const int32_t deficit = (int32_t)((uint32_t)o.arg - (uint32_t)ubm_cache_remaining(D));
-        if (deficit > 0) ubm_adjust_agg<TW>(D, -deficit);
+        if (deficit > 0) ubm_adjust_agg<TW, TIMES>(D, -deficit);
         const int i = dq_find<TW>(D, o.key);
         if (i >= 0) {
             dq_touch<TW>(D, i, o.time, now);
             dq_reposition<TW>(D, i);
             dq_refresh_oldest(D);
-            if (deficit > 0) ubm_adjust_agg<TW>(D, deficit);
+            if (deficit > 0) ubm_adjust_agg<TW, TIMES>(D, deficit);
             return 0;
         }
         D.wsize += o.arg;
         dq_insert<TW>(D, o.time == 0 ? now : o.time, o.arg, o.key);
-        dq_evict<TW>(D, true);
+        dq_evict<TW, TIMES>(D, true);
         dq_refresh_oldest(D);
-        ubm_drain<TW>(D);
+        ubm_drain<TW, TIMES>(D);
         D.occ += o.arg;
         if (deficit > 0) D.deficit += deficit;
         return 1;
@@ -514,7 +534,10 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
 // small caches to 8- or 16-lane teams, 8 or 4 caches per wavefront; caches above kTeam16Slots to a wavefront each).
 constexpr int kTeam8Slots = 48, kTeam16Slots = 160;
 
-template <int TW>
+// TIMES: the eviction record also carries every victim's lastUsed (A.evicted_lu).  The pending LIFO gets its third column, so a
+// slot takes 32 bytes of LDS instead of 24: 2 048 x 32 = 65 536 for the full tile of a wavefront, the most dynamic LDS a launch
+// gets without a function attribute.  The 8-byte columns come first.
+template <int TW, bool TIMES = false>
 __global__ __launch_bounds__(64) void cache_replay_kernel(ReplayArgs A, const int32_t *__restrict__ ids, int32_t n_ids)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -525,7 +548,11 @@ __global__ __launch_bounds__(64) void cache_replay_kernel(ReplayArgs A, const in
     const int lane = team_lane<TW>();
     Deque D;
     D.lu = reinterpret_cast<int64_t *>(smem) + (size_t)team * A.tile;  // columns of all teams side by side: 8-byte column first
-    D.wt = reinterpret_cast<int32_t *>(reinterpret_cast<int64_t *>(smem) + (size_t)kTeams * A.tile) + (size_t)team * 4 * A.tile;
+    if constexpr (TIMES) {
+        D.stk_lu = reinterpret_cast<int64_t *>(smem) + (size_t)(kTeams + team) * A.tile;
+        D.wt = reinterpret_cast<int32_t *>(reinterpret_cast<int64_t *>(smem) + (size_t)2 * kTeams * A.tile) + (size_t)team * 4 * A.tile;
+    } else
+        D.wt = reinterpret_cast<int32_t *>(reinterpret_cast<int64_t *>(smem) + (size_t)kTeams * A.tile) + (size_t)team * 4 * A.tile;
     D.key = D.wt + A.tile;
     D.stk_key = D.key + A.tile;
     D.stk_wt = D.stk_key + A.tile;
@@ -558,6 +585,7 @@ __global__ __launch_bounds__(64) void cache_replay_kernel(ReplayArgs A, const in
     D.occ = u.total_occupancy;
     D.deficit = u.cache_deficit;
     D.ev = A.evicted + A.ev_off[c];
+    if constexpr (TIMES) D.ev_lu = A.evicted_lu + A.ev_off[c];
     D.nev = 0;
     mmp_cache_op o = A.ops[o0];
     int oi = A.op_order[o0];
@@ -571,7 +599,7 @@ __global__ __launch_bounds__(64) void cache_replay_kernel(ReplayArgs A, const in
             oi_next = A.op_order[q + 1];
         }
         const int ev0 = D.nev;
-        const int32_t res = apply_op<TW>(D, o, A.now);
+        const int32_t res = apply_op<TW, TIMES>(D, o, A.now);
         const int ubi = u.reserved >= 0 ? dq_find<TW>(D, MMP_UNLOADBUF_KEY_C) : -1;
         if (lane == 0) {
             mmp_cache_op_out r;

@@ -43,6 +43,22 @@ __device__ __forceinline__ bool load_change(int32_t cur_rpm, int32_t rpm)
     return diff >= 100 || (cur_rpm == 0 ? rpm != 0 : (100 * diff) / cur_rpm > 10);
 }
 
+// onEviction's reload rule, stated once for gate_eval and evict_stage_kernel (evictions_kernels.hpp).  MM.java:2895: loaded for more
+// than twice the load timeout (strict, long arithmetic); :2918-2920: the instances the record's type may be placed on are not full.
+__device__ __forceinline__ bool reload_overdue(int64_t now, int64_t loaded_time, int64_t load_timeout_ms)
+{
+    return jsub64(now, loaded_time) > 2 * load_timeout_ms;
+}
+__device__ __forceinline__ bool reload_room_elsewhere(int64_t total_cap, int32_t inst_count, int64_t total_free)
+{
+    return total_cap > 0 && inst_count > 1 && (20 * total_free) / total_cap >= 1;
+}
+// typeSetStats(mr.getType()) (MM.java:1432-1439) of the committed snapshot; a type outside the table reads row 0
+__device__ __forceinline__ const StatsAcc *type_stats_row(const StatsAcc *tstats, int32_t T_rows, int32_t type)
+{
+    return &tstats[(type < 0 || type >= T_rows) ? 0 : type];
+}
+
 // A launch lasts as long as its chain of dependent fetches, so everything a level of that chain needs is requested
 // together before anything is evaluated: (1) the request; (2) the model row, the caller's own instance row, the first
 // exclusions and the explicit pool; (3) the first copies and failure records, the type's stats row, its allowed bit;
@@ -71,7 +87,7 @@ __device__ __forceinline__ mmp_gate_out gate_eval(const GateArgs &A, const mmp_g
     }
     // ---- level 3
     // typeSetStats(mr.getType()) at MM.java:5169 (loadLocal) and :2918 (onEviction); cluster-wide without a record
-    const StatsAcc *st = have_model ? &A.tstats[(m.type < 0 || m.type >= A.T_rows) ? 0 : m.type] : A.stats;
+    const StatsAcc *st = have_model ? type_stats_row(A.tstats, A.T_rows, m.type) : A.stats;
     const int64_t total_cap = (int64_t)st->total_capacity, total_free = (int64_t)st->total_free;
     const int32_t copy_count = st->model_copy_count, inst_count = st->instance_count;
     int32_t l_iid[kGatePre], f_iid[kGatePre];
@@ -216,9 +232,8 @@ __device__ __forceinline__ mmp_gate_out gate_eval(const GateArgs &A, const mmp_g
     }
 
     // ---- onEviction reload rule, MM.java:2886-2920
-    if (!(r.flags & MMP_GATE_ENTRY_FAILED) && r.loaded_time >= 0 &&
-        jsub64(A.now, r.loaded_time) > 2 * r.load_timeout_ms) {
-        if (total_cap > 0 && inst_count > 1 && (20 * total_free) / total_cap >= 1) bits |= MMP_GATE_RELOAD_ELSEWHERE;
+    if (!(r.flags & MMP_GATE_ENTRY_FAILED) && r.loaded_time >= 0 && reload_overdue(A.now, r.loaded_time, r.load_timeout_ms)) {
+        if (reload_room_elsewhere(total_cap, inst_count, total_free)) bits |= MMP_GATE_RELOAD_ELSEWHERE;
     }
 
     // ---- publishInstanceRecord hysteresis, MM.java:5397-5468

@@ -45,6 +45,7 @@
 #include "status_kernels.hpp"
 #include "status_keyed_kernels.hpp"
 #include "registry_ops_keyed_kernels.hpp"
+#include "evictions_kernels.hpp"
 #include "cache_keyed_kernels.hpp"
 #include "tasks_keyed_kernels.hpp"
 #include "census_kernels.hpp"
@@ -531,7 +532,7 @@ struct mmp_ctx {
     std::vector<int32_t> k_n;  // host mirror of the live entry counts
     DevBuf r_part;  // per-workgroup partials of the proactive plan's first pass
     DevBuf rs_split, rs_int;  // rank_sample.hpp: the sorted samples; range_of[P] | idx[P] | hist | cur | off
-    DevBuf k_cap, k_wsize, k_oldest, k_ubm, k_ops, k_order, k_opoff, k_outs, k_ev, k_evoff, k_ids;  // k_ids: cache ids grouped by replay team width
+    DevBuf k_cap, k_wsize, k_oldest, k_ubm, k_ops, k_order, k_opoff, k_outs, k_ev, k_evlu, k_evoff, k_ids;  // k_ids: cache ids grouped by replay team width
     // the caches by model id (cache_keyed_kernels.hpp).  k_bound: the keys of the current store are registry rows (set by
     // mmp_caches_load_keyed_k; dropped by mmp_caches_load_keyed and mmp_model_ids_load).  k_slots: the deque slots of the current
     // store, off[k_caches].  evid_*: the eviction record of the last mmp_cache_replay_k, as bytes — a retirement cannot change it.
@@ -539,6 +540,9 @@ struct mmp_ctx {
     int32_t k_slots = 0;
     std::vector<char> evid_bytes;
     std::vector<int32_t> evid_off{0};
+    std::vector<int64_t> evid_lu;  // the victims' lastUsed by slot, kept with the id record; evid_timed: the last replay recorded them
+    bool evid_timed = false;       // (mmp_cache_replay_kt; a plain mmp_cache_replay_k or a cache load clears it)
+    DevBuf ev_in, ev_out;  // mmp_evictions_k: the victims' entries, their mmp_evicted_out rows
     DevBuf k_inv, k_kstat, k_krow, k_len, k_goff, k_gbytes;  // inverse of k_order; status / row by caller op; the id gather's lengths, offsets, bytes
 
     // wire-format ingestion: per-pod id attributes and the hash tables the parsers probe
@@ -7704,9 +7708,17 @@ namespace {
 // the keys in front of the evaluation when there are any (rops_keyed_kernel: `model` of the staged op is then the device's, the
 // caller's is never read), evaluates, reads back and applies.  max_kind: the last MMP_ROP_* kind the entry point admits.
 // keys / key_off both NULL: by row, `model` range-checked here.  *info is written only by a call that answers MMP_OK.
+// ev (mmp_evictions_k; keyed, ops == nullptr): the op rows are not the caller's — evict_stage_kernel (evictions_kernels.hpp) builds them
+// on the device from the victims' entries, behind the resolve stage and in front of the evaluation, and reads the row for
+// onEviction's decision there; ev->outs is written where status_out is.
+struct RopsEvict {
+    const mmp_evicted_entry *entries;
+    const mmp_evict_params *p;
+    mmp_evicted_out *outs;
+};
 int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_op *ops, int32_t n, const char *keys, const int32_t *key_off,
                int64_t now, uint32_t flags, int32_t *model_idx_out, uint8_t *status_out, mmp_registry_op_edit *edits_out, int32_t max_edits,
-               mmp_registry_ops_info_k *info)
+               mmp_registry_ops_info_k *info, const RopsEvict *ev = nullptr)
 {
     const bool keyed = keys || key_off;
     // batch_mu owns c->stream, the scratch, the map and the model-id table for the whole call, and every writer of the state this
@@ -7719,7 +7731,12 @@ int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_
     const int32_t M = c->n_models, P = c->snap.P;
     // the ops index the map, the rows and the instance table: their ranges are settled here, before any kernel reads them (that
     // no model is named twice is settled by the first kernel, on the map; by key the row is the device's own and lies in [-1, M))
-    for (int32_t i = 0; i < n; i++) {
+    if (ev) {
+        if (ev->p->self_pod < 0 || ev->p->self_pod >= P) return fail(c, MMP_EINVAL, "%s: self_pod %d of %d", fn, ev->p->self_pod, P);
+        for (int32_t i = 0; i < n; i++)
+            if (ev->entries[i].flags & ~MMP_EVF_FAILED) return fail(c, MMP_EINVAL, "%s: entry %d has flags %u", fn, i, ev->entries[i].flags);
+    }
+    for (int32_t i = 0; i < n && !ev; i++) {
         const mmp_registry_op &o = ops[i];
         if (!keyed && (o.model < 0 || o.model >= M)) return fail(c, MMP_EINVAL, "%s: op %d names model %d of %d", fn, i, o.model, M);
         if (o.pod < 0 || o.pod >= P) return fail(c, MMP_EINVAL, "%s: op %d names pod %d of %d", fn, i, o.pod, P);
@@ -7751,6 +7768,10 @@ int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_
         if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
         HIP_TRY(c, c->me_row.ensure((size_t)n * 4));
     }
+    if (ev) {
+        HIP_TRY(c, c->ev_in.ensure((size_t)n * sizeof(mmp_evicted_entry)));
+        HIP_TRY(c, c->ev_out.ensure((size_t)n * sizeof(mmp_evicted_out)));
+    }
     if (const int rc = model_map_cover(c, M, st)) return rc;  // (in doubt until the scatter kernel has been seen to complete)
     const mmp_pod_row *pods = c->sb[c->cur].pods.as<mmp_pod_row>();  // the committed rows: what the janitor's insert reads
     const mmp_model_row *models = c->models.as<mmp_model_row>();
@@ -7761,7 +7782,10 @@ int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_
     RopsScalars *rs = c->plan.call_scalars.as<RopsScalars>();
     PruneScalars *ps = c->plan.totals.as<PruneScalars>();
     uint8_t *d_status = c->plan.row_tmp.as<uint8_t>();
-    HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, ops, (size_t)n * sizeof(mmp_registry_op), hipMemcpyHostToDevice, st));
+    if (ev)
+        HIP_TRY(c, hipMemcpyAsync(c->ev_in.p, ev->entries, (size_t)n * sizeof(mmp_evicted_entry), hipMemcpyHostToDevice, st));
+    else
+        HIP_TRY(c, hipMemcpyAsync(c->plan.rows_in.p, ops, (size_t)n * sizeof(mmp_registry_op), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(rs, 0, sizeof(RopsScalars), st));
     HIP_TRY(c, hipMemsetAsync(ps, 0, sizeof(PruneScalars), st));
     KT_BEGIN(c, st);  // device span of the evaluation
@@ -7770,6 +7794,11 @@ int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_
         const RopsKeyArgs A{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
                             c->me_row.as<int32_t>(), d_ops};
         hipLaunchKernelGGL(rops_keyed_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, A);
+    }
+    if (ev) {  // the registry read and the op rows: of the state the evaluation behind it reads, before any edit
+        const EvictStageArgs E{c->ev_in.as<mmp_evicted_entry>(), n, ev->p->self_pod, ev->p->now, ev->p->load_timeout_ms, models, ent_pod, ent_time,
+                               cur_side(c).tstats.as<StatsAcc>(), std::max(c->n_types, 1), d_ops, c->ev_out.as<mmp_evicted_out>()};
+        hipLaunchKernelGGL(evict_stage_kernel, dim3(div_up(n, kEvictBlock)), dim3(kEvictBlock), 0, st, E);
     }
     hipLaunchKernelGGL(rops_count_kernel, dim3(nb), dim3(kRopsBlock), 0, st, d_ops, n, models, ent_pod, ent_time, pods, P, now, map, rs,
                        c->plan.block_counts.as<int32_t>());
@@ -7794,6 +7823,12 @@ int rops_drive(mmp_ctx *c, const char *fn, int32_t max_kind, const mmp_registry_
             for (int32_t i = 0; i < n; i++) model_idx_out[i] = ops[i].model;
     }
     if (status_out) HIP_TRY(c, copy_sync(c, status_out, d_status, (size_t)n, hipMemcpyDeviceToHost));
+    if (ev) {
+        std::vector<uint8_t> stv((size_t)n);
+        HIP_TRY(c, copy_sync(c, stv.data(), d_status, (size_t)n, hipMemcpyDeviceToHost));
+        HIP_TRY(c, copy_sync(c, ev->outs, c->ev_out.p, (size_t)n * sizeof(mmp_evicted_out), hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < n; i++) ev->outs[i].status = stv[i];
+    }
     if (ne > 0) HIP_TRY(c, copy_sync(c, edits_out, c->plan.edits.p, (size_t)ne * sizeof(mmp_registry_op_edit), hipMemcpyDeviceToHost));
     *info = mmp_registry_ops_info_k{};
     info->n_edits = h.n_edits;
@@ -7851,6 +7886,32 @@ try {
     return rops_drive(c, "mmp_registry_ops_k", MMP_ROP_DROP_LOCAL, ops, n, keys, key_off, now, flags, model_idx_out, status_out, edits_out,
                       max_edits, info);
 } MMP_CATCH(c, "mmp_registry_ops_k")
+
+// onEviction's task body by model id: the registry read, the reload decision and the deregistration of one registry state
+int mmp_evictions_k(mmp_ctx *c, const mmp_evicted_entry *entries, int32_t n, const char *keys, const int32_t *key_off, const mmp_evict_params *p,
+                    uint32_t flags, int32_t *model_idx_out, mmp_evicted_out *outs, uint8_t *status_out, mmp_registry_op_edit *edits_out,
+                    int32_t max_edits, mmp_evictions_info *info)
+try {
+    if (!c || !info || !p || n < 0 || max_edits < 0 || (n > 0 && (!entries || !outs || !key_off)) || (max_edits > 0 && !edits_out) || p->now <= 0 ||
+        plan_flags_bad(flags) || (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "mmp_evictions_k: bad argument");
+    const RopsEvict ev{entries, p, outs};
+    mmp_registry_ops_info_k k{};
+    if (const int rc = rops_drive(c, "mmp_evictions_k", MMP_ROP_DROP_LOCAL, nullptr, n, keys, key_off, p->now, flags, model_idx_out, status_out,
+                                  edits_out, max_edits, &k, &ev))
+        return rc;
+    *info = mmp_evictions_info{};
+    for (int32_t i = 0; i < n; i++) {
+        const uint32_t f = outs[i].flags;
+        info->n_in_registry += (f & MMP_EVO_IN_REGISTRY) != 0;
+        info->n_attempt_reload += (f & MMP_EVO_ATTEMPT_RELOAD) != 0;
+        info->n_reload += (f & MMP_EVO_RELOAD) != 0;
+        info->n_log += (f & MMP_EVO_LOG) != 0;
+    }
+    info->n_no_record = k.n_no_record;
+    info->ops = k;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_evictions_k")
 
 namespace {
 // What a caller of status_drive adds around the pipeline; each defaults to nothing.
@@ -8885,6 +8946,8 @@ int caches_keyed_store(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, con
     c->k_bound = bound;
     c->evid_bytes.clear();  // the eviction record of a keyed replay ends with the store it was made on
     c->evid_off.assign(1, 0);
+    c->evid_lu.clear();
+    c->evid_timed = false;
     return MMP_OK;
 }
 
@@ -8943,6 +9006,8 @@ struct ReplayKeyed {
     char *id_bytes_out;
     int32_t max_id_bytes;
     int32_t *id_off_out, *n_id_bytes_out;
+    bool times;           // mmp_cache_replay_kt: the TIMES instantiations, the record carries the victims' lastUsed
+    int64_t *ev_lu_out;   // (may be NULL: the times stay in the context)
 };
 }  // namespace
 
@@ -9015,6 +9080,8 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
         if (kx) {  // a valid call: its record is the empty one
             c->evid_bytes.clear();
             c->evid_off.assign(1, 0);
+            c->evid_lu.clear();
+            c->evid_timed = kx->times;
             *kx->n_id_bytes_out = 0;
             if (kx->id_off_out) kx->id_off_out[0] = 0;
             if (c->prof) c->last_kernel_ms = -1;
@@ -9086,6 +9153,8 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     HIP_TRY(c, c->k_outs.ensure((size_t)n_ops * sizeof(mmp_cache_op_out)));
     HIP_TRY(c, c->k_ev.ensure((size_t)std::max(ev_off[NC], 1) * 4));
     HIP_TRY(c, c->k_evoff.ensure((size_t)(NC + 1) * 4));
+    const bool times = kx && kx->times;
+    if (times) HIP_TRY(c, c->k_evlu.ensure((size_t)std::max(ev_off[NC], 1) * 8));
     HIP_TRY(c, hipMemcpyAsync(D.off.p, new_off.data(), (size_t)(NC + 1) * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->k_ops.p, grouped.data(), (size_t)n_ops * sizeof(mmp_cache_op), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->k_order.p, order.data(), (size_t)n_ops * 4, hipMemcpyHostToDevice, st));
@@ -9103,6 +9172,7 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     A.op_off = c->k_opoff.as<int32_t>();
     A.outs = c->k_outs.as<mmp_cache_op_out>();
     A.evicted = c->k_ev.as<int32_t>();
+    A.evicted_lu = times ? c->k_evlu.as<int64_t>() : nullptr;
     A.ev_off = c->k_evoff.as<int32_t>();
     A.n_caches = NC;
     A.tile = tile;
@@ -9117,6 +9187,8 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     }
     if (kx && n_slots)  // a slot no op used holds -1
         HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->k_ev.as<int32_t>()), -1, (size_t)n_slots, st));
+    if (times && n_slots)  // and its time is 0
+        HIP_TRY(c, hipMemsetAsync(c->k_evlu.p, 0, (size_t)n_slots * 8, st));
     KT_BEGIN(c, st);
     if (kx) {
         // (the staged copy keeps keyed_resolve_kernel's contract: the buffer is an allocation of its own with 16 bytes behind the keys)
@@ -9127,21 +9199,31 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     const int32_t *d_ids = c->k_ids.as<int32_t>();
     for (int w = 0; w < 3; w++)
         if ((int32_t)ids[w].size() == NC) d_ids = nullptr;  // one width for every cache: the list is the identity
-    if (!ids[0].empty()) {
-        A.tile = tiles[0];
-        hipLaunchKernelGGL(cache_replay_kernel<8>, dim3(div_up((int)ids[0].size(), 8)), dim3(64), (size_t)tiles[0] * 24 * 8, st, A, d_ids,
-                           (int32_t)ids[0].size());
-    }
-    if (!ids[1].empty()) {
-        A.tile = tiles[1];
-        hipLaunchKernelGGL(cache_replay_kernel<16>, dim3(div_up((int)ids[1].size(), 4)), dim3(64), (size_t)tiles[1] * 24 * 4, st, A,
-                           d_ids ? d_ids + ids[0].size() : nullptr, (int32_t)ids[1].size());
-    }
-    if (!ids[2].empty()) {
-        A.tile = tiles[2];
-        hipLaunchKernelGGL(cache_replay_kernel<64>, dim3((int)ids[2].size()), dim3(64), (size_t)tiles[2] * 24, st, A,
-                           d_ids ? d_ids + ids[0].size() + ids[1].size() : nullptr, (int32_t)ids[2].size());
-    }
+    // bytes of LDS per deque slot: lu 8, weight 4, key 4, the pending LIFO 4 + 4 — and 8 for its lastUsed column with TIMES, where
+    // the full tile of a wavefront (2 048 slots) takes 65 536 bytes: the most a launch gets without a function attribute
+    const size_t slot_lds = times ? 32 : 24;
+    static_assert(kCacheTile * 32 <= 65536 && kTeam8Slots * 32 * 8 <= 65536 && kTeam16Slots * 32 * 4 <= 65536, "replay tile exceeds the LDS of a launch");
+    const auto launch = [&](auto k8, auto k16, auto k64) {
+        if (!ids[0].empty()) {
+            A.tile = tiles[0];
+            hipLaunchKernelGGL(k8, dim3(div_up((int)ids[0].size(), 8)), dim3(64), (size_t)tiles[0] * slot_lds * 8, st, A, d_ids,
+                               (int32_t)ids[0].size());
+        }
+        if (!ids[1].empty()) {
+            A.tile = tiles[1];
+            hipLaunchKernelGGL(k16, dim3(div_up((int)ids[1].size(), 4)), dim3(64), (size_t)tiles[1] * slot_lds * 4, st, A,
+                               d_ids ? d_ids + ids[0].size() : nullptr, (int32_t)ids[1].size());
+        }
+        if (!ids[2].empty()) {
+            A.tile = tiles[2];
+            hipLaunchKernelGGL(k64, dim3((int)ids[2].size()), dim3(64), (size_t)tiles[2] * slot_lds, st, A,
+                               d_ids ? d_ids + ids[0].size() + ids[1].size() : nullptr, (int32_t)ids[2].size());
+        }
+    };
+    if (times)
+        launch(cache_replay_kernel<8, true>, cache_replay_kernel<16, true>, cache_replay_kernel<64, true>);
+    else
+        launch(cache_replay_kernel<8, false>, cache_replay_kernel<16, false>, cache_replay_kernel<64, false>);
     if (kx && n_slots)  // the lengths of the victims' ids and their scan, in the same span
         if (const int rc = ckey_gather_sizes(c, c->k_ev.as<int32_t>(), n_slots)) return rc;
     KT_END(c, st);
@@ -9155,6 +9237,8 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
         if (kx->row_out) HIP_TRY(c, hipMemcpyAsync(kx->row_out, c->k_krow.p, (size_t)n_ops * 4, hipMemcpyDeviceToHost, st));
         if (n_slots) HIP_TRY(c, hipMemcpyAsync(id_off.data(), c->k_goff.p, ((size_t)n_slots + 1) * 4, hipMemcpyDeviceToHost, st));
     }
+    std::vector<int64_t> ev_lu(times ? (size_t)n_slots : 0);
+    if (times && n_slots) HIP_TRY(c, hipMemcpyAsync(ev_lu.data(), c->k_evlu.p, (size_t)n_slots * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     kt_collect(c);
     // the replay is applied from here on, whatever becomes of the record: it is stateful and cannot be asked twice
@@ -9166,12 +9250,19 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     // them), the caller gets them when they fit
     const int32_t need = id_off[n_slots];
     c->evid_off.assign(1, 0);
+    c->evid_lu.clear();
+    c->evid_timed = false;
     c->evid_bytes.assign((size_t)need, 0);
     if (const int rc = ckey_gather_bytes(c, c->k_ev.as<int32_t>(), n_slots, need, c->evid_bytes.data())) {
         c->evid_bytes.clear();
         return rc;
     }
     c->evid_off = id_off;
+    if (times) {
+        if (kx->ev_lu_out && n_slots) memcpy(kx->ev_lu_out, ev_lu.data(), (size_t)n_slots * 8);
+        c->evid_lu = std::move(ev_lu);
+        c->evid_timed = true;
+    }
     *kx->n_id_bytes_out = need;
     if (kx->id_off_out) memcpy(kx->id_off_out, id_off.data(), ((size_t)n_slots + 1) * 4);
     if (need > 0 && kx->max_id_bytes >= need) memcpy(kx->id_bytes_out, c->evid_bytes.data(), (size_t)need);
@@ -9201,9 +9292,41 @@ try {
     std::lock_guard<std::mutex> gb(c->batch_mu);
     std::lock_guard<std::shared_mutex> g(c->mu);
     if (const int rc = caches_bound_guard(c, "mmp_cache_replay_k")) return rc;
-    const ReplayKeyed kx{keys, key_off, key_status_out, key_row_out, ev_id_bytes_out, max_id_bytes, ev_id_off_out, n_id_bytes_out};
+    const ReplayKeyed kx{keys, key_off, key_status_out, key_row_out, ev_id_bytes_out, max_id_bytes, ev_id_off_out, n_id_bytes_out, false, nullptr};
     return cache_replay_drive(c, "mmp_cache_replay_k", ops, n_ops, now, outs, evicted_rows, max_evicted, n_evicted_slots, &kx);
 } MMP_CATCH(c, "mmp_cache_replay_k")
+
+int mmp_cache_replay_kt(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, const char *keys, const int32_t *key_off, int64_t now,
+                        int32_t *key_status_out, int32_t *key_row_out, mmp_cache_op_out *outs, int32_t *evicted_rows, int32_t max_evicted,
+                        int32_t *n_evicted_slots, char *ev_id_bytes_out, int32_t max_id_bytes, int32_t *ev_id_off_out, int32_t *n_id_bytes_out,
+                        int64_t *ev_last_used_out)
+try {
+    if (!c || n_ops < 0 || max_evicted < 0 || (n_ops > 0 && (!ops || !outs)) || (max_evicted > 0 && !evicted_rows) || !n_evicted_slots ||
+        !n_id_bytes_out || max_id_bytes < 0 || (max_id_bytes > 0 && !ev_id_bytes_out) || (keys == nullptr) != (key_off == nullptr) ||
+        (n_ops > 0 && !key_off))
+        return fail(c, MMP_EINVAL, "mmp_cache_replay_kt: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, "mmp_cache_replay_kt")) return rc;
+    const ReplayKeyed kx{keys, key_off, key_status_out, key_row_out, ev_id_bytes_out, max_id_bytes, ev_id_off_out, n_id_bytes_out, true,
+                         ev_last_used_out};
+    return cache_replay_drive(c, "mmp_cache_replay_kt", ops, n_ops, now, outs, evicted_rows, max_evicted, n_evicted_slots, &kx);
+} MMP_CATCH(c, "mmp_cache_replay_kt")
+
+int mmp_cache_evicted_times(mmp_ctx *c, int64_t *out, int32_t max_slots, int32_t *n_slots_out)
+try {
+    if (!c || !n_slots_out || max_slots < 0 || (max_slots > 0 && !out)) return fail(c, MMP_EINVAL, "mmp_cache_evicted_times: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, "mmp_cache_evicted_times")) return rc;
+    if (!c->evid_timed)
+        return fail(c, MMP_ESTATE, "mmp_cache_evicted_times: the last replay recorded no times (mmp_cache_replay_kt records them)");
+    const int32_t ns = (int32_t)c->evid_lu.size();
+    *n_slots_out = ns;
+    if (ns > 0 && max_slots >= ns) memcpy(out, c->evid_lu.data(), (size_t)ns * 8);
+    if (c->prof) c->last_kernel_ms = -1;  // no kernel: the record is words the context holds
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_cache_evicted_times")
 
 int mmp_cache_evicted_ids(mmp_ctx *c, char *bytes_out, int32_t max_bytes, int32_t *off_out, int32_t *n_slots_out, int32_t *n_bytes_out)
 try {

@@ -1010,9 +1010,10 @@ class Solver:
         self._kcache_slots = E
         return rows[:E]
 
-    def cache_replay_k_raw(self, ops, keys, now, max_id_bytes, key_off=None, blob=None, fill=0, max_evicted=None):
+    def cache_replay_k_raw(self, ops, keys, now, max_id_bytes, key_off=None, blob=None, fill=0, max_evicted=None, times=None):
         """mmp_cache_replay_k with a caller-sized id buffer.  Returns a dict: outs, evicted_rows, status, rows, id_off, id_bytes (the
-        raw buffer, `fill` where nothing was written), need."""
+        raw buffer, `fill` where nothing was written), need.  times: None = mmp_cache_replay_k; "out" = mmp_cache_replay_kt, the
+        victims' lastUsed under "last_used"; "ctx" = mmp_cache_replay_kt with a NULL ev_last_used_out (the context keeps them)."""
         from ._lib import CACHE_OP, CACHE_OP_OUT
         ops = np.ascontiguousarray(ops, dtype=CACHE_OP)
         n = len(ops)
@@ -1028,14 +1029,22 @@ class Solver:
         id_off = np.full(max(slots, 0) + 1, fill, np.int32)
         buf = np.full(max(max_id_bytes, 1), fill, np.uint8)
         used, need = C.c_int32(0), C.c_int32(0)
-        self._ck(self.lib.mmp_cache_replay_k(self.h, ptr(ops) if n else None, n, blob, ptr(off), int(now), ptr(status), ptr(rows),
-                                             ptr(outs) if n else None, ptr(ev), slots, C.byref(used), ptr(buf) if max_id_bytes else None,
-                                             int(max_id_bytes), ptr(id_off), C.byref(need)))
+        args = (self.h, ptr(ops) if n else None, n, blob, ptr(off), int(now), ptr(status), ptr(rows), ptr(outs) if n else None, ptr(ev),
+                slots, C.byref(used), ptr(buf) if max_id_bytes else None, int(max_id_bytes), ptr(id_off), C.byref(need))
+        lu = None
+        if times is None:
+            self._ck(self.lib.mmp_cache_replay_k(*args))
+        else:
+            lu = np.full(max(slots, 1), fill, np.int64) if times == "out" else None
+            self._ck(self.lib.mmp_cache_replay_kt(*args, ptr(lu)))
         if max_evicted is None:
             self._kcache_slots = slots
         u = used.value
-        return {"outs": outs, "evicted_rows": ev[:u], "status": status[:n], "rows": rows[:n], "id_off": id_off[: u + 1],
-                "id_bytes": buf[:max_id_bytes], "need": need.value}
+        r = {"outs": outs, "evicted_rows": ev[:u], "status": status[:n], "rows": rows[:n], "id_off": id_off[: u + 1],
+             "id_bytes": buf[:max_id_bytes], "need": need.value}
+        if lu is not None:
+            r["last_used"] = lu[:u]
+        return r
 
     def cache_replay_k(self, ops, keys, now, id_bytes_hint: int = 4096):
         """Apply cache operations by model id (mmp_cache_replay_k).  Returns (outs, evicted_rows, evicted_ids, status, rows):
@@ -1048,6 +1057,26 @@ class Solver:
         else:
             ids = self.cache_evicted_ids()
         return r["outs"], r["evicted_rows"], ids, r["status"], r["rows"]
+
+    def cache_replay_kt(self, ops, keys, now, id_bytes_hint: int = 4096):
+        """cache_replay_k with the victims' lastUsed (mmp_cache_replay_kt): returns (outs, evicted_rows, evicted_ids, status, rows,
+        evicted_last_used); evicted_last_used[s] is the time entry evicted_rows[s] had when it was evicted, 0 for an unused slot."""
+        r = self.cache_replay_k_raw(ops, keys, now, id_bytes_hint, times="out")
+        u = len(r["evicted_rows"])
+        if r["need"] <= id_bytes_hint:
+            ids = self._spans(r["id_bytes"][: r["need"]].tobytes(), r["id_off"], u)
+        else:
+            ids = self.cache_evicted_ids()
+        return r["outs"], r["evicted_rows"], ids, r["status"], r["rows"], r["last_used"]
+
+    def cache_evicted_times(self):
+        """The lastUsed of the victims of the last cache_replay_kt, one per eviction slot (mmp_cache_evicted_times, size then list).
+        MmpError (MMP_ESTATE) when the last replay recorded none."""
+        ns = C.c_int32(0)
+        self._ck(self.lib.mmp_cache_evicted_times(self.h, None, 0, C.byref(ns)))
+        out = np.zeros(max(ns.value, 1), np.int64)
+        self._ck(self.lib.mmp_cache_evicted_times(self.h, ptr(out), ns.value, C.byref(ns)))
+        return out[: ns.value]
 
     def cache_evicted_ids(self):
         """The ids the last cache_replay_k evicted, one per eviction slot (mmp_cache_evicted_ids, sizes then list)."""
@@ -1412,6 +1441,49 @@ class Solver:
                                          ptr(edits) if max_edits else None, int(max_edits), None if null_info else ptr(info))
         ne = max_edits if rc != 0 else min(max_edits, int(info[0]["n_edits"]))
         return idx[:n].copy(), status[:n].copy(), edits[:ne].copy(), info[0].copy(), rc
+
+    def evictions_k(self, entries, keys, self_pod: int, now: int, load_timeout_ms: int, apply: bool = True, dry: bool = False,
+                    max_edits: int = 1024):
+        """onEviction's task body by model id (mmp_evictions_k, MM.java:2886-2920) for a batch of victims — mmp_evicted_entry rows
+        and their ids, e.g. the record of cache_replay_kt: (model_idx, outs, status, edits, info).  outs[i]: EVO_* flags, the
+        deregistration's status, loaded_time, millis_since_last_used.  Regrown like registry_ops_k when truncated."""
+        from ._lib import ROPS_APPLY, ROPS_DRY
+        flags = ROPS_DRY if dry else (ROPS_APPLY if apply else 0)
+        while True:
+            idx, outs, status, edits, info, rc = self.evictions_k_raw(entries, keys, self_pod, now, load_timeout_ms, flags, max_edits)
+            self._ck(rc)
+            if not info["ops"]["truncated"]:
+                break
+            max_edits = max(max_edits, int(info["ops"]["n_edits"]))
+        if flags == ROPS_APPLY and int(info["ops"]["n_edits"]) and getattr(self, "_models", None) is not None:
+            self._models, self._ent_pod, _ = (a.copy() for a in self.get_models())  # the host mirror serve_counters reads
+        return idx, outs, status, edits, info
+
+    def evictions_k_raw(self, entries, keys, self_pod, now, load_timeout_ms, flags, max_edits, fill=0, key_off=None, blob=None):
+        """One mmp_evictions_k call with exactly this edit capacity, the outputs filled with the byte `fill` first:
+        (model_idx, outs, status, edits, info, rc).  Does not raise."""
+        from ._lib import EVICT_PARAMS, EVICTED_ENTRY, EVICTED_OUT, EVICTIONS_INFO, REGISTRY_OP_EDIT
+        entries = np.ascontiguousarray(entries, dtype=EVICTED_ENTRY)
+        n = len(entries)
+        kblob, off = self._pack(keys)
+        off32 = off.astype(np.int32)
+        if blob is not None:
+            kblob = blob
+        if key_off is not None:
+            off32 = np.ascontiguousarray(key_off, dtype=np.int32)
+        p = np.zeros(1, dtype=EVICT_PARAMS)
+        p[0] = (int(self_pod), 0, int(now), int(load_timeout_ms))
+        info = np.zeros(1, dtype=EVICTIONS_INFO)
+        idx = np.zeros(max(n, 1), np.int32)
+        outs = np.zeros(max(n, 1), dtype=EVICTED_OUT)
+        status = np.zeros(max(n, 1), np.uint8)
+        edits = np.zeros(max(max_edits, 1), dtype=REGISTRY_OP_EDIT)
+        for a in (info, idx, outs, status, edits):
+            a.view(np.uint8)[:] = fill
+        rc = self.lib.mmp_evictions_k(self.h, ptr(entries) if n else None, n, kblob, ptr(off32), ptr(p), int(flags), ptr(idx), ptr(outs),
+                                      ptr(status), ptr(edits) if max_edits else None, int(max_edits), ptr(info))
+        ne = max_edits if rc != 0 else min(max_edits, int(info[0]["ops"]["n_edits"]))
+        return idx[:n].copy(), outs[:n].copy(), status[:n].copy(), edits[:ne].copy(), info[0].copy(), rc
 
     def models_status(self, reqs, now: int):
         """getStatus answers (MM.java:3247; class :3760-3768, copy list makeStatusInfo :3013-3058) for a batch of mmp_status_req
