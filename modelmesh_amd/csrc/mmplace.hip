@@ -100,6 +100,26 @@ struct DevBuf {
     T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// A DevBuf built beside a published one: the carrier of the library's ownership rule (written out at mmp_ctx::mid_hash).  Its
+// owner holds batch_mu and declares it ahead of the work; move_into, under the state lock held EXCLUSIVE, publishes it and takes
+// what it replaced, which stays allocated and unwritten until this object ends or is released explicitly.  Between the swap and
+// that end the owner runs the drain (quiesce_decisions: inside the hold, or behind it), so no kernel that captured the replaced
+// buffer is still running when it goes.  Never published: released on every way out, a thrown one included.
+struct ScopedDevBuf {
+    DevBuf b;
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { b.release(); }
+    bool move_into(DevBuf &dst)  // whether there was anything to publish
+    {
+        if (!b.p) return false;
+        std::swap(dst, b);
+        return true;
+    }
+    void release() { b.release(); }
+};
+
 // device storage of one committed snapshot
 struct SnapBufs {
     DevBuf pods, lru, rem, cnt, rpm, orig, pos_of, elig, elig_nors, pref, has_pref, fullw, ge, pc, ph, nz, heads, bslots, bpm, bwin, bsurv, bpcs;
@@ -579,6 +599,8 @@ struct mmp_ctx {
     // (n_models); readers hold batch_mu, or — the request calls by model id on a latency slot — the state lock SHARED while they
     // capture the fields and enqueue.  A buffer a swap retires (the old table, which becomes mid_next_*; an arena or offset array
     // that moved) is neither rewritten nor released before quiesce_decisions has run behind the swap (model_ids_retired_drain).
+    // ScopedDevBuf carries the rule for every buffer that is not one of a ping-pong pair: built in it, published by move_into, the
+    // retired allocation released when it ends.
     // me_*: one call's keys on the device — hashes, resolved rows, dedupe
     // slots, the call-local table (owner | first | first_nd), the flags and their scan, model_idx, the joining events, what the
     // verify found.  (slot / slot_model and the deleted bytes are written where the pipeline reads them: j_ev.)
@@ -645,8 +667,8 @@ struct mmp_ctx {
     // vm_arena_bytes, which nothing a captured table lists refers to.  The published fields change under the state lock held
     // EXCLUSIVE, all in one hold.  Readers hold batch_mu (mmp_vmodels_resolve, _transitions, _get, _info, _write_json), or — the
     // request calls by vmodel id on a latency slot — the state lock SHARED while they capture the fields and enqueue.  What a swap
-    // retires (the old id table, now vid_next_*; the old rows, now vm_rows_next; an arena that moved) is neither rewritten nor
-    // released before quiesce_decisions has run behind the swap (vmodels_retired_drain).
+    // retires (the old id table, now vid_next_*; the old rows, now vm_rows_next; an arena that moved, in its ScopedDevBuf) is neither
+    // rewritten nor released before quiesce_decisions has run behind the swap (vmodels_retired_drain).
     // vq_*: the staged path of the request calls by vmodel id — the nf bytes, their offsets, the flags, the mmp_vseam_row (the keys
     // and the load-target half take kq_*).  Owned by batch_mu, used on c->stream.
     DevBuf vid_hash, vid_val, vid_next_hash, vid_next_val, vid_bytes, vid_off;
@@ -1934,29 +1956,23 @@ hipError_t order_after_registry(mmp_ctx *c, hipStream_t st)
 
 // Growing a table decisions read, without holding them off for the copy: the new allocation is filled beside the old one
 // (batch_mu keeps other writers away), the pointer is swapped under the state lock, and the old allocation is freed once the
-// kernels that captured it have drained.  `old_out` receives the old allocation (released by the caller after quiesce).
-int grow_cow(mmp_ctx *c, DevBuf &b, size_t used, size_t want, DevBuf &fresh)
+// kernels that captured it have drained.  grow_cow fills `fresh` (enqueued on c->stream) where b has to grow, and leaves it
+// empty where it has not; the caller publishes it with move_into and drains before `fresh`, then holding the old allocation, ends.
+int grow_cow(mmp_ctx *c, const DevBuf &b, size_t used, size_t want, ScopedDevBuf &fresh)
 {
     if (want <= b.cap) return MMP_OK;
-    HIP_TRY(c, fresh.ensure(std::max(want, b.cap * 2)));
-    if (used && b.p) HIP_TRY(c, hipMemcpyAsync(fresh.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, fresh.b.ensure(std::max(want, b.cap * 2)));
+    if (used && b.p) HIP_TRY(c, hipMemcpyAsync(fresh.b.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
     return MMP_OK;
 }
 
 int grow_keep(mmp_ctx *c, DevBuf &b, size_t used, size_t want)
 {
     if (want <= b.cap) return MMP_OK;
-    DevBuf nb;
-    HIP_TRY(c, nb.ensure(std::max(want, b.cap * 2)));
-    if (used && b.p) {
-        const hipError_t e = copy_sync(c, nb.p, b.p, used, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            nb.release();
-            HIP_TRY(c, e);
-        }
-    }
-    b.release();
-    b = nb;
+    ScopedDevBuf nb;
+    HIP_TRY(c, nb.b.ensure(std::max(want, b.cap * 2)));
+    if (used && b.p) HIP_TRY(c, copy_sync(c, nb.b.p, b.p, used, hipMemcpyDeviceToDevice));
+    nb.move_into(b);  // (no kernel in flight reads b: the old allocation goes when nb ends)
     return MMP_OK;
 }
 
@@ -1975,42 +1991,28 @@ int compact_registry(mmp_ctx *c)
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, c->u_cnt.as<int32_t>(), c->u_offs.as<int32_t>(), (int32_t)0, (size_t)n + 1,
                                        rocprim::plus<int32_t>(), st));
     HIP_TRY(c, c->u_tmp.ensure(std::max<size_t>(tmp, 16)));
-    DevBuf nm, np, nt;
+    ScopedDevBuf nm, np, nt;
     const size_t cap = (size_t)std::max<int64_t>(c->ent_live + c->ent_live / 2, 1024);
-    auto drop = [&] { nm.release(); np.release(); nt.release(); };
-    if (nm.ensure(std::max<size_t>(c->models.cap, 16)) != hipSuccess || np.ensure(cap * 4) != hipSuccess || nt.ensure(cap * 8) != hipSuccess) {
-        drop();
+    if (nm.b.ensure(std::max<size_t>(c->models.cap, 16)) != hipSuccess || np.b.ensure(cap * 4) != hipSuccess || nt.b.ensure(cap * 8) != hipSuccess)
         return fail(c, MMP_ENOMEM, "compact_registry: out of device memory");
-    }
-    hipError_t e = hipMemcpyAsync(nm.p, c->models.p, (size_t)n * sizeof(mmp_model_row), hipMemcpyDeviceToDevice, st);
+    hipError_t e = hipMemcpyAsync(nm.b.p, c->models.p, (size_t)n * sizeof(mmp_model_row), hipMemcpyDeviceToDevice, st);
     hipLaunchKernelGGL(model_counts_kernel, dim3(div_up(n + 1, 256)), dim3(256), 0, st, c->models.as<mmp_model_row>(), n,
                        c->u_cnt.as<int32_t>());
     (void)rocprim::exclusive_scan(c->u_tmp.p, tmp, c->u_cnt.as<int32_t>(), c->u_offs.as<int32_t>(), (int32_t)0, (size_t)n + 1,
                                   rocprim::plus<int32_t>(), st);
-    hipLaunchKernelGGL(move_entries_kernel, dim3(div_up(std::max(n, 1), 256)), dim3(256), 0, st, nm.as<mmp_model_row>(), n,
-                       c->u_offs.as<int32_t>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), np.as<int32_t>(),
-                       nt.as<int64_t>());
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        drop();
-        HIP_TRY(c, e);
-    }
-    DevBuf om, op, ot;
+    hipLaunchKernelGGL(move_entries_kernel, dim3(div_up(std::max(n, 1), 256)), dim3(256), 0, st, nm.b.as<mmp_model_row>(), n,
+                       c->u_offs.as<int32_t>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), np.b.as<int32_t>(),
+                       nt.b.as<int64_t>());
+    const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
+    HIP_TRY(c, e != hipSuccess ? e : se);
     {
         std::lock_guard<std::shared_mutex> g(c->mu);  // the swap: three pointers
-        om = c->models;
-        op = c->ent_pod;
-        ot = c->ent_time;
-        c->models = nm;
-        c->ent_pod = np;
-        c->ent_time = nt;
+        nm.move_into(c->models);
+        np.move_into(c->ent_pod);
+        nt.move_into(c->ent_time);
         c->n_entries = (int32_t)c->ent_live;
     }
-    const hipError_t q = quiesce_decisions(c);  // kernels that captured the old tables
-    om.release();
-    op.release();
-    ot.release();
-    HIP_TRY(c, q);
+    HIP_TRY(c, quiesce_decisions(c));  // kernels that captured the old tables, which go when nm / np / nt end
     return MMP_OK;
 }
 
@@ -2024,8 +2026,7 @@ int registry_grow(mmp_ctx *c, int32_t count, int32_t base, int32_t n_entries)
                        (size_t)(base + n_entries) * 8 > c->ent_time.cap ||
                        (cur_side(c).rmodels_ok && ((size_t)count * sizeof(ResolvedModel) > cur_side(c).rmodels.cap || (size_t)count * 4 > cur_side(c).mtw.cap));
     if (grows) {  // copy-on-write (grow_cow): decisions are held off for the pointer swap only
-        DevBuf fm, fp, ft, fr, fw;
-        auto drop = [&] { fm.release(); fp.release(); ft.release(); fr.release(); fw.release(); };
+        ScopedDevBuf fm, fp, ft, fr, fw;
         int rc = grow_cow(c, c->models, (size_t)c->n_models * sizeof(mmp_model_row), (size_t)count * sizeof(mmp_model_row), fm);
         if (rc == MMP_OK) rc = grow_cow(c, c->ent_pod, (size_t)base * 4, (size_t)(base + n_entries) * 4, fp);
         if (rc == MMP_OK) rc = grow_cow(c, c->ent_time, (size_t)base * 8, (size_t)(base + n_entries) * 8, ft);
@@ -2034,22 +2035,16 @@ int registry_grow(mmp_ctx *c, int32_t count, int32_t base, int32_t n_entries)
             rc = grow_cow(c, cur_side(c).rmodels, (size_t)c->n_models * sizeof(ResolvedModel), (size_t)count * sizeof(ResolvedModel), fr);
         if (rc == MMP_OK && cur_side(c).rmodels_ok) rc = grow_cow(c, cur_side(c).mtw, (size_t)c->n_models * 4, (size_t)count * 4, fw);
         if (rc == MMP_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, MMP_EHIP, "growing the registry tables failed");
-        if (rc != MMP_OK) {
-            drop();
-            return rc;
-        }
-        DevBuf olds[5];
+        if (rc != MMP_OK) return rc;
         {
             std::lock_guard<std::shared_mutex> g(c->mu);
-            if (fm.p) { olds[0] = c->models; c->models = fm; }
-            if (fp.p) { olds[1] = c->ent_pod; c->ent_pod = fp; }
-            if (ft.p) { olds[2] = c->ent_time; c->ent_time = ft; }
-            if (fr.p) { olds[3] = cur_side(c).rmodels; cur_side(c).rmodels = fr; }
-            if (fw.p) { olds[4] = cur_side(c).mtw; cur_side(c).mtw = fw; }
+            fm.move_into(c->models);
+            fp.move_into(c->ent_pod);
+            ft.move_into(c->ent_time);
+            fr.move_into(cur_side(c).rmodels);
+            fw.move_into(cur_side(c).mtw);
         }
-        const hipError_t q = quiesce_decisions(c);  // kernels that captured the old allocations
-        for (DevBuf &o : olds) o.release();
-        HIP_TRY(c, q);
+        HIP_TRY(c, quiesce_decisions(c));  // kernels that captured the old allocations, which go when fm ... fw end
     }
     return MMP_OK;
 }
@@ -3161,6 +3156,171 @@ int next_table(mmp_ctx *c, const DevBuf &hash, const DevBuf &val, uint32_t cap0,
     return MMP_OK;
 }
 
+// An id table of the context as one host sequence sees it: the model-id table (mid_*) or the vmodel-id table (vid_*).  Both are
+// one ModelIdTab on the device, so one sequence drives the kernels of model_ids_kernels.hpp and retire_kernels.hpp for either.
+struct IdTabRef {
+    DevBuf &hash, &val, &next_hash, &next_val, &bytes, &off;
+    uint32_t &mask;
+    int32_t &n, &nbytes;
+    int32_t hash_bits;
+    ModelIdTab published() const { return ModelIdTab{hash.as<uint64_t>(), val.as<int32_t>(), mask, bytes.as<char>(), off.as<int32_t>()}; }
+};
+extern "C++" IdTabRef model_id_tab(mmp_ctx *c)  // (references: no C linkage inside the file's extern "C" block)
+{
+    return IdTabRef{c->mid_hash, c->mid_val, c->mid_next_hash, c->mid_next_val, c->mid_bytes, c->mid_off, c->mid_mask, c->mid_n, c->mid_nbytes,
+                    c->tune.model_id_hash_bits};
+}
+extern "C++" IdTabRef vmodel_id_tab(mmp_ctx *c)
+{
+    return IdTabRef{c->vid_hash, c->vid_val, c->vid_next_hash, c->vid_next_val, c->vid_bytes, c->vid_off, c->vid_mask, c->vid_n, c->vid_nbytes,
+                    c->tune.vmodel_id_hash_bits};
+}
+
+// ---- The retire frame: what mmp_models_retire, mmp_vmodels_retire and mmp_pods_retire do alike -------------------------------
+// A retire call squeezes named indices out of an index space of N0 and answers remap[old] = new or -1.  With batch_mu held:
+//   guard     retire_list_guard refuses a list out of range or a remap_out too small; a call that retires nothing answers the
+//             identity (retire_nothing) without touching the device;
+//   mark      (registry side) retire_mark_scan: keep[index] from the list, the caller's count kernel, the scan that numbers the
+//             survivors; ONE host round trip brings back the totals and the guard word (an *_ONLY flag refuses here);
+//   build     everything compacted BESIDE what is published, in ScopedDevBufs and the table's next_* pair — for an id table
+//             retire_id_table_room ahead of the bracket, retire_id_table inside it: the survivors' stored hashes claimed under
+//             their new numbers (retire_table_claim, no key is read), then a verifying lookup in a launch of its own;
+//   read      (registry side) retire_build: the SECOND round trip, remap and the lost word; whatever was enqueued has finished
+//             before a new buffer may go;
+//   publish   the caller's swap under the state lock held EXCLUSIVE (an id table: retire_id_table_publish), and its drain.
+// mmp_pods_retire numbers the survivors on the host and reads back one PodsRetireWords: it takes the guard, the table's room, the
+// emptying and the claim from here, and has one round trip in all.
+struct RetireNoun {
+    const char *list, *item, *holder;  // "rows", "row", "the registry"
+};
+int retire_list_guard(mmp_ctx *c, const char *fn, const RetireNoun &w, const int32_t *list, int32_t n, int32_t N0, const int32_t *remap_out,
+                      int32_t max_out)
+{
+    if (remap_out && max_out < N0) return fail(c, MMP_EINVAL, "%s: room for %d %s in remap_out, %s has %d", fn, max_out, w.list, w.holder, N0);
+    for (int32_t i = 0; i < n; i++)
+        if (list[i] < 0 || list[i] >= N0) return fail(c, MMP_EINVAL, "%s: %s[%d] names %s %d of %d", fn, w.list, i, w.item, list[i], N0);
+    return MMP_OK;
+}
+int retire_nothing(mmp_ctx *c, int32_t N0, int32_t *remap_out, int32_t *n_after_out)  // nothing leaves: no launch
+{
+    if (remap_out)
+        for (int32_t r = 0; r < N0; r++) remap_out[r] = r;
+    if (n_after_out) *n_after_out = N0;
+    if (c->prof) c->last_kernel_ms = -1;
+    return MMP_OK;
+}
+
+// What the mark step brings back: the scan's totals, the guard word (INT32_MAX: nothing refused), the caller's own word read in
+// the same round trip, and the bracket's span.  On the device it leaves keep in ret_keep and the scan in me_pos.
+extern "C++" template <class Count>
+struct RetireMarked {
+    Count tot{};
+    int32_t refused = INT32_MAX, extra = INT32_MAX;
+    double ms = 0;
+};
+// list == nullptr: no list is staged and keep is not preset (the caller's mark writes every word of it).  enqueue(d_list, d_keep,
+// d_word, d_cnt) launches the caller's mark and count kernels inside the bracket; d_extra: a device word of the caller's, or nullptr.
+extern "C++" template <class Count, class Plus, class Enqueue>
+int retire_mark_scan(mmp_ctx *c, const int32_t *list, int32_t n, int32_t N0, Enqueue &&enqueue, RetireMarked<Count> &R,
+                     const int32_t *d_extra = nullptr)
+{
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->ret_rows.ensure((size_t)std::max(n, 1) * 4));
+    HIP_TRY(c, c->ret_keep.ensure((size_t)N0 * 4));
+    HIP_TRY(c, c->ret_remap.ensure((size_t)N0 * 4));
+    HIP_TRY(c, c->ret_word.ensure(8));
+    HIP_TRY(c, c->me_cnt.ensure(((size_t)N0 + 1) * sizeof(Count)));
+    HIP_TRY(c, c->me_pos.ensure(((size_t)N0 + 1) * sizeof(Count)));
+    Count *d_cnt = c->me_cnt.as<Count>(), *d_pos = c->me_pos.as<Count>();
+    int32_t *d_keep = c->ret_keep.as<int32_t>(), *d_word = c->ret_word.as<int32_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, Count{}, (size_t)N0 + 1, Plus(), st));
+    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+    if (list) {
+        HIP_TRY(c, hipMemcpyAsync(c->ret_rows.p, list, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_keep), 1, (size_t)N0, st));
+    }
+    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
+    KT_BEGIN(c, st);
+    enqueue(c->ret_rows.as<int32_t>(), d_keep, d_word, d_cnt);
+    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, Count{}, (size_t)N0 + 1, Plus(), st));
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&R.refused, d_word, 4, hipMemcpyDeviceToHost, st));
+    if (d_extra) HIP_TRY(c, hipMemcpyAsync(&R.extra, d_extra, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, copy_sync(c, &R.tot, d_pos + N0, sizeof R.tot, hipMemcpyDeviceToHost));
+    kt_collect(c);
+    R.ms = c->last_kernel_ms;
+    return MMP_OK;
+}
+
+// The survivors' stored hashes of the published table hash / val claimed in the emptied `next` under their new numbers (enqueued)
+void retire_table_claim(mmp_ctx *c, const DevBuf &hash, const DevBuf &val, uint32_t cap0, const int32_t *d_remap, const HashTabW &next)
+{
+    hipLaunchKernelGGL(retire_table_kernel, dim3(div_up((int)cap0, kRetireBlock)), dim3(kRetireBlock), 0, c->stream, hash.as<uint64_t>(),
+                       val.as<int32_t>(), cap0, d_remap, next);
+}
+
+// The compacted id table of T, for `survivors` ids of `bytes` bytes.  _room, ahead of the bracket: the id arena in nb / no, the
+// table (it may shrink: tab_capacity(survivors)) in T.next_*, emptied, and new_off[0] = 0.  A failure behind the first enqueue
+// waits for the stream before it returns: nb / no go with the caller.
+int retire_id_table_room(mmp_ctx *c, const char *fn, const IdTabRef &T, int32_t survivors, int32_t bytes, ScopedDevBuf &nb, ScopedDevBuf &no,
+                         HashTabW &next)
+{
+    if (nb.b.ensure((size_t)bytes + 16) != hipSuccess || no.b.ensure(((size_t)survivors + 1) * 4) != hipSuccess ||
+        next_table_room(c, 0, survivors, T.next_hash, T.next_val, next) != MMP_OK)
+        return fail(c, MMP_ENOMEM, "%s: out of device memory", fn);
+    int rc = empty_table(c, next);
+    if (rc == MMP_OK && hipMemsetAsync(no.b.p, 0, 4, c->stream) != hipSuccess) rc = fail(c, MMP_EHIP, "%s: hipMemsetAsync failed", fn);
+    if (rc != MMP_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+// inside the bracket, behind the caller's move kernel (which wrote d_remap and the arena): the claims, then the verifying lookup of
+// every survivor's id in a launch of its own; *d_lost: the lowest new row it did not find
+void retire_id_table(mmp_ctx *c, const IdTabRef &T, const int32_t *d_remap, const HashTabW &next, const ScopedDevBuf &nb, const ScopedDevBuf &no,
+                     int32_t *d_lost)
+{
+    const uint32_t cap0 = T.mask + 1;
+    retire_table_claim(c, T.hash, T.val, cap0, d_remap, next);
+    hipLaunchKernelGGL(retire_verify_kernel, dim3(div_up((int)cap0, kRetireBlock)), dim3(kRetireBlock), 0, c->stream, T.hash.as<uint64_t>(),
+                       T.val.as<int32_t>(), cap0, d_remap, ModelIdTab{next.hash, next.val, next.mask, nb.b.as<char>(), no.b.as<int32_t>()}, d_lost);
+}
+// under the state lock held EXCLUSIVE: the table, the arena and the counts change together; nb / no hold the old arena afterwards
+void retire_id_table_publish(const IdTabRef &T, const HashTabW &next, ScopedDevBuf &nb, ScopedDevBuf &no, int32_t survivors, int32_t bytes)
+{
+    std::swap(T.hash, T.next_hash);
+    std::swap(T.val, T.next_val);
+    nb.move_into(T.bytes);
+    no.move_into(T.off);
+    T.mask = next.mask;
+    T.n = survivors;
+    T.nbytes = bytes;
+}
+
+// The second round trip of a registry-side retire.  enqueue() launches the caller's move kernel and, for an id table,
+// retire_id_table, inside the bracket; remap (N0 words) and the lost word come back behind them.  The stream is waited for on
+// every way out: whatever was enqueued has finished before the caller's new buffers may go.  mark_ms: the first bracket's span.
+extern "C++" template <class Enqueue>
+int retire_build(mmp_ctx *c, const char *fn, int32_t N0, double mark_ms, Enqueue &&enqueue, std::vector<int32_t> &remap)
+{
+    hipStream_t st = c->stream;
+    const int32_t *d_remap = c->ret_remap.as<int32_t>(), *d_lost = c->ret_word.as<int32_t>() + 1;
+    int32_t lost = INT32_MAX;
+    KT_BEGIN(c, st);
+    enqueue();
+    KT_END(c, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(remap.data(), d_remap, (size_t)N0 * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&lost, d_lost, 4, hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return fail(c, MMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    if (lost != INT32_MAX) return fail(c, MMP_EHIP, "%s: the id of new row %d was not found in the compacted table", fn, lost);
+    kt_collect(c);
+    kt_add(c, mark_ms);  // the call's device span: mark + scan + move + table + verify
+    return MMP_OK;
+}
+
 // What ingest_models_kernel is given by either caller, for n staged values of `bytes` bytes: the tables, the per-record status /
 // lul / count words, and the parking arrays: ent_cap slots (ingest_kernels.hpp, the parking rule: n entries take >= 5n + 1 bytes
 // of JSON).  The rows and the event members are the caller's to set.
@@ -3819,41 +3979,16 @@ try {
 } MMP_CATCH(c, "mmp_models_upsert_json")
 
 namespace {
-// An id table of the context as the by-key sequence below sees it: the model-id table (mid_*) or the vmodel-id table (vid_*).
-// Both are one ModelIdTab on the device, so one host sequence drives the kernels of model_ids_kernels.hpp for either.
-struct IdTabRef {
-    DevBuf &hash, &val, &next_hash, &next_val, &bytes, &off;
-    uint32_t &mask;
-    int32_t &n, &nbytes;
-    int32_t hash_bits;
-    ModelIdTab published() const { return ModelIdTab{hash.as<uint64_t>(), val.as<int32_t>(), mask, bytes.as<char>(), off.as<int32_t>()}; }
-};
-extern "C++" IdTabRef model_id_tab(mmp_ctx *c)  // (references: no C linkage inside the file's extern "C" block)
-{
-    return IdTabRef{c->mid_hash, c->mid_val, c->mid_next_hash, c->mid_next_val, c->mid_bytes, c->mid_off, c->mid_mask, c->mid_n, c->mid_nbytes,
-                    c->tune.model_id_hash_bits};
-}
-extern "C++" IdTabRef vmodel_id_tab(mmp_ctx *c)
-{
-    return IdTabRef{c->vid_hash, c->vid_val, c->vid_next_hash, c->vid_next_val, c->vid_bytes, c->vid_off, c->vid_mask, c->vid_n, c->vid_nbytes,
-                    c->tune.vmodel_id_hash_bits};
-}
-
 // One call's keys resolved, deduplicated and numbered on the device, and the table / arena that would hold the joining ids built
 // beside the published ones.  Nothing of the context's published state has changed until model_ids_publish.
 struct ModelIdsPlan {
     int32_t k = 0, n_join = 0, join_bytes = 0;  // distinct applicable rows; ids that join; their bytes
     int32_t n_before = 0, bytes_before = 0;
     uint32_t cap = 0;                // capacity of the table built in mid_next_* (0: none was needed)
-    DevBuf fresh_bytes, fresh_off;   // the arena, where it had to move (or is replaced)
-    DevBuf old_bytes, old_off;       // after model_ids_publish: the arena it replaced (released with the plan)
-    bool swapped = false;            // ... and whether the publish retired anything a captured ModelIdTab may name
+    ScopedDevBuf fresh_bytes, fresh_off;  // the arena, where it had to move (or is replaced); after model_ids_publish: what it replaced
+    bool swapped = false;            // whether the publish retired anything a captured ModelIdTab may name
     std::vector<int32_t> idx;        // model_idx per event
     double ms = 0;                   // device span (profiling)
-    ~ModelIdsPlan()
-    {
-        for (DevBuf *b : {&fresh_bytes, &fresh_off, &old_bytes, &old_off}) b->release();
-    }
 };
 
 // The staged keys (ida_*) hashed once into me_hash and looked up in `tab` into me_row (enqueued inside the caller's bracket)
@@ -3924,15 +4059,15 @@ int model_ids_plan(mmp_ctx *c, const IdTabRef &T, const char *fn, const char *ke
     if ((int64_t)B0 + P.join_bytes > INT32_MAX) return fail(c, MMP_EINVAL, "%s: more than 2^31 id bytes", fn);
     // 2. the arena the joining ids are appended to: in place beyond the published rows, or moved when it has to grow
     if (replace) {
-        HIP_TRY(c, P.fresh_bytes.ensure((size_t)P.join_bytes + 16));
-        HIP_TRY(c, P.fresh_off.ensure(((size_t)P.n_join + 1) * 4));
-        HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, st));
+        HIP_TRY(c, P.fresh_bytes.b.ensure((size_t)P.join_bytes + 16));
+        HIP_TRY(c, P.fresh_off.b.ensure(((size_t)P.n_join + 1) * 4));
+        HIP_TRY(c, hipMemsetAsync(P.fresh_off.b.p, 0, 4, st));
     } else {
         if (const int rc = grow_cow(c, T.bytes, (size_t)B0, (size_t)B0 + P.join_bytes, P.fresh_bytes)) return rc;
         if (const int rc = grow_cow(c, T.off, ((size_t)M0 + 1) * 4, ((size_t)M0 + P.n_join + 1) * 4, P.fresh_off)) return rc;
     }
-    char *a_bytes = P.fresh_bytes.p ? P.fresh_bytes.as<char>() : T.bytes.as<char>();
-    int32_t *a_off = P.fresh_off.p ? P.fresh_off.as<int32_t>() : T.off.as<int32_t>();
+    char *a_bytes = P.fresh_bytes.b.p ? P.fresh_bytes.b.as<char>() : T.bytes.as<char>();
+    int32_t *a_off = P.fresh_off.b.p ? P.fresh_off.b.as<int32_t>() : T.off.as<int32_t>();
     // 3. number the events; 4. the next table, copy-on-write, and a verifying lookup in a launch of its own
     KT_BEGIN(c, st);
     hipLaunchKernelGGL(mid_number_kernel, grid, block, 0, st, n, M0, P.k, c->me_row.as<int32_t>(), c->me_slot.as<int32_t>(), B, append ? 1 : 0,
@@ -3966,8 +4101,8 @@ int model_ids_plan(mmp_ctx *c, const IdTabRef &T, const char *fn, const char *ke
 
 // nothing fails from here on: the table, the arena and the counts change together (batch_mu held, the stream idle; for the
 // model-id table the state lock held exclusive as well: the ownership rule at mmp_ctx::mid_hash).  What the swap retires stays
-// allocated and unwritten: the old table is mid_next_* now, the old arena goes to the plan, which releases it when it ends —
-// for the model-id table only behind model_ids_retired_drain.
+// allocated and unwritten: the old table is mid_next_* now, the old arena stands in the plan's ScopedDevBufs, which release it
+// when the plan ends — for the model-id table only behind model_ids_retired_drain.
 void model_ids_publish(const IdTabRef &T, ModelIdsPlan &P)
 {
     if (P.cap) {
@@ -3975,17 +4110,8 @@ void model_ids_publish(const IdTabRef &T, ModelIdsPlan &P)
         std::swap(T.val, T.next_val);
         T.mask = P.cap - 1;
     }
-    if (P.fresh_bytes.p) {
-        P.old_bytes = T.bytes;
-        T.bytes = P.fresh_bytes;
-        P.fresh_bytes = DevBuf{};
-    }
-    if (P.fresh_off.p) {
-        P.old_off = T.off;
-        T.off = P.fresh_off;
-        P.fresh_off = DevBuf{};
-    }
-    P.swapped = P.cap || P.old_bytes.p || P.old_off.p;
+    const bool moved_bytes = P.fresh_bytes.move_into(T.bytes), moved_off = P.fresh_off.move_into(T.off);
+    P.swapped = P.cap || moved_bytes || moved_off;
     T.n = P.n_before + P.n_join;
     T.nbytes = P.bytes_before + P.join_bytes;
 }
@@ -4019,10 +4145,10 @@ try {
         HashTabW nt;
         if (const int rc = next_table_room(c, 0, 0, c->mid_next_hash, c->mid_next_val, nt)) return rc;
         P.cap = nt.mask + 1;
-        HIP_TRY(c, P.fresh_bytes.ensure(16));
-        HIP_TRY(c, P.fresh_off.ensure(4));
+        HIP_TRY(c, P.fresh_bytes.b.ensure(16));
+        HIP_TRY(c, P.fresh_off.b.ensure(4));
         if (const int rc = next_table(c, c->mid_hash, c->mid_val, 0, nt)) return rc;
-        HIP_TRY(c, hipMemsetAsync(P.fresh_off.p, 0, 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(P.fresh_off.b.p, 0, 4, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
         if (const int rc = model_ids_plan(c, model_id_tab(c), "mmp_model_ids_load", ids, id_off, n_models, nullptr, true, true, P)) return rc;
@@ -4135,18 +4261,6 @@ try {
 } MMP_CATCH(c, "mmp_models_events_json")
 
 namespace {
-// A DevBuf built beside a published one.  move_into (under the state lock held exclusive) publishes it and takes what it replaced,
-// which stays allocated and unwritten until this object ends: its owner declares it ahead of the work and runs
-// vmodels_retired_drain between the swap and its own return (the ownership rule at mmp_ctx::vid_hash).  Never handed over: released.
-struct ScopedDevBuf {
-    DevBuf b;
-    ~ScopedDevBuf() { b.release(); }
-    void move_into(DevBuf &dst)
-    {
-        if (b.p) std::swap(dst, b);
-    }
-};
-
 // Behind a swap of the vmodel table, with batch_mu and without the state lock (model_ids_retired_drain for the vmodel side): a
 // request call by vmodel id that captured the table before the swap may still be running on a latency slot; it was enqueued under
 // the state lock, so quiesce_decisions sees it.  Only then may what the swap retired be rewritten (vid_next_*, vm_rows_next: by the
@@ -4270,7 +4384,7 @@ try {
         const int32_t base = c->vm_arena_bytes;
         if ((int64_t)base + tot.add > INT32_MAX)  // (nothing but scratch has been written so far)
             return fail(c, MMP_EINVAL, "mmp_vmodels_events_json: more than 2^31 bytes in the string arena");
-        if (const int rc = grow_cow(c, c->vm_arena, (size_t)base, (size_t)base + tot.add + 16, fresh_arena.b)) return rc;
+        if (const int rc = grow_cow(c, c->vm_arena, (size_t)base, (size_t)base + tot.add + 16, fresh_arena)) return rc;
         VmRow *rows = rows_beside ? c->vm_rows_next.as<VmRow>() : c->vm_rows.as<VmRow>();
         char *arena = fresh_arena.b.p ? fresh_arena.b.as<char>() : c->vm_arena.as<char>();
         // nothing is refused from here on: the winners' strings behind the published bytes, the rows beside the published ones
@@ -4462,115 +4576,59 @@ try {
     if (!c || n < 0 || (n > 0 && !rows) || (flags & ~(MMP_VMRETIRE_ABSENT_ONLY | MMP_VMRETIRE_ALL_ABSENT)) || max_vmodels < 0)
         return fail(c, MMP_EINVAL, "mmp_vmodels_retire: bad argument");
     if (all && n > 0) return fail(c, MMP_EINVAL, "mmp_vmodels_retire: MMP_VMRETIRE_ALL_ABSENT takes no list (n = %d)", n);
-    // The ownership rule at mmp_ctx::vid_hash: batch_mu for the call, the compacted rows, arenas and table built BESIDE the published
-    // ones (the request calls by vmodel id go on reading those from the latency slots), the state lock exclusive for the swap only,
-    // and the drain behind it before anything the swap retired is released.  No decision kernel reads a vmodel row: no rebuild_resolved.
+    // The retire frame (at retire_list_guard).  Its own: the state lock for the swap only, the drain BEHIND the hold (the request calls
+    // by vmodel id go on reading the old table from the latency slots); no decision kernel reads a vmodel row: no rebuild_resolved.
     std::lock_guard<std::mutex> gb(c->batch_mu);
+    const char *fn = "mmp_vmodels_retire";
     const int32_t V0 = c->have_vmodels ? c->vid_n : 0;
-    if (remap_out && max_vmodels < V0)
-        return fail(c, MMP_EINVAL, "mmp_vmodels_retire: room for %d rows in remap_out, the table has %d", max_vmodels, V0);
-    for (int32_t i = 0; i < n; i++)
-        if (rows[i] < 0 || rows[i] >= V0) return fail(c, MMP_EINVAL, "mmp_vmodels_retire: rows[%d] names row %d of %d", i, rows[i], V0);
-    auto unchanged = [&] {
-        if (remap_out)
-            for (int32_t r = 0; r < V0; r++) remap_out[r] = r;
-        if (n_vmodels_after_out) *n_vmodels_after_out = V0;
-        return (int)MMP_OK;
-    };
-    if (all ? c->vm_live_rows == V0 : n == 0) {  // nothing leaves: no squeeze, no launch
-        if (c->prof) c->last_kernel_ms = -1;
-        return unchanged();
-    }
+    if (const int rc = retire_list_guard(c, fn, RetireNoun{"rows", "row", "the table"}, rows, n, V0, remap_out, max_vmodels)) return rc;
+    if (all ? c->vm_live_rows == V0 : n == 0) return retire_nothing(c, V0, remap_out, n_vmodels_after_out);  // (no squeeze either)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    HIP_TRY(c, c->ret_rows.ensure((size_t)std::max(n, 1) * 4));
-    HIP_TRY(c, c->ret_keep.ensure((size_t)V0 * 4));
-    HIP_TRY(c, c->ret_remap.ensure((size_t)V0 * 4));
-    HIP_TRY(c, c->ret_word.ensure(8));
-    HIP_TRY(c, c->me_cnt.ensure(((size_t)V0 + 1) * sizeof(VmRetireCount)));
-    HIP_TRY(c, c->me_pos.ensure(((size_t)V0 + 1) * sizeof(VmRetireCount)));
-    VmRetireCount *d_cnt = c->me_cnt.as<VmRetireCount>(), *d_pos = c->me_pos.as<VmRetireCount>();
-    int32_t *d_keep = c->ret_keep.as<int32_t>(), *d_remap = c->ret_remap.as<int32_t>(), *d_word = c->ret_word.as<int32_t>();
-    size_t scan_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, VmRetireCount{0, 0, 0, 0}, (size_t)V0 + 1, VmRetirePlus(), st));
-    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-    if (!all) {
-        HIP_TRY(c, hipMemcpyAsync(c->ret_rows.p, rows, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_keep), 1, (size_t)V0, st));
-    }
-    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
+    const IdTabRef T = vmodel_id_tab(c);
     const dim3 block(kRetireBlock), vgrid(div_up(V0, kRetireBlock));
     const VmRow *old_rows = c->vm_rows.as<VmRow>();
-    const int32_t *old_off = c->vid_off.as<int32_t>();
-    // 1. mark — the list, and with ABSENT_ONLY the lowest named row that is not ABSENT, or every ABSENT row; the counts and their scan
-    KT_BEGIN(c, st);
-    if (all)
-        hipLaunchKernelGGL(vm_retire_absent_kernel, vgrid, block, 0, st, V0, old_rows, d_keep);
-    else
-        hipLaunchKernelGGL(vm_retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, c->ret_rows.as<int32_t>(), n, old_rows,
-                           (flags & MMP_VMRETIRE_ABSENT_ONLY) ? 1 : 0, d_keep, d_word);
-    hipLaunchKernelGGL(vm_retire_count_kernel, dim3(div_up(V0 + 1, kRetireBlock)), block, 0, st, V0, d_keep, old_rows, old_off, d_cnt);
-    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, VmRetireCount{0, 0, 0, 0}, (size_t)V0 + 1, VmRetirePlus(), st));
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    int32_t word[2] = {INT32_MAX, INT32_MAX};
-    VmRetireCount tot{};
-    HIP_TRY(c, hipMemcpyAsync(word, d_word, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, copy_sync(c, &tot, d_pos + V0, sizeof tot, hipMemcpyDeviceToHost));
-    kt_collect(c);
-    const double mark_ms = c->last_kernel_ms;
-    if (word[0] != INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_vmodels_retire: row %d is not ABSENT (set again since its deletion?); nothing was retired", word[0]);
-    const int32_t V1 = tot.row, B1 = tot.bytes, S1 = tot.strs;
-    // 2. the compacted rows, string arena, id arena and table, beside the published ones
-    ScopedDevBuf nr, na, nb, no;
-    const uint32_t cap0 = c->vid_mask + 1, cap1 = tab_capacity(V1);
-    if (nr.b.ensure((size_t)std::max(V1, 1) * sizeof(VmRow)) != hipSuccess || na.b.ensure((size_t)S1 + 16) != hipSuccess ||
-        nb.b.ensure((size_t)B1 + 16) != hipSuccess || no.b.ensure(((size_t)V1 + 1) * 4) != hipSuccess ||
-        c->vid_next_hash.ensure((size_t)cap1 * 8) != hipSuccess || c->vid_next_val.ensure((size_t)cap1 * 4) != hipSuccess)
-        return fail(c, MMP_ENOMEM, "mmp_vmodels_retire: out of device memory");
-    const HashTabW next{c->vid_next_hash.as<uint64_t>(), c->vid_next_val.as<int32_t>(), cap1 - 1};
-    int rc = empty_table(c, next);
-    if (rc == MMP_OK && hipMemsetAsync(no.b.p, 0, 4, st) != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: hipMemsetAsync failed");
+    // mark — the list, and with ABSENT_ONLY the lowest named row that is not ABSENT, or every ABSENT row
+    RetireMarked<VmRetireCount> K;
+    if (const int rc = retire_mark_scan<VmRetireCount, VmRetirePlus>(
+            c, all ? nullptr : rows, n, V0,
+            [&](const int32_t *d_list, int32_t *d_keep, int32_t *d_word, VmRetireCount *d_cnt) {
+                if (all)
+                    hipLaunchKernelGGL(vm_retire_absent_kernel, vgrid, block, 0, st, V0, old_rows, d_keep);
+                else
+                    hipLaunchKernelGGL(vm_retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, d_list, n, old_rows,
+                                       (flags & MMP_VMRETIRE_ABSENT_ONLY) ? 1 : 0, d_keep, d_word);
+                hipLaunchKernelGGL(vm_retire_count_kernel, dim3(div_up(V0 + 1, kRetireBlock)), block, 0, st, V0, d_keep, old_rows, T.off.as<int32_t>(),
+                                   d_cnt);
+            },
+            K))
+        return rc;
+    if (K.refused != INT32_MAX)
+        return fail(c, MMP_EINVAL, "%s: row %d is not ABSENT (set again since its deletion?); nothing was retired", fn, K.refused);
+    const int32_t V1 = K.tot.row, B1 = K.tot.bytes, S1 = K.tot.strs;
+    // build: the compacted rows, string arena, id arena and table
     std::vector<int32_t> remap((size_t)V0);
-    if (rc == MMP_OK) {
-        const VmRetireMove A{old_rows, c->vm_arena.as<char>(), c->vid_bytes.as<char>(), old_off, nr.b.as<VmRow>(), na.b.as<char>(),
-                             nb.b.as<char>(), no.b.as<int32_t>()};
-        // 3. the stored hashes of the survivors into the emptied next table; 4. a verifying lookup in a launch of its own
-        const dim3 sgrid(div_up((int)cap0, kRetireBlock));
-        KT_BEGIN(c, st);
-        hipLaunchKernelGGL(vm_retire_move_kernel, vgrid, block, 0, st, V0, d_keep, d_pos, A, d_remap);
-        hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->vid_hash.as<uint64_t>(), c->vid_val.as<int32_t>(), cap0, d_remap, next);
-        hipLaunchKernelGGL(retire_verify_kernel, sgrid, block, 0, st, c->vid_hash.as<uint64_t>(), c->vid_val.as<int32_t>(), cap0, d_remap,
-                           ModelIdTab{next.hash, next.val, next.mask, nb.b.as<char>(), no.b.as<int32_t>()}, d_word + 1);
-        KT_END(c, st);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(remap.data(), d_remap, (size_t)V0 * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(word + 1, d_word + 1, 4, hipMemcpyDeviceToHost, st);
-        const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
-        if (e == hipSuccess) e = se;
-        if (e != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: %s", hipGetErrorString(e));
-    } else
-        (void)hipStreamSynchronize(st);
-    if (rc == MMP_OK && word[1] != INT32_MAX)
-        rc = fail(c, MMP_EHIP, "mmp_vmodels_retire: the id of new row %d was not found in the compacted table", word[1]);
+    ScopedDevBuf nr, na, nb, no;
+    HashTabW next{};
+    if (nr.b.ensure((size_t)std::max(V1, 1) * sizeof(VmRow)) != hipSuccess || na.b.ensure((size_t)S1 + 16) != hipSuccess)
+        return fail(c, MMP_ENOMEM, "%s: out of device memory", fn);
+    if (const int rc = retire_id_table_room(c, fn, T, V1, B1, nb, no, next)) return rc;
+    const VmRetireMove A{old_rows, c->vm_arena.as<char>(), T.bytes.as<char>(), T.off.as<int32_t>(), nr.b.as<VmRow>(), na.b.as<char>(),
+                         nb.b.as<char>(), no.b.as<int32_t>()};
+    int32_t *d_remap = c->ret_remap.as<int32_t>();
+    const int rc = retire_build(c, fn, V0, K.ms, [&] {
+        hipLaunchKernelGGL(vm_retire_move_kernel, vgrid, block, 0, st, V0, c->ret_keep.as<int32_t>(), c->me_pos.as<VmRetireCount>(), A, d_remap);
+        retire_id_table(c, T, d_remap, next, nb, no, c->ret_word.as<int32_t>() + 1);
+    }, remap);
     if (rc != MMP_OK) return rc;
-    kt_collect(c);
-    kt_add(c, mark_ms);  // the call's device span: mark + scan + move + table + verify
     {
         std::lock_guard<std::shared_mutex> g(c->mu);  // nothing fails from here on: rows, arenas, table and counts change together
         nr.move_into(c->vm_rows);
         na.move_into(c->vm_arena);
-        nb.move_into(c->vid_bytes);
-        no.move_into(c->vid_off);
-        std::swap(c->vid_hash, c->vid_next_hash);
-        std::swap(c->vid_val, c->vid_next_val);
-        c->vid_mask = cap1 - 1;
-        c->vid_n = V1;
-        c->vid_nbytes = B1;
+        retire_id_table_publish(T, next, nb, no, V1, B1);
         c->vm_arena_bytes = S1;
         c->vm_live_bytes = S1;
-        c->vm_live_rows = tot.live;
+        c->vm_live_rows = K.tot.live;
         c->have_vmodels = V1 > 0;  // (no row: the state before the first vmodel call, which the next event batch starts from)
     }
     // a request call by vmodel id saw the numbering before the swap or sees the one after it; the ones that captured the old rows,
@@ -4586,42 +4644,20 @@ int mmp_models_retire(mmp_ctx *c, const int32_t *rows, int32_t n, uint32_t flags
 try {
     if (!c || n < 0 || (n > 0 && !rows) || (flags & ~MMP_RETIRE_EMPTY_ONLY) || max_models < 0)
         return fail(c, MMP_EINVAL, "mmp_models_retire: bad argument");
-    // batch_mu keeps every other writer of the registry and the id table away while the compacted tables are built BESIDE the
-    // published ones (decisions go on reading those); the state lock is taken for the swap and the re-resolution only.
+    // The retire frame (at retire_list_guard).  Its own: the drain INSIDE the hold, which also covers the re-resolution.
     std::lock_guard<std::mutex> gb(c->batch_mu);
+    const char *fn = "mmp_models_retire";
     const int32_t M0 = c->n_models;
     const bool ids = c->have_model_ids;
     if (ids && c->mid_n != M0)
-        return fail(c, MMP_ESTATE, "mmp_models_retire: the registry has %d rows for %d loaded model ids (resized by index since mmp_model_ids_load)",
-                    M0, c->mid_n);
-    if (remap_out && max_models < M0) return fail(c, MMP_EINVAL, "mmp_models_retire: room for %d rows in remap_out, the registry has %d", max_models, M0);
-    for (int32_t i = 0; i < n; i++)
-        if (rows[i] < 0 || rows[i] >= M0) return fail(c, MMP_EINVAL, "mmp_models_retire: rows[%d] names row %d of %d", i, rows[i], M0);
-    if (n == 0) {
-        if (remap_out)
-            for (int32_t r = 0; r < M0; r++) remap_out[r] = r;
-        if (n_models_after_out) *n_models_after_out = M0;
-        if (c->prof) c->last_kernel_ms = -1;  // no kernel
-        return MMP_OK;
-    }
+        return fail(c, MMP_ESTATE, "%s: the registry has %d rows for %d loaded model ids (resized by index since mmp_model_ids_load)", fn, M0, c->mid_n);
+    if (const int rc = retire_list_guard(c, fn, RetireNoun{"rows", "row", "the registry"}, rows, n, M0, remap_out, max_models)) return rc;
+    if (n == 0) return retire_nothing(c, M0, remap_out, n_models_after_out);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
-    HIP_TRY(c, c->ret_rows.ensure((size_t)n * 4));
-    HIP_TRY(c, c->ret_keep.ensure((size_t)M0 * 4));
-    HIP_TRY(c, c->ret_remap.ensure((size_t)M0 * 4));
-    HIP_TRY(c, c->ret_word.ensure(8));
-    HIP_TRY(c, c->me_cnt.ensure(((size_t)M0 + 1) * sizeof(RetireCount)));
-    HIP_TRY(c, c->me_pos.ensure(((size_t)M0 + 1) * sizeof(RetireCount)));
-    RetireCount *d_cnt = c->me_cnt.as<RetireCount>(), *d_pos = c->me_pos.as<RetireCount>();
-    int32_t *d_keep = c->ret_keep.as<int32_t>(), *d_remap = c->ret_remap.as<int32_t>(), *d_word = c->ret_word.as<int32_t>();
-    size_t scan_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_pos, RetireCount{0, 0, 0}, (size_t)M0 + 1, RetirePlus(), st));
-    HIP_TRY(c, c->j_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-    HIP_TRY(c, hipMemcpyAsync(c->ret_rows.p, rows, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_keep), 1, (size_t)M0, st));
-    HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_word), INT32_MAX, 2, st));
+    const IdTabRef T = model_id_tab(c);
     const dim3 block(kRetireBlock);
-    const int32_t *old_off = ids ? c->mid_off.as<int32_t>() : nullptr;
+    const int32_t *old_off = ids ? T.off.as<int32_t>() : nullptr;
     // bound caches are carried along (cache_keyed_kernels.hpp); the cache calls hold batch_mu too, so the store stands still
     const bool carry = c->k_bound && c->k_caches > 0 && c->k_slots > 0;
     mmp_ctx::KeyedStore &KS = c->ks[c->ks_cur];
@@ -4632,94 +4668,52 @@ try {
         d_live_key = c->k_len.as<int32_t>();
         HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_live_key), INT32_MAX, 1, st));
     }
-    // 1. mark, and with the flag the lowest named row that is not empty; the triples and their scan
-    KT_BEGIN(c, st);
-    hipLaunchKernelGGL(retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, c->ret_rows.as<int32_t>(), n, c->models.as<mmp_model_row>(),
-                       (flags & MMP_RETIRE_EMPTY_ONLY) ? 1 : 0, d_keep, d_word);
-    if (carry)  // the lowest named row that is the key of a live entry
-        hipLaunchKernelGGL(ckey_retire_check_kernel, dim3(div_up(c->k_slots, kRetireBlock)), block, 0, st, kstore, c->k_caches, c->k_slots, M0,
-                           d_keep, d_live_key);
-    hipLaunchKernelGGL(retire_flags_kernel, dim3(div_up(M0 + 1, kRetireBlock)), block, 0, st, M0, d_keep, c->models.as<mmp_model_row>(), old_off, d_cnt);
-    HIP_TRY(c, rocprim::exclusive_scan(c->j_scan_tmp.p, scan_bytes, d_cnt, d_pos, RetireCount{0, 0, 0}, (size_t)M0 + 1, RetirePlus(), st));
-    KT_END(c, st);
-    HIP_TRY(c, hipGetLastError());
-    int32_t word[2] = {INT32_MAX, INT32_MAX};
-    RetireCount tot{};
-    int32_t live_key = INT32_MAX;
-    HIP_TRY(c, hipMemcpyAsync(word, d_word, 4, hipMemcpyDeviceToHost, st));
-    if (carry) HIP_TRY(c, hipMemcpyAsync(&live_key, d_live_key, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, copy_sync(c, &tot, d_pos + M0, sizeof tot, hipMemcpyDeviceToHost));
-    kt_collect(c);
-    const double mark_ms = c->last_kernel_ms;
-    if (word[0] != INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_models_retire: row %d is not empty (registered again since its deletion?); nothing was retired", word[0]);
-    if (live_key != INT32_MAX)
-        return fail(c, MMP_EINVAL, "mmp_models_retire: row %d is the key of a live cache entry (remove the entry first); nothing was retired",
-                    live_key);
-    const int32_t M1 = tot.row, B1 = tot.bytes, E1 = tot.ents;
-    // 2. the compacted registry, id arena and table, beside the published ones
-    DevBuf nm, np, nt, nb, no;
-    auto drop = [&] { nm.release(); np.release(); nt.release(); nb.release(); no.release(); };
-    const size_t ecap = (size_t)std::max<int64_t>((int64_t)E1 + E1 / 2, 1024);
-    bool room = nm.ensure((size_t)std::max(M1, 1) * sizeof(mmp_model_row)) == hipSuccess && np.ensure(ecap * 4) == hipSuccess &&
-                nt.ensure(ecap * 8) == hipSuccess;
-    const uint32_t cap0 = ids ? c->mid_mask + 1 : 0u, cap1 = tab_capacity(M1);
-    HashTabW next{};
-    if (room && ids)
-        room = nb.ensure((size_t)B1 + 16) == hipSuccess && no.ensure(((size_t)M1 + 1) * 4) == hipSuccess &&
-               c->mid_next_hash.ensure((size_t)cap1 * 8) == hipSuccess && c->mid_next_val.ensure((size_t)cap1 * 4) == hipSuccess;
-    if (!room) {
-        drop();
-        return fail(c, MMP_ENOMEM, "mmp_models_retire: out of device memory");
-    }
-    int rc = MMP_OK;
-    if (ids) {
-        next = HashTabW{c->mid_next_hash.as<uint64_t>(), c->mid_next_val.as<int32_t>(), cap1 - 1};
-        rc = empty_table(c, next);
-        if (rc == MMP_OK && hipMemsetAsync(no.p, 0, 4, st) != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_models_retire: hipMemsetAsync failed");
-    }
-    std::vector<int32_t> remap((size_t)M0);
-    if (rc == MMP_OK) {
-        const RetireMove A{c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(),
-                           ids ? c->mid_bytes.as<char>() : nullptr, old_off, nm.as<mmp_model_row>(), np.as<int32_t>(), nt.as<int64_t>(),
-                           nb.as<char>(), no.as<int32_t>()};
-        KT_BEGIN(c, st);
-        hipLaunchKernelGGL(retire_move_kernel, dim3(div_up(M0, kRetireBlock)), block, 0, st, M0, d_keep, d_pos, A, d_remap);
-        if (ids) {
-            // 3. the stored hashes of the survivors into the emptied next table; 4. a verifying lookup in a launch of its own
-            const dim3 sgrid(div_up((int)cap0, kRetireBlock));
-            hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), cap0, d_remap, next);
-            hipLaunchKernelGGL(retire_verify_kernel, sgrid, block, 0, st, c->mid_hash.as<uint64_t>(), c->mid_val.as<int32_t>(), cap0, d_remap,
-                               ModelIdTab{next.hash, next.val, next.mask, nb.as<char>(), no.as<int32_t>()}, d_word + 1);
-        }
-        KT_END(c, st);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(remap.data(), d_remap, (size_t)M0 * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(word + 1, d_word + 1, 4, hipMemcpyDeviceToHost, st);
-        const hipError_t se = hipStreamSynchronize(st);  // (whatever was enqueued has finished before the new buffers may go)
-        if (e == hipSuccess) e = se;
-        if (e != hipSuccess) rc = fail(c, MMP_EHIP, "mmp_models_retire: %s", hipGetErrorString(e));
-    } else
-        (void)hipStreamSynchronize(st);
-    if (rc == MMP_OK && word[1] != INT32_MAX)
-        rc = fail(c, MMP_EHIP, "mmp_models_retire: the id of new row %d was not found in the compacted table", word[1]);
-    if (rc != MMP_OK) {
-        drop();
+    // mark, and with the flag the lowest named row that is not empty; with bound caches the lowest that is the key of a live entry
+    RetireMarked<RetireCount> K;
+    if (const int rc = retire_mark_scan<RetireCount, RetirePlus>(
+            c, rows, n, M0,
+            [&](const int32_t *d_list, int32_t *d_keep, int32_t *d_word, RetireCount *d_cnt) {
+                hipLaunchKernelGGL(retire_mark_kernel, dim3(div_up(n, kRetireBlock)), block, 0, st, d_list, n, c->models.as<mmp_model_row>(),
+                                   (flags & MMP_RETIRE_EMPTY_ONLY) ? 1 : 0, d_keep, d_word);
+                if (carry)
+                    hipLaunchKernelGGL(ckey_retire_check_kernel, dim3(div_up(c->k_slots, kRetireBlock)), block, 0, st, kstore, c->k_caches, c->k_slots,
+                                       M0, d_keep, d_live_key);
+                hipLaunchKernelGGL(retire_flags_kernel, dim3(div_up(M0 + 1, kRetireBlock)), block, 0, st, M0, d_keep, c->models.as<mmp_model_row>(),
+                                   old_off, d_cnt);
+            },
+            K, d_live_key))
         return rc;
-    }
-    kt_collect(c);
-    kt_add(c, mark_ms);  // the call's device span: mark + scan + move + table + verify
-    // 3. nothing fails from here on but the drain and the re-resolution: registry, arena, table and counts change together
-    DevBuf om, op, ot;
+    if (K.refused != INT32_MAX)
+        return fail(c, MMP_EINVAL, "%s: row %d is not empty (registered again since its deletion?); nothing was retired", fn, K.refused);
+    if (K.extra != INT32_MAX)
+        return fail(c, MMP_EINVAL, "%s: row %d is the key of a live cache entry (remove the entry first); nothing was retired", fn, K.extra);
+    const int32_t M1 = K.tot.row, B1 = K.tot.bytes, E1 = K.tot.ents;
+    // build: the compacted registry, and with loaded ids their arena and table
+    std::vector<int32_t> remap((size_t)M0);
+    ScopedDevBuf nm, np, nt, nb, no;
+    HashTabW next{};
+    const size_t ecap = (size_t)std::max<int64_t>((int64_t)E1 + E1 / 2, 1024);
+    if (nm.b.ensure((size_t)std::max(M1, 1) * sizeof(mmp_model_row)) != hipSuccess || np.b.ensure(ecap * 4) != hipSuccess ||
+        nt.b.ensure(ecap * 8) != hipSuccess)
+        return fail(c, MMP_ENOMEM, "%s: out of device memory", fn);
+    if (ids)
+        if (const int rc = retire_id_table_room(c, fn, T, M1, B1, nb, no, next)) return rc;
+    const RetireMove A{c->models.as<mmp_model_row>(), c->ent_pod.as<int32_t>(), c->ent_time.as<int64_t>(), ids ? T.bytes.as<char>() : nullptr,
+                       old_off, nm.b.as<mmp_model_row>(), np.b.as<int32_t>(), nt.b.as<int64_t>(), nb.b.as<char>(), no.b.as<int32_t>()};
+    int32_t *d_remap = c->ret_remap.as<int32_t>();
+    const int rc = retire_build(c, fn, M0, K.ms, [&] {
+        hipLaunchKernelGGL(retire_move_kernel, dim3(div_up(M0, kRetireBlock)), block, 0, st, M0, c->ret_keep.as<int32_t>(), c->me_pos.as<RetireCount>(), A,
+                           d_remap);
+        if (ids) retire_id_table(c, T, d_remap, next, nb, no, c->ret_word.as<int32_t>() + 1);
+    }, remap);
+    if (rc != MMP_OK) return rc;
+    // nothing fails from here on but the drain and the re-resolution: registry, arena, table and counts change together
     {
         std::lock_guard<std::shared_mutex> g(c->mu);
-        const hipError_t q = quiesce_decisions(c);  // kernels that captured the old tables; the resolved view is rewritten in place
-        if (q != hipSuccess) {
-            drop();
-            HIP_TRY(c, q);
-        }
-        om = c->models, op = c->ent_pod, ot = c->ent_time;
-        c->models = nm, c->ent_pod = np, c->ent_time = nt;
+        HIP_TRY(c, quiesce_decisions(c));  // kernels that captured the old tables; the resolved view is rewritten in place
+        nm.move_into(c->models);
+        np.move_into(c->ent_pod);
+        nt.move_into(c->ent_time);
         c->n_models = M1;
         c->n_entries = E1;
         c->ent_live = E1;
@@ -4729,21 +4723,10 @@ try {
         c->m_cnt.resize(M1);
         c->u_stamp.assign(std::min<size_t>(c->u_stamp.size(), (size_t)M1), 0);  // (stamps name a call generation: zero = none)
         c->plan.model_map_n = std::min(c->plan.model_map_n, M1);
-        if (ids) {
-            // (the id table's ownership rule, mmp_ctx::mid_hash: the drain above ran inside this exclusive hold, so no request call
-            // by model id holds the table swapped out here or the arena released here)
-            std::swap(c->mid_hash, c->mid_next_hash);
-            std::swap(c->mid_val, c->mid_next_val);
-            c->mid_mask = cap1 - 1;
-            c->mid_bytes.release();
-            c->mid_off.release();
-            c->mid_bytes = nb, c->mid_off = no;
-            c->mid_n = M1;
-            c->mid_nbytes = B1;
-        }
-        om.release();
-        op.release();
-        ot.release();
+        if (ids) retire_id_table_publish(T, next, nb, no, M1, B1);
+        // (the drain above ran inside this exclusive hold, so no decision and no request call by model id holds what the swap
+        // retired: it goes here, before rebuild_resolved allocates)
+        for (ScopedDevBuf *b : {&nm, &np, &nt, &nb, &no}) b->release();
         c->side[0].rmodels_ok = c->side[1].rmodels_ok = false;
         split_reset(c);
         if (carry) {  // the keys of the bound caches follow their rows, in place (d_remap: the M0 words retire_move_kernel wrote)
@@ -4764,8 +4747,7 @@ int mmp_pods_retire(mmp_ctx *c, const int32_t *pods, int32_t n, uint32_t flags, 
 try {
     if (!c || n < 0 || (n > 0 && !pods) || (flags & ~(MMP_PODS_RETIRE_GONE_ONLY | MMP_PODS_RETIRE_UNREFERENCED)) || max_pods < 0)
         return fail(c, MMP_EINVAL, "mmp_pods_retire: bad argument");
-    // batch_mu keeps every other writer of the commit's inputs, the registry and the id table away while the compacted state is
-    // built BESIDE the published one (decisions go on reading that); the state lock is taken for the swap and held across the commit.
+    // The retire frame (at retire_list_guard).  Its own: the remap made on the host, one round trip, the hold kept across the commit.
     std::lock_guard<std::mutex> gb(c->batch_mu);
     if (c->n_shards > 0) return fail(c, MMP_ESTATE, "mmp_pods_retire: not available on a pod-axis shard context");
     const int32_t P0 = (int32_t)c->pods.size();
@@ -4777,16 +4759,11 @@ try {
     if (c->n_types > 0 && c->types_w != div_up(P0, 64))
         return fail(c, MMP_ESTATE, "mmp_pods_retire: the type bitmaps were loaded for a different pod count (%d words for %d pods); reload them first",
                     c->types_w, P0);
-    if (remap_out && max_pods < P0) return fail(c, MMP_EINVAL, "mmp_pods_retire: room for %d pods in remap_out, the table has %d", max_pods, P0);
-    for (int32_t i = 0; i < n; i++)
-        if (pods[i] < 0 || pods[i] >= P0) return fail(c, MMP_EINVAL, "mmp_pods_retire: pods[%d] names instance %d of %d", i, pods[i], P0);
+    if (const int rc = retire_list_guard(c, "mmp_pods_retire", RetireNoun{"pods", "instance", "the table"}, pods, n, P0, remap_out, max_pods))
+        return rc;
     if (n == 0) {
-        if (remap_out)
-            for (int32_t p = 0; p < P0; p++) remap_out[p] = p;
-        if (n_pods_after_out) *n_pods_after_out = P0;
         if (n_entries_unresolved_out) *n_entries_unresolved_out = 0;
-        if (c->prof) c->last_kernel_ms = -1;  // no kernel
-        return MMP_OK;
+        return retire_nothing(c, P0, remap_out, n_pods_after_out);
     }
     // 1. the remap, on the host: P0 words from the caller's list
     std::vector<int32_t> remap((size_t)P0, 0);
@@ -4811,21 +4788,12 @@ try {
     const int32_t *d_remap = c->ret_remap.as<int32_t>();
     PodsRetireWords *d_words = c->ret_word.as<PodsRetireWords>();
     PodsRetireWords words{0ull, INT32_MAX, INT32_MAX};
-    // the new arena and marks, after the swap the old ones: freed on every way out, an exception of step 3 included
-    struct Beside {
-        DevBuf np, nmiss;
-        ~Beside() { np.release(), nmiss.release(); }
-    } beside;
-    DevBuf &np = beside.np, &nmiss = beside.nmiss;
-    auto drop = [&] { np.release(); nmiss.release(); };
+    ScopedDevBuf np, nmiss;  // the new arena and marks, after the swap the old ones (marks with no survivor stay: miss_n says so)
     const uint32_t cap0 = ids ? c->idtab_mask + 1 : 0u;
     HashTabW next{};
-    bool room = (!c->ent_pod.p || np.ensure(c->ent_pod.cap) == hipSuccess) && (miss1 == 0 || nmiss.ensure((size_t)miss1 * 8) == hipSuccess);
+    bool room = (!c->ent_pod.p || np.b.ensure(c->ent_pod.cap) == hipSuccess) && (miss1 == 0 || nmiss.b.ensure((size_t)miss1 * 8) == hipSuccess);
     if (room && ids) room = next_table_room(c, 0, P1, c->idtab_next_hash, c->idtab_next_val, next) == MMP_OK;  // tab_capacity(P1): the table shrinks
-    if (!room) {
-        drop();
-        return fail(c, MMP_ENOMEM, "mmp_pods_retire: out of device memory");
-    }
+    if (!room) return fail(c, MMP_ENOMEM, "mmp_pods_retire: out of device memory");
     const dim3 block(kRetireBlock);
     hipError_t e = hipMemcpyAsync(c->ret_remap.p, remap.data(), (size_t)P0 * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_words, &words, sizeof words, hipMemcpyHostToDevice, st);
@@ -4834,22 +4802,17 @@ try {
     if (e == hipSuccess) {
         if (E > 0)
             hipLaunchKernelGGL(pods_retire_entries_kernel, dim3(div_up(E, kRetireBlock)), block, 0, st, c->ent_pod.as<int32_t>(), E, d_remap, P0,
-                               np.as<int32_t>());
+                               np.b.as<int32_t>());
         if (M > 0)
             hipLaunchKernelGGL(pods_retire_count_kernel, dim3(div_up(M, kRetireBlock)), block, 0, st, c->models.as<mmp_model_row>(), M,
                                c->ent_pod.as<int32_t>(), d_remap, P0, d_words);
         if (miss0 > 0 && miss1 > 0)
             hipLaunchKernelGGL(pods_retire_marks_kernel, dim3(div_up(miss0, kRetireBlock)), block, 0, st, c->miss_since.as<int64_t>(), miss0,
-                               d_remap, nmiss.as<int64_t>());
-        if (ids) {
-            // the stored hashes of the survivors into the emptied next table; a verifying lookup in a launch of its own
-            rc = empty_table(c, next);
-            if (rc == MMP_OK) {
-                const dim3 sgrid(div_up((int)cap0, kRetireBlock));
-                hipLaunchKernelGGL(retire_table_kernel, sgrid, block, 0, st, c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), cap0, d_remap, next);
-                hipLaunchKernelGGL(pods_retire_verify_kernel, sgrid, block, 0, st, c->idtab_hash.as<uint64_t>(), c->idtab_val.as<int32_t>(), cap0,
-                                   d_remap, P0, HashTab{next.hash, next.val, next.mask}, d_words);
-            }
+                               d_remap, nmiss.b.as<int64_t>());
+        if (ids && (rc = empty_table(c, next)) == MMP_OK) {  // the frame's claims; the verify is this call's own (the ids are on the host)
+            retire_table_claim(c, c->idtab_hash, c->idtab_val, cap0, d_remap, next);
+            hipLaunchKernelGGL(pods_retire_verify_kernel, dim3(div_up((int)cap0, kRetireBlock)), block, 0, st, c->idtab_hash.as<uint64_t>(),
+                               c->idtab_val.as<int32_t>(), cap0, d_remap, P0, HashTab{next.hash, next.val, next.mask}, d_words);
         }
     }
     KT_END(c, st);
@@ -4863,10 +4826,7 @@ try {
                   words.lowest_named);
     if (rc == MMP_OK && words.lost != INT32_MAX)
         rc = fail(c, MMP_EHIP, "mmp_pods_retire: the id of new instance %d was not found in the compacted table", words.lost);
-    if (rc != MMP_OK) {
-        drop();
-        return rc;
-    }
+    if (rc != MMP_OK) return rc;
     kt_collect(c);
     const double build_ms = c->last_kernel_ms;
     // 3. what the host holds by instance index: rows, labels, type bit rows, the id store
@@ -4927,11 +4887,7 @@ try {
     // 4. the swap and the commit, under the state lock: a decision sees the whole old index space or the whole new one
     {
         std::lock_guard<std::shared_mutex> g(c->mu);
-        const hipError_t q = quiesce_decisions(c);
-        if (q != hipSuccess) {
-            drop();
-            HIP_TRY(c, q);
-        }
+        HIP_TRY(c, quiesce_decisions(c));
         const bool dirty_all0 = c->dirty_all;
         const int32_t miss_n0 = c->miss_n;
         const uint32_t mask0 = c->idtab_mask;
@@ -4957,8 +4913,8 @@ try {
                 std::swap(c->idtab_hash, c->idtab_next_hash);
                 std::swap(c->idtab_val, c->idtab_next_val);
             }
-            std::swap(c->ent_pod, np);
-            std::swap(c->miss_since, nmiss);
+            np.move_into(c->ent_pod);
+            nmiss.move_into(c->miss_since);
         };
         swap_inputs();
         c->idtab_mask = ids ? next.mask : mask0;
@@ -4976,12 +4932,11 @@ try {
             c->idtab_mask = mask0;
             c->miss_n = miss_n0;
             c->dirty_all = dirty_all0;
-            drop();
             return rc;
         }
         if (commit) kt_add(c, build_ms);  // the call's device span: remap + count + marks + table + verify, and the commit's
     }
-    drop();  // the old arena and marks
+    // (the old arena and marks go with np / nmiss, after the hold: the drain ran inside it)
     if (remap_out) memcpy(remap_out, remap.data(), (size_t)P0 * 4);
     if (n_pods_after_out) *n_pods_after_out = P1;
     if (n_entries_unresolved_out) *n_entries_unresolved_out = (int64_t)words.n_turned;
