@@ -915,7 +915,11 @@ int mmp_registry_prune(mmp_ctx *ctx, int32_t self_pod, int64_t now_ms, int64_t g
 /* The missing map (`missings`, MM.java:6776): since_out[p] = the time pod p was first seen missing, 0 = no mark; *n_out = pod
  * slots the map covers.  Lifetime: the map is kept BY POD INDEX inside the context; it grows (unmarked) when pods are appended;
  * it survives mmp_pods_load / _upsert / _remove, which keep the index space; mmp_pod_ids_load, which redefines the index space,
- * clears it; mmp_registry_missing_reset is missings.clear() on a leader change (:6427, :6827). */
+ * clears it; mmp_registry_missing_reset is missings.clear() on a leader change (:6427, :6827).
+ * LIMIT: a mark of 0 cannot be told from no mark, which is why mmp_registry_prune refuses now_ms <= 0.  The reference run at a
+ * clock value of 0 writes the mark 0 and prunes on it one run later; that case, and an entry whose id the instance table does not
+ * hold (UNRESOLVED above: the reference prunes it like any missing instance), are kept in tests/golden/ref_registry_edges.npz
+ * marked as outside this domain (docs/PARITY.md). */
 int mmp_registry_missing_get(mmp_ctx *ctx, int64_t *since_out, int32_t max_pods, int32_t *n_out);
 int mmp_registry_missing_reset(mmp_ctx *ctx);
 

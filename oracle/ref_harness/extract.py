@@ -227,6 +227,37 @@ TCMI_RANGES = [
 ]
 
 
+# ---- a16' / a17': the janitor's cache loop and registry loop, pruneModelRegistry with pruneMissingInstances, and the ModelRecord
+# methods they call — compiled by registry_harness.cc (a fourth binary).  The registry loop is cut in two: :6014-6107 and its last
+# line (:6108, the `}` that closes the `for`), so that the harness can put the target of `continue registryLoop` between them
+MR = "src/main/java/com/ibm/watson/modelmesh/ModelRecord.java"
+REG_RANGES = [
+    ("reg_failure_expiry_constants", MM, 219, 221, "LOAD_FAILURE_EXPIRY_MS = getLongParameter(LOAD_FAILURE_EXPIRY_ENV_VAR, 900_000L);",
+     "IN_USE_LOAD_FAILURE_EXPIRY_MS = LOAD_FAILURE_EXPIRY_MS / 2;", "REG"),
+    ("reg_janitor_freq_constant", MM, 235, 235, 'LOCAL_JANITOR_FREQ_SECS = Long.getLong("tas.janitor_freq_secs", 6 * 60);', "6mins", "REG"),
+    ("reg_lastused_age_constant", MM, 266, 266, "LASTUSED_AGE_ON_ADD_MS = 3600_000;", "1hour", "REG"),
+    ("reg_gone_after_constant", MM, 270, 270, "ASSUME_INSTANCE_GONE_AFTER_MS = 10 * 60_000L;", "10min", "REG"),
+    ("reg_short_expiry_constant", MM, 280, 280, "SHORT_EXPIRY_RECENT_USE_TIME_MS = 3 * 60_000L;", "3mins", "REG"),
+    ("reg_ce_states", MM, 1841, 1848, "NEW = 0,", "REMOVED = 7;", "REG"),
+    ("reg_unloadAttemptedRecently_body", MM, 1865, 1865, "return age(lastUnloadAttemptTime) < 600_000L;", "10 mins", "REG"),
+    ("reg_janitor_cache_loop", MM, 5892, 6008, "Map<String, CacheEntry<?>> cacheEntries = runtimeCache.descendingMap();", "}", "REG"),
+    ("reg_janitor_between_loops", MM, 6010, 6013, "if (shuttingDown) {", "before = nanoTime();", "REG"),
+    ("reg_janitor_registry_loop", MM, 6014, 6107, "// find references to this instance in the registry and prune where necessary", "}", "REG"),
+    ("reg_janitor_registry_loop_close", MM, 6108, 6108, "}", "}", "REG"),  # the brace that closes the `for`
+    ("reg_updateIfStale_body", MM, 6167, 6184, "if (lastUsed == Long.MAX_VALUE) {", "}", "REG"),
+    ("reg_repairLastUsed_body", MM, 6843, 6849, "if (mr != null && mr.getLastUsed() == Long.MAX_VALUE) {", "}", "REG"),
+    ("reg_value_comp_body", MM, 6876, 6880, "Long l1 = e1.getValue(), l2 = e2.getValue();", "return l1.compareTo(l2);", "REG"),
+    ("reg_prune_body", MM, 6529, 6608, "int kvConnectionErrorCount = 0;", "return true;", "REG"),
+    ("reg_pruneMissing_body", MM, 6754, 6783, "if (instances.isEmpty()) {", "return modCount;", "REG"),
+    ("reg_mr_removeLoadFailure_body", MR, 170, 170, "return loadFailedInstanceIds.remove(instanceId) != null | failures.remove(instanceId) != null;",
+     "!= null;", "REG"),
+    ("reg_mr_getLastUsed_body", MR, 229, 229, "return lastUsed;", "lastUsed;", "REG"),
+    ("reg_mr_setLastUsed_body", MR, 233, 233, "this.lastUsed = lastUsed;", "lastUsed;", "REG"),
+    ("reg_mr_updateLastUsed_body", MR, 240, 245, "if (lastUsed == 0L) {", "}", "REG"),
+    ("reg_mr_updateLastUnloadTime_body", MR, 261, 261, "this.lastUnloadTime = instanceIds.size() <= 2 ? 0L : System.currentTimeMillis();",
+     "currentTimeMillis();", "REG"),
+]
+
 # The one control-flow rewrite: the listener's `switch (type)` (MM.java:1474-1563) declares locals in `case ENTRY_UPDATED` and
 # falls through into `case ENTRY_DELETED`; C++ forbids the jump past those initialisations that a direct entry at the second
 # label would be.  Its four label lines become the equivalent if-chain (ADDED/UPDATED run both blocks, DELETED the second,
@@ -321,6 +352,29 @@ EXTRA_RULES["TCMI"] = EXTRA_RULES["TCM"] + [
     (re.compile(r"\bInstanceSetStatsTracker\.EMPTY_STATS\b"), "EMPTY_STATS"),
 ]
 
+# The janitor's loops and the prune (registry_harness.cc).  Syntax only:
+#  - `registryLoop:` labels the `for` (:6019) and `continue registryLoop;` (:6031) leaves the inner `while (true)` for the next
+#    record: C++ has no labelled continue, the statement becomes a `goto` to a label that the harness puts in front of the brace
+#    closing that `for` (:6108), and the Java label line becomes a comment
+#  - `new Object[] { a, b, c }` (:6098) is an aggregate of the stand-in for Object[]; `new TreeSet<>(VALUE_COMP)` / `new HashSet<>()`
+#    become factory calls; `CacheEntry.LOADING` names a constant of a class (`::`); `instanceInfo::contains` (:6549, a method
+#    reference in the readOnlyMode branch) names a function object
+#  - the `removeIf` lambda (:6604-6605) is an expression lambda that spans two lines: head, `return` and the closing brace
+#  - member modifiers of the instance constants (`public final long`)
+EXTRA_RULES["REG"] = [
+    (re.compile(r"^(\s*)registryLoop:\s*$"), r"\1// registryLoop:"),
+    (re.compile(r"\bcontinue registryLoop;"), "goto registryLoop_continue;"),
+    (re.compile(r"\bnew Object\[\] \{"), "ObjectArr3{"),
+    (re.compile(r"\bnew TreeSet<>\(VALUE_COMP\)"), "SortedSet_new(VALUE_COMP)"),
+    (re.compile(r"\bnew HashSet<>\("), "HashSet_new("),
+    (re.compile(r"\bCacheEntry\.(LOADING|ACTIVE)\b"), r"CacheEntry::\1"),
+    (re.compile(r"\binstanceInfo::contains\b"), "instanceInfo_contains"),
+    (re.compile(r"\.removeIf\(ent -> "), ".removeIf([=](auto ent) { return "),
+    (re.compile(r"(\|\| instanceInfo\.contains\(ent\.getKey\(\)\))\);"), r"\1; });"),
+    (re.compile(r"^\s*public\s+final\s+long\s+"), "static const long "),
+    (re.compile(r"\bSystem\.currentTimeMillis\(\)"), "currentTimeMillis()"),
+]
+
 # token-level rewrites, applied in order to every extracted line
 RULES = [
     # Java numeric literals may carry underscores: 120_000L -> 120000L
@@ -374,7 +428,7 @@ def extract():
     out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_ref", "gen")
     os.makedirs(out_dir, exist_ok=True)
     manifest = []
-    for name, rel, a, b, must_first, must_last, *extra in RANGES + CLHM_RANGES + TCMI_RANGES:
+    for name, rel, a, b, must_first, must_last, *extra in RANGES + CLHM_RANGES + TCMI_RANGES + REG_RANGES:
         path = os.path.join(REF, rel)
         lines = open(path, encoding="utf-8").read().split("\n")
         body = lines[a - 1:b]

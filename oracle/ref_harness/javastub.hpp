@@ -77,6 +77,8 @@ struct Long {
     bool operator!=(std::nullptr_t) const { return !isnull; }
     static constexpr long MAX_VALUE = LONG_MAX;
     static int compare(long a, long b) { return a < b ? -1 : a > b ? 1 : 0; }
+    int compareTo(const Long &o) const { return compare(v, o.v); }
+    static long getLong(const String &, long def) { return def; }  // Long.getLong(property, default): no system property is set
 };
 struct Integer {
     static constexpr int MAX_VALUE = INT_MAX;
@@ -163,6 +165,7 @@ public:
     void set(int i, const T &t) const { p->v[i] = t; }
     int size() const { return (int)p->v.size(); }
     boolean isEmpty() const { return p->v.empty(); }
+    void clear() const { p->v.clear(); }
     Iterator<T> iterator() const
     {
         auto r = p;
@@ -247,9 +250,32 @@ public:
     boolean containsKey(const K &k) const { return p->count(k) != 0; }
     V get(const K &k) const { auto it = p->find(k); return it == p->end() ? V(null) : it->second; }
     V put(const K &k, const V &v) const { auto it = p->find(k); V old = it == p->end() ? V(null) : it->second; (*p)[k] = v; return old; }
-    std::vector<Entry<K, V>> entrySet() const
+    V putIfAbsent(const K &k, const V &v) const { auto it = p->find(k); if (it != p->end()) return it->second; (*p)[k] = v; return V(null); }
+    V remove(const K &k) const { auto it = p->find(k); if (it == p->end()) return V(null); V old = it->second; p->erase(it); return old; }
+    // entrySet(): the entries in key order (a copy to range over), with the two calls that write through to the map:
+    // iterator() whose remove() takes the entry next() returned last out of the map, and removeIf(predicate)
+    struct EntrySet : std::vector<Entry<K, V>> {
+        std::shared_ptr<std::map<String, V, String::Less>> m;
+        Iterator<Entry<K, V>> iterator() const
+        {
+            auto es = std::make_shared<std::vector<Entry<K, V>>>(*this);
+            auto i = std::make_shared<size_t>(0);
+            auto mm = m;
+            return Iterator<Entry<K, V>>([es, i] { return *i < es->size(); }, [es, i] { return (*es)[(*i)++]; },
+                                         [es, i, mm] { mm->erase((*es)[*i - 1].getKey()); });
+        }
+        template <class P> boolean removeIf(P pred) const
+        {
+            bool any = false;
+            for (auto &e : *this)
+                if (pred(e)) { m->erase(e.getKey()); any = true; }
+            return any;
+        }
+    };
+    EntrySet entrySet() const
     {
-        std::vector<Entry<K, V>> es;
+        EntrySet es;
+        es.m = p;
         for (auto &kv : *p) es.emplace_back(kv.first, kv.second);
         return es;
     }
@@ -267,7 +293,11 @@ public:
     }
 };
 // java.util.Collections.min over boxed longs
+struct EmptyMapT {  // Collections.emptyMap() where only remove() is called on it
+    template <class K> void remove(const K &) const {}
+};
 struct Collections {
+    static EmptyMapT emptyMap() { return EmptyMapT(); }
     static Set<String> emptySet() { return Set<String>::make(); }
     static Set<String> singleton(const String &x) { Set<String> s = Set<String>::make(); s.add(x); return s; }
     static List<String> singletonList(const String &x) { List<String> l = ArrayList_new(1); l.add(x); return l; }

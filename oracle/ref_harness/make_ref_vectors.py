@@ -558,9 +558,117 @@ def type_edge_vectors():
     print(f"wrote {TYPE_EDGE_OUT}: {os.path.getsize(TYPE_EDGE_OUT) / 1e3:.0f} kB, {len(names)} cases")
 
 
+REGISTRY_EDGE_OUT = os.environ.get("MMP_REF_REGISTRY_EDGE_OUT") or os.path.join(ROOT, "tests", "golden", "ref_registry_edges.npz")
+REGISTRY_HARNESS = os.environ.get("MMP_REG_HARNESS") or os.path.join(ROOT, "oracle", "_ref", "registry_harness")
+
+
+def save_npz_fixed(path, arrays):
+    """an .npz whose bytes depend on the arrays alone: members in the order given, a fixed member time, deflate"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def registry_edge_vectors():
+    """tests/golden/ref_registry_edges.npz: the janitor's cache and registry loops and pruneModelRegistry, the reference's own text
+    (oracle/_ref/registry_harness), on the cases of tests/ref_registry_edges.py.  Refused: a pair the text answers alike in what it is
+    there for (a pair marked alike: one it answers differently), a case or a tier in which a named exit does not occur, a case
+    without its digest — all on the evidence of the inputs and the text's recorded calls."""
+    import json
+    from tests import ref_registry_edges as re_
+    from tests import registry_prune_model as rp
+    out, names, runs_of, inputs = {}, [], {}, {}
+    seen = {t: dict(cases=0, rows=0, records=0, pairs=0, alike=0, exits={}) for t in re_.TIERS}
+    for c in re_.cases():
+        name, meta, fleet, reg = c["name"], c["meta"], c["fleet"], c["reg"]
+        pods = fleet.pods
+        if meta["kind"] == "janitor":
+            text = re_.janitor_input(pods, reg, c["entries"], c["states"], c["prm"])
+        else:
+            text = re_.prune_input(pods, reg, meta["self_pod"], meta["runs"])
+        res = subprocess.run([REGISTRY_HARNESS], input=text.encode(), stdout=subprocess.PIPE, check=True)
+        parsed = re_.parse(res.stdout.decode(), pods)
+        assert len(parsed) == (1 if meta["kind"] == "janitor" else len(meta["runs"])), name
+        out[f"{name}/pods"] = pods
+        out[f"{name}/models"], out[f"{name}/ent_pod"], out[f"{name}/ent_time"] = rp.registry_to_arrays(reg)
+        if meta["kind"] == "janitor":
+            out[f"{name}/entries"], out[f"{name}/states"], out[f"{name}/prm"] = c["entries"], c["states"], c["prm"]
+        for k, run in enumerate(parsed):
+            for key, arr in re_.pack_run(run, c.get("entries")).items():
+                out[f"{name}/r{k}/{key}"] = arr
+        out[f"{name}/meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), np.uint8)
+        out[f"{name}/digest"] = np.frombuffer(re_.digest(text).encode(), np.uint8)
+        names.append(name)
+        inputs[name] = c
+    save_npz_fixed(REGISTRY_EDGE_OUT, dict(out, names=np.array(names)))
+    z = np.load(REGISTRY_EDGE_OUT)  # everything below reads what the file holds
+    for name in names:
+        c, meta = inputs[name], inputs[name]["meta"]
+        st = seen[meta["tier"]]
+        reg = rp.registry_from_arrays(z[f"{name}/models"], z[f"{name}/ent_pod"], z[f"{name}/ent_time"])
+        if f"{name}/digest" not in z.files:
+            sys.exit(f"{name}: no digest: refused")
+        st["cases"], st["records"] = st["cases"] + 1, st["records"] + len(reg)
+        if meta["kind"] == "janitor":
+            run, entries, prm = re_.Run(z, f"{name}/r0/"), z[f"{name}/entries"], z[f"{name}/prm"]
+            runs_of[name] = (run, entries, reg)
+            st["rows"] += len(entries)
+            for kind, a, b, what in meta["pairs"]:
+                if re_.answer(run, entries, kind, a, reg) == re_.answer(run, entries, kind, b, reg):
+                    sys.exit(f"{name}: the text answers pair {kind} {a} / {b} ({what}) alike: refused")
+            for kind, a, b, what in meta["alike"]:
+                if re_.answer(run, entries, kind, a, reg) != re_.answer(run, entries, kind, b, reg):
+                    sys.exit(f"{name}: the text answers pair {kind} {a} / {b} ({what}), marked alike, differently: refused")
+            st["pairs"], st["alike"] = st["pairs"] + len(meta["pairs"]), st["alike"] + len(meta["alike"])
+            shown = re_.exits_of(run, reg, entries, prm)
+        else:
+            runs = [re_.Run(z, f"{name}/r{k}/") for k in range(len(meta["runs"]))]
+            runs_of[name] = (runs, None, reg)
+            st["rows"] += len(runs)
+            for want_same, pairs in ((False, meta["pairs"]), (True, meta["alike"])):
+                for kind, a, b, what in pairs:
+                    if (re_.prune_rec_answer(runs, reg, a) == re_.prune_rec_answer(runs, reg, b)) != want_same:
+                        sys.exit(f"{name}: the text answers pair {kind} {a} / {b} ({what}) {'differently' if want_same else 'alike'}: refused")
+            st["pairs"], st["alike"] = st["pairs"] + len(meta["pairs"]), st["alike"] + len(meta["alike"])
+            shown = re_.prune_exits_of(runs, reg, meta) if meta["domain"] else set()
+        missing = set(meta["exits"]) - shown
+        if missing:
+            sys.exit(f"{name}: the case does not show {sorted(missing)} (it shows {sorted(shown)}): refused")
+        for e in shown:
+            st["exits"][e] = st["exits"].get(e, 0) + 1
+        print(f"{name}: {len(reg)} records, {len(z[name + '/entries']) if meta['kind'] == 'janitor' else len(meta['runs'])} rows / runs, "
+              f"{len(meta['pairs'])} pairs, {len(meta['alike'])} alike; shows {sorted(shown)}")
+    for a, b, kind, what, alike in re_.run_pairs():
+        if kind == "row":
+            at = inputs[b]["meta"]["stop_at"]
+            same = re_.answer(*runs_of[a][:2], "row", at, runs_of[a][2]) == re_.answer(*runs_of[b][:2], "row", at, runs_of[b][2])
+        else:
+            same = re_.prune_answer(runs_of[a][0], runs_of[a][2], inputs[a]["meta"]) == re_.prune_answer(runs_of[b][0], runs_of[b][2], inputs[b]["meta"])
+        if same != alike:
+            sys.exit(f"{a} / {b} ({what}): the text answers them {'alike' if same else 'differently'}: refused")
+        seen[inputs[a]["meta"]["tier"]]["alike" if alike else "pairs"] += 1
+    for t in re_.TIERS:
+        lacking = set(re_.TIER_EXITS[t]) - set(seen[t]["exits"])
+        if lacking:
+            sys.exit(f"tier {t}: no case shows {sorted(lacking)}: refused")
+        s = seen[t]
+        print(f"tier {t}: {s['cases']} cases, {s['records']} records, {s['rows']} cache rows / runs, {s['pairs']} pairs, {s['alike']} alike; exits " +
+              ", ".join(f"{k} x{v}" for k, v in sorted(s["exits"].items())))
+    print(f"wrote {REGISTRY_EDGE_OUT}: {os.path.getsize(REGISTRY_EDGE_OUT)} bytes, {len(names)} cases")
+
+
 def main():
     if not os.environ.get("MMP_REF_HARNESS"):
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "ref_harness", "build.sh")], check=True)
+    if "--registry-edges" in sys.argv[1:]:  # only the janitor's loops and the registry prune
+        return registry_edge_vectors()
     if "--type-edges" in sys.argv[1:]:  # only the type-constraint edge cases
         return type_edge_vectors()
     if "--gate-edges" in sys.argv[1:]:  # only the guard edge cases: ref_getnext.npz stays as it is

@@ -9,8 +9,9 @@ most one cache entry and its record is decided from that entry alone; what coupl
 tests/test_janitor_model.py holds the two against each other.
 
 The reference has no test that names this code (nothing under its src/test mentions janitorTask, scaleCopiesCandidates,
-updateLastUsedTimeInRegistryIfStale or unloadAttemptedRecently), so there are no reference vectors: the restatement is read
-against the Java text.
+updateLastUsedTimeInRegistryIfStale or unloadAttemptedRecently).  The vectors are the text's own answers: the two loops are cut
+out of the reference tree and compiled by oracle/ref_harness/registry_harness.cc, tests/golden/ref_registry_edges.npz holds what
+they did at the value edges (tests/ref_registry_edges.py), and tests/test_registry_edges.py holds both forms below to every row.
 
 One run uses ONE clock value (the library's convention); the Java reads currentTimeMillis() at :5899 and :6018.  Not restated:
 verifyKvStoreConnection (:5886), the conditional-set retries (:5983-5996, :6074-6078; a record is what the registry holds),

@@ -8,7 +8,9 @@ without a mark, whose entries are then never removed in that run.  tests/test_re
 each other.
 
 The reference has no test that names this code (nothing under its src/test mentions pruneModelRegistry,
-pruneMissingInstances or missings), so there are no reference vectors for it: the restatement is read against the Java text.
+pruneMissingInstances or missings).  The vectors are the text's own answers: the methods are cut out of the reference tree and
+compiled by oracle/ref_harness/registry_harness.cc, tests/golden/ref_registry_edges.npz holds what they did over sequences of runs
+at the value edges (tests/ref_registry_edges.py), and tests/test_registry_edges.py holds both forms below to every run.
 
 One run uses ONE clock value (the library's convention); the Java reads currentTimeMillis() per record (:6758, :6603, :6844).
 Not restated: readOnlyMode (:6543-6550), loadFailureInfos (:6779), the kv-error counter (:6583-6600) and the

@@ -24,6 +24,12 @@ for f in *.inc.gcov; do mv "$f" "h12_$f"; done   # (bodies shared with the third
 g++ -std=c++17 -O0 -g -fwrapv --coverage -w "$root/oracle/ref_harness/tcm_harness.cc" -o tcm_harness_cov
 MMP_TCM_HARNESS="$tmp/tcm_harness_cov" MMP_TCM_OUT="$tmp/out_tcm.npz" python3 "$root/oracle/ref_harness/make_tcm_vectors.py" > gen_tcm.log
 gcov tcm_harness_cov-tcm_harness.gcda >> gcov.log 2>&1
+# the janitor's cache and registry loops + pruneModelRegistry: the fourth binary, tests/golden/ref_registry_edges.npz (its reg_* bodies are
+# compiled into no other binary; age_body, which it shares with the first, keeps the first binary's view)
+g++ -std=c++17 -O0 -g -fwrapv --coverage -w "$root/oracle/ref_harness/registry_harness.cc" -o registry_harness_cov
+MMP_REF_HARNESS=1 MMP_REG_HARNESS="$tmp/registry_harness_cov" MMP_REF_REGISTRY_EDGE_OUT="$tmp/out_reg.npz" \
+    python3 "$root/oracle/ref_harness/make_ref_vectors.py" --registry-edges > gen_reg.log
+mkdir reg && (cd reg && gcov ../registry_harness_cov-registry_harness.gcda >> ../gcov.log 2>&1 && mv reg_*.inc.gcov ..)
 # a body compiled into two binaries (PLACEMENT_ORDER, isFull, InstanceSetStatsTracker, the listener's text as tcmi_listener_body):
 # a line counts as executed if either binary executed it
 python3 - <<'PY'
@@ -44,7 +50,7 @@ for g in glob.glob("h12_*.inc.gcov"):
     os.rename(g, g[4:])
 PY
 {
-  echo "# reference text executed by tests/golden/ref_getnext.npz ($(tail -1 gen.log | sed 's/.*: //')) tests/golden/ref_clhm.npz ($(tail -1 gen_clhm.log | sed 's/.*: //')) and tests/golden/ref_tcm.npz ($(tail -1 gen_tcm.log | sed 's/.*: //'))"
+  echo "# reference text executed by tests/golden/ref_getnext.npz ($(tail -1 gen.log | sed 's/.*: //')) tests/golden/ref_clhm.npz ($(tail -1 gen_clhm.log | sed 's/.*: //')) tests/golden/ref_tcm.npz ($(tail -1 gen_tcm.log | sed 's/.*: //')) and tests/golden/ref_registry_edges.npz ($(tail -1 gen_reg.log | sed 's/.*: //'))"
   echo "# body (oracle/_ref/gen/<name>.inc; source range in oracle/ref_harness/extract.py)   executed/executable lines"
   tot=0; hit=0
   for f in *.inc.gcov; do
