@@ -615,9 +615,17 @@ int mmp_caches_load_keyed(mmp_ctx *ctx, int32_t n_caches, const int32_t *seg_off
                           const int32_t *weight, const int32_t *key, const int64_t *capacity, const mmp_ubm_state *ubm);
 /* Apply n_ops operations (each cache's operations in the order given) to the stateful caches.
  * evicted_keys has room for max_evicted keys; *n_evicted_slots = slots the call used (outs index into
- * it).  MMP_EINVAL if one cache's entries + inserts exceed the 2048-slot tile or max_evicted is too small. */
+ * it).  MMP_EINVAL if max_evicted is too small, or if one cache with operations needs more deque slots (its entries + the
+ * call's inserts on it) than the context accepts: 2047 unless mmp_cache_slots_limit raised it.  Every cache is then unchanged. */
 int mmp_cache_replay(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n_ops, int64_t now_ms, mmp_cache_op_out *outs,
                      int32_t *evicted_keys, int32_t max_evicted, int32_t *n_evicted_slots);
+/* The most deque slots per cache that a replay on this context accepts (mmp_cache_replay, _k and _kt alike).  The default, 2047,
+ * is what one wavefront stages in LDS; a cache that needs more is replayed on a blocked deque in global memory
+ * (cache_wide_kernels.hpp), with the same answers.  max_slots outside [MMP_CACHE_SLOTS_DEFAULT, MMP_CACHE_SLOTS_MAX] is
+ * MMP_EINVAL.  Takes the locks the replay takes. */
+#define MMP_CACHE_SLOTS_DEFAULT 2047
+#define MMP_CACHE_SLOTS_MAX 262144
+int mmp_cache_slots_limit(mmp_ctx *ctx, int32_t max_slots);
 /* Read one cache back (deque order). */
 int mmp_cache_read(mmp_ctx *ctx, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *key,
                    int32_t *n_out, int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm);

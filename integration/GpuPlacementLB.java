@@ -98,6 +98,8 @@ final class MmPlace {
                                     int maxEvicted, ByteBuffer evIdBytesOut, int maxIdBytes, ByteBuffer evIdOffOut, ByteBuffer sizes,
                                     ByteBuffer evLastUsedOut);
     static native int cacheEvictedTimes(long h, ByteBuffer out, int maxSlots, ByteBuffer nSlotsOut);
+    // the most deque slots (entries + a call's inserts) per cache a replay accepts: 2047 by default, up to 262144 (INTEGRATION.md)
+    static native int cacheSlotsLimit(long h, int maxSlots);
     static native int cacheReadK(long h, int cache, int maxEntries, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer rowOut,
                                  ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut, ByteBuffer scalars, ByteBuffer ubm);
     // request guards and rebalancer plans

@@ -335,6 +335,10 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheEvictedTimes(J
         return check(env, ctx_of(h), MMP_EINVAL);
     return check(env, ctx_of(h), mmp_cache_evicted_times(ctx_of(h), buf<int64_t>(env, out), maxSlots, buf<int32_t>(env, nSlotsOut)));
 }
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheSlotsLimit(JNIEnv *env, jclass, jlong h, jint maxSlots)
+{
+    return check(env, ctx_of(h), mmp_cache_slots_limit(ctx_of(h), maxSlots));
+}
 // scalars: direct buffer {int32 n; int32 nIdBytes; int64 capacity; int64 weightedSize}
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReadK(JNIEnv *env, jclass, jlong h, jint cache, jint maxEntries,
                                                                         jobject lastUsed, jobject weight, jobject rowOut, jobject idBytesOut,

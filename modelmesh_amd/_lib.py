@@ -373,6 +373,7 @@ SYMBOLS = [
     ("mmp_cache_replay_kt", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32,
                                       _P, C.POINTER(C.c_int32), _P]),
     ("mmp_cache_evicted_times", C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mmp_cache_slots_limit", C.c_int, [_P, C.c_int32]),
     ("mmp_cache_read_k", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     ("mmp_gate_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),

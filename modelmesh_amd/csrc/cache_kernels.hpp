@@ -62,12 +62,13 @@ __device__ __forceinline__ uint64_t team_ballot(bool p)
     return (b >> (lane_id() & ~(TW - 1))) & ((1ull << (TW & 63)) - 1ull);
 }
 
-struct Deque {
-    int64_t *lu;
-    int32_t *wt, *key;
+// What the rules below (dq_evict, ubm_*, apply_op) keep of a cache whatever holds its deque: they are generic over the deque
+// type and reach the entries only through dq_find, dq_touch, dq_reposition, dq_insert, dq_unlink, dq_set_wt, dq_refresh_oldest,
+// dq_head, dq_lu and dq_wt.  `Deque` is the LDS tile; cache_wide_kernels.hpp has the blocked one in global memory.
+struct CacheRegs {
     int32_t *stk_key, *stk_wt;  // pending victims (LIFO)
     int64_t *stk_lu;            // with TIMES: their lastUsed, a third column that moves with the two above
-    int head, n, sp;
+    int n, sp;
     int64_t wsize, cap;
     int64_t oldest;  // clhm `oldestTime`: what updateOldestTime() last stored (afterWrite :444, tryToDrainBuffers :463) — setCapacity's
                      // own evict (:305-316) does not store it, so it can be stale after a failed unload (unloadComplete :318-338)
@@ -79,6 +80,17 @@ struct Deque {
     int64_t *ev_lu;  // with TIMES
     int nev;
 };
+
+struct Deque : CacheRegs {
+    int64_t *lu;
+    int32_t *wt, *key;
+    int head;
+};
+
+// a position is the index from the head
+__device__ __forceinline__ int dq_head(const Deque &) { return 0; }
+__device__ __forceinline__ int64_t dq_lu(const Deque &D, int i) { return D.lu[D.head + i]; }
+__device__ __forceinline__ int32_t dq_wt(const Deque &D, int i) { return D.wt[D.head + i]; }
 
 template <int TW>
 __device__ __forceinline__ int dq_find(const Deque &D, int32_t k)
@@ -212,8 +224,8 @@ __device__ __forceinline__ void dq_refresh_oldest(Deque &D) { D.oldest = D.n ? D
 
 // `lu` is what the clhm hands the listener: node.getLastUsed() at notification (clhm :578-586), which is the value the node
 // had when evict() unlinked it — nothing touches a dead node
-template <int TW, bool TIMES>
-__device__ __forceinline__ void record_evicted(Deque &D, int32_t k, int64_t lu)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void record_evicted(DQ &D, int32_t k, int64_t lu)
 {
     if (team_lane<TW>() == 0) {
         D.ev[D.nev] = k;
@@ -224,14 +236,14 @@ __device__ __forceinline__ void record_evicted(Deque &D, int32_t k, int64_t lu)
 
 // evict(), clhm :329-352 (makeDead subtracts |weight|, :566-575).  Plain caches record the victims
 // directly; with a manager they go onto the pending LIFO, oldest on top.
-template <int TW, bool TIMES>
-__device__ __forceinline__ void dq_evict(Deque &D, bool managed)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void dq_evict(DQ &D, bool managed)
 {
     const int first = D.sp;
     while (D.wsize > D.cap && D.n > 0) {
         int64_t ts;
         int32_t w, k;
-        dq_unlink<TW>(D, 0, ts, w, k);
+        dq_unlink<TW>(D, dq_head(D), ts, w, k);
         D.wsize -= w < 0 ? -(int64_t)w : (int64_t)w;
         if (managed) {
             if (team_lane<TW>() == 0) {
@@ -279,14 +291,14 @@ __device__ __forceinline__ void dq_evict(Deque &D, bool managed)
 }
 
 // CacheEntry.updateWeightLocked -> replaceQuietly -> UpdateTask(quiet), without running the listener
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_set_weight_nodrain(Deque &D, int32_t k, int32_t w)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_set_weight_nodrain(DQ &D, int32_t k, int32_t w)
 {
     // the weigher is CacheEntry.getWeight = Math.abs(weight) (MM.java:1759): a sum that wrapped negative weighs its magnitude
     if (w < 0) w = (int32_t)(0u - (uint32_t)w);
     const int i = dq_find<TW>(D, k);
     if (i < 0) return;
-    const int32_t diff = (int32_t)((uint32_t)w - (uint32_t)D.wt[D.head + i]);
+    const int32_t diff = (int32_t)((uint32_t)w - (uint32_t)dq_wt(D, i));
     if (diff == 0) return;
     dq_set_wt<TW>(D, i, w);
     D.wsize += diff;
@@ -295,8 +307,8 @@ __device__ __forceinline__ void ubm_set_weight_nodrain(Deque &D, int32_t k, int3
 }
 
 // adjustAggregateUnloadingWeight, ModelCacheUnloadBufManager.java:375-392 (listener not yet run)
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_adjust_agg_nodrain(Deque &D, int32_t delta)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_adjust_agg_nodrain(DQ &D, int32_t delta)
 {
     if (delta == 0) return;
     D.tu = (int32_t)((uint32_t)D.tu + (uint32_t)delta);
@@ -311,8 +323,8 @@ __device__ __forceinline__ void ubm_adjust_agg_nodrain(Deque &D, int32_t delta)
 }
 
 // the eviction listener: ModelMesh.onEviction -> entryRemoved (:311-316) per victim, depth first
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_drain(Deque &D)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_drain(DQ &D)
 {
     while (D.sp > 0) {
         D.sp--;
@@ -326,22 +338,23 @@ __device__ __forceinline__ void ubm_drain(Deque &D)
     }
 }
 
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_adjust_agg(Deque &D, int32_t delta)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_adjust_agg(DQ &D, int32_t delta)
 {
     ubm_adjust_agg_nodrain<TW, TIMES>(D, delta);
     ubm_drain<TW, TIMES>(D);
 }
 
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_set_weight(Deque &D, int32_t k, int32_t w)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_set_weight(DQ &D, int32_t k, int32_t w)
 {
     ubm_set_weight_nodrain<TW, TIMES>(D, k, w);
     ubm_drain<TW, TIMES>(D);
 }
 
 // cacheSpaceIsReady, :395-402
-__device__ __forceinline__ bool ubm_space_ready(const Deque &D, int32_t required)
+template <class DQ>
+__device__ __forceinline__ bool ubm_space_ready(const DQ &D, int32_t required)
 {
     const int32_t ntu = (int32_t)((uint32_t)D.tu + (uint32_t)required);
     if (ntu <= D.reserved) return true;
@@ -349,8 +362,8 @@ __device__ __forceinline__ bool ubm_space_ready(const Deque &D, int32_t required
 }
 
 // payDownDeficitAndNotifyWaiters, :351-366
-template <int TW, bool TIMES>
-__device__ __forceinline__ void ubm_pay_down(Deque &D, int32_t weight, bool release)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ void ubm_pay_down(DQ &D, int32_t weight, bool release)
 {
     const int32_t reduction = weight < D.deficit ? weight : D.deficit;
     if (reduction != 0) {
@@ -361,14 +374,15 @@ __device__ __forceinline__ void ubm_pay_down(Deque &D, int32_t weight, bool rele
 }
 
 // cacheRemaining, :340-342
-__device__ __forceinline__ int32_t ubm_cache_remaining(const Deque &D)
+template <class DQ>
+__device__ __forceinline__ int32_t ubm_cache_remaining(const DQ &D)
 {
     const int64_t r = D.cap - D.wsize;
     return r > INT32_MAX ? INT32_MAX : (int32_t)r;
 }
 
-template <int TW, bool TIMES>
-__device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int64_t now)
+template <int TW, bool TIMES, class DQ>
+__device__ __forceinline__ int32_t apply_op(DQ &D, const mmp_cache_op &o, int64_t now)
 {
     switch (o.op) {
     case MMP_COP_PUT_IF_ABSENT: {  // clhm :804-834, AddTask :590-611
@@ -398,7 +412,7 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
     case MMP_COP_UPDATE_WEIGHT: {  // clhm :902-985, UpdateTask :629-652; time -1 = quiet
         const int i = dq_find<TW>(D, o.key);
         if (i < 0) return 0;
-        const int32_t diff = (int32_t)((uint32_t)o.arg - (uint32_t)D.wt[D.head + i]);
+        const int32_t diff = (int32_t)((uint32_t)o.arg - (uint32_t)dq_wt(D, i));
         dq_set_wt<TW>(D, i, o.arg);
         if (diff == 0) {
             if (o.time >= 0) {
@@ -409,7 +423,7 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
             return 1;
         }
         D.wsize += diff;
-        if (o.time >= 0 && o.time != D.lu[D.head + i]) {
+        if (o.time >= 0 && o.time != dq_lu(D, i)) {
             dq_touch<TW>(D, i, o.time, now);
             dq_reposition<TW>(D, i);
         }
@@ -449,7 +463,7 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
     case MMP_COP_UBM_ADJUST_SPACE_REQUEST: {  // adjustNewEntrySpaceRequest, :152-166
         const int i = dq_find<TW>(D, o.key);
         if (i < 0) return 0;
-        const int32_t nw = (int32_t)((uint32_t)D.wt[D.head + i] + (uint32_t)o.arg);
+        const int32_t nw = (int32_t)((uint32_t)dq_wt(D, i) + (uint32_t)o.arg);
         D.occ += o.arg;
         ubm_adjust_agg<TW, TIMES>(D, -o.arg);
         ubm_set_weight<TW, TIMES>(D, o.key, nw);
@@ -473,7 +487,7 @@ __device__ __forceinline__ int32_t apply_op(Deque &D, const mmp_cache_op &o, int
         }
         D.occ += delta;
         const int i = dq_find<TW>(D, o.key);
-        if (i >= 0) ubm_set_weight<TW, TIMES>(D, o.key, (int32_t)((uint32_t)D.wt[D.head + i] + (uint32_t)delta));
+        if (i >= 0) ubm_set_weight<TW, TIMES>(D, o.key, (int32_t)((uint32_t)dq_wt(D, i) + (uint32_t)delta));
         if (delta < 0) ubm_pay_down<TW, TIMES>(D, -delta, false);
         return i >= 0 ? 1 : 0;
     }
@@ -616,8 +630,8 @@ __global__ __launch_bounds__(64) void cache_replay_kernel(ReplayArgs A, const in
         oi = oi_next;
     }
     for (int i = lane; i < D.n; i += TW) {
-        A.dst.lu[dn + i] = D.lu[D.head + i];
-        A.dst.wt[dn + i] = D.wt[D.head + i];
+        A.dst.lu[dn + i] = dq_lu(D, i);
+        A.dst.wt[dn + i] = dq_wt(D, i);
         A.dst.key[dn + i] = D.key[D.head + i];
     }
     if (lane == 0) {

@@ -47,6 +47,7 @@
 #include "registry_ops_keyed_kernels.hpp"
 #include "evictions_kernels.hpp"
 #include "cache_keyed_kernels.hpp"
+#include "cache_wide_kernels.hpp"
 #include "tasks_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
@@ -366,6 +367,7 @@ struct Tuning {
     int32_t label_hash_bits = 64;     // MMP_LABEL_HASH_BITS=b: the same for the label-name hashes (tests: the byte comparison of label_find)
     int32_t model_id_hash_bits = 64;  // MMP_MODEL_ID_HASH_BITS=b: every model-id hash is masked to its low b bits, 0: all equal (tests: ids that collide)
     int32_t vmodel_id_hash_bits = 64;  // MMP_VMODEL_ID_HASH_BITS=b: the same for the vmodel-id hashes
+    int32_t cache_wide_from = kCacheTile;  // MMP_CACHE_WIDE_FROM=n: a replayed cache with slots + 1 > n takes the blocked deque in global memory (0: every one; tests)
 };
 
 struct mmp_ctx {
@@ -564,6 +566,10 @@ struct mmp_ctx {
     bool evid_timed = false;       // (mmp_cache_replay_kt; a plain mmp_cache_replay_k or a cache load clears it)
     DevBuf ev_in, ev_out;  // mmp_evictions_k: the victims' entries, their mmp_evicted_out rows
     DevBuf k_inv, k_kstat, k_krow, k_len, k_goff, k_gbytes;  // inverse of k_order; status / row by caller op; the id gather's lengths, offsets, bytes
+    // the blocked replay (cache_wide_kernels.hpp): the most deque slots a replay accepts per cache (mmp_cache_slots_limit) and the
+    // scratch of a call's caches on that route: descriptors | directory | two copies of the blocks | pending LIFO | key index
+    int32_t k_slots_limit = MMP_CACHE_SLOTS_DEFAULT;
+    DevBuf k_wide;
 
     // wire-format ingestion: per-pod id attributes and the hash tables the parsers probe
     std::vector<uint32_t> id_order_v;
@@ -974,6 +980,8 @@ Tuning read_tuning()
     t.vmodel_id_hash_bits = std::max(0, std::min(t.vmodel_id_hash_bits, 64));
     num("MMP_LABEL_HASH_BITS", t.label_hash_bits);
     t.label_hash_bits = std::max(0, std::min(t.label_hash_bits, 64));
+    num("MMP_CACHE_WIDE_FROM", t.cache_wide_from);
+    t.cache_wide_from = std::max(0, std::min(t.cache_wide_from, kCacheTile));  // (beyond the tile there is no other route)
     return t;
 }
 
@@ -1584,7 +1592,7 @@ void mmp_destroy(mmp_ctx *c)
                       &c->c_lu, &c->c_wt, &c->c_cap, &c->s_reqs, &c->s_outs, &c->s_extra, &c->s_a, &c->s_b,
                       &c->s_c, &c->s_d, &c->r_ps, &c->r_counts, &c->r_keys, &c->r_vals, &c->r_keys2, &c->r_vals2,
                       &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
-                      &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->k_inv, &c->k_kstat, &c->k_krow, &c->k_len, &c->k_goff, &c->k_gbytes, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
+                      &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->k_inv, &c->k_kstat, &c->k_krow, &c->k_len, &c->k_goff, &c->k_gbytes, &c->k_wide, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
                       &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
                       &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu, &c->rf_refs, &c->vw_reqs, &c->vw_strs, &c->vw_soff, &c->vw_rows,
                       &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_rows_next, &c->vm_arena,
@@ -9056,22 +9064,46 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
             ins[o.cache]++;
     }
     std::vector<int32_t> op_off(NC + 1, 0), new_off(NC + 1, 0), ev_off(NC + 1, 0);
-    // team width per cache by the deque slots its replay needs: [0] 8 lanes, [1] 16 lanes, [2] the whole wavefront
+    // team width per cache by the deque slots its replay needs: [0] 8 lanes, [1] 16 lanes, [2] the whole wavefront; [3]: a cache with
+    // operations that the LDS tile does not hold (or MMP_CACHE_WIDE_FROM sends there): the blocked deque of cache_wide_kernels.hpp
     int32_t tile = 1, tiles[3] = {1, 1, 1};
-    std::vector<int32_t> ids[3];
+    std::vector<int32_t> ids[4];
+    std::vector<WideDesc> wide;
+    int64_t wide_blocks = 0, wide_cells = 0, wide_stk = 0;
+    int32_t wide_nb = 0;
     for (int32_t k = 0; k < NC; k++) {
         op_off[k + 1] = op_off[k] + cnt[k + 1];
         const int32_t slots = c->k_n[k] + ins[k];
         new_off[k + 1] = new_off[k] + slots;
         ev_off[k + 1] = ev_off[k] + (cnt[k + 1] ? slots : 0);  // a cache cannot evict more than it ever held
+        if (cnt[k + 1]) tile = std::max(tile, slots + 1);
+        if (cnt[k + 1] && slots + 1 > c->tune.cache_wide_from) {
+            WideDesc d{};
+            d.cache = k;
+            d.nb = div_up(slots, kWideFill) + 1;
+            d.blk0 = (int32_t)wide_blocks;
+            int32_t cells = 64;
+            while (cells < 2 * slots) cells *= 2;
+            d.tab0 = (int32_t)wide_cells;
+            d.tab_mask = cells - 1;
+            d.stk0 = (int32_t)wide_stk;
+            wide.push_back(d);
+            ids[3].push_back(k);
+            wide_blocks += d.nb, wide_cells += cells, wide_stk += slots;
+            wide_nb = std::max(wide_nb, d.nb);
+            continue;
+        }
         const int w = slots + 1 <= kTeam8Slots ? 0 : slots + 1 <= kTeam16Slots ? 1 : 2;
         ids[w].push_back(k);
-        if (cnt[k + 1]) {
-            tile = std::max(tile, slots + 1);
-            tiles[w] = std::max(tiles[w], slots + 1);
-        }
+        if (cnt[k + 1]) tiles[w] = std::max(tiles[w], slots + 1);
     }
-    if (tile > kCacheTile) return fail(c, MMP_EINVAL, "%s: a cache needs %d deque slots, the tile holds %d", fn, tile, kCacheTile);
+    if (tile > c->k_slots_limit + 1) {
+        if (c->k_slots_limit == MMP_CACHE_SLOTS_DEFAULT)
+            return fail(c, MMP_EINVAL, "%s: a cache needs %d deque slots, the tile holds %d", fn, tile, kCacheTile);
+        return fail(c, MMP_EINVAL, "%s: a cache needs %d deque slots, the context accepts %d (mmp_cache_slots_limit)", fn, tile - 1, c->k_slots_limit);
+    }
+    if (wide_blocks * kWideBlock > INT32_MAX || wide_cells > INT32_MAX)
+        return fail(c, MMP_EINVAL, "%s: the caches beyond the LDS tile need %lld blocks of %d slots in one call", fn, (long long)wide_blocks, kWideBlock);
     if (ev_off[NC] > max_evicted) return fail(c, MMP_EINVAL, "%s: evicted_keys needs room for %d keys", fn, ev_off[NC]);
     if (kx)
         if (const int rc = check_offsets(c, fn, "key ", kx->key_off, n_ops)) return rc;
@@ -9132,11 +9164,42 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     A.n_caches = NC;
     A.tile = tile;
     A.now = now;
+    // the scratch of the blocked route, carved from one buffer (8-byte columns first)
+    WideArgs W{};
+    if (!wide.empty()) {
+        const size_t nblk = (size_t)wide_blocks, nslot = nblk * kWideBlock, nstk = (size_t)std::max<int64_t>(wide_stk, 1);
+        const size_t desc_bytes = (wide.size() * sizeof(WideDesc) + 15) & ~(size_t)15;
+        const size_t bytes = desc_bytes + nblk * 8 + 2 * nslot * 8 + nstk * 8 + (size_t)wide_cells * 8 + nblk * 8 + 4 * nslot * 4 + 2 * nstk * 4 +
+                             wide.size() * 4;
+        HIP_TRY(c, c->k_wide.ensure(bytes));
+        char *p = c->k_wide.as<char>();
+        const auto take = [&p](size_t n) { char *q = p; p += n; return q; };
+        W.desc = reinterpret_cast<const WideDesc *>(take(desc_bytes));
+        W.n_wide = (int32_t)wide.size();
+        W.n_blocks = (int32_t)wide_blocks;
+        W.bmin = reinterpret_cast<int64_t *>(take(nblk * 8));
+        W.lu0 = reinterpret_cast<int64_t *>(take(nslot * 8));
+        W.lu1 = reinterpret_cast<int64_t *>(take(nslot * 8));
+        W.stk_lu = reinterpret_cast<int64_t *>(take(nstk * 8));
+        W.tab = reinterpret_cast<unsigned long long *>(take((size_t)wide_cells * 8));
+        W.bfc = reinterpret_cast<uint32_t *>(take(nblk * 4));
+        W.bflat = reinterpret_cast<int32_t *>(take(nblk * 4));
+        W.wt0 = reinterpret_cast<int32_t *>(take(nslot * 4));
+        W.wt1 = reinterpret_cast<int32_t *>(take(nslot * 4));
+        W.key0 = reinterpret_cast<int32_t *>(take(nslot * 4));
+        W.key1 = reinterpret_cast<int32_t *>(take(nslot * 4));
+        W.stk_key = reinterpret_cast<int32_t *>(take(nstk * 4));
+        W.stk_wt = reinterpret_cast<int32_t *>(take(nstk * 4));
+        W.cur = reinterpret_cast<int32_t *>(take(wide.size() * 4));
+        HIP_TRY(c, hipMemcpyAsync(c->k_wide.p, wide.data(), wide.size() * sizeof(WideDesc), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemsetAsync(W.tab, 0xff, (size_t)wide_cells * 8, st));  // every cell {-1, kCellEmpty}
+    }
     HIP_TRY(c, c->k_ids.ensure((size_t)NC * 4));
     {
         std::vector<int32_t> all;
         all.reserve(NC);
-        for (auto &v : ids) all.insert(all.end(), v.begin(), v.end());
+        for (int w = 0; w < 3; w++) all.insert(all.end(), ids[w].begin(), ids[w].end());
+        all.resize((size_t)NC, 0);  // (the caches of the blocked route are listed in its descriptors)
         HIP_TRY(c, hipMemcpyAsync(c->k_ids.p, all.data(), (size_t)NC * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipStreamSynchronize(st));  // `all` leaves scope (the other uploads above are from vectors that live to the end)
     }
@@ -9179,6 +9242,15 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
         launch(cache_replay_kernel<8, true>, cache_replay_kernel<16, true>, cache_replay_kernel<64, true>);
     else
         launch(cache_replay_kernel<8, false>, cache_replay_kernel<16, false>, cache_replay_kernel<64, false>);
+    if (!wide.empty()) {  // blocks from the flat store, the replay on the blocks, the flat store from the blocks
+        const size_t dir_lds = (size_t)wide_nb * 12;
+        hipLaunchKernelGGL(cache_wide_spread_kernel, dim3(W.n_blocks), dim3(64), 0, st, A, W);
+        if (times)
+            hipLaunchKernelGGL(cache_wide_replay_kernel<true>, dim3(W.n_wide), dim3(64), dir_lds, st, A, W, wide_nb);
+        else
+            hipLaunchKernelGGL(cache_wide_replay_kernel<false>, dim3(W.n_wide), dim3(64), dir_lds, st, A, W, wide_nb);
+        hipLaunchKernelGGL(cache_wide_compact_kernel, dim3(W.n_blocks), dim3(64), 0, st, A, W);
+    }
     if (kx && n_slots)  // the lengths of the victims' ids and their scan, in the same span
         if (const int rc = ckey_gather_sizes(c, c->k_ev.as<int32_t>(), n_slots)) return rc;
     KT_END(c, st);
@@ -9235,6 +9307,17 @@ try {
     std::lock_guard<std::shared_mutex> g(c->mu);
     return cache_replay_drive(c, "mmp_cache_replay", ops, n_ops, now, outs, evicted_keys, max_evicted, n_evicted_slots, nullptr);
 } MMP_CATCH(c, "mmp_cache_replay")
+
+int mmp_cache_slots_limit(mmp_ctx *c, int32_t max_slots)
+try {
+    if (!c) return MMP_EINVAL;
+    if (max_slots < MMP_CACHE_SLOTS_DEFAULT || max_slots > MMP_CACHE_SLOTS_MAX)
+        return fail(c, MMP_EINVAL, "mmp_cache_slots_limit: %d is outside [%d, %d]", max_slots, MMP_CACHE_SLOTS_DEFAULT, MMP_CACHE_SLOTS_MAX);
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    c->k_slots_limit = max_slots;
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_cache_slots_limit")
 
 int mmp_cache_replay_k(mmp_ctx *c, const mmp_cache_op *ops, int32_t n_ops, const char *keys, const int32_t *key_off, int64_t now,
                        int32_t *key_status_out, int32_t *key_row_out, mmp_cache_op_out *outs, int32_t *evicted_rows, int32_t max_evicted,

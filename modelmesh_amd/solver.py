@@ -969,6 +969,11 @@ class Solver:
                                            ptr(outs) if len(ops) else None, ptr(ev), len(ev), C.byref(used)))
         return outs, ev[: used.value]
 
+    def cache_slots_limit(self, max_slots: int):
+        """The most deque slots (entries + a call's inserts) per cache that a replay on this solver accepts (mmp_cache_slots_limit):
+        2047 by default, up to 262144; caches beyond 2047 slots are replayed on a blocked deque in device memory."""
+        self._ck(self.lib.mmp_cache_slots_limit(self.h, int(max_slots)))
+
     def cache_read(self, cache: int, max_entries: int = 4096):
         from ._lib import UBM_STATE
         lu = np.zeros(max_entries, np.int64)
