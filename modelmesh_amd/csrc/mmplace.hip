@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/mmplace.h"
+#include "devbuf.hpp"  // behind hip_runtime.h: it names the HIP calls and declares none
 #include "aux_kernels.hpp"
 #include "cache_kernels.hpp"
 #include "gate_kernel.hpp"
@@ -76,51 +77,6 @@ namespace {
 // slots) and the JNI veneer hands this pointer to ThrowNew, so it must not be a string another thread can rewrite.
 thread_local std::string g_thread_err;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 256);
-        want = (want + 255) & ~size_t(255);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// A DevBuf built beside a published one: the carrier of the library's ownership rule (written out at mmp_ctx::mid_hash).  Its
-// owner holds batch_mu and declares it ahead of the work; move_into, under the state lock held EXCLUSIVE, publishes it and takes
-// what it replaced, which stays allocated and unwritten until this object ends or is released explicitly.  Between the swap and
-// that end the owner runs the drain (quiesce_decisions: inside the hold, or behind it), so no kernel that captured the replaced
-// buffer is still running when it goes.  Never published: released on every way out, a thrown one included.
-struct ScopedDevBuf {
-    DevBuf b;
-    ScopedDevBuf() = default;
-    ScopedDevBuf(const ScopedDevBuf &) = delete;
-    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
-    ~ScopedDevBuf() { b.release(); }
-    bool move_into(DevBuf &dst)  // whether there was anything to publish
-    {
-        if (!b.p) return false;
-        std::swap(dst, b);
-        return true;
-    }
-    void release() { b.release(); }
-};
-
 // device storage of one committed snapshot
 struct SnapBufs {
     DevBuf pods, lru, rem, cnt, rpm, orig, pos_of, elig, elig_nors, pref, has_pref, fullw, ge, pc, ph, nz, heads, bslots, bpm, bwin, bsurv, bpcs;
@@ -132,11 +88,6 @@ struct SnapBufs {
     DevBuf ctpos;  // Snap::ctpos
     uint64_t types_gen = 0;  // has_pref holds the type table of this generation
     int32_t n_bslots = 0;  // case (b) slots this snapshot has (place_kernel.hpp: BSlot), read back at commit
-    void release()
-    {
-        for (DevBuf *b : {&pods, &lru, &rem, &cnt, &rpm, &orig, &pos_of, &elig, &elig_nors, &pref, &has_pref, &fullw, &ge, &pc, &ph, &nz, &heads, &bslots, &bpm, &bwin, &bsurv, &bpcs, &ctpos, &sel, &rk, &amul, &memo, &memo_cand, &memo_rk, &lmemo})
-            b->release();
-    }
 };
 
 // What Snap and ShardSnap share: the sizes, and B's rank-ordered columns and bitmaps (a template: in front of the extern "C" part).
@@ -176,10 +127,6 @@ struct SnapSide {
     std::vector<uint64_t> pts_prohib;   // [n_pts][tw] prohibited type rows
     int32_t n_pts = 0, pts_tw = 1;
     std::vector<StatsAcc> pstats_h, tstats_h;  // host mirrors (pstats_h has n_pts + 1 entries: the last is EMPTY_STATS)
-    void release()
-    {
-        for (DevBuf *b : {&d_allowed, &d_has_allowed, &stats_acc, &d_pts, &d_prohib, &pstats, &tstats, &rmodels, &mtw}) b->release();
-    }
 };
 
 }  // namespace
@@ -201,11 +148,11 @@ constexpr int kFastExtra = 16384;  // extra-exclusion pool entries per fast call
 struct FastSlot {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    mmp_place_req *reqs = nullptr;  // hipHostMalloc'ed: same pointer is valid on the device
-    int32_t *extra = nullptr;
-    mmp_place_out *outs = nullptr;
-    uint32_t *done = nullptr;  // pinned: the kernel stores the call's sequence number here when its results are visible
-    uint32_t *blocks = nullptr;  // device: finished-workgroup counter of the call in flight
+    PinBuf<mmp_place_req> reqs;  // hipHostMalloc'ed: same pointer is valid on the device
+    PinBuf<int32_t> extra;
+    PinBuf<mmp_place_out> outs;
+    PinBuf<uint32_t> done;  // pinned: the kernel stores the call's sequence number here when its results are visible
+    DevBuf blocks;          // device: finished-workgroup counter of the call in flight
     // sequence number of the slot's last launch: bumped by the owner (under f.mu and the shared state lock), read by
     // quiesce_decisions without either — hence atomic
     std::atomic<uint32_t> seq{0};
@@ -394,9 +341,9 @@ struct mmp_ctx {
         std::atomic<bool> enabled{false}, running{false};
         std::atomic<uint32_t> generation{0};  // of the kernel launched last (1, 2, ...)
         hipStream_t stream = nullptr;
-        ResidentSlot *slots = nullptr;  // pinned, device-mapped: host -> device
-        ResidentAnswer *answers = nullptr;  // pinned, device-mapped: device -> host
-        ResidentCtl *ctl = nullptr;     // pinned
+        PinBuf<ResidentSlot> slots;      // pinned, device-mapped: host -> device
+        PinBuf<ResidentAnswer> answers;  // pinned, device-mapped: device -> host
+        PinBuf<ResidentCtl> ctl;         // pinned
         std::mutex launch_mu;           // taken AFTER the state lock
         std::mutex slot_mu[kResidentSlots];
         uint32_t seq[kResidentSlots] = {};
@@ -432,17 +379,16 @@ struct mmp_ctx {
     // buffer's lookup until the tail is enqueued (two host threads on one stream).  Slots have fixed addresses; mmp_stream_retire
     // returns a stream's slot.
     struct MissBuf {
-        std::mutex mu;             // taken after the state lock, before miss_mu; guards words / cap
+        std::mutex mu;             // taken after the state lock, before miss_mu; guards words
         bool used = false;         // (used, st, report: under miss_mu; a slot in use is returned only with mu held as well)
         hipStream_t st = nullptr;
-        int32_t *words = nullptr;  // place_kernel.hpp: rest_buffer_ints — counters, gate line + kRestLists lists
-        size_t cap = 0;            // ints
+        DevBuf words;              // place_kernel.hpp: rest_buffer_ints — counters, gate line + kRestLists lists (grown by miss_buffer's own policy)
         uint32_t calls = 0;        // split batches enqueued on `words`: its parity names the call's gate word (place_kernel.hpp, above kRestLists); under mu
         int32_t *report = nullptr;
     };
     MissBuf miss_bufs[kMaxMissBufs];
-    std::vector<void *> miss_retired; // outgrown word buffers: a launch in flight may still read them; freed with the context (miss_mu)
-    int32_t *miss_reports = nullptr;  // pinned, kMaxMissBufs pairs (slot i: pair i)
+    std::vector<DevBuf> miss_retired; // outgrown word buffers: a launch in flight may still read them; freed with the context (miss_mu)
+    PinBuf<int32_t> miss_reports;     // pinned, kMaxMissBufs pairs (slot i: pair i)
     std::mutex miss_mu;               // a leaf lock: slot lookup / allocation, miss_retired, miss_reports
     std::atomic<bool> split_off{false};  // a tail reported more than 1/32 of its batch: batches go unsplit until the next commit / registry event
     std::atomic<int64_t> n_split{0};     // split batches issued (mmp_split_batches)
@@ -489,7 +435,7 @@ struct mmp_ctx {
     // batch is completed after the NEXT one has been enqueued, so the two must not share flags, counter, word or exchange words
     DevBuf f_flags[2];             // per decision: undecided by the single exchange
     DevBuf f_cnt[2];               // finished workgroups << 32 | flagged decisions of the finish launch in flight (zero between launches)
-    uint64_t *f_done = nullptr;    // pinned, words [0] and [8]: seq << 32 | flagged decisions, stored by the finish kernel's last workgroup
+    PinBuf<uint64_t> f_done;       // pinned, words [0] and [8]: seq << 32 | flagged decisions, stored by the finish kernel's last workgroup
     uint32_t f_slot = 0;
     uint32_t f_seq = 0;
     // mmp_shard_place_batch_async_dev: the batch whose finish kernel is enqueued and whose rest count has not been read yet
@@ -606,7 +552,8 @@ struct mmp_ctx {
     // capture the fields and enqueue.  A buffer a swap retires (the old table, which becomes mid_next_*; an arena or offset array
     // that moved) is neither rewritten nor released before quiesce_decisions has run behind the swap (model_ids_retired_drain).
     // ScopedDevBuf carries the rule for every buffer that is not one of a ping-pong pair: built in it, published by move_into, the
-    // retired allocation released when it ends.
+    // retired allocation released when it ends.  Every buffer frees itself with its context (devbuf.hpp); ScopedDevBuf is about
+    // WHEN a replaced buffer may go.
     // me_*: one call's keys on the device — hashes, resolved rows, dedupe
     // slots, the call-local table (owner | first | first_nd), the flags and their scan, model_idx, the joining events, what the
     // verify found.  (slot / slot_model and the deleted bytes are written where the pipeline reads them: j_ev.)
@@ -770,10 +717,10 @@ hipError_t copy_sync(mmp_ctx *c, void *dst, const void *src, size_t bytes, hipMe
 void resident_stop(mmp_ctx *c)
 {
     auto &R = c->res;
-    if (!R.slots) return;
+    if (!R.slots.p) return;
     std::lock_guard<std::mutex> g(R.launch_mu);
     if (!R.running) return;
-    __atomic_store_n(&R.ctl->stop, R.generation.load(std::memory_order_relaxed), __ATOMIC_RELEASE);
+    __atomic_store_n(&R.ctl.p->stop, R.generation.load(std::memory_order_relaxed), __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(R.stream);
     R.running = false;
 }
@@ -788,9 +735,9 @@ hipError_t quiesce_decisions(mmp_ctx *c)
     // exclusive lock).  The number is read ONCE per slot: the quiescer waits for the launches that existed when it came, not for
     // the ones a busy owner keeps adding behind them (sequence numbers wrap: compare by difference).
     for (FastSlot &f : c->fast) {
-        if (!f.done) continue;
+        if (!f.done.p) continue;
         const uint32_t snap = f.seq.load(std::memory_order_acquire);
-        if ((int32_t)(__atomic_load_n(f.done, __ATOMIC_ACQUIRE) - snap) >= 0) continue;
+        if ((int32_t)(__atomic_load_n(f.done.p, __ATOMIC_ACQUIRE) - snap) >= 0) continue;
         hipError_t e = slot_wait(&f, snap);
         if (e != hipSuccess) return e;
     }
@@ -872,7 +819,7 @@ hipError_t slot_wait(FastSlot *f, uint32_t seq)
 {
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 0;; spins++) {
-        if ((int32_t)(__atomic_load_n(f->done, __ATOMIC_ACQUIRE) - seq) >= 0) return hipSuccess;
+        if ((int32_t)(__atomic_load_n(f->done.p, __ATOMIC_ACQUIRE) - seq) >= 0) return hipSuccess;
         if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(500)) break;
         __builtin_ia32_pause();
     }
@@ -898,16 +845,13 @@ bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32
             }
             if (!mb) {
                 if (!fresh) return false;
-                if (!c->miss_reports) {
-                    if (hipHostMalloc(reinterpret_cast<void **>(&c->miss_reports), (size_t)kMaxMissBufs * 2 * sizeof(int32_t), kPinnedFlags) != hipSuccess) {
-                        c->miss_reports = nullptr;
-                        return false;
-                    }
-                    memset(c->miss_reports, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
+                if (!c->miss_reports.p) {
+                    if (c->miss_reports.alloc((size_t)kMaxMissBufs * 2, kPinnedFlags) != hipSuccess) return false;
+                    memset(c->miss_reports.p, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
                 }
                 fresh->used = true;
                 fresh->st = st;
-                fresh->report = c->miss_reports + 2 * (fresh - c->miss_bufs);
+                fresh->report = c->miss_reports.p + 2 * (fresh - c->miss_bufs);
                 fresh->report[0] = fresh->report[1] = 0;  // (a reused slot: what the retired stream's tails reported is not this one's)
                 mb = fresh;
             }
@@ -920,32 +864,31 @@ bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32
             mb = nullptr;
         }
     }
-    if (mb->cap < ints) {
+    const size_t cap = mb->words.cap / sizeof(int32_t);  // ints
+    if (cap < ints) {
         size_t want = std::max<size_t>(ints, 65536);
-        want = std::max(want, mb->cap + mb->cap / 2);
-        void *p = nullptr;
-        if (hipMalloc(&p, want * sizeof(int32_t)) != hipSuccess) {
+        want = std::max(want, cap + cap / 2);
+        DevBuf grown;  // never published: freed on the way out
+        if (grown.alloc(want * sizeof(int32_t)) != hipSuccess) {
             hold.unlock();
             return false;
         }
         // the counters and both gate words start at zero (every tail leaves its lists' counters and the other call's gate word so);
         // ordered before the stream's first launch on this buffer
-        if (hipMemsetAsync(p, 0, (size_t)kRestHeadInts * sizeof(int32_t), st) != hipSuccess) {
-            (void)hipFree(p);
+        if (hipMemsetAsync(grown.p, 0, (size_t)kRestHeadInts * sizeof(int32_t), st) != hipSuccess) {
             hold.unlock();
             return false;
         }
-        if (mb->words) {  // (a launch in flight may still read it)
+        if (mb->words.p) {  // (a launch in flight may still read it)
             std::lock_guard<std::mutex> g(c->miss_mu);
-            c->miss_retired.push_back(mb->words);
+            c->miss_retired.push_back(std::move(mb->words));
         }
-        mb->words = static_cast<int32_t *>(p);
-        mb->cap = want;
+        mb->words = std::move(grown);
     }
     // the last tail of this stream that has finished: more than 1/32 of its batch undecided -> the records do not fit these batches
     const int32_t undecided = __atomic_load_n(&mb->report[0], __ATOMIC_RELAXED), of = __atomic_load_n(&mb->report[1], __ATOMIC_RELAXED);
     if (of > 0 && (int64_t)undecided * 32 > (int64_t)of) c->split_off.store(true, std::memory_order_relaxed);
-    *words = mb->words;
+    *words = mb->words.as<int32_t>();
     *report = mb->report;
     *calls = &mb->calls;
     return true;
@@ -954,7 +897,7 @@ bool miss_buffer(mmp_ctx *c, hipStream_t st, size_t ints, int32_t **words, int32
 void split_reset(mmp_ctx *c)
 {
     std::lock_guard<std::mutex> g(c->miss_mu);
-    if (c->miss_reports) memset(c->miss_reports, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
+    if (c->miss_reports.p) memset(c->miss_reports.p, 0, (size_t)kMaxMissBufs * 2 * sizeof(int32_t));
     c->split_off.store(false, std::memory_order_relaxed);
 }
 
@@ -1372,7 +1315,7 @@ std::array<SeamIo *, sizeof...(Io) + N> seam_list(const std::array<SeamIo *, N> 
 }
 inline void *slot_ptr(FastSlot *f, const SlotRegion &r)
 {
-    char *base = r.buf == kSlotReq ? reinterpret_cast<char *>(f->reqs) : r.buf == kSlotPool ? reinterpret_cast<char *>(f->extra) : reinterpret_cast<char *>(f->outs);
+    char *base = r.buf == kSlotReq ? reinterpret_cast<char *>(f->reqs.p) : r.buf == kSlotPool ? reinterpret_cast<char *>(f->extra.p) : reinterpret_cast<char *>(f->outs.p);
     return base + r.off;
 }
 
@@ -1400,7 +1343,7 @@ __attribute__((always_inline)) inline int seam_slot(mmp_ctx *c, SeamSpan ins, Se
     {
         std::shared_lock<std::shared_mutex> g(c->mu);  // capture the published state + enqueue
         if (const int rc = check()) return rc;
-        if (const int rc = launch(f->stream, DoneFlag{f->done, f->blocks, ++f->seq}, std::true_type{})) return rc;
+        if (const int rc = launch(f->stream, DoneFlag{f->done.p, f->blocks.as<uint32_t>(), ++f->seq}, std::true_type{})) return rc;
     }
     HIP_TRY(c, slot_wait(f, f->seq.load(std::memory_order_relaxed)));
     for (SeamIo *io : outs) memcpy(io->host, io->dev, io->bytes);
@@ -1513,13 +1456,13 @@ int mmp_create(const mmp_config *cfg, mmp_ctx **out)
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // hi is the numerically lowest = highest priority
         hipError_t e1 = hipStreamCreateWithPriority(&f.stream, hipStreamNonBlocking, hi);
-        hipError_t e2 = hipHostMalloc(reinterpret_cast<void **>(&f.reqs), kFastN * sizeof(mmp_place_req), kPinnedFlags);
-        hipError_t e3 = hipHostMalloc(reinterpret_cast<void **>(&f.extra), kFastExtra * sizeof(int32_t), kPinnedFlags);
-        hipError_t e4 = hipHostMalloc(reinterpret_cast<void **>(&f.outs), kFastN * sizeof(mmp_place_out), kPinnedFlags);
-        if (e4 == hipSuccess) e4 = hipHostMalloc(reinterpret_cast<void **>(&f.done), 64, kPinnedFlags);
-        if (e4 == hipSuccess) *f.done = 0;
-        if (e4 == hipSuccess) e4 = hipMalloc(reinterpret_cast<void **>(&f.blocks), 64);
-        if (e4 == hipSuccess) e4 = hipMemsetAsync(f.blocks, 0, 64, c->stream);
+        hipError_t e2 = f.reqs.alloc(kFastN, kPinnedFlags);
+        hipError_t e3 = f.extra.alloc(kFastExtra, kPinnedFlags);
+        hipError_t e4 = f.outs.alloc(kFastN, kPinnedFlags);
+        if (e4 == hipSuccess) e4 = f.done.alloc(16, kPinnedFlags);
+        if (e4 == hipSuccess) *f.done.p = 0;
+        if (e4 == hipSuccess) e4 = f.blocks.alloc(64);
+        if (e4 == hipSuccess) e4 = hipMemsetAsync(f.blocks.p, 0, 64, c->stream);
         if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
             mmp_destroy(c);
             return fail(nullptr, MMP_EHIP, "fast-slot allocation failed");
@@ -1551,58 +1494,24 @@ void mmp_destroy(mmp_ctx *c)
     (void)hipSetDevice(c->cfg.device);
     resident_stop(c);
     if (c->res.stream) (void)hipStreamDestroy(c->res.stream);
-    if (c->res.slots) (void)hipHostFree(c->res.slots);
-    if (c->res.ctl) (void)hipHostFree(c->res.ctl);
-    if (c->res.answers) (void)hipHostFree(c->res.answers);
-    c->res.slots = nullptr;
     for (FastSlot &f : c->fast) {
         if (f.stream) {
             (void)hipStreamSynchronize(f.stream);
             (void)hipStreamDestroy(f.stream);
         }
-        if (f.reqs) (void)hipHostFree(f.reqs);
-        if (f.done) (void)hipHostFree(f.done);
-        if (f.blocks) (void)hipFree(f.blocks);
-        if (f.extra) (void)hipHostFree(f.extra);
-        if (f.outs) (void)hipHostFree(f.outs);
     }
 
     if (c->stream) (void)hipStreamSynchronize(c->stream);  // (an asynchronous pod-axis batch may still be writing its count)
-    if (c->f_done) (void)hipHostFree(c->f_done);
     if (c->comm) {
         group_comm_destroy(c->comm);
         c->comm = nullptr;
     }
-    for (DevBuf *b : {&c->g_rankbuf, &c->g_xf[0], &c->g_xf[1], &c->g_x[0], &c->g_x[1], &c->g_x[2], &c->g_x[3], &c->g_x[4], &c->g_x[5]}) b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->reg_event) (void)hipEventDestroy(c->reg_event);
     if (c->pe0) (void)hipEventDestroy(c->pe0);
     if (c->pe1) (void)hipEventDestroy(c->pe1);
-    c->sb[0].release();
-    c->sb[1].release();
-    c->side[0].release();
-    c->side[1].release();
-    // (caller-owned streams a split batch ran on are the caller's to drain before it destroys the context, as for every *_dev call)
-    for (auto &mb : c->miss_bufs)
-        if (mb.words) (void)hipFree(mb.words);
-    for (void *p : c->miss_retired) (void)hipFree(p);
-    if (c->miss_reports) (void)hipHostFree(c->miss_reports);
-    for (DevBuf *b : {&c->rank, &c->occupancy, &c->flag, &c->rs_list, &c->rs_bad, &c->d_prefer,
-                      &c->models, &c->ent_pod, &c->ent_time, &c->c_seg,
-                      &c->c_lu, &c->c_wt, &c->c_cap, &c->s_reqs, &c->s_outs, &c->s_extra, &c->s_a, &c->s_b,
-                      &c->s_c, &c->s_d, &c->r_ps, &c->r_counts, &c->r_keys, &c->r_vals, &c->r_keys2, &c->r_vals2,
-                      &c->r_tmp, &c->r_part, &c->rs_split, &c->rs_int, &c->r_out_model, &c->r_out_lu, &c->rt_sreqs, &c->rt_souts, &c->rt_cnt, &c->k_ids, &c->k_cap, &c->k_wsize, &c->k_oldest, &c->k_ubm, &c->k_ops, &c->k_order,
-                      &c->k_opoff, &c->k_outs, &c->k_ev, &c->k_evoff, &c->k_inv, &c->k_kstat, &c->k_krow, &c->k_len, &c->k_goff, &c->k_gbytes, &c->k_wide, &c->idtab_hash, &c->idtab_val, &c->tytab_hash,
-                      &c->tytab_val, &c->j_buf, &c->j_off, &c->j_rows, &c->j_aux, &c->j_status, &c->j_cnt, &c->j_offs, &c->j_tmp_pod, &c->idd_bytes, &c->idd_off, &c->rw_rows, &c->rw_lul, &c->rw_fpod, &c->rw_fmsg, &c->rw_fmoff, &c->rw_len,
-                      &c->rw_off, &c->rw_status, &c->rw_out, &c->rg_reqs, &c->rg_info, &c->rg_ioff, &c->rg_cls, &c->rg_lu, &c->rf_refs, &c->vw_reqs, &c->vw_strs, &c->vw_soff, &c->vw_rows,
-                      &c->vid_hash, &c->vid_val, &c->vid_next_hash, &c->vid_next_val, &c->vid_bytes, &c->vid_off, &c->vm_rows, &c->vm_rows_next, &c->vm_arena,
-                      &c->vq_nf, &c->vq_nf_off, &c->vq_flags, &c->vq_out,
-                      &c->vm_ev, &c->vm_cnt, &c->vm_pos, &c->vm_nf_bytes, &c->vm_nf_off, &c->vm_ow_bytes, &c->vm_ow_off, &c->vm_rflags,
-                      &c->vm_ans, &c->vm_list,
-                      &c->j_tmp_time, &c->j_scan_tmp, &c->j_ev, &c->rk_rows, &c->rk_idx, &c->rk_tmp, &c->u_idx, &c->u_rows, &c->u_cnt, &c->u_offs, &c->u_tmp, &c->miss_since, &c->p_state, &c->p_seen, &c->plan.totals, &c->plan.block_counts, &c->plan.edits, &c->p_removed, &c->plan.keep_off, &c->plan.model_map, &c->plan.rows_in, &c->plan.call_scalars, &c->plan.row_tmp, &c->cn_out, &c->st_copies, &c->sk_fpod, &c->sk_flags, &c->sk_sc, &c->sk_str, &c->idtab_next_hash, &c->idtab_next_val, &c->ida_bytes, &c->ida_off, &c->ida_hash, &c->ida_found, &c->unres_list, &c->kq_keys, &c->kq_off, &c->kq_idx, &c->kq_preqs, &c->kq_pouts, &c->mid_hash, &c->mid_val, &c->mid_next_hash, &c->mid_next_val, &c->mid_bytes, &c->mid_off, &c->me_hash, &c->me_row, &c->me_slot, &c->me_tab, &c->me_cnt, &c->me_pos, &c->me_idx, &c->me_join, &c->me_found, &c->ret_rows, &c->ret_keep, &c->ret_remap, &c->ret_word, &c->f_flags[0], &c->f_flags[1], &c->f_offs, &c->f_idx, &c->f_reqs, &c->f_outs, &c->f_scan_tmp, &c->f_cnt[0], &c->f_cnt[1],
-                      &c->ks[0].off, &c->ks[0].lu, &c->ks[0].wt,
-                      &c->ks[0].key, &c->ks[0].n, &c->ks[1].off, &c->ks[1].lu, &c->ks[1].wt, &c->ks[1].key, &c->ks[1].n})
-        b->release();
+    // every buffer frees itself in there, on this thread, which set the device (caller-owned streams a split batch ran on are the
+    // caller's to drain before it destroys the context, as for every *_dev call)
     delete c;
 }
 
@@ -4734,7 +4643,7 @@ try {
         if (ids) retire_id_table_publish(T, next, nb, no, M1, B1);
         // (the drain above ran inside this exclusive hold, so no decision and no request call by model id holds what the swap
         // retired: it goes here, before rebuild_resolved allocates)
-        for (ScopedDevBuf *b : {&nm, &np, &nt, &nb, &no}) b->release();
+        for (ScopedDevBuf *retired : {&nm, &np, &nt, &nb, &no}) retired->release();
         c->side[0].rmodels_ok = c->side[1].rmodels_ok = false;
         split_reset(c);
         if (carry) {  // the keys of the bound caches follow their rows, in place (d_remap: the M0 words retire_move_kernel wrote)
@@ -5251,9 +5160,9 @@ int shard_finish_prepare(mmp_ctx *c, uint32_t slot, int32_t n, hipStream_t st, u
         HIP_TRY(c, c->f_cnt[slot].ensure(16));
         HIP_TRY(c, hipMemsetAsync(c->f_cnt[slot].p, 0, 16, st));
     }
-    if (!c->f_done) {
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->f_done), 128, kPinnedFlags));
-        c->f_done[0] = c->f_done[8] = 0;
+    if (!c->f_done.p) {
+        HIP_TRY(c, c->f_done.alloc(16, kPinnedFlags));
+        c->f_done.p[0] = c->f_done.p[8] = 0;
     }
     *seq_out = ++c->f_seq;
     return MMP_OK;
@@ -5265,7 +5174,7 @@ int shard_finish_enqueue(mmp_ctx *c, uint32_t slot, int32_t n, const void *d_xf,
     if (prc != MMP_OK) return prc;
     hipLaunchKernelGGL(place_shard_fast_finish_kernel, dim3(div_up(n + 1, 256)), dim3(256), 0, st, static_cast<const int64_t *>(d_xf),
                        n, c->ssnap.any_rs, static_cast<mmp_place_out *>(d_outs), c->f_flags[slot].as<int32_t>(),
-                       c->f_cnt[slot].as<unsigned long long>(), c->f_done + 8 * slot, seq);
+                       c->f_cnt[slot].as<unsigned long long>(), c->f_done.p + 8 * slot, seq);
     HIP_TRY(c, hipGetLastError());
     *seq_out = seq;
     return MMP_OK;
@@ -5275,7 +5184,7 @@ int shard_finish_enqueue(mmp_ctx *c, uint32_t slot, int32_t n, const void *d_xf,
 // Everything the host does with the count afterwards is enqueued on the same stream, i.e. ordered behind the kernel.
 int shard_finish_collect(mmp_ctx *c, uint32_t slot, hipStream_t st, uint32_t seq, int32_t *n_rest_out)
 {
-    const uint64_t *w = c->f_done + 8 * slot;
+    const uint64_t *w = c->f_done.p + 8 * slot;
     uint64_t word = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 0;; spins++) {
@@ -5641,7 +5550,7 @@ int shard_place_batch_locked(mmp_ctx *c, const void *d_reqs, int32_t n, const vo
         const PlaceArgs A = shard_args(c, d_reqs, n, d_extra, now, d_outs);
         hipLaunchKernelGGL(place_shard_fast_direct_kernel, dim3(div_up(n + 1, kPlaceBlock)), dim3(kPlaceBlock), (size_t)place_lane_lds(c->sview.T),
                            st, c->sview, A, c->shard, c->ssnap.any_rs, c->f_flags[slot].as<int32_t>(), c->f_cnt[slot].as<unsigned long long>(),
-                           c->f_done + 8 * slot, seq);
+                           c->f_done.p + 8 * slot, seq);
         HIP_TRY(c, hipGetLastError());
     } else {
         HIP_TRY(c, c->g_xf[slot].ensure((size_t)n * kXF * 8));
@@ -5870,7 +5779,7 @@ int resident_ensure(mmp_ctx *c)
     if (!c->committed) return fail(c, MMP_ESTATE, "no committed snapshot");
     if (c->n_shards > 0) return kResidentFallback;
     std::lock_guard<std::mutex> g(R.launch_mu);
-    if (R.running && __atomic_load_n(&R.ctl->exited, __ATOMIC_ACQUIRE) != R.generation) return MMP_OK;
+    if (R.running && __atomic_load_n(&R.ctl.p->exited, __ATOMIC_ACQUIRE) != R.generation) return MMP_OK;
     if (R.running) {
         HIP_TRY(c, hipStreamSynchronize(R.stream));  // it left by itself (idle): returns at once
         R.running = false;
@@ -5883,7 +5792,7 @@ int resident_ensure(mmp_ctx *c)
     PlaceArgs A = place_args(c, nullptr, 1, nullptr, 0, nullptr, true, c->snap.P);
     A.wins = c->sb[c->cur].heads.as<TypeWin>();
     HIP_TRY(c, order_after_registry(c, R.stream));
-    hipLaunchKernelGGL(place_resident_kernel, dim3(1), dim3(64), (size_t)kPlaceLaneLds, R.stream, c->snap, A, R.slots, R.answers, R.ctl,
+    hipLaunchKernelGGL(place_resident_kernel, dim3(1), dim3(64), (size_t)kPlaceLaneLds, R.stream, c->snap, A, R.slots.p, R.answers.p, R.ctl.p,
                        R.idle_ticks, R.generation.load(std::memory_order_relaxed));
     HIP_TRY(c, hipGetLastError());
     R.running = true;
@@ -5914,8 +5823,8 @@ int resident_place(mmp_ctx *c, const mmp_place_req &rq, int64_t now, mmp_place_o
         si = (int)(first % kResidentSlots);
         sl = std::unique_lock<std::mutex>(R.slot_mu[si]);
     }
-    ResidentSlot *S = &R.slots[si];
-    ResidentAnswer *Ans = &R.answers[si];
+    ResidentSlot *S = &R.slots.p[si];
+    ResidentAnswer *Ans = &R.answers.p[si];
     uint32_t seq = (R.seq[si] + 1) & 0xfffffu;  // 20 bits ride in the bell next to now_ms
     if (seq == 0) seq = 1;
     R.seq[si] = seq;
@@ -5923,7 +5832,7 @@ int resident_place(mmp_ctx *c, const mmp_place_req &rq, int64_t now, mmp_place_o
     __atomic_store_n(&S->bell, ((uint64_t)seq << kResidentNowBits) | ((uint64_t)now & ((1ull << kResidentNowBits) - 1ull)),
                      __ATOMIC_RELEASE);  // the bell: written last
     bool restarted = false;  // this call (re)started the kernel, or waited for a commit to do so: not a sample for the self-check
-    if (!R.running || __atomic_load_n(&R.ctl->exited, __ATOMIC_ACQUIRE) == R.generation) {
+    if (!R.running || __atomic_load_n(&R.ctl.p->exited, __ATOMIC_ACQUIRE) == R.generation) {
         const int rc = resident_ensure(c);
         if (rc != MMP_OK) return rc;
         restarted = true;
@@ -5959,7 +5868,7 @@ int resident_place(mmp_ctx *c, const mmp_place_req &rq, int64_t now, mmp_place_o
             return MMP_OK;
         }
         if ((spins & 255) == 255) {
-            if (__atomic_load_n(&R.ctl->exited, __ATOMIC_ACQUIRE) == R.generation) {  // it left (idle, or stopped for a commit) before it saw the bell
+            if (__atomic_load_n(&R.ctl.p->exited, __ATOMIC_ACQUIRE) == R.generation) {  // it left (idle, or stopped for a commit) before it saw the bell
                 const int rc = resident_ensure(c);
                 if (rc != MMP_OK) return rc;
                 restarted = true;
@@ -5978,7 +5887,7 @@ try {
     std::lock_guard<std::mutex> gb(c->batch_mu);
     auto &R = c->res;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (enable && !R.slots) {
+    if (enable && !R.slots.p) {
         // A stream of the LOWEST priority: HIP multiplexes the streams of one priority level onto a small pool of hardware
         // queues, and a kernel that never ends blocks whatever else lands on its queue.  On the latency slots' level (highest)
         // it held their launches back until it idled out — 50 ms per request that it had handed back to the launch path
@@ -5986,12 +5895,12 @@ try {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         HIP_TRY(c, hipStreamCreateWithPriority(&R.stream, hipStreamNonBlocking, lo));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&R.slots), sizeof(ResidentSlot) * kResidentSlots, kPinnedFlags));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&R.ctl), sizeof(ResidentCtl), kPinnedFlags));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&R.answers), sizeof(ResidentAnswer) * kResidentSlots, kPinnedFlags));
-        memset(R.answers, 0, sizeof(ResidentAnswer) * kResidentSlots);
-        memset(R.slots, 0, sizeof(ResidentSlot) * kResidentSlots);
-        memset(R.ctl, 0, sizeof(ResidentCtl));
+        HIP_TRY(c, R.slots.alloc(kResidentSlots, kPinnedFlags));
+        HIP_TRY(c, R.ctl.alloc(1, kPinnedFlags));
+        HIP_TRY(c, R.answers.alloc(kResidentSlots, kPinnedFlags));
+        memset(R.answers.p, 0, sizeof(ResidentAnswer) * kResidentSlots);
+        memset(R.slots.p, 0, sizeof(ResidentSlot) * kResidentSlots);
+        memset(R.ctl.p, 0, sizeof(ResidentCtl));
         int khz = 100000;
         (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device);
         long long ms = 50;
@@ -6124,18 +6033,16 @@ try {
     }
     if (mb) {
         std::lock_guard<std::mutex> gs(mb->mu);
-        void *words = nullptr;
+        DevBuf words;
         {
             std::lock_guard<std::mutex> g(c->miss_mu);
             if (mb->used && mb->st == st) {
-                words = mb->words;
-                mb->words = nullptr;
-                mb->cap = 0;
+                words = std::move(mb->words);
                 mb->used = false;
                 mb->st = nullptr;
             }
         }
-        if (words) HIP_TRY(c, hipFree(words));
+        HIP_TRY(c, words.release_checked());
     }
     return MMP_OK;
 } MMP_CATCH(c, "mmp_stream_retire")
