@@ -608,6 +608,20 @@ int mmp_caches_load(mmp_ctx *ctx, int32_t n_caches, const int32_t *seg_off, cons
                     const int32_t *weight, const int64_t *capacity);
 int mmp_evict_batch(mmp_ctx *ctx, const mmp_evict_req *reqs, int32_t n, int64_t now_ms,
                     mmp_evict_out *outs);
+/* How mmp_evict_batch decides on long deques (evict_tree_kernels.hpp).  A mmp_caches_load that brings a cache of more than
+ * `search_from` entries (MMP_EVICT_SEARCH_FROM, 0: every cache) also builds prefix-weight tables of the loaded store; a request on
+ * such a cache is then decided by search — when the cache is SEARCHABLE (lastUsed non-decreasing along the deque, no negative
+ * weight) and the request's weight is >= 0 — and by the walk otherwise, with the same answers.  mmp_caches_load is the only call
+ * that writes the store mmp_evict_batch reads: the stateful caches of mmp_caches_load_keyed / mmp_cache_replay are another store.
+ * The call launches nothing; it waits for evaluations in flight when the last one searched. */
+typedef struct {
+    int32_t search_from;   /* the threshold in force                                                     */
+    int32_t n_above;       /* caches of the last mmp_caches_load with more entries than that             */
+    int32_t n_searchable;  /* ... of which searchable                                                    */
+    int32_t rows_searched; /* rows of the last mmp_evict_batch that were decided by search               */
+    int64_t generation;    /* table builds so far (0: none; a load of short caches only builds nothing)  */
+} mmp_evict_search_stats; /* 24 bytes */
+int mmp_evict_search_info(mmp_ctx *ctx, mmp_evict_search_stats *out);
 
 /* Stateful caches: entry i of cache c's segment is the i-th node of its evictionDeque (oldest first)
  * with its key; ubm may be NULL (no cache is managed). */

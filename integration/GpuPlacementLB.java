@@ -73,6 +73,8 @@ final class MmPlace {
     static native int cachesLoad(long h, int nCaches, ByteBuffer segOff, ByteBuffer lastUsed, ByteBuffer weight,
                                  ByteBuffer capacity);
     static native int evictBatch(long h, ByteBuffer reqs, int n, long nowMs, ByteBuffer outs);
+    /** how evictBatch decides on long deques (mmp_evict_search_info): out = one mmp_evict_search_stats, 24 bytes */
+    static native int evictSearchInfo(long h, ByteBuffer out);
     static native int cachesLoadKeyed(long h, int nCaches, ByteBuffer segOff, ByteBuffer lastUsed, ByteBuffer weight,
                                       ByteBuffer key, ByteBuffer capacity, ByteBuffer ubm);
     static native int cacheReplay(long h, ByteBuffer ops, int nOps, long nowMs, ByteBuffer outs, ByteBuffer evictedKeys,

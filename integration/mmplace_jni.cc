@@ -234,6 +234,12 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_evictBatch(JNIEnv *
     return check(env, ctx_of(h),
                  mmp_evict_batch(ctx_of(h), buf<mmp_evict_req>(env, reqs), n, nowMs, buf<mmp_evict_out>(env, outs)));
 }
+// out: one mmp_evict_search_stats (24 bytes)
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_evictSearchInfo(JNIEnv *env, jclass, jlong h, jobject out)
+{
+    if (!holds<mmp_evict_search_stats>(env, out, 1, "evictSearchInfo: out shorter than one mmp_evict_search_stats")) return MMP_EINVAL;
+    return check(env, ctx_of(h), mmp_evict_search_info(ctx_of(h), buf<mmp_evict_search_stats>(env, out)));
+}
 
 // ---- stateful caches + ModelCacheUnloadBufManager (ModelCacheUnloadBufManager.java:130-402) --------
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cachesLoadKeyed(JNIEnv *env, jclass, jlong h,

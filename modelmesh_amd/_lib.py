@@ -79,6 +79,9 @@ EVICT_REQ = np.dtype([("cache", "<i4"), ("weight", "<i4"), ("last_used", "<i8")]
 EVICT_OUT = np.dtype(
     [("insert_pos", "<i4"), ("n_victims", "<i4"), ("self_evicted", "<i4"), ("pad", "<i4"),
      ("weighted_size", "<i8"), ("oldest_time", "<i8")])
+EVICT_SEARCH_STATS = np.dtype([("search_from", "<i4"), ("n_above", "<i4"), ("n_searchable", "<i4"), ("rows_searched", "<i4"),
+                               ("generation", "<i8")])
+assert EVICT_SEARCH_STATS.itemsize == 24
 
 GATE_REQ = np.dtype(
     [("model", "<i4"), ("self_pod", "<i4"), ("flags", "<u4"), ("excl_off", "<i4"), ("n_excl", "<i4"),
@@ -362,6 +365,7 @@ SYMBOLS = [
     ("mmp_serve_batch", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P]),
     ("mmp_caches_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("mmp_evict_batch", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
+    ("mmp_evict_search_info", C.c_int, [_P, _P]),
     ("mmp_caches_load_keyed", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("mmp_cache_replay", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("mmp_cache_read", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64),

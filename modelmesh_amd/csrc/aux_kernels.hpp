@@ -179,31 +179,16 @@ __device__ __forceinline__ int64_t team_sum_i64(int64_t v)
     return v;
 }
 
+// The walk of one evaluation by its TEAM lanes, for every team of the wavefront at once (the whole wavefront calls it: the teams
+// loop together and the ballots are the wavefront's).  A team with nothing to decide passes valid = false and E = 0.
 template <int TEAM>
-__global__ __launch_bounds__(kEvBlock) void evict_batch_kernel(EvictArgs A)
+__device__ __forceinline__ void evict_team_walk(const int64_t *lu, const int32_t *wt, int E, int32_t weight, int64_t ts, bool valid,
+                                                int64_t cap, int &pos_out, int &n_victims_out, int64_t &after_out)
 {
     constexpr int kEvTeam = TEAM;
     constexpr uint32_t kTeamMask = (1u << TEAM) - 1u;
     const int lane = lane_id();
     const int team = lane / kEvTeam, tl = lane & (kEvTeam - 1), tbase = team * kEvTeam;
-    const int i = (blockIdx.x * blockDim.x + threadIdx.x) / kEvTeam;
-    const bool in_range = i < A.n;
-    mmp_evict_req r;
-    r.cache = -1;
-    r.weight = 0;
-    r.last_used = 0;
-    if (in_range) r = A.reqs[i];
-    const bool valid = in_range && r.cache >= 0 && r.cache < A.n_caches;
-    int s0 = 0, E = 0;
-    int64_t cap = 0;
-    if (valid) {
-        s0 = A.seg_off[r.cache];
-        E = A.seg_off[r.cache + 1] - s0;
-        cap = A.capacity[r.cache];
-    }
-    const int64_t *lu = A.last_used + s0;
-    const int32_t *wt = A.weight + s0;
-    const int64_t ts = r.last_used == 0 ? A.now : r.last_used;  // Node ctor / touch, clhm :1357-1360
     int emax = E;  // the four teams loop together
 #pragma unroll
     for (int o = 32; o >= kEvTeam; o >>= 1) {
@@ -212,7 +197,9 @@ __global__ __launch_bounds__(kEvBlock) void evict_batch_kernel(EvictArgs A)
     }
 
     // insert(): walk from the tail to the first node with lastUsed <= ts, link after it
-    int pos = 0;
+    // (the results are worked on in place: with copies out at the end evict_batch_kernel<16> compiled to 42 VGPRs instead of its 40)
+    int &pos = pos_out;
+    pos = 0;
     int64_t sum = 0;
     for (int base = 0; base < emax; base += kEvTeam) {
         const int j = base + tl;
@@ -222,19 +209,21 @@ __global__ __launch_bounds__(kEvBlock) void evict_batch_kernel(EvictArgs A)
         sum += j < E ? (int64_t)wt[j] : 0;
     }
     sum = team_sum_i64<TEAM>(sum);
-    const int64_t total = sum + (int64_t)r.weight;  // weightedSize + weight, clhm :603
+    const int64_t total = sum + (int64_t)weight;  // weightedSize + weight, clhm :603
 
     // evict(): poll the head while weightedSize > capacity
     const bool need = valid && total > cap;
-    int n_victims = need ? E + 1 : 0;
-    int64_t after = need ? 0 : total;
+    int &n_victims = n_victims_out;
+    int64_t &after = after_out;
+    n_victims = need ? E + 1 : 0;
+    after = need ? 0 : total;
     int64_t carry = 0;
     bool done = !need;
     for (int base = 0; base <= emax; base += kEvTeam) {
         if (__ballot(!done) == 0) break;
         const int j = base + tl;
         int64_t w = 0;
-        if (need && j <= E) w = j < pos ? (int64_t)wt[j] : (j == pos ? (int64_t)r.weight : (int64_t)wt[j - 1]);
+        if (need && j <= E) w = j < pos ? (int64_t)wt[j] : (j == pos ? (int64_t)weight : (int64_t)wt[j - 1]);
         int64_t incl = w;  // inclusive scan of the team's 64-bit weights
 #pragma unroll
         for (int o2 = 1; o2 < kEvTeam; o2 <<= 1) {
@@ -253,20 +242,51 @@ __global__ __launch_bounds__(kEvBlock) void evict_batch_kernel(EvictArgs A)
         }
         carry += last_incl;
     }
-    if (in_range && tl == 0) {
-        mmp_evict_out o;
-        o.insert_pos = 0; o.n_victims = 0; o.self_evicted = 0; o.pad = 0; o.weighted_size = 0; o.oldest_time = -1;
-        if (valid) {
-            o.insert_pos = pos;
-            o.n_victims = n_victims;
-            o.self_evicted = n_victims > pos ? 1 : 0;
-            o.weighted_size = after;
-            // oldestTime(): head of what is left, clhm :1125-1133
-            const int h = n_victims;  // merged index of the new head
-            if (h <= E) o.oldest_time = h < pos ? lu[h] : (h == pos ? ts : lu[h - 1]);
-        }
-        A.outs[i] = o;
+}
+
+// the result row of one evaluation (the zero row for a request that names no cache)
+__device__ __forceinline__ mmp_evict_out evict_out_row(bool valid, const int64_t *lu, int E, int64_t ts, int pos, int n_victims, int64_t after)
+{
+    mmp_evict_out o;
+    o.insert_pos = 0; o.n_victims = 0; o.self_evicted = 0; o.pad = 0; o.weighted_size = 0; o.oldest_time = -1;
+    if (valid) {
+        o.insert_pos = pos;
+        o.n_victims = n_victims;
+        o.self_evicted = n_victims > pos ? 1 : 0;
+        o.weighted_size = after;
+        // oldestTime(): head of what is left, clhm :1125-1133
+        const int h = n_victims;  // merged index of the new head
+        if (h <= E) o.oldest_time = h < pos ? lu[h] : (h == pos ? ts : lu[h - 1]);
     }
+    return o;
+}
+
+template <int TEAM>
+__global__ __launch_bounds__(kEvBlock) void evict_batch_kernel(EvictArgs A)
+{
+    const int tl = lane_id() & (TEAM - 1);
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) / TEAM;
+    const bool in_range = i < A.n;
+    mmp_evict_req r;
+    r.cache = -1;
+    r.weight = 0;
+    r.last_used = 0;
+    if (in_range) r = A.reqs[i];
+    const bool valid = in_range && r.cache >= 0 && r.cache < A.n_caches;
+    int s0 = 0, E = 0;
+    int64_t cap = 0;
+    if (valid) {
+        s0 = A.seg_off[r.cache];
+        E = A.seg_off[r.cache + 1] - s0;
+        cap = A.capacity[r.cache];
+    }
+    const int64_t *lu = A.last_used + s0;
+    const int32_t *wt = A.weight + s0;
+    const int64_t ts = r.last_used == 0 ? A.now : r.last_used;  // Node ctor / touch, clhm :1357-1360
+    int pos, n_victims;
+    int64_t after;
+    evict_team_walk<TEAM>(lu, wt, E, r.weight, ts, valid, cap, pos, n_victims, after);
+    if (in_range && tl == 0) A.outs[i] = evict_out_row(valid, lu, E, ts, pos, n_victims, after);
     announce_done(A.done);
 }
 

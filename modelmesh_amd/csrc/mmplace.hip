@@ -34,6 +34,7 @@
 #include "../../include/mmplace.h"
 #include "devbuf.hpp"  // behind hip_runtime.h: it names the HIP calls and declares none
 #include "aux_kernels.hpp"
+#include "evict_tree_kernels.hpp"
 #include "cache_kernels.hpp"
 #include "gate_kernel.hpp"
 #include "seam_caller_kernels.hpp"
@@ -140,7 +141,11 @@ struct SnapSide {
 constexpr unsigned int kPinnedFlags = hipHostMallocCoherent | hipHostMallocMapped;
 constexpr size_t kSelMaxBytes = (size_t)32 << 20;  // Snap::sel / ::rk are built up to this size each (per snapshot side)
 constexpr int kTailStaticLds = 512;  // what place_tail_body keeps in static LDS beside place_block's own
-constexpr int kTailBlocks = 64;    // one-wavefront workgroups of a split batch's tail launch (measured: profiles/tail_slot)
+// Entries from which a loaded cache is evaluated by search (MMP_EVICT_SEARCH_FROM).  The smallest measured size at which the search
+// is not slower at n = 256 (profiles/evict_search, call wall on a latency slot): 1 024 entries, 17.2-17.6 us against the walk's
+// 33.5-33.7; at 20 entries the search is 17.5-17.8 us against 17.2-17.4.  Sizes between 20 and 1 024 were not measured.
+constexpr int kEvictSearchFrom = 1024;
+constexpr int kTailBlocks = 64;   // one-wavefront workgroups of a split batch's tail launch (measured: profiles/tail_slot)
 constexpr int kMaxMissBufs = 64;   // streams with split batches in flight that get a buffer of their own (more: those batches go unsplit)
 constexpr int kFastSlots = 4;
 constexpr int kFastN = 4096;       // decisions per fast call
@@ -315,6 +320,10 @@ struct Tuning {
     int32_t model_id_hash_bits = 64;  // MMP_MODEL_ID_HASH_BITS=b: every model-id hash is masked to its low b bits, 0: all equal (tests: ids that collide)
     int32_t vmodel_id_hash_bits = 64;  // MMP_VMODEL_ID_HASH_BITS=b: the same for the vmodel-id hashes
     int32_t cache_wide_from = kCacheTile;  // MMP_CACHE_WIDE_FROM=n: a replayed cache with slots + 1 > n takes the blocked deque in global memory (0: every one; tests)
+    // MMP_EVICT_SEARCH_FROM=n: a loaded cache of more than n entries gets mmp_evict_batch's search over prefix weights, and a context
+    // with such a cache the tables for it (evict_tree_kernels.hpp; 0: every cache; tests).  The default is the measured crossover:
+    // see kEvictSearchFrom.
+    int32_t evict_search_from = kEvictSearchFrom;
 };
 
 struct mmp_ctx {
@@ -490,6 +499,20 @@ struct mmp_ctx {
     DevBuf c_seg, c_lu, c_wt, c_cap;
     int32_t n_caches = 0;
     int64_t cache_entries = 0;  // entries of all deques loaded by mmp_caches_load (picks the eviction kernel's team size)
+    // The prefix-weight tables of that store (evict_tree_kernels.hpp), carved out of ev_tab: P | chunk totals | ok | chunk_off |
+    // chunk ok.  Built by mmp_caches_load — the one writer of c_lu / c_wt — when some cache has more than tune.evict_search_from
+    // entries; ev_on says they stand for the store as it is (evict_launch then takes evict_search_kernel).  ev_above / ev_ok /
+    // ev_gen: what the last load found (caches above the threshold, the searchable among them) and the builds so far.
+    // ev_ring: kSearchRing slots of rows_searched.  A call counts in slot seq % 16 and clears slot (seq + 8) % 16; calls in flight
+    // are the latency slots' and one staged batch, five at most, so no call's slot is cleared under it.  ev_last: the seq of the
+    // last mmp_evict_batch launch that searched, -1 if the last launch took the walk (mmp_evict_search_info reads the word then).
+    DevBuf ev_tab, ev_ring;
+    EvictTables ev_t{};
+    bool ev_on = false;
+    int32_t ev_above = 0, ev_ok = 0;
+    int64_t ev_gen = 0;
+    std::atomic<uint32_t> ev_seq{0};
+    std::atomic<int64_t> ev_last{-1};
 
     // stateful keyed caches (mmp_caches_load_keyed / mmp_cache_replay): two layouts, ping-pong
     struct KeyedStore {
@@ -925,6 +948,8 @@ Tuning read_tuning()
     t.label_hash_bits = std::max(0, std::min(t.label_hash_bits, 64));
     num("MMP_CACHE_WIDE_FROM", t.cache_wide_from);
     t.cache_wide_from = std::max(0, std::min(t.cache_wide_from, kCacheTile));  // (beyond the tile there is no other route)
+    num("MMP_EVICT_SEARCH_FROM", t.evict_search_from);
+    t.evict_search_from = std::max(0, t.evict_search_from);
     return t;
 }
 
@@ -1265,9 +1290,60 @@ EvictArgs evict_args(mmp_ctx *c, int32_t n, int64_t now)
     A.done = DoneFlag{nullptr, nullptr, 0};
     return A;
 }
-// eight lanes per evaluation while the deques are short, sixteen otherwise (aux_kernels.hpp)
+// The prefix-weight tables of the store mmp_caches_load has just written (seg_off: the caller's, n_caches + 1 values), when a cache
+// is above the threshold; a context of short caches launches and allocates nothing.  Called under batch_mu and the state lock held
+// exclusive, behind quiesce_decisions; the tables are complete when it returns.
+int evict_tables_build(mmp_ctx *c, const int32_t *seg_off)
+{
+    const int32_t nc = c->n_caches, from = c->tune.evict_search_from;
+    c->ev_on = false;
+    c->ev_above = c->ev_ok = 0;
+    for (int32_t k = 0; k < nc; k++) c->ev_above += seg_off[k + 1] - seg_off[k] > from;
+    if (!c->ev_above) return MMP_OK;  // (a load of short caches pays this loop and nothing else)
+    std::vector<int32_t> chunk_off((size_t)nc + 1, 0);
+    for (int32_t k = 0; k < nc; k++) chunk_off[k + 1] = chunk_off[k] + std::max(1, div_up(seg_off[k + 1] - seg_off[k], kScanChunk));
+    const int32_t chunks = chunk_off[nc];
+    const auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_tot = up(((size_t)c->cache_entries + nc) * 8), o_ok = o_tot + up((size_t)chunks * 8), o_coff = o_ok + up((size_t)nc * 4),
+                 o_cok = o_coff + up(((size_t)nc + 1) * 4), bytes = o_cok + up((size_t)chunks * 4);
+    HIP_TRY(c, c->ev_tab.ensure(bytes));
+    if (!c->ev_ring.p) {
+        HIP_TRY(c, c->ev_ring.alloc(kSearchRing * kSearchSlotWords * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemsetAsync(c->ev_ring.p, 0, kSearchRing * kSearchSlotWords * sizeof(uint32_t), c->stream));
+    }
+    char *b = c->ev_tab.as<char>();
+    EvictTables T{reinterpret_cast<int64_t *>(b), reinterpret_cast<int32_t *>(b + o_ok), reinterpret_cast<int32_t *>(b + o_coff),
+                  reinterpret_cast<int64_t *>(b + o_tot), reinterpret_cast<int32_t *>(b + o_cok), c->ev_ring.as<uint32_t>()};
+    HIP_TRY(c, hipMemcpyAsync(b + o_coff, chunk_off.data(), ((size_t)nc + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    EvictArgs A = evict_args(c, 0, 0);  // (the store; the scan has no requests)
+    A.reqs = nullptr;
+    A.outs = nullptr;
+    KT_BEGIN(c, c->stream);
+    hipLaunchKernelGGL(evict_chunk_reduce_kernel, dim3(chunks), dim3(kScanBlock), 0, c->stream, A, T);
+    hipLaunchKernelGGL(evict_chunk_scan_kernel, dim3(chunks), dim3(kScanBlock), 0, c->stream, A, T);
+    KT_END(c, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> ok((size_t)nc);
+    HIP_TRY(c, copy_sync(c, ok.data(), T.ok, (size_t)nc * 4, hipMemcpyDeviceToHost));  // (chunk_off is ours until here)
+    kt_collect(c);
+    for (int32_t k = 0; k < nc; k++) c->ev_ok += ok[k] && seg_off[k + 1] - seg_off[k] > from;
+    c->ev_t = T;
+    c->ev_on = true;
+    c->ev_gen++;
+    return MMP_OK;
+}
+
+// eight lanes per evaluation while the deques are short, sixteen otherwise (aux_kernels.hpp); with the prefix-weight tables built —
+// some cache is above tune.evict_search_from — the kernel that searches them, sixteen lanes (evict_tree_kernels.hpp)
 void evict_launch(mmp_ctx *c, const EvictArgs &A, int32_t n, hipStream_t st)
 {
+    if (c->ev_on) {
+        const uint32_t seq = c->ev_seq.fetch_add(1, std::memory_order_relaxed);
+        c->ev_last.store((int64_t)seq, std::memory_order_relaxed);
+        hipLaunchKernelGGL(evict_search_kernel<16>, dim3(div_up(n, kEvBlock / 16)), dim3(kEvBlock), 0, st, A, c->ev_t, c->tune.evict_search_from, seq);
+        return;
+    }
+    c->ev_last.store(-1, std::memory_order_relaxed);
     if (c->cache_entries <= (int64_t)24 * std::max(c->n_caches, 1))
         hipLaunchKernelGGL(evict_batch_kernel<8>, dim3(div_up(n, kEvBlock / 8)), dim3(kEvBlock), 0, st, A);
     else
@@ -9385,7 +9461,28 @@ try {
     if (n_caches) HIP_TRY(c, copy_sync(c, c->c_cap.p, capacity, (size_t)n_caches * 8, hipMemcpyHostToDevice));
     c->n_caches = n_caches;
     c->cache_entries = E;
-    return MMP_OK;
+    return evict_tables_build(c, seg_off);
 } MMP_CATCH(c, "mmp_caches_load")
+
+int mmp_evict_search_info(mmp_ctx *c, mmp_evict_search_stats *out)
+try {
+    if (!c || !out) return fail(c, MMP_EINVAL, "mmp_evict_search_info: bad argument");
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    out->search_from = c->tune.evict_search_from;
+    out->n_above = c->ev_above;
+    out->n_searchable = c->ev_ok;
+    out->rows_searched = 0;
+    out->generation = c->ev_gen;
+    const int64_t last = c->ev_last.load(std::memory_order_relaxed);
+    if (last >= 0 && c->ev_ring.p) {
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        HIP_TRY(c, quiesce_decisions(c));
+        uint32_t w[kSearchSlotWords];
+        HIP_TRY(c, copy_sync(c, w, c->ev_ring.as<uint32_t>() + (uint32_t)last % kSearchRing * kSearchSlotWords, sizeof w, hipMemcpyDeviceToHost));
+        for (int k = 0; k < kSearchWays; k++) out->rows_searched += (int32_t)w[k * kSearchWayStride];
+    }
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_evict_search_info")
 
 }  // extern "C"

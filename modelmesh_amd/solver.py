@@ -942,6 +942,14 @@ class Solver:
         self._ck(self.lib.mmp_evict_batch(self.h, ptr(reqs), len(reqs), int(now), ptr(outs)))
         return outs
 
+    def evict_search_info(self) -> dict:
+        """How evict() decides on long deques (mmp_evict_search_info): the threshold in force, the caches of the last load_caches
+        above it and the searchable among them, the table builds so far, and the rows of the last evict() decided by search."""
+        from ._lib import EVICT_SEARCH_STATS
+        st = np.zeros(1, dtype=EVICT_SEARCH_STATS)
+        self._ck(self.lib.mmp_evict_search_info(self.h, ptr(st)))
+        return {f: int(st[0][f]) for f in EVICT_SEARCH_STATS.names}
+
     # ---- stateful keyed caches (rows a12 + a13) -------------------------------------------------
     def load_caches_keyed(self, seg_off, last_used, weight, key, capacity, ubm=None):
         from ._lib import UBM_STATE
