@@ -221,15 +221,16 @@ __global__ __launch_bounds__(kEvBlock) void evict_search_kernel(EvictArgs A, Evi
         const int64_t *P = T.P + s0 + (valid ? r.cache : 0);
         const int64_t w = (int64_t)r.weight;
         const int p = team_search<TEAM>(0, srch ? E : 0, tl, tbase, [&](int j) { return lu[j] > ts; });
-        int64_t total = 0, need = 0;
+        int64_t total = 0;
         bool over = false;
         if (srch) {
             total = P[E] + w;
             over = total > cap;
-            need = total - cap;  // the victims' weights must reach this
         }
         const auto M = [&](int j) { return j <= p ? P[j] : P[j - 1] + w; };  // merged prefix, j in 0 .. E+1
-        const int v = team_search<TEAM>(over ? 1 : 0, over ? E + 1 : 0, tl, tbase, [&](int j) { return M(j) >= need; });
+        // the walk's own compare, what is left against the capacity: 0 <= total - M(j) <= total on a searchable cache, where
+        // "M(j) >= total - cap" wraps for a capacity below total - 2^63 and stopped at one victim where the walk polls them all
+        const int v = team_search<TEAM>(over ? 1 : 0, over ? E + 1 : 0, tl, tbase, [&](int j) { return total - M(j) <= cap; });
         if (srch) {
             pos = p;
             n_victims = over ? v : 0;

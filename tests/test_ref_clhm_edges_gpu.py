@@ -158,16 +158,20 @@ def _evict_rows(v):
     return rows
 
 
-@pytest.mark.parametrize("name,team", [("clhm", 8), ("wide", 8), ("lengths_plain", 16), ("lengths_big", 16), ("mass_plain", 16)])
-def test_stateless_eviction_equals_the_reference_text_at_the_edges(vec, solver, name, team):
-    """Every such probe as one mmp_evict_batch evaluation on the recorded state before it (the first probe of a run: the state in
-    front of a later probe is not recorded).  evict_launch takes 8 lanes per evaluation while the loaded deques average <= 24
-    entries, 16 beyond: which one a case takes is asserted from the states loaded.  lengths_big: the two inserts on a deque of
-    2 046 entries, 128 trips of the 16-lane loops."""
-    v = rc.load_edge_case(vec, name)
-    pre, last = len(v["bounds"]) - 2, len(v["bounds"]) - 1
+EVICT_CASES = [("clhm", 8), ("wide", 8), ("lengths_plain", 16), ("lengths_big", 16), ("mass_plain", 16)]
+
+
+def _evict_states(v):
+    """_evict_rows and the recorded state in front of each: (rows, [(hdr, key, weight, last_used)])"""
     rows = _evict_rows(v)
-    states = [rc.edge_state(v, pre, c) for c, _ in rows]
+    return rows, [rc.edge_state(v, len(v["bounds"]) - 2, c) for c, _ in rows]
+
+
+def _check_evict_case(vec, solver, name, team):
+    """one case of EVICT_CASES through mmp_evict_batch on `solver`, every row against the reference's record; -> (rows, states)"""
+    v = rc.load_edge_case(vec, name)
+    last = len(v["bounds"]) - 1
+    rows, states = _evict_states(v)
     seg = np.concatenate([[0], np.cumsum([len(k) for _, k, _, _ in states])]).astype(np.int32)
     assert rows and (8 if seg[-1] <= 24 * len(rows) else 16) == team  # (evict_launch's rule, mmplace.hip)
     solver.load_caches(seg, np.concatenate([lu for _, _, _, lu in states]), np.concatenate([w for _, _, w, _ in states]),
@@ -198,3 +202,18 @@ def test_stateless_eviction_equals_the_reference_text_at_the_edges(vec, solver, 
         assert lengths == set(rc.LENGTHS) and len(rows) >= 4 * len(rc.LENGTHS)
     else:
         assert len(rows) == want[name] and (name != "lengths_big" or lengths == {2046})
+    return rows, states
+
+
+@pytest.mark.parametrize("name,team", EVICT_CASES)
+def test_stateless_eviction_equals_the_reference_text_at_the_edges(vec, solver, name, team):
+    """Every such probe as one mmp_evict_batch evaluation on the recorded state before it (the first probe of a run: the state in
+    front of a later probe is not recorded).  evict_launch takes 8 lanes per evaluation while the loaded deques average <= 24
+    entries, 16 beyond: which one a case takes is asserted from the states loaded.  lengths_big: the two inserts on a deque of
+    2 046 entries.  At the default threshold (1 024 entries) those two deques are above it and both rows are decided by the search
+    of evict_tree_kernels.hpp, three steps each, not by the 16-lane loops; every other case stays below it and walks.  The same
+    five cases with every deque searched: tests/test_evict_search_edges_gpu.py."""
+    _, states = _check_evict_case(vec, solver, name, team)
+    info = solver.evict_search_info()
+    assert info["search_from"] == 1024 and info["n_above"] == sum(len(k) > 1024 for _, k, _, _ in states)
+    assert (info["n_above"], info["rows_searched"]) == ((2, 2) if name == "lengths_big" else (0, 0))
