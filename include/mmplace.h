@@ -612,7 +612,8 @@ int mmp_evict_batch(mmp_ctx *ctx, const mmp_evict_req *reqs, int32_t n, int64_t 
  * `search_from` entries (MMP_EVICT_SEARCH_FROM, 0: every cache) also builds prefix-weight tables of the loaded store; a request on
  * such a cache is then decided by search — when the cache is SEARCHABLE (lastUsed non-decreasing along the deque, no negative
  * weight) and the request's weight is >= 0 — and by the walk otherwise, with the same answers.  mmp_caches_load is the only call
- * that writes the store mmp_evict_batch reads: the stateful caches of mmp_caches_load_keyed / mmp_cache_replay are another store.
+ * that writes the store mmp_evict_batch reads: the stateful caches of mmp_caches_load_keyed / mmp_cache_replay are another store,
+ * which mmp_evict_batch_k asks.
  * The call launches nothing; it waits for evaluations in flight when the last one searched. */
 typedef struct {
     int32_t search_from;   /* the threshold in force                                                     */
@@ -721,6 +722,44 @@ int mmp_cache_evicted_times(mmp_ctx *ctx, int64_t *out, int32_t max_slots, int32
 int mmp_cache_read_k(mmp_ctx *ctx, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *row_out,
                      char *id_bytes_out, int32_t max_id_bytes, int32_t *id_off_out, int32_t *n_out, int32_t *n_id_bytes_out,
                      int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm);
+/* "What would this load evict here?" on the resident caches, by model id (evict_resident_kernels.hpp).  outs[i] is what
+ * mmp_cache_replay_k would answer for a call of the single operation ops[i], with id i, on the resident caches as they stand.
+ * NOTHING IS APPLIED, and the n rows are independent of each other.  The accepted `op` values are MMP_COP_PUT_IF_ABSENT and
+ * MMP_COP_UBM_INSERT_NEW_ENTRY, the two inserts a cache miss issues; any other code is MMP_EINVAL for the whole call, as is
+ * everything mmp_cache_replay_k refuses about keys and offsets (keys without key_off or the reverse, non-monotone offsets, reserved
+ * outside {0, MMP_COPK_RAW_KEY}, MMP_COPK_RAW_KEY with another key).  The locks, the MMP_ESTATE conditions and the key format are
+ * those of the other _k cache calls.
+ * On a managed cache the buffer grows with every victim, as entryRemoved does (ModelCacheUnloadBufManager.java:306-310): the buffer
+ * entry's weight is clamped to the reserve from below and to the capacity from above, the loop runs on until weightedSize <=
+ * capacity, and the pinned entry is never a victim.  (Domain: that of the replay — weights >= 1 — and a weightedSize within the
+ * capacity before the call, which every state a replay leaves has.)
+ *   key_status, row   MMP_CKEY_* and the key the evaluation ran with
+ *   result            1: the entry would be inserted.  0: the key is present; nothing is evicted, insert_pos is the entry's
+ *                     position and the state fields are the current ones (oldest_time as the hit's touch would leave it).
+ *                     -1: not evaluated — an unknown id (an inserting op is not run, as in the replay; the state fields are the
+ *                     current ones) or a cache index out of range (every field 0, oldest_time -1)
+ *   n_evicted, self_evicted, insert_pos   as mmp_evict_out's n_victims, self_evicted, insert_pos
+ *   buffer_weight, weighted_size, oldest_time   as the three fields of mmp_cache_op_out would stand after the operation
+ * The victims are not listed: what either operation evicts is the head run of the deque, the new entry among it when self_evicted
+ * is set, and mmp_cache_read_k(cache, max_entries = n_evicted) already returns those rows and ids.  Listener order, which on a
+ * managed cache is the reversed pending run, is not reported.
+ * A cache of more than MMP_EVICT_SEARCH_FROM live entries is decided through tables of the resident store (prefix weights and a key
+ * index), built by the first evaluation that names the cache behind a change of the store — a keyed load, a replay,
+ * mmp_models_retire, mmp_model_ids_load — and reused until the next; a context that never calls this builds nothing. */
+typedef struct {
+    int32_t key_status;    /* MMP_CKEY_*                                                  */
+    int32_t row;           /* the key the evaluation ran with                             */
+    int32_t result;        /* 1 inserted, 0 present, -1 not evaluated                     */
+    int32_t n_evicted;     /* entries the operation would evict                           */
+    int32_t self_evicted;  /* 1 if the new entry itself is among them                     */
+    int32_t insert_pos;    /* deque position the new node would be linked at              */
+    int32_t buffer_weight; /* getUnloadBufferWeight() after the operation (0: unmanaged)  */
+    int32_t pad;
+    int64_t weighted_size; /* runtimeCache.weightedSize() after the operation             */
+    int64_t oldest_time;   /* runtimeCache.oldestTime(), -1 if empty                      */
+} mmp_evict_k_out; /* 48 bytes */
+int mmp_evict_batch_k(mmp_ctx *ctx, const mmp_cache_op *ops, int32_t n, const char *keys, const int32_t *key_off,
+                      int64_t now_ms, mmp_evict_k_out *outs);
 
 /* n guard evaluations (rows a10/a11/a14/a20). in_use_failure_expiry_ms = IN_USE_LOAD_FAILURE_EXPIRY_MS
  * (MM.java:221). excl_pod/excl_time and explicit_pool are the pools the requests index. */

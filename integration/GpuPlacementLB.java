@@ -104,6 +104,8 @@ final class MmPlace {
     static native int cacheSlotsLimit(long h, int maxSlots);
     static native int cacheReadK(long h, int cache, int maxEntries, ByteBuffer lastUsed, ByteBuffer weight, ByteBuffer rowOut,
                                  ByteBuffer idBytesOut, int maxIdBytes, ByteBuffer idOffOut, ByteBuffer scalars, ByteBuffer ubm);
+    // what a load would evict on the resident caches, nothing applied: outs = n mmp_evict_k_out rows of 48 bytes
+    static native int evictBatchK(long h, ByteBuffer ops, int n, ByteBuffer keys, ByteBuffer keyOff, long nowMs, ByteBuffer outs);
     // request guards and rebalancer plans
     static native int gateBatch(long h, ByteBuffer reqs, int n, ByteBuffer exclPod, ByteBuffer exclTime, int nExcl,
                                 ByteBuffer explicitPool, int nExplicit, long nowMs, long inUseFailureExpiryMs,

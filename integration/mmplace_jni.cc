@@ -361,6 +361,14 @@ JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_cacheReadK(JNIEnv *
                                   &sc->n_id_bytes, &sc->capacity, &sc->weighted_size, buf<mmp_ubm_state>(env, ubm)));
 }
 
+JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_evictBatchK(JNIEnv *env, jclass, jlong h, jobject ops, jint n, jobject keys,
+                                                                         jobject keyOff, jlong nowMs, jobject outs)
+{
+    return check(env, ctx_of(h),
+                 mmp_evict_batch_k(ctx_of(h), buf<mmp_cache_op>(env, ops), n, buf<char>(env, keys), buf<int32_t>(env, keyOff), nowMs,
+                                   buf<mmp_evict_k_out>(env, outs)));
+}
+
 // ---- request guards (MM.java:3603-3626, 3870-3884, 4003-4042, 4590-4627, 5158-5197, 2867-2933, 5440-5468)
 JNIEXPORT jint JNICALL Java_com_ibm_watson_modelmesh_MmPlace_gateBatch(JNIEnv *env, jclass, jlong h, jobject reqs,
                                                                        jint n, jobject exclPod, jobject exclTime,

@@ -308,6 +308,9 @@ CKEY_LIVE, CKEY_EMPTY_ROW, CKEY_UNKNOWN = range(3)
 CACHE_KEY_UNKNOWN = -(2 ** 31)
 COP_KEYLESS = (COP_UBM_SPACE_IS_READY, COP_UBM_CLAIM_SPACE, COP_UBM_UNLOAD_COMPLETE, COP_UBM_DISCARD_FAILED)
 COP_INSERTING = (COP_PUT_IF_ABSENT, COP_UBM_INSERT_NEW_ENTRY, COP_UBM_INSERT_FAILED_PLACEHOLDER)
+EVICT_K_OUT = np.dtype([("key_status", "<i4"), ("row", "<i4"), ("result", "<i4"), ("n_evicted", "<i4"), ("self_evicted", "<i4"),
+                        ("insert_pos", "<i4"), ("buffer_weight", "<i4"), ("pad", "<i4"), ("weighted_size", "<i8"), ("oldest_time", "<i8")])
+assert EVICT_K_OUT.itemsize == 48
 
 assert POD_ROW.itemsize == 64 and MODEL_ROW.itemsize == 24 and PLACE_REQ.itemsize == 64
 assert PLACE_OUT.itemsize == 16 and SERVE_REQ.itemsize == 48 and SERVE_COUNTER.itemsize == 16 and SERVE_OUT.itemsize == 16
@@ -380,6 +383,7 @@ SYMBOLS = [
     ("mmp_cache_slots_limit", C.c_int, [_P, C.c_int32]),
     ("mmp_cache_read_k", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    ("mmp_evict_batch_k", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P]),
     ("mmp_gate_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),
     ("mmp_miss_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     ("mmp_route_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),

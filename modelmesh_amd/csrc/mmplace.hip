@@ -50,6 +50,7 @@
 #include "evictions_kernels.hpp"
 #include "cache_keyed_kernels.hpp"
 #include "cache_wide_kernels.hpp"
+#include "evict_resident_kernels.hpp"
 #include "tasks_keyed_kernels.hpp"
 #include "census_kernels.hpp"
 #include "pod_events_kernels.hpp"
@@ -539,6 +540,14 @@ struct mmp_ctx {
     // scratch of a call's caches on that route: descriptors | directory | two copies of the blocks | pending LIFO | key index
     int32_t k_slots_limit = MMP_CACHE_SLOTS_DEFAULT;
     DevBuf k_wide;
+    // mmp_evict_batch_k (evict_resident_kernels.hpp).  k_gen: the generation of the resident store; every writer of it bumps it
+    // (the keyed loads, the replays, mmp_models_retire's renumbering, mmp_model_ids_load).  kx_gen: the generation the tables
+    // stand for; kx_desc_h: per cache where its tables lie in kx_tab (P == nullptr: none), kx_used the bytes of kx_tab taken.
+    // kx_desc: the descriptors and the ok words on the device; kx_scr: one build's cache list, chunk offsets, totals and bits.
+    int64_t k_gen = 0, kx_gen = -1;
+    std::vector<ResDesc> kx_desc_h;
+    size_t kx_used = 0;
+    DevBuf kx_tab, kx_desc, kx_scr, kx_outs;
 
     // wire-format ingestion: per-pod id attributes and the hash tables the parsers probe
     std::vector<uint32_t> id_order_v;
@@ -1348,6 +1357,96 @@ void evict_launch(mmp_ctx *c, const EvictArgs &A, int32_t n, hipStream_t st)
         hipLaunchKernelGGL(evict_batch_kernel<8>, dim3(div_up(n, kEvBlock / 8)), dim3(kEvBlock), 0, st, A);
     else
         hipLaunchKernelGGL(evict_batch_kernel<16>, dim3(div_up(n, kEvBlock / 16)), dim3(kEvBlock), 0, st, A);
+}
+
+// The tables of the RESIDENT store for mmp_evict_batch_k (evict_resident_kernels.hpp): on return every cache that `ops` names
+// and that holds more than tune.evict_search_from live entries has its prefix weights, its ok word and its key index, for the
+// store as it stands.  Lazy: a change of the store (k_gen) drops every table, and a cache is built by the first batch that names
+// it behind the change; short caches build, allocate and launch nothing.  The tables of one generation are appended to kx_tab;
+// when it has to grow, what was built goes with it and is built again beside the new.  The caller holds batch_mu and the state
+// lock, has set the device and synchronises the stream before it returns (the uploads below are from vectors of `keep`).
+struct ResidentBuildKeep {
+    std::vector<int32_t> bcache, bchunk_off;
+};
+int evict_resident_tables(mmp_ctx *c, const mmp_cache_op *ops, int32_t n, ResidentBuildKeep &keep)
+{
+    const int32_t NC = c->k_caches, from = c->tune.evict_search_from;
+    hipStream_t st = c->stream;
+    if (c->kx_gen != c->k_gen || (int32_t)c->kx_desc_h.size() != NC) {
+        c->kx_desc_h.assign((size_t)NC, ResDesc{nullptr, nullptr, 0, 0});
+        c->kx_used = 0;
+        c->kx_gen = c->k_gen;
+    }
+    std::vector<uint8_t> want((size_t)NC, 0);
+    std::vector<int32_t> &bc = keep.bcache;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t k = ops[i].cache;
+        if (k < 0 || k >= NC || want[k] || c->k_n[k] <= from || c->kx_desc_h[k].P) continue;
+        want[k] = 1;
+        bc.push_back(k);
+    }
+    if (bc.empty()) return MMP_OK;
+    const auto cells_of = [](int32_t e) {
+        size_t cells = 64;
+        while (cells < 2 * (size_t)e) cells *= 2;
+        return cells;
+    };
+    const auto bytes_of = [&](const std::vector<int32_t> &list) {
+        size_t b = 0;
+        for (const int32_t k : list) b += ((size_t)c->k_n[k] + 1 + cells_of(c->k_n[k])) * 8;
+        return b;
+    };
+    if (c->kx_used + bytes_of(bc) > c->kx_tab.cap) {  // grow: everything of this generation again
+        for (int32_t k = 0; k < NC; k++)
+            if (c->kx_desc_h[k].P) {
+                bc.push_back(k);
+                c->kx_desc_h[k] = ResDesc{nullptr, nullptr, 0, 0};
+            }
+        c->kx_used = 0;
+        HIP_TRY(c, hipStreamSynchronize(st));
+        HIP_TRY(c, c->kx_tab.ensure(bytes_of(bc)));
+    }
+    // this build's P regions first, its index tables behind them in one run (cleared by one fill)
+    char *base = c->kx_tab.as<char>() + c->kx_used;
+    size_t p_bytes = 0, tab_bytes = 0;
+    for (const int32_t k : bc) p_bytes += ((size_t)c->k_n[k] + 1) * 8;
+    std::vector<int32_t> &bchunk = keep.bchunk_off;
+    bchunk.assign(bc.size() + 1, 0);
+    for (size_t b = 0, po = 0; b < bc.size(); b++) {
+        const int32_t k = bc[b], e = c->k_n[k];
+        const size_t cells = cells_of(e);
+        c->kx_desc_h[k] = ResDesc{reinterpret_cast<int64_t *>(base + po), reinterpret_cast<unsigned long long *>(base + p_bytes + tab_bytes),
+                                  (uint32_t)(cells - 1), 0};
+        po += ((size_t)e + 1) * 8;
+        tab_bytes += cells * 8;
+        bchunk[b + 1] = bchunk[b] + std::max(1, div_up(e, kScanChunk));
+    }
+    c->kx_used += p_bytes + tab_bytes;
+    const int32_t chunks = bchunk.back(), nb = (int32_t)bc.size();
+    const auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_ok = up((size_t)NC * sizeof(ResDesc));
+    HIP_TRY(c, c->kx_desc.ensure(o_ok + (size_t)NC * 4));
+    const size_t o_off = up((size_t)chunks * 8), o_cok = o_off + up(((size_t)nb + 1) * 4), o_bc = o_cok + up((size_t)chunks * 4);
+    HIP_TRY(c, c->kx_scr.ensure(o_bc + (size_t)nb * 4));
+    char *s = c->kx_scr.as<char>();
+    HIP_TRY(c, hipMemcpyAsync(c->kx_desc.p, c->kx_desc_h.data(), (size_t)NC * sizeof(ResDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(s + o_off, bchunk.data(), ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(s + o_bc, bc.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(base + p_bytes, 0xff, tab_bytes, st));  // every cell empty
+    mmp_ctx::KeyedStore &K = c->ks[c->ks_cur];
+    ResBuildArgs B;
+    B.S = CacheStore{K.off.as<int32_t>(), K.lu.as<int64_t>(), K.wt.as<int32_t>(), K.key.as<int32_t>(), K.n.as<int32_t>()};
+    B.desc = c->kx_desc.as<ResDesc>();
+    B.ok = reinterpret_cast<int32_t *>(c->kx_desc.as<char>() + o_ok);
+    B.bcache = reinterpret_cast<const int32_t *>(s + o_bc);
+    B.bchunk_off = reinterpret_cast<const int32_t *>(s + o_off);
+    B.nb = nb;
+    B.chunk_total = reinterpret_cast<int64_t *>(s);
+    B.chunk_ok = reinterpret_cast<int32_t *>(s + o_cok);
+    hipLaunchKernelGGL(resident_chunk_reduce_kernel, dim3(chunks), dim3(kScanBlock), 0, st, B);
+    hipLaunchKernelGGL(resident_chunk_scan_kernel, dim3(chunks), dim3(kScanBlock), 0, st, B);
+    HIP_TRY(c, hipGetLastError());
+    return MMP_OK;
 }
 
 // One input or output array of a request call: the caller's array, its region of a slot (the layout table beside FastSlot), and the
@@ -4156,6 +4255,7 @@ try {
         model_ids_publish(model_id_tab(c), P);
         c->have_model_ids = true;
         c->k_bound = false;  // the keys of bound caches named rows of the replaced table: the contents stay, the binding goes
+        c->k_gen++;
     }
     HIP_TRY(c, model_ids_retired_drain(c, P));  // request calls by model id that captured the replaced table
     return MMP_OK;
@@ -4727,6 +4827,7 @@ try {
                                d_remap);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(st));
+            c->k_gen++;  // (the key index of mmp_evict_batch_k's tables holds the old numbers)
         }
         if (const int rr = rebuild_resolved(c)) return rr;
     }
@@ -8890,6 +8991,7 @@ int caches_keyed_store(mmp_ctx *c, int32_t n_caches, const int32_t *seg_off, con
     c->k_caches = n_caches;
     c->k_slots = E;
     c->k_bound = bound;
+    c->k_gen++;
     c->evid_bytes.clear();  // the eviction record of a keyed replay ends with the store it was made on
     c->evid_off.assign(1, 0);
     c->evid_lu.clear();
@@ -9254,6 +9356,7 @@ int cache_replay_drive(mmp_ctx *c, const char *fn, const mmp_cache_op *ops, int3
     // the replay is applied from here on, whatever becomes of the record: it is stateful and cannot be asked twice
     c->ks_cur = 1 - c->ks_cur;
     c->k_slots = Enew;
+    c->k_gen++;
     *n_evicted_slots = ev_off[NC];
     if (!kx) return MMP_OK;
     // the eviction record: the context keeps the bytes (a retirement between this call and mmp_cache_evicted_ids cannot change
@@ -9409,6 +9512,69 @@ try {
     if (ubm) HIP_TRY(c, copy_sync(c, ubm, c->k_ubm.as<mmp_ubm_state>() + cache, sizeof(mmp_ubm_state), hipMemcpyDeviceToHost));
     return MMP_OK;
 } MMP_CATCH(c, "mmp_cache_read_k")
+
+int mmp_evict_batch_k(mmp_ctx *c, const mmp_cache_op *ops, int32_t n, const char *keys, const int32_t *key_off, int64_t now,
+                      mmp_evict_k_out *outs)
+try {
+    const char *fn = "mmp_evict_batch_k";
+    if (!c || n < 0 || (n > 0 && (!ops || !outs || !key_off)) || (keys == nullptr) != (key_off == nullptr))
+        return fail(c, MMP_EINVAL, "%s: bad argument", fn);
+    for (int32_t i = 0; i < n; i++) {
+        const mmp_cache_op &o = ops[i];
+        if (o.op != MMP_COP_PUT_IF_ABSENT && o.op != MMP_COP_UBM_INSERT_NEW_ENTRY)
+            return fail(c, MMP_EINVAL, "%s: op %d has code %d (the two inserts only)", fn, i, o.op);
+        if (o.reserved < 0 || o.reserved > MMP_COPK_RAW_KEY || (o.reserved == MMP_COPK_RAW_KEY && o.key != MMP_UNLOADBUF_KEY))
+            return fail(c, MMP_EINVAL, "%s: op %d has reserved %d with key %d", fn, i, o.reserved, o.key);
+    }
+    std::lock_guard<std::mutex> gb(c->batch_mu);
+    std::lock_guard<std::shared_mutex> g(c->mu);
+    if (const int rc = caches_bound_guard(c, fn)) return rc;
+    if (c->prof) c->last_kernel_ms = -1;
+    if (n == 0) return MMP_OK;
+    if (c->k_caches <= 0) return fail(c, MMP_ESTATE, "no keyed caches loaded");
+    if (const int rc = check_offsets(c, fn, "key ", key_off, n)) return rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    std::vector<int32_t> krel, ident((size_t)n);
+    for (int32_t i = 0; i < n; i++) ident[i] = i;  // the rows are asked in caller order: the resolver's permutation is the identity
+    if (const int rc = stage_strings(c, fn, "key ", keys, key_off, n, c->ida_bytes, c->ida_off, krel)) return rc;
+    HIP_TRY(c, c->k_ops.ensure((size_t)n * sizeof(mmp_cache_op)));
+    HIP_TRY(c, c->k_inv.ensure((size_t)n * 4));
+    HIP_TRY(c, c->k_kstat.ensure((size_t)n * 4));
+    HIP_TRY(c, c->k_krow.ensure((size_t)n * 4));
+    HIP_TRY(c, c->kx_outs.ensure((size_t)n * sizeof(mmp_evict_k_out)));
+    HIP_TRY(c, hipMemcpyAsync(c->k_ops.p, ops, (size_t)n * sizeof(mmp_cache_op), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->k_inv.p, ident.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    KT_BEGIN(c, st);
+    ResidentBuildKeep keep;
+    if (const int rc = evict_resident_tables(c, ops, n, keep)) return rc;
+    const CkeyOpsArgs K{c->ida_bytes.as<char>(), c->ida_off.as<int32_t>(), n, hash_mask(c->tune.model_id_hash_bits), vmodel_models(c),
+                        c->k_inv.as<int32_t>(), c->k_ops.as<mmp_cache_op>(), c->k_kstat.as<int32_t>(), c->k_krow.as<int32_t>()};
+    hipLaunchKernelGGL(ckey_ops_kernel, dim3(div_up(n, kIdTabBlock)), dim3(kIdTabBlock), 0, st, K);
+    mmp_ctx::KeyedStore &S = c->ks[c->ks_cur];
+    ResidentArgs A;
+    A.S = CacheStore{S.off.as<int32_t>(), S.lu.as<int64_t>(), S.wt.as<int32_t>(), S.key.as<int32_t>(), S.n.as<int32_t>()};
+    A.capacity = c->k_cap.as<int64_t>();
+    A.weighted_size = c->k_wsize.as<int64_t>();
+    A.oldest = c->k_oldest.as<int64_t>();
+    A.ubm = c->k_ubm.as<mmp_ubm_state>();
+    A.desc = c->kx_desc.as<ResDesc>();
+    A.ok = reinterpret_cast<const int32_t *>(c->kx_desc.as<char>() + (((size_t)c->k_caches * sizeof(ResDesc) + 255) & ~size_t(255)));
+    A.ops = c->k_ops.as<mmp_cache_op>();
+    A.status = c->k_kstat.as<int32_t>();
+    A.outs = c->kx_outs.as<mmp_evict_k_out>();
+    A.n = n;
+    A.n_caches = c->k_caches;
+    A.from = c->tune.evict_search_from;
+    A.now = now;
+    hipLaunchKernelGGL(evict_resident_kernel<16>, dim3(div_up(n, kEvBlock / 16)), dim3(kEvBlock), 0, st, A);
+    KT_END(c, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(outs, c->kx_outs.p, (size_t)n * sizeof(mmp_evict_k_out), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    kt_collect(c);
+    return MMP_OK;
+} MMP_CATCH(c, "mmp_evict_batch_k")
 
 int mmp_cache_read(mmp_ctx *c, int32_t cache, int32_t max_entries, int64_t *last_used, int32_t *weight, int32_t *key,
                    int32_t *n_out, int64_t *capacity, int64_t *weighted_size, mmp_ubm_state *ubm)

@@ -1119,6 +1119,20 @@ class Solver:
         return {"last_used": lu[:m], "weight": wt[:m], "row": row[:m], "ids": self._spans(buf.tobytes(), off, m),
                 "capacity": cap.value, "weighted_size": ws.value, "ubm": ubm[0]}
 
+    def evict_batch_k(self, ops, keys, now, key_off=None, blob=None) -> np.ndarray:
+        """What a cache_replay_k of each single insert of `ops` (COP_PUT_IF_ABSENT / COP_UBM_INSERT_NEW_ENTRY, id keys[i]) would
+        answer on the resident caches as they stand, nothing applied (mmp_evict_batch_k): EVICT_K_OUT rows."""
+        from ._lib import CACHE_OP, EVICT_K_OUT
+        ops = np.ascontiguousarray(ops, dtype=CACHE_OP)
+        n = len(ops)
+        if blob is None:
+            blob, off = self.pack_keys(keys)
+        if key_off is not None:
+            off = np.ascontiguousarray(key_off, dtype=np.int32)
+        outs = np.zeros(n, dtype=EVICT_K_OUT)
+        self._ck(self.lib.mmp_evict_batch_k(self.h, ptr(ops) if n else None, n, blob, ptr(off), int(now), ptr(outs) if n else None))
+        return outs
+
     def gates(self, reqs, excl_pod, excl_time, explicit_pool, now, in_use_failure_expiry_ms=450_000) -> np.ndarray:
         from ._lib import GATE_OUT, GATE_REQ
         reqs = np.ascontiguousarray(reqs, dtype=GATE_REQ)
